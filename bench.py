@@ -12,9 +12,13 @@ n = 1204, L = 2419 sigma points, fp64.  With --gpus N every rank runs its own in
 sequence (Monte-Carlo run: shared initial map broadcast from rank 0 over RCCL, own measurement
 noise) — weak scaling, no per-frame collective.  Rank 0 prints ONE JSON line.
 
-The timed region is EXACTLY K frames between barrier + synchronize on both sides, max over ranks; it is run --repetitions times (default 5) on consecutive blocks of the
-staged sequence and `value` / `ms_per_step` are the MEDIAN repetition (`value_repetitions` lists all of them; `run_fixed_us` = what a run of K frames costs besides its frames).
-`launch_plan` names the kernels' plan and every fallback counter; `step_api` is the drop-in rate (one frame at a time through a C++ host: not the headline value).
+The timed region is EXACTLY K frames between barrier + synchronize on both sides, max over ranks.  A plain run sets up, warms up W frames, times ONE block of K frames
+and prints the line (`value` / `ms_per_step` are that block).  `--full` adds everything else the benchmark measures: the per-kernel leg (`roofline`,
+`kernels_us_per_frame`), --repetitions blocks (default 5 with --full; `value` / `ms_per_step` = the MEDIAN one, `value_repetitions` lists all of them; `run_fixed_us` =
+what a run of K frames costs besides its frames), multi_sequence, configs4, theta_clamp, the CPU baselines, step_api (the drop-in rate: one frame at a time through a
+C++ host, not the headline value) and collectives_check.  `launch_plan` names the kernels' plan and every fallback counter.
+`--dump-outputs DIR`: after the timed frames, the trajectory of the last timed block and the filter state after its last frame as DIR/<name>.npy (float64; inputs are
+seeded, so two builds can be compared output for output).
 """
 from __future__ import annotations
 
@@ -540,6 +544,29 @@ def plan_keys(f):
     return {k: int(f.debug_get(k)) for k in keys}
 
 
+PREPARE_MAX_FRAMES = 512       # srukf_prepare_frames captures at most this many frames as one graph; longer blocks replay the library's graphs of 8 frames
+DUMP_STATE_BYTES = 48 << 20      # the n x n factor above this is written as a fixed, seeded sample of its rows (64 MB in all with the rest)
+
+
+def dump_outputs(path, f, traj_block):
+    """--dump-outputs: what a caller of the timed path receives, as float64 .npy files under `path`: the trajectory rows of the last timed block (K x 8: pose, robot
+    covariance per frame) and the filter state after its last frame (X, and the square-root factor S — a seeded sample of rows when it is larger than
+    DUMP_STATE_BYTES, e.g. at N = 500).  Called after the timed frames; nothing here is timed."""
+    os.makedirs(path, exist_ok=True)
+    X, S = f.get_state()
+    S = np.asarray(S, dtype=np.float64)
+    rows = None
+    if S.nbytes > DUMP_STATE_BYTES:
+        keep = DUMP_STATE_BYTES // (S.shape[1] * 8)
+        rows = np.sort(np.random.default_rng(0).choice(S.shape[0], keep, replace=False))
+        S = S[rows]
+    np.save(os.path.join(path, "trajectory.npy"), np.asarray(traj_block.cpu().numpy(), dtype=np.float64))
+    np.save(os.path.join(path, "state_X.npy"), np.asarray(X, dtype=np.float64))
+    np.save(os.path.join(path, "state_S.npy" if rows is None else "state_S_row_sample.npy"), S)
+    if rows is not None:
+        np.save(os.path.join(path, "state_S_sample_rows.npy"), rows.astype(np.float64))
+
+
 def step_api_leg(synth, sizes=(200, 50), K=200, W=20, timeout=300):
     """The DROP-IN frame rate (SLAM.cpp:87-112 per frame: predict, host association, update), wall clock, through a C++ host (cv-monoslam_amd/host/
     cslam_step_bench.cpp) in child processes: the C-ABI step by step (`capi`; `capi_hint`: the host announces the next frame's odometry, as a host that has its
@@ -614,12 +641,20 @@ def main():
     ap.add_argument("--pmc-serial", action="store_true", help="rocprofv3 --pmc serialises the dispatches: the split form of the factorisation (N >= 400: two launches that "
                     "wait for each other) cannot run under it and is switched off — the counters of that pass are the memory-tile form's")
     ap.add_argument("--lib", default=None, help="measurement only: an A/B build of libsrukf_hip.so (scripts/build_variants.sh, scripts/ab_head.sh) instead of the in-tree one")
-    ap.add_argument("--repetitions", type=int, default=5, help="the timed block of K frames is run this many times (consecutive frames of the staged sequence); `value` is the median")
+    ap.add_argument("--repetitions", type=int, default=None, help="the timed block of K frames is run this many times (consecutive frames of the staged sequence); `value` is the median "
+                    "(default: 1, with --full 5)")
     ap.add_argument("--no-step-api", action="store_true", help="skip the step_api leg (drop-in frame rate through the C++ host)")
     ap.add_argument("--no-theta-clamp", action="store_true", help="skip the theta_clamp leg (the shipped a1..a4 = 8: what the verified-afterwards clamp costs when it fires)")
     ap.add_argument("--no-collectives-check", action="store_true",
-                    help="skip the short --force-dist child run whose outcome the default 1-GPU line reports as `collectives_check`")
+                    help="skip the short --force-dist child run whose outcome the --full 1-GPU line reports as `collectives_check`")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline as well: per-kernel leg and roofline, repetitions and run_fixed_us, multi_sequence, configs4, theta_clamp, "
+                         "CPU baselines, step_api, collectives_check (each still has its --no-* switch).  Without it: set-up, warm-up, K timed frames, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames write the trajectory of the last timed block and the filter state after its last frame as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.warmup < 1 and not args.launch_selftest:
+        ap.error("--warmup must be at least 1: the first frame of a fresh state runs eagerly and makes its null rows canonical, it is not a timed step")
 
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become the launcher.  Nothing in this process has touched torch / HIP yet.
@@ -656,11 +691,13 @@ def main():
         os.environ.setdefault("MASTER_PORT", str(_free_port()))
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
 
-    N, K, W, PF = args.landmarks, args.steps, args.warmup, args.profile_frames
-    R = max(1, args.repetitions)
-    KL = 300 if K < 300 else 0                                 # one longer block behind the repetitions: the two-point fit wall(K) = fixed + K * per_frame
+    full = args.full
+    N, K, W = args.landmarks, args.steps, args.warmup
+    PF0, PF = (4, args.profile_frames) if full else (0, 0)     # the per-kernel measurement leg runs with --full only
+    R = max(1, args.repetitions if args.repetitions is not None else (5 if full else 1))
+    KL = 300 if full and K < 300 else 0                        # one longer block behind the repetitions: the two-point fit wall(K) = fixed + K * per_frame
     n = 6 * N + 4
-    F = W + R * K + KL + PF + 4
+    F = W + R * K + KL + PF + PF0
     sc = build_inputs(synth, N, F, rank)
     binfo = {}
     X0, S0 = broadcast_map(torch, dist, sc, n, rank, world, device, force=use_dist, info=binfo)
@@ -681,24 +718,27 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # Frame order of the staged sequence: [0, 4 + PF) the per-kernel measurement leg (eager launches with HIP events on the launch
+    # Frame order of the staged sequence: with --full, [0, 4 + PF) the per-kernel measurement leg (eager launches with HIP events on the launch
     # stream; the first 4 frames after the fresh state are not averaged: cold clocks and first-touch effects made the dominant
     # kernel's average 158 us against the 142 us of the rocprofv3 trace), then [.., + W) the W warm-up steps, then the K timed steps.
-    # The leg comes first so that nothing sits between warm-up and timing; the block of K frames is captured as one graph
-    # beforehand (setup: nothing runs).
-    PF0 = 4
-    f.set_profiling(1)
-    f.run_frames_async(0, PF0, srukf.UPDATE_BATCHED, traj.data_ptr())
-    f.synchronize()
-    f.profile_reset()
-    f.run_frames_async(PF0, PF, srukf.UPDATE_BATCHED, traj[PF0:].data_ptr())
-    f.synchronize()
-    prof = f.profile()
-    f.set_profiling(0)
-    f.prepare_frames(K)
+    # The leg comes first so that nothing sits between warm-up and timing.  A plain run starts with the warm-up.  The block of K frames is captured as one
+    # graph AFTER the warm-up (setup: nothing runs): the first frame of a fresh joint-initialised state makes its null rows canonical and drops every
+    # captured graph (set_null_canonical), so a graph captured before that frame would not survive to the timed block.
+    prof = None
+    if full:
+        f.set_profiling(1)
+        f.run_frames_async(0, PF0, srukf.UPDATE_BATCHED, traj.data_ptr())
+        f.synchronize()
+        f.profile_reset()
+        f.run_frames_async(PF0, PF, srukf.UPDATE_BATCHED, traj[PF0:].data_ptr())
+        f.synchronize()
+        prof = f.profile()
+        f.set_profiling(0)
     # warmup (untimed)
     f.run_frames_async(PF0 + PF, W, srukf.UPDATE_BATCHED, traj[PF0 + PF:].data_ptr())
     f.synchronize()
+    if K <= PREPARE_MAX_FRAMES:
+        f.prepare_frames(K)
     # timed region: exactly K frames between barrier + synchronize on both sides, max over ranks — R times on consecutive blocks of the staged sequence (same
     # captured graph); `value` is the median repetition, every repetition is printed (a block of 20 frames is a 4 ms sample)
     walls_rep, dev_rep, per_rank_rep = [], [], []
@@ -721,6 +761,8 @@ def main():
         walls_rep.append(float(tt.item()))
     med = int(np.argsort(walls_rep)[len(walls_rep) // 2])
     wall_max, walls, dev_ms = walls_rep[med], per_rank_rep[med], dev_rep[med]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, f, traj[first:first + K])
     run_fixed_us = None
     if KL:
         first = PF0 + PF + W + R * K
@@ -746,21 +788,6 @@ def main():
         trajs = np.stack([t.cpu().numpy() for t in allt])
         truth = sc["odo"][1:F + 1]
         pose_rmse_truth = float(np.sqrt(np.mean((trajs[:, :F, :2] - truth[None, :F, :2]) ** 2)))
-        dom = max((k for k in prof if prof[k]["launches"]), key=lambda k: prof[k]["ms"])
-        d = prof[dom]
-        avg_s = d["ms"] / d["launches"] * 1e-3
-        fl, by = d["alg_flops"] / d["launches"], d["alg_bytes"] / d["launches"]
-        ridge = FP64_MFMA_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)
-        if fl / max(by, 1.0) > ridge:
-            roof = {"bound": "mfma", "achieved": fl / avg_s / 1e12, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s"}
-        else:
-            roof = {"bound": "hbm", "achieved": by / avg_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s"}
-        roof["frac"] = roof["achieved"] / roof["peak"]
-        roof["traffic"], roof["traffic_source"] = pmc_traffic(dom)
-        roof["mfma_busy_pct"], roof["mfma_gflop_counted"], roof["mfma_source"] = pmc_mfma(dom)
-        roof["kernel"] = dom
-        roof["avg_launch_us"] = avg_s * 1e6
-        roof["launches_per_frame"] = d["launches"] / PF
         out = {
             "metric": "srukf_updates_per_sec", "value": world * K / wall_max, "unit": "frames/s",
             "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": wall_max / K * 1e3,
@@ -773,12 +800,7 @@ def main():
             "config": {"workload": f"BASELINE configs[2]: {N} inverse-depth landmarks (n={n}, Na={n + 5}, L={2 * (n + 5) + 1}), "
                                    "M=N matched, fp64, one batched refactor per frame, synthetic 640x480 figure-8 sequence",
                        "landmarks": N, "state_dim": n, "sequences_per_gpu": 1, "update_mode": "batched"},
-            "roofline": roof,
-            # flop of the formulation that RUNS (sum of the per-kernel models; the rank-aware refactorisation skips the
-            # structurally null pivots) and of the full-rank formulation of earlier rounds, for comparison
-            "frame_alg_gflop": sum(v["alg_flops"] for v in prof.values()) / PF / 1e9,
-            "frame_full_rank_gflop": w_alg(N) / 1e9,
-            "frame_mfma_frac": sum(v["alg_flops"] for v in prof.values()) / PF * (K / wall_max) / (FP64_MFMA_PEAK_TFLOPS * 1e12),
+            "full": full,
             "collectives": (dist.get_backend() if use_dist else None),     # "nccl" = RCCL: broadcast of the map, barrier, max all-reduce, all-gather all ran
             # what a scaling run can be checked against: the world size the process group saw, every rank's own rate (value = world * K / max wall), who was slowest
             "rccl_world_size": (dist.get_world_size() if use_dist else 1), "per_rank_frames_per_s": [K / w for w in walls], "slowest_rank": int(np.argmax(walls)),
@@ -786,9 +808,31 @@ def main():
             "null_directions_skipped": f.null_directions(),
             "device_ms_per_step": dev_ms / K,
             "pose_rmse_vs_truth_m": pose_rmse_truth,
-            "kernels_us_per_frame": {k: round(v["ms"] / PF * 1e3, 2) for k, v in prof.items() if v["launches"]},
         }
-        if world == 1 and args.sequences_per_gpu > 1:
+        if full:
+            dom = max((k for k in prof if prof[k]["launches"]), key=lambda k: prof[k]["ms"])
+            d = prof[dom]
+            avg_s = d["ms"] / d["launches"] * 1e-3
+            fl, by = d["alg_flops"] / d["launches"], d["alg_bytes"] / d["launches"]
+            ridge = FP64_MFMA_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)
+            if fl / max(by, 1.0) > ridge:
+                roof = {"bound": "mfma", "achieved": fl / avg_s / 1e12, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s"}
+            else:
+                roof = {"bound": "hbm", "achieved": by / avg_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s"}
+            roof["frac"] = roof["achieved"] / roof["peak"]
+            roof["traffic"], roof["traffic_source"] = pmc_traffic(dom)
+            roof["mfma_busy_pct"], roof["mfma_gflop_counted"], roof["mfma_source"] = pmc_mfma(dom)
+            roof["kernel"] = dom
+            roof["avg_launch_us"] = avg_s * 1e6
+            roof["launches_per_frame"] = d["launches"] / PF
+            out["roofline"] = roof
+            # flop of the formulation that RUNS (sum of the per-kernel models; the rank-aware refactorisation skips the
+            # structurally null pivots) and of the full-rank formulation of earlier rounds, for comparison
+            out["frame_alg_gflop"] = sum(v["alg_flops"] for v in prof.values()) / PF / 1e9
+            out["frame_full_rank_gflop"] = w_alg(N) / 1e9
+            out["frame_mfma_frac"] = sum(v["alg_flops"] for v in prof.values()) / PF * (K / wall_max) / (FP64_MFMA_PEAK_TFLOPS * 1e12)
+            out["kernels_us_per_frame"] = {k: round(v["ms"] / PF * 1e3, 2) for k, v in prof.items() if v["launches"]}
+        if full and world == 1 and args.sequences_per_gpu > 1:
             B = args.sequences_per_gpu
             small = tuple(b for b in (4, 8) if b < B)
             rates, same, flagged = multi_sequence_throughput(torch, synth, srukf, N, B, 96, 10, local, small=small)
@@ -803,14 +847,14 @@ def main():
                             "no admission gate, no residency assumption, default hardware-queue count",
                 "note": "B independent Monte-Carlo sequences (one map, own measurement noise) replayed on one GPU; median over the repetitions; not the headline value"}
         c4_traj = c4_frames = None
-        if world == 1 and not args.no_configs4:
+        if full and world == 1 and not args.no_configs4:
             out["configs4"] = configs4_leg(torch, synth, srukf, local)
             c4_traj, c4_frames = out["configs4"].pop("_traj"), out["configs4"].pop("_frames")
         # (before the CPU legs: they run OpenMP teams on every CPU the cgroup grants, and a launch-heavy frame — the exact path is 151 launches — that starts while
         #  the quota is being paid back stalls for tens of milliseconds: measured as one 70 - 80 ms flagged frame among 6.5-ms ones when this leg ran behind them)
-        if world == 1 and not use_dist and not args.no_theta_clamp:
+        if full and world == 1 and not use_dist and not args.no_theta_clamp:
             out["theta_clamp"] = theta_clamp_leg(synth, srukf, local)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             cb, otraj = cpu_baseline(synth, sc, N, args.cpu_frames)
             # the whole run (every frame the device computed: measurement leg, warm-up, timed block) against the CPU port's trajectory of the same scene
             out["whole_run_vs_cpu_port"] = whole_run_vs_cpu_port(N, F, trajs[0], cb["full_rank_cores"], 1000 + rank, "headline")
@@ -850,9 +894,9 @@ def main():
                         "matched_same_algorithm is against those CPUs only"}
             out["pose_rmse_vs_oracle_m"] = float(np.sqrt(np.mean((gt[:, :2] - otraj[:, :2]) ** 2)))
             out["max_abs_dP_robot_vs_oracle"] = float(np.abs(gt[:, 4:] - otraj[:, 4:]).max())
-        if world == 1 and not use_dist and not args.no_step_api:
+        if full and world == 1 and not use_dist and not args.no_step_api:
             out["step_api"] = step_api_leg(synth)
-        if world == 1 and not use_dist and not args.no_collectives_check:
+        if full and world == 1 and not use_dist and not args.no_collectives_check:
             out["collectives_check"] = collectives_check()
         print(json.dumps(out))
     if use_dist:

@@ -69,6 +69,7 @@ def lib():
         L.orc_get_state.argtypes = [C.c_void_p, _dp, _dp]
         L.orc_set_newton_early_exit.argtypes = [C.c_void_p, C.c_int]
         L.orc_set_frozen_center.argtypes = [C.c_void_p, C.c_int]
+        L.orc_set_exact_means.argtypes = [C.c_void_p, C.c_int]
         L.orc_get_clamp_stats.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
         L.orc_predict_motion.argtypes = [C.c_void_p, _dp, _dp]
         L.orc_predict_measurement.argtypes = [C.c_void_p, _dp, _dp, _ip]
@@ -137,6 +138,11 @@ class Oracle:
     def set_frozen_center(self, on):
         """Test knob (not the reference): centre the cross covariance on the state at the start of the update."""
         lib().orc_set_frozen_center(self._h, int(on))
+
+    def set_exact_means(self, on):
+        """Test knob (not the reference): the weighted means of the motion and measurement sigma points summed in binary128 and rounded once
+        (fixtures whose h must not carry the reference's running-sum rounding: make_golden.py g9 f64)."""
+        lib().orc_set_exact_means(self._h, int(on))
 
     def clamp_stats(self):
         out = (C.c_longlong * 3)()

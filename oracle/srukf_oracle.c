@@ -59,6 +59,9 @@ typedef struct orc_state {
     int frozen_center;              /* test knob, NOT the reference: 1 = the cross covariance centres on the state at the
                                        start of KalmanUpdate instead of the running m_X_k (SLAM.cpp:2030); quantifies
                                        what the running-state term is worth when wc0 != wm0 (tests only)            */
+    int exact_means;                /* test knob, NOT the reference: 1 = the weighted means of the motion and the measurement sigma points
+                                       (addWeighted, 1526-1529 / 1678-1681) summed in binary128 and rounded once, instead of the reference's
+                                       running double sum whose cancellation (wm0 = 1 - Na/3) leaves ~4e-8 px in h at N = 500 (fixtures only) */
     const double *Xcenter;          /* state the cross covariance centres on (X, or the frozen copy)                 */
     long long clamp_eps, clamp_theta, pivots;            /* GMW statistics             */
 } orc_state;
@@ -421,6 +424,7 @@ ORC_API void orc_get_state(const orc_state *st, double *X, double *S)
 }
 ORC_API void orc_set_newton_early_exit(orc_state *st, int on) { st->newton_early_exit = on; }
 ORC_API void orc_set_frozen_center(orc_state *st, int on) { st->frozen_center = on; }
+ORC_API void orc_set_exact_means(orc_state *st, int on) { st->exact_means = on; }
 ORC_API void orc_get_clamp_stats(const orc_state *st, long long out[3]) { out[0] = st->clamp_eps; out[1] = st->clamp_theta; out[2] = st->pivots; }
 ORC_API const double *orc_sigma_ptr(const orc_state *st) { return st->sigma; }
 ORC_API const double *orc_Z_ptr(const orc_state *st) { return st->Z; }
@@ -460,6 +464,7 @@ ORC_API int orc_predict_motion(orc_state *st, const double odo_prev[3], const do
     /* passSigmaThroughMotionFunction, 1476-1532 (FLAG_4_NOISE1 branch 1490-1494) */
     double *sg = st->sigma;
     double mean[4] = {0, 0, 0, 0};
+    __float128 mean_q[4] = {0, 0, 0, 0};
     for (int i = 0; i < L; i++) {
         double r1 = st->Ut[0] - sg[(size_t)(dim + 0) * L + i];
         double tr = st->Ut[1] - sg[(size_t)(dim + 1) * L + i];
@@ -471,8 +476,10 @@ ORC_API int orc_predict_motion(orc_state *st, const double odo_prev[3], const do
             double e = sg[(size_t)(dim - 4 + d) * L + i];
             if (!i) mean[d] = e * st->wm0 + mean[d] * 0 + 0;
             else    mean[d] = e * st->wi + mean[d] * 1 + 0;
+            if (st->exact_means) mean_q[d] += (__float128)e * (__float128)(i ? st->wi : st->wm0);
         }
     }
+    if (st->exact_means) for (int d = 0; d < 4; d++) mean[d] = (double)mean_q[d];
     for (int d = 0; d < 4; d++) st->X[dim - 4 + d] = mean[d];                      /* 1531 */
 
     /* QrAndCholeskyForMotion, 1539-1555: QR rows = wi_sr*(sigma_{i+1}[0:dim] - sigma_0[0:dim])^T */
@@ -494,6 +501,8 @@ ORC_API int orc_predict_measurement(orc_state *st, double *h_out, double *Si_out
     int dim = st->n, Na = st->Na, L = st->L, N = st->N;
     const double *sg = st->sigma;
     double *Z = st->Z;
+    __float128 *h_q = st->exact_means ? (__float128 *)calloc((size_t)2 * N, sizeof(__float128)) : NULL;
+    if (st->exact_means && !h_q) return SRUKF_ERR_NOMEM;
     for (int i = 0; i < L; i++) {                                                  /* 1634 */
         double err[2] = { sg[(size_t)(dim + 3) * L + i], sg[(size_t)(dim + 4) * L + i] };                   /* 1637 */
         double pos[3] = { sg[(size_t)(dim - 4) * L + i], sg[(size_t)(dim - 3) * L + i], sg[(size_t)(dim - 2) * L + i] };   /* 1640 */
@@ -509,8 +518,10 @@ ORC_API int orc_predict_measurement(orc_state *st, double *h_out, double *Si_out
             double e = Z[(size_t)r * L + i];
             if (!i) st->h[r] = e * st->wm0 + st->h[r] * 0 + 0;
             else    st->h[r] = e * st->wi + st->h[r] * 1 + 0;
+            if (h_q) h_q[r] += (__float128)e * (__float128)(i ? st->wi : st->wm0);
         }
     }
+    if (h_q) { for (int r = 0; r < 2 * N; r++) st->h[r] = (double)h_q[r]; free(h_q); }
     /* QrAndCholeskyForMeasurement, 1700-1748 */
     double *QR = (double *)malloc(sizeof(double) * (size_t)2 * Na * 2);
     for (int id = 0; id < N; id++) {

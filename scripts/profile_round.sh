@@ -6,7 +6,8 @@
 #    split form of the factorisation (N >= 400: two launches that wait for each other) is switched off in them
 # 3. one PMC pass with the MFMA / VALU utilisation counters
 # Outputs land in gpurun_out/<tag>_*; scripts/summarize_profiles.py turns them into profiles/.
-tag=$1; shift; wl="$@"
+# --full: the traced runs keep the eager per-kernel leg (--profile-frames), the repeated timed blocks and the 300-frame block of the benchmark
+tag=$1; shift; wl="--full $*"
 st=${PROFILE_STEPS:-100}; wu=${PROFILE_WARMUP:-20}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_stats -- python3 bench.py $wl --steps $st --warmup $wu --no-cpu-baseline --sequences-per-gpu 0 --no-collectives-check --no-configs4 --no-step-api --no-theta-clamp > gpurun_out/${tag}_stats.log 2>&1

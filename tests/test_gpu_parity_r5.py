@@ -136,8 +136,9 @@ def _pin_scene(g, synth):
 @pytest.mark.parametrize("variant", ["default", "mem_tiles", "split_calls"])
 def test_g9_n500_fp64_against_8_oracle_frames(srukf, golden, synth, variant):
     """Fixture g9 (tests/golden/make_golden.py g9 f64): 8 consecutive BATCHED oracle frames at N = 500, a third of the landmarks unmatched per frame, frame 3 without
-    a match, frame 5 with a single one.  default: what bench.py's configs4 leg launches apart from the storage — split form of the factorisation, fused tail on the
-    permuted operands, split-K k_syrk over the kept rows; mem_tiles: the memory-tile instance of k_gmw_persist instead of the split form; split_calls: 1 + 3 + 4 frames."""
+    a match, frame 5 with a single one; the oracle's weighted means summed exactly (Oracle.set_exact_means: the reference's running sum for h is off by ~4e-8 px
+    here).  default: what bench.py's configs4 leg launches apart from the storage — split form of the factorisation, fused tail on the permuted operands, split-K
+    k_syrk over the kept rows; mem_tiles: the memory-tile instance of k_gmw_persist instead of the split form; split_calls: 1 + 3 + 4 frames."""
     g = golden["g9_batched_n500_f64"]
     N, F, p, sc, matched = _pin_scene(g, synth)
     if variant == "mem_tiles":
