@@ -114,12 +114,20 @@ int srukf_app_tmpl_stride(void);
 //                                                          // groups of filters srukf_run_frames_batch runs side by side, each on a stream of its own
 
 enum KClass { KC_MOTION = 0, KC_PROJECT, KC_STATS, KC_PXY, KC_GAIN, KC_SYRK, KC_GMW_TRAIL, KC_GMW_PERSIST, KC_GMW_CHECK,
-              KC_GMW_COL, KC_RANK_EXPAND, KC_PROJECT_MOTION, KC_PROJECT_TABLE, KC_PXY2, KC_MISC, KC_COUNT };
+              KC_GMW_COL, KC_RANK_EXPAND, KC_PROJECT_MOTION, KC_PROJECT_TABLE, KC_PXY2, KC_MISC,
+              KC_DET_RESPONSE, KC_DET_CAND, KC_DET_RANK, KC_DET_SELECT, KC_CAPTURE, KC_COUNT };
 struct ProfEvent { hipEvent_t a, b; int kc; };
 
 // ---- persistent GMW launch (k_gmw_persist): per-matrix-size resources --------------------------------
 // nreal: the tiles that hold values (ntiles minus the T - Tp pass-on tiles of the rank-aware form, which ride as a register-free third slot of the first workers)
 struct GmwPlan { void* pans = nullptr; void* sync = nullptr; void* tiles = nullptr; int ntiles = 0, nreal = 0, T = 0, Tp = 0, workers = -1, tenants = 1, cus = 0; };
+
+// feature detection (srukf_detect.hip): scratch of one pass over an image_w x image_h frame, allocated on the first srukf_detect_features;
+// in / out grow with the caller's map, archive and output capacities
+struct DetScratch {
+    double *resp = nullptr, *cand_r = nullptr; int *cand_pix = nullptr, *sorted = nullptr, *rank = nullptr, *gxy = nullptr, *blk = nullptr; void* hdr = nullptr;
+    void *in = nullptr, *out = nullptr; size_t in_bytes = 0, out_bytes = 0;
+};
 
 struct srukf_ctx {
     int device = 0;
@@ -148,6 +156,9 @@ struct srukf_ctx {
     unsigned char *app_patch = nullptr, *app_tmpl = nullptr, *d_image = nullptr;
     double *appR = nullptr, *appT = nullptr, *appPx = nullptr, *corr = nullptr;
     int* has_app = nullptr;
+    bool frame_valid = false;              // d_image holds the caller's last frame (srukf_associate / srukf_detect_features / srukf_capture_appearance with a
+                                           // frame): handed over at map changes with the buffer (adopt_context), dropped by srukf_reset
+    DetScratch det;                        // srukf_detect_features (handed over at map changes too)
     int storage = SRUKF_STORAGE_F64;       // SRUKF_STORAGE_F32 / _F32_MIXED: X32 / S32 hold the inter-frame state
     float *S32 = nullptr, *X32 = nullptr;
     // SRUKF_STORAGE_F32_MIXED: S^T S - U U^T on the fp32 matrix pipe (srukf_mixed.hip)
@@ -355,6 +366,13 @@ void prof_collect(srukf_ctx* c);
 void adopt_context(srukf_ctx* c, srukf_ctx* c2);
 int ctx_obtain(srukf_ctx* handle, srukf_ctx** out, int N);     // a context for N landmarks with the handle's device / stream / parameters: a retired one revived, or srukf_create
 void ctx_retire(srukf_ctx* handle, srukf_ctx* old);
+
+// ---- feature detection and appearance capture (srukf_detect.hip) ----
+void det_scratch_free(DetScratch& s, hipStream_t st);
+int ensure_image(srukf_ctx* c);
+int take_frame(srukf_ctx* c, const unsigned char* gray);       // gray -> d_image (the held frame); NULL: the held one or SRUKF_ERR_SEQUENCE
+void launch_capture_patch(hipStream_t st, const unsigned char* img, int W, int first, int K, const double* uv, const double* X, int n,
+                          unsigned char* app_patch, unsigned char* app_tmpl, double* appR, double* appT, double* appPx, int* has_app);
 
 struct ProfScope {
     srukf_ctx* c; int kc; hipEvent_t a = nullptr, b = nullptr;

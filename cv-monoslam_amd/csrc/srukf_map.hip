@@ -22,12 +22,11 @@ struct MapTimer {
 
 static int ensure_appearance(srukf_ctx* c)
 {
+    int rc = ensure_image(c); if (rc) return rc;               // (a context may hold the frame buffer without appearance records, and the other way round: adopt_context)
     if (c->app_patch) return SRUKF_OK;
     const size_t N = c->d.N > 0 ? c->d.N : 1;
-    const size_t img = (size_t)c->p.image_w * c->p.image_h;
     HIPCHK(c, srukf_dmalloc((void**)&c->app_patch, N * srukf_app_patch_stride()));
     HIPCHK(c, srukf_dmalloc((void**)&c->app_tmpl, N * srukf_app_tmpl_stride()));
-    HIPCHK(c, srukf_dmalloc((void**)&c->d_image, img));
     HIPCHK(c, srukf_dmalloc((void**)&c->appR, sizeof(double) * 9 * N));
     HIPCHK(c, srukf_dmalloc((void**)&c->appT, sizeof(double) * 3 * N));
     HIPCHK(c, srukf_dmalloc((void**)&c->appPx, sizeof(double) * 2 * N));
@@ -71,6 +70,9 @@ void adopt_context(srukf_ctx* c, srukf_ctx* c2)
     memcpy(c->prof_ms, c2->prof_ms, sizeof c->prof_ms); memcpy(c->prof_n, c2->prof_n, sizeof c->prof_n);
     memcpy(c->prof_flops, c2->prof_flops, sizeof c->prof_flops); memcpy(c->prof_bytes, c2->prof_bytes, sizeof c->prof_bytes);
     c2->profiling = false; c2->pev.clear();
+    // the frame the handle holds and the detection scratch stay with the handle (same image size in every context of a handle)
+    std::swap(c->d_image, c2->d_image); std::swap(c->frame_valid, c2->frame_valid); std::swap(c->det, c2->det);
+    c2->frame_valid = false;
     ctx_retire(c, c2);                                           // (not destroyed: revived when the map has this size again — ctx_obtain)
     c->phase = 0;
     if (shared != c->gmw_shared) set_shared(c, shared, tenants);
@@ -96,6 +98,36 @@ int srukf_set_landmark_appearance(srukf_ctx* c, int k, const unsigned char* patc
     HIPCHK(c, hipMemcpy(c->appT + 3 * k, t, sizeof(double) * 3, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->appPx + 2 * k, px, sizeof(double) * 2, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->has_app + k, &one, sizeof(int), hipMemcpyHostToDevice));
+    return SRUKF_OK;
+}
+
+// integrateFeaturesInformation's appearance fields (SLAM.cpp:918-926) of landmarks first .. first + K - 1 cut on the device from `gray` (NULL: the
+// frame the handle holds): what srukf_set_landmark_appearance records for a host-cut initPatch at cvRound(uv), Rwc of the current heading and the
+// robot position, byte for byte.
+int srukf_capture_appearance(srukf_ctx* c, int first, int K, const double* uv, const unsigned char* gray)
+{
+    if (!c || !uv || K < 1 || first < 0 || first + K > c->d.N) return SRUKF_ERR_BAD_ARG;
+    const int W = (int)c->p.image_w, H = (int)c->p.image_h;
+    for (int q = 0; q < K; q++) {                                        // the 21 x 21 window must lie inside the frame
+        if (!(std::fabs(uv[2 * q]) < 1e9) || !(std::fabs(uv[2 * q + 1]) < 1e9)) { c->err = "capture_appearance: pixel is not finite"; return SRUKF_ERR_BAD_ARG; }
+        const int u = (int)std::nearbyint(uv[2 * q]), v = (int)std::nearbyint(uv[2 * q + 1]);
+        if (u - 10 < 0 || u + 10 > W - 1 || v - 10 < 0 || v + 10 > H - 1) { c->err = "capture_appearance: the 21 x 21 window leaves the image"; return SRUKF_ERR_BAD_ARG; }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    step_commit_motion(c);
+    int rc = ensure_appearance(c); if (rc) return rc;
+    rc = take_frame(c, gray); if (rc) return rc;
+    double* d_uv = nullptr;
+    HIPCHK(c, srukf_dmalloc_on(&d_uv, sizeof(double) * 2 * K, c->stream));
+    hipError_t e = hipMemcpyAsync(d_uv, uv, sizeof(double) * 2 * K, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        ProfScope ps(c, KC_CAPTURE, 0, 441.0 * K);
+        launch_capture_patch(c->stream, c->d_image, W, first, K, d_uv, c->X, c->d.n, c->app_patch, c->app_tmpl, c->appR, c->appT, c->appPx, c->has_app);
+        e = hipGetLastError();
+    }
+    srukf_dfree_on(d_uv, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->err = std::string("capture_appearance: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
     return SRUKF_OK;
 }
 
@@ -137,6 +169,7 @@ int srukf_associate(srukf_ctx* c, const unsigned char* gray, double* z, int* mat
     } else {
         HIPCHK(c, hipMemcpyAsync(c->d_image, gray, img, hipMemcpyHostToDevice, c->stream));
     }
+    c->frame_valid = true;
     srukf_launch_associate(c->stream, c->d, c->p, c->d_image, c->h, c->Si, c->vis, c->has_app, c->app_tmpl, c->zcur, c->mcur, c->corr);
     // z | matched | corr written into the pinned buffer by ONE short launch, flag behind them: three small device-to-host copies were three blit kernels with their gaps
     const unsigned long long seq = ++c->step_seq;

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <algorithm>
 
 namespace monoslam {
 
@@ -49,6 +50,8 @@ void CSLAM::initializeParameters()
     m_nMapFeatures = m_nPredicts = m_nMatches = m_nAddings = 0;
     m_nDeletes = m_nStores = 0; m_deleteID.clear(); isAdding = false;
     m_frameTime = m_totalTime = 0;
+    m_blockSize = 3; m_qualityLevel = 0.1; m_nInitialRaws = 8; m_nProcessRaws = 8; m_minDist = 15.0; m_minDist2 = m_minDist * m_minDist;   // 175-181
+    m_keyPoints.clear(); m_loopPointID.clear(); m_loopPointCounter = 0; m_nFilters = 0; firstDetect_ = true; runningCount_ = 0;
     mapStore.clear(); relinkMap();
 }
 
@@ -140,6 +143,93 @@ bool CSLAM::dataAssociationOnDevice(const unsigned char* gray)
         if (m[k]) { map[k].matchLocation.x = z[2 * k]; map[k].matchLocation.y = z[2 * k + 1]; m_nMatches++; }
     }
     return true;
+}
+
+// ---- finding new landmarks on the device ------------------------------------------------------------------------------------------------
+// SLAM.cpp:574-768.  The GFTT budget (590-599), the filter switches (653, 660, 614) and the map / archive inputs go to srukf_detect_features; the
+// key points it accepts become m_keyPoints, the archived features it met again m_loopPointID; counter = both (719, 748), and the running map
+// count moves as 758-766 move m_nMapFeatures (the facade's m_nMapFeatures stays the true map size).
+bool CSLAM::detectAndfilteringFeatures()
+{
+    if (!ctx_ || !m_gryImage) { lastError = "detectAndfilteringFeatures: no context or no m_gryImage"; return false; }
+    srukf_detect_params dp;
+    dp.max_corners = (1 == m_frame.counter || isAdding) ? m_nInitialRaws : m_nProcessRaws;                     // 590-597
+    dp.quality_level = m_qualityLevel; dp.min_dist = m_minDist; dp.block_size = m_blockSize; dp.dist_to_border = DIST_2_BORDER;
+    dp.unfiltered = (1 == m_frame.counter || firstDetect_) ? 1 : 0;                                             // 653
+    dp.map_gate = (0 != m_nMatches) ? 1 : 0;                                                                    // 660
+    dp.project_archived = isAdding ? 1 : 0;                                                                     // 614-635
+    std::vector<double> mp, ar;
+    for (const PointsMap* map_p = map; NULL != map_p; map_p = map_p->next) {
+        const double e[4] = { map_p->matchLocation.x, map_p->matchLocation.y, map_p->predictLocation.x, map_p->predictLocation.y };
+        mp.insert(mp.end(), e, e + 4);
+    }
+    for (const FeatureInfo& fi : m_featuresAllInfo) ar.insert(ar.end(), fi.state, fi.state + 6);
+    const int cap = std::max(dp.max_corners, 1);
+    const int nA = (int)m_featuresAllInfo.size(), loopCap = std::max(1, cap * nA);
+    std::vector<double> uv(2 * (size_t)cap);
+    std::vector<int> loops(2 * (size_t)loopCap);
+    int nUv = 0, nLoop = 0;
+    if (!check(srukf_detect_features(ctx_, m_gryImage, &dp, (int)(mp.size() / 4), mp.data(), nA, ar.data(), uv.data(), cap, &nUv,
+                                     loops.data(), loopCap, &nLoop))) return false;
+    firstDetect_ = false;                                                                                       // 754
+    nUv = std::min(nUv, cap); nLoop = std::min(nLoop, loopCap);
+    m_keyPoints.clear();
+    for (int k = 0; k < nUv; k++) { Point2d p; p.x = uv[2 * k]; p.y = uv[2 * k + 1]; m_keyPoints.push_back(p); }
+    if (isAdding) m_loopPointID.clear();                                                                        // 618
+    m_loopPointCounter = nLoop;                                                                                 // 604, 721
+    if ((int)m_loopPointID.size() < nLoop) m_loopPointID.resize(nLoop);
+    for (int q = 0; q < nLoop; q++) m_loopPointID[q] = m_featuresAllInfo[loops[2 * q + 1]].ID;                 // 719
+    const int counter = nUv + nLoop;
+    m_nFilters = counter;                                                                                       // 756-766
+    runningCount_ = isAdding ? counter : runningCount_ + counter;
+    if (logDetectPasses) {
+        DetectPass dpass; dpass.call = addCalls_; dpass.frame = m_frame.counter; dpass.n_map = m_nMapFeatures; dpass.n_matches = m_nMatches;
+        dpass.params = dp; dpass.map_px = mp; dpass.archived = ar;
+        double P4[16];
+        if (!check(srukf_get_robot(ctx_, dpass.pose, P4))) return false;
+        dpass.uv.assign(uv.begin(), uv.begin() + 2 * nUv); dpass.loops.assign(loops.begin(), loops.begin() + 2 * nLoop); dpass.running = runningCount_;
+        m_detectLog.push_back(dpass);
+    }
+    return true;
+}
+
+// SLAM.cpp:777-808
+bool CSLAM::insureEnoughFeatures()
+{
+    const int numberStore = m_nInitialRaws;
+    const double qualityLevelStore = m_qualityLevel;
+    bool ok = true;
+    while (runningCount_ < m_minNUM) {
+        m_nInitialRaws += m_minNUM;
+        if (m_nInitialRaws > 30) break;
+        m_keyPoints.clear();
+        if (!(ok = detectAndfilteringFeatures())) break;
+    }
+    m_nInitialRaws = numberStore;
+    m_qualityLevel = qualityLevelStore;
+    return ok;
+}
+
+// addFeatures (552-562) on the device: detect, then integrate the accepted key points and capture their appearance from the frame the
+// detection left on the device (it survives the map change)
+bool CSLAM::addFeaturesOnDevice()
+{
+    Stopwatch swd(m_detectTime); m_nDetectCalls++;
+    m_nAddings = 0;
+    addCalls_++;
+    if (!ctx_) {                                                                                                // frame 1: robot block only (221-231)
+        if (!check(srukf_create(&ctx_, 0, &m_params, device_, nullptr))) return false;
+        m_nMapFeatures = 0; mapStore.clear(); relinkMap();
+    }
+    runningCount_ = m_nMapFeatures;
+    m_keyPoints.clear();
+    if (!detectAndfilteringFeatures() || !insureEnoughFeatures()) return false;
+    const int K = (int)m_keyPoints.size(), first = m_nMapFeatures;
+    if (K == 0) return true;
+    std::vector<double> kp(2 * (size_t)K);
+    for (int k = 0; k < K; k++) { kp[2 * k] = m_keyPoints[k].x; kp[2 * k + 1] = m_keyPoints[k].y; }
+    if (!integrateFeaturesInformation(K, kp.data())) return false;
+    return check(srukf_capture_appearance(ctx_, first, K, kp.data(), nullptr));                                  // 918-926
 }
 
 // ---- display accessors -----------------------------------------------------------------------------------------
@@ -391,8 +481,15 @@ bool CSLAM::redirection()
     mapStore.clear(); relinkMap();
     m_X_k.create(4, 1); m_S_k.create(4, 4); m_P_k.create(4, 4);
     std::vector<double> keyPoints;
-    const int K = addFeatures ? addFeatures(*this, keyPoints) : 0;                                             // 1418-1420 (isAdding; addFeatures 552-562)
-    if (K > 0 && !integrateFeaturesInformation(K, keyPoints.data())) return false;
+    if (!addFeatures && m_gryImage) {                                                                          // 1418-1420 on the device: isAdding semantics
+        isAdding = true;
+        const bool ok = addFeaturesOnDevice();
+        isAdding = false;
+        if (!ok) return false;
+    } else {
+        const int K = addFeatures ? addFeatures(*this, keyPoints) : 0;                                         // 1418-1420 (isAdding; addFeatures 552-562)
+        if (K > 0 && !integrateFeaturesInformation(K, keyPoints.data())) return false;
+    }
     m_nShowMap = m_nMapFeatures + m_nStoreMap;                                                                 // 1422
     m_frame.counter++;                                                                                         // 1424-1425
     m_frame.index = (int)m_odoTheta.at(0, m_frame.counter);
@@ -409,6 +506,10 @@ bool CSLAM::redirection()
 // SLAM.cpp:1343-1465: the redirection restart, then the numeric tail 1430-1465 on the device.
 void CSLAM::predictMotion()
 {
+    if (!ctx_ && m_gryImage && !addFeatures) {                                                                 // on-device detection from frame 1: the 4-state filter of
+        if (!check(srukf_create(&ctx_, 0, &m_params, device_, nullptr))) return;                               // initializeParameters (221-231, heading of loadOdometryData 397)
+        if (!check(srukf_set_state(ctx_, m_X_k.data.data(), m_S_k.data.data()))) return;
+    }
     if (!ctx_) { lastError = "predictMotion before setMap"; return; }
     m_frame.index = (int)m_odoTheta.at(0, m_frame.counter);                                                    // 1351
     if (m_odoTheta.at(2, m_frame.counter) == 1 && !redirection()) return;                                      // 1354-1428
@@ -517,6 +618,8 @@ void CSLAM::SLAM()
         std::vector<double> keyPoints;
         const int K = addFeatures(*this, keyPoints);
         if (K > 0) integrateFeaturesInformation(K, keyPoints.data());
+    } else if ((m_nMatches < m_minNUM || isAdding) && m_gryImage) {
+        addFeaturesOnDevice();                                                                                 // 556-561 on the device
     }
     m_frame.counter++;                                                                                         // stopTimer 142-151
     m_frameTime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -6,7 +6,8 @@
 // m_nMatches, m_frameTime, m_totalTime, m_path, m_odoXY, map ...; MonoSLAMView.cpp:76-93,
 // OpenGlDisplay.cpp:386-571).  This class keeps those names and meanings for the SRUKF path and
 // routes the numerics to the MI355X kernels.  What is NOT here (out of scope): image
-// I/O, feature detection, patch matching, drawing, MFC controls.  The step between
+// I/O, drawing, MFC controls.  Feature detection runs on the device when the host points m_gryImage at its
+// gray frame and installs no addFeatures callback (detectAndfilteringFeatures / insureEnoughFeatures below).  The step between
 // predictMeasurement() and KalmanUpdate() — loadPictures() + dataAssociation() in the reference
 // (SLAM.cpp:95-97) — is a host callback: it receives the predicted pixels / Si / visibility the
 // reference's dataAssociation consumes and fills matchLocation / isMatching.
@@ -137,6 +138,34 @@ public:
     // the host detects key points on its current image and returns them as (u, v) pairs (distorted pixels); the facade
     // joint-initialises them (integrateFeaturesInformation).  Used by the redirection restart of predictMotion.
     std::function<int(CSLAM&, std::vector<double>& keyPoints)> addFeatures;
+    // ---- finding new landmarks on the device (addFeatures 552-562) --------------------------------------------------------------------------
+    // With m_gryImage set and no addFeatures callback installed, SLAM() and the redirection restart detect on the device: detectAndfilteringFeatures,
+    // insureEnoughFeatures, then integrateFeaturesInformation for the accepted key points and srukf_capture_appearance for the new landmarks
+    // (initPatch / initRotation / initTrans, 918-926).  Loop points are reported (m_loopPointID, m_loopPointCounter), not added; m_nMapFeatures stays
+    // the true map size.
+    const unsigned char* m_gryImage = nullptr;          // the current gray frame, image_h x image_w, row-major (SLAM.h: m_gryImage); set by the host
+    int    m_blockSize = 3;                             // SLAM.cpp:175
+    double m_qualityLevel = 0.1;                        // 176
+    int    m_nInitialRaws = 8, m_nProcessRaws = 8;      // 177-178: corner budget at frame 1 / isAdding, otherwise
+    double m_minDist = 15.0, m_minDist2 = 225.0;        // 180-181
+    std::vector<Point2d> m_keyPoints;                   // the accepted key points of the last pass (SLAM.h:169)
+    std::vector<int> m_loopPointID;                     // IDs of the archived features the last pass met again (SLAM.cpp:719)
+    int    m_loopPointCounter = 0;                      // their number (603, 721)
+    int    m_nFilters = 0;                              // key points + loop points of the last pass (758-765)
+    // detectAndfilteringFeatures (574-768) on m_gryImage: GFTT + the filter pass on the device (srukf_detect_features); fills m_keyPoints, the loop
+    // points and the running count the pass schedule reads
+    bool detectAndfilteringFeatures();
+    // insureEnoughFeatures (777-808): further passes while the running count is below m_minNUM, m_nInitialRaws += m_minNUM each, until it exceeds 30
+    bool insureEnoughFeatures();
+    // every pass of detectAndfilteringFeatures with its inputs, when logDetectPasses is on (hosts that check or replay detection)
+    struct DetectPass {
+        int call = 0, frame = 0, n_map = 0, n_matches = 0, running = 0;   // which addFeatures, m_frame.counter, true map size, m_nMatches, running count after the pass
+        srukf_detect_params params{}; double pose[4] = {0, 0, 0, 0};     // the switches and the robot pose the archive was projected under
+        std::vector<double> map_px, archived, uv; std::vector<int> loops;
+    };
+    bool logDetectPasses = false;
+    double m_detectTime = 0; int m_nDetectCalls = 0;    // wall time of the on-device addFeatures (detection passes + integration + capture) and their number
+    std::vector<DetectPass> m_detectLog;
     // ---- redirection (SLAM.cpp:1354-1428): when the odometry heading jumps by more than MIN_STEP_THETA the reference
     //      archives the current map in m_featuresAllInfo and restarts a fresh 4-state filter at the current position ----
     std::vector<FeatureInfo> m_featuresAllInfo;          // SLAM.h:170
@@ -175,6 +204,7 @@ public:
 
 private:
     bool redirection();
+    bool addFeaturesOnDevice();
     void relinkMap();
     void refreshMirrors();
     bool check(int rc);
@@ -183,6 +213,9 @@ private:
     int device_ = 0;
     FILE* robotFile_ = nullptr;
     double initOdo_[2] = {0, 0}, initPos_[2] = {0, 0};
+    bool firstDetect_ = true;            // the reference's `static bool flag` of detectAndfilteringFeatures (590, 653-656), per facade instance
+    int runningCount_ = 0;               // the reference's running m_nMapFeatures of the pass schedule (758-766, 782)
+    int addCalls_ = 0;                   // addFeaturesOnDevice calls (DetectPass::call)
 };
 
 }  // namespace monoslam

@@ -1,0 +1,75 @@
+// cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
+// frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
+// -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup]
+// frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
+// redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
+//   addFeatures runs with isAdding (archived features projected, empty map).
+// warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
+// Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "cslam.hpp"
+
+int main(int argc, char** argv)
+{
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>]\n", argv[0]); return 2; }
+    FILE* f = fopen(argv[1], "rb");
+    if (!f) { perror(argv[1]); return 2; }
+    int W = 0, H = 0, F = 0;
+    if (fread(&W, 4, 1, f) != 1 || fread(&H, 4, 1, f) != 1 || fread(&F, 4, 1, f) != 1 || W < 8 || H < 8 || F < 1) { fprintf(stderr, "bad frames file\n"); return 2; }
+    std::vector<unsigned char> frames((size_t)W * H * F);
+    if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
+    fclose(f);
+    int redirect = 0; bool warmup = false;
+    for (int a = 3; a < argc; a++) if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true;
+    if (warmup) {
+        monoslam::CSLAM w;
+        w.m_params.image_w = W; w.m_params.image_h = H; w.MIN_STEP_X = w.MIN_STEP_Y = 0.0;
+        if (!w.loadOdometryData(argv[2])) { fprintf(stderr, "%s\n", w.lastError.c_str()); return 1; }
+        w.m_gryImage = frames.data();
+        w.SLAM();
+        if (!w.lastError.empty()) { fprintf(stderr, "warmup: %s\n", w.lastError.c_str()); return 1; }
+    }
+
+    monoslam::CSLAM SLAM;
+    SLAM.m_params.image_w = W; SLAM.m_params.image_h = H;
+    SLAM.MIN_STEP_X = SLAM.MIN_STEP_Y = 0.0;
+    if (!SLAM.loadOdometryData(argv[2])) { fprintf(stderr, "%s\n", SLAM.lastError.c_str()); return 1; }
+    if (redirect > 0) SLAM.m_odoTheta.at(2, redirect) = 1;
+    SLAM.logDetectPasses = true;
+    const unsigned char* cur = nullptr;
+    SLAM.dataAssociation = [&](monoslam::CSLAM& s) { s.dataAssociationOnDevice(cur); };     // loadPictures + dataAssociation (SLAM.cpp:95-97)
+    const int steps = SLAM.m_odoCounter - 1 - (redirect > 0 ? 1 : 0);
+    double addWall = -1.0;
+    for (int fr = 0; fr < steps; fr++) {
+        cur = frames.data() + (size_t)(fr % F) * W * H;
+        SLAM.m_gryImage = cur;
+        const size_t logged = SLAM.m_detectLog.size();
+        const double addBefore = SLAM.m_detectTime;
+        SLAM.SLAM();
+        if (!SLAM.lastError.empty()) { fprintf(stderr, "frame %d: %s\n", fr, SLAM.lastError.c_str()); return 1; }
+        if (fr == 0) addWall = SLAM.m_detectTime - addBefore;
+        for (size_t q = logged; q < SLAM.m_detectLog.size(); q++) {
+            const auto& p = SLAM.m_detectLog[q];
+            const auto& d = p.params;
+            printf("pass image %d call %d frame %d n_map %d n_matches %d running %d mc %d q %.17g md %.17g bs %d border %.17g unf %d gate %d proj %d pose %.17g %.17g %.17g %.17g\n",
+                   fr % F, p.call, p.frame, p.n_map, p.n_matches, p.running, d.max_corners, d.quality_level, d.min_dist, d.block_size, d.dist_to_border,
+                   d.unfiltered, d.map_gate, d.project_archived, p.pose[0], p.pose[1], p.pose[2], p.pose[3]);
+            printf("map"); for (double v : p.map_px) printf(" %.17g", v); printf("\n");
+            printf("arch"); for (double v : p.archived) printf(" %.17g", v); printf("\n");
+            printf("uv"); for (double v : p.uv) printf(" %.17g", v); printf("\n");
+            printf("loops"); for (int v : p.loops) printf(" %d", v); printf("\n");
+        }
+        printf("frame %d n_map %d map_size %d archived %d matches %d loops %d\n", fr, SLAM.m_nMapFeatures, (int)SLAM.mapStore.size(),
+               (int)SLAM.m_featuresAllInfo.size(), SLAM.m_nMatches, SLAM.m_loopPointCounter);
+        printf("init"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %.17g %.17g", m->initPixel.x, m->initPixel.y); printf("\n");
+        const int n = SLAM.m_X_k.rows;
+        printf("pose %.17g %.17g %.17g %.17g\n", SLAM.m_X_k.at(n - 4, 0), SLAM.m_X_k.at(n - 3, 0), SLAM.m_X_k.at(n - 2, 0), SLAM.m_X_k.at(n - 1, 0));
+    }
+    printf("add_features_frame1_ms %.3f  frame_time_ms %.3f\n", addWall * 1e3, SLAM.m_frameTime * 1e3);
+    return 0;
+}

@@ -25,7 +25,7 @@ EXPORTS = [
     "srukf_get_landmark_block", "srukf_get_landmarks_cartesian", "srukf_get_frame_view", "srukf_get_covariance", "srukf_predict_motion", "srukf_predict_motion_next", "srukf_predict_measurement",
     "srukf_update", "srukf_set_new_landmarks", "srukf_add_landmarks", "srukf_delete_landmark", "srukf_set_storage", "srukf_set_exclusive", "srukf_set_rank_aware", "srukf_null_directions", "srukf_run_frames_batch", "srukf_prepare_frames", "srukf_debug_poke_state", "srukf_get_state_f32", "srukf_set_landmark_appearance", "srukf_associate", "srukf_get_match_patch", "srukf_stage_sequence", "srukf_run_frames_async", "srukf_run_frames", "srukf_synchronize", "srukf_set_profiling",
     "srukf_clamp_info", "srukf_debug_set", "srukf_debug_get", "srukf_debug_copy", "srukf_debug_upload", "srukf_debug_split_replay", "srukf_debug_gmw_stamps", "srukf_debug_starve_workers", "srukf_debug_allow_mixed", "srukf_profile_count", "srukf_profile_get", "srukf_profile_reset", "srukf_dims", "srukf_gmw_host",
-    "srukf_project_host",
+    "srukf_project_host", "srukf_detect_features", "srukf_capture_appearance",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -53,6 +53,12 @@ class Params(C.Structure):
 
     def to_dict(self):
         return {k: getattr(self, k) for k in _DBL_FIELDS + _INT_FIELDS}
+
+
+class DetectParams(C.Structure):
+    """struct srukf_detect_params (defaults: SLAM.cpp:175-181, 48)."""
+    _fields_ = [("max_corners", C.c_int), ("quality_level", C.c_double), ("min_dist", C.c_double), ("block_size", C.c_int),
+                ("dist_to_border", C.c_double), ("unfiltered", C.c_int), ("map_gate", C.c_int), ("project_archived", C.c_int)]
 
 
 class SrukfError(RuntimeError):
@@ -114,6 +120,9 @@ def load_library(path=None):
     L.srukf_set_landmark_appearance.argtypes = [C.c_void_p, C.c_int, _bp, _dp, _dp, _dp]
     L.srukf_associate.argtypes = [C.c_void_p, _bp, _dp, _ip, _dp]
     L.srukf_get_match_patch.argtypes = [C.c_void_p, C.c_int, _bp]
+    if hasattr(L, "srukf_detect_features"):            # (an A/B build of an older library, bench.py --lib, has no detection: build() checks EXPORTS)
+        L.srukf_detect_features.argtypes = [C.c_void_p, _bp, C.POINTER(DetectParams), C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _ip, C.c_int, _ip]
+        L.srukf_capture_appearance.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _bp]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -292,6 +301,42 @@ class Filter:
         out = np.zeros((17, 17), dtype=np.uint8)
         self._chk(self._lib.srukf_get_match_patch(self._h, int(k), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return out
+
+    def detect_features(self, gray=None, max_corners=8, quality=0.1, min_dist=15.0, block_size=3, border=20, unfiltered=False,
+                        map_px=None, map_gate=False, archived=None, project_archived=False):
+        """detectAndfilteringFeatures on the device (srukf_detect_features): Shi-Tomasi corners of `gray` (image_h x image_w uint8; None: the
+        frame the filter holds) and the reference's filter pass.  map_px[M,4] = (matchLocation, predictLocation) per map entry, archived[A,6] =
+        FeatureInfo::state rows.  Returns (uv[K,2] accepted key points, loops[L,2] (key point index, archived index))."""
+        dp = DetectParams(int(max_corners), float(quality), float(min_dist), int(block_size), float(border), int(bool(unfiltered)),
+                          int(bool(map_gate)), int(bool(project_archived)))
+        w, h = int(self.params.image_w), int(self.params.image_h)
+        g = None
+        if gray is not None:
+            gray = np.ascontiguousarray(gray, dtype=np.uint8)
+            assert gray.shape == (h, w)
+            g = gray.ctypes.data_as(C.POINTER(C.c_ubyte))
+        mp = _c(map_px).reshape(-1, 4) if map_px is not None else np.zeros((0, 4))
+        ar = _c(archived).reshape(-1, 6) if archived is not None else np.zeros((0, 6))
+        cap = int(max_corners) if max_corners > 0 else w * h
+        loop_cap = min(cap * ar.shape[0], 1 << 20)
+        uv = np.zeros((cap, 2))
+        loops = np.zeros((max(loop_cap, 1), 2), dtype=np.int32)
+        n_uv, n_loop = C.c_int(), C.c_int()
+        self._chk(self._lib.srukf_detect_features(self._h, g, C.byref(dp), mp.shape[0], _d(mp) if mp.size else None, ar.shape[0],
+                                                  _d(ar) if ar.size else None, _d(uv), cap, C.byref(n_uv), _i(loops), loop_cap,
+                                                  C.byref(n_loop)))
+        return uv[:min(n_uv.value, cap)].copy(), loops[:min(n_loop.value, loop_cap)].copy()
+
+    def capture_appearance(self, first, uv, gray=None):
+        """integrateFeaturesInformation's appearance fields (SLAM.cpp:918-926) of landmarks first .. first + K - 1 cut on the device:
+        the 21x21 init patch at cvRound(uv) of `gray` (None: the held frame), Rwc of the current heading, the robot position."""
+        uv = _c(uv).reshape(-1, 2)
+        g = None
+        if gray is not None:
+            gray = np.ascontiguousarray(gray, dtype=np.uint8)
+            assert gray.shape == (int(self.params.image_h), int(self.params.image_w))
+            g = gray.ctypes.data_as(C.POINTER(C.c_ubyte))
+        self._chk(self._lib.srukf_capture_appearance(self._h, int(first), uv.shape[0], _d(uv), g))
 
     def set_exclusive(self, exclusive):
         """True / GPU_EXCLUSIVE (default): the filter has the GPU to itself (one persistent refactorisation launch per frame that may

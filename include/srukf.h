@@ -189,6 +189,50 @@ int  srukf_set_landmark_appearance(srukf_ctx* ctx, int k, const unsigned char* p
 int  srukf_associate(srukf_ctx* ctx, const unsigned char* gray, double* z, int* matched, double* corr);
 int  srukf_get_match_patch(srukf_ctx* ctx, int k, unsigned char* out);
 
+/* ---- finding new landmarks on the device (addFeatures 552-562: detectAndfilteringFeatures 574-768, integrateFeaturesInformation 918-926) ----
+ * srukf_detect_features: Shi-Tomasi "good features to track" as OpenCV 2.4's goodFeaturesToTrack(gray, max_corners, quality_level, min_dist,
+ *   no mask, block_size, useHarris = false) computes it (GoodFeaturesToTrackDetector, SLAM.cpp:599-600), then the reference's filter pass over
+ *   its key points in order.  One change makes it exactly reproducible: the 3x3 Sobel gradients and their block x block box sums are exact
+ *   integers (BORDER_REFLECT_101 on the frame and on the product maps) and the response r = 0.5 ((A + C) - sqrt((A - C)^2 + 4 B^2)) is fp64
+ *   with a correctly rounded sqrt (OpenCV's cornerMinEigenVal is r / (4 block_size 255)^2: the same ranking).  block_size 3 or 5, otherwise
+ *   SRUKF_ERR_UNSUPPORTED.  Candidates: 1 <= x <= w - 2, 1 <= y <= h - 2, r > quality_level r_max, r = the 3x3 maximum of the thresholded map
+ *   (plateaus all kept); sorted by r descending, EQUAL r IN ASCENDING RASTER ORDER y w + x (std::sort leaves ties unspecified: this rule is
+ *   ours); greedy: rejected when dx^2 + dy^2 < min_dist^2 to a corner accepted before (no test when min_dist < 1); at most max_corners
+ *   (<= 0: no limit but uv_cap).  Key points are integer (x = column, y = row).  The filter pass (SLAM.cpp:647-752), per key point:
+ *     border     DIST_2_BORDER <= x <= w - DIST_2_BORDER, the same for y, or it is dropped;
+ *     unfiltered accept (frame 1 / the first call: the `static flag` of 590, 653-656);
+ *     map veto   (map_gate: m_nMatches != 0, 660) map_px[4 n_map] = (matchLocation.x, .y, predictLocation.x, .y) per map entry: rejected when
+ *                any entry has a zero among its four values (the isThereNoZero else branch, 690-693) or an all-nonzero entry lies within
+ *                min_dist^2 on either location;
+ *     archived   archived_state6[6 n_archived] = FeatureInfo::state of m_featuresAllInfo: with project_archived (isAdding) projected under
+ *                the context's current robot pose (srukf_project, zero pixel error), otherwise at (0, 0) (the zeroed pixelPos, 614-635); every
+ *                archived pixel within min_dist^2 rejects the key point and is reported as a loop point (key point index in GFTT order,
+ *                archived index), all of them (no break, 726);
+ *     pairwise   rejected within min_dist^2 of a key point accepted before in this call (731-750).
+ *   gray = the image_h x image_w frame, or NULL for the frame the handle holds (the last one passed to srukf_associate / srukf_detect_features /
+ *   srukf_capture_appearance; it survives map changes, srukf_reset drops it): SRUKF_ERR_SEQUENCE when it holds none.  uv_out[2 uv_cap] receives
+ *   the accepted key points, *n_uv their number; loop_out[2 loop_cap] the loop points in the order the reference records them (719-723), *n_loop
+ *   their number (either pointer pair may be NULL / 0: what does not fit is counted, not written).  The scratch is allocated on the first call.
+ *   Loop points are reported, not added: the caller integrates the *n_uv key points.
+ * srukf_capture_appearance: integrateFeaturesInformation's appearance fields (918-926) for landmarks [first, first + K) on the device: initPatch
+ *   = the 21 x 21 window of gray (NULL: the held frame) at cvRound(uv) (round half to even), initRotation = Rwc of the current heading
+ *   (getTransferMatrix 1031-1037), initTrans = the robot x, y, z (834-836), initPixel = uv (the pixels passed to srukf_add_landmarks), matchPatch
+ *   zeroed.  Byte for byte what srukf_set_landmark_appearance records for a host-cut patch.  SRUKF_ERR_BAD_ARG when a window leaves the image. */
+typedef struct srukf_detect_params {
+    int    max_corners;       /* m_nInitialRaws at frame 1 / isAdding, m_nProcessRaws otherwise: 8 and 8      SLAM.cpp:177-178, 590-599 */
+    double quality_level;     /* m_qualityLevel 0.1                                                          SLAM.cpp:176 */
+    double min_dist;          /* m_minDist 15.0 (m_minDist2 = min_dist^2)                                    SLAM.cpp:180-181 */
+    int    block_size;        /* m_blockSize 3 (3 or 5 supported)                                            SLAM.cpp:175 */
+    double dist_to_border;    /* DIST_2_BORDER 20.0                                                          SLAM.cpp:48 */
+    int    unfiltered;        /* 1 == m_frame.counter || the first call (static flag)                        SLAM.cpp:590, 653 */
+    int    map_gate;          /* 0 != m_nMatches                                                             SLAM.cpp:660 */
+    int    project_archived;  /* isAdding: archived features projected under the current pose               SLAM.cpp:614-635 */
+} srukf_detect_params;
+int  srukf_detect_features(srukf_ctx* ctx, const unsigned char* gray, const srukf_detect_params* params, int n_map, const double* map_px,
+                           int n_archived, const double* archived_state6, double* uv_out, int uv_cap, int* n_uv,
+                           int* loop_out, int loop_cap, int* n_loop);
+int  srukf_capture_appearance(srukf_ctx* ctx, int first, int K, const double* uv, const unsigned char* gray);
+
 /* Select the storage precision (default SRUKF_STORAGE_F64).  With SRUKF_STORAGE_F32 the state is rounded to float at
  * the end of every refactorisation (and by srukf_set_state); srukf_get_state returns those values widened to double,
  * srukf_get_state_f32 the float arrays themselves (X[n], S[n*n] row-major). */
@@ -313,7 +357,7 @@ int  srukf_debug_set(srukf_ctx* ctx, const char* key, int value);
  * "plan_workers", "plan_kept"). */
 int  srukf_debug_get(srukf_ctx* ctx, const char* key, long long* value);
 /* Diagnostic copy of a device work buffer (tests compare the launch sequences stage by stage): key = "Z", "DZ", "sigR", "Cmat", "Xr1",
- * "Utp", "P1", "h", "Si"; `count` doubles from the start of the buffer. */
+ * "Utp", "P1", "h", "Si", "det_resp" (the response map r of the last srukf_detect_features, image_h x image_w); `count` doubles from the start of the buffer. */
 int  srukf_debug_copy(srukf_ctx* ctx, const char* key, double* out, long long count);
 /* ... and the other way (same keys, plus the operands of one factorisation: "Wf", "Gbak", "G", "D", "gsW", "gsL", "pans", "sync" — byte buffers counted in doubles).
  * srukf_debug_split_replay: ONE launch of the split form's pair (0: k_gmw_pivslab_persist, 1: k_gmw_tiles_persist) `reps` times ALONE against the buffers and flags a
