@@ -4,7 +4,8 @@
 //   srukf_replay.hip  the launch sequences of a frame (seq_*), the rank-aware null set, graph cache, staged replay (srukf_run_frames*)
 //   srukf_split.hip   split form of the persistent factorisation: side stream, probe, buffers
 //   srukf_batch.hip   batched replay (srukf_run_frames_batch)
-//   srukf_map.hip     map changes (srukf_add_landmarks / srukf_delete_landmark) and data association
+//   srukf_map.hip     map changes (srukf_add_landmarks / srukf_delete_landmark / srukf_insert_landmarks) and data association
+//   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -373,6 +374,12 @@ int ensure_image(srukf_ctx* c);
 int take_frame(srukf_ctx* c, const unsigned char* gray);       // gray -> d_image (the held frame); NULL: the held one or SRUKF_ERR_SEQUENCE
 void launch_capture_patch(hipStream_t st, const unsigned char* img, int W, int first, int K, const double* uv, const double* X, int n,
                           unsigned char* app_patch, unsigned char* app_tmpl, double* appR, double* appT, double* appPx, int* has_app);
+
+// ---- loop points (srukf_loop.hip) ----
+#define SRUKF_LM_RECORD_DOUBLES 113                              // k_lm_record's staging block: X6 | S66 | R | t | px | has_app | 448 patch bytes
+void launch_lm_record(hipStream_t st, const double* P66, const double* X, int k, double eps, const unsigned char* app_patch, const double* appR,
+                      const double* appT, const double* appPx, const int* has_app, double* out);
+void launch_lm_insert(hipStream_t st, const double* S, int ld, const double* X, int p6, int L, const double* blk, double* S2, double* X2, int n2, int ld2);
 
 struct ProfScope {
     srukf_ctx* c; int kc; hipEvent_t a = nullptr, b = nullptr;

@@ -1,8 +1,10 @@
-// srukf_map.hip — map changes on the device (srukf_add_landmarks: integrateFeaturesInformation, SLAM.cpp:818-871; srukf_delete_landmark: deleteOneFeature, 2637-2668)
+// srukf_map.hip — map changes on the device (srukf_add_landmarks: integrateFeaturesInformation, SLAM.cpp:818-871; srukf_delete_landmark: deleteOneFeature, 2637-2668;
+// srukf_insert_landmarks / srukf_get_landmark_record: loop points, 948-1015 and 1357-1378)
 // and data association (wrapPatch + dataAssociation, 1803-2009).  A map change rebuilds the context behind the handle (adopt_context).
 
 #include "srukf_ctx.h"
 #include <chrono>
+#include <cmath>
 using namespace srukf_impl;
 
 // srukf_debug_set(0, "timing", 1): wall time of the phases of a map change on stderr (measurement: where do the milliseconds of srukf_add_landmarks /
@@ -39,16 +41,30 @@ static int ensure_appearance(srukf_ctx* c)
     return SRUKF_OK;
 }
 
-// the appearance record of landmark `from` of `a` becomes the one of landmark `to` of `b` (map changes)
-static void copy_appearance(srukf_ctx* a, int from, srukf_ctx* b, int to)
+// the appearance records of landmarks `from` .. `from + count - 1` of `a` become the ones of landmarks `to` .. of `b` (map changes)
+static void copy_appearance(srukf_ctx* a, int from, srukf_ctx* b, int to, int count = 1)
 {
-    const size_t ps = srukf_app_patch_stride(), ts = srukf_app_tmpl_stride();
-    hipMemcpyAsync(b->app_patch + to * ps, a->app_patch + from * ps, ps, hipMemcpyDeviceToDevice, b->stream);
-    hipMemcpyAsync(b->app_tmpl + to * ts, a->app_tmpl + from * ts, ts, hipMemcpyDeviceToDevice, b->stream);
-    hipMemcpyAsync(b->appR + 9 * to, a->appR + 9 * from, sizeof(double) * 9, hipMemcpyDeviceToDevice, b->stream);
-    hipMemcpyAsync(b->appT + 3 * to, a->appT + 3 * from, sizeof(double) * 3, hipMemcpyDeviceToDevice, b->stream);
-    hipMemcpyAsync(b->appPx + 2 * to, a->appPx + 2 * from, sizeof(double) * 2, hipMemcpyDeviceToDevice, b->stream);
-    hipMemcpyAsync(b->has_app + to, a->has_app + from, sizeof(int), hipMemcpyDeviceToDevice, b->stream);
+    if (count < 1) return;
+    const size_t ps = srukf_app_patch_stride(), ts = srukf_app_tmpl_stride(), m = (size_t)count;
+    hipMemcpyAsync(b->app_patch + to * ps, a->app_patch + from * ps, ps * m, hipMemcpyDeviceToDevice, b->stream);
+    hipMemcpyAsync(b->app_tmpl + to * ts, a->app_tmpl + from * ts, ts * m, hipMemcpyDeviceToDevice, b->stream);
+    hipMemcpyAsync(b->appR + 9 * to, a->appR + 9 * from, sizeof(double) * 9 * m, hipMemcpyDeviceToDevice, b->stream);
+    hipMemcpyAsync(b->appT + 3 * to, a->appT + 3 * from, sizeof(double) * 3 * m, hipMemcpyDeviceToDevice, b->stream);
+    hipMemcpyAsync(b->appPx + 2 * to, a->appPx + 2 * from, sizeof(double) * 2 * m, hipMemcpyDeviceToDevice, b->stream);
+    hipMemcpyAsync(b->has_app + to, a->has_app + from, sizeof(int) * m, hipMemcpyDeviceToDevice, b->stream);
+}
+
+// no appearance record for landmarks `to` .. `to + count - 1` of `b`: has_app = 0, every field zeroed (a revived context holds a past life's records there)
+static void clear_appearance(srukf_ctx* b, int to, int count)
+{
+    if (count < 1) return;
+    const size_t ps = srukf_app_patch_stride(), ts = srukf_app_tmpl_stride(), m = (size_t)count;
+    hipMemsetAsync(b->app_patch + to * ps, 0, ps * m, b->stream);
+    hipMemsetAsync(b->app_tmpl + to * ts, 0, ts * m, b->stream);
+    hipMemsetAsync(b->appR + 9 * to, 0, sizeof(double) * 9 * m, b->stream);
+    hipMemsetAsync(b->appT + 3 * to, 0, sizeof(double) * 3 * m, b->stream);
+    hipMemsetAsync(b->appPx + 2 * to, 0, sizeof(double) * 2 * m, b->stream);
+    hipMemsetAsync(b->has_app + to, 0, sizeof(int) * m, b->stream);
 }
 
 namespace srukf_impl {
@@ -310,6 +326,104 @@ int srukf_delete_landmark(srukf_ctx* c, int id)
         if (rc) { c->err = c2->err; srukf_destroy(c2); return rc; }
         for (int k = 0, a = 0; k < N; k++) if (k != id) copy_appearance(c, k, c2, a++);
         hipStreamSynchronize(c->stream);
+    }
+    const int storage = c->storage;
+    mt.mark("appearance");
+    adopt_context(c, c2);
+    mt.mark("adopt+destroy");
+    rc = srukf_set_storage(c, storage); if (rc) return rc;
+    mt.mark("set_storage");
+    rc = update_null_set(c); if (rc) return rc;
+    canonicalize_null_rows(c);
+    mt.mark("null_set");
+    return srukf_set_new_landmarks(c, k_new);
+}
+
+// What an archived landmark takes along (FeatureInfo, SLAM.cpp:1357-1378, 2516-2532): its six rows of X, the upper Cholesky factor of its marginal block
+// P66 = (S^T S)[6k:6k+6, 6k:6k+6] (k_block_cov, then k_lm_record factors it in the order include/srukf.h states) and its appearance record, in one round trip.
+int srukf_get_landmark_record(srukf_ctx* c, int k, double X6[6], double S66[36], unsigned char* patch, double R[9], double t[3], double px[2], int* has_app)
+{
+    if (!c || k < 0 || k >= c->d.N) return SRUKF_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    step_commit_motion(c);
+    double* dout = c->G;                                                 // G is scratch outside the refactorisation
+    srukf_launch_block_cov(c->stream, c->d, c->S, 6 * k, 6, c->small, nullptr);
+    launch_lm_record(c->stream, c->small, c->X, k, c->p.epsilon, c->app_patch, c->appR, c->appT, c->appPx, c->has_app, dout);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->hstage, dout, sizeof(double) * SRUKF_LM_RECORD_DOUBLES, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double* h = c->hstage;
+    if (X6) memcpy(X6, h, sizeof(double) * 6);
+    if (S66) memcpy(S66, h + 6, sizeof(double) * 36);
+    if (R) memcpy(R, h + 42, sizeof(double) * 9);
+    if (t) memcpy(t, h + 51, sizeof(double) * 3);
+    if (px) memcpy(px, h + 54, sizeof(double) * 2);
+    if (has_app) *has_app = h[56] != 0.0 ? 1 : 0;
+    if (patch) memcpy(patch, h + 57, 441);
+    return SRUKF_OK;
+}
+
+// integrateFeaturesInformation's loop points (SLAM.cpp:948-1015) with stated semantics: L landmarks with known means X6 and upper-triangular square-root blocks
+// S66 and no cross-covariance enter the state at landmark positions [N - K_new, N - K_new + L), in front of the landmarks the last srukf_add_landmarks armed.
+// X' and S' are copies (k_lm_insert): P' = Pi (P (+) S66_0^T S66_0 (+) ...) Pi^T.  The context is rebuilt for N + L landmarks in place as srukf_add_landmarks
+// rebuilds it; K_new is kept.  The new slots get exactly the appearance record passed (patches NULL: none, whatever a revived context held there).
+int srukf_insert_landmarks(srukf_ctx* c, int L, const double* X6, const double* S66, const unsigned char* patches, const double* R, const double* t, const double* px)
+{
+    if (!c || L < 1 || !X6 || !S66) return SRUKF_ERR_BAD_ARG;
+    if (patches && (!R || !t || !px)) { c->err = "insert_landmarks: a patch needs R, t and px"; return SRUKF_ERR_BAD_ARG; }
+    auto finite = [](const double* a, size_t m) { for (size_t i = 0; i < m; i++) if (!std::isfinite(a[i])) return false; return true; };
+    if (!finite(X6, 6 * (size_t)L) || !finite(S66, 36 * (size_t)L) || (R && !finite(R, 9 * (size_t)L)) || (t && !finite(t, 3 * (size_t)L)) ||
+        (px && !finite(px, 2 * (size_t)L))) { c->err = "insert_landmarks: an input is not finite"; return SRUKF_ERR_BAD_ARG; }
+    for (int j = 0; j < L; j++)
+        for (int a = 1; a < 6; a++)
+            for (int b = 0; b < a; b++)
+                if (S66[36 * (size_t)j + 6 * a + b] != 0.0) { c->err = "insert_landmarks: S66 is not upper triangular"; return SRUKF_ERR_BAD_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    MapTimer mt("insert_landmarks");
+    step_commit_motion(c); step_invalidate(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    mt.mark("sync");
+    const int N = c->d.N, k_new = c->K_new, p0 = N - k_new;
+    srukf_ctx* c2 = nullptr;
+    int rc = ctx_obtain(c, &c2, N + L);
+    if (rc) { c->err = std::string("insert_landmarks: ") + g_create_error; return rc; }
+    mt.mark("create");
+    double* d_blk = nullptr;
+    if (srukf_dmalloc_on(&d_blk, sizeof(double) * 42 * (size_t)L, c->stream) != hipSuccess) { srukf_destroy(c2); c->err = "insert_landmarks: out of device memory"; return SRUKF_ERR_NOMEM; }
+    hipError_t e = hipMemcpyAsync(d_blk, X6, sizeof(double) * 6 * (size_t)L, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk + 6 * (size_t)L, S66, sizeof(double) * 36 * (size_t)L, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_lm_insert(c->stream, c->S, c->d.np, c->X, 6 * p0, L, d_blk, c2->S, c2->X, c2->d.n, c2->d.np);
+        e = hipGetLastError();
+    }
+    srukf_dfree_on(d_blk, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    mt.mark("numeric");
+    if (e != hipSuccess) { srukf_destroy(c2); c->err = std::string("insert_landmarks: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
+    if (c->app_patch || patches || c2->app_patch) {
+        rc = ensure_appearance(c2);
+        if (rc) { c->err = c2->err; srukf_destroy(c2); return rc; }
+        if (c->app_patch) {                                              // the old landmarks keep their records
+            copy_appearance(c, 0, c2, 0, p0);
+            copy_appearance(c, p0, c2, p0 + L, k_new);
+        } else {
+            clear_appearance(c2, 0, N + L);
+        }
+        if (patches) {
+            const size_t ps = srukf_app_patch_stride(), ts = srukf_app_tmpl_stride();
+            std::vector<int> one(L, 1);
+            e = hipMemcpy2DAsync(c2->app_patch + p0 * ps, ps, patches, 441, 441, L, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(c2->app_tmpl + p0 * ts, 0, ts * (size_t)L, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(c2->appR + 9 * p0, R, sizeof(double) * 9 * (size_t)L, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(c2->appT + 3 * p0, t, sizeof(double) * 3 * (size_t)L, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(c2->appPx + 2 * p0, px, sizeof(double) * 2 * (size_t)L, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(c2->has_app + p0, one.data(), sizeof(int) * (size_t)L, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);     // (pageable host memory)
+        } else {
+            clear_appearance(c2, p0, L);
+            e = hipStreamSynchronize(c->stream);
+        }
+        if (e != hipSuccess) { srukf_destroy(c2); c->err = std::string("insert_landmarks: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
     }
     const int storage = c->storage;
     mt.mark("appearance");

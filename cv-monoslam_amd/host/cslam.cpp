@@ -179,6 +179,8 @@ bool CSLAM::detectAndfilteringFeatures()
     m_loopPointCounter = nLoop;                                                                                 // 604, 721
     if ((int)m_loopPointID.size() < nLoop) m_loopPointID.resize(nLoop);
     for (int q = 0; q < nLoop; q++) m_loopPointID[q] = m_featuresAllInfo[loops[2 * q + 1]].ID;                 // 719
+    loopArchive_.clear();
+    for (int q = 0; q < nLoop; q++) loopArchive_.push_back(loops[2 * q + 1]);
     const int counter = nUv + nLoop;
     m_nFilters = counter;                                                                                       // 756-766
     runningCount_ = isAdding ? counter : runningCount_ + counter;
@@ -224,12 +226,83 @@ bool CSLAM::addFeaturesOnDevice()
     runningCount_ = m_nMapFeatures;
     m_keyPoints.clear();
     if (!detectAndfilteringFeatures() || !insureEnoughFeatures()) return false;
+    const bool reinsert = isAdding && reinsertLoopPoints;
+    if (reinsert && !reinsertLoops()) return false;                                                             // 948-1015: in front of the key points
     const int K = (int)m_keyPoints.size(), first = m_nMapFeatures;
-    if (K == 0) return true;
-    std::vector<double> kp(2 * (size_t)K);
-    for (int k = 0; k < K; k++) { kp[2 * k] = m_keyPoints[k].x; kp[2 * k + 1] = m_keyPoints[k].y; }
-    if (!integrateFeaturesInformation(K, kp.data())) return false;
-    return check(srukf_capture_appearance(ctx_, first, K, kp.data(), nullptr));                                  // 918-926
+    if (K > 0) {
+        std::vector<double> kp(2 * (size_t)K);
+        for (int k = 0; k < K; k++) { kp[2 * k] = m_keyPoints[k].x; kp[2 * k + 1] = m_keyPoints[k].y; }
+        if (!integrateFeaturesInformation(K, kp.data())) return false;
+        if (!check(srukf_capture_appearance(ctx_, first, K, kp.data(), nullptr))) return false;                 // 918-926
+    }
+    if (reinsert && logDetectPasses && !m_detectLog.empty()) { m_detectLog.back().n_after = m_nMapFeatures; m_detectLog.back().archived_after = (int)m_featuresAllInfo.size(); }
+    return true;
+}
+
+// What an archived landmark takes along for re-insertion (the reference's FeatureInfo::sr / initPatch / initRotation / initTrans, read back at 961-973):
+// landmark k of the current state, one device round trip.  fi.state keeps the rows the archive site copied from m_X_k (the same values).
+bool CSLAM::recordFeature(FeatureInfo& fi, int k)
+{
+    double X6[6], px[2]; int has = 0;
+    if (!check(srukf_get_landmark_record(ctx_, k, X6, fi.sr, fi.initPatch, fi.initRotation, fi.initTrans, px, &has))) return false;
+    fi.hasInitPatch = has != 0;
+    fi.hasRecord = true;
+    return true;
+}
+
+// The isLoop branch of integrateFeaturesInformation (SLAM.cpp:948-1015) with the semantics of DESIGN.md §12: the archived entries the last detection pass
+// reported as loop points, each once, in the order first reported, go back into the filter with their archived state and sr (srukf_insert_landmarks) and
+// their appearance record, behind the map and in front of the key points integrated next.  Entries without a record stay archived (they are still reported).
+// The new nodes keep their archived ID (ID is not advanced) with isLoop = true; their archive entries are erased.
+bool CSLAM::reinsertLoops()
+{
+    std::vector<int> take;
+    for (int a : loopArchive_)
+        if (a >= 0 && a < (int)m_featuresAllInfo.size() && m_featuresAllInfo[a].hasRecord && std::find(take.begin(), take.end(), a) == take.end()) take.push_back(a);
+    std::vector<int> ids;
+    std::vector<double> x6s, srs;
+    if (!take.empty()) {
+        mirrorsFresh_ = false;
+        if (!check(srukf_set_new_landmarks(ctx_, 0))) return false;             // m_nAddings = 0 here: the loop points go behind the whole map
+        // one srukf_insert_landmarks per run of entries with / without an appearance record (a call gives records to all of its landmarks or to none)
+        for (size_t q = 0; q < take.size();) {
+            const bool app = m_featuresAllInfo[take[q]].hasInitPatch;
+            size_t e = q;
+            while (e < take.size() && m_featuresAllInfo[take[e]].hasInitPatch == app) e++;
+            const int L = (int)(e - q);
+            std::vector<double> X6(6 * (size_t)L), S66(36 * (size_t)L), R(9 * (size_t)L), t(3 * (size_t)L), px(2 * (size_t)L);
+            std::vector<unsigned char> patches(app ? 441 * (size_t)L : 0);
+            for (int j = 0; j < L; j++) {
+                const FeatureInfo& fi = m_featuresAllInfo[take[q + j]];
+                memcpy(&X6[6 * j], fi.state, sizeof fi.state); memcpy(&S66[36 * j], fi.sr, sizeof fi.sr);
+                memcpy(&R[9 * j], fi.initRotation, sizeof fi.initRotation); memcpy(&t[3 * j], fi.initTrans, sizeof fi.initTrans);
+                px[2 * j] = fi.initPixel.x; px[2 * j + 1] = fi.initPixel.y;
+                if (app) memcpy(&patches[441 * (size_t)j], fi.initPatch, 441);
+            }
+            if (!check(srukf_insert_landmarks(ctx_, L, X6.data(), S66.data(), app ? patches.data() : nullptr, app ? R.data() : nullptr,
+                                              app ? t.data() : nullptr, app ? px.data() : nullptr))) return false;
+            q = e;
+        }
+        for (int a : take) {
+            const FeatureInfo& fi = m_featuresAllInfo[a];
+            PointsMap pm; pm.ID = fi.ID; pm.isLoop = true; pm.xyz = fi.initXYZ; pm.initPixel = fi.initPixel;
+            mapStore.push_back(pm); ids.push_back(fi.ID);
+            x6s.insert(x6s.end(), fi.state, fi.state + 6); srs.insert(srs.end(), fi.sr, fi.sr + 36);
+        }
+        relinkMap();
+        m_nMapFeatures += (int)take.size();
+        std::vector<int> gone = take;
+        std::sort(gone.rbegin(), gone.rend());
+        for (int a : gone) m_featuresAllInfo.erase(m_featuresAllInfo.begin() + a);
+        const int n = 6 * m_nMapFeatures + 4;
+        m_X_k.create(n, 1); m_S_k.create(n, n); m_P_k.create(n, n);
+        refreshMirrors();
+    }
+    if (logDetectPasses && !m_detectLog.empty()) {
+        DetectPass& d = m_detectLog.back();
+        d.reinsertRan = true; d.reinserted = ids; d.reinsertedX6 = x6s; d.reinsertedSr = srs;
+    }
+    return true;
 }
 
 // ---- display accessors -----------------------------------------------------------------------------------------
@@ -294,6 +367,7 @@ bool CSLAM::updateFeaturesInformation()
                 fi.initXYZ = map_p->xyz; fi.initPixel = map_p->initPixel;
                 for (int e = 0; e < 6; e++) fi.state[e] = m_X_k.at(6 * id + e, 0);
                 fi.position = map_p->xyz; memcpy(fi.cov, map_p->cov, sizeof fi.cov); fi.axis = map_p->axis; fi.sigma = map_p->sigma;
+                if (reinsertLoopPoints && !recordFeature(fi, id)) return false;                                   // before the landmark leaves
                 m_featuresAllInfo.push_back(fi);
             }
             if (!deleteOneFeature(id)) return false;                                                             // 2554 (m_nDeletes++, m_nMapFeatures--: 2662-2664)
@@ -469,6 +543,7 @@ bool CSLAM::redirection()
         fi.position = map_p->xyz;
         memcpy(fi.cov, map_p->cov, sizeof fi.cov);
         fi.axis = map_p->axis; fi.sigma = map_p->sigma;
+        if (reinsertLoopPoints && !recordFeature(fi, id)) return false;                                           // before srukf_destroy
         m_featuresAllInfo.push_back(fi);
     }
     const double X4[4] = { m_X_k.at(n - 4, 0), m_X_k.at(n - 3, 0), 0.0, m_odoTheta.at(1, c) };                 // 1396-1400

@@ -64,6 +64,14 @@ struct FeatureInfo {
     double  cov[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     Quaternion axis;
     Point3d sigma;
+    // what the reference's isLoop branch of integrateFeaturesInformation reads back (SLAM.cpp:961-973), filled by srukf_get_landmark_record when
+    // CSLAM::reinsertLoopPoints is on (hasRecord): sr = upper Cholesky factor of the landmark's marginal 6x6 block of P (row-major), the appearance record
+    double  sr[36] = {0};
+    unsigned char initPatch[441] = {0};
+    double  initRotation[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double  initTrans[3] = {0, 0, 0};
+    bool    hasInitPatch = false;            // the landmark had an appearance record (initPatch / initRotation / initTrans / initPixel)
+    bool    hasRecord = false;
 };
 
 // SLAM.h:85-92
@@ -141,8 +149,9 @@ public:
     // ---- finding new landmarks on the device (addFeatures 552-562) --------------------------------------------------------------------------
     // With m_gryImage set and no addFeatures callback installed, SLAM() and the redirection restart detect on the device: detectAndfilteringFeatures,
     // insureEnoughFeatures, then integrateFeaturesInformation for the accepted key points and srukf_capture_appearance for the new landmarks
-    // (initPatch / initRotation / initTrans, 918-926).  Loop points are reported (m_loopPointID, m_loopPointCounter), not added; m_nMapFeatures stays
-    // the true map size.
+    // (initPatch / initRotation / initTrans, 918-926).  Loop points are reported (m_loopPointID, m_loopPointCounter); with reinsertLoopPoints on, the
+    // archived landmarks an isAdding pass met again go back into the filter in front of the new key points (isLoop nodes).  m_nMapFeatures stays the
+    // true map size.
     const unsigned char* m_gryImage = nullptr;          // the current gray frame, image_h x image_w, row-major (SLAM.h: m_gryImage); set by the host
     int    m_blockSize = 3;                             // SLAM.cpp:175
     double m_qualityLevel = 0.1;                        // 176
@@ -162,6 +171,9 @@ public:
         int call = 0, frame = 0, n_map = 0, n_matches = 0, running = 0;   // which addFeatures, m_frame.counter, true map size, m_nMatches, running count after the pass
         srukf_detect_params params{}; double pose[4] = {0, 0, 0, 0};     // the switches and the robot pose the archive was projected under
         std::vector<double> map_px, archived, uv; std::vector<int> loops;
+        bool reinsertRan = false; std::vector<int> reinserted;           // (last pass of an isAdding call with reinsertLoopPoints on) the IDs put back,
+        std::vector<double> reinsertedX6, reinsertedSr;                   // their archived state (6 each) and sr (36 each)
+        int n_after = 0, archived_after = 0;                              // the map size and the archive size when the call returned
     };
     bool logDetectPasses = false;
     double m_detectTime = 0; int m_nDetectCalls = 0;    // wall time of the on-device addFeatures (detection passes + integration + capture) and their number
@@ -193,6 +205,10 @@ public:
     Mat    m_odoTheta;                   // 3 x (CAPACITY+1): index, theta, redirection flag (SLAM.cpp:235)
     Mat    m_X_k, m_S_k, m_P_k;          // host mirrors, refreshed after every frame (m_P_k: robot block only unless fullCovariance)
     bool   fullCovariance = false;       // true: m_P_k = S^T S in full (SLAM.cpp:2404), false: only the blocks the host reads
+    // true: the archive sites (redirection, updateFeaturesInformation) keep each landmark's record (srukf_get_landmark_record) and an isAdding
+    // addFeatures puts the loop points of its last pass back into the filter (srukf_insert_landmarks, SLAM.cpp:948-1015).
+    // false (default): loop points are only reported
+    bool   reinsertLoopPoints = false;
     bool   isRecordRobotInfo = false;
     std::string m_recordRobotDir = "RobotPath.txt";
     double MIN_STEP_X = 0.01, MIN_STEP_Y = 0.01, MIN_STEP_THETA = 45;   // SLAM.cpp:45-47
@@ -205,6 +221,8 @@ public:
 private:
     bool redirection();
     bool addFeaturesOnDevice();
+    bool recordFeature(FeatureInfo& fi, int k);
+    bool reinsertLoops();
     void relinkMap();
     void refreshMirrors();
     bool check(int rc);
@@ -216,6 +234,7 @@ private:
     bool firstDetect_ = true;            // the reference's `static bool flag` of detectAndfilteringFeatures (590, 653-656), per facade instance
     int runningCount_ = 0;               // the reference's running m_nMapFeatures of the pass schedule (758-766, 782)
     int addCalls_ = 0;                   // addFeaturesOnDevice calls (DetectPass::call)
+    std::vector<int> loopArchive_;       // archive indices of the loop points of the last detection pass, in the order reported
 };
 
 }  // namespace monoslam

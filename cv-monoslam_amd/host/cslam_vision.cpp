@@ -1,10 +1,14 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
+// loops: CSLAM::reinsertLoopPoints on (the restart's isAdding addFeatures puts the archived landmarks its last pass met again back into the filter).
+//   Adds, and only with it, a "reinsert" line per restart (the archive's IDs before the frame, the IDs put back, map and archive size behind the
+//   restart's addFeatures, the archived X6 and sr of what was put back) and an
+//   "ids" line per frame (ID and isLoop of every map node, state order).
 // warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
 // Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
 #include <cstdio>
@@ -16,7 +20,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -24,8 +28,9 @@ int main(int argc, char** argv)
     std::vector<unsigned char> frames((size_t)W * H * F);
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
-    int redirect = 0; bool warmup = false;
-    for (int a = 3; a < argc; a++) if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true;
+    int redirect = 0; bool warmup = false, loops = false;
+    for (int a = 3; a < argc; a++)
+        if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
     if (warmup) {
         monoslam::CSLAM w;
         w.m_params.image_w = W; w.m_params.image_h = H; w.MIN_STEP_X = w.MIN_STEP_Y = 0.0;
@@ -41,6 +46,7 @@ int main(int argc, char** argv)
     if (!SLAM.loadOdometryData(argv[2])) { fprintf(stderr, "%s\n", SLAM.lastError.c_str()); return 1; }
     if (redirect > 0) SLAM.m_odoTheta.at(2, redirect) = 1;
     SLAM.logDetectPasses = true;
+    SLAM.reinsertLoopPoints = loops;
     const unsigned char* cur = nullptr;
     SLAM.dataAssociation = [&](monoslam::CSLAM& s) { s.dataAssociationOnDevice(cur); };     // loadPictures + dataAssociation (SLAM.cpp:95-97)
     const int steps = SLAM.m_odoCounter - 1 - (redirect > 0 ? 1 : 0);
@@ -50,6 +56,8 @@ int main(int argc, char** argv)
         SLAM.m_gryImage = cur;
         const size_t logged = SLAM.m_detectLog.size();
         const double addBefore = SLAM.m_detectTime;
+        std::vector<monoslam::FeatureInfo> archive;
+        if (loops) archive = SLAM.m_featuresAllInfo;                                // (what the restart of this frame may put back)
         SLAM.SLAM();
         if (!SLAM.lastError.empty()) { fprintf(stderr, "frame %d: %s\n", fr, SLAM.lastError.c_str()); return 1; }
         if (fr == 0) addWall = SLAM.m_detectTime - addBefore;
@@ -63,10 +71,19 @@ int main(int argc, char** argv)
             printf("arch"); for (double v : p.archived) printf(" %.17g", v); printf("\n");
             printf("uv"); for (double v : p.uv) printf(" %.17g", v); printf("\n");
             printf("loops"); for (int v : p.loops) printf(" %d", v); printf("\n");
+            if (loops && p.reinsertRan) {
+                printf("reinsert call %d archive %d", p.call, (int)archive.size()); for (const auto& fi : archive) printf(" %d", fi.ID);
+                printf(" ids %d", (int)p.reinserted.size()); for (int id : p.reinserted) printf(" %d", id);
+                printf(" n_after %d archived_after %d", p.n_after, p.archived_after);
+                printf(" x6"); for (double v : p.reinsertedX6) printf(" %.17g", v);
+                printf(" sr"); for (double v : p.reinsertedSr) printf(" %.17g", v);
+                printf("\n");
+            }
         }
         printf("frame %d n_map %d map_size %d archived %d matches %d loops %d\n", fr, SLAM.m_nMapFeatures, (int)SLAM.mapStore.size(),
                (int)SLAM.m_featuresAllInfo.size(), SLAM.m_nMatches, SLAM.m_loopPointCounter);
         printf("init"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %.17g %.17g", m->initPixel.x, m->initPixel.y); printf("\n");
+        if (loops) { printf("ids"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %d %d", m->ID, m->isLoop ? 1 : 0); printf("\n"); }
         const int n = SLAM.m_X_k.rows;
         printf("pose %.17g %.17g %.17g %.17g\n", SLAM.m_X_k.at(n - 4, 0), SLAM.m_X_k.at(n - 3, 0), SLAM.m_X_k.at(n - 2, 0), SLAM.m_X_k.at(n - 1, 0));
     }

@@ -25,7 +25,7 @@ EXPORTS = [
     "srukf_get_landmark_block", "srukf_get_landmarks_cartesian", "srukf_get_frame_view", "srukf_get_covariance", "srukf_predict_motion", "srukf_predict_motion_next", "srukf_predict_measurement",
     "srukf_update", "srukf_set_new_landmarks", "srukf_add_landmarks", "srukf_delete_landmark", "srukf_set_storage", "srukf_set_exclusive", "srukf_set_rank_aware", "srukf_null_directions", "srukf_run_frames_batch", "srukf_prepare_frames", "srukf_debug_poke_state", "srukf_get_state_f32", "srukf_set_landmark_appearance", "srukf_associate", "srukf_get_match_patch", "srukf_stage_sequence", "srukf_run_frames_async", "srukf_run_frames", "srukf_synchronize", "srukf_set_profiling",
     "srukf_clamp_info", "srukf_debug_set", "srukf_debug_get", "srukf_debug_copy", "srukf_debug_upload", "srukf_debug_split_replay", "srukf_debug_gmw_stamps", "srukf_debug_starve_workers", "srukf_debug_allow_mixed", "srukf_profile_count", "srukf_profile_get", "srukf_profile_reset", "srukf_dims", "srukf_gmw_host",
-    "srukf_project_host", "srukf_detect_features", "srukf_capture_appearance",
+    "srukf_project_host", "srukf_detect_features", "srukf_capture_appearance", "srukf_get_landmark_record", "srukf_insert_landmarks",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -123,6 +123,9 @@ def load_library(path=None):
     if hasattr(L, "srukf_detect_features"):            # (an A/B build of an older library, bench.py --lib, has no detection: build() checks EXPORTS)
         L.srukf_detect_features.argtypes = [C.c_void_p, _bp, C.POINTER(DetectParams), C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, _ip, _ip, C.c_int, _ip]
         L.srukf_capture_appearance.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _bp]
+    if hasattr(L, "srukf_insert_landmarks"):           # (idem: loop points)
+        L.srukf_get_landmark_record.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _bp, _dp, _dp, _dp, _ip]
+        L.srukf_insert_landmarks.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _bp, _dp, _dp, _dp]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -337,6 +340,31 @@ class Filter:
             assert gray.shape == (int(self.params.image_h), int(self.params.image_w))
             g = gray.ctypes.data_as(C.POINTER(C.c_ubyte))
         self._chk(self._lib.srukf_capture_appearance(self._h, int(first), uv.shape[0], _d(uv), g))
+
+    def get_landmark_record(self, k):
+        """What an archived landmark takes along (srukf_get_landmark_record): dict with X6[6], S66[6,6] (upper Cholesky factor of the marginal block
+        P66), patch[21,21] uint8, R[3,3], t[3], px[2] and has_app (False: no appearance record, the other appearance fields are zero)."""
+        x6, S, patch, R, t, px, has = np.zeros(6), np.zeros((6, 6)), np.zeros((21, 21), dtype=np.uint8), np.zeros((3, 3)), np.zeros(3), np.zeros(2), C.c_int()
+        self._chk(self._lib.srukf_get_landmark_record(self._h, int(k), _d(x6), _d(S), patch.ctypes.data_as(C.POINTER(C.c_ubyte)), _d(R), _d(t), _d(px),
+                                                      C.byref(has)))
+        return {"X6": x6, "S66": S, "patch": patch, "R": R, "t": t, "px": px, "has_app": bool(has.value)}
+
+    def insert_landmarks(self, X6, S66, patches=None, R=None, t=None, px=None):
+        """Loop points back into the filter (srukf_insert_landmarks): L landmarks with means X6[L,6] and upper-triangular square-root blocks S66[L,6,6],
+        no cross-covariance, at positions [N - K_new, N - K_new + L).  patches[L,21,21] uint8 with R[L,3,3], t[L,3], px[L,2]: their appearance records
+        (None: no record).  The filter grows to N + L."""
+        X6 = _c(X6).reshape(-1, 6)
+        L = X6.shape[0]
+        S66 = _c(S66).reshape(L, 6, 6)
+        pb = None
+        if patches is not None:
+            patches = np.ascontiguousarray(patches, dtype=np.uint8).reshape(L, 21, 21)
+            pb = patches.ctypes.data_as(C.POINTER(C.c_ubyte))
+        R = _c(R).reshape(L, 9) if R is not None else None
+        t = _c(t).reshape(L, 3) if t is not None else None
+        px = _c(px).reshape(L, 2) if px is not None else None
+        self._chk(self._lib.srukf_insert_landmarks(self._h, L, _d(X6), _d(S66), pb, _d(R), _d(t), _d(px)))
+        self._refresh_dims()
 
     def set_exclusive(self, exclusive):
         """True / GPU_EXCLUSIVE (default): the filter has the GPU to itself (one persistent refactorisation launch per frame that may

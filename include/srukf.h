@@ -213,7 +213,8 @@ int  srukf_get_match_patch(srukf_ctx* ctx, int k, unsigned char* out);
  *   srukf_capture_appearance; it survives map changes, srukf_reset drops it): SRUKF_ERR_SEQUENCE when it holds none.  uv_out[2 uv_cap] receives
  *   the accepted key points, *n_uv their number; loop_out[2 loop_cap] the loop points in the order the reference records them (719-723), *n_loop
  *   their number (either pointer pair may be NULL / 0: what does not fit is counted, not written).  The scratch is allocated on the first call.
- *   Loop points are reported, not added: the caller integrates the *n_uv key points.
+ *   Loop points are reported, not added by this call: the caller integrates the *n_uv key points and may put the archived landmarks back
+ *   with srukf_insert_landmarks.
  * srukf_capture_appearance: integrateFeaturesInformation's appearance fields (918-926) for landmarks [first, first + K) on the device: initPatch
  *   = the 21 x 21 window of gray (NULL: the held frame) at cvRound(uv) (round half to even), initRotation = Rwc of the current heading
  *   (getTransferMatrix 1031-1037), initTrans = the robot x, y, z (834-836), initPixel = uv (the pixels passed to srukf_add_landmarks), matchPatch
@@ -232,6 +233,23 @@ int  srukf_detect_features(srukf_ctx* ctx, const unsigned char* gray, const sruk
                            int n_archived, const double* archived_state6, double* uv_out, int uv_cap, int* n_uv,
                            int* loop_out, int loop_cap, int* n_loop);
 int  srukf_capture_appearance(srukf_ctx* ctx, int first, int K, const double* uv, const unsigned char* gray);
+
+/* ---- loop points: archived landmarks put back into the filter (the redirection archive, SLAM.cpp:1357-1378, 2516-2532; integrateFeaturesInformation's
+ * isLoop branch, 948-1015) ----
+ * srukf_get_landmark_record: what an archived landmark takes along, in one device round trip.  X6 = rows 6k .. 6k+5 of X; S66 = the upper Cholesky
+ *   factor of the landmark's MARGINAL block P66 = (S^T S)[6k:6k+6, 6k:6k+6] (the P66 of srukf_get_landmark_block), with eps = params.epsilon and
+ *   sums in ascending m: d_j = max(eps, P_jj - sum_{m<j} S_mj^2), S_jj = sqrt(d_j), S_ji = (P_ji - sum_{m<j} S_mj S_mi) / S_jj for i > j, zeros
+ *   below the diagonal (row-major).  patch[441] / R[9] / t[3] / px[2] = the landmark's appearance record as srukf_set_landmark_appearance or
+ *   srukf_capture_appearance left it; *has_app = 0 (and zeros) when it has none.  Any output pointer may be NULL.
+ * srukf_insert_landmarks: L landmarks with means X6[6L] and upper-triangular square-root blocks S66[36L] (row-major) and no cross-covariance enter the
+ *   state at landmark positions [N - K_new, N - K_new + L): after the older landmarks, before the K_new landmarks the last srukf_add_landmarks armed
+ *   (which stay the last K_new; K_new is unchanged) and the robot block.  X and S are copied, no arithmetic: P' = Pi (P (+) S66_0^T S66_0 (+) ...) Pi^T.
+ *   The context grows in place like srukf_add_landmarks (staged sequences are dropped).  Old landmarks keep their appearance records; the new ones get
+ *   patches[441 L] / R[9L] / t[3L] / px[2L] (matchPatch zeroed), or with patches == NULL no record (they never match in srukf_associate).
+ *   SRUKF_ERR_BAD_ARG: L < 1, a non-finite input, a nonzero entry below the diagonal of an S66, patches without R, t and px. */
+int  srukf_get_landmark_record(srukf_ctx* ctx, int k, double X6[6], double S66[36], unsigned char* patch, double R[9], double t[3], double px[2], int* has_app);
+int  srukf_insert_landmarks(srukf_ctx* ctx, int L, const double* X6, const double* S66, const unsigned char* patches, const double* R, const double* t,
+                            const double* px);
 
 /* Select the storage precision (default SRUKF_STORAGE_F64).  With SRUKF_STORAGE_F32 the state is rounded to float at
  * the end of every refactorisation (and by srukf_set_state); srukf_get_state returns those values widened to double,
