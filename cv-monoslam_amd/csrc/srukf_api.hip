@@ -390,6 +390,7 @@ int srukf_destroy(srukf_ctx* c)
                      c->perm, c->iperm, c->Sdis, c->ckS, c->ckX, c->ckS2, c->ckX2, c->odo_step, c->export_cnt, c->red_perm, c->red_iperm, c->gdiag, c->red_syrk_tiles, c->syrk_head_tiles_b, c->red_head0_tiles, c->split_fold_list, c->shadowA, c->Utp, c->P1, c->pxy2_tiles, c->nskip, c->slabW, c->slabL, c->gsW, c->gsL, c->S32, c->X32, c->U32, c->mx_part, c->mx_tasks, c->mx_tiles, c->fold_sync, c->dxk, c->A32, c->mxr_part, c->mxr_tasks, c->mxr_tiles, c->mxr_f64_tiles, c->mxr_xt, c->app_patch, c->app_tmpl, c->d_image, c->appR, c->appT, c->appPx, c->corr, c->has_app };
     for (void* b : bufs) if (b) srukf_dfree_on(b, c->stream);
     det_scratch_free(c->det, c->stream);
+    ransac_scratch_free(c->ransac, c->stream);
     gmw_plan_destroy(c->gplan, c->stream);
     gmw_plan_destroy(c->gplan_red, c->stream);
     if (c->side) { hipStreamSynchronize(c->side); hipStreamDestroy(c->side); hipEventDestroy(c->ev_fork); hipEventDestroy(c->ev_join); }
@@ -452,6 +453,7 @@ static int ctx_revive(srukf_ctx* r)
     r->next_odo_valid = false; r->fs_seq_step = false; r->last_update_sequential = false;
     r->step_export_attached = false; r->step_export = StepExport{}; r->mirror_next = false; r->meas_seq = 0;
     r->view_auto = false; r->view_unused = 0; r->view_hits = 0;
+    ransac_scratch_free(r->ransac, r->stream);                   // (allocated again, zeroed, by the first call that needs it: nothing of the former life is read)
     r->step_fast_frames = r->step_slow_frames = 0; r->exact_frames = 0;
     r->profiling = false; r->pev.clear();
     r->err.clear();

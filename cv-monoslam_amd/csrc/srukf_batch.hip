@@ -221,7 +221,7 @@ static int batch_run(srukf_ctx* const* cs, int B, int first, int count, double* 
         srukf_launch_sigr_rows(st, c->d, c->w, c->X, c->S, c->sigR, c->fs, c->red_iperm, c->red_r);
         srukf_launch_project_table(st, c->d, c->w, c->p, c->X, c->S, c->sigR, c->Cmat, c->Z, c->DZ, c->fs, rank_args(c, false, true), null_skip(c));
         c->xr1_pending = false; c->dx_pending = false;          // (the batched launches apply both themselves, every frame)
-        c->async_pending = true; c->phase = 0;
+        c->async_pending = true; c->phase = 0; c->frame_updated = false;
     }
     int f = 0;
     if (graphs) {

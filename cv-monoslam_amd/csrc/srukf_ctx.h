@@ -5,6 +5,7 @@
 //   srukf_split.hip   split form of the persistent factorisation: side stream, probe, buffers
 //   srukf_batch.hip   batched replay (srukf_run_frames_batch)
 //   srukf_map.hip     map changes (srukf_add_landmarks / srukf_delete_landmark / srukf_insert_landmarks) and data association
+//   srukf_ransac.hip  1-point RANSAC: the consensus over all single-match hypotheses, the measurement prediction from the posterior
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
 #pragma once
@@ -130,6 +131,16 @@ struct DetScratch {
     void *in = nullptr, *out = nullptr; size_t in_bytes = 0, out_bytes = 0;
 };
 
+// 1-point RANSAC (srukf_ransac.hip), allocated on the first call and sized by the context's N (it stays with its context through retire / revive, which frees it).
+// Ut: k_pxy's product for the consensus; D / F: d_ij and the inlier flag of every pair (N x N); zin: z | matched; res: dist | inlier | votes | best.
+// X, S, odo, Cm, fs: a copy of the state, an odometry pair and where k_motion leaves its by-products (the fast path's consensus; srukf_repredict_measurement);
+// the rest: the slow path's predict half on that copy
+struct RansacScratch {
+    double *Ut = nullptr, *D = nullptr, *zin = nullptr, *res = nullptr, *X = nullptr, *S = nullptr, *odo = nullptr;
+    double *sigR = nullptr, *Cm = nullptr, *Z = nullptr, *DZ = nullptr, *h = nullptr, *PxyR = nullptr, *mpart = nullptr;
+    unsigned char* F = nullptr; int* votes = nullptr; FrameScalars* fs = nullptr;
+};
+
 struct srukf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -160,6 +171,7 @@ struct srukf_ctx {
     bool frame_valid = false;              // d_image holds the caller's last frame (srukf_associate / srukf_detect_features / srukf_capture_appearance with a
                                            // frame): handed over at map changes with the buffer (adopt_context), dropped by srukf_reset
     DetScratch det;                        // srukf_detect_features (handed over at map changes too)
+    RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
     int storage = SRUKF_STORAGE_F64;       // SRUKF_STORAGE_F32 / _F32_MIXED: X32 / S32 hold the inter-frame state
     float *S32 = nullptr, *X32 = nullptr;
     // SRUKF_STORAGE_F32_MIXED: S^T S - U U^T on the fp32 matrix pipe (srukf_mixed.hip)
@@ -258,6 +270,7 @@ struct srukf_ctx {
     double* hmeas = nullptr;               // inside the hfs allocation, behind the robot view and the flag word
     // state machine
     int phase = 0;   // 0 idle, 1 after predict_motion, 2 after predict_measurement
+    bool frame_updated = false;            // the last call that touched the state was a srukf_update of the frame in hand (srukf_repredict_measurement may follow)
     double next_odo[6] = { 0, 0, 0, 0, 0, 0 }; bool next_odo_valid = false;   // srukf_predict_motion_next: the pair the next srukf_predict_motion will bring
     // Fast path of the step-wise API (step_* below): a frame of the staged replay's own launch sequence ("fused tail" mode) cut in two at the host's association step
     double* odo_step = nullptr;            // device: (prev, cur, next) poses of the frame in flight — a three-pose "staged sequence" fs->odo_seq points at
@@ -374,6 +387,9 @@ int ensure_image(srukf_ctx* c);
 int take_frame(srukf_ctx* c, const unsigned char* gray);       // gray -> d_image (the held frame); NULL: the held one or SRUKF_ERR_SEQUENCE
 void launch_capture_patch(hipStream_t st, const unsigned char* img, int W, int first, int K, const double* uv, const double* X, int n,
                           unsigned char* app_patch, unsigned char* app_tmpl, double* appR, double* appT, double* appPx, int* has_app);
+
+// ---- 1-point RANSAC (srukf_ransac.hip) ----
+void ransac_scratch_free(RansacScratch& s, hipStream_t st);
 
 // ---- loop points (srukf_loop.hip) ----
 #define SRUKF_LM_RECORD_DOUBLES 113                              // k_lm_record's staging block: X6 | S66 | R | t | px | has_app | 448 patch bytes

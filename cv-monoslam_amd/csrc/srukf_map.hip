@@ -90,7 +90,7 @@ void adopt_context(srukf_ctx* c, srukf_ctx* c2)
     std::swap(c->d_image, c2->d_image); std::swap(c->frame_valid, c2->frame_valid); std::swap(c->det, c2->det);
     c2->frame_valid = false;
     ctx_retire(c, c2);                                           // (not destroyed: revived when the map has this size again — ctx_obtain)
-    c->phase = 0;
+    c->phase = 0; c->frame_updated = false;
     if (shared != c->gmw_shared) set_shared(c, shared, tenants);
 }
 

@@ -1105,7 +1105,7 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
         hipLaunchKernelGGL(k_set_run, dim3(1), dim3(1), 0, c->stream, c->fs, first, clear, traj);
         replay_one_frame(c);
         set_null_canonical(c);
-        c->async_pending = true; c->phase = 0; clear = 0;
+        c->async_pending = true; c->phase = 0; c->frame_updated = false; clear = 0;
         first += 1; count -= 1;
         HIPCHK(c, hipGetLastError());
         if (count == 0) return SRUKF_OK;
@@ -1136,7 +1136,7 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
     // fp32 storage in "fused tail" mode: S and X are rounded as they are written; the float copies (srukf_get_state_f32) once per run
     if (storage_f32_like(c) && replay_fuse_mode(c)) quantize_state(c);
     c->async_pending = true;
-    c->phase = 0;
+    c->phase = 0; c->frame_updated = false;
     HIPCHK(c, hipGetLastError());
     return SRUKF_OK;
 }

@@ -15,7 +15,7 @@ void step_ck_join(srukf_ctx* c)
     // then — a flagged frame that is rewound, a state that is replaced — it is still reading S and X)
     if (c->ck3_inflight) { hipStreamWaitEvent(c->stream, c->ck_e3, 0); c->ck3_inflight = false; }
 }
-void step_state_replaced(srukf_ctx* c) { step_ck_join(c); c->step_uncommitted = false; c->step_fast = false; c->xr1_pending = false; step_invalidate(c); c->f32_stale = false; c->robot_cached = false; }
+void step_state_replaced(srukf_ctx* c) { step_ck_join(c); c->frame_updated = false; c->step_uncommitted = false; c->step_fast = false; c->xr1_pending = false; step_invalidate(c); c->f32_stale = false; c->robot_cached = false; }
 
 }  // namespace srukf_impl
 
@@ -385,7 +385,7 @@ int srukf_predict_motion(srukf_ctx* c, const double odo_prev[3], const double od
     if (!c || !odo_prev || !odo_cur) return SRUKF_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->step_uncommitted) { step_commit_motion(c); step_invalidate(c); }      // a frame that was predicted and never updated: its motion step stands (as on the other path)
-    c->step_fast = false; c->robot_cached = false; c->view_cached = false;
+    c->step_fast = false; c->robot_cached = false; c->view_cached = false; c->frame_updated = false;
     if (step_fast_eligible(c)) return step_predict_fast(c, odo_prev, odo_cur);
     step_invalidate(c);
     return step_predict_slow(c, odo_prev, odo_cur);
@@ -440,13 +440,19 @@ int srukf_update(srukf_ctx* c, const double* z, const int* matched, int reorder,
     const int N = c->d.N;
     int nm = 0; for (int k = 0; k < N; k++) nm += matched[k] ? 1 : 0;
     c->last_update_sequential = mode == SRUKF_UPDATE_SEQUENTIAL;
-    if (c->step_fast) {
-        if (reorder == SRUKF_NEEDNOT_REORDER && mode == SRUKF_UPDATE_BATCHED) { c->phase = 0; return step_update_fast(c, z, matched, nm); }
-        const int rc = step_rewind_to_slow(c); if (rc) return rc;       // predicted on the fast path, updated in a mode it does not have
-        c->step_fast = false;
+    c->frame_updated = false;
+    int rc;
+    if (c->step_fast && reorder == SRUKF_NEEDNOT_REORDER && mode == SRUKF_UPDATE_BATCHED) { c->phase = 0; rc = step_update_fast(c, z, matched, nm); }
+    else {
+        if (c->step_fast) {
+            rc = step_rewind_to_slow(c); if (rc) return rc;             // predicted on the fast path, updated in a mode it does not have
+            c->step_fast = false;
+        }
+        c->phase = 0;
+        rc = step_update_slow(c, z, matched, reorder, mode, nm);
     }
-    c->phase = 0;
-    return step_update_slow(c, z, matched, reorder, mode, nm);
+    c->frame_updated = rc == SRUKF_OK;                                   // (srukf_repredict_measurement: the posterior of this frame stands)
+    return rc;
 }
 
 }  // extern "C"

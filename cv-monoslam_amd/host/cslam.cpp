@@ -629,12 +629,81 @@ void CSLAM::KalmanUpdate()
     const int N = m_nMapFeatures;
     std::vector<double> z(2 * N, 0.0);
     std::vector<int> m(N, 0);
-    m_nMatches = 0;
-    for (int k = 0; k < N; k++)
-        if (map[k].isMatching) { m[k] = 1; z[2 * k] = map[k].matchLocation.x; z[2 * k + 1] = map[k].matchLocation.y; m_nMatches++; map[k].nMatchTimes++; }
+    m_nMatches = 0; m_nLowInliers = 0; m_nHighInliers = 0;
+    for (int k = 0; k < N; k++) {
+        map[k].inliner_L = map[k].inliner_H = false;
+        if (map[k].isMatching) { m[k] = 1; z[2 * k] = map[k].matchLocation.x; z[2 * k + 1] = map[k].matchLocation.y; m_nMatches++; }
+    }
     if (m_nMatches == 0) return;                                                                               // 2050-2051
-    const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;                      // 2083-2090
-    check(srukf_update(ctx_, z.data(), m.data(), reorder, m_updateMode));
+    if (!isUseRANSAC || m_nMatches < 2) {                                                                      // 2058-2095 (one match cannot out-vote itself)
+        for (int k = 0; k < N; k++) if (m[k]) map[k].nMatchTimes++;
+        const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;                  // 2083-2090
+        check(srukf_update(ctx_, z.data(), m.data(), reorder, m_updateMode));
+        return;
+    }
+    ransacZ_.swap(z); ransacM_.swap(m);                                                                        // 2097-2103
+    if (onePointRansacHypotheses() && updateLowInnovationInliers() && rescueHighInnovationInliers()) updateHighInnovationInliers();
+    // what the filter really used: the deletion policy (2443) and addFeatures' trigger (556) read these
+    for (int k = 0; k < N; k++) {
+        if (!ransacM_[k]) continue;
+        if (map[k].inliner_L || map[k].inliner_H) map[k].nMatchTimes++;
+        else map[k].isMatching = false;
+    }
+    m_nMatches = m_nLowInliers + m_nHighInliers;
+}
+
+// Civera's 1-point hypotheses, all of them (srukf_ransac_consensus): the low-innovation inliers are the consensus set of the best one
+bool CSLAM::onePointRansacHypotheses()
+{
+    const int N = m_nMapFeatures;
+    std::vector<int> inl(N, 0);
+    int best = -1;
+    if (!check(srukf_ransac_consensus(ctx_, ransacZ_.data(), ransacM_.data(), THRESHOLD_RANSAC, inl.data(), nullptr, nullptr, &best))) return false;
+    for (int k = 0; k < N; k++) { map[k].inliner_L = inl[k] != 0; m_nLowInliers += inl[k] ? 1 : 0; }
+    return true;
+}
+
+bool CSLAM::updateLowInnovationInliers()
+{
+    if (m_nLowInliers == 0) return true;
+    const int N = m_nMapFeatures;
+    std::vector<int> m(N, 0);
+    for (int k = 0; k < N; k++) m[k] = map[k].inliner_L ? 1 : 0;
+    const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;                      // as the plain branch, 2083-2090
+    return check(srukf_update(ctx_, ransacZ_.data(), m.data(), reorder, m_updateMode));
+}
+
+// a match outside the consensus set is rescued when, seen from the posterior of the first update, it is still visible and passes the chi-square gate
+// dataAssociation uses (1977): (z - h)^T (Si^T Si)^-1 (z - h) < CHI2INV_TABLE(0, 2)
+bool CSLAM::rescueHighInnovationInliers()
+{
+    const int N = m_nMapFeatures;
+    if (m_nLowInliers == 0 || m_nLowInliers == m_nMatches) return true;
+    std::vector<double> h(2 * N), Si(4 * N);
+    std::vector<int> vis(N);
+    if (!check(srukf_repredict_measurement(ctx_, h.data(), Si.data(), vis.data()))) return false;
+    const double CHI2INV_0_2 = 5.99146454710798;
+    for (int k = 0; k < N; k++) {
+        if (!ransacM_[k] || map[k].inliner_L || !vis[k]) continue;
+        const double s00 = Si[4 * k], s01 = Si[4 * k + 1], s11 = Si[4 * k + 3];
+        if (s00 == 0.0 || s11 == 0.0) continue;
+        // y = Si^-T (z - h) by forward substitution (Si is upper triangular: the library stores Si[2] = 0): the distance is |y|^2
+        const double v0 = ransacZ_[2 * k] - h[2 * k], v1 = ransacZ_[2 * k + 1] - h[2 * k + 1];
+        const double y0 = v0 / s00, y1 = (v1 - s01 * y0) / s11;
+        if (y0 * y0 + y1 * y1 < CHI2INV_0_2) { map[k].inliner_H = true; m_nHighInliers++; }
+    }
+    return true;
+}
+
+bool CSLAM::updateHighInnovationInliers()
+{
+    if (m_nHighInliers == 0) return true;
+    const int N = m_nMapFeatures;
+    std::vector<int> m(N, 0);
+    for (int k = 0; k < N; k++) m[k] = map[k].inliner_H ? 1 : 0;
+    // (a frame that follows a landmark addition keeps FLAG_4_NEED_REORDER for this update too, as every per-landmark update of such a frame does in the reference, 2083-2090)
+    const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;
+    return check(srukf_update(ctx_, ransacZ_.data(), m.data(), reorder, m_updateMode));
 }
 
 void CSLAM::refreshMirrors()

@@ -40,6 +40,8 @@ struct PointsMap {
     bool    isVisible = false;
     bool    isMatching = false;
     bool    isLoop = false;           // delayed deletion flag the OpenGL view colours by (OpenGlDisplay.cpp:497)      (SLAM.h:52)
+    bool    inliner_L = false;        // 1-point RANSAC: low-innovation inlier of this frame (SLAM.cpp:2599-2603)
+    bool    inliner_H = false;        // ... high-innovation inlier (rescued after the first update)
     int     nPredictTimes = 0;
     int     nMatchTimes = 0;
     Point2d predictLocation;
@@ -94,6 +96,16 @@ public:
     void predictMotion();                                      // SLAM.cpp:1343-1466 (numeric tail 1430-1465)
     void predictMeasurement();                                 // SLAM.cpp:1604-1608
     void KalmanUpdate();                                       // SLAM.cpp:2048-2104
+    // ---- 1-point RANSAC: the four steps KalmanUpdate's isUseRANSAC branch names (2097-2103) and the reference never wrote.  They run in this
+    //      order inside KalmanUpdate when isUseRANSAC is on and at least two landmarks matched; a match that is neither kind of inlier is dropped for the frame
+    //      (isMatching = false, nMatchTimes not incremented, m_nMatches = m_nLowInliers + m_nHighInliers)
+    bool onePointRansacHypotheses();                           // srukf_ransac_consensus: inliner_L, m_nLowInliers
+    bool updateLowInnovationInliers();                         // srukf_update with the low-innovation inliers
+    bool rescueHighInnovationInliers();                        // srukf_repredict_measurement + dataAssociation's chi-square gate (1977): inliner_H, m_nHighInliers
+    bool updateHighInnovationInliers();                        // srukf_update with the rescued matches (skipped when there are none)
+    bool   isUseRANSAC = false;                                // SLAM.cpp:185
+    double THRESHOLD_RANSAC = 8.0;                             // SLAM.cpp:186, SLAM.h:249: Euclidean pixel distance between measurement and prediction
+    int    m_nLowInliers = 0, m_nHighInliers = 0;              // SLAM.h:227-228
     void updateRobotInformation();                             // SLAM.cpp:2957-3000 (m_path only)
     void recordRobotInformation();                             // SLAM.cpp:3512-3562 (RobotPath.txt rows)
     bool loadOdometryData(const std::string& path);            // SLAM.cpp:363-496 ("%d : %*lf %lf %lf %lf")
@@ -234,6 +246,7 @@ private:
     bool firstDetect_ = true;            // the reference's `static bool flag` of detectAndfilteringFeatures (590, 653-656), per facade instance
     int runningCount_ = 0;               // the reference's running m_nMapFeatures of the pass schedule (758-766, 782)
     int addCalls_ = 0;                   // addFeaturesOnDevice calls (DetectPass::call)
+    std::vector<double> ransacZ_; std::vector<int> ransacM_;   // the frame's matches as KalmanUpdate gathered them (the RANSAC steps share them)
     std::vector<int> loopArchive_;       // archive indices of the loop points of the last detection pass, in the order reported
 };
 

@@ -10,6 +10,9 @@
 //   the addFeatures slot (SLAM.cpp:552-562), which "detects" the K key points uv_new; from then on landmark ID N + 1 + j is measured at
 //   z_new[frame][2j..].  Landmarks leave through the deletion policy of updateFeaturesInformation (2443-2460).  Every map change is
 //   printed as an `event` line.
+// ransac=<file>: KalmanUpdate runs 1-point RANSAC (isUseRANSAC); per frame the file receives int32 m_nLowInliers, int32 m_nHighInliers, int32 n (landmarks of
+//   the map in that frame), then per landmark int32 ID, uint8 inliner_L, uint8 inliner_H, and after the last frame int32 -1, int32 n, then per landmark int32 ID,
+//   int32 nMatchTimes.  Outliers are planted by writing displaced pixels into the scene file.
 // scene.bin: int32 N, int32 F, double a1..a4, double X0[n], double S0[n*n], double z[F][2N]
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +39,12 @@ int main(int argc, char** argv)
     if (argc > 5 && !strcmp(argv[5], "sequential")) SLAM.m_updateMode = SRUKF_UPDATE_SEQUENTIAL;
     int redirect = 0;
     for (int a = 5; a < argc; a++) if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9);
+    FILE* rf = nullptr;
+    for (int a = 5; a < argc; a++) if (!strncmp(argv[a], "ransac=", 7)) {
+        rf = fopen(argv[a] + 7, "wb");
+        if (!rf) { perror(argv[a] + 7); return 2; }
+        SLAM.isUseRANSAC = true;
+    }
     int K_new = 0, f_starve = -1, keep = 0;
     std::vector<double> uv_new, z_new;
     for (int a = 5; a < argc; a++) if (!strncmp(argv[a], "extra=", 6)) {
@@ -85,10 +94,21 @@ int main(int argc, char** argv)
         SLAM.SLAM();
         for (int q = 0; q < SLAM.m_nDeletes; q++) printf("event frame %d delete %d\n", fr, SLAM.m_deleteID[q]);
         if (!SLAM.lastError.empty()) { fprintf(stderr, "frame %d: %s\n", fr, SLAM.lastError.c_str()); return 1; }
+        if (rf) {
+            const int hd[3] = { SLAM.m_nLowInliers, SLAM.m_nHighInliers, SLAM.m_nMapFeatures };
+            fwrite(hd, 4, 3, rf);
+            for (const monoslam::PointsMap* mp = SLAM.map; NULL != mp; mp = mp->next) { const unsigned char b[2] = { mp->inliner_L, mp->inliner_H }; fwrite(&mp->ID, 4, 1, rf); fwrite(b, 1, 2, rf); }
+        }
         const int nn = SLAM.m_X_k.rows;
         for (int e = 0; e < 4; e++) traj[8 * fr + e] = SLAM.m_X_k.at(nn - 4 + e, 0);
         traj[8 * fr + 4] = SLAM.m_P_k.at(nn - 4, nn - 4); traj[8 * fr + 5] = SLAM.m_P_k.at(nn - 4, nn - 3);
         traj[8 * fr + 6] = SLAM.m_P_k.at(nn - 3, nn - 4); traj[8 * fr + 7] = SLAM.m_P_k.at(nn - 3, nn - 3);
+    }
+    if (rf) {
+        const int hd[2] = { -1, SLAM.m_nMapFeatures };
+        fwrite(hd, 4, 2, rf);
+        for (const monoslam::PointsMap* mp = SLAM.map; NULL != mp; mp = mp->next) { fwrite(&mp->ID, 4, 1, rf); fwrite(&mp->nMatchTimes, 4, 1, rf); }
+        fclose(rf);
     }
     FILE* o = fopen(argv[4], "wb");
     fwrite(traj.data(), 8, traj.size(), o);

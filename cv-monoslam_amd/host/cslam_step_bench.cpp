@@ -18,6 +18,7 @@
 //              integrateFeaturesInformation (joint initialisation on the device); the next frame's KalmanUpdate then runs FLAG_4_NEED_REORDER.  N stays where it
 //              was.  Every landmark is "found" at its predicted pixel + 0.5 px of noise (new landmarks have no entry in the scene's z).  Prints frames/s,
 //              the map changes and their wall time per operation, and how many frames ran on the step-wise fast path / on the other one
+//     ransac=1 (facade): CSLAM::isUseRANSAC on (KalmanUpdate runs the 1-point RANSAC steps: consensus, update, and the rescue when matches remain outside it)
 // scene.bin: int32 N, int32 F, double a1..a4, double X0[n], double S0[n*n], double z[F][2N]   (the file cslam_replay reads)
 // Prints ONE JSON object.
 #include <chrono>
@@ -36,7 +37,7 @@ int main(int argc, char** argv)
 {
     if (argc < 4) { fprintf(stderr, "usage: %s scene.bin odometry.txt mode=<capi|facade|assoc> [frames=K] [warmup=W] [hint=0|1]\n", argv[0]); return 2; }
     std::string mode = "capi";
-    int K = 200, W = 20, hint = 0, churn = 0;
+    int K = 200, W = 20, hint = 0, churn = 0, ransac = 0;
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -44,6 +45,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "warmup=", 7)) W = atoi(argv[a] + 7);
         else if (!strncmp(argv[a], "hint=", 5)) hint = atoi(argv[a] + 5);
         else if (!strncmp(argv[a], "churn=", 6)) churn = atoi(argv[a] + 6);
+        else if (!strncmp(argv[a], "ransac=", 7)) ransac = atoi(argv[a] + 7);
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } sets.emplace_back(std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))), atoi(q + 1)); }
     }
     for (auto& kv : sets) (void)srukf_debug_set(nullptr, kv.first.c_str(), kv.second);      // process-wide keys (e.g. set=timing:1) apply in every mode; per-filter keys: mode=capi, below
@@ -75,6 +77,7 @@ int main(int argc, char** argv)
     if (mode == "facade") {
         monoslam::CSLAM SLAM;
         SLAM.m_params.a1 = a4[0]; SLAM.m_params.a2 = a4[1]; SLAM.m_params.a3 = a4[2]; SLAM.m_params.a4 = a4[3];
+        SLAM.isUseRANSAC = ransac != 0;
         if (!SLAM.setMap(N, X0.data(), S0.data(), nullptr)) { fprintf(stderr, "%s\n", SLAM.lastError.c_str()); return 1; }
         SLAM.MIN_STEP_X = SLAM.MIN_STEP_Y = 0.0;
         if (!SLAM.loadOdometryData(argv[2])) { fprintf(stderr, "%s\n", SLAM.lastError.c_str()); return 1; }

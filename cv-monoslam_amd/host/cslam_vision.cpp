@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [ransac=<threshold>]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -9,6 +9,8 @@
 //   Adds, and only with it, a "reinsert" line per restart (the archive's IDs before the frame, the IDs put back, map and archive size behind the
 //   restart's addFeatures, the archived X6 and sr of what was put back) and an
 //   "ids" line per frame (ID and isLoop of every map node, state order).
+// ransac=<threshold>: KalmanUpdate runs 1-point RANSAC (CSLAM::isUseRANSAC, THRESHOLD_RANSAC = threshold in pixels; 8 is the reference's constant).  Adds, and
+//   only with it, a "ransac" line per frame (low- and high-innovation inliers).
 // warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
 // Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
 #include <cstdio>
@@ -20,7 +22,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [ransac=<threshold>]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -28,9 +30,10 @@ int main(int argc, char** argv)
     std::vector<unsigned char> frames((size_t)W * H * F);
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
-    int redirect = 0; bool warmup = false, loops = false;
+    int redirect = 0; bool warmup = false, loops = false, ransac = false; double ransacThr = 8.0;
     for (int a = 3; a < argc; a++)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
+        else if (!strncmp(argv[a], "ransac=", 7)) { ransac = true; ransacThr = atof(argv[a] + 7); }
     if (warmup) {
         monoslam::CSLAM w;
         w.m_params.image_w = W; w.m_params.image_h = H; w.MIN_STEP_X = w.MIN_STEP_Y = 0.0;
@@ -47,6 +50,7 @@ int main(int argc, char** argv)
     if (redirect > 0) SLAM.m_odoTheta.at(2, redirect) = 1;
     SLAM.logDetectPasses = true;
     SLAM.reinsertLoopPoints = loops;
+    if (ransac) { SLAM.isUseRANSAC = true; SLAM.THRESHOLD_RANSAC = ransacThr; }
     const unsigned char* cur = nullptr;
     SLAM.dataAssociation = [&](monoslam::CSLAM& s) { s.dataAssociationOnDevice(cur); };     // loadPictures + dataAssociation (SLAM.cpp:95-97)
     const int steps = SLAM.m_odoCounter - 1 - (redirect > 0 ? 1 : 0);
@@ -82,6 +86,7 @@ int main(int argc, char** argv)
         }
         printf("frame %d n_map %d map_size %d archived %d matches %d loops %d\n", fr, SLAM.m_nMapFeatures, (int)SLAM.mapStore.size(),
                (int)SLAM.m_featuresAllInfo.size(), SLAM.m_nMatches, SLAM.m_loopPointCounter);
+        if (ransac) printf("ransac low %d high %d\n", SLAM.m_nLowInliers, SLAM.m_nHighInliers);
         printf("init"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %.17g %.17g", m->initPixel.x, m->initPixel.y); printf("\n");
         if (loops) { printf("ids"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %d %d", m->ID, m->isLoop ? 1 : 0); printf("\n"); }
         const int n = SLAM.m_X_k.rows;

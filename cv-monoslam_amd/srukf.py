@@ -26,6 +26,7 @@ EXPORTS = [
     "srukf_update", "srukf_set_new_landmarks", "srukf_add_landmarks", "srukf_delete_landmark", "srukf_set_storage", "srukf_set_exclusive", "srukf_set_rank_aware", "srukf_null_directions", "srukf_run_frames_batch", "srukf_prepare_frames", "srukf_debug_poke_state", "srukf_get_state_f32", "srukf_set_landmark_appearance", "srukf_associate", "srukf_get_match_patch", "srukf_stage_sequence", "srukf_run_frames_async", "srukf_run_frames", "srukf_synchronize", "srukf_set_profiling",
     "srukf_clamp_info", "srukf_debug_set", "srukf_debug_get", "srukf_debug_copy", "srukf_debug_upload", "srukf_debug_split_replay", "srukf_debug_gmw_stamps", "srukf_debug_starve_workers", "srukf_debug_allow_mixed", "srukf_profile_count", "srukf_profile_get", "srukf_profile_reset", "srukf_dims", "srukf_gmw_host",
     "srukf_project_host", "srukf_detect_features", "srukf_capture_appearance", "srukf_get_landmark_record", "srukf_insert_landmarks",
+    "srukf_ransac_consensus", "srukf_repredict_measurement",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -126,6 +127,9 @@ def load_library(path=None):
     if hasattr(L, "srukf_insert_landmarks"):           # (idem: loop points)
         L.srukf_get_landmark_record.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _bp, _dp, _dp, _dp, _ip]
         L.srukf_insert_landmarks.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _bp, _dp, _dp, _dp]
+    if hasattr(L, "srukf_ransac_consensus"):           # (idem: 1-point RANSAC)
+        L.srukf_ransac_consensus.argtypes = [C.c_void_p, _dp, _ip, C.c_double, _ip, _ip, _dp, _ip]
+        L.srukf_repredict_measurement.argtypes = [C.c_void_p, _dp, _dp, _ip]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -264,6 +268,21 @@ class Filter:
         z, m = _c(z), _c(matched, np.int32)
         assert z.shape == (2 * self.N,) and m.shape == (self.N,)
         self._chk(self._lib.srukf_update(self._h, _d(z), _i(m), reorder, mode))
+
+    def ransac_consensus(self, z, matched, threshold=8.0):
+        """1-point RANSAC consensus over ALL single-match hypotheses (srukf_ransac_consensus), between predict_measurement and update.
+        Returns (inlier[N], votes[N], dist[N], best); best = -1 when no matched landmark is visible.  The filter is not changed."""
+        z, m = _c(z), _c(matched, np.int32)
+        assert z.shape == (2 * self.N,) and m.shape == (self.N,)
+        inl, votes, dist, best = np.zeros(self.N, dtype=np.int32), np.zeros(self.N, dtype=np.int32), np.zeros(self.N), C.c_int(-1)
+        self._chk(self._lib.srukf_ransac_consensus(self._h, _d(z), _i(m), float(threshold), _i(inl), _i(votes), _d(dist), C.byref(best)))
+        return inl, votes, dist, best.value
+
+    def repredict_measurement(self):
+        """predict_measurement once more from the posterior of the update just made (srukf_repredict_measurement); a second update may follow."""
+        h, Si, vis = np.empty(2 * self.N), np.empty((self.N, 2, 2)), np.empty(self.N, dtype=np.int32)
+        self._chk(self._lib.srukf_repredict_measurement(self._h, _d(h), _d(Si), _i(vis)))
+        return h, Si, vis
 
     def set_new_landmarks(self, K_new):
         """m_nFilters: the last K_new landmarks of the map were just added (NEED_REORDER updates use it)."""

@@ -160,6 +160,26 @@ int  srukf_predict_measurement(srukf_ctx* ctx, double* h, double* Si, int* visib
  * (SRUKF_ERR_SEQUENCE otherwise). */
 int  srukf_update(srukf_ctx* ctx, const double* z, const int* matched, int reorder, int mode);
 
+/* ---- 1-point RANSAC (KalmanUpdate's isUseRANSAC branch, SLAM.cpp:2097-2103: onePointRansacHypotheses, updateLowInnovationInliers, rescueHighInnovationInliers,
+ * updateHighInnovationInliers are named there and never written; isUseRANSAC / THRESHOLD_RANSAC 185-186, m_nLowInliers / m_nHighInliers SLAM.h:227-228) ----
+ * srukf_ransac_consensus: between srukf_predict_measurement and srukf_update (SRUKF_ERR_SEQUENCE otherwise).  A = { k : matched[k] != 0 and visible[k] }.  Every
+ *   i in A is a hypothesis — all of them, where the paper draws a random subset: the result is deterministic —: x(i) = X + K_i (z_i - h_i) with Pxy_i as
+ *   calculateOneFeatureCrossCovariance forms it (2020-2038) around the predicted state and K_i = Pxy_i sii sii^T, sii = Si_i^-1 (2077-2079); the mean only.  For
+ *   every j in A, d_ij = |z_j - h(x(i))_j|_2 with landmark j of x(i) projected from the robot rows of x(i) (passSigmaThroughMesaurementFunction 1615-1690, zero pixel
+ *   noise); the pair is an inlier when both coordinates of that pixel are non-zero (predictMeasurement's visibility test, 1727) and d_ij < threshold (THRESHOLD_RANSAC
+ *   8.0: the Euclidean pixel distance of the comment at SLAM.h:249).  votes[i] = inliers of hypothesis i (0 outside A); *best = the i with the most votes, the lowest
+ *   index among equals, -1 when A is empty; inlier[j] = 1 for the inliers of *best; dist[j] = d_best,j for j in A, 0 elsewhere.  Outputs are host pointers, any may be
+ *   NULL.  The call changes nothing of the filter: the srukf_update that follows returns bit for bit what it returns without it.
+ *   A frame predicted on the step-wise fast path (srukf_predict_motion_next announced) keeps its motion step beside the state; there the consensus forms X, h, Si and
+ *   visible once more, with the other path's launch sequence on a copy of the state before the frame, and uses THOSE: they equal what srukf_predict_measurement
+ *   returned to rounding (1e-8 px; in SRUKF_STORAGE_F32 the copy is the rounded state, the predicted one is not rounded again), so a landmark whose predicted pixel
+ *   lies within that of the image border could belong to A for one and not for the other.
+ * srukf_repredict_measurement: after a srukf_update, in the same frame (SRUKF_ERR_SEQUENCE otherwise): predictMeasurement (1604-1608) once more from the posterior
+ *   (X, S), no motion step; outputs as srukf_predict_measurement.  A second srukf_update may follow (the rescue of high-innovation inliers).  What the first update
+ *   prepared for the next frame (srukf_predict_motion_next) is dropped and formed again by the next frame. */
+int  srukf_ransac_consensus(srukf_ctx* ctx, const double* z, const int* matched, double threshold, int* inlier, int* votes, double* dist, int* best);
+int  srukf_repredict_measurement(srukf_ctx* ctx, double* h, double* Si, int* visible);
+
 /* m_nFilters (SLAM.cpp:826-830, 2126-2131): the number of landmarks added by the last augmentation, i.e. the LAST
  * K_new landmarks of the map.  Defines the permutation of getPermutationMatrix (SLAM.cpp:1303-1334) and the rank
  * n - 3*K_new used by SRUKF_NEED_REORDER updates.  0 clears it. */
