@@ -55,7 +55,7 @@ namespace srukf_impl {
 
 const char* const kclass_name[KC_COUNT] = { "k_motion", "k_project", "k_meas_stats", "k_pxy", "k_gain", "k_syrk",
                                              "k_gmw_step64", "k_gmw_persist", "k_gmw_check", "k_gmw_col", "k_rank_expand", "k_project_motion", "k_project_table", "k_pxy2",
-                                             "misc", "k_det_response", "k_det_cand", "k_det_rank", "k_det_select", "k_capture_patch" };
+                                             "misc", "k_det_response", "k_det_cand", "k_det_rank", "k_det_select", "k_capture_patch", "k_lm_ellipsoid" };
 
 void gmw_plan_destroy(GmwPlan& g, hipStream_t st)
 {
@@ -387,7 +387,7 @@ int srukf_destroy(srukf_ctx* c)
     if (c->graphN) hipGraphDestroy(c->graphN);
     void* bufs[] = { c->X, c->S, c->G, c->Gbak, c->Wf, c->sigR, c->Cmat, c->Z, c->DZ, c->Ut, c->h /* + Si, vis */, c->PxyR, c->D,
                      c->zcur /* + mcur */, c->odocur, c->small, c->theta, c->fs, c->odo_seq, c->z_seq, c->m_seq, c->pan[0], c->pan[1], c->mpart, c->dxp, c->syrk_tiles, c->pxy_tiles, c->syrk_head_tiles,
-                     c->perm, c->iperm, c->Sdis, c->ckS, c->ckX, c->ckS2, c->ckX2, c->odo_step, c->export_cnt, c->red_perm, c->red_iperm, c->gdiag, c->red_syrk_tiles, c->syrk_head_tiles_b, c->red_head0_tiles, c->split_fold_list, c->shadowA, c->Utp, c->P1, c->pxy2_tiles, c->nskip, c->slabW, c->slabL, c->gsW, c->gsL, c->S32, c->X32, c->U32, c->mx_part, c->mx_tasks, c->mx_tiles, c->fold_sync, c->dxk, c->A32, c->mxr_part, c->mxr_tasks, c->mxr_tiles, c->mxr_f64_tiles, c->mxr_xt, c->app_patch, c->app_tmpl, c->d_image, c->appR, c->appT, c->appPx, c->corr, c->has_app };
+                     c->perm, c->iperm, c->Sdis, c->ckS, c->ckX, c->ckS2, c->ckX2, c->odo_step, c->export_cnt, c->red_perm, c->red_iperm, c->gdiag, c->red_syrk_tiles, c->syrk_head_tiles_b, c->red_head0_tiles, c->split_fold_list, c->shadowA, c->Utp, c->P1, c->pxy2_tiles, c->nskip, c->slabW, c->slabL, c->gsW, c->gsL, c->S32, c->X32, c->U32, c->mx_part, c->mx_tasks, c->mx_tiles, c->fold_sync, c->dxk, c->A32, c->mxr_part, c->mxr_tasks, c->mxr_tiles, c->mxr_f64_tiles, c->mxr_xt, c->app_patch, c->app_tmpl, c->d_image, c->appR, c->appT, c->appPx, c->corr, c->has_app, c->disp };
     for (void* b : bufs) if (b) srukf_dfree_on(b, c->stream);
     det_scratch_free(c->det, c->stream);
     ransac_scratch_free(c->ransac, c->stream);
@@ -681,6 +681,68 @@ int srukf_get_frame_view(srukf_ctx* c, double* X, double* xyz, double* cov, doub
     if (pose4) memcpy(pose4, hr + 16, sizeof(double) * 4);
     if (X) memcpy(X, hs + 12 * (size_t)N + 32, sizeof(double) * n);
     return SRUKF_OK;
+}
+
+}  // extern "C"
+
+// The display part of updateFeaturesInformation (SLAM.cpp:2566-2575 per landmark) on the committed state: k_landmarks_cartesian, k_lm_ellipsoid on the covariances it
+// left on the device, ONE copy of xyz | cov | axis | sigma | robot view | rot and one synchronisation (the state vector, when asked for, rides as a second copy in
+// front of the same synchronisation, as in srukf_get_frame_view).  It never reads or changes the view an update exported (view_cached / view_auto / view_hits are
+// srukf_get_frame_view's): its two launches form the same values from the same X and S, and its device buffer is the context's own (srukf_ctx::disp), so the next
+// frame's pre-issued first launch (srukf_predict_motion_next) is not disturbed.
+static int display_fetch(srukf_ctx* c, double* X, double* xyz, double* cov, double* axis, double* sigma, int* rot, double* pose4, double* P4)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->d.N; const int n = c->d.n;
+    const bool lm = N > 0 && (xyz || cov || axis || sigma || rot), ell = N > 0 && (axis || sigma || rot);
+    const size_t o_axis = 12 * N, o_sigma = 16 * N, o_robot = 19 * N, o_rot = 19 * N + 20, total = o_rot + (N + 1) / 2;
+    if (!c->disp && srukf_dmalloc(&c->disp, sizeof(double) * total) != hipSuccess) { (void)hipGetLastError(); c->disp = nullptr; c->err = "display: out of device memory"; return SRUKF_ERR_NOMEM; }
+    step_commit_motion(c);
+    double* dv = c->disp;
+    if (lm) srukf_launch_landmarks_cartesian(c->stream, c->d, c->X, c->S, dv, dv + 3 * N);
+    if (ell) {
+        ProfScope ps(c, KC_LM_ELLIPSOID, 0, 8.0 * 16 * N + 4.0 * N);
+        launch_lm_ellipsoid(c->stream, (int)N, c->p.epsilon, dv + 3 * N, dv + o_axis, dv + o_sigma, (int*)(dv + o_rot));
+    }
+    const bool robot = (pose4 || P4) && !c->robot_cached;
+    if (robot) srukf_launch_block_cov(c->stream, c->d, c->S, n - 4, 4, dv + o_robot, c->X);
+    double* hs = c->hstage;
+    const size_t o_X = (total + 63) / 64 * 64;
+    if (lm) HIPCHK(c, hipMemcpyAsync(hs, dv, sizeof(double) * (ell ? total : robot ? o_robot + 20 : o_axis), hipMemcpyDeviceToHost, c->stream));
+    else if (robot) HIPCHK(c, hipMemcpyAsync(hs + o_robot, dv + o_robot, sizeof(double) * 20, hipMemcpyDeviceToHost, c->stream));
+    if (X) HIPCHK(c, hipMemcpyAsync(hs + o_X, c->X, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    if (N > 0) {
+        if (xyz) memcpy(xyz, hs, sizeof(double) * 3 * N);
+        if (cov) memcpy(cov, hs + 3 * N, sizeof(double) * 9 * N);
+        if (axis) memcpy(axis, hs + o_axis, sizeof(double) * 4 * N);
+        if (sigma) memcpy(sigma, hs + o_sigma, sizeof(double) * 3 * N);
+        if (rot) memcpy(rot, hs + o_rot, sizeof(int) * N);
+    }
+    const double* hr = c->robot_cached ? (const double*)((const char*)c->hfs + sizeof(FrameScalars)) : hs + o_robot;
+    if (P4) memcpy(P4, hr, sizeof(double) * 16);
+    if (pose4) memcpy(pose4, hr + 16, sizeof(double) * 4);
+    if (X) memcpy(X, hs + o_X, sizeof(double) * n);
+    return SRUKF_OK;
+}
+
+extern "C" {
+
+// getFeatureCartesianInformation + get3DdisplayInformation (SLAM.cpp:2721-2806) for all landmarks: xyz[3N], cov[9N], axis[4N] (r, x, y, z), sigma[3N], rot[N]
+// (plane rotations applied; -1: the iteration limit ran out).  Any may be NULL.
+int srukf_get_landmarks_display(srukf_ctx* c, double* xyz, double* cov, double* axis, double* sigma, int* rot)
+{
+    if (!c || (!xyz && !cov && !axis && !sigma && !rot)) return SRUKF_ERR_BAD_ARG;
+    if (c->d.N == 0) return SRUKF_OK;
+    return display_fetch(c, nullptr, xyz, cov, axis, sigma, rot, nullptr, nullptr);
+}
+
+// srukf_get_frame_view plus the ellipsoids: what updateFeaturesInformation shows of the posterior, in one round trip
+int srukf_get_frame_view_display(srukf_ctx* c, double* X, double* xyz, double* cov, double* axis, double* sigma, double pose4[4], double P4[16])
+{
+    if (!c || (!X && !xyz && !cov && !axis && !sigma && !pose4 && !P4)) return SRUKF_ERR_BAD_ARG;
+    return display_fetch(c, X, xyz, cov, axis, sigma, nullptr, pose4, P4);
 }
 
 int srukf_get_covariance(srukf_ctx* c, double* P)

@@ -117,7 +117,7 @@ int srukf_app_tmpl_stride(void);
 
 enum KClass { KC_MOTION = 0, KC_PROJECT, KC_STATS, KC_PXY, KC_GAIN, KC_SYRK, KC_GMW_TRAIL, KC_GMW_PERSIST, KC_GMW_CHECK,
               KC_GMW_COL, KC_RANK_EXPAND, KC_PROJECT_MOTION, KC_PROJECT_TABLE, KC_PXY2, KC_MISC,
-              KC_DET_RESPONSE, KC_DET_CAND, KC_DET_RANK, KC_DET_SELECT, KC_CAPTURE, KC_COUNT };
+              KC_DET_RESPONSE, KC_DET_CAND, KC_DET_RANK, KC_DET_SELECT, KC_CAPTURE, KC_LM_ELLIPSOID, KC_COUNT };
 struct ProfEvent { hipEvent_t a, b; int kc; };
 
 // ---- persistent GMW launch (k_gmw_persist): per-matrix-size resources --------------------------------
@@ -172,6 +172,9 @@ struct srukf_ctx {
                                            // frame): handed over at map changes with the buffer (adopt_context), dropped by srukf_reset
     DetScratch det;                        // srukf_detect_features (handed over at map changes too)
     RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
+    // srukf_get_landmarks_display / srukf_get_frame_view_display: xyz (3N) | cov (9N) | axis (4N) | sigma (3N) | P4, pose (20) | rot (N ints).  A buffer of its own, sized
+    // by the context's N and allocated by the first call (not G: the next frame's pre-issued first launch may be in flight behind the update); it stays with its context
+    double* disp = nullptr;
     int storage = SRUKF_STORAGE_F64;       // SRUKF_STORAGE_F32 / _F32_MIXED: X32 / S32 hold the inter-frame state
     float *S32 = nullptr, *X32 = nullptr;
     // SRUKF_STORAGE_F32_MIXED: S^T S - U U^T on the fp32 matrix pipe (srukf_mixed.hip)
@@ -390,6 +393,9 @@ void launch_capture_patch(hipStream_t st, const unsigned char* img, int W, int f
 
 // ---- 1-point RANSAC (srukf_ransac.hip) ----
 void ransac_scratch_free(RansacScratch& s, hipStream_t st);
+
+// ---- display ellipsoids (srukf_display.hip) ----
+void launch_lm_ellipsoid(hipStream_t st, int N, double eps, const double* cov, double* axis, double* sigma, int* rot);
 
 // ---- loop points (srukf_loop.hip) ----
 #define SRUKF_LM_RECORD_DOUBLES 113                              // k_lm_record's staging block: X6 | S66 | R | t | px | has_app | 448 patch bytes

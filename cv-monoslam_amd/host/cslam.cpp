@@ -310,22 +310,30 @@ bool CSLAM::refreshFeaturesDisplay(bool withMirrors)
 {
     const int N = m_nMapFeatures;
     if (!ctx_ || N == 0) return true;
-    std::vector<double> xyz(3 * (size_t)N), cov(9 * (size_t)N);
+    std::vector<double> xyz(3 * (size_t)N), cov(9 * (size_t)N), axis, sigma;
+    const bool dev = ellipsoidsOnDevice;
+    if (dev) { axis.resize(4 * (size_t)N); sigma.resize(3 * (size_t)N); }
     if (withMirrors && !fullCovariance) {
         double pose[4], P4[16];
-        if (!check(srukf_get_frame_view(ctx_, m_X_k.data.data(), xyz.data(), cov.data(), pose, P4))) return false;
+        if (!check(dev ? srukf_get_frame_view_display(ctx_, m_X_k.data.data(), xyz.data(), cov.data(), axis.data(), sigma.data(), pose, P4)
+                       : srukf_get_frame_view(ctx_, m_X_k.data.data(), xyz.data(), cov.data(), pose, P4))) return false;
         const int n = m_X_k.rows;
         for (int a = 0; a < 4; a++) for (int b = 0; b < 4; b++) m_P_k.at(n - 4 + a, n - 4 + b) = P4[4 * a + b];
         mirrorsFresh_ = true;
     } else {
         if (withMirrors && !check(srukf_get_state(ctx_, m_X_k.data.data(), nullptr))) return false;
-        if (!check(srukf_get_landmarks_cartesian(ctx_, xyz.data(), cov.data()))) return false;
+        if (!check(dev ? srukf_get_landmarks_display(ctx_, xyz.data(), cov.data(), axis.data(), sigma.data(), nullptr)
+                       : srukf_get_landmarks_cartesian(ctx_, xyz.data(), cov.data()))) return false;
     }
     Mat c; c.create(3, 3);
     for (int k = 0; k < N; k++) {
         map[k].xyz.x = xyz[3 * k]; map[k].xyz.y = xyz[3 * k + 1]; map[k].xyz.z = xyz[3 * k + 2];
         for (int e = 0; e < 9; e++) { map[k].cov[e] = cov[9 * (size_t)k + e]; c.data[e] = map[k].cov[e]; }
-        get3DdisplayInformation(map[k].axis, map[k].sigma, c);                                                 // 2575
+        if (dev) {                                                                                             // k_lm_ellipsoid: the same arithmetic on the device
+            const double* q = &axis[4 * (size_t)k]; const double* sg = &sigma[3 * (size_t)k];
+            map[k].axis.r = q[0]; map[k].axis.x = q[1]; map[k].axis.y = q[2]; map[k].axis.z = q[3];
+            map[k].sigma.x = sg[0]; map[k].sigma.y = sg[1]; map[k].sigma.z = sg[2];
+        } else get3DdisplayInformation(map[k].axis, map[k].sigma, c);                                          // 2575
     }
     return true;
 }

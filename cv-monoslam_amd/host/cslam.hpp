@@ -221,6 +221,10 @@ public:
     // addFeatures puts the loop points of its last pass back into the filter (srukf_insert_landmarks, SLAM.cpp:948-1015).
     // false (default): loop points are only reported
     bool   reinsertLoopPoints = false;
+    // true: refreshFeaturesDisplay takes axis / sigma of every map node from the device with the frame view (srukf_get_frame_view_display /
+    // srukf_get_landmarks_display: k_lm_ellipsoid runs this class's Jacobi and quaternion arithmetic operation for operation, same bits)
+    // instead of calling get3DdisplayInformation per landmark.  false (default): the host computes them
+    bool   ellipsoidsOnDevice = false;
     bool   isRecordRobotInfo = false;
     std::string m_recordRobotDir = "RobotPath.txt";
     double MIN_STEP_X = 0.01, MIN_STEP_Y = 0.01, MIN_STEP_THETA = 45;   // SLAM.cpp:45-47

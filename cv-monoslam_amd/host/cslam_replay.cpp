@@ -13,7 +13,11 @@
 // ransac=<file>: KalmanUpdate runs 1-point RANSAC (isUseRANSAC); per frame the file receives int32 m_nLowInliers, int32 m_nHighInliers, int32 n (landmarks of
 //   the map in that frame), then per landmark int32 ID, uint8 inliner_L, uint8 inliner_H, and after the last frame int32 -1, int32 n, then per landmark int32 ID,
 //   int32 nMatchTimes.  Outliers are planted by writing displaced pixels into the scene file.
+// ellipsoids=1: CSLAM::ellipsoidsOnDevice (axis / sigma of the map nodes come from the device with the frame view instead of the host's Jacobi iteration)
+// display=<file>: after the last frame, one text line per map node: ID, then xyz (3), cov (9), axis (r, x, y, z), sigma (3) printed with %a (every bit of
+//   every value; a NaN prints as "nan" whatever its sign bit, which the host's and the device's sqrt of a negative number set differently)
 // scene.bin: int32 N, int32 F, double a1..a4, double X0[n], double S0[n*n], double z[F][2N]
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,6 +48,11 @@ int main(int argc, char** argv)
         rf = fopen(argv[a] + 7, "wb");
         if (!rf) { perror(argv[a] + 7); return 2; }
         SLAM.isUseRANSAC = true;
+    }
+    const char* display_fn = nullptr;
+    for (int a = 5; a < argc; a++) {
+        if (!strncmp(argv[a], "ellipsoids=", 11)) SLAM.ellipsoidsOnDevice = atoi(argv[a] + 11) != 0;
+        else if (!strncmp(argv[a], "display=", 8)) display_fn = argv[a] + 8;
     }
     int K_new = 0, f_starve = -1, keep = 0;
     std::vector<double> uv_new, z_new;
@@ -126,6 +135,19 @@ int main(int argc, char** argv)
             fwrite(rec, 8, 19, ff);
         }
         fclose(ff);
+    }
+    if (display_fn) {
+        FILE* df = fopen(display_fn, "w");
+        if (!df) { perror(display_fn); return 2; }
+        for (const monoslam::PointsMap* map_p = SLAM.map; NULL != map_p; map_p = map_p->next) {
+            const monoslam::PointsMap& pm = *map_p;
+            const double rec[19] = { pm.xyz.x, pm.xyz.y, pm.xyz.z, pm.cov[0], pm.cov[1], pm.cov[2], pm.cov[3], pm.cov[4], pm.cov[5], pm.cov[6], pm.cov[7], pm.cov[8],
+                                     pm.axis.r, pm.axis.x, pm.axis.y, pm.axis.z, pm.sigma.x, pm.sigma.y, pm.sigma.z };
+            fprintf(df, "%d", pm.ID);
+            for (double v : rec) { if (std::isnan(v)) fprintf(df, " nan"); else fprintf(df, " %a", v); }
+            fprintf(df, "\n");
+        }
+        fclose(df);
     }
     if (redirect > 0) printf("redirection: archived %d  stored map %d  show map %d\n", (int)SLAM.m_featuresAllInfo.size(), SLAM.m_nStoreMap, SLAM.m_nShowMap);
     printf("frames %d  landmarks %d  predicts %d  matches %d  total %.3f s\n", F, SLAM.m_nMapFeatures, SLAM.m_nPredicts, SLAM.m_nMatches, SLAM.m_totalTime);

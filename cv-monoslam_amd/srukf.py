@@ -27,6 +27,7 @@ EXPORTS = [
     "srukf_clamp_info", "srukf_debug_set", "srukf_debug_get", "srukf_debug_copy", "srukf_debug_upload", "srukf_debug_split_replay", "srukf_debug_gmw_stamps", "srukf_debug_starve_workers", "srukf_debug_allow_mixed", "srukf_profile_count", "srukf_profile_get", "srukf_profile_reset", "srukf_dims", "srukf_gmw_host",
     "srukf_project_host", "srukf_detect_features", "srukf_capture_appearance", "srukf_get_landmark_record", "srukf_insert_landmarks",
     "srukf_ransac_consensus", "srukf_repredict_measurement",
+    "srukf_get_landmarks_display", "srukf_get_frame_view_display",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -110,6 +111,8 @@ def load_library(path=None):
     L.srukf_get_covariance.argtypes = [C.c_void_p, _dp]
     L.srukf_get_landmarks_cartesian.argtypes = [C.c_void_p, _dp, _dp]
     L.srukf_get_frame_view.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
+    L.srukf_get_landmarks_display.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]
+    L.srukf_get_frame_view_display.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
     L.srukf_predict_motion.argtypes = [C.c_void_p, _dp, _dp]
     L.srukf_predict_motion_next.argtypes = [C.c_void_p, _dp, _dp]
     L.srukf_predict_measurement.argtypes = [C.c_void_p, _dp, _dp, _ip]
@@ -305,6 +308,21 @@ class Filter:
         X, xyz, cov, pose, P4 = np.zeros(self.n), np.zeros((self.N, 3)), np.zeros((self.N, 3, 3)), np.zeros(4), np.zeros((4, 4))
         self._chk(self._lib.srukf_get_frame_view(self._h, _d(X), _d(xyz), _d(cov), _d(pose), _d(P4)))
         return X, xyz, cov, pose, P4
+
+    def get_landmarks_display(self):
+        """(xyz[N,3], cov[N,3,3], axis[N,4], sigma[N,3], rot[N]): get_landmarks_cartesian plus the display ellipsoid of every covariance (quaternion
+        (r, x, y, z) of the Jacobi eigenvectors, unsorted 1-sigma semi-axes, plane rotations applied or -1) from the device (srukf_get_landmarks_display)."""
+        xyz, cov, axis, sigma = np.zeros((self.N, 3)), np.zeros((self.N, 3, 3)), np.zeros((self.N, 4)), np.zeros((self.N, 3))
+        rot = np.zeros(self.N, dtype=np.int32)
+        self._chk(self._lib.srukf_get_landmarks_display(self._h, _d(xyz), _d(cov), _d(axis), _d(sigma), _i(rot)))
+        return xyz, cov, axis, sigma, rot
+
+    def get_frame_view_display(self):
+        """(X, xyz[N,3], cov[N,3,3], axis[N,4], sigma[N,3], pose[4], P4[4,4]): get_frame_view plus the ellipsoids in one round trip (srukf_get_frame_view_display)."""
+        X, xyz, cov, pose, P4 = np.zeros(self.n), np.zeros((self.N, 3)), np.zeros((self.N, 3, 3)), np.zeros(4), np.zeros((4, 4))
+        axis, sigma = np.zeros((self.N, 4)), np.zeros((self.N, 3))
+        self._chk(self._lib.srukf_get_frame_view_display(self._h, _d(X), _d(xyz), _d(cov), _d(axis), _d(sigma), _d(pose), _d(P4)))
+        return X, xyz, cov, axis, sigma, pose, P4
 
     def set_landmark_appearance(self, k, patch, R, t, px):
         """PointsMap::initPatch (21x21 uint8), initRotation (3x3), initTrans (3), initPixel (2) of landmark k."""

@@ -130,6 +130,17 @@ int  srukf_get_landmarks_cartesian(srukf_ctx* ctx, double* xyz, double* cov);
  * views nobody fetched end that).  Same values either way. */
 int  srukf_get_frame_view(srukf_ctx* ctx, double* X, double* xyz, double* cov, double pose4[4], double P4[16]);
 
+/* getFeatureCartesianInformation + get3DdisplayInformation (SLAM.cpp:2721-2806) for all landmarks: besides xyz / cov as above, the display ellipsoid of each
+ * covariance — axis[4N], the unit quaternion (r, x, y, z) of the eigenvector matrix (matrix2Quaternion, 2903-2948), and sigma[3N], the square roots of the
+ * eigenvalues in the positions the Jacobi rotations left them (calculateEigenvaluesAndEigenvectors, 2815-2892: not sorted; a negative eigenvalue gives NaN) —
+ * and rot[N], the number of plane rotations applied (-1: the limit of 30 * 9 + 1 passes ran out).  The device runs the host facade's arithmetic operation for
+ * operation: same bits.  Any pointer may be NULL (all of them: SRUKF_ERR_BAD_ARG).  One device round trip. */
+int  srukf_get_landmarks_display(srukf_ctx* ctx, double* xyz, double* cov, double* axis, double* sigma, int* rot);
+/* srukf_get_frame_view plus axis[4N], sigma[3N]: updateFeaturesInformation's display part in one round trip.  Always formed from the committed state by two
+ * launches of its own (same values as srukf_get_frame_view, whose exported view and accounting it neither uses nor changes). */
+int  srukf_get_frame_view_display(srukf_ctx* ctx, double* X, double* xyz, double* cov, double* axis, double* sigma,
+                                  double pose4[4], double P4[16]);
+
 /* Full covariance m_P_k = S^T S (SLAM.cpp:2404), n*n row-major, for hosts that want it. */
 int  srukf_get_covariance(srukf_ctx* ctx, double* P);
 
