@@ -6,6 +6,7 @@
 //   srukf_batch.hip   batched replay (srukf_run_frames_batch)
 //   srukf_map.hip     map changes (srukf_add_landmarks / srukf_delete_landmark / srukf_insert_landmarks) and data association
 //   srukf_ransac.hip  1-point RANSAC: the consensus over all single-match hypotheses, the measurement prediction from the posterior
+//   srukf_overlay.hip colour-frame intake (srukf_set_frame_bgr) and the 2-D feature overlay (srukf_render_overlay)
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
 #pragma once
@@ -117,7 +118,7 @@ int srukf_app_tmpl_stride(void);
 
 enum KClass { KC_MOTION = 0, KC_PROJECT, KC_STATS, KC_PXY, KC_GAIN, KC_SYRK, KC_GMW_TRAIL, KC_GMW_PERSIST, KC_GMW_CHECK,
               KC_GMW_COL, KC_RANK_EXPAND, KC_PROJECT_MOTION, KC_PROJECT_TABLE, KC_PXY2, KC_MISC,
-              KC_DET_RESPONSE, KC_DET_CAND, KC_DET_RANK, KC_DET_SELECT, KC_CAPTURE, KC_LM_ELLIPSOID, KC_COUNT };
+              KC_DET_RESPONSE, KC_DET_CAND, KC_DET_RANK, KC_DET_SELECT, KC_CAPTURE, KC_LM_ELLIPSOID, KC_BGR2GRAY, KC_OVERLAY, KC_COUNT };
 struct ProfEvent { hipEvent_t a, b; int kc; };
 
 // ---- persistent GMW launch (k_gmw_persist): per-matrix-size resources --------------------------------
@@ -170,6 +171,12 @@ struct srukf_ctx {
     int* has_app = nullptr;
     bool frame_valid = false;              // d_image holds the caller's last frame (srukf_associate / srukf_detect_features / srukf_capture_appearance with a
                                            // frame): handed over at map changes with the buffer (adopt_context), dropped by srukf_reset
+    // srukf_set_frame_bgr / srukf_render_overlay (srukf_overlay.hip): the held colour frame (W x H x 3, B G R) and the overlay's output, both padded to whole groups of
+    // four pixels, allocated on first use and handed over at map changes like d_image; bgr_valid: d_bgr is the colour of the held gray frame (a later call that brings
+    // a gray frame, srukf_reset and adopt_context's retired side clear it)
+    unsigned char *d_bgr = nullptr, *d_ovl = nullptr; bool bgr_valid = false;
+    // ... and what the overlay is drawn from, sized by the context's N (stays with its context): h | Si | z (8N doubles) | matched (N ints), the per-landmark records
+    double* ov_in = nullptr; void* ov_rec = nullptr;
     DetScratch det;                        // srukf_detect_features (handed over at map changes too)
     RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
     // srukf_get_landmarks_display / srukf_get_frame_view_display: xyz (3N) | cov (9N) | axis (4N) | sigma (3N) | P4, pose (20) | rot (N ints).  A buffer of its own, sized
@@ -396,6 +403,13 @@ void ransac_scratch_free(RansacScratch& s, hipStream_t st);
 
 // ---- display ellipsoids (srukf_display.hip) ----
 void launch_lm_ellipsoid(hipStream_t st, int N, double eps, const double* cov, double* axis, double* sigma, int* rot);
+
+// ---- colour-frame intake, 2-D overlay (srukf_overlay.hip) ----
+size_t overlay_rec_bytes(int N);
+size_t overlay_bgr_bytes(int npix);
+void launch_bgr2gray(hipStream_t st, int npix, const unsigned char* bgr, unsigned char* gray);
+void launch_overlay(hipStream_t st, int W, int H, int N, const double* h, const double* Si, const double* z, const int* matched, void* rec,
+                    const unsigned char* bgr /* NULL: gray three times */, const unsigned char* gray, unsigned char* out);
 
 // ---- loop points (srukf_loop.hip) ----
 #define SRUKF_LM_RECORD_DOUBLES 113                              // k_lm_record's staging block: X6 | S66 | R | t | px | has_app | 448 patch bytes

@@ -367,7 +367,7 @@ int take_frame(srukf_ctx* c, const unsigned char* gray)
     }
     int rc = ensure_image(c); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_image, gray, (size_t)c->p.image_w * c->p.image_h, hipMemcpyHostToDevice, c->stream));
-    c->frame_valid = true;
+    c->frame_valid = true; c->bgr_valid = false;                 // (a gray frame of the caller's: the held colour frame is no longer its colour)
     return SRUKF_OK;
 }
 

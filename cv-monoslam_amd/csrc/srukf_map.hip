@@ -88,7 +88,8 @@ void adopt_context(srukf_ctx* c, srukf_ctx* c2)
     c2->profiling = false; c2->pev.clear();
     // the frame the handle holds and the detection scratch stay with the handle (same image size in every context of a handle)
     std::swap(c->d_image, c2->d_image); std::swap(c->frame_valid, c2->frame_valid); std::swap(c->det, c2->det);
-    c2->frame_valid = false;
+    std::swap(c->d_bgr, c2->d_bgr); std::swap(c->d_ovl, c2->d_ovl); std::swap(c->bgr_valid, c2->bgr_valid);      // (the colour frame and the overlay's output likewise)
+    c2->frame_valid = false; c2->bgr_valid = false;
     ctx_retire(c, c2);                                           // (not destroyed: revived when the map has this size again — ctx_obtain)
     c->phase = 0; c->frame_updated = false;
     if (shared != c->gmw_shared) set_shared(c, shared, tenants);
@@ -160,9 +161,9 @@ int srukf_get_match_patch(srukf_ctx* c, int k, unsigned char* out)
 // wrapPatch + dataAssociation (SLAM.cpp:1803-2009) between srukf_predict_measurement and srukf_update: gray = the
 // image_h x image_w frame (row-major uchar).  Out (host, any may be NULL): z[2N] = matchLocation, matched[N] =
 // isMatching, corr[N] = best normalised cross correlation.  Landmarks without an appearance record never match.
-int srukf_associate(srukf_ctx* c, const unsigned char* gray, double* z, int* matched, double* corr)
+// (gray == NULL: the frame the handle holds, no upload — srukf_associate_held, which has checked that there is one)
+static int associate_frame(srukf_ctx* c, const unsigned char* gray, double* z, int* matched, double* corr)
 {
-    if (!c || !gray) return SRUKF_ERR_BAD_ARG;
     if (c->phase < 2) { c->err = "associate before predict_measurement"; return SRUKF_ERR_SEQUENCE; }
     const int N = c->d.N;
     if (N == 0) return SRUKF_OK;
@@ -178,14 +179,15 @@ int srukf_associate(srukf_ctx* c, const unsigned char* gray, double* z, int* mat
     srukf_launch_warp_patch(c->stream, c->d, c->p, c->X, dxyz, c->h, c->appR, c->appT, c->appPx, c->app_patch, c->has_app, c->app_tmpl);
     double* hs = c->hstage;
     const size_t img_off = (zm + (size_t)N + 7) & ~(size_t)7;           // (doubles) behind the results' place in the staging buffer
-    if ((img_off + (img + 7) / 8) * sizeof(double) <= c->hstage_bytes) {
+    if (!gray) {
+    } else if ((img_off + (img + 7) / 8) * sizeof(double) <= c->hstage_bytes) {
         unsigned char* himg = (unsigned char*)(hs + img_off);
         memcpy(himg, gray, img);
         HIPCHK(c, hipMemcpyAsync(c->d_image, himg, img, hipMemcpyHostToDevice, c->stream));
     } else {
         HIPCHK(c, hipMemcpyAsync(c->d_image, gray, img, hipMemcpyHostToDevice, c->stream));
     }
-    c->frame_valid = true;
+    if (gray) { c->frame_valid = true; c->bgr_valid = false; }
     srukf_launch_associate(c->stream, c->d, c->p, c->d_image, c->h, c->Si, c->vis, c->has_app, c->app_tmpl, c->zcur, c->mcur, c->corr);
     // z | matched | corr written into the pinned buffer by ONE short launch, flag behind them: three small device-to-host copies were three blit kernels with their gaps
     const unsigned long long seq = ++c->step_seq;
@@ -196,6 +198,21 @@ int srukf_associate(srukf_ctx* c, const unsigned char* gray, double* z, int* mat
     if (matched) memcpy(matched, hs + mp, sizeof(int) * N);
     if (corr) memcpy(corr, hs + zm, sizeof(double) * N);
     return SRUKF_OK;
+}
+
+int srukf_associate(srukf_ctx* c, const unsigned char* gray, double* z, int* matched, double* corr)
+{
+    if (!c || !gray) return SRUKF_ERR_BAD_ARG;
+    return associate_frame(c, gray, z, matched, corr);
+}
+
+// srukf_associate on the frame the handle holds (loadPictures ran before: srukf_set_frame_bgr, or any call that brought a gray frame): no upload
+int srukf_associate_held(srukf_ctx* c, double* z, int* matched, double* corr)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    if (c->phase < 2) { c->err = "associate before predict_measurement"; return SRUKF_ERR_SEQUENCE; }
+    if (!c->frame_valid || !c->d_image) { c->err = "associate_held: no frame held"; return SRUKF_ERR_SEQUENCE; }
+    return associate_frame(c, nullptr, z, matched, corr);
 }
 
 // integrateFeaturesInformation, numeric part (SLAM.cpp:826-871): K new landmarks at the distorted pixels uv[K][2] are

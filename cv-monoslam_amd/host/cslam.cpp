@@ -145,6 +145,48 @@ bool CSLAM::dataAssociationOnDevice(const unsigned char* gray)
     return true;
 }
 
+// dataAssociationOnDevice's bookkeeping (1989-2000) on the frame the handle holds (loadPictures ran before): no upload
+bool CSLAM::dataAssociationOnDeviceHeld()
+{
+    const int N = m_nMapFeatures;
+    if (!ctx_ || N == 0) return true;
+    std::vector<double> z(2 * (size_t)N); std::vector<int> m(N);
+    if (!check(srukf_associate_held(ctx_, z.data(), m.data(), nullptr))) return false;
+    m_nMatches = 0;
+    for (int k = 0; k < N; k++) {
+        map[k].isMatching = m[k] != 0;
+        if (m[k]) { map[k].matchLocation.x = z[2 * k]; map[k].matchLocation.y = z[2 * k + 1]; m_nMatches++; }
+    }
+    return true;
+}
+
+// ---- colour-frame intake and the 2-D feature overlay ----------------------------------------------------------------------------------------
+// loadPictures (529-543): the colour frame goes to the device, comes back as the gray frame the reference's cvCvtColor(CV_RGB2GRAY) makes of B, G, R data
+bool CSLAM::loadPictures(const unsigned char* bgr)
+{
+    if (!ctx_ || !bgr) { lastError = "loadPictures: no context or no frame"; return false; }
+    m_grayStore.resize((size_t)m_params.image_w * (size_t)m_params.image_h);
+    if (!check(srukf_set_frame_bgr(ctx_, bgr, m_grayStore.data()))) return false;
+    m_gryImage = m_grayStore.data();
+    return true;
+}
+
+// display2DFeatureModel (3009-3051): m_srcImage = the held frame with every matched landmark's predicted cross, matched cross and chi-square ellipse
+bool CSLAM::display2DFeatureModel()
+{
+    if (!ctx_) { lastError = "display2DFeatureModel: no context"; return false; }
+    const int N = m_nMapFeatures;
+    std::vector<double> h(2 * (size_t)N), Si(4 * (size_t)N), z(2 * (size_t)N); std::vector<int> m(N);
+    for (int k = 0; k < N; k++) {                                                                               // 3024-3031
+        h[2 * k] = map[k].predictLocation.x; h[2 * k + 1] = map[k].predictLocation.y;
+        memcpy(&Si[4 * k], map[k].Si, sizeof map[k].Si);
+        z[2 * k] = map[k].matchLocation.x; z[2 * k + 1] = map[k].matchLocation.y;
+        m[k] = map[k].isMatching ? 1 : 0;
+    }
+    m_srcImage.resize(3 * (size_t)m_params.image_w * (size_t)m_params.image_h);
+    return check(srukf_render_overlay(ctx_, h.data(), Si.data(), z.data(), m.data(), m_srcImage.data()));
+}
+
 // ---- finding new landmarks on the device ------------------------------------------------------------------------------------------------
 // SLAM.cpp:574-768.  The GFTT budget (590-599), the filter switches (653, 660, 614) and the map / archive inputs go to srukf_detect_features; the
 // key points it accepts become m_keyPoints, the archived features it met again m_loopPointID; counter = both (719, 748), and the running map

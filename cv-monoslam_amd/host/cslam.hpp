@@ -131,6 +131,20 @@ public:
     // isMatching / matchLocation / nMatchTimes of every map entry and m_nMatches.  Install it as the association step:
     //   SLAM.dataAssociation = [&](monoslam::CSLAM& s) { s.dataAssociationOnDevice(grabGrayFrame()); };
     bool dataAssociationOnDevice(const unsigned char* gray);
+    // the same on the frame the handle holds (after loadPictures): srukf_associate_held, no upload
+    bool dataAssociationOnDeviceHeld();
+
+    // ---- colour-frame intake and the 2-D feature overlay.  SLAM() calls none of them by itself ------------------------------------
+    // loadPictures (SLAM.cpp:529-543): bgr = the image_h x image_w x 3 colour frame (B, G, R interleaved, as cvLoadImage / cvQueryFrame deliver it) goes to the
+    // device (srukf_set_frame_bgr); m_gryImage then points at m_grayStore, its conversion as the reference converts it (CV_RGB2GRAY on B, G, R data: the blue
+    // byte gets 0.299).  Hosts that set m_gryImage themselves need not call it
+    bool loadPictures(const unsigned char* bgr);
+    std::vector<unsigned char> m_grayStore;
+    // display2DFeatureModel + draw2DEllipse (3009-3083): m_srcImage (image_h x image_w x 3, B, G, R) = the held frame with the predicted cross (blue), the matched
+    // cross and the chi-square ellipse of Si^T Si (red) of every map node with isMatching, from predictLocation / Si / matchLocation (srukf_render_overlay; the ID
+    // text is not drawn)
+    bool display2DFeatureModel();
+    std::vector<unsigned char> m_srcImage;
 
     // ---- display accessors (what OpenGlDisplay.cpp:449-583 reads per paint) ------------------------------
     // updateFeaturesInformation (SLAM.cpp:2397-2621), as SLAM() calls it after KalmanUpdate: the deletion policy (2443-2460:

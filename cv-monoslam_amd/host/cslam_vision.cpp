@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [ransac=<threshold>]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [ransac=<threshold>] [colour=1] [overlay=<file>]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -11,6 +11,10 @@
 //   "ids" line per frame (ID and isLoop of every map node, state order).
 // ransac=<threshold>: KalmanUpdate runs 1-point RANSAC (CSLAM::isUseRANSAC, THRESHOLD_RANSAC = threshold in pixels; 8 is the reference's constant).  Adds, and
 //   only with it, a "ransac" line per frame (low- and high-innovation inliers).
+// colour=1: every gray frame is fed as a B = G = R colour frame through CSLAM::loadPictures (srukf_set_frame_bgr) and associated on the held frame
+//   (dataAssociationOnDeviceHeld).  The conversion keeps such a frame byte for byte (the weights sum to 2^14), so the output equals the default run's.
+// overlay=<file>: after the last frame, CSLAM::display2DFeatureModel's bytes (H x W x 3, B G R) go to <file> and the rows they were drawn from to <file>.in:
+//   per map node "h.x h.y Si00 Si01 Si10 Si11 z.x z.y matched" (%a).  Nothing else changes.
 // warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
 // Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
 #include <cstdio>
@@ -22,7 +26,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [ransac=<threshold>]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [ransac=<threshold>] [colour=1] [overlay=<file>]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -30,10 +34,12 @@ int main(int argc, char** argv)
     std::vector<unsigned char> frames((size_t)W * H * F);
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
-    int redirect = 0; bool warmup = false, loops = false, ransac = false; double ransacThr = 8.0;
+    int redirect = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay;
     for (int a = 3; a < argc; a++)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
         else if (!strncmp(argv[a], "ransac=", 7)) { ransac = true; ransacThr = atof(argv[a] + 7); }
+        else if (!strncmp(argv[a], "colour=", 7)) colour = atoi(argv[a] + 7) != 0;
+        else if (!strncmp(argv[a], "overlay=", 8)) overlay = argv[a] + 8;
     if (warmup) {
         monoslam::CSLAM w;
         w.m_params.image_w = W; w.m_params.image_h = H; w.MIN_STEP_X = w.MIN_STEP_Y = 0.0;
@@ -52,7 +58,12 @@ int main(int argc, char** argv)
     SLAM.reinsertLoopPoints = loops;
     if (ransac) { SLAM.isUseRANSAC = true; SLAM.THRESHOLD_RANSAC = ransacThr; }
     const unsigned char* cur = nullptr;
-    SLAM.dataAssociation = [&](monoslam::CSLAM& s) { s.dataAssociationOnDevice(cur); };     // loadPictures + dataAssociation (SLAM.cpp:95-97)
+    std::vector<unsigned char> bgr(colour ? (size_t)3 * W * H : 0);
+    SLAM.dataAssociation = [&](monoslam::CSLAM& s) {                                         // loadPictures + dataAssociation (SLAM.cpp:95-97)
+        if (!colour) { s.dataAssociationOnDevice(cur); return; }
+        for (size_t q = 0; q < (size_t)W * H; q++) bgr[3 * q] = bgr[3 * q + 1] = bgr[3 * q + 2] = cur[q];
+        if (s.loadPictures(bgr.data())) s.dataAssociationOnDeviceHeld();
+    };
     const int steps = SLAM.m_odoCounter - 1 - (redirect > 0 ? 1 : 0);
     double addWall = -1.0;
     for (int fr = 0; fr < steps; fr++) {
@@ -91,6 +102,18 @@ int main(int argc, char** argv)
         if (loops) { printf("ids"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %d %d", m->ID, m->isLoop ? 1 : 0); printf("\n"); }
         const int n = SLAM.m_X_k.rows;
         printf("pose %.17g %.17g %.17g %.17g\n", SLAM.m_X_k.at(n - 4, 0), SLAM.m_X_k.at(n - 3, 0), SLAM.m_X_k.at(n - 2, 0), SLAM.m_X_k.at(n - 1, 0));
+    }
+    if (!overlay.empty()) {
+        if (!SLAM.display2DFeatureModel()) { fprintf(stderr, "overlay: %s\n", SLAM.lastError.c_str()); return 1; }
+        FILE* fo = fopen(overlay.c_str(), "wb");
+        if (!fo || fwrite(SLAM.m_srcImage.data(), 1, SLAM.m_srcImage.size(), fo) != SLAM.m_srcImage.size()) { perror(overlay.c_str()); return 1; }
+        fclose(fo);
+        fo = fopen((overlay + ".in").c_str(), "w");
+        if (!fo) { perror((overlay + ".in").c_str()); return 1; }
+        for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next)
+            fprintf(fo, "%a %a %a %a %a %a %a %a %d\n", m->predictLocation.x, m->predictLocation.y, m->Si[0], m->Si[1], m->Si[2], m->Si[3], m->matchLocation.x,
+                    m->matchLocation.y, m->isMatching ? 1 : 0);
+        fclose(fo);
     }
     printf("add_features_frame1_ms %.3f  frame_time_ms %.3f\n", addWall * 1e3, SLAM.m_frameTime * 1e3);
     return 0;

@@ -28,6 +28,7 @@ EXPORTS = [
     "srukf_project_host", "srukf_detect_features", "srukf_capture_appearance", "srukf_get_landmark_record", "srukf_insert_landmarks",
     "srukf_ransac_consensus", "srukf_repredict_measurement",
     "srukf_get_landmarks_display", "srukf_get_frame_view_display",
+    "srukf_set_frame_bgr", "srukf_associate_held", "srukf_render_overlay",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -133,6 +134,10 @@ def load_library(path=None):
     if hasattr(L, "srukf_ransac_consensus"):           # (idem: 1-point RANSAC)
         L.srukf_ransac_consensus.argtypes = [C.c_void_p, _dp, _ip, C.c_double, _ip, _ip, _dp, _ip]
         L.srukf_repredict_measurement.argtypes = [C.c_void_p, _dp, _dp, _ip]
+    if hasattr(L, "srukf_render_overlay"):             # (idem: colour-frame intake, 2-D overlay)
+        L.srukf_set_frame_bgr.argtypes = [C.c_void_p, _bp, _bp]
+        L.srukf_associate_held.argtypes = [C.c_void_p, _dp, _ip, _dp]
+        L.srukf_render_overlay.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, _bp]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -336,6 +341,33 @@ class Filter:
         z, m, cr = np.zeros(2 * self.N), np.zeros(self.N, dtype=np.int32), np.zeros(self.N)
         self._chk(self._lib.srukf_associate(self._h, gray.ctypes.data_as(C.POINTER(C.c_ubyte)), _d(z), _i(m), _d(cr)))
         return z, m, cr
+
+    def set_frame_bgr(self, bgr, want_gray=True):
+        """loadPictures on the device (srukf_set_frame_bgr): bgr[image_h, image_w, 3] uint8 (B, G, R) becomes the held colour frame, its conversion
+        (the reference's: the blue byte gets 0.299) the held gray frame.  Returns the gray frame [image_h, image_w] (None with want_gray=False)."""
+        h, w = int(self.params.image_h), int(self.params.image_w)
+        bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
+        assert bgr.shape == (h, w, 3)
+        gray = np.zeros((h, w), dtype=np.uint8) if want_gray else None
+        self._chk(self._lib.srukf_set_frame_bgr(self._h, bgr.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                gray.ctypes.data_as(C.POINTER(C.c_ubyte)) if want_gray else None))
+        return gray
+
+    def associate_held(self):
+        """associate() on the frame the filter holds (srukf_associate_held): no upload.  Returns (z[2N], matched[N], corr[N])."""
+        z, m, cr = np.zeros(2 * self.N), np.zeros(self.N, dtype=np.int32), np.zeros(self.N)
+        self._chk(self._lib.srukf_associate_held(self._h, _d(z), _i(m), _d(cr)))
+        return z, m, cr
+
+    def render_overlay(self, h, Si, z, matched):
+        """display2DFeatureModel on the device (srukf_render_overlay): the held frame with the predicted cross, the matched cross and the chi-square
+        ellipse of every matched landmark, from the caller's h[2N], Si[4N], z[2N], matched[N].  Returns bgr[image_h, image_w, 3] uint8."""
+        N = self.N
+        h, Si, z = _c(h).reshape(2 * N), _c(Si).reshape(4 * N), _c(z).reshape(2 * N)
+        m = np.ascontiguousarray(matched, dtype=np.int32).reshape(N)
+        out = np.zeros((int(self.params.image_h), int(self.params.image_w), 3), dtype=np.uint8)
+        self._chk(self._lib.srukf_render_overlay(self._h, _d(h), _d(Si), _d(z), _i(m), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out
 
     def get_match_patch(self, k):
         out = np.zeros((17, 17), dtype=np.uint8)

@@ -265,6 +265,29 @@ int  srukf_detect_features(srukf_ctx* ctx, const unsigned char* gray, const sruk
                            int* loop_out, int loop_cap, int* n_loop);
 int  srukf_capture_appearance(srukf_ctx* ctx, int first, int K, const double* uv, const unsigned char* gray);
 
+/* ---- colour-frame intake and the 2-D feature overlay (loadPictures 529-543; display2DFeatureModel 3009-3051, draw2DEllipse 3067-3083) ----
+ * srukf_set_frame_bgr: loadPictures (529-543).  bgr = the image_h x image_w x 3 colour frame, interleaved B, G, R bytes, row-major, no row padding (what
+ *   cvLoadImage / cvQueryFrame deliver).  It is uploaded, converted into the held gray frame as the reference converts it — cvCvtColor(CV_RGB2GRAY) on B, G, R
+ *   data, so with c0, c1, c2 a pixel's bytes in memory order gray = (4899 c0 + 9617 c1 + 1868 c2 + 8192) >> 14 (OpenCV 2.4's fixed-point weights: the BLUE
+ *   byte gets red's 0.299) — and kept on the handle beside it.  gray_out (NULL ok) receives the image_h x image_w gray bytes.  The held frame is then what
+ *   srukf_associate_held, srukf_detect_features(gray = NULL) and srukf_capture_appearance(gray = NULL) read.  The colour frame survives map changes as the gray
+ *   one does; srukf_reset drops both; a later call that passes a gray frame replaces the gray one and invalidates the colour one.
+ * srukf_associate_held: srukf_associate (wrapPatch + dataAssociation, 1803-2009) on the held frame, no upload.  SRUKF_ERR_SEQUENCE before
+ *   srukf_predict_measurement or when no frame is held.
+ * srukf_render_overlay: display2DFeatureModel (3009-3051) with draw2DEllipse (3067-3083) into out_bgr[image_h x image_w x 3]: the held colour frame (the held
+ *   gray byte three times when no colour frame is held) with, for every landmark k of the context's N with matched[k] != 0 and finite h, z of magnitude below
+ *   2^30, in state order, later over earlier: the predicted cross at cvRound(h) in B, G, R = (255, 0, 0) (3035-3036), the matched cross at cvRound(z) in
+ *   (0, 0, 255) (3040-3041), the chi-square ellipse of Pi = Si^T Si (3031) around cvRound(z) in (0, 0, 255) (3042).  Our raster rules (OpenCV's line and
+ *   ellipse polygons are not reproducible outside it): a cross is |dx| <= 10 && |dy| <= 1 or |dy| <= 10 && |dx| <= 1; the ellipse has the integer semi-axes
+ *   a = max(1, (int)(sqrt(l0) sqrt(5.99146454710798))), b likewise from l1 (3076-3079), l0 >= l1 the eigenvalues of Pi in closed form, (c, s) the unit
+ *   eigenvector of l0, and with p = c dx + s dy, q = c dy - s dx a pixel is painted when (p/(a+1))^2 + (q/(b+1))^2 <= 1 and not (a >= 2 && b >= 2 &&
+ *   (p/(a-1))^2 + (q/(b-1))^2 <= 1).  No ellipse when l0 is not finite or >= 1e12 (eigen fails, 3073).  The ID text (cvPutText, 3034, 3039) is not drawn.
+ *   h[2N], Si[4N] (row-major 2 x 2), z[2N], matched[N] are the caller's (host; NULL allowed when N = 0): the call reads and writes nothing of the filter, is
+ *   valid in any phase and changes no later result.  SRUKF_ERR_SEQUENCE when no frame is held. */
+int  srukf_set_frame_bgr(srukf_ctx* ctx, const unsigned char* bgr, unsigned char* gray_out);
+int  srukf_associate_held(srukf_ctx* ctx, double* z, int* matched, double* corr);
+int  srukf_render_overlay(srukf_ctx* ctx, const double* h, const double* Si, const double* z, const int* matched, unsigned char* out_bgr);
+
 /* ---- loop points: archived landmarks put back into the filter (the redirection archive, SLAM.cpp:1357-1378, 2516-2532; integrateFeaturesInformation's
  * isLoop branch, 948-1015) ----
  * srukf_get_landmark_record: what an archived landmark takes along, in one device round trip.  X6 = rows 6k .. 6k+5 of X; S66 = the upper Cholesky
