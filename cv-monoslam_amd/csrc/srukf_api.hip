@@ -55,7 +55,8 @@ namespace srukf_impl {
 
 const char* const kclass_name[KC_COUNT] = { "k_motion", "k_project", "k_meas_stats", "k_pxy", "k_gain", "k_syrk",
                                              "k_gmw_step64", "k_gmw_persist", "k_gmw_check", "k_gmw_col", "k_rank_expand", "k_project_motion", "k_project_table", "k_pxy2",
-                                             "misc", "k_det_response", "k_det_cand", "k_det_rank", "k_det_select", "k_capture_patch", "k_lm_ellipsoid", "k_bgr2gray", "k_overlay" };
+                                             "misc", "k_det_response", "k_det_cand", "k_det_rank", "k_det_select", "k_capture_patch", "k_lm_ellipsoid", "k_bgr2gray", "k_overlay",
+                                             "k_archive_predict", "k_archive_warp", "k_archive_search" };
 
 void gmw_plan_destroy(GmwPlan& g, hipStream_t st)
 {
@@ -391,6 +392,7 @@ int srukf_destroy(srukf_ctx* c)
     for (void* b : bufs) if (b) srukf_dfree_on(b, c->stream);
     det_scratch_free(c->det, c->stream);
     ransac_scratch_free(c->ransac, c->stream);
+    archive_free(c->archive, c->stream);
     gmw_plan_destroy(c->gplan, c->stream);
     gmw_plan_destroy(c->gplan_red, c->stream);
     if (c->side) { hipStreamSynchronize(c->side); hipStreamDestroy(c->side); hipEventDestroy(c->ev_fork); hipEventDestroy(c->ev_join); }
@@ -504,6 +506,7 @@ int srukf_reset(srukf_ctx* c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->phase = 0; c->async_pending = false;
     c->frame_valid = false; c->bgr_valid = false;                // (the held frame goes with the state, gray and colour)
+    archive_free(c->archive, c->stream);                         // (and the archive: srukf_archive_set)
     if (c->red_r) { c->red_r = 0; drop_graphs(c); }            // the state is the robot block only: nothing to reduce until a state arrives
     return SRUKF_OK;
 }

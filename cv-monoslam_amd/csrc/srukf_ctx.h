@@ -8,6 +8,7 @@
 //   srukf_ransac.hip  1-point RANSAC: the consensus over all single-match hypotheses, the measurement prediction from the posterior
 //   srukf_overlay.hip colour-frame intake (srukf_set_frame_bgr) and the 2-D feature overlay (srukf_render_overlay)
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
+//   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search)
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -118,7 +119,8 @@ int srukf_app_tmpl_stride(void);
 
 enum KClass { KC_MOTION = 0, KC_PROJECT, KC_STATS, KC_PXY, KC_GAIN, KC_SYRK, KC_GMW_TRAIL, KC_GMW_PERSIST, KC_GMW_CHECK,
               KC_GMW_COL, KC_RANK_EXPAND, KC_PROJECT_MOTION, KC_PROJECT_TABLE, KC_PXY2, KC_MISC,
-              KC_DET_RESPONSE, KC_DET_CAND, KC_DET_RANK, KC_DET_SELECT, KC_CAPTURE, KC_LM_ELLIPSOID, KC_BGR2GRAY, KC_OVERLAY, KC_COUNT };
+              KC_DET_RESPONSE, KC_DET_CAND, KC_DET_RANK, KC_DET_SELECT, KC_CAPTURE, KC_LM_ELLIPSOID, KC_BGR2GRAY, KC_OVERLAY,
+              KC_ARCHIVE_PREDICT, KC_ARCHIVE_WARP, KC_ARCHIVE_SEARCH, KC_COUNT };
 struct ProfEvent { hipEvent_t a, b; int kc; };
 
 // ---- persistent GMW launch (k_gmw_persist): per-matrix-size resources --------------------------------
@@ -140,6 +142,15 @@ struct RansacScratch {
     double *Ut = nullptr, *D = nullptr, *zin = nullptr, *res = nullptr, *X = nullptr, *S = nullptr, *odo = nullptr;
     double *sigR = nullptr, *Cm = nullptr, *Z = nullptr, *DZ = nullptr, *h = nullptr, *PxyR = nullptr, *mpart = nullptr;
     unsigned char* F = nullptr; int* votes = nullptr; FrameScalars* fs = nullptr;
+};
+
+// the archive searched by appearance (srukf_archive.hip): L records in the layouts of srukf_insert_landmarks (patch / tmpl with the strides of the map's appearance
+// records), rob = pose | P4 of the search in hand, out = h | Si | z | corr | xyz | visible | matched, hst = the same pinned, then pose | P4.  On the handle: it
+// survives map changes as the held frame does (adopt_context); srukf_reset and srukf_destroy drop it
+struct ArchiveState {
+    int L = 0;
+    double *X6 = nullptr, *S66 = nullptr, *R = nullptr, *t = nullptr, *px = nullptr, *rob = nullptr, *out = nullptr, *hst = nullptr;
+    unsigned char *patch = nullptr, *tmpl = nullptr;
 };
 
 struct srukf_ctx {
@@ -179,6 +190,7 @@ struct srukf_ctx {
     double* ov_in = nullptr; void* ov_rec = nullptr;
     DetScratch det;                        // srukf_detect_features (handed over at map changes too)
     RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
+    ArchiveState archive;                  // srukf_archive_set / srukf_archive_search (handed over at map changes)
     // srukf_get_landmarks_display / srukf_get_frame_view_display: xyz (3N) | cov (9N) | axis (4N) | sigma (3N) | P4, pose (20) | rot (N ints).  A buffer of its own, sized
     // by the context's N and allocated by the first call (not G: the next frame's pre-issued first launch may be in flight behind the update); it stays with its context
     double* disp = nullptr;
@@ -400,6 +412,9 @@ void launch_capture_patch(hipStream_t st, const unsigned char* img, int W, int f
 
 // ---- 1-point RANSAC (srukf_ransac.hip) ----
 void ransac_scratch_free(RansacScratch& s, hipStream_t st);
+
+// ---- archive search (srukf_archive.hip) ----
+void archive_free(ArchiveState& a, hipStream_t st);
 
 // ---- display ellipsoids (srukf_display.hip) ----
 void launch_lm_ellipsoid(hipStream_t st, int N, double eps, const double* cov, double* axis, double* sigma, int* rot);

@@ -89,6 +89,7 @@ void adopt_context(srukf_ctx* c, srukf_ctx* c2)
     // the frame the handle holds and the detection scratch stay with the handle (same image size in every context of a handle)
     std::swap(c->d_image, c2->d_image); std::swap(c->frame_valid, c2->frame_valid); std::swap(c->det, c2->det);
     std::swap(c->d_bgr, c2->d_bgr); std::swap(c->d_ovl, c2->d_ovl); std::swap(c->bgr_valid, c2->bgr_valid);      // (the colour frame and the overlay's output likewise)
+    std::swap(c->archive, c2->archive);                          // (the archive srukf_archive_search reads: the handle's too)
     c2->frame_valid = false; c2->bgr_valid = false;
     ctx_retire(c, c2);                                           // (not destroyed: revived when the map has this size again — ctx_obtain)
     c->phase = 0; c->frame_updated = false;

@@ -53,6 +53,8 @@ void CSLAM::initializeParameters()
     m_blockSize = 3; m_qualityLevel = 0.1; m_nInitialRaws = 8; m_nProcessRaws = 8; m_minDist = 15.0; m_minDist2 = m_minDist * m_minDist;   // 175-181
     m_keyPoints.clear(); m_loopPointID.clear(); m_loopPointCounter = 0; m_nFilters = 0; firstDetect_ = true; runningCount_ = 0;
     mapStore.clear(); relinkMap();
+    m_nArchiveMatches = m_nArchiveRejected = m_nArchiveReacquired = 0;
+    archiveMirror_.clear(); archiveVerdict_.clear(); reacquire_.clear(); reacquired_.clear(); frameHeld_ = false; m_archiveLog.clear();
 }
 
 // `map` = head of the singly linked list over mapStore (state order), NULL when the map is empty (SLAM.h:69, 154)
@@ -137,6 +139,7 @@ bool CSLAM::dataAssociationOnDevice(const unsigned char* gray)
     if (!ctx_ || N == 0) return true;
     std::vector<double> z(2 * (size_t)N); std::vector<int> m(N);
     if (!check(srukf_associate(ctx_, gray, z.data(), m.data(), nullptr))) return false;
+    frameHeld_ = true;
     m_nMatches = 0;
     for (int k = 0; k < N; k++) {                                                                               // 1989-2000
         map[k].isMatching = m[k] != 0;
@@ -167,6 +170,7 @@ bool CSLAM::loadPictures(const unsigned char* bgr)
     if (!ctx_ || !bgr) { lastError = "loadPictures: no context or no frame"; return false; }
     m_grayStore.resize((size_t)m_params.image_w * (size_t)m_params.image_h);
     if (!check(srukf_set_frame_bgr(ctx_, bgr, m_grayStore.data()))) return false;
+    frameHeld_ = true;
     m_gryImage = m_grayStore.data();
     return true;
 }
@@ -298,11 +302,28 @@ bool CSLAM::recordFeature(FeatureInfo& fi, int k)
 // The new nodes keep their archived ID (ID is not advanced) with isLoop = true; their archive entries are erased.
 bool CSLAM::reinsertLoops()
 {
-    std::vector<int> take;
-    for (int a : loopArchive_)
-        if (a >= 0 && a < (int)m_featuresAllInfo.size() && m_featuresAllInfo[a].hasRecord && std::find(take.begin(), take.end(), a) == take.end()) take.push_back(a);
+    std::vector<int> take, seen;
+    for (int a : loopArchive_) {
+        if (a < 0 || a >= (int)m_featuresAllInfo.size() || !m_featuresAllInfo[a].hasRecord || std::find(seen.begin(), seen.end(), a) != seen.end()) continue;
+        seen.push_back(a);
+        // searchArchivedLandmarks: the geometric test alone does not put a landmark back; the search of this frame has to have matched it (the matched entries
+        // went back when it ran, so what a pass still meets here was refused)
+        if (searchArchivedLandmarks && std::find(archiveVerdict_.begin(), archiveVerdict_.end(), m_featuresAllInfo[a].ID) == archiveVerdict_.end()) { m_nArchiveRejected++; continue; }
+        take.push_back(a);
+    }
     std::vector<int> ids;
     std::vector<double> x6s, srs;
+    if (!reinsertEntries(take, ids, x6s, srs)) return false;
+    if (logDetectPasses && !m_detectLog.empty()) {
+        DetectPass& d = m_detectLog.back();
+        d.reinsertRan = true; d.reinserted = ids; d.reinsertedX6 = x6s; d.reinsertedSr = srs;
+    }
+    return true;
+}
+
+// the archive entries `take` (indices, each once) go behind the map as isLoop nodes with their archived state, sr and appearance record; their entries are erased
+bool CSLAM::reinsertEntries(const std::vector<int>& take, std::vector<int>& ids, std::vector<double>& x6s, std::vector<double>& srs)
+{
     if (!take.empty()) {
         mirrorsFresh_ = false;
         if (!check(srukf_set_new_landmarks(ctx_, 0))) return false;             // m_nAddings = 0 here: the loop points go behind the whole map
@@ -339,10 +360,6 @@ bool CSLAM::reinsertLoops()
         const int n = 6 * m_nMapFeatures + 4;
         m_X_k.create(n, 1); m_S_k.create(n, n); m_P_k.create(n, n);
         refreshMirrors();
-    }
-    if (logDetectPasses && !m_detectLog.empty()) {
-        DetectPass& d = m_detectLog.back();
-        d.reinsertRan = true; d.reinserted = ids; d.reinsertedX6 = x6s; d.reinsertedSr = srs;
     }
     return true;
 }
@@ -608,7 +625,8 @@ bool CSLAM::redirection()
     std::vector<double> keyPoints;
     if (!addFeatures && m_gryImage) {                                                                          // 1418-1420 on the device: isAdding semantics
         isAdding = true;
-        const bool ok = addFeaturesOnDevice();
+        frameHeld_ = false;                                                                                    // (a new handle holds nothing)
+        const bool ok = (!searchArchivedLandmarks || searchArchive()) && addFeaturesOnDevice();
         isAdding = false;
         if (!ok) return false;
     } else {
@@ -682,13 +700,14 @@ void CSLAM::KalmanUpdate()
     m_nMatches = 0; m_nLowInliers = 0; m_nHighInliers = 0;
     for (int k = 0; k < N; k++) {
         map[k].inliner_L = map[k].inliner_H = false;
-        if (map[k].isMatching) { m[k] = 1; z[2 * k] = map[k].matchLocation.x; z[2 * k + 1] = map[k].matchLocation.y; m_nMatches++; }
+        if (!map[k].isMatching || std::find(reacquired_.begin(), reacquired_.end(), k) != reacquired_.end()) continue;   // (those come last, one at a time)
+        m[k] = 1; z[2 * k] = map[k].matchLocation.x; z[2 * k + 1] = map[k].matchLocation.y; m_nMatches++;
     }
-    if (m_nMatches == 0) return;                                                                               // 2050-2051
+    if (m_nMatches == 0) { updateReacquiredLoopNodes(false); return; }                                         // 2050-2051
     if (!isUseRANSAC || m_nMatches < 2) {                                                                      // 2058-2095 (one match cannot out-vote itself)
         for (int k = 0; k < N; k++) if (m[k]) map[k].nMatchTimes++;
         const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;                  // 2083-2090
-        check(srukf_update(ctx_, z.data(), m.data(), reorder, m_updateMode));
+        if (check(srukf_update(ctx_, z.data(), m.data(), reorder, m_updateMode))) updateReacquiredLoopNodes(true);
         return;
     }
     ransacZ_.swap(z); ransacM_.swap(m);                                                                        // 2097-2103
@@ -700,6 +719,109 @@ void CSLAM::KalmanUpdate()
         else map[k].isMatching = false;
     }
     m_nMatches = m_nLowInliers + m_nHighInliers;
+    if (lastError.empty()) updateReacquiredLoopNodes(m_nMatches > 0);
+}
+
+// ---- archived landmarks found in the frame by appearance ---------------------------------------------------------------------
+// After updateFeaturesInformation and before addFeatures (and in front of a redirection restart's addFeatures).  The entries with a record and an init patch are
+// the device's archive, sent again only when their IDs or the handle's count differ from what the last mirror sent; the search runs on the held frame (on
+// m_gryImage when nothing uploaded this frame yet); every matched entry goes back by the loop-point route
+bool CSLAM::searchArchive()
+{
+    archiveVerdict_.clear(); reacquire_.clear();
+    if (!ctx_ || !reinsertLoopPoints) return true;
+    std::vector<int> idx, ids;
+    for (int a = 0; a < (int)m_featuresAllInfo.size(); a++)
+        if (m_featuresAllInfo[a].hasRecord && m_featuresAllInfo[a].hasInitPatch) { idx.push_back(a); ids.push_back(m_featuresAllInfo[a].ID); }
+    const int L = (int)idx.size();
+    if (ids != archiveMirror_ || srukf_archive_count(ctx_) != L) {
+        std::vector<double> X6(6 * (size_t)L), S66(36 * (size_t)L), R(9 * (size_t)L), t(3 * (size_t)L), px(2 * (size_t)L);
+        std::vector<unsigned char> patches(441 * (size_t)L);
+        for (int j = 0; j < L; j++) {
+            const FeatureInfo& fi = m_featuresAllInfo[idx[j]];
+            memcpy(&X6[6 * j], fi.state, sizeof fi.state); memcpy(&S66[36 * j], fi.sr, sizeof fi.sr);
+            memcpy(&R[9 * j], fi.initRotation, sizeof fi.initRotation); memcpy(&t[3 * j], fi.initTrans, sizeof fi.initTrans);
+            px[2 * j] = fi.initPixel.x; px[2 * j + 1] = fi.initPixel.y;
+            memcpy(&patches[441 * (size_t)j], fi.initPatch, 441);
+        }
+        if (!check(srukf_archive_set(ctx_, L, X6.data(), S66.data(), patches.data(), R.data(), t.data(), px.data()))) return false;
+        archiveMirror_ = ids;
+    }
+    if (L == 0 || (!frameHeld_ && !m_gryImage)) return true;
+    srukf_archive_params ap; ap.half_cap = archiveSearchHalfCap; ap.corr_threshold = 0.8; ap.chi2 = 5.99146454710798;
+    std::vector<int> matched(L);
+    if (!check(srukf_archive_search(ctx_, frameHeld_ ? nullptr : m_gryImage, &ap, nullptr, nullptr, nullptr, nullptr, matched.data(), nullptr))) return false;
+    frameHeld_ = true;
+    std::vector<int> take;
+    for (int j = 0; j < L; j++) if (matched[j]) { take.push_back(idx[j]); archiveVerdict_.push_back(ids[j]); reacquire_.push_back(std::make_pair(ids[j], j)); }
+    ArchiveSearch log; log.frame = m_frame.counter; log.searched = L; log.n_before = m_nMapFeatures; log.archived_before = (int)m_featuresAllInfo.size();
+    std::vector<double> x6s, srs;
+    if (!reinsertEntries(take, log.ids, x6s, srs)) return false;
+    m_nArchiveMatches += (int)take.size();
+    log.n_after = m_nMapFeatures; log.archived_after = (int)m_featuresAllInfo.size();
+    if (logDetectPasses) m_archiveLog.push_back(log);
+    return true;
+}
+
+// The frame after a search put nodes back: the ordinary association looks +- 10 px around the prediction (HP_INIT, 1955-1956), the drift that archived landmarks
+// are looked for across is larger.  Their records are still on the device in their slots, with the state and factor the nodes went back with, so one more search
+// of this frame (pose and P4 of the predicted state) finds them with the gate's window; its z becomes the match of every such node the association left unmatched
+bool CSLAM::reacquireLoopNodes()
+{
+    reacquired_.clear();
+    std::vector<std::pair<int, int>> want; want.swap(reacquire_);
+    const int L = (int)archiveMirror_.size();
+    if (want.empty() || !ctx_ || srukf_archive_count(ctx_) != L || (!frameHeld_ && !m_gryImage)) return true;
+    srukf_archive_params ap; ap.half_cap = archiveSearchHalfCap; ap.corr_threshold = 0.8; ap.chi2 = 5.99146454710798;
+    std::vector<int> matched(L); std::vector<double> z(2 * (size_t)L);
+    if (!check(srukf_archive_search(ctx_, frameHeld_ ? nullptr : m_gryImage, &ap, nullptr, nullptr, nullptr, z.data(), matched.data(), nullptr))) return false;
+    frameHeld_ = true;
+    for (const auto& w : want) {
+        if (!matched[w.second]) continue;
+        for (int k = 0; k < m_nMapFeatures; k++) {
+            if (map[k].ID != w.first || !map[k].isLoop) continue;
+            if (map[k].isVisible && !map[k].isMatching) {
+                map[k].isMatching = true; map[k].matchLocation.x = z[2 * w.second]; map[k].matchLocation.y = z[2 * w.second + 1];
+                reacquired_.push_back(k);
+            }
+            break;
+        }
+    }
+    return true;
+}
+
+// KalmanUpdate's part for the nodes reacquireLoopNodes matched: one srukf_update each, predicted again from the posterior in between, behind the frame's ordinary
+// matches.  The reference's update forms every landmark's gain from the same prior and sums the corrections (2070-2080): landmarks that agree on an innovation of
+// tens of pixels, which is what a re-found landmark brings, overshoot together; taken one at a time each sees what the ones before left.  From the second update of
+// the frame on, a node must pass dataAssociation's chi-square gate (1977) at the prediction from the posterior, as a rescued RANSAC match must
+bool CSLAM::updateReacquiredLoopNodes(bool updated)
+{
+    if (reacquired_.empty()) return true;
+    std::vector<int> nodes; nodes.swap(reacquired_);
+    const int N = m_nMapFeatures;
+    const double CHI2INV_0_2 = 5.99146454710798;
+    const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;
+    std::vector<double> z(2 * (size_t)N, 0.0), h(2 * (size_t)N), Si(4 * (size_t)N); std::vector<int> m(N, 0), vis(N);
+    for (int k : nodes) {
+        bool take = true;
+        if (updated) {
+            if (!check(srukf_repredict_measurement(ctx_, h.data(), Si.data(), vis.data()))) return false;
+            const double s00 = Si[4 * k], s01 = Si[4 * k + 1], s11 = Si[4 * k + 3];
+            take = vis[k] && s00 != 0.0 && s11 != 0.0;
+            if (take) {
+                const double v0 = map[k].matchLocation.x - h[2 * k], v1 = map[k].matchLocation.y - h[2 * k + 1];
+                const double y0 = v0 / s00, y1 = (v1 - s01 * y0) / s11;
+                take = y0 * y0 + y1 * y1 < CHI2INV_0_2;
+            }
+        }
+        if (!take) { map[k].isMatching = false; continue; }
+        std::fill(m.begin(), m.end(), 0); m[k] = 1;
+        z[2 * k] = map[k].matchLocation.x; z[2 * k + 1] = map[k].matchLocation.y;
+        if (!check(srukf_update(ctx_, z.data(), m.data(), reorder, m_updateMode))) return false;
+        updated = true;
+        map[k].nMatchTimes++; m_nMatches++; m_nArchiveReacquired++;
+    }
+    return true;
 }
 
 // Civera's 1-point hypotheses, all of them (srukf_ransac_consensus): the low-innovation inliers are the consensus set of the best one
@@ -799,11 +921,14 @@ void CSLAM::SLAM()
     const auto t0 = std::chrono::steady_clock::now();                                                          // startTimer 122-132
     m_showCounter++;
     mirrorsFresh_ = false;
+    frameHeld_ = false;
     predictMotion();
     predictMeasurement();
     if (dataAssociation) dataAssociation(*this);                                                               // loadPictures + dataAssociation (95-97)
+    if (searchArchivedLandmarks) reacquireLoopNodes();
     KalmanUpdate();
     updateFeaturesInformation();                                                                               // deletion policy + display refresh (2397-2621)
+    if (searchArchivedLandmarks) searchArchive();
     refreshMirrors();                                                                                          // m_P_k (2404), m_X_k, m_S_k
     updateRobotInformation();
     recordRobotInformation();

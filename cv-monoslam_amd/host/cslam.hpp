@@ -235,6 +235,22 @@ public:
     // addFeatures puts the loop points of its last pass back into the filter (srukf_insert_landmarks, SLAM.cpp:948-1015).
     // false (default): loop points are only reported
     bool   reinsertLoopPoints = false;
+    // true (needs reinsertLoopPoints, which provides the records, and m_gryImage / a held frame): SLAM() looks for every archived landmark in the frame by
+    // appearance (srukf_archive_search) after updateFeaturesInformation and before addFeatures.  The archive entries with a record and an init patch
+    // are mirrored to the device when the archive changed; every matched entry goes back into the filter by the loop-point route (archived ID kept, isLoop = true,
+    // archive entry erased); the geometric loop points of a detection pass are filtered by the same verdict (an entry the search of that frame did not match stays
+    // archived).  The frame after, the nodes put back are looked for once more with the search's window (the ordinary association's ends at 10 px) and
+    // KalmanUpdate measures those one at a time (updateReacquiredLoopNodes).  false (default): none of this runs
+    bool   searchArchivedLandmarks = false;
+    int    archiveSearchHalfCap = 40;                          // srukf_archive_params::half_cap, [10, 40]
+    int    m_nArchiveMatches = 0, m_nArchiveRejected = 0;      // entries the searches put back / geometric loop points the searches refused, since initializeParameters
+    int    m_nArchiveReacquired = 0;                           // nodes measured through the wide search the frame after they went back
+    bool searchArchive();                                      // mirror, search the held frame, re-insert the matched entries
+    struct ArchiveSearch { int frame = 0, n_before = 0, n_after = 0, archived_before = 0, archived_after = 0, searched = 0; std::vector<int> ids; };
+    std::vector<ArchiveSearch> m_archiveLog;                   // every search that looked at records, when logDetectPasses is on: m_frame.counter, map and archive
+                                                               // size around it, the records searched and the IDs put back
+    bool reacquireLoopNodes();                                 // between dataAssociation and KalmanUpdate of the frame after
+    bool updateReacquiredLoopNodes(bool updated);              // one srukf_update per re-acquired node, re-predicted in between (updated: an update ran this frame)
     // true: refreshFeaturesDisplay takes axis / sigma of every map node from the device with the frame view (srukf_get_frame_view_display /
     // srukf_get_landmarks_display: k_lm_ellipsoid runs this class's Jacobi and quaternion arithmetic operation for operation, same bits)
     // instead of calling get3DdisplayInformation per landmark.  false (default): the host computes them
@@ -253,6 +269,7 @@ private:
     bool addFeaturesOnDevice();
     bool recordFeature(FeatureInfo& fi, int k);
     bool reinsertLoops();
+    bool reinsertEntries(const std::vector<int>& take, std::vector<int>& ids, std::vector<double>& x6s, std::vector<double>& srs);
     void relinkMap();
     void refreshMirrors();
     bool check(int rc);
@@ -266,6 +283,12 @@ private:
     int addCalls_ = 0;                   // addFeaturesOnDevice calls (DetectPass::call)
     std::vector<double> ransacZ_; std::vector<int> ransacM_;   // the frame's matches as KalmanUpdate gathered them (the RANSAC steps share them)
     std::vector<int> loopArchive_;       // archive indices of the loop points of the last detection pass, in the order reported
+    // searchArchivedLandmarks: the IDs of the records on the device in their order there (what the last mirror sent), the IDs the last search matched, whether
+    // the handle holds this frame (an association or loadPictures uploaded it), and the nodes put back last frame with their slot on the device (the records stay
+    // there until the next mirror)
+    std::vector<int> archiveMirror_, archiveVerdict_; bool frameHeld_ = false;
+    std::vector<std::pair<int, int>> reacquire_;         // (ID, device slot)
+    std::vector<int> reacquired_;                        // map indices whose match of this frame came from the wide search, in slot order
 };
 
 }  // namespace monoslam

@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [ransac=<threshold>] [colour=1] [overlay=<file>]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -9,6 +9,10 @@
 //   Adds, and only with it, a "reinsert" line per restart (the archive's IDs before the frame, the IDs put back, map and archive size behind the
 //   restart's addFeatures, the archived X6 and sr of what was put back) and an
 //   "ids" line per frame (ID and isLoop of every map node, state order).
+// archive=<half_cap>: CSLAM::searchArchivedLandmarks on, together with loops (archiveSearchHalfCap = half_cap, 10 .. 40): every frame the archived landmarks are
+//   looked for in the frame by appearance and the matched ones put back.  Adds, and only with it, an "archive" line per search that looked at
+//   records (frame counter, records searched, map and archive size around it, the IDs put back), "reacquired <n>" on the frame line's next line, and the run's
+//   counters m_nArchiveMatches / m_nArchiveRejected / m_nArchiveReacquired at the end.
 // ransac=<threshold>: KalmanUpdate runs 1-point RANSAC (CSLAM::isUseRANSAC, THRESHOLD_RANSAC = threshold in pixels; 8 is the reference's constant).  Adds, and
 //   only with it, a "ransac" line per frame (low- and high-innovation inliers).
 // colour=1: every gray frame is fed as a B = G = R colour frame through CSLAM::loadPictures (srukf_set_frame_bgr) and associated on the held frame
@@ -26,7 +30,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [ransac=<threshold>] [colour=1] [overlay=<file>]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -34,9 +38,10 @@ int main(int argc, char** argv)
     std::vector<unsigned char> frames((size_t)W * H * F);
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
-    int redirect = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay;
+    int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay;
     for (int a = 3; a < argc; a++)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
+        else if (!strncmp(argv[a], "archive=", 8)) { archiveCap = atoi(argv[a] + 8); loops = true; }
         else if (!strncmp(argv[a], "ransac=", 7)) { ransac = true; ransacThr = atof(argv[a] + 7); }
         else if (!strncmp(argv[a], "colour=", 7)) colour = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "overlay=", 8)) overlay = argv[a] + 8;
@@ -56,6 +61,7 @@ int main(int argc, char** argv)
     if (redirect > 0) SLAM.m_odoTheta.at(2, redirect) = 1;
     SLAM.logDetectPasses = true;
     SLAM.reinsertLoopPoints = loops;
+    if (archiveCap > 0) { SLAM.searchArchivedLandmarks = true; SLAM.archiveSearchHalfCap = archiveCap; }
     if (ransac) { SLAM.isUseRANSAC = true; SLAM.THRESHOLD_RANSAC = ransacThr; }
     const unsigned char* cur = nullptr;
     std::vector<unsigned char> bgr(colour ? (size_t)3 * W * H : 0);
@@ -69,7 +75,8 @@ int main(int argc, char** argv)
     for (int fr = 0; fr < steps; fr++) {
         cur = frames.data() + (size_t)(fr % F) * W * H;
         SLAM.m_gryImage = cur;
-        const size_t logged = SLAM.m_detectLog.size();
+        const size_t logged = SLAM.m_detectLog.size(), searches = SLAM.m_archiveLog.size();
+        const int reacquiredBefore = SLAM.m_nArchiveReacquired;
         const double addBefore = SLAM.m_detectTime;
         std::vector<monoslam::FeatureInfo> archive;
         if (loops) archive = SLAM.m_featuresAllInfo;                                // (what the restart of this frame may put back)
@@ -97,6 +104,16 @@ int main(int argc, char** argv)
         }
         printf("frame %d n_map %d map_size %d archived %d matches %d loops %d\n", fr, SLAM.m_nMapFeatures, (int)SLAM.mapStore.size(),
                (int)SLAM.m_featuresAllInfo.size(), SLAM.m_nMatches, SLAM.m_loopPointCounter);
+        if (archiveCap > 0) {
+            for (size_t q = searches; q < SLAM.m_archiveLog.size(); q++) {
+                const auto& a = SLAM.m_archiveLog[q];
+                printf("archive frame %d searched %d n_before %d n_after %d archived_before %d archived_after %d ids", a.frame, a.searched, a.n_before, a.n_after,
+                       a.archived_before, a.archived_after);
+                for (int id : a.ids) printf(" %d", id);
+                printf("\n");
+            }
+            printf("reacquired %d\n", SLAM.m_nArchiveReacquired - reacquiredBefore);
+        }
         if (ransac) printf("ransac low %d high %d\n", SLAM.m_nLowInliers, SLAM.m_nHighInliers);
         printf("init"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %.17g %.17g", m->initPixel.x, m->initPixel.y); printf("\n");
         if (loops) { printf("ids"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %d %d", m->ID, m->isLoop ? 1 : 0); printf("\n"); }
@@ -115,6 +132,7 @@ int main(int argc, char** argv)
                     m->matchLocation.y, m->isMatching ? 1 : 0);
         fclose(fo);
     }
+    if (archiveCap > 0) printf("archive_matches %d archive_rejected %d archive_reacquired %d\n", SLAM.m_nArchiveMatches, SLAM.m_nArchiveRejected, SLAM.m_nArchiveReacquired);
     printf("add_features_frame1_ms %.3f  frame_time_ms %.3f\n", addWall * 1e3, SLAM.m_frameTime * 1e3);
     return 0;
 }

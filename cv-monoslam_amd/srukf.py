@@ -29,6 +29,7 @@ EXPORTS = [
     "srukf_ransac_consensus", "srukf_repredict_measurement",
     "srukf_get_landmarks_display", "srukf_get_frame_view_display",
     "srukf_set_frame_bgr", "srukf_associate_held", "srukf_render_overlay",
+    "srukf_archive_set", "srukf_archive_count", "srukf_archive_get_template", "srukf_archive_search",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -62,6 +63,11 @@ class DetectParams(C.Structure):
     """struct srukf_detect_params (defaults: SLAM.cpp:175-181, 48)."""
     _fields_ = [("max_corners", C.c_int), ("quality_level", C.c_double), ("min_dist", C.c_double), ("block_size", C.c_int),
                 ("dist_to_border", C.c_double), ("unfiltered", C.c_int), ("map_gate", C.c_int), ("project_archived", C.c_int)]
+
+
+class ArchiveParams(C.Structure):
+    """struct srukf_archive_params."""
+    _fields_ = [("half_cap", C.c_int), ("corr_threshold", C.c_double), ("chi2", C.c_double)]
 
 
 class SrukfError(RuntimeError):
@@ -138,6 +144,11 @@ def load_library(path=None):
         L.srukf_set_frame_bgr.argtypes = [C.c_void_p, _bp, _bp]
         L.srukf_associate_held.argtypes = [C.c_void_p, _dp, _ip, _dp]
         L.srukf_render_overlay.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip, _bp]
+    if hasattr(L, "srukf_archive_search"):             # (idem: archive search by appearance)
+        L.srukf_archive_set.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _bp, _dp, _dp, _dp]
+        L.srukf_archive_count.argtypes = [C.c_void_p]
+        L.srukf_archive_get_template.argtypes = [C.c_void_p, C.c_int, _bp]
+        L.srukf_archive_search.argtypes = [C.c_void_p, _bp, C.POINTER(ArchiveParams), _dp, _dp, _ip, _dp, _ip, _dp]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -434,6 +445,39 @@ class Filter:
         px = _c(px).reshape(L, 2) if px is not None else None
         self._chk(self._lib.srukf_insert_landmarks(self._h, L, _d(X6), _d(S66), pb, _d(R), _d(t), _d(px)))
         self._refresh_dims()
+
+    def archive_set(self, X6, S66, patches, R, t, px):
+        """The archive archive_search covers (srukf_archive_set): L records with means X6[L,6], upper-triangular square-root blocks S66[L,6,6] and appearance
+        records patches[L,21,21] uint8, R[L,3,3], t[L,3], px[L,2].  Replaces the whole archive; L = 0 (empty arrays) clears it."""
+        X6 = _c(X6).reshape(-1, 6)
+        L = X6.shape[0]
+        S66, R, t, px = _c(S66).reshape(L, 36), _c(R).reshape(L, 9), _c(t).reshape(L, 3), _c(px).reshape(L, 2)
+        patches = np.ascontiguousarray(patches, dtype=np.uint8).reshape(L, 441)
+        self._chk(self._lib.srukf_archive_set(self._h, L, _d(X6), _d(S66), patches.ctypes.data_as(C.POINTER(C.c_ubyte)), _d(R), _d(t), _d(px)))
+
+    def archive_count(self):
+        return int(self._lib.srukf_archive_count(self._h))
+
+    def archive_search(self, gray=None, half_cap=40, corr_threshold=0.8, chi2=5.99146454710798):
+        """Every archived record searched for in `gray` (None: the held frame) by appearance (srukf_archive_search).  Returns (h[2L], Si[L,2,2], visible[L],
+        z[2L], matched[L], corr[L]).  The filter is not changed."""
+        L = self.archive_count()
+        g = None
+        if gray is not None:
+            gray = np.ascontiguousarray(gray, dtype=np.uint8)
+            assert gray.shape == (int(self.params.image_h), int(self.params.image_w))
+            g = gray.ctypes.data_as(C.POINTER(C.c_ubyte))
+        ap = ArchiveParams(int(half_cap), float(corr_threshold), float(chi2))
+        h, Si, vis = np.zeros(2 * L), np.zeros((L, 2, 2)), np.zeros(L, dtype=np.int32)
+        z, m, cr = np.zeros(2 * L), np.zeros(L, dtype=np.int32), np.zeros(L)
+        self._chk(self._lib.srukf_archive_search(self._h, g, C.byref(ap), _d(h), _d(Si), _i(vis), _d(z), _i(m), _d(cr)))
+        return h, Si, vis, z, m, cr
+
+    def archive_template(self, j):
+        """The 17 x 17 template the last archive_search warped for record j (zeros before any search)."""
+        out = np.zeros((17, 17), dtype=np.uint8)
+        self._chk(self._lib.srukf_archive_get_template(self._h, int(j), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out
 
     def set_exclusive(self, exclusive):
         """True / GPU_EXCLUSIVE (default): the filter has the GPU to itself (one persistent refactorisation launch per frame that may

@@ -305,6 +305,45 @@ int  srukf_get_landmark_record(srukf_ctx* ctx, int k, double X6[6], double S66[3
 int  srukf_insert_landmarks(srukf_ctx* ctx, int L, const double* X6, const double* S66, const unsigned char* patches, const double* R, const double* t,
                             const double* px);
 
+/* ---- archived landmarks found in the frame by appearance (no reference counterpart: the reference meets an archived landmark again only when a
+ * corner of a detection pass lies within m_minDist of its projected mean, SLAM.cpp:699-727) ----
+ * srukf_archive_set: the archive the search covers, on the handle: it survives map changes as the held frame does, srukf_reset and srukf_destroy drop it.  The call
+ *   replaces the whole archive; L = 0 clears it.  Layouts as srukf_insert_landmarks: X6[6L], S66[36L] (row-major upper triangular), patches[441L], R[9L], t[3L],
+ *   px[2L]; every record has an appearance (the caller leaves the others out).  SRUKF_ERR_BAD_ARG: L < 0, a non-finite number, a nonzero entry below the diagonal
+ *   of an S66, a NULL array with L > 0; such a call leaves the archive as it was.  A call that fails with SRUKF_ERR_NOMEM or SRUKF_ERR_HIP leaves it empty.
+ *   srukf_archive_count: L.
+ * srukf_archive_search: valid in any phase; gray = the image_h x image_w frame, or NULL for the held one (SRUKF_ERR_SEQUENCE when none is held).  params NULL:
+ *   half_cap 40, corr_threshold 0.8 (THRESHOLD_MATCH_PATCH), chi2 5.99146454710798.  SRUKF_ERR_BAD_ARG: half_cap outside [10, 40], chi2 not a finite number > 0,
+ *   corr_threshold not finite.  Outputs (host, any may be NULL):
+ *   h[2L], Si[4L], visible[L], z[2L], matched[L], corr[L].  The robot pose and its 4 x 4 covariance P4 are what srukf_get_robot returns at that moment.  Per record j:
+ *   (a) the unscented transform over the 12-vector [record 6 | robot 4 | pixel noise 2] with the weights of Na = 12 (weight type 0: wm0 = -3, wi = 1/6, gamma =
+ *       sqrt 3) and S_aug = blockdiag(S66_j, S_rr, sigma_measure I2), S_rr the upper Cholesky factor of P4 by srukf_get_landmark_record's rule.  Sigma points
+ *       mu, mu + gamma row_i, mu - gamma row_i (25), each through the device's projection (the one srukf_project_host runs) with its two noise entries as the
+ *       pixel error: Z_0 .. Z_24.  h = wm0 Z_0 + wi sum_{i>=1} Z_i;  Pi = wi sum_{i>=1} (Z_i - Z_0)(Z_i - Z_0)^T (deviations from the centre point, no centre
+ *       term: predictMeasurement's form, 1769-1773);  Si = the upper Cholesky factor of Pi by the same rule;  visible = both coordinates of all 25 pixels >= 1:
+ *       a sigma point outside the projection's validity border has its undistorted pixel zeroed, which the distortion maps to a fraction of a pixel from the origin,
+ *       and such a point would drag the mean (stricter than the reference's test of the mean, 1727).  The threshold 1 assumes what holds for any usable camera
+ *       model here: a valid pixel (>= 10 px inside the image) is moved by the distortion by less than 9 px, and the image of the zeroed pixel, c (1 - 1/d) per
+ *       coordinate with c the principal point and d the distortion factor at the origin, stays below 1 px (0.037, 0.028 with the default intrinsics).  Sums in
+ *       ascending sigma index.
+ *   (b) wrapPatch (1803-1906) of every visible record under the current pose around h, with the record's Cartesian mean (x + cos phi sin theta / rho, y - sin phi /
+ *       rho, z + cos phi cos theta / rho), into the archive's template buffer, which is zeroed at the start of every search.  srukf_archive_get_template returns the
+ *       17 x 17 template of record j (zeros before any search, for records not visible, and where the warp leaves the init patch).
+ *   (c) the search.  Pi = Si^T Si; half_x = clamp(ceil(sqrt(chi2 Pi00)), 8, half_cap), half_y from Pi11; candidate centres (i, j) = ((int)h_x - half_x + c % wx,
+ *       (int)h_y - half_y + c / wx), c row-major over wx x wy = (2 half_x + 1) x (2 half_y + 1).  A candidate scores 0 when its 17 x 17 patch leaves the image or
+ *       e^T Pi^-1 e >= chi2, e = (i - h_x, j - h_y) (closed-form 2 x 2 inverse).  Otherwise, with v the frame bytes, t the template bytes, NP = 289 and exact integer
+ *       sums, A = NP sum vt - sum v sum t, B = NP sum v^2 - (sum v)^2, C = NP sum t^2 - (sum t)^2: score = (B == 0 || C == 0) ? 0 : (double)A / sqrt((double)B *
+ *       (double)C) — the normalised cross correlation of calculateCrossCorrelation (3141-3166) without its rounding.  corr = the maximum score, the first one in
+ *       row-major order; matched = corr > corr_threshold; z = that centre (integers), (0, 0) when not matched.  Not visible: matched 0, corr 0, z (0, 0).
+ *   The call writes nothing the filter reads: every later result of the filter is bit for bit what it is without the call, in any phase, and what an update
+ *   submitted ahead for the next frame stays valid.  Matched records are the caller's to put back (srukf_insert_landmarks). */
+typedef struct srukf_archive_params { int half_cap; double corr_threshold; double chi2; } srukf_archive_params;
+int  srukf_archive_set(srukf_ctx* ctx, int L, const double* X6, const double* S66, const unsigned char* patches, const double* R, const double* t, const double* px);
+int  srukf_archive_count(srukf_ctx* ctx);
+int  srukf_archive_get_template(srukf_ctx* ctx, int j, unsigned char out[289]);
+int  srukf_archive_search(srukf_ctx* ctx, const unsigned char* gray, const srukf_archive_params* params, double* h, double* Si, int* visible, double* z,
+                          int* matched, double* corr);
+
 /* Select the storage precision (default SRUKF_STORAGE_F64).  With SRUKF_STORAGE_F32 the state is rounded to float at
  * the end of every refactorisation (and by srukf_set_state); srukf_get_state returns those values widened to double,
  * srukf_get_state_f32 the float arrays themselves (X[n], S[n*n] row-major). */
