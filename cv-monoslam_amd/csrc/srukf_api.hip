@@ -56,7 +56,7 @@ namespace srukf_impl {
 const char* const kclass_name[KC_COUNT] = { "k_motion", "k_project", "k_meas_stats", "k_pxy", "k_gain", "k_syrk",
                                              "k_gmw_step64", "k_gmw_persist", "k_gmw_check", "k_gmw_col", "k_rank_expand", "k_project_motion", "k_project_table", "k_pxy2",
                                              "misc", "k_det_response", "k_det_cand", "k_det_rank", "k_det_select", "k_capture_patch", "k_lm_ellipsoid", "k_bgr2gray", "k_overlay",
-                                             "k_archive_predict", "k_archive_warp", "k_archive_search" };
+                                             "k_archive_predict", "k_archive_warp", "k_archive_search", "k_associate_checked" };
 
 void gmw_plan_destroy(GmwPlan& g, hipStream_t st)
 {
@@ -388,7 +388,7 @@ int srukf_destroy(srukf_ctx* c)
     if (c->graphN) hipGraphDestroy(c->graphN);
     void* bufs[] = { c->X, c->S, c->G, c->Gbak, c->Wf, c->sigR, c->Cmat, c->Z, c->DZ, c->Ut, c->h /* + Si, vis */, c->PxyR, c->D,
                      c->zcur /* + mcur */, c->odocur, c->small, c->theta, c->fs, c->odo_seq, c->z_seq, c->m_seq, c->pan[0], c->pan[1], c->mpart, c->dxp, c->syrk_tiles, c->pxy_tiles, c->syrk_head_tiles,
-                     c->perm, c->iperm, c->Sdis, c->ckS, c->ckX, c->ckS2, c->ckX2, c->odo_step, c->export_cnt, c->red_perm, c->red_iperm, c->gdiag, c->red_syrk_tiles, c->syrk_head_tiles_b, c->red_head0_tiles, c->split_fold_list, c->shadowA, c->Utp, c->P1, c->pxy2_tiles, c->nskip, c->slabW, c->slabL, c->gsW, c->gsL, c->S32, c->X32, c->U32, c->mx_part, c->mx_tasks, c->mx_tiles, c->fold_sync, c->dxk, c->A32, c->mxr_part, c->mxr_tasks, c->mxr_tiles, c->mxr_f64_tiles, c->mxr_xt, c->app_patch, c->app_tmpl, c->d_image, c->appR, c->appT, c->appPx, c->corr, c->has_app, c->disp, c->d_bgr, c->d_ovl, c->ov_in, c->ov_rec };
+                     c->perm, c->iperm, c->Sdis, c->ckS, c->ckX, c->ckS2, c->ckX2, c->odo_step, c->export_cnt, c->red_perm, c->red_iperm, c->gdiag, c->red_syrk_tiles, c->syrk_head_tiles_b, c->red_head0_tiles, c->split_fold_list, c->shadowA, c->Utp, c->P1, c->pxy2_tiles, c->nskip, c->slabW, c->slabL, c->gsW, c->gsL, c->S32, c->X32, c->U32, c->mx_part, c->mx_tasks, c->mx_tiles, c->fold_sync, c->dxk, c->A32, c->mxr_part, c->mxr_tasks, c->mxr_tiles, c->mxr_f64_tiles, c->mxr_xt, c->app_patch, c->app_tmpl, c->d_image, c->appR, c->appT, c->appPx, c->corr, c->has_app, c->disp, c->d_bgr, c->d_ovl, c->ov_in, c->ov_rec, c->match_res, c->match_scores };
     for (void* b : bufs) if (b) srukf_dfree_on(b, c->stream);
     det_scratch_free(c->det, c->stream);
     ransac_scratch_free(c->ransac, c->stream);
@@ -507,6 +507,7 @@ int srukf_reset(srukf_ctx* c)
     c->phase = 0; c->async_pending = false;
     c->frame_valid = false; c->bgr_valid = false;                // (the held frame goes with the state, gray and colour)
     archive_free(c->archive, c->stream);                         // (and the archive: srukf_archive_set)
+    match_drop(c);                                               // (and the score maps of srukf_associate_checked)
     if (c->red_r) { c->red_r = 0; drop_graphs(c); }            // the state is the robot block only: nothing to reduce until a state arrives
     return SRUKF_OK;
 }

@@ -9,6 +9,7 @@
 //   srukf_overlay.hip colour-frame intake (srukf_set_frame_bgr) and the 2-D feature overlay (srukf_render_overlay)
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search)
+//   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip)
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -107,6 +108,10 @@ void srukf_launch_gain_dx(hipStream_t, int, int, const double*, double*, const d
 void srukf_launch_syrk32(hipStream_t, int, int, int, const float*, const float*, const void*, int, const void*, int, double*, double*, void*, int);
 int srukf_app_patch_stride(void);
 int srukf_app_tmpl_stride(void);
+void srukf_launch_associate_checked(hipStream_t, KDims, srukf_params, double, double, int, int, const unsigned char*, const double*, const double*, const int*, const int*,
+                                    const unsigned char*, double*, int*, double*, double*, double*);
+int srukf_match_score_stride(void);
+int srukf_match_tmpl_stride(void);
 }
 
 #define SRUKF_GRAPH_FRAMES 8
@@ -120,7 +125,7 @@ int srukf_app_tmpl_stride(void);
 enum KClass { KC_MOTION = 0, KC_PROJECT, KC_STATS, KC_PXY, KC_GAIN, KC_SYRK, KC_GMW_TRAIL, KC_GMW_PERSIST, KC_GMW_CHECK,
               KC_GMW_COL, KC_RANK_EXPAND, KC_PROJECT_MOTION, KC_PROJECT_TABLE, KC_PXY2, KC_MISC,
               KC_DET_RESPONSE, KC_DET_CAND, KC_DET_RANK, KC_DET_SELECT, KC_CAPTURE, KC_LM_ELLIPSOID, KC_BGR2GRAY, KC_OVERLAY,
-              KC_ARCHIVE_PREDICT, KC_ARCHIVE_WARP, KC_ARCHIVE_SEARCH, KC_COUNT };
+              KC_ARCHIVE_PREDICT, KC_ARCHIVE_WARP, KC_ARCHIVE_SEARCH, KC_ASSOC_CHECKED, KC_COUNT };
 struct ProfEvent { hipEvent_t a, b; int kc; };
 
 // ---- persistent GMW launch (k_gmw_persist): per-matrix-size resources --------------------------------
@@ -188,6 +193,10 @@ struct srukf_ctx {
     unsigned char *d_bgr = nullptr, *d_ovl = nullptr; bool bgr_valid = false;
     // ... and what the overlay is drawn from, sized by the context's N (stays with its context): h | Si | z (8N doubles) | matched (N ints), the per-landmark records
     double* ov_in = nullptr; void* ov_rec = nullptr;
+    // srukf_associate_checked (srukf_unique.hip), allocated on its first call and sized by the context's N: match_res = z | corr | corr2 | z2 | matched, flags (7N doubles,
+    // exported in one piece), match_scores = every landmark's score map (448 doubles each: map | wx wy x0 y0).  match_valid: the maps are the last checked call's
+    // (srukf_get_match_scores); a map change and srukf_reset drop both buffers (match_drop)
+    double *match_res = nullptr, *match_scores = nullptr; bool match_valid = false;
     DetScratch det;                        // srukf_detect_features (handed over at map changes too)
     RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
     ArchiveState archive;                  // srukf_archive_set / srukf_archive_search (handed over at map changes)
@@ -412,6 +421,9 @@ void launch_capture_patch(hipStream_t st, const unsigned char* img, int W, int f
 
 // ---- 1-point RANSAC (srukf_ransac.hip) ----
 void ransac_scratch_free(RansacScratch& s, hipStream_t st);
+
+// ---- srukf_associate_checked's buffers (srukf_map.hip) ----
+void match_drop(srukf_ctx* c);
 
 // ---- archive search (srukf_archive.hip) ----
 void archive_free(ArchiveState& a, hipStream_t st);

@@ -71,6 +71,13 @@ namespace srukf_impl {
 
 // the handle keeps its identity when the map changes size: swap the guts of a freshly built context in, keep the
 // stream ownership and the profile, destroy the old buffers
+void match_drop(srukf_ctx* c)
+{
+    if (c->match_res) srukf_dfree_on(c->match_res, c->stream);
+    if (c->match_scores) srukf_dfree_on(c->match_scores, c->stream);
+    c->match_res = nullptr; c->match_scores = nullptr; c->match_valid = false;
+}
+
 void adopt_context(srukf_ctx* c, srukf_ctx* c2)
 {
     const bool own = c->own_stream;
@@ -91,6 +98,7 @@ void adopt_context(srukf_ctx* c, srukf_ctx* c2)
     std::swap(c->d_bgr, c2->d_bgr); std::swap(c->d_ovl, c2->d_ovl); std::swap(c->bgr_valid, c2->bgr_valid);      // (the colour frame and the overlay's output likewise)
     std::swap(c->archive, c2->archive);                          // (the archive srukf_archive_search reads: the handle's too)
     c2->frame_valid = false; c2->bgr_valid = false;
+    match_drop(c2);                                              // (the score maps of srukf_associate_checked go with the map they were made for)
     ctx_retire(c, c2);                                           // (not destroyed: revived when the map has this size again — ctx_obtain)
     c->phase = 0; c->frame_updated = false;
     if (shared != c->gmw_shared) set_shared(c, shared, tenants);
@@ -163,15 +171,24 @@ int srukf_get_match_patch(srukf_ctx* c, int k, unsigned char* out)
 // image_h x image_w frame (row-major uchar).  Out (host, any may be NULL): z[2N] = matchLocation, matched[N] =
 // isMatching, corr[N] = best normalised cross correlation.  Landmarks without an appearance record never match.
 // (gray == NULL: the frame the handle holds, no upload — srukf_associate_held, which has checked that there is one)
-static int associate_frame(srukf_ctx* c, const unsigned char* gray, double* z, int* matched, double* corr)
+// chk != NULL: srukf_associate_checked — the same launches with k_associate_checked (srukf_unique.hip) in k_associate's place, its seven result arrays in one export
+static int associate_frame(srukf_ctx* c, const unsigned char* gray, double* z, int* matched, double* corr,
+                           const srukf_match_params* chk = nullptr, double* corr2 = nullptr, double* z2 = nullptr, int* flags = nullptr)
 {
     if (c->phase < 2) { c->err = "associate before predict_measurement"; return SRUKF_ERR_SEQUENCE; }
     const int N = c->d.N;
     if (N == 0) return SRUKF_OK;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_appearance(c); if (rc) return rc;
+    if (chk && !c->match_res) {
+        if (srukf_app_tmpl_stride() != srukf_match_tmpl_stride()) { c->err = "associate_checked: template strides differ"; return SRUKF_ERR_UNSUPPORTED; }
+        if (srukf_dmalloc(&c->match_res, sizeof(double) * 7 * (size_t)N) != hipSuccess || srukf_dmalloc(&c->match_scores, sizeof(double) * srukf_match_score_stride() * (size_t)N) != hipSuccess) {
+            (void)hipGetLastError(); match_drop(c); c->err = "associate_checked: out of device memory"; return SRUKF_ERR_NOMEM;
+        }
+    }
     const size_t img = (size_t)c->p.image_w * c->p.image_h;
     const size_t mp = c->d.mp, zm = mp + ((size_t)N + 1) / 2;             // zcur | mcur: one device allocation of zm doubles
+    const size_t res_doubles = chk ? 7 * (size_t)N : zm + (size_t)N;      // what the export writes to the front of the staging buffer: match_res, or zcur | mcur | corr
     // What does not need the frame goes out first — the warp uses the PREDICTED robot pose (wrapPatch reads m_X_k after predictMotion, SLAM.cpp:1812-1830) — and runs while
     // the host copies the frame into pinned memory: a hipMemcpyAsync from the caller's pageable buffer is staged by the runtime, synchronously, in front of everything.
     step_commit_motion(c);
@@ -179,7 +196,7 @@ static int associate_frame(srukf_ctx* c, const unsigned char* gray, double* z, i
     srukf_launch_landmarks_cartesian(c->stream, c->d, c->X, c->S, dxyz, nullptr);                           // PointsMap::xyz (2574): the points only, no covariances
     srukf_launch_warp_patch(c->stream, c->d, c->p, c->X, dxyz, c->h, c->appR, c->appT, c->appPx, c->app_patch, c->has_app, c->app_tmpl);
     double* hs = c->hstage;
-    const size_t img_off = (zm + (size_t)N + 7) & ~(size_t)7;           // (doubles) behind the results' place in the staging buffer
+    const size_t img_off = (res_doubles + 7) & ~(size_t)7;              // (doubles) behind the results' place in the staging buffer
     if (!gray) {
     } else if ((img_off + (img + 7) / 8) * sizeof(double) <= c->hstage_bytes) {
         unsigned char* himg = (unsigned char*)(hs + img_off);
@@ -189,12 +206,28 @@ static int associate_frame(srukf_ctx* c, const unsigned char* gray, double* z, i
         HIPCHK(c, hipMemcpyAsync(c->d_image, gray, img, hipMemcpyHostToDevice, c->stream));
     }
     if (gray) { c->frame_valid = true; c->bgr_valid = false; }
+    if (chk) {
+        ProfScope ps(c, KC_ASSOC_CHECKED, 0, (37.0 * 37.0 + 289.0 + 8.0 * srukf_match_score_stride()) * N);
+        srukf_launch_associate_checked(c->stream, c->d, c->p, chk->corr_threshold, chk->ratio, chk->exclusion, chk->subpixel, c->d_image, c->h, c->Si, c->vis, c->has_app,
+                                       c->app_tmpl, c->zcur, c->mcur, c->corr, c->match_res, c->match_scores);
+        c->match_valid = true;
+    } else
     srukf_launch_associate(c->stream, c->d, c->p, c->d_image, c->h, c->Si, c->vis, c->has_app, c->app_tmpl, c->zcur, c->mcur, c->corr);
     // z | matched | corr written into the pinned buffer by ONE short launch, flag behind them: three small device-to-host copies were three blit kernels with their gaps
     const unsigned long long seq = ++c->step_seq;
-    launch_export(c->stream, c->zcur, sizeof(double) * zm, c->corr, sizeof(double) * N, hs, c->dbg.step_spin ? step_flag(c) : nullptr, seq);
+    if (chk) launch_export(c->stream, c->match_res, sizeof(double) * 7 * N, nullptr, 0, hs, c->dbg.step_spin ? step_flag(c) : nullptr, seq);
+    else launch_export(c->stream, c->zcur, sizeof(double) * zm, c->corr, sizeof(double) * N, hs, c->dbg.step_spin ? step_flag(c) : nullptr, seq);
     rc = step_wait_export(c, seq); if (rc) return rc;
     HIPCHK(c, hipGetLastError());
+    if (chk) {                                                            // z | corr | corr2 | z2 | matched, flags
+        if (z) memcpy(z, hs, sizeof(double) * 2 * N);
+        if (corr) memcpy(corr, hs + 2 * (size_t)N, sizeof(double) * N);
+        if (corr2) memcpy(corr2, hs + 3 * (size_t)N, sizeof(double) * N);
+        if (z2) memcpy(z2, hs + 4 * (size_t)N, sizeof(double) * 2 * N);
+        if (matched) memcpy(matched, hs + 6 * (size_t)N, sizeof(int) * N);
+        if (flags) memcpy(flags, (const int*)(hs + 6 * (size_t)N) + N, sizeof(int) * N);
+        return SRUKF_OK;
+    }
     if (z) memcpy(z, hs, sizeof(double) * 2 * N);
     if (matched) memcpy(matched, hs + mp, sizeof(int) * N);
     if (corr) memcpy(corr, hs + zm, sizeof(double) * N);
@@ -214,6 +247,39 @@ int srukf_associate_held(srukf_ctx* c, double* z, int* matched, double* corr)
     if (c->phase < 2) { c->err = "associate before predict_measurement"; return SRUKF_ERR_SEQUENCE; }
     if (!c->frame_valid || !c->d_image) { c->err = "associate_held: no frame held"; return SRUKF_ERR_SEQUENCE; }
     return associate_frame(c, nullptr, z, matched, corr);
+}
+
+// srukf_associate / srukf_associate_held with the score map kept (srukf_unique.hip): the same phase rule and the same launches, k_associate_checked
+// in k_associate's place, one export, one wait.  matchPatch evolves identically whichever call a frame uses
+int srukf_associate_checked(srukf_ctx* c, const unsigned char* gray, const srukf_match_params* params, double* z, int* matched, double* corr, double* corr2, double* z2, int* flags)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    srukf_match_params mp = { 0.8, 0.9, 4, 0 };
+    if (params) mp = *params;
+    if (!std::isfinite(mp.ratio) || mp.ratio <= 0.0) { c->err = "associate_checked: ratio must be finite and positive"; return SRUKF_ERR_BAD_ARG; }
+    if (mp.exclusion < 1 || mp.exclusion > 20) { c->err = "associate_checked: exclusion outside [1, 20]"; return SRUKF_ERR_BAD_ARG; }
+    if (!std::isfinite(mp.corr_threshold)) { c->err = "associate_checked: corr_threshold is not finite"; return SRUKF_ERR_BAD_ARG; }
+    if (c->phase < 2) { c->err = "associate before predict_measurement"; return SRUKF_ERR_SEQUENCE; }
+    if (!gray && (!c->frame_valid || !c->d_image)) { c->err = "associate_checked: no frame held"; return SRUKF_ERR_SEQUENCE; }
+    return associate_frame(c, gray, z, matched, corr, &mp, corr2, z2, flags);
+}
+
+// the score map the last srukf_associate_checked left for landmark k: out[wx * wy] row-major, (x0, y0) = the pixel of the window's top-left candidate centre
+int srukf_get_match_scores(srukf_ctx* c, int k, double out[441], int* wx, int* wy, int* x0, int* y0)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    if (!c->match_valid || !c->match_scores) { c->err = "get_match_scores: no checked association since the last map change or reset"; return SRUKF_ERR_SEQUENCE; }
+    if (k < 0 || k >= c->d.N) return SRUKF_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int stride = srukf_match_score_stride();
+    std::vector<double> buf(stride);
+    HIPCHK(c, hipMemcpy(buf.data(), c->match_scores + (size_t)k * stride, sizeof(double) * stride, hipMemcpyDeviceToHost));
+    const int w = (int)buf[441], hgt = (int)buf[442];
+    if (w < 0 || hgt < 0 || w * hgt > 441) { c->err = "get_match_scores: corrupt window"; return SRUKF_ERR_HIP; }
+    if (out) memcpy(out, buf.data(), sizeof(double) * (size_t)(w * hgt));
+    if (wx) *wx = w; if (wy) *wy = hgt; if (x0) *x0 = (int)buf[443]; if (y0) *y0 = (int)buf[444];
+    return SRUKF_OK;
 }
 
 // integrateFeaturesInformation, numeric part (SLAM.cpp:826-871): K new landmarks at the distorted pixels uv[K][2] are

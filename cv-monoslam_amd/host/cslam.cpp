@@ -54,6 +54,7 @@ void CSLAM::initializeParameters()
     m_keyPoints.clear(); m_loopPointID.clear(); m_loopPointCounter = 0; m_nFilters = 0; firstDetect_ = true; runningCount_ = 0;
     mapStore.clear(); relinkMap();
     m_nArchiveMatches = m_nArchiveRejected = m_nArchiveReacquired = 0;
+    m_nAmbiguous = m_nAmbiguousTotal = 0; m_ambiguousID.clear();
     archiveMirror_.clear(); archiveVerdict_.clear(); reacquire_.clear(); reacquired_.clear(); frameHeld_ = false; m_archiveLog.clear();
 }
 
@@ -136,7 +137,9 @@ bool CSLAM::setFeatureAppearance(int id, const unsigned char* patch, const doubl
 bool CSLAM::dataAssociationOnDevice(const unsigned char* gray)
 {
     const int N = m_nMapFeatures;
+    clearAmbiguity();
     if (!ctx_ || N == 0) return true;
+    if (rejectAmbiguousMatches || subpixelMatches) { if (!associateChecked(gray)) return false; frameHeld_ = true; return true; }
     std::vector<double> z(2 * (size_t)N); std::vector<int> m(N);
     if (!check(srukf_associate(ctx_, gray, z.data(), m.data(), nullptr))) return false;
     frameHeld_ = true;
@@ -152,7 +155,9 @@ bool CSLAM::dataAssociationOnDevice(const unsigned char* gray)
 bool CSLAM::dataAssociationOnDeviceHeld()
 {
     const int N = m_nMapFeatures;
+    clearAmbiguity();
     if (!ctx_ || N == 0) return true;
+    if (rejectAmbiguousMatches || subpixelMatches) return associateChecked(nullptr);
     std::vector<double> z(2 * (size_t)N); std::vector<int> m(N);
     if (!check(srukf_associate_held(ctx_, z.data(), m.data(), nullptr))) return false;
     m_nMatches = 0;
@@ -160,6 +165,34 @@ bool CSLAM::dataAssociationOnDeviceHeld()
         map[k].isMatching = m[k] != 0;
         if (m[k]) { map[k].matchLocation.x = z[2 * k]; map[k].matchLocation.y = z[2 * k + 1]; m_nMatches++; }
     }
+    return true;
+}
+
+// dataAssociationOnDevice / dataAssociationOnDeviceHeld with rejectAmbiguousMatches or subpixelMatches on (srukf_associate_checked; gray == NULL: the
+// held frame).  A vetoed landmark is simply not matched this frame; with only subpixelMatches on the ratio is 2.0, which never vetoes
+// every association through the facade starts from "nothing vetoed": a frame run with the switches off leaves no flag of an earlier frame behind
+void CSLAM::clearAmbiguity()
+{
+    m_nAmbiguous = 0; m_ambiguousID.clear();
+    for (PointsMap& pm : mapStore) pm.isAmbiguous = false;
+}
+
+bool CSLAM::associateChecked(const unsigned char* gray)
+{
+    const int N = m_nMapFeatures;
+    srukf_match_params mp = { 0.8, rejectAmbiguousMatches ? AMBIGUITY_RATIO : 2.0, AMBIGUITY_EXCLUSION, subpixelMatches ? 1 : 0 };
+    std::vector<double> z(2 * (size_t)N), corr(N), corr2(N), z2(2 * (size_t)N); std::vector<int> m(N), fl(N);
+    if (!check(srukf_associate_checked(ctx_, gray, &mp, z.data(), m.data(), corr.data(), corr2.data(), z2.data(), fl.data()))) return false;
+    m_nMatches = 0;
+    for (int k = 0; k < N; k++) {                                                                               // 1989-2000
+        map[k].isMatching = m[k] != 0;
+        map[k].isAmbiguous = (fl[k] & 2) != 0;
+        map[k].corr = corr[k]; map[k].corr2 = corr2[k];
+        map[k].rivalLocation.x = z2[2 * k]; map[k].rivalLocation.y = z2[2 * k + 1];
+        if (m[k]) { map[k].matchLocation.x = z[2 * k]; map[k].matchLocation.y = z[2 * k + 1]; m_nMatches++; }
+        if (map[k].isAmbiguous) { m_nAmbiguous++; m_ambiguousID.push_back(map[k].ID); }
+    }
+    m_nAmbiguousTotal += m_nAmbiguous;
     return true;
 }
 

@@ -46,6 +46,11 @@ struct PointsMap {
     int     nMatchTimes = 0;
     Point2d predictLocation;
     Point2d matchLocation;
+    bool    isAmbiguous = false;      // the last association through the facade (dataAssociationOnDevice / ...Held) vetoed this landmark's match: a second correlation
+                                      // peak as good as the best (CSLAM::rejectAmbiguousMatches).  Cleared by every such association; a host-installed association
+                                      // that does not call them leaves it as it was
+    double  corr = 0, corr2 = 0;      // best and second-peak normalised cross correlation of the last association that ran with a switch on (not cleared otherwise)
+    Point2d rivalLocation;            // where that second peak sat ((0, 0) without one)
     double  Si[4] = {0, 0, 0, 0};     // 2x2 upper-triangular sqrt innovation covariance
     Point2d initPixel;
     Point3d xyz;                      // Cartesian mean                                  (SLAM.h:64)
@@ -133,6 +138,19 @@ public:
     bool dataAssociationOnDevice(const unsigned char* gray);
     // the same on the frame the handle holds (after loadPictures): srukf_associate_held, no upload
     bool dataAssociationOnDeviceHeld();
+    // ---- ambiguity veto and sub-pixel matches (opt-in).  With either switch on, the two calls above go through srukf_associate_checked, which keeps
+    //      every candidate's correlation.  rejectAmbiguousMatches: a landmark whose second peak (a local maximum more than AMBIGUITY_EXCLUSION pixels, Chebyshev,
+    //      from the best) reaches AMBIGUITY_RATIO times the best is not matched this frame: isMatching = false, isAmbiguous = true, not in m_nMatches.
+    //      KalmanUpdate therefore does not count it in nMatchTimes, and the reference's own deletion policy (nPredictTimes > 2 nMatchTimes with >= 10 predictions,
+    //      updateFeaturesInformation) retires a landmark that stays ambiguous.  subpixelMatches: matchLocation = the integer peak + the offset of the parabola
+    //      through its 4-neighbours, WITHOUT the fraction of the prediction the reference adds (1991-1992); alone, it passes ratio 2.0 (no veto).
+    //      The defaults 0.9 and 4 are reasoned, not tuned (4 = half the template's half-width).  With both switches off none of this runs
+    bool   rejectAmbiguousMatches = false;
+    double AMBIGUITY_RATIO = 0.9;
+    int    AMBIGUITY_EXCLUSION = 4;
+    bool   subpixelMatches = false;
+    int    m_nAmbiguous = 0, m_nAmbiguousTotal = 0;            // landmarks vetoed in this frame's association / since initializeParameters
+    std::vector<int> m_ambiguousID;                            // their IDs, in state order at the time of the association (later deletions do not touch the list)
 
     // ---- colour-frame intake and the 2-D feature overlay.  SLAM() calls none of them by itself ------------------------------------
     // loadPictures (SLAM.cpp:529-543): bgr = the image_h x image_w x 3 colour frame (B, G, R interleaved, as cvLoadImage / cvQueryFrame deliver it) goes to the
@@ -267,6 +285,8 @@ public:
 private:
     bool redirection();
     bool addFeaturesOnDevice();
+    bool associateChecked(const unsigned char* gray);
+    void clearAmbiguity();
     bool recordFeature(FeatureInfo& fi, int k);
     bool reinsertLoops();
     bool reinsertEntries(const std::vector<int>& take, std::vector<int>& ids, std::vector<double>& x6s, std::vector<double>& srs);

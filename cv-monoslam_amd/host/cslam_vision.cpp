@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -19,6 +19,9 @@
 //   (dataAssociationOnDeviceHeld).  The conversion keeps such a frame byte for byte (the weights sum to 2^14), so the output equals the default run's.
 // overlay=<file>: after the last frame, CSLAM::display2DFeatureModel's bytes (H x W x 3, B G R) go to <file> and the rows they were drawn from to <file>.in:
 //   per map node "h.x h.y Si00 Si01 Si10 Si11 z.x z.y matched" (%a).  Nothing else changes.
+// unique=<ratio>[,<exclusion>]: CSLAM::rejectAmbiguousMatches on (AMBIGUITY_RATIO = ratio, AMBIGUITY_EXCLUSION = exclusion, default 4).  Adds, and
+//   only with it, an "ambiguous <n> <IDs...>" line per frame: the landmarks this frame's association vetoed.
+// subpix=1: CSLAM::subpixelMatches on.
 // warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
 // Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
 #include <cstdio>
@@ -30,7 +33,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -39,12 +42,15 @@ int main(int argc, char** argv)
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
     int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay;
+    bool unique = false, subpix = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
     for (int a = 3; a < argc; a++)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
         else if (!strncmp(argv[a], "archive=", 8)) { archiveCap = atoi(argv[a] + 8); loops = true; }
         else if (!strncmp(argv[a], "ransac=", 7)) { ransac = true; ransacThr = atof(argv[a] + 7); }
         else if (!strncmp(argv[a], "colour=", 7)) colour = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "overlay=", 8)) overlay = argv[a] + 8;
+        else if (!strncmp(argv[a], "unique=", 7)) { unique = true; uniqueRatio = atof(argv[a] + 7); const char* cm = strchr(argv[a] + 7, ','); if (cm) uniqueExcl = atoi(cm + 1); }
+        else if (!strncmp(argv[a], "subpix=", 7)) subpix = atoi(argv[a] + 7) != 0;
     if (warmup) {
         monoslam::CSLAM w;
         w.m_params.image_w = W; w.m_params.image_h = H; w.MIN_STEP_X = w.MIN_STEP_Y = 0.0;
@@ -63,6 +69,8 @@ int main(int argc, char** argv)
     SLAM.reinsertLoopPoints = loops;
     if (archiveCap > 0) { SLAM.searchArchivedLandmarks = true; SLAM.archiveSearchHalfCap = archiveCap; }
     if (ransac) { SLAM.isUseRANSAC = true; SLAM.THRESHOLD_RANSAC = ransacThr; }
+    if (unique) { SLAM.rejectAmbiguousMatches = true; SLAM.AMBIGUITY_RATIO = uniqueRatio; SLAM.AMBIGUITY_EXCLUSION = uniqueExcl; }
+    SLAM.subpixelMatches = subpix;
     const unsigned char* cur = nullptr;
     std::vector<unsigned char> bgr(colour ? (size_t)3 * W * H : 0);
     SLAM.dataAssociation = [&](monoslam::CSLAM& s) {                                         // loadPictures + dataAssociation (SLAM.cpp:95-97)
@@ -113,6 +121,11 @@ int main(int argc, char** argv)
                 printf("\n");
             }
             printf("reacquired %d\n", SLAM.m_nArchiveReacquired - reacquiredBefore);
+        }
+        if (unique) {
+            printf("ambiguous %d", SLAM.m_nAmbiguous);
+            for (int id : SLAM.m_ambiguousID) printf(" %d", id);
+            printf("\n");
         }
         if (ransac) printf("ransac low %d high %d\n", SLAM.m_nLowInliers, SLAM.m_nHighInliers);
         printf("init"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %.17g %.17g", m->initPixel.x, m->initPixel.y); printf("\n");

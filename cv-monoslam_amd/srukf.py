@@ -30,6 +30,7 @@ EXPORTS = [
     "srukf_get_landmarks_display", "srukf_get_frame_view_display",
     "srukf_set_frame_bgr", "srukf_associate_held", "srukf_render_overlay",
     "srukf_archive_set", "srukf_archive_count", "srukf_archive_get_template", "srukf_archive_search",
+    "srukf_associate_checked", "srukf_get_match_scores",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -68,6 +69,11 @@ class DetectParams(C.Structure):
 class ArchiveParams(C.Structure):
     """struct srukf_archive_params."""
     _fields_ = [("half_cap", C.c_int), ("corr_threshold", C.c_double), ("chi2", C.c_double)]
+
+
+class MatchParams(C.Structure):
+    """struct srukf_match_params."""
+    _fields_ = [("corr_threshold", C.c_double), ("ratio", C.c_double), ("exclusion", C.c_int), ("subpixel", C.c_int)]
 
 
 class SrukfError(RuntimeError):
@@ -149,6 +155,9 @@ def load_library(path=None):
         L.srukf_archive_count.argtypes = [C.c_void_p]
         L.srukf_archive_get_template.argtypes = [C.c_void_p, C.c_int, _bp]
         L.srukf_archive_search.argtypes = [C.c_void_p, _bp, C.POINTER(ArchiveParams), _dp, _dp, _ip, _dp, _ip, _dp]
+    if hasattr(L, "srukf_associate_checked"):          # (idem: ambiguity veto, sub-pixel matches)
+        L.srukf_associate_checked.argtypes = [C.c_void_p, _bp, C.POINTER(MatchParams), _dp, _ip, _dp, _dp, _dp, _ip]
+        L.srukf_get_match_scores.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _ip, _ip, _ip]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -369,6 +378,30 @@ class Filter:
         z, m, cr = np.zeros(2 * self.N), np.zeros(self.N, dtype=np.int32), np.zeros(self.N)
         self._chk(self._lib.srukf_associate_held(self._h, _d(z), _i(m), _d(cr)))
         return z, m, cr
+
+    def associate_checked(self, gray=None, corr_threshold=0.8, ratio=0.9, exclusion=4, subpixel=False):
+        """associate() (gray = None: associate_held()) with the score map kept (srukf_associate_checked): a match whose second peak reaches ratio * the best
+        is vetoed, subpixel=True refines the best peak by the parabola through its 4-neighbours.  Returns a dict of arrays: z[2N], matched[N], corr[N],
+        corr2[N], z2[2N], flags[N] (bit 0 raw, bit 1 ambiguous, bit 2 refined)."""
+        N = self.N
+        g = None
+        if gray is not None:
+            gray = np.ascontiguousarray(gray, dtype=np.uint8)
+            assert gray.shape == (int(self.params.image_h), int(self.params.image_w))
+            g = gray.ctypes.data_as(C.POINTER(C.c_ubyte))
+        mp = MatchParams(float(corr_threshold), float(ratio), int(exclusion), int(bool(subpixel)))
+        out = dict(z=np.zeros(2 * N), matched=np.zeros(N, dtype=np.int32), corr=np.zeros(N), corr2=np.zeros(N), z2=np.zeros(2 * N),
+                   flags=np.zeros(N, dtype=np.int32))
+        self._chk(self._lib.srukf_associate_checked(self._h, g, C.byref(mp), _d(out["z"]), _i(out["matched"]), _d(out["corr"]), _d(out["corr2"]),
+                                                    _d(out["z2"]), _i(out["flags"])))
+        return out
+
+    def match_scores(self, k):
+        """(map[wy, wx], x0, y0): the score map the last associate_checked left for landmark k, (x0, y0) the pixel of its top-left candidate centre."""
+        buf = np.zeros(441)
+        wx, wy, x0, y0 = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self._lib.srukf_get_match_scores(self._h, int(k), _d(buf), C.byref(wx), C.byref(wy), C.byref(x0), C.byref(y0)))
+        return buf[:wx.value * wy.value].reshape(wy.value, wx.value).copy(), x0.value, y0.value
 
     def render_overlay(self, h, Si, z, matched):
         """display2DFeatureModel on the device (srukf_render_overlay): the held frame with the predicted cross, the matched cross and the chi-square

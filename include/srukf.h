@@ -288,6 +288,36 @@ int  srukf_set_frame_bgr(srukf_ctx* ctx, const unsigned char* bgr, unsigned char
 int  srukf_associate_held(srukf_ctx* ctx, double* z, int* matched, double* corr);
 int  srukf_render_overlay(srukf_ctx* ctx, const double* h, const double* Si, const double* z, const int* matched, unsigned char* out_bgr);
 
+/* ---- association that rejects ambiguous matches and refines matches to sub-pixel (opt-in) ----
+ * srukf_associate_checked: srukf_associate (gray != NULL) / srukf_associate_held (gray == NULL) with every candidate's score kept.  Same phase rule, same launches
+ *   (k_associate_checked in k_associate's place), one export and one wait: matchPatch evolves identically whichever call a frame uses.  Per landmark, with s[c] the
+ *   normalised cross correlation of candidate c (row-major over the wx x wy window; 0 for a candidate the border test or the chi-square gate skips):
+ *     best       the first maximum in row-major order, as srukf_associate finds it; corr = s[best]; raw = corr > corr_threshold;
+ *     rival      (only when raw) a candidate with Chebyshev distance > exclusion from best, s > 0 and s >= every neighbour of the window at Chebyshev distance 1
+ *                (plateaus count; gated neighbours count with their 0); corr2 = the largest rival score, first in row-major order among equals, z2 = its location
+ *                by the reference's formula (1991-1992); both 0 without a rival;
+ *     ambiguous  raw && corr2 >= ratio * corr (a ratio > 1 never vetoes: corr2 <= corr);
+ *     flags[k]   bit 0 raw, bit 1 ambiguous, bit 2 sub-pixel refinement applied;  matched[k] = raw && !ambiguous;
+ *     z[k]       the best's location whenever raw (also when vetoed), (0, 0) otherwise.  subpixel == 0: the reference's form, integer offset + h (1991-1992).
+ *                subpixel != 0: the integer centre ((int)h.x - half_x + bx, (int)h.y - half_y + by) plus (dx, dy) — this mode deliberately DROPS the reference's
+ *                + frac(h): a refinement on top of an arbitrary fractional offset means nothing.  dx = dy = 0 unless best is off the window's edge and its four
+ *                4-neighbours all score > 0 (then bit 2): den = (sL - 2 s0) + sR, dx = den < 0 ? (0.5 (sL - sR)) / den : 0, clamped to [-0.5, 0.5]; dy likewise
+ *                from the upper and lower neighbours.
+ *   A landmark that is not visible or has no appearance record gets all outputs zero.  params == NULL: { 0.8, 0.9, 4, 0 }.  Any output pointer may be NULL.
+ *   SRUKF_ERR_BAD_ARG: ratio not finite or <= 0, exclusion outside [1, 20], corr_threshold not finite.  SRUKF_ERR_SEQUENCE: as srukf_associate / _held.
+ * srukf_get_match_scores: the map the last srukf_associate_checked left for landmark k: out[wx * wy] row-major, (x0, y0) the pixel of the window's top-left
+ *   candidate centre (wx = wy = 0 for a landmark that was not searched).  SRUKF_ERR_SEQUENCE when there is none (no checked call yet, or a map change or
+ *   srukf_reset since). */
+typedef struct srukf_match_params {
+    double corr_threshold;    /* THRESHOLD_MATCH_PATCH 0.8                                                    SLAM.cpp:1989 */
+    double ratio;             /* 0.9: a second peak within 10 % of the best vetoes the match */
+    int    exclusion;         /* 4: half the template's half-width — nearer maxima share most of their 289 pixels with the best's patch */
+    int    subpixel;          /* 0 */
+} srukf_match_params;
+int  srukf_associate_checked(srukf_ctx* ctx, const unsigned char* gray, const srukf_match_params* params,
+                             double* z, int* matched, double* corr, double* corr2, double* z2, int* flags);
+int  srukf_get_match_scores(srukf_ctx* ctx, int k, double out[441], int* wx, int* wy, int* x0, int* y0);
+
 /* ---- loop points: archived landmarks put back into the filter (the redirection archive, SLAM.cpp:1357-1378, 2516-2532; integrateFeaturesInformation's
  * isLoop branch, 948-1015) ----
  * srukf_get_landmark_record: what an archived landmark takes along, in one device round trip.  X6 = rows 6k .. 6k+5 of X; S66 = the upper Cholesky
