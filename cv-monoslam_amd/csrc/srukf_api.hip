@@ -276,8 +276,6 @@ int srukf_create(srukf_ctx** out, int N, const srukf_params* p, int device, void
     srukf_ctx* c = new srukf_ctx();
     c->device = device; c->p = *p;
     if (!g_dbg_graphs) c->use_graph = false;                 // eager launches (profilers): srukf_debug_set(0, "graphs", 0)
-    memset(c->prof_ms, 0, sizeof c->prof_ms); memset(c->prof_n, 0, sizeof c->prof_n);
-    memset(c->prof_flops, 0, sizeof c->prof_flops); memset(c->prof_bytes, 0, sizeof c->prof_bytes);
     if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
     else {
         if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { g_create_error = "hipStreamCreate failed"; delete c; return SRUKF_ERR_HIP; }
@@ -366,13 +364,46 @@ int srukf_create(srukf_ctx** out, int N, const srukf_params* p, int device, void
     return SRUKF_OK;
 }
 
+}  // extern "C"
+
+// srukf_destroy's two halves, one per scope.  Which device buffers a scope owns is written beside its members (each_device_buffer, srukf_ctx.h); what is listed here
+// is only what is not a pool allocation.  The caller has synchronised the filter's stream and the two side streams.
+static void map_scope_free(srukf_map_scope& m, hipStream_t st)
+{
+    drop_graphs(&m);
+    m.each_device_buffer([st](void* b) { if (b) srukf_dfree_on(b, st); });
+    ransac_scratch_free(m.ransac, st);
+    gmw_plan_destroy(m.gplan, st);
+    gmw_plan_destroy(m.gplan_red, st);
+    if (m.side) { hipStreamSynchronize(m.side); hipStreamDestroy(m.side); hipEventDestroy(m.ev_fork); hipEventDestroy(m.ev_join); }
+    if (m.ck_stream) { hipStreamSynchronize(m.ck_stream); hipStreamDestroy(m.ck_stream); hipEventDestroy(m.ck_e1); hipEventDestroy(m.ck_e2); if (m.ck_e3) hipEventDestroy(m.ck_e3); }
+    if (m.hstage) {
+        // keep ONE pinned staging buffer for the next context (pinning 16 MB costs milliseconds; map changes rebuild contexts)
+        if (!g_spare_stage || g_spare_stage_bytes < m.hstage_bytes) { if (g_spare_stage) hipHostFree(g_spare_stage); g_spare_stage = m.hstage; g_spare_stage_bytes = m.hstage_bytes; }
+        else hipHostFree(m.hstage);
+    }
+    if (m.hfs) hipHostFree(m.hfs);
+    if (m.hview) hipHostFree(m.hview);
+}
+
+// (a retired context owns of this scope only what it allocated there itself: a frame buffer — never the stream, a list or a spare staging area)
+static void handle_scope_free(srukf_handle_scope& h)
+{
+    h.each_device_buffer([&h](void* b) { if (b) srukf_dfree_on(b, h.stream); });
+    det_scratch_free(h.det, h.stream);
+    archive_free(h.archive, h.stream);
+    if (h.spare_stage) hipHostFree(h.spare_stage);
+    if (h.own_stream && h.stream) { hipStreamSynchronize(h.stream); hipStreamDestroy(h.stream); }
+}
+
+extern "C" {
+
 int srukf_destroy(srukf_ctx* c)
 {
     if (!c) return SRUKF_OK;
     hipSetDevice(c->device);
     for (srukf_ctx* r : c->retired) srukf_destroy(r);            // (they launch on this handle's stream: before it goes)
     c->retired.clear();
-    if (c->spare_stage) { hipHostFree(c->spare_stage); c->spare_stage = nullptr; c->spare_stage_bytes = 0; }
     batch_plan_forget(c);
     if (c->stream) hipStreamSynchronize(c->stream);
     // the side streams too, BEFORE any buffer goes back to the pool: the step-wise fast path returns as soon as the tail raises its pinned flag and has by then queued
@@ -380,32 +411,8 @@ int srukf_destroy(srukf_ctx* c)
     if (c->ck_stream) hipStreamSynchronize(c->ck_stream);
     if (c->side) hipStreamSynchronize(c->side);
     prof_collect(c);
-    if (c->graph_exec) hipGraphExecDestroy(c->graph_exec);
-    if (c->graph) hipGraphDestroy(c->graph);
-    if (c->graph8_exec) hipGraphExecDestroy(c->graph8_exec);
-    if (c->graph8) hipGraphDestroy(c->graph8);
-    if (c->graphN_exec) hipGraphExecDestroy(c->graphN_exec);
-    if (c->graphN) hipGraphDestroy(c->graphN);
-    void* bufs[] = { c->X, c->S, c->G, c->Gbak, c->Wf, c->sigR, c->Cmat, c->Z, c->DZ, c->Ut, c->h /* + Si, vis */, c->PxyR, c->D,
-                     c->zcur /* + mcur */, c->odocur, c->small, c->theta, c->fs, c->odo_seq, c->z_seq, c->m_seq, c->pan[0], c->pan[1], c->mpart, c->dxp, c->syrk_tiles, c->pxy_tiles, c->syrk_head_tiles,
-                     c->perm, c->iperm, c->Sdis, c->ckS, c->ckX, c->ckS2, c->ckX2, c->odo_step, c->export_cnt, c->red_perm, c->red_iperm, c->gdiag, c->red_syrk_tiles, c->syrk_head_tiles_b, c->red_head0_tiles, c->split_fold_list, c->shadowA, c->Utp, c->P1, c->pxy2_tiles, c->nskip, c->slabW, c->slabL, c->gsW, c->gsL, c->S32, c->X32, c->U32, c->mx_part, c->mx_tasks, c->mx_tiles, c->fold_sync, c->dxk, c->A32, c->mxr_part, c->mxr_tasks, c->mxr_tiles, c->mxr_f64_tiles, c->mxr_xt, c->app_patch, c->app_tmpl, c->d_image, c->appR, c->appT, c->appPx, c->corr, c->has_app, c->disp, c->d_bgr, c->d_ovl, c->ov_in, c->ov_rec, c->match_res, c->match_scores };
-    for (void* b : bufs) if (b) srukf_dfree_on(b, c->stream);
-    det_scratch_free(c->det, c->stream);
-    ransac_scratch_free(c->ransac, c->stream);
-    archive_free(c->archive, c->stream);
-    gmw_plan_destroy(c->gplan, c->stream);
-    gmw_plan_destroy(c->gplan_red, c->stream);
-    if (c->side) { hipStreamSynchronize(c->side); hipStreamDestroy(c->side); hipEventDestroy(c->ev_fork); hipEventDestroy(c->ev_join); }
-    if (c->ck_stream) { hipStreamSynchronize(c->ck_stream); hipStreamDestroy(c->ck_stream); hipEventDestroy(c->ck_e1); hipEventDestroy(c->ck_e2); if (c->ck_e3) hipEventDestroy(c->ck_e3); }
-    if (c->own_stream && c->stream) hipStreamSynchronize(c->stream);
-    if (c->hstage) {
-        // keep ONE pinned staging buffer for the next context (pinning 16 MB costs milliseconds; map changes rebuild contexts)
-        if (!g_spare_stage || g_spare_stage_bytes < c->hstage_bytes) { if (g_spare_stage) hipHostFree(g_spare_stage); g_spare_stage = c->hstage; g_spare_stage_bytes = c->hstage_bytes; }
-        else hipHostFree(c->hstage);
-    }
-    if (c->hfs) hipHostFree(c->hfs);
-    if (c->hview) hipHostFree(c->hview);
-    if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
+    map_scope_free(*c, c->stream);
+    handle_scope_free(*c);
     delete c;
     return SRUKF_OK;
 }
@@ -414,13 +421,15 @@ int srukf_destroy(srukf_ctx* c)
 
 namespace srukf_impl {
 
-// A context the handle outgrew at a map change, kept for the next time the map has that size.  Everything of it that depends on the STATE is rebuilt by whoever revives
-// it (srukf_reset here; the caller's factorisation, srukf_set_storage and update_null_set afterwards); what depends only on N, the device and the parameters — buffers,
-// plans, tile tables, pinned areas, side streams — is what it is kept for.
+// A context the handle outgrew at a map change, kept for the next time the map has that size.  Everything of its map-size scope that depends on the STATE is rebuilt
+// by whoever revives it (srukf_reset here; the caller's factorisation, srukf_set_storage and update_null_set afterwards).
 void ctx_retire(srukf_ctx* handle, srukf_ctx* old)
 {
     drop_graphs(old);
-    old->own_stream = false;
+    // The factorisation of this context's next map change runs on it BEFORE it is adopted (run_gmw, read_fs: debug_starve, split_off and dbg.split_record are read
+    // there), under the switches its handle has now.  That is what the whole-struct swap of earlier versions left behind, kept as it was: a context created new
+    // runs that factorisation under the defaults.
+    static_cast<srukf_switches&>(*old) = *handle;
     // its pinned staging area goes to the handle: the next context this handle creates or revives takes it (srukf_create's hipHostMalloc of np^2 doubles was 2.5 of the
     // 3.5 ms a map change to a size not seen before cost)
     if (old->hstage) {
@@ -440,27 +449,18 @@ void ctx_retire(srukf_ctx* handle, srukf_ctx* old)
     while (handle->retired.size() > keep) { srukf_destroy(handle->retired.front()); handle->retired.erase(handle->retired.begin()); }
 }
 
+// a new life for a retired context: the flags and counters of the former one go in one assignment (srukf_life); the device-side leftovers are listed
 static int ctx_revive(srukf_ctx* r)
 {
     if (r->ck_stream) HIPCHK(r, hipStreamSynchronize(r->ck_stream));
     if (r->side) HIPCHK(r, hipStreamSynchronize(r->side));
-    r->ck_pending = false; r->ck3_inflight = false; r->ck_valid = false;
+    static_cast<srukf_life&>(*r) = srukf_life{};                 // (storage too, as in a fresh context: the caller sets the handle's mode; S32 / X32 / A32 stay allocated)
     if (r->odo_seq) { srukf_dfree_on(r->odo_seq, r->stream); srukf_dfree_on(r->z_seq, r->stream); srukf_dfree_on(r->m_seq, r->stream); r->odo_seq = nullptr; r->z_seq = nullptr; r->m_seq = nullptr; }
-    r->seqF = 0;
-    r->storage = SRUKF_STORAGE_F64;                              // (as a fresh context: the caller sets the handle's mode; S32 / X32 / A32 stay allocated)
-    r->K_new = 0; r->dx_pending = false; r->dx_lm = false; r->xr1_pending = false;
     if (r->fold_sync) HIPCHK(r, hipMemsetAsync(r->fold_sync, 0, sizeof(unsigned int) * (size_t)srukf_fold_words(r->d.mp / 64, r->d.np / 64), r->stream));
-    r->null_canonical = false; r->tail_ok = false;
-    r->clamp_frame_host = r->clamp_row_host = -1;
-    r->next_odo_valid = false; r->fs_seq_step = false; r->last_update_sequential = false;
-    r->step_export_attached = false; r->step_export = StepExport{}; r->mirror_next = false; r->meas_seq = 0;
-    r->view_auto = false; r->view_unused = 0; r->view_hits = 0;
     ransac_scratch_free(r->ransac, r->stream);                   // (allocated again, zeroed, by the first call that needs it: nothing of the former life is read)
-    r->step_fast_frames = r->step_slow_frames = 0; r->exact_frames = 0;
-    r->profiling = false; r->pev.clear();
-    r->err.clear();
+    r->err.clear();                                              // (the text of the map change this context is obtained for: adopt_context)
     HIPCHK(r, hipMemsetAsync(r->fs, 0, sizeof(FrameScalars), r->stream));
-    return srukf_reset(r);                                       // step-path flags, X / S as srukf_create leaves them, frame scalars, null set off, graphs dropped
+    return srukf_reset(r);                                       // X / S as srukf_create leaves them, frame scalars, null set off
 }
 
 int ctx_obtain(srukf_ctx* handle, srukf_ctx** out, int N)

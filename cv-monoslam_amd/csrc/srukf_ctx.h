@@ -139,7 +139,7 @@ struct DetScratch {
     void *in = nullptr, *out = nullptr; size_t in_bytes = 0, out_bytes = 0;
 };
 
-// 1-point RANSAC (srukf_ransac.hip), allocated on the first call and sized by the context's N (it stays with its context through retire / revive, which frees it).
+// 1-point RANSAC (srukf_ransac.hip), allocated on the first call and sized by the context's N (map-size scope; a revive frees it).
 // Ut: k_pxy's product for the consensus; D / F: d_ij and the inlier flag of every pair (N x N); zin: z | matched; res: dist | inlier | votes | best.
 // X, S, odo, Cm, fs: a copy of the state, an odometry pair and where k_motion leaves its by-products (the fast path's consensus; srukf_repredict_measurement);
 // the rest: the slow path's predict half on that copy
@@ -150,104 +150,27 @@ struct RansacScratch {
 };
 
 // the archive searched by appearance (srukf_archive.hip): L records in the layouts of srukf_insert_landmarks (patch / tmpl with the strides of the map's appearance
-// records), rob = pose | P4 of the search in hand, out = h | Si | z | corr | xyz | visible | matched, hst = the same pinned, then pose | P4.  On the handle: it
-// survives map changes as the held frame does (adopt_context); srukf_reset and srukf_destroy drop it
+// records), rob = pose | P4 of the search in hand, out = h | Si | z | corr | xyz | visible | matched, hst = the same pinned, then pose | P4.  Handle scope;
+// srukf_reset and srukf_destroy drop it
 struct ArchiveState {
     int L = 0;
     double *X6 = nullptr, *S66 = nullptr, *R = nullptr, *t = nullptr, *px = nullptr, *rob = nullptr, *out = nullptr, *hst = nullptr;
     unsigned char *patch = nullptr, *tmpl = nullptr;
 };
 
-struct srukf_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    srukf_params p;
-    KDims d;
-    KWeights w;
-    // HBM buffers
-    double *X = nullptr, *S = nullptr, *G = nullptr, *Gbak = nullptr, *Wf = nullptr;
-    double *sigR = nullptr, *Cmat = nullptr, *Z = nullptr, *DZ = nullptr, *Ut = nullptr;
-    double *h = nullptr, *Si = nullptr, *PxyR = nullptr, *D = nullptr;
-    double *zcur = nullptr, *odocur = nullptr, *small = nullptr, *mpart = nullptr, *dxp = nullptr;
-    int *vis = nullptr, *mcur = nullptr;
-    unsigned long long* theta = nullptr;
-    bool dx_pending = false;               // k_gain left slice partials of dX that the next k_syrk must add to X
-    bool dx_lm = false;                    // ... as per-landmark shares in dxk (the gain fold of k_pxy2) instead of k_gain's slice partials in dxp
-    // gain fold (round 6: k_gain's work inside k_pxy2 in the staged replay's "fused tail" mode): its sync words (zero between frames), the per-landmark shares of the
-    // state update (N x np), how many tile workgroups read the robot columns of the permuted copy
-    unsigned int* fold_sync = nullptr; double* dxk = nullptr; int fold_robot_tiles = 0;
-    bool xr1_pending = false;              // replay path: the robot mean after the motion step waits in fs->Xr1 for the same launch
-    // NEED_REORDER (frames that follow a landmark addition): K_new = m_nFilters, permutation between the normal and the
-    // disordered layout (getPermutationMatrix, SLAM.cpp:1303-1334), disordered factor
-    int K_new = 0;
-    // data association (srukf_assoc.hip): per-landmark appearance records, allocated on first use
-    unsigned char *app_patch = nullptr, *app_tmpl = nullptr, *d_image = nullptr;
-    double *appR = nullptr, *appT = nullptr, *appPx = nullptr, *corr = nullptr;
-    int* has_app = nullptr;
-    bool frame_valid = false;              // d_image holds the caller's last frame (srukf_associate / srukf_detect_features / srukf_capture_appearance with a
-                                           // frame): handed over at map changes with the buffer (adopt_context), dropped by srukf_reset
-    // srukf_set_frame_bgr / srukf_render_overlay (srukf_overlay.hip): the held colour frame (W x H x 3, B G R) and the overlay's output, both padded to whole groups of
-    // four pixels, allocated on first use and handed over at map changes like d_image; bgr_valid: d_bgr is the colour of the held gray frame (a later call that brings
-    // a gray frame, srukf_reset and adopt_context's retired side clear it)
-    unsigned char *d_bgr = nullptr, *d_ovl = nullptr; bool bgr_valid = false;
-    // ... and what the overlay is drawn from, sized by the context's N (stays with its context): h | Si | z (8N doubles) | matched (N ints), the per-landmark records
-    double* ov_in = nullptr; void* ov_rec = nullptr;
-    // srukf_associate_checked (srukf_unique.hip), allocated on its first call and sized by the context's N: match_res = z | corr | corr2 | z2 | matched, flags (7N doubles,
-    // exported in one piece), match_scores = every landmark's score map (448 doubles each: map | wx wy x0 y0).  match_valid: the maps are the last checked call's
-    // (srukf_get_match_scores); a map change and srukf_reset drop both buffers (match_drop)
-    double *match_res = nullptr, *match_scores = nullptr; bool match_valid = false;
-    DetScratch det;                        // srukf_detect_features (handed over at map changes too)
-    RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
-    ArchiveState archive;                  // srukf_archive_set / srukf_archive_search (handed over at map changes)
-    // srukf_get_landmarks_display / srukf_get_frame_view_display: xyz (3N) | cov (9N) | axis (4N) | sigma (3N) | P4, pose (20) | rot (N ints).  A buffer of its own, sized
-    // by the context's N and allocated by the first call (not G: the next frame's pre-issued first launch may be in flight behind the update); it stays with its context
-    double* disp = nullptr;
-    int storage = SRUKF_STORAGE_F64;       // SRUKF_STORAGE_F32 / _F32_MIXED: X32 / S32 hold the inter-frame state
-    float *S32 = nullptr, *X32 = nullptr;
-    // SRUKF_STORAGE_F32_MIXED: S^T S - U U^T on the fp32 matrix pipe (srukf_mixed.hip)
-    float *U32 = nullptr; double* mx_part = nullptr; void *mx_tasks = nullptr, *mx_tiles = nullptr; int mx_ntasks = 0, mx_ntiles = 0;
-    // ... in the rank-aware form (round 6): the kept rows of S in permuted column order as float (the permuted copy's values are the stored floats), K <= r, only the
-    // macro tiles of the pivoted panels; task list / partials of that shape (mixed_red_ensure)
-    float* A32 = nullptr; double* mxr_part = nullptr; void *mxr_tasks = nullptr, *mxr_tiles = nullptr; int mxr_ntasks = 0, mxr_ntiles = 0, mxr_krows = 0, mxr_for_r = 0;
-    // ... and which 32 x 32 tiles of it are formed in FP64 after all (k_syrk over this list, behind the fp32 launch): the tile rows / columns that hold the robot block
-    // and the map's shared anchor (permuted positions r-4 .. r-1 and 0 .. 2).  The robot's pivots are its variance GIVEN the map — 2e-6 .. 9e-6 of its marginal variance
-    // in the benchmark scene, the z coordinate exactly null (scripts/pivot_ratio_probe.py) — and the regression that produces them has weight ~1 on the anchor the
-    // robot position was copied into: an fp32-formed entry there (relative error ~1e-7 .. 1e-6) is as large as the pivot itself.  Every other kept pivot is >= 0.1 of
-    // its marginal variance
-    int* mxr_f64_tiles = nullptr; int mxr_n_f64_tiles = 0;
-    // ... and the operands of the bf16-piece form of the product (k_split_bf3 / k_syrk_bf3): X^T = [kept rows of S | U^T]^T as three planes of bf16, [np columns][mxr_ktot]
-    unsigned short* mxr_xt = nullptr; size_t mxr_xt_stride = 0; int mxr_ktot = 0;
-    int *perm = nullptr, *iperm = nullptr;
-    double* Sdis = nullptr;
-    void* pan[2] = { nullptr, nullptr };   // GMW panel hand-off buffers (double-buffered), one launch per panel
-    GmwPlan gplan;                         // persistent GMW launch: panel buffers, sync block, task list
-    // rank-aware refactorisation (srukf_rank.hip): red_r > 0 = the n - red_r structurally null directions are not pivoted
-    int red_r = 0, red_Tp = 0;
-    int rank_aware = 1;                                // srukf_set_rank_aware
-    int *red_perm = nullptr, *red_iperm = nullptr;     // permuted position <-> state index, kept indices first
-    double* gdiag = nullptr;                           // diagonal of G in permuted order (the factorisation overwrites it)
-    double *shadowA = nullptr, *Utp = nullptr;         // replay form: kept rows of S / U^T in permuted column order (srukf_rank.hip)
-    double *slabW = nullptr, *slabL = nullptr;         // batched replay: two panels' slabs W and L = W / D (2 x 64 x np each: the K = 128 trailing update reads a pair)
-    // split form of the persistent factorisation (memory-tile sizes, a filter that has the GPU to itself): the slabs of every pivoted panel (gs_panels x 64 x np
-    // each), the side stream the tile launch runs on and the events that fork it off / join it to the filter's stream
-    double *gsW = nullptr, *gsL = nullptr; int gs_panels = 0;
-    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool split_off = false;                // a split-form pair of this context was abandoned (its two launches did not run side by side — e.g. the branches of a captured
-                                           // graph sharing a hardware queue): the context keeps to the memory-tile instance of k_gmw_persist (read_fs; srukf_debug_get "split_off")
-    double* P1 = nullptr; int* pxy2_tiles = nullptr; int n_pxy2_tiles = 0, pxy2_split_b0 = 0;   // "table" mode: k_pxy2's second K half, its tile list
-    int* nskip = nullptr; int ns_full = 0, ns_null = 0, ns_rows = 0;   // NullSkip lists (srukf_device.h): [dirs | nulls | rows] in one buffer
-    int* red_head0_tiles = nullptr; int n_red_head0_tiles = 0; // split fold: the k_syrk tiles that stay with the launch in front (block row 0, tile (1, 1)) ...
-    void* split_fold_list = nullptr; int n_split_fold = 0;     // ... and the grid of k_gmw_tiles_fold (forming jobs + tile workgroups, row by row: srukf_gmw_build_fold_list)
-    double red_head0_flop = 0.0;                               // flop of the tiles in red_head0_tiles (the rest of k_syrk's count moves to the persistent launch's line of the profile)
-    int* red_syrk_tiles = nullptr; int n_red_syrk_tiles = 0;   // k_syrk tiles of the kept rows (rows < 64 red_Tp) in permuted order: replay form without the owners' fold
-    double red_fac_flop = 0, red_own_flop = 0;         // algorithmic flop of the rank-aware persistent launch: factorisation / owners' tiles of S^T S - U U^T
-    GmwPlan gplan_red;                                 // tile list / sync block of the persistent launch with red_Tp pivoted panels
-    int shared_tenants = 2;                // SRUKF_GPU_SHARED: how many persistent launches share the GPU (each keeps to cus / tenants CUs; the gate admits that many)
-    int gmw_shared = 0;                    // 0: the filter has the GPU to itself; 1: shared with other filters — persistent launches of at most half the CUs behind
-                                           // the admission gate (k_gmw_gate); 2: one launch per panel (forced, or after an abandoned persistent launch)
+// ---- the context: who owns what across a map change ("who owns what across a map change") ----------------------
+// srukf_ctx = srukf_handle_scope + srukf_map_scope (which holds one srukf_life).  WHERE a member is declared says what a map change, a revive and srukf_destroy do
+// with it; adopt_context, ctx_revive and srukf_destroy hold no list of members, only the few exceptions, each with its reason.
+
+// The per-filter switches, a part of the handle scope with a name of its own for one reason: ctx_retire gives the retiring context a copy in one assignment (see there)
+struct srukf_switches {
+    int rank_aware = 1;                    // srukf_set_rank_aware
     int debug_allow_mixed = 0;             // srukf_debug_allow_mixed: the tolerance study runs the mixed mode below its epsilon floor on purpose
-    // Measurement / test switches of srukf_debug_set (all default to the product path); one struct, so that a rebuilt context (map change) inherits them in one assignment
+    int debug_starve = 0;                  // srukf_debug_starve_workers: persistent launches start without their workers (tests of the fallback)
+    bool split_off = false;                // a split-form pair of this filter was abandoned (its two launches did not run side by side — e.g. the branches of a captured
+                                           // graph sharing a hardware queue): it keeps to the memory-tile instance of k_gmw_persist (read_fs; srukf_debug_get "split_off")
+    bool use_graph = true;
+    // Measurement / test switches of srukf_debug_set (all default to the product path)
     struct DbgSwitches {
         int fused_motion = 2;              // "fused_motion": the replay's motion step — 0: its own launch (k_motion + k_project), 1: inside the projection launch
                                            // (k_project_motion), 2: "table" mode where the rank-aware tail allows it (replay_motion_mode)
@@ -280,83 +203,202 @@ struct srukf_ctx {
                                            // 1.6 x the fp32 pipe's (12.5 against 7.7 eps32 units over fixture g9).  Kept behind the switch, held to the same fixture
         int mixed_f64_robot = 1;           // "mixed_f64_robot": ... with the tiles of the robot block and of the shared anchor in FP64 (mxr_f64_tiles); 0: every kept tile from the fp32 pipe (study)
     } dbg;
+};
+
+// Handle scope: what stays at the caller's address through every map change.  A context built for another map size (ctx_obtain) carries a handle scope too: its own
+// defaults, on the handle's device / stream / parameters, never the owner of the stream; what it allocates there itself (ensure_image) it frees itself.
+struct srukf_handle_scope : srukf_switches {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    srukf_params p;
+    // Map changes rebuild the map-size scope behind the handle.  A rebuilt context used to be destroyed and the next one created from nothing — ~0.3 ms of
+    // allocations, plans and tile tables, 0.5 - 2.4 ms of frees (pinned host memory among them) per map change at N = 200, where the reference's map changes every
+    // few frames (SLAM.cpp:552-562, 2443-2460) and N only moves by +- 1.  The handle keeps the last few contexts it outgrew and revives one instead: ctx_obtain / ctx_retire
+    std::vector<srukf_ctx*> retired;
+    double* spare_stage = nullptr; size_t spare_stage_bytes = 0;   // pinned staging of the context retired last (retired contexts keep none: pinning 11.8 MB costs ~2.5 ms)
+    // profiling
+    bool profiling = false;
+    std::vector<ProfEvent> pev;
+    double prof_ms[KC_COUNT] = {}; long long prof_n[KC_COUNT] = {}; double prof_flops[KC_COUNT] = {}; double prof_bytes[KC_COUNT] = {};
+    // the frame the filter holds (same image size whatever the map's): d_image, gray (srukf_associate / srukf_detect_features / srukf_capture_appearance with a frame);
+    // d_bgr, its colour (srukf_set_frame_bgr: W x H x 3, B G R), and d_ovl, the overlay's output (srukf_render_overlay), both padded to whole groups of four pixels.
+    // All allocated on first use.  frame_valid: d_image holds the caller's last frame; bgr_valid: d_bgr is its colour (a later call that brings a gray frame clears
+    // it).  srukf_reset drops both flags
+    unsigned char *d_image = nullptr, *d_bgr = nullptr, *d_ovl = nullptr; bool frame_valid = false, bgr_valid = false;
+    DetScratch det;                        // srukf_detect_features
+    ArchiveState archive;                  // srukf_archive_set / srukf_archive_search
+    std::string err;
+    // the pool allocations among the members above (det and archive: det_scratch_free / archive_free).  A new buffer of this scope is added HERE
+    template <class F> void each_device_buffer(F f) const { void* b[] = { d_image, d_bgr, d_ovl }; for (void* q : b) f(q); }
+};
+
+// One life of a context — from srukf_create or ctx_revive to the map change that retires it: the flags and counters a revive sets back, by assigning a fresh one.
+// A member belongs here only if a revived context must find it at its initialiser; what survives a revive (spin_ok, step_seq, the mxr_* shape, ...) stays below
+struct srukf_life {
+    int storage = SRUKF_STORAGE_F64;       // SRUKF_STORAGE_F32 / _F32_MIXED: X32 / S32 hold the inter-frame state (a map change sets the handle's mode again; the buffers stay)
+    bool dx_pending = false;               // k_gain left slice partials of dX that the next k_syrk must add to X
+    bool dx_lm = false;                    // ... as per-landmark shares in dxk (the gain fold of k_pxy2) instead of k_gain's slice partials in dxp
+    bool xr1_pending = false;              // replay path: the robot mean after the motion step waits in fs->Xr1 for the same launch
+    // NEED_REORDER (frames that follow a landmark addition): K_new = m_nFilters, permutation between the normal and the
+    // disordered layout (getPermutationMatrix, SLAM.cpp:1303-1334), disordered factor
+    int K_new = 0;
     bool null_canonical = false;           // every structurally null row of S is exactly sqrt(EPSILON) e_k (update_null_set checks; true behind every rank-aware frame tail)
     bool tail_ok = false;                  // "fused tail" mode is possible: directions 0 and 1 are kept rows (the Si factor names their Z rows: they are projected for every landmark, which
                                            // the frame tail only does for kept rows — a state where they are structurally null stays with k_project_table)
-    int debug_starve = 0;                  // srukf_debug_starve_workers: persistent launches start without their workers (tests of the fallback)
     int clamp_frame_host = -1, clamp_row_host = -1;   // what the last SRUKF_ERR_CLAMP_PENDING was about (srukf_clamp_info)
-    double *ckS = nullptr, *ckX = nullptr; // srukf_run_frames: state before the block of frames in flight (recovery from a theta-clamp frame)
-    int *syrk_tiles = nullptr, *pxy_tiles = nullptr;   // (by, bx) per workgroup, XCD-aware order
-    int *syrk_head_tiles = nullptr;                    // k_syrk tiles of the first srukf_gmw_head_rows() rows only (fused refactor)
-    int n_syrk_tiles = 0, n_pxy_tiles = 0, n_syrk_head_tiles = 0, n_syrk_head_crit = 0;
-    int* syrk_head_tiles_b = nullptr; int n_syrk_head_tiles_b = 0;      // the same tiles in the batched launch's order (k_syrk_b): one pair of tile columns per XCD, empty slots (-1) where a share is shorter
-    FrameScalars* fs = nullptr;
-    // staged sequence
-    int seqF = 0;
-    double *odo_seq = nullptr, *z_seq = nullptr;
-    int* m_seq = nullptr;
-    // pinned staging
-    double* hstage = nullptr; size_t hstage_bytes = 0;
-    FrameScalars* hfs = nullptr;
-    double* hmeas = nullptr;               // inside the hfs allocation, behind the robot view and the flag word
+    int seqF = 0;                          // frames of the staged sequence (odo_seq / z_seq / m_seq below)
     // state machine
     int phase = 0;   // 0 idle, 1 after predict_motion, 2 after predict_measurement
     bool frame_updated = false;            // the last call that touched the state was a srukf_update of the frame in hand (srukf_repredict_measurement may follow)
-    double next_odo[6] = { 0, 0, 0, 0, 0, 0 }; bool next_odo_valid = false;   // srukf_predict_motion_next: the pair the next srukf_predict_motion will bring
-    // Fast path of the step-wise API (step_* below): a frame of the staged replay's own launch sequence ("fused tail" mode) cut in two at the host's association step
-    double* odo_step = nullptr;            // device: (prev, cur, next) poses of the frame in flight — a three-pose "staged sequence" fs->odo_seq points at
-    double step_odo[6] = { 0, 0, 0, 0, 0, 0 };   // the pair srukf_predict_motion was called with (the fallback to the other path needs it again)
-    int step_seqF = 1;                     // 2: odo_step holds the next pose too (hint), the tail prepares and projects the next frame
+    bool next_odo_valid = false;           // srukf_predict_motion_next: next_odo is the pair the next srukf_predict_motion will bring
+    bool async_pending = false;
+    // the step-wise fast path (step_* below)
     bool step_fast = false;                // the frame in flight runs on the fast path
     bool step_uncommitted = false;         // ... and its motion step still waits beside the state (fs->Xr1, Cmat): state getters commit it first (k_commit_motion)
     bool step_chain = false;               // X, S, the permuted copy and the frame scalars are exactly what the last fast-path tail left: its constant rows stand
-    bool proj_valid = false; double proj_odo[6] = { 0, 0, 0, 0, 0, 0 };   // ... and that tail projected the frame with this odometry pair (Z, DZ, the table, fs->ctl)
+    bool proj_valid = false;               // ... and that tail projected the frame with the odometry pair proj_odo (Z, DZ, the table, fs->ctl)
     bool fs_seq_step = false;              // fs->odo_seq points at odo_step (srukf_run_frames_async points it back at the staged sequence)
     bool last_update_sequential = false;   // a host that updates in SRUKF_UPDATE_SEQUENTIAL mode never takes the fast path (decided at predict time)
-    // The copy for the NEXT frame is submitted by the update that ends this one, right behind its last launch (into the second pair of buffers; pair and event swap
-    // when the frame turns out clean): the next srukf_predict_motion then finds its checkpoint made (ck_valid) and submits its first launch at once
-    double *ckS2 = nullptr, *ckX2 = nullptr; hipEvent_t ck_e3 = nullptr; bool ck_valid = false;
+    bool ck_valid = false;                 // the next srukf_predict_motion finds its checkpoint made (ckS2 / ckX2)
     bool ck3_inflight = false;             // ... and until then the copy is in flight on ck_stream with nothing but ck_e3 to wait on (step_ck_join)
-    unsigned spin_ok = 0;                  // successful spin waits (step_wait_export queries the stream every 256th)
-    bool pre_issued = false; double pre_odo[6] = { 0, 0, 0, 0, 0, 0 };   // the NEXT frame's first launch (k_pxy2) went out behind this frame's tail, for this odometry pair
+    bool ck_pending = false;               // the copy of the state before the frame runs beside the frame's first launch (step_ck_join)
+    bool pre_issued = false;               // the NEXT frame's first launch (k_pxy2) went out behind this frame's tail, for the odometry pair pre_odo
     bool next_pose_pending = false;        // the next k_gain launch carries next_odo[3..5] as the sequence's third pose (no launch of its own)
-    bool setstep_done = false; double setstep_odo[6] = { 0, 0, 0, 0, 0, 0 };   // k_set_step for the announced next frame went out behind this frame's tail (poses: prev, cur)
-    hipStream_t ck_stream = nullptr; hipEvent_t ck_e1 = nullptr, ck_e2 = nullptr; bool ck_pending = false;   // the copy of the state before the frame runs BESIDE the frame's
-                                           // first launch on a stream of its own (it only has to be complete before k_gain touches S): step_ck_join
+    bool setstep_done = false;             // k_set_step for the announced next frame went out behind this frame's tail (poses: setstep_odo)
     unsigned long long meas_seq = 0;       // != 0: k_pxy2's statistics jobs mirror h | Si | visible into hstage and raise the flag word with this number (srukf_predict_measurement waits for it)
     bool step_export_attached = false;     // the last rank_expand carried step_export
-    int* export_cnt = nullptr;             // 64 x 64 ints (zero): first-level counters of the exporting launch (StepExport::cnt)
     StepExport step_export = {};           // dst != null: the next rank_expand is the step-wise fast path's and exports the frame's status + robot view itself
     bool mirror_next = false;              // the next seq_pxy is the step-wise fast path's: its MeasArgs carry the host mirror
-    unsigned long long step_seq = 0;       // sequence number of the step-wise fast path's exports: the host spins on a pinned word (behind the robot view) that receives it
-    double* hview = nullptr; size_t hview_doubles = 0;      // pinned: xyz (3N) | cov (9N) | X (n) of the state an update of the fast path left, when the host is known to ask for it
     bool view_auto = false; int view_unused = 0;   // the host called srukf_get_frame_view after its last update -> the following updates export the view with their status; three views nobody read end it
     int view_hits = 0;
     bool view_cached = false;              // *hview is the view of the CURRENT state (same lifetime as robot_cached)
     bool robot_cached = false;             // the 20 doubles behind *hfs hold P4 and the pose of the CURRENT state (fast path: fetched with the frame's status)
     bool f32_stale = false;                // fp32 storage: X32 / S32 (srukf_get_state_f32) are behind the rounded fp64 working copies (refreshed on demand)
     int step_fast_frames = 0, step_slow_frames = 0;   // srukf_debug_get "step_fast" / "step_slow"
-    double* spare_stage = nullptr; size_t spare_stage_bytes = 0;   // pinned staging of the context retired last (a handle's retired contexts keep none: pinning 11.8 MB costs ~2.5 ms)
+    int exact_frames = 0;                  // staged frames srukf_run_frames repeated on the exact column path (flagged: theta clamp, a skipped direction that is not null, an abandoned launch): "exact_frames"
+};
+
+// Map-size scope: everything sized by N or tied to one factor.  adopt_context swaps it between the handle and the context built for the new size, whole; a retired
+// context keeps it for the next time the map has that size (what depends only on N, the device and the parameters — buffers, plans, tile tables, pinned areas,
+// side streams — is what it is kept for), srukf_destroy frees it (map_scope_free, over the list at the end)
+struct srukf_map_scope : srukf_life {
+    KDims d;
+    KWeights w;
+    // HBM buffers
+    double *X = nullptr, *S = nullptr, *G = nullptr, *Gbak = nullptr, *Wf = nullptr;
+    double *sigR = nullptr, *Cmat = nullptr, *Z = nullptr, *DZ = nullptr, *Ut = nullptr;
+    double *h = nullptr, *Si = nullptr, *PxyR = nullptr, *D = nullptr;
+    double *zcur = nullptr, *odocur = nullptr, *small = nullptr, *mpart = nullptr, *dxp = nullptr;
+    int *vis = nullptr, *mcur = nullptr;
+    unsigned long long* theta = nullptr;
+    // gain fold (round 6: k_gain's work inside k_pxy2 in the staged replay's "fused tail" mode): its sync words (zero between frames), the per-landmark shares of the
+    // state update (N x np), how many tile workgroups read the robot columns of the permuted copy
+    unsigned int* fold_sync = nullptr; double* dxk = nullptr; int fold_robot_tiles = 0;
+    // data association (srukf_assoc.hip): per-landmark appearance records, allocated on first use
+    unsigned char *app_patch = nullptr, *app_tmpl = nullptr;
+    double *appR = nullptr, *appT = nullptr, *appPx = nullptr, *corr = nullptr;
+    int* has_app = nullptr;
+    // what the overlay is drawn from: h | Si | z (8N doubles) | matched (N ints), the per-landmark records
+    double* ov_in = nullptr; void* ov_rec = nullptr;
+    // srukf_associate_checked (srukf_unique.hip), allocated on its first call: match_res = z | corr | corr2 | z2 | matched, flags (7N doubles, exported in one piece),
+    // match_scores = every landmark's score map (448 doubles each: map | wx wy x0 y0).  match_valid: the maps are the last checked call's (srukf_get_match_scores);
+    // a map change and srukf_reset drop both buffers (match_drop)
+    double *match_res = nullptr, *match_scores = nullptr; bool match_valid = false;
+    RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
+    // srukf_get_landmarks_display / srukf_get_frame_view_display: xyz (3N) | cov (9N) | axis (4N) | sigma (3N) | P4, pose (20) | rot (N ints).  A buffer of its own,
+    // allocated by the first call (not G: the next frame's pre-issued first launch may be in flight behind the update)
+    double* disp = nullptr;
+    float *S32 = nullptr, *X32 = nullptr;  // storage != SRUKF_STORAGE_F64
+    // SRUKF_STORAGE_F32_MIXED: S^T S - U U^T on the fp32 matrix pipe (srukf_mixed.hip)
+    float *U32 = nullptr; double* mx_part = nullptr; void *mx_tasks = nullptr, *mx_tiles = nullptr; int mx_ntasks = 0, mx_ntiles = 0;
+    // ... in the rank-aware form (round 6): the kept rows of S in permuted column order as float (the permuted copy's values are the stored floats), K <= r, only the
+    // macro tiles of the pivoted panels; task list / partials of that shape (mixed_red_ensure)
+    float* A32 = nullptr; double* mxr_part = nullptr; void *mxr_tasks = nullptr, *mxr_tiles = nullptr; int mxr_ntasks = 0, mxr_ntiles = 0, mxr_krows = 0, mxr_for_r = 0;
+    // ... and which 32 x 32 tiles of it are formed in FP64 after all (k_syrk over this list, behind the fp32 launch): the tile rows / columns that hold the robot block
+    // and the map's shared anchor (permuted positions r-4 .. r-1 and 0 .. 2).  The robot's pivots are its variance GIVEN the map — 2e-6 .. 9e-6 of its marginal variance
+    // in the benchmark scene, the z coordinate exactly null (scripts/pivot_ratio_probe.py) — and the regression that produces them has weight ~1 on the anchor the
+    // robot position was copied into: an fp32-formed entry there (relative error ~1e-7 .. 1e-6) is as large as the pivot itself.  Every other kept pivot is >= 0.1 of
+    // its marginal variance
+    int* mxr_f64_tiles = nullptr; int mxr_n_f64_tiles = 0;
+    // ... and the operands of the bf16-piece form of the product (k_split_bf3 / k_syrk_bf3): X^T = [kept rows of S | U^T]^T as three planes of bf16, [np columns][mxr_ktot]
+    unsigned short* mxr_xt = nullptr; size_t mxr_xt_stride = 0; int mxr_ktot = 0;
+    int *perm = nullptr, *iperm = nullptr;
+    double* Sdis = nullptr;
+    void* pan[2] = { nullptr, nullptr };   // GMW panel hand-off buffers (double-buffered), one launch per panel
+    GmwPlan gplan;                         // persistent GMW launch: panel buffers, sync block, task list
+    // rank-aware refactorisation (srukf_rank.hip): red_r > 0 = the n - red_r structurally null directions are not pivoted
+    int red_r = 0, red_Tp = 0;
+    int *red_perm = nullptr, *red_iperm = nullptr;     // permuted position <-> state index, kept indices first
+    double* gdiag = nullptr;                           // diagonal of G in permuted order (the factorisation overwrites it)
+    double *shadowA = nullptr, *Utp = nullptr;         // replay form: kept rows of S / U^T in permuted column order (srukf_rank.hip)
+    double *slabW = nullptr, *slabL = nullptr;         // batched replay: two panels' slabs W and L = W / D (2 x 64 x np each: the K = 128 trailing update reads a pair)
+    // split form of the persistent factorisation (memory-tile sizes, a filter that has the GPU to itself): the slabs of every pivoted panel (gs_panels x 64 x np
+    // each), the side stream the tile launch runs on and the events that fork it off / join it to the filter's stream
+    double *gsW = nullptr, *gsL = nullptr; int gs_panels = 0;
+    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    double* P1 = nullptr; int* pxy2_tiles = nullptr; int n_pxy2_tiles = 0, pxy2_split_b0 = 0;   // "table" mode: k_pxy2's second K half, its tile list
+    int* nskip = nullptr; int ns_full = 0, ns_null = 0, ns_rows = 0;   // NullSkip lists (srukf_device.h): [dirs | nulls | rows] in one buffer
+    int* red_head0_tiles = nullptr; int n_red_head0_tiles = 0; // split fold: the k_syrk tiles that stay with the launch in front (block row 0, tile (1, 1)) ...
+    void* split_fold_list = nullptr; int n_split_fold = 0;     // ... and the grid of k_gmw_tiles_fold (forming jobs + tile workgroups, row by row: srukf_gmw_build_fold_list)
+    double red_head0_flop = 0.0;                               // flop of the tiles in red_head0_tiles (the rest of k_syrk's count moves to the persistent launch's line of the profile)
+    int* red_syrk_tiles = nullptr; int n_red_syrk_tiles = 0;   // k_syrk tiles of the kept rows (rows < 64 red_Tp) in permuted order: replay form without the owners' fold
+    double red_fac_flop = 0, red_own_flop = 0;         // algorithmic flop of the rank-aware persistent launch: factorisation / owners' tiles of S^T S - U U^T
+    GmwPlan gplan_red;                                 // tile list / sync block of the persistent launch with red_Tp pivoted panels
+    // Sharing the GPU is the handle's choice, but the plans above are built for it: adopt_context applies the outgoing side's pair again through set_shared
+    int shared_tenants = 2;                // SRUKF_GPU_SHARED: how many persistent launches share the GPU (each keeps to cus / tenants CUs; the gate admits that many)
+    int gmw_shared = 0;                    // 0: the filter has the GPU to itself; 1: shared with other filters — persistent launches of at most half the CUs behind
+                                           // the admission gate (k_gmw_gate); 2: one launch per panel (forced, or after an abandoned persistent launch)
+    double *ckS = nullptr, *ckX = nullptr; // srukf_run_frames: state before the block of frames in flight (recovery from a theta-clamp frame)
+    int *syrk_tiles = nullptr, *pxy_tiles = nullptr;   // (by, bx) per workgroup, XCD-aware order
+    int *syrk_head_tiles = nullptr;                    // k_syrk tiles of the first srukf_gmw_head_rows() rows only (fused refactor)
+    int n_syrk_tiles = 0, n_pxy_tiles = 0, n_syrk_head_tiles = 0, n_syrk_head_crit = 0;
+    int* syrk_head_tiles_b = nullptr; int n_syrk_head_tiles_b = 0;      // the same tiles in the batched launch's order (k_syrk_b): one pair of tile columns per XCD, empty slots (-1) where a share is shorter
+    FrameScalars* fs = nullptr;
+    // staged sequence (seqF frames)
+    double *odo_seq = nullptr, *z_seq = nullptr;
+    int* m_seq = nullptr;
+    // pinned staging
+    double* hstage = nullptr; size_t hstage_bytes = 0;
+    FrameScalars* hfs = nullptr;
+    double* hmeas = nullptr;               // inside the hfs allocation, behind the robot view and the flag word
+    double next_odo[6] = { 0, 0, 0, 0, 0, 0 };   // srukf_predict_motion_next (next_odo_valid)
+    // Fast path of the step-wise API: a frame of the staged replay's own launch sequence ("fused tail" mode) cut in two at the host's association step
+    double* odo_step = nullptr;            // device: (prev, cur, next) poses of the frame in flight — a three-pose "staged sequence" fs->odo_seq points at
+    double step_odo[6] = { 0, 0, 0, 0, 0, 0 };   // the pair srukf_predict_motion was called with (the fallback to the other path needs it again)
+    int step_seqF = 1;                     // 2: odo_step holds the next pose too (hint), the tail prepares and projects the next frame
+    double proj_odo[6] = { 0, 0, 0, 0, 0, 0 };   // proj_valid
+    // The copy for the NEXT frame is submitted by the update that ends this one, right behind its last launch (into the second pair of buffers; pair and event swap
+    // when the frame turns out clean): the next srukf_predict_motion then finds its checkpoint made (ck_valid) and submits its first launch at once
+    double *ckS2 = nullptr, *ckX2 = nullptr; hipEvent_t ck_e3 = nullptr;
+    unsigned spin_ok = 0;                  // successful spin waits (step_wait_export queries the stream every 256th)
+    double pre_odo[6] = { 0, 0, 0, 0, 0, 0 };       // pre_issued
+    double setstep_odo[6] = { 0, 0, 0, 0, 0, 0 };   // setstep_done (poses: prev, cur)
+    hipStream_t ck_stream = nullptr; hipEvent_t ck_e1 = nullptr, ck_e2 = nullptr;   // the copy of the state before the frame runs BESIDE the frame's first launch on a
+                                           // stream of its own (it only has to be complete before k_gain touches S): ck_pending
+    int* export_cnt = nullptr;             // 64 x 64 ints (zero): first-level counters of the exporting launch (StepExport::cnt)
+    unsigned long long step_seq = 0;       // sequence number of the step-wise fast path's exports: the host spins on a pinned word (behind the robot view) that receives it
+    double* hview = nullptr; size_t hview_doubles = 0;      // pinned: xyz (3N) | cov (9N) | X (n) of the state an update of the fast path left, when the host is known to ask for it
     int split_fold_seqs = 0;               // split-form pairs enqueued (or captured) with the split fold: "split_fold_seqs"
     int fold_seqs = 0;                     // frame sequences enqueued (or captured) with the gain fold: "fold_seqs" (tests: the switch took effect)
-    int exact_frames = 0;                  // staged frames srukf_run_frames repeated on the exact column path (flagged: theta clamp, a skipped direction that is not null, an abandoned launch): "exact_frames"
-    bool async_pending = false;
-    // Map changes rebuild the context behind the handle (srukf_add_landmarks / srukf_delete_landmark: adopt_context).  A rebuilt context used to be destroyed and the
-    // next one created from nothing — ~0.3 ms of allocations, plans and tile tables, 0.5 - 2.4 ms of frees (pinned host memory among them) per map change at N = 200,
-    // where the reference's map changes every few frames (SLAM.cpp:552-562, 2443-2460) and N only moves by +- 1.  The handle keeps the last few contexts it outgrew
-    // (shape, device, stream and parameters identical when N comes back) and revives one instead of creating it: ctx_obtain / ctx_retire (srukf_api.hip)
-    std::vector<srukf_ctx*> retired;
-    std::string err;
     // one captured frame (BATCHED, staged inputs): replayed by srukf_run_frames_async
     hipGraph_t graph = nullptr, graph8 = nullptr;          // one frame / SRUKF_GRAPH_FRAMES frames
     hipGraphExec_t graph_exec = nullptr, graph8_exec = nullptr;
     hipGraph_t graphN = nullptr; hipGraphExec_t graphN_exec = nullptr; int graphN_frames = 0;   // srukf_prepare_frames: a whole block of frames in ONE graph
-    bool use_graph = true;
-    // profiling
-    bool profiling = false;
-    std::vector<ProfEvent> pev;
-    double prof_ms[KC_COUNT]; long long prof_n[KC_COUNT]; double prof_flops[KC_COUNT]; double prof_bytes[KC_COUNT];
+    // the pool allocations among the members above (Si and vis are inside h, mcur inside zcur; ransac, gplan, gplan_red: ransac_scratch_free / gmw_plan_destroy).
+    // A new buffer of this scope is added HERE
+    template <class F> void each_device_buffer(F f) const {
+        void* b[] = { X, S, G, Gbak, Wf, sigR, Cmat, Z, DZ, Ut, h, PxyR, D, zcur, odocur, small, mpart, dxp, theta, fold_sync, dxk,
+                      app_patch, app_tmpl, appR, appT, appPx, corr, has_app, ov_in, ov_rec, match_res, match_scores, disp,
+                      S32, X32, U32, mx_part, mx_tasks, mx_tiles, A32, mxr_part, mxr_tasks, mxr_tiles, mxr_f64_tiles, mxr_xt,
+                      perm, iperm, Sdis, pan[0], pan[1], red_perm, red_iperm, gdiag, shadowA, Utp, slabW, slabL, gsW, gsL, P1, pxy2_tiles, nskip,
+                      red_head0_tiles, split_fold_list, red_syrk_tiles, ckS, ckX, syrk_tiles, pxy_tiles, syrk_head_tiles, syrk_head_tiles_b, fs,
+                      odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt };
+        for (void* q : b) f(q);
+    }
 };
+
+struct srukf_ctx : srukf_handle_scope, srukf_map_scope {};
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     char b_[256]; snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
@@ -498,7 +540,7 @@ void seq_gain_only(srukf_ctx* c, const double* z_dev, const int* m_dev, bool fus
 void seq_gain(srukf_ctx* c, const double* z_dev, const int* m_dev, bool fused_stats, bool fused_motion = false, bool table = false, bool preamble = false, bool fmode = false);
 int update_null_set(srukf_ctx* c);
 int mixed_red_ensure(srukf_ctx* c);
-void drop_graphs(srukf_ctx* c);
+void drop_graphs(srukf_map_scope* c);
 void exact_path(srukf_ctx* c, const double* Gbuf, double* Sout);      // the exact column path for Gbuf -> Sout (D, theta, clamp count as side effects)
 void set_null_canonical(srukf_ctx* c);
 void canonicalize_null_rows(srukf_ctx* c);      // after update_null_set on a factor of the library's own making (NEED_REORDER, map changes): the next frame may take the fast path

@@ -162,7 +162,8 @@ int srukf_debug_gmw_stamps(srukf_ctx* c, unsigned long long* buf)
     return SRUKF_OK;
 }
 
-// Diagnostic read-out of the device-resident frame scalars (synchronises the stream): "gmw_aborts", "clamp_rows", "frame", "frozen", "gate_timeouts"; "gmw_shared", "split_form"
+// Diagnostic read-out of the device-resident frame scalars (synchronises the stream): "gmw_aborts", "clamp_rows", "frame", "frozen", "gate_timeouts"; "gmw_shared", "split_form";
+// of the filter's own switches: "split_off", "use_graph" (what srukf_debug_set(ctx, "use_graph", v) or the process-wide "graphs" left: tests follow it through map changes)
 int srukf_debug_get(srukf_ctx* c, const char* key, long long* value)
 {
     if (!c || !key || !value) return SRUKF_ERR_BAD_ARG;
@@ -176,6 +177,7 @@ int srukf_debug_get(srukf_ctx* c, const char* key, long long* value)
     else if (!strcmp(key, "gate_timeouts")) *value = c->hfs->gate_timeouts;
     else if (!strcmp(key, "gmw_shared")) *value = c->gmw_shared;
     else if (!strcmp(key, "split_off")) *value = c->split_off ? 1 : 0;
+    else if (!strcmp(key, "use_graph")) *value = c->use_graph ? 1 : 0;
     else if (!strncmp(key, "pad", 3) && key[3] >= '1' && key[3] <= '7' && !key[4]) {
         // diagnostic builds (-DSRUKF_GMW_DBG): words 1..7 of the sync block's pad (helpers started / finished, head counters at the last exit, grid, helpers); cleared by the read
         const GmwPlan& gp = c->red_r > 0 ? c->gplan_red : c->gplan;

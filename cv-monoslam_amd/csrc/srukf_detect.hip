@@ -400,7 +400,7 @@ int srukf_detect_features(srukf_ctx* c, const unsigned char* gray, const srukf_d
     DetScratch& s = c->det;
     const size_t WH = (size_t)W * H;
     const int nb = (int)((WH + DET_BLK - 1) / DET_BLK);
-    if (!s.resp) {                                                       // the scratch of a context, on its first pass (and handed over at map changes)
+    if (!s.resp) {                                                       // the scratch of the handle scope, on its first pass
         if (srukf_dmalloc_on(&s.resp, sizeof(double) * WH, c->stream) != hipSuccess || srukf_dmalloc_on(&s.cand_r, sizeof(double) * WH, c->stream) != hipSuccess ||
             srukf_dmalloc_on(&s.cand_pix, sizeof(int) * WH, c->stream) != hipSuccess || srukf_dmalloc_on(&s.sorted, sizeof(int) * WH, c->stream) != hipSuccess ||
             srukf_dmalloc_on(&s.rank, sizeof(int) * WH, c->stream) != hipSuccess ||

@@ -1,6 +1,6 @@
 // srukf_map.hip — map changes on the device (srukf_add_landmarks: integrateFeaturesInformation, SLAM.cpp:818-871; srukf_delete_landmark: deleteOneFeature, 2637-2668;
 // srukf_insert_landmarks / srukf_get_landmark_record: loop points, 948-1015 and 1357-1378)
-// and data association (wrapPatch + dataAssociation, 1803-2009).  A map change rebuilds the context behind the handle (adopt_context).
+// and data association (wrapPatch + dataAssociation, 1803-2009).  A map change swaps the map-size scope behind the handle (adopt_context).
 
 #include "srukf_ctx.h"
 #include <chrono>
@@ -24,7 +24,7 @@ struct MapTimer {
 
 static int ensure_appearance(srukf_ctx* c)
 {
-    int rc = ensure_image(c); if (rc) return rc;               // (a context may hold the frame buffer without appearance records, and the other way round: adopt_context)
+    int rc = ensure_image(c); if (rc) return rc;               // (the frame buffer is the handle scope's, the records are per map size: either may exist without the other)
     if (c->app_patch) return SRUKF_OK;
     const size_t N = c->d.N > 0 ? c->d.N : 1;
     HIPCHK(c, srukf_dmalloc((void**)&c->app_patch, N * srukf_app_patch_stride()));
@@ -69,8 +69,6 @@ static void clear_appearance(srukf_ctx* b, int to, int count)
 
 namespace srukf_impl {
 
-// the handle keeps its identity when the map changes size: swap the guts of a freshly built context in, keep the
-// stream ownership and the profile, destroy the old buffers
 void match_drop(srukf_ctx* c)
 {
     if (c->match_res) srukf_dfree_on(c->match_res, c->stream);
@@ -78,29 +76,17 @@ void match_drop(srukf_ctx* c)
     c->match_res = nullptr; c->match_scores = nullptr; c->match_valid = false;
 }
 
+// The handle keeps its identity when the map changes size: the map-size scope of the context built for the new size comes in, the handle's own goes out with c2
+// and is retired.  Nothing of the handle scope moves ("who owns what across a map change"); what is written out below is neither "stays" nor "goes".
 void adopt_context(srukf_ctx* c, srukf_ctx* c2)
 {
-    const bool own = c->own_stream;
-    std::vector<srukf_ctx*> kept = std::move(c->retired);       // (the handle's list of retired contexts stays with the handle)
-    std::swap(*c, *c2);
-    c->retired = std::move(kept); c2->retired.clear();
-    c->spare_stage = c2->spare_stage; c->spare_stage_bytes = c2->spare_stage_bytes; c2->spare_stage = nullptr; c2->spare_stage_bytes = 0;      // (the handle's spare staging area too)
-    c->own_stream = own; c2->own_stream = false;
-    c->profiling = c2->profiling; c->use_graph = c2->use_graph;
-    // per-context switches the caller set on the handle survive the rebuild (before srukf_set_storage / update_null_set run on it)
-    c->rank_aware = c2->rank_aware; c->debug_allow_mixed = c2->debug_allow_mixed; c->debug_starve = c2->debug_starve; c->dbg = c2->dbg; c->split_off = c2->split_off;
-    const int shared = c2->gmw_shared, tenants = c2->shared_tenants;
-    memcpy(c->prof_ms, c2->prof_ms, sizeof c->prof_ms); memcpy(c->prof_n, c2->prof_n, sizeof c->prof_n);
-    memcpy(c->prof_flops, c2->prof_flops, sizeof c->prof_flops); memcpy(c->prof_bytes, c2->prof_bytes, sizeof c->prof_bytes);
-    c2->profiling = false; c2->pev.clear();
-    // the frame the handle holds and the detection scratch stay with the handle (same image size in every context of a handle)
-    std::swap(c->d_image, c2->d_image); std::swap(c->frame_valid, c2->frame_valid); std::swap(c->det, c2->det);
-    std::swap(c->d_bgr, c2->d_bgr); std::swap(c->d_ovl, c2->d_ovl); std::swap(c->bgr_valid, c2->bgr_valid);      // (the colour frame and the overlay's output likewise)
-    std::swap(c->archive, c2->archive);                          // (the archive srukf_archive_search reads: the handle's too)
-    c2->frame_valid = false; c2->bgr_valid = false;
+    prof_collect(c);                                             // (the events pending on the handle were recorded around launches on the scope that leaves)
+    std::swap(static_cast<srukf_map_scope&>(*c), static_cast<srukf_map_scope&>(*c2));
+    std::swap(c->err, c2->err);                                  // (the text is the map change's: what its factorisation on c2 left, empty when nothing was abandoned)
+    const int shared = c2->gmw_shared, tenants = c2->shared_tenants;      // (sharing the GPU is the handle's choice, the plans built for it are per map size: below)
     match_drop(c2);                                              // (the score maps of srukf_associate_checked go with the map they were made for)
     ctx_retire(c, c2);                                           // (not destroyed: revived when the map has this size again — ctx_obtain)
-    c->phase = 0; c->frame_updated = false;
+    c->phase = 0; c->frame_updated = false;                      // (whatever call sequence the numeric part ran on the new scope: the handle is between frames)
     if (shared != c->gmw_shared) set_shared(c, shared, tenants);
 }
 
@@ -282,6 +268,67 @@ int srukf_get_match_scores(srukf_ctx* c, int k, double out[441], int* wx, int* w
     return SRUKF_OK;
 }
 
+}  // extern "C"
+
+// ---- what the map changes share around their numeric parts ---------------------------------------------------------------------------------------
+// begin: the frame in flight is committed, the fast path's chain ends, the stream is idle, c2 is a context for N2 landmarks (ctx_obtain).  From here to
+// map_change_finish the handle is untouched: a failure ends in map_change_fail (the caller frees its temporaries first).
+static int map_change_begin(srukf_ctx* c, MapTimer& mt, int N2, srukf_ctx** c2)
+{
+    step_commit_motion(c); step_invalidate(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    mt.mark("sync");
+    const int rc = ctx_obtain(c, c2, N2);
+    if (rc) { c->err = std::string(mt.what) + ": " + g_create_error; return rc; }
+    mt.mark("create");
+    return SRUKF_OK;
+}
+
+static int map_change_fail(srukf_ctx* c, srukf_ctx* c2, int rc, std::string text)
+{
+    srukf_destroy(c2);
+    c->err = std::move(text);
+    return rc;
+}
+static int map_change_fail(srukf_ctx* c, srukf_ctx* c2, const MapTimer& mt, hipError_t e) { return map_change_fail(c, c2, SRUKF_ERR_HIP, std::string(mt.what) + ": " + hipGetErrorString(e)); }
+
+// the n2 x n2 matrix src (leading dimension lds), its rows and columns taken in the order d_map names, factored into c2->S: on the fast path, and again on the exact
+// path if a row was clamped.  zero_fast: S is cleared in front of the fast pass too (the exact pass always starts from zeros)
+static int map_change_factor(srukf_ctx* c, srukf_ctx* c2, int n2, const double* src, int lds, const int* d_map, bool zero_fast)
+{
+    const int ldn = c2->d.np;
+    for (int slow = 0; slow < 2; slow++) {
+        launch_set_frame(c->stream, c2->fs, 0, 1);
+        launch_refactor_reset(c->stream, ldn, c2->theta, c2->fs, 1);
+        launch_sym_permute(c->stream, n2, ldn, src, lds, c2->Gbak, d_map);
+        srukf_launch_gmw_stats(c->stream, n2, ldn, c2->Gbak, c2->fs);
+        if (slow || zero_fast) hipMemsetAsync(c2->S, 0, sizeof(double) * (size_t)ldn * ldn, c->stream);
+        run_gmw(c2, c2->Gbak, c2->S, slow != 0);
+        if (slow) break;
+        const int rc = read_fs(c2);
+        if (rc) return rc;
+        if (c2->hfs->clamp_rows == 0) break;
+    }
+    return SRUKF_OK;
+}
+
+// finish: c2's map-size scope becomes the handle's (adopt_context), in the handle's storage mode, with its null set, and with k_new landmarks armed for NEED_REORDER
+static int map_change_finish(srukf_ctx* c, srukf_ctx* c2, MapTimer& mt, int k_new)
+{
+    const int storage = c->storage;                              // (per map size, F64 in a context just obtained; the mode itself is the caller's)
+    mt.mark("appearance");
+    adopt_context(c, c2);
+    mt.mark("adopt+destroy");
+    int rc = srukf_set_storage(c, storage); if (rc) return rc;
+    mt.mark("set_storage");
+    rc = update_null_set(c); if (rc) return rc;
+    canonicalize_null_rows(c);
+    mt.mark("null_set");
+    return srukf_set_new_landmarks(c, k_new);
+}
+
+extern "C" {
+
 // integrateFeaturesInformation, numeric part (SLAM.cpp:826-871): K new landmarks at the distorted pixels uv[K][2] are
 // appended to the map (normal order: before the robot block).  The context is rebuilt for N + K landmarks in place
 // (the handle stays valid; staged sequences and captured graphs are dropped) and K_new = K is armed for the
@@ -291,15 +338,10 @@ int srukf_add_landmarks(srukf_ctx* c, int K, const double* uv)
     if (!c || K < 1 || !uv) return SRUKF_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     MapTimer mt("add_landmarks");
-    step_commit_motion(c); step_invalidate(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    mt.mark("sync");
     const int dim = c->d.n, ld = c->d.np;
     const int Na = dim + 3 * K, L = 2 * Na + 1, dimn = dim + 6 * K;                          // 827-828
     srukf_ctx* c2 = nullptr;
-    int rc = ctx_obtain(c, &c2, c->d.N + K);
-    if (rc) { c->err = std::string("add_landmarks: ") + g_create_error; return rc; }
-    mt.mark("create");
+    int rc = map_change_begin(c, mt, c->d.N + K, &c2); if (rc) return rc;
     const int ldn = c2->d.np, rows_p = round_up(2 * Na, 16);
     KWeights wa; host_weights(Na, c->p, wa);                                                 // 867
     std::vector<int> perm(dimn);
@@ -317,7 +359,7 @@ int srukf_add_landmarks(srukf_ctx* c, int K, const double* uv)
     if (srukf_dmalloc((void**)&d_uv, sizeof(double) * 2 * K) != hipSuccess || srukf_dmalloc((void**)&d_ang, sizeof(double) * (size_t)L * 3 * K) != hipSuccess ||
         srukf_dmalloc((void**)&d_A, sizeof(double) * (size_t)rows_p * ldn) != hipSuccess || srukf_dmalloc((void**)&d_mu, sizeof(double) * 3 * K) != hipSuccess ||
         srukf_dmalloc((void**)&d_perm, sizeof(int) * dimn) != hipSuccess) {
-        cleanup(); srukf_destroy(c2); c->err = "add_landmarks: out of device memory"; return SRUKF_ERR_NOMEM;
+        cleanup(); return map_change_fail(c, c2, SRUKF_ERR_NOMEM, "add_landmarks: out of device memory");
     }
     hipMemcpyAsync(d_uv, uv, sizeof(double) * 2 * K, hipMemcpyHostToDevice, c->stream);
     hipMemcpyAsync(d_perm, perm.data(), sizeof(int) * dimn, hipMemcpyHostToDevice, c->stream);
@@ -326,38 +368,19 @@ int srukf_add_landmarks(srukf_ctx* c, int K, const double* uv)
     srukf_launch_aug_x(c->stream, dim, K, Na, wa.wm0, wa.wi, c->X, d_ang, d_perm, d_mu, c2->X, dimn, ldn);
     srukf_launch_aug_build(c->stream, dim, ld, K, Na, wa.gamma, wa.wi_sr, c->X, c->S, d_ang, d_A, rows_p, dimn, ldn);
     srukf_launch_gram(c->stream, rows_p, ldn, d_A, c2->G);                                   // A^T A, disordered layout
-    for (int slow = 0; slow < 2; slow++) {
-        launch_set_frame(c->stream, c2->fs, 0, 1);
-        launch_refactor_reset(c->stream, ldn, c2->theta, c2->fs, 1);
-        launch_sym_permute(c->stream, dimn, ldn, c2->G, ldn, c2->Gbak, d_perm);      // Pi (A^T A) Pi^T
-        srukf_launch_gmw_stats(c->stream, dimn, ldn, c2->Gbak, c2->fs);
-        if (slow) hipMemsetAsync(c2->S, 0, sizeof(double) * (size_t)ldn * ldn, c->stream);
-        run_gmw(c2, c2->Gbak, c2->S, slow != 0);
-        if (slow) break;
-        rc = read_fs(c2);
-        if (rc) { c->err = c2->err; cleanup(); srukf_destroy(c2); return rc; }
-        if (c2->hfs->clamp_rows == 0) break;
-    }
+    rc = map_change_factor(c, c2, dimn, c2->G, ldn, d_perm, false);                          // Pi (A^T A) Pi^T
+    if (rc) { cleanup(); return map_change_fail(c, c2, rc, c2->err); }
     hipError_t e = hipStreamSynchronize(c->stream);
     cleanup();
     mt.mark("numeric");
-    if (e != hipSuccess) { srukf_destroy(c2); c->err = std::string("add_landmarks: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
+    if (e != hipSuccess) return map_change_fail(c, c2, mt, e);
     if (c->app_patch) {                                      // the old landmarks keep their appearance records
         rc = ensure_appearance(c2);
-        if (rc) { c->err = c2->err; srukf_destroy(c2); return rc; }
+        if (rc) return map_change_fail(c, c2, rc, c2->err);
         for (int k = 0; k < c->d.N; k++) copy_appearance(c, k, c2, k);
         hipStreamSynchronize(c->stream);
     }
-    const int storage = c->storage;
-    mt.mark("appearance");
-    adopt_context(c, c2);
-    mt.mark("adopt+destroy");
-    rc = srukf_set_storage(c, storage); if (rc) return rc;
-    mt.mark("set_storage");
-    rc = update_null_set(c); if (rc) return rc;
-    canonicalize_null_rows(c);
-    mt.mark("null_set");
-    return srukf_set_new_landmarks(c, K);
+    return map_change_finish(c, c2, mt, K);
 }
 
 // deleteOneFeature, numeric part (SLAM.cpp:2637-2668): landmark id (0-based, state order) leaves the state.  The
@@ -371,56 +394,32 @@ int srukf_delete_landmark(srukf_ctx* c, int id)
     if (id < 0 || id >= N) { c->err = "delete_landmark: no such landmark"; return SRUKF_ERR_BAD_ARG; }
     HIPCHK(c, hipSetDevice(c->device));
     MapTimer mt("delete_landmark");
-    step_commit_motion(c); step_invalidate(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    mt.mark("sync");
     srukf_ctx* c2 = nullptr;
-    int rc = ctx_obtain(c, &c2, N - 1);
-    if (rc) { c->err = std::string("delete_landmark: ") + g_create_error; return rc; }
-    mt.mark("create");
+    int rc = map_change_begin(c, mt, N - 1, &c2); if (rc) return rc;
     const int nn = n - 6, ldn = c2->d.np;
     std::vector<int> map(nn);
     for (int a = 0; a < nn; a++) map[a] = a < 6 * id ? a : a + 6;
     int* d_map = nullptr;
-    if (srukf_dmalloc((void**)&d_map, sizeof(int) * nn) != hipSuccess) { srukf_destroy(c2); c->err = "delete_landmark: out of device memory"; return SRUKF_ERR_NOMEM; }
+    if (srukf_dmalloc((void**)&d_map, sizeof(int) * nn) != hipSuccess) return map_change_fail(c, c2, SRUKF_ERR_NOMEM, "delete_landmark: out of device memory");
     hipMemcpy(d_map, map.data(), sizeof(int) * nn, hipMemcpyHostToDevice);
     launch_refactor_reset(c->stream, np, c->theta, c->fs, 1);
     srukf_launch_syrk(c->stream, c->d, c->S, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, nullptr, c->X, RankArgs{}, nullptr);   // P = S^T S
     launch_gather(c->stream, nn, ldn, c->X, c2->X, d_map);
-    for (int slow = 0; slow < 2; slow++) {
-        launch_set_frame(c->stream, c2->fs, 0, 1);
-        launch_refactor_reset(c->stream, ldn, c2->theta, c2->fs, 1);
-        launch_sym_permute(c->stream, nn, ldn, c->G, np, c2->Gbak, d_map);
-        srukf_launch_gmw_stats(c->stream, nn, ldn, c2->Gbak, c2->fs);
-        hipMemsetAsync(c2->S, 0, sizeof(double) * (size_t)ldn * ldn, c->stream);
-        run_gmw(c2, c2->Gbak, c2->S, slow != 0);
-        if (slow) break;
-        rc = read_fs(c2);
-        if (rc) { c->err = c2->err; srukf_dfree(d_map); srukf_destroy(c2); return rc; }
-        if (c2->hfs->clamp_rows == 0) break;
-    }
+    rc = map_change_factor(c, c2, nn, c->G, np, d_map, true);
+    if (rc) { srukf_dfree(d_map); return map_change_fail(c, c2, rc, c2->err); }
     hipError_t e = hipStreamSynchronize(c->stream);
     srukf_dfree(d_map);
     mt.mark("numeric");
-    if (e != hipSuccess) { srukf_destroy(c2); c->err = std::string("delete_landmark: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
+    if (e != hipSuccess) return map_change_fail(c, c2, mt, e);
     // m_nFilters-- when one of the landmarks added last is the one that goes (SLAM.cpp:2468-2492)
     const int k_new = c->K_new > 0 ? (id >= N - c->K_new ? c->K_new - 1 : c->K_new) : 0;
     if (c->app_patch) {
         rc = ensure_appearance(c2);
-        if (rc) { c->err = c2->err; srukf_destroy(c2); return rc; }
+        if (rc) return map_change_fail(c, c2, rc, c2->err);
         for (int k = 0, a = 0; k < N; k++) if (k != id) copy_appearance(c, k, c2, a++);
         hipStreamSynchronize(c->stream);
     }
-    const int storage = c->storage;
-    mt.mark("appearance");
-    adopt_context(c, c2);
-    mt.mark("adopt+destroy");
-    rc = srukf_set_storage(c, storage); if (rc) return rc;
-    mt.mark("set_storage");
-    rc = update_null_set(c); if (rc) return rc;
-    canonicalize_null_rows(c);
-    mt.mark("null_set");
-    return srukf_set_new_landmarks(c, k_new);
+    return map_change_finish(c, c2, mt, k_new);
 }
 
 // What an archived landmark takes along (FeatureInfo, SLAM.cpp:1357-1378, 2516-2532): its six rows of X, the upper Cholesky factor of its marginal block
@@ -464,16 +463,11 @@ int srukf_insert_landmarks(srukf_ctx* c, int L, const double* X6, const double* 
                 if (S66[36 * (size_t)j + 6 * a + b] != 0.0) { c->err = "insert_landmarks: S66 is not upper triangular"; return SRUKF_ERR_BAD_ARG; }
     HIPCHK(c, hipSetDevice(c->device));
     MapTimer mt("insert_landmarks");
-    step_commit_motion(c); step_invalidate(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    mt.mark("sync");
     const int N = c->d.N, k_new = c->K_new, p0 = N - k_new;
     srukf_ctx* c2 = nullptr;
-    int rc = ctx_obtain(c, &c2, N + L);
-    if (rc) { c->err = std::string("insert_landmarks: ") + g_create_error; return rc; }
-    mt.mark("create");
+    int rc = map_change_begin(c, mt, N + L, &c2); if (rc) return rc;
     double* d_blk = nullptr;
-    if (srukf_dmalloc_on(&d_blk, sizeof(double) * 42 * (size_t)L, c->stream) != hipSuccess) { srukf_destroy(c2); c->err = "insert_landmarks: out of device memory"; return SRUKF_ERR_NOMEM; }
+    if (srukf_dmalloc_on(&d_blk, sizeof(double) * 42 * (size_t)L, c->stream) != hipSuccess) return map_change_fail(c, c2, SRUKF_ERR_NOMEM, "insert_landmarks: out of device memory");
     hipError_t e = hipMemcpyAsync(d_blk, X6, sizeof(double) * 6 * (size_t)L, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_blk + 6 * (size_t)L, S66, sizeof(double) * 36 * (size_t)L, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
@@ -483,10 +477,10 @@ int srukf_insert_landmarks(srukf_ctx* c, int L, const double* X6, const double* 
     srukf_dfree_on(d_blk, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     mt.mark("numeric");
-    if (e != hipSuccess) { srukf_destroy(c2); c->err = std::string("insert_landmarks: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
+    if (e != hipSuccess) return map_change_fail(c, c2, mt, e);
     if (c->app_patch || patches || c2->app_patch) {
         rc = ensure_appearance(c2);
-        if (rc) { c->err = c2->err; srukf_destroy(c2); return rc; }
+        if (rc) return map_change_fail(c, c2, rc, c2->err);
         if (c->app_patch) {                                              // the old landmarks keep their records
             copy_appearance(c, 0, c2, 0, p0);
             copy_appearance(c, p0, c2, p0 + L, k_new);
@@ -507,18 +501,9 @@ int srukf_insert_landmarks(srukf_ctx* c, int L, const double* X6, const double* 
             clear_appearance(c2, p0, L);
             e = hipStreamSynchronize(c->stream);
         }
-        if (e != hipSuccess) { srukf_destroy(c2); c->err = std::string("insert_landmarks: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
+        if (e != hipSuccess) return map_change_fail(c, c2, mt, e);
     }
-    const int storage = c->storage;
-    mt.mark("appearance");
-    adopt_context(c, c2);
-    mt.mark("adopt+destroy");
-    rc = srukf_set_storage(c, storage); if (rc) return rc;
-    mt.mark("set_storage");
-    rc = update_null_set(c); if (rc) return rc;
-    canonicalize_null_rows(c);
-    mt.mark("null_set");
-    return srukf_set_new_landmarks(c, k_new);
+    return map_change_finish(c, c2, mt, k_new);
 }
 
 }  // extern "C"

@@ -905,7 +905,7 @@ int read_fs_host(srukf_ctx* c)
     return SRUKF_OK;
 }
 
-void drop_graphs(srukf_ctx* c)
+void drop_graphs(srukf_map_scope* c)
 {
     if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
     if (c->graph) { hipGraphDestroy(c->graph); c->graph = nullptr; }

@@ -51,7 +51,69 @@ def test_map_changes_keep_the_context_switches(srukf, synth):
     assert f.null_directions() > 0
     f.delete_landmark(0)
     assert f.null_directions() > 0
+    # The other members of the handle scope that no test followed through a map change: "use_graph" 0 and the profiling switch with its accumulators (here), a
+    # srukf_debug_set switch (below).  N = 3 -> 2 -> 3 is the smallest map that reaches a context created new (2) and a revived one (3 again).
+    N = 3
+    sc = synth.make_scene(N, 2, seed=5, p=p)
+    f = srukf.Filter(N, p); f.set_state(sc["X0"], sc["S0"])
+    f.debug_set("use_graph", 0); f.set_profiling(True)
 
+    def frame(f, sc, t, reorder, keep=None):
+        """one step-wise frame with every visible landmark (of the first `keep`) matched at its predicted pixel"""
+        f.predict_motion(sc["odo"][t], sc["odo"][t + 1])
+        h, Si, vis = f.predict_measurement()
+        m = np.asarray(vis, dtype=np.int32).copy()
+        if keep is not None: m[keep:] = 0
+        f.update(np.asarray(h, dtype=np.float64).reshape(-1), m, reorder=reorder if m.sum() else srukf.NEEDNOT_REORDER)
+
+    def launches():
+        return {k: v["launches"] for k, v in f.profile().items()}
+
+    def total(a, b):
+        return sum(b[k] - a[k] for k in a)
+
+    n00 = launches()
+    frame(f, sc, 0, srukf.NEEDNOT_REORDER, keep=2)                   # (the landmark that is deleted and added back is never matched)
+    assert f.debug_get("step_slow") == 1 and f.debug_get("step_fast") == 0      # (n = 22: no rank-aware form, so never the fast path)
+    n0 = launches()
+    assert total(n00, n0) > 0
+    f.delete_landmark(2)                                             # a context created new; nothing is pending on the handle
+    assert f.debug_get("use_graph") == 0
+    n1 = launches()
+    assert all(n1[k] >= n0[k] for k in n0), (n0, n1)               # a count taken before the map change is still in the read-out
+    f.add_landmarks(np.array([[300.0, 200.0]]))                      # the first context, revived
+    assert f.debug_get("use_graph") == 0
+    n2 = launches()
+    assert all(n2[k] >= n1[k] for k in n1), (n1, n2)
+    frame(f, sc, 1, srukf.NEED_REORDER, keep=2)                      # (its launches wait on the handle, uncollected, when the next map change comes)
+    assert f.debug_get("step_slow") == 1 and f.debug_get("step_fast") == 0      # the revived context counts from zero (srukf_life)
+    f.delete_landmark(2)                                             # the same deletion as above, 3 -> 2, now with a frame's events pending
+    n3 = launches()
+    assert all(n3[k] >= n2[k] for k in n2), (n2, n3)               # profiling stayed on ...
+    assert total(n2, n3) > total(n0, n1), (n0, n1, n2, n3)         # ... and the pending events were collected: more than the deletion's own launches arrived
+
+    # A srukf_debug_set switch with an effect: "step_fast" 0 at N = 50, where the rank-aware form exists and the default takes the fast path (the control filter shows
+    # it at every stage).  50 -> 49 (created new) -> 50 (revived); the frame behind the addition is the NEED_REORDER one, which never runs on the fast path.
+    N = 50
+    sc = synth.make_scene(N, 7, seed=5, p=p)
+    counts = {}
+    for fast in (1, 0):
+        f = srukf.Filter(N, p); f.set_state(sc["X0"], sc["S0"]); f.debug_set("step_fast", fast)
+        assert f.null_directions() > 0
+        for t in (0, 1): frame(f, sc, t, srukf.NEEDNOT_REORDER)       # (the first frame of a state from outside makes its null rows canonical, on the other path)
+        got = [(f.debug_get("step_fast"), f.debug_get("step_slow"))]
+        f.delete_landmark(N - 1)
+        for t in (2, 3): frame(f, sc, t, srukf.NEEDNOT_REORDER)
+        got.append((f.debug_get("step_fast"), f.debug_get("step_slow")))
+        f.add_landmarks(np.array([[300.0, 200.0]]))
+        frame(f, sc, 4, srukf.NEED_REORDER)
+        for t in (5, 6): frame(f, sc, t, srukf.NEEDNOT_REORDER)
+        got.append((f.debug_get("step_fast"), f.debug_get("step_slow")))
+        counts[fast] = got
+    print("step_fast / step_slow per stage:", counts)
+    assert [a + b for a, b in counts[1]] == [2, 2, 3] and [a + b for a, b in counts[0]] == [2, 2, 3]      # every context counts its own life
+    assert all(a >= 1 for a, b in counts[1]), counts                 # the default takes the fast path at every stage: the switch has an effect here
+    assert all(a == 0 for a, b in counts[0]), counts                 # ... and "step_fast" 0 holds in the first, the new and the revived context
 
 def test_bench_force_dist_runs_the_rccl_collectives_with_one_rank():
     """`bench.py --gpus 1 --force-dist`: torch.distributed.run -> one rank -> init_process_group("nccl") -> broadcast of the map ->
