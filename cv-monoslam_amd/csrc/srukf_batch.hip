@@ -174,7 +174,7 @@ static int batch_run(srukf_ctx* const* cs, int B, int first, int count, double* 
         a1[b] = Pxy2Args{ c->DZ, c->shadowA, c->Utp, c->P1,
                           MeasArgs{ c->X, c->sigR, c->sigR, c->Z, c->mpart, c->h, c->Si, c->vis, c->PxyR, c->fs, (d.N + 31) / 32, null_skip(c), 1, 1, c->Cmat } };
         a2[b] = GainArgs{ c->Ut, c->PxyR, c->Si, c->vis, c->h, c->z_seq, c->m_seq, c->fs, c->dxp, rank_args(c), c->Cmat, c->S, c->P1, c->DZ, c->sigR, c->Z };
-        a3[b] = SyrkArgs{ c->shadowA, c->Utp, c->Wf, c->fs, c->dxp, c->X, rank_args(c, true), (const double*)((const char*)c->fs + offsetof(FrameScalars, Xr1)) };
+        a3[b] = SyrkArgs{ c->shadowA, c->Utp, c->Wf, c->fs, c->dxp, c->X, tail_rank_args(c, FORM_FUSED_TAIL), (const double*)((const char*)c->fs + offsetof(FrameScalars, Xr1)) };
         a4[b] = SyrkOwnArgs{ c->shadowA, c->Utp, c->Wf, c->fs };
         if (!c->slabW) {
             HIPCHK(c, srukf_dmalloc(&c->slabW, sizeof(double) * 2 * 64 * (size_t)d.np)); HIPCHK(c, srukf_dmalloc(&c->slabL, sizeof(double) * 2 * 64 * (size_t)d.np));
@@ -219,7 +219,9 @@ static int batch_run(srukf_ctx* const* cs, int B, int first, int count, double* 
         double* traj = dt[b] ? dt[b] - (size_t)8 * first : nullptr;
         launch_set_run(st, c->fs, first, c->async_pending ? 0 : 1, traj);
         srukf_launch_sigr_rows(st, c->d, c->w, c->X, c->S, c->sigR, c->fs, c->red_iperm, c->red_r);
-        srukf_launch_project_table(st, c->d, c->w, c->p, c->X, c->S, c->sigR, c->Cmat, c->Z, c->DZ, c->fs, rank_args(c, false, true), null_skip(c));
+        RankArgs pra = rank_args(c);
+        pra.dzperm = 1;
+        srukf_launch_project_table(st, c->d, c->w, c->p, c->X, c->S, c->sigR, c->Cmat, c->Z, c->DZ, c->fs, pra, null_skip(c));
         c->xr1_pending = false; c->dx_pending = false;          // (the batched launches apply both themselves, every frame)
         c->async_pending = true; c->phase = 0; c->frame_updated = false;
     }

@@ -407,7 +407,7 @@ struct srukf_ctx : srukf_handle_scope, srukf_map_scope {};
 namespace srukf_impl {
 
 // fp32 storage of the state with everything that goes with it in "fused tail" mode (the tail and the state update round what they write).  The mixed-precision downdate in
-// its rank-aware form (round 6) IS that mode with one difference: where the staged frame forms S^T S - U U^T over the kept rows (seq_refactor, red_perm branch)
+// its rank-aware form (round 6) IS that mode with one difference: where the staged frame forms S^T S - U U^T over the kept rows (RF_PERMUTED_SYRK)
 inline bool storage_f32_like(const srukf_ctx* c) { return c->storage == SRUKF_STORAGE_F32 || (c->storage == SRUKF_STORAGE_F32_MIXED && c->dbg.mixed_rank && c->A32); }
 
 extern const char* const kclass_name[KC_COUNT];
@@ -430,9 +430,7 @@ hipError_t srukf_dfree_on(void* p, hipStream_t st);
 
 // ---- small kernels of the host layer behind launchers (srukf_replay.hip) ----
 void launch_refactor_reset(hipStream_t st, int np, unsigned long long* theta_bits, FrameScalars* fs, int reset_stats);
-void launch_set_seq(hipStream_t st, FrameScalars* fs, const double* odo_seq, int seqF, double a1, double a2, double a3, double a4);
 void launch_set_frame(hipStream_t st, FrameScalars* fs, int frame, int clear_clamp);
-void launch_set_traj(hipStream_t st, FrameScalars* fs, double* traj_base);
 void launch_set_run(hipStream_t st, FrameScalars* fs, int frame, int clear_clamp, double* traj_base);
 void launch_set_step(hipStream_t st, FrameScalars* fs, double* odo, int seqF, double a1, double a2, double a3, double a4, int fresh, const double poses[9]);
 // device -> pinned host memory, two segments of 8-byte words; flag (pinned too, may be null) receives seq behind the data
@@ -441,8 +439,6 @@ void launch_set_frame_control(hipStream_t st, FrameScalars* fs);
 void launch_commit_motion(hipStream_t st, int n, int ld, double* X, double* S, const double* Cm, const FrameScalars* fs, double* A, const int* iperm, int rk);
 void launch_sym_permute(hipStream_t st, int n, int ld, const double* src, int lds, double* dst, const int* map);
 void launch_gather(hipStream_t st, int n, int ld, const double* src, double* dst, const int* map);
-void launch_zero_rows(hipStream_t st, int ld, int r0, double* A);
-void launch_quantize(hipStream_t st, int n, int ld, double* S, double* X, float* S32, float* X32);
 
 // ---- plans, tables (srukf_api.hip) ----
 void gmw_plan_destroy(GmwPlan& g, hipStream_t st = nullptr);
@@ -507,37 +503,54 @@ void step_invalidate(srukf_ctx* c);
 void step_state_replaced(srukf_ctx* c);
 void step_ck_join(srukf_ctx* c);
 
-// ---- launch sequences (srukf_replay.hip) ----
+// ---- launch sequences (srukf_replay.hip; DESIGN.md section 4) ----
+// The measurement half of a frame, a ladder: k_meas_stats as a launch of its own (step-wise slow path) / the statistics ride on k_pxy / ... and the motion step ran
+// inside the projection launch / ... and the product is k_pxy2's, on the permuted operands / ... and the previous frame's tail projected this frame.
+enum MeasForm { MEAS_SEPARATE_STATS, MEAS_PLAIN, MEAS_FUSED_MOTION, MEAS_TABLE, MEAS_FUSED_TAIL };
+struct FrameForm {
+    MeasForm meas; bool robot_table;       // robot_table: projection and tail work on the table of robot poses — from MEAS_TABLE on, and with "pxy2" off below it
+    bool fused_stats() const { return meas >= MEAS_PLAIN; }
+    bool fused_motion() const { return meas >= MEAS_FUSED_MOTION; }
+    bool pxy2() const { return meas >= MEAS_TABLE; }
+    bool fused_tail() const { return meas >= MEAS_FUSED_TAIL; }
+};
+constexpr FrameForm FORM_SEPARATE_STATS{ MEAS_SEPARATE_STATS, false }, FORM_PLAIN{ MEAS_PLAIN, false }, FORM_FUSED_TAIL{ MEAS_FUSED_TAIL, true };
+// What is asked of a refactorisation  S <- gmw(S^T S - U[ub:ue] U[ub:ue]^T):  the tail of a staged or fast-path frame (no backup, the last launch ends the frame) /
+// checked (G kept in Gbak, the host reads clamp_rows afterwards) / one column of SEQUENTIAL mode (as checked, behind a reset of the gamma / xi accumulators)
+struct RefactorRequest { enum Kind { FRAME_TAIL, CHECKED, SEQ_COLUMN } kind; int ub, ue; };
+inline RefactorRequest refactor_frame_tail(const srukf_ctx* c) { return RefactorRequest{ RefactorRequest::FRAME_TAIL, 0, c->d.mp }; }
+inline RefactorRequest refactor_checked(const srukf_ctx* c) { return RefactorRequest{ RefactorRequest::CHECKED, 0, c->d.mp }; }
+inline RefactorRequest refactor_column(int m) { return RefactorRequest{ RefactorRequest::SEQ_COLUMN, m, m + 1 }; }
+// ... and the launches it consists of (refactor_form): the owners of the persistent launch form their tiles / k_syrk over the kept rows in permuted order / k_syrk in
+// state order + permutation pass / every pivot factored.  sub: head fold (owners' fold), own order or split fold (permuted k_syrk), fused (full rank)
+enum RefactorForm { RF_OWNERS_FOLD, RF_PERMUTED_SYRK, RF_RANK_VIA_PERMUTATION, RF_FULL_RANK };
+struct RefactorPlan { RefactorForm form; bool persist, head_fold, own_order, split_fold, fused; };      // persist: persistent launch(es), not one launch per panel
+enum GmwPanels { GMW_ALL_PANELS, GMW_KEPT_PANELS, GMW_KEPT_PANELS_SPLIT_FOLD };      // launch_gmw_fast: the full plan / the rank-aware plan / ... whose tile launch forms tiles too
+inline int kept_rows16(const srukf_ctx* c) { return (c->red_r + 15) & ~15; }      // K range of the products over the kept rows
 void quantize_state(srukf_ctx* c);
-RankArgs rank_args(const srukf_ctx* c, bool prep_next = false, bool dzperm = false, bool f32round = false);
+RankArgs rank_args(const srukf_ctx* c);
+RankArgs tail_rank_args(const srukf_ctx* c, FrameForm ff);
 NullSkip null_skip(const srukf_ctx* c);
-const double* take_xr1(srukf_ctx* c);
-void seq_predict_fused(srukf_ctx* c, int mode);
+FrameForm frame_form(const srukf_ctx* c);
+RefactorPlan refactor_form(const srukf_ctx* c, const RefactorRequest& rq);
+void seq_predict_fused(srukf_ctx* c, FrameForm ff);
 void seq_predict_motion(srukf_ctx* c, const double* odo_pair_dev);
-void seq_predict_measurement(srukf_ctx* c, bool fused_stats);
+void seq_predict_measurement(srukf_ctx* c, FrameForm ff);
 void shadow_rebuild(srukf_ctx* c);
-bool gmw_plan_persists(const srukf_ctx* c, const GmwPlan& gp);
-bool gmw_use_persist(const srukf_ctx* c);
+bool plan_persists(const srukf_ctx* c, const GmwPlan& gp);
 int gmw_persist_mode();
-int plan_tenants(const srukf_ctx* c);
 int gate_limit(const srukf_ctx* c);
-void rank_expand(srukf_ctx* c, bool frame_tail, bool table = false, bool fuse = false);
-bool replay_red_fused(const srukf_ctx* c);
 bool replay_red_perm(const srukf_ctx* c);
 int replay_motion_mode(const srukf_ctx* c);
-bool replay_fuse_mode(const srukf_ctx* c);
-bool head_fold_ok(const srukf_ctx* c);
-int gmw_fused_mode();
 int rank_fused_mode();
-int rank_fold_mode();
-void seq_refactor(srukf_ctx* c, int ub, int ue, bool slow, bool keep_backup, bool need_reset, bool frame_tail, bool table = false, bool fuse = false);
-void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, bool reduced = false, bool fold = false);
-bool split_fold_ok(const srukf_ctx* c);
+void seq_refactor(srukf_ctx* c, const RefactorRequest& rq, FrameForm ff);
+int exact_repeat_begin(srukf_ctx* c, int frame, double* traj_base);
+void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, GmwPanels which);
 void run_gmw(srukf_ctx* c, double* Gbuf, double* Sout, bool slow);
 int refactor_reorder(srukf_ctx* c, int ub, int ue);
-void seq_pxy(srukf_ctx* c, bool fused_stats, bool fused_motion = false, bool table = false, bool preamble = false, bool fmode = false, bool fold = false);
-void seq_gain_only(srukf_ctx* c, const double* z_dev, const int* m_dev, bool fused_motion = false, bool table = false, bool fmode = false);
-void seq_gain(srukf_ctx* c, const double* z_dev, const int* m_dev, bool fused_stats, bool fused_motion = false, bool table = false, bool preamble = false, bool fmode = false);
+void seq_pxy(srukf_ctx* c, FrameForm ff);
+void seq_gain_only(srukf_ctx* c, const double* z_dev, const int* m_dev, FrameForm ff);
+void seq_gain(srukf_ctx* c, const double* z_dev, const int* m_dev, FrameForm ff);
 int update_null_set(srukf_ctx* c);
 int mixed_red_ensure(srukf_ctx* c);
 void drop_graphs(srukf_map_scope* c);
@@ -547,7 +560,6 @@ void canonicalize_null_rows(srukf_ctx* c);      // after update_null_set on a fa
 int read_fs(srukf_ctx* c);
 int read_fs_host(srukf_ctx* c);
 int set_shared(srukf_ctx* c, int shared, int tenants);
-void replay_one_frame(srukf_ctx* c);
 
 // ---- split form of the persistent factorisation (srukf_split.hip) ----
 bool split_form(const srukf_ctx* c, const GmwPlan& gp, bool ignore_starve = false);

@@ -209,7 +209,8 @@ int srukf_debug_get(srukf_ctx* c, const char* key, long long* value)
     else if (!strncmp(key, "plan_", 5)) {
         // which launch plan the next staged frame takes (tests assert it next to the oracle comparison: every N is a product size, SLAM.cpp:552-562, 2443-2460)
         const GmwPlan& gp = c->red_r > 0 ? c->gplan_red : c->gplan;
-        const bool persist = gmw_use_persist(c) && gmw_plan_persists(c, gp);
+        const RefactorPlan rp = refactor_form(c, refactor_frame_tail(c));
+        const bool persist = plan_persists(c, gp);
         const char* k = key + 5;
         if (!strcmp(k, "T")) *value = gp.T;
         else if (!strcmp(k, "Tp")) *value = gp.Tp;
@@ -218,11 +219,11 @@ int srukf_debug_get(srukf_ctx* c, const char* key, long long* value)
         else if (!strcmp(k, "persist")) *value = persist ? 1 : 0;                                        // 0: one launch per 64-row panel
         else if (!strcmp(k, "register_form")) *value = (persist && !split_form(c, gp) && srukf_gmw_register_form(gp.T, gp.Tp, gp.ntiles, gp.workers)) ? 1 : 0;
         else if (!strcmp(k, "tiles_per_worker")) *value = gp.workers > 0 ? (gp.nreal + gp.workers - 1) / gp.workers : -1;
-        else if (!strcmp(k, "fold")) *value = replay_red_fused(c) ? 1 : 0;                               // the owners form their tiles of S^T S - U U^T themselves
-        else if (!strcmp(k, "head_fold")) *value = (replay_red_fused(c) && head_fold_ok(c)) ? 1 : 0;     // ... and the head tiles ride on the persistent launch
-        else if (!strcmp(k, "red_perm")) *value = (!replay_red_fused(c) && replay_red_perm(c)) ? 1 : 0;  // k_syrk over the kept rows in permuted order
+        else if (!strcmp(k, "fold")) *value = rp.form == RF_OWNERS_FOLD ? 1 : 0;                         // the owners form their tiles of S^T S - U U^T themselves
+        else if (!strcmp(k, "head_fold")) *value = rp.head_fold ? 1 : 0;                                 // ... and the head tiles ride on the persistent launch
+        else if (!strcmp(k, "red_perm")) *value = replay_red_perm(c) ? 1 : 0;     // RF_PERMUTED_SYRK as "table" mode may build on it: 0 with "table_perm" 0, though the form still runs
         else if (!strcmp(k, "motion")) *value = replay_motion_mode(c);                                   // 2: "table" mode
-        else if (!strcmp(k, "fuse")) *value = replay_fuse_mode(c) ? 1 : 0;                               // "fused tail" mode
+        else if (!strcmp(k, "fuse")) *value = frame_form(c).fused_tail() ? 1 : 0;                               // "fused tail" mode
         else if (!strcmp(k, "kept")) *value = c->red_r;
         else if (!strcmp(k, "sync_doubles")) *value = gp.sync ? srukf_gmw_sync_bytes(gp.T) / 8 : 0;      // sizes of the byte buffers srukf_debug_copy counts in doubles
         else if (!strcmp(k, "pans_doubles")) *value = gp.pans ? (long long)srukf_gmw_panel_bytes() * gp.T / 8 : 0;

@@ -213,7 +213,7 @@ int srukf_repredict_measurement(srukf_ctx* c, double* h, double* Si, int* visibl
     HIPCHK(c, hipMemcpyAsync(s.X, c->X, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(s.S, c->S, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream));
     srukf_launch_motion(c->stream, d, c->w, c->p, s.X, s.S, c->sigR, s.Cm, s.fs, nullptr, s.odo, RankArgs{});
-    seq_predict_measurement(c, false);
+    seq_predict_measurement(c, FORM_SEPARATE_STATS);
     double* hs = c->hstage;
     const size_t out_bytes = sizeof(double) * (mp + 4 * (size_t)N) + sizeof(int) * N;
     HIPCHK(c, hipMemcpyAsync(hs, c->h, out_bytes, hipMemcpyDeviceToHost, c->stream));

@@ -142,9 +142,7 @@ __global__ __launch_bounds__(256) void k_quantize(int n, int ld, double* __restr
 
 namespace srukf_impl {
 void launch_refactor_reset(hipStream_t st, int np, unsigned long long* theta_bits, FrameScalars* fs, int reset_stats) { hipLaunchKernelGGL(k_refactor_reset, dim3((np + 255) / 256), dim3(256), 0, st, np, theta_bits, fs, reset_stats); }
-void launch_set_seq(hipStream_t st, FrameScalars* fs, const double* odo_seq, int seqF, double a1, double a2, double a3, double a4) { hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, st, fs, odo_seq, seqF, a1, a2, a3, a4); }
 void launch_set_frame(hipStream_t st, FrameScalars* fs, int frame, int clear_clamp) { hipLaunchKernelGGL(k_set_frame, dim3(1), dim3(1), 0, st, fs, frame, clear_clamp); }
-void launch_set_traj(hipStream_t st, FrameScalars* fs, double* traj_base) { hipLaunchKernelGGL(k_set_traj, dim3(1), dim3(1), 0, st, fs, traj_base); }
 void launch_set_run(hipStream_t st, FrameScalars* fs, int frame, int clear_clamp, double* traj_base) { hipLaunchKernelGGL(k_set_run, dim3(1), dim3(1), 0, st, fs, frame, clear_clamp, traj_base); }
 void launch_set_step(hipStream_t st, FrameScalars* fs, double* odo, int seqF, double a1, double a2, double a3, double a4, int fresh, const double poses[9])
 {
@@ -161,32 +159,28 @@ void launch_set_frame_control(hipStream_t st, FrameScalars* fs) { hipLaunchKerne
 void launch_commit_motion(hipStream_t st, int n, int ld, double* X, double* S, const double* Cm, const FrameScalars* fs, double* A, const int* iperm, int rk) { hipLaunchKernelGGL(k_commit_motion, dim3((n + 255) / 256), dim3(256), 0, st, n, ld, X, S, Cm, fs, A, iperm, rk); }
 void launch_sym_permute(hipStream_t st, int n, int ld, const double* src, int lds, double* dst, const int* map) { hipLaunchKernelGGL(k_sym_permute, dim3(ld), dim3(256), 0, st, n, ld, src, lds, dst, map); }
 void launch_gather(hipStream_t st, int n, int ld, const double* src, double* dst, const int* map) { hipLaunchKernelGGL(k_gather, dim3((ld + 255) / 256), dim3(256), 0, st, n, ld, src, dst, map); }
-void launch_zero_rows(hipStream_t st, int ld, int r0, double* A) { if (ld > r0) hipLaunchKernelGGL(k_zero_rows, dim3(ld - r0), dim3(256), 0, st, ld, r0, A); }
-void launch_quantize(hipStream_t st, int n, int ld, double* S, double* X, float* S32, float* X32) { hipLaunchKernelGGL(k_quantize, dim3(n + 1), dim3(256), 0, st, n, ld, S, X, S32, X32); }
-}  // namespace srukf_impl
-
-namespace srukf_impl {
 
 int gmw_persist_mode() { return g_dbg_gmw_persist; }
 
 void quantize_state(srukf_ctx* c)
 {
-    if (c->storage != SRUKF_STORAGE_F64)
-        hipLaunchKernelGGL(k_quantize, dim3(c->d.n + 1), dim3(256), 0, c->stream, c->d.n, c->d.np, c->S, c->X, c->S32, c->X32);
+    if (c->storage != SRUKF_STORAGE_F64) hipLaunchKernelGGL(k_quantize, dim3(c->d.n + 1), dim3(256), 0, c->stream, c->d.n, c->d.np, c->S, c->X, c->S32, c->X32);
 }
 
 // rank-aware replay form: what k_motion / k_gain / k_syrk carry along (all null when the shadow copy does not exist)
 // the pending state update as the launch that applies it takes it: k_gain's slice partials, or the per-landmark shares the gain fold of k_pxy2 left (RankArgs::dxN)
 static const double* dx_src(const srukf_ctx* c) { return c->dx_pending ? (c->dx_lm ? c->dxk : c->dxp) : nullptr; }
 
-RankArgs rank_args(const srukf_ctx* c, bool prep_next, bool dzperm, bool f32round)
+RankArgs rank_args(const srukf_ctx* c)
 {
     RankArgs ra = {};
-    ra.prep_next = prep_next ? 1 : 0; ra.dzperm = dzperm ? 1 : 0; ra.f32round = f32round ? 1 : 0;
     ra.dxN = (c->dx_pending && c->dx_lm) ? c->d.N : 0;
     if (c->red_r > 0 && c->shadowA) { ra.A = c->shadowA; ra.Utp = c->Utp; ra.gdiag = c->gdiag; ra.iperm = c->red_iperm; ra.perm = c->red_perm; ra.r = c->red_r; }
     return ra;
 }
+
+// ... as the launch that applies the state update in front of a frame tail takes them (the tail prepares the next table; "fused tail" on fp32 storage rounds)
+RankArgs tail_rank_args(const srukf_ctx* c, FrameForm ff) { RankArgs ra = rank_args(c); ra.prep_next = ff.robot_table ? 1 : 0; ra.f32round = (ff.fused_tail() && storage_f32_like(c)) ? 1 : 0; return ra; }
 
 // NullSkip of the "table" mode (all null: every direction is projected and read in full)
 NullSkip null_skip(const srukf_ctx* c)
@@ -200,7 +194,7 @@ NullSkip null_skip(const srukf_ctx* c)
 }
 
 // fs->Xr1 for the launch that applies the pending state update (and only once)
-const double* take_xr1(srukf_ctx* c)
+static const double* take_xr1(srukf_ctx* c)
 {
     if (!c->xr1_pending) return nullptr;
     c->xr1_pending = false;
@@ -209,12 +203,14 @@ const double* take_xr1(srukf_ctx* c)
 
 // Replay path: motion step + projection of all sigma points in ONE launch (k_project_motion): workgroup 0 is the motion step,
 // whose results wait beside the state (fs->Xr1, Cmat) until k_gain / the dX job commit them.
-void seq_predict_fused(srukf_ctx* c, int mode)
+void seq_predict_fused(srukf_ctx* c, FrameForm ff)
 {
     const KDims& d = c->d;
-    ProfScope ps(c, mode == 2 ? KC_PROJECT_TABLE : KC_PROJECT_MOTION, 2.0 * 60.0 * d.Na * d.N + 60.0 * d.L, 8.0 * ((double)d.n * d.n / 2 + 2.0 * d.L * 2 * d.N + (double)d.n * 2 * d.N + 8.0 * d.L + 8.0 * d.n));
-    if (mode == 2) srukf_launch_project_table(c->stream, d, c->w, c->p, c->X, c->S, c->sigR, c->Cmat, c->Z, c->DZ, c->fs, rank_args(c, false, c->dbg.pxy2 != 0), null_skip(c));
-    else srukf_launch_project_motion(c->stream, d, c->w, c->p, c->X, c->S, c->sigR, c->Cmat, c->Z, c->DZ, c->fs, rank_args(c));
+    ProfScope ps(c, ff.robot_table ? KC_PROJECT_TABLE : KC_PROJECT_MOTION, 2.0 * 60.0 * d.Na * d.N + 60.0 * d.L, 8.0 * ((double)d.n * d.n / 2 + 2.0 * d.L * 2 * d.N + (double)d.n * 2 * d.N + 8.0 * d.L + 8.0 * d.n));
+    RankArgs ra = rank_args(c);
+    ra.dzperm = (ff.robot_table && ff.pxy2()) ? 1 : 0;          // (k_pxy2 reads DZ in permuted order)
+    if (ff.robot_table) srukf_launch_project_table(c->stream, d, c->w, c->p, c->X, c->S, c->sigR, c->Cmat, c->Z, c->DZ, c->fs, ra, null_skip(c));
+    else srukf_launch_project_motion(c->stream, d, c->w, c->p, c->X, c->S, c->sigR, c->Cmat, c->Z, c->DZ, c->fs, ra);
     c->xr1_pending = true;
 }
 
@@ -225,58 +221,47 @@ void seq_predict_motion(srukf_ctx* c, const double* odo_pair_dev)
     srukf_launch_motion(c->stream, d, c->w, c->p, c->X, c->S, c->sigR, c->Cmat, c->fs, c->odo_seq, odo_pair_dev, rank_args(c));
 }
 
-// fused_stats: the statistics ride on the k_pxy launch of seq_gain (replay path, no host in between)
-void seq_predict_measurement(srukf_ctx* c, bool fused_stats)
+// (from MEAS_PLAIN on the statistics ride on the k_pxy launch of seq_gain: replay path, no host in between)
+void seq_predict_measurement(srukf_ctx* c, FrameForm ff)
 {
     const KDims& d = c->d;
     {
         ProfScope ps(c, KC_PROJECT, 2.0 * 60.0 * d.Na * d.N, 8.0 * ((double)d.n * d.n / 2 + 2.0 * d.L * 2 * d.N + (double)d.n * 2 * d.N));
         srukf_launch_project(c->stream, d, c->w, c->p, c->X, c->S, c->sigR, c->Z, c->DZ, c->fs);
     }
-    if (!fused_stats) {
+    if (!ff.fused_stats()) {
         ProfScope ps(c, KC_STATS, 30.0 * d.L * d.N, 8.0 * 3.0 * d.L * 2 * d.N);
         srukf_launch_meas_stats(c->stream, d, c->w, c->X, c->sigR, c->Z, c->mpart, c->h, c->Si, c->vis, c->PxyR);
     }
 }
 
-// one refactorisation  S <- gmw(S^T S - U[ub:ue] U[ub:ue]^T);  slow = column-by-column path.
-// need_reset: the gamma/xi accumulators were not just cleared by k_gain (SEQUENTIAL mode, fallbacks).
-// frame_tail: the check kernel also records the trajectory row and advances the staged frame counter.
-int gmw_fused_mode() { return g_dbg_gmw_fused; }
-
 int rank_fused_mode() { return g_dbg_rank_fused; }
-
-int rank_fold_mode() { return g_dbg_rank_fold; }
 
 void shadow_rebuild(srukf_ctx* c)
 {
     if (c->red_r > 0 && c->shadowA) srukf_launch_rank_shadow(c->stream, c->d.n, c->d.np, c->red_r, c->S, c->red_perm, c->shadowA);
 }
 
-bool gmw_plan_persists(const srukf_ctx* c, const GmwPlan& gp) { return gp.workers >= 0 || split_form(c, gp, true); }
-
-bool gmw_use_persist(const srukf_ctx* c) { return gmw_persist_mode() && c->gmw_shared != 2 && gmw_plan_persists(c, c->gplan); }
-
-}  // namespace srukf_impl
+// does a factorisation on plan gp run as persistent launch(es), or as one launch per 64-row panel?  (the filter at all: gmw_use_persist)
+static bool gmw_plan_persists(const srukf_ctx* c, const GmwPlan& gp) { return gp.workers >= 0 || split_form(c, gp, true); }
+static bool gmw_use_persist(const srukf_ctx* c) { return gmw_persist_mode() && c->gmw_shared != 2 && gmw_plan_persists(c, c->gplan); }
+bool plan_persists(const srukf_ctx* c, const GmwPlan& gp) { return gmw_use_persist(c) && gmw_plan_persists(c, gp); }
 
 // SRUKF_GPU_SHARED: how many persistent launches share the GPU (each keeps to 1 / tenants of the CUs; the gate admits that many)
 // (per context: srukf_run_frames_batch picks it from the number of filters it runs — one tenant per filter up to SRUKF_MAX_TENANTS; srukf_set_exclusive alone uses the
 //  process-wide default of srukf_debug_set "shared_tenants")
-
-namespace srukf_impl {
-
-int plan_tenants(const srukf_ctx* c) { return c->gmw_shared == 1 ? c->shared_tenants : 1; }
-
+static int plan_tenants(const srukf_ctx* c) { return c->gmw_shared == 1 ? c->shared_tenants : 1; }
 int gate_limit(const srukf_ctx* c) { return c->gmw_shared == 1 ? c->shared_tenants : 0; }
 
 // Tail of every rank-aware refactorisation: factor rows (c->G, permuted order) -> S and the permuted copy, checks, frame tail.
 // fp32 storage: S, X and the permuted copy are rounded to the stored values first, and the trajectory row is taken from those
 // (as the full-rank form does: quantize_state before the tail).
-// table: "table" mode of the replay — the tail also prepares the next frame's table of robot poses (k_rank_expand)
-// fuse: "fused tail" mode — this launch also projects the next frame's sigma points (k_rank_expand<2>)
-void rank_expand(srukf_ctx* c, bool frame_tail, bool table, bool fuse)
+// ff.robot_table: the tail also prepares the next frame's table of robot poses (k_rank_expand)
+// ff.fused_tail(): this launch also projects the next frame's sigma points (k_rank_expand<2>)
+static void rank_expand(srukf_ctx* c, const RefactorRequest& rq, FrameForm ff)
 {
     const int n = c->d.n, np = c->d.np;
+    const bool frame_tail = rq.kind == RefactorRequest::FRAME_TAIL, table = ff.robot_table, fuse = ff.fused_tail();
     const bool f32s = c->storage != SRUKF_STORAGE_F64;            // (the mixed mode stores floats as well: the launches behind the tail round, as for fp32 storage without "fused tail" mode)
     const bool f32fuse = storage_f32_like(c) && fuse && table && frame_tail;      // fp32 storage in "fused tail" mode: the launch rounds what it writes (no k_quantize / k_rank_round / k_traj behind it)
     const bool f32 = f32s && !f32fuse;
@@ -294,9 +279,6 @@ void rank_expand(srukf_ctx* c, bool frame_tail, bool table, bool fuse)
     }
 }
 
-}  // namespace srukf_impl
-
-// the rank-aware replay whose owners form their tiles of S^T S - U U^T themselves (seq_refactor below): what a whole staged frame takes
 // How many tiles per worker (in percent) the owners' fold accepts.  A filter that has the GPU to itself: 106 = about one tile per worker (measured in round 2: with two
 // tiles per worker, both to be formed before the first step, the exclusive replay loses — N = 300: 1 544 against 1 663 frames/s; srukf_debug_set "fold_tiles_pct").
 // A filter that shares the GPU (three or four tenants of 256 / tenants CUs: two register tiles per worker): 200 — measured in round 4 at N = 200, four filters and four
@@ -304,23 +286,18 @@ void rank_expand(srukf_ctx* c, bool frame_tail, bool table, bool fuse)
 // split-K k_syrk over the kept rows 13 100 but then the results differ in rounding from the same filter running alone.
 static int fold_tiles_pct(const srukf_ctx* c) { return c->gmw_shared == 1 ? 200 : 106; }
 
-namespace srukf_impl {
-
-bool replay_red_fused(const srukf_ctx* c)
+static bool replay_red_fused(const srukf_ctx* c)
 {
     return c->red_r > 0 && c->storage != SRUKF_STORAGE_F32_MIXED && c->shadowA && c->w.wc0 == c->w.wm0 && gmw_use_persist(c) &&
            c->gplan_red.workers >= 0 && c->gplan_red.nreal <= c->gplan_red.workers * fold_tiles_pct(c) / 100 && c->gplan_red.T >= 16 &&
-           !c->debug_starve && gmw_fused_mode() && rank_fused_mode() && rank_fold_mode();
+           !c->debug_starve && g_dbg_gmw_fused && rank_fused_mode() && g_dbg_rank_fold;
 }
+
+// RF_PERMUTED_SYRK as far as "table" mode may build on it ("table_perm" 0: the form runs, "table" mode does not); srukf_debug_get "plan_red_perm" reports THIS
+bool replay_red_perm(const srukf_ctx* c) { return c->dbg.table_perm && refactor_form(c, refactor_frame_tail(c)).form == RF_PERMUTED_SYRK; }
 
 // 0: k_motion + k_project; 1: k_project_motion (motion workgroup + projection with the robot part inline); 2: "table" (k_project_table: the
-// previous frame's tail prepared the robot part of every sigma point) — only where the tail is k_rank_expand on fp64 storage
-// ... or forms them with k_syrk over the kept rows, still in permuted order (memory tiles, two tiles per worker, one launch per panel: seq_refactor's second branch)
-bool replay_red_perm(const srukf_ctx* c)
-{
-    return c->red_r > 0 && (c->storage != SRUKF_STORAGE_F32_MIXED || (c->dbg.mixed_rank && c->A32)) && c->shadowA && c->w.wc0 == c->w.wm0 && rank_fused_mode() && c->dbg.table_perm;
-}
-
+// previous frame's tail prepared the robot part of every sigma point) — only where the tail is k_rank_expand on the permuted operands
 int replay_motion_mode(const srukf_ctx* c)
 {
     // fp32 storage: only as "fused tail" mode (k_rank_expand<2> and the state update round what they write; "table" mode alone has no such form)
@@ -332,15 +309,15 @@ int replay_motion_mode(const srukf_ctx* c)
     return c->dbg.fused_motion;
 }
 
-// "fused tail" mode (default where "table" mode runs with k_pxy2 and NullSkip): k_rank_expand also projects the next frame (k_rank_expand<2>), the frame's motion reduction
-// rides on k_pxy2 (MeasArgs::fmode), k_gain re-centres the robot rows: a frame is k_pxy2, k_gain, k_gmw_persist, k_rank_expand, and only a run's first frame has a projection launch
-bool replay_fuse_mode(const srukf_ctx* c)
+// The form of the next staged frame's measurement half, chosen here and nowhere else ("pxy2" off: "table" mode keeps k_pxy, robot_table).
+// "fused tail" mode: k_rank_expand<2> also projects the next frame, the motion reduction rides on k_pxy2 (MeasArgs::fmode), k_gain re-centres the robot rows
+FrameForm frame_form(const srukf_ctx* c)
 {
-    return replay_motion_mode(c) == 2 && c->dbg.pxy2 && c->dbg.nullskip && c->nskip && c->tail_ok && c->dbg.tail_fuse &&
-           (size_t)c->d.np * sizeof(double) <= 48 * 1024;      // (k_rank_expand<2> keeps a row of the factor in dynamic LDS)
+    const int mode = replay_motion_mode(c);
+    const bool fuse = mode == 2 && c->dbg.pxy2 && c->dbg.nullskip && c->nskip && c->tail_ok && c->dbg.tail_fuse &&
+                      (size_t)c->d.np * sizeof(double) <= 48 * 1024;      // (k_rank_expand<2> keeps a row of the factor in dynamic LDS)
+    return FrameForm{ fuse ? MEAS_FUSED_TAIL : (mode == 2 && c->dbg.pxy2) ? MEAS_TABLE : mode ? MEAS_FUSED_MOTION : MEAS_PLAIN, mode == 2 };
 }
-
-}  // namespace srukf_impl
 
 // Round 5 measured where the head fold pays and where it cannot run at all (scripts/head_fold_sweep.py, scripts/abort_probe.py with the diagnostic build's time stamps):
 //   * every worker's first step waits for ALL head tiles, and the helpers only get the CUs that pivot + workers leave free: with 261 helper jobs on 34 free CUs (N = 266) the
@@ -353,131 +330,152 @@ bool replay_fuse_mode(const srukf_ctx* c)
 //     panel without saying so.
 #define SRUKF_HEAD_FOLD_MIN_FREE_CUS 32
 
-namespace srukf_impl {
+// the helper workgroups of a head fold: one per head tile, per 256 rows of the pending X += dX, per SRUKF_RANK_COLS dropped diagonal entries
+struct HeadJobs { int tiles, dx, gd; int total() const { return tiles + dx + gd; } };
+static HeadJobs head_fold_jobs(const srukf_ctx* c) { return HeadJobs{ c->n_syrk_head_tiles, (c->d.n + 255) / 256, (c->d.n - c->red_r + SRUKF_RANK_COLS - 1) / SRUKF_RANK_COLS }; }
 
-bool head_fold_ok(const srukf_ctx* c)
+static bool head_fold_ok(const srukf_ctx* c)
 {
     const int need = g_dbg_head_fold_free.load() > 0 ? g_dbg_head_fold_free.load() : SRUKF_HEAD_FOLD_MIN_FREE_CUS;
     const int free_cus = c->gplan_red.cus - 1 - c->gplan_red.workers;
-    const int nhelp = c->n_syrk_head_tiles + (c->d.n + 255) / 256 + (c->d.n - c->red_r + SRUKF_RANK_COLS - 1) / SRUKF_RANK_COLS;       // as seq_refactor counts them
+    const int nhelp = head_fold_jobs(c).total();
     const bool pays = g_dbg_head_fold_free.load() > 0 || 4 * nhelp <= 9 * free_cus;      // (the A/B switch "head_fold_free" overrides the rounds rule: measurements)
     return c->dbg.head_fold && c->gmw_shared == 0 && free_cus >= need && pays;
 }
 
-void seq_refactor(srukf_ctx* c, int ub, int ue, bool slow, bool keep_backup, bool need_reset, bool frame_tail, bool table, bool fuse)
+// split fold (srukf_gmw_persist.hip, k_gmw_tiles_fold): the rank-aware replay's k_syrk over the kept rows becomes jobs of the split form's tile launch
+static bool split_fold_ok(const srukf_ctx* c)
 {
-    const KDims& d = c->d;
-    const int np = d.np, n = d.n;
-    if (need_reset || slow) {
-        ProfScope ps(c, KC_MISC, 0, 8.0 * np);
-        hipLaunchKernelGGL(k_refactor_reset, dim3((np + 255) / 256), dim3(256), 0, c->stream, np, c->theta, c->fs, 1);
+    // Only while every tile workgroup of the plan can be resident beside the pivot / slab launch (four per CU): they hold their places from dispatch to their row's
+    // last update, and beyond that the forming jobs queue behind waiting workgroups — frames/s with / without the fold: N = 400 2 150 / 1 960, 500 1 385 / 1 350,
+    // 600 (1 190 tile workgroups for 796 places) 855 / 893, 800 393 / 459.
+    const GmwPlan& gp = c->gplan_red;
+    const bool fits = gp.nreal <= 4 * (gp.cus - gp.T) || g_dbg_fold_force.load() != 0;      // ("fold_force": measurements)
+    return c->dbg.split_fold && (fits || c->dbg.split_fold == 2) && c->red_r > 0 && c->storage != SRUKF_STORAGE_F32_MIXED && c->split_fold_list && c->n_split_fold > 0 && c->red_head0_tiles &&
+           !c->debug_starve && !c->dbg.split_record && plan_persists(c, gp) && split_form(c, gp, true);
+}
+
+// Which launches a refactorisation consists of, chosen here and nowhere else: seq_refactor runs it, srukf_debug_get "plan_*" reports it.
+RefactorPlan refactor_form(const srukf_ctx* c, const RefactorRequest& rq)
+{
+    RefactorPlan p = {};
+    const GmwPlan& gr = c->gplan_red;
+    const bool tail = rq.kind == RefactorRequest::FRAME_TAIL;    // the forms on the permuted operands keep no backup and take all of U: frame tails only
+    // rank-aware (srukf_rank.hip): the null directions permuted to the end, only the leading red_Tp panels pivoted (the mixed-precision downdate too, round 6)
+    const bool reduced = c->red_r > 0 && (c->storage != SRUKF_STORAGE_F32_MIXED || (c->dbg.mixed_rank && c->A32));
+    if (tail && replay_red_fused(c)) {                           // (pays with about one tile per worker and T >= 16: docs/LAB_NOTEBOOK.md, round 2)
+        p.form = RF_OWNERS_FOLD; p.persist = true; p.head_fold = head_fold_ok(c);
+    } else if (reduced && tail && c->shadowA && c->w.wc0 == c->w.wm0 && rank_fused_mode()) {
+        p.form = RF_PERMUTED_SYRK; p.persist = plan_persists(c, gr);
+        // own order (a filter that shares the GPU, two register tiles per worker): head rows by k_syrk, every other tile by k_syrk_own in the owners' summation order —
+        // bit for bit what the same filter computes alone.  (Memory tiles and launches per panel keep the split-K k_syrk over the kept rows: nothing to be identical to.)
+        p.own_order = c->gmw_shared == 1 && gmw_use_persist(c) && gr.workers > 0 && gr.T >= 16 && !c->debug_starve && g_dbg_gmw_fused && g_dbg_rank_fold &&
+                      srukf_gmw_register_form(gr.T, gr.Tp, gr.ntiles, gr.workers);
+        p.split_fold = !p.own_order && split_fold_ok(c);
+    } else if (reduced) {
+        p.form = RF_RANK_VIA_PERMUTATION; p.persist = plan_persists(c, gr);
+    } else {
+        // fused only with one tile per worker and T >= 16 (frames/s fused / not: N = 200 2 965 / 2 910, N = 100 5 247 / 5 262, N = 50 9 256 / 9 465, N = 300 1 544 / 1 663)
+        p.form = RF_FULL_RANK; p.persist = gmw_use_persist(c);
+        p.fused = tail && p.persist && c->storage == SRUKF_STORAGE_F64 && c->gplan.ntiles <= c->gplan.workers && c->gplan.T >= 16 && !c->debug_starve && g_dbg_gmw_fused;
     }
-    // Fused form (replay path): k_syrk only for the first block rows, the persistent launch computes the other tiles of
-    // S^T S - U U^T itself while it is already factoring; it reads the filter's S for that, so the factor goes to the
-    // scratch buffer Wf and k_gmw_check copies it into S.
-    // Measured (frames/s, fused against not fused): N = 200 2 965 / 2 910, N = 100 5 247 / 5 262, N = 50 9 256 / 9 465,
-    // N = 300 (two tiles per worker, both to be computed first) 1 544 / 1 663 — so only with one tile per worker and T >= 16.
-    // rank-aware form (srukf_rank.hip): permute the null directions to the end, pivot only the leading red_Tp panels
-    // (the mixed-precision downdate too, round 6: the null pivots its fp32-formed G cannot resolve — what made the full-rank form of the mode diverge — are not factored at all)
-    const bool reduced = !slow && c->red_r > 0 && (c->storage != SRUKF_STORAGE_F32_MIXED || (c->dbg.mixed_rank && c->A32));
-    // ... and on the replay path directly in permuted order from the shadow copy (no full k_syrk, no permutation pass)
-    // (the owners' fold pays with about one tile per worker and T >= 16, as in the full-rank form: frames/s fold / k_syrk over the kept
-    //  rows: N = 100 7 360 / 7 610, N = 200 4 360 / 4 300, N = 300 — two tiles per worker — 2 400 / 2 580)
-    const bool red_fused = reduced && !keep_backup && ub == 0 && ue == d.mp && replay_red_fused(c);
-    if (red_fused) {
-        const double rr = c->red_r, hr = srukf_gmw_head_rows();
-        const double head_flop = 2.0 * hr * n * (hr / 2.0 + d.mp) + 2.0 * (n - rr) * (rr + d.mp), head_byte = 8.0 * ((hr + d.mp) * n + (n - rr) * (rr + d.mp));
-        // head fold (a filter that has the GPU to itself): the head tiles, the pending X += dX and the dropped diagonal are helper
-        // workgroups of the persistent launch instead of a k_syrk launch in front of it (srukf_debug_set "head_fold", 0: two launches)
-        // Only with CUs to spare: the helpers are dispatched behind the pivot and the workers, which spin on their tiles — and the launch's static LDS allows one
-        // workgroup per CU.  A plan whose pivot + workers (nearly) fill the GPU (255-270 tiles) would leave the helpers waiting for a main workgroup to exit:
-        // the pivot's bounded wait would expire.  Such plans keep the k_syrk launch in front (head_fold_ok).
-        const bool head_fold = head_fold_ok(c);
-        if (!head_fold) {
-            // head rows of Gp: K = hr rows of the shadow copy (upper triangular) + the 2N measurement rows; + the dropped diagonal
-            ProfScope ps(c, KC_SYRK, head_flop, head_byte);
-            srukf_launch_syrk(c->stream, d, c->shadowA, c->Utp, 0, d.mp, c->Wf, c->fs, c->syrk_head_tiles, c->n_syrk_head_tiles, dx_src(c), c->X, rank_args(c, table, false, fuse && storage_f32_like(c)), take_xr1(c));
+    return p;
+}
+
+// k_syrk on the permuted operands (shadow copy, U^T with permuted columns) for one tile list, into Gp; spare workgroups: the pending state update, the dropped diagonal
+static void syrk_permuted(srukf_ctx* c, FrameForm ff, const int* tiles, int ntiles)
+{
+    srukf_launch_syrk(c->stream, c->d, c->shadowA, c->Utp, 0, c->d.mp, c->Wf, c->fs, tiles, ntiles, dx_src(c), c->X, tail_rank_args(c, ff), take_xr1(c));
+    c->dx_pending = false;
+}
+
+// RF_OWNERS_FOLD: the owners form their tiles of S^T S - U U^T themselves, in permuted order from the shadow copy (no full k_syrk, no permutation pass)
+static void refactor_owners_fold(srukf_ctx* c, const RefactorRequest& rq, const RefactorPlan& plan, FrameForm ff)
+{
+    const KDims& d = c->d; const int np = d.np, n = d.n;
+    const double rr = c->red_r, hr = srukf_gmw_head_rows();
+    const double head_flop = 2.0 * hr * n * (hr / 2.0 + d.mp) + 2.0 * (n - rr) * (rr + d.mp), head_byte = 8.0 * ((hr + d.mp) * n + (n - rr) * (rr + d.mp));
+    // head fold (head_fold_ok): the head tiles, the pending X += dX and the dropped diagonal are helper workgroups of the persistent launch, not a k_syrk launch in front
+    if (!plan.head_fold) {                                      // head rows of Gp: K = hr rows of the shadow copy + the 2N measurement rows; + the dropped diagonal
+        ProfScope ps(c, KC_SYRK, head_flop, head_byte);
+        syrk_permuted(c, ff, c->syrk_head_tiles, c->n_syrk_head_tiles);
+    }
+    {
+        // factorisation of the leading red_Tp panels (all n columns carried along) + the owners' tiles of S^T S - U U^T
+        // (kept rows below the head x all columns, K <= r and 2N): red_*_flop, update_null_set
+        ProfScope ps(c, KC_GMW_PERSIST, c->red_fac_flop + c->red_own_flop + (plan.head_fold ? head_flop : 0.0), 8.0 * (2.0 * rr * n + (double)d.mp * n));
+        HeadArgs ha = {};
+        if (plan.head_fold) {
+            HeadJobs hj = head_fold_jobs(c);
+            if (!c->dx_pending) hj.dx = 0;
+            ha.tiles = (const int2*)c->syrk_head_tiles; ha.ntiles = hj.tiles; ha.ncrit = c->n_syrk_head_crit;
+            ha.dxp = dx_src(c); ha.X = c->X; ha.xr1 = take_xr1(c); ha.ndx = hj.dx;
+            ha.ra = tail_rank_args(c, ff); ha.ngd = hj.gd;
+            ha.nhelp = hj.total();                              // one helper workgroup per job, behind the pivot and the workers in dispatch order
             c->dx_pending = false;
         }
-        {
-            // factorisation of the leading red_Tp panels (all n columns carried along) + the owners' tiles of S^T S - U U^T
-            // (kept rows below the head x all columns, K <= r and 2N): red_*_flop, update_null_set
-            ProfScope ps(c, KC_GMW_PERSIST, c->red_fac_flop + c->red_own_flop + (head_fold ? head_flop : 0.0), 8.0 * (2.0 * rr * n + (double)d.mp * n));
-            HeadArgs ha = {};
-            if (head_fold) {
-                ha.tiles = (const int2*)c->syrk_head_tiles; ha.ntiles = c->n_syrk_head_tiles; ha.ncrit = c->n_syrk_head_crit;
-                ha.dxp = dx_src(c); ha.X = c->X; ha.xr1 = take_xr1(c); ha.ndx = c->dx_pending ? (n + 255) / 256 : 0;
-                ha.ra = rank_args(c, table, false, fuse && storage_f32_like(c)); ha.ngd = (n - c->red_r + SRUKF_RANK_COLS - 1) / SRUKF_RANK_COLS;
-                ha.nhelp = ha.ntiles + ha.ndx + ha.ngd;             // one helper workgroup per job, behind the pivot and the workers in dispatch order
-                c->dx_pending = false;
+        srukf_launch_gmw_persist_head(c->stream, n, np, c->p.epsilon, c->Wf, c->gplan_red.pans, c->D, c->G, c->gplan_red.sync, c->gplan_red.tiles, c->gplan_red.ntiles,
+                                      c->gplan_red.workers, c->fs, c->shadowA, c->Utp, 0, d.mp, c->red_Tp, kept_rows16(c), gate_limit(c), plan.head_fold ? &ha : nullptr);
+    }
+    ProfScope ps(c, KC_RANK_EXPAND, 0, 8.0 * 2.5 * (double)n * n);
+    rank_expand(c, rq, ff);
+}
+
+// RF_PERMUTED_SYRK: where the owners cannot fold (memory tiles, one launch per panel), still in permuted order: k_syrk over the kept rows only, K <= r, into Gp
+static void refactor_permuted_syrk(srukf_ctx* c, const RefactorRequest& rq, const RefactorPlan& plan, FrameForm ff)
+{
+    const KDims& d = c->d; const int np = d.np, n = d.n;
+    const double rr = c->red_r, rp = 64.0 * c->red_Tp;
+    const bool sfold = plan.split_fold;
+    const double syrk_flop_all = rr * rr * rr / 3.0 + rr * rr * (n - rr) + 2.0 * d.mp * (rr * n - rr * rr / 2.0) + 2.0 * (n - rr) * (rr + d.mp);
+    {
+        ProfScope ps(c, KC_SYRK, sfold ? c->red_head0_flop + 2.0 * (n - rr) * (rr + d.mp) : syrk_flop_all, 8.0 * (rr * n + (double)d.mp * n + rp * n));
+        if (c->storage == SRUKF_STORAGE_F32_MIXED) {
+            // the mixed-precision downdate in the rank-aware form: the kept rows of S in permuted column order (what the stored floats hold: the permuted copy is
+            // rounded with S) and U^T with permuted columns as fp32 operands, K <= r, products on the fp32 matrix pipe, chunk sums in FP64 — only the macro tiles of the
+            // pivoted panels; the state update and the dropped diagonal (FP64, from the same operands) by k_syrk's spare workgroups with an empty tile list
+            if (c->dbg.mixed_bf16 && c->mxr_xt) {
+                // operands as three bf16 pieces each, transposed (K contiguous per column): the products on the bf16 matrix pipe, six per fp32 product
+                srukf_launch_split_bf3(c->stream, c->mxr_krows, np, c->mxr_ktot, 0, c->shadowA, c->mxr_xt, c->mxr_xt_stride);
+                srukf_launch_split_bf3(c->stream, d.mp, np, c->mxr_ktot, c->mxr_krows, c->Utp, c->mxr_xt, c->mxr_xt_stride);
+                srukf_launch_syrk_bf3(c->stream, n, np, d.mp, c->mxr_krows, c->mxr_ktot, c->mxr_xt, c->mxr_xt_stride, c->mxr_tasks, c->mxr_ntasks, c->mxr_tiles, c->mxr_ntiles,
+                                      c->mxr_part, c->Wf, c->fs);
+            } else {
+                srukf_launch_cvt_f32(c->stream, (size_t)c->mxr_krows * np, c->shadowA, c->A32);
+                srukf_launch_cvt_f32(c->stream, (size_t)d.mp * np, c->Utp, c->U32);
+                srukf_launch_syrk32(c->stream, n, np, d.mp, c->A32, c->U32, c->mxr_tasks, c->mxr_ntasks, c->mxr_tiles, c->mxr_ntiles, c->mxr_part, c->Wf, c->fs, c->mxr_krows);
             }
-            srukf_launch_gmw_persist_head(c->stream, n, np, c->p.epsilon, c->Wf, c->gplan_red.pans, c->D, c->G, c->gplan_red.sync, c->gplan_red.tiles, c->gplan_red.ntiles,
-                                          c->gplan_red.workers, c->fs, c->shadowA, c->Utp, 0, d.mp, c->red_Tp, (c->red_r + 15) & ~15, gate_limit(c), head_fold ? &ha : nullptr);
-        }
-        ProfScope ps(c, KC_RANK_EXPAND, 0, 8.0 * 2.5 * (double)n * n);
-        rank_expand(c, frame_tail, table, fuse);
-        return;
+            // ... and BEHIND it, in FP64 from the FP64 operands, the few tiles whose pivots an fp32-formed product cannot resolve (the robot block, the shared anchor:
+            // mxr_f64_tiles) — they overwrite what the fp32 launch left there
+            syrk_permuted(c, ff, c->mxr_f64_tiles, c->dbg.mixed_f64_robot ? c->mxr_n_f64_tiles : 0);
+        } else if (plan.own_order) {
+            syrk_permuted(c, ff, c->syrk_head_tiles, c->n_syrk_head_tiles);
+            srukf_launch_syrk_own(c->stream, n, np, c->shadowA, c->Utp, 0, d.mp, kept_rows16(c), c->Wf, c->fs, c->gplan_red.tiles, c->gplan_red.ntiles, c->red_Tp);
+        } else if (sfold && c->dbg.split_fold != 2)
+            // split fold: block row 0 and tile (1, 1) here (+ the state update and the dropped diagonal, as always); the tile launch of the pair forms the rest
+            syrk_permuted(c, ff, c->red_head0_tiles, c->n_red_head0_tiles);
+        else
+            syrk_permuted(c, ff, c->red_syrk_tiles, c->n_red_syrk_tiles);
     }
-    // ... or, where the owners cannot fold (memory tiles: more than two tiles per worker; one launch per panel), still in permuted
-    // order: k_syrk over the tiles of the kept rows only, K <= r, straight into Gp
-    const bool red_perm = reduced && !red_fused && !keep_backup && ub == 0 && ue == d.mp && c->shadowA && c->w.wc0 == c->w.wm0 && rank_fused_mode();
-    if (red_perm) {
-        const double rr = c->red_r, rp = 64.0 * c->red_Tp;
-        // A filter that shares the GPU and whose workers own two register tiles (three or four tenants): the head rows by k_syrk, every other tile by k_syrk_own in
-        // the summation order of the owners' fold — bit for bit what the same filter computes when it runs alone (its owners fold) — then the persistent launch reads
-        // its tiles from Gp.  (The memory-tile form and the launches per panel keep the split-K k_syrk over the kept rows: nothing to be identical to.)
-        const bool own_order = c->gmw_shared == 1 && gmw_use_persist(c) && c->gplan_red.workers > 0 && c->gplan_red.T >= 16 && !c->debug_starve && gmw_fused_mode() && rank_fold_mode() &&
-                               srukf_gmw_register_form(c->gplan_red.T, c->gplan_red.Tp, c->gplan_red.ntiles, c->gplan_red.workers);
-        const bool sfold = !own_order && split_fold_ok(c);
-        const double syrk_flop_all = rr * rr * rr / 3.0 + rr * rr * (n - rr) + 2.0 * d.mp * (rr * n - rr * rr / 2.0) + 2.0 * (n - rr) * (rr + d.mp);
-        {
-            ProfScope ps(c, KC_SYRK, sfold ? c->red_head0_flop + 2.0 * (n - rr) * (rr + d.mp) : syrk_flop_all, 8.0 * (rr * n + (double)d.mp * n + rp * n));
-            if (c->storage == SRUKF_STORAGE_F32_MIXED) {
-                // the mixed-precision downdate in the rank-aware form: the kept rows of S in permuted column order (what the stored floats hold: the permuted copy is
-                // rounded with S) and U^T with permuted columns as fp32 operands, K <= r, products on the fp32 matrix pipe, chunk sums in FP64 — only the macro tiles of the
-                // pivoted panels; the state update and the dropped diagonal (FP64, from the same operands) by k_syrk's spare workgroups with an empty tile list
-                if (c->dbg.mixed_bf16 && c->mxr_xt) {
-                    // operands as three bf16 pieces each, transposed (K contiguous per column): the products on the bf16 matrix pipe, six per fp32 product
-                    srukf_launch_split_bf3(c->stream, c->mxr_krows, np, c->mxr_ktot, 0, c->shadowA, c->mxr_xt, c->mxr_xt_stride);
-                    srukf_launch_split_bf3(c->stream, d.mp, np, c->mxr_ktot, c->mxr_krows, c->Utp, c->mxr_xt, c->mxr_xt_stride);
-                    srukf_launch_syrk_bf3(c->stream, n, np, d.mp, c->mxr_krows, c->mxr_ktot, c->mxr_xt, c->mxr_xt_stride, c->mxr_tasks, c->mxr_ntasks, c->mxr_tiles, c->mxr_ntiles,
-                                          c->mxr_part, c->Wf, c->fs);
-                } else {
-                    srukf_launch_cvt_f32(c->stream, (size_t)c->mxr_krows * np, c->shadowA, c->A32);
-                    srukf_launch_cvt_f32(c->stream, (size_t)d.mp * np, c->Utp, c->U32);
-                    srukf_launch_syrk32(c->stream, n, np, d.mp, c->A32, c->U32, c->mxr_tasks, c->mxr_ntasks, c->mxr_tiles, c->mxr_ntiles, c->mxr_part, c->Wf, c->fs, c->mxr_krows);
-                }
-                // ... and BEHIND it, in FP64 from the FP64 operands, the few tiles whose pivots an fp32-formed product cannot resolve (the robot block, the shared anchor:
-                // mxr_f64_tiles) — they overwrite what the fp32 launch left there
-                srukf_launch_syrk(c->stream, d, c->shadowA, c->Utp, 0, d.mp, c->Wf, c->fs, c->mxr_f64_tiles, c->dbg.mixed_f64_robot ? c->mxr_n_f64_tiles : 0,
-                                  dx_src(c), c->X, rank_args(c, table, false, fuse && storage_f32_like(c)), take_xr1(c));
-            } else if (own_order) {
-                srukf_launch_syrk(c->stream, d, c->shadowA, c->Utp, 0, d.mp, c->Wf, c->fs, c->syrk_head_tiles, c->n_syrk_head_tiles, dx_src(c), c->X, rank_args(c, table, false, fuse && storage_f32_like(c)), take_xr1(c));
-                srukf_launch_syrk_own(c->stream, n, np, c->shadowA, c->Utp, 0, d.mp, (c->red_r + 15) & ~15, c->Wf, c->fs, c->gplan_red.tiles, c->gplan_red.ntiles, c->red_Tp);
-            } else if (sfold && c->dbg.split_fold != 2)
-                // split fold: block row 0 and tile (1, 1) here (+ the state update and the dropped diagonal, as always); the tile launch of the pair forms the rest
-                srukf_launch_syrk(c->stream, d, c->shadowA, c->Utp, 0, d.mp, c->Wf, c->fs, c->red_head0_tiles, c->n_red_head0_tiles, dx_src(c), c->X, rank_args(c, table, false, fuse && storage_f32_like(c)), take_xr1(c));
-            else
-            srukf_launch_syrk(c->stream, d, c->shadowA, c->Utp, 0, d.mp, c->Wf, c->fs, c->red_syrk_tiles, c->n_red_syrk_tiles, dx_src(c), c->X, rank_args(c, table, false, fuse && storage_f32_like(c)), take_xr1(c));
-            c->dx_pending = false;
-        }
-        {
-            ProfScope ps(c, gmw_use_persist(c) && gmw_plan_persists(c, c->gplan_red) ? KC_GMW_PERSIST : KC_GMW_TRAIL, c->red_fac_flop + (sfold ? syrk_flop_all - c->red_head0_flop : 0.0), 8.0 * 2.0 * rp * n);
-            launch_gmw_fast(c, c->Wf, c->G, true, sfold);
-        }
-        ProfScope ps(c, KC_RANK_EXPAND, 0, 8.0 * 2.5 * (double)n * n);
-        rank_expand(c, frame_tail, table, fuse);
-        return;
+    {
+        ProfScope ps(c, plan.persist ? KC_GMW_PERSIST : KC_GMW_TRAIL, c->red_fac_flop + (sfold ? syrk_flop_all - c->red_head0_flop : 0.0), 8.0 * 2.0 * rp * n);
+        launch_gmw_fast(c, c->Wf, c->G, sfold ? GMW_KEPT_PANELS_SPLIT_FOLD : GMW_KEPT_PANELS);
     }
-    const bool fused = !reduced && !slow && !keep_backup && gmw_use_persist(c) && ub == 0 && ue == d.mp && c->storage == SRUKF_STORAGE_F64 &&
-                       c->gplan.ntiles <= c->gplan.workers && c->gplan.T >= 16 &&
-                       !c->debug_starve && gmw_fused_mode();
+    ProfScope ps(c, KC_RANK_EXPAND, 0, 8.0 * 2.5 * (double)n * n);
+    rank_expand(c, rq, ff);
+}
+
+// G = S^T S - U[ub:ue] U[ub:ue]^T in state order; plan.fused: only the head rows (returns the share k_syrk computed).  Checked requests keep a copy in Gbak.
+static double product_state_order(srukf_ctx* c, const RefactorRequest& rq, const RefactorPlan& plan)
+{
+    const KDims& d = c->d; const int np = d.np, n = d.n, ub = rq.ub, ue = rq.ue;
+    const bool fused = plan.fused;
     const double nn = n;
     const double syrk_flop = nn * nn * nn / 3.0 + nn * nn * (ue - ub), syrk_byte = 8.0 * (nn * nn + (double)(ue - ub) * nn);
-    const double head_frac = fused ? fmin(1.0, 2.0 * srukf_gmw_head_rows() / nn) : 1.0;      // share of the tiles k_syrk still computes (rows / n, upper triangle)
+    const double head_frac = fused ? fmin(1.0, 2.0 * srukf_gmw_head_rows() / nn) : 1.0;      // rows / n, upper triangle
     if (c->storage == SRUKF_STORAGE_F32_MIXED && ub == 0 && ue == d.mp && !(c->dbg.mixed_rank && c->A32)) {
         // mixed precision, round 2's full-rank form (study: "mixed_rank" 0): the fp32 state S32 and U^T rounded once, products on the fp32 matrix pipe, chunk sums in FP64.
-        // (In the rank-aware form of the mode only the staged replay's branch above forms the product in fp32; whatever comes through here — the step-wise calls, a
+        // (In the rank-aware form of the mode only RF_PERMUTED_SYRK forms the product in fp32; whatever comes through here — the step-wise calls, a
         //  flagged frame's repeat on the exact path — forms it in FP64 from the FP64 working copies of the stored floats: the exact path must not divide fp32 noise.)
         ProfScope ps(c, KC_SYRK, syrk_flop, 4.0 * (nn * nn + (double)(ue - ub) * nn) + 8.0 * nn * nn / 2);
         if (c->dx_pending) srukf_launch_gain_dx(c->stream, n, np, c->dxp, c->X, take_xr1(c));
@@ -491,76 +489,102 @@ void seq_refactor(srukf_ctx* c, int ub, int ue, bool slow, bool keep_backup, boo
                           fused ? c->n_syrk_head_tiles : c->n_syrk_tiles, dx_src(c), c->X, RankArgs{}, take_xr1(c));
         c->dx_pending = false;
     }
-    if (keep_backup) hipMemcpyAsync(c->Gbak, c->G, sizeof(double) * (size_t)np * np, hipMemcpyDeviceToDevice, c->stream);
-    if (reduced) {
-        // Gp = Pi^T G Pi into Wf (+ its diagonal), factor the leading red_Tp panels of Gp with the factor rows going to G (scratch
-        // now), then back to state order with the theta check, the null-direction check and the frame tail in one kernel
-        {
-            ProfScope ps(c, KC_MISC, 0, 16.0 * nn * nn);
-            hipLaunchKernelGGL(k_sym_permute, dim3(np), dim3(256), 0, c->stream, n, np, c->G, np, c->Wf, c->red_perm);
-            srukf_launch_rank_diag(c->stream, n, np, c->G, c->red_perm, c->gdiag);
-        }
-        {
-            const double rr = 64.0 * c->red_Tp;
-            ProfScope ps(c, gmw_use_persist(c) && gmw_plan_persists(c, c->gplan_red) ? KC_GMW_PERSIST : KC_GMW_TRAIL, rr * rr * rr / 3.0 + rr * rr * (nn - rr) + rr * (nn - rr) * (nn - rr) / 2.0,
-                         8.0 * (rr * nn));
-            launch_gmw_fast(c, c->Wf, c->G, true);
-        }
-        ProfScope ps(c, KC_GMW_CHECK, 0, 8.0 * nn * nn);
-        rank_expand(c, frame_tail);
-        return;
+    if (rq.kind != RefactorRequest::FRAME_TAIL) hipMemcpyAsync(c->Gbak, c->G, sizeof(double) * (size_t)np * np, hipMemcpyDeviceToDevice, c->stream);
+    return head_frac;
+}
+
+// RF_RANK_VIA_PERMUTATION: Gp = Pi^T G Pi into Wf (+ its diagonal), factor the leading red_Tp panels of Gp with the factor rows going to G (scratch
+// now), then back to state order with the theta check, the null-direction check and the frame tail in one kernel
+static void refactor_via_permutation(srukf_ctx* c, const RefactorRequest& rq, const RefactorPlan& plan)
+{
+    const int np = c->d.np, n = c->d.n;
+    const double nn = n;
+    product_state_order(c, rq, plan);
+    {
+        ProfScope ps(c, KC_MISC, 0, 16.0 * nn * nn);
+        launch_sym_permute(c->stream, n, np, c->G, np, c->Wf, c->red_perm);
+        srukf_launch_rank_diag(c->stream, n, np, c->G, c->red_perm, c->gdiag);
     }
-    if (!slow) {
-        // 64-row panels: j0 = -64 factors the first 64x64 region, then one launch per panel
-        // per panel: trailing update 64*r2^2 (upper half, 2 flop) + three-stage slab recompute + next 64x64 diagonal region
-        auto panel_flop = [&](int j0) { const double r2 = np - j0 - 64; return j0 < 0 ? 64.0 * 64.0 * 64.0 / 3.0 : 64.0 * r2 * r2 + 3.0 * 2.0 * 32.0 * 32.0 * r2 + 64.0 * 64.0 * 64.0 / 3.0; };
-        auto panel_byte = [&](int j0) { const double r2 = np - j0 - 64; return 8.0 * (r2 * r2 + 2.0 * 64.0 * r2); };
-        if (gmw_use_persist(c)) {
-            double fl = 0.0, by = 0.0;
-            for (int j0 = -64; j0 + 64 < np; j0 += 64) { fl += panel_flop(j0); by += panel_byte(j0); }
-            ProfScope ps(c, KC_GMW_PERSIST, fl + syrk_flop * (1.0 - head_frac), by + syrk_byte * (1.0 - head_frac));
-            if (fused) srukf_launch_gmw_persist(c->stream, n, np, c->p.epsilon, c->G, c->gplan.pans, c->D, c->Wf, c->gplan.sync, c->gplan.tiles, c->gplan.ntiles,
-                                                c->gplan.workers, c->fs, c->S, c->Ut, ub, ue, 0, 0, gate_limit(c));
-            else launch_gmw_fast(c, c->G, c->S);
-        } else {
-            int pb = 0;
-            for (int j0 = -64; j0 + 64 < np; j0 += 64, pb ^= 1) {
-                ProfScope ps(c, KC_GMW_TRAIL, panel_flop(j0), panel_byte(j0));
-                srukf_launch_gmw_step64(c->stream, n, np, j0, c->p.epsilon, c->G, c->pan[pb ^ 1], c->pan[pb], c->D, c->S, c->fs);
-            }
-        }
-        quantize_state(c);
-        ProfScope ps(c, KC_GMW_CHECK, 0, 8.0 * (double)n * n / 2);
-        srukf_launch_gmw_check(c->stream, n, np, c->D, fused ? c->Wf : c->S, c->fs, c->X, frame_tail ? 1 : 0, fused ? c->S : nullptr);
+    {
+        const double rr = 64.0 * c->red_Tp;
+        ProfScope ps(c, plan.persist ? KC_GMW_PERSIST : KC_GMW_TRAIL, rr * rr * rr / 3.0 + rr * rr * (nn - rr) + rr * (nn - rr) * (nn - rr) / 2.0, 8.0 * (rr * nn));
+        launch_gmw_fast(c, c->Wf, c->G, GMW_KEPT_PANELS);
+    }
+    ProfScope ps(c, KC_GMW_CHECK, 0, 8.0 * nn * nn);
+    rank_expand(c, rq, FORM_PLAIN);      // (a frame tail on this form never runs "table" mode: replay_motion_mode)
+}
+
+// RF_FULL_RANK: every pivot factored.  fused (replay path): k_syrk only for the first block rows, the persistent launch computes the other tiles of S^T S - U U^T
+// itself while it is already factoring; it reads the filter's S for that, so the factor goes to the scratch buffer Wf and k_gmw_check copies it into S.
+static void refactor_full_rank(srukf_ctx* c, const RefactorRequest& rq, const RefactorPlan& plan)
+{
+    const int np = c->d.np, n = c->d.n;
+    const double nn = n;
+    const bool fused = plan.fused;
+    const double head_frac = product_state_order(c, rq, plan);
+    const double syrk_flop = nn * nn * nn / 3.0 + nn * nn * (rq.ue - rq.ub), syrk_byte = 8.0 * (nn * nn + (double)(rq.ue - rq.ub) * nn);
+    // 64-row panels: j0 = -64 factors the first 64x64 region, then one launch per panel
+    // per panel: trailing update 64*r2^2 (upper half, 2 flop) + three-stage slab recompute + next 64x64 diagonal region
+    auto panel_flop = [&](int j0) { const double r2 = np - j0 - 64; return j0 < 0 ? 64.0 * 64.0 * 64.0 / 3.0 : 64.0 * r2 * r2 + 3.0 * 2.0 * 32.0 * 32.0 * r2 + 64.0 * 64.0 * 64.0 / 3.0; };
+    auto panel_byte = [&](int j0) { const double r2 = np - j0 - 64; return 8.0 * (r2 * r2 + 2.0 * 64.0 * r2); };
+    if (plan.persist) {
+        double fl = 0.0, by = 0.0;
+        for (int j0 = -64; j0 + 64 < np; j0 += 64) { fl += panel_flop(j0); by += panel_byte(j0); }
+        ProfScope ps(c, KC_GMW_PERSIST, fl + syrk_flop * (1.0 - head_frac), by + syrk_byte * (1.0 - head_frac));
+        if (fused) srukf_launch_gmw_persist(c->stream, n, np, c->p.epsilon, c->G, c->gplan.pans, c->D, c->Wf, c->gplan.sync, c->gplan.tiles, c->gplan.ntiles,
+                                            c->gplan.workers, c->fs, c->S, c->Ut, rq.ub, rq.ue, 0, 0, gate_limit(c));
+        else launch_gmw_fast(c, c->G, c->S, GMW_ALL_PANELS);
     } else {
-        ProfScope ps(c, KC_GMW_COL, (double)n * n * n / 3.0, 8.0 * (double)n * n * n / 3.0);
-        exact_path(c, c->G, c->S);
-        quantize_state(c);
-        if (frame_tail) srukf_launch_traj(c->stream, d, c->X, c->S, c->fs, nullptr, 1);
+        int pb = 0;
+        for (int j0 = -64; j0 + 64 < np; j0 += 64, pb ^= 1) {
+            ProfScope ps(c, KC_GMW_TRAIL, panel_flop(j0), panel_byte(j0));
+            srukf_launch_gmw_step64(c->stream, n, np, j0, c->p.epsilon, c->G, c->pan[pb ^ 1], c->pan[pb], c->D, c->S, c->fs);
+        }
+    }
+    quantize_state(c);
+    {
+        ProfScope ps(c, KC_GMW_CHECK, 0, 8.0 * (double)n * n / 2);      // (frame tail: the check kernel also records the trajectory row and advances the frame counter)
+        srukf_launch_gmw_check(c->stream, n, np, c->D, fused ? c->Wf : c->S, c->fs, c->X, rq.kind == RefactorRequest::FRAME_TAIL ? 1 : 0, fused ? c->S : nullptr);
     }
     shadow_rebuild(c);                                 // S was rewritten by a path that does not keep the permuted copy in step
 }
 
-// Blocked fast path (or, slow, the exact column path) on an arbitrary matrix buffer: Gbuf (upper triangle,
-// destroyed) -> upper-triangular factor rows in Sout (whose lower triangle must already be zero).
-// split fold (srukf_gmw_persist.hip, k_gmw_tiles_fold): the rank-aware replay's k_syrk over the kept rows becomes jobs of the split form's tile launch
-bool split_fold_ok(const srukf_ctx* c)
+void seq_refactor(srukf_ctx* c, const RefactorRequest& rq, FrameForm ff)
 {
-    // Only while every tile workgroup of the plan can be resident beside the pivot / slab launch (four per CU): they hold their places from dispatch to their row's
-    // last update, and beyond that the forming jobs queue behind waiting workgroups — frames/s with / without the fold: N = 400 2 150 / 1 960, 500 1 385 / 1 350,
-    // 600 (1 190 tile workgroups for 796 places) 855 / 893, 800 393 / 459.
-    const GmwPlan& gp = c->gplan_red;
-    const bool fits = gp.nreal <= 4 * (gp.cus - gp.T) || g_dbg_fold_force.load() != 0;      // ("fold_force": measurements)
-    return c->dbg.split_fold && (fits || c->dbg.split_fold == 2) && c->red_r > 0 && c->storage != SRUKF_STORAGE_F32_MIXED && c->split_fold_list && c->n_split_fold > 0 && c->red_head0_tiles &&
-           !c->debug_starve && !c->dbg.split_record && gmw_use_persist(c) && gmw_plan_persists(c, gp) && split_form(c, gp, true);
+    if (rq.kind == RefactorRequest::SEQ_COLUMN) {               // the gamma/xi accumulators were not just cleared by k_gain
+        ProfScope ps(c, KC_MISC, 0, 8.0 * c->d.np);
+        launch_refactor_reset(c->stream, c->d.np, c->theta, c->fs, 1);
+    }
+    const RefactorPlan plan = refactor_form(c, rq);
+    switch (plan.form) {
+    case RF_OWNERS_FOLD: refactor_owners_fold(c, rq, plan, ff); break;
+    case RF_PERMUTED_SYRK: refactor_permuted_syrk(c, rq, plan, ff); break;
+    case RF_RANK_VIA_PERMUTATION: refactor_via_permutation(c, rq, plan); break;
+    case RF_FULL_RANK: refactor_full_rank(c, rq, plan); break;
+    }
 }
 
-void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, bool reduced, bool fold)
+// A flagged refactorisation again from the backup its checked request kept: what goes in front of the caller's exact_path + quantize_state (traj_base: staged form)
+int exact_repeat_begin(srukf_ctx* c, int frame, double* traj_base)
+{
+    const size_t np = c->d.np;
+    launch_set_frame(c->stream, c->fs, frame, 1);
+    if (traj_base) hipLaunchKernelGGL(k_set_traj, dim3(1), dim3(1), 0, c->stream, c->fs, traj_base);
+    launch_refactor_reset(c->stream, (int)np, c->theta, c->fs, 0);
+    HIPCHK(c, hipMemcpyAsync(c->G, c->Gbak, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream));
+    return SRUKF_OK;
+}
+
+// The blocked factorisation on an arbitrary matrix buffer: Gbuf (upper triangle, destroyed) -> upper-triangular factor rows in Sout (whose lower triangle must already
+// be zero).  which: every panel (the full plan), or the leading red_Tp panels of a permuted matrix (the rank-aware plan; split fold: its tile launch forms tiles too)
+void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, GmwPanels which)
 {
     const int np = c->d.np, n = c->d.n;
+    const bool reduced = which != GMW_ALL_PANELS, fold = which == GMW_KEPT_PANELS_SPLIT_FOLD;
     const GmwPlan& gp = reduced ? c->gplan_red : c->gplan;
     const int Tp = reduced ? c->red_Tp : np / 64;
-    if (gmw_use_persist(c) && gmw_plan_persists(c, gp)) {
+    const int krows = reduced ? kept_rows16(c) : 0;              // where the kept pivots end — the last pivoted panel is not factored beyond them
+    if (plan_persists(c, gp)) {
         // srukf_debug_starve_workers (tests only): launch without workers, as if the GPU were taken — the pivot's bounded wait
         // expires, the frame is flagged and repeated on the exact path, and the context falls back to one launch per panel
         const int workers = c->debug_starve == 1 ? 0 : gp.workers;   // (2: only a split-form pair is starved — the tier below it then runs undisturbed)
@@ -569,19 +593,17 @@ void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, bool reduced, boo
             if (c->dbg.split_record) hipMemcpyAsync(c->Gbak, Gbuf, sizeof(double) * (size_t)np * np, hipMemcpyDeviceToDevice, c->stream);
             hipEventRecord(c->ev_fork, c->stream);
             hipStreamWaitEvent(c->side, c->ev_fork, 0);
-            if (fold && reduced) c->split_fold_seqs++;
-            if (fold && reduced)
-                srukf_launch_gmw_split_fold(c->stream, c->side, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, c->split_fold_list, c->n_split_fold, c->fs, Tp, (c->red_r + 15) & ~15,
+            if (fold) {
+                c->split_fold_seqs++;
+                srukf_launch_gmw_split_fold(c->stream, c->side, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, c->split_fold_list, c->n_split_fold, c->fs, Tp, krows,
                                             c->gsW, c->gsL, c->shadowA, c->Utp, c->d.mp);
-            else
-            srukf_launch_gmw_split(c->stream, c->side, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, gp.tiles, gp.ntiles, c->fs, Tp, reduced ? ((c->red_r + 15) & ~15) : 0, c->gsW, c->gsL, c->debug_starve ? 1 : 0);
+            } else
+                srukf_launch_gmw_split(c->stream, c->side, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, gp.tiles, gp.ntiles, c->fs, Tp, krows, c->gsW, c->gsL, c->debug_starve ? 1 : 0);
             hipEventRecord(c->ev_join, c->side);
             hipStreamWaitEvent(c->stream, c->ev_join, 0);
             return;
         }
-        // (krows: where the kept pivots end — the last pivoted panel is not factored beyond them)
-        srukf_launch_gmw_persist(c->stream, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, gp.tiles, gp.ntiles, workers, c->fs, nullptr, nullptr, 0, 0, Tp,
-                                 reduced ? ((c->red_r + 15) & ~15) : 0, gate_limit(c));
+        srukf_launch_gmw_persist(c->stream, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, gp.tiles, gp.ntiles, workers, c->fs, nullptr, nullptr, 0, 0, Tp, krows, gate_limit(c));
         return;
     }
     // one launch per panel; rank-aware form: the step after the last pivoted panel still runs (it writes that panel's S rows)
@@ -603,10 +625,10 @@ void run_gmw(srukf_ctx* c, double* Gbuf, double* Sout, bool slow)
 {
     const int np = c->d.np, n = c->d.n;
     if (!slow) {
-        launch_gmw_fast(c, Gbuf, Sout);
+        launch_gmw_fast(c, Gbuf, Sout, GMW_ALL_PANELS);
         srukf_launch_gmw_check(c->stream, n, np, c->D, Sout, c->fs, c->X, 0, nullptr);
     } else {
-        hipLaunchKernelGGL(k_refactor_reset, dim3((np + 255) / 256), dim3(256), 0, c->stream, np, c->theta, c->fs, 0);
+        launch_refactor_reset(c->stream, np, c->theta, c->fs, 0);
         exact_path(c, Gbuf, Sout);
     }
 }
@@ -624,18 +646,18 @@ int refactor_reorder(srukf_ctx* c, int ub, int ue)
     const int np = d.np, n = d.n, r = n - 3 * c->K_new;
     const size_t bytes = sizeof(double) * (size_t)np * np;
     if (!c->Sdis) { if (srukf_dmalloc((void**)&c->Sdis, bytes) != hipSuccess) { c->err = "out of device memory (NEED_REORDER buffer)"; return SRUKF_ERR_NOMEM; } }
-    hipLaunchKernelGGL(k_refactor_reset, dim3((np + 255) / 256), dim3(256), 0, c->stream, np, c->theta, c->fs, 1);
+    launch_refactor_reset(c->stream, np, c->theta, c->fs, 1);
     srukf_launch_syrk(c->stream, d, c->S, c->Ut, ub, ue, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, dx_src(c), c->X, RankArgs{}, take_xr1(c));
     c->dx_pending = false;
     for (int stage = 0; stage < 2; stage++) {
         double* out = stage == 0 ? c->Sdis : c->S;
         if (stage == 1) {
-            hipLaunchKernelGGL(k_refactor_reset, dim3((np + 255) / 256), dim3(256), 0, c->stream, np, c->theta, c->fs, 1);
+            launch_refactor_reset(c->stream, np, c->theta, c->fs, 1);
             srukf_launch_syrk(c->stream, d, c->Sdis, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, nullptr, c->X, RankArgs{}, nullptr);
         }
         for (int slow = 0; slow < 2; slow++) {
-            hipLaunchKernelGGL(k_set_frame, dim3(1), dim3(1), 0, c->stream, c->fs, 0, 1);
-            hipLaunchKernelGGL(k_sym_permute, dim3(np), dim3(256), 0, c->stream, n, np, c->G, np, c->Gbak, stage == 0 ? c->iperm : c->perm);
+            launch_set_frame(c->stream, c->fs, 0, 1);
+            launch_sym_permute(c->stream, n, np, c->G, np, c->Gbak, stage == 0 ? c->iperm : c->perm);
             if (stage == 0) HIPCHK(c, hipMemsetAsync(c->Sdis, 0, bytes, c->stream));
             run_gmw(c, c->Gbak, out, slow != 0);
             if (stage == 0 && r < np) hipLaunchKernelGGL(k_zero_rows, dim3(np - r), dim3(256), 0, c->stream, np, r, c->Sdis);
@@ -648,18 +670,17 @@ int refactor_reorder(srukf_ctx* c, int ub, int ue)
     return SRUKF_OK;
 }
 
-// fused_motion: the frame's motion step ran inside k_project_motion: the statistics take the robot mean from fs->Xr1, k_gain commits Cmat
-// table: "table" mode of the replay — the product on the permuted operands (k_pxy2), k_gain takes it from there
-// first half: the cross covariances (and, riding on the launch, the measurement statistics h / Si / visible; in "fused tail" mode the frame's motion reduction)
-void seq_pxy(srukf_ctx* c, bool fused_stats, bool fused_motion, bool table, bool preamble, bool fmode, bool fold)
+// first half: the cross covariances (riding on the launch: the statistics h / Si / visible, in "fused tail" mode the motion reduction); gf: the gain fold's, or null
+static void launch_pxy(srukf_ctx* c, FrameForm ff, const GainFold& gf)
 {
     const KDims& d = c->d;
     const double nn = d.n;
+    const bool fused_stats = ff.fused_stats(), fused_motion = ff.fused_motion(), table = ff.pxy2(), fmode = ff.fused_tail();
     ProfScope ps(c, table ? KC_PXY2 : KC_PXY, nn * nn * 2.0 * d.N, 8.0 * (nn * nn / 2 + 2.0 * nn * 2 * d.N));
     MeasArgs ms = {};
     // ("fused tail" mode: the statistics are centred on the centre point's robot part, row 0 of the table: the mean does not exist yet)
     const double* xrob = fmode ? c->sigR : fused_motion ? (const double*)((const char*)c->fs + offsetof(FrameScalars, Xr1)) : c->X + (d.n - 4);
-    if (fused_stats) ms = MeasArgs{ c->X, xrob, c->sigR, c->Z, c->mpart, c->h, c->Si, c->vis, c->PxyR, c->fs, (d.N + 31) / 32, table ? null_skip(c) : NullSkip{}, preamble ? 1 : 0,
+    if (fused_stats) ms = MeasArgs{ c->X, xrob, c->sigR, c->Z, c->mpart, c->h, c->Si, c->vis, c->PxyR, c->fs, (d.N + 31) / 32, table ? null_skip(c) : NullSkip{}, fmode ? 1 : 0,
                                     fmode ? 1 : 0, c->Cmat };
     if (fused_stats && c->mirror_next) {                       // step-wise API: the host's pinned copy of h | Si | visible is filled by the statistics jobs themselves
         ms.hmirror = (char*)c->hmeas;
@@ -667,23 +688,17 @@ void seq_pxy(srukf_ctx* c, bool fused_stats, bool fused_motion, bool table, bool
         ms.hseq = c->meas_seq;
         ms.hstamp = (unsigned long long*)(c->hmeas + c->d.mp + 5 * (size_t)c->d.N);       // (the spare words behind h | Si | visible)
     }
-    GainFold gf = {};
-    if (fold && table && fmode) {
-        gf.sync = c->fold_sync; gf.Utp = c->Utp; gf.dxk = c->dxk; gf.z_seq = c->z_seq; gf.m_seq = c->m_seq;
-        gf.DZp = c->DZ; gf.perm = c->red_perm; gf.iperm = c->red_iperm; gf.r = c->red_r; gf.split_b0 = c->pxy2_split_b0;
-        gf.sqeps = storage_f32_like(c) ? (double)(float)sqrt(c->p.epsilon) : sqrt(c->p.epsilon);      // (the null rows of S as they are stored: what seq_gain_only hands k_gain)
-        gf.sc = c->w.wi * c->w.gamma;
-        gf.S = c->S; gf.A = c->shadowA;
-        gf.nmt = d.mp / 64; gf.nbt = d.np / 64; gf.bt_r0 = (c->red_r - 4) / 64; gf.bt_r1 = (c->red_r - 1) / 64; gf.robot_tiles = c->fold_robot_tiles;
-    }
-    if (table) srukf_launch_pxy2(c->stream, d, c->DZ, c->shadowA, c->Utp, c->P1, c->pxy2_tiles, c->n_pxy2_tiles, (c->red_r + 15) & ~15, c->w, ms, gf);
+    if (table) srukf_launch_pxy2(c->stream, d, c->DZ, c->shadowA, c->Utp, c->P1, c->pxy2_tiles, c->n_pxy2_tiles, kept_rows16(c), c->w, ms, gf);
     else srukf_launch_pxy(c->stream, d, c->DZ, c->S, c->Ut, c->pxy_tiles, c->n_pxy_tiles, c->w, ms);
 }
 
+void seq_pxy(srukf_ctx* c, FrameForm ff) { launch_pxy(c, ff, GainFold{}); }
+
 // second half: gains, U^T, slice partials of the state update; z_dev / m_dev: this frame's measurements and matches on the device (null: the staged sequence's)
-void seq_gain_only(srukf_ctx* c, const double* z_dev, const int* m_dev, bool fused_motion, bool table, bool fmode)
+void seq_gain_only(srukf_ctx* c, const double* z_dev, const int* m_dev, FrameForm ff)
 {
     const KDims& d = c->d;
+    const bool fused_motion = ff.fused_motion(), table = ff.pxy2(), fmode = ff.fused_tail();
     ProfScope ps(c, KC_GAIN, 8.0 * d.n * 2 * d.N, 8.0 * 2.0 * d.n * 2 * d.N);
     srukf_launch_gain(c->stream, d, c->w, c->Ut, c->PxyR, c->Si, c->vis, c->h, c->z_seq, z_dev, c->m_seq, m_dev, c->fs, c->dxp, c->X, c->Z, rank_args(c),
                       fused_motion ? c->Cmat : nullptr, c->S, table ? c->P1 : nullptr, c->pxy2_split_b0, c->DZ,
@@ -693,22 +708,28 @@ void seq_gain_only(srukf_ctx* c, const double* z_dev, const int* m_dev, bool fus
     c->dx_pending = true; c->dx_lm = false;           // applied by the next k_syrk launch (seq_refactor)
 }
 
-void seq_gain(srukf_ctx* c, const double* z_dev, const int* m_dev, bool fused_stats, bool fused_motion, bool table, bool preamble, bool fmode)
+void seq_gain(srukf_ctx* c, const double* z_dev, const int* m_dev, FrameForm ff)
 {
     // gain fold: the staged replay's "fused tail" frames (staged measurements, nothing for the host in between) form U^T and the state update inside k_pxy2
-    const bool fold = c->dbg.gain_fold && fmode && table && fused_stats && fused_motion && !z_dev && !m_dev && !c->mirror_next && !c->next_pose_pending &&
+    const bool fold = c->dbg.gain_fold && ff.fused_tail() && !z_dev && !m_dev && !c->mirror_next && !c->next_pose_pending &&
                       c->fold_sync && c->dxk && c->w.wc0 == c->w.wm0 && c->z_seq && c->m_seq;
-    seq_pxy(c, fused_stats, fused_motion, table, preamble, fmode, fold);
+    GainFold gf = {};
+    if (fold) {
+        const KDims& d = c->d;
+        gf.sync = c->fold_sync; gf.Utp = c->Utp; gf.dxk = c->dxk; gf.z_seq = c->z_seq; gf.m_seq = c->m_seq;
+        gf.DZp = c->DZ; gf.perm = c->red_perm; gf.iperm = c->red_iperm; gf.r = c->red_r; gf.split_b0 = c->pxy2_split_b0;
+        gf.sqeps = storage_f32_like(c) ? (double)(float)sqrt(c->p.epsilon) : sqrt(c->p.epsilon);      // (the null rows of S as they are stored: what seq_gain_only hands k_gain)
+        gf.sc = c->w.wi * c->w.gamma;
+        gf.S = c->S; gf.A = c->shadowA;
+        gf.nmt = d.mp / 64; gf.nbt = d.np / 64; gf.bt_r0 = (c->red_r - 4) / 64; gf.bt_r1 = (c->red_r - 1) / 64; gf.robot_tiles = c->fold_robot_tiles;
+    }
+    launch_pxy(c, ff, gf);
     if (fold) { c->dx_pending = true; c->dx_lm = true; c->fold_seqs++; }
-    else seq_gain_only(c, z_dev, m_dev, fused_motion, table, fmode);
+    else seq_gain_only(c, z_dev, m_dev, ff);
 }
-
-}  // namespace srukf_impl
 
 // Which directions of the state are structurally null (srukf_rank.hip)?  Called whenever a state arrives from outside
 // (srukf_set_state*, map changes): row energies of S on the device, the lists on the host.  srukf_debug_set(0, "rank_aware", 0) switches it off.
-
-namespace srukf_impl {
 
 int update_null_set(srukf_ctx* c)
 {
@@ -937,26 +958,19 @@ int set_shared(srukf_ctx* c, int shared, int tenants)
 }
 
 // srukf_debug_set(ctx, "fused_motion", 0): the replay keeps k_motion and k_project as two launches (A/B runs)
-void replay_one_frame(srukf_ctx* c)
+static void replay_one_frame(srukf_ctx* c)
 {
-    const int mode = replay_motion_mode(c);
-    const bool fuse = replay_fuse_mode(c);
-    if (fuse) {
-        // the previous frame's tail (or, for a run's first frame, run_frames_async) projected this frame; its motion reduction rides on k_pxy2
-        c->xr1_pending = true;
-        seq_gain(c, nullptr, nullptr, true, true, true, true, true);
-    } else if (mode) {
-        seq_predict_fused(c, mode);
-        seq_gain(c, nullptr, nullptr, true, true, mode == 2 && c->dbg.pxy2);
-    } else {
+    const FrameForm ff = frame_form(c);
+    // "fused tail" mode: the previous frame's tail (or, for a run's first frame, run_frames_async) projected this frame; its motion reduction rides on k_pxy2
+    if (ff.fused_tail()) c->xr1_pending = true;
+    else if (ff.fused_motion()) seq_predict_fused(c, ff);
+    else {
         seq_predict_motion(c, nullptr);
-        seq_predict_measurement(c, true);
-        seq_gain(c, nullptr, nullptr, true);
+        seq_predict_measurement(c, ff);
     }
-    seq_refactor(c, 0, c->d.mp, false, false, false, true, mode == 2, fuse);
+    seq_gain(c, nullptr, nullptr, ff);
+    seq_refactor(c, refactor_frame_tail(c), ff);
 }
-
-}  // namespace srukf_impl
 
 static int capture_frames(srukf_ctx* c, int nframes, hipGraph_t* g, hipGraphExec_t* ge)
 {
@@ -968,8 +982,6 @@ static int capture_frames(srukf_ctx* c, int nframes, hipGraph_t* g, hipGraphExec
     HIPCHK(c, hipGraphInstantiate(ge, *g, nullptr, nullptr, 0));
     return SRUKF_OK;
 }
-
-namespace srukf_impl {
 
 // the null rows are canonical from here on (a rank-aware frame tail has been issued): captured frames of the other launch sequence are stale
 // fp64 storage only (the float-stored modes keep their rounded copies in step elsewhere); "null_canon" 0: the first frame behind such a factor runs the launch sequence that
@@ -1001,21 +1013,18 @@ static int run_staged_frame_exact(srukf_ctx* c, int frame, double* traj_row)
     auto t0 = now();
     auto lap = [&](const char* what) { if (timing) { hipStreamSynchronize(c->stream); auto t1 = now(); fprintf(stderr, "[exact frame] %s %.0f us\n", what, std::chrono::duration<double, std::micro>(t1 - t0).count()); t0 = t1; } };
     double* tb = traj_row ? traj_row - (size_t)8 * frame : nullptr;
-    hipLaunchKernelGGL(k_set_frame, dim3(1), dim3(1), 0, c->stream, c->fs, frame, 1);
+    launch_set_frame(c->stream, c->fs, frame, 1);
     hipLaunchKernelGGL(k_set_traj, dim3(1), dim3(1), 0, c->stream, c->fs, tb);
     seq_predict_motion(c, nullptr);
-    seq_predict_measurement(c, true);
+    seq_predict_measurement(c, FORM_PLAIN);
     lap("predict");
-    seq_gain(c, nullptr, nullptr, true);
+    seq_gain(c, nullptr, nullptr, FORM_PLAIN);
     lap("gain");
-    seq_refactor(c, 0, d.mp, false, true, false, false);
+    seq_refactor(c, refactor_checked(c), FORM_PLAIN);
     int rc = read_fs(c); if (rc) return rc;
     lap("blocked refactor");
     if (c->hfs->clamp_rows > 0) {
-        hipLaunchKernelGGL(k_set_frame, dim3(1), dim3(1), 0, c->stream, c->fs, frame, 1);
-        hipLaunchKernelGGL(k_set_traj, dim3(1), dim3(1), 0, c->stream, c->fs, tb);
-        hipLaunchKernelGGL(k_refactor_reset, dim3((d.np + 255) / 256), dim3(256), 0, c->stream, d.np, c->theta, c->fs, 0);
-        HIPCHK(c, hipMemcpyAsync(c->G, c->Gbak, sizeof(double) * (size_t)d.np * d.np, hipMemcpyDeviceToDevice, c->stream));
+        rc = exact_repeat_begin(c, frame, tb); if (rc) return rc;
         ProfScope ps(c, KC_GMW_COL, 0, 0);
         exact_path(c, c->G, c->S);
         quantize_state(c);
@@ -1047,13 +1056,7 @@ int srukf_stage_sequence(srukf_ctx* c, int F, const double* odo, const double* z
     const int N = c->d.N;
     HIPCHK(c, hipStreamSynchronize(c->stream));             // frames in flight may still read the staged inputs
     if (c->odo_seq) { srukf_dfree(c->odo_seq); srukf_dfree(c->z_seq); srukf_dfree(c->m_seq); c->odo_seq = nullptr; c->z_seq = nullptr; c->m_seq = nullptr; }
-    if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-    if (c->graph) { hipGraphDestroy(c->graph); c->graph = nullptr; }
-    if (c->graph8_exec) { hipGraphExecDestroy(c->graph8_exec); c->graph8_exec = nullptr; }
-    if (c->graph8) { hipGraphDestroy(c->graph8); c->graph8 = nullptr; }
-    if (c->graphN_exec) { hipGraphExecDestroy(c->graphN_exec); c->graphN_exec = nullptr; }
-    if (c->graphN) { hipGraphDestroy(c->graphN); c->graphN = nullptr; }
-    c->graphN_frames = 0;
+    drop_graphs(c);
     HIPCHK(c, srukf_dmalloc((void**)&c->odo_seq, sizeof(double) * 3 * (F + 1)));
     HIPCHK(c, srukf_dmalloc((void**)&c->z_seq, sizeof(double) * (size_t)F * 2 * N));
     HIPCHK(c, srukf_dmalloc((void**)&c->m_seq, sizeof(int) * (size_t)F * N));
@@ -1102,7 +1105,7 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
         // A state that arrived from outside with structurally null rows that are not (yet) sqrt(EPSILON) e_k — zero rows after the joint initialisation, say: the
         // run's first frame takes the launch sequence that reads those rows as they are (k_project_motion, k_pxy; replay_motion_mode), eagerly; its tail writes the
         // canonical rows, and the frames behind it run the default sequence.
-        hipLaunchKernelGGL(k_set_run, dim3(1), dim3(1), 0, c->stream, c->fs, first, clear, traj);
+        launch_set_run(c->stream, c->fs, first, clear, traj);
         replay_one_frame(c);
         set_null_canonical(c);
         c->async_pending = true; c->phase = 0; c->frame_updated = false; clear = 0;
@@ -1110,11 +1113,12 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
         HIPCHK(c, hipGetLastError());
         if (count == 0) return SRUKF_OK;
     }
-    hipLaunchKernelGGL(k_set_run, dim3(1), dim3(1), 0, c->stream, c->fs, first, clear, traj);
+    launch_set_run(c->stream, c->fs, first, clear, traj);
     // "table" mode: the first frame's table of robot poses (the frames after it get theirs from their predecessor's tail)
-    if (replay_motion_mode(c) == 2) srukf_launch_sigr_rows(c->stream, d, c->w, c->X, c->S, c->sigR, c->fs, c->red_iperm, c->red_r);
+    const FrameForm ff = frame_form(c);
+    if (ff.robot_table) srukf_launch_sigr_rows(c->stream, d, c->w, c->X, c->S, c->sigR, c->fs, c->red_iperm, c->red_r);
     // "fused tail" mode: ... and the first frame's projection (k_project_table); every later frame is projected by its predecessor's tail
-    if (replay_fuse_mode(c)) seq_predict_fused(c, 2);
+    if (ff.fused_tail()) seq_predict_fused(c, ff);
     if (c->use_graph && !c->profiling) {
         // every per-frame argument lives in HBM (frame counter, staged inputs, trajectory base), so ONE
         // captured frame replays for all frames: the 45 launches cost one hipGraphLaunch on the host
@@ -1134,7 +1138,7 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
         for (int f = 0; f < count; f++) replay_one_frame(c);
     }
     // fp32 storage in "fused tail" mode: S and X are rounded as they are written; the float copies (srukf_get_state_f32) once per run
-    if (storage_f32_like(c) && replay_fuse_mode(c)) quantize_state(c);
+    if (storage_f32_like(c) && ff.fused_tail()) quantize_state(c);
     c->async_pending = true;
     c->phase = 0; c->frame_updated = false;
     HIPCHK(c, hipGetLastError());

@@ -17,12 +17,10 @@ void step_ck_join(srukf_ctx* c)
 }
 void step_state_replaced(srukf_ctx* c) { step_ck_join(c); c->frame_updated = false; c->step_uncommitted = false; c->step_fast = false; c->xr1_pending = false; step_invalidate(c); c->f32_stale = false; c->robot_cached = false; }
 
-}  // namespace srukf_impl
-
 // ---- step-wise API: the fast path ---------------------------------------------------------------------------------------------------------------
 // The step-wise calls used to run launch sequences of their own (k_motion, k_project, k_meas_*, k_pxy, k_gain, a full k_syrk, the permutation pass, the persistent launch
 // reading its tiles from memory, k_rank_expand, the rebuild of the permuted copy): ~2 x the staged replay's time per frame before the host round trips.  Where the replay's
-// "fused tail" mode applies (replay_fuse_mode: rank-aware form with canonical null rows; BATCHED, NEEDNOT_REORDER) a step-wise frame now IS a frame of the staged replay, cut
+// "fused tail" mode applies (frame_form: rank-aware form with canonical null rows; BATCHED, NEEDNOT_REORDER) a step-wise frame now IS a frame of the staged replay, cut
 // in two at the host's association step:
 //   srukf_predict_motion       [k_set_step; unless the previous frame's tail projected this very odometry pair: k_sigr_rows + k_project_table;] k_pxy2 (motion reduction,
 //                              measurement statistics, cross covariances);  the state before the frame is kept (ckS / ckX, copied on a stream of its own).  Nothing at
@@ -35,15 +33,9 @@ void step_state_replaced(srukf_ctx* c) { step_ck_join(c); c->frame_updated = fal
 //                              that is not) is rewound and repeated on the other path, as srukf_run_frames does; what was submitted ahead is then ignored
 // Same kernels on the same values as the staged replay: bit-identical states (tests/test_gpu_parity_r5.py::test_step_api_equals_staged_replay).
 
-namespace srukf_impl {
-
 void step_invalidate(srukf_ctx* c) { step_ck_join(c); c->step_chain = false; c->proj_valid = false; c->robot_cached = false; c->view_cached = false; c->ck_valid = false; c->setstep_done = false; c->next_pose_pending = false; c->pre_issued = false; }
 
-}  // namespace srukf_impl
-
-static bool step_fast_eligible(const srukf_ctx* c) { return c->dbg.step_fast && !c->last_update_sequential && c->d.N > 0 && replay_fuse_mode(c); }
-
-namespace srukf_impl {
+static bool step_fast_eligible(const srukf_ctx* c) { return c->dbg.step_fast && !c->last_update_sequential && c->d.N > 0 && frame_form(c).fused_tail(); }
 
 // a state getter between predict and update (or a frame that ends without an update): the motion step's results go where k_gain / the state update would put them
 void step_commit_motion(srukf_ctx* c)
@@ -55,13 +47,10 @@ void step_commit_motion(srukf_ctx* c)
     c->step_uncommitted = false;
 }
 
-}  // namespace srukf_impl
-
 // Wait for an export of the fast path: spin on the pinned flag word the export kernel writes behind its data (a completion signal through hipStreamSynchronize costs
 // ~10 us more per round trip); after 2 ms on the steady clock without it — or with the switch off — the stream is synchronised the ordinary way (which also surfaces a
 // faulted launch).  A spin that succeeds never asks the runtime anything, so every 256th of them queries the stream: a launch that faulted is then reported within 256
 // frames of the one that caused it instead of at some later synchronising call.
-namespace srukf_impl {
 unsigned long long* step_flag(srukf_ctx* c) { return (unsigned long long*)((char*)c->hfs + sizeof(FrameScalars) + sizeof(double) * 32); }
 int step_wait_export(srukf_ctx* c, unsigned long long seq)
 {
@@ -125,7 +114,7 @@ static int step_predict_fast(srukf_ctx* c, const double odo_prev[3], const doubl
     if (!projected) {
         if (c->step_chain) launch_set_frame_control(c->stream, c->fs);      // (the tail prepared the control of ANOTHER pair, or none)
         srukf_launch_sigr_rows(c->stream, d, c->w, c->X, c->S, c->sigR, c->fs, c->red_iperm, c->red_r);
-        seq_predict_fused(c, 2);
+        seq_predict_fused(c, FORM_FUSED_TAIL);
     }
     c->xr1_pending = true;
     // h | Si | visible reach the host's pinned buffer from the statistics jobs of this very launch (their final passes: the first ~10 us of it), flag behind them: the host
@@ -133,7 +122,7 @@ static int step_predict_fast(srukf_ctx* c, const double odo_prev[3], const doubl
     if (!pre) {
         c->meas_seq = c->dbg.step_fuse_export ? ++c->step_seq : 0;
         c->mirror_next = c->meas_seq != 0;
-        seq_pxy(c, true, true, true, true, true);
+        seq_pxy(c, FORM_FUSED_TAIL);
         c->mirror_next = false;
     }
     c->next_pose_pending = preset && hint;                     // (k_set_step went out with two poses; the third rides on the update's k_gain launch: its successor needs it)
@@ -171,7 +160,7 @@ static int step_rewind_to_slow(srukf_ctx* c)
     step_invalidate(c);
     int rc = step_predict_slow(c, c->step_odo, c->step_odo + 3);
     if (rc) return rc;
-    seq_predict_measurement(c, false);
+    seq_predict_measurement(c, FORM_SEPARATE_STATS);
     c->phase = 2;
     return SRUKF_OK;
 }
@@ -203,7 +192,7 @@ static int step_update_fast(srukf_ctx* c, const double* z, const int* matched, i
         c->step_seqF = 2;
     }
     step_ck_join(c);
-    seq_gain_only(c, hs, (const int*)(hs + mp), true, true, true);
+    seq_gain_only(c, hs, (const int*)(hs + mp), FORM_FUSED_TAIL);
     c->step_uncommitted = false;                               // (k_gain and the state update commit the motion step)
     // The frame's status and the robot view (pose, 4 x 4 block of P: what the host records per frame, SLAM.cpp:3539-3556; srukf_get_robot then costs no round trip) reach the
     // pinned buffer from the frame's LAST launch: k_rank_expand<2>'s frame tail forms the block from the factor rows it walks anyway, the last workgroup through exports
@@ -226,7 +215,7 @@ static int step_update_fast(srukf_ctx* c, const double* z, const int* matched, i
         }
     }
     c->step_export_attached = false;
-    seq_refactor(c, 0, d.mp, false, false, false, true, true, true);
+    seq_refactor(c, refactor_frame_tail(c), FORM_FUSED_TAIL);
     early_set = c->step_export_attached && c->step_export.set;
     c->step_export = StepExport{};
     if (!c->step_export_attached) {                            // (the form with launches of their own: "step_fuse_export" 0, or a tail that is not k_rank_expand<2>)
@@ -267,7 +256,7 @@ static int step_update_fast(srukf_ctx* c, const double* z, const int* matched, i
                 // nothing of the state — so a host that then does something else (another pair, a new state, a map change) just has it ignored and repeated
                 c->meas_seq = c->dbg.step_fuse_export ? ++c->step_seq : 0;
                 c->mirror_next = c->meas_seq != 0;
-                seq_pxy(c, true, true, true, true, true);
+                seq_pxy(c, FORM_FUSED_TAIL);
                 c->mirror_next = false;
                 early_pxy = true;
             }
@@ -319,7 +308,7 @@ static int step_update_slow(srukf_ctx* c, const double* z, const int* matched, i
     HIPCHK(c, hipMemcpyAsync(c->mcur, hm, sizeof(int) * N, hipMemcpyHostToDevice, c->stream));
     launch_set_frame(c->stream, c->fs, 0, 1);
     bool exact_ran = false;
-    seq_gain(c, c->zcur, c->mcur, false);
+    seq_gain(c, c->zcur, c->mcur, FORM_SEPARATE_STATS);
     // visibility is needed on the host only to skip no-op refactors in SEQUENTIAL mode
     if (reorder == SRUKF_NEED_REORDER) {
         if (mode == SRUKF_UPDATE_BATCHED) { int rc = refactor_reorder(c, 0, d.mp); if (rc) return rc; }
@@ -330,14 +319,12 @@ static int step_update_slow(srukf_ctx* c, const double* z, const int* matched, i
             }
         }
     } else if (mode == SRUKF_UPDATE_BATCHED) {
-        seq_refactor(c, 0, d.mp, false, true, false, false);
+        seq_refactor(c, refactor_checked(c), FORM_SEPARATE_STATS);
         int rc = read_fs(c); if (rc) return rc;
         if (c->hfs->clamp_rows > 0) {
             // the reference's theta clamp would have been active: redo this refactor on the exact path
             exact_ran = true;
-            launch_set_frame(c->stream, c->fs, 0, 1);
-            launch_refactor_reset(c->stream, d.np, c->theta, c->fs, 0);
-            HIPCHK(c, hipMemcpyAsync(c->G, c->Gbak, sizeof(double) * (size_t)d.np * d.np, hipMemcpyDeviceToDevice, c->stream));
+            rc = exact_repeat_begin(c, 0, nullptr); if (rc) return rc;
             ProfScope ps(c, KC_GMW_COL, 0, 0);
             exact_path(c, c->G, c->S);
             quantize_state(c);
@@ -350,14 +337,11 @@ static int step_update_slow(srukf_ctx* c, const double* z, const int* matched, i
         for (int k = 0; k < N; k++) {
             if (!matched[k]) continue;                                   // SLAM.cpp:2068
             for (int col = 0; col < 2; col++) {                          // SLAM.cpp:2116
-                const int m = 2 * k + col;
-                seq_refactor(c, m, m + 1, false, true, true, false);
+                seq_refactor(c, refactor_column(2 * k + col), FORM_SEPARATE_STATS);
                 int rc = read_fs(c); if (rc) return rc;
                 if (c->hfs->clamp_rows > 0) {
                     exact_ran = true;
-                    launch_set_frame(c->stream, c->fs, 0, 1);
-                    launch_refactor_reset(c->stream, d.np, c->theta, c->fs, 0);
-                    HIPCHK(c, hipMemcpyAsync(c->G, c->Gbak, sizeof(double) * (size_t)d.np * d.np, hipMemcpyDeviceToDevice, c->stream));
+                    rc = exact_repeat_begin(c, 0, nullptr); if (rc) return rc;
                     exact_path(c, c->G, c->S);
                     quantize_state(c);
                     launch_set_frame(c->stream, c->fs, 0, 1);
@@ -406,7 +390,7 @@ int srukf_predict_measurement(srukf_ctx* c, double* h, double* Si, int* visible)
     HIPCHK(c, hipSetDevice(c->device));
     const int N = c->d.N;
     if (N == 0) { c->phase = 2; return SRUKF_OK; }                       // empty map: nothing to predict
-    if (!c->step_fast) seq_predict_measurement(c, false);                // (fast path: the statistics rode on srukf_predict_motion's k_pxy2 launch: this call is a copy)
+    if (!c->step_fast) seq_predict_measurement(c, FORM_SEPARATE_STATS);                // (fast path: the statistics rode on srukf_predict_motion's k_pxy2 launch: this call is a copy)
     double* hs = c->hstage;
     const size_t mp = c->d.mp;                                           // (h | Si | visible are one device allocation: one transfer)
     const size_t out_bytes = sizeof(double) * (mp + 4 * (size_t)N) + sizeof(int) * N;
