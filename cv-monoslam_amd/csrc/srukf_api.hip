@@ -75,7 +75,7 @@ void gmw_plan_destroy(GmwPlan& g, hipStream_t st)
 // list order every XCD touches every column block (8 copies of the 9.8 MB operand set through 4 MB L2s — the 17 bandwidth-bound us at the head
 // of the launch).  Here the tiles whose owners compute them are cut into 8 compact 2D regions (two bands of block rows x four ranges of block
 // columns), one per XCD; the others (head rows, pass-on row) fill the XCDs up to equal counts.  Which worker owns which tile changes nothing else.
-static void gmw_tiles_xcd_order(std::vector<short>& tk, int ntiles_all, int workers, int T, int Tp)
+static void gmw_tiles_xcd_order(std::vector<short>& tk, int ntiles_all, int workers, int T, int Tp, int npiv)
 {
     const int ntiles = ntiles_all - ((Tp > 0 && Tp < T) ? T - Tp : 0);         // the pass-on tiles stay at the end of the list (third slot of the first workers)
     if (ntiles > workers || ntiles < 16) return;
@@ -99,15 +99,15 @@ static void gmw_tiles_xcd_order(std::vector<short>& tk, int ntiles_all, int work
         std::sort(b.begin(), b.end(), [](const Tl& x, const Tl& y) { return x.v[1] != y.v[1] ? x.v[1] < y.v[1] : x.v[0] < y.v[0]; });
         for (size_t q = 0; q < b.size(); q++) grp[4 * band + std::min<size_t>(3, q * 4 / b.size())].push_back(b[q]);
     }
-    // positions of XCD x: list index w with (w + 1) % 8 == x (blockIdx = w + 1: the pivot is workgroup 0)
+    // positions of XCD x: list index w with (w + npiv) % 8 == x (blockIdx = w + npiv: the pivots are the first workgroups)
     int cap[8] = { 0 };
-    for (int w = 0; w < ntiles; w++) cap[(w + 1) % 8]++;
+    for (int w = 0; w < ntiles; w++) cap[(w + npiv) % 8]++;
     std::vector<Tl> spill(rest);
     for (int x = 0; x < 8; x++) while ((int)grp[x].size() > cap[x]) { spill.push_back(grp[x].back()); grp[x].pop_back(); }
     for (int x = 0; x < 8; x++) while ((int)grp[x].size() < cap[x] && !spill.empty()) { grp[x].push_back(spill.back()); spill.pop_back(); }
     size_t pos[8] = { 0 };
     for (int w = 0; w < ntiles; w++) {
-        const int x = (w + 1) % 8;
+        const int x = (w + npiv) % 8;
         const Tl t = grp[x][pos[x]++];
         for (int e = 0; e < 4; e++) tk[4 * w + e] = t.v[e];
     }
@@ -123,13 +123,23 @@ int gmw_plan_create(GmwPlan& g, int np, hipStream_t st, int Tp, int tenants)
     int cus = 0, dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 2) cus = 2;
     g.cus = cus;
-    const int cap = cus / (tenants > 1 ? tenants : 1) - 1;    // one workgroup per CU (registers), all of them resident
-    g.workers = cap >= 1 ? srukf_gmw_persist_workers(g.T, g.Tp, cap) : -1;
     g.ntiles = srukf_gmw_build_tiles(g.T, g.Tp, nullptr);
+    // one workgroup per CU (registers), all of them resident: pivot(s) + workers <= the CUs of this tenant.  Pivot relay (two pivot workgroups): where the switch is on
+    // and the plan is still the register-tile form with one CU less for the workers; every other plan keeps one pivot.
+    g.relay = 0;
+    if (srukf_gmw_get_pivot_relay() && g.Tp >= 2) {
+        const int cap2 = cus / (tenants > 1 ? tenants : 1) - 2;
+        const int w2 = cap2 >= 1 ? srukf_gmw_persist_workers(g.T, g.Tp, cap2) : -1;
+        const int w1 = srukf_gmw_persist_workers(g.T, g.Tp, cap2 + 1), nreal = g.ntiles - (g.Tp < g.T ? g.T - g.Tp : 0);
+        // (not where the CU given to the second pivot would change how many tiles a worker owns: the plan thresholds stay where they were measured)
+        if (w2 > 0 && w1 > 0 && srukf_gmw_register_form(g.T, g.Tp, g.ntiles, w2) && (nreal + w2 - 1) / w2 == (nreal + w1 - 1) / w1) g.relay = 1;
+    }
+    const int cap = cus / (tenants > 1 ? tenants : 1) - (g.relay ? 2 : 1);
+    g.workers = cap >= 1 ? srukf_gmw_persist_workers(g.T, g.Tp, cap) : -1;
     g.nreal = g.ntiles - (g.Tp < g.T ? g.T - g.Tp : 0);
     std::vector<short> tk((size_t)4 * (g.ntiles > 0 ? g.ntiles : 1), 0);
     srukf_gmw_build_tiles(g.T, g.Tp, tk.data());
-    gmw_tiles_xcd_order(tk, g.ntiles, g.workers, g.T, g.Tp);
+    gmw_tiles_xcd_order(tk, g.ntiles, g.workers, g.T, g.Tp, g.relay ? 2 : 1);
     const size_t sync_bytes = (size_t)srukf_gmw_sync_bytes(g.T);
     if (srukf_dmalloc_on(&g.pans, (size_t)srukf_gmw_panel_bytes() * g.T, st) != hipSuccess ||
         srukf_dmalloc_on(&g.sync, sync_bytes, st) != hipSuccess ||

@@ -94,6 +94,7 @@ int srukf_debug_set(srukf_ctx* c, const char* key, int value)
                                                   };
     if (!strcmp(key, "batch_split")) { g_dbg_batch_split = value ? 1 : 0; batch_drop_all_graphs(); return SRUKF_OK; }
     if (!strcmp(key, "head_fold_free")) { if (value < 1) return SRUKF_ERR_BAD_ARG; g_dbg_head_fold_free = value; if (c) { hipSetDevice(c->device); step_commit_motion(c); step_invalidate(c); hipStreamSynchronize(c->stream); drop_graphs(c); } return SRUKF_OK; }
+    if (!strcmp(key, "pivot_relay")) { srukf_gmw_set_pivot_relay(value); return SRUKF_OK; }       // two pivot workgroups in the register-tile persistent launch; read when a plan is built
     if (!strcmp(key, "batch_groups")) { if (value < 0 || value > SRUKF_BATCH_GROUPS_MAX) return SRUKF_ERR_BAD_ARG; g_dbg_batch_groups = value; return SRUKF_OK; }
     if (!strcmp(key, "batch_wide")) { g_dbg_batch_wide = value ? 1 : 0; return SRUKF_OK; }
     if (!strcmp(key, "timing")) { g_dbg_timing = value ? 1 : 0; return SRUKF_OK; }              // phases of map changes and of flagged frames on stderr
@@ -218,6 +219,7 @@ int srukf_debug_get(srukf_ctx* c, const char* key, long long* value)
         else if (!strcmp(k, "workers")) *value = gp.workers;
         else if (!strcmp(k, "persist")) *value = persist ? 1 : 0;                                        // 0: one launch per 64-row panel
         else if (!strcmp(k, "register_form")) *value = (persist && !split_form(c, gp) && srukf_gmw_register_form(gp.T, gp.Tp, gp.ntiles, gp.workers)) ? 1 : 0;
+        else if (!strcmp(k, "relay")) *value = (persist && !split_form(c, gp) && gp.relay && srukf_gmw_register_form(gp.T, gp.Tp, gp.ntiles, gp.workers)) ? 1 : 0;      // two pivot workgroups
         else if (!strcmp(k, "tiles_per_worker")) *value = gp.workers > 0 ? (gp.nreal + gp.workers - 1) / gp.workers : -1;
         else if (!strcmp(k, "fold")) *value = rp.form == RF_OWNERS_FOLD ? 1 : 0;                         // the owners form their tiles of S^T S - U U^T themselves
         else if (!strcmp(k, "head_fold")) *value = rp.head_fold ? 1 : 0;                                 // ... and the head tiles ride on the persistent launch
@@ -297,7 +299,7 @@ int srukf_gmw_host(int device, int n, const double* G, double* S_out, double* D_
         // the plan knows how many workgroups THIS device can keep resident (CU count); workers < 0: per-panel launches
         if (gmw_persist_mode()) { const int rc = gmw_plan_create(r.gp, np, st); if (rc) return rc; }
         if (gmw_persist_mode() && r.gp.workers >= 0) {
-            srukf_launch_gmw_persist(st, n, np, epsilon, r.dG, r.gp.pans, r.dD, r.dS, r.gp.sync, r.gp.tiles, r.gp.ntiles, r.gp.workers, r.dFs, nullptr, nullptr, 0, 0, 0, 0, 0);
+            srukf_launch_gmw_persist(st, n, np, epsilon, r.dG, r.gp.pans, r.dD, r.dS, r.gp.sync, r.gp.tiles, r.gp.ntiles, r.gp.workers, r.dFs, nullptr, nullptr, 0, 0, 0, 0, 0, r.gp.relay);
         } else {
             GH(srukf_dmalloc(&r.pan[0], srukf_gmw_panel_bytes())); GH(srukf_dmalloc(&r.pan[1], srukf_gmw_panel_bytes()));
             GH(hipMemset(r.pan[0], 0, srukf_gmw_panel_bytes())); GH(hipMemset(r.pan[1], 0, srukf_gmw_panel_bytes()));

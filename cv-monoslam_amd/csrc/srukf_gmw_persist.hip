@@ -59,7 +59,7 @@ __device__ __forceinline__ bool gmw_wait_ge(const unsigned long long* f, unsigne
 }
 // Abandon the launch (a bounded wait expired): everybody leaves, the frame is flagged.  The FIRST to give up also leaves who and where (site << 32 | blockIdx + 1) in the
 // sync block's pad word 0 (srukf_debug_get "abort_code"): cold path, diagnostic only.
-// sites: 1 pivot (operands of the next panel), 2 pivot (critical head tiles), 3 worker (head tiles), 4 worker (a tile step), 5 slab workgroup, 6 tile workgroup, 7 residency gate
+// sites: 1 pivot (operands of the next panel), 2 pivot (critical head tiles), 3 worker (head tiles), 4 worker (a tile step), 5 slab workgroup, 6 tile workgroup, 7 residency gate, 8 second pivot of the relay (any of its waits)
 __device__ __forceinline__ void gmw_abandon(GmwSync* sy, unsigned int site)
 {
     __hip_atomic_store(&sy->abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -365,6 +365,317 @@ __device__ __forceinline__ void gmw_pivot_persist(int n, int ld, int T, int Tp, 
     // the last panel buffers are never read by a worker (steps T-2 and T-1 have no trailing tiles)
 }
 
+// ------------------------------------------------------------------------------------------------
+// Pivot relay (register-tile instance only; srukf_debug_set(0, "pivot_relay", 1)): TWO pivot workgroups, blockIdx 0 and 1, take the
+// panels alternately (workgroup q factors the panels p = q, q + 2, ...).  What gmw_pivot_persist does between the last pivot of panel
+// p - 1 and the first pivot of panel p — wait for the T wave's stores, stage two tiles, slab stages 1 - 3, K = 64 of the region
+// update — is cut by what it depends on, and the workgroup that is NOT factoring does everything that does not need the other's
+// second 32-pivot factor while that factor runs, on a CU whose waves have nothing else to do:
+//   1. stage  tiles (p-1, p) -> Lr and (p, p) -> Wc behind their version flags, then LDS -> registers               (off the chain)
+//   2. half   behind half_ready = p: Tt1, E, 1/D[0..31] of pans[p-1] -> W1 = T1' G1, G2' = G2 - E'^T W1, rows 0..31 of the
+//             slab, K = 0..31 of the region update                                                                    (off the chain)
+//   3. full   behind panel_ready = p: Tt2, 1/D[32..63], sqrt(D)/D -> W2 = T2' G2', rows 32..63, K = 32..63, Xm      (on the chain)
+//   then factor 1, C1, C2, factor 2 and the outputs as in gmw_pivot_persist; panel_ready = p + 1 as soon as the output waves have drained.
+// The panel matrices come from the panel buffer (agent-scope loads straight into MFMA fragments) instead of the LDS copies a lone
+// pivot keeps: the same bits (nxt->E is stored from the Lr values kp.Ep holds, Tt1 / Tt2 through gmw_copy_t / the T wave from the LDS
+// T', rD / sq by the same expressions from the same D), applied as the same products in the same order — K ascending on every
+// accumulator, the K loops merely cut at 32: bit-identical to gmw_pivot_persist and to the per-panel path.
+// Each pivot polls copies of the two panel flags in lines of its own (GMW_PIVOT_COPY).
+// GMW_RELAY_ACC_EARLY: waves 1 / 3 apply K = 0..31 to the (0,1) / (1,1) quarters in step 2 (1) or, with K = 32..63, under factor 1 (0).
+#ifndef GMW_RELAY_ACC_EARLY
+#define GMW_RELAY_ACC_EARLY 1
+#endif
+#define GMW_PIVOT_COPY(q) ((q) * GMW_FLAG_STRIDE + 128)
+__device__ __forceinline__ void gmw_set_panel_flag_relay(unsigned long long* f, unsigned long long v, int lane)
+{
+    const int idx = lane < GMW_FLAG_COPIES ? lane * GMW_FLAG_STRIDE : GMW_PIVOT_COPY((lane - GMW_FLAG_COPIES) & 1);
+    if (lane < GMW_FLAG_COPIES + 2) __hip_atomic_store(&f[idx], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// abandon sites: 1 the first pivot workgroup, 8 the second
+__device__ __forceinline__ void gmw_pivot_relay(int n, int ld, int T, int Tp, double eps, double* __restrict__ G, GmwPanel64* __restrict__ pans,
+                                                double* __restrict__ Dall, double* __restrict__ Sout, GmwSync* sy, unsigned long long ebase,
+                                                double (*Lr)[G64_LS], double (*Wc)[G64_LS], double* facreg, double* xreg,
+                                                int* okp, int* halfcnt, int tid, int klim, const int q)
+{
+    const int lane = tid & 63, wv = tid >> 6, lr = lane & 15, lk = lane >> 4;
+    const int qa = wv >> 1, qb = wv & 1;
+    const GmwColsLds ws = gmw_cols_carve(facreg), ws2 = gmw_cols_carve(facreg + GMW_FAC_DOUBLES);
+    double (*X01)[32] = (double (*)[32])xreg;
+    double (*X11)[32] = (double (*)[32])(xreg + 1024);
+    double* const T1l = xreg + 2048;                           // T1' of the panel being factored (T wave of factor 1 -> C1, first half of the panel buffer)
+    double* const T2l = xreg;                                  // transposition buffer of the T wave of factor 2
+    unsigned long long* ver = gmw_sync_ver(sy);
+    const unsigned long long* my_half = &sy->half_ready[GMW_PIVOT_COPY(q)];
+    const unsigned long long* my_full = &sy->panel_ready[GMW_PIVOT_COPY(q)];
+    const int ro = (wv == 1) ? 0 : 32;
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    const bool wv0 = wvu == 0, wv1 = wvu == 1, wv3 = wvu == 3;
+    const unsigned int site = q ? 8u : 1u;
+    // (diagnostic builds: the stamps are indexed by the panel, so each pivot has the slots of its own panels.  [p]: 5 iteration start, 6 tiles staged, 7 half flag seen,
+    //  0 first half applied, 1 panel flag seen, 2 Xm complete, 3 factor 1 done, 4 C2 done;  [p + 64]: 4 / 0 pivot wave after factor 1 / 2, 5 / 3 T wave, 6 / 7 and 1 / 2 waves 1 / 3)
+    if (wv0) *okp = 1;
+    if (q == 0 && wv3) gmw_stage_tile(Wc, G, ld, 0, 0, lane);  // region R_0 as k_syrk / the head helpers left it
+    __syncthreads();
+    for (int p = q; p < Tp; p += 2) {
+        const int j0 = 64 * (p - 1), base = 64 * p;
+        const bool first = (p == 0);
+        const bool half_only = (p == Tp - 1) && (Tp < T) && (klim <= base + 32);
+        GmwPanel64* nxt = pans + p;
+        const GmwPanel64* prv = pans + (first ? 0 : p - 1);
+        if (wv0) GMW_TS(sy, p, 5);
+        // ---- 1. stage: every wave fetches 32 rows of one of the two tiles (tile (p-1, p) -> Lr by waves 1 / 0, tile (p, p) -> Wc by waves 3 / 2) ----
+        if (!first) {
+            const bool tileA = wvu < 2;
+            const int tr = tileA ? p - 1 : p, r0 = (wvu & 1) ? 0 : 32;
+            // (panel 1: tiles (0,1) and (1,1) carry no update and no version; they exist before the launch or behind the critical head tiles)
+            const bool ready = p == 1 || gmw_wait_ge(&ver[GMW_VIDX(tr, p, T)], ebase + p - 1, &sy->abort);
+            if (!ready) *okp = 0;
+            else {
+                double (*dst)[G64_LS] = tileA ? Lr : Wc;
+                const double* src = G + (size_t)(64 * tr + r0) * ld + base + lane;
+                double v[32];
+#pragma unroll
+                for (int r = 0; r < 32; r++) v[r] = ld_dev(src + (size_t)r * ld);
+#pragma unroll
+                for (int r = 0; r < 32; r++) dst[r0 + r][lane] = v[r];
+            }
+            __syncthreads();
+            if (!*okp) { if (wv0) gmw_abandon(sy, site); return; }
+        }
+        if (wv0) GMW_TS(sy, p, 6);
+        if (wv0) { ws.Dv[lane & 31] = 0.0; ws2.Dv[lane & 31] = 0.0; *halfcnt = 0; }
+        d4 g;
+#pragma unroll
+        for (int t = 0; t < 4; t++) g[t] = Wc[16 * qa + lk + 4 * t][16 * qb + lr];
+        d4 acc[2][2];
+        zero_acc(acc);
+        if (wv & 1) {
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int t = 0; t < 4; t++) acc[a][b][t] = Wc[ro + 16 * a + lk + 4 * t][32 + 16 * b + lr];
+        }
+        d4 X2[2];
+        double fb[8], sqv[8];
+        if (!first) {
+#pragma unroll
+            for (int u = 0; u < 8; u++) fb[u] = Lr[4 * u + lk][16 * wv + lr];
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+                for (int t = 0; t < 4; t++) X2[a][t] = Lr[32 + 16 * a + lk + 4 * t][16 * wv + lr];
+        }
+        __syncthreads();                                       // staged tiles are in registers: Lr / Wc may be rewritten
+        if (!first) {
+            const int cc = 16 * wv + lr;
+            // ---- 2. first half of panel p - 1 (the other pivot is in its second factor) ----
+            if (!gmw_wait_ge(my_half, ebase + p, &sy->abort)) *okp = 0;
+            if (wv0) GMW_TS(sy, p, 7);
+            {
+                double ta0[4], ta1[8], ea0[8], ea1[8], dr[2][4];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {                  // every fragment is requested before the first MFMA
+                    const int o = (4 * u + lk) * 32 + lr;
+                    if (u < 4) ta0[u] = ld_dev(&prv->Tt1[o]);
+                    ta1[u] = ld_dev(&prv->Tt1[o + 16]);
+                    ea0[u] = ld_dev(&prv->E[o]); ea1[u] = ld_dev(&prv->E[o + 16]);
+                }
+#pragma unroll
+                for (int a = 0; a < 2; a++)
+#pragma unroll
+                    for (int t = 0; t < 4; t++) dr[a][t] = ld_dev(&prv->rD[16 * a + lk + 4 * t]);
+                d4 W1[2] = { (d4){0, 0, 0, 0}, (d4){0, 0, 0, 0} };
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    if (u < 4) W1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta0[u], fb[u], W1[0], 0, 0, 0);
+                    W1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta1[u], fb[u], W1[1], 0, 0, 0);
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    X2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ea0[u], W1[u >> 2][u & 3], X2[0], 0, 0, 0);
+                    X2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ea1[u], W1[u >> 2][u & 3], X2[1], 0, 0, 0);
+                }
+#pragma unroll
+                for (int a = 0; a < 2; a++)
+#pragma unroll
+                    for (int t = 0; t < 4; t++) {
+                        const int jj = 16 * a + lk + 4 * t;
+                        Wc[jj][cc] = W1[a][t];       Lr[jj][cc] = W1[a][t] * dr[a][t];
+                    }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 32; k += 4)
+                g = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], g, 0, 0, 0);
+#if GMW_RELAY_ACC_EARLY
+            if (wv & 1) {
+#pragma unroll
+                for (int k = 0; k < 32; k += 4) {
+                    const double a0 = -Lr[k + lk][ro + lr], a1 = -Lr[k + lk][ro + 16 + lr];
+                    const double b0 = Wc[k + lk][32 + lr], b1 = Wc[k + lk][48 + lr];
+                    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+                    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+                    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+                    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+                }
+            }
+#endif
+            if (wv0) GMW_TS(sy, p, 0);
+            // ---- 3. second half: the only part between the other pivot's last pivot and this one's first ----
+            if (!gmw_wait_ge(my_full, ebase + p, &sy->abort)) *okp = 0;
+            if (wv0) GMW_TS(sy, p, 1);
+            {
+                double tb0[4], tb1[8], dr2[2][4];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int o = (4 * u + lk) * 32 + lr;
+                    if (u < 4) tb0[u] = ld_dev(&prv->Tt2[o]);
+                    tb1[u] = ld_dev(&prv->Tt2[o + 16]);
+                }
+#pragma unroll
+                for (int a = 0; a < 2; a++)
+#pragma unroll
+                    for (int t = 0; t < 4; t++) dr2[a][t] = ld_dev(&prv->rD[32 + 16 * a + lk + 4 * t]);
+                if (wv & 1) {
+#pragma unroll
+                    for (int i = 0; i < 8; i++) sqv[i] = ld_dev(&prv->sq[ro + 4 * i + lk]);
+                }
+                d4 W2[2] = { (d4){0, 0, 0, 0}, (d4){0, 0, 0, 0} };
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    if (u < 4) W2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(tb0[u], X2[u >> 2][u & 3], W2[0], 0, 0, 0);
+                    W2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(tb1[u], X2[u >> 2][u & 3], W2[1], 0, 0, 0);
+                }
+#pragma unroll
+                for (int a = 0; a < 2; a++)
+#pragma unroll
+                    for (int t = 0; t < 4; t++) {
+                        const int jj = 32 + 16 * a + lk + 4 * t;
+                        Wc[jj][cc] = W2[a][t];       Lr[jj][cc] = W2[a][t] * dr2[a][t];
+                    }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 32; k < 64; k += 4)
+                g = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], g, 0, 0, 0);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; t++) ws.Xm[16 * qa + lk + 4 * t][16 * qb + lr] = g[t];
+        __syncthreads();
+        if (wv0) GMW_TS(sy, p, 2);
+        if (!*okp) { if (wv0) gmw_abandon(sy, site); return; }  // a wait of step 2 / 3 expired: nothing of this panel has been published
+        // ---- factor 1 (+ panel S rows, tiles (0,1), (1,1)) ----
+        if (wv0) { gmw_cols_pivot_wave(ws, eps, lane); GMW_TS(sy, p + 64, 4); }
+        else if (wvu == 2) { gmw_cols_t_wave<0>(ws, lane, nullptr, T1l); GMW_TS(sy, p + 64, 5); }
+        else {
+            if (!first) {
+#pragma unroll
+                for (int k = GMW_RELAY_ACC_EARLY ? 32 : 0; k < 64; k += 4) {
+                    const double a0 = -Lr[k + lk][ro + lr], a1 = -Lr[k + lk][ro + 16 + lr];
+                    const double b0 = Wc[k + lk][32 + lr], b1 = Wc[k + lk][48 + lr];
+                    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+                    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+                    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+                    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+                }
+            }
+            double (*X)[32] = (wv == 1) ? X01 : X11;
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int t = 0; t < 4; t++) X[16 * a + lk + 4 * t][16 * b + lr] = acc[a][b][t];
+            if (!first) {
+                const int c4 = lr * 4;
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const int row = ro + 4 * i + lk;
+                    const double sq = sqv[i];
+                    d4 w = *(const d4*)&Wc[row][c4];
+                    w[0] *= sq; w[1] *= sq; w[2] *= sq; w[3] *= sq;
+                    *(d4*)&Sout[(size_t)(j0 + row) * ld + base + c4] = w;
+                }
+            }
+            if (wv1) GMW_TS(sy, p + 64, 6); else GMW_TS(sy, p + 64, 7);
+        }
+        __syncthreads();
+        if (wv0) GMW_TS(sy, p, 3);
+        // ---- C1: quarter (qa, qb) of W1d = T1' X01 and of E' = W1d / D' ----
+        {
+            d4 wq = (d4){0, 0, 0, 0};
+#pragma unroll
+            for (int u = 0; u < 8; u++)
+                wq = __builtin_amdgcn_mfma_f64_16x16x4f64(T1l[(4 * u + lk) * 33 + 16 * qa + lr], X01[4 * u + lk][16 * qb + lr], wq, 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int k = 16 * qa + lk + 4 * t, cc = 16 * qb + lr;
+                const double e = wq[t] * gmw_pivot_rcp(ws.Dv[k]);
+                Wc[k][cc] = wq[t];
+                Lr[k][cc] = e;
+            }
+        }
+        __syncthreads();
+        // ---- C2: quarter of X11 -= E'^T W1d -> Xm of factor 2 ----
+        if (!half_only) {
+            d4 x;
+#pragma unroll
+            for (int t = 0; t < 4; t++) x[t] = X11[16 * qa + lk + 4 * t][16 * qb + lr];
+#pragma unroll
+            for (int k = 0; k < 32; k += 4)
+                x = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], x, 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < 4; t++) ws2.Xm[16 * qa + lk + 4 * t][16 * qb + lr] = x[t];
+        }
+        __syncthreads();
+        if (wv0) GMW_TS(sy, p, 4);
+        // ---- factor 2: wave 0 pivots, wave 2 follows with T2', waves 1 / 3 publish the first half of the panel buffer and write the outputs ----
+        if (wv0) { if (!half_only) gmw_cols_pivot_wave(ws2, eps, lane); GMW_TS(sy, p + 64, 0); }
+        else if (wvu == 2) {
+            if (!half_only) { gmw_cols_t_wave<2>(ws2, lane, nxt->Tt2, T2l); GMW_TS(sy, p + 64, 3); }
+        } else {
+            const int c4 = (lane & 7) * 4;
+            if (wv1) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int row = 8 * i + (lane >> 3);
+                    st_d4<true>(&nxt->E[row * 32 + c4], *(const d4*)&Lr[row][c4]);
+                }
+                if (lane < 32) {
+                    const double D = ws.Dv[lane], rc = gmw_pivot_rcp(D), sq = sqrt(D) * rc;
+                    st_dev(&nxt->D[lane], D); st_dev(&nxt->sq[lane], sq); st_dev(&nxt->rD[lane], rc);
+                }
+            } else gmw_copy_t<true>(T1l, nxt->Tt1, lane);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            {
+                int prev = 0;
+                if (lane == 0) prev = __hip_atomic_fetch_add(halfcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (__builtin_amdgcn_readfirstlane(prev) == 1) gmw_set_panel_flag_relay(sy->half_ready, ebase + p + 1, lane);
+            }
+            if (!wv1) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int row = 8 * i + (lane >> 3);
+                    const double Dr = ws.Dv[row];
+                    const double sq = (base + row < n) ? sqrt(Dr) * gmw_pivot_rcp(Dr) : 0.0;
+                    d4 w = *(const d4*)&Wc[row][c4];
+                    w[0] *= sq; w[1] *= sq; w[2] *= sq; w[3] *= sq;
+                    *(d4*)&Sout[(size_t)(base + row) * ld + base + 32 + c4] = w;
+                }
+            }
+            gmw_cols_out_wave<true>(ws, wv1 ? 0 : 1, lane, n, ld, base, nxt->D, nxt->sq, nxt->rD, Dall, Sout);
+            if (!half_only) gmw_cols_out_wave<true>(ws2, wv1 ? 0 : 1, lane, n, ld, base + 32, nxt->D + 32, nxt->sq + 32, nxt->rD + 32, Dall, Sout);
+            if (wv1) GMW_TS(sy, p + 64, 1); else GMW_TS(sy, p + 64, 2);
+        }
+        // ---- 4. publish: every storing wave drains, then the barrier, then one wave raises the flag.  Nothing is staged in front of it. ----
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (wv3 && p + 1 < T) gmw_set_panel_flag_relay(sy->panel_ready, ebase + p + 1, lane);
+    }
+}
+
 // A memory-tile worker that is behind the pivot: 2 = it requests ALL operands of a step at once (one memory round trip per step, as the register form does;
 // with the accumulator set, the three-stage slab and both halves' operands live the instance needs ~40 VGPR spills, 164 B of scratch), 1 = only the second
 // half's T fragments early (27 spills), 0 = the second half requested after the first: no spills, no scratch (256 VGPRs + 236 AGPRs), one more round trip per step.
@@ -426,7 +737,7 @@ __device__ __forceinline__ bool gmw_owner_step(int n, int ld, int T, int k, cons
         behind && (!memtile || GMW_MEM_EARLY2 > 0), rows32 && tl.passon, memtile && GMW_MEM_EARLY2 == 1);
 }
 
-// k_gmw_persist: grid = 1 + workers; worker w owns tiles[w - 1] and tiles[w - 1 + workers] (if any), both kept in accumulator
+// k_gmw_persist: grid = 1 + workers (pivot relay: 2 + workers, gmw_pivot_relay); worker w owns tiles[w - 1] and tiles[w - 1 + workers] (if any), both kept in accumulator
 // registers from their first update to their last.
 // k_gmw_persist<MEM = true>: matrices with more tiles than 2 x workers (N >= 340: 1 081 tiles at N = 500).  Worker w owns
 // tiles[w - 1 + m workers], m = 0 .. GMW_OWNED_MEM - 1; every tile lives in G and passes through one accumulator set per step
@@ -601,7 +912,7 @@ __global__ __launch_bounds__(256) void k_gmw_persist(int n, int ld, int T, int T
                                                      GmwSync* __restrict__ sy, const GmwTile* __restrict__ tiles, int ntiles,
                                                      FrameScalars* __restrict__ fs,
                                                      const double* __restrict__ S0, const double* __restrict__ Ut0, int u0, int u1, int krows, int gated,
-                                                     const HeadArgs ha)
+                                                     const HeadArgs ha, const int relay)
 {
     __shared__ double Lr[64][G64_LS];
     __shared__ double Wc[64][G64_LS];
@@ -611,8 +922,9 @@ __global__ __launch_bounds__(256) void k_gmw_persist(int n, int ld, int T, int T
     __shared__ int ok, halfcnt, stageok[2];
     const int tid = threadIdx.x;
     const int nhelp = ha.nhelp;                                // head fold: helper workgroups BEHIND the pivot and the workers (0 without it)
-    const int nmain = (int)gridDim.x - nhelp;                  // 1 + workers: dispatched first, so that the owners start forming their tiles at once
-    const int role = (int)blockIdx.x < nmain ? (int)blockIdx.x : -1;      // -1: helper, 0: pivot, > 0: worker role - 1
+    const int nmain = (int)gridDim.x - nhelp;                  // pivots + workers: dispatched first, so that the owners start forming their tiles at once
+    const int npiv = (!MEM && relay) ? 2 : 1;                  // pivot relay (gmw_pivot_relay): workgroups 0 and 1 take the panels alternately
+    const int role = (int)blockIdx.x < nmain ? (int)blockIdx.x : -1;      // -1: helper, < npiv: pivot, otherwise: worker role - npiv
     // What a role needs first — its entry of the tile list — is requested TOGETHER with the frozen flag and the epoch: a round trip in a freshly
     // launched grid is ~2 us (cold TLB and L2, 256 workgroups asking at once), and flag -> list entry -> operands was a chain of three of them in front
     // of the critical head tiles (time stamps: 7.5 us before the first MFMA).  The asm pins all four loads in front of the first use.
@@ -624,11 +936,11 @@ __global__ __launch_bounds__(256) void k_gmw_persist(int n, int ld, int T, int T
     const int npass = (!MEM && Tp < T) ? T - Tp : 0, nreal = ntiles - npass;
     if (!MEM) {
         if (role < 0) { const int hb = (int)blockIdx.x - nmain; if (hb < ha.ntiles) mytile = ha.tiles[hb]; }
-        else if (role > 0) {
+        else if (role >= npiv) {
             const unsigned long long* tq = (const unsigned long long*)tiles;
-            if (role - 1 < nreal) t01 = tq[role - 1];
-            if (role - 1 + nmain - 1 < nreal) t23 = tq[role - 1 + nmain - 1];
-            if (role - 1 < npass) t45 = tq[nreal + role - 1];
+            if (role - npiv < nreal) t01 = tq[role - npiv];
+            if (role - npiv + nmain - npiv < nreal) t23 = tq[role - npiv + nmain - npiv];
+            if (role - npiv < npass) t45 = tq[nreal + role - npiv];
         }
     }
     int frozen_now = fs->frozen;
@@ -676,7 +988,7 @@ __global__ __launch_bounds__(256) void k_gmw_persist(int n, int ld, int T, int T
         if (tid == 0) atomicAdd(&sy->pad[2], 1ull);
 #endif
         }
-    } else if (role == 0) {
+    } else if (role < npiv) {
         bool head_ok = true;
         GMW_TS(sy, 128, 0);
         if (ha.ntiles > 0) {                                   // region R_0 and the two tiles behind it come from the helpers of this launch
@@ -686,12 +998,13 @@ __global__ __launch_bounds__(256) void k_gmw_persist(int n, int ld, int T, int T
             __syncthreads();
         }
         GMW_TS(sy, 128, 1);
-        if (head_ok) gmw_pivot_persist(n, ld, T, Tp, eps, G, pans, Dall, Sout, sy, ebase, Lr, Wc, facreg, xreg, keepreg, &ok, &halfcnt, stageok, tid, krows);
-        else if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) gmw_abandon(sy, 2);
+        if (!head_ok) { if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) gmw_abandon(sy, 2); }
+        else if (npiv == 2) { if constexpr (!MEM) gmw_pivot_relay(n, ld, T, Tp, eps, G, pans, Dall, Sout, sy, ebase, Lr, Wc, facreg, xreg, &ok, &halfcnt, tid, krows, role); }
+        else gmw_pivot_persist(n, ld, T, Tp, eps, G, pans, Dall, Sout, sy, ebase, Lr, Wc, facreg, xreg, keepreg, &ok, &halfcnt, stageok, tid, krows);
         GMW_TS(sy, 128, 2);
     } else {
         const bool wv0 = __builtin_amdgcn_readfirstlane(tid >> 6) == 0;
-        const int workers = nmain - 1, w = role - 1;
+        const int workers = nmain - npiv, w = role - npiv;
         bool good = true;
         const bool half_last = (Tp < T) && (krows <= 64 * (Tp - 1) + 32);     // the pivot stops after the first half of the last pivoted panel (gmw_pivot_persist)
         if constexpr (MEM) {
@@ -717,7 +1030,7 @@ __global__ __launch_bounds__(256) void k_gmw_persist(int n, int ld, int T, int T
         if (w < npass) { const GmwTile t = entry(t45); tc.I = t.I; tc.J = t.J; tc.nsteps = t.nsteps; tc.kfirst = t.pad; tc.passon = true; tc.computed = true; }
         d4 acca[2][2], accb[2][2];
         zero_acc(acca); zero_acc(accb);
-        if (role == 1) GMW_TS(sy, 129, 0);
+        if (role == npiv) GMW_TS(sy, 129, 0);
         if (role == nmain - 1) GMW_TS(sy, 130, 0);
         if (S0) {
             const KDimsLite dl = { n, ld };
@@ -725,7 +1038,7 @@ __global__ __launch_bounds__(256) void k_gmw_persist(int n, int ld, int T, int T
             if (ta.nsteps > 0 && gmw_owner_computes(ta.I, ta.J)) { if (!ta.passon) gmw_owner_syrk(dl, S0, Ut0, u0, u1, ta.I, ta.J, acca, fs, tid, krows); ta.computed = true; }
             if (tb.nsteps > 0 && gmw_owner_computes(tb.I, tb.J)) { if (!tb.passon) gmw_owner_syrk(dl, S0, Ut0, u0, u1, tb.I, tb.J, accb, fs, tid, krows); tb.computed = true; }
         }
-        if (role == 1) GMW_TS(sy, 129, 1);
+        if (role == npiv) GMW_TS(sy, 129, 1);
         if (role == nmain - 1) GMW_TS(sy, 130, 1);
         if (ha.ntiles > 0) {                                   // step 0 reads the head rows of G (and a row-1 / 2 x 2-block tile is loaded from there)
             if (wv0) ok = (gmw_wait_head(gmw_head_crit(sy), (unsigned)ha.ncrit, &sy->abort) && gmw_wait_head(gmw_head_done(sy), (unsigned)(ha.ntiles - ha.ncrit), &sy->abort)) ? 1 : 0;
@@ -734,7 +1047,7 @@ __global__ __launch_bounds__(256) void k_gmw_persist(int n, int ld, int T, int T
             if (!good && wv0) gmw_abandon(sy, 3);
             __syncthreads();
         }
-        if (role == 1) GMW_TS(sy, 129, 2);
+        if (role == npiv) GMW_TS(sy, 129, 2);
         if (role == nmain - 1) GMW_TS(sy, 130, 2);
         const int kmax = max(ta.nsteps, tb.nsteps);
         for (int k = 0; k < kmax && good; k++) {
@@ -745,7 +1058,7 @@ __global__ __launch_bounds__(256) void k_gmw_persist(int n, int ld, int T, int T
         if (good && tc.nsteps > 0) good = gmw_owner_step(n, ld, T, tc.kfirst, tc, acca, G, pans, Sout, sy, ebase, Lr, Wc, &ok, wv0, tid, false, half_last);
         }
         if (!good && wv0) gmw_abandon(sy, 4);
-        if (role == 1) GMW_TS(sy, 129, 3);
+        if (role == npiv) GMW_TS(sy, 129, 3);
         if (role == nmain - 1) GMW_TS(sy, 130, 3);
     }
     // the last workgroup out re-arms the block for the next launch and reports an abandoned run
@@ -1130,6 +1443,9 @@ __global__ void k_gmw_split_gate(GmwSync* __restrict__ sy, const FrameScalars* _
 }
 
 extern "C" {
+#ifndef SRUKF_PIVOT_RELAY_DEFAULT
+#define SRUKF_PIVOT_RELAY_DEFAULT 1      // measured (docs/LAB_NOTEBOOK.md, pivot relay): N = 100 +5 %, N = 200 +1.2 %, N = 300 +4.8 % frames/s
+#endif
 int srukf_gmw_sync_bytes(int T) { return (int)(sizeof(GmwSync) + 3 * sizeof(unsigned long long) * (size_t)T * T * GMW_VER_STRIDE); }
 // host-side tile list of the persistent launch: every tile (I, J), 1 <= I <= J < T, with the number of panel updates
 // its owner applies (I off the diagonal; I - 1 on it: the pivot applies the last one itself), ordered by the step at
@@ -1150,6 +1466,10 @@ int srukf_gmw_build_tiles(int T, int Tp, short* out)
     return cnt;
 }
 // workers the persistent launch needs for T block rows (each owns at most GMW_OWNED_MAX tiles); -1: too many tiles
+// pivot relay: process-wide switch (srukf_debug_set(0, "pivot_relay", v)), read when a plan is built
+static int g_pivot_relay = SRUKF_PIVOT_RELAY_DEFAULT;
+void srukf_gmw_set_pivot_relay(int v) { g_pivot_relay = v ? 1 : 0; }
+int srukf_gmw_get_pivot_relay(void) { return g_pivot_relay; }
 int srukf_gmw_persist_workers(int T, int Tp, int max_workers)
 {
     const int nt = srukf_gmw_build_tiles(T, Tp, nullptr);
@@ -1172,7 +1492,7 @@ static bool gmw_register_form(int T, int Tp, int ntiles, int workers)
 // S0 / Ut0 / [u0, u1): see k_gmw_persist (null: every tile is read from G); gate_limit > 0: behind k_gmw_gate
 void srukf_launch_gmw_persist_head(hipStream_t st, int n, int ld, double eps, double* G, void* pans, double* D, double* Sout,
                                    void* sync, const void* tiles, int ntiles, int workers, void* fs,
-                                   const double* S0, const double* Ut0, int u0, int u1, int Tp, int krows, int gate_limit, const HeadArgs* hap)
+                                   const double* S0, const double* Ut0, int u0, int u1, int Tp, int krows, int gate_limit, const HeadArgs* hap, int relay)
 {
     if (gate_limit > 0) hipLaunchKernelGGL(k_gmw_gate, dim3(1), dim3(64), 0, st, (FrameScalars*)fs, gate_limit);
     const int T = ld / 64;
@@ -1182,16 +1502,16 @@ void srukf_launch_gmw_persist_head(hipStream_t st, int n, int ld, double eps, do
     if (hap) ha = *hap;
     if (workers > 0 && !gmw_register_form(T, Tp, ntiles, workers))
         hipLaunchKernelGGL((k_gmw_persist<true>), dim3(1 + workers), dim3(256), 0, st, n, ld, T, Tp, G, (GmwPanel64*)pans, Sout, D, eps,
-                           (GmwSync*)sync, (const GmwTile*)tiles, ntiles, (FrameScalars*)fs, S0, Ut0, u0, u1, krows, gate_limit > 0 ? 1 : 0, HeadArgs{});
+                           (GmwSync*)sync, (const GmwTile*)tiles, ntiles, (FrameScalars*)fs, S0, Ut0, u0, u1, krows, gate_limit > 0 ? 1 : 0, HeadArgs{}, 0);
     else
-        hipLaunchKernelGGL((k_gmw_persist<false>), dim3(ha.nhelp + 1 + workers), dim3(256), 0, st, n, ld, T, Tp, G, (GmwPanel64*)pans, Sout, D, eps,
-                           (GmwSync*)sync, (const GmwTile*)tiles, ntiles, (FrameScalars*)fs, S0, Ut0, u0, u1, krows, gate_limit > 0 ? 1 : 0, ha);
+        hipLaunchKernelGGL((k_gmw_persist<false>), dim3(ha.nhelp + (relay ? 2 : 1) + workers), dim3(256), 0, st, n, ld, T, Tp, G, (GmwPanel64*)pans, Sout, D, eps,
+                           (GmwSync*)sync, (const GmwTile*)tiles, ntiles, (FrameScalars*)fs, S0, Ut0, u0, u1, krows, gate_limit > 0 ? 1 : 0, ha, relay ? 1 : 0);
 }
 void srukf_launch_gmw_persist(hipStream_t st, int n, int ld, double eps, double* G, void* pans, double* D, double* Sout,
                               void* sync, const void* tiles, int ntiles, int workers, void* fs,
-                              const double* S0, const double* Ut0, int u0, int u1, int Tp, int krows, int gate_limit)
+                              const double* S0, const double* Ut0, int u0, int u1, int Tp, int krows, int gate_limit, int relay)
 {
-    srukf_launch_gmw_persist_head(st, n, ld, eps, G, pans, D, Sout, sync, tiles, ntiles, workers, fs, S0, Ut0, u0, u1, Tp, krows, gate_limit, nullptr);
+    srukf_launch_gmw_persist_head(st, n, ld, eps, G, pans, D, Sout, sync, tiles, ntiles, workers, fs, S0, Ut0, u0, u1, Tp, krows, gate_limit, nullptr, relay);
 }
 // the owners' tiles as a launch of its own (k_syrk_own): tiles / ntiles = the persistent launch's list, Tp / T its shape
 void srukf_launch_syrk_own(hipStream_t st, int n, int ld, const double* S0, const double* Ut0, int u0, int u1, int krows, double* G, void* fs, const void* tiles, int ntiles, int Tp)

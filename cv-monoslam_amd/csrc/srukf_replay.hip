@@ -337,9 +337,10 @@ static HeadJobs head_fold_jobs(const srukf_ctx* c) { return HeadJobs{ c->n_syrk_
 static bool head_fold_ok(const srukf_ctx* c)
 {
     const int need = g_dbg_head_fold_free.load() > 0 ? g_dbg_head_fold_free.load() : SRUKF_HEAD_FOLD_MIN_FREE_CUS;
-    const int free_cus = c->gplan_red.cus - 1 - c->gplan_red.workers;
+    const int free_cus = c->gplan_red.cus - (c->gplan_red.relay ? 2 : 1) - c->gplan_red.workers;      // what pivot(s) + workers really leave free
     const int nhelp = head_fold_jobs(c).total();
-    const bool pays = g_dbg_head_fold_free.load() > 0 || 4 * nhelp <= 9 * free_cus;      // (the A/B switch "head_fold_free" overrides the rounds rule: measurements)
+    // (the rounds rule was measured with one pivot workgroup and keeps counting that way: the relay's CU does not move the sizes at which the fold is taken)
+    const bool pays = g_dbg_head_fold_free.load() > 0 || 4 * nhelp <= 9 * (c->gplan_red.cus - 1 - c->gplan_red.workers);      // (the A/B switch "head_fold_free" overrides the rounds rule: measurements)
     return c->dbg.head_fold && c->gmw_shared == 0 && free_cus >= need && pays;
 }
 
@@ -415,7 +416,7 @@ static void refactor_owners_fold(srukf_ctx* c, const RefactorRequest& rq, const 
             c->dx_pending = false;
         }
         srukf_launch_gmw_persist_head(c->stream, n, np, c->p.epsilon, c->Wf, c->gplan_red.pans, c->D, c->G, c->gplan_red.sync, c->gplan_red.tiles, c->gplan_red.ntiles,
-                                      c->gplan_red.workers, c->fs, c->shadowA, c->Utp, 0, d.mp, c->red_Tp, kept_rows16(c), gate_limit(c), plan.head_fold ? &ha : nullptr);
+                                      c->gplan_red.workers, c->fs, c->shadowA, c->Utp, 0, d.mp, c->red_Tp, kept_rows16(c), gate_limit(c), plan.head_fold ? &ha : nullptr, c->gplan_red.relay);
     }
     ProfScope ps(c, KC_RANK_EXPAND, 0, 8.0 * 2.5 * (double)n * n);
     rank_expand(c, rq, ff);
@@ -532,7 +533,7 @@ static void refactor_full_rank(srukf_ctx* c, const RefactorRequest& rq, const Re
         for (int j0 = -64; j0 + 64 < np; j0 += 64) { fl += panel_flop(j0); by += panel_byte(j0); }
         ProfScope ps(c, KC_GMW_PERSIST, fl + syrk_flop * (1.0 - head_frac), by + syrk_byte * (1.0 - head_frac));
         if (fused) srukf_launch_gmw_persist(c->stream, n, np, c->p.epsilon, c->G, c->gplan.pans, c->D, c->Wf, c->gplan.sync, c->gplan.tiles, c->gplan.ntiles,
-                                            c->gplan.workers, c->fs, c->S, c->Ut, rq.ub, rq.ue, 0, 0, gate_limit(c));
+                                            c->gplan.workers, c->fs, c->S, c->Ut, rq.ub, rq.ue, 0, 0, gate_limit(c), c->gplan.relay);
         else launch_gmw_fast(c, c->G, c->S, GMW_ALL_PANELS);
     } else {
         int pb = 0;
@@ -603,7 +604,7 @@ void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, GmwPanels which)
             hipStreamWaitEvent(c->stream, c->ev_join, 0);
             return;
         }
-        srukf_launch_gmw_persist(c->stream, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, gp.tiles, gp.ntiles, workers, c->fs, nullptr, nullptr, 0, 0, Tp, krows, gate_limit(c));
+        srukf_launch_gmw_persist(c->stream, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, gp.tiles, gp.ntiles, workers, c->fs, nullptr, nullptr, 0, 0, Tp, krows, gate_limit(c), gp.relay);
         return;
     }
     // one launch per panel; rank-aware form: the step after the last pivoted panel still runs (it writes that panel's S rows)
