@@ -581,9 +581,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // ------------------------------------------------------------------------------------------------
 
 #include "srukf_gmw_panel.h"
+#include "srukf_gmw_pivot.h"
 
 // Critical-path workgroup of a 64-row step: owns the next panel's 64x64 diagonal region R = [base, base+64),
-// tiles (0,0), (0,1), (1,1).
+// tiles (0,0), (0,1), (1,1).  The arithmetic of each phase is in srukf_gmw_pivot.h, shared with the two pivots of the persistent launch.
 //   A   Tt1 | E | Tt2 are staged through LDS once (each wave needs all three); each wave then runs the
 //       three-stage slab for 16 of R's 64 columns -> LDS (W and L = W/D)
 //   B   quarters of tile (0,0) with K = 64 -> Xm;  factor 1: wave 0 pivots, wave 2 follows with T1'; waves 1 / 3
@@ -599,9 +600,9 @@ __device__ __forceinline__ void gmw_step64_block00(int n, int ld, int j0, int fi
                                                    double (*Lr)[G64_LS], double (*Wc)[G64_LS], double* facreg,
                                                    double* xreg, int tid)
 {
-    const int lane = tid & 63, wv = tid >> 6, lr = lane & 15, lk = lane >> 4;
+    const GmwLane L = gmw_lane_view(tid);
+    const int lane = L.lane, wv = L.wv, lr = L.lr, lk = L.lk, qa = L.qa, qb = L.qb, ro = L.ro;   // ro, waves 1 / 3: tile rows base + ro .., columns base + 32 ..
     const int base = j0 + 64;
-    const int qa = wv >> 1, qb = wv & 1;
     // two factor workspaces: factor 1's rows stay readable while factor 2 runs, so its outputs can be written then
     const GmwColsLds ws = gmw_cols_carve(facreg), ws2 = gmw_cols_carve(facreg + GMW_FAC_DOUBLES);
     double (*X01)[32] = (double (*)[32])xreg;                  // tiles (0,1) / (1,1) after the K = 64 update
@@ -614,23 +615,19 @@ __device__ __forceinline__ void gmw_step64_block00(int n, int ld, int j0, int fi
 #pragma unroll
     for (int t = 0; t < 4; t++) g[t] = G[(size_t)(base + 16 * qa + lk + 4 * t) * ld + base + 16 * qb + lr];
     const int cw = base + 16 * wv;
-    const int ro = (wv == 1) ? 0 : 32;                         // waves 1 / 3: tile rows base + ro .., columns base + 32 ..
     d4 acc[2][2];
     zero_acc(acc);
     if (!first) {
-        d4 pt[3], X2[2];
-        double fb[8], dr[4][4];
+        d4 pt[3], Gs[2][2];                                    // Gs: this wave's 16 columns of the panel rows: rows 0..31, rows 32..63 (-> G2')
+        double dr[2][2][4];
         pt[0] = *(const d4*)&cur->Tt1[4 * tid]; pt[1] = *(const d4*)&cur->E[4 * tid]; pt[2] = *(const d4*)&cur->Tt2[4 * tid];
-#pragma unroll
-        for (int u = 0; u < 8; u++) fb[u] = G[(size_t)(j0 + 4 * u + lk) * ld + cw + lr];
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int t = 0; t < 4; t++) X2[a][t] = G[(size_t)(j0 + 32 + 16 * a + lk + 4 * t) * ld + cw + lr];
 #pragma unroll
         for (int q = 0; q < 4; q++)
 #pragma unroll
-            for (int t = 0; t < 4; t++) dr[q][t] = cur->rD[16 * q + lk + 4 * t];     // 1/D of rows 16 q + lk + 4 t
+            for (int t = 0; t < 4; t++) {
+                Gs[q >> 1][q & 1][t] = G[(size_t)(j0 + 16 * q + lk + 4 * t) * ld + cw + lr];
+                dr[q >> 1][q & 1][t] = cur->rD[16 * q + lk + 4 * t];                 // 1/D of rows 16 q + lk + 4 t
+            }
         STAMP(1);
         {
             const int row = tid >> 3, c4 = ((tid & 7) * 4) ^ (16 * (row & 1));
@@ -648,33 +645,11 @@ __device__ __forceinline__ void gmw_step64_block00(int n, int ld, int j0, int fi
         }
         // ---- A: slab for columns cw .. cw+15; A operand (k = 4u + lk, column 16a + lr) of matrix m from LDS ----
         d4 W1[2] = { (d4){0, 0, 0, 0}, (d4){0, 0, 0, 0} }, W2[2] = { (d4){0, 0, 0, 0}, (d4){0, 0, 0, 0} };
-        const int sw = 16 * (lk & 1);                          // (4u + lk) & 1 == lk & 1
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const double* rowp = &PT[(4 * u + lk) * 32];
-            if (u < 4) W1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[lr ^ sw], fb[u], W1[0], 0, 0, 0);   // Tt[k][j] = 0 for k > j
-            W1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[(16 + lr) ^ sw], fb[u], W1[1], 0, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const double* rowp = &PT[1024 + (4 * u + lk) * 32];
-            X2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-rowp[lr ^ sw], W1[u >> 2][u & 3], X2[0], 0, 0, 0);
-            X2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-rowp[(16 + lr) ^ sw], W1[u >> 2][u & 3], X2[1], 0, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const double* rowp = &PT[2048 + (4 * u + lk) * 32];
-            if (u < 4) W2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[lr ^ sw], X2[u >> 2][u & 3], W2[0], 0, 0, 0);
-            W2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[(16 + lr) ^ sw], X2[u >> 2][u & 3], W2[1], 0, 0, 0);
-        }
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const int jj = 16 * a + lk + 4 * t, cc = 16 * wv + lr;
-                Wc[jj][cc] = W1[a][t];       Lr[jj][cc] = W1[a][t] * dr[a][t];
-                Wc[32 + jj][cc] = W2[a][t];  Lr[32 + jj][cc] = W2[a][t] * dr[2 + a][t];
-            }
+        gmw_slab_stage<true, false>(GmwAFromLdsSwz(PT, L), Gs[0], W1);
+        gmw_slab_stage<false, true>(GmwAFromLdsSwz(PT + 1024, L), W1, Gs[1]);
+        gmw_slab_stage<true, false>(GmwAFromLdsSwz(PT + 2048, L), Gs[1], W2);
+        gmw_slab_store<0>(L, Lr, Wc, W1, dr[0]);
+        gmw_slab_store<1>(L, Lr, Wc, W2, dr[1]);
     } else {
         STAMP(1);
         if (wv & 1) {
@@ -690,105 +665,37 @@ __device__ __forceinline__ void gmw_step64_block00(int n, int ld, int j0, int fi
     __syncthreads();
     STAMP(3);
     // ---- B: quarter (qa, qb) of tile (0,0), K = 64 ----
-    if (!first) {
-#pragma unroll
-        for (int k = 0; k < 64; k += 4)
-            g = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], g, 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; t++) ws.Xm[16 * qa + lk + 4 * t][16 * qb + lr] = g[t];
+    if (!first) gmw_quarter_update<0, 64>(L, Lr, Wc, g);
+    gmw_quarter_store(L, ws.Xm, g);
     __syncthreads();
     STAMP(4);
     // ---- factor 1 (+ panel S rows, tiles (0,1), (1,1)) ----
     if (wv == 0) gmw_cols_pivot_wave(ws, eps, lane);
     else if (wv == 2) { gmw_cols_t_wave<false>(ws, lane, nxt->Tt1, Tl); STAMPW(13); }
     else {
-        if (!first) {
-#pragma unroll
-            for (int k = 0; k < 64; k += 4) {
-                const double a0 = -Lr[k + lk][ro + lr], a1 = -Lr[k + lk][ro + 16 + lr];
-                const double b0 = Wc[k + lk][32 + lr], b1 = Wc[k + lk][48 + lr];
-                acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-            }
-        }
-        double (*X)[32] = (wv == 1) ? X01 : X11;
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int b = 0; b < 2; b++)
-#pragma unroll
-                for (int t = 0; t < 4; t++) X[16 * a + lk + 4 * t][16 * b + lr] = acc[a][b][t];
-        if (!first) {
-            // S rows of the panel for R's columns, from the LDS slab: wave 1 rows j0..j0+31, wave 3 rows j0+32..j0+63
-            // (rows / columns >= n carry zeros: G is zero there)
-            const int c4 = lr * 4;
-#pragma unroll 4
-            for (int i = 0; i < 8; i++) {
-                const int row = ro + 4 * i + lk;
-                const double sq = cur->sq[row];
-                d4 w = *(const d4*)&Wc[row][c4];
-                w[0] *= sq; w[1] *= sq; w[2] *= sq; w[3] *= sq;
-                *(d4*)&Sout[(size_t)(j0 + row) * ld + base + c4] = w;
-            }
-        }
+        if (!first) gmw_side_update<0, 64>(L, Lr, Wc, acc);
+        gmw_side_park(L, wv == 1 ? X01 : X11, acc);
+        if (!first) gmw_panel_s_rows(L, Wc, Sout, ld, j0, base, GmwSqFromMem{cur->sq});
         STAMPW(11 + wv);
     }
     STAMP(5);
     __syncthreads();
     STAMP(6);
-    // ---- C1: quarter (qa, qb) of W1d = T1' X01 and of E' = W1d / D' -> LDS (the slabs are dead by now) ----
-    {
-        d4 wq = (d4){0, 0, 0, 0};
-#pragma unroll
-        for (int u = 0; u < 8; u++)
-            wq = __builtin_amdgcn_mfma_f64_16x16x4f64(Tl[(4 * u + lk) * 33 + 16 * qa + lr], X01[4 * u + lk][16 * qb + lr], wq, 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int k = 16 * qa + lk + 4 * t, cc = 16 * qb + lr;
-            Wc[k][cc] = wq[t];                                 // Wd
-            Lr[k][cc] = wq[t] * gmw_pivot_rcp(ws.Dv[k]);       // Ld = E'
-        }
-    }
+    // ---- C1: W1d -> Wc, E' -> Lr ----
+    gmw_c1(L, Tl, X01, ws.Dv, Lr, Wc);
     __syncthreads();
-    // ---- C2: quarter of X11 -= E'^T W1d -> Xm; reset the row flags ----
-    {
-        d4 x;
-#pragma unroll
-        for (int t = 0; t < 4; t++) x[t] = X11[16 * qa + lk + 4 * t][16 * qb + lr];
-#pragma unroll
-        for (int k = 0; k < 32; k += 4)
-            x = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], x, 0, 0, 0);
-#pragma unroll
-        for (int t = 0; t < 4; t++) ws2.Xm[16 * qa + lk + 4 * t][16 * qb + lr] = x[t];
-    }
+    // ---- C2 ----
+    gmw_c2(L, X11, Lr, Wc, ws2.Xm);
     __syncthreads();
     STAMP(7);
     // ---- factor 2 ----
     if (wv == 0) gmw_cols_pivot_wave(ws2, eps, lane);
     else if (wv == 2) gmw_cols_t_wave<true>(ws2, lane, nxt->Tt2, xreg);          // X01 / X11 are dead: staging buffer
     else {
-        const int c4 = (lane & 7) * 4;
         if (wv == 1) {                                         // E' and T1' for the next launch
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int row = 8 * i + (lane >> 3);
-                *(d4*)&nxt->E[row * 32 + c4] = *(const d4*)&Lr[row][c4];
-            }
+            gmw_store_e<false>(L, Lr, nxt->E);
             gmw_copy_t(Tl, nxt->Tt1, lane);
-        } else {                                               // S rows base..base+31, columns base+32..base+63
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int row = 8 * i + (lane >> 3);
-                const double Dr = ws.Dv[row];
-                const double sq = (base + row < n) ? sqrt(Dr) * gmw_pivot_rcp(Dr) : 0.0;
-                d4 w = *(const d4*)&Wc[row][c4];
-                w[0] *= sq; w[1] *= sq; w[2] *= sq; w[3] *= sq;
-                *(d4*)&Sout[(size_t)(base + row) * ld + base + 32 + c4] = w;
-            }
-        }
+        } else gmw_s01_rows(L, ws.Dv, Wc, Sout, n, ld, base);
         gmw_cols_out_wave(ws, wv == 1 ? 0 : 1, lane, n, ld, base, nxt->D, nxt->sq, nxt->rD, Dall, Sout);             // factor 1 (all rows published long ago)
         gmw_cols_out_wave(ws2, wv == 1 ? 0 : 1, lane, n, ld, base + 32, nxt->D + 32, nxt->sq + 32, nxt->rD + 32, Dall, Sout);
     }

@@ -12,6 +12,7 @@
 #include "srukf_tiles.h"
 #include "srukf_gmw_cols.h"
 #include "srukf_gmw_panel.h"
+#include "srukf_gmw_pivot.h"
 #include "srukf_rank.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -103,9 +104,9 @@ __device__ __forceinline__ void gmw_stage_tile(double (*dst)[G64_LS], const doub
     for (int r = 0; r < 64; r++) dst[r][lane] = v[r];
 }
 
-// Pivot workgroup: panels p = 0 .. T-1.  Same phases as gmw_step64_block00 (A slab, B tile (0,0), factor 1, C, factor 2);
-// what differs is where the operands come from: the previous panel from LDS, G tiles through agent-scope loads after
-// their version flags, and the panel buffer is published for the workers.
+// Pivot workgroup: panels p = 0 .. T-1.  The panel phases of srukf_gmw_pivot.h (A slab, B tile (0,0), factor 1, C, factor 2), as in
+// gmw_step64_block00; what differs is where the operands come from: the previous panel from LDS, G tiles through agent-scope loads
+// after their version flags, and the panel buffer is published for the workers.
 // Tp <= T: number of 64-row panels that are actually pivoted.  Tp < T = rank-aware form: the matrix arrives permuted so that its
 // structurally null directions come last, only the leading Tp panels are factored, and the column blocks behind them are carried
 // along as ordinary off-diagonal tiles (row block Tp exists in the tile list so that somebody writes the last panel's S rows).
@@ -114,16 +115,14 @@ __device__ __forceinline__ void gmw_pivot_persist(int n, int ld, int T, int Tp, 
                                                   double (*Lr)[G64_LS], double (*Wc)[G64_LS], double* facreg, double* xreg, double* keepreg,
                                                   int* okp, int* halfcnt, int* stageok, int tid, int klim)
 {
-    const int lane = tid & 63, wv = tid >> 6, lr = lane & 15, lk = lane >> 4;
-    const int qa = wv >> 1, qb = wv & 1;
+    const GmwLane L = gmw_lane_view(tid);
+    const int lane = L.lane, wv = L.wv, wvu = L.wvu;           // wvu: wave-uniform copy, scalar branches around everything that polls or raises flags
     const GmwColsLds ws = gmw_cols_carve(facreg), ws2 = gmw_cols_carve(facreg + GMW_FAC_DOUBLES);
     double (*X01)[32] = (double (*)[32])xreg;
     double (*X11)[32] = (double (*)[32])(xreg + 1024);
     GmwPivotKeep kp;
     kp.T1 = xreg + 2048; kp.T2 = xreg; kp.Ep = keepreg; kp.rD = keepreg + 1024; kp.sq = keepreg + 1088;
     unsigned long long* ver = gmw_sync_ver(sy);
-    const int ro = (wv == 1) ? 0 : 32;
-    const int wvu = __builtin_amdgcn_readfirstlane(wv);        // wave-uniform copy: scalar branches around everything that polls or raises flags
     const bool wv0 = wvu == 0, wv1 = wvu == 1, wv3 = wvu == 3;
     if (wv0) *okp = 1;
     if (wv3) gmw_stage_tile(Wc, G, ld, 0, 0, lane);            // region R_0 as k_syrk left it
@@ -139,141 +138,52 @@ __device__ __forceinline__ void gmw_pivot_persist(int n, int ld, int T, int Tp, 
         // operands staged in LDS by waves 1 / 3 during factor 2 of the previous panel: Lr = tile (p-1, p) (rows of the
         // current panel, columns of R), Wc = tile (p, p) (R itself)
         if (wv0) { ws.Dv[lane & 31] = 0.0; ws2.Dv[lane & 31] = 0.0; *halfcnt = 0; stageok[lane & 1] = 0; }
-        d4 g;
-#pragma unroll
-        for (int t = 0; t < 4; t++) g[t] = Wc[16 * qa + lk + 4 * t][16 * qb + lr];
+        d4 g = gmw_quarter_load(L, Wc);
         d4 acc[2][2];
         zero_acc(acc);
-        if (wv & 1) {
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++)
-#pragma unroll
-                    for (int t = 0; t < 4; t++) acc[a][b][t] = Wc[ro + 16 * a + lk + 4 * t][32 + 16 * b + lr];
-        }
-        d4 X2[2];
-        double fb[8], dr[4][4];
+        if (wv & 1) gmw_side_load(L, Wc, acc);
+        d4 Gs[2][2];                                           // this wave's 16 columns of tile (p-1, p): rows 0..31, rows 32..63 (-> G2')
+        double dr[2][2][4];
         if (!first) {
-#pragma unroll
-            for (int u = 0; u < 8; u++) fb[u] = Lr[4 * u + lk][16 * wv + lr];
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int t = 0; t < 4; t++) X2[a][t] = Lr[32 + 16 * a + lk + 4 * t][16 * wv + lr];
+            gmw_slab_operands(L, Lr, Gs);
 #pragma unroll
             for (int q = 0; q < 4; q++)
 #pragma unroll
-                for (int t = 0; t < 4; t++) dr[q][t] = kp.rD[16 * q + lk + 4 * t];
+                for (int t = 0; t < 4; t++) dr[q >> 1][q & 1][t] = kp.rD[16 * q + L.lk + 4 * t];
         }
         __syncthreads();                                       // staged tiles are in registers: Lr / Wc may be rewritten
         if (!first) {
             // ---- A: slab for columns cw .. cw+15, panel matrices from LDS ----
             d4 W1[2] = { (d4){0, 0, 0, 0}, (d4){0, 0, 0, 0} }, W2[2] = { (d4){0, 0, 0, 0}, (d4){0, 0, 0, 0} };
-            const int sw = 16 * (lk & 1);
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const double* rowp = &kp.T1[(4 * u + lk) * 33];
-                if (u < 4) W1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[lr], fb[u], W1[0], 0, 0, 0);
-                W1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[16 + lr], fb[u], W1[1], 0, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const double* rowp = &kp.Ep[(4 * u + lk) * 32];
-                X2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-rowp[lr ^ sw], W1[u >> 2][u & 3], X2[0], 0, 0, 0);
-                X2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-rowp[(16 + lr) ^ sw], W1[u >> 2][u & 3], X2[1], 0, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const double* rowp = &kp.T2[(4 * u + lk) * 33];
-                if (u < 4) W2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[lr], X2[u >> 2][u & 3], W2[0], 0, 0, 0);
-                W2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(rowp[16 + lr], X2[u >> 2][u & 3], W2[1], 0, 0, 0);
-            }
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const int jj = 16 * a + lk + 4 * t, cc = 16 * wv + lr;
-                    Wc[jj][cc] = W1[a][t];       Lr[jj][cc] = W1[a][t] * dr[a][t];
-                    Wc[32 + jj][cc] = W2[a][t];  Lr[32 + jj][cc] = W2[a][t] * dr[2 + a][t];
-                }
+            gmw_slab_stage<true, false>(GmwAFromLds33(kp.T1, L), Gs[0], W1);
+            gmw_slab_stage<false, true>(GmwAFromLdsSwz(kp.Ep, L), W1, Gs[1]);
+            gmw_slab_stage<true, false>(GmwAFromLds33(kp.T2, L), Gs[1], W2);
+            gmw_slab_store<0>(L, Lr, Wc, W1, dr[0]);
+            gmw_slab_store<1>(L, Lr, Wc, W2, dr[1]);
         }
         if (wv0) GMW_TS(sy, p, 1);
         __syncthreads();
         // ---- B: quarter (qa, qb) of tile (0,0), K = 64 ----
-        if (!first) {
-#pragma unroll
-            for (int k = 0; k < 64; k += 4)
-                g = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], g, 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < 4; t++) ws.Xm[16 * qa + lk + 4 * t][16 * qb + lr] = g[t];
+        if (!first) gmw_quarter_update<0, 64>(L, Lr, Wc, g);
+        gmw_quarter_store(L, ws.Xm, g);
         __syncthreads();
         if (wv0) GMW_TS(sy, p, 2);
         // ---- factor 1 (+ panel S rows, tiles (0,1), (1,1)) ----
         if (wv0) { gmw_cols_pivot_wave(ws, eps, lane); GMW_TS(sy, p + 64, 4); }
         else if (wvu == 2) { gmw_cols_t_wave<0>(ws, lane, nullptr, kp.T1); GMW_TS(sy, p + 64, 5); }
         else {
-            if (!first) {
-#pragma unroll
-                for (int k = 0; k < 64; k += 4) {
-                    const double a0 = -Lr[k + lk][ro + lr], a1 = -Lr[k + lk][ro + 16 + lr];
-                    const double b0 = Wc[k + lk][32 + lr], b1 = Wc[k + lk][48 + lr];
-                    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-                }
-            }
-            double (*X)[32] = (wv == 1) ? X01 : X11;           // X01 overwrites T2 of the previous panel: dead since phase A
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++)
-#pragma unroll
-                    for (int t = 0; t < 4; t++) X[16 * a + lk + 4 * t][16 * b + lr] = acc[a][b][t];
-            if (!first) {
-                const int c4 = lr * 4;
-#pragma unroll 4
-                for (int i = 0; i < 8; i++) {
-                    const int row = ro + 4 * i + lk;
-                    const double sq = kp.sq[row];
-                    d4 w = *(const d4*)&Wc[row][c4];
-                    w[0] *= sq; w[1] *= sq; w[2] *= sq; w[3] *= sq;
-                    *(d4*)&Sout[(size_t)(j0 + row) * ld + base + c4] = w;
-                }
-            }
+            if (!first) gmw_side_update<0, 64>(L, Lr, Wc, acc);
+            gmw_side_park(L, wv == 1 ? X01 : X11, acc);        // X01 overwrites T2 of the previous panel: dead since phase A
+            if (!first) gmw_panel_s_rows(L, Wc, Sout, ld, j0, base, GmwSqFromMem{kp.sq});
             if (wv1) GMW_TS(sy, p + 64, 6); else GMW_TS(sy, p + 64, 7);
         }
         __syncthreads();
         if (wv0) GMW_TS(sy, p, 3);
-        // ---- C1: quarter (qa, qb) of W1d = T1' X01 and of E' = W1d / D' ----
-        {
-            d4 wq = (d4){0, 0, 0, 0};
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                wq = __builtin_amdgcn_mfma_f64_16x16x4f64(kp.T1[(4 * u + lk) * 33 + 16 * qa + lr], X01[4 * u + lk][16 * qb + lr], wq, 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const int k = 16 * qa + lk + 4 * t, cc = 16 * qb + lr;
-                const double e = wq[t] * gmw_pivot_rcp(ws.Dv[k]);
-                Wc[k][cc] = wq[t];
-                Lr[k][cc] = e;
-                kp.Ep[k * 32 + (cc ^ (16 * (k & 1)))] = e;
-            }
-        }
+        // ---- C1: W1d, E' (also kept in LDS for the next panel's stage 2) ----
+        gmw_c1(L, kp.T1, X01, ws.Dv, Lr, Wc, [&](int k, int cc, double e) { kp.Ep[k * 32 + (cc ^ (16 * (k & 1)))] = e; });
         __syncthreads();
-        // ---- C2: quarter of X11 -= E'^T W1d -> Xm of factor 2 ----
-        if (!half_only) {
-            d4 x;
-#pragma unroll
-            for (int t = 0; t < 4; t++) x[t] = X11[16 * qa + lk + 4 * t][16 * qb + lr];
-#pragma unroll
-            for (int k = 0; k < 32; k += 4)
-                x = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], x, 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 4; t++) ws2.Xm[16 * qa + lk + 4 * t][16 * qb + lr] = x[t];
-        }
+        // ---- C2 ----
+        if (!half_only) gmw_c2(L, X11, Lr, Wc, ws2.Xm);
         __syncthreads();
         if (wv0) GMW_TS(sy, p, 4);
         // ---- factor 2.  Wave 0 pivots, wave 2 follows with T2'.  Waves 1 / 3, in the order of who is waiting for what:
@@ -304,38 +214,14 @@ __device__ __forceinline__ void gmw_pivot_persist(int n, int ld, int T, int Tp, 
             GMW_TS(sy, p + 192, 0);
             }
         } else {
-            const int c4 = (lane & 7) * 4;
-            if (wv1) {
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int row = 8 * i + (lane >> 3);
-                    st_d4<true>(&nxt->E[row * 32 + c4], *(const d4*)&Lr[row][c4]);
-                }
-                if (lane < 32) {
-                    const double D = ws.Dv[lane], rc = gmw_pivot_rcp(D), sq = sqrt(D) * rc;
-                    st_dev(&nxt->D[lane], D); st_dev(&nxt->sq[lane], sq); st_dev(&nxt->rD[lane], rc);
-                }
-            } else gmw_copy_t<true>(kp.T1, nxt->Tt1, lane);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            {
-                int prev = 0;
-                if (lane == 0) prev = __hip_atomic_fetch_add(halfcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (__builtin_amdgcn_readfirstlane(prev) == 1) gmw_set_panel_flag(sy->half_ready, ebase + p + 1, lane);
-            }
-            if (!wv1) {
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int row = 8 * i + (lane >> 3);
-                    const double Dr = ws.Dv[row];
-                    const double sq = (base + row < n) ? sqrt(Dr) * gmw_pivot_rcp(Dr) : 0.0;
-                    d4 w = *(const d4*)&Wc[row][c4];
-                    w[0] *= sq; w[1] *= sq; w[2] *= sq; w[3] *= sq;
-                    *(d4*)&Sout[(size_t)(base + row) * ld + base + 32 + c4] = w;
-                }
-            }
-            gmw_cols_out_wave<true>(ws, wv1 ? 0 : 1, lane, n, ld, base, nxt->D, nxt->sq, nxt->rD, Dall, Sout, kp.sq, kp.rD);
-            if (!half_only) gmw_cols_out_wave<true>(ws2, wv1 ? 0 : 1, lane, n, ld, base + 32, nxt->D + 32, nxt->sq + 32, nxt->rD + 32, Dall, Sout, kp.sq + 32, kp.rD + 32,
-                                                    [&] { if (p >= 1 && p + 1 < Tp) early = __hip_atomic_load(&ver[GMW_VIDX((wv1 ? p : p + 1), p + 1, T)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
+            gmw_factor2_outputs(L, ws, ws2, half_only, kp.T1, Lr, Wc, nxt, n, ld, base, Dall, Sout, kp.sq, kp.rD,
+                [&] {                                          // whoever of waves 1 / 3 sees its stores acknowledged last raises half_ready
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    int prev = 0;
+                    if (lane == 0) prev = __hip_atomic_fetch_add(halfcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (__builtin_amdgcn_readfirstlane(prev) == 1) gmw_set_panel_flag(sy->half_ready, ebase + p + 1, lane);
+                },
+                [&] { if (p >= 1 && p + 1 < Tp) early = __hip_atomic_load(&ver[GMW_VIDX((wv1 ? p : p + 1), p + 1, T)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
             if (wv1) GMW_TS(sy, p + 64, 1); else GMW_TS(sy, p + 64, 2);
         }
         if (p + 1 < Tp) {
@@ -375,16 +261,13 @@ __device__ __forceinline__ void gmw_pivot_persist(int n, int ld, int T, int Tp, 
 //   2. half   behind half_ready = p: Tt1, E, 1/D[0..31] of pans[p-1] -> W1 = T1' G1, G2' = G2 - E'^T W1, rows 0..31 of the
 //             slab, K = 0..31 of the region update                                                                    (off the chain)
 //   3. full   behind panel_ready = p: Tt2, 1/D[32..63], sqrt(D)/D -> W2 = T2' G2', rows 32..63, K = 32..63, Xm      (on the chain)
-//   then factor 1, C1, C2, factor 2 and the outputs as in gmw_pivot_persist; panel_ready = p + 1 as soon as the output waves have drained.
+//   then factor 1, C1, C2, factor 2 and the outputs: the same phases of srukf_gmw_pivot.h that gmw_pivot_persist calls; panel_ready = p + 1 as soon as the output waves have drained.
 // The panel matrices come from the panel buffer (agent-scope loads straight into MFMA fragments) instead of the LDS copies a lone
 // pivot keeps: the same bits (nxt->E is stored from the Lr values kp.Ep holds, Tt1 / Tt2 through gmw_copy_t / the T wave from the LDS
 // T', rD / sq by the same expressions from the same D), applied as the same products in the same order — K ascending on every
 // accumulator, the K loops merely cut at 32: bit-identical to gmw_pivot_persist and to the per-panel path.
 // Each pivot polls copies of the two panel flags in lines of its own (GMW_PIVOT_COPY).
-// GMW_RELAY_ACC_EARLY: waves 1 / 3 apply K = 0..31 to the (0,1) / (1,1) quarters in step 2 (1) or, with K = 32..63, under factor 1 (0).
-#ifndef GMW_RELAY_ACC_EARLY
-#define GMW_RELAY_ACC_EARLY 1
-#endif
+// Waves 1 / 3 apply K = 0..31 to the (0,1) / (1,1) quarters in step 2 and K = 32..63 under factor 1 (all of K under factor 1 measured the same frames/s).
 #define GMW_PIVOT_COPY(q) ((q) * GMW_FLAG_STRIDE + 128)
 __device__ __forceinline__ void gmw_set_panel_flag_relay(unsigned long long* f, unsigned long long v, int lane)
 {
@@ -397,8 +280,8 @@ __device__ __forceinline__ void gmw_pivot_relay(int n, int ld, int T, int Tp, do
                                                 double (*Lr)[G64_LS], double (*Wc)[G64_LS], double* facreg, double* xreg,
                                                 int* okp, int* halfcnt, int tid, int klim, const int q)
 {
-    const int lane = tid & 63, wv = tid >> 6, lr = lane & 15, lk = lane >> 4;
-    const int qa = wv >> 1, qb = wv & 1;
+    const GmwLane L = gmw_lane_view(tid);
+    const int lane = L.lane, wv = L.wv, wvu = L.wvu;
     const GmwColsLds ws = gmw_cols_carve(facreg), ws2 = gmw_cols_carve(facreg + GMW_FAC_DOUBLES);
     double (*X01)[32] = (double (*)[32])xreg;
     double (*X11)[32] = (double (*)[32])(xreg + 1024);
@@ -407,8 +290,6 @@ __device__ __forceinline__ void gmw_pivot_relay(int n, int ld, int T, int Tp, do
     unsigned long long* ver = gmw_sync_ver(sy);
     const unsigned long long* my_half = &sy->half_ready[GMW_PIVOT_COPY(q)];
     const unsigned long long* my_full = &sy->panel_ready[GMW_PIVOT_COPY(q)];
-    const int ro = (wv == 1) ? 0 : 32;
-    const int wvu = __builtin_amdgcn_readfirstlane(wv);
     const bool wv0 = wvu == 0, wv1 = wvu == 1, wv3 = wvu == 3;
     const unsigned int site = q ? 8u : 1u;
     // (diagnostic builds: the stamps are indexed by the panel, so each pivot has the slots of its own panels.  [p]: 5 iteration start, 6 tiles staged, 7 half flag seen,
@@ -444,125 +325,54 @@ __device__ __forceinline__ void gmw_pivot_relay(int n, int ld, int T, int Tp, do
         }
         if (wv0) GMW_TS(sy, p, 6);
         if (wv0) { ws.Dv[lane & 31] = 0.0; ws2.Dv[lane & 31] = 0.0; *halfcnt = 0; }
-        d4 g;
-#pragma unroll
-        for (int t = 0; t < 4; t++) g[t] = Wc[16 * qa + lk + 4 * t][16 * qb + lr];
+        d4 g = gmw_quarter_load(L, Wc);
         d4 acc[2][2];
         zero_acc(acc);
-        if (wv & 1) {
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++)
-#pragma unroll
-                    for (int t = 0; t < 4; t++) acc[a][b][t] = Wc[ro + 16 * a + lk + 4 * t][32 + 16 * b + lr];
-        }
-        d4 X2[2];
-        double fb[8], sqv[8];
-        if (!first) {
-#pragma unroll
-            for (int u = 0; u < 8; u++) fb[u] = Lr[4 * u + lk][16 * wv + lr];
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int t = 0; t < 4; t++) X2[a][t] = Lr[32 + 16 * a + lk + 4 * t][16 * wv + lr];
-        }
+        if (wv & 1) gmw_side_load(L, Wc, acc);
+        d4 Gs[2][2];                                           // this wave's 16 columns of tile (p-1, p): rows 0..31, rows 32..63 (-> G2')
+        GmwSqFromBuffer sqv;
+        if (!first) gmw_slab_operands(L, Lr, Gs);
         __syncthreads();                                       // staged tiles are in registers: Lr / Wc may be rewritten
         if (!first) {
-            const int cc = 16 * wv + lr;
             // ---- 2. first half of panel p - 1 (the other pivot is in its second factor) ----
             if (!gmw_wait_ge(my_half, ebase + p, &sy->abort)) *okp = 0;
             if (wv0) GMW_TS(sy, p, 7);
             {
-                double ta0[4], ta1[8], ea0[8], ea1[8], dr[2][4];
-#pragma unroll
-                for (int u = 0; u < 8; u++) {                  // every fragment is requested before the first MFMA
-                    const int o = (4 * u + lk) * 32 + lr;
-                    if (u < 4) ta0[u] = ld_dev(&prv->Tt1[o]);
-                    ta1[u] = ld_dev(&prv->Tt1[o + 16]);
-                    ea0[u] = ld_dev(&prv->E[o]); ea1[u] = ld_dev(&prv->E[o + 16]);
-                }
+                const GmwAFromBuffer<true> tt1(prv->Tt1, L);   // every fragment is requested before the first MFMA
+                const GmwAFromBuffer<false> ep(prv->E, L);
+                double dr[2][4];
 #pragma unroll
                 for (int a = 0; a < 2; a++)
 #pragma unroll
-                    for (int t = 0; t < 4; t++) dr[a][t] = ld_dev(&prv->rD[16 * a + lk + 4 * t]);
+                    for (int t = 0; t < 4; t++) dr[a][t] = ld_dev(&prv->rD[16 * a + L.lk + 4 * t]);
                 d4 W1[2] = { (d4){0, 0, 0, 0}, (d4){0, 0, 0, 0} };
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    if (u < 4) W1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta0[u], fb[u], W1[0], 0, 0, 0);
-                    W1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(ta1[u], fb[u], W1[1], 0, 0, 0);
-                }
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    X2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ea0[u], W1[u >> 2][u & 3], X2[0], 0, 0, 0);
-                    X2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ea1[u], W1[u >> 2][u & 3], X2[1], 0, 0, 0);
-                }
-#pragma unroll
-                for (int a = 0; a < 2; a++)
-#pragma unroll
-                    for (int t = 0; t < 4; t++) {
-                        const int jj = 16 * a + lk + 4 * t;
-                        Wc[jj][cc] = W1[a][t];       Lr[jj][cc] = W1[a][t] * dr[a][t];
-                    }
+                gmw_slab_stage<true, false>(tt1, Gs[0], W1);
+                gmw_slab_stage<false, true>(ep, W1, Gs[1]);
+                gmw_slab_store<0>(L, Lr, Wc, W1, dr);
             }
             __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 32; k += 4)
-                g = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], g, 0, 0, 0);
-#if GMW_RELAY_ACC_EARLY
-            if (wv & 1) {
-#pragma unroll
-                for (int k = 0; k < 32; k += 4) {
-                    const double a0 = -Lr[k + lk][ro + lr], a1 = -Lr[k + lk][ro + 16 + lr];
-                    const double b0 = Wc[k + lk][32 + lr], b1 = Wc[k + lk][48 + lr];
-                    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-                }
-            }
-#endif
+            gmw_quarter_update<0, 32>(L, Lr, Wc, g);
+            if (wv & 1) gmw_side_update<0, 32>(L, Lr, Wc, acc);
             if (wv0) GMW_TS(sy, p, 0);
             // ---- 3. second half: the only part between the other pivot's last pivot and this one's first ----
             if (!gmw_wait_ge(my_full, ebase + p, &sy->abort)) *okp = 0;
             if (wv0) GMW_TS(sy, p, 1);
             {
-                double tb0[4], tb1[8], dr2[2][4];
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const int o = (4 * u + lk) * 32 + lr;
-                    if (u < 4) tb0[u] = ld_dev(&prv->Tt2[o]);
-                    tb1[u] = ld_dev(&prv->Tt2[o + 16]);
-                }
+                const GmwAFromBuffer<true> tt2(prv->Tt2, L);
+                double dr2[2][4];
 #pragma unroll
                 for (int a = 0; a < 2; a++)
 #pragma unroll
-                    for (int t = 0; t < 4; t++) dr2[a][t] = ld_dev(&prv->rD[32 + 16 * a + lk + 4 * t]);
-                if (wv & 1) {
-#pragma unroll
-                    for (int i = 0; i < 8; i++) sqv[i] = ld_dev(&prv->sq[ro + 4 * i + lk]);
-                }
+                    for (int t = 0; t < 4; t++) dr2[a][t] = ld_dev(&prv->rD[32 + 16 * a + L.lk + 4 * t]);
+                if (wv & 1) sqv.load(L, prv->sq);
                 d4 W2[2] = { (d4){0, 0, 0, 0}, (d4){0, 0, 0, 0} };
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    if (u < 4) W2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(tb0[u], X2[u >> 2][u & 3], W2[0], 0, 0, 0);
-                    W2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(tb1[u], X2[u >> 2][u & 3], W2[1], 0, 0, 0);
-                }
-#pragma unroll
-                for (int a = 0; a < 2; a++)
-#pragma unroll
-                    for (int t = 0; t < 4; t++) {
-                        const int jj = 32 + 16 * a + lk + 4 * t;
-                        Wc[jj][cc] = W2[a][t];       Lr[jj][cc] = W2[a][t] * dr2[a][t];
-                    }
+                gmw_slab_stage<true, false>(tt2, Gs[1], W2);
+                gmw_slab_store<1>(L, Lr, Wc, W2, dr2);
             }
             __syncthreads();
-#pragma unroll
-            for (int k = 32; k < 64; k += 4)
-                g = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], g, 0, 0, 0);
+            gmw_quarter_update<32, 64>(L, Lr, Wc, g);
         }
-#pragma unroll
-        for (int t = 0; t < 4; t++) ws.Xm[16 * qa + lk + 4 * t][16 * qb + lr] = g[t];
+        gmw_quarter_store(L, ws.Xm, g);
         __syncthreads();
         if (wv0) GMW_TS(sy, p, 2);
         if (!*okp) { if (wv0) gmw_abandon(sy, site); return; }  // a wait of step 2 / 3 expired: nothing of this panel has been published
@@ -570,65 +380,18 @@ __device__ __forceinline__ void gmw_pivot_relay(int n, int ld, int T, int Tp, do
         if (wv0) { gmw_cols_pivot_wave(ws, eps, lane); GMW_TS(sy, p + 64, 4); }
         else if (wvu == 2) { gmw_cols_t_wave<0>(ws, lane, nullptr, T1l); GMW_TS(sy, p + 64, 5); }
         else {
-            if (!first) {
-#pragma unroll
-                for (int k = GMW_RELAY_ACC_EARLY ? 32 : 0; k < 64; k += 4) {
-                    const double a0 = -Lr[k + lk][ro + lr], a1 = -Lr[k + lk][ro + 16 + lr];
-                    const double b0 = Wc[k + lk][32 + lr], b1 = Wc[k + lk][48 + lr];
-                    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-                }
-            }
-            double (*X)[32] = (wv == 1) ? X01 : X11;
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++)
-#pragma unroll
-                    for (int t = 0; t < 4; t++) X[16 * a + lk + 4 * t][16 * b + lr] = acc[a][b][t];
-            if (!first) {
-                const int c4 = lr * 4;
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int row = ro + 4 * i + lk;
-                    const double sq = sqv[i];
-                    d4 w = *(const d4*)&Wc[row][c4];
-                    w[0] *= sq; w[1] *= sq; w[2] *= sq; w[3] *= sq;
-                    *(d4*)&Sout[(size_t)(j0 + row) * ld + base + c4] = w;
-                }
-            }
+            if (!first) gmw_side_update<32, 64>(L, Lr, Wc, acc);
+            gmw_side_park(L, wv == 1 ? X01 : X11, acc);
+            if (!first) gmw_panel_s_rows(L, Wc, Sout, ld, j0, base, sqv);
             if (wv1) GMW_TS(sy, p + 64, 6); else GMW_TS(sy, p + 64, 7);
         }
         __syncthreads();
         if (wv0) GMW_TS(sy, p, 3);
-        // ---- C1: quarter (qa, qb) of W1d = T1' X01 and of E' = W1d / D' ----
-        {
-            d4 wq = (d4){0, 0, 0, 0};
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                wq = __builtin_amdgcn_mfma_f64_16x16x4f64(T1l[(4 * u + lk) * 33 + 16 * qa + lr], X01[4 * u + lk][16 * qb + lr], wq, 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const int k = 16 * qa + lk + 4 * t, cc = 16 * qb + lr;
-                const double e = wq[t] * gmw_pivot_rcp(ws.Dv[k]);
-                Wc[k][cc] = wq[t];
-                Lr[k][cc] = e;
-            }
-        }
+        // ---- C1: W1d, E' ----
+        gmw_c1(L, T1l, X01, ws.Dv, Lr, Wc);
         __syncthreads();
-        // ---- C2: quarter of X11 -= E'^T W1d -> Xm of factor 2 ----
-        if (!half_only) {
-            d4 x;
-#pragma unroll
-            for (int t = 0; t < 4; t++) x[t] = X11[16 * qa + lk + 4 * t][16 * qb + lr];
-#pragma unroll
-            for (int k = 0; k < 32; k += 4)
-                x = __builtin_amdgcn_mfma_f64_16x16x4f64(-Lr[k + lk][16 * qa + lr], Wc[k + lk][16 * qb + lr], x, 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 4; t++) ws2.Xm[16 * qa + lk + 4 * t][16 * qb + lr] = x[t];
-        }
+        // ---- C2 ----
+        if (!half_only) gmw_c2(L, X11, Lr, Wc, ws2.Xm);
         __syncthreads();
         if (wv0) GMW_TS(sy, p, 4);
         // ---- factor 2: wave 0 pivots, wave 2 follows with T2', waves 1 / 3 publish the first half of the panel buffer and write the outputs ----
@@ -636,37 +399,13 @@ __device__ __forceinline__ void gmw_pivot_relay(int n, int ld, int T, int Tp, do
         else if (wvu == 2) {
             if (!half_only) { gmw_cols_t_wave<2>(ws2, lane, nxt->Tt2, T2l); GMW_TS(sy, p + 64, 3); }
         } else {
-            const int c4 = (lane & 7) * 4;
-            if (wv1) {
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int row = 8 * i + (lane >> 3);
-                    st_d4<true>(&nxt->E[row * 32 + c4], *(const d4*)&Lr[row][c4]);
-                }
-                if (lane < 32) {
-                    const double D = ws.Dv[lane], rc = gmw_pivot_rcp(D), sq = sqrt(D) * rc;
-                    st_dev(&nxt->D[lane], D); st_dev(&nxt->sq[lane], sq); st_dev(&nxt->rD[lane], rc);
-                }
-            } else gmw_copy_t<true>(T1l, nxt->Tt1, lane);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            {
-                int prev = 0;
-                if (lane == 0) prev = __hip_atomic_fetch_add(halfcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (__builtin_amdgcn_readfirstlane(prev) == 1) gmw_set_panel_flag_relay(sy->half_ready, ebase + p + 1, lane);
-            }
-            if (!wv1) {
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int row = 8 * i + (lane >> 3);
-                    const double Dr = ws.Dv[row];
-                    const double sq = (base + row < n) ? sqrt(Dr) * gmw_pivot_rcp(Dr) : 0.0;
-                    d4 w = *(const d4*)&Wc[row][c4];
-                    w[0] *= sq; w[1] *= sq; w[2] *= sq; w[3] *= sq;
-                    *(d4*)&Sout[(size_t)(base + row) * ld + base + 32 + c4] = w;
-                }
-            }
-            gmw_cols_out_wave<true>(ws, wv1 ? 0 : 1, lane, n, ld, base, nxt->D, nxt->sq, nxt->rD, Dall, Sout);
-            if (!half_only) gmw_cols_out_wave<true>(ws2, wv1 ? 0 : 1, lane, n, ld, base + 32, nxt->D + 32, nxt->sq + 32, nxt->rD + 32, Dall, Sout);
+            gmw_factor2_outputs(L, ws, ws2, half_only, T1l, Lr, Wc, nxt, n, ld, base, Dall, Sout, nullptr, nullptr,
+                [&] {                                          // whoever of waves 1 / 3 sees its stores acknowledged last raises half_ready
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    int prev = 0;
+                    if (lane == 0) prev = __hip_atomic_fetch_add(halfcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (__builtin_amdgcn_readfirstlane(prev) == 1) gmw_set_panel_flag_relay(sy->half_ready, ebase + p + 1, lane);
+                });
             if (wv1) GMW_TS(sy, p + 64, 1); else GMW_TS(sy, p + 64, 2);
         }
         // ---- 4. publish: every storing wave drains, then the barrier, then one wave raises the flag.  Nothing is staged in front of it. ----

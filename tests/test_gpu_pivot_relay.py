@@ -4,7 +4,10 @@ The relay applies the same products in the same order as the single pivot workgr
 X and S of the same replay with "pivot_relay" 0.  The sizes are the smallest at which the exclusive replay selects the register-tile persistent launch with
   Tp = 2  one hand-off, the second pivot factors the last panel        Tp = 3  the first pivot returns and its LDS is reused        Tp = 4  an even number of panels,
 each with a last panel that stops after its first 32 pivots (half_only) and with one that does not; the full-rank form (Tp = T); fp32 storage once.
-The kept rank r comes from null_directions(), the expected panel count and the half_only condition from r (gmw_pivot_persist: klim = r rounded up to 16)."""
+The kept rank r comes from null_directions(), the expected panel count and the half_only condition from r (gmw_pivot_persist: klim = r rounded up to 16).
+
+Both persistent pivots and the per-panel pivot (srukf_factor.hip, gmw_step64_block00) are built from the panel phases of srukf_gmw_pivot.h, so every case replays a third
+time with "gmw_persist" 0 (one launch per 64-row panel) and must again give the same bits."""
 import numpy as np
 import pytest
 
@@ -17,9 +20,10 @@ def _relay_default(srukf):
     return int(srukf.load_library().srukf_gmw_get_pivot_relay())
 
 
-def _replay(srukf, synth, N, relay, rank_aware, storage):
+def _replay(srukf, synth, N, relay, rank_aware, storage, persist=1):
     was = _relay_default(srukf)
     srukf.debug_set_global("pivot_relay", relay)                # read when a plan is built: before the filter exists
+    srukf.debug_set_global("gmw_persist", persist)
     try:
         p = synth.scene_params()
         sc = synth.make_scene(N, F, seed=5, p=p)
@@ -38,9 +42,10 @@ def _replay(srukf, synth, N, relay, rank_aware, storage):
         traj = f.run_frames(0, F)
         X, S = f.get_state()
         info = dict(aborts=f.debug_get("gmw_aborts"), clamp=f.debug_get("clamp_rows"), relay=f.debug_get("plan_relay"), reg=f.debug_get("plan_register_form"),
-                    T=f.debug_get("plan_T"), Tp=f.debug_get("plan_Tp"), null=f.null_directions(), n=6 * N + 4)
+                    persist=f.debug_get("plan_persist"), T=f.debug_get("plan_T"), Tp=f.debug_get("plan_Tp"), null=f.null_directions(), n=6 * N + 4)
         f.close()
     finally:
+        srukf.debug_set_global("gmw_persist", 1)
         srukf.debug_set_global("pivot_relay", was)
     return traj, X, S, info
 
@@ -59,9 +64,11 @@ CASES = [
 def test_relay_replay_is_bit_identical_to_the_single_pivot(srukf, synth, N, rank_aware, storage, Tp, half_only):
     t1, X1, S1, i1 = _replay(srukf, synth, N, 1, rank_aware, storage)
     t0, X0, S0, i0 = _replay(srukf, synth, N, 0, rank_aware, storage)
-    print(N, i1, i0)
+    tp, Xp, Sp, ip = _replay(srukf, synth, N, 1, rank_aware, storage, persist=0)     # one launch per panel: gmw_step64_block00
+    print(N, i1, i0, ip)
     for i in (i1, i0):
-        assert i["aborts"] == 0 and i["clamp"] == 0 and i["reg"] == 1, i
+        assert i["aborts"] == 0 and i["clamp"] == 0 and i["reg"] == 1 and i["persist"] == 1, i
+    assert ip["persist"] == 0 and ip["aborts"] == 0 and ip["clamp"] == 0, ip
     assert i1["relay"] == 1 and i0["relay"] == 0
     # the case is the one its name says: panels pivoted, and whether the kept pivots end in the first half of the last one
     r = i1["n"] - i1["null"]
@@ -72,6 +79,9 @@ def test_relay_replay_is_bit_identical_to_the_single_pivot(srukf, synth, N, rank
     assert np.array_equal(t1, t0)
     assert np.array_equal(X1, X0)
     assert np.array_equal(S1, S0)
+    assert np.array_equal(tp, t1)
+    assert np.array_equal(Xp, X1)
+    assert np.array_equal(Sp, S1)
 
 
 def test_relay_step_api_is_bit_identical_to_the_single_pivot(srukf, synth):
