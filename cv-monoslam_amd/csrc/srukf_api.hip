@@ -304,7 +304,7 @@ int srukf_create(srukf_ctx** out, int N, const srukf_params* p, int device, void
       ALLOC(c->zcur, mp + (Nn + 1) / 2); c->mcur = (int*)(c->zcur + mp); }                       // rows 0..3: robot rows of the cross covariances; row 4: scratch of the "fused tail" statistics
     ALLOC(c->D, np); ALLOC(c->odocur, 8); ALLOC(c->small, 64);
     ALLOC(c->theta, np); ALLOC(c->fs, 1);
-    { char* pb0 = nullptr; char* pb1 = nullptr; ALLOC(pb0, srukf_gmw_panel_bytes()); ALLOC(pb1, srukf_gmw_panel_bytes()); c->pan[0] = pb0; c->pan[1] = pb1; }
+    { char* pb0 = nullptr; char* pb1 = nullptr; ALLOC(pb0, srukf_gmw_panel_bytes()); ALLOC(pb1, srukf_gmw_panel_bytes()); c->pan[0] = (GmwPanel64*)pb0; c->pan[1] = (GmwPanel64*)pb1; }
     { const int rcg = gmw_plan_create(c->gplan, d.np, c->stream); if (rcg) { g_create_error = "persistent GMW resources: allocation failed"; srukf_destroy(c); return rcg; } }
     split_ensure(c, c->gplan);
     {
@@ -766,7 +766,7 @@ int srukf_get_covariance(srukf_ctx* c, double* P)
     HIPCHK(c, hipSetDevice(c->device));
     const int n = c->d.n; const size_t np = c->d.np;
     step_commit_motion(c);
-    srukf_launch_syrk(c->stream, c->d, c->S, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, nullptr, c->X, RankArgs{}, nullptr);
+    srukf_launch_syrk(c->stream, c->d, c->S, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, SyrkRider{});
     HIPCHK(c, hipMemcpyAsync(c->hstage, c->G, sizeof(double) * np * np, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int r = 0; r < n; r++) for (int cc = r; cc < n; cc++) { const double v = c->hstage[(size_t)r * np + cc]; P[(size_t)r * n + cc] = v; P[(size_t)cc * n + r] = v; }

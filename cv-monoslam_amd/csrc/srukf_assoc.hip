@@ -14,6 +14,7 @@
 // patch keep their previous value, as in the reference (the Mat is only zeroed at creation).
 #include "srukf_device.h"
 #include "srukf_crtrig.h"
+#include "srukf_launch.h"
 
 #define HP_INIT 10             // SLAM.cpp:41-42
 #define HP_MATCH 8             // SLAM.cpp:43-44

@@ -15,6 +15,7 @@
 // The sigma matrix itself is never materialised: only the 3K mapped angle rows (ang) are stored.
 #include "srukf_device.h"
 #include "srukf_tiles.h"
+#include "srukf_launch.h"
 
 // sigma column i of the augmented state: which row of the sqrt matrix it is built from, and its sign
 __device__ __forceinline__ void aug_column(int i, int Na, double gamma, int& row, double& g)

@@ -14,7 +14,7 @@ using namespace srukf_impl;
 struct BatchPlan {
     std::vector<srukf_ctx*> cs;
     int B = 0;
-    void *t_pxy2 = nullptr, *t_gain = nullptr, *t_syrk = nullptr, *t_own = nullptr, *t_step = nullptr, *t_exp = nullptr;
+    Pxy2Args* t_pxy2 = nullptr; GainArgs* t_gain = nullptr; SyrkArgs* t_syrk = nullptr; SyrkOwnArgs* t_own = nullptr; Step64Args* t_step = nullptr; ExpandArgs* t_exp = nullptr;
     hipGraph_t g1 = nullptr, g8 = nullptr; hipGraphExec_t e1 = nullptr, e8 = nullptr;
     std::vector<unsigned long long> sig;                    // what the captured launches depend on besides the tables' CONTENTS
 };
@@ -50,7 +50,7 @@ static void batch_plan_destroy(int device, int grp, bool keep_streams = false)
     if (bp) {
         hipSetDevice(device);
         batch_plan_drop_graphs(bp);
-        for (void* t : { bp->t_pxy2, bp->t_gain, bp->t_syrk, bp->t_own, bp->t_step, bp->t_exp }) if (t) srukf_dfree(t);
+        for (void* t : { (void*)bp->t_pxy2, (void*)bp->t_gain, (void*)bp->t_syrk, (void*)bp->t_own, (void*)bp->t_step, (void*)bp->t_exp }) if (t) srukf_dfree(t);
         delete bp;
         bd.plans[grp] = nullptr;
     }

@@ -1,5 +1,5 @@
-// srukf_ctx.h — what the host-side translation units of libsrukf_hip.so share: the context (struct srukf_ctx), the launchers of the kernel files, the
-// helpers behind the C-ABI.  Internal: include/srukf.h is the boundary.
+// srukf_ctx.h — what the host-side translation units of libsrukf_hip.so share: the context (struct srukf_ctx), the helpers behind the C-ABI.  Internal:
+// include/srukf.h is the boundary.  What the kernel files offer (launchers, size / table helpers, their argument structs) comes from srukf_launch.h, declared there only.
 //   srukf_api.hip     context lifetime, state accessors, the step-wise calls (predictMotion / predictMeasurement / KalmanUpdate), storage, profiling read-out
 //   srukf_replay.hip  the launch sequences of a frame (seq_*), the rank-aware null set, graph cache, staged replay (srukf_run_frames*)
 //   srukf_split.hip   split form of the persistent factorisation: side stream, probe, buffers
@@ -25,96 +25,7 @@
 #include <atomic>
 #include <mutex>
 #include <map>
-#include "srukf_device.h"
-#include "srukf_rank.h"
-
-extern "C" {
-void srukf_launch_motion(hipStream_t, KDims, KWeights, srukf_params, double*, double*, double*, double*, FrameScalars*, const double*, const double*, RankArgs);
-void srukf_launch_project(hipStream_t, KDims, KWeights, srukf_params, const double*, const double*, const double*, double*, double*, const FrameScalars*);
-void srukf_launch_meas_stats(hipStream_t, KDims, KWeights, const double*, const double*, const double*, double*, double*, double*, int*, double*);
-int srukf_meas_part_doubles(int);
-void srukf_launch_gain(hipStream_t, KDims, KWeights, double*, const double*, const double*, const int*, const double*, const double*,
-                       const double*, const int*, const int*, FrameScalars*, double*, double*, const double*, RankArgs, const double*, double*,
-                       const double*, int, const double*, double, const double*, int, const double*, double*);
-void srukf_launch_project_motion(hipStream_t, KDims, KWeights, srukf_params, double*, double*, double*, double*, double*, double*, FrameScalars*, RankArgs);
-int srukf_gain_part_doubles(int);
-void srukf_launch_traj(hipStream_t, KDims, const double*, const double*, FrameScalars*, double*, int);
-void srukf_launch_block_cov(hipStream_t, KDims, const double*, int, int, double*, const double*);
-void srukf_launch_project_points(hipStream_t, srukf_params, int, const double*, const double*, const double*, const double*, double*);
-void srukf_launch_pxy(hipStream_t, KDims, const double*, const double*, double*, const void*, int, KWeights, MeasArgs);
-void srukf_launch_pxy2(hipStream_t, KDims, const double*, const double*, double*, double*, const void*, int, int, KWeights, MeasArgs, GainFold);
-int srukf_pxy2_build_tiles(int mp, int np, int kr, int* out);
-int srukf_pxy2_split_groups(void);
-void srukf_launch_syrk(hipStream_t, KDims, const double*, const double*, int, int, double*, FrameScalars*, const void*, int, const double*, double*, RankArgs, const double*);
-void srukf_launch_gmw_step64(hipStream_t, int, int, int, double, double*, const void*, void*, double*, double*, const FrameScalars*);
-int srukf_gmw_panel_bytes(void);
-int srukf_gmw_sync_bytes(int T);
-int srukf_gmw_build_tiles(int T, int Tp, short* out);
-int srukf_gmw_persist_workers(int T, int Tp, int max_workers);
-void srukf_launch_gmw_persist(hipStream_t, int, int, double, double*, void*, double*, double*, void*, const void*, int, int, void*, const double*, const double*, int, int, int, int, int, int);
-void srukf_gmw_set_pivot_relay(int);
-int srukf_gmw_get_pivot_relay(void);
-void srukf_launch_gmw_persist_head(hipStream_t, int, int, double, double*, void*, double*, double*, void*, const void*, int, int, void*, const double*, const double*, int, int, int, int, int, const HeadArgs*, int);
-void srukf_launch_gmw_split(hipStream_t, hipStream_t, int, int, double, double*, void*, double*, double*, void*, const void*, int, void*, int, int, double*, double*, int);
-void srukf_launch_gmw_split_fold(hipStream_t, hipStream_t, int, int, double, double*, void*, double*, double*, void*, const void*, int, void*, int, int, double*, double*, const double*, const double*, int);
-int srukf_gmw_build_fold_list(int T, int Tp, short* out);
-int srukf_gmw_fold_head_tile(int tr, int tc, int head_rows);
-int srukf_gmw_fold_head_rows(int Tp);
-void srukf_gmw_fold_head_override(int v);
-void srukf_launch_gmw_split_alone(hipStream_t, int, int, int, double, double*, void*, double*, double*, void*, const void*, int, void*, int, int, double*, double*);
-void srukf_launch_row_energy(hipStream_t, int, int, const double*, double*);
-void srukf_launch_rank_diag(hipStream_t, int, int, const double*, const int*, double*);
-void srukf_launch_rank_expand(hipStream_t, int, int, int, double, const double*, const double*, const int*, const int*, const double*, void*, const double*, int, double*, double*, double*, double, int, KDims, KWeights, srukf_params, double*, double*, int, const StepExport*, double, unsigned int*, int);
-void srukf_launch_project_table(hipStream_t, KDims, KWeights, srukf_params, double*, double*, double*, double*, double*, double*, FrameScalars*, RankArgs, NullSkip);
-void srukf_launch_sigr_rows(hipStream_t, KDims, KWeights, const double*, const double*, double*, const FrameScalars*, const int*, int);
-void srukf_launch_rank_shadow(hipStream_t, int, int, int, const double*, const int*, double*);
-void srukf_launch_rank_canon(hipStream_t, int, int, int, double, const int*, double*);
-void srukf_launch_rank_round(hipStream_t, int, int, double*);
-void srukf_launch_syrk_own(hipStream_t, int, int, const double*, const double*, int, int, int, double*, void*, const void*, int, int);
-int srukf_gmw_register_form(int, int, int, int);
-int srukf_pxy2_b_per(int, int);
-void srukf_launch_pxy2_b(hipStream_t, KDims, const void*, int, const void*, int, int, KWeights, int);
-void srukf_launch_gain_b(hipStream_t, KDims, KWeights, const void*, int, int, double);
-void srukf_launch_syrk_b(hipStream_t, KDims, const void*, int, const void*, int, int, int, int);
-void srukf_launch_syrk_own_b(hipStream_t, int, int, const void*, int, int, int, int, const void*, int, int);
-void srukf_launch_gmw_step64_b(hipStream_t, int, int, int, double, const void*, int, int, int);
-void srukf_launch_gmw_pivslab_b(hipStream_t, int, int, int, double, const void*, int, int, int);
-void srukf_launch_gmw_trail_b(hipStream_t, int, int, const void*, int, int, int, int);
-void srukf_launch_rank_expand_b(hipStream_t, int, int, int, double, const void*, int, double, KDims, KWeights, srukf_params);
-int srukf_gmw_head_rows(void);
-int srukf_gmw_head_extra_diag(void);
-void srukf_launch_gmw_check(hipStream_t, int, int, const double*, const double*, FrameScalars*, const double*, int, double*);
-void srukf_launch_gmw_col(hipStream_t, int, int, int, double, const double*, double*, double*, unsigned long long*, FrameScalars*, double*);
-void srukf_set_exact_right_looking(int on);
-void srukf_warm_exact_path(hipStream_t st, FrameScalars* fs);
-int srukf_get_exact_right_looking(void);
-void srukf_launch_gmw_stats(hipStream_t, int, int, const double*, FrameScalars*);
-void srukf_launch_landmarks_cartesian(hipStream_t, KDims, const double*, const double*, double*, double*);
-void srukf_launch_aug_map(hipStream_t, srukf_params, int, int, int, int, double, const double*, const double*, const double*, double*);
-void srukf_launch_aug_x(hipStream_t, int, int, int, double, double, const double*, const double*, const int*, double*, double*, int, int);
-void srukf_launch_aug_build(hipStream_t, int, int, int, int, double, double, const double*, const double*, const double*, double*, int, int, int);
-void srukf_launch_gram(hipStream_t, int, int, const double*, double*);
-void srukf_launch_warp_patch(hipStream_t, KDims, srukf_params, const double*, const double*, const double*, const double*, const double*, const double*,
-                             const unsigned char*, const int*, unsigned char*);
-void srukf_launch_associate(hipStream_t, KDims, srukf_params, const unsigned char*, const double*, const double*, const int*, const int*,
-                            const unsigned char*, double*, int*, double*);
-int srukf_mixed_build_tasks(int np, int ue, short* out_tasks, int* out_tiles, int* ntiles);
-int srukf_mixed_build_tasks_red(int np, int ue, int krows, int rows_lim, short* out_tasks, int* out_tiles, int* ntiles);
-int srukf_mixed_krows(int r);
-void srukf_launch_split_bf3(hipStream_t, int, int, int, int, const double*, void*, size_t);
-void srukf_launch_syrk_bf3(hipStream_t, int, int, int, int, int, const void*, size_t, const void*, int, const void*, int, double*, double*, void*);
-size_t srukf_mixed_part_bytes(int ntasks);
-void srukf_launch_cvt_f32(hipStream_t, size_t, const double*, float*);
-void srukf_launch_cvt_robot_cols(hipStream_t, int, int, const double*, float*);
-void srukf_launch_gain_dx(hipStream_t, int, int, const double*, double*, const double*);
-void srukf_launch_syrk32(hipStream_t, int, int, int, const float*, const float*, const void*, int, const void*, int, double*, double*, void*, int);
-int srukf_app_patch_stride(void);
-int srukf_app_tmpl_stride(void);
-void srukf_launch_associate_checked(hipStream_t, KDims, srukf_params, double, double, int, int, const unsigned char*, const double*, const double*, const int*, const int*,
-                                    const unsigned char*, double*, int*, double*, double*, double*);
-int srukf_match_score_stride(void);
-int srukf_match_tmpl_stride(void);
-}
+#include "srukf_launch.h"
 
 #define SRUKF_GRAPH_FRAMES 8
 #define SRUKF_MAX_TENANTS 4                                    // 4 x (1 pivot + 63 workers with two register tiles each) fill 256 CUs at N = 200
@@ -132,7 +43,7 @@ struct ProfEvent { hipEvent_t a, b; int kc; };
 
 // ---- persistent GMW launch (k_gmw_persist): per-matrix-size resources --------------------------------
 // nreal: the tiles that hold values (ntiles minus the T - Tp pass-on tiles of the rank-aware form, which ride as a register-free third slot of the first workers)
-struct GmwPlan { void* pans = nullptr; void* sync = nullptr; void* tiles = nullptr; int ntiles = 0, nreal = 0, T = 0, Tp = 0, workers = -1, tenants = 1, cus = 0, relay = 0; };      // relay: two pivot workgroups (gmw_pivot_relay), 2 + workers resident
+struct GmwPlan { GmwPanel64* pans = nullptr; GmwSync* sync = nullptr; GmwTile* tiles = nullptr; int ntiles = 0, nreal = 0, T = 0, Tp = 0, workers = -1, tenants = 1, cus = 0, relay = 0; };      // relay: two pivot workgroups (gmw_pivot_relay), 2 + workers resident
 
 // feature detection (srukf_detect.hip): scratch of one pass over an image_w x image_h frame, allocated on the first srukf_detect_features;
 // in / out grow with the caller's map, archive and output capacities
@@ -327,7 +238,7 @@ struct srukf_map_scope : srukf_life {
     unsigned short* mxr_xt = nullptr; size_t mxr_xt_stride = 0; int mxr_ktot = 0;
     int *perm = nullptr, *iperm = nullptr;
     double* Sdis = nullptr;
-    void* pan[2] = { nullptr, nullptr };   // GMW panel hand-off buffers (double-buffered), one launch per panel
+    GmwPanel64* pan[2] = { nullptr, nullptr };   // GMW panel hand-off buffers (double-buffered), one launch per panel
     GmwPlan gplan;                         // persistent GMW launch: panel buffers, sync block, task list
     // rank-aware refactorisation (srukf_rank.hip): red_r > 0 = the n - red_r structurally null directions are not pivoted
     int red_r = 0, red_Tp = 0;
@@ -342,7 +253,7 @@ struct srukf_map_scope : srukf_life {
     double* P1 = nullptr; int* pxy2_tiles = nullptr; int n_pxy2_tiles = 0, pxy2_split_b0 = 0;   // "table" mode: k_pxy2's second K half, its tile list
     int* nskip = nullptr; int ns_full = 0, ns_null = 0, ns_rows = 0;   // NullSkip lists (srukf_device.h): [dirs | nulls | rows] in one buffer
     int* red_head0_tiles = nullptr; int n_red_head0_tiles = 0; // split fold: the k_syrk tiles that stay with the launch in front (block row 0, tile (1, 1)) ...
-    void* split_fold_list = nullptr; int n_split_fold = 0;     // ... and the grid of k_gmw_tiles_fold (forming jobs + tile workgroups, row by row: srukf_gmw_build_fold_list)
+    GmwTile* split_fold_list = nullptr; int n_split_fold = 0;     // ... and the grid of k_gmw_tiles_fold (forming jobs + tile workgroups, row by row: srukf_gmw_build_fold_list)
     double red_head0_flop = 0.0;                               // flop of the tiles in red_head0_tiles (the rest of k_syrk's count moves to the persistent launch's line of the profile)
     int* red_syrk_tiles = nullptr; int n_red_syrk_tiles = 0;   // k_syrk tiles of the kept rows (rows < 64 red_Tp) in permuted order: replay form without the owners' fold
     double red_fac_flop = 0, red_own_flop = 0;         // algorithmic flop of the rank-aware persistent launch: factorisation / owners' tiles of S^T S - U U^T
@@ -548,6 +459,20 @@ int rank_fused_mode();
 void seq_refactor(srukf_ctx* c, const RefactorRequest& rq, FrameForm ff);
 int exact_repeat_begin(srukf_ctx* c, int frame, double* traj_base);
 void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, GmwPanels which);
+// the arguments of a factorisation Gbuf -> Sout on plan gp of this context (Tp / krows <= 0: every panel pivoted / every row kept)
+GmwLaunch gmw_launch(const srukf_ctx* c, const GmwPlan& gp, double* Gbuf, double* Sout, int Tp, int krows);
+// ... as one launch per 64-row panel (g.pans / sync / tiles are not used), the two hand-off buffers alternating: j0 = -64 factors the first 64 x 64 region; rank-aware
+// form: the step after the last pivoted panel still runs (it writes that panel's S rows).  per_step(j0): what the caller holds around each launch (a ProfScope)
+template <class PerStep> inline void gmw_per_panel(hipStream_t st, const GmwLaunch& gl, GmwPanel64* const* pan, PerStep per_step)
+{
+    const GmwLaunch g = gmw_normalised(gl);
+    int pb = 0;
+    for (int j0 = -64; j0 + 64 < g.ld && j0 + 64 <= 64 * g.Tp; j0 += 64, pb ^= 1) {
+        auto around = per_step(j0);
+        srukf_launch_gmw_step64(st, g.n, g.ld, j0, g.eps, g.G, pan[pb ^ 1], pan[pb], g.D, g.Sout, g.fs);
+    }
+}
+static inline void gmw_per_panel(hipStream_t st, const GmwLaunch& g, GmwPanel64* const* pan) { gmw_per_panel(st, g, pan, [](int) { return 0; }); }
 void run_gmw(srukf_ctx* c, double* Gbuf, double* Sout, bool slow);
 int refactor_reorder(srukf_ctx* c, int ub, int ue);
 void seq_pxy(srukf_ctx* c, FrameForm ff);

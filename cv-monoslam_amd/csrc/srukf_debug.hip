@@ -283,8 +283,8 @@ int srukf_gmw_host(int device, int n, const double* G, double* S_out, double* D_
     // every device resource of the call in one holder: released on every path out
     struct Res {
         double *dG = nullptr, *dS = nullptr, *dD = nullptr, *dWf = nullptr; unsigned long long* dTh = nullptr; FrameScalars* dFs = nullptr;
-        void* pan[2] = { nullptr, nullptr }; GmwPlan gp;
-        ~Res() { for (void* b : { (void*)dG, (void*)dS, (void*)dD, (void*)dWf, (void*)dTh, (void*)dFs, pan[0], pan[1] }) if (b) srukf_dfree(b); gmw_plan_destroy(gp); }
+        GmwPanel64* pan[2] = { nullptr, nullptr }; GmwPlan gp;
+        ~Res() { for (void* b : { (void*)dG, (void*)dS, (void*)dD, (void*)dWf, (void*)dTh, (void*)dFs, (void*)pan[0], (void*)pan[1] }) if (b) srukf_dfree(b); gmw_plan_destroy(gp); }
     } r;
 #define GH(call) do { if ((call) != hipSuccess) return SRUKF_ERR_HIP; } while (0)
     GH(srukf_dmalloc((void**)&r.dG, bytes)); GH(srukf_dmalloc((void**)&r.dS, bytes)); GH(srukf_dmalloc((void**)&r.dWf, bytes));
@@ -298,14 +298,15 @@ int srukf_gmw_host(int device, int n, const double* G, double* S_out, double* D_
     if (!force_slow) {
         // the plan knows how many workgroups THIS device can keep resident (CU count); workers < 0: per-panel launches
         if (gmw_persist_mode()) { const int rc = gmw_plan_create(r.gp, np, st); if (rc) return rc; }
+        // every panel pivoted, every row kept, no gate
+        const GmwLaunch g = { .n = n, .ld = np, .eps = epsilon, .G = r.dG, .pans = r.gp.pans, .D = r.dD, .Sout = r.dS, .sync = r.gp.sync, .tiles = r.gp.tiles, .ntiles = r.gp.ntiles,
+                              .workers = r.gp.workers, .fs = r.dFs, .Tp = 0, .krows = 0, .gate_limit = 0, .relay = r.gp.relay };
         if (gmw_persist_mode() && r.gp.workers >= 0) {
-            srukf_launch_gmw_persist(st, n, np, epsilon, r.dG, r.gp.pans, r.dD, r.dS, r.gp.sync, r.gp.tiles, r.gp.ntiles, r.gp.workers, r.dFs, nullptr, nullptr, 0, 0, 0, 0, 0, r.gp.relay);
+            srukf_launch_gmw_persist(st, g, nullptr, nullptr);
         } else {
             GH(srukf_dmalloc(&r.pan[0], srukf_gmw_panel_bytes())); GH(srukf_dmalloc(&r.pan[1], srukf_gmw_panel_bytes()));
             GH(hipMemset(r.pan[0], 0, srukf_gmw_panel_bytes())); GH(hipMemset(r.pan[1], 0, srukf_gmw_panel_bytes()));
-            int pb = 0;
-            for (int j0 = -64; j0 + 64 < np; j0 += 64, pb ^= 1)
-                srukf_launch_gmw_step64(st, n, np, j0, epsilon, r.dG, r.pan[pb ^ 1], r.pan[pb], r.dD, r.dS, nullptr);
+            gmw_per_panel(st, g, r.pan);
         }
         GH(hipDeviceSynchronize());
         srukf_launch_gmw_check(st, n, np, r.dD, r.dS, r.dFs, nullptr, 0, nullptr);

@@ -15,6 +15,7 @@
 #include "srukf_motion_reduce.h"
 #include <vector>
 #include <algorithm>
+#include "srukf_launch.h"
 
 // A statistics job that rides on a contraction launch has stored its partial sums: the LAST of the MEAS_SLICES jobs of a landmark
 // group (device-scope counter per group) runs that group's final pass with its whole workgroup.  (One last workgroup for all
@@ -979,12 +980,12 @@ __global__ __launch_bounds__(256) void k_gmw_stats(int n, int ld, const double* 
 
 extern "C" {
 // ms.Z != null: MEAS_SLICES * ms.gx extra workgroups compute the measurement statistics of the frame
-void srukf_launch_pxy(hipStream_t st, KDims d, const double* DZ, const double* S, double* Ut, const void* tiles, int ntiles, KWeights w, MeasArgs ms)
+void srukf_launch_pxy(hipStream_t st, KDims d, const double* DZ, const double* S, double* Ut, const int* tiles, int ntiles, KWeights w, MeasArgs ms)
 {
     const int extra = ms.Z ? MEAS_SLICES * ms.gx : 0;
     hipLaunchKernelGGL(k_pxy, dim3(ntiles + extra), dim3(256), 0, st, d, DZ, S, Ut, (const int2*)tiles, ntiles, w, ms);
 }
-void srukf_launch_pxy2(hipStream_t st, KDims d, const double* DZp, const double* A, double* P0, double* P1, const void* tiles, int ntiles, int kr, KWeights w, MeasArgs ms, GainFold gf)
+void srukf_launch_pxy2(hipStream_t st, KDims d, const double* DZp, const double* A, double* P0, double* P1, const int* tiles, int ntiles, int kr, KWeights w, MeasArgs ms, GainFold gf)
 {
     const int extra = ms.Z ? MEAS_SLICES * ms.gx : 0;
     const dim3 grid(ntiles + extra + (ms.fmode ? 1 : 0));
@@ -1037,64 +1038,64 @@ int srukf_pxy2_build_tiles(int mp, int np, int kr, int* out)
 int srukf_pxy2_split_groups(void) { return PXY2_SPLIT; }
 // dxp != null: (n + 255)/256 extra workgroups apply the pending state update
 // ra.A != null (rank-aware replay): S / Ut are the permuted operands, ceil((n - r) / 16) more workgroups form the dropped diagonal
-void srukf_launch_syrk(hipStream_t st, KDims d, const double* S, const double* Ut, int ub, int ue, double* G, FrameScalars* fs,
-                       const void* tiles, int ntiles, const double* dxp, double* X, RankArgs ra, const double* xr1)
+void srukf_launch_syrk(hipStream_t st, KDims d, const double* S, const double* Ut, int ub, int ue, double* G, FrameScalars* fs, const int* tiles, int ntiles, const SyrkRider& rider)
 {
+    const double* dxp = rider.dxp; const RankArgs& ra = rider.ra;
     const int ndx = dxp ? (d.n + 255) / 256 : 0;
     const int krows = ra.A ? min(d.np, (ra.r + 15) & ~15) : d.np;
     const int extra = ndx + (ra.A ? (d.n - ra.r + SRUKF_RANK_COLS - 1) / SRUKF_RANK_COLS : 0);
-    hipLaunchKernelGGL(k_syrk, dim3(ntiles + extra), dim3(256), 0, st, d, S, Ut, ub, ue, G, fs, (const int2*)tiles, ntiles, dxp, X, krows, ndx, ra, xr1);
+    hipLaunchKernelGGL(k_syrk, dim3(ntiles + extra), dim3(256), 0, st, d, S, Ut, ub, ue, G, fs, (const int2*)tiles, ntiles, dxp, rider.X, krows, ndx, ra, rider.xr1);
 }
 // 64-row panel step; j0 = -64 factors the first 64x64 region only (one workgroup)
-void srukf_launch_gmw_step64(hipStream_t st, int n, int ld, int j0, double eps, double* G, const void* cur, void* nxt, double* D, double* Sout,
+void srukf_launch_gmw_step64(hipStream_t st, int n, int ld, int j0, double eps, double* G, const GmwPanel64* cur, GmwPanel64* nxt, double* D, double* Sout,
                              const FrameScalars* fs)
 {
     const int rem = ld - j0 - 64;
     if (rem <= 0) return;
     const int T = (j0 < 0) ? 1 : rem / 64;
-    hipLaunchKernelGGL(k_gmw_step64, dim3(T, T), dim3(256), 0, st, n, ld, j0, j0 < 0 ? 1 : 0, G, (const GmwPanel64*)cur, Sout, (GmwPanel64*)nxt, D, eps, fs);
+    hipLaunchKernelGGL(k_gmw_step64, dim3(T, T), dim3(256), 0, st, n, ld, j0, j0 < 0 ? 1 : 0, G, cur, Sout, nxt, D, eps, fs);
 }
 int srukf_gmw_panel_bytes(void) { return (int)sizeof(GmwPanel64); }
 // split form of a batched panel step: A (critical-path workgroups + slabs of every column block of the trailing square), B (trailing tiles of `rows` block rows)
-void srukf_launch_gmw_pivslab_b(hipStream_t st, int n, int ld, int j0, double eps, const void* tab, int B, int flip, int sel)
+void srukf_launch_gmw_pivslab_b(hipStream_t st, int n, int ld, int j0, double eps, const Step64Args* tab, int B, int flip, int sel)
 {
     const int rem = ld - j0 - 64;
     if (rem <= 0) return;
     const int cols = (j0 < 0) ? 0 : rem / 64;                  // j0 = -64: no panel yet, block (0,0) only
-    hipLaunchKernelGGL(k_gmw_pivslab_b, dim3((1 + (cols + 1) / 2) * B), dim3(256), 0, st, n, ld, j0, j0 < 0 ? 1 : 0, (const Step64Args*)tab, B, flip, eps, sel);
+    hipLaunchKernelGGL(k_gmw_pivslab_b, dim3((1 + (cols + 1) / 2) * B), dim3(256), 0, st, n, ld, j0, j0 < 0 ? 1 : 0, tab, B, flip, eps, sel);
 }
 // form: 0 the plain K = 64 update of `rows` block rows; 1 thin (block row 0 and tile (1, 1) only: two block rows of workgroups); 2 K = 128 (this panel's slabs `sel` behind the
 // previous panel's `sel ^ 1`)
-void srukf_launch_gmw_trail_b(hipStream_t st, int ld, int j0, const void* tab, int B, int rows, int sel, int form)
+void srukf_launch_gmw_trail_b(hipStream_t st, int ld, int j0, const Step64Args* tab, int B, int rows, int sel, int form)
 {
     const int cols = (ld - j0 - 64) / 64;
     if (j0 < 0 || cols <= 0 || rows < 1) return;
     if (rows > cols) rows = cols;
     if (form == 1) rows = std::min(rows, 2);
-    if (form == 2) hipLaunchKernelGGL(k_gmw_trail2_b, dim3(rows * cols * B), dim3(256), 0, st, ld, j0, (const Step64Args*)tab, B, cols, sel);
-    else hipLaunchKernelGGL(k_gmw_trail_b, dim3(rows * cols * B), dim3(256), 0, st, ld, j0, (const Step64Args*)tab, B, cols, sel, form == 1 ? 1 : 0);
+    if (form == 2) hipLaunchKernelGGL(k_gmw_trail2_b, dim3(rows * cols * B), dim3(256), 0, st, ld, j0, tab, B, cols, sel);
+    else hipLaunchKernelGGL(k_gmw_trail_b, dim3(rows * cols * B), dim3(256), 0, st, ld, j0, tab, B, cols, sel, form == 1 ? 1 : 0);
 }
 // ---- batched launches (srukf_run_frames_batch): B filters of one shape, one launch per stage, arguments per filter in device tables ----
 int srukf_pxy2_b_per(int ntiles, int gx) { return (ntiles + MEAS_SLICES * gx + 1 + 7) & ~7; }
-void srukf_launch_pxy2_b(hipStream_t st, KDims d, const void* tab, int B, const void* tiles, int ntiles, int kr, KWeights w, int gx)
+void srukf_launch_pxy2_b(hipStream_t st, KDims d, const Pxy2Args* tab, int B, const int* tiles, int ntiles, int kr, KWeights w, int gx)
 {
     const int per = srukf_pxy2_b_per(ntiles, gx);
-    hipLaunchKernelGGL(k_pxy2_b, dim3(per * B), dim3(512), 0, st, d, (const Pxy2Args*)tab, per, (const int4*)tiles, ntiles, kr, w);
+    hipLaunchKernelGGL(k_pxy2_b, dim3(per * B), dim3(512), 0, st, d, tab, per, (const int4*)tiles, ntiles, kr, w);
 }
-void srukf_launch_syrk_b(hipStream_t st, KDims d, const void* tab, int B, const void* tiles, int ntiles, int krows, int ndx, int ngd)
+void srukf_launch_syrk_b(hipStream_t st, KDims d, const SyrkArgs* tab, int B, const int* tiles, int ntiles, int krows, int ndx, int ngd)
 {
     const int nblocks = ntiles + ndx + ngd, per = (nblocks + 7) & ~7;
-    hipLaunchKernelGGL(k_syrk_b, dim3(per * B), dim3(256), 0, st, d, (const SyrkArgs*)tab, per, nblocks, d.mp, (const int2*)tiles, ntiles, krows, ndx);
+    hipLaunchKernelGGL(k_syrk_b, dim3(per * B), dim3(256), 0, st, d, tab, per, nblocks, d.mp, (const int2*)tiles, ntiles, krows, ndx);
 }
 // j0 = -64: the first 64 x 64 region only; rows = block rows of the trailing square that are updated (>= 1), flip = which panel buffer receives the new panel
-void srukf_launch_gmw_step64_b(hipStream_t st, int n, int ld, int j0, double eps, const void* tab, int B, int rows, int flip)
+void srukf_launch_gmw_step64_b(hipStream_t st, int n, int ld, int j0, double eps, const Step64Args* tab, int B, int rows, int flip)
 {
     const int rem = ld - j0 - 64;
     if (rem <= 0) return;
     const int cols = (j0 < 0) ? 1 : rem / 64;
     if (j0 < 0 || rows < 1) rows = 1;
     if (rows > cols) rows = cols;
-    hipLaunchKernelGGL(k_gmw_step64_b, dim3(rows * cols * B), dim3(256), 0, st, n, ld, j0, j0 < 0 ? 1 : 0, (const Step64Args*)tab, B, cols, flip, eps);
+    hipLaunchKernelGGL(k_gmw_step64_b, dim3(rows * cols * B), dim3(256), 0, st, n, ld, j0, j0 < 0 ? 1 : 0, tab, B, cols, flip, eps);
 }
 void srukf_launch_gmw_check(hipStream_t st, int n, int ld, const double* D, const double* S, FrameScalars* fs, const double* X, int do_traj, double* Scopy)
 {

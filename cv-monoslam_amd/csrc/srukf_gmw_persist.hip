@@ -14,6 +14,7 @@
 #include "srukf_gmw_panel.h"
 #include "srukf_gmw_pivot.h"
 #include "srukf_rank.h"
+#include "srukf_launch.h"
 
 // ------------------------------------------------------------------------------------------------
 // Persistent form: the whole factorisation in ONE launch (k_gmw_persist).
@@ -1222,78 +1223,71 @@ int srukf_gmw_persist_workers(int T, int Tp, int max_workers)
     if (nt <= GMW_OWNED_MEM * max_workers) return max_workers;   // > GMW_OWNED_MAX tiles per worker: the memory-tile form (no third slot: every tile is a list entry)
     return -1;
 }
-// register form (true) or memory-tile form (false) for `workers` workers: what srukf_launch_gmw_persist_head decides by
+// register form (true) or memory-tile form (false) for `workers` workers: what srukf_launch_gmw_persist decides by
 static bool gmw_register_form(int T, int Tp, int ntiles, int workers)
 {
     const int npass = (Tp > 0 && Tp < T) ? T - Tp : 0, nreal = ntiles - npass;
     return workers > 0 && nreal <= GMW_OWNED_MAX * workers && npass <= workers;
 }
-// S0 / Ut0 / [u0, u1): see k_gmw_persist (null: every tile is read from G); gate_limit > 0: behind k_gmw_gate
-void srukf_launch_gmw_persist_head(hipStream_t st, int n, int ld, double eps, double* G, void* pans, double* D, double* Sout,
-                                   void* sync, const void* tiles, int ntiles, int workers, void* fs,
-                                   const double* S0, const double* Ut0, int u0, int u1, int Tp, int krows, int gate_limit, const HeadArgs* hap, int relay)
+// fused: see k_gmw_persist (null: every tile is read from G); head: the head fold's helper workgroups (null: none); g.gate_limit > 0: behind k_gmw_gate
+void srukf_launch_gmw_persist(hipStream_t st, const GmwLaunch& gl, const GmwFused* fused, const HeadArgs* head)
 {
-    if (gate_limit > 0) hipLaunchKernelGGL(k_gmw_gate, dim3(1), dim3(64), 0, st, (FrameScalars*)fs, gate_limit);
-    const int T = ld / 64;
-    if (Tp <= 0 || Tp > T) Tp = T;
-    if (krows <= 0 || krows > ld) krows = ld;
-    HeadArgs ha = {};
-    if (hap) ha = *hap;
-    if (workers > 0 && !gmw_register_form(T, Tp, ntiles, workers))
-        hipLaunchKernelGGL((k_gmw_persist<true>), dim3(1 + workers), dim3(256), 0, st, n, ld, T, Tp, G, (GmwPanel64*)pans, Sout, D, eps,
-                           (GmwSync*)sync, (const GmwTile*)tiles, ntiles, (FrameScalars*)fs, S0, Ut0, u0, u1, krows, gate_limit > 0 ? 1 : 0, HeadArgs{}, 0);
+    const GmwLaunch g = gmw_normalised(gl);
+    if (g.gate_limit > 0) hipLaunchKernelGGL(k_gmw_gate, dim3(1), dim3(64), 0, st, g.fs, g.gate_limit);
+    const int T = g.ld / 64;
+    const GmwFused fu = fused ? *fused : GmwFused{};
+    const HeadArgs ha = head ? *head : HeadArgs{};
+    if (g.workers > 0 && !gmw_register_form(T, g.Tp, g.ntiles, g.workers))
+        hipLaunchKernelGGL((k_gmw_persist<true>), dim3(1 + g.workers), dim3(256), 0, st, g.n, g.ld, T, g.Tp, g.G, g.pans, g.Sout, g.D, g.eps,
+                           g.sync, g.tiles, g.ntiles, g.fs, fu.S0, fu.Ut0, fu.u0, fu.u1, g.krows, g.gate_limit > 0 ? 1 : 0, HeadArgs{}, 0);
     else
-        hipLaunchKernelGGL((k_gmw_persist<false>), dim3(ha.nhelp + (relay ? 2 : 1) + workers), dim3(256), 0, st, n, ld, T, Tp, G, (GmwPanel64*)pans, Sout, D, eps,
-                           (GmwSync*)sync, (const GmwTile*)tiles, ntiles, (FrameScalars*)fs, S0, Ut0, u0, u1, krows, gate_limit > 0 ? 1 : 0, ha, relay ? 1 : 0);
-}
-void srukf_launch_gmw_persist(hipStream_t st, int n, int ld, double eps, double* G, void* pans, double* D, double* Sout,
-                              void* sync, const void* tiles, int ntiles, int workers, void* fs,
-                              const double* S0, const double* Ut0, int u0, int u1, int Tp, int krows, int gate_limit, int relay)
-{
-    srukf_launch_gmw_persist_head(st, n, ld, eps, G, pans, D, Sout, sync, tiles, ntiles, workers, fs, S0, Ut0, u0, u1, Tp, krows, gate_limit, nullptr, relay);
+        hipLaunchKernelGGL((k_gmw_persist<false>), dim3(ha.nhelp + (g.relay ? 2 : 1) + g.workers), dim3(256), 0, st, g.n, g.ld, T, g.Tp, g.G, g.pans, g.Sout, g.D, g.eps,
+                           g.sync, g.tiles, g.ntiles, g.fs, fu.S0, fu.Ut0, fu.u0, fu.u1, g.krows, g.gate_limit > 0 ? 1 : 0, ha, g.relay ? 1 : 0);
 }
 // the owners' tiles as a launch of its own (k_syrk_own): tiles / ntiles = the persistent launch's list, Tp / T its shape
-void srukf_launch_syrk_own(hipStream_t st, int n, int ld, const double* S0, const double* Ut0, int u0, int u1, int krows, double* G, void* fs, const void* tiles, int ntiles, int Tp)
+void srukf_launch_syrk_own(hipStream_t st, int n, int ld, const double* S0, const double* Ut0, int u0, int u1, int krows, double* G, FrameScalars* fs, const GmwTile* tiles, int ntiles, int Tp)
 {
     const int T = ld / 64;
     const int nreal = ntiles - ((Tp > 0 && Tp < T) ? T - Tp : 0);
     if (krows <= 0 || krows > ld) krows = ld;
-    if (nreal > 0) hipLaunchKernelGGL(k_syrk_own, dim3(nreal), dim3(256), 0, st, n, ld, S0, Ut0, u0, u1, krows, G, (FrameScalars*)fs, (const GmwTile*)tiles, nreal);
+    if (nreal > 0) hipLaunchKernelGGL(k_syrk_own, dim3(nreal), dim3(256), 0, st, n, ld, S0, Ut0, u0, u1, krows, G, fs, tiles, nreal);
 }
-void srukf_launch_syrk_own_b(hipStream_t st, int n, int ld, const void* tab, int B, int u0, int u1, int krows, const void* tiles, int ntiles, int Tp)
+void srukf_launch_syrk_own_b(hipStream_t st, int n, int ld, const SyrkOwnArgs* tab, int B, int u0, int u1, int krows, const GmwTile* tiles, int ntiles, int Tp)
 {
     const int T = ld / 64;
     const int nreal = ntiles - ((Tp > 0 && Tp < T) ? T - Tp : 0);
     if (krows <= 0 || krows > ld) krows = ld;
-    if (nreal > 0) hipLaunchKernelGGL(k_syrk_own_b, dim3(nreal * B), dim3(256), 0, st, n, ld, (const SyrkOwnArgs*)tab, B, u0, u1, krows, (const GmwTile*)tiles, nreal);
+    if (nreal > 0) hipLaunchKernelGGL(k_syrk_own_b, dim3(nreal * B), dim3(256), 0, st, n, ld, tab, B, u0, u1, krows, tiles, nreal);
 }
 int srukf_gmw_register_form(int T, int Tp, int ntiles, int workers) { return gmw_register_form(T, Tp, ntiles, workers) ? 1 : 0; }
 // split form: stA = the filter's stream (k_gmw_pivslab_persist), stB = its side stream (gate + k_gmw_tiles_persist); the caller orders stB behind whatever produced
-// G (event) and stA behind stB afterwards.  tiles / ntiles: the plan's list (the pass-on tiles at its end are not launched: the slab workgroups write their S rows).
-void srukf_launch_gmw_split(hipStream_t stA, hipStream_t stB, int n, int ld, double eps, double* G, void* pans, double* D, double* Sout, void* sync,
-                            const void* tiles, int ntiles, void* fs, int Tp, int krows, double* Wslab, double* Lslab, int starve)
+// G (event) and stA behind stB afterwards.  g.tiles / g.ntiles: the plan's list (the pass-on tiles at its end are not launched: the slab workgroups write their S rows).
+// The pivot / slab launch of the pair, which every form of it starts with; total: the workgroups of both launches (the last one out re-arms the sync block)
+static void gmw_launch_pivslab(hipStream_t st, const GmwLaunch& g, double* Wslab, double* Lslab, unsigned int total)
 {
-    const int T = ld / 64;
-    if (Tp <= 0 || Tp > T) Tp = T;
-    if (krows <= 0 || krows > ld) krows = ld;
-    const int nreal = ntiles - ((Tp < T) ? T - Tp : 0);
+    const int T = g.ld / 64;
+    hipLaunchKernelGGL(k_gmw_pivslab_persist, dim3(T), dim3(256), 0, st, g.n, g.ld, T, g.Tp, g.G, g.pans, g.Sout, g.D, g.eps, g.sync, g.fs, g.krows, Wslab, Lslab, total);
+}
+void srukf_launch_gmw_split(hipStream_t stA, hipStream_t stB, const GmwLaunch& gl, double* Wslab, double* Lslab, int starve)
+{
+    const GmwLaunch g = gmw_normalised(gl);
+    const int T = g.ld / 64;
+    const int nreal = g.ntiles - ((g.Tp < T) ? T - g.Tp : 0);
     const unsigned int total = (unsigned)(T + (starve ? 0 : nreal));
-    hipLaunchKernelGGL(k_gmw_pivslab_persist, dim3(T), dim3(256), 0, stA, n, ld, T, Tp, G, (GmwPanel64*)pans, Sout, D, eps, (GmwSync*)sync, (FrameScalars*)fs, krows, Wslab, Lslab, total);
-    hipLaunchKernelGGL(k_gmw_split_gate, dim3(1), dim3(64), 0, stB, (GmwSync*)sync, (const FrameScalars*)fs, (unsigned)T);
+    gmw_launch_pivslab(stA, g, Wslab, Lslab, total);
+    hipLaunchKernelGGL(k_gmw_split_gate, dim3(1), dim3(64), 0, stB, g.sync, (const FrameScalars*)g.fs, (unsigned)T);
     // starve (tests): the tile launch never arrives, as if the GPU were taken — the bounded waits of the pivot and the slab workgroups expire, the frame is flagged
-    if (nreal > 0 && !starve) hipLaunchKernelGGL(k_gmw_tiles_persist, dim3(nreal), dim3(256), 0, stB, ld, T, G, (GmwSync*)sync, (const GmwTile*)tiles, (FrameScalars*)fs, Wslab, Lslab, total);
+    if (nreal > 0 && !starve) hipLaunchKernelGGL(k_gmw_tiles_persist, dim3(nreal), dim3(256), 0, stB, g.ld, T, g.G, g.sync, g.tiles, g.fs, Wslab, Lslab, total);
 }
 // Measurement only (srukf_debug_split_replay): ONE launch of the pair, alone, against the buffers and flags a real run of the pair left behind (epoch set back by
 // the caller): which = 0 the pivot / slab launch, 1 the tile launch without its residency gate.  The last workgroup out re-arms the block as in the real pair.
-void srukf_launch_gmw_split_alone(hipStream_t st, int which, int n, int ld, double eps, double* G, void* pans, double* D, double* Sout, void* sync,
-                                  const void* tiles, int ntiles, void* fs, int Tp, int krows, double* Wslab, double* Lslab)
+void srukf_launch_gmw_split_alone(hipStream_t st, int which, const GmwLaunch& gl, double* Wslab, double* Lslab)
 {
-    const int T = ld / 64;
-    if (Tp <= 0 || Tp > T) Tp = T;
-    if (krows <= 0 || krows > ld) krows = ld;
-    const int nreal = ntiles - ((Tp < T) ? T - Tp : 0);
-    if (which == 0) hipLaunchKernelGGL(k_gmw_pivslab_persist, dim3(T), dim3(256), 0, st, n, ld, T, Tp, G, (GmwPanel64*)pans, Sout, D, eps, (GmwSync*)sync, (FrameScalars*)fs, krows, Wslab, Lslab, (unsigned)T);
-    else if (nreal > 0) hipLaunchKernelGGL(k_gmw_tiles_persist, dim3(nreal), dim3(256), 0, st, ld, T, G, (GmwSync*)sync, (const GmwTile*)tiles, (FrameScalars*)fs, Wslab, Lslab, (unsigned)nreal);
+    const GmwLaunch g = gmw_normalised(gl);
+    const int T = g.ld / 64;
+    const int nreal = g.ntiles - ((g.Tp < T) ? T - g.Tp : 0);
+    if (which == 0) gmw_launch_pivslab(st, g, Wslab, Lslab, (unsigned)T);
+    else if (nreal > 0) hipLaunchKernelGGL(k_gmw_tiles_persist, dim3(nreal), dim3(256), 0, st, g.ld, T, g.G, g.sync, g.tiles, g.fs, Wslab, Lslab, (unsigned)nreal);
 }
 // Split fold: the grid of k_gmw_tiles_fold (4 shorts per entry; out may be null; returns the number of entries) for T block columns, Tp pivoted panels.  Per block row
 // I >= 1 with tile workgroups: the row's forming jobs — every 32 x 32 tile (tr, tc), tr in {2 I, 2 I + 1}, tc >= tr, that srukf_gmw_fold_head_tile() does not give to the
@@ -1356,17 +1350,17 @@ int srukf_gmw_build_fold_list(int T, int Tp, short* out)
     }
     return cnt;
 }
-// the pair of the split form with the fold: A / Ut (mp rows) / krows = the operands k_syrk would have read (the permuted copy of the kept rows, U^T with permuted columns)
-void srukf_launch_gmw_split_fold(hipStream_t stA, hipStream_t stB, int n, int ld, double eps, double* G, void* pans, double* D, double* Sout, void* sync,
-                                 const void* list, int nlist, void* fs, int Tp, int krows, double* Wslab, double* Lslab, const double* A, const double* Ut, int mp)
+// the pair of the split form with the fold: list / nlist = the tile launch's grid (srukf_gmw_build_fold_list; g.tiles is not used), A / Ut (mp rows) / g.krows = the
+// operands k_syrk would have read (the permuted copy of the kept rows, U^T with permuted columns)
+void srukf_launch_gmw_split_fold(hipStream_t stA, hipStream_t stB, const GmwLaunch& gl, double* Wslab, double* Lslab, const GmwTile* list, int nlist,
+                                 const double* A, const double* Ut, int mp)
 {
-    const int T = ld / 64;
-    if (Tp <= 0 || Tp > T) Tp = T;
-    if (krows <= 0 || krows > ld) krows = ld;
+    const GmwLaunch g = gmw_normalised(gl);
+    const int T = g.ld / 64;
     const unsigned int total = (unsigned)(T + nlist);
-    hipLaunchKernelGGL(k_gmw_pivslab_persist, dim3(T), dim3(256), 0, stA, n, ld, T, Tp, G, (GmwPanel64*)pans, Sout, D, eps, (GmwSync*)sync, (FrameScalars*)fs, krows, Wslab, Lslab, total);
-    hipLaunchKernelGGL(k_gmw_split_gate, dim3(1), dim3(64), 0, stB, (GmwSync*)sync, (const FrameScalars*)fs, (unsigned)T);
-    if (nlist > 0) hipLaunchKernelGGL(k_gmw_tiles_fold, dim3(nlist), dim3(256), 0, stB, n, ld, T, G, (GmwSync*)sync, (const GmwTile*)list, (FrameScalars*)fs, Wslab, Lslab, total, A, Ut, mp, krows, srukf_gmw_fold_head_rows(Tp));
+    gmw_launch_pivslab(stA, g, Wslab, Lslab, total);
+    hipLaunchKernelGGL(k_gmw_split_gate, dim3(1), dim3(64), 0, stB, g.sync, (const FrameScalars*)g.fs, (unsigned)T);
+    if (nlist > 0) hipLaunchKernelGGL(k_gmw_tiles_fold, dim3(nlist), dim3(256), 0, stB, g.n, g.ld, T, g.G, g.sync, list, g.fs, Wslab, Lslab, total, A, Ut, mp, g.krows, srukf_gmw_fold_head_rows(g.Tp));
 }
 int srukf_gmw_head_rows(void) { return 64 * GMW_HEAD_ROWS; }
 int srukf_gmw_head_extra_diag(void) { return GMW_HEAD_EXTRA_DIAG; }

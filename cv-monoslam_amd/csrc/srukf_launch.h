@@ -1,0 +1,169 @@
+// srukf_launch.h — what the kernel files offer the host layer, declared ONCE: every srukf_launch_* launcher, the size / table / list helpers, the process-wide
+// switches of the kernel files.  Included by srukf_ctx.h (the callers) and, behind their own headers, by the eight files that define these functions (srukf_predict,
+// srukf_factor, srukf_gmw_persist, srukf_rank, srukf_mixed, srukf_augment, srukf_assoc, srukf_unique): linkage is C, so only the compiler can compare a declaration
+// with its definition, and it does so in the file that defines it.  A function of this kind is declared here and nowhere else (tests/test_host.py holds the tree to it).
+#pragma once
+#include "srukf_device.h"
+#include "srukf_rank.h"
+
+struct GmwPanel64;      // srukf_gmw_panel.h: the hand-off buffer of one 64-row panel
+struct GmwTile;         // srukf_gmw_persist.hip: one entry of a persistent launch's tile list (4 shorts)
+
+// ---- argument structs of the launchers whose lists nobody can read: plain aggregates, filled by name at the call site, unpacked into the kernel call ----
+
+// One blocked factorisation G (upper triangle, destroyed) -> factor rows in Sout, as every form of it is launched (persistent, split pair, one launch per panel).
+// pans / sync / tiles / ntiles / workers / relay: the plan's (GmwPlan); Tp: pivoted panels (<= 0: all ld / 64), krows: where the kept pivots end (<= 0: ld) — see
+// gmw_normalised; gate_limit > 0: behind the admission gate (k_gmw_gate) for that many tenants
+struct GmwLaunch {
+    int n, ld; double eps;
+    double* G; GmwPanel64* pans; double* D; double* Sout; GmwSync* sync;
+    const GmwTile* tiles; int ntiles, workers;
+    FrameScalars* fs;
+    int Tp, krows, gate_limit, relay;
+};
+inline GmwLaunch gmw_normalised(GmwLaunch g)
+{
+    const int T = g.ld / 64;
+    if (g.Tp <= 0 || g.Tp > T) g.Tp = T;
+    if (g.krows <= 0 || g.krows > g.ld) g.krows = g.ld;
+    return g;
+}
+// fused form of the persistent launch: the owners form their tiles of S0^T S0 - Ut0[u0:u1]^T Ut0[u0:u1] themselves (k_gmw_persist)
+struct GmwFused { const double* S0; const double* Ut0; int u0, u1; };
+
+// The riders of a k_syrk launch: the pending state update X += dX (dxp: slice partials or per-landmark shares; xr1: the robot mean after the motion step) and the
+// rank-aware replay's operands (ra.A != null: S / Ut are the permuted operands, the dropped diagonal is formed too).  Empty: the plain product
+struct SyrkRider { const double* dxp; double* X; RankArgs ra; const double* xr1; };
+
+// k_gain: U^T, the gains and the slice partials of the state update.  z_cur / m_cur: this frame's measurements and matches (null: the staged sequence's z_seq / m_seq);
+// Cm != null: the motion step's columns are committed here; P1 != null: the cross covariances are k_pxy2's (second K half, cut at split_b0); fmode: "fused tail" mode
+// (the robot rows are re-centred); next_pose (3 doubles, host) with odo_dev: the launch also stores the sequence's third pose
+struct GainLaunch {
+    KDims d; KWeights w;
+    double* Ut; const double* PxyR; const double* Si; const int* vis; const double* h;
+    const double* z_seq; const double* z_cur; const int* m_seq; const int* m_cur;
+    FrameScalars* fs; double* dxp; const double* Z; RankArgs ra;
+    const double* Cm; double* S; const double* P1; int split_b0; const double* DZp; double sqeps; const double* sigR;
+    bool fmode; const double* next_pose; double* odo_dev;
+};
+
+// k_rank_expand, the tail of a rank-aware refactorisation: factor rows Sp (permuted order) -> S and the permuted copy A, theta / null-direction checks.
+// do_traj: it ends a frame (trajectory row, frame counter); sigR != null: it prepares the next frame's table of robot poses; fuse: "fused tail" mode, it projects
+// the next frame into Z / DZ (k_rank_expand<2>) and then may round what it writes (f32round), export the step-wise frame's status (step_export) and clear the gain
+// fold's sync words (fold_sync); null_rel: what the null-direction check allows relative to G_aa
+struct RankExpandLaunch {
+    KDims d; KWeights w; srukf_params p;
+    int r;
+    const double* Sp; const double* D; const int* perm; const int* iperm; const double* gdiag; FrameScalars* fs; const double* X;
+    double* S; double* A; double* sigR; double* Z; double* DZ;
+    bool do_traj, fuse, f32round;
+    const StepExport* step_export; double null_rel; unsigned int* fold_sync; int fold_words;
+};
+
+extern "C" {
+// ---- srukf_predict.hip ----
+void srukf_launch_landmarks_cartesian(hipStream_t st, KDims d, const double* X, const double* S, double* xyz, double* cov);
+void srukf_launch_motion(hipStream_t st, KDims d, KWeights w, srukf_params p, double* X, double* S, double* sigR, double* Cmat, FrameScalars* fs, const double* odo_seq,
+                         const double* odo_pair, RankArgs ra);
+void srukf_launch_project_motion(hipStream_t st, KDims d, KWeights w, srukf_params p, double* X, double* S, double* sigR, double* Cm, double* Z, double* DZ, FrameScalars* fs,
+                                 RankArgs ra);
+void srukf_launch_project_table(hipStream_t st, KDims d, KWeights w, srukf_params p, double* X, double* S, double* sigR, double* Cm, double* Z, double* DZ, FrameScalars* fs,
+                                RankArgs ra, NullSkip ns);
+void srukf_launch_sigr_rows(hipStream_t st, KDims d, KWeights w, const double* X, const double* S, double* sigR, const FrameScalars* fs, const int* iperm, int rkeep);
+void srukf_launch_project(hipStream_t st, KDims d, KWeights w, srukf_params p, const double* X, const double* S, const double* sigR, double* Z, double* DZ, const FrameScalars* fs);
+void srukf_launch_meas_stats(hipStream_t st, KDims d, KWeights w, const double* X, const double* sigR, const double* Z, double* part, double* h, double* Si, int* vis, double* PxyR);
+int srukf_meas_part_doubles(int mp);
+void srukf_launch_gain(hipStream_t st, const GainLaunch& a);
+void srukf_launch_gain_b(hipStream_t st, KDims d, KWeights w, const GainArgs* tab, int B, int split_b0, double sqeps);
+int srukf_gain_part_doubles(int np);
+void srukf_launch_traj(hipStream_t st, KDims d, const double* X, const double* S, FrameScalars* fs, double* traj, int advance);
+void srukf_launch_block_cov(hipStream_t st, KDims d, const double* S, int off, int bs, double* out, const double* X);
+void srukf_launch_project_points(hipStream_t st, srukf_params p, int count, const double* feat6, const double* pos3, const double* psi, const double* err2, double* out);
+
+// ---- srukf_factor.hip ----
+void srukf_launch_pxy(hipStream_t st, KDims d, const double* DZ, const double* S, double* Ut, const int* tiles, int ntiles, KWeights w, MeasArgs ms);
+void srukf_launch_pxy2(hipStream_t st, KDims d, const double* DZp, const double* A, double* P0, double* P1, const int* tiles, int ntiles, int kr, KWeights w, MeasArgs ms, GainFold gf);
+int srukf_pxy2_build_tiles(int mp, int np, int kr, int* out);
+int srukf_pxy2_split_groups(void);
+void srukf_launch_syrk(hipStream_t st, KDims d, const double* S, const double* Ut, int ub, int ue, double* G, FrameScalars* fs, const int* tiles, int ntiles, const SyrkRider& rider);
+void srukf_launch_gmw_step64(hipStream_t st, int n, int ld, int j0, double eps, double* G, const GmwPanel64* cur, GmwPanel64* nxt, double* D, double* Sout, const FrameScalars* fs);
+int srukf_gmw_panel_bytes(void);
+void srukf_launch_gmw_pivslab_b(hipStream_t st, int n, int ld, int j0, double eps, const Step64Args* tab, int B, int flip, int sel);
+void srukf_launch_gmw_trail_b(hipStream_t st, int ld, int j0, const Step64Args* tab, int B, int rows, int sel, int form);
+int srukf_pxy2_b_per(int ntiles, int gx);
+void srukf_launch_pxy2_b(hipStream_t st, KDims d, const Pxy2Args* tab, int B, const int* tiles, int ntiles, int kr, KWeights w, int gx);
+void srukf_launch_syrk_b(hipStream_t st, KDims d, const SyrkArgs* tab, int B, const int* tiles, int ntiles, int krows, int ndx, int ngd);
+void srukf_launch_gmw_step64_b(hipStream_t st, int n, int ld, int j0, double eps, const Step64Args* tab, int B, int rows, int flip);
+void srukf_launch_gmw_check(hipStream_t st, int n, int ld, const double* D, const double* S, FrameScalars* fs, const double* X, int do_traj, double* Scopy);
+void srukf_set_exact_right_looking(int on);
+int srukf_get_exact_right_looking(void);
+void srukf_warm_exact_path(hipStream_t st, FrameScalars* fs);
+void srukf_launch_gmw_col(hipStream_t st, int n, int ld, int j, double eps, const double* G, double* Wf, double* D, unsigned long long* theta_bits, FrameScalars* fs, double* Sout);
+void srukf_launch_gmw_stats(hipStream_t st, int n, int ld, const double* G, FrameScalars* fs);
+
+// ---- srukf_gmw_persist.hip ----
+int srukf_gmw_sync_bytes(int T);
+int srukf_gmw_build_tiles(int T, int Tp, short* out);
+void srukf_gmw_set_pivot_relay(int v);
+int srukf_gmw_get_pivot_relay(void);
+int srukf_gmw_persist_workers(int T, int Tp, int max_workers);
+int srukf_gmw_register_form(int T, int Tp, int ntiles, int workers);
+// fused / head: null = every tile is read from G / no helper workgroups (head fold)
+void srukf_launch_gmw_persist(hipStream_t st, const GmwLaunch& g, const GmwFused* fused, const HeadArgs* head);
+void srukf_launch_syrk_own(hipStream_t st, int n, int ld, const double* S0, const double* Ut0, int u0, int u1, int krows, double* G, FrameScalars* fs, const GmwTile* tiles, int ntiles, int Tp);
+void srukf_launch_syrk_own_b(hipStream_t st, int n, int ld, const SyrkOwnArgs* tab, int B, int u0, int u1, int krows, const GmwTile* tiles, int ntiles, int Tp);
+// the split pair: stA = the filter's stream (pivot / slab launch), stB = its side stream (gate + tile launch); Wslab / Lslab: the slabs of every pivoted panel
+void srukf_launch_gmw_split(hipStream_t stA, hipStream_t stB, const GmwLaunch& g, double* Wslab, double* Lslab, int starve);
+void srukf_launch_gmw_split_alone(hipStream_t st, int which, const GmwLaunch& g, double* Wslab, double* Lslab);
+// ... whose tile launch forms tiles too: list / nlist = its grid (srukf_gmw_build_fold_list) in place of g.tiles, A / Ut (mp rows) = the operands k_syrk would have read
+void srukf_launch_gmw_split_fold(hipStream_t stA, hipStream_t stB, const GmwLaunch& g, double* Wslab, double* Lslab, const GmwTile* list, int nlist, const double* A, const double* Ut, int mp);
+void srukf_gmw_fold_head_override(int v);
+int srukf_gmw_fold_head_rows(int Tp);
+int srukf_gmw_fold_head_tile(int tr, int tc, int head_rows);
+int srukf_gmw_build_fold_list(int T, int Tp, short* out);
+int srukf_gmw_head_rows(void);
+int srukf_gmw_head_extra_diag(void);
+
+// ---- srukf_rank.hip ----
+void srukf_launch_rank_round(hipStream_t st, int ld, int r, double* A);
+void srukf_launch_row_energy(hipStream_t st, int n, int ld, const double* S, double* e);
+void srukf_launch_rank_diag(hipStream_t st, int n, int ld, const double* G, const int* perm, double* gdiag);
+void srukf_launch_rank_expand(hipStream_t st, const RankExpandLaunch& a);
+void srukf_launch_rank_expand_b(hipStream_t st, int n, int ld, int r, double eps, const ExpandArgs* tab, int B, double gamma, KDims d, KWeights w, srukf_params p);
+void srukf_launch_rank_canon(hipStream_t st, int n, int ld, int r, double sq, const int* perm, double* S);
+void srukf_launch_rank_shadow(hipStream_t st, int n, int ld, int r, const double* S, const int* perm, double* A);
+
+// ---- srukf_mixed.hip (tasks / tiles / planes: the lists and operand planes of srukf_mixed_build_tasks* and k_split_bf3, opaque to the host) ----
+int srukf_mixed_build_tasks_red(int np, int ue, int krows, int rows_lim, short* out_tasks, int* out_tiles, int* ntiles);
+int srukf_mixed_build_tasks(int np, int ue, short* out_tasks, int* out_tiles, int* ntiles);
+int srukf_mixed_krows(int r);
+size_t srukf_mixed_part_bytes(int ntasks);
+void srukf_launch_cvt_f32(hipStream_t st, size_t count, const double* src, float* dst);
+void srukf_launch_gain_dx(hipStream_t st, int n, int np, const double* dxp, double* X, const double* xr1);
+void srukf_launch_cvt_robot_cols(hipStream_t st, int n, int np, const double* S, float* S32);
+void srukf_launch_syrk32(hipStream_t st, int n, int np, int ue, const float* S32, const float* U32, const void* tasks, int ntasks, const void* tiles, int ntiles, double* part,
+                         double* G, FrameScalars* fs, int krows);
+void srukf_launch_split_bf3(hipStream_t st, int rows, int ld, int ktot, int koff, const double* src, void* planes, size_t plane_stride);
+void srukf_launch_syrk_bf3(hipStream_t st, int n, int np, int ue, int krows, int ktot, const void* planes, size_t plane_stride, const void* tasks, int ntasks, const void* tiles,
+                           int ntiles, double* part, double* G, FrameScalars* fs);
+
+// ---- srukf_augment.hip ----
+void srukf_launch_aug_map(hipStream_t st, srukf_params p, int dim, int ld, int K, int Na, double gamma, const double* X, const double* S, const double* uv, double* ang);
+void srukf_launch_aug_x(hipStream_t st, int dim, int K, int Na, double wm0, double wi, const double* X, const double* ang, const int* perm, double* mu_ang, double* Xn, int dimn, int ldn);
+void srukf_launch_aug_build(hipStream_t st, int dim, int ld, int K, int Na, double gamma, double wi_sr, const double* X, const double* S, const double* ang, double* A, int rows_p,
+                            int dimn, int ldn);
+void srukf_launch_gram(hipStream_t st, int rows_p, int ld, const double* A, double* G);
+
+// ---- srukf_assoc.hip, srukf_unique.hip ----
+void srukf_launch_warp_patch(hipStream_t st, KDims d, srukf_params p, const double* X, const double* xyz, const double* h, const double* appR, const double* appT,
+                             const double* appPx, const unsigned char* initPatch, const int* has_app, unsigned char* matchPatch);
+void srukf_launch_associate(hipStream_t st, KDims d, srukf_params p, const unsigned char* image, const double* h, const double* Si, const int* vis, const int* has_app,
+                            const unsigned char* matchPatch, double* z, int* matched, double* corr);
+int srukf_app_patch_stride(void);
+int srukf_app_tmpl_stride(void);
+void srukf_launch_associate_checked(hipStream_t st, KDims d, srukf_params p, double corr_threshold, double ratio, int exclusion, int subpixel, const unsigned char* image,
+                                    const double* h, const double* Si, const int* vis, const int* has_app, const unsigned char* matchPatch, double* z, int* matched, double* corr,
+                                    double* res, double* scores);
+int srukf_match_score_stride(void);
+int srukf_match_tmpl_stride(void);
+}  // extern "C"

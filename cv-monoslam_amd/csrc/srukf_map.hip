@@ -403,7 +403,7 @@ int srukf_delete_landmark(srukf_ctx* c, int id)
     if (srukf_dmalloc((void**)&d_map, sizeof(int) * nn) != hipSuccess) return map_change_fail(c, c2, SRUKF_ERR_NOMEM, "delete_landmark: out of device memory");
     hipMemcpy(d_map, map.data(), sizeof(int) * nn, hipMemcpyHostToDevice);
     launch_refactor_reset(c->stream, np, c->theta, c->fs, 1);
-    srukf_launch_syrk(c->stream, c->d, c->S, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, nullptr, c->X, RankArgs{}, nullptr);   // P = S^T S
+    srukf_launch_syrk(c->stream, c->d, c->S, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, SyrkRider{});   // P = S^T S
     launch_gather(c->stream, nn, ldn, c->X, c2->X, d_map);
     rc = map_change_factor(c, c2, nn, c->G, np, d_map, true);
     if (rc) { srukf_dfree(d_map); return map_change_fail(c, c2, rc, c2->err); }

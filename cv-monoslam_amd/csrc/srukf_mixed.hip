@@ -14,6 +14,7 @@
 // bound (SLAM.cpp:2204-2211).
 #include <hip/hip_runtime.h>
 #include "srukf_device.h"
+#include "srukf_launch.h"
 
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef float f4v __attribute__((ext_vector_type(4)));
@@ -357,10 +358,10 @@ void srukf_launch_cvt_robot_cols(hipStream_t st, int n, int np, const double* S,
     hipLaunchKernelGGL(k_cvt_robot_cols, dim3((n + 255) / 256), dim3(256), 0, st, n, np, S, S32);
 }
 void srukf_launch_syrk32(hipStream_t st, int n, int np, int ue, const float* S32, const float* U32, const void* tasks, int ntasks,
-                         const void* tiles, int ntiles, double* part, double* G, void* fs, int krows)
+                         const void* tiles, int ntiles, double* part, double* G, FrameScalars* fs, int krows)
 {
     hipLaunchKernelGGL(k_syrk32, dim3(ntasks), dim3(256), 0, st, np, ue, S32, U32, (const MxTask*)tasks, part, krows > 0 ? krows : np);
-    hipLaunchKernelGGL(k_syrk32_reduce, dim3(ntiles), dim3(256), 0, st, n, np, (const int2*)tiles, (const MxTask*)tasks, part, G, (FrameScalars*)fs);
+    hipLaunchKernelGGL(k_syrk32_reduce, dim3(ntiles), dim3(256), 0, st, n, np, (const int2*)tiles, (const MxTask*)tasks, part, G, fs);
 }
 // the bf16-piece form: operands as X^T planes (k_split_bf3), products by k_syrk_bf3, the same reduction
 void srukf_launch_split_bf3(hipStream_t st, int rows, int ld, int ktot, int koff, const double* src, void* planes, size_t plane_stride)
@@ -368,9 +369,9 @@ void srukf_launch_split_bf3(hipStream_t st, int rows, int ld, int ktot, int koff
     hipLaunchKernelGGL(k_split_bf3, dim3(ld / 64, (rows + 31) / 32), dim3(256), 0, st, rows, ld, ktot, koff, src, (unsigned short*)planes, plane_stride);
 }
 void srukf_launch_syrk_bf3(hipStream_t st, int n, int np, int ue, int krows, int ktot, const void* planes, size_t plane_stride, const void* tasks, int ntasks,
-                           const void* tiles, int ntiles, double* part, double* G, void* fs)
+                           const void* tiles, int ntiles, double* part, double* G, FrameScalars* fs)
 {
     hipLaunchKernelGGL(k_syrk_bf3, dim3(ntasks), dim3(256), 0, st, np, ktot, krows, ue, (const unsigned short*)planes, plane_stride, (const MxTask*)tasks, part);
-    hipLaunchKernelGGL(k_syrk32_reduce, dim3(ntiles), dim3(256), 0, st, n, np, (const int2*)tiles, (const MxTask*)tasks, part, G, (FrameScalars*)fs);
+    hipLaunchKernelGGL(k_syrk32_reduce, dim3(ntiles), dim3(256), 0, st, n, np, (const int2*)tiles, (const MxTask*)tasks, part, G, fs);
 }
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include "srukf_rank.h"
 #include "srukf_motion.h"
 #include "srukf_motion_reduce.h"
+#include "srukf_launch.h"
 
 // control from two odometry poses (SLAM.cpp:1444-1458): srukf_motion_control_a in srukf_device.h
 __device__ __forceinline__ void srukf_motion_control(const srukf_params& p, const double* o, double (&ut)[3], double (&mt)[3])
@@ -761,21 +762,19 @@ void srukf_launch_meas_stats(hipStream_t st, KDims d, KWeights w, const double* 
     hipLaunchKernelGGL(k_meas_final, dim3((d.N + 255) / 256), dim3(256), 0, st, d, w, X, sigR, Z, part, h, Si, vis, PxyR);
 }
 int srukf_meas_part_doubles(int mp) { return MEAS_SLICES * MEAS_NS * (mp / 2); }
-void srukf_launch_gain_b(hipStream_t st, KDims d, KWeights w, const void* tab, int B, int split_b0, double sqeps)
+void srukf_launch_gain_b(hipStream_t st, KDims d, KWeights w, const GainArgs* tab, int B, int split_b0, double sqeps)
 {
-    hipLaunchKernelGGL(k_gain_b, dim3(d.np / 64, GAIN_SLICES * B), dim3(256), 0, st, d, w, (const GainArgs*)tab, split_b0, sqeps);
+    hipLaunchKernelGGL(k_gain_b, dim3(d.np / 64, GAIN_SLICES * B), dim3(256), 0, st, d, w, tab, split_b0, sqeps);
 }
-void srukf_launch_gain(hipStream_t st, KDims d, KWeights w, double* Ut, const double* PxyR, const double* Si, const int* vis,
-                       const double* h, const double* z_seq, const double* z_cur, const int* m_seq, const int* m_cur,
-                       FrameScalars* fs, double* dxp, double* X, const double* Z, RankArgs ra, const double* Cm, double* S,
-                       const double* P1, int split_b0, const double* DZp, double sqeps, const double* sigR, int fmode, const double* next_pose, double* odo_dev)
+void srukf_launch_gain(hipStream_t st, const GainLaunch& a)
 {
+    const KDims& d = a.d; const KWeights& w = a.w;
     GainNextPose np3 = { { 0, 0, 0 }, nullptr };
-    if (next_pose && odo_dev) { np3.v[0] = next_pose[0]; np3.v[1] = next_pose[1]; np3.v[2] = next_pose[2]; np3.odo = odo_dev; }
-    hipLaunchKernelGGL(k_gain, dim3(d.np / 64, GAIN_SLICES), dim3(256), 0, st, d, w, Ut, PxyR, Si, vis, h, z_seq, z_cur, m_seq, m_cur, fs, dxp, ra, Cm, S,
-                       P1, split_b0, DZp, sqeps, sigR, Z, fmode, np3);
+    if (a.next_pose && a.odo_dev) { np3.v[0] = a.next_pose[0]; np3.v[1] = a.next_pose[1]; np3.v[2] = a.next_pose[2]; np3.odo = a.odo_dev; }
+    hipLaunchKernelGGL(k_gain, dim3(d.np / 64, GAIN_SLICES), dim3(256), 0, st, d, w, a.Ut, a.PxyR, a.Si, a.vis, a.h, a.z_seq, a.z_cur, a.m_seq, a.m_cur, a.fs, a.dxp, a.ra, a.Cm, a.S,
+                       a.P1, a.split_b0, a.DZp, a.sqeps, a.sigR, a.Z, a.fmode ? 1 : 0, np3);
     if (w.wc0 != w.wm0)
-        hipLaunchKernelGGL(k_gain_center, dim3(d.np / 256 + 1), dim3(256), 0, st, d, w, Ut, Z, Si, vis, h, z_seq, z_cur, m_seq, m_cur, fs, dxp);
+        hipLaunchKernelGGL(k_gain_center, dim3(d.np / 256 + 1), dim3(256), 0, st, d, w, a.Ut, a.Z, a.Si, a.vis, a.h, a.z_seq, a.z_cur, a.m_seq, a.m_cur, a.fs, a.dxp);
 }
 int srukf_gain_part_doubles(int np) { return GAIN_SLICES * np; }
 void srukf_launch_traj(hipStream_t st, KDims d, const double* X, const double* S, FrameScalars* fs, double* traj, int advance)

@@ -29,6 +29,7 @@
 #include "srukf_rank.h"
 #include "srukf_motion.h"
 #include "srukf_motion_reduce.h"
+#include "srukf_launch.h"
 
 // A[a][b] = S[perm[a]][perm[b]] for a < r (the kept rows in permuted column order), zero rows below
 __global__ __launch_bounds__(256) void k_rank_shadow(int n, int ld, int r, const double* __restrict__ S, const int* __restrict__ perm, double* __restrict__ A)
@@ -413,23 +414,23 @@ void srukf_launch_rank_diag(hipStream_t st, int n, int ld, const double* G, cons
 {
     hipLaunchKernelGGL(k_rank_diag, dim3((n + 255) / 256), dim3(256), 0, st, n, ld, G, perm, gdiag);
 }
-void srukf_launch_rank_expand(hipStream_t st, int n, int ld, int r, double eps, const double* Sp, const double* D, const int* perm, const int* iperm,
-                              const double* gdiag, void* fs, const double* X, int do_traj, double* S, double* A, double* sigR, double gamma,
-                              int fuse, KDims d, KWeights w, srukf_params p, double* Z, double* DZ, int f32, const StepExport* exp, double null_rel,
-                              unsigned int* fold_sync, int fold_words)
+void srukf_launch_rank_expand(hipStream_t st, const RankExpandLaunch& a)
 {
-    const StepExport ex = (exp && fuse) ? *exp : StepExport{};
+    const int n = a.d.n, ld = a.d.np, r = a.r, do_traj = a.do_traj ? 1 : 0;
+    const bool fuse = a.fuse;
+    const double eps = a.p.epsilon;
+    const StepExport ex = (a.step_export && fuse) ? *a.step_export : StepExport{};
     // fuse: "fused tail" mode (projection of the next frame: five more workgroups, the row in LDS)
     const int nchk = (n - r + SRUKF_RANK_COLS - 1) / SRUKF_RANK_COLS;
     const dim3 grid(n + 1 + nchk + (fuse ? 5 : 0));
-    if (fuse) hipLaunchKernelGGL(k_rank_expand<2>, grid, dim3(256), sizeof(double) * (size_t)ld, st, n, ld, r, eps, Sp, D, perm, iperm, gdiag, (FrameScalars*)fs, X, do_traj, S, A, sigR, gamma, d, w, p, Z, DZ, f32, ex, null_rel, fold_sync, fold_words);
-    else hipLaunchKernelGGL(k_rank_expand<0>, grid, dim3(256), 0, st, n, ld, r, eps, Sp, D, perm, iperm, gdiag, (FrameScalars*)fs, X, do_traj, S, A, sigR, gamma, d, w, p, Z, DZ, 0, StepExport{}, null_rel, fold_sync, fold_words);
+    if (fuse) hipLaunchKernelGGL(k_rank_expand<2>, grid, dim3(256), sizeof(double) * (size_t)ld, st, n, ld, r, eps, a.Sp, a.D, a.perm, a.iperm, a.gdiag, a.fs, a.X, do_traj, a.S, a.A, a.sigR, a.w.gamma, a.d, a.w, a.p, a.Z, a.DZ, a.f32round ? 1 : 0, ex, a.null_rel, a.fold_sync, a.fold_words);
+    else hipLaunchKernelGGL(k_rank_expand<0>, grid, dim3(256), 0, st, n, ld, r, eps, a.Sp, a.D, a.perm, a.iperm, a.gdiag, a.fs, a.X, do_traj, a.S, a.A, a.sigR, a.w.gamma, a.d, a.w, a.p, a.Z, a.DZ, 0, StepExport{}, a.null_rel, a.fold_sync, a.fold_words);
 }
-void srukf_launch_rank_expand_b(hipStream_t st, int n, int ld, int r, double eps, const void* tab, int B, double gamma, KDims d, KWeights w, srukf_params p)
+void srukf_launch_rank_expand_b(hipStream_t st, int n, int ld, int r, double eps, const ExpandArgs* tab, int B, double gamma, KDims d, KWeights w, srukf_params p)
 {
     const int nchk = (n - r + SRUKF_RANK_COLS - 1) / SRUKF_RANK_COLS;
     const int per = n + 1 + nchk + 5;
-    hipLaunchKernelGGL(k_rank_expand_b, dim3(per * B), dim3(256), sizeof(double) * (size_t)ld, st, n, ld, r, eps, (const ExpandArgs*)tab, per, gamma, d, w, p);
+    hipLaunchKernelGGL(k_rank_expand_b, dim3(per * B), dim3(256), sizeof(double) * (size_t)ld, st, n, ld, r, eps, tab, per, gamma, d, w, p);
 }
 // The structurally null rows of S made what the reference's clamp leaves there and every rank-aware frame tail rewrites: sqrt(EPSILON) e_k (a factor from a path that
 // factors every pivot — NEED_REORDER, the map operations — holds rounding noise / sqrt(EPSILON) beside that diagonal).  One workgroup per dropped row.

@@ -260,17 +260,21 @@ int gate_limit(const srukf_ctx* c) { return c->gmw_shared == 1 ? c->shared_tenan
 // ff.fused_tail(): this launch also projects the next frame's sigma points (k_rank_expand<2>)
 static void rank_expand(srukf_ctx* c, const RefactorRequest& rq, FrameForm ff)
 {
-    const int n = c->d.n, np = c->d.np;
+    const int np = c->d.np;
     const bool frame_tail = rq.kind == RefactorRequest::FRAME_TAIL, table = ff.robot_table, fuse = ff.fused_tail();
     const bool f32s = c->storage != SRUKF_STORAGE_F64;            // (the mixed mode stores floats as well: the launches behind the tail round, as for fp32 storage without "fused tail" mode)
     const bool f32fuse = storage_f32_like(c) && fuse && table && frame_tail;      // fp32 storage in "fused tail" mode: the launch rounds what it writes (no k_quantize / k_rank_round / k_traj behind it)
     const bool f32 = f32s && !f32fuse;
     const bool tt = table && frame_tail && !f32;
     const bool exports = c->step_export.dst && tt && fuse;         // step-wise fast path: this launch is the frame's last and hands status + robot view to the host itself
-    srukf_launch_rank_expand(c->stream, n, np, c->red_r, c->p.epsilon, c->G, c->D, c->red_perm, c->red_iperm, c->gdiag, c->fs, c->X, (frame_tail && !f32) ? 1 : 0, c->S, c->shadowA,
-                             tt ? c->sigR : nullptr, c->w.gamma, (tt && fuse) ? 1 : 0, c->d, c->w, c->p, c->Z, c->DZ, f32fuse ? 1 : 0, exports ? &c->step_export : nullptr,
-                             c->storage == SRUKF_STORAGE_F32_MIXED ? 1e-6 * c->dbg.mixed_null_ppm : 0.0,
-                             (tt && fuse) ? c->fold_sync : nullptr, c->fold_sync ? 4 * (c->d.mp / 64) * (c->d.np / 64) : 0);
+    srukf_launch_rank_expand(c->stream, RankExpandLaunch{
+        .d = c->d, .w = c->w, .p = c->p, .r = c->red_r,
+        .Sp = c->G, .D = c->D, .perm = c->red_perm, .iperm = c->red_iperm, .gdiag = c->gdiag, .fs = c->fs, .X = c->X,
+        .S = c->S, .A = c->shadowA, .sigR = tt ? c->sigR : nullptr, .Z = c->Z, .DZ = c->DZ,
+        .do_traj = frame_tail && !f32, .fuse = tt && fuse, .f32round = f32fuse,
+        .step_export = exports ? &c->step_export : nullptr,
+        .null_rel = c->storage == SRUKF_STORAGE_F32_MIXED ? 1e-6 * c->dbg.mixed_null_ppm : 0.0,
+        .fold_sync = (tt && fuse) ? c->fold_sync : nullptr, .fold_words = c->fold_sync ? 4 * (c->d.mp / 64) * (c->d.np / 64) : 0 });
     c->step_export_attached = exports;
     if (f32) {
         quantize_state(c);
@@ -386,14 +390,14 @@ RefactorPlan refactor_form(const srukf_ctx* c, const RefactorRequest& rq)
 // k_syrk on the permuted operands (shadow copy, U^T with permuted columns) for one tile list, into Gp; spare workgroups: the pending state update, the dropped diagonal
 static void syrk_permuted(srukf_ctx* c, FrameForm ff, const int* tiles, int ntiles)
 {
-    srukf_launch_syrk(c->stream, c->d, c->shadowA, c->Utp, 0, c->d.mp, c->Wf, c->fs, tiles, ntiles, dx_src(c), c->X, tail_rank_args(c, ff), take_xr1(c));
+    srukf_launch_syrk(c->stream, c->d, c->shadowA, c->Utp, 0, c->d.mp, c->Wf, c->fs, tiles, ntiles, SyrkRider{ dx_src(c), c->X, tail_rank_args(c, ff), take_xr1(c) });
     c->dx_pending = false;
 }
 
 // RF_OWNERS_FOLD: the owners form their tiles of S^T S - U U^T themselves, in permuted order from the shadow copy (no full k_syrk, no permutation pass)
 static void refactor_owners_fold(srukf_ctx* c, const RefactorRequest& rq, const RefactorPlan& plan, FrameForm ff)
 {
-    const KDims& d = c->d; const int np = d.np, n = d.n;
+    const KDims& d = c->d; const int n = d.n;
     const double rr = c->red_r, hr = srukf_gmw_head_rows();
     const double head_flop = 2.0 * hr * n * (hr / 2.0 + d.mp) + 2.0 * (n - rr) * (rr + d.mp), head_byte = 8.0 * ((hr + d.mp) * n + (n - rr) * (rr + d.mp));
     // head fold (head_fold_ok): the head tiles, the pending X += dX and the dropped diagonal are helper workgroups of the persistent launch, not a k_syrk launch in front
@@ -415,8 +419,8 @@ static void refactor_owners_fold(srukf_ctx* c, const RefactorRequest& rq, const 
             ha.nhelp = hj.total();                              // one helper workgroup per job, behind the pivot and the workers in dispatch order
             c->dx_pending = false;
         }
-        srukf_launch_gmw_persist_head(c->stream, n, np, c->p.epsilon, c->Wf, c->gplan_red.pans, c->D, c->G, c->gplan_red.sync, c->gplan_red.tiles, c->gplan_red.ntiles,
-                                      c->gplan_red.workers, c->fs, c->shadowA, c->Utp, 0, d.mp, c->red_Tp, kept_rows16(c), gate_limit(c), plan.head_fold ? &ha : nullptr, c->gplan_red.relay);
+        const GmwFused fused = { c->shadowA, c->Utp, 0, d.mp };
+        srukf_launch_gmw_persist(c->stream, gmw_launch(c, c->gplan_red, c->Wf, c->G, c->red_Tp, kept_rows16(c)), &fused, plan.head_fold ? &ha : nullptr);
     }
     ProfScope ps(c, KC_RANK_EXPAND, 0, 8.0 * 2.5 * (double)n * n);
     rank_expand(c, rq, ff);
@@ -487,7 +491,7 @@ static double product_state_order(srukf_ctx* c, const RefactorRequest& rq, const
     } else {
         ProfScope ps(c, KC_SYRK, syrk_flop * head_frac, syrk_byte * head_frac);
         srukf_launch_syrk(c->stream, d, c->S, c->Ut, ub, ue, c->G, c->fs, fused ? c->syrk_head_tiles : c->syrk_tiles,
-                          fused ? c->n_syrk_head_tiles : c->n_syrk_tiles, dx_src(c), c->X, RankArgs{}, take_xr1(c));
+                          fused ? c->n_syrk_head_tiles : c->n_syrk_tiles, SyrkRider{ dx_src(c), c->X, RankArgs{}, take_xr1(c) });
         c->dx_pending = false;
     }
     if (rq.kind != RefactorRequest::FRAME_TAIL) hipMemcpyAsync(c->Gbak, c->G, sizeof(double) * (size_t)np * np, hipMemcpyDeviceToDevice, c->stream);
@@ -532,16 +536,11 @@ static void refactor_full_rank(srukf_ctx* c, const RefactorRequest& rq, const Re
         double fl = 0.0, by = 0.0;
         for (int j0 = -64; j0 + 64 < np; j0 += 64) { fl += panel_flop(j0); by += panel_byte(j0); }
         ProfScope ps(c, KC_GMW_PERSIST, fl + syrk_flop * (1.0 - head_frac), by + syrk_byte * (1.0 - head_frac));
-        if (fused) srukf_launch_gmw_persist(c->stream, n, np, c->p.epsilon, c->G, c->gplan.pans, c->D, c->Wf, c->gplan.sync, c->gplan.tiles, c->gplan.ntiles,
-                                            c->gplan.workers, c->fs, c->S, c->Ut, rq.ub, rq.ue, 0, 0, gate_limit(c), c->gplan.relay);
+        const GmwFused operands = { c->S, c->Ut, rq.ub, rq.ue };
+        if (fused) srukf_launch_gmw_persist(c->stream, gmw_launch(c, c->gplan, c->G, c->Wf, 0, 0), &operands, nullptr);
         else launch_gmw_fast(c, c->G, c->S, GMW_ALL_PANELS);
-    } else {
-        int pb = 0;
-        for (int j0 = -64; j0 + 64 < np; j0 += 64, pb ^= 1) {
-            ProfScope ps(c, KC_GMW_TRAIL, panel_flop(j0), panel_byte(j0));
-            srukf_launch_gmw_step64(c->stream, n, np, j0, c->p.epsilon, c->G, c->pan[pb ^ 1], c->pan[pb], c->D, c->S, c->fs);
-        }
-    }
+    } else
+        gmw_per_panel(c->stream, gmw_launch(c, c->gplan, c->G, c->S, 0, 0), c->pan, [&](int j0) { return ProfScope(c, KC_GMW_TRAIL, panel_flop(j0), panel_byte(j0)); });
     quantize_state(c);
     {
         ProfScope ps(c, KC_GMW_CHECK, 0, 8.0 * (double)n * n / 2);      // (frame tail: the check kernel also records the trajectory row and advances the frame counter)
@@ -578,17 +577,21 @@ int exact_repeat_begin(srukf_ctx* c, int frame, double* traj_base)
 
 // The blocked factorisation on an arbitrary matrix buffer: Gbuf (upper triangle, destroyed) -> upper-triangular factor rows in Sout (whose lower triangle must already
 // be zero).  which: every panel (the full plan), or the leading red_Tp panels of a permuted matrix (the rank-aware plan; split fold: its tile launch forms tiles too)
+GmwLaunch gmw_launch(const srukf_ctx* c, const GmwPlan& gp, double* Gbuf, double* Sout, int Tp, int krows)
+{
+    return GmwLaunch{ .n = c->d.n, .ld = c->d.np, .eps = c->p.epsilon, .G = Gbuf, .pans = gp.pans, .D = c->D, .Sout = Sout, .sync = gp.sync, .tiles = gp.tiles, .ntiles = gp.ntiles,
+                      .workers = gp.workers, .fs = c->fs, .Tp = Tp, .krows = krows, .gate_limit = gate_limit(c), .relay = gp.relay };
+}
+
 void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, GmwPanels which)
 {
-    const int np = c->d.np, n = c->d.n;
+    const int np = c->d.np;
     const bool reduced = which != GMW_ALL_PANELS, fold = which == GMW_KEPT_PANELS_SPLIT_FOLD;
     const GmwPlan& gp = reduced ? c->gplan_red : c->gplan;
     const int Tp = reduced ? c->red_Tp : np / 64;
     const int krows = reduced ? kept_rows16(c) : 0;              // where the kept pivots end — the last pivoted panel is not factored beyond them
+    GmwLaunch g = gmw_launch(c, gp, Gbuf, Sout, Tp, krows);
     if (plan_persists(c, gp)) {
-        // srukf_debug_starve_workers (tests only): launch without workers, as if the GPU were taken — the pivot's bounded wait
-        // expires, the frame is flagged and repeated on the exact path, and the context falls back to one launch per panel
-        const int workers = c->debug_starve == 1 ? 0 : gp.workers;   // (2: only a split-form pair is starved — the tier below it then runs undisturbed)
         if (split_form(c, gp, true)) {                         // (srukf_debug_starve_workers: the pair without its tile launch)
             // the tile launch depends on what produced Gbuf, not on the pivot / slab launch: fork before, join after (in a capture: two parallel branches)
             if (c->dbg.split_record) hipMemcpyAsync(c->Gbak, Gbuf, sizeof(double) * (size_t)np * np, hipMemcpyDeviceToDevice, c->stream);
@@ -596,21 +599,20 @@ void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, GmwPanels which)
             hipStreamWaitEvent(c->side, c->ev_fork, 0);
             if (fold) {
                 c->split_fold_seqs++;
-                srukf_launch_gmw_split_fold(c->stream, c->side, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, c->split_fold_list, c->n_split_fold, c->fs, Tp, krows,
-                                            c->gsW, c->gsL, c->shadowA, c->Utp, c->d.mp);
+                srukf_launch_gmw_split_fold(c->stream, c->side, g, c->gsW, c->gsL, c->split_fold_list, c->n_split_fold, c->shadowA, c->Utp, c->d.mp);
             } else
-                srukf_launch_gmw_split(c->stream, c->side, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, gp.tiles, gp.ntiles, c->fs, Tp, krows, c->gsW, c->gsL, c->debug_starve ? 1 : 0);
+                srukf_launch_gmw_split(c->stream, c->side, g, c->gsW, c->gsL, c->debug_starve ? 1 : 0);
             hipEventRecord(c->ev_join, c->side);
             hipStreamWaitEvent(c->stream, c->ev_join, 0);
             return;
         }
-        srukf_launch_gmw_persist(c->stream, n, np, c->p.epsilon, Gbuf, gp.pans, c->D, Sout, gp.sync, gp.tiles, gp.ntiles, workers, c->fs, nullptr, nullptr, 0, 0, Tp, krows, gate_limit(c), gp.relay);
+        // srukf_debug_starve_workers (tests only): launch without workers, as if the GPU were taken — the pivot's bounded wait
+        // expires, the frame is flagged and repeated on the exact path, and the context falls back to one launch per panel
+        if (c->debug_starve == 1) g.workers = 0;               // (2: only a split-form pair is starved — the tier below it then runs undisturbed)
+        srukf_launch_gmw_persist(c->stream, g, nullptr, nullptr);
         return;
     }
-    // one launch per panel; rank-aware form: the step after the last pivoted panel still runs (it writes that panel's S rows)
-    int pb = 0;
-    for (int j0 = -64; j0 + 64 < np && j0 + 64 <= 64 * Tp; j0 += 64, pb ^= 1)
-        srukf_launch_gmw_step64(c->stream, n, np, j0, c->p.epsilon, Gbuf, c->pan[pb ^ 1], c->pan[pb], c->D, Sout, c->fs);
+    gmw_per_panel(c->stream, g, c->pan);
 }
 
 // The exact path: n + 1 launches behind one call (srukf_launch_gmw_col submits the right-looking sequence on its first call).  Launch-bound: 13.6 ms per flagged frame at
@@ -648,13 +650,13 @@ int refactor_reorder(srukf_ctx* c, int ub, int ue)
     const size_t bytes = sizeof(double) * (size_t)np * np;
     if (!c->Sdis) { if (srukf_dmalloc((void**)&c->Sdis, bytes) != hipSuccess) { c->err = "out of device memory (NEED_REORDER buffer)"; return SRUKF_ERR_NOMEM; } }
     launch_refactor_reset(c->stream, np, c->theta, c->fs, 1);
-    srukf_launch_syrk(c->stream, d, c->S, c->Ut, ub, ue, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, dx_src(c), c->X, RankArgs{}, take_xr1(c));
+    srukf_launch_syrk(c->stream, d, c->S, c->Ut, ub, ue, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, SyrkRider{ dx_src(c), c->X, RankArgs{}, take_xr1(c) });
     c->dx_pending = false;
     for (int stage = 0; stage < 2; stage++) {
         double* out = stage == 0 ? c->Sdis : c->S;
         if (stage == 1) {
             launch_refactor_reset(c->stream, np, c->theta, c->fs, 1);
-            srukf_launch_syrk(c->stream, d, c->Sdis, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, nullptr, c->X, RankArgs{}, nullptr);
+            srukf_launch_syrk(c->stream, d, c->Sdis, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, SyrkRider{});
         }
         for (int slow = 0; slow < 2; slow++) {
             launch_set_frame(c->stream, c->fs, 0, 1);
@@ -701,10 +703,13 @@ void seq_gain_only(srukf_ctx* c, const double* z_dev, const int* m_dev, FrameFor
     const KDims& d = c->d;
     const bool fused_motion = ff.fused_motion(), table = ff.pxy2(), fmode = ff.fused_tail();
     ProfScope ps(c, KC_GAIN, 8.0 * d.n * 2 * d.N, 8.0 * 2.0 * d.n * 2 * d.N);
-    srukf_launch_gain(c->stream, d, c->w, c->Ut, c->PxyR, c->Si, c->vis, c->h, c->z_seq, z_dev, c->m_seq, m_dev, c->fs, c->dxp, c->X, c->Z, rank_args(c),
-                      fused_motion ? c->Cmat : nullptr, c->S, table ? c->P1 : nullptr, c->pxy2_split_b0, c->DZ,
-                      (fmode && storage_f32_like(c)) ? (double)(float)sqrt(c->p.epsilon) : sqrt(c->p.epsilon),   // (the null rows of S as they are stored)
-                      c->sigR, fmode ? 1 : 0, c->next_pose_pending ? c->next_odo + 3 : nullptr, c->odo_step);
+    srukf_launch_gain(c->stream, GainLaunch{
+        .d = d, .w = c->w, .Ut = c->Ut, .PxyR = c->PxyR, .Si = c->Si, .vis = c->vis, .h = c->h,
+        .z_seq = c->z_seq, .z_cur = z_dev, .m_seq = c->m_seq, .m_cur = m_dev,
+        .fs = c->fs, .dxp = c->dxp, .Z = c->Z, .ra = rank_args(c),
+        .Cm = fused_motion ? c->Cmat : nullptr, .S = c->S, .P1 = table ? c->P1 : nullptr, .split_b0 = c->pxy2_split_b0, .DZp = c->DZ,
+        .sqeps = (fmode && storage_f32_like(c)) ? (double)(float)sqrt(c->p.epsilon) : sqrt(c->p.epsilon),   // (the null rows of S as they are stored)
+        .sigR = c->sigR, .fmode = fmode, .next_pose = c->next_pose_pending ? c->next_odo + 3 : nullptr, .odo_dev = c->odo_step });
     c->next_pose_pending = false;
     c->dx_pending = true; c->dx_lm = false;           // applied by the next k_syrk launch (seq_refactor)
 }

@@ -138,7 +138,7 @@ int srukf_debug_split_replay(srukf_ctx* c, int which, int reps)
         HIPCHK(c, hipMemcpyAsync((char*)gp.sync + offsetof(GmwSync, epoch), &prev, sizeof prev, hipMemcpyHostToDevice, c->stream));
         if (which == 1) HIPCHK(c, hipMemcpyAsync(c->Wf, c->Gbak, sizeof(double) * (size_t)np * np, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));              // (&prev is pageable)
-        srukf_launch_gmw_split_alone(c->stream, which, n, np, c->p.epsilon, c->Wf, gp.pans, c->D, c->G, gp.sync, gp.tiles, gp.ntiles, c->fs, Tp, reduced ? kept_rows16(c) : 0, c->gsW, c->gsL);
+        srukf_launch_gmw_split_alone(c->stream, which, gmw_launch(c, gp, c->Wf, c->G, Tp, reduced ? kept_rows16(c) : 0), c->gsW, c->gsL);
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     HIPCHK(c, hipGetLastError());

@@ -22,6 +22,7 @@
 //          upper (y - 1) and lower neighbours
 // One workgroup of 256 threads per landmark, static LDS only (~20 KB), no atomics, nothing between workgroups.
 #include "srukf_device.h"
+#include "srukf_launch.h"
 
 #define HP_INIT 10             // SLAM.cpp:41-42
 #define HP_MATCH 8             // SLAM.cpp:43-44

@@ -8,7 +8,7 @@ int main()
     const int n = 1204, ld = 1216;
     std::vector<double> h((size_t)ld * ld);
     for (int r = 0; r < ld; r++) for (int c = 0; c < ld; c++) h[(size_t)r * ld + c] = (r == c) ? 2.0 + 0.001 * r : 0.3 / (1 + abs(r - c));
-    double *G, *D, *S; void* pan[2];
+    double *G, *D, *S; GmwPanel64* pan[2];
     hipMalloc(&G, sizeof(double) * ld * ld); hipMalloc(&S, sizeof(double) * ld * ld); hipMalloc(&D, sizeof(double) * ld);
     hipMalloc(&pan[0], sizeof(GmwPanel64)); hipMalloc(&pan[1], sizeof(GmwPanel64));
     hipStream_t st; hipStreamCreate(&st);

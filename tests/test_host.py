@@ -187,3 +187,73 @@ def test_cpp_hosts_are_built_and_print_their_usage(exe):
     assert os.path.exists(path), "run __graft_entry__.build() first"
     r = subprocess.run([path], capture_output=True, text=True, timeout=60)
     assert r.returncode == 2 and "usage" in r.stderr
+
+
+# ---- the seam between the kernel files and the host layer: one declaration per function, in srukf_launch.h ----
+KERNEL_FILES = ["srukf_predict", "srukf_factor", "srukf_gmw_persist", "srukf_rank", "srukf_mixed", "srukf_augment", "srukf_assoc", "srukf_unique"]
+_TYPE = r"\b(?:void|int|size_t|double|float|bool|unsigned|long|char|short)\b[\s\*]*"
+
+
+def _code(path):
+    """Source text without comments and string contents (the extern "C" marker survives as extern C)."""
+    txt = open(path).read().replace('extern "C"', "extern C")
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+    return re.sub(r'"(?:\\.|[^"\\\n])*"', '""', txt)
+
+
+def _close(txt, i, op, cl):
+    """Index behind the bracket that closes txt[i] == op."""
+    depth = 0
+    for j in range(i, len(txt)):
+        depth += (txt[j] == op) - (txt[j] == cl)
+        if depth == 0:
+            return j + 1
+    raise AssertionError("unbalanced " + op)
+
+
+def _signatures(txt):
+    """(name, has_body) of every srukf_* function declared or defined in txt (a return type in front tells them from calls)."""
+    out = []
+    for m in re.finditer(_TYPE + r"(srukf_\w+)\s*\(", txt):
+        end = _close(txt, m.end() - 1, "(", ")")
+        nxt = txt[end:end + 40].lstrip()[:1]
+        if nxt in ("{", ";"):
+            out.append((m.group(1), nxt == "{"))
+    return out
+
+
+def _c_linkage_definitions(txt):
+    names = []
+    for m in re.finditer(r"extern C\s*", txt):
+        if txt[m.end()] == "{":
+            region = txt[m.end():_close(txt, m.end(), "{", "}")]
+        else:
+            region = txt[m.end():_close(txt, txt.index("{", m.end()), "{", "}")]
+        names += [n for n, body in _signatures(region) if body]
+    return names
+
+
+def test_every_launcher_is_declared_once_in_srukf_launch_h():
+    csrc = os.path.join(ROOT, "cv-monoslam_amd", "csrc")
+    public = set(_header_functions())
+    offered = set()
+    for f in KERNEL_FILES:
+        txt = _code(os.path.join(csrc, f + ".hip"))
+        assert re.search(r'^#include "srukf_launch\.h"', open(os.path.join(csrc, f + ".hip")).read(), flags=re.M), f"{f}.hip does not include srukf_launch.h"
+        defs = _c_linkage_definitions(txt)
+        assert len(defs) == len(set(defs)), f
+        assert not offered & set(defs), f"defined twice: {sorted(offered & set(defs))}"
+        offered |= set(defs) - public
+    assert len(offered) >= 70 and "srukf_launch_gmw_persist" in offered and "srukf_gmw_build_fold_list" in offered     # the scan found the launchers and the helpers
+    declared = [n for n, body in _signatures(_code(os.path.join(csrc, "srukf_launch.h"))) if not body]
+    for n in sorted(offered):
+        assert declared.count(n) == 1, f"srukf_launch.h declares {n} {declared.count(n)} times"
+    assert sorted(set(declared)) == sorted(offered), f"declared but not defined by a kernel file: {sorted(set(declared) - offered)}"
+    # ... and nowhere else: no other file re-declares one of them
+    for d in (csrc, os.path.join(ROOT, "scripts", "mb")):
+        for f in sorted(os.listdir(d)):
+            if f == "srukf_launch.h" or not f.endswith((".h", ".hip", ".cpp", ".hpp", ".c")):
+                continue
+            again = [n for n, body in _signatures(_code(os.path.join(d, f))) if not body and n in offered]
+            assert not again, f"{f} declares {again} itself: include srukf_launch.h"
