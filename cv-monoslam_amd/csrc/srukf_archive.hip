@@ -6,22 +6,21 @@
 //                         the record's Cartesian mean
 //     k_warp_patch        (srukf_assoc.hip, unchanged) on the archive's arrays: the 17 x 17 template of every visible record under the current pose
 //     k_archive_search    one workgroup per visible record: the frame bytes of the gate's bounding box in LDS, the normalised cross correlation of every gated
-//                         candidate from exact integer sums, the first maximum in row-major order
+//                         candidate from exact integer sums, the first maximum in row-major order.  The gate (Si^T Si, its inverse, the distance) and the
+//                         first-maximum reduction are the association's (srukf_patch.h); the window rule, the score and the byte staging are this file's
 // The robot pose and its 4 x 4 covariance are what srukf_get_robot returns at that moment (that call is made); every buffer written is the archive's own, and the
 // staging area is the archive's own pinned block (the context's may hold a statistics mirror the next srukf_predict_measurement reads).
 // This file is built with -ffp-contract=off: tests/np_archive.py restates its arithmetic.
 #include "srukf_ctx.h"
 #include "srukf_crtrig.h"
+#include "srukf_patch.h"
 #include <cmath>
 using namespace srukf_impl;
 
 #define AR_NA 12                       // record 6 | robot 4 | pixel noise 2
 #define AR_L (2 * AR_NA + 1)
-#define AR_HP 8                        // HP_MATCH: half width of the 17 x 17 template
-#define AR_TW (2 * AR_HP + 1)
-#define AR_NP (AR_TW * AR_TW)
 #define AR_CAP_MAX 40
-#define AR_RG_W (2 * AR_CAP_MAX + 1 + 2 * AR_HP)      // 97: bytes per side every candidate of the widest window can touch
+#define AR_RG_W (2 * AR_CAP_MAX + 1 + 2 * PT_MATCH_HALF)      // 97: bytes per side every candidate of the widest window can touch
 #define AR_RG_STRIDE 100                              // LDS row stride of the staged region (whole dwords per row)
 
 // upper Cholesky factor by the rule of k_lm_record: d_j = max(eps, P_jj - sum_{m<j} S_mj^2), S_jj = sqrt(d_j), S_ji = (P_ji - sum_{m<j} S_mj S_mi) / S_jj, sums in ascending m
@@ -107,7 +106,7 @@ __global__ __launch_bounds__(64) void k_archive_predict(srukf_params p, KWeights
 // One workgroup per record.  Window: half_x = clamp(ceil(sqrt(chi2 Pi00)), 8, cap), half_y from Pi11 (Pi = Si^T Si): the bounding box of the gate ellipse; candidate c
 // (row-major) has the centre (i, j) = ((int)h_x - half_x + c % wx, (int)h_y - half_y + c / wx) and is skipped (cc = 0) when its 17 x 17 patch leaves the image or
 // e^T Pi^-1 e >= chi2, e = (i - h_x, j - h_y).  With v the frame bytes under the template and t the template bytes, all sums exact integers:
-//   A = NP sum(vt) - sum(v) sum(t),  B = NP sum(v^2) - sum(v)^2,  C = NP sum(t^2) - sum(t)^2,  cc = (B == 0 || C == 0) ? 0 : (double)A / sqrt((double)B (double)C)
+//   (NP = PT_TMPL_BYTES)  A = NP sum(vt) - sum(v) sum(t),  B = NP sum(v^2) - sum(v)^2,  C = NP sum(t^2) - sum(t)^2,  cc = (B == 0 || C == 0) ? 0 : (double)A / sqrt((double)B (double)C)
 // The staged bytes stay bytes (<= 97 x 97 in rows of 100): neighbouring lanes take neighbouring centres, so a wave's byte reads of one template position fall into
 // <= 17 consecutive dwords of a row (and the rows of a wave that spans two window rows lie 25 banks apart); the template is read as one broadcast dword per position.
 __global__ __launch_bounds__(256) void k_archive_search(srukf_params p, int cap, double thr, double chi2, const unsigned char* __restrict__ image,
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(256) void k_archive_search(srukf_params p, int cap,
                                                         double* __restrict__ corr)
 {
     __shared__ unsigned char rg[AR_RG_W * AR_RG_STRIDE];
-    __shared__ int tm[AR_NP];
+    __shared__ int tm[PT_TMPL_BYTES];
     __shared__ int tsum[2];
     __shared__ double bestv[256];
     __shared__ int besti[256];
@@ -124,65 +123,53 @@ __global__ __launch_bounds__(256) void k_archive_search(srukf_params p, int cap,
     const int W = (int)p.image_w, H = (int)p.image_h;
     if (!vis[k]) { if (tid == 0) { matched[k] = 0; corr[k] = 0.0; z[2 * k] = 0.0; z[2 * k + 1] = 0.0; } return; }
     const double px = h[2 * k], py = h[2 * k + 1];
-    const double s00 = Si[4 * k], s01 = Si[4 * k + 1], s10 = Si[4 * k + 2], s11 = Si[4 * k + 3];
-    const double p00 = s00 * s00 + s10 * s10, p01 = s00 * s01 + s10 * s11, p10 = s01 * s00 + s11 * s10, p11 = s01 * s01 + s11 * s11;   // Si^T Si
-    double det = p00 * p11 - p01 * p10, i00 = 0, i01 = 0, i10 = 0, i11 = 0;                             // 2 x 2 closed-form inverse, as k_associate
-    if (det != 0.0) { det = 1.0 / det; i00 = p11 * det; i01 = -p01 * det; i10 = -p10 * det; i11 = p00 * det; }
-    const double capd = (double)min(max(cap, AR_HP), AR_CAP_MAX);
-    const int half_x = (int)fmin(fmax(ceil(sqrt(chi2 * p00)), (double)AR_HP), capd);                    // (a NaN ends as 8: fmax / fmin return the other operand)
-    const int half_y = (int)fmin(fmax(ceil(sqrt(chi2 * p11)), (double)AR_HP), capd);
+    const PatchGate g = patch_gate(Si + 4 * k);
+    const double capd = (double)min(max(cap, PT_MATCH_HALF), AR_CAP_MAX);
+    const int half_x = (int)fmin(fmax(ceil(sqrt(chi2 * g.p00)), (double)PT_MATCH_HALF), capd);   // (a NaN ends as 8: fmax / fmin return the other operand)
+    const int half_y = (int)fmin(fmax(ceil(sqrt(chi2 * g.p11)), (double)PT_MATCH_HALF), capd);
     const int wx = 2 * half_x + 1, wy = 2 * half_y + 1;
     const int x0 = (int)px - half_x, y0 = (int)py - half_y;
-    const int rw = wx + 2 * AR_HP, rh = wy + 2 * AR_HP, rx0 = x0 - AR_HP, ry0 = y0 - AR_HP;              // rw, rh <= 97
+    const int rw = wx + 2 * PT_MATCH_HALF, rh = wy + 2 * PT_MATCH_HALF, rx0 = x0 - PT_MATCH_HALF, ry0 = y0 - PT_MATCH_HALF;   // rw, rh <= 97
     for (int e = tid; e < rw * rh; e += 256) {
         const int ry = e / rw, rx = e % rw, yy = ry0 + ry, xx = rx0 + rx;
         rg[ry * AR_RG_STRIDE + rx] = (xx >= 0 && xx < W && yy >= 0 && yy < H) ? image[(size_t)yy * W + xx] : (unsigned char)0;
     }
     const unsigned char* mp = tmpl + (size_t)k * tmpl_stride;
-    for (int e = tid; e < AR_NP; e += 256) tm[e] = mp[e];
+    for (int e = tid; e < PT_TMPL_BYTES; e += 256) tm[e] = mp[e];
     __syncthreads();
     if (tid < 64) {                                            // sum(t), sum(t^2): one wave, integer adds (any order gives the same sums)
         int a = 0, b = 0;
-        for (int e = tid; e < AR_NP; e += 64) { const int t = tm[e]; a += t; b += t * t; }
+        for (int e = tid; e < PT_TMPL_BYTES; e += 64) { const int t = tm[e]; a += t; b += t * t; }
         for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
         if (tid == 0) { tsum[0] = a; tsum[1] = b; }
     }
     __syncthreads();
     const long long St = tsum[0], Stt = tsum[1];
-    const long long C = AR_NP * Stt - St * St;
-    double bv = -2.0; int bi = 0x7fffffff;
+    const long long C = PT_TMPL_BYTES * Stt - St * St;
+    double bv = -2.0; int bi = PT_NO_CAND;
     for (int c = tid; c < wx * wy; c += 256) {
         const int cy = c / wx, cx = c % wx, j = y0 + cy, i = x0 + cx;
         double cc = 0.0;
-        if (i >= AR_HP && i <= W - AR_HP - 1 && j >= AR_HP && j <= H - AR_HP - 1) {
+        if (i >= PT_MATCH_HALF && i <= W - PT_MATCH_HALF - 1 && j >= PT_MATCH_HALF && j <= H - PT_MATCH_HALF - 1) {
             const double ex = i - px, ey = j - py;
-            const double pii = (ex * i00 + ey * i10) * ex + (ex * i01 + ey * i11) * ey;
-            if (pii < chi2) {
+            if (patch_gate_dist(g, ex, ey) < chi2) {
                 const unsigned char* roi = rg + cy * AR_RG_STRIDE + cx;        // image(j - 8 .., i - 8 ..)
-                int sv = 0, svv = 0, svt = 0;                                  // <= 289 * 255^2 < 2^31
-                for (int r = 0; r < AR_TW; r++) {
+                int sv = 0, svv = 0, svt = 0;                                  // <= PT_TMPL_BYTES * 255^2 < 2^31
+                for (int r = 0; r < PT_TMPL_W; r++) {
 #pragma unroll
-                    for (int cl = 0; cl < AR_TW; cl++) {
+                    for (int cl = 0; cl < PT_TMPL_W; cl++) {
                         const int v = roi[r * AR_RG_STRIDE + cl];
-                        sv += v; svv += v * v; svt += v * tm[r * AR_TW + cl];
+                        sv += v; svv += v * v; svt += v * tm[r * PT_TMPL_W + cl];
                     }
                 }
-                const long long A = (long long)AR_NP * svt - (long long)sv * St;
-                const long long B = (long long)AR_NP * svv - (long long)sv * sv;
+                const long long A = (long long)PT_TMPL_BYTES * svt - (long long)sv * St;
+                const long long B = (long long)PT_TMPL_BYTES * svv - (long long)sv * sv;
                 cc = (B == 0 || C == 0) ? 0.0 : (double)A / sqrt((double)B * (double)C);
             }
         }
         if (cc > bv) { bv = cc; bi = c; }                      // a thread's candidates come in increasing index: its first maximum
     }
-    bestv[tid] = bv; besti[tid] = bi;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) {
-            const double ov = bestv[tid + st]; const int oi = besti[tid + st];
-            if (ov > bestv[tid] || (ov == bestv[tid] && oi < besti[tid])) { bestv[tid] = ov; besti[tid] = oi; }
-        }
-        __syncthreads();
-    }
+    block_first_max(bv, bi, bestv, besti);
     if (tid == 0) {
         const double mx = bestv[0];
         const int c = besti[0];
@@ -229,7 +216,7 @@ int srukf_archive_set(srukf_ctx* c, int L, const double* X6, const double* S66, 
     archive_free(c->archive, c->stream);
     if (L == 0) return SRUKF_OK;
     ArchiveState& a = c->archive;
-    const size_t ps = srukf_app_patch_stride(), ts = srukf_app_tmpl_stride(), n = (size_t)L, od = ar_out_doubles(L);
+    const size_t ps = PT_PATCH_STRIDE, ts = PT_TMPL_STRIDE, n = (size_t)L, od = ar_out_doubles(L);
     hipError_t e = srukf_dmalloc_on(&a.X6, sizeof(double) * 6 * n, c->stream);
     if (e == hipSuccess) e = srukf_dmalloc_on(&a.S66, sizeof(double) * 36 * n, c->stream);
     if (e == hipSuccess) e = srukf_dmalloc_on(&a.R, sizeof(double) * 9 * n, c->stream);
@@ -247,7 +234,7 @@ int srukf_archive_set(srukf_ctx* c, int L, const double* X6, const double* S66, 
     if (e == hipSuccess) e = hipMemcpyAsync(a.t, t, sizeof(double) * 3 * n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(a.px, px, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.patch, 0, ps * n, c->stream);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(a.patch, ps, patches, 441, 441, n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(a.patch, ps, patches, PT_PATCH_BYTES, PT_PATCH_BYTES, n, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.tmpl, 0, ts * n, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);         // (pageable host memory)
     if (e != hipSuccess) { archive_free(a, c->stream); c->err = std::string("archive_set: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
@@ -257,12 +244,12 @@ int srukf_archive_set(srukf_ctx* c, int L, const double* X6, const double* S66, 
 
 int srukf_archive_count(srukf_ctx* c) { return c ? c->archive.L : SRUKF_ERR_BAD_ARG; }
 
-int srukf_archive_get_template(srukf_ctx* c, int j, unsigned char out[289])
+int srukf_archive_get_template(srukf_ctx* c, int j, unsigned char out[PT_TMPL_BYTES])
 {
     if (!c || !out || j < 0 || j >= c->archive.L) return SRUKF_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, c->archive.tmpl + (size_t)j * srukf_app_tmpl_stride(), 289, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->archive.tmpl + (size_t)j * PT_TMPL_STRIDE, PT_TMPL_BYTES, hipMemcpyDeviceToHost));
     return SRUKF_OK;
 }
 
@@ -285,7 +272,7 @@ int srukf_archive_search(srukf_ctx* c, const unsigned char* gray, const srukf_ar
     HIPCHK(c, hipMemcpyAsync(a.rob, hrob, sizeof(double) * 20, hipMemcpyHostToDevice, c->stream));
     double* dh = a.out; double* dSi = dh + 2 * (size_t)L; double* dz = dSi + 4 * (size_t)L; double* dcorr = dz + 2 * (size_t)L; double* dxyz = dcorr + L;
     int* dvis = (int*)(dxyz + 3 * (size_t)L); int* dm = dvis + L;
-    HIPCHK(c, hipMemsetAsync(a.tmpl, 0, (size_t)L * srukf_app_tmpl_stride(), c->stream));               // a template depends on this call's inputs only
+    HIPCHK(c, hipMemsetAsync(a.tmpl, 0, (size_t)L * PT_TMPL_STRIDE, c->stream));  // a template depends on this call's inputs only
     KWeights w; host_weights(AR_NA, c->p, w);
     {
         ProfScope ps(c, KC_ARCHIVE_PREDICT, 0, 8.0 * 62 * L);
@@ -293,14 +280,14 @@ int srukf_archive_search(srukf_ctx* c, const unsigned char* gray, const srukf_ar
     }
     KDims ad = {}; ad.N = L; ad.n = 4;                                                                  // k_warp_patch reads d.N and X[n - 4 .. n - 1]: the archive's pose
     {
-        ProfScope ps(c, KC_ARCHIVE_WARP, 0, (441.0 + 289.0) * L);
+        ProfScope ps(c, KC_ARCHIVE_WARP, 0, (double)(PT_PATCH_BYTES + PT_TMPL_BYTES) * L);
         srukf_launch_warp_patch(c->stream, ad, c->p, a.rob, dxyz, dh, a.R, a.t, a.px, a.patch, dvis, a.tmpl);
     }
     {
         const double side = 2.0 * prm.half_cap + 1.0;
-        ProfScope ps(c, KC_ARCHIVE_SEARCH, 0, ((side + 16.0) * (side + 16.0) + 289.0) * L);
+        ProfScope ps(c, KC_ARCHIVE_SEARCH, 0, ((side + 2.0 * PT_MATCH_HALF) * (side + 2.0 * PT_MATCH_HALF) + PT_TMPL_BYTES) * L);
         hipLaunchKernelGGL(k_archive_search, dim3(L), dim3(256), 0, c->stream, c->p, prm.half_cap, prm.corr_threshold, prm.chi2, c->d_image, dh, dSi, dvis, a.tmpl,
-                           srukf_app_tmpl_stride(), dz, dm, dcorr);
+                           PT_TMPL_STRIDE, dz, dm, dcorr);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(a.hst, a.out, sizeof(double) * od, hipMemcpyDeviceToHost, c->stream));

@@ -12,16 +12,12 @@
 // k_associate scans the chi-square gated window around the predicted pixel for the best normalised
 // cross correlation.  matchPatch persists from frame to frame: pixels whose warp leaves the init
 // patch keep their previous value, as in the reference (the Mat is only zeroed at creation).
+// The record's sizes and the search itself (template statistics, gate, window, staging, candidate
+// score, first maximum) are srukf_patch.h's: k_associate_checked (srukf_unique.hip) runs the same front.
 #include "srukf_device.h"
 #include "srukf_crtrig.h"
 #include "srukf_launch.h"
-
-#define HP_INIT 10             // SLAM.cpp:41-42
-#define HP_MATCH 8             // SLAM.cpp:43-44
-#define PATCH_W (2 * HP_INIT + 1)
-#define TMPL_W (2 * HP_MATCH + 1)
-#define APP_PATCH_STRIDE 448   // bytes per landmark in the initPatch array (441 used)
-#define APP_TMPL_STRIDE 320    // bytes per landmark in the matchPatch array (289 used)
+#include "srukf_patch.h"
 
 // Everything below feeds floor / ceil / a truncating uchar cast (wrapPatch 1884-1900): this file is compiled with
 // -ffp-contract=off and every expression keeps the reference's association, operation for operation, so that the
@@ -93,12 +89,13 @@ __device__ void dev_inv4(const double a[16], double out[16])
     for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) out[4 * r + c] = m[r][4 + c];
 }
 
-// k_warp_patch: wrapPatch for every landmark.  One workgroup (320 threads, 289 used) per landmark: thread 0 builds the
+// k_warp_patch: wrapPatch for every landmark.  One workgroup (five waves, one thread per template pixel) per landmark: thread 0 builds the
 // homography H = K (R - r n^T / d) K^-1 and the template centre, then thread (i, j) warps its pixel.
-__global__ __launch_bounds__(320) void k_warp_patch(KDims d, srukf_params p, const double* __restrict__ X, const double* __restrict__ xyz,
-                                                    const double* __restrict__ h, const double* __restrict__ appR, const double* __restrict__ appT,
-                                                    const double* __restrict__ appPx, const unsigned char* __restrict__ initPatch,
-                                                    const int* __restrict__ has_app, unsigned char* __restrict__ matchPatch)
+constexpr int WARP_THREADS = 5 * 64;       // a thread count (five waves cover the template's pixels), not the template stride
+__global__ __launch_bounds__(WARP_THREADS) void k_warp_patch(KDims d, srukf_params p, const double* __restrict__ X, const double* __restrict__ xyz,
+                                                             const double* __restrict__ h, const double* __restrict__ appR, const double* __restrict__ appT,
+                                                             const double* __restrict__ appPx, const unsigned char* __restrict__ initPatch,
+                                                             const int* __restrict__ has_app, unsigned char* __restrict__ matchPatch)
 {
     __shared__ double sh[12];          // H[9], uv[2]
     const int k = blockIdx.x;
@@ -160,9 +157,9 @@ __global__ __launch_bounds__(320) void k_warp_patch(KDims d, srukf_params p, con
     }
     __syncthreads();
     const int t = threadIdx.x;
-    if (t >= TMPL_W * TMPL_W) return;
-    const int i = t / TMPL_W, j = t % TMPL_W;
-    const double ax = sh[9] - HP_MATCH + i, ay = sh[10] - HP_MATCH + j;                                 // 1869-1870
+    if (t >= PT_TMPL_W * PT_TMPL_W) return;
+    const int i = t / PT_TMPL_W, j = t % PT_TMPL_W;
+    const double ax = sh[9] - PT_MATCH_HALF + i, ay = sh[10] - PT_MATCH_HALF + j;                                 // 1869-1870
     double bx, by;
     dev_undistort(p, ax, ay, bx, by);                                                                   // 1871
     double w0 = sh[0] * bx + sh[1] * by + sh[2] * 1, w1 = sh[3] * bx + sh[4] * by + sh[5] * 1;         // 1874
@@ -170,102 +167,42 @@ __global__ __launch_bounds__(320) void k_warp_patch(KDims d, srukf_params p, con
     w0 /= w2; w1 /= w2;                                                                                 // 1875
     double cx1, cy1;
     dev_distort(p, w0, w1, cx1, cy1);                                                                   // 1879
-    cx1 -= (ipx - HP_INIT - 1);                                                                         // 1881
-    cy1 -= (ipy - HP_INIT - 1);                                                                         // 1882
+    cx1 -= (ipx - PT_INIT_HALF - 1);                                                                         // 1881
+    cy1 -= (ipy - PT_INIT_HALF - 1);                                                                         // 1882
     const int lx = (int)floor(cx1), ly = (int)floor(cy1), rx = (int)ceil(cx1), ry = (int)ceil(cy1);     // 1884-1887
-    if (lx >= 0 && rx < 2 * HP_INIT && ly >= 0 && ry < 2 * HP_INIT) {                                   // 1889
+    if (lx >= 0 && rx < 2 * PT_INIT_HALF && ly >= 0 && ry < 2 * PT_INIT_HALF) {                                   // 1889
         const double rate_lx = rx - cx1, rate_ly = ry - cy1, rate_rx = 1.0 - rate_lx, rate_ry = 1.0 - rate_ly;
-        const unsigned char* ip = initPatch + (size_t)k * APP_PATCH_STRIDE;
-        const unsigned char ll = ip[lx * PATCH_W + ly], lr = ip[lx * PATCH_W + ry];                     // at<uchar>(row = x index, col = y index)
-        const unsigned char rl = ip[rx * PATCH_W + ly], rr = ip[rx * PATCH_W + ry];
-        matchPatch[(size_t)k * APP_TMPL_STRIDE + i * TMPL_W + j] =
+        const unsigned char* ip = initPatch + (size_t)k * PT_PATCH_STRIDE;
+        const unsigned char ll = ip[lx * PT_PATCH_W + ly], lr = ip[lx * PT_PATCH_W + ry];                     // at<uchar>(row = x index, col = y index)
+        const unsigned char rl = ip[rx * PT_PATCH_W + ly], rr = ip[rx * PT_PATCH_W + ry];
+        matchPatch[(size_t)k * PT_TMPL_STRIDE + i * PT_TMPL_W + j] =
             (unsigned char)(ll * rate_lx * rate_ly + lr * rate_lx * rate_ry + rl * rate_rx * rate_ly + rr * rate_rx * rate_ry);   // 1899-1900
     }
 }
 
-// k_associate: dataAssociation for every visible landmark.  One workgroup per landmark: the template minus its mean
-// and its norm are staged in LDS; every thread takes candidate centres of the (2 half_y + 1) x (2 half_x + 1) window
-// (<= 21 x 21), gates them with the Mahalanobis distance under Si^T Si and correlates; the block keeps the FIRST
-// maximum in row-major order (cv::minMaxLoc).  Out: z (matchLocation), matched (isMatching), corr (maxVal).
+// k_associate: dataAssociation for every visible landmark.  One workgroup per landmark runs the matching front of srukf_patch.h (match_front: the template minus
+// its mean and its norm in LDS, the candidate centres of the (2 half_y + 1) x (2 half_x + 1) window (<= 21 x 21) gated with the Mahalanobis distance under Si^T Si
+// and correlated) and keeps the FIRST maximum in row-major order (cv::minMaxLoc), nothing else.  Out: z (matchLocation), matched (isMatching), corr (maxVal).
 __global__ __launch_bounds__(256) void k_associate(KDims d, srukf_params p, const unsigned char* __restrict__ image,
                                                    const double* __restrict__ h, const double* __restrict__ Si, const int* __restrict__ vis,
                                                    const int* __restrict__ has_app, const unsigned char* __restrict__ matchPatch,
                                                    double* __restrict__ z, int* __restrict__ matched, double* __restrict__ corr)
 {
-    __shared__ double tm[TMPL_W * TMPL_W];
+    __shared__ double tm[PT_TMPL_BYTES];
     __shared__ double red[8];
     __shared__ double bestv[256];
     __shared__ int besti[256];
+    __shared__ double rg[PT_REGION_W * PT_REGION_W];
     const int k = blockIdx.x, tid = threadIdx.x;
-    const int W = p.image_w, H = p.image_h, NP = TMPL_W * TMPL_W;
     if (!vis[k] || !has_app[k]) { if (tid == 0) { matched[k] = 0; corr[k] = 0.0; z[2 * k] = 0.0; z[2 * k + 1] = 0.0; } return; }   // 1946
-    // template statistics (calculateCrossCorrelation, 3151-3161): cv::mean, subtract, cv::norm
-    const unsigned char* mp = matchPatch + (size_t)k * APP_TMPL_STRIDE;
-    double s[1] = { 0.0 };
-    for (int e = tid; e < NP; e += 256) s[0] += mp[e];
-    block_sum<1>(s, red);
-    const double a2 = s[0] / NP;
-    double q[1] = { 0.0 };
-    for (int e = tid; e < NP; e += 256) { const double v = mp[e] - a2; tm[e] = v; q[0] += v * v; }
-    block_sum<1>(q, red);
-    const double std2 = sqrt(q[0]);
-    __syncthreads();
-    const double px = h[2 * k], py = h[2 * k + 1];
-    const double s00 = Si[4 * k], s01 = Si[4 * k + 1], s10 = Si[4 * k + 2], s11 = Si[4 * k + 3];
-    const double p00 = s00 * s00 + s10 * s10, p01 = s00 * s01 + s10 * s11, p10 = s01 * s00 + s11 * s10, p11 = s01 * s01 + s11 * s11;   // Si^T Si, 1951
-    double det = p00 * p11 - p01 * p10, i00 = 0, i01 = 0, i10 = 0, i11 = 0;                             // cv 2x2 closed-form inverse
-    if (det != 0.0) { det = 1.0 / det; i00 = p11 * det; i01 = -p01 * det; i10 = -p10 * det; i11 = p00 * det; }
-    int half_x = (int)ceil(2 * s00), half_y = (int)ceil(2 * s11);                                       // 1953-1954
-    half_x = min(HP_INIT, max(HP_MATCH, half_x)); half_y = min(HP_INIT, max(HP_MATCH, half_y));         // 1955-1956
-    const int wx = 2 * half_x + 1, wy = 2 * half_y + 1;
-    const int x0 = (int)px - half_x, y0 = (int)py - half_y;
-    // The pixels every candidate of this landmark can touch — the window plus the template's half width on every side, <= 37 x 37 — go to LDS once (as doubles: what the sums
-    // take); the candidates' two passes over their 17 x 17 patch then read LDS instead of issuing 578 single-byte global loads each.  Same values, same order of the sums.
-    // Pixels outside the image are staged as 0: a candidate whose patch would touch them is skipped by the border test below.
-    constexpr int RG_W = 2 * HP_INIT + 1 + 2 * HP_MATCH;       // 37
-    __shared__ double rg[RG_W * RG_W];
-    const int rw = wx + 2 * HP_MATCH, rh = wy + 2 * HP_MATCH, rx0 = x0 - HP_MATCH, ry0 = y0 - HP_MATCH;
-    for (int e = tid; e < rw * rh; e += 256) {
-        const int yy = ry0 + e / rw, xx = rx0 + e % rw;
-        rg[(e / rw) * RG_W + e % rw] = (xx >= 0 && xx < W && yy >= 0 && yy < H) ? (double)image[(size_t)yy * W + xx] : 0.0;
-    }
-    __syncthreads();
-    double bv = -1.0; int bi = 0x7fffffff;
-    for (int c = tid; c < wx * wy; c += 256) {
-        const int j = y0 + c / wx, i = x0 + c % wx;                                                     // row-major index of `correlation`
-        double cc = 0.0;
-        if (!(i < HP_MATCH || i > W - HP_MATCH - 1) && !(j < HP_MATCH || j > H - HP_MATCH - 1)) {       // 1962, 1969
-            const double ex = i - px, ey = j - py;
-            const double pii = (ex * i00 + ey * i10) * ex + (ex * i01 + ey * i11) * ey;                 // 1975
-            if (pii < 5.99146454710798) {                                                               // 1977
-                const double* roi = rg + (j - y0) * RG_W + (i - x0);                                    // 1979: image(j - HP_MATCH .., i - HP_MATCH ..) = rg(j - y0 .., i - x0 ..)
-                double s1 = 0.0;
-                for (int r = 0; r < TMPL_W; r++) for (int cl = 0; cl < TMPL_W; cl++) s1 += roi[r * RG_W + cl];
-                const double a1 = s1 / NP;
-                double q1 = 0.0, dot = 0.0;
-                for (int r = 0; r < TMPL_W; r++) for (int cl = 0; cl < TMPL_W; cl++) { const double v1 = roi[r * RG_W + cl] - a1; q1 += v1 * v1; dot += v1 * tm[r * TMPL_W + cl]; }
-                const double std1 = sqrt(q1);
-                cc = (std1 == 0.0 || std2 == 0.0) ? 0.0 : dot / std1 / std2;                            // 3163-3166
-            }
-        }
-        if (cc > bv) { bv = cc; bi = c; }                       // candidates of one thread come in increasing index: first maximum kept
-    }
-    bestv[tid] = bv; besti[tid] = bi;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) {
-            const double ov = bestv[tid + st]; const int oi = besti[tid + st];
-            if (ov > bestv[tid] || (ov == bestv[tid] && oi < besti[tid])) { bestv[tid] = ov; besti[tid] = oi; }
-        }
-        __syncthreads();
-    }
+    const MatchWindow w = match_front(k, p, image, h, Si, matchPatch, tm, red, rg, bestv, besti, [](int, double) {});
     if (tid == 0) {
         const double maxVal = bestv[0];
         const int c = besti[0];
         corr[k] = maxVal;
         if (maxVal > 0.8) {                                                                             // 1989
-            z[2 * k] = (c % wx) - half_x + px;                                                          // 1991-1992
-            z[2 * k + 1] = (c / wx) - half_y + py;
+            z[2 * k] = (c % w.wx) - w.half_x + w.px;                                                    // 1991-1992
+            z[2 * k + 1] = (c / w.wx) - w.half_y + w.py;
             matched[k] = 1;
         } else { z[2 * k] = 0.0; z[2 * k + 1] = 0.0; matched[k] = 0; }
     }
@@ -276,13 +213,11 @@ void srukf_launch_warp_patch(hipStream_t st, KDims d, srukf_params p, const doub
                              const double* appR, const double* appT, const double* appPx, const unsigned char* initPatch,
                              const int* has_app, unsigned char* matchPatch)
 {
-    hipLaunchKernelGGL(k_warp_patch, dim3(d.N), dim3(320), 0, st, d, p, X, xyz, h, appR, appT, appPx, initPatch, has_app, matchPatch);
+    hipLaunchKernelGGL(k_warp_patch, dim3(d.N), dim3(WARP_THREADS), 0, st, d, p, X, xyz, h, appR, appT, appPx, initPatch, has_app, matchPatch);
 }
 void srukf_launch_associate(hipStream_t st, KDims d, srukf_params p, const unsigned char* image, const double* h, const double* Si,
                             const int* vis, const int* has_app, const unsigned char* matchPatch, double* z, int* matched, double* corr)
 {
     hipLaunchKernelGGL(k_associate, dim3(d.N), dim3(256), 0, st, d, p, image, h, Si, vis, has_app, matchPatch, z, matched, corr);
 }
-int srukf_app_patch_stride(void) { return APP_PATCH_STRIDE; }
-int srukf_app_tmpl_stride(void) { return APP_TMPL_STRIDE; }
 }  // extern "C"

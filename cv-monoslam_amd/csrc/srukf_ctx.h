@@ -10,6 +10,7 @@
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search)
 //   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip)
+//   srukf_patch.h     (through srukf_launch.h) the appearance record's sizes, the checked association's buffer layouts, the search kernels' shared front
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
 #pragma once
 #include <hip/hip_runtime.h>
@@ -215,7 +216,7 @@ struct srukf_map_scope : srukf_life {
     // what the overlay is drawn from: h | Si | z (8N doubles) | matched (N ints), the per-landmark records
     double* ov_in = nullptr; void* ov_rec = nullptr;
     // srukf_associate_checked (srukf_unique.hip), allocated on its first call: match_res = z | corr | corr2 | z2 | matched, flags (7N doubles, exported in one piece),
-    // match_scores = every landmark's score map (448 doubles each: map | wx wy x0 y0).  match_valid: the maps are the last checked call's (srukf_get_match_scores);
+    // match_scores = every landmark's score map (PT_SCORE_STRIDE doubles each: map | wx wy x0 y0).  match_valid: the maps are the last checked call's (srukf_get_match_scores);
     // a map change and srukf_reset drop both buffers (match_drop)
     double *match_res = nullptr, *match_scores = nullptr; bool match_valid = false;
     RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
@@ -390,7 +391,8 @@ void launch_overlay(hipStream_t st, int W, int H, int N, const double* h, const 
                     const unsigned char* bgr /* NULL: gray three times */, const unsigned char* gray, unsigned char* out);
 
 // ---- loop points (srukf_loop.hip) ----
-#define SRUKF_LM_RECORD_DOUBLES 113                              // k_lm_record's staging block: X6 | S66 | R | t | px | has_app | 448 patch bytes
+// k_lm_record's staging block: X6 | S66 | R | t | px | has_app, then the patch at its stride (zero-filled behind its bytes)
+constexpr int LM_REC_DOUBLES = 6 + 36 + 9 + 3 + 2 + 1, LM_REC_PATCH_DOUBLES = PT_PATCH_STRIDE / 8, SRUKF_LM_RECORD_DOUBLES = LM_REC_DOUBLES + LM_REC_PATCH_DOUBLES;
 void launch_lm_record(hipStream_t st, const double* P66, const double* X, int k, double eps, const unsigned char* app_patch, const double* appR,
                       const double* appT, const double* appPx, const int* has_app, double* out);
 void launch_lm_insert(hipStream_t st, const double* S, int ld, const double* X, int p6, int L, const double* blk, double* S2, double* X2, int n2, int ld2);

@@ -312,15 +312,15 @@ __global__ __launch_bounds__(256) void k_det_select(DetArgs a, srukf_params p, D
 
 // integrateFeaturesInformation's appearance fields (SLAM.cpp:918-926) for landmarks first .. first + K - 1: initPatch = the 21 x 21 window at
 // cvRound(uv) (round half to even), initRotation = Rwc of the current heading (getTransferMatrix 1031-1037; correctly rounded sin / cos, as the
-// warp reads its own pose), initTrans = the robot x, y, z (834-836), matchPatch zeroed, has_app = 1.  One workgroup per landmark.
-__global__ __launch_bounds__(448) void k_capture_patch(const unsigned char* __restrict__ img, int W, int first, const double* __restrict__ uv,
+// warp reads its own pose), initTrans = the robot x, y, z (834-836), matchPatch zeroed, has_app = 1.  One workgroup per landmark, one thread per byte of a patch record.
+__global__ __launch_bounds__(PT_PATCH_STRIDE) void k_capture_patch(const unsigned char* __restrict__ img, int W, int first, const double* __restrict__ uv,
                                                        const double* __restrict__ X, int n, unsigned char* __restrict__ app_patch, int patch_stride,
                                                        unsigned char* __restrict__ app_tmpl, int tmpl_stride, double* __restrict__ appR,
                                                        double* __restrict__ appT, double* __restrict__ appPx, int* __restrict__ has_app)
 {
     const int q = blockIdx.x, k = first + q, t = threadIdx.x;
     const int u = (int)rint(uv[2 * q]), v = (int)rint(uv[2 * q + 1]);
-    if (t < 441) app_patch[(size_t)k * patch_stride + t] = img[(size_t)(v - 10 + t / 21) * W + (u - 10 + t % 21)];
+    if (t < PT_PATCH_BYTES) app_patch[(size_t)k * patch_stride + t] = img[(size_t)(v - PT_INIT_HALF + t / PT_PATCH_W) * W + (u - PT_INIT_HALF + t % PT_PATCH_W)];
     if (t < tmpl_stride) app_tmpl[(size_t)k * tmpl_stride + t] = 0;
     if (t == 0) {
         double sn, cs;
@@ -347,8 +347,8 @@ void det_scratch_free(DetScratch& s, hipStream_t st)
 void launch_capture_patch(hipStream_t st, const unsigned char* img, int W, int first, int K, const double* uv, const double* X, int n,
                           unsigned char* app_patch, unsigned char* app_tmpl, double* appR, double* appT, double* appPx, int* has_app)
 {
-    hipLaunchKernelGGL(k_capture_patch, dim3(K), dim3(448), 0, st, img, W, first, uv, X, n, app_patch, srukf_app_patch_stride(), app_tmpl,
-                       srukf_app_tmpl_stride(), appR, appT, appPx, has_app);
+    hipLaunchKernelGGL(k_capture_patch, dim3(K), dim3(PT_PATCH_STRIDE), 0, st, img, W, first, uv, X, n, app_patch, PT_PATCH_STRIDE, app_tmpl,
+                       PT_TMPL_STRIDE, appR, appT, appPx, has_app);
 }
 
 int ensure_image(srukf_ctx* c)

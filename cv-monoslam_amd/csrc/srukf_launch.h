@@ -5,6 +5,7 @@
 #pragma once
 #include "srukf_device.h"
 #include "srukf_rank.h"
+#include "srukf_patch.h"       // the appearance record's sizes, MatchArgs
 
 struct GmwPanel64;      // srukf_gmw_panel.h: the hand-off buffer of one 64-row panel
 struct GmwTile;         // srukf_gmw_persist.hip: one entry of a persistent launch's tile list (4 shorts)
@@ -159,11 +160,7 @@ void srukf_launch_warp_patch(hipStream_t st, KDims d, srukf_params p, const doub
                              const double* appPx, const unsigned char* initPatch, const int* has_app, unsigned char* matchPatch);
 void srukf_launch_associate(hipStream_t st, KDims d, srukf_params p, const unsigned char* image, const double* h, const double* Si, const int* vis, const int* has_app,
                             const unsigned char* matchPatch, double* z, int* matched, double* corr);
-int srukf_app_patch_stride(void);
-int srukf_app_tmpl_stride(void);
-void srukf_launch_associate_checked(hipStream_t st, KDims d, srukf_params p, double corr_threshold, double ratio, int exclusion, int subpixel, const unsigned char* image,
-                                    const double* h, const double* Si, const int* vis, const int* has_app, const unsigned char* matchPatch, double* z, int* matched, double* corr,
-                                    double* res, double* scores);
-int srukf_match_score_stride(void);
-int srukf_match_tmpl_stride(void);
+// res / scores: the packed result block and the score buffer (match_res, PT_SCORE_*: srukf_patch.h)
+void srukf_launch_associate_checked(hipStream_t st, KDims d, srukf_params p, MatchArgs ma, const unsigned char* image, const double* h, const double* Si, const int* vis,
+                                    const int* has_app, const unsigned char* matchPatch, double* z, int* matched, double* corr, double* res, double* scores);
 }  // extern "C"

@@ -7,9 +7,6 @@
 #include "srukf_ctx.h"
 using namespace srukf_impl;
 
-#define LM_REC_DOUBLES 57               // X6 | S66 | R | t | px | has_app, then the 441 patch bytes
-#define LM_REC_PATCH_DOUBLES 56         // (448 bytes)
-
 // one workgroup: thread 0 factors, the others copy the patch.  P66 symmetric row-major; eps = params.epsilon.
 //   d_j = max(eps, P_jj - sum_{m<j} S_mj^2),  S_jj = sqrt(d_j),  S_ji = (P_ji - sum_{m<j} S_mj S_mi) / S_jj  (i > j), sums in ascending m
 __global__ __launch_bounds__(64) void k_lm_record(const double* __restrict__ P66, const double* __restrict__ X, int k, double eps,
@@ -20,7 +17,7 @@ __global__ __launch_bounds__(64) void k_lm_record(const double* __restrict__ P66
     const int t = threadIdx.x;
     const bool app = has_app && has_app[k] != 0;
     unsigned char* pb = (unsigned char*)(out + LM_REC_DOUBLES);
-    for (int i = t; i < 8 * LM_REC_PATCH_DOUBLES; i += 64) pb[i] = (app && i < 441) ? app_patch[(size_t)k * patch_stride + i] : 0;
+    for (int i = t; i < 8 * LM_REC_PATCH_DOUBLES; i += 64) pb[i] = (app && i < PT_PATCH_BYTES) ? app_patch[(size_t)k * patch_stride + i] : 0;
     if (t != 0) return;
     double S[36];
     for (int e = 0; e < 36; e++) S[e] = 0.0;
@@ -42,7 +39,7 @@ __global__ __launch_bounds__(64) void k_lm_record(const double* __restrict__ P66
     for (int e = 0; e < 9; e++) out[42 + e] = app ? appR[9 * k + e] : 0.0;
     for (int e = 0; e < 3; e++) out[51 + e] = app ? appT[3 * k + e] : 0.0;
     for (int e = 0; e < 2; e++) out[54 + e] = app ? appPx[2 * k + e] : 0.0;
-    out[56] = app ? 1.0 : 0.0;
+    out[LM_REC_DOUBLES - 1] = app ? 1.0 : 0.0;
 }
 
 // state index of the grown state -> index of the old one: landmarks before the insertion point keep theirs, the L new ones have none (-1),
@@ -80,7 +77,7 @@ namespace srukf_impl {
 void launch_lm_record(hipStream_t st, const double* P66, const double* X, int k, double eps, const unsigned char* app_patch, const double* appR,
                       const double* appT, const double* appPx, const int* has_app, double* out)
 {
-    hipLaunchKernelGGL(k_lm_record, dim3(1), dim3(64), 0, st, P66, X, k, eps, app_patch, srukf_app_patch_stride(), appR, appT, appPx, has_app, out);
+    hipLaunchKernelGGL(k_lm_record, dim3(1), dim3(64), 0, st, P66, X, k, eps, app_patch, PT_PATCH_STRIDE, appR, appT, appPx, has_app, out);
 }
 
 void launch_lm_insert(hipStream_t st, const double* S, int ld, const double* X, int p6, int L, const double* blk, double* S2, double* X2, int n2, int ld2)

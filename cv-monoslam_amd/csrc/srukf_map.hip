@@ -27,15 +27,15 @@ static int ensure_appearance(srukf_ctx* c)
     int rc = ensure_image(c); if (rc) return rc;               // (the frame buffer is the handle scope's, the records are per map size: either may exist without the other)
     if (c->app_patch) return SRUKF_OK;
     const size_t N = c->d.N > 0 ? c->d.N : 1;
-    HIPCHK(c, srukf_dmalloc((void**)&c->app_patch, N * srukf_app_patch_stride()));
-    HIPCHK(c, srukf_dmalloc((void**)&c->app_tmpl, N * srukf_app_tmpl_stride()));
+    HIPCHK(c, srukf_dmalloc((void**)&c->app_patch, N * PT_PATCH_STRIDE));
+    HIPCHK(c, srukf_dmalloc((void**)&c->app_tmpl, N * PT_TMPL_STRIDE));
     HIPCHK(c, srukf_dmalloc((void**)&c->appR, sizeof(double) * 9 * N));
     HIPCHK(c, srukf_dmalloc((void**)&c->appT, sizeof(double) * 3 * N));
     HIPCHK(c, srukf_dmalloc((void**)&c->appPx, sizeof(double) * 2 * N));
     HIPCHK(c, srukf_dmalloc((void**)&c->corr, sizeof(double) * N));
     HIPCHK(c, srukf_dmalloc((void**)&c->has_app, sizeof(int) * N));
-    HIPCHK(c, hipMemsetAsync(c->app_patch, 0, N * srukf_app_patch_stride(), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->app_tmpl, 0, N * srukf_app_tmpl_stride(), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->app_patch, 0, N * PT_PATCH_STRIDE, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->app_tmpl, 0, N * PT_TMPL_STRIDE, c->stream));
     HIPCHK(c, hipMemsetAsync(c->has_app, 0, sizeof(int) * N, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SRUKF_OK;
@@ -45,7 +45,7 @@ static int ensure_appearance(srukf_ctx* c)
 static void copy_appearance(srukf_ctx* a, int from, srukf_ctx* b, int to, int count = 1)
 {
     if (count < 1) return;
-    const size_t ps = srukf_app_patch_stride(), ts = srukf_app_tmpl_stride(), m = (size_t)count;
+    const size_t ps = PT_PATCH_STRIDE, ts = PT_TMPL_STRIDE, m = (size_t)count;
     hipMemcpyAsync(b->app_patch + to * ps, a->app_patch + from * ps, ps * m, hipMemcpyDeviceToDevice, b->stream);
     hipMemcpyAsync(b->app_tmpl + to * ts, a->app_tmpl + from * ts, ts * m, hipMemcpyDeviceToDevice, b->stream);
     hipMemcpyAsync(b->appR + 9 * to, a->appR + 9 * from, sizeof(double) * 9 * m, hipMemcpyDeviceToDevice, b->stream);
@@ -58,7 +58,7 @@ static void copy_appearance(srukf_ctx* a, int from, srukf_ctx* b, int to, int co
 static void clear_appearance(srukf_ctx* b, int to, int count)
 {
     if (count < 1) return;
-    const size_t ps = srukf_app_patch_stride(), ts = srukf_app_tmpl_stride(), m = (size_t)count;
+    const size_t ps = PT_PATCH_STRIDE, ts = PT_TMPL_STRIDE, m = (size_t)count;
     hipMemsetAsync(b->app_patch + to * ps, 0, ps * m, b->stream);
     hipMemsetAsync(b->app_tmpl + to * ts, 0, ts * m, b->stream);
     hipMemsetAsync(b->appR + 9 * to, 0, sizeof(double) * 9 * m, b->stream);
@@ -95,17 +95,16 @@ void adopt_context(srukf_ctx* c, srukf_ctx* c2)
 extern "C" {
 
 // PointsMap::initPatch / initRotation / initTrans / initPixel as set at creation (SLAM.cpp:920-925): patch = the
-// (2 HP_INIT + 1)^2 = 21 x 21 gray window image(Rect(round(u) - 10, round(v) - 10, 21, 21)), row-major as cv::Mat;
+// PT_PATCH_W^2 = 21 x 21 gray window image(Rect(round(u) - 10, round(v) - 10, 21, 21)), row-major as cv::Mat;
 // R = Rwc (3x3 row-major), t = camera position, px = the distorted pixel.  matchPatch is zeroed (926).
 int srukf_set_landmark_appearance(srukf_ctx* c, int k, const unsigned char* patch, const double R[9], const double t[3], const double px[2])
 {
     if (!c || !patch || !R || !t || !px || k < 0 || k >= c->d.N) return SRUKF_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_appearance(c); if (rc) return rc;
-    const size_t ps = srukf_app_patch_stride(), ts = srukf_app_tmpl_stride();
     const int one = 1;
-    HIPCHK(c, hipMemcpy(c->app_patch + k * ps, patch, 441, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemset(c->app_tmpl + k * ts, 0, ts));
+    HIPCHK(c, hipMemcpy(c->app_patch + (size_t)k * PT_PATCH_STRIDE, patch, PT_PATCH_BYTES, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(c->app_tmpl + (size_t)k * PT_TMPL_STRIDE, 0, PT_TMPL_STRIDE));
     HIPCHK(c, hipMemcpy(c->appR + 9 * k, R, sizeof(double) * 9, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->appT + 3 * k, t, sizeof(double) * 3, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->appPx + 2 * k, px, sizeof(double) * 2, hipMemcpyHostToDevice));
@@ -123,7 +122,7 @@ int srukf_capture_appearance(srukf_ctx* c, int first, int K, const double* uv, c
     for (int q = 0; q < K; q++) {                                        // the 21 x 21 window must lie inside the frame
         if (!(std::fabs(uv[2 * q]) < 1e9) || !(std::fabs(uv[2 * q + 1]) < 1e9)) { c->err = "capture_appearance: pixel is not finite"; return SRUKF_ERR_BAD_ARG; }
         const int u = (int)std::nearbyint(uv[2 * q]), v = (int)std::nearbyint(uv[2 * q + 1]);
-        if (u - 10 < 0 || u + 10 > W - 1 || v - 10 < 0 || v + 10 > H - 1) { c->err = "capture_appearance: the 21 x 21 window leaves the image"; return SRUKF_ERR_BAD_ARG; }
+        if (u - PT_INIT_HALF < 0 || u + PT_INIT_HALF > W - 1 || v - PT_INIT_HALF < 0 || v + PT_INIT_HALF > H - 1) { c->err = "capture_appearance: the 21 x 21 window leaves the image"; return SRUKF_ERR_BAD_ARG; }
     }
     HIPCHK(c, hipSetDevice(c->device));
     step_commit_motion(c);
@@ -133,7 +132,7 @@ int srukf_capture_appearance(srukf_ctx* c, int first, int K, const double* uv, c
     HIPCHK(c, srukf_dmalloc_on(&d_uv, sizeof(double) * 2 * K, c->stream));
     hipError_t e = hipMemcpyAsync(d_uv, uv, sizeof(double) * 2 * K, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        ProfScope ps(c, KC_CAPTURE, 0, 441.0 * K);
+        ProfScope ps(c, KC_CAPTURE, 0, (double)PT_PATCH_BYTES * K);
         launch_capture_patch(c->stream, c->d_image, W, first, K, d_uv, c->X, c->d.n, c->app_patch, c->app_tmpl, c->appR, c->appT, c->appPx, c->has_app);
         e = hipGetLastError();
     }
@@ -149,7 +148,7 @@ int srukf_get_match_patch(srukf_ctx* c, int k, unsigned char* out)
     if (!c->app_tmpl) { c->err = "get_match_patch: no appearance records"; return SRUKF_ERR_SEQUENCE; }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, c->app_tmpl + (size_t)k * srukf_app_tmpl_stride(), 289, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->app_tmpl + (size_t)k * PT_TMPL_STRIDE, PT_TMPL_BYTES, hipMemcpyDeviceToHost));
     return SRUKF_OK;
 }
 
@@ -167,14 +166,13 @@ static int associate_frame(srukf_ctx* c, const unsigned char* gray, double* z, i
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_appearance(c); if (rc) return rc;
     if (chk && !c->match_res) {
-        if (srukf_app_tmpl_stride() != srukf_match_tmpl_stride()) { c->err = "associate_checked: template strides differ"; return SRUKF_ERR_UNSUPPORTED; }
-        if (srukf_dmalloc(&c->match_res, sizeof(double) * 7 * (size_t)N) != hipSuccess || srukf_dmalloc(&c->match_scores, sizeof(double) * srukf_match_score_stride() * (size_t)N) != hipSuccess) {
+        if (srukf_dmalloc(&c->match_res, sizeof(double) * match_res(N).doubles) != hipSuccess || srukf_dmalloc(&c->match_scores, sizeof(double) * PT_SCORE_STRIDE * (size_t)N) != hipSuccess) {
             (void)hipGetLastError(); match_drop(c); c->err = "associate_checked: out of device memory"; return SRUKF_ERR_NOMEM;
         }
     }
     const size_t img = (size_t)c->p.image_w * c->p.image_h;
     const size_t mp = c->d.mp, zm = mp + ((size_t)N + 1) / 2;             // zcur | mcur: one device allocation of zm doubles
-    const size_t res_doubles = chk ? 7 * (size_t)N : zm + (size_t)N;      // what the export writes to the front of the staging buffer: match_res, or zcur | mcur | corr
+    const size_t res_doubles = chk ? match_res(N).doubles : zm + (size_t)N;      // what the export writes to the front of the staging buffer: match_res, or zcur | mcur | corr
     // What does not need the frame goes out first — the warp uses the PREDICTED robot pose (wrapPatch reads m_X_k after predictMotion, SLAM.cpp:1812-1830) — and runs while
     // the host copies the frame into pinned memory: a hipMemcpyAsync from the caller's pageable buffer is staged by the runtime, synchronously, in front of everything.
     step_commit_motion(c);
@@ -193,25 +191,28 @@ static int associate_frame(srukf_ctx* c, const unsigned char* gray, double* z, i
     }
     if (gray) { c->frame_valid = true; c->bgr_valid = false; }
     if (chk) {
-        ProfScope ps(c, KC_ASSOC_CHECKED, 0, (37.0 * 37.0 + 289.0 + 8.0 * srukf_match_score_stride()) * N);
-        srukf_launch_associate_checked(c->stream, c->d, c->p, chk->corr_threshold, chk->ratio, chk->exclusion, chk->subpixel, c->d_image, c->h, c->Si, c->vis, c->has_app,
-                                       c->app_tmpl, c->zcur, c->mcur, c->corr, c->match_res, c->match_scores);
+        ProfScope ps(c, KC_ASSOC_CHECKED, 0, (double)(PT_REGION_W * PT_REGION_W + PT_TMPL_BYTES + 8 * PT_SCORE_STRIDE) * N);
+        const MatchArgs ma = { .corr_threshold = chk->corr_threshold, .ratio = chk->ratio, .exclusion = chk->exclusion, .subpixel = chk->subpixel };
+        srukf_launch_associate_checked(c->stream, c->d, c->p, ma, c->d_image, c->h, c->Si, c->vis, c->has_app, c->app_tmpl, c->zcur, c->mcur, c->corr, c->match_res,
+                                       c->match_scores);
         c->match_valid = true;
     } else
     srukf_launch_associate(c->stream, c->d, c->p, c->d_image, c->h, c->Si, c->vis, c->has_app, c->app_tmpl, c->zcur, c->mcur, c->corr);
     // z | matched | corr written into the pinned buffer by ONE short launch, flag behind them: three small device-to-host copies were three blit kernels with their gaps
     const unsigned long long seq = ++c->step_seq;
-    if (chk) launch_export(c->stream, c->match_res, sizeof(double) * 7 * N, nullptr, 0, hs, c->dbg.step_spin ? step_flag(c) : nullptr, seq);
+    if (chk) launch_export(c->stream, c->match_res, sizeof(double) * match_res(N).doubles, nullptr, 0, hs, c->dbg.step_spin ? step_flag(c) : nullptr, seq);
     else launch_export(c->stream, c->zcur, sizeof(double) * zm, c->corr, sizeof(double) * N, hs, c->dbg.step_spin ? step_flag(c) : nullptr, seq);
     rc = step_wait_export(c, seq); if (rc) return rc;
     HIPCHK(c, hipGetLastError());
-    if (chk) {                                                            // z | corr | corr2 | z2 | matched, flags
-        if (z) memcpy(z, hs, sizeof(double) * 2 * N);
-        if (corr) memcpy(corr, hs + 2 * (size_t)N, sizeof(double) * N);
-        if (corr2) memcpy(corr2, hs + 3 * (size_t)N, sizeof(double) * N);
-        if (z2) memcpy(z2, hs + 4 * (size_t)N, sizeof(double) * 2 * N);
-        if (matched) memcpy(matched, hs + 6 * (size_t)N, sizeof(int) * N);
-        if (flags) memcpy(flags, (const int*)(hs + 6 * (size_t)N) + N, sizeof(int) * N);
+    if (chk) {
+        const MatchRes at = match_res(N);
+        const int* hm = (const int*)(hs + at.matched);
+        if (z) memcpy(z, hs + at.z, sizeof(double) * 2 * N);
+        if (corr) memcpy(corr, hs + at.corr, sizeof(double) * N);
+        if (corr2) memcpy(corr2, hs + at.corr2, sizeof(double) * N);
+        if (z2) memcpy(z2, hs + at.z2, sizeof(double) * 2 * N);
+        if (matched) memcpy(matched, hm, sizeof(int) * N);
+        if (flags) memcpy(flags, hm + at.flags_ints, sizeof(int) * N);
         return SRUKF_OK;
     }
     if (z) memcpy(z, hs, sizeof(double) * 2 * N);
@@ -251,20 +252,19 @@ int srukf_associate_checked(srukf_ctx* c, const unsigned char* gray, const srukf
 }
 
 // the score map the last srukf_associate_checked left for landmark k: out[wx * wy] row-major, (x0, y0) = the pixel of the window's top-left candidate centre
-int srukf_get_match_scores(srukf_ctx* c, int k, double out[441], int* wx, int* wy, int* x0, int* y0)
+int srukf_get_match_scores(srukf_ctx* c, int k, double out[PT_SCORE_W * PT_SCORE_W], int* wx, int* wy, int* x0, int* y0)
 {
     if (!c) return SRUKF_ERR_BAD_ARG;
     if (!c->match_valid || !c->match_scores) { c->err = "get_match_scores: no checked association since the last map change or reset"; return SRUKF_ERR_SEQUENCE; }
     if (k < 0 || k >= c->d.N) return SRUKF_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int stride = srukf_match_score_stride();
-    std::vector<double> buf(stride);
-    HIPCHK(c, hipMemcpy(buf.data(), c->match_scores + (size_t)k * stride, sizeof(double) * stride, hipMemcpyDeviceToHost));
-    const int w = (int)buf[441], hgt = (int)buf[442];
-    if (w < 0 || hgt < 0 || w * hgt > 441) { c->err = "get_match_scores: corrupt window"; return SRUKF_ERR_HIP; }
-    if (out) memcpy(out, buf.data(), sizeof(double) * (size_t)(w * hgt));
-    if (wx) *wx = w; if (wy) *wy = hgt; if (x0) *x0 = (int)buf[443]; if (y0) *y0 = (int)buf[444];
+    double buf[PT_SCORE_STRIDE];
+    HIPCHK(c, hipMemcpy(buf, c->match_scores + (size_t)k * PT_SCORE_STRIDE, sizeof buf, hipMemcpyDeviceToHost));
+    const int w = (int)buf[PT_SCORE_WX], hgt = (int)buf[PT_SCORE_WY];
+    if (w < 0 || hgt < 0 || w * hgt > PT_SCORE_W * PT_SCORE_W) { c->err = "get_match_scores: corrupt window"; return SRUKF_ERR_HIP; }
+    if (out) memcpy(out, buf, sizeof(double) * (size_t)(w * hgt));
+    if (wx) *wx = w; if (wy) *wy = hgt; if (x0) *x0 = (int)buf[PT_SCORE_X0]; if (y0) *y0 = (int)buf[PT_SCORE_Y0];
     return SRUKF_OK;
 }
 
@@ -441,8 +441,8 @@ int srukf_get_landmark_record(srukf_ctx* c, int k, double X6[6], double S66[36],
     if (R) memcpy(R, h + 42, sizeof(double) * 9);
     if (t) memcpy(t, h + 51, sizeof(double) * 3);
     if (px) memcpy(px, h + 54, sizeof(double) * 2);
-    if (has_app) *has_app = h[56] != 0.0 ? 1 : 0;
-    if (patch) memcpy(patch, h + 57, 441);
+    if (has_app) *has_app = h[LM_REC_DOUBLES - 1] != 0.0 ? 1 : 0;
+    if (patch) memcpy(patch, h + LM_REC_DOUBLES, PT_PATCH_BYTES);
     return SRUKF_OK;
 }
 
@@ -488,10 +488,9 @@ int srukf_insert_landmarks(srukf_ctx* c, int L, const double* X6, const double* 
             clear_appearance(c2, 0, N + L);
         }
         if (patches) {
-            const size_t ps = srukf_app_patch_stride(), ts = srukf_app_tmpl_stride();
             std::vector<int> one(L, 1);
-            e = hipMemcpy2DAsync(c2->app_patch + p0 * ps, ps, patches, 441, 441, L, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemsetAsync(c2->app_tmpl + p0 * ts, 0, ts * (size_t)L, c->stream);
+            e = hipMemcpy2DAsync(c2->app_patch + (size_t)p0 * PT_PATCH_STRIDE, PT_PATCH_STRIDE, patches, PT_PATCH_BYTES, PT_PATCH_BYTES, L, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(c2->app_tmpl + (size_t)p0 * PT_TMPL_STRIDE, 0, PT_TMPL_STRIDE * (size_t)L, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(c2->appR + 9 * p0, R, sizeof(double) * 9 * (size_t)L, hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(c2->appT + 3 * p0, t, sizeof(double) * 3 * (size_t)L, hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(c2->appPx + 2 * p0, px, sizeof(double) * 2 * (size_t)L, hipMemcpyHostToDevice, c->stream);

@@ -7,9 +7,9 @@
 // and not used; (2) the reference's matchLocation is the integer candidate centre plus the FRACTION OF THE PREDICTION (1991-1992), a pull of up to one pixel
 // towards where the filter already believes the landmark is — the parabola through the peak's 4-neighbours locates it to a fraction of a pixel instead.
 //
-// k_associate_checked restates k_associate's template statistics, window, border test, gate and candidate score operation for operation (this file is compiled
-// with -ffp-contract=off like srukf_assoc.hip; the GPU tests hold the two kernels together bit for bit), keeps every candidate's score in LDS and in a device
-// buffer (448 doubles per landmark: the map row-major, then wx, wy, x0, y0), and then decides:
+// k_associate_checked runs the matching front k_associate runs (srukf_patch.h, match_front: template statistics, window, border test, gate and candidate score —
+// one text, so the two kernels' scores are the same bits; the GPU tests hold them together all the same), keeps every candidate's score in LDS and in a device
+// buffer (PT_SCORE_STRIDE doubles per landmark: the map row-major, then wx, wy, x0, y0), and then decides:
 //   best   the first maximum in row-major order (start value -1, ties to the lower index); corr = s[best]; raw = corr > corr_threshold
 //   rival  (only when raw) the largest s[c], first in row-major order among equals, over the candidates with Chebyshev distance > exclusion from best, s[c] > 0
 //          and s[c] >= s[c'] for every c' of the window at Chebyshev distance 1 (neighbours outside the window do not exist, gated ones count with their 0);
@@ -23,33 +23,9 @@
 // One workgroup of 256 threads per landmark, static LDS only (~20 KB), no atomics, nothing between workgroups.
 #include "srukf_device.h"
 #include "srukf_launch.h"
+#include "srukf_patch.h"
 
-#define HP_INIT 10             // SLAM.cpp:41-42
-#define HP_MATCH 8             // SLAM.cpp:43-44
-#define TMPL_W (2 * HP_MATCH + 1)
-#define APP_TMPL_STRIDE 320    // bytes per landmark in the matchPatch array (srukf_assoc.hip; the host checks it against srukf_app_tmpl_stride)
-#define SCORE_W (2 * HP_INIT + 1)
-#define SCORE_STRIDE 448       // doubles per landmark in the score buffer: 441 scores | wx | wy | x0 | y0 | 3 unused
-#define NO_CAND 0x7fffffff
-
-struct MatchArgs { double corr_threshold, ratio; int exclusion, subpixel; };
-
-// the block's maximum of (bv, bi), ties to the lower index: k_associate's reduction.  Result in bestv[0] / besti[0], valid for every thread after the call
-__device__ __forceinline__ void block_first_max(double bv, int bi, double* bestv, int* besti)
-{
-    const int tid = threadIdx.x;
-    bestv[tid] = bv; besti[tid] = bi;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) {
-            const double ov = bestv[tid + st]; const int oi = besti[tid + st];
-            if (ov > bestv[tid] || (ov == bestv[tid] && oi < besti[tid])) { bestv[tid] = ov; besti[tid] = oi; }
-        }
-        __syncthreads();
-    }
-}
-
-// res (7 N doubles, what the host exports in one piece): z[2N] | corr[N] | corr2[N] | z2[2N] | matched[N ints] flags[N ints]
+// res: the packed result block the host exports in one piece (match_res, srukf_patch.h); scores: the score buffer (PT_SCORE_*)
 // z / matched / corr: the filter's own buffers, left as k_associate leaves them
 __global__ __launch_bounds__(256) void k_associate_checked(KDims d, srukf_params p, MatchArgs ma, const unsigned char* __restrict__ image,
                                                            const double* __restrict__ h, const double* __restrict__ Si, const int* __restrict__ vis,
@@ -57,85 +33,38 @@ __global__ __launch_bounds__(256) void k_associate_checked(KDims d, srukf_params
                                                            double* __restrict__ z, int* __restrict__ matched, double* __restrict__ corr,
                                                            double* __restrict__ res, double* __restrict__ scores)
 {
-    __shared__ double tm[TMPL_W * TMPL_W];
+    __shared__ double tm[PT_TMPL_BYTES];
     __shared__ double red[8];
     __shared__ double bestv[256];
     __shared__ int besti[256];
-    __shared__ double smap[SCORE_W * SCORE_W];
+    __shared__ double rg[PT_REGION_W * PT_REGION_W];
+    __shared__ double smap[PT_SCORE_W * PT_SCORE_W];
     const int k = blockIdx.x, tid = threadIdx.x, N = d.N;
-    const int W = p.image_w, H = p.image_h, NP = TMPL_W * TMPL_W;
-    double* rz = res; double* rcorr = res + 2 * (size_t)N; double* rcorr2 = res + 3 * (size_t)N; double* rz2 = res + 4 * (size_t)N;
-    int* rmatched = (int*)(res + 6 * (size_t)N); int* rflags = rmatched + N;
-    double* sc = scores + (size_t)k * SCORE_STRIDE;
+    const MatchRes at = match_res(N);
+    double* rz = res + at.z; double* rcorr = res + at.corr; double* rcorr2 = res + at.corr2; double* rz2 = res + at.z2;
+    int* rmatched = (int*)(res + at.matched); int* rflags = rmatched + at.flags_ints;
+    double* sc = scores + (size_t)k * PT_SCORE_STRIDE;
     if (!vis[k] || !has_app[k]) {                                                                       // 1946
         if (tid == 0) {
             matched[k] = 0; corr[k] = 0.0; z[2 * k] = 0.0; z[2 * k + 1] = 0.0;
             rz[2 * k] = 0.0; rz[2 * k + 1] = 0.0; rcorr[k] = 0.0; rcorr2[k] = 0.0; rz2[2 * k] = 0.0; rz2[2 * k + 1] = 0.0; rmatched[k] = 0; rflags[k] = 0;
-            sc[441] = 0.0; sc[442] = 0.0; sc[443] = 0.0; sc[444] = 0.0;
+            sc[PT_SCORE_WX] = 0.0; sc[PT_SCORE_WY] = 0.0; sc[PT_SCORE_X0] = 0.0; sc[PT_SCORE_Y0] = 0.0;
         }
         return;
     }
-    // ---- k_associate, restated (srukf_assoc.hip:201-249) ----
-    // template statistics (calculateCrossCorrelation, 3151-3161): cv::mean, subtract, cv::norm
-    const unsigned char* mp = matchPatch + (size_t)k * APP_TMPL_STRIDE;
-    double s[1] = { 0.0 };
-    for (int e = tid; e < NP; e += 256) s[0] += mp[e];
-    block_sum<1>(s, red);
-    const double a2 = s[0] / NP;
-    double q[1] = { 0.0 };
-    for (int e = tid; e < NP; e += 256) { const double v = mp[e] - a2; tm[e] = v; q[0] += v * v; }
-    block_sum<1>(q, red);
-    const double std2 = sqrt(q[0]);
-    __syncthreads();
-    const double px = h[2 * k], py = h[2 * k + 1];
-    const double s00 = Si[4 * k], s01 = Si[4 * k + 1], s10 = Si[4 * k + 2], s11 = Si[4 * k + 3];
-    const double p00 = s00 * s00 + s10 * s10, p01 = s00 * s01 + s10 * s11, p10 = s01 * s00 + s11 * s10, p11 = s01 * s01 + s11 * s11;   // Si^T Si, 1951
-    double det = p00 * p11 - p01 * p10, i00 = 0, i01 = 0, i10 = 0, i11 = 0;                             // cv 2x2 closed-form inverse
-    if (det != 0.0) { det = 1.0 / det; i00 = p11 * det; i01 = -p01 * det; i10 = -p10 * det; i11 = p00 * det; }
-    int half_x = (int)ceil(2 * s00), half_y = (int)ceil(2 * s11);                                       // 1953-1954
-    half_x = min(HP_INIT, max(HP_MATCH, half_x)); half_y = min(HP_INIT, max(HP_MATCH, half_y));         // 1955-1956
-    const int wx = 2 * half_x + 1, wy = 2 * half_y + 1;
-    const int x0 = (int)px - half_x, y0 = (int)py - half_y;
-    // the pixels every candidate can touch, staged once as doubles; outside the image: 0 (such a candidate is skipped by the border test)
-    constexpr int RG_W = 2 * HP_INIT + 1 + 2 * HP_MATCH;       // 37
-    __shared__ double rg[RG_W * RG_W];
-    const int rw = wx + 2 * HP_MATCH, rh = wy + 2 * HP_MATCH, rx0 = x0 - HP_MATCH, ry0 = y0 - HP_MATCH;
-    for (int e = tid; e < rw * rh; e += 256) {
-        const int yy = ry0 + e / rw, xx = rx0 + e % rw;
-        rg[(e / rw) * RG_W + e % rw] = (xx >= 0 && xx < W && yy >= 0 && yy < H) ? (double)image[(size_t)yy * W + xx] : 0.0;
-    }
-    __syncthreads();
-    double bv = -1.0; int bi = NO_CAND;
-    for (int c = tid; c < wx * wy; c += 256) {
-        const int j = y0 + c / wx, i = x0 + c % wx;                                                     // row-major index of `correlation`
-        double cc = 0.0;
-        if (!(i < HP_MATCH || i > W - HP_MATCH - 1) && !(j < HP_MATCH || j > H - HP_MATCH - 1)) {       // 1962, 1969
-            const double ex = i - px, ey = j - py;
-            const double pii = (ex * i00 + ey * i10) * ex + (ex * i01 + ey * i11) * ey;                 // 1975
-            if (pii < 5.99146454710798) {                                                               // 1977
-                const double* roi = rg + (j - y0) * RG_W + (i - x0);                                    // 1979
-                double s1 = 0.0;
-                for (int r = 0; r < TMPL_W; r++) for (int cl = 0; cl < TMPL_W; cl++) s1 += roi[r * RG_W + cl];
-                const double a1 = s1 / NP;
-                double q1 = 0.0, dot = 0.0;
-                for (int r = 0; r < TMPL_W; r++) for (int cl = 0; cl < TMPL_W; cl++) { const double v1 = roi[r * RG_W + cl] - a1; q1 += v1 * v1; dot += v1 * tm[r * TMPL_W + cl]; }
-                const double std1 = sqrt(q1);
-                cc = (std1 == 0.0 || std2 == 0.0) ? 0.0 : dot / std1 / std2;                            // 3163-3166
-            }
-        }
-        smap[c] = cc; sc[c] = cc;                               // c < 441: inside both
-        if (cc > bv) { bv = cc; bi = c; }                       // candidates of one thread come in increasing index: first maximum kept
-    }
-    block_first_max(bv, bi, bestv, besti);                      // (its barriers also complete smap)
+    // k_associate's front, every score kept (c < PT_SCORE_W^2: inside both); the barriers of its reduction also complete smap
+    const MatchWindow w = match_front(k, p, image, h, Si, matchPatch, tm, red, rg, bestv, besti, [&](int c, double cc) { smap[c] = sc[c] = cc; });
+    const int wx = w.wx, wy = w.wy, x0 = w.x0, y0 = w.y0, half_x = w.half_x, half_y = w.half_y;
+    const double px = w.px, py = w.py;
     // ---- what the map is kept for ----
     const double maxVal = bestv[0];
     const int b = besti[0];
     const bool raw = maxVal > ma.corr_threshold;                // the same for every thread
     const int bx = b % wx, by = b / wx;
     __syncthreads();                                            // bestv / besti are used again
-    double corr2 = 0.0; int rv = NO_CAND;
+    double corr2 = 0.0; int rv = PT_NO_CAND;
     if (raw) {
-        double v2 = 0.0; int r2 = NO_CAND;
+        double v2 = 0.0; int r2 = PT_NO_CAND;
         for (int c = tid; c < wx * wy; c += 256) {
             const int cx = c % wx, cy = c / wx;
             const double v = smap[c];
@@ -151,14 +80,14 @@ __global__ __launch_bounds__(256) void k_associate_checked(KDims d, srukf_params
         }
         block_first_max(v2, r2, bestv, besti);
         rv = besti[0];
-        corr2 = rv == NO_CAND ? 0.0 : bestv[0];
+        corr2 = rv == PT_NO_CAND ? 0.0 : bestv[0];
     }
     if (tid != 0) return;
     int flags = 0, ok = 0;
     double zx = 0.0, zy = 0.0, z2x = 0.0, z2y = 0.0;
     if (raw) {                                                                                          // 1989
         flags = 1;
-        if (rv != NO_CAND) { z2x = (rv % wx) - half_x + px; z2y = (rv / wx) - half_y + py; }            // 1991-1992
+        if (rv != PT_NO_CAND) { z2x = (rv % wx) - half_x + px; z2y = (rv / wx) - half_y + py; }         // 1991-1992
         const bool ambiguous = corr2 >= ma.ratio * maxVal;
         if (ambiguous) flags |= 2;
         ok = ambiguous ? 0 : 1;
@@ -184,17 +113,13 @@ __global__ __launch_bounds__(256) void k_associate_checked(KDims d, srukf_params
     }
     corr[k] = maxVal; z[2 * k] = zx; z[2 * k + 1] = zy; matched[k] = ok;
     rz[2 * k] = zx; rz[2 * k + 1] = zy; rcorr[k] = maxVal; rcorr2[k] = corr2; rz2[2 * k] = z2x; rz2[2 * k + 1] = z2y; rmatched[k] = ok; rflags[k] = flags;
-    sc[441] = (double)wx; sc[442] = (double)wy; sc[443] = (double)x0; sc[444] = (double)y0;
+    sc[PT_SCORE_WX] = (double)wx; sc[PT_SCORE_WY] = (double)wy; sc[PT_SCORE_X0] = (double)x0; sc[PT_SCORE_Y0] = (double)y0;
 }
 
 extern "C" {
-void srukf_launch_associate_checked(hipStream_t st, KDims d, srukf_params p, double corr_threshold, double ratio, int exclusion, int subpixel,
-                                    const unsigned char* image, const double* h, const double* Si, const int* vis, const int* has_app,
-                                    const unsigned char* matchPatch, double* z, int* matched, double* corr, double* res, double* scores)
+void srukf_launch_associate_checked(hipStream_t st, KDims d, srukf_params p, MatchArgs ma, const unsigned char* image, const double* h, const double* Si, const int* vis,
+                                    const int* has_app, const unsigned char* matchPatch, double* z, int* matched, double* corr, double* res, double* scores)
 {
-    MatchArgs ma; ma.corr_threshold = corr_threshold; ma.ratio = ratio; ma.exclusion = exclusion; ma.subpixel = subpixel;
     hipLaunchKernelGGL(k_associate_checked, dim3(d.N), dim3(256), 0, st, d, p, ma, image, h, Si, vis, has_app, matchPatch, z, matched, corr, res, scores);
 }
-int srukf_match_score_stride(void) { return SCORE_STRIDE; }
-int srukf_match_tmpl_stride(void) { return APP_TMPL_STRIDE; }
 }  // extern "C"

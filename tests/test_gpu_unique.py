@@ -1,7 +1,7 @@
 """GPU tests of the checked association (srukf_associate_checked / srukf_get_match_scores, cv-monoslam_amd/csrc/srukf_unique.hip): it must EQUAL
 srukf_associate when nothing vetoes, its score map must be the restatement's (tests/np_unique.py: score_map) to 1e-9, and every decision taken on that map — best,
 rival, flags, sub-pixel offset — must EQUAL np_unique.peaks run on the device's own map.  The scenes follow test_gpu_parity.py::test_data_association_matches_oracle
-(N = 24, seed 13, appearance set by the host), and N = 1."""
+(N = 24, seed 13, appearance set by the host), and N = 1; the equality with srukf_associate is also held at 21-wide windows and at a window the image border cuts."""
 import math
 import os
 
@@ -119,11 +119,20 @@ def _check_peaks(s, r, params, ks=None):
     return recs
 
 
-@pytest.mark.parametrize("N", [24, 1])
-def test_equals_associate_when_nothing_vetoes(srukf, synth, N):
+def _scene(srukf, synth, N, sigma, H, flip):
+    s = Scene(srukf, synth, N, sigma=sigma, H=H)
+    if flip:
+        s.flip_si()
+    return s
+
+
+# the scenes of test_score_map_against_restatement: 17-wide windows, 21-wide windows (sigma_measure 5, Si's diagonal made positive), a window cut by the border
+@pytest.mark.parametrize("N, sigma, H, flip", [(24, None, 480, False), (1, None, 480, False), (24, 5, 480, True), (24, 3, 380, False)],
+                         ids=["24", "1", "24-sigma5-flipped", "24-sigma3-H380"])
+def test_equals_associate_when_nothing_vetoes(srukf, synth, N, sigma, H, flip):
     T = _texture(np.random.default_rng(2))
-    frame = _frame(T)
-    s = Scene(srukf, synth, N)
+    frame = _frame(T, H)
+    s = _scene(srukf, synth, N, sigma, H, flip)
     f = s.f
     skip = (5,) if N > 5 else ()
     for half in ("turned", "identity"):
@@ -140,11 +149,16 @@ def test_equals_associate_when_nothing_vetoes(srukf, synth, N):
         assert _same(a, r) and all(np.array_equal(x, y) for x, y in zip(pa, pr))
         if half == "identity":
             assert r["matched"].sum() >= max(1, int(s.vis.sum()) // 2)      # (something did match: the comparison is not between zeros)
+        maps = [f.match_scores(k) for k in range(N)]            # (the scene is what its name says)
+        if flip:
+            assert any(21 in m.shape for m, _, _ in maps)
+        if H < 480:
+            assert any(m.size and y0 + m.shape[0] - 1 > H - 9 for m, _, y0 in maps)
     # two consecutive frames: one call on the first, the other on the second, against associate on both
     sc = s.sc
     runs = []
     for order in (("a", "a"), ("c", "a"), ("a", "c")):
-        g = Scene(srukf, synth, N)
+        g = _scene(srukf, synth, N, sigma, H, flip)             # (the flipped Si is the first frame's: the second frame's is the device's own)
         g.set_current(frame, skip)
         out = []
         for t, which in enumerate(order):

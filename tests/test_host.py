@@ -257,3 +257,26 @@ def test_every_launcher_is_declared_once_in_srukf_launch_h():
                 continue
             again = [n for n, body in _signatures(_code(os.path.join(d, f))) if not body and n in offered]
             assert not again, f"{f} declares {again} itself: include srukf_launch.h"
+
+
+# ---- the appearance record's geometry: every size named once, in srukf_patch.h ----
+PATCH_GEOMETRY = ["PT_INIT_HALF", "PT_MATCH_HALF", "PT_PATCH_W", "PT_TMPL_W", "PT_PATCH_BYTES", "PT_TMPL_BYTES", "PT_PATCH_STRIDE", "PT_TMPL_STRIDE", "PT_SCORE_W",
+                  "PT_REGION_W", "PT_SCORE_STRIDE", "PT_SCORE_WX", "PT_SCORE_WY", "PT_SCORE_X0", "PT_SCORE_Y0"]
+PATCH_MACROS_GONE = ["HP_INIT", "HP_MATCH", "TMPL_W", "PATCH_W", "APP_PATCH_STRIDE", "APP_TMPL_STRIDE", "SCORE_STRIDE"]
+STRIDE_FUNCTIONS_GONE = ["srukf_app_patch_stride", "srukf_app_tmpl_stride", "srukf_match_score_stride", "srukf_match_tmpl_stride"]
+
+
+def test_patch_geometry_is_defined_once_in_srukf_patch_h():
+    csrc = os.path.join(ROOT, "cv-monoslam_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".hip")))
+    assert "srukf_patch.h" in files and len(files) >= 30
+    code = {f: _code(os.path.join(csrc, f)) for f in files}
+    for name in PATCH_GEOMETRY:
+        where = [f for f in files if re.search(r"\bconstexpr\s+int\b[^;]*?\b" + name + r"\s*=(?!=)|#\s*define\s+" + name + r"\b", code[f])]
+        assert where == ["srukf_patch.h"], f"{name} is defined in {where}"
+    for f in files:
+        macros = re.findall(r"^\s*#\s*define\s+(\w+)", code[f], flags=re.M)
+        assert not set(macros) & set(PATCH_MACROS_GONE), f"{f} defines {sorted(set(macros) & set(PATCH_MACROS_GONE))} as a macro"
+        named = [n for n, body in _signatures(code[f]) if n in STRIDE_FUNCTIONS_GONE]
+        assert not named, f"{f} declares or defines {named}"
+        assert not re.search(r"\b(?:" + "|".join(STRIDE_FUNCTIONS_GONE) + r")\b", code[f]), f"{f} names a removed stride function"
