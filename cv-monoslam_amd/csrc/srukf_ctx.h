@@ -9,6 +9,7 @@
 //   srukf_overlay.hip colour-frame intake (srukf_set_frame_bgr) and the 2-D feature overlay (srukf_render_overlay)
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search)
+//   srukf_joint.hip   the joint measurement update's kernels (srukf_update_joint; its host code is in srukf_step.hip)
 //   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip)
 //   srukf_patch.h     (through srukf_launch.h) the appearance record's sizes, the checked association's buffer layouts, the search kernels' shared front
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
@@ -220,6 +221,9 @@ struct srukf_map_scope : srukf_life {
     // a map change and srukf_reset drop both buffers (match_drop)
     double *match_res = nullptr, *match_scores = nullptr; bool match_valid = false;
     RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
+    // srukf_update_joint (srukf_joint.hip), allocated on its first call: jointZd = the sigma points' deviations dZ (joint_dev_rows x mp), jointW = [ Pzz | Pxy^T | z - h ]
+    // (mp x joint_work_ld), jointRd = the factored diagonal blocks (mp x 64) with the status word behind them
+    double *jointZd = nullptr, *jointW = nullptr, *jointRd = nullptr;
     // srukf_get_landmarks_display / srukf_get_frame_view_display: xyz (3N) | cov (9N) | axis (4N) | sigma (3N) | P4, pose (20) | rot (N ints).  A buffer of its own,
     // allocated by the first call (not G: the next frame's pre-issued first launch may be in flight behind the update)
     double* disp = nullptr;
@@ -307,7 +311,7 @@ struct srukf_map_scope : srukf_life {
                       S32, X32, U32, mx_part, mx_tasks, mx_tiles, A32, mxr_part, mxr_tasks, mxr_tiles, mxr_f64_tiles, mxr_xt,
                       perm, iperm, Sdis, pan[0], pan[1], red_perm, red_iperm, gdiag, shadowA, Utp, slabW, slabL, gsW, gsL, P1, pxy2_tiles, nskip,
                       red_head0_tiles, split_fold_list, red_syrk_tiles, ckS, ckX, syrk_tiles, pxy_tiles, syrk_head_tiles, syrk_head_tiles_b, fs,
-                      odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt };
+                      odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt, jointZd, jointW, jointRd };
         for (void* q : b) f(q);
     }
 };

@@ -42,6 +42,9 @@ static bool debug_buffer(srukf_ctx* c, const char* key, double** ptr, long long*
     else if (!strcmp(key, "P1")) { src = c->P1; n = c->P1 ? (long long)d.mp * d.np : 0; }
     else if (!strcmp(key, "h")) { src = c->h; n = 2LL * d.N; }
     else if (!strcmp(key, "Si")) { src = c->Si; n = 4LL * d.N; }
+    else if (!strcmp(key, "Ut")) { src = c->Ut; n = (long long)d.mp * d.np; }
+    else if (!strcmp(key, "PxyR")) { src = c->PxyR; n = 5LL * d.mp; }
+    else if (!strcmp(key, "joint_R")) { src = c->jointW; n = c->jointW ? (long long)d.mp * joint_work_ld(d.mp, d.np) : 0; }      // R | U^T | w as srukf_update_joint left them
     else if (!strcmp(key, "det_resp")) { src = c->det.resp; n = c->det.resp ? (long long)c->p.image_w * (long long)c->p.image_h : 0; }   // the response map of the last srukf_detect_features
     // the operands of one factorisation (scripts/split_replay.py: a split-form pair recorded from a real frame, each launch then replayed alone under the counters)
     else if (!strcmp(key, "Wf")) { src = c->Wf; n = (long long)d.np * d.np; }

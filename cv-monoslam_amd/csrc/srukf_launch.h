@@ -2,6 +2,7 @@
 // switches of the kernel files.  Included by srukf_ctx.h (the callers) and, behind their own headers, by the eight files that define these functions (srukf_predict,
 // srukf_factor, srukf_gmw_persist, srukf_rank, srukf_mixed, srukf_augment, srukf_assoc, srukf_unique): linkage is C, so only the compiler can compare a declaration
 // with its definition, and it does so in the file that defines it.  A function of this kind is declared here and nowhere else (tests/test_host.py holds the tree to it).
+// srukf_joint.hip's launchers (launch_joint_*, C++ linkage) are declared at the end.
 #pragma once
 #include "srukf_device.h"
 #include "srukf_rank.h"
@@ -164,3 +165,14 @@ void srukf_launch_associate(hipStream_t st, KDims d, srukf_params p, const unsig
 void srukf_launch_associate_checked(hipStream_t st, KDims d, srukf_params p, MatchArgs ma, const unsigned char* image, const double* h, const double* Si, const int* vis,
                                     const int* has_app, const unsigned char* matchPatch, double* z, int* matched, double* corr, double* res, double* scores);
 }  // extern "C"
+
+// ---- srukf_joint.hip (the joint measurement update; C++ linkage: its launchers are named launch_joint_*) ----
+// Zd: joint_dev_rows(Na) x mp, W: mp x joint_work_ld(mp, np) = [ Pzz | Pxy^T | z - h ], Rd: mp x 64 (the factored diagonal blocks), status: one int (0, or 1 + the row
+// of the first non-positive pivot).  form: W from Z and k_pxy's products (Ut raw, PxyR); factor: the blocked Cholesky, two launches per 64-row panel, leaves R, U^T and
+// w in W; dx: X += U w, U^T -> Ut in state order, the gamma / xi accumulators cleared for the k_syrk launch that follows
+int joint_dev_rows(int Na);
+int joint_work_ld(int mp, int np);
+void launch_joint_form(hipStream_t st, KDims d, KWeights w, const double* Z, const int* vis, const int* mt, const double* Si, const double* Ut, const double* PxyR, const double* h,
+                       const double* z, double* Zd, double* W, int* status);
+void launch_joint_factor(hipStream_t st, KDims d, double* W, double* Rd, int* status);
+void launch_joint_dx(hipStream_t st, KDims d, double* W, const double* Rd, const int* status, double* Ut, double* X, FrameScalars* fs);

@@ -147,6 +147,42 @@ static int step_predict_slow(srukf_ctx* c, const double odo_prev[3], const doubl
 }
 
 static int step_update_slow(srukf_ctx* c, const double* z, const int* matched, int reorder, int mode, int nm);
+// srukf_update_joint's mode on the slow form (internal: not a value of srukf_update's mode argument): BATCHED in everything but the launches that form U^T and the state update
+constexpr int STEP_UPDATE_JOINT = 2;
+
+// The joint update's launches in k_gain's place (srukf_joint.hip): behind seq_pxy, from the frame's Z, h, visible and k_pxy's products to U^T in
+// c->Ut (state order) and X += U w.  dx_pending stays false: the state update is applied here.  One round trip for the status word before anything touches the state
+static int seq_joint(srukf_ctx* c, const double* z_dev, const int* m_dev)
+{
+    const KDims& d = c->d;
+    const size_t mp = d.mp, ldw = joint_work_ld(d.mp, d.np);
+    if (!c->jointW) {
+        if (srukf_dmalloc(&c->jointZd, sizeof(double) * joint_dev_rows(d.Na) * mp) != hipSuccess || srukf_dmalloc(&c->jointW, sizeof(double) * mp * ldw) != hipSuccess ||
+            srukf_dmalloc(&c->jointRd, sizeof(double) * (mp * 64 + 1)) != hipSuccess) {
+            (void)hipGetLastError();
+            for (double** q : { &c->jointZd, &c->jointW, &c->jointRd }) { if (*q) srukf_dfree_on(*q, c->stream); *q = nullptr; }
+            c->err = "update_joint: out of device memory (work buffers)"; return SRUKF_ERR_NOMEM;
+        }
+    }
+    int* status = (int*)(c->jointRd + mp * 64);
+    const double mm = d.mp, nn = d.n, kk = 2.0 * d.Na;
+    {
+        ProfScope ps(c, KC_GAIN, mm * mm * kk + mm * mm * mm / 3.0 + mm * mm * (nn + 1) + 2.0 * mm * nn, 8.0 * (kk * mm * 2 + 3.0 * mm * (double)ldw + 2.0 * mm * nn));
+        launch_joint_form(c->stream, d, c->w, c->Z, c->vis, m_dev, c->Si, c->Ut, c->PxyR, c->h, z_dev, c->jointZd, c->jointW, status);
+        launch_joint_factor(c->stream, d, c->jointW, c->jointRd, status);
+        launch_joint_dx(c->stream, d, c->jointW, c->jointRd, status, c->Ut, c->X, c->fs);
+    }
+    int* hst = (int*)(c->hstage + 6 * (size_t)d.N + 8);
+    HIPCHK(c, hipMemcpyAsync(hst, status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (*hst != 0) {
+        // Pzz is a Gram matrix plus the noise blocks: the inputs were not finite.  k_joint_dx has left X alone; S has not been touched
+        char b[160]; snprintf(b, sizeof b, "update_joint: non-positive pivot in the innovation covariance (row %d): the frame's inputs are not finite; the state is unchanged", *hst - 1);
+        c->err = b; return SRUKF_ERR_UNSUPPORTED;
+    }
+    c->dx_pending = false;
+    return SRUKF_OK;
+}
 
 // the frame in flight leaves the fast path: the state before the frame comes back and the frame's predict half runs again on the other path
 static int step_rewind_to_slow(srukf_ctx* c)
@@ -308,19 +344,28 @@ static int step_update_slow(srukf_ctx* c, const double* z, const int* matched, i
     HIPCHK(c, hipMemcpyAsync(c->mcur, hm, sizeof(int) * N, hipMemcpyHostToDevice, c->stream));
     launch_set_frame(c->stream, c->fs, 0, 1);
     bool exact_ran = false;
-    seq_gain(c, c->zcur, c->mcur, FORM_SEPARATE_STATS);
+    if (mode == STEP_UPDATE_JOINT) {
+        seq_pxy(c, FORM_SEPARATE_STATS);
+        const int rc = seq_joint(c, c->zcur, c->mcur); if (rc) return rc;
+    } else
+        seq_gain(c, c->zcur, c->mcur, FORM_SEPARATE_STATS);
     // visibility is needed on the host only to skip no-op refactors in SEQUENTIAL mode
     if (reorder == SRUKF_NEED_REORDER) {
-        if (mode == SRUKF_UPDATE_BATCHED) { int rc = refactor_reorder(c, 0, d.mp); if (rc) return rc; }
+        if (mode != SRUKF_UPDATE_SEQUENTIAL) { int rc = refactor_reorder(c, 0, d.mp); if (rc) return rc; }
         else {
             for (int k = 0; k < N; k++) {
                 if (!matched[k]) continue;                               // SLAM.cpp:2068
                 for (int col = 0; col < 2; col++) { int rc = refactor_reorder(c, 2 * k + col, 2 * k + col + 1); if (rc) return rc; }
             }
         }
-    } else if (mode == SRUKF_UPDATE_BATCHED) {
+    } else if (mode != SRUKF_UPDATE_SEQUENTIAL) {
+        // (checked requests take the product in state order from c->Ut — RF_RANK_VIA_PERMUTATION / RF_FULL_RANK —, which is where the joint launches leave U^T too)
         seq_refactor(c, refactor_checked(c), FORM_SEPARATE_STATS);
         int rc = read_fs(c); if (rc) return rc;
+        if (mode == STEP_UPDATE_JOINT) {                                 // srukf_clamp_info: was the joint frame flagged (frame 0 / the first flagged row), or not (-1 / -1)?
+            const bool flagged = c->hfs->clamp_rows > 0;
+            c->clamp_frame_host = flagged ? 0 : -1; c->clamp_row_host = flagged ? c->hfs->clamp_first : -1;
+        }
         if (c->hfs->clamp_rows > 0) {
             // the reference's theta clamp would have been active: redo this refactor on the exact path
             exact_ran = true;
@@ -436,6 +481,30 @@ int srukf_update(srukf_ctx* c, const double* z, const int* matched, int reorder,
         rc = step_update_slow(c, z, matched, reorder, mode, nm);
     }
     c->frame_updated = rc == SRUKF_OK;                                   // (srukf_repredict_measurement: the posterior of this frame stands)
+    return rc;
+}
+
+// One Kalman update over all of the frame's matches with the full innovation covariance.  Always on the slow form: a frame predicted on the
+// fast path is rewound, as for the modes the fast path does not have; the next frame may take the fast path again
+int srukf_update_joint(srukf_ctx* c, const double* z, const int* matched, int reorder)
+{
+    if (!c || !z || !matched) return SRUKF_ERR_BAD_ARG;
+    if (c->phase < 2) { c->err = "update before predict_measurement"; return SRUKF_ERR_SEQUENCE; }
+    if (reorder != SRUKF_NEEDNOT_REORDER && reorder != SRUKF_NEED_REORDER) return SRUKF_ERR_BAD_ARG;
+    if (reorder == SRUKF_NEED_REORDER && c->K_new <= 0) { c->err = "NEED_REORDER without srukf_set_new_landmarks (m_nFilters = 0)"; return SRUKF_ERR_SEQUENCE; }
+    if (c->storage == SRUKF_STORAGE_F32_MIXED) { c->err = "update_joint: not available in SRUKF_STORAGE_F32_MIXED"; return SRUKF_ERR_UNSUPPORTED; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int N = c->d.N;
+    int nm = 0; for (int k = 0; k < N; k++) nm += matched[k] ? 1 : 0;
+    c->last_update_sequential = false;
+    c->frame_updated = false;
+    if (c->step_fast) {
+        int rc = step_rewind_to_slow(c); if (rc) return rc;
+        c->step_fast = false;
+    }
+    c->phase = 0;
+    const int rc = step_update_slow(c, z, matched, reorder, STEP_UPDATE_JOINT, nm);
+    c->frame_updated = rc == SRUKF_OK;
     return rc;
 }
 

@@ -723,6 +723,16 @@ void CSLAM::predictMeasurement()
     }
 }
 
+// every update of the facade: the reference's form in m_updateMode, or with jointUpdate the joint form
+int CSLAM::filterUpdate(const double* z, const int* matched, int reorder)
+{
+    if (!jointUpdate) return srukf_update(ctx_, z, matched, reorder, m_updateMode);
+    const int rc = srukf_update_joint(ctx_, z, matched, reorder);
+    int fr = -1;
+    if (rc == SRUKF_OK && reorder == FLAG_4_NEEDNOT_REORDER && srukf_clamp_info(ctx_, &fr, nullptr) == SRUKF_OK && fr >= 0) m_nJointFlagged++;
+    return rc;
+}
+
 // SLAM.cpp:2048-2104
 void CSLAM::KalmanUpdate()
 {
@@ -740,7 +750,7 @@ void CSLAM::KalmanUpdate()
     if (!isUseRANSAC || m_nMatches < 2) {                                                                      // 2058-2095 (one match cannot out-vote itself)
         for (int k = 0; k < N; k++) if (m[k]) map[k].nMatchTimes++;
         const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;                  // 2083-2090
-        if (check(srukf_update(ctx_, z.data(), m.data(), reorder, m_updateMode))) updateReacquiredLoopNodes(true);
+        if (check(filterUpdate(z.data(), m.data(), reorder))) updateReacquiredLoopNodes(true);
         return;
     }
     ransacZ_.swap(z); ransacM_.swap(m);                                                                        // 2097-2103
@@ -835,6 +845,30 @@ bool CSLAM::updateReacquiredLoopNodes(bool updated)
     const double CHI2INV_0_2 = 5.99146454710798;
     const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;
     std::vector<double> z(2 * (size_t)N, 0.0), h(2 * (size_t)N), Si(4 * (size_t)N); std::vector<int> m(N, 0), vis(N);
+    if (jointUpdate) {
+        // the joint form has the cross terms the one-at-a-time order stands in for: all nodes in ONE update; behind an update of this frame each must still pass the
+        // gate at the prediction from the posterior
+        if (updated && !check(srukf_repredict_measurement(ctx_, h.data(), Si.data(), vis.data()))) return false;
+        int taken = 0;
+        for (int k : nodes) {
+            bool take = true;
+            if (updated) {
+                const double s00 = Si[4 * k], s01 = Si[4 * k + 1], s11 = Si[4 * k + 3];
+                take = vis[k] && s00 != 0.0 && s11 != 0.0;
+                if (take) {
+                    const double v0 = map[k].matchLocation.x - h[2 * k], v1 = map[k].matchLocation.y - h[2 * k + 1];
+                    const double y0 = v0 / s00, y1 = (v1 - s01 * y0) / s11;
+                    take = y0 * y0 + y1 * y1 < CHI2INV_0_2;
+                }
+            }
+            if (!take) { map[k].isMatching = false; continue; }
+            m[k] = 1; z[2 * k] = map[k].matchLocation.x; z[2 * k + 1] = map[k].matchLocation.y; taken++;
+        }
+        if (taken == 0) return true;
+        if (!check(filterUpdate(z.data(), m.data(), reorder))) return false;
+        for (int k = 0; k < N; k++) if (m[k]) { map[k].nMatchTimes++; m_nMatches++; m_nArchiveReacquired++; }
+        return true;
+    }
     for (int k : nodes) {
         bool take = true;
         if (updated) {
@@ -850,7 +884,7 @@ bool CSLAM::updateReacquiredLoopNodes(bool updated)
         if (!take) { map[k].isMatching = false; continue; }
         std::fill(m.begin(), m.end(), 0); m[k] = 1;
         z[2 * k] = map[k].matchLocation.x; z[2 * k + 1] = map[k].matchLocation.y;
-        if (!check(srukf_update(ctx_, z.data(), m.data(), reorder, m_updateMode))) return false;
+        if (!check(filterUpdate(z.data(), m.data(), reorder))) return false;
         updated = true;
         map[k].nMatchTimes++; m_nMatches++; m_nArchiveReacquired++;
     }
@@ -875,7 +909,7 @@ bool CSLAM::updateLowInnovationInliers()
     std::vector<int> m(N, 0);
     for (int k = 0; k < N; k++) m[k] = map[k].inliner_L ? 1 : 0;
     const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;                      // as the plain branch, 2083-2090
-    return check(srukf_update(ctx_, ransacZ_.data(), m.data(), reorder, m_updateMode));
+    return check(filterUpdate(ransacZ_.data(), m.data(), reorder));
 }
 
 // a match outside the consensus set is rescued when, seen from the posterior of the first update, it is still visible and passes the chi-square gate
@@ -908,7 +942,7 @@ bool CSLAM::updateHighInnovationInliers()
     for (int k = 0; k < N; k++) m[k] = map[k].inliner_H ? 1 : 0;
     // (a frame that follows a landmark addition keeps FLAG_4_NEED_REORDER for this update too, as every per-landmark update of such a frame does in the reference, 2083-2090)
     const int reorder = (m_nAddings != 0) ? FLAG_4_NEED_REORDER : FLAG_4_NEEDNOT_REORDER;
-    return check(srukf_update(ctx_, ransacZ_.data(), m.data(), reorder, m_updateMode));
+    return check(filterUpdate(ransacZ_.data(), m.data(), reorder));
 }
 
 void CSLAM::refreshMirrors()

@@ -111,6 +111,12 @@ public:
     bool   isUseRANSAC = false;                                // SLAM.cpp:185
     double THRESHOLD_RANSAC = 8.0;                             // SLAM.cpp:186, SLAM.h:249: Euclidean pixel distance between measurement and prediction
     int    m_nLowInliers = 0, m_nHighInliers = 0;              // SLAM.h:227-228
+    // ---- the joint measurement update (ours).  On: KalmanUpdate's plain branch and the RANSAC inlier updates are ONE update over all of their
+    //      matches with the full innovation covariance (srukf_update_joint; m_updateMode is not consulted), and updateReacquiredLoopNodes measures all re-acquired
+    //      nodes in one such update instead of one update each.  Off (default): nothing changes
+    bool   jointUpdate = false;
+    int    m_nJointFlagged = 0;                                // joint updates whose refactorisation was flagged and went to the exact path (srukf_clamp_info)
+    int    filterUpdate(const double* z, const int* matched, int reorder);   // srukf_update(m_updateMode), or srukf_update_joint
     void updateRobotInformation();                             // SLAM.cpp:2957-3000 (m_path only)
     void recordRobotInformation();                             // SLAM.cpp:3512-3562 (RobotPath.txt rows)
     bool loadOdometryData(const std::string& path);            // SLAM.cpp:363-496 ("%d : %*lf %lf %lf %lf")
@@ -268,7 +274,7 @@ public:
     std::vector<ArchiveSearch> m_archiveLog;                   // every search that looked at records, when logDetectPasses is on: m_frame.counter, map and archive
                                                                // size around it, the records searched and the IDs put back
     bool reacquireLoopNodes();                                 // between dataAssociation and KalmanUpdate of the frame after
-    bool updateReacquiredLoopNodes(bool updated);              // one srukf_update per re-acquired node, re-predicted in between (updated: an update ran this frame)
+    bool updateReacquiredLoopNodes(bool updated);              // one srukf_update per re-acquired node, re-predicted in between (updated: an update ran this frame); jointUpdate: one joint update of all
     // true: refreshFeaturesDisplay takes axis / sigma of every map node from the device with the frame view (srukf_get_frame_view_display /
     // srukf_get_landmarks_display: k_lm_ellipsoid runs this class's Jacobi and quaternion arithmetic operation for operation, same bits)
     // instead of calling get3DdisplayInformation per landmark.  false (default): the host computes them

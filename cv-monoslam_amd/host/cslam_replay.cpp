@@ -13,6 +13,7 @@
 // ransac=<file>: KalmanUpdate runs 1-point RANSAC (isUseRANSAC); per frame the file receives int32 m_nLowInliers, int32 m_nHighInliers, int32 n (landmarks of
 //   the map in that frame), then per landmark int32 ID, uint8 inliner_L, uint8 inliner_H, and after the last frame int32 -1, int32 n, then per landmark int32 ID,
 //   int32 nMatchTimes.  Outliers are planted by writing displaced pixels into the scene file.
+// joint=1: CSLAM::jointUpdate (every update of the frame is the joint measurement update).  Adds, and only with it, a last line "joint flagged <n>"
 // ellipsoids=1: CSLAM::ellipsoidsOnDevice (axis / sigma of the map nodes come from the device with the frame view instead of the host's Jacobi iteration)
 // display=<file>: after the last frame, one text line per map node: ID, then xyz (3), cov (9), axis (r, x, y, z), sigma (3) printed with %a (every bit of
 //   every value; a NaN prints as "nan" whatever its sign bit, which the host's and the device's sqrt of a negative number set differently)
@@ -49,6 +50,7 @@ int main(int argc, char** argv)
         if (!rf) { perror(argv[a] + 7); return 2; }
         SLAM.isUseRANSAC = true;
     }
+    for (int a = 5; a < argc; a++) if (!strncmp(argv[a], "joint=", 6)) SLAM.jointUpdate = atoi(argv[a] + 6) != 0;
     const char* display_fn = nullptr;
     for (int a = 5; a < argc; a++) {
         if (!strncmp(argv[a], "ellipsoids=", 11)) SLAM.ellipsoidsOnDevice = atoi(argv[a] + 11) != 0;
@@ -151,5 +153,6 @@ int main(int argc, char** argv)
     }
     if (redirect > 0) printf("redirection: archived %d  stored map %d  show map %d\n", (int)SLAM.m_featuresAllInfo.size(), SLAM.m_nStoreMap, SLAM.m_nShowMap);
     printf("frames %d  landmarks %d  predicts %d  matches %d  total %.3f s\n", F, SLAM.m_nMapFeatures, SLAM.m_nPredicts, SLAM.m_nMatches, SLAM.m_totalTime);
+    if (SLAM.jointUpdate) printf("joint flagged %d\n", SLAM.m_nJointFlagged);
     return 0;
 }

@@ -19,6 +19,8 @@
 //              was.  Every landmark is "found" at its predicted pixel + 0.5 px of noise (new landmarks have no entry in the scene's z).  Prints frames/s,
 //              the map changes and their wall time per operation, and how many frames ran on the step-wise fast path / on the other one
 //     ransac=1 (facade): CSLAM::isUseRANSAC on (KalmanUpdate runs the 1-point RANSAC steps: consensus, update, and the rescue when matches remain outside it)
+//     joint=1 : every update is the joint measurement update (capi / assoc: srukf_update_joint; facade: CSLAM::jointUpdate).  Adds, and only with it,
+//              "joint": 1 and "joint_flagged_frames" (updates whose refactorisation was flagged and went to the exact path) to the output
 //     ellipsoids=1 (facade): CSLAM::ellipsoidsOnDevice on (axis / sigma of every landmark come from the device with the frame view, srukf_get_frame_view_display,
 //              instead of the host's Jacobi iteration per landmark); the run's figures are then also printed under "facade_ellipsoids_on_device"
 // scene.bin: int32 N, int32 F, double a1..a4, double X0[n], double S0[n*n], double z[F][2N]   (the file cslam_replay reads)
@@ -39,7 +41,7 @@ int main(int argc, char** argv)
 {
     if (argc < 4) { fprintf(stderr, "usage: %s scene.bin odometry.txt mode=<capi|facade|assoc> [frames=K] [warmup=W] [hint=0|1]\n", argv[0]); return 2; }
     std::string mode = "capi";
-    int K = 200, W = 20, hint = 0, churn = 0, ransac = 0, ellipsoids = 0;
+    int K = 200, W = 20, hint = 0, churn = 0, ransac = 0, ellipsoids = 0, joint = 0;
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -49,6 +51,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "churn=", 6)) churn = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "ransac=", 7)) ransac = atoi(argv[a] + 7);
         else if (!strncmp(argv[a], "ellipsoids=", 11)) ellipsoids = atoi(argv[a] + 11);
+        else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } sets.emplace_back(std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))), atoi(q + 1)); }
     }
     for (auto& kv : sets) (void)srukf_debug_set(nullptr, kv.first.c_str(), kv.second);      // process-wide keys (e.g. set=timing:1) apply in every mode; per-filter keys: mode=capi, below
@@ -78,10 +81,12 @@ int main(int argc, char** argv)
     long long flag_ticks = -1;                                       // last frame: start of the frame's first launch -> h / Si / visible flagged to the host (10 ns ticks)
     char churn_json[900] = "";
     char ell_json[200] = "";
+    int joint_flagged = 0;
     if (mode == "facade") {
         monoslam::CSLAM SLAM;
         SLAM.m_params.a1 = a4[0]; SLAM.m_params.a2 = a4[1]; SLAM.m_params.a3 = a4[2]; SLAM.m_params.a4 = a4[3];
         SLAM.isUseRANSAC = ransac != 0;
+        SLAM.jointUpdate = joint != 0;
         SLAM.ellipsoidsOnDevice = ellipsoids != 0;
         if (!SLAM.setMap(N, X0.data(), S0.data(), nullptr)) { fprintf(stderr, "%s\n", SLAM.lastError.c_str()); return 1; }
         SLAM.MIN_STEP_X = SLAM.MIN_STEP_Y = 0.0;
@@ -148,6 +153,7 @@ int main(int argc, char** argv)
                      n_phase[3] ? by_phase[3] / n_phase[3] * 1e6 : 0.0);
         }
         if (!SLAM.lastError.empty()) { fprintf(stderr, "%s\n", SLAM.lastError.c_str()); return 1; }
+        joint_flagged = SLAM.m_nJointFlagged;
         const int nn = SLAM.m_X_k.rows;
         for (int e = 0; e < 4; e++) pose[e] = SLAM.m_X_k.at(nn - 4 + e, 0);
         P4[0] = SLAM.m_P_k.at(nn - 4, nn - 4); P4[1] = SLAM.m_P_k.at(nn - 4, nn - 3); P4[4] = SLAM.m_P_k.at(nn - 3, nn - 4); P4[5] = SLAM.m_P_k.at(nn - 3, nn - 3);
@@ -209,7 +215,8 @@ int main(int argc, char** argv)
             const double* zz = &z[(size_t)fr * 2 * N];
             for (int k = 0; k < N; k++) m[k] = vis[k];                 // the host's association: every visible landmark found where the scene put it
             const double s3 = now_s();
-            CK(srukf_update(c, zz, m.data(), SRUKF_NEEDNOT_REORDER, SRUKF_UPDATE_BATCHED));
+            if (joint) { CK(srukf_update_joint(c, zz, m.data(), SRUKF_NEEDNOT_REORDER)); int ffr = -1; if (srukf_clamp_info(c, &ffr, nullptr) == SRUKF_OK && ffr >= 0) joint_flagged++; }
+            else CK(srukf_update(c, zz, m.data(), SRUKF_NEEDNOT_REORDER, SRUKF_UPDATE_BATCHED));
             const double s4 = now_s();
             CK(srukf_get_robot(c, pose, P4));
             if (fr >= W) { tcall[0] += s1 - s0; tcall[1] += s2 - s1; tcall[2] += s3 - s2; tcall[3] += s4 - s3; tcall[4] += now_s() - s4; }
@@ -218,10 +225,12 @@ int main(int argc, char** argv)
         srukf_debug_get(c, "meas_flag_ticks", &flag_ticks);
         srukf_destroy(c);
     }
-    printf("{\"mode\": \"%s\", %s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
+    char joint_json[80] = "";
+    if (joint) snprintf(joint_json, sizeof joint_json, "\"joint\": 1, \"joint_flagged_frames\": %d, ", joint_flagged);
+    printf("{\"mode\": \"%s\", %s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
            "\"pose\": [%.17g, %.17g, %.17g, %.17g], \"P_robot\": [%.17g, %.17g, %.17g, %.17g], \"device_matches\": %lld, \"stats_flag_us_into_first_launch\": %.2f, \"host_us_per_call\": {\"predict_motion\": %.2f, \"predict_measurement\": %.2f, \"association\": %.2f, \"update\": %.2f, \"get_robot\": %.2f}, "
            "\"filter_driven_by\": \"scene z / matched (host association)\"}\n",
-           mode.c_str(), churn_json, ell_json, hint, N, K, W, K / t_timed, t_timed / K * 1e6, pose[0], pose[1], pose[2], pose[3], P4[0], P4[1], P4[4], P4[5], matches_dev, flag_ticks * 0.01,
+           mode.c_str(), churn_json, ell_json, joint_json, hint, N, K, W, K / t_timed, t_timed / K * 1e6, pose[0], pose[1], pose[2], pose[3], P4[0], P4[1], P4[4], P4[5], matches_dev, flag_ticks * 0.01,
            tcall[0] / K * 1e6, tcall[1] / K * 1e6, tcall[2] / K * 1e6, tcall[3] / K * 1e6, tcall[4] / K * 1e6);
     fflush(stdout);                                                // (the line must not depend on what the runtimes' exit handlers do)
     return 0;

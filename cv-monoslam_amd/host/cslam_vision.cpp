@@ -15,6 +15,7 @@
 //   counters m_nArchiveMatches / m_nArchiveRejected / m_nArchiveReacquired at the end.
 // ransac=<threshold>: KalmanUpdate runs 1-point RANSAC (CSLAM::isUseRANSAC, THRESHOLD_RANSAC = threshold in pixels; 8 is the reference's constant).  Adds, and
 //   only with it, a "ransac" line per frame (low- and high-innovation inliers).
+// joint=1: CSLAM::jointUpdate (every update of the frame is the joint measurement update).  Adds, and only with it, a last line "joint flagged <n>".
 // colour=1: every gray frame is fed as a B = G = R colour frame through CSLAM::loadPictures (srukf_set_frame_bgr) and associated on the held frame
 //   (dataAssociationOnDeviceHeld).  The conversion keeps such a frame byte for byte (the weights sum to 2^14), so the output equals the default run's.
 // overlay=<file>: after the last frame, CSLAM::display2DFeatureModel's bytes (H x W x 3, B G R) go to <file> and the rows they were drawn from to <file>.in:
@@ -42,7 +43,7 @@ int main(int argc, char** argv)
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
     int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay;
-    bool unique = false, subpix = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
+    bool unique = false, subpix = false, joint = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
     for (int a = 3; a < argc; a++)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
         else if (!strncmp(argv[a], "archive=", 8)) { archiveCap = atoi(argv[a] + 8); loops = true; }
@@ -51,6 +52,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "overlay=", 8)) overlay = argv[a] + 8;
         else if (!strncmp(argv[a], "unique=", 7)) { unique = true; uniqueRatio = atof(argv[a] + 7); const char* cm = strchr(argv[a] + 7, ','); if (cm) uniqueExcl = atoi(cm + 1); }
         else if (!strncmp(argv[a], "subpix=", 7)) subpix = atoi(argv[a] + 7) != 0;
+        else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6) != 0;
     if (warmup) {
         monoslam::CSLAM w;
         w.m_params.image_w = W; w.m_params.image_h = H; w.MIN_STEP_X = w.MIN_STEP_Y = 0.0;
@@ -71,6 +73,7 @@ int main(int argc, char** argv)
     if (ransac) { SLAM.isUseRANSAC = true; SLAM.THRESHOLD_RANSAC = ransacThr; }
     if (unique) { SLAM.rejectAmbiguousMatches = true; SLAM.AMBIGUITY_RATIO = uniqueRatio; SLAM.AMBIGUITY_EXCLUSION = uniqueExcl; }
     SLAM.subpixelMatches = subpix;
+    SLAM.jointUpdate = joint;
     const unsigned char* cur = nullptr;
     std::vector<unsigned char> bgr(colour ? (size_t)3 * W * H : 0);
     SLAM.dataAssociation = [&](monoslam::CSLAM& s) {                                         // loadPictures + dataAssociation (SLAM.cpp:95-97)
@@ -146,6 +149,7 @@ int main(int argc, char** argv)
         fclose(fo);
     }
     if (archiveCap > 0) printf("archive_matches %d archive_rejected %d archive_reacquired %d\n", SLAM.m_nArchiveMatches, SLAM.m_nArchiveRejected, SLAM.m_nArchiveReacquired);
+    if (joint) printf("joint flagged %d\n", SLAM.m_nJointFlagged);
     printf("add_features_frame1_ms %.3f  frame_time_ms %.3f\n", addWall * 1e3, SLAM.m_frameTime * 1e3);
     return 0;
 }

@@ -23,7 +23,7 @@ EXPORTS = [
     "srukf_abi_version", "srukf_default_params", "srukf_create", "srukf_destroy", "srukf_reset", "srukf_last_error",
     "srukf_set_state", "srukf_get_state", "srukf_set_state_device", "srukf_get_state_device", "srukf_get_robot",
     "srukf_get_landmark_block", "srukf_get_landmarks_cartesian", "srukf_get_frame_view", "srukf_get_covariance", "srukf_predict_motion", "srukf_predict_motion_next", "srukf_predict_measurement",
-    "srukf_update", "srukf_set_new_landmarks", "srukf_add_landmarks", "srukf_delete_landmark", "srukf_set_storage", "srukf_set_exclusive", "srukf_set_rank_aware", "srukf_null_directions", "srukf_run_frames_batch", "srukf_prepare_frames", "srukf_debug_poke_state", "srukf_get_state_f32", "srukf_set_landmark_appearance", "srukf_associate", "srukf_get_match_patch", "srukf_stage_sequence", "srukf_run_frames_async", "srukf_run_frames", "srukf_synchronize", "srukf_set_profiling",
+    "srukf_update", "srukf_update_joint", "srukf_set_new_landmarks", "srukf_add_landmarks", "srukf_delete_landmark", "srukf_set_storage", "srukf_set_exclusive", "srukf_set_rank_aware", "srukf_null_directions", "srukf_run_frames_batch", "srukf_prepare_frames", "srukf_debug_poke_state", "srukf_get_state_f32", "srukf_set_landmark_appearance", "srukf_associate", "srukf_get_match_patch", "srukf_stage_sequence", "srukf_run_frames_async", "srukf_run_frames", "srukf_synchronize", "srukf_set_profiling",
     "srukf_clamp_info", "srukf_debug_set", "srukf_debug_get", "srukf_debug_copy", "srukf_debug_upload", "srukf_debug_split_replay", "srukf_debug_gmw_stamps", "srukf_debug_starve_workers", "srukf_debug_allow_mixed", "srukf_profile_count", "srukf_profile_get", "srukf_profile_reset", "srukf_dims", "srukf_gmw_host",
     "srukf_project_host", "srukf_detect_features", "srukf_capture_appearance", "srukf_get_landmark_record", "srukf_insert_landmarks",
     "srukf_ransac_consensus", "srukf_repredict_measurement",
@@ -130,6 +130,7 @@ def load_library(path=None):
     L.srukf_predict_motion_next.argtypes = [C.c_void_p, _dp, _dp]
     L.srukf_predict_measurement.argtypes = [C.c_void_p, _dp, _dp, _ip]
     L.srukf_update.argtypes = [C.c_void_p, _dp, _ip, C.c_int, C.c_int]
+    L.srukf_update_joint.argtypes = [C.c_void_p, _dp, _ip, C.c_int]
     L.srukf_set_new_landmarks.argtypes = [C.c_void_p, C.c_int]
     L.srukf_add_landmarks.argtypes = [C.c_void_p, C.c_int, _dp]
     L.srukf_delete_landmark.argtypes = [C.c_void_p, C.c_int]
@@ -296,6 +297,12 @@ class Filter:
         z, m = _c(z), _c(matched, np.int32)
         assert z.shape == (2 * self.N,) and m.shape == (self.N,)
         self._chk(self._lib.srukf_update(self._h, _d(z), _i(m), reorder, mode))
+
+    def update_joint(self, z, matched, reorder=NEEDNOT_REORDER):
+        """One Kalman update over all of the frame's matches with the full innovation covariance (srukf_update_joint)."""
+        z, m = _c(z), _c(matched, np.int32)
+        assert z.shape == (2 * self.N,) and m.shape == (self.N,)
+        self._chk(self._lib.srukf_update_joint(self._h, _d(z), _i(m), reorder))
 
     def ransac_consensus(self, z, matched, threshold=8.0):
         """1-point RANSAC consensus over ALL single-match hypotheses (srukf_ransac_consensus), between predict_measurement and update.
@@ -587,7 +594,7 @@ class Filter:
         return v.value
 
     def debug_copy(self, key, count):
-        """Diagnostic copy of the first `count` doubles of a device work buffer ("Z", "DZ", "sigR", "Cmat", "Xr1", "Utp", "P1", "h", "Si")."""
+        """Diagnostic copy of the first `count` doubles of a device work buffer ("Z", "DZ", "sigR", "Cmat", "Xr1", "Utp", "P1", "h", "Si", "Ut", "PxyR", "joint_R")."""
         out = np.empty(int(count), dtype=np.float64)
         self._chk(self._lib.srukf_debug_copy(self._h, key.encode(), out.ctypes.data_as(C.POINTER(C.c_double)), int(count)))
         return out

@@ -171,6 +171,22 @@ int  srukf_predict_measurement(srukf_ctx* ctx, double* h, double* Si, int* visib
  * (SRUKF_ERR_SEQUENCE otherwise). */
 int  srukf_update(srukf_ctx* ctx, const double* z, const int* matched, int reorder, int mode);
 
+/* ---- the joint measurement update (ours: the reference has no counterpart) ----
+ * srukf_update_joint: in srukf_update's place for a frame (same phase rules, same z / matched / reorder).  ONE Kalman update over all matched and visible landmarks whose Si is not singular (the reference's closed-form inverse of a singular Si is zero, 2073: no gain)
+ *   with the full 2N x 2N innovation covariance
+ *       Pzz = wi sum_{i not noise} dZ_i dZ_i^T + blockdiag_k(wi sum_{i in noise} dZ_i,k dZ_i,k^T),   dZ_i = Z_i - Z_0   (no centre term, as 1769-1773)
+ *       Pzz = R^T R,  U^T = R^-T Pxy^T,  w = R^-T (z - h),  X += U w,  S <- gmw(S^T S - U U^T)
+ *   where KalmanUpdate (2070-2080; SRUKF_UPDATE_BATCHED) takes every landmark's gain from the same prior with that landmark's own 2 x 2 Si and adds them, so that
+ *   landmarks which agree on a large innovation overshoot together.  noise = the four sigma points of the two pixel-noise directions: every landmark keeps its own
+ *   pixel noise (the diagonal blocks are exactly the reference's Si^T Si; taken literally the reference's shared err components would be perfectly correlated
+ *   across landmarks); the motion-noise points stay in the off-diagonal blocks.  Pxy is what SRUKF_UPDATE_BATCHED forms from the single prior.  With one active
+ *   landmark the call equals srukf_update(BATCHED) for that landmark.  The refactorisation is srukf_update's own (theta check, exact path behind it;
+ *   SRUKF_NEED_REORDER as there).  No match: no-op (2050-2051).  Runs on the step-wise path's slow form (a frame predicted on the fast path is predicted again);
+ *   srukf_repredict_measurement and the RANSAC calls work behind it.  SRUKF_ERR_UNSUPPORTED: SRUKF_STORAGE_F32_MIXED; or a non-positive pivot in Pzz (inputs not
+ *   finite: the state is left as predicted, srukf_last_error names the row).  srukf_clamp_info behind a SRUKF_NEEDNOT_REORDER call: (0, first flagged pivot row)
+ *   when the refactorisation was flagged and went to the exact path, (-1, -1) when it was not.  Not part of the staged replay, the graphs or srukf_run_frames_batch. */
+int  srukf_update_joint(srukf_ctx* ctx, const double* z, const int* matched, int reorder);
+
 /* ---- 1-point RANSAC (KalmanUpdate's isUseRANSAC branch, SLAM.cpp:2097-2103: onePointRansacHypotheses, updateLowInnovationInliers, rescueHighInnovationInliers,
  * updateHighInnovationInliers are named there and never written; isUseRANSAC / THRESHOLD_RANSAC 185-186, m_nLowInliers / m_nHighInliers SLAM.h:227-228) ----
  * srukf_ransac_consensus: between srukf_predict_measurement and srukf_update (SRUKF_ERR_SEQUENCE otherwise).  A = { k : matched[k] != 0 and visible[k] }.  Every
@@ -498,7 +514,8 @@ int  srukf_debug_set(srukf_ctx* ctx, const char* key, int value);
  * "plan_workers", "plan_kept"). */
 int  srukf_debug_get(srukf_ctx* ctx, const char* key, long long* value);
 /* Diagnostic copy of a device work buffer (tests compare the launch sequences stage by stage): key = "Z", "DZ", "sigR", "Cmat", "Xr1",
- * "Utp", "P1", "h", "Si", "det_resp" (the response map r of the last srukf_detect_features, image_h x image_w); `count` doubles from the start of the buffer. */
+ * "Utp", "P1", "h", "Si", "det_resp" (the response map r of the last srukf_detect_features, image_h x image_w), "Ut" (mp x np: U^T in state order behind an update of the
+ * slow form), "PxyR" (5 x mp), "joint_R" (behind srukf_update_joint: mp rows of mp + np + 32 doubles, R | U^T | w); `count` doubles from the start of the buffer. */
 int  srukf_debug_copy(srukf_ctx* ctx, const char* key, double* out, long long count);
 /* ... and the other way (same keys, plus the operands of one factorisation: "Wf", "Gbak", "G", "D", "gsW", "gsL", "pans", "sync" — byte buffers counted in doubles).
  * srukf_debug_split_replay: ONE launch of the split form's pair (0: k_gmw_pivslab_persist, 1: k_gmw_tiles_persist) `reps` times ALONE against the buffers and flags a
