@@ -285,7 +285,7 @@ int srukf_create(srukf_ctx** out, int N, const srukf_params* p, int device, void
     }
     srukf_ctx* c = new srukf_ctx();
     c->device = device; c->p = *p;
-    if (!g_dbg_graphs) c->use_graph = false;                 // eager launches (profilers): srukf_debug_set(0, "graphs", 0)
+    if (!g_sw.graphs) c->use_graph = false;                 // eager launches (profilers): srukf_debug_set(0, "graphs", 0)
     if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
     else {
         if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { g_create_error = "hipStreamCreate failed"; delete c; return SRUKF_ERR_HIP; }
@@ -455,7 +455,7 @@ void ctx_retire(srukf_ctx* handle, srukf_ctx* old)
     // exits with exactly 32 retired contexts behind a handle — 950 to 1 100 frames of the churn leg — crashed in the HIP runtime's own exit handler after every srukf call
     // had returned (SIGSEGV under __cxa_finalize in libamdhip64; 30, 31, 33, 36 and 40 contexts: no crash; trimming the memory pool first: no difference).
     const double ctx_bytes = 14.0 * 8.0 * (double)old->d.np * old->d.np;
-    const size_t keep = (size_t)std::min((double)g_dbg_ctx_keep.load(), std::max(4.0, 16e9 / ctx_bytes));
+    const size_t keep = (size_t)std::min((double)g_sw.ctx_keep.load(), std::max(4.0, 16e9 / ctx_bytes));
     while (handle->retired.size() > keep) { srukf_destroy(handle->retired.front()); handle->retired.erase(handle->retired.begin()); }
 }
 

@@ -88,7 +88,7 @@ void batch_drop_all_graphs()
 // operands, fp64 storage), canonical null rows, nothing pending.
 static bool batch_eligible(srukf_ctx* const* cs, int B, bool ignore_canonical = false)
 {
-    if (B < 2 || B > 64 || !g_dbg_batch_wide.load()) return false;
+    if (B < 2 || B > 64 || !g_sw.batch_wide.load()) return false;
     const srukf_ctx* a = cs[0];
     for (int b = 0; b < B; b++) {
         const srukf_ctx* c = cs[b];
@@ -99,7 +99,7 @@ static bool batch_eligible(srukf_ctx* const* cs, int B, bool ignore_canonical = 
         // (the batched launches take these from the group's first filter: shape-only quantities today — checked, not assumed)
         if (c->n_syrk_head_tiles != a->n_syrk_head_tiles || c->gplan_red.ntiles != a->gplan_red.ntiles || c->pxy2_split_b0 != a->pxy2_split_b0 || memcmp(&c->w, &a->w, sizeof c->w) != 0) return false;
         if (!c->dbg.pxy2 || !c->dbg.nullskip || !c->dbg.tail_fuse || c->dbg.fused_motion != 2 || !c->dbg.table_perm || c->profiling || c->use_graph != a->use_graph || c->debug_starve) return false;
-        if (memcmp(&c->p, &a->p, sizeof c->p) != 0 || c->gplan_red.T < 16 || (size_t)c->d.np * sizeof(double) > 48 * 1024 || !rank_fused_mode()) return false;
+        if (memcmp(&c->p, &a->p, sizeof c->p) != 0 || c->gplan_red.T < 16 || (size_t)c->d.np * sizeof(double) > 48 * 1024 || !g_sw.rank_fused) return false;
         if (!c->odo_seq || c->seqF != a->seqF) return false;
     }
     return true;
@@ -111,12 +111,12 @@ static void batch_frame(const BatchPlan* bp, hipStream_t st)
     const int n = d.n, np = d.np, r = c->red_r, Tp = c->red_Tp, B = bp->B, kr = (r + 15) & ~15;
     srukf_launch_pxy2_b(st, d, bp->t_pxy2, B, c->pxy2_tiles, c->n_pxy2_tiles, kr, c->w, (d.N + 31) / 32);
     srukf_launch_gain_b(st, d, c->w, bp->t_gain, B, c->pxy2_split_b0, sqrt(c->p.epsilon));
-    srukf_launch_syrk_b(st, d, bp->t_syrk, B, g_dbg_batch_xcd.load() ? c->syrk_head_tiles_b : c->syrk_head_tiles, g_dbg_batch_xcd.load() ? c->n_syrk_head_tiles_b : c->n_syrk_head_tiles, std::min(np, kr), (n + 255) / 256,
+    srukf_launch_syrk_b(st, d, bp->t_syrk, B, g_sw.batch_xcd.load() ? c->syrk_head_tiles_b : c->syrk_head_tiles, g_sw.batch_xcd.load() ? c->n_syrk_head_tiles_b : c->n_syrk_head_tiles, std::min(np, kr), (n + 255) / 256,
                         (n - r + SRUKF_RANK_COLS - 1) / SRUKF_RANK_COLS);
     srukf_launch_syrk_own_b(st, n, np, bp->t_own, B, 0, d.mp, kr, c->gplan_red.tiles, c->gplan_red.ntiles, Tp);
     int pb = 0;
     for (int j0 = -64; j0 + 64 < np && j0 + 64 <= 64 * Tp; j0 += 64, pb ^= 1) {
-        if (!g_dbg_batch_split.load()) {
+        if (!g_sw.batch_split.load()) {
             srukf_launch_gmw_step64_b(st, n, np, j0, c->p.epsilon, bp->t_step, B, std::max(1, Tp - j0 / 64 - 1), pb);    // rows of the kept pivots only; the last panel: the pass-on row
             continue;
         }
@@ -126,7 +126,7 @@ static void batch_frame(const BatchPlan* bp, hipStream_t st)
         // step b's pass applies panel a's slabs and then panel b's to everything else — one pass over G instead of two, the products per element in the same order
         // (bit-identical).  A pair needs step b to have trailing tiles; the slabs of a pair live in the two halves of slabW / slabL.
         const int rows = Tp - j0 / 64 - 1, pair = j0 >= 0 ? (j0 / 64) & 1 : 0;
-        const bool k128 = g_dbg_batch_k128.load() != 0;
+        const bool k128 = g_sw.batch_k128.load() != 0;
         const bool first_of_pair = k128 && j0 >= 0 && pair == 0 && rows - 1 >= 1 && j0 + 128 < np && j0 + 128 <= 64 * Tp;
         const bool second_of_pair = k128 && j0 >= 64 && pair == 1 && rows >= 1;
         srukf_launch_gmw_pivslab_b(st, n, np, j0, c->p.epsilon, bp->t_step, B, pb, second_of_pair ? 1 : 0);
@@ -196,7 +196,7 @@ static int batch_run(srukf_ctx* const* cs, int B, int first, int count, double* 
         for (size_t q = 0; q < sizeof c0->p; q++) h = (h ^ pb[q]) * 1099511628211ull;
         const unsigned char* wb = (const unsigned char*)&c0->w;
         for (size_t q = 0; q < sizeof c0->w; q++) h = (h ^ wb[q]) * 1099511628211ull;
-        sig.push_back(h); sig.push_back((unsigned long long)g_dbg_batch_split.load());
+        sig.push_back(h); sig.push_back((unsigned long long)g_sw.batch_split.load());
     }
     if (sig != bp->sig) { batch_plan_drop_graphs(bp); bp->sig = sig; }
     HIPCHK(c0, hipSetDevice(c0->device));
@@ -274,7 +274,7 @@ int srukf_run_frames_batch(srukf_ctx* const* ctxs, int B, int first, int count, 
     //  permuted copy from S in between and is then no longer bit-identical to the same filter running alone)
     bool fresh = false, others_ok = true;
     for (int b = 0; b < B; b++) { fresh = fresh || (ctxs[b]->red_r > 0 && !ctxs[b]->null_canonical); others_ok = others_ok && ctxs[b]->odo_seq && ctxs[b]->seqF >= first + count; }
-    if (rc == SRUKF_OK && B > 1 && mode == SRUKF_UPDATE_BATCHED && g_dbg_batch_wide.load() && others_ok && batch_eligible(ctxs, B, true) && !(fresh && count < 2)) {
+    if (rc == SRUKF_OK && B > 1 && mode == SRUKF_UPDATE_BATCHED && g_sw.batch_wide.load() && others_ok && batch_eligible(ctxs, B, true) && !(fresh && count < 2)) {
         for (int b = 0; b < B; b++) hipStreamSynchronize(ctxs[b]->stream);       // the checkpoint copies; whatever the filters did before
         if (fresh) {
             for (int b = 0; b < B; b++) {
@@ -293,7 +293,7 @@ int srukf_run_frames_batch(srukf_ctx* const* ctxs, int B, int first, int count, 
             // (the pivot chains of a panel step), the other groups' launches do
             // (measured at N = 200, round 4, aggregate frames/s with 1 / 2 / 3 / 4 groups: 8 filters 10 270 / 11 450 / 11 280 / 11 700; 16: 12 710 / 14 260 / 14 300 / 14 790;
             //  32: 14 600 / 15 560 / 15 790 / 16 430; 48: 14 840 / 15 710 / 16 460 / 16 650)
-            int G = g_dbg_batch_groups.load() > 0 ? g_dbg_batch_groups.load() : SRUKF_BATCH_GROUPS_MAX;
+            int G = g_sw.batch_groups.load() > 0 ? g_sw.batch_groups.load() : SRUKF_BATCH_GROUPS_MAX;
             G = std::max(1, std::min(std::min(G, SRUKF_BATCH_GROUPS_MAX), nb / 2));
             for (int grp = 0; grp < G && rc == SRUKF_OK; grp++) {
                 const int b0 = (int)((long long)nb * grp / G), b1 = (int)((long long)nb * (grp + 1) / G);

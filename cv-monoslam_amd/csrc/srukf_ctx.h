@@ -13,6 +13,7 @@
 //   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip)
 //   srukf_patch.h     (through srukf_launch.h) the appearance record's sizes, the checked association's buffer layouts, the search kernels' shared front
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
+//   srukf_switches.h  where the switches of srukf_debug_set are stored: the process-wide struct g_sw, the per-filter DbgSwitches
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -28,6 +29,7 @@
 #include <mutex>
 #include <map>
 #include "srukf_launch.h"
+#include "srukf_switches.h"
 
 #define SRUKF_GRAPH_FRAMES 8
 #define SRUKF_MAX_TENANTS 4                                    // 4 x (1 pivot + 63 workers with two register tiles each) fill 256 CUs at N = 200
@@ -80,44 +82,11 @@ struct ArchiveState {
 // The per-filter switches, a part of the handle scope with a name of its own for one reason: ctx_retire gives the retiring context a copy in one assignment (see there)
 struct srukf_switches {
     int rank_aware = 1;                    // srukf_set_rank_aware
-    int debug_allow_mixed = 0;             // srukf_debug_allow_mixed: the tolerance study runs the mixed mode below its epsilon floor on purpose
     int debug_starve = 0;                  // srukf_debug_starve_workers: persistent launches start without their workers (tests of the fallback)
     bool split_off = false;                // a split-form pair of this filter was abandoned (its two launches did not run side by side — e.g. the branches of a captured
                                            // graph sharing a hardware queue): it keeps to the memory-tile instance of k_gmw_persist (read_fs; srukf_debug_get "split_off")
     bool use_graph = true;
-    // Measurement / test switches of srukf_debug_set (all default to the product path)
-    struct DbgSwitches {
-        int fused_motion = 2;              // "fused_motion": the replay's motion step — 0: its own launch (k_motion + k_project), 1: inside the projection launch
-                                           // (k_project_motion), 2: "table" mode where the rank-aware tail allows it (replay_motion_mode)
-        int f32_fuse = 1;                  // "f32_fuse": fp32 storage also runs in "fused tail" mode (rounding inside k_rank_expand<2> and the state update)
-        int table_perm = 1;                // "table_perm": "table" / "fused tail" mode also where the owners do not fold (k_syrk over the kept rows: N >= 300); 0: k_project_motion + k_pxy there
-        int tail_fuse = 1;                 // "tail_fuse": k_rank_expand also projects the next frame ("fused tail" mode); 0: k_project_table in front of every frame
-        int head_fold = 1;                 // "head_fold": exclusive rank-aware replay without the k_syrk launch (helper workgroups of the persistent launch)
-        int nullskip = 1;                  // "nullskip": with pxy2, structurally null directions are projected for their own landmark only (NullSkip)
-        int pxy2 = 1;                      // "pxy2": "table" mode forms the cross covariances on the permuted operands (k_pxy2); 0: k_pxy
-        int step_fuse_export = 1;          // "step_fuse_export": the step-wise fast path's results reach the host from the launches that form them (the statistics' final passes inside
-                                           // k_pxy2, the status + robot view from k_block_cov) instead of two k_export launches behind them (0: round 5's first form, for A/B)
-        int view_auto = 1;                 // "view_auto": a host that fetched srukf_get_frame_view after its last update gets the view exported with the next update's status (0: never)
-        int step_early = 2;                // "step_early": the update submits the next frame's checkpoint copy and (announced odometry) its k_set_step behind its own last launch (0: the predict
-                                           // does), 2: and that frame's first launch, k_pxy2, too — srukf_predict_motion for the announced pair then has nothing left to submit
-                                           // (the statistics as a launch of their own in front of it were tried: alone they still take 16 us — eight dependent memory round trips —, and
-                                           //  16 + 25 us of launches lose to 25 us + the 12-us round trip they were meant to hide)
-        int step_spin = 1;                 // "step_spin": the step-wise fast path waits for its two exports by spinning on a pinned flag word (0: hipStreamSynchronize)
-        int step_fast = 1;                 // "step_fast": 0: the step-wise API keeps to its own launch sequences (k_motion, k_project, k_meas_*, k_pxy, ...: round 4's path)
-        int split_record = 0;              // "split_record": every split-form factorisation first copies its input matrix to Gbak (scripts/split_replay.py)
-        int null_canon = 1;                // "null_canon": a factor of the library's own making that was not produced by a rank-aware tail (NEED_REORDER, map changes) gets its null rows rewritten as sqrt(EPSILON) e_k at once
-        int split_fold = 1;                // "split_fold": the split form's tile launch forms the tiles of S^T S - U U^T itself (k_gmw_tiles_fold), k_syrk in front keeps block row 0; 0: k_syrk forms everything first
-        int gain_fold = 0;                 // "gain_fold": the staged replay's "fused tail" frames form U^T and the state update in the tile epilogue of k_pxy2 (three launches per frame); 0: k_gain
-        int mixed_rank = 1;                // "mixed_rank": SRUKF_STORAGE_F32_MIXED runs the rank-aware refactorisation (fp32-formed S^T S - U U^T over the kept rows, FP64 factorisation
-                                           // of the kept pivots only); 0: round 2's full-rank form, in which the null pivots divide fp32 noise (the negative study of rounds 2 / 5)
-        int mixed_null_ppm = 1;            // "mixed_null_ppm": ... and its null-direction check allows this many 1e-6 of G_aa on top of 1e-12 (an fp32-formed G cannot resolve 1e-12)
-        int mixed_bf16 = 0;                // "mixed_bf16": 1: the fp32 products from three bf16 pieces per operand on the bf16 matrix pipe (k_syrk_bf3) instead of the fp32 pipe
-                                           // (k_syrk32).  Built and measured in round 6 (N = 500): 168 us + 2 x 19 us of splitting against 187 us + 2 x 9 us of conversion —
-                                           // no gain: at one workgroup per CU (the FP64 accumulators beside the fp32 ones: 256 + 65 registers) every 32-row slab waits for its
-                                           // operands (~1 us of load latency against 0.64 us of matrix work), so neither form is bound by its matrix pipe; and its error is
-                                           // 1.6 x the fp32 pipe's (12.5 against 7.7 eps32 units over fixture g9).  Kept behind the switch, held to the same fixture
-        int mixed_f64_robot = 1;           // "mixed_f64_robot": ... with the tiles of the robot block and of the shared anchor in FP64 (mxr_f64_tiles); 0: every kept tile from the fp32 pipe (study)
-    } dbg;
+    DbgSwitches dbg;                       // the measurement / test switches of srukf_debug_set (srukf_switches.h)
 };
 
 // Handle scope: what stays at the caller's address through every map change.  A context built for another map size (ctx_obtain) carries a handle scope too: its own
@@ -330,10 +299,6 @@ inline bool storage_f32_like(const srukf_ctx* c) { return c->storage == SRUKF_ST
 
 extern const char* const kclass_name[KC_COUNT];
 extern thread_local std::string g_create_error;
-// srukf_debug_set switches (process-wide; srukf_debug.hip)
-extern std::atomic<int> g_dbg_gmw_persist, g_dbg_gmw_fused, g_dbg_rank_fused, g_dbg_rank_fold, g_dbg_rank_aware, g_dbg_graphs, g_dbg_mem_split, g_dbg_shared_tenants;
-extern std::atomic<int> g_dbg_batch_wide, g_dbg_batch_groups, g_dbg_batch_split, g_dbg_head_fold_free;
-extern std::atomic<int> g_dbg_timing, g_dbg_fold_head, g_dbg_fold_force, g_dbg_ctx_keep, g_dbg_batch_xcd, g_dbg_batch_k128;      // process-wide measurement switches (srukf_debug_set(0, "timing" / "fold_head" / "fold_force", v)): the library reads no environment variable
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -457,11 +422,9 @@ void seq_predict_motion(srukf_ctx* c, const double* odo_pair_dev);
 void seq_predict_measurement(srukf_ctx* c, FrameForm ff);
 void shadow_rebuild(srukf_ctx* c);
 bool plan_persists(const srukf_ctx* c, const GmwPlan& gp);
-int gmw_persist_mode();
 int gate_limit(const srukf_ctx* c);
 bool replay_red_perm(const srukf_ctx* c);
 int replay_motion_mode(const srukf_ctx* c);
-int rank_fused_mode();
 void seq_refactor(srukf_ctx* c, const RefactorRequest& rq, FrameForm ff);
 int exact_repeat_begin(srukf_ctx* c, int frame, double* traj_base);
 void launch_gmw_fast(srukf_ctx* c, double* Gbuf, double* Sout, GmwPanels which);

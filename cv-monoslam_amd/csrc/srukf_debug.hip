@@ -2,36 +2,102 @@
 // primitives the parity tests call (srukf_gmw_host, srukf_project_host).
 
 #include "srukf_ctx.h"
+#include <climits>
 using namespace srukf_impl;
 
-// A/B switches of srukf_debug_set (process-wide; measurement and test knobs, all 1 in the product):
-//   gmw_persist  1 = one persistent launch per factorisation, 0 = one launch per 64-row panel
-//   gmw_fused    0 = the persistent launch reads every tile from G (k_syrk computes all of them)
-//   rank_fused   0 = the rank-aware form always goes through the full k_syrk + permutation pass
-//   rank_fold    0 = the owners never form their tiles themselves in the rank-aware replay (k_syrk over all kept rows instead)
-//   rank_aware   0 = no context looks for structurally null directions (per filter: srukf_set_rank_aware)
-//   graphs       0 = contexts created from now on launch eagerly (profilers with --pmc; per filter: key "use_graph")
-// (atomics: another thread's context may be launching while a switch is set; a switch applies to whatever is built or captured afterwards)
+// ---- the switches of srukf_debug_set: ONE row per key (storage: srukf_switches.h) ----
+// range: what is stored for a value v — SW_ONOFF: v ? 1 : 0; SW_CLAMP: the nearest value of lo..hi; SW_REFUSE: v, and outside lo..hi nothing (SRUKF_ERR_BAD_ARG).
+// after: what a change invalidates — SW_KEEP: nothing (the switch is read when something is built later); SW_DROP: the captured graphs and the step-wise chain of the
+// filter in hand (a process-wide key: if a filter was passed); SW_DROP_NULL_SET: ... and its null set is looked for again (update_null_set's result is the call's);
+// SW_DROP_VIEW: ... and 0 also forgets the cached display view; SW_DROP_BATCH: the captured graphs of every batch
+enum SwKind : unsigned char { SW_ONOFF, SW_CLAMP, SW_REFUSE };
+struct SwRange { SwKind kind; int lo, hi; };
+constexpr SwRange ONOFF{ SW_ONOFF, 0, 1 }, RAW{ SW_CLAMP, INT_MIN, INT_MAX }, FROM0{ SW_CLAMP, 0, INT_MAX };
+enum SwAfter : unsigned char { SW_KEEP, SW_DROP, SW_DROP_NULL_SET, SW_DROP_VIEW, SW_DROP_BATCH };
+struct SwitchRow {
+    const char* key;
+    std::atomic<int> ProcessSwitches::* proc;      // process-wide (ctx may be NULL): the member of g_sw
+    int DbgSwitches::* filt;                        // per filter: the member of c->dbg (both null: c->use_graph)
+    int def; SwRange range; SwAfter after;
+};
+#define SW_P(member) &ProcessSwitches::member, nullptr
+#define SW_F(member) nullptr, &DbgSwitches::member
+static const SwitchRow k_switches[] = {
+    // process-wide
+    { "gmw_persist", SW_P(gmw_persist), 1, ONOFF, SW_DROP },            // 0: one launch per 64-row panel instead of one persistent launch per factorisation
+    { "gmw_fused", SW_P(gmw_fused), 1, ONOFF, SW_DROP },                // 0: the persistent launch reads every tile from G (k_syrk computes all of them)
+    { "rank_fused", SW_P(rank_fused), 1, ONOFF, SW_DROP },              // 0: the rank-aware form always goes through the full k_syrk + permutation pass
+    { "rank_fold", SW_P(rank_fold), 1, ONOFF, SW_DROP },                // 0: the owners never form their tiles themselves in the rank-aware replay (k_syrk over all kept rows instead)
+    { "rank_aware", SW_P(rank_aware), 1, ONOFF, SW_DROP_NULL_SET },     // 0: no context looks for structurally null directions (per filter: srukf_set_rank_aware)
+    { "graphs", SW_P(graphs), 1, ONOFF, SW_DROP },                      // 0: contexts created from now on launch eagerly (profilers with --pmc; per filter: "use_graph")
+    { "mem_split", SW_P(mem_split), 1, RAW, SW_DROP },                  // 0: sizes beyond two tiles per worker keep the memory-tile instance of k_gmw_persist instead of the split form; 2 (measurements): the split form also where the workers own two register tiles each
+    { "head_fold_free", SW_P(head_fold_free), 0, { SW_REFUSE, 1, INT_MAX }, SW_DROP },      // CUs a plan must leave beside the pivot and the workers for the head fold; 0: SRUKF_HEAD_FOLD_MIN_FREE_CUS and the rounds rule — the default, which cannot be set back (values below 1 are refused)
+    { "batch_split", SW_P(batch_split), 1, ONOFF, SW_DROP_BATCH },      // 0: one k_gmw_step64_b launch per panel in the batched replay (every tile recomputes its slabs) instead of slabs + plain updates
+    { "batch_k128", SW_P(batch_k128), 1, ONOFF, SW_DROP_BATCH },        // 0: every panel's trailing update a pass of its own over G (K = 64)
+    { "batch_xcd", SW_P(batch_xcd), 1, ONOFF, SW_DROP_BATCH },          // 0: k_syrk_b walks the head tiles in the solo launch's order
+    { "batch_wide", SW_P(batch_wide), 1, ONOFF, SW_KEEP },              // 0: srukf_run_frames_batch never takes the batched launches (one stream per filter, persistent launches behind the gate: round 3's form)
+    { "timing", SW_P(timing), 0, ONOFF, SW_KEEP },                      // 1: phases of map changes and of flagged frames on stderr
+    { "fold_force", SW_P(fold_force), 0, ONOFF, SW_KEEP },              // 1: split fold also where the tile workgroups do not all fit
+    { "pivot_relay", SW_P(pivot_relay), SRUKF_PIVOT_RELAY_DEFAULT, ONOFF, SW_KEEP },    // two pivot workgroups in the register-tile persistent launch; read when a plan is built
+    { "batch_groups", SW_P(batch_groups), 0, { SW_REFUSE, 0, SRUKF_BATCH_GROUPS_MAX }, SW_KEEP },       // groups the batched filters are cut into (0: as many as pay)
+    { "shared_tenants", SW_P(shared_tenants), 2, { SW_REFUSE, 2, 8 }, SW_KEEP },            // persistent launches that share the GPU, for filters switched to SRUKF_GPU_SHARED afterwards
+    { "fold_head", SW_P(fold_head), 0, FROM0, SW_KEEP },                // split fold: block rows formed in front of the pair (0: the rule); before the state is set
+    { "ctx_keep", SW_P(ctx_keep), 24, FROM0, SW_KEEP },                 // contexts a handle keeps across map changes (and at most ~16 GB of them)
+    { "exact_rl", SW_P(exact_rl), 1, RAW, SW_KEEP },                    // 0: k_gmw_col, the left-looking exact path (one row per launch); 1: right-looking, as many pivots per launch as fit; 1 + B: B pivots per launch
+    // per filter (their measurement notes: DbgSwitches)
+    { "use_graph", nullptr, nullptr, 1, ONOFF, SW_DROP },               // 0: eager launches
+    { "pxy2", SW_F(pxy2), 1, ONOFF, SW_DROP },                          // 0: k_pxy instead of k_pxy2 in "table" mode
+    { "nullskip", SW_F(nullskip), 1, ONOFF, SW_DROP },                  // 0: with pxy2, structurally null directions are projected for every landmark
+    { "head_fold", SW_F(head_fold), 1, ONOFF, SW_DROP },                // 0: k_syrk launch in front of the persistent launch
+    { "tail_fuse", SW_F(tail_fuse), 1, ONOFF, SW_DROP },                // 0: k_project_table in front of every frame
+    { "table_perm", SW_F(table_perm), 1, ONOFF, SW_DROP },              // 0: k_project_motion + k_pxy where the owners do not fold
+    { "f32_fuse", SW_F(f32_fuse), 1, ONOFF, SW_DROP },                  // 0: fp32 storage stays out of "fused tail" mode
+    { "split_record", SW_F(split_record), 0, ONOFF, SW_DROP },          // 1: every split-form factorisation first copies its input matrix to Gbak
+    { "gain_fold", SW_F(gain_fold), 0, ONOFF, SW_DROP },                // 1: U^T and the state update in the tile epilogue of k_pxy2 instead of k_gain
+    { "null_canon", SW_F(null_canon), 1, ONOFF, SW_DROP },              // 0: null rows that NEED_REORDER or a map change produced wait for a frame tail
+    { "mixed_rank", SW_F(mixed_rank), 1, ONOFF, SW_DROP },              // 0: round 2's full-rank form of SRUKF_STORAGE_F32_MIXED
+    { "mixed_f64_robot", SW_F(mixed_f64_robot), 1, ONOFF, SW_DROP },    // 0: every tile of the mixed downdate on the fp32 pipe
+    { "mixed_bf16", SW_F(mixed_bf16), 0, ONOFF, SW_DROP },              // 1: the mixed downdate's fp32 products from three bf16 pieces
+    { "step_fast", SW_F(step_fast), 1, ONOFF, SW_DROP },                // 0: the step-wise API keeps to its own launch sequences
+    { "step_spin", SW_F(step_spin), 1, ONOFF, SW_DROP },                // 0: hipStreamSynchronize instead of spinning on the pinned flag word
+    { "step_fuse_export", SW_F(step_fuse_export), 1, ONOFF, SW_DROP },  // 0: the fast path's results leave through export launches of their own
+    { "view_auto", SW_F(view_auto), 1, ONOFF, SW_DROP_VIEW },           // 0: the display view is never exported with an update's status
+    { "split_fold", SW_F(split_fold), 1, { SW_CLAMP, 0, 2 }, SW_DROP },     // 0: k_syrk forms everything in front of the split form's pair; 2 (measurements): the fold's launch behind a k_syrk that has formed everything
+    { "step_early", SW_F(step_early), 2, { SW_CLAMP, 0, 2 }, SW_DROP },     // what srukf_update submits of the next frame: 0 nothing, 1 checkpoint copy + frame scalars, 2 also its first launch
+    { "fused_motion", SW_F(fused_motion), 2, { SW_CLAMP, 0, 2 }, SW_DROP }, // the replay's motion step: 0 k_motion + k_project, 1 k_project_motion, 2 "table" mode
+    { "mixed_null_ppm", SW_F(mixed_null_ppm), 1, FROM0, SW_DROP },      // 1e-6 of G_aa the mixed mode's null-direction check allows on top of 1e-12
+};
+#undef SW_P
+#undef SW_F
+static int switch_value(const SwitchRow& r, const srukf_ctx* c) { return r.proc ? (g_sw.*r.proc).load() : r.filt ? c->dbg.*r.filt : c->use_graph ? 1 : 0; }
 
-// Diagnostic copy of a device work buffer (synchronises the stream): "Z" (L x mp), "DZ" (np x mp), "sigR" ((L + 1) x 8), "Cmat" (n x 4),
-// "Xr1" (4), "Utp" / "P1" (mp x np), "h" (2N), "Si" (4N).  count doubles from the start of the buffer.
-namespace srukf_impl {
-std::atomic<int> g_dbg_gmw_persist{1}, g_dbg_gmw_fused{1}, g_dbg_rank_fused{1}, g_dbg_rank_fold{1}, g_dbg_rank_aware{1}, g_dbg_graphs{1};
-std::atomic<int> g_dbg_mem_split{1};          // "mem_split" 0: sizes beyond two tiles per worker keep the memory-tile instance of k_gmw_persist instead of the split form; 2 (measurements): also
-                                              // the plans whose workers own two register tiles each
-std::atomic<int> g_dbg_shared_tenants{2};     // "shared_tenants": persistent launches that share the GPU after srukf_set_exclusive(SRUKF_GPU_SHARED)
-// srukf_run_frames_batch: "batch_wide" 0: never the batched launches (one stream per filter, persistent launches behind the gate: round 3's form); "batch_groups": groups the batched
-// filters are cut into (0: as many as pay); "batch_split" 0: one k_gmw_step64_b launch per panel (every tile recomputes its slabs) instead of slabs + plain updates
-std::atomic<int> g_dbg_batch_wide{1}, g_dbg_batch_groups{0}, g_dbg_batch_split{1};
-std::atomic<int> g_dbg_timing{0}, g_dbg_fold_head{0}, g_dbg_fold_force{0}, g_dbg_ctx_keep{24}, g_dbg_batch_xcd{1}, g_dbg_batch_k128{1};
-// "head_fold_free": CUs a plan must leave beside the pivot and the workers for the head fold (helper workgroups of the persistent launch); default SRUKF_HEAD_FOLD_MIN_FREE_CUS
-std::atomic<int> g_dbg_head_fold_free{0};
-}  // namespace srukf_impl
+// the filter at rest: its step-wise motion committed, its chain forgotten, its stream idle
+static int quiesce(srukf_ctx* c)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    step_commit_motion(c); step_invalidate(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SRUKF_OK;
+}
+// the plan the next frame's factorisation runs on
+static const GmwPlan& frame_plan(const srukf_ctx* c) { return c->red_r > 0 ? c->gplan_red : c->gplan; }
+// word `word` of that plan's sync block pad, cleared by the read (0 where the plan has no sync block)
+static int take_pad_word(srukf_ctx* c, int word, long long* value)
+{
+    const GmwPlan& gp = frame_plan(c);
+    unsigned long long v = 0, zero = 0;
+    const size_t off = offsetof(GmwSync, pad) + 8 * (size_t)word;
+    if (gp.sync) { HIPCHK(c, hipMemcpy(&v, (char*)gp.sync + off, sizeof v, hipMemcpyDeviceToHost)); HIPCHK(c, hipMemcpy((char*)gp.sync + off, &zero, sizeof zero, hipMemcpyHostToDevice)); }
+    *value = (long long)v;
+    return SRUKF_OK;
+}
 
+// The device work buffers srukf_debug_copy / srukf_debug_upload know: "Z" (L x mp), "DZ" (np x mp), "sigR" ((L + 1) x 8), "Cmat" (n x 4),
+// "Xr1" (4), "Utp" / "P1" (mp x np), "h" (2N), "Si" (4N), ...
 static bool debug_buffer(srukf_ctx* c, const char* key, double** ptr, long long* cap)
 {
     const KDims& d = c->d;
-    const GmwPlan& gp = c->red_r > 0 ? c->gplan_red : c->gplan;
+    const GmwPlan& gp = frame_plan(c);
     double* src = nullptr; long long n = 0;
     if (!strcmp(key, "Z")) { src = c->Z; n = (long long)d.L * d.mp; }
     else if (!strcmp(key, "DZ")) { src = c->DZ; n = (long long)d.np * d.mp; }
@@ -63,88 +129,51 @@ static bool debug_buffer(srukf_ctx* c, const char* key, double** ptr, long long*
 
 extern "C" {
 
-// Tolerance study only (scripts/mixed_eps_study.py): lets srukf_set_storage accept SRUKF_STORAGE_F32_MIXED below epsilon 1e-9,
-// where it is known to diverge — that divergence is what the study documents.
-int srukf_debug_allow_mixed(srukf_ctx* c, int on)
-{
-    if (!c) return SRUKF_ERR_BAD_ARG;
-    c->debug_allow_mixed = on ? 1 : 0;
-    return SRUKF_OK;
-}
+// Kept for ABI compatibility and for the study scripts that still call it (rounds 2 - 5: let srukf_set_storage accept SRUKF_STORAGE_F32_MIXED below its then
+// epsilon floor): no effect since round 6.
+int srukf_debug_allow_mixed(srukf_ctx* c, int on) { return c ? SRUKF_OK : SRUKF_ERR_BAD_ARG; }
 
-// Tests only: persistent factorisation launches of this context start WITHOUT their worker workgroups, as if another
-// process held the GPU — exercises the bounded waits and the fallback to per-panel launches.
 // Test hook: S[row][col] = value on the device, behind the back of everything that tracks S (the null set of the rank-aware
 // refactorisation, the permuted copy): the next frame has to notice by itself.
 int srukf_debug_poke_state(srukf_ctx* c, int row, int col, double value)
 {
     if (!c || row < 0 || col < row || col >= c->d.n) return SRUKF_ERR_BAD_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    step_commit_motion(c); step_invalidate(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (const int rc = quiesce(c)) return rc;
     HIPCHK(c, hipMemcpy(c->S + (size_t)row * c->d.np + col, &value, sizeof(double), hipMemcpyHostToDevice));
     return SRUKF_OK;
 }
 
-// Measurement / test switches behind ONE entry point (none of them is needed to use the library; all default to the product
-// path).  ctx may be NULL for the process-wide keys listed above g_dbg_*; per-context keys: "use_graph" (0: eager launches),
-// "fused_motion" (0: the replay keeps k_motion and k_project as two launches).  Captured graphs are dropped.
+// Measurement / test switches behind ONE entry point: the row of k_switches the key names says what is stored and what the change invalidates.
 int srukf_debug_set(srukf_ctx* c, const char* key, int value)
 {
     if (!key) return SRUKF_ERR_BAD_ARG;
-    struct { const char* k; std::atomic<int>* v; } globals[] = { { "gmw_persist", &g_dbg_gmw_persist }, { "gmw_fused", &g_dbg_gmw_fused }, { "rank_fused", &g_dbg_rank_fused },
-                                                    { "rank_fold", &g_dbg_rank_fold }, { "rank_aware", &g_dbg_rank_aware }, { "graphs", &g_dbg_graphs }, { "mem_split", &g_dbg_mem_split }
-                                                  };
-    if (!strcmp(key, "batch_split")) { g_dbg_batch_split = value ? 1 : 0; batch_drop_all_graphs(); return SRUKF_OK; }
-    if (!strcmp(key, "head_fold_free")) { if (value < 1) return SRUKF_ERR_BAD_ARG; g_dbg_head_fold_free = value; if (c) { hipSetDevice(c->device); step_commit_motion(c); step_invalidate(c); hipStreamSynchronize(c->stream); drop_graphs(c); } return SRUKF_OK; }
-    if (!strcmp(key, "pivot_relay")) { srukf_gmw_set_pivot_relay(value); return SRUKF_OK; }       // two pivot workgroups in the register-tile persistent launch; read when a plan is built
-    if (!strcmp(key, "batch_groups")) { if (value < 0 || value > SRUKF_BATCH_GROUPS_MAX) return SRUKF_ERR_BAD_ARG; g_dbg_batch_groups = value; return SRUKF_OK; }
-    if (!strcmp(key, "batch_wide")) { g_dbg_batch_wide = value ? 1 : 0; return SRUKF_OK; }
-    if (!strcmp(key, "timing")) { g_dbg_timing = value ? 1 : 0; return SRUKF_OK; }              // phases of map changes and of flagged frames on stderr
-    if (!strcmp(key, "fold_head")) { g_dbg_fold_head = value < 0 ? 0 : value; srukf_gmw_fold_head_override(g_dbg_fold_head); return SRUKF_OK; }   // split fold: block rows formed in front of the pair (0: the rule); before the state is set
-    if (!strcmp(key, "batch_k128")) { g_dbg_batch_k128 = value ? 1 : 0; batch_drop_all_graphs(); return SRUKF_OK; }    // 0: every panel's trailing update a pass of its own over G (K = 64)
-    if (!strcmp(key, "batch_xcd")) { g_dbg_batch_xcd = value ? 1 : 0; batch_drop_all_graphs(); return SRUKF_OK; }      // 0: k_syrk_b walks the head tiles in the solo launch's order
-    if (!strcmp(key, "ctx_keep")) { g_dbg_ctx_keep = value < 0 ? 0 : value; return SRUKF_OK; }       // contexts a handle keeps across map changes (default 24, and at most ~16 GB of them)
-    if (!strcmp(key, "fold_force")) { g_dbg_fold_force = value ? 1 : 0; return SRUKF_OK; }         // split fold also where the tile workgroups do not all fit
-    if (!strcmp(key, "exact_rl")) { srukf_set_exact_right_looking(value); return SRUKF_OK; }      // 0: k_gmw_col, the left-looking exact path (one row per launch)
-    if (!strcmp(key, "shared_tenants")) {                      // applies to filters switched to SRUKF_GPU_SHARED afterwards
-        if (value < 2 || value > 8) return SRUKF_ERR_BAD_ARG;
-        g_dbg_shared_tenants = value;
-        return SRUKF_OK;
+    const SwitchRow* r = std::find_if(std::begin(k_switches), std::end(k_switches), [key](const SwitchRow& s) { return !strcmp(s.key, key); });
+    if (r == std::end(k_switches)) { if (c) c->err = std::string("srukf_debug_set: unknown key ") + key; return SRUKF_ERR_BAD_ARG; }
+    if (!r->proc && !c) return SRUKF_ERR_BAD_ARG;
+    const SwRange& g = r->range;
+    if (g.kind == SW_ONOFF) value = value ? 1 : 0;
+    else if (value < g.lo || value > g.hi) { if (g.kind == SW_REFUSE) return SRUKF_ERR_BAD_ARG; value = value < g.lo ? g.lo : g.hi; }
+    // a filter's own switch changes while the filter is at rest; a process-wide one at once (another thread's filter sees it when it builds or captures next)
+    if (!r->proc) { if (const int rc = quiesce(c)) return rc; }
+    if (r->proc) (g_sw.*r->proc).store(value); else if (r->filt) c->dbg.*r->filt = value; else c->use_graph = value != 0;
+    if (r->after == SW_DROP_VIEW && !value) { c->view_auto = false; c->view_cached = false; }
+    if (r->after == SW_DROP_BATCH) batch_drop_all_graphs();
+    else if (r->after != SW_KEEP && c) {
+        if (r->proc) quiesce(c);
+        drop_graphs(c);
+        if (r->after == SW_DROP_NULL_SET) return update_null_set(c);
     }
-    for (auto& g : globals)
-        if (!strcmp(key, g.k)) {
-            g.v->store(!strcmp(key, "mem_split") ? value : (value ? 1 : 0));
-            if (c) { hipSetDevice(c->device); step_commit_motion(c); step_invalidate(c); hipStreamSynchronize(c->stream); drop_graphs(c); if (!strcmp(key, "rank_aware")) return update_null_set(c); }
-            return SRUKF_OK;
-        }
-    if (!c) return SRUKF_ERR_BAD_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    step_commit_motion(c); step_invalidate(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!strcmp(key, "use_graph")) c->use_graph = value != 0;
-    else if (!strcmp(key, "pxy2")) c->dbg.pxy2 = value ? 1 : 0;
-    else if (!strcmp(key, "nullskip")) c->dbg.nullskip = value ? 1 : 0;
-    else if (!strcmp(key, "head_fold")) c->dbg.head_fold = value ? 1 : 0;
-    else if (!strcmp(key, "tail_fuse")) c->dbg.tail_fuse = value ? 1 : 0;
-    else if (!strcmp(key, "table_perm")) c->dbg.table_perm = value ? 1 : 0;
-    else if (!strcmp(key, "f32_fuse")) c->dbg.f32_fuse = value ? 1 : 0;
-    else if (!strcmp(key, "split_record")) c->dbg.split_record = value ? 1 : 0;
-    else if (!strcmp(key, "gain_fold")) c->dbg.gain_fold = value ? 1 : 0;
-    else if (!strcmp(key, "null_canon")) c->dbg.null_canon = value ? 1 : 0;
-    else if (!strcmp(key, "split_fold")) c->dbg.split_fold = value < 0 ? 0 : value > 2 ? 2 : value;      // (2: measurements — the fold's launch behind a k_syrk that has formed everything)
-    else if (!strcmp(key, "mixed_rank")) c->dbg.mixed_rank = value ? 1 : 0;
-    else if (!strcmp(key, "mixed_f64_robot")) c->dbg.mixed_f64_robot = value ? 1 : 0;
-    else if (!strcmp(key, "mixed_bf16")) c->dbg.mixed_bf16 = value ? 1 : 0;
-    else if (!strcmp(key, "mixed_null_ppm")) c->dbg.mixed_null_ppm = value < 0 ? 0 : value;
-    else if (!strcmp(key, "step_fast")) c->dbg.step_fast = value ? 1 : 0;
-    else if (!strcmp(key, "step_spin")) c->dbg.step_spin = value ? 1 : 0;
-    else if (!strcmp(key, "step_early")) c->dbg.step_early = value < 0 ? 0 : value > 2 ? 2 : value;
-    else if (!strcmp(key, "view_auto")) { c->dbg.view_auto = value ? 1 : 0; if (!value) { c->view_auto = false; c->view_cached = false; } }
-    else if (!strcmp(key, "step_fuse_export")) c->dbg.step_fuse_export = value ? 1 : 0;
-    else if (!strcmp(key, "fused_motion")) c->dbg.fused_motion = value < 0 ? 0 : value > 2 ? 2 : value;
-    else { c->err = std::string("srukf_debug_set: unknown key ") + key; return SRUKF_ERR_BAD_ARG; }
-    drop_graphs(c);
+    return SRUKF_OK;
+}
+
+int srukf_debug_switch_at(srukf_ctx* c, int index, const char** key, int* per_filter, int* default_value, int* value)
+{
+    if (index < 0 || index >= (int)(sizeof k_switches / sizeof k_switches[0])) return SRUKF_ERR_BAD_ARG;
+    const SwitchRow& r = k_switches[index];
+    if (key) *key = r.key;
+    if (per_filter) *per_filter = r.proc ? 0 : 1;
+    if (default_value) *default_value = r.def;
+    if (value) *value = r.proc || c ? switch_value(r, c) : r.def;
     return SRUKF_OK;
 }
 
@@ -158,7 +187,7 @@ int srukf_debug_gmw_stamps(srukf_ctx* c, unsigned long long* buf)
     static unsigned long long* dbuf = nullptr;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    GmwPlan& g = c->red_r > 0 ? c->gplan_red : c->gplan;
+    const GmwPlan& g = frame_plan(c);
     if (!g.sync) return SRUKF_ERR_SEQUENCE;
     if (!dbuf) { HIPCHK(c, hipMalloc((void**)&dbuf, 8 * 4096)); HIPCHK(c, hipMemset(dbuf, 0, 8 * 4096)); }
     if (buf) HIPCHK(c, hipMemcpy(buf, dbuf, 8 * 4096, hipMemcpyDeviceToHost));
@@ -182,24 +211,10 @@ int srukf_debug_get(srukf_ctx* c, const char* key, long long* value)
     else if (!strcmp(key, "gmw_shared")) *value = c->gmw_shared;
     else if (!strcmp(key, "split_off")) *value = c->split_off ? 1 : 0;
     else if (!strcmp(key, "use_graph")) *value = c->use_graph ? 1 : 0;
-    else if (!strncmp(key, "pad", 3) && key[3] >= '1' && key[3] <= '7' && !key[4]) {
-        // diagnostic builds (-DSRUKF_GMW_DBG): words 1..7 of the sync block's pad (helpers started / finished, head counters at the last exit, grid, helpers); cleared by the read
-        const GmwPlan& gp = c->red_r > 0 ? c->gplan_red : c->gplan;
-        unsigned long long v = 0, zero = 0;
-        const size_t off = offsetof(GmwSync, pad) + 8 * (size_t)(key[3] - '0');
-        if (gp.sync) { HIPCHK(c, hipMemcpy(&v, (char*)gp.sync + off, sizeof v, hipMemcpyDeviceToHost)); HIPCHK(c, hipMemcpy((char*)gp.sync + off, &zero, sizeof zero, hipMemcpyHostToDevice)); }
-        *value = (long long)v;
-    }
-    else if (!strcmp(key, "abort_code")) {
-        // who abandoned a persistent launch first, and where (gmw_abandon, srukf_gmw_persist.hip: site << 32 | blockIdx + 1; 0: nobody since the last read); cleared by the read
-        const GmwPlan& gp = c->red_r > 0 ? c->gplan_red : c->gplan;
-        unsigned long long code = 0, zero = 0;
-        if (gp.sync) {
-            HIPCHK(c, hipMemcpy(&code, (char*)gp.sync + offsetof(GmwSync, pad), sizeof code, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy((char*)gp.sync + offsetof(GmwSync, pad), &zero, sizeof zero, hipMemcpyHostToDevice));
-        }
-        *value = (long long)code;
-    }
+    // diagnostic builds (-DSRUKF_GMW_DBG): words 1..7 of the sync block's pad (helpers started / finished, head counters at the last exit, grid, helpers); cleared by the read
+    else if (!strncmp(key, "pad", 3) && key[3] >= '1' && key[3] <= '7' && !key[4]) return take_pad_word(c, key[3] - '0', value);
+    // who abandoned a persistent launch first, and where (gmw_abandon, srukf_gmw_persist.hip: site << 32 | blockIdx + 1; 0: nobody since the last read); cleared by the read
+    else if (!strcmp(key, "abort_code")) return take_pad_word(c, 0, value);
     else if (!strcmp(key, "step_fast")) *value = c->step_fast_frames;          // frames the step-wise API ran on the staged replay's launch sequence / on its own
     else if (!strcmp(key, "step_slow")) *value = c->step_slow_frames;
     else if (!strcmp(key, "exact_frames")) *value = c->exact_frames;
@@ -209,10 +224,10 @@ int srukf_debug_get(srukf_ctx* c, const char* key, long long* value)
     else if (!strcmp(key, "meas_flag_ticks")) { const unsigned long long* t = (const unsigned long long*)(c->hmeas + c->d.mp + 5 * (size_t)c->d.N); *value = (long long)(t[1] - t[0]); }   // last fast-path k_pxy2: first workgroup's start -> statistics flag, 10 ns ticks
     else if (!strcmp(key, "view_hits")) *value = c->view_hits;                     // srukf_get_frame_view calls served from the view an update exported with its status
     else if (!strcmp(key, "view_auto")) *value = c->view_auto ? 1 : 0;
-    else if (!strcmp(key, "split_form")) *value = split_form(c, c->red_r > 0 ? c->gplan_red : c->gplan) ? 1 : 0;       // would the next persistent factorisation be the split form?
+    else if (!strcmp(key, "split_form")) *value = split_form(c, frame_plan(c)) ? 1 : 0;       // would the next persistent factorisation be the split form?
     else if (!strncmp(key, "plan_", 5)) {
         // which launch plan the next staged frame takes (tests assert it next to the oracle comparison: every N is a product size, SLAM.cpp:552-562, 2443-2460)
-        const GmwPlan& gp = c->red_r > 0 ? c->gplan_red : c->gplan;
+        const GmwPlan& gp = frame_plan(c);
         const RefactorPlan rp = refactor_form(c, refactor_frame_tail(c));
         const bool persist = plan_persists(c, gp);
         const char* k = key + 5;
@@ -239,30 +254,24 @@ int srukf_debug_get(srukf_ctx* c, const char* key, long long* value)
     return SRUKF_OK;
 }
 
-int srukf_debug_copy(srukf_ctx* c, const char* key, double* out, long long count)
+// Diagnostic copy of a device work buffer (synchronises the stream; the keys: debug_buffer): `count` doubles from the start of the buffer, in either direction
+static int debug_transfer(srukf_ctx* c, const char* key, double* host, long long count, hipMemcpyKind kind)
 {
-    if (!c || !key || !out || count < 0) return SRUKF_ERR_BAD_ARG;
+    if (!c || !key || !host || count < 0) return SRUKF_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    double* src = nullptr; long long cap = 0;
-    if (!debug_buffer(c, key, &src, &cap)) return SRUKF_ERR_BAD_ARG;
-    if (!src || count > cap) return SRUKF_ERR_DIM_MISMATCH;
-    HIPCHK(c, hipMemcpy(out, src, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
+    double* dev = nullptr; long long cap = 0;
+    if (!debug_buffer(c, key, &dev, &cap)) return SRUKF_ERR_BAD_ARG;
+    if (!dev || count > cap) return SRUKF_ERR_DIM_MISMATCH;
+    const bool up = kind == hipMemcpyHostToDevice;
+    HIPCHK(c, hipMemcpy(up ? dev : host, up ? host : dev, sizeof(double) * (size_t)count, kind));
     return SRUKF_OK;
 }
+int srukf_debug_copy(srukf_ctx* c, const char* key, double* out, long long count) { return debug_transfer(c, key, out, count, hipMemcpyDeviceToHost); }
+int srukf_debug_upload(srukf_ctx* c, const char* key, const double* in, long long count) { return debug_transfer(c, key, const_cast<double*>(in), count, hipMemcpyHostToDevice); }
 
-// the other direction (same keys): `count` doubles to the start of the buffer
-int srukf_debug_upload(srukf_ctx* c, const char* key, const double* in, long long count)
-{
-    if (!c || !key || !in || count < 0) return SRUKF_ERR_BAD_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    double* dst = nullptr; long long cap = 0;
-    if (!debug_buffer(c, key, &dst, &cap)) return SRUKF_ERR_BAD_ARG;
-    if (!dst || count > cap) return SRUKF_ERR_DIM_MISMATCH;
-    HIPCHK(c, hipMemcpy(dst, in, sizeof(double) * (size_t)count, hipMemcpyHostToDevice));
-    return SRUKF_OK;
-}
+// Tests only: persistent factorisation launches of this context start WITHOUT their worker workgroups, as if another
+// process held the GPU — exercises the bounded waits and the fallback to per-panel launches.
 
 int srukf_debug_starve_workers(srukf_ctx* c, int on)
 {
@@ -300,11 +309,11 @@ int srukf_gmw_host(int device, int n, const double* G, double* S_out, double* D_
     FrameScalars fs;
     if (!force_slow) {
         // the plan knows how many workgroups THIS device can keep resident (CU count); workers < 0: per-panel launches
-        if (gmw_persist_mode()) { const int rc = gmw_plan_create(r.gp, np, st); if (rc) return rc; }
+        if (g_sw.gmw_persist) { const int rc = gmw_plan_create(r.gp, np, st); if (rc) return rc; }
         // every panel pivoted, every row kept, no gate
         const GmwLaunch g = { .n = n, .ld = np, .eps = epsilon, .G = r.dG, .pans = r.gp.pans, .D = r.dD, .Sout = r.dS, .sync = r.gp.sync, .tiles = r.gp.tiles, .ntiles = r.gp.ntiles,
                               .workers = r.gp.workers, .fs = r.dFs, .Tp = 0, .krows = 0, .gate_limit = 0, .relay = r.gp.relay };
-        if (gmw_persist_mode() && r.gp.workers >= 0) {
+        if (g_sw.gmw_persist && r.gp.workers >= 0) {
             srukf_launch_gmw_persist(st, g, nullptr, nullptr);
         } else {
             GH(srukf_dmalloc(&r.pan[0], srukf_gmw_panel_bytes())); GH(srukf_dmalloc(&r.pan[1], srukf_gmw_panel_bytes()));

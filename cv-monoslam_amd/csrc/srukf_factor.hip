@@ -16,6 +16,7 @@
 #include <vector>
 #include <algorithm>
 #include "srukf_launch.h"
+#include "srukf_switches.h"
 
 // A statistics job that rides on a contraction launch has stored its partial sums: the LAST of the MEAS_SLICES jobs of a landmark
 // group (device-scope counter per group) runs that group's final pass with its whole workgroup.  (One last workgroup for all
@@ -1170,10 +1171,6 @@ __global__ __launch_bounds__(256) void k_gmw_rl(int n, int ld, int j0, int B, do
         }
     }
 }
-static bool g_exact_right_looking = true;
-static int g_exact_rl_block = 0;                              // 0: as many pivots per launch as fit                     // srukf_debug_set(0, "exact_rl", 0): k_gmw_col (the left-looking form, one row per launch)
-void srukf_set_exact_right_looking(int on) { g_exact_right_looking = on != 0; g_exact_rl_block = on > 1 ? std::min(on - 1, GMW_RL_BMAX) : 0; }
-int srukf_get_exact_right_looking(void) { return g_exact_right_looking ? 1 : 0; }
 // The first launch of a kernel with more than 64 KB of dynamic LDS costs ~75 ms once per stream (measured: the first flagged frame at N = 200 took 82 ms, the others 6.5).
 // srukf_create pays it: an empty launch (n = 0: every thread leaves at once) with the largest panel the exact path asks for.
 void srukf_warm_exact_path(hipStream_t st, FrameScalars* fs)
@@ -1186,12 +1183,13 @@ void srukf_warm_exact_path(hipStream_t st, FrameScalars* fs)
 void srukf_launch_gmw_col(hipStream_t st, int n, int ld, int j, double eps, const double* G, double* Wf, double* D,
                           unsigned long long* theta_bits, FrameScalars* fs, double* Sout)
 {
-    if (g_exact_right_looking) {
+    const int rl = srukf_impl::g_sw.exact_rl;                // the switch "exact_rl": 0: k_gmw_col (the left-looking form, one row per launch), 1: right-looking, 1 + B: ... B pivots per launch
+    if (rl != 0) {
         // (callers loop j = 0 .. n - 1: the first call submits the whole sequence on a working copy of G, the others nothing)
         if (j != 0) return;
         hipMemcpyAsync(Wf, G, sizeof(double) * (size_t)ld * ld, hipMemcpyDeviceToDevice, st);
         // B pivots per launch: as many rows of n doubles as fit in ~144 KB of LDS, at most 8 (srukf_debug_set(0, "exact_rl", 1 + B) forces B: tests)
-        int B = g_exact_rl_block > 0 ? g_exact_rl_block : (int)std::min<size_t>(GMW_RL_BMAX, (144 * 1024) / (sizeof(double) * (size_t)n));
+        int B = rl > 1 ? std::min(rl - 1, GMW_RL_BMAX) : (int)std::min<size_t>(GMW_RL_BMAX, (144 * 1024) / (sizeof(double) * (size_t)n));
         if (B < 1) B = 1;
         { static bool attr2 = false; if (!attr2) { (void)hipFuncSetAttribute((const void*)k_gmw_rl, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr2 = true; } }
         for (int q = 0; q < n; q += B) {

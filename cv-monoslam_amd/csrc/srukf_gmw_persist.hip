@@ -15,6 +15,7 @@
 #include "srukf_gmw_pivot.h"
 #include "srukf_rank.h"
 #include "srukf_launch.h"
+#include "srukf_switches.h"
 
 // ------------------------------------------------------------------------------------------------
 // Persistent form: the whole factorisation in ONE launch (k_gmw_persist).
@@ -1183,9 +1184,6 @@ __global__ void k_gmw_split_gate(GmwSync* __restrict__ sy, const FrameScalars* _
 }
 
 extern "C" {
-#ifndef SRUKF_PIVOT_RELAY_DEFAULT
-#define SRUKF_PIVOT_RELAY_DEFAULT 1      // measured (docs/LAB_NOTEBOOK.md, pivot relay): N = 100 +5 %, N = 200 +1.2 %, N = 300 +4.8 % frames/s
-#endif
 int srukf_gmw_sync_bytes(int T) { return (int)(sizeof(GmwSync) + 3 * sizeof(unsigned long long) * (size_t)T * T * GMW_VER_STRIDE); }
 // host-side tile list of the persistent launch: every tile (I, J), 1 <= I <= J < T, with the number of panel updates
 // its owner applies (I off the diagonal; I - 1 on it: the pivot applies the last one itself), ordered by the step at
@@ -1205,11 +1203,9 @@ int srukf_gmw_build_tiles(int T, int Tp, short* out)
         }
     return cnt;
 }
-// workers the persistent launch needs for T block rows (each owns at most GMW_OWNED_MAX tiles); -1: too many tiles
 // pivot relay: process-wide switch (srukf_debug_set(0, "pivot_relay", v)), read when a plan is built
-static int g_pivot_relay = SRUKF_PIVOT_RELAY_DEFAULT;
-void srukf_gmw_set_pivot_relay(int v) { g_pivot_relay = v ? 1 : 0; }
-int srukf_gmw_get_pivot_relay(void) { return g_pivot_relay; }
+int srukf_gmw_get_pivot_relay(void) { return srukf_impl::g_sw.pivot_relay; }
+// workers the persistent launch needs for T block rows (each owns at most GMW_OWNED_MAX tiles); -1: too many tiles
 int srukf_gmw_persist_workers(int T, int Tp, int max_workers)
 {
     const int nt = srukf_gmw_build_tiles(T, Tp, nullptr);
@@ -1297,12 +1293,10 @@ void srukf_launch_gmw_split_alone(hipStream_t st, int which, const GmwLaunch& gl
 // forming inside the pair is worth less than forming in front of it (the jobs share SIMDs and places with the tile workgroups: §10 of DESIGN.md) and the more so the
 // fuller the machine is with tile workgroups: frames/s by head rows — N = 400 (Tp = 19): 1 2 168, 4 2 188, 8 2 130, 12 2 058 (all in front: 1 958); N = 450 (Tp = 22): 1 1 682,
 // 4 1 702, 8 1 712, 10 1 720, 14 1 686 (1 587); N = 500 (Tp = 24, fp32 storage): 1 1 370, 4 1 394, 10 1 426, 12 1 433, 14 1 450, 16 1 440, 18 1 420 (1 342).  2 (Tp - 17) fits the three.
-static int g_fold_head_override = 0;
-void srukf_gmw_fold_head_override(int v) { g_fold_head_override = v; }
 int srukf_gmw_fold_head_rows(int Tp)
 {
-    int v = 2 * (Tp - 17);
-    if (g_fold_head_override > 0) v = g_fold_head_override;                          // (measurements: srukf_debug_set(0, "fold_head", v))
+    const int forced = srukf_impl::g_sw.fold_head;                                   // (measurements: srukf_debug_set(0, "fold_head", v))
+    const int v = forced > 0 ? forced : 2 * (Tp - 17);
     return std::max(1, std::min(v, Tp - 4));
 }
 int srukf_gmw_fold_head_tile(int tr, int tc, int head_rows) { return (tr < 2 * head_rows || (tr < 4 && tc < 4)) ? 1 : 0; }

@@ -1,5 +1,5 @@
-// srukf_launch.h — what the kernel files offer the host layer, declared ONCE: every srukf_launch_* launcher, the size / table / list helpers, the process-wide
-// switches of the kernel files.  Included by srukf_ctx.h (the callers) and, behind their own headers, by the eight files that define these functions (srukf_predict,
+// srukf_launch.h — what the kernel files offer the host layer, declared ONCE: every srukf_launch_* launcher, the size / table / list helpers (the process-wide
+// switches their host code reads are members of g_sw, srukf_switches.h).  Included by srukf_ctx.h (the callers) and, behind their own headers, by the eight files that define these functions (srukf_predict,
 // srukf_factor, srukf_gmw_persist, srukf_rank, srukf_mixed, srukf_augment, srukf_assoc, srukf_unique): linkage is C, so only the compiler can compare a declaration
 // with its definition, and it does so in the file that defines it.  A function of this kind is declared here and nowhere else (tests/test_host.py holds the tree to it).
 // srukf_joint.hip's launchers (launch_joint_*, C++ linkage) are declared at the end.
@@ -97,8 +97,6 @@ void srukf_launch_pxy2_b(hipStream_t st, KDims d, const Pxy2Args* tab, int B, co
 void srukf_launch_syrk_b(hipStream_t st, KDims d, const SyrkArgs* tab, int B, const int* tiles, int ntiles, int krows, int ndx, int ngd);
 void srukf_launch_gmw_step64_b(hipStream_t st, int n, int ld, int j0, double eps, const Step64Args* tab, int B, int rows, int flip);
 void srukf_launch_gmw_check(hipStream_t st, int n, int ld, const double* D, const double* S, FrameScalars* fs, const double* X, int do_traj, double* Scopy);
-void srukf_set_exact_right_looking(int on);
-int srukf_get_exact_right_looking(void);
 void srukf_warm_exact_path(hipStream_t st, FrameScalars* fs);
 void srukf_launch_gmw_col(hipStream_t st, int n, int ld, int j, double eps, const double* G, double* Wf, double* D, unsigned long long* theta_bits, FrameScalars* fs, double* Sout);
 void srukf_launch_gmw_stats(hipStream_t st, int n, int ld, const double* G, FrameScalars* fs);
@@ -106,7 +104,6 @@ void srukf_launch_gmw_stats(hipStream_t st, int n, int ld, const double* G, Fram
 // ---- srukf_gmw_persist.hip ----
 int srukf_gmw_sync_bytes(int T);
 int srukf_gmw_build_tiles(int T, int Tp, short* out);
-void srukf_gmw_set_pivot_relay(int v);
 int srukf_gmw_get_pivot_relay(void);
 int srukf_gmw_persist_workers(int T, int Tp, int max_workers);
 int srukf_gmw_register_form(int T, int Tp, int ntiles, int workers);
@@ -119,7 +116,6 @@ void srukf_launch_gmw_split(hipStream_t stA, hipStream_t stB, const GmwLaunch& g
 void srukf_launch_gmw_split_alone(hipStream_t st, int which, const GmwLaunch& g, double* Wslab, double* Lslab);
 // ... whose tile launch forms tiles too: list / nlist = its grid (srukf_gmw_build_fold_list) in place of g.tiles, A / Ut (mp rows) = the operands k_syrk would have read
 void srukf_launch_gmw_split_fold(hipStream_t stA, hipStream_t stB, const GmwLaunch& g, double* Wslab, double* Lslab, const GmwTile* list, int nlist, const double* A, const double* Ut, int mp);
-void srukf_gmw_fold_head_override(int v);
 int srukf_gmw_fold_head_rows(int Tp);
 int srukf_gmw_fold_head_tile(int tr, int tc, int head_rows);
 int srukf_gmw_build_fold_list(int T, int Tp, short* out);

@@ -12,7 +12,7 @@ using namespace srukf_impl;
 namespace {
 struct MapTimer {
     bool on; const char* what; std::chrono::steady_clock::time_point t0, tl; std::string line;
-    explicit MapTimer(const char* w) : on(g_dbg_timing.load() != 0), what(w), t0(std::chrono::steady_clock::now()), tl(t0) {}
+    explicit MapTimer(const char* w) : on(g_sw.timing.load() != 0), what(w), t0(std::chrono::steady_clock::now()), tl(t0) {}
     void mark(const char* label) {
         if (!on) return;
         const auto t = std::chrono::steady_clock::now();

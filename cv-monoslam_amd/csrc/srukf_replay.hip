@@ -160,8 +160,6 @@ void launch_commit_motion(hipStream_t st, int n, int ld, double* X, double* S, c
 void launch_sym_permute(hipStream_t st, int n, int ld, const double* src, int lds, double* dst, const int* map) { hipLaunchKernelGGL(k_sym_permute, dim3(ld), dim3(256), 0, st, n, ld, src, lds, dst, map); }
 void launch_gather(hipStream_t st, int n, int ld, const double* src, double* dst, const int* map) { hipLaunchKernelGGL(k_gather, dim3((ld + 255) / 256), dim3(256), 0, st, n, ld, src, dst, map); }
 
-int gmw_persist_mode() { return g_dbg_gmw_persist; }
-
 void quantize_state(srukf_ctx* c)
 {
     if (c->storage != SRUKF_STORAGE_F64) hipLaunchKernelGGL(k_quantize, dim3(c->d.n + 1), dim3(256), 0, c->stream, c->d.n, c->d.np, c->S, c->X, c->S32, c->X32);
@@ -235,8 +233,6 @@ void seq_predict_measurement(srukf_ctx* c, FrameForm ff)
     }
 }
 
-int rank_fused_mode() { return g_dbg_rank_fused; }
-
 void shadow_rebuild(srukf_ctx* c)
 {
     if (c->red_r > 0 && c->shadowA) srukf_launch_rank_shadow(c->stream, c->d.n, c->d.np, c->red_r, c->S, c->red_perm, c->shadowA);
@@ -244,7 +240,7 @@ void shadow_rebuild(srukf_ctx* c)
 
 // does a factorisation on plan gp run as persistent launch(es), or as one launch per 64-row panel?  (the filter at all: gmw_use_persist)
 static bool gmw_plan_persists(const srukf_ctx* c, const GmwPlan& gp) { return gp.workers >= 0 || split_form(c, gp, true); }
-static bool gmw_use_persist(const srukf_ctx* c) { return gmw_persist_mode() && c->gmw_shared != 2 && gmw_plan_persists(c, c->gplan); }
+static bool gmw_use_persist(const srukf_ctx* c) { return g_sw.gmw_persist && c->gmw_shared != 2 && gmw_plan_persists(c, c->gplan); }
 bool plan_persists(const srukf_ctx* c, const GmwPlan& gp) { return gmw_use_persist(c) && gmw_plan_persists(c, gp); }
 
 // SRUKF_GPU_SHARED: how many persistent launches share the GPU (each keeps to 1 / tenants of the CUs; the gate admits that many)
@@ -294,7 +290,7 @@ static bool replay_red_fused(const srukf_ctx* c)
 {
     return c->red_r > 0 && c->storage != SRUKF_STORAGE_F32_MIXED && c->shadowA && c->w.wc0 == c->w.wm0 && gmw_use_persist(c) &&
            c->gplan_red.workers >= 0 && c->gplan_red.nreal <= c->gplan_red.workers * fold_tiles_pct(c) / 100 && c->gplan_red.T >= 16 &&
-           !c->debug_starve && g_dbg_gmw_fused && rank_fused_mode() && g_dbg_rank_fold;
+           !c->debug_starve && g_sw.gmw_fused && g_sw.rank_fused && g_sw.rank_fold;
 }
 
 // RF_PERMUTED_SYRK as far as "table" mode may build on it ("table_perm" 0: the form runs, "table" mode does not); srukf_debug_get "plan_red_perm" reports THIS
@@ -340,11 +336,11 @@ static HeadJobs head_fold_jobs(const srukf_ctx* c) { return HeadJobs{ c->n_syrk_
 
 static bool head_fold_ok(const srukf_ctx* c)
 {
-    const int need = g_dbg_head_fold_free.load() > 0 ? g_dbg_head_fold_free.load() : SRUKF_HEAD_FOLD_MIN_FREE_CUS;
+    const int need = g_sw.head_fold_free.load() > 0 ? g_sw.head_fold_free.load() : SRUKF_HEAD_FOLD_MIN_FREE_CUS;
     const int free_cus = c->gplan_red.cus - (c->gplan_red.relay ? 2 : 1) - c->gplan_red.workers;      // what pivot(s) + workers really leave free
     const int nhelp = head_fold_jobs(c).total();
     // (the rounds rule was measured with one pivot workgroup and keeps counting that way: the relay's CU does not move the sizes at which the fold is taken)
-    const bool pays = g_dbg_head_fold_free.load() > 0 || 4 * nhelp <= 9 * (c->gplan_red.cus - 1 - c->gplan_red.workers);      // (the A/B switch "head_fold_free" overrides the rounds rule: measurements)
+    const bool pays = g_sw.head_fold_free.load() > 0 || 4 * nhelp <= 9 * (c->gplan_red.cus - 1 - c->gplan_red.workers);      // (the A/B switch "head_fold_free" overrides the rounds rule: measurements)
     return c->dbg.head_fold && c->gmw_shared == 0 && free_cus >= need && pays;
 }
 
@@ -355,7 +351,7 @@ static bool split_fold_ok(const srukf_ctx* c)
     // last update, and beyond that the forming jobs queue behind waiting workgroups — frames/s with / without the fold: N = 400 2 150 / 1 960, 500 1 385 / 1 350,
     // 600 (1 190 tile workgroups for 796 places) 855 / 893, 800 393 / 459.
     const GmwPlan& gp = c->gplan_red;
-    const bool fits = gp.nreal <= 4 * (gp.cus - gp.T) || g_dbg_fold_force.load() != 0;      // ("fold_force": measurements)
+    const bool fits = gp.nreal <= 4 * (gp.cus - gp.T) || g_sw.fold_force.load() != 0;      // ("fold_force": measurements)
     return c->dbg.split_fold && (fits || c->dbg.split_fold == 2) && c->red_r > 0 && c->storage != SRUKF_STORAGE_F32_MIXED && c->split_fold_list && c->n_split_fold > 0 && c->red_head0_tiles &&
            !c->debug_starve && !c->dbg.split_record && plan_persists(c, gp) && split_form(c, gp, true);
 }
@@ -370,11 +366,11 @@ RefactorPlan refactor_form(const srukf_ctx* c, const RefactorRequest& rq)
     const bool reduced = c->red_r > 0 && (c->storage != SRUKF_STORAGE_F32_MIXED || (c->dbg.mixed_rank && c->A32));
     if (tail && replay_red_fused(c)) {                           // (pays with about one tile per worker and T >= 16: docs/LAB_NOTEBOOK.md, round 2)
         p.form = RF_OWNERS_FOLD; p.persist = true; p.head_fold = head_fold_ok(c);
-    } else if (reduced && tail && c->shadowA && c->w.wc0 == c->w.wm0 && rank_fused_mode()) {
+    } else if (reduced && tail && c->shadowA && c->w.wc0 == c->w.wm0 && g_sw.rank_fused) {
         p.form = RF_PERMUTED_SYRK; p.persist = plan_persists(c, gr);
         // own order (a filter that shares the GPU, two register tiles per worker): head rows by k_syrk, every other tile by k_syrk_own in the owners' summation order —
         // bit for bit what the same filter computes alone.  (Memory tiles and launches per panel keep the split-K k_syrk over the kept rows: nothing to be identical to.)
-        p.own_order = c->gmw_shared == 1 && gmw_use_persist(c) && gr.workers > 0 && gr.T >= 16 && !c->debug_starve && g_dbg_gmw_fused && g_dbg_rank_fold &&
+        p.own_order = c->gmw_shared == 1 && gmw_use_persist(c) && gr.workers > 0 && gr.T >= 16 && !c->debug_starve && g_sw.gmw_fused && g_sw.rank_fold &&
                       srukf_gmw_register_form(gr.T, gr.Tp, gr.ntiles, gr.workers);
         p.split_fold = !p.own_order && split_fold_ok(c);
     } else if (reduced) {
@@ -382,7 +378,7 @@ RefactorPlan refactor_form(const srukf_ctx* c, const RefactorRequest& rq)
     } else {
         // fused only with one tile per worker and T >= 16 (frames/s fused / not: N = 200 2 965 / 2 910, N = 100 5 247 / 5 262, N = 50 9 256 / 9 465, N = 300 1 544 / 1 663)
         p.form = RF_FULL_RANK; p.persist = gmw_use_persist(c);
-        p.fused = tail && p.persist && c->storage == SRUKF_STORAGE_F64 && c->gplan.ntiles <= c->gplan.workers && c->gplan.T >= 16 && !c->debug_starve && g_dbg_gmw_fused;
+        p.fused = tail && p.persist && c->storage == SRUKF_STORAGE_F64 && c->gplan.ntiles <= c->gplan.workers && c->gplan.T >= 16 && !c->debug_starve && g_sw.gmw_fused;
     }
     return p;
 }
@@ -739,7 +735,7 @@ void seq_gain(srukf_ctx* c, const double* z_dev, const int* m_dev, FrameForm ff)
 
 int update_null_set(srukf_ctx* c)
 {
-    const int enabled = g_dbg_rank_aware;
+    const int enabled = g_sw.rank_aware;
     const int n = c->d.n, np = c->d.np, T = np / 64;
     const int was = c->red_r;
     step_invalidate(c);
@@ -1014,7 +1010,7 @@ static int run_staged_frame_exact(srukf_ctx* c, int frame, double* traj_row)
 {
     const KDims& d = c->d;
     c->exact_frames++;
-    const bool timing = g_dbg_timing.load() != 0;              // (srukf_debug_set(0, "timing", 1): where a flagged frame's milliseconds go, on stderr)
+    const bool timing = g_sw.timing.load() != 0;              // (srukf_debug_set(0, "timing", 1): where a flagged frame's milliseconds go, on stderr)
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t0 = now();
     auto lap = [&](const char* what) { if (timing) { hipStreamSynchronize(c->stream); auto t1 = now(); fprintf(stderr, "[exact frame] %s %.0f us\n", what, std::chrono::duration<double, std::micro>(t1 - t0).count()); t0 = t1; } };
@@ -1052,7 +1048,7 @@ int srukf_set_exclusive(srukf_ctx* c, int exclusive)
     HIPCHK(c, hipSetDevice(c->device));                         // the plans below size themselves on the CURRENT device's CU count
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int shared = exclusive == SRUKF_GPU_SHARED ? 1 : exclusive == SRUKF_GPU_SHARED_PER_PANEL ? 2 : 0;
-    return set_shared(c, shared, g_dbg_shared_tenants.load());
+    return set_shared(c, shared, g_sw.shared_tenants.load());
 }
 
 int srukf_stage_sequence(srukf_ctx* c, int F, const double* odo, const double* z, const int* matched)
@@ -1175,7 +1171,7 @@ int srukf_run_frames(srukf_ctx* c, int first, int count, int mode, double* traj_
         else { if (c->null_canonical != ck_canon) { c->null_canonical = ck_canon; drop_graphs(c); } quantize_state(c); shadow_rebuild(c); }
     };
     int rc = SRUKF_OK, done = 0;
-    const bool timing = g_dbg_timing.load() != 0;
+    const bool timing = g_sw.timing.load() != 0;
     auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (timing) { hipStreamSynchronize(c->stream); auto t1 = std::chrono::steady_clock::now(); fprintf(stderr, "[run_frames] %s %.0f us\n", what, std::chrono::duration<double, std::micro>(t1 - t0).count()); t0 = t1; } };
     while (done < count) {

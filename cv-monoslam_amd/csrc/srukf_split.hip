@@ -20,7 +20,7 @@ static void spare_side_drop()
 static bool split_wanted(const GmwPlan& gp)
 {
     if (!srukf_gmw_register_form(gp.T, gp.Tp, gp.ntiles, gp.workers)) return true;
-    return g_dbg_mem_split == 2 && gp.nreal > gp.workers;
+    return g_sw.mem_split == 2 && gp.nreal > gp.workers;
 }
 
 // Do kernels on streams a and b run side by side?  HIP maps streams onto a handful of hardware queues (four by default: GPU_MAX_HW_QUEUES) and two streams that share
@@ -60,7 +60,7 @@ namespace srukf_impl {
 // Buffers / side stream of the split form for a plan with Tp pivoted panels (not inside a capture).  Failure is not an error: the memory-tile form is used.
 void split_ensure(srukf_ctx* c, const GmwPlan& gp)
 {
-    if (!g_dbg_mem_split || gp.T < 16 || !split_wanted(gp)) return;           // (gp.workers < 0 — more tiles than the memory-tile form can own — included: the split form has no such limit)
+    if (!g_sw.mem_split || gp.T < 16 || !split_wanted(gp)) return;           // (gp.workers < 0 — more tiles than the memory-tile form can own — included: the split form has no such limit)
     if (gp.T + 1 > gp.cus) return;                              // the pivot / slab launch must be resident as a whole with CUs left for the tiles
     if (c->gs_panels < gp.Tp) {
         if (c->gsW) srukf_dfree_on(c->gsW, c->stream);
@@ -98,7 +98,7 @@ void split_ensure(srukf_ctx* c, const GmwPlan& gp)
 
 bool split_form(const srukf_ctx* c, const GmwPlan& gp, bool ignore_starve)
 {
-    return g_dbg_mem_split && !c->split_off && c->gmw_shared == 0 && (ignore_starve || !c->debug_starve) && c->side && c->gsW && c->gs_panels >= gp.Tp && gp.T >= 16 && gp.T + 1 <= gp.cus && split_wanted(gp);
+    return g_sw.mem_split && !c->split_off && c->gmw_shared == 0 && (ignore_starve || !c->debug_starve) && c->side && c->gsW && c->gs_panels >= gp.Tp && gp.T >= 16 && gp.T + 1 <= gp.cus && split_wanted(gp);
 }
 
 // a context about to be rebuilt (map change) offers its verified side stream to the context srukf_create builds next on the same filter stream (split_ensure)

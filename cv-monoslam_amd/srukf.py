@@ -24,7 +24,7 @@ EXPORTS = [
     "srukf_set_state", "srukf_get_state", "srukf_set_state_device", "srukf_get_state_device", "srukf_get_robot",
     "srukf_get_landmark_block", "srukf_get_landmarks_cartesian", "srukf_get_frame_view", "srukf_get_covariance", "srukf_predict_motion", "srukf_predict_motion_next", "srukf_predict_measurement",
     "srukf_update", "srukf_update_joint", "srukf_set_new_landmarks", "srukf_add_landmarks", "srukf_delete_landmark", "srukf_set_storage", "srukf_set_exclusive", "srukf_set_rank_aware", "srukf_null_directions", "srukf_run_frames_batch", "srukf_prepare_frames", "srukf_debug_poke_state", "srukf_get_state_f32", "srukf_set_landmark_appearance", "srukf_associate", "srukf_get_match_patch", "srukf_stage_sequence", "srukf_run_frames_async", "srukf_run_frames", "srukf_synchronize", "srukf_set_profiling",
-    "srukf_clamp_info", "srukf_debug_set", "srukf_debug_get", "srukf_debug_copy", "srukf_debug_upload", "srukf_debug_split_replay", "srukf_debug_gmw_stamps", "srukf_debug_starve_workers", "srukf_debug_allow_mixed", "srukf_profile_count", "srukf_profile_get", "srukf_profile_reset", "srukf_dims", "srukf_gmw_host",
+    "srukf_clamp_info", "srukf_debug_set", "srukf_debug_switch_at", "srukf_debug_get", "srukf_debug_copy", "srukf_debug_upload", "srukf_debug_split_replay", "srukf_debug_gmw_stamps", "srukf_debug_starve_workers", "srukf_debug_allow_mixed", "srukf_profile_count", "srukf_profile_get", "srukf_profile_reset", "srukf_dims", "srukf_gmw_host",
     "srukf_project_host", "srukf_detect_features", "srukf_capture_appearance", "srukf_get_landmark_record", "srukf_insert_landmarks",
     "srukf_ransac_consensus", "srukf_repredict_measurement",
     "srukf_get_landmarks_display", "srukf_get_frame_view_display",
@@ -174,6 +174,7 @@ def load_library(path=None):
     L.srukf_clamp_info.argtypes = [C.c_void_p, _ip, _ip]
     L.srukf_debug_starve_workers.argtypes = [C.c_void_p, C.c_int]
     L.srukf_debug_set.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.srukf_debug_switch_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), _ip, _ip, _ip]
     L.srukf_debug_get.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_longlong)]
     L.srukf_debug_copy.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.c_longlong]
     L.srukf_debug_upload.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.c_longlong]
@@ -638,6 +639,16 @@ def debug_set_global(key, value):
     rc = load_library().srukf_debug_set(None, key.encode(), int(value))
     if rc != 0:
         raise SrukfError(rc, f"srukf_debug_set({key})")
+
+
+def debug_switches(filter=None):
+    """Every switch of srukf_debug_set -> {key: (per_filter, default, value)}; value: the current setting (per-filter keys: this filter's; without one, the default)."""
+    lib, out, i = load_library(), {}, 0
+    key, per, dflt, val = C.c_char_p(), C.c_int(), C.c_int(), C.c_int()
+    while lib.srukf_debug_switch_at(filter._h if filter is not None else None, i, C.byref(key), C.byref(per), C.byref(dflt), C.byref(val)) == 0:
+        out[key.value.decode()] = (bool(per.value), dflt.value, val.value)
+        i += 1
+    return out
 
 
 def run_frames_batch(filters, first, count, mode=UPDATE_BATCHED):

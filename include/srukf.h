@@ -486,7 +486,7 @@ int  srukf_debug_allow_mixed(srukf_ctx* ctx, int on);
  *   "gmw_persist" (0: one launch per 64-row panel), "gmw_fused", "rank_fused", "rank_fold" (0: the owners of the persistent launch never form
  *   their tiles of S^T S - U U^T themselves), "rank_aware", "graphs" (0: contexts created afterwards launch eagerly, which rocprofv3 --pmc needs),
  *   "shared_tenants" (2..8: persistent launches that share the GPU after srukf_set_exclusive(SRUKF_GPU_SHARED); srukf_run_frames_batch picks its own),
- *   "batch_wide" (0: srukf_run_frames_batch never takes the batched launches), "batch_groups" (1..4: groups the batched filters are cut into),
+ *   "batch_wide" (0: srukf_run_frames_batch never takes the batched launches), "batch_groups" (1..4: groups the batched filters are cut into; 0, the default: as many as pay),
  *   "batch_split" (0: one launch per panel in the batched replay instead of slabs + plain trailing updates),
  *   "mem_split" (0: sizes beyond two register tiles per worker — N >= 400 — keep the memory-tile instance of k_gmw_persist instead of the split form
  *   k_gmw_pivslab_persist + k_gmw_tiles_persist; 2: the split form also where a worker would own two register tiles),
@@ -494,7 +494,9 @@ int  srukf_debug_allow_mixed(srukf_ctx* ctx, int on);
  *   launch), "fold_head" (block rows the k_syrk launch in front of the split fold forms; 0: the rule 2 (Tp - 17)), "fold_force" (the split fold also where the tile workgroups
  *   do not all fit beside the pivot / slab launch), "timing" (1: phases of map changes and of flagged frames on stderr), "ctx_keep" (contexts a handle keeps across map
  *   changes: default 24), "batch_xcd" (0: k_syrk_b walks the head tiles in the solo launch's order), "batch_k128" (0: one pass over G per panel in the batched replay's
- *   trailing updates instead of one per pair of panels).
+ *   trailing updates instead of one per pair of panels), "head_fold_free" (>= 1: CUs a plan must leave beside the pivot and the workers for the head fold, in place of
+ *   the built-in rule — which, once replaced, cannot be set back), "pivot_relay" (0: one pivot workgroup instead of two in the register-tile persistent launch; read when
+ *   a plan is built).
  * Per-context keys: "use_graph" (0: eager launches), "fused_motion" (0: k_motion + k_project as two launches, 1: k_project_motion, 2: "table"
  *   mode), "pxy2" (0: k_pxy instead of k_pxy2), "nullskip", "head_fold" (0: k_syrk launch in front of the persistent launch), "tail_fuse"
  *   (0: k_project_table in front of every frame), "table_perm", "f32_fuse", "step_fast" (0: the step-wise API keeps to its own launch sequences instead of the
@@ -505,8 +507,11 @@ int  srukf_debug_allow_mixed(srukf_ctx* ctx, int on);
  *   slower: off), "split_fold" (0: k_syrk over all kept rows in front of the split form's pair instead of forming jobs inside its tile launch), "mixed_rank" (0: round 2's
  *   full-rank form of SRUKF_STORAGE_F32_MIXED), "mixed_f64_robot" (0: every tile of the mixed downdate on the fp32 pipe), "mixed_bf16" (1: its fp32 products from three bf16
  *   pieces), "mixed_null_ppm", "null_canon" (0: the null rows of a factor that NEED_REORDER or a map operation produced are left as they are until a frame tail rewrites them).
- *   See srukf_ctx.h (srukf_ctx::DbgSwitches). */
+ *   Every key with its range, its default and what a change invalidates: the table in srukf_debug.hip; the measurements behind them: srukf_switches.h. */
 int  srukf_debug_set(srukf_ctx* ctx, const char* key, int value);
+/* Row `index` of the switch table (0 .. count-1; SRUKF_ERR_BAD_ARG beyond). Any out pointer may be NULL.
+ * value: the current setting; for a per-filter row with ctx == NULL, the default. Touches no stream. */
+int  srukf_debug_switch_at(srukf_ctx* ctx, int index, const char** key, int* per_filter, int* default_value, int* value);
 /* Diagnostic read-out of device-resident counters ("gmw_aborts", "clamp_rows", "frame", "frozen", "gate_timeouts", "gmw_shared", "split_form", "split_off",
  * "step_fast" / "step_slow": frames the step-wise API ran on the fast / the other path, "view_hits": srukf_get_frame_view calls served from an exported view,
  * "meas_flag_ticks": 10-ns ticks from the start of the fast path's last k_pxy2 to the moment the host had its statistics) and of the launch plan the next staged frame takes ("plan_persist",
