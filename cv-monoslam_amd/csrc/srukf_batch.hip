@@ -247,6 +247,10 @@ int srukf_run_frames_batch(srukf_ctx* const* ctxs, int B, int first, int count, 
 {
     if (!ctxs || B < 1 || count < 1) return SRUKF_ERR_BAD_ARG;
     for (int b = 0; b < B; b++) if (!ctxs[b]) return SRUKF_ERR_BAD_ARG;
+    if (mode == SRUKF_UPDATE_JOINT) {                          // the batched launches have k_gain's further duties in their form; nothing runs
+        for (int b = 0; b < B; b++) { ctxs[b]->err = "run_frames_batch: SRUKF_UPDATE_JOINT is not available (use srukf_run_frames / srukf_run_frames_async per filter)"; if (status) status[b] = SRUKF_ERR_UNSUPPORTED; }
+        return SRUKF_ERR_UNSUPPORTED;
+    }
     std::vector<double*> dt(B, nullptr);
     std::vector<int> rcs(B, SRUKF_OK), canon0(B, 0);
     int rc = SRUKF_OK;

@@ -9,7 +9,7 @@
 //   srukf_overlay.hip colour-frame intake (srukf_set_frame_bgr) and the 2-D feature overlay (srukf_render_overlay)
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search)
-//   srukf_joint.hip   the joint measurement update's kernels (srukf_update_joint; its host code is in srukf_step.hip)
+//   srukf_joint.hip   the joint measurement update's kernels (srukf_update_joint, SRUKF_UPDATE_JOINT frames of the staged replay; host code: srukf_step.hip, srukf_replay.hip)
 //   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip)
 //   srukf_patch.h     (through srukf_launch.h) the appearance record's sizes, the checked association's buffer layouts, the search kernels' shared front
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
@@ -44,6 +44,13 @@ enum KClass { KC_MOTION = 0, KC_PROJECT, KC_STATS, KC_PXY, KC_GAIN, KC_SYRK, KC_
               KC_DET_RESPONSE, KC_DET_CAND, KC_DET_RANK, KC_DET_SELECT, KC_CAPTURE, KC_LM_ELLIPSOID, KC_BGR2GRAY, KC_OVERLAY,
               KC_ARCHIVE_PREDICT, KC_ARCHIVE_WARP, KC_ARCHIVE_SEARCH, KC_ASSOC_CHECKED, KC_COUNT };
 struct ProfEvent { hipEvent_t a, b; int kc; };
+
+// the captured frames of one update mode of the staged replay: one frame / SRUKF_GRAPH_FRAMES frames / srukf_prepare_frames*: a whole block of frames in ONE graph
+struct ReplayGraphs {
+    hipGraph_t one = nullptr, eight = nullptr, block = nullptr;
+    hipGraphExec_t one_exec = nullptr, eight_exec = nullptr, block_exec = nullptr;
+    int block_frames = 0;
+};
 
 // ---- persistent GMW launch (k_gmw_persist): per-matrix-size resources --------------------------------
 // nreal: the tiles that hold values (ntiles minus the T - Tp pass-on tiles of the rank-aware form, which ride as a register-free third slot of the first workers)
@@ -137,6 +144,7 @@ struct srukf_life {
     bool frame_updated = false;            // the last call that touched the state was a srukf_update of the frame in hand (srukf_repredict_measurement may follow)
     bool next_odo_valid = false;           // srukf_predict_motion_next: next_odo is the pair the next srukf_predict_motion will bring
     bool async_pending = false;
+    bool joint_bad_host = false;           // the SRUKF_ERR_UNSUPPORTED in hand is a joint frame's non-finite input (joint_bad_report): srukf_run_frames restores its checkpoint
     // the step-wise fast path (step_* below)
     bool step_fast = false;                // the frame in flight runs on the fast path
     bool step_uncommitted = false;         // ... and its motion step still waits beside the state (fs->Xr1, Cmat): state getters commit it first (k_commit_motion)
@@ -190,7 +198,7 @@ struct srukf_map_scope : srukf_life {
     // a map change and srukf_reset drop both buffers (match_drop)
     double *match_res = nullptr, *match_scores = nullptr; bool match_valid = false;
     RansacScratch ransac;                  // srukf_ransac_consensus / srukf_repredict_measurement
-    // srukf_update_joint (srukf_joint.hip), allocated on its first call: jointZd = the sigma points' deviations dZ (joint_dev_rows x mp), jointW = [ Pzz | Pxy^T | z - h ]
+    // the joint update (srukf_update_joint, SRUKF_UPDATE_JOINT frames of the staged replay; srukf_joint.hip), allocated by joint_ensure on first use: jointZd = the sigma points' deviations dZ (joint_dev_rows x mp), jointW = [ Pzz | Pxy^T | z - h ]
     // (mp x joint_work_ld), jointRd = the factored diagonal blocks (mp x 64) with the status word behind them
     double *jointZd = nullptr, *jointW = nullptr, *jointRd = nullptr;
     // srukf_get_landmarks_display / srukf_get_frame_view_display: xyz (3N) | cov (9N) | axis (4N) | sigma (3N) | P4, pose (20) | rot (N ints).  A buffer of its own,
@@ -268,10 +276,9 @@ struct srukf_map_scope : srukf_life {
     double* hview = nullptr; size_t hview_doubles = 0;      // pinned: xyz (3N) | cov (9N) | X (n) of the state an update of the fast path left, when the host is known to ask for it
     int split_fold_seqs = 0;               // split-form pairs enqueued (or captured) with the split fold: "split_fold_seqs"
     int fold_seqs = 0;                     // frame sequences enqueued (or captured) with the gain fold: "fold_seqs" (tests: the switch took effect)
-    // one captured frame (BATCHED, staged inputs): replayed by srukf_run_frames_async
-    hipGraph_t graph = nullptr, graph8 = nullptr;          // one frame / SRUKF_GRAPH_FRAMES frames
-    hipGraphExec_t graph_exec = nullptr, graph8_exec = nullptr;
-    hipGraph_t graphN = nullptr; hipGraphExec_t graphN_exec = nullptr; int graphN_frames = 0;   // srukf_prepare_frames: a whole block of frames in ONE graph
+    // captured frames (staged inputs), replayed by srukf_run_frames_async: one set per update mode of the replay ([0] BATCHED, [1] JOINT: replay_graphs), so that a call in
+    // one mode never replays the other's launch sequence; drop_graphs drops both
+    ReplayGraphs graphs[2];
     // the pool allocations among the members above (Si and vis are inside h, mcur inside zcur; ransac, gplan, gplan_red: ransac_scratch_free / gmw_plan_destroy).
     // A new buffer of this scope is added HERE
     template <class F> void each_device_buffer(F f) const {
@@ -447,6 +454,9 @@ int refactor_reorder(srukf_ctx* c, int ub, int ue);
 void seq_pxy(srukf_ctx* c, FrameForm ff);
 void seq_gain_only(srukf_ctx* c, const double* z_dev, const int* m_dev, FrameForm ff);
 void seq_gain(srukf_ctx* c, const double* z_dev, const int* m_dev, FrameForm ff);
+// the joint update in seq_gain_only's place behind seq_pxy (srukf_step.hip): its work buffers, allocated outside any capture; its launches (no host in between)
+int joint_ensure(srukf_ctx* c, const char* what);
+void seq_joint_launches(srukf_ctx* c, const double* z_dev, const int* m_dev);
 int update_null_set(srukf_ctx* c);
 int mixed_red_ensure(srukf_ctx* c);
 void drop_graphs(srukf_map_scope* c);

@@ -20,8 +20,14 @@
 //                  k_joint_trail  A_q,x -= R_p,q^T R_p,x for the rows q > p: Pzz columns >= q and all Pxy^T / innovation columns, one wave per 32 x 32 tile
 //   k_joint_dx     dX = U w in fixed order, X += dX, U^T -> c->Ut in state order (rows of inactive landmarks are zero), the gamma / xi accumulators of the k_syrk
 //                  launch that follows cleared as k_gain's block (0, 0) does; R_pp back into W's diagonal blocks (srukf_debug_copy "joint_R")
-// A non-positive pivot (Pzz is a Gram matrix plus the noise blocks: the inputs were not finite) sets *status = 1 + its row; the pivot is replaced by 1, k_joint_dx
-// then leaves X alone and writes U^T = 0, and the host returns SRUKF_ERR_UNSUPPORTED with the row in srukf_last_error.
+// A non-positive pivot (Pzz is a Gram matrix plus the noise blocks: the inputs were not finite) sets *status = 1 + its row and the pivot is replaced by 1; an innovation
+// z - h that is not finite (Pzz does not depend on z) sets it the same way and enters W as zero.  k_joint_dx then leaves X alone and writes U^T = 0 (both copies), and
+// records frame + 1 and the row in the frame scalars' sticky pair (first hit only; k_set_run / k_set_frame clear it with the clamp counters): nothing loops, no NaN
+// reaches the state, and the later frames of a replayed block run to their end on finite data.  The step-wise call reads *status and returns SRUKF_ERR_UNSUPPORTED with
+// the row in srukf_last_error; the staged replay needs no host inside a block: srukf_synchronize reads the pair with the frame scalars.
+// Staged replay ("the joint frame of the replay"): z_cur / m_cur null -> this frame's rows of the staged z_seq / m_seq through fs->frame, as k_gain
+// reads them, so that one captured frame replays for every frame; k_joint_dx also writes U^T with permuted columns (ra.Utp through ra.iperm, k_gain's duty in the plain
+// frame form: the frame-tail refactor forms on the permuted operands read U^T there and nowhere else).
 #include "srukf_launch.h"
 #include "srukf_tiles.h"
 
@@ -34,10 +40,24 @@ __device__ __forceinline__ bool joint_active(int m, int N, const int* __restrict
     return k < N && mt[k] != 0 && vis[k] != 0 && fma(Si[4 * k], Si[4 * k + 3], -(Si[4 * k + 1] * Si[4 * k + 2])) != 0.0;
 }
 
-// dZ[i][m] = Z[i + 1][m] - Z[0][m], i < 2 Na; zero: the four noise rows, the columns of inactive rows, the padding rows up to Kp.  grid = Kp, one row each
-__global__ __launch_bounds__(256) void k_joint_dev(KDims d, int Kp, const double* __restrict__ Z, const int* __restrict__ vis, const int* __restrict__ mt, const double* __restrict__ Si, double* __restrict__ Zd)
+// this frame's measurements and matches: the step-wise call's own, or the staged sequence's rows of the frame in hand (gain_body reads them the same way)
+__device__ __forceinline__ const double* joint_z(const double* z_cur, const double* __restrict__ z_seq, const FrameScalars* __restrict__ fs, int N) { return z_cur ? z_cur : z_seq + (size_t)fs->frame * 2 * N; }
+__device__ __forceinline__ const int* joint_m(const int* m_cur, const int* __restrict__ m_seq, const FrameScalars* __restrict__ fs, int N) { return m_cur ? m_cur : m_seq + (size_t)fs->frame * N; }
+
+// *status = 1 + row unless an earlier row holds it already (several rows of one launch may report: the smallest stays, whatever the order)
+__device__ __forceinline__ void joint_report(int* status, int row)
+{
+    int old = atomicCAS(status, 0, 1 + row);
+    while (old != 0 && old > 1 + row) { const int seen = atomicCAS(status, old, 1 + row); if (seen == old) break; old = seen; }
+}
+
+// dZ[i][m] = Z[i + 1][m] - Z[0][m], i < 2 Na; zero: the four noise rows, the columns of inactive rows, the padding rows up to Kp.  grid = Kp, one row each; the first one clears the status word
+__global__ __launch_bounds__(256) void k_joint_dev(KDims d, int Kp, const double* __restrict__ Z, const int* __restrict__ vis, const int* m_cur, const int* __restrict__ m_seq,
+                                                   const FrameScalars* __restrict__ fs, const double* __restrict__ Si, double* __restrict__ Zd, int* __restrict__ status)
 {
     const int i = blockIdx.x, mp = d.mp;
+    const int* mt = joint_m(m_cur, m_seq, fs, d.N);
+    if (i == 0 && threadIdx.x == 0) *status = 0;
     const int a = i < d.Na ? i : i - d.Na;
     const bool common = i < 2 * d.Na && a != d.n + 3 && a != d.n + 4;
     for (int m = threadIdx.x; m < mp; m += 256)
@@ -46,11 +66,14 @@ __global__ __launch_bounds__(256) void k_joint_dev(KDims d, int Kp, const double
 
 // W = [ Pzz | Pxy^T | z - h ].  grid = (ldw / 32, mp / 32): one 32 x 32 tile of W per workgroup
 __global__ __launch_bounds__(256) void k_joint_form(KDims d, KWeights w, int Kp, int ldw, const double* __restrict__ Zd, const double* __restrict__ Z,
-                                                    const int* __restrict__ vis, const int* __restrict__ mt, const double* __restrict__ Si, const double* __restrict__ Ut,
-                                                    const double* __restrict__ PxyR, const double* __restrict__ h, const double* __restrict__ z, double* __restrict__ W)
+                                                    const int* __restrict__ vis, const int* m_cur, const int* __restrict__ m_seq, const double* __restrict__ Si, const double* __restrict__ Ut,
+                                                    const double* __restrict__ PxyR, const double* __restrict__ h, const double* z_cur, const double* __restrict__ z_seq,
+                                                    const FrameScalars* __restrict__ fs, double* __restrict__ W, int* __restrict__ status)
 {
     __shared__ double red[3][64][17];
     const int mp = d.mp, np = d.np, n = d.n, N = d.N;
+    const int* mt = joint_m(m_cur, m_seq, fs, N);
+    const double* z = joint_z(z_cur, z_seq, fs, N);
     const int m0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
     if (c0 >= mp) {
         // Pxy^T as k_gain reads it, and the innovation in the first of the last 32 columns
@@ -61,7 +84,10 @@ __global__ __launch_bounds__(256) void k_joint_form(KDims d, KWeights w, int Kp,
             if (joint_active(m, N, vis, mt, Si)) {
                 if (r < n - 4) v = sc * Ut[(size_t)m * np + r];
                 else if (r < n) v = PxyR[(size_t)(r - (n - 4)) * mp + m];
-                else if (r == np) v = z[m] - h[m];
+                else if (r == np) {
+                    v = z[m] - h[m];
+                    if (!(fabs(v) <= 1.79769313486231570e308)) { joint_report(status, m); v = 0.0; }      // NaN or infinite: Pzz would never show it
+                }
             }
             W[(size_t)m * ldw + c] = v;
         }
@@ -163,9 +189,10 @@ __global__ __launch_bounds__(256) void k_joint_trail(int p, int ldw, double* __r
                 W[(size_t)(rt * 32 + 16 * a + lk + 4 * t) * ldw + ct * 32 + 16 * b + lr] += acc[a][b][t];
 }
 
-// dX = U w, X += dX, U^T -> Ut (mp x np, state order).  grid = np / 64 workgroups of 64 (one state row per thread), then mp / 64 that put R_pp back into W
+// dX = U w, X += dX, U^T -> Ut (mp x np, state order) and, where the rank-aware operands exist, -> ra.Utp with permuted columns.  grid = np / 64 workgroups of 64 (one
+// state row per thread), then mp / 64 that put R_pp back into W.  A frame whose status word is set: zero U^T, X untouched, the sticky pair of the frame scalars
 __global__ __launch_bounds__(64) void k_joint_dx(KDims d, int ldw, double* __restrict__ W, const double* __restrict__ Rd, const int* __restrict__ status,
-                                                 double* __restrict__ Ut, double* __restrict__ X, FrameScalars* __restrict__ fs)
+                                                 double* __restrict__ Ut, double* __restrict__ X, FrameScalars* __restrict__ fs, double* __restrict__ Utp, const int* __restrict__ iperm)
 {
     const int mp = d.mp, np = d.np, nb = np / 64;
     if ((int)blockIdx.x >= nb) {
@@ -173,14 +200,20 @@ __global__ __launch_bounds__(64) void k_joint_dx(KDims d, int ldw, double* __res
         for (int i = 0; i < 64; i++) W[(size_t)(j0 + i) * ldw + j0 + threadIdx.x] = Rd[(size_t)(j0 + i) * 64 + threadIdx.x];
         return;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { fs->gmax_bits = 0ull; fs->ximax_bits = 0ull; }
+    const int st = *status;
+    const bool ok = st == 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        fs->gmax_bits = 0ull; fs->ximax_bits = 0ull;
+        if (!ok && fs->joint_bad_frame == 0) { fs->joint_bad_frame = fs->frame + 1; fs->joint_bad_row = st - 1; }
+    }
     const int r = blockIdx.x * 64 + threadIdx.x;
-    const bool ok = *status == 0;
+    const int rp = Utp ? iperm[r] : 0;
     double dx = 0.0;
     for (int m = 0; m < mp; m++) {
         const double u = ok ? W[(size_t)m * ldw + mp + r] : 0.0;
         Ut[(size_t)m * np + r] = u;
-        dx = fma(u, W[(size_t)m * ldw + mp + np], dx);
+        if (Utp) Utp[(size_t)m * np + rp] = u;
+        if (ok) dx = fma(u, W[(size_t)m * ldw + mp + np], dx);
     }
     if (ok && r < d.n) X[r] += dx;
 }
@@ -188,13 +221,12 @@ __global__ __launch_bounds__(64) void k_joint_dx(KDims d, int ldw, double* __res
 int joint_dev_rows(int Na) { return (2 * Na + 15) & ~15; }
 int joint_work_ld(int mp, int np) { return mp + np + 32; }
 
-void launch_joint_form(hipStream_t st, KDims d, KWeights w, const double* Z, const int* vis, const int* mt, const double* Si, const double* Ut, const double* PxyR, const double* h,
-                       const double* z, double* Zd, double* W, int* status)
+void launch_joint_form(hipStream_t st, KDims d, KWeights w, const JointFrame& f, const double* Z, const int* vis, const double* Si, const double* Ut, const double* PxyR, const double* h,
+                       double* Zd, double* W, int* status)
 {
     const int Kp = joint_dev_rows(d.Na), ldw = joint_work_ld(d.mp, d.np);
-    (void)hipMemsetAsync(status, 0, sizeof(int), st);
-    hipLaunchKernelGGL(k_joint_dev, dim3(Kp), dim3(256), 0, st, d, Kp, Z, vis, mt, Si, Zd);
-    hipLaunchKernelGGL(k_joint_form, dim3(ldw / 32, d.mp / 32), dim3(256), 0, st, d, w, Kp, ldw, Zd, Z, vis, mt, Si, Ut, PxyR, h, z, W);
+    hipLaunchKernelGGL(k_joint_dev, dim3(Kp), dim3(256), 0, st, d, Kp, Z, vis, f.m_cur, f.m_seq, f.fs, Si, Zd, status);
+    hipLaunchKernelGGL(k_joint_form, dim3(ldw / 32, d.mp / 32), dim3(256), 0, st, d, w, Kp, ldw, Zd, Z, vis, f.m_cur, f.m_seq, Si, Ut, PxyR, h, f.z_cur, f.z_seq, f.fs, W, status);
 }
 
 void launch_joint_factor(hipStream_t st, KDims d, double* W, double* Rd, int* status)
@@ -210,7 +242,7 @@ void launch_joint_factor(hipStream_t st, KDims d, double* W, double* Rd, int* st
     }
 }
 
-void launch_joint_dx(hipStream_t st, KDims d, double* W, const double* Rd, const int* status, double* Ut, double* X, FrameScalars* fs)
+void launch_joint_dx(hipStream_t st, KDims d, double* W, const double* Rd, const int* status, double* Ut, double* X, FrameScalars* fs, const RankArgs& ra)
 {
-    hipLaunchKernelGGL(k_joint_dx, dim3(d.np / 64 + d.mp / 64), dim3(64), 0, st, d, joint_work_ld(d.mp, d.np), W, Rd, status, Ut, X, fs);
+    hipLaunchKernelGGL(k_joint_dx, dim3(d.np / 64 + d.mp / 64), dim3(64), 0, st, d, joint_work_ld(d.mp, d.np), W, Rd, status, Ut, X, fs, ra.Utp, ra.iperm);
 }

@@ -164,11 +164,15 @@ void srukf_launch_associate_checked(hipStream_t st, KDims d, srukf_params p, Mat
 
 // ---- srukf_joint.hip (the joint measurement update; C++ linkage: its launchers are named launch_joint_*) ----
 // Zd: joint_dev_rows(Na) x mp, W: mp x joint_work_ld(mp, np) = [ Pzz | Pxy^T | z - h ], Rd: mp x 64 (the factored diagonal blocks), status: one int (0, or 1 + the row
-// of the first non-positive pivot).  form: W from Z and k_pxy's products (Ut raw, PxyR); factor: the blocked Cholesky, two launches per 64-row panel, leaves R, U^T and
-// w in W; dx: X += U w, U^T -> Ut in state order, the gamma / xi accumulators cleared for the k_syrk launch that follows
+// of the first non-positive pivot / non-finite innovation; cleared by the form launch).  form: W from Z and k_pxy's products (Ut raw, PxyR); factor: the blocked Cholesky,
+// two launches per 64-row panel, leaves R, U^T and w in W; dx: X += U w, U^T -> Ut in state order and -> ra.Utp with permuted columns (ra.Utp != null: what k_gain leaves
+// for the frame-tail forms on the permuted operands), the gamma / xi accumulators cleared for the k_syrk launch that follows; a set status word: zero U^T, X untouched,
+// fs->joint_bad_frame / joint_bad_row (first hit only).
+// JointFrame: whose measurements — z_cur / m_cur (the step-wise call's, on the device), or null: the rows of frame fs->frame in the staged z_seq / m_seq, as k_gain reads them
+struct JointFrame { const double* z_cur; const int* m_cur; const double* z_seq; const int* m_seq; const FrameScalars* fs; };
 int joint_dev_rows(int Na);
 int joint_work_ld(int mp, int np);
-void launch_joint_form(hipStream_t st, KDims d, KWeights w, const double* Z, const int* vis, const int* mt, const double* Si, const double* Ut, const double* PxyR, const double* h,
-                       const double* z, double* Zd, double* W, int* status);
+void launch_joint_form(hipStream_t st, KDims d, KWeights w, const JointFrame& f, const double* Z, const int* vis, const double* Si, const double* Ut, const double* PxyR, const double* h,
+                       double* Zd, double* W, int* status);
 void launch_joint_factor(hipStream_t st, KDims d, double* W, double* Rd, int* status);
-void launch_joint_dx(hipStream_t st, KDims d, double* W, const double* Rd, const int* status, double* Ut, double* X, FrameScalars* fs);
+void launch_joint_dx(hipStream_t st, KDims d, double* W, const double* Rd, const int* status, double* Ut, double* X, FrameScalars* fs, const RankArgs& ra);

@@ -28,7 +28,7 @@ __global__ void k_set_frame(FrameScalars* fs, int frame, int clear_clamp)
     fs->const_rows_ok = 0; fs->const_rows_pending = 0;         // whatever happened to S since the last staged frame: its first tail writes every row again
     for (int q = 0; q < SRUKF_STAT_GROUPS; q++) fs->stat_cnt[q] = 0;
     fs->traj_base = nullptr;
-    if (clear_clamp) { fs->clamp_rows = 0; fs->clamp_first = 0x7fffffff; fs->clamp_frame = 0x7fffffff; fs->frozen = 0; fs->gmw_aborts = 0; }
+    if (clear_clamp) { fs->clamp_rows = 0; fs->clamp_first = 0x7fffffff; fs->clamp_frame = 0x7fffffff; fs->frozen = 0; fs->gmw_aborts = 0; fs->joint_bad_frame = 0; fs->joint_bad_row = 0; }
 }
 
 __global__ void k_set_traj(FrameScalars* fs, double* traj_base) { fs->traj_base = traj_base; }
@@ -42,7 +42,7 @@ __global__ void k_set_run(FrameScalars* fs, int frame, int clear_clamp, double* 
     fs->const_rows_ok = 0; fs->const_rows_pending = 0;         // whatever happened to S since the last staged frame: its first tail writes every row again
     for (int q = 0; q < SRUKF_STAT_GROUPS; q++) fs->stat_cnt[q] = 0;
     fs->traj_base = traj_base;
-    if (clear_clamp) { fs->clamp_rows = 0; fs->clamp_first = 0x7fffffff; fs->clamp_frame = 0x7fffffff; fs->frozen = 0; fs->gmw_aborts = 0; }
+    if (clear_clamp) { fs->clamp_rows = 0; fs->clamp_first = 0x7fffffff; fs->clamp_frame = 0x7fffffff; fs->frozen = 0; fs->gmw_aborts = 0; fs->joint_bad_frame = 0; fs->joint_bad_row = 0; }
 }
 
 // Step-wise API, fast path: start of a frame.  odo = (prev, cur[, next]) poses on the device: a staged sequence of one (two) frames the frame scalars point at.
@@ -930,13 +930,11 @@ int read_fs_host(srukf_ctx* c)
 
 void drop_graphs(srukf_map_scope* c)
 {
-    if (c->graph_exec) { hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-    if (c->graph) { hipGraphDestroy(c->graph); c->graph = nullptr; }
-    if (c->graph8_exec) { hipGraphExecDestroy(c->graph8_exec); c->graph8_exec = nullptr; }
-    if (c->graph8) { hipGraphDestroy(c->graph8); c->graph8 = nullptr; }
-    if (c->graphN_exec) { hipGraphExecDestroy(c->graphN_exec); c->graphN_exec = nullptr; }
-    if (c->graphN) { hipGraphDestroy(c->graphN); c->graphN = nullptr; }
-    c->graphN_frames = 0;
+    for (ReplayGraphs& g : c->graphs) {                        // the captured frames of both update modes
+        for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec, &g.block_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
+        for (hipGraph_t* q : { &g.one, &g.eight, &g.block }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
+        g.block_frames = 0;
+    }
 }
 
 // shared: 0 exclusive, 1 shared (tenants persistent launches at a time), 2 one launch per panel
@@ -959,9 +957,27 @@ int set_shared(srukf_ctx* c, int shared, int tenants)
     return SRUKF_OK;
 }
 
-// srukf_debug_set(ctx, "fused_motion", 0): the replay keeps k_motion and k_project as two launches (A/B runs)
-static void replay_one_frame(srukf_ctx* c)
+// the captured frames of an update mode the replay has (BATCHED, JOINT)
+static ReplayGraphs& replay_graphs(srukf_ctx* c, int mode) { return c->graphs[mode == SRUKF_UPDATE_JOINT ? 1 : 0]; }
+
+// A joint frame of the staged replay (SRUKF_UPDATE_JOINT): always the plain frame form, whatever "fused_motion" and its neighbours say — all of
+// c->Z is written, c->Ut holds S^T DZ in state order, nothing of the motion step is pending: what the joint kernels read — with the joint launches in k_gain's place.
+// They leave what k_gain leaves in this form (gain_body with Cm, P1 null): U^T in c->Ut and, with permuted columns, in c->Utp; the gamma / xi accumulators cleared;
+// and X updated already, where k_gain leaves slice partials for the k_syrk launch (dx_pending false: the tail's launches carry no state update).
+// joint_ensure has run (run_frames_async, prepare_frames_mode: never inside a capture)
+static void replay_one_frame_joint(srukf_ctx* c)
 {
+    seq_predict_motion(c, nullptr);
+    seq_predict_measurement(c, FORM_PLAIN);
+    seq_pxy(c, FORM_PLAIN);
+    seq_joint_launches(c, nullptr, nullptr);
+    seq_refactor(c, refactor_frame_tail(c), FORM_PLAIN);
+}
+
+// srukf_debug_set(ctx, "fused_motion", 0): the replay keeps k_motion and k_project as two launches (A/B runs)
+static void replay_one_frame(srukf_ctx* c, int mode)
+{
+    if (mode == SRUKF_UPDATE_JOINT) { replay_one_frame_joint(c); return; }
     const FrameForm ff = frame_form(c);
     // "fused tail" mode: the previous frame's tail (or, for a run's first frame, run_frames_async) projected this frame; its motion reduction rides on k_pxy2
     if (ff.fused_tail()) c->xr1_pending = true;
@@ -974,10 +990,10 @@ static void replay_one_frame(srukf_ctx* c)
     seq_refactor(c, refactor_frame_tail(c), ff);
 }
 
-static int capture_frames(srukf_ctx* c, int nframes, hipGraph_t* g, hipGraphExec_t* ge)
+static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge)
 {
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    for (int q = 0; q < nframes; q++) replay_one_frame(c);
+    for (int q = 0; q < nframes; q++) replay_one_frame(c, mode);
     const hipError_t launch_err = hipGetLastError();            // a failed launch inside the capture must not leave the stream capturing
     HIPCHK(c, hipStreamEndCapture(c->stream, g));
     HIPCHK(c, launch_err);
@@ -1003,10 +1019,34 @@ void set_null_canonical(srukf_ctx* c)
 
 }  // namespace srukf_impl
 
+// which update modes the staged replay has, and on which storage: BATCHED everywhere; JOINT on fp64 storage (the step-wise srukf_update_joint refuses
+// SRUKF_STORAGE_F32_MIXED too; SRUKF_STORAGE_F32: the replay's frame tails round in launches the step-wise call's checked refactorisation does not share —
+// not shown to round at the same points, so refused, include/srukf.h)
+static int replay_mode_check(srukf_ctx* c, int mode, const char* who)
+{
+    if (mode == SRUKF_UPDATE_BATCHED) return SRUKF_OK;
+    if (mode != SRUKF_UPDATE_JOINT) { c->err = std::string(who) + " supports BATCHED and JOINT only (SEQUENTIAL needs a host check per column)"; return SRUKF_ERR_UNSUPPORTED; }
+    if (c->storage != SRUKF_STORAGE_F64) {
+        c->err = std::string(who) + (c->storage == SRUKF_STORAGE_F32_MIXED ? ": SRUKF_UPDATE_JOINT is not available in SRUKF_STORAGE_F32_MIXED" : ": SRUKF_UPDATE_JOINT frames are not available in SRUKF_STORAGE_F32 (use srukf_update_joint)");
+        return SRUKF_ERR_UNSUPPORTED;
+    }
+    return SRUKF_OK;
+}
+
+// *c->hfs holds a set sticky pair of the joint update: the error the caller returns.  Frames before that one are valid; it and the later ones are not
+static int joint_bad_report(srukf_ctx* c)
+{
+    char b[240]; snprintf(b, sizeof b, "joint update: non-positive pivot in the innovation covariance or non-finite innovation in staged frame %d, row %d: the frame's inputs are not finite "
+                                       "(frames before it are valid; it and the later ones are not)", c->hfs->joint_bad_frame - 1, c->hfs->joint_bad_row);
+    c->err = b; c->joint_bad_host = true;
+    return SRUKF_ERR_UNSUPPORTED;
+}
+
 // One staged frame (index `frame`) through the path that checks the theta clamp on the host and repeats the
 // refactorisation column by column when the reference's third pivot candidate would have won — what srukf_update does,
 // with the staged inputs.  traj_row: device pointer of this frame's trajectory row, or null.
-static int run_staged_frame_exact(srukf_ctx* c, int frame, double* traj_row)
+// mode JOINT: seq_pxy + the joint launches in seq_gain's place, as step_update_slow runs them (built by passing the mode through; no test reaches it: DESIGN.md section 19)
+static int run_staged_frame_exact(srukf_ctx* c, int frame, double* traj_row, int mode)
 {
     const KDims& d = c->d;
     c->exact_frames++;
@@ -1020,11 +1060,17 @@ static int run_staged_frame_exact(srukf_ctx* c, int frame, double* traj_row)
     seq_predict_motion(c, nullptr);
     seq_predict_measurement(c, FORM_PLAIN);
     lap("predict");
-    seq_gain(c, nullptr, nullptr, FORM_PLAIN);
+    if (mode == SRUKF_UPDATE_JOINT) {
+        const int rcj = joint_ensure(c, "run_frames"); if (rcj) return rcj;
+        seq_pxy(c, FORM_PLAIN);
+        seq_joint_launches(c, nullptr, nullptr);
+    } else
+        seq_gain(c, nullptr, nullptr, FORM_PLAIN);
     lap("gain");
     seq_refactor(c, refactor_checked(c), FORM_PLAIN);
     int rc = read_fs(c); if (rc) return rc;
     lap("blocked refactor");
+    if (mode == SRUKF_UPDATE_JOINT && c->hfs->joint_bad_frame > 0) return joint_bad_report(c);
     if (c->hfs->clamp_rows > 0) {
         rc = exact_repeat_begin(c, frame, tb); if (rc) return rc;
         ProfScope ps(c, KC_GMW_COL, 0, 0);
@@ -1074,27 +1120,35 @@ int srukf_stage_sequence(srukf_ctx* c, int F, const double* odo, const double* z
 // A block of `count` staged frames as ONE captured graph for the next srukf_run_frames_async(ctx, *, count, ...) calls (the default
 // is graphs of 8 frames + single frames; between two graph launches the device idles for ~10 us, which shows in short blocks).
 // Nothing runs; the graph is dropped with the others whenever the launch sequence changes.  count <= 512.
-int srukf_prepare_frames(srukf_ctx* c, int count)
+int srukf_prepare_frames_mode(srukf_ctx* c, int count, int mode)
 {
     if (!c || count < 1 || count > 512) return SRUKF_ERR_BAD_ARG;
+    int rc = replay_mode_check(c, mode, "prepare_frames"); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->use_graph || (c->graphN_exec && c->graphN_frames == count)) return SRUKF_OK;
-    if (c->graphN_exec) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipGraphExecDestroy(c->graphN_exec); c->graphN_exec = nullptr; }   // a launch of the old one may still be in flight
-    if (c->graphN) { hipGraphDestroy(c->graphN); c->graphN = nullptr; }
-    c->graphN_frames = 0;
-    const int rc = capture_frames(c, count, &c->graphN, &c->graphN_exec);
+    ReplayGraphs& g = replay_graphs(c, mode);
+    if (!c->use_graph || (g.block_exec && g.block_frames == count)) return SRUKF_OK;
+    if (g.block_exec) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipGraphExecDestroy(g.block_exec); g.block_exec = nullptr; }   // a launch of the old one may still be in flight
+    if (g.block) { hipGraphDestroy(g.block); g.block = nullptr; }
+    g.block_frames = 0;
+    if (mode == SRUKF_UPDATE_JOINT) { rc = joint_ensure(c, "prepare_frames"); if (rc) return rc; }      // (before the capture begins)
+    rc = capture_frames(c, count, mode, &g.block, &g.block_exec);
     if (rc) return rc;
-    c->graphN_frames = count;
+    g.block_frames = count;
     return SRUKF_OK;
 }
+
+int srukf_prepare_frames(srukf_ctx* c, int count) { return srukf_prepare_frames_mode(c, count, SRUKF_UPDATE_BATCHED); }
 
 int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double* d_traj)
 {
     if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
     if (!c->odo_seq || first + count > c->seqF) { c->err = "frames outside the staged sequence"; return SRUKF_ERR_DIM_MISMATCH; }
-    if (mode != SRUKF_UPDATE_BATCHED) { c->err = "run_frames_async supports BATCHED only (SEQUENTIAL needs a host check per column)"; return SRUKF_ERR_UNSUPPORTED; }
+    c->joint_bad_host = false;
+    { const int rcm = replay_mode_check(c, mode, "run_frames_async"); if (rcm) return rcm; }
     HIPCHK(c, hipSetDevice(c->device));
     const KDims& d = c->d;
+    const bool joint = mode == SRUKF_UPDATE_JOINT;
+    if (joint) { const int rcj = joint_ensure(c, "run_frames_async"); if (rcj) return rcj; }      // (before any capture begins)
     step_commit_motion(c); step_state_replaced(c);
     if (c->fs_seq_step) {                                      // the step-wise fast path pointed the frame scalars at its own three poses
         hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, c->stream, c->fs, c->odo_seq, c->seqF, c->p.a1, c->p.a2, c->p.a3, c->p.a4);
@@ -1108,7 +1162,7 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
         // run's first frame takes the launch sequence that reads those rows as they are (k_project_motion, k_pxy; replay_motion_mode), eagerly; its tail writes the
         // canonical rows, and the frames behind it run the default sequence.
         launch_set_run(c->stream, c->fs, first, clear, traj);
-        replay_one_frame(c);
+        replay_one_frame(c, mode);
         set_null_canonical(c);
         c->async_pending = true; c->phase = 0; c->frame_updated = false; clear = 0;
         first += 1; count -= 1;
@@ -1117,27 +1171,29 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
     }
     launch_set_run(c->stream, c->fs, first, clear, traj);
     // "table" mode: the first frame's table of robot poses (the frames after it get theirs from their predecessor's tail)
-    const FrameForm ff = frame_form(c);
+    // (a joint frame is always the plain form: nothing is prepared in front of it)
+    const FrameForm ff = joint ? FORM_PLAIN : frame_form(c);
     if (ff.robot_table) srukf_launch_sigr_rows(c->stream, d, c->w, c->X, c->S, c->sigR, c->fs, c->red_iperm, c->red_r);
     // "fused tail" mode: ... and the first frame's projection (k_project_table); every later frame is projected by its predecessor's tail
     if (ff.fused_tail()) seq_predict_fused(c, ff);
     if (c->use_graph && !c->profiling) {
         // every per-frame argument lives in HBM (frame counter, staged inputs, trajectory base), so ONE
         // captured frame replays for all frames: the 45 launches cost one hipGraphLaunch on the host
-        if (!c->graph_exec) {
-            int rc = capture_frames(c, 1, &c->graph, &c->graph_exec); if (rc) return rc;
+        ReplayGraphs& g = replay_graphs(c, mode);               // (per mode: a BATCHED call never replays a captured JOINT frame, nor the other way round)
+        if (!g.one_exec) {
+            int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec); if (rc) return rc;
             // and a graph of SRUKF_GRAPH_FRAMES consecutive frames: one host launch per 8 frames keeps the host
             // ahead of the device when several filters share one host thread
-            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, &c->graph8, &c->graph8_exec); if (rc) return rc;
+            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec); if (rc) return rc;
         }
-        if (c->graphN_exec && c->graphN_frames == count) HIPCHK(c, hipGraphLaunch(c->graphN_exec, c->stream));   // srukf_prepare_frames
+        if (g.block_exec && g.block_frames == count) HIPCHK(c, hipGraphLaunch(g.block_exec, c->stream));   // srukf_prepare_frames / srukf_prepare_frames_mode
         else {
             int f = 0;
-            for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(c->graph8_exec, c->stream));
-            for (; f < count; f++) HIPCHK(c, hipGraphLaunch(c->graph_exec, c->stream));
+            for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(g.eight_exec, c->stream));
+            for (; f < count; f++) HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
         }
     } else {
-        for (int f = 0; f < count; f++) replay_one_frame(c);
+        for (int f = 0; f < count; f++) replay_one_frame(c, mode);
     }
     // fp32 storage in "fused tail" mode: S and X are rounded as they are written; the float copies (srukf_get_state_f32) once per run
     if (storage_f32_like(c) && ff.fused_tail()) quantize_state(c);
@@ -1147,7 +1203,7 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
     return SRUKF_OK;
 }
 
-// Synchronous form.  Unlike the asynchronous replay it never returns SRUKF_ERR_CLAMP_PENDING: the state before the
+// Synchronous form (BATCHED or JOINT frames).  Unlike the asynchronous replay it never returns SRUKF_ERR_CLAMP_PENDING: the state before the
 // block is kept, and when a frame is flagged (theta clamp of the modified Cholesky, SLAM.cpp:2279-2285, or an abandoned
 // persistent launch) the block is rewound to that state, the frames before the flagged one are replayed, the flagged
 // frame runs on the exact path, and the replay continues behind it.
@@ -1190,9 +1246,17 @@ int srukf_run_frames(srukf_ctx* c, int first, int count, int mode, double* traj_
             if (rc == SRUKF_OK) rc = srukf_synchronize(c);
             if (rc != SRUKF_OK) break;                                    // (the same frames passed a moment ago)
         }
-        rc = run_staged_frame_exact(c, fc, dt + (size_t)8 * (fc - first));
+        rc = run_staged_frame_exact(c, fc, dt + (size_t)8 * (fc - first), mode);
         if (rc != SRUKF_OK) break;
         done = fc - first + 1;
+    }
+    if (rc == SRUKF_ERR_UNSUPPORTED && c->joint_bad_host) {
+        // a joint frame's inputs were not finite (srukf_synchronize, or the flagged frame's repeat, names frame and row): the block leaves nothing behind — the checkpoint
+        // comes back (the state before the call; behind a flagged frame of the same block, the state behind that frame)
+        const std::string why = c->err;
+        checkpoint(false);
+        hipStreamSynchronize(c->stream);
+        c->err = why;
     }
     if (traj_host && rc == SRUKF_OK) hipMemcpy(traj_host, dt, sizeof(double) * 8 * (size_t)count, hipMemcpyDeviceToHost);
     srukf_dfree(dt);
@@ -1228,9 +1292,12 @@ int srukf_synchronize(srukf_ctx* c)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
+    c->joint_bad_host = false;
     if (c->async_pending) {
         c->async_pending = false;
         int rc = read_fs(c); if (rc) return rc;
+        // joint frames: the sticky pair k_joint_dx left (first hit).  A clamp flag of an EARLIER frame goes first: from that frame on nothing is valid anyway
+        if (c->hfs->joint_bad_frame > 0 && !(c->hfs->clamp_rows > 0 && c->hfs->clamp_frame < c->hfs->joint_bad_frame - 1)) return joint_bad_report(c);
         if (c->hfs->clamp_rows > 0) {
             c->clamp_frame_host = c->hfs->clamp_frame; c->clamp_row_host = c->hfs->clamp_first;
             char b[220]; snprintf(b, sizeof b, "GMW theta clamp active on %d pivot rows (first row %d), first in staged frame %d, during async frames%s", c->hfs->clamp_rows, c->hfs->clamp_first, c->hfs->clamp_frame,

@@ -147,40 +147,59 @@ static int step_predict_slow(srukf_ctx* c, const double odo_prev[3], const doubl
 }
 
 static int step_update_slow(srukf_ctx* c, const double* z, const int* matched, int reorder, int mode, int nm);
-// srukf_update_joint's mode on the slow form (internal: not a value of srukf_update's mode argument): BATCHED in everything but the launches that form U^T and the state update
-constexpr int STEP_UPDATE_JOINT = 2;
+// srukf_update_joint's mode on the slow form (SRUKF_UPDATE_JOINT; not a value srukf_update accepts): BATCHED in everything but the launches that form U^T and the state update
+constexpr int STEP_UPDATE_JOINT = SRUKF_UPDATE_JOINT;
+
+namespace srukf_impl {
+// the joint update's three work buffers (map-size scope), allocated by whoever needs them first — never inside a stream capture: the staged replay calls this before it
+// captures a frame.  what: the caller's name for the error text
+int joint_ensure(srukf_ctx* c, const char* what)
+{
+    if (c->jointW) return SRUKF_OK;
+    const KDims& d = c->d;
+    const size_t mp = d.mp, ldw = joint_work_ld(d.mp, d.np);
+    if (srukf_dmalloc(&c->jointZd, sizeof(double) * joint_dev_rows(d.Na) * mp) != hipSuccess || srukf_dmalloc(&c->jointW, sizeof(double) * mp * ldw) != hipSuccess ||
+        srukf_dmalloc(&c->jointRd, sizeof(double) * (mp * 64 + 1)) != hipSuccess) {
+        (void)hipGetLastError();
+        for (double** q : { &c->jointZd, &c->jointW, &c->jointRd }) { if (*q) srukf_dfree_on(*q, c->stream); *q = nullptr; }
+        c->err = std::string(what) + ": out of device memory (joint update work buffers)"; return SRUKF_ERR_NOMEM;
+    }
+    return SRUKF_OK;
+}
 
 // The joint update's launches in k_gain's place (srukf_joint.hip): behind seq_pxy, from the frame's Z, h, visible and k_pxy's products to U^T in
-// c->Ut (state order) and X += U w.  dx_pending stays false: the state update is applied here.  One round trip for the status word before anything touches the state
-static int seq_joint(srukf_ctx* c, const double* z_dev, const int* m_dev)
+// c->Ut (state order; with permuted columns in c->Utp too where the rank-aware operands exist) and X += U w.  dx_pending stays false: the state update is applied here.
+// z_dev / m_dev: this frame's measurements and matches on the device (null: the staged sequence's rows of the frame in hand, as in seq_gain).  Launches only: joint_ensure
+// has run, nothing waits for the host — a frame whose status word comes out set leaves X alone, U^T zero and the frame scalars' sticky pair (srukf_synchronize)
+void seq_joint_launches(srukf_ctx* c, const double* z_dev, const int* m_dev)
 {
     const KDims& d = c->d;
     const size_t mp = d.mp, ldw = joint_work_ld(d.mp, d.np);
-    if (!c->jointW) {
-        if (srukf_dmalloc(&c->jointZd, sizeof(double) * joint_dev_rows(d.Na) * mp) != hipSuccess || srukf_dmalloc(&c->jointW, sizeof(double) * mp * ldw) != hipSuccess ||
-            srukf_dmalloc(&c->jointRd, sizeof(double) * (mp * 64 + 1)) != hipSuccess) {
-            (void)hipGetLastError();
-            for (double** q : { &c->jointZd, &c->jointW, &c->jointRd }) { if (*q) srukf_dfree_on(*q, c->stream); *q = nullptr; }
-            c->err = "update_joint: out of device memory (work buffers)"; return SRUKF_ERR_NOMEM;
-        }
-    }
     int* status = (int*)(c->jointRd + mp * 64);
     const double mm = d.mp, nn = d.n, kk = 2.0 * d.Na;
-    {
-        ProfScope ps(c, KC_GAIN, mm * mm * kk + mm * mm * mm / 3.0 + mm * mm * (nn + 1) + 2.0 * mm * nn, 8.0 * (kk * mm * 2 + 3.0 * mm * (double)ldw + 2.0 * mm * nn));
-        launch_joint_form(c->stream, d, c->w, c->Z, c->vis, m_dev, c->Si, c->Ut, c->PxyR, c->h, z_dev, c->jointZd, c->jointW, status);
-        launch_joint_factor(c->stream, d, c->jointW, c->jointRd, status);
-        launch_joint_dx(c->stream, d, c->jointW, c->jointRd, status, c->Ut, c->X, c->fs);
-    }
+    ProfScope ps(c, KC_GAIN, mm * mm * kk + mm * mm * mm / 3.0 + mm * mm * (nn + 1) + 2.0 * mm * nn, 8.0 * (kk * mm * 2 + 3.0 * mm * (double)ldw + 2.0 * mm * nn));
+    launch_joint_form(c->stream, d, c->w, JointFrame{ z_dev, m_dev, c->z_seq, c->m_seq, c->fs }, c->Z, c->vis, c->Si, c->Ut, c->PxyR, c->h, c->jointZd, c->jointW, status);
+    launch_joint_factor(c->stream, d, c->jointW, c->jointRd, status);
+    launch_joint_dx(c->stream, d, c->jointW, c->jointRd, status, c->Ut, c->X, c->fs, rank_args(c));
+    c->dx_pending = false;
+}
+}  // namespace srukf_impl
+
+// ... of the step-wise call: one round trip for the status word before anything touches the state
+static int seq_joint(srukf_ctx* c, const double* z_dev, const int* m_dev)
+{
+    const KDims& d = c->d;
+    int rc = joint_ensure(c, "update_joint"); if (rc) return rc;
+    seq_joint_launches(c, z_dev, m_dev);
+    const int* status = (const int*)(c->jointRd + (size_t)d.mp * 64);
     int* hst = (int*)(c->hstage + 6 * (size_t)d.N + 8);
     HIPCHK(c, hipMemcpyAsync(hst, status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (*hst != 0) {
-        // Pzz is a Gram matrix plus the noise blocks: the inputs were not finite.  k_joint_dx has left X alone; S has not been touched
-        char b[160]; snprintf(b, sizeof b, "update_joint: non-positive pivot in the innovation covariance (row %d): the frame's inputs are not finite; the state is unchanged", *hst - 1);
+        // Pzz is a Gram matrix plus the noise blocks: the inputs were not finite (or the innovation itself was not).  k_joint_dx has left X alone; S has not been touched
+        char b[200]; snprintf(b, sizeof b, "update_joint: non-positive pivot in the innovation covariance or non-finite innovation (row %d): the frame's inputs are not finite; the state is unchanged", *hst - 1);
         c->err = b; return SRUKF_ERR_UNSUPPORTED;
     }
-    c->dx_pending = false;
     return SRUKF_OK;
 }
 

@@ -1,13 +1,16 @@
 // cslam_step_bench — wall-clock frame rate of the DROP-IN path: what a host that binds this library the way the MFC view binds the reference's
 // CSLAM gets per frame (SLAM.cpp:87-112, called from MonoSLAMView.cpp:499-572): predict, host (or device) data association, update — one frame at a
 // time, with the host round trips in between.  bench.py's headline is the staged replay (inputs resident in HBM, no host in the loop); this is the other number.
-//   cslam_step_bench scene.bin odometry.txt mode=<capi|facade|assoc> [frames=K] [warmup=W] [hint=0|1] [set=key:value ...]
+//   cslam_step_bench scene.bin odometry.txt mode=<capi|facade|assoc|replay> [frames=K] [warmup=W] [hint=0|1] [set=key:value ...]
 //     capi   : srukf_predict_motion -> srukf_predict_measurement (D->H h, Si, visible) -> host association (matched = visible, z from the scene)
 //              -> srukf_update (H->D) -> srukf_get_robot (the pose and robot block RobotPath.txt records, SLAM.cpp:3539-3556)
 //     facade : monoslam::CSLAM::SLAM() with the same association as a callback (what cslam_replay does), display refresh and mirrors included
 //     assoc  : capi with srukf_associate (wrapPatch + dataAssociation on the device, SLAM.cpp:1803-2009) on a 640 x 480 gray frame between predict and
 //              update.  The frame is a static synthetic texture the landmarks' init patches were cut from, so the templates stop correlating as the
 //              robot moves: the launches and their D->H copy are what is timed, the filter itself is driven by the scene's z / matched (stated in the output).
+//     replay : the staged replay, for comparison on the same scene file: srukf_stage_sequence (every landmark offered as matched; the device's visibility decides,
+//              as in capi), then srukf_run_frames_async + srukf_synchronize in blocks of `frames` (the warm-up frames first, as one block of their own), srukf_get_robot
+//              at the end.  Honours joint=1 (SRUKF_UPDATE_JOINT frames) and set=key:value; prints the same keys as capi (the per-call host times are zero)
 //     hint=1 : capi / assoc announce the NEXT frame's odometry with srukf_predict_motion_next before every update (a host that has its odometry
 //              file loaded, as the reference has: loadOdometryData reads it whole, SLAM.cpp:363-496)
 //     set=key:value : srukf_debug_set(ctx, key, value) after the context exists (capi / assoc; measurement switches, e.g. set=step_fuse_export:0)
@@ -39,7 +42,7 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 
 int main(int argc, char** argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: %s scene.bin odometry.txt mode=<capi|facade|assoc> [frames=K] [warmup=W] [hint=0|1]\n", argv[0]); return 2; }
+    if (argc < 4) { fprintf(stderr, "usage: %s scene.bin odometry.txt mode=<capi|facade|assoc|replay> [frames=K] [warmup=W] [hint=0|1]\n", argv[0]); return 2; }
     std::string mode = "capi";
     int K = 200, W = 20, hint = 0, churn = 0, ransac = 0, ellipsoids = 0, joint = 0;
     std::vector<std::pair<std::string, int>> sets;
@@ -82,6 +85,7 @@ int main(int argc, char** argv)
     char churn_json[900] = "";
     char ell_json[200] = "";
     int joint_flagged = 0;
+    const char* replay_form = "run_frames_async + synchronize";
     if (mode == "facade") {
         monoslam::CSLAM SLAM;
         SLAM.m_params.a1 = a4[0]; SLAM.m_params.a2 = a4[1]; SLAM.m_params.a3 = a4[2]; SLAM.m_params.a4 = a4[3];
@@ -158,6 +162,48 @@ int main(int argc, char** argv)
         for (int e = 0; e < 4; e++) pose[e] = SLAM.m_X_k.at(nn - 4 + e, 0);
         P4[0] = SLAM.m_P_k.at(nn - 4, nn - 4); P4[1] = SLAM.m_P_k.at(nn - 4, nn - 3); P4[4] = SLAM.m_P_k.at(nn - 3, nn - 4); P4[5] = SLAM.m_P_k.at(nn - 3, nn - 3);
         if (!churn && SLAM.m_nMapFeatures != N) { fprintf(stderr, "the map changed size (%d landmarks left)\n", SLAM.m_nMapFeatures); return 1; }
+    } else if (mode == "replay") {
+        srukf_params p;
+        srukf_default_params(&p);
+        p.a1 = a4[0]; p.a2 = a4[1]; p.a3 = a4[2]; p.a4 = a4[3];
+        srukf_ctx* c = nullptr;
+        int rc = srukf_create(&c, N, &p, 0, nullptr);
+        if (rc) { fprintf(stderr, "srukf_create: %d %s\n", rc, srukf_last_error(nullptr)); return 1; }
+#define CK(call) do { rc = (call); if (rc) { fprintf(stderr, "%s: %d %s\n", #call, rc, srukf_last_error(c)); return 1; } } while (0)
+        for (auto& kv : sets) CK(srukf_debug_set(c, kv.first.c_str(), kv.second));
+        CK(srukf_set_state(c, X0.data(), S0.data()));
+        const int upd = joint ? SRUKF_UPDATE_JOINT : SRUKF_UPDATE_BATCHED;
+        std::vector<int> m((size_t)(W + K) * N, 1);               // the host's association of capi: every visible landmark found where the scene put it
+        CK(srukf_stage_sequence(c, W + K, odo.data(), z.data(), m.data()));
+        // rc of a block: 0, 1 (error, reported) or 2: a frame was flagged (theta clamp; srukf_synchronize's SRUKF_ERR_CLAMP_PENDING) and the state is no longer valid
+        auto block = [&](int first, int count) -> int {
+            rc = srukf_run_frames_async(c, first, count, upd, nullptr);
+            if (rc == SRUKF_OK) rc = srukf_synchronize(c);
+            if (rc == SRUKF_ERR_CLAMP_PENDING) return 2;
+            if (rc) { fprintf(stderr, "replay block [%d, %d): %d %s\n", first, first + count, rc, srukf_last_error(c)); return 1; }
+            return 0;
+        };
+        int st = W > 0 ? block(0, W) : 0;
+        double t0 = now_s();
+        if (st == 0) st = block(W, K);
+        if (st == 1) return 1;
+        if (st == 2) {
+            // as a host of the asynchronous calls is told to: back to the state the run started from, and through srukf_run_frames, which repeats a flagged frame on the
+            // exact path by itself; the timed block is then that call ("replay_form" says which one was timed)
+            replay_form = "run_frames (a block was flagged)";
+            CK(srukf_set_state(c, X0.data(), S0.data()));
+            if (W > 0) CK(srukf_run_frames(c, 0, W, upd, nullptr));
+            long long e0 = 0, e1 = 0;
+            srukf_debug_get(c, "exact_frames", &e0);
+            t0 = now_s();
+            CK(srukf_run_frames(c, W, K, upd, nullptr));
+            srukf_debug_get(c, "exact_frames", &e1);
+            joint_flagged = (int)(e1 - e0);
+        }
+        CK(srukf_get_robot(c, pose, P4));
+        t_timed = now_s() - t0;
+        srukf_destroy(c);
+#undef CK
     } else {
         srukf_params p;
         srukf_default_params(&p);
@@ -225,8 +271,9 @@ int main(int argc, char** argv)
         srukf_debug_get(c, "meas_flag_ticks", &flag_ticks);
         srukf_destroy(c);
     }
-    char joint_json[80] = "";
+    char joint_json[200] = "";
     if (joint) snprintf(joint_json, sizeof joint_json, "\"joint\": 1, \"joint_flagged_frames\": %d, ", joint_flagged);
+    if (mode == "replay") snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"replay_form\": \"%s\", \"exact_frames\": %d, ", replay_form, joint_flagged);
     printf("{\"mode\": \"%s\", %s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
            "\"pose\": [%.17g, %.17g, %.17g, %.17g], \"P_robot\": [%.17g, %.17g, %.17g, %.17g], \"device_matches\": %lld, \"stats_flag_us_into_first_launch\": %.2f, \"host_us_per_call\": {\"predict_motion\": %.2f, \"predict_measurement\": %.2f, \"association\": %.2f, \"update\": %.2f, \"get_robot\": %.2f}, "
            "\"filter_driven_by\": \"scene z / matched (host association)\"}\n",

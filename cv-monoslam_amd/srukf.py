@@ -23,7 +23,7 @@ EXPORTS = [
     "srukf_abi_version", "srukf_default_params", "srukf_create", "srukf_destroy", "srukf_reset", "srukf_last_error",
     "srukf_set_state", "srukf_get_state", "srukf_set_state_device", "srukf_get_state_device", "srukf_get_robot",
     "srukf_get_landmark_block", "srukf_get_landmarks_cartesian", "srukf_get_frame_view", "srukf_get_covariance", "srukf_predict_motion", "srukf_predict_motion_next", "srukf_predict_measurement",
-    "srukf_update", "srukf_update_joint", "srukf_set_new_landmarks", "srukf_add_landmarks", "srukf_delete_landmark", "srukf_set_storage", "srukf_set_exclusive", "srukf_set_rank_aware", "srukf_null_directions", "srukf_run_frames_batch", "srukf_prepare_frames", "srukf_debug_poke_state", "srukf_get_state_f32", "srukf_set_landmark_appearance", "srukf_associate", "srukf_get_match_patch", "srukf_stage_sequence", "srukf_run_frames_async", "srukf_run_frames", "srukf_synchronize", "srukf_set_profiling",
+    "srukf_update", "srukf_update_joint", "srukf_set_new_landmarks", "srukf_add_landmarks", "srukf_delete_landmark", "srukf_set_storage", "srukf_set_exclusive", "srukf_set_rank_aware", "srukf_null_directions", "srukf_run_frames_batch", "srukf_prepare_frames", "srukf_prepare_frames_mode", "srukf_debug_poke_state", "srukf_get_state_f32", "srukf_set_landmark_appearance", "srukf_associate", "srukf_get_match_patch", "srukf_stage_sequence", "srukf_run_frames_async", "srukf_run_frames", "srukf_synchronize", "srukf_set_profiling",
     "srukf_clamp_info", "srukf_debug_set", "srukf_debug_switch_at", "srukf_debug_get", "srukf_debug_copy", "srukf_debug_upload", "srukf_debug_split_replay", "srukf_debug_gmw_stamps", "srukf_debug_starve_workers", "srukf_debug_allow_mixed", "srukf_profile_count", "srukf_profile_get", "srukf_profile_reset", "srukf_dims", "srukf_gmw_host",
     "srukf_project_host", "srukf_detect_features", "srukf_capture_appearance", "srukf_get_landmark_record", "srukf_insert_landmarks",
     "srukf_ransac_consensus", "srukf_repredict_measurement",
@@ -39,7 +39,7 @@ STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", 
 
 STORAGE_F64, STORAGE_F32, STORAGE_F32_MIXED = 0, 1, 2
 GPU_SHARED, GPU_EXCLUSIVE, GPU_SHARED_PER_PANEL = 0, 1, 2          # srukf_set_exclusive
-UPDATE_SEQUENTIAL, UPDATE_BATCHED = 0, 1
+UPDATE_SEQUENTIAL, UPDATE_BATCHED, UPDATE_JOINT = 0, 1, 2          # UPDATE_JOINT: the staged replay only (run_frames*, prepare_frames); step-wise: update_joint
 NEED_REORDER, NEEDNOT_REORDER = 0, 1
 
 
@@ -163,6 +163,8 @@ def load_library(path=None):
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
     L.srukf_prepare_frames.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "srukf_prepare_frames_mode"):        # (idem: the joint update as a mode of the staged replay)
+        L.srukf_prepare_frames_mode.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.srukf_debug_poke_state.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double]
     L.srukf_run_frames_batch.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.srukf_null_directions.argtypes = [C.c_void_p]
@@ -559,9 +561,10 @@ class Filter:
         self._chk(self._lib.srukf_stage_sequence(self._h, F, _d(odo), _d(z), _i(m)))
         self.F = F
 
-    def prepare_frames(self, count):
-        """Capture `count` staged frames as one graph for the following run_frames_async(*, count) calls (nothing runs)."""
-        self._chk(self._lib.srukf_prepare_frames(self._h, int(count)))
+    def prepare_frames(self, count, mode=UPDATE_BATCHED):
+        """Capture `count` staged frames of `mode` as one graph for the following run_frames_async(*, count, mode) calls (nothing runs)."""
+        if mode == UPDATE_BATCHED: self._chk(self._lib.srukf_prepare_frames(self._h, int(count)))
+        else: self._chk(self._lib.srukf_prepare_frames_mode(self._h, int(count), int(mode)))
 
     def run_frames_async(self, first, count, mode=UPDATE_BATCHED, d_traj_ptr=None):
         self._chk(self._lib.srukf_run_frames_async(self._h, first, count, mode,

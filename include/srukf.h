@@ -68,7 +68,9 @@ typedef struct srukf_params {
  *              measurement columns u:  S <- gmw(S^T S - u u^T)   (SLAM.cpp:2066-2095, 2116-2154).
  *  BATCHED   : one  S <- gmw(S^T S - U U^T)  per frame (gains do not depend on the S updates,
  *              SLAM.cpp:2070-2080; see DESIGN.md for the equivalence evidence).               */
-typedef enum srukf_update_mode { SRUKF_UPDATE_SEQUENTIAL = 0, SRUKF_UPDATE_BATCHED = 1 } srukf_update_mode;
+/* SRUKF_UPDATE_JOINT: the joint measurement update (below) as a mode of the staged replay (srukf_run_frames, srukf_run_frames_async, srukf_prepare_frames_mode).  srukf_update
+ * does not take it (its step-wise entry is srukf_update_joint), nor does srukf_run_frames_batch (SRUKF_ERR_UNSUPPORTED). */
+typedef enum srukf_update_mode { SRUKF_UPDATE_SEQUENTIAL = 0, SRUKF_UPDATE_BATCHED = 1, SRUKF_UPDATE_JOINT = 2 } srukf_update_mode;
 
 /* SLAM.cpp:36-37 FLAG_4_NEED_REORDER(0) / FLAG_4_NEEDNOT_REORDER(1) */
 typedef enum srukf_reorder { SRUKF_NEED_REORDER = 0, SRUKF_NEEDNOT_REORDER = 1 } srukf_reorder;
@@ -182,9 +184,11 @@ int  srukf_update(srukf_ctx* ctx, const double* z, const int* matched, int reord
  *   across landmarks); the motion-noise points stay in the off-diagonal blocks.  Pxy is what SRUKF_UPDATE_BATCHED forms from the single prior.  With one active
  *   landmark the call equals srukf_update(BATCHED) for that landmark.  The refactorisation is srukf_update's own (theta check, exact path behind it;
  *   SRUKF_NEED_REORDER as there).  No match: no-op (2050-2051).  Runs on the step-wise path's slow form (a frame predicted on the fast path is predicted again);
- *   srukf_repredict_measurement and the RANSAC calls work behind it.  SRUKF_ERR_UNSUPPORTED: SRUKF_STORAGE_F32_MIXED; or a non-positive pivot in Pzz (inputs not
- *   finite: the state is left as predicted, srukf_last_error names the row).  srukf_clamp_info behind a SRUKF_NEEDNOT_REORDER call: (0, first flagged pivot row)
- *   when the refactorisation was flagged and went to the exact path, (-1, -1) when it was not.  Not part of the staged replay, the graphs or srukf_run_frames_batch. */
+ *   srukf_repredict_measurement and the RANSAC calls work behind it.  SRUKF_ERR_UNSUPPORTED: SRUKF_STORAGE_F32_MIXED; or a non-positive pivot in Pzz or an innovation
+ *   z - h that is not finite (inputs not finite: the state is left as predicted, srukf_last_error names the row).  srukf_clamp_info behind a SRUKF_NEEDNOT_REORDER call: (0, first flagged pivot row)
+ *   when the refactorisation was flagged and went to the exact path, (-1, -1) when it was not.
+ *   In the staged replay the same update is the mode SRUKF_UPDATE_JOINT of srukf_run_frames / srukf_run_frames_async / srukf_prepare_frames_mode (captured frames of its own,
+ *   no host inside a block; see there); the step-wise fast path and srukf_run_frames_batch do not have it. */
 int  srukf_update_joint(srukf_ctx* ctx, const double* z, const int* matched, int reorder);
 
 /* ---- 1-point RANSAC (KalmanUpdate's isUseRANSAC branch, SLAM.cpp:2097-2103: onePointRansacHypotheses, updateLowInnovationInliers, rescueHighInnovationInliers,
@@ -436,27 +440,39 @@ int  srukf_stage_sequence(srukf_ctx* ctx, int n_frames, const double* odo, const
 /* Run frames [first, first+count) back to back (predictMotion + predictMeasurement +
  * KalmanUpdate per frame, no host round trip in between), asynchronously on the context's
  * stream.  traj, if not NULL, is a DEVICE buffer of count*8 doubles receiving per frame
- * (x, y, z, theta, P00, P01, P10, P11) — the RobotPath.txt columns of SLAM.cpp:3549-3556. */
+ * (x, y, z, theta, P00, P01, P10, P11) — the RobotPath.txt columns of SLAM.cpp:3549-3556.
+ * mode: SRUKF_UPDATE_BATCHED, or SRUKF_UPDATE_JOINT: every frame's update is the joint measurement update (srukf_update_joint's) on the plain frame form
+ *   (k_motion, k_project, k_pxy, the joint launches, the frame-tail refactorisation), whatever the launch switches say, from captured frames of its own: calls in the two
+ *   modes may alternate.  SRUKF_ERR_UNSUPPORTED for SRUKF_UPDATE_SEQUENTIAL, and for JOINT in SRUKF_STORAGE_F32_MIXED (as srukf_update_joint) and in SRUKF_STORAGE_F32
+ *   (the replay's frame tails round in other launches than the step-wise call's checked refactorisation; the two are not shown to round at the same points, so the mode
+ *   is refused there: use srukf_update_joint). */
 int  srukf_run_frames_async(srukf_ctx* ctx, int first, int count, int mode, double* d_traj);
 /* Synchronous form: runs the frames, waits, and copies the trajectory to the HOST buffer traj_host[count*8] (may be
  * NULL).  Never returns SRUKF_ERR_CLAMP_PENDING: the state before the block is kept on the device, and when a frame
  * needs the reference's theta-clamp branch of the modified Cholesky (SLAM.cpp:2279-2285) the block is rewound, the
  * frames before it are replayed, that frame runs on the exact column-by-column path (as srukf_update does) and the
- * replay continues behind it. */
+ * replay continues behind it (a JOINT frame repeats with the joint update in front of the checked refactorisation).  SRUKF_ERR_UNSUPPORTED from a JOINT block whose
+ * inputs were not finite (srukf_synchronize, below): the state the block started from is restored. */
 int  srukf_run_frames(srukf_ctx* ctx, int first, int count, int mode, double* traj_host);
 /* Wait for the stream; reports SRUKF_ERR_CLAMP_PENDING if any async frame needed the reference's theta-clamp branch of
  * the modified Cholesky: the frames BEFORE the first such frame are valid, that frame and the later ones are not
- * (srukf_clamp_info names it; restore the state the block started from and use srukf_run_frames or the step-wise API). */
+ * (srukf_clamp_info names it; restore the state the block started from and use srukf_run_frames or the step-wise API).
+ * SRUKF_ERR_UNSUPPORTED behind SRUKF_UPDATE_JOINT frames: a frame's innovation covariance had a non-positive pivot, or its innovation was not finite — the frame's
+ * inputs were not finite.  srukf_last_error names "frame f, row r" (the first such frame); that frame kept its predicted mean and took no update, the later ones ran to
+ * their end on finite data, nothing in the state is NaN: the frames before f are valid, f and the later ones are not. */
 int  srukf_synchronize(srukf_ctx* ctx);
 /* Optional: capture a block of `count` staged frames as ONE graph for the following srukf_run_frames_async calls with that count
  * (default: graphs of 8 frames + single frames; the device idles ~10 us between two graph launches, which shows in short blocks).
  * Nothing is executed.  1 <= count <= 512. */
 int  srukf_prepare_frames(srukf_ctx* ctx, int count);
+/* ... for the frames of `mode` (SRUKF_UPDATE_BATCHED: srukf_prepare_frames; SRUKF_UPDATE_JOINT): each mode keeps its own block graph. */
+int  srukf_prepare_frames_mode(srukf_ctx* ctx, int count, int mode);
 /* B filters (independent sequences over the same frame range: the Monte-Carlo use, MonoSLAMView.cpp:526-572 once per run) replayed
  * concurrently on one GPU: frames are issued round-robin in chunks so that the filters' launches interleave, then all are awaited;
  * filters still in SRUKF_GPU_EXCLUSIVE are switched to SRUKF_GPU_SHARED.  A filter with a flagged frame in its block is rerun
  * alone through srukf_run_frames.  ctxs[b] must have its own sequence staged (srukf_stage_sequence) and must live on the same
- * device.  traj_host: [B][count][8] or NULL; status: [B] per-filter return codes or NULL.  Returns the first error. */
+ * device.  traj_host: [B][count][8] or NULL; status: [B] per-filter return codes or NULL.  Returns the first error.
+ * SRUKF_UPDATE_JOINT: SRUKF_ERR_UNSUPPORTED, nothing runs (srukf_last_error of every filter says so). */
 int  srukf_run_frames_batch(srukf_ctx* const* ctxs, int B, int first, int count, int mode, double* traj_host, int* status);
 /* First flagged staged frame / pivot row of the last SRUKF_ERR_CLAMP_PENDING (-1, -1: none).  Either may be NULL. */
 int  srukf_clamp_info(srukf_ctx* ctx, int* frame, int* row);
