@@ -518,6 +518,7 @@ int srukf_reset(srukf_ctx* c)
     c->frame_valid = false; c->bgr_valid = false;                // (the held frame goes with the state, gray and colour)
     archive_free(c->archive, c->stream);                         // (and the archive: srukf_archive_set)
     match_drop(c);                                               // (and the score maps of srukf_associate_checked)
+    images_drop(c, c->stream);                                   // (and the staged images of srukf_stage_images)
     if (c->red_r) { c->red_r = 0; drop_graphs(c); }            // the state is the robot block only: nothing to reduce until a state arrives
     return SRUKF_OK;
 }

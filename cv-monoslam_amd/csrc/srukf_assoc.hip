@@ -208,7 +208,47 @@ __global__ __launch_bounds__(256) void k_associate(KDims d, srukf_params p, cons
     }
 }
 
+// k_associate_staged: k_associate for a frame of the staged replay (srukf_run_images*).  The frame is image fs->frame of the staged
+// stack, and the results go where the frame's update reads them — the rows of frame fs->frame in the staged z_seq / m_seq (k_gain and the joint kernels take
+// z_seq + fs->frame * 2N) — and into the per-frame record beside them (corr, the frame's visible and predicted pixels).  The same front, pixel rule, threshold
+// and zeroing as k_associate; every dependency is a launch boundary on the stream.  A frame counter outside the staged stack writes nothing.
+__global__ __launch_bounds__(256) void k_associate_staged(KDims d, srukf_params p, StagedAssoc a, const double* __restrict__ h, const double* __restrict__ Si,
+                                                          const int* __restrict__ vis, const int* __restrict__ has_app, const unsigned char* __restrict__ matchPatch)
+{
+    __shared__ double tm[PT_TMPL_BYTES];
+    __shared__ double red[8];
+    __shared__ double bestv[256];
+    __shared__ int besti[256];
+    __shared__ double rg[PT_REGION_W * PT_REGION_W];
+    const int k = blockIdx.x, tid = threadIdx.x, N = d.N;
+    const int f = a.fs->frame;
+    if (f < 0 || f >= a.frames) return;
+    double* z = a.z_seq + (size_t)f * 2 * N;
+    int* matched = a.m_seq + (size_t)f * N;
+    double* corr = a.corr_seq + (size_t)f * N;
+    const int v = vis[k];
+    if (tid == 0) { a.vis_seq[(size_t)f * N + k] = v; a.h_seq[(size_t)f * 2 * N + 2 * k] = h[2 * k]; a.h_seq[(size_t)f * 2 * N + 2 * k + 1] = h[2 * k + 1]; }
+    if (!v || !has_app[k]) { if (tid == 0) { matched[k] = 0; corr[k] = 0.0; z[2 * k] = 0.0; z[2 * k + 1] = 0.0; } return; }   // 1946
+    const unsigned char* image = a.images + (size_t)f * (size_t)((int)p.image_w * (int)p.image_h);
+    const MatchWindow w = match_front(k, p, image, h, Si, matchPatch, tm, red, rg, bestv, besti, [](int, double) {});
+    if (tid == 0) {
+        const double maxVal = bestv[0];
+        const int c = besti[0];
+        corr[k] = maxVal;
+        if (maxVal > 0.8) {                                                                             // 1989
+            z[2 * k] = (c % w.wx) - w.half_x + w.px;                                                    // 1991-1992
+            z[2 * k + 1] = (c / w.wx) - w.half_y + w.py;
+            matched[k] = 1;
+        } else { z[2 * k] = 0.0; z[2 * k + 1] = 0.0; matched[k] = 0; }
+    }
+}
+
 extern "C" {
+void srukf_launch_associate_staged(hipStream_t st, KDims d, srukf_params p, StagedAssoc a, const double* h, const double* Si, const int* vis, const int* has_app,
+                                   const unsigned char* matchPatch)
+{
+    hipLaunchKernelGGL(k_associate_staged, dim3(d.N), dim3(256), 0, st, d, p, a, h, Si, vis, has_app, matchPatch);
+}
 void srukf_launch_warp_patch(hipStream_t st, KDims d, srukf_params p, const double* X, const double* xyz, const double* h,
                              const double* appR, const double* appT, const double* appPx, const unsigned char* initPatch,
                              const int* has_app, unsigned char* matchPatch)

@@ -1,7 +1,7 @@
 // srukf_ctx.h — what the host-side translation units of libsrukf_hip.so share: the context (struct srukf_ctx), the helpers behind the C-ABI.  Internal:
 // include/srukf.h is the boundary.  What the kernel files offer (launchers, size / table helpers, their argument structs) comes from srukf_launch.h, declared there only.
 //   srukf_api.hip     context lifetime, state accessors, the step-wise calls (predictMotion / predictMeasurement / KalmanUpdate), storage, profiling read-out
-//   srukf_replay.hip  the launch sequences of a frame (seq_*), the rank-aware null set, graph cache, staged replay (srukf_run_frames*)
+//   srukf_replay.hip  the launch sequences of a frame (seq_*), the rank-aware null set, graph cache, staged replay (srukf_run_frames*, srukf_run_images*)
 //   srukf_split.hip   split form of the persistent factorisation: side stream, probe, buffers
 //   srukf_batch.hip   batched replay (srukf_run_frames_batch)
 //   srukf_map.hip     map changes (srukf_add_landmarks / srukf_delete_landmark / srukf_insert_landmarks) and data association
@@ -80,6 +80,20 @@ struct ArchiveState {
     int L = 0;
     double *X6 = nullptr, *S66 = nullptr, *R = nullptr, *t = nullptr, *px = nullptr, *rob = nullptr, *out = nullptr, *hst = nullptr;
     unsigned char *patch = nullptr, *tmpl = nullptr;
+};
+
+// image runs of the staged replay (srukf_stage_images / srukf_run_images*): the staged gray frames [frames][image_h][image_w], the per-frame
+// record the association leaves beside the staged z_seq / m_seq rows it overwrites (corr_seq [F][N], vis_seq [F][N], h_seq [F][2N]), the Cartesian points the warp
+// reads (xyz, 3N: not c->G — nothing has shown G to be free inside a replayed block), and the block's checkpoint: X, S, the matchPatch array and whether the null rows
+// were canonical.  pending: the frames srukf_synchronize waits for are image frames (a flagged block comes back to the checkpoint there).  Captured frames of their own
+// per update mode.  Map-size scope, the staged sequence's lifetime: images_drop
+struct ImageReplay {
+    unsigned char *images = nullptr, *ck_tmpl = nullptr;
+    double *corr_seq = nullptr, *h_seq = nullptr, *xyz = nullptr, *ckS = nullptr, *ckX = nullptr;
+    int* vis_seq = nullptr;
+    int frames = 0;
+    bool pending = false, ck_canon = false;
+    ReplayGraphs graphs[2];
 };
 
 // ---- the context: who owns what across a map change ("who owns what across a map change") ----------------------
@@ -279,6 +293,7 @@ struct srukf_map_scope : srukf_life {
     // captured frames (staged inputs), replayed by srukf_run_frames_async: one set per update mode of the replay ([0] BATCHED, [1] JOINT: replay_graphs), so that a call in
     // one mode never replays the other's launch sequence; drop_graphs drops both
     ReplayGraphs graphs[2];
+    ImageReplay img;                       // srukf_stage_images / srukf_run_images* (captured frames with the association in them: never the ones above, nor the other way round)
     // the pool allocations among the members above (Si and vis are inside h, mcur inside zcur; ransac, gplan, gplan_red: ransac_scratch_free / gmw_plan_destroy).
     // A new buffer of this scope is added HERE
     template <class F> void each_device_buffer(F f) const {
@@ -287,7 +302,8 @@ struct srukf_map_scope : srukf_life {
                       S32, X32, U32, mx_part, mx_tasks, mx_tiles, A32, mxr_part, mxr_tasks, mxr_tiles, mxr_f64_tiles, mxr_xt,
                       perm, iperm, Sdis, pan[0], pan[1], red_perm, red_iperm, gdiag, shadowA, Utp, slabW, slabL, gsW, gsL, P1, pxy2_tiles, nskip,
                       red_head0_tiles, split_fold_list, red_syrk_tiles, ckS, ckX, syrk_tiles, pxy_tiles, syrk_head_tiles, syrk_head_tiles_b, fs,
-                      odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt, jointZd, jointW, jointRd };
+                      odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt, jointZd, jointW, jointRd,
+                      img.images, img.ck_tmpl, img.corr_seq, img.h_seq, img.xyz, img.ckS, img.ckX, img.vis_seq };
         for (void* q : b) f(q);
     }
 };
@@ -350,8 +366,9 @@ void launch_capture_patch(hipStream_t st, const unsigned char* img, int W, int f
 // ---- 1-point RANSAC (srukf_ransac.hip) ----
 void ransac_scratch_free(RansacScratch& s, hipStream_t st);
 
-// ---- srukf_associate_checked's buffers (srukf_map.hip) ----
+// ---- srukf_associate_checked's buffers, the appearance records (srukf_map.hip) ----
 void match_drop(srukf_ctx* c);
+int ensure_appearance(srukf_ctx* c);      // the per-landmark appearance records (and the handle's frame buffer), allocated and zeroed on first use
 
 // ---- archive search (srukf_archive.hip) ----
 void archive_free(ArchiveState& a, hipStream_t st);
@@ -460,6 +477,7 @@ void seq_joint_launches(srukf_ctx* c, const double* z_dev, const int* m_dev);
 int update_null_set(srukf_ctx* c);
 int mixed_red_ensure(srukf_ctx* c);
 void drop_graphs(srukf_map_scope* c);
+void images_drop(srukf_map_scope* c, hipStream_t st);      // the staged images, their record, checkpoint and captured frames go (the caller has synchronised the stream)
 void exact_path(srukf_ctx* c, const double* Gbuf, double* Sout);      // the exact column path for Gbuf -> Sout (D, theta, clamp count as side effects)
 void set_null_canonical(srukf_ctx* c);
 void canonicalize_null_rows(srukf_ctx* c);      // after update_null_set on a factor of the library's own making (NEED_REORDER, map changes): the next frame may take the fast path

@@ -62,6 +62,13 @@ struct RankExpandLaunch {
     const StepExport* step_export; double null_rel; unsigned int* fold_sync; int fold_words;
 };
 
+// k_associate_staged: the staged image stack and where frame fs->frame's rows go (frames: how many the stack and every per-frame array hold)
+struct StagedAssoc {
+    const unsigned char* images; int frames;
+    double* z_seq; int* m_seq; double* corr_seq; int* vis_seq; double* h_seq;
+    const FrameScalars* fs;
+};
+
 extern "C" {
 // ---- srukf_predict.hip ----
 void srukf_launch_landmarks_cartesian(hipStream_t st, KDims d, const double* X, const double* S, double* xyz, double* cov);
@@ -157,6 +164,10 @@ void srukf_launch_warp_patch(hipStream_t st, KDims d, srukf_params p, const doub
                              const double* appPx, const unsigned char* initPatch, const int* has_app, unsigned char* matchPatch);
 void srukf_launch_associate(hipStream_t st, KDims d, srukf_params p, const unsigned char* image, const double* h, const double* Si, const int* vis, const int* has_app,
                             const unsigned char* matchPatch, double* z, int* matched, double* corr);
+// k_associate_staged (image runs of the staged replay): frame fs->frame of the staged images [frames][image_h][image_w] is searched; z / matched go into that frame's
+// rows of the staged sequence (z_seq stride 2N, m_seq stride N), corr / visible / the predicted pixels into the record's (corr_seq, vis_seq stride N, h_seq stride 2N)
+void srukf_launch_associate_staged(hipStream_t st, KDims d, srukf_params p, StagedAssoc a, const double* h, const double* Si, const int* vis, const int* has_app,
+                                   const unsigned char* matchPatch);
 // res / scores: the packed result block and the score buffer (match_res, PT_SCORE_*: srukf_patch.h)
 void srukf_launch_associate_checked(hipStream_t st, KDims d, srukf_params p, MatchArgs ma, const unsigned char* image, const double* h, const double* Si, const int* vis,
                                     const int* has_app, const unsigned char* matchPatch, double* z, int* matched, double* corr, double* res, double* scores);

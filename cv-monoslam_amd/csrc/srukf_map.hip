@@ -22,7 +22,8 @@ struct MapTimer {
 };
 }
 
-static int ensure_appearance(srukf_ctx* c)
+namespace srukf_impl {
+int ensure_appearance(srukf_ctx* c)
 {
     int rc = ensure_image(c); if (rc) return rc;               // (the frame buffer is the handle scope's, the records are per map size: either may exist without the other)
     if (c->app_patch) return SRUKF_OK;
@@ -40,6 +41,7 @@ static int ensure_appearance(srukf_ctx* c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SRUKF_OK;
 }
+}  // namespace srukf_impl
 
 // the appearance records of landmarks `from` .. `from + count - 1` of `a` become the ones of landmarks `to` .. of `b` (map changes)
 static void copy_appearance(srukf_ctx* a, int from, srukf_ctx* b, int to, int count = 1)
@@ -85,6 +87,7 @@ void adopt_context(srukf_ctx* c, srukf_ctx* c2)
     std::swap(c->err, c2->err);                                  // (the text is the map change's: what its factorisation on c2 left, empty when nothing was abandoned)
     const int shared = c2->gmw_shared, tenants = c2->shared_tenants;      // (sharing the GPU is the handle's choice, the plans built for it are per map size: below)
     match_drop(c2);                                              // (the score maps of srukf_associate_checked go with the map they were made for)
+    images_drop(c2, c2->stream);                                 // (and the staged images: the scope that comes in has no staged sequence either)
     ctx_retire(c, c2);                                           // (not destroyed: revived when the map has this size again — ctx_obtain)
     c->phase = 0; c->frame_updated = false;                      // (whatever call sequence the numeric part ran on the new scope: the handle is between frames)
     if (shared != c->gmw_shared) set_shared(c, shared, tenants);

@@ -930,11 +930,20 @@ int read_fs_host(srukf_ctx* c)
 
 void drop_graphs(srukf_map_scope* c)
 {
-    for (ReplayGraphs& g : c->graphs) {                        // the captured frames of both update modes
+    for (ReplayGraphs* gs : { c->graphs, c->img.graphs }) for (int m = 0; m < 2; m++) {      // the captured frames of both update modes, without and with the association
+        ReplayGraphs& g = gs[m];
         for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec, &g.block_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
         for (hipGraph_t* q : { &g.one, &g.eight, &g.block }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
         g.block_frames = 0;
     }
+}
+
+void images_drop(srukf_map_scope* c, hipStream_t st)
+{
+    ImageReplay& im = c->img;
+    if (im.images) drop_graphs(c);                               // (the captured image frames hold these pointers)
+    for (void* b : { (void*)im.images, (void*)im.ck_tmpl, (void*)im.corr_seq, (void*)im.h_seq, (void*)im.xyz, (void*)im.ckS, (void*)im.ckX, (void*)im.vis_seq }) if (b) srukf_dfree_on(b, st);
+    im = ImageReplay{};
 }
 
 // shared: 0 exclusive, 1 shared (tenants persistent launches at a time), 2 one launch per panel
@@ -990,10 +999,35 @@ static void replay_one_frame(srukf_ctx* c, int mode)
     seq_refactor(c, refactor_frame_tail(c), ff);
 }
 
-static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge)
+// A frame of an image run (srukf_run_images*): the plain frame form as in replay_one_frame_joint, whatever "fused_motion" and its neighbours say,
+// with the association between k_pxy and what stands in k_gain's place.  Behind seq_pxy(FORM_PLAIN) the device holds h, Si, visible and the predicted pose in X: what
+// k_warp_patch and the matching front read (srukf_associate finds the same behind srukf_predict_measurement).  k_associate_staged writes this frame's rows of z_seq /
+// m_seq, which k_gain / the joint kernels then read as they read staged rows.  BATCHED: seq_gain_only — seq_gain is seq_pxy + seq_gain_only in this form (no gain fold
+// below "fused tail" mode), and k_pxy has run.  The points go to the image state's own scratch, not c->G.
+// joint_ensure has run for JOINT (run_images_async: never inside a capture)
+static void replay_one_image_frame(srukf_ctx* c, int mode)
+{
+    ImageReplay& im = c->img;
+    const KDims& d = c->d;
+    seq_predict_motion(c, nullptr);
+    seq_predict_measurement(c, FORM_PLAIN);
+    seq_pxy(c, FORM_PLAIN);
+    {
+        ProfScope ps(c, KC_MISC, 0, (double)(PT_REGION_W * PT_REGION_W + PT_TMPL_BYTES + PT_PATCH_BYTES) * d.N);
+        srukf_launch_landmarks_cartesian(c->stream, d, c->X, c->S, im.xyz, nullptr);      // the points only
+        srukf_launch_warp_patch(c->stream, d, c->p, c->X, im.xyz, c->h, c->appR, c->appT, c->appPx, c->app_patch, c->has_app, c->app_tmpl);
+        srukf_launch_associate_staged(c->stream, d, c->p, StagedAssoc{ im.images, im.frames, c->z_seq, c->m_seq, im.corr_seq, im.vis_seq, im.h_seq, c->fs },
+                                      c->h, c->Si, c->vis, c->has_app, c->app_tmpl);
+    }
+    if (mode == SRUKF_UPDATE_JOINT) seq_joint_launches(c, nullptr, nullptr);
+    else seq_gain_only(c, nullptr, nullptr, FORM_PLAIN);
+    seq_refactor(c, refactor_frame_tail(c), FORM_PLAIN);
+}
+
+static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge, bool images = false)
 {
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    for (int q = 0; q < nframes; q++) replay_one_frame(c, mode);
+    for (int q = 0; q < nframes; q++) { if (images) replay_one_image_frame(c, mode); else replay_one_frame(c, mode); }
     const hipError_t launch_err = hipGetLastError();            // a failed launch inside the capture must not leave the stream capturing
     HIPCHK(c, hipStreamEndCapture(c->stream, g));
     HIPCHK(c, launch_err);
@@ -1105,6 +1139,7 @@ int srukf_stage_sequence(srukf_ctx* c, int F, const double* odo, const double* z
     HIPCHK(c, hipStreamSynchronize(c->stream));             // frames in flight may still read the staged inputs
     if (c->odo_seq) { srukf_dfree(c->odo_seq); srukf_dfree(c->z_seq); srukf_dfree(c->m_seq); c->odo_seq = nullptr; c->z_seq = nullptr; c->m_seq = nullptr; }
     drop_graphs(c);
+    images_drop(c, c->stream);                              // (staged images belong to the sequence they were staged for: srukf_stage_images)
     HIPCHK(c, srukf_dmalloc((void**)&c->odo_seq, sizeof(double) * 3 * (F + 1)));
     HIPCHK(c, srukf_dmalloc((void**)&c->z_seq, sizeof(double) * (size_t)F * 2 * N));
     HIPCHK(c, srukf_dmalloc((void**)&c->m_seq, sizeof(int) * (size_t)F * N));
@@ -1263,6 +1298,145 @@ int srukf_run_frames(srukf_ctx* c, int first, int count, int mode, double* traj_
     return rc;
 }
 
+// ---- image runs: the staged replay with the association on the device ----
+
+// The gray frames of the staged sequence, copied to the device once; with them the per-frame record, the scratch for the Cartesian points and the block's checkpoint
+// (X, S, matchPatch): everything an image run needs that can fail for want of memory is allocated here, outside any capture.
+int srukf_stage_images(srukf_ctx* c, int F, const unsigned char* gray)
+{
+    if (!c || F < 1 || !gray) return SRUKF_ERR_BAD_ARG;
+    if (!c->odo_seq) { c->err = "stage_images: no staged sequence (srukf_stage_sequence first)"; return SRUKF_ERR_SEQUENCE; }
+    if (F != c->seqF) { c->err = "stage_images: n_frames is not the staged sequence's"; return SRUKF_ERR_DIM_MISMATCH; }
+    if (c->d.N < 1) { c->err = "stage_images: the map is empty"; return SRUKF_ERR_DIM_MISMATCH; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // frames in flight may still read the images staged before
+    images_drop(c, c->stream);
+    int rc = ensure_appearance(c); if (rc) return rc;
+    ImageReplay& im = c->img;
+    const size_t N = c->d.N, np = c->d.np, img = (size_t)c->p.image_w * (size_t)c->p.image_h, f = (size_t)F;
+    if (srukf_dmalloc(&im.images, f * img) != hipSuccess || srukf_dmalloc(&im.corr_seq, sizeof(double) * f * N) != hipSuccess ||
+        srukf_dmalloc(&im.vis_seq, sizeof(int) * f * N) != hipSuccess || srukf_dmalloc(&im.h_seq, sizeof(double) * f * 2 * N) != hipSuccess ||
+        srukf_dmalloc(&im.xyz, sizeof(double) * 3 * N) != hipSuccess || srukf_dmalloc(&im.ck_tmpl, N * PT_TMPL_STRIDE) != hipSuccess ||
+        srukf_dmalloc(&im.ckS, sizeof(double) * np * np) != hipSuccess || srukf_dmalloc(&im.ckX, sizeof(double) * np) != hipSuccess) {
+        (void)hipGetLastError();
+        images_drop(c, c->stream);
+        c->err = "stage_images: out of device memory"; return SRUKF_ERR_NOMEM;
+    }
+    im.frames = F;
+    hipError_t e = hipMemcpy(im.images, gray, f * img, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemsetAsync(im.corr_seq, 0, sizeof(double) * f * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.vis_seq, 0, sizeof(int) * f * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.h_seq, 0, sizeof(double) * f * 2 * N, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { images_drop(c, c->stream); c->err = std::string("stage_images: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
+    return SRUKF_OK;
+}
+
+// the state the block of image frames started from comes back: X, S and the matchPatch array (its pixels persist from frame to frame, so a flagged block must not
+// leave its own behind), as srukf_run_frames' checkpoint comes back.  Keeps c->err
+static void images_restore(srukf_ctx* c)
+{
+    ImageReplay& im = c->img;
+    const size_t np = c->d.np;
+    const std::string why = c->err;
+    hipMemcpyAsync(c->S, im.ckS, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream);
+    hipMemcpyAsync(c->X, im.ckX, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream);
+    hipMemcpyAsync(c->app_tmpl, im.ck_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream);
+    if (c->null_canonical != im.ck_canon) { c->null_canonical = im.ck_canon; drop_graphs(c); }
+    shadow_rebuild(c);
+    hipStreamSynchronize(c->stream);
+    c->err = why;
+}
+
+int srukf_run_images_async(srukf_ctx* c, int first, int count, int mode, double* d_traj)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    { const int rcm = replay_mode_check(c, mode, "run_images_async"); if (rcm) return rcm; }
+    if (c->storage != SRUKF_STORAGE_F64) { c->err = "run_images_async: image runs are available in SRUKF_STORAGE_F64 only"; return SRUKF_ERR_UNSUPPORTED; }
+    ImageReplay& im = c->img;
+    if (!im.images) { c->err = "run_images_async: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!c->odo_seq || im.frames != c->seqF || first + count > c->seqF) { c->err = "frames outside the staged sequence"; return SRUKF_ERR_DIM_MISMATCH; }
+    if (c->async_pending && !im.pending) { c->err = "run_images_async: frames of srukf_run_frames_async are in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    c->joint_bad_host = false;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (mode == SRUKF_UPDATE_JOINT) { const int rcj = joint_ensure(c, "run_images_async"); if (rcj) return rcj; }      // (before any capture begins)
+    step_commit_motion(c); step_state_replaced(c);
+    if (c->fs_seq_step) {                                      // the step-wise fast path pointed the frame scalars at its own three poses
+        hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, c->stream, c->fs, c->odo_seq, c->seqF, c->p.a1, c->p.a2, c->p.a3, c->p.a4);
+        c->fs_seq_step = false;
+    }
+    if (!im.pending) {
+        // the block's checkpoint: a block is every image run since the last srukf_synchronize
+        const size_t np = c->d.np;
+        HIPCHK(c, hipMemcpyAsync(im.ckS, c->S, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(im.ckX, c->X, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(im.ck_tmpl, c->app_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream));
+        im.ck_canon = c->null_canonical;
+    }
+    double* traj = d_traj ? d_traj - (size_t)8 * first : nullptr;
+    int clear = c->async_pending ? 0 : 1;
+    if (c->red_r > 0 && !c->null_canonical) {
+        // null rows that are not (yet) sqrt(EPSILON) e_k: the run's first frame eagerly, as in srukf_run_frames_async (the plain form reads the rows as they are)
+        launch_set_run(c->stream, c->fs, first, clear, traj);
+        replay_one_image_frame(c, mode);
+        set_null_canonical(c);
+        c->async_pending = true; im.pending = true; c->phase = 0; c->frame_updated = false; clear = 0;
+        first += 1; count -= 1;
+        HIPCHK(c, hipGetLastError());
+        if (count == 0) return SRUKF_OK;
+    }
+    launch_set_run(c->stream, c->fs, first, clear, traj);
+    if (c->use_graph && !c->profiling) {
+        ReplayGraphs& g = im.graphs[mode == SRUKF_UPDATE_JOINT ? 1 : 0];      // (image frames only: never a captured frame without the association)
+        if (!g.one_exec) {
+            int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true); if (rc) return rc;
+            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true); if (rc) return rc;
+        }
+        int f = 0;
+        for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(g.eight_exec, c->stream));
+        for (; f < count; f++) HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
+    } else {
+        for (int f = 0; f < count; f++) replay_one_image_frame(c, mode);
+    }
+    c->async_pending = true; im.pending = true;
+    c->phase = 0; c->frame_updated = false;
+    HIPCHK(c, hipGetLastError());
+    return SRUKF_OK;
+}
+
+// Synchronous form.  No recovery inside the call: a flagged block comes back to its checkpoint (srukf_synchronize) and SRUKF_ERR_CLAMP_PENDING is returned
+int srukf_run_images(srukf_ctx* c, int first, int count, int mode, double* traj_host)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    double* dt = nullptr;
+    HIPCHK(c, srukf_dmalloc((void**)&dt, sizeof(double) * 8 * (size_t)count));
+    int rc = srukf_run_images_async(c, first, count, mode, dt);
+    if (rc == SRUKF_OK) rc = srukf_synchronize(c);
+    if (traj_host && rc == SRUKF_OK) hipMemcpy(traj_host, dt, sizeof(double) * 8 * (size_t)count, hipMemcpyDeviceToHost);
+    srukf_dfree(dt);
+    return rc;
+}
+
+// rows [first, first + count) of what the association wrote (rows no image run has written: z / matched as staged, the rest zero).  Waits for the stream only: flags
+// of frames in flight are still srukf_synchronize's to report
+int srukf_get_image_matches(srukf_ctx* c, int first, int count, double* z, int* matched, double* corr, int* visible, double* h)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_matches: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_matches: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    if (z) HIPCHK(c, hipMemcpy(z, c->z_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
+    if (matched) HIPCHK(c, hipMemcpy(matched, c->m_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (corr) HIPCHK(c, hipMemcpy(corr, im.corr_seq + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
+    if (visible) HIPCHK(c, hipMemcpy(visible, im.vis_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (h) HIPCHK(c, hipMemcpy(h, im.h_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
+    return SRUKF_OK;
+}
+
 // What the last SRUKF_ERR_CLAMP_PENDING of srukf_synchronize was about: the first flagged staged frame (frames before it
 // are valid) and the first flagged pivot row.  -1 / -1 if there was none.
 int srukf_clamp_info(srukf_ctx* c, int* frame, int* row)
@@ -1295,10 +1469,17 @@ int srukf_synchronize(srukf_ctx* c)
     c->joint_bad_host = false;
     if (c->async_pending) {
         c->async_pending = false;
+        const bool image_run = c->img.pending;                  // the frames were image frames: a flagged block comes back to its checkpoint here (X, S, matchPatch)
+        c->img.pending = false;
         int rc = read_fs(c); if (rc) return rc;
         // joint frames: the sticky pair k_joint_dx left (first hit).  A clamp flag of an EARLIER frame goes first: from that frame on nothing is valid anyway
-        if (c->hfs->joint_bad_frame > 0 && !(c->hfs->clamp_rows > 0 && c->hfs->clamp_frame < c->hfs->joint_bad_frame - 1)) return joint_bad_report(c);
+        if (c->hfs->joint_bad_frame > 0 && !(c->hfs->clamp_rows > 0 && c->hfs->clamp_frame < c->hfs->joint_bad_frame - 1)) {
+            rc = joint_bad_report(c);
+            if (image_run) { images_restore(c); c->joint_bad_host = false; }
+            return rc;
+        }
         if (c->hfs->clamp_rows > 0) {
+            if (image_run) images_restore(c);
             c->clamp_frame_host = c->hfs->clamp_frame; c->clamp_row_host = c->hfs->clamp_first;
             char b[220]; snprintf(b, sizeof b, "GMW theta clamp active on %d pivot rows (first row %d), first in staged frame %d, during async frames%s", c->hfs->clamp_rows, c->hfs->clamp_first, c->hfs->clamp_frame,
                                  c->hfs->gmw_aborts > 0 ? " (a persistent factorisation launch was abandoned: the GPU is shared; see srukf_set_exclusive)" : "");

@@ -1,7 +1,7 @@
 // cslam_step_bench — wall-clock frame rate of the DROP-IN path: what a host that binds this library the way the MFC view binds the reference's
 // CSLAM gets per frame (SLAM.cpp:87-112, called from MonoSLAMView.cpp:499-572): predict, host (or device) data association, update — one frame at a
 // time, with the host round trips in between.  bench.py's headline is the staged replay (inputs resident in HBM, no host in the loop); this is the other number.
-//   cslam_step_bench scene.bin odometry.txt mode=<capi|facade|assoc|replay> [frames=K] [warmup=W] [hint=0|1] [set=key:value ...]
+//   cslam_step_bench scene.bin odometry.txt mode=<capi|facade|assoc|replay|assoc_replay> [frames=K] [warmup=W] [hint=0|1] [set=key:value ...]
 //     capi   : srukf_predict_motion -> srukf_predict_measurement (D->H h, Si, visible) -> host association (matched = visible, z from the scene)
 //              -> srukf_update (H->D) -> srukf_get_robot (the pose and robot block RobotPath.txt records, SLAM.cpp:3539-3556)
 //     facade : monoslam::CSLAM::SLAM() with the same association as a callback (what cslam_replay does), display refresh and mirrors included
@@ -11,6 +11,10 @@
 //     replay : the staged replay, for comparison on the same scene file: srukf_stage_sequence (every landmark offered as matched; the device's visibility decides,
 //              as in capi), then srukf_run_frames_async + srukf_synchronize in blocks of `frames` (the warm-up frames first, as one block of their own), srukf_get_robot
 //              at the end.  Honours joint=1 (SRUKF_UPDATE_JOINT frames) and set=key:value; prints the same keys as capi (the per-call host times are zero)
+//     assoc_replay : the staged replay with the association on the device, on assoc's scene, gray frame and appearance set-up: the frame is staged once
+//              per staged frame (srukf_stage_images), then srukf_run_images_async + srukf_synchronize in blocks of `block` frames (default 8: the churn leg changes the
+//              map every ten frames), the warm-up frames first.  The filter is driven by what the device's association finds.  A flagged block comes back restored and
+//              is run step-wise (srukf_associate + srukf_update / srukf_update_joint), inside the timed region; "flagged_blocks" counts them.  Honours joint=1 and set=
 //     hint=1 : capi / assoc announce the NEXT frame's odometry with srukf_predict_motion_next before every update (a host that has its odometry
 //              file loaded, as the reference has: loadOdometryData reads it whole, SLAM.cpp:363-496)
 //     set=key:value : srukf_debug_set(ctx, key, value) after the context exists (capi / assoc; measurement switches, e.g. set=step_fuse_export:0)
@@ -42,9 +46,10 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 
 int main(int argc, char** argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: %s scene.bin odometry.txt mode=<capi|facade|assoc|replay> [frames=K] [warmup=W] [hint=0|1]\n", argv[0]); return 2; }
+    if (argc < 4) { fprintf(stderr, "usage: %s scene.bin odometry.txt mode=<capi|facade|assoc|replay> [frames=K] [warmup=W] [hint=0|1]\n"
+                                "       (mode=assoc_replay [block=B]: the staged replay with the association on the device)\n", argv[0]); return 2; }
     std::string mode = "capi";
-    int K = 200, W = 20, hint = 0, churn = 0, ransac = 0, ellipsoids = 0, joint = 0;
+    int K = 200, W = 20, hint = 0, churn = 0, ransac = 0, ellipsoids = 0, joint = 0, block_frames = 8;
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -55,6 +60,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "ransac=", 7)) ransac = atoi(argv[a] + 7);
         else if (!strncmp(argv[a], "ellipsoids=", 11)) ellipsoids = atoi(argv[a] + 11);
         else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6);
+        else if (!strncmp(argv[a], "block=", 6)) block_frames = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } sets.emplace_back(std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))), atoi(q + 1)); }
     }
     for (auto& kv : sets) (void)srukf_debug_set(nullptr, kv.first.c_str(), kv.second);      // process-wide keys (e.g. set=timing:1) apply in every mode; per-filter keys: mode=capi, below
@@ -86,6 +92,9 @@ int main(int argc, char** argv)
     char ell_json[200] = "";
     int joint_flagged = 0;
     const char* replay_form = "run_frames_async + synchronize";
+    int flagged_blocks = 0;
+    const bool areplay = mode == "assoc_replay";
+    if (areplay && (block_frames < 1 || W < 1)) { fprintf(stderr, "assoc_replay: block >= 1 and warmup >= 1 (frame 0 sets the appearance records up)\n"); return 2; }
     if (mode == "facade") {
         monoslam::CSLAM SLAM;
         SLAM.m_params.a1 = a4[0]; SLAM.m_params.a2 = a4[1]; SLAM.m_params.a3 = a4[2]; SLAM.m_params.a4 = a4[3];
@@ -217,7 +226,7 @@ int main(int argc, char** argv)
         std::vector<double> h(2 * N), Si(4 * N), zc(2 * N), corr(N);
         std::vector<int> vis(N), m(N), md(N);
         std::vector<unsigned char> gray;
-        const bool assoc = mode == "assoc";
+        const bool assoc = mode == "assoc" || areplay;
         if (assoc) {
             // texture: box-filtered noise (11 x 11), 640 x 480; every landmark's init patch is cut from it around its first predicted pixel, "created" at the start pose
             const int Wd = 640, Hd = 480;
@@ -249,6 +258,48 @@ int main(int argc, char** argv)
         }
         const int f0 = assoc ? 1 : 0;
         double t0 = 0.0;
+        if (areplay) {
+            const int upd = joint ? SRUKF_UPDATE_JOINT : SRUKF_UPDATE_BATCHED;
+            const size_t img = gray.size();
+            {
+                std::vector<double> z0((size_t)(W + K) * 2 * N, 0.0);       // the rows the image runs write
+                std::vector<int> m0((size_t)(W + K) * N, 0);
+                CK(srukf_stage_sequence(c, W + K, odo.data(), z0.data(), m0.data()));
+                std::vector<unsigned char> stack((size_t)(W + K) * img);
+                for (int fr = 0; fr < W + K; fr++) memcpy(stack.data() + (size_t)fr * img, gray.data(), img);
+                CK(srukf_stage_images(c, W + K, stack.data()));
+            }
+            std::vector<int> mrow((size_t)block_frames * N);
+            auto run = [&](int first, int end, bool timed) -> int {
+                for (int b = first; b < end; b += block_frames) {
+                    const int cnt = end - b < block_frames ? end - b : block_frames;
+                    rc = srukf_run_images_async(c, b, cnt, upd, nullptr);
+                    if (rc == SRUKF_OK) rc = srukf_synchronize(c);
+                    if (rc == SRUKF_ERR_CLAMP_PENDING) {
+                        // the block came back restored (X, S, matchPatch): its frames step by step, the device's association driving the filter as in the block
+                        if (timed) flagged_blocks++;
+                        for (int fr = b; fr < b + cnt; fr++) {
+                            CK(srukf_predict_motion(c, &odo[3 * fr], &odo[3 * fr + 3]));
+                            CK(srukf_predict_measurement(c, h.data(), Si.data(), vis.data()));
+                            CK(srukf_associate(c, gray.data(), zc.data(), md.data(), corr.data()));
+                            if (timed) for (int k = 0; k < N; k++) matches_dev += md[k];
+                            if (joint) CK(srukf_update_joint(c, zc.data(), md.data(), SRUKF_NEEDNOT_REORDER));
+                            else CK(srukf_update(c, zc.data(), md.data(), SRUKF_NEEDNOT_REORDER, SRUKF_UPDATE_BATCHED));
+                        }
+                    } else if (rc) { fprintf(stderr, "image block [%d, %d): %d %s\n", b, b + cnt, rc, srukf_last_error(c)); return 1; }
+                    else if (timed) {
+                        // (the record is the host's to read after every block: nPredictTimes / nMatchTimes and the border test need it)
+                        CK(srukf_get_image_matches(c, b, cnt, nullptr, mrow.data(), nullptr, nullptr, nullptr));
+                        for (int q = 0; q < cnt * N; q++) matches_dev += mrow[q];
+                    }
+                }
+                return 0;
+            };
+            if (run(f0, W, false)) return 1;
+            t0 = now_s();
+            if (run(W, W + K, true)) return 1;
+            CK(srukf_get_robot(c, pose, P4));
+        } else
         for (int fr = f0; fr < W + K; fr++) {
             if (fr == W) t0 = now_s();
             const double s0 = now_s();
@@ -273,12 +324,14 @@ int main(int argc, char** argv)
     }
     char joint_json[200] = "";
     if (joint) snprintf(joint_json, sizeof joint_json, "\"joint\": 1, \"joint_flagged_frames\": %d, ", joint_flagged);
+    if (areplay) snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"block_frames\": %d, \"flagged_blocks\": %d, ", block_frames, flagged_blocks);
     if (mode == "replay") snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"replay_form\": \"%s\", \"exact_frames\": %d, ", replay_form, joint_flagged);
     printf("{\"mode\": \"%s\", %s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
            "\"pose\": [%.17g, %.17g, %.17g, %.17g], \"P_robot\": [%.17g, %.17g, %.17g, %.17g], \"device_matches\": %lld, \"stats_flag_us_into_first_launch\": %.2f, \"host_us_per_call\": {\"predict_motion\": %.2f, \"predict_measurement\": %.2f, \"association\": %.2f, \"update\": %.2f, \"get_robot\": %.2f}, "
-           "\"filter_driven_by\": \"scene z / matched (host association)\"}\n",
+           "\"filter_driven_by\": \"%s\"}\n",
            mode.c_str(), churn_json, ell_json, joint_json, hint, N, K, W, K / t_timed, t_timed / K * 1e6, pose[0], pose[1], pose[2], pose[3], P4[0], P4[1], P4[4], P4[5], matches_dev, flag_ticks * 0.01,
-           tcall[0] / K * 1e6, tcall[1] / K * 1e6, tcall[2] / K * 1e6, tcall[3] / K * 1e6, tcall[4] / K * 1e6);
+           tcall[0] / K * 1e6, tcall[1] / K * 1e6, tcall[2] / K * 1e6, tcall[3] / K * 1e6, tcall[4] / K * 1e6,
+           areplay ? "device association" : "scene z / matched (host association)");
     fflush(stdout);                                                // (the line must not depend on what the runtimes' exit handlers do)
     return 0;
 }

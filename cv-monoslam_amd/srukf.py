@@ -31,6 +31,7 @@ EXPORTS = [
     "srukf_set_frame_bgr", "srukf_associate_held", "srukf_render_overlay",
     "srukf_archive_set", "srukf_archive_count", "srukf_archive_get_template", "srukf_archive_search",
     "srukf_associate_checked", "srukf_get_match_scores",
+    "srukf_stage_images", "srukf_run_images_async", "srukf_run_images", "srukf_get_image_matches",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -159,6 +160,11 @@ def load_library(path=None):
     if hasattr(L, "srukf_associate_checked"):          # (idem: ambiguity veto, sub-pixel matches)
         L.srukf_associate_checked.argtypes = [C.c_void_p, _bp, C.POINTER(MatchParams), _dp, _ip, _dp, _dp, _dp, _ip]
         L.srukf_get_match_scores.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _ip, _ip, _ip]
+    if hasattr(L, "srukf_run_images"):                 # (idem: image runs of the staged replay)
+        L.srukf_stage_images.argtypes = [C.c_void_p, C.c_int, _bp]
+        L.srukf_run_images_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.srukf_run_images.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp]
+        L.srukf_get_image_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _ip, _dp, _ip, _dp]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -574,6 +580,49 @@ class Filter:
         traj = np.empty((count, 8))
         self._chk(self._lib.srukf_run_frames(self._h, first, count, mode, _d(traj)))
         return traj
+
+    def stage_images(self, gray):
+        """The gray frames gray[F, image_h, image_w] uint8 of the staged sequence (F = its frame count), copied to the device once (srukf_stage_images).
+        Image runs overwrite the z / matched rows of that sequence with what the association finds."""
+        if not isinstance(gray, np.ndarray) or gray.dtype != np.uint8:
+            raise TypeError("stage_images: gray must be a uint8 array")
+        if gray.ndim != 3 or gray.shape[1:] != (int(self.params.image_h), int(self.params.image_w)):
+            raise ValueError(f"stage_images: gray must be [F, {int(self.params.image_h)}, {int(self.params.image_w)}], got {gray.shape}")
+        if gray.shape[0] < 1:
+            raise ValueError("stage_images: no frames")
+        gray = np.ascontiguousarray(gray)
+        self._chk(self._lib.srukf_stage_images(self._h, gray.shape[0], gray.ctypes.data_as(C.POINTER(C.c_ubyte))))
+
+    @staticmethod
+    def _image_run_args(first, count, mode):
+        for name, v in (("first", first), ("count", count), ("mode", mode)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"run_images: {name} must be an integer")
+        if first < 0 or count < 1:
+            raise ValueError("run_images: first >= 0 and count >= 1")
+
+    def run_images_async(self, first, count, mode=UPDATE_BATCHED, d_traj_ptr=None):
+        """Staged frames [first, first + count) with the association on the device (srukf_run_images_async); a flagged block is restored by synchronize()."""
+        self._image_run_args(first, count, mode)
+        self._chk(self._lib.srukf_run_images_async(self._h, int(first), int(count), int(mode), C.c_void_p(d_traj_ptr) if d_traj_ptr else None))
+
+    def run_images(self, first, count, mode=UPDATE_BATCHED):
+        """run_images_async + synchronize -> traj[count, 8].  SrukfError(SRUKF_ERR_CLAMP_PENDING) for a flagged block: X, S and every matchPatch are as before the call."""
+        self._image_run_args(first, count, mode)
+        traj = np.empty((count, 8))
+        self._chk(self._lib.srukf_run_images(self._h, int(first), int(count), int(mode), _d(traj)))
+        return traj
+
+    def get_image_matches(self, first, count):
+        """What the association wrote for staged frames [first, first + count) (srukf_get_image_matches): dict of z[count, 2N], matched[count, N], corr[count, N],
+        visible[count, N], h[count, 2N]."""
+        self._image_run_args(first, count, UPDATE_BATCHED)
+        N = self.N
+        out = dict(z=np.zeros((count, 2 * N)), matched=np.zeros((count, N), dtype=np.int32), corr=np.zeros((count, N)),
+                   visible=np.zeros((count, N), dtype=np.int32), h=np.zeros((count, 2 * N)))
+        self._chk(self._lib.srukf_get_image_matches(self._h, int(first), int(count), _d(out["z"]), _i(out["matched"]), _d(out["corr"]), _i(out["visible"]),
+                                                    _d(out["h"])))
+        return out
 
     def synchronize(self):
         self._chk(self._lib.srukf_synchronize(self._h))

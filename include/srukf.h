@@ -477,6 +477,36 @@ int  srukf_run_frames_batch(srukf_ctx* const* ctxs, int B, int first, int count,
 /* First flagged staged frame / pivot row of the last SRUKF_ERR_CLAMP_PENDING (-1, -1: none).  Either may be NULL. */
 int  srukf_clamp_info(srukf_ctx* ctx, int* frame, int* row);
 
+/* ---- image runs: staged frames with the association on the device ---------------------------
+ * The staged replay for a host that has the camera frames but not z / matched: every frame runs wrapPatch + dataAssociation (what srukf_associate runs, the
+ * same matching front) on its own staged image, between the measurement prediction and the update, and the update reads what that wrote.  No host inside a
+ * block; the map is fixed over a block; the host reads the per-frame record afterwards and applies its add / delete policy between blocks.
+ * srukf_stage_images: gray[n_frames][image_h][image_w] (host) is copied to the device once.  Needs a sequence of exactly n_frames frames staged with
+ *   srukf_stage_sequence (SRUKF_ERR_SEQUENCE when there is none, SRUKF_ERR_DIM_MISMATCH when the count differs or the map is empty); its odometry is used, and ITS
+ *   z / matched ROWS ARE OVERWRITTEN by every image run, frame by frame, with what the association found (a later srukf_run_frames of those frames replays the
+ *   association's matches, not the host's).  The images live as long as that sequence: the next srukf_stage_sequence, a map change, srukf_reset and
+ *   srukf_destroy drop them.  The frame the handle holds (srukf_associate_held, srukf_set_frame_bgr) is neither read nor written by any of these calls.
+ * srukf_run_images_async: frames [first, first + count) of the staged images; d_traj as in srukf_run_frames_async.  mode: SRUKF_UPDATE_BATCHED or
+ *   SRUKF_UPDATE_JOINT (anything else: SRUKF_ERR_UNSUPPORTED, as srukf_run_frames_async).  SRUKF_STORAGE_F64 only (the float-stored modes: SRUKF_ERR_UNSUPPORTED).
+ *   Every frame is the plain frame form (k_motion, k_project, k_pxy, then k_landmarks_cartesian, k_warp_patch, k_associate_staged, then k_gain or the joint
+ *   launches, then the frame-tail refactorisation) whatever the launch switches say, from captured frames of its own per mode: an image run never replays a
+ *   captured frame of srukf_run_frames_async, nor the other way round.  SRUKF_ERR_SEQUENCE: nothing staged with srukf_stage_images, or frames of
+ *   srukf_run_frames_async still in flight; SRUKF_ERR_DIM_MISMATCH: frames outside the staged sequence.
+ *   Flagged frames: there is no recovery inside the call.  The first image run after a srukf_synchronize keeps a checkpoint of X, S and every landmark's
+ *   matchPatch (its pixels persist from frame to frame); a block is every image run up to the next srukf_synchronize.  When that srukf_synchronize finds a
+ *   frame of the block flagged (SRUKF_ERR_CLAMP_PENDING; srukf_clamp_info names the frame) or a joint frame's inputs not finite (SRUKF_ERR_UNSUPPORTED, as for
+ *   srukf_run_frames_async), IT restores the checkpoint before it returns: a host of the asynchronous form asks for nothing else, and runs that block
+ *   step-wise (srukf_predict_motion .. srukf_associate .. srukf_update).  The record rows and the trajectory rows of the block are then not valid.
+ * srukf_run_images: srukf_run_images_async + srukf_synchronize, the trajectory copied to traj_host[count*8] (may be NULL) when the block was clean.  Unlike
+ *   srukf_run_frames it can return SRUKF_ERR_CLAMP_PENDING: X, S and every matchPatch are then what they were before the call.
+ * srukf_get_image_matches: rows [first, first + count) of what the association wrote, after waiting for the stream (it does not collect the flags of frames in
+ *   flight: srukf_synchronize still reports them): z[count][2N], matched[count][N], corr[count][N], visible[count][N] (the frame's visibility), h[count][2N] (the
+ *   predicted pixels).  Any may be NULL.  Rows no image run has written hold z / matched as staged and zeros in the rest. */
+int  srukf_stage_images(srukf_ctx* ctx, int n_frames, const unsigned char* gray);
+int  srukf_run_images_async(srukf_ctx* ctx, int first, int count, int mode, double* d_traj);
+int  srukf_run_images(srukf_ctx* ctx, int first, int count, int mode, double* traj_host);
+int  srukf_get_image_matches(srukf_ctx* ctx, int first, int count, double* z, int* matched, double* corr, int* visible, double* h);
+
 /* ---- instrumentation ------------------------------------------------------------------------ */
 
 /* When on, every kernel launch is bracketed by HIP events on the context's stream and the
