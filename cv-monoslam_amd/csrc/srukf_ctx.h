@@ -10,7 +10,7 @@
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search)
 //   srukf_joint.hip   the joint measurement update's kernels (srukf_update_joint, SRUKF_UPDATE_JOINT frames of the staged replay; host code: srukf_step.hip, srukf_replay.hip)
-//   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip)
+//   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip; srukf_run_images_checked*: srukf_replay.hip)
 //   srukf_patch.h     (through srukf_launch.h) the appearance record's sizes, the checked association's buffer layouts, the search kernels' shared front
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
 //   srukf_switches.h  where the switches of srukf_debug_set are stored: the process-wide struct g_sw, the per-filter DbgSwitches
@@ -87,6 +87,10 @@ struct ArchiveState {
 // reads (xyz, 3N: not c->G — nothing has shown G to be free inside a replayed block), and the block's checkpoint: X, S, the matchPatch array and whether the null rows
 // were canonical.  pending: the frames srukf_synchronize waits for are image frames (a flagged block comes back to the checkpoint there).  Captured frames of their own
 // per update mode.  Map-size scope, the staged sequence's lifetime: images_drop
+// Checked image runs (srukf_run_images_checked*), allocated by images_checked_ensure on the first one: the checked record corr2_seq [F][N],
+// z2_seq [F][2N], flags_seq [F][N] (zero until a checked run writes a row), the parameters the checked frames read (match_args, written in stream order in front of every
+// checked run) and captured frames of their own per update mode (chk_graphs: never the plain image run's, nor the other way round; they hold the pointer of the
+// filter's score buffer they were captured with, chk_scores).  checked: the block in flight holds a checked run (a flagged block then leaves no valid score map)
 struct ImageReplay {
     unsigned char *images = nullptr, *ck_tmpl = nullptr;
     double *corr_seq = nullptr, *h_seq = nullptr, *xyz = nullptr, *ckS = nullptr, *ckX = nullptr;
@@ -94,6 +98,10 @@ struct ImageReplay {
     int frames = 0;
     bool pending = false, ck_canon = false;
     ReplayGraphs graphs[2];
+    double *corr2_seq = nullptr, *z2_seq = nullptr; int* flags_seq = nullptr;
+    MatchArgs* match_args = nullptr; const double* chk_scores = nullptr;
+    bool checked = false;
+    ReplayGraphs chk_graphs[2];
 };
 
 // ---- the context: who owns what across a map change ("who owns what across a map change") ----------------------
@@ -303,7 +311,8 @@ struct srukf_map_scope : srukf_life {
                       perm, iperm, Sdis, pan[0], pan[1], red_perm, red_iperm, gdiag, shadowA, Utp, slabW, slabL, gsW, gsL, P1, pxy2_tiles, nskip,
                       red_head0_tiles, split_fold_list, red_syrk_tiles, ckS, ckX, syrk_tiles, pxy_tiles, syrk_head_tiles, syrk_head_tiles_b, fs,
                       odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt, jointZd, jointW, jointRd,
-                      img.images, img.ck_tmpl, img.corr_seq, img.h_seq, img.xyz, img.ckS, img.ckX, img.vis_seq };
+                      img.images, img.ck_tmpl, img.corr_seq, img.h_seq, img.xyz, img.ckS, img.ckX, img.vis_seq,
+                      img.corr2_seq, img.z2_seq, img.flags_seq, img.match_args };
         for (void* q : b) f(q);
     }
 };
@@ -368,6 +377,7 @@ void ransac_scratch_free(RansacScratch& s, hipStream_t st);
 
 // ---- srukf_associate_checked's buffers, the appearance records (srukf_map.hip) ----
 void match_drop(srukf_ctx* c);
+int match_ensure(srukf_ctx* c, const char* who);      // match_res and match_scores, allocated on first use (never inside a capture)
 int ensure_appearance(srukf_ctx* c);      // the per-landmark appearance records (and the handle's frame buffer), allocated and zeroed on first use
 
 // ---- archive search (srukf_archive.hip) ----

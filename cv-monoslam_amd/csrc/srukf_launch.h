@@ -68,6 +68,13 @@ struct StagedAssoc {
     double* z_seq; int* m_seq; double* corr_seq; int* vis_seq; double* h_seq;
     const FrameScalars* fs;
 };
+// k_associate_checked_staged: k_associate_staged's addressing (rec), the checked record beside it (corr2_seq, flags_seq stride N, z2_seq stride 2N), the filter's score
+// buffer (PT_SCORE_STRIDE doubles per landmark: the last frame's maps) and the parameters on the device (ma: written in stream order, srukf_launch_set_match_args)
+struct StagedChecked {
+    StagedAssoc rec;
+    double* corr2_seq; double* z2_seq; int* flags_seq; double* scores;
+    const MatchArgs* ma;
+};
 
 extern "C" {
 // ---- srukf_predict.hip ----
@@ -171,6 +178,10 @@ void srukf_launch_associate_staged(hipStream_t st, KDims d, srukf_params p, Stag
 // res / scores: the packed result block and the score buffer (match_res, PT_SCORE_*: srukf_patch.h)
 void srukf_launch_associate_checked(hipStream_t st, KDims d, srukf_params p, MatchArgs ma, const unsigned char* image, const double* h, const double* Si, const int* vis,
                                     const int* has_app, const unsigned char* matchPatch, double* z, int* matched, double* corr, double* res, double* scores);
+// k_associate_checked_staged (checked image runs): k_associate_checked with k_associate_staged's addressing; srukf_launch_set_match_args: *dst = v on the stream
+void srukf_launch_associate_checked_staged(hipStream_t st, KDims d, srukf_params p, StagedChecked a, const double* h, const double* Si, const int* vis, const int* has_app,
+                                           const unsigned char* matchPatch);
+void srukf_launch_set_match_args(hipStream_t st, MatchArgs* dst, MatchArgs v);
 }  // extern "C"
 
 // ---- srukf_joint.hip (the joint measurement update; C++ linkage: its launchers are named launch_joint_*) ----

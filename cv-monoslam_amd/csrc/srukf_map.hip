@@ -78,6 +78,16 @@ void match_drop(srukf_ctx* c)
     c->match_res = nullptr; c->match_scores = nullptr; c->match_valid = false;
 }
 
+int match_ensure(srukf_ctx* c, const char* who)
+{
+    if (c->match_res) return SRUKF_OK;
+    const int N = c->d.N;
+    if (srukf_dmalloc(&c->match_res, sizeof(double) * match_res(N).doubles) != hipSuccess || srukf_dmalloc(&c->match_scores, sizeof(double) * PT_SCORE_STRIDE * (size_t)N) != hipSuccess) {
+        (void)hipGetLastError(); match_drop(c); c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
+    }
+    return SRUKF_OK;
+}
+
 // The handle keeps its identity when the map changes size: the map-size scope of the context built for the new size comes in, the handle's own goes out with c2
 // and is retired.  Nothing of the handle scope moves ("who owns what across a map change"); what is written out below is neither "stays" nor "goes".
 void adopt_context(srukf_ctx* c, srukf_ctx* c2)
@@ -168,11 +178,7 @@ static int associate_frame(srukf_ctx* c, const unsigned char* gray, double* z, i
     if (N == 0) return SRUKF_OK;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_appearance(c); if (rc) return rc;
-    if (chk && !c->match_res) {
-        if (srukf_dmalloc(&c->match_res, sizeof(double) * match_res(N).doubles) != hipSuccess || srukf_dmalloc(&c->match_scores, sizeof(double) * PT_SCORE_STRIDE * (size_t)N) != hipSuccess) {
-            (void)hipGetLastError(); match_drop(c); c->err = "associate_checked: out of device memory"; return SRUKF_ERR_NOMEM;
-        }
-    }
+    if (chk) { rc = match_ensure(c, "associate_checked"); if (rc) return rc; }
     const size_t img = (size_t)c->p.image_w * c->p.image_h;
     const size_t mp = c->d.mp, zm = mp + ((size_t)N + 1) / 2;             // zcur | mcur: one device allocation of zm doubles
     const size_t res_doubles = chk ? match_res(N).doubles : zm + (size_t)N;      // what the export writes to the front of the staging buffer: match_res, or zcur | mcur | corr

@@ -4,7 +4,8 @@
 // file of the host layer (srukf_map, srukf_detect, srukf_loop); include/srukf.h states the same sizes as array lengths of the ABI (out[441], out[289]).
 //
 // One matching front (dataAssociation, SLAM.cpp:1946-1987, with calculateCrossCorrelation, 3141-3166), two consumers: k_associate (srukf_assoc.hip) keeps the
-// first maximum, k_associate_checked (srukf_unique.hip) keeps every candidate's score too and decides on the whole map.  match_front is that front; the two
+// first maximum, k_associate_checked (srukf_unique.hip) keeps every candidate's score too and decides on the whole map (each with a twin for the frames of an image run:
+// k_associate_staged, k_associate_checked_staged).  match_front is that front; the two
 // kernels differ in the hook it calls per candidate and in what they do with the first maximum.  k_archive_search (srukf_archive.hip) has a window rule, a
 // score (exact integer sums) and a byte staging of its own and takes the gate, block_first_max and the constants only.
 // Every arithmetic function below switches contraction off itself: the bits do not depend on the including file's compiler flags.

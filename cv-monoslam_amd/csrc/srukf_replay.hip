@@ -930,7 +930,7 @@ int read_fs_host(srukf_ctx* c)
 
 void drop_graphs(srukf_map_scope* c)
 {
-    for (ReplayGraphs* gs : { c->graphs, c->img.graphs }) for (int m = 0; m < 2; m++) {      // the captured frames of both update modes, without and with the association
+    for (ReplayGraphs* gs : { c->graphs, c->img.graphs, c->img.chk_graphs }) for (int m = 0; m < 2; m++) {      // the captured frames of both update modes: without the association, with it, with the checked one
         ReplayGraphs& g = gs[m];
         for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec, &g.block_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
         for (hipGraph_t* q : { &g.one, &g.eight, &g.block }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
@@ -942,7 +942,8 @@ void images_drop(srukf_map_scope* c, hipStream_t st)
 {
     ImageReplay& im = c->img;
     if (im.images) drop_graphs(c);                               // (the captured image frames hold these pointers)
-    for (void* b : { (void*)im.images, (void*)im.ck_tmpl, (void*)im.corr_seq, (void*)im.h_seq, (void*)im.xyz, (void*)im.ckS, (void*)im.ckX, (void*)im.vis_seq }) if (b) srukf_dfree_on(b, st);
+    for (void* b : { (void*)im.images, (void*)im.ck_tmpl, (void*)im.corr_seq, (void*)im.h_seq, (void*)im.xyz, (void*)im.ckS, (void*)im.ckX, (void*)im.vis_seq,
+                      (void*)im.corr2_seq, (void*)im.z2_seq, (void*)im.flags_seq, (void*)im.match_args }) if (b) srukf_dfree_on(b, st);
     im = ImageReplay{};
 }
 
@@ -1005,7 +1006,8 @@ static void replay_one_frame(srukf_ctx* c, int mode)
 // m_seq, which k_gain / the joint kernels then read as they read staged rows.  BATCHED: seq_gain_only — seq_gain is seq_pxy + seq_gain_only in this form (no gain fold
 // below "fused tail" mode), and k_pxy has run.  The points go to the image state's own scratch, not c->G.
 // joint_ensure has run for JOINT (run_images_async: never inside a capture)
-static void replay_one_image_frame(srukf_ctx* c, int mode)
+// checked: a frame of a checked image run — the same frame with k_associate_checked_staged in k_associate_staged's place; images_checked_ensure has run
+static void replay_one_image_frame(srukf_ctx* c, int mode, bool checked)
 {
     ImageReplay& im = c->img;
     const KDims& d = c->d;
@@ -1016,18 +1018,23 @@ static void replay_one_image_frame(srukf_ctx* c, int mode)
         ProfScope ps(c, KC_MISC, 0, (double)(PT_REGION_W * PT_REGION_W + PT_TMPL_BYTES + PT_PATCH_BYTES) * d.N);
         srukf_launch_landmarks_cartesian(c->stream, d, c->X, c->S, im.xyz, nullptr);      // the points only
         srukf_launch_warp_patch(c->stream, d, c->p, c->X, im.xyz, c->h, c->appR, c->appT, c->appPx, c->app_patch, c->has_app, c->app_tmpl);
-        srukf_launch_associate_staged(c->stream, d, c->p, StagedAssoc{ im.images, im.frames, c->z_seq, c->m_seq, im.corr_seq, im.vis_seq, im.h_seq, c->fs },
-                                      c->h, c->Si, c->vis, c->has_app, c->app_tmpl);
+        const StagedAssoc rec = { im.images, im.frames, c->z_seq, c->m_seq, im.corr_seq, im.vis_seq, im.h_seq, c->fs };
+        if (checked)
+            srukf_launch_associate_checked_staged(c->stream, d, c->p, StagedChecked{ rec, im.corr2_seq, im.z2_seq, im.flags_seq, c->match_scores, im.match_args },
+                                                  c->h, c->Si, c->vis, c->has_app, c->app_tmpl);
+        else
+        srukf_launch_associate_staged(c->stream, d, c->p, rec, c->h, c->Si, c->vis, c->has_app, c->app_tmpl);
     }
     if (mode == SRUKF_UPDATE_JOINT) seq_joint_launches(c, nullptr, nullptr);
     else seq_gain_only(c, nullptr, nullptr, FORM_PLAIN);
     seq_refactor(c, refactor_frame_tail(c), FORM_PLAIN);
 }
 
-static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge, bool images = false)
+// images: frames of an image run (checked: of a checked one)
+static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge, bool images = false, bool checked = false)
 {
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    for (int q = 0; q < nframes; q++) { if (images) replay_one_image_frame(c, mode); else replay_one_frame(c, mode); }
+    for (int q = 0; q < nframes; q++) { if (images) replay_one_image_frame(c, mode, checked); else replay_one_frame(c, mode); }
     const hipError_t launch_err = hipGetLastError();            // a failed launch inside the capture must not leave the stream capturing
     HIPCHK(c, hipStreamEndCapture(c->stream, g));
     HIPCHK(c, launch_err);
@@ -1348,18 +1355,55 @@ static void images_restore(srukf_ctx* c)
     c->err = why;
 }
 
-int srukf_run_images_async(srukf_ctx* c, int first, int count, int mode, double* d_traj)
+// what a checked image run needs beyond srukf_stage_images' buffers, allocated on the first one and outside any capture: the checked record (zeroed), the
+// parameters' place on the device, and the filter's score buffer if no srukf_associate_checked has made it.  Captured checked frames hold the score buffer's
+// pointer: they are dropped when it is not the one they were captured with (match_drop has run in between)
+static int images_checked_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    int rc = match_ensure(c, who); if (rc) return rc;
+    if (im.chk_scores != c->match_scores) {
+        for (int m = 0; m < 2; m++) if (im.chk_graphs[m].one_exec) { HIPCHK(c, hipStreamSynchronize(c->stream)); drop_graphs(c); break; }
+        im.chk_scores = c->match_scores;
+    }
+    if (im.corr2_seq) return SRUKF_OK;
+    const size_t N = c->d.N, f = (size_t)im.frames;
+    hipError_t e = srukf_dmalloc(&im.corr2_seq, sizeof(double) * f * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.z2_seq, sizeof(double) * f * 2 * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.flags_seq, sizeof(int) * f * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.match_args, sizeof(MatchArgs));
+    if (e == hipSuccess) e = hipMemsetAsync(im.corr2_seq, 0, sizeof(double) * f * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.z2_seq, 0, sizeof(double) * f * 2 * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.flags_seq, 0, sizeof(int) * f * N, c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* b : { (void*)im.corr2_seq, (void*)im.z2_seq, (void*)im.flags_seq, (void*)im.match_args }) if (b) srukf_dfree_on(b, c->stream);
+        im.corr2_seq = im.z2_seq = nullptr; im.flags_seq = nullptr; im.match_args = nullptr;
+        c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
+    }
+    return SRUKF_OK;
+}
+
+// srukf_run_images_async (chk null) and srukf_run_images_checked_async (chk: the validated parameters): one body, the frames differ in the association launch
+static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double* d_traj, const MatchArgs* chk, const char* who)
 {
     if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    { const int rcm = replay_mode_check(c, mode, "run_images_async"); if (rcm) return rcm; }
-    if (c->storage != SRUKF_STORAGE_F64) { c->err = "run_images_async: image runs are available in SRUKF_STORAGE_F64 only"; return SRUKF_ERR_UNSUPPORTED; }
+    const std::string w = who;
+    { const int rcm = replay_mode_check(c, mode, who); if (rcm) return rcm; }
+    if (c->storage != SRUKF_STORAGE_F64) { c->err = w + ": image runs are available in SRUKF_STORAGE_F64 only"; return SRUKF_ERR_UNSUPPORTED; }
     ImageReplay& im = c->img;
-    if (!im.images) { c->err = "run_images_async: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.images) { c->err = w + ": no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
     if (!c->odo_seq || im.frames != c->seqF || first + count > c->seqF) { c->err = "frames outside the staged sequence"; return SRUKF_ERR_DIM_MISMATCH; }
-    if (c->async_pending && !im.pending) { c->err = "run_images_async: frames of srukf_run_frames_async are in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    if (c->async_pending && !im.pending) { c->err = w + ": frames of srukf_run_frames_async are in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
     c->joint_bad_host = false;
     HIPCHK(c, hipSetDevice(c->device));
-    if (mode == SRUKF_UPDATE_JOINT) { const int rcj = joint_ensure(c, "run_images_async"); if (rcj) return rcj; }      // (before any capture begins)
+    if (mode == SRUKF_UPDATE_JOINT) { const int rcj = joint_ensure(c, who); if (rcj) return rcj; }      // (before any capture begins)
+    const bool checked = chk != nullptr;
+    if (checked) {
+        const int rce = images_checked_ensure(c, who); if (rce) return rce;                           // (idem)
+        srukf_launch_set_match_args(c->stream, im.match_args, *chk);      // in stream order: behind the frames of an earlier run of the block, in front of this run's
+        im.checked = true; c->match_valid = true;
+    }
     step_commit_motion(c); step_state_replaced(c);
     if (c->fs_seq_step) {                                      // the step-wise fast path pointed the frame scalars at its own three poses
         hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, c->stream, c->fs, c->odo_seq, c->seqF, c->p.a1, c->p.a2, c->p.a3, c->p.a4);
@@ -1378,7 +1422,7 @@ int srukf_run_images_async(srukf_ctx* c, int first, int count, int mode, double*
     if (c->red_r > 0 && !c->null_canonical) {
         // null rows that are not (yet) sqrt(EPSILON) e_k: the run's first frame eagerly, as in srukf_run_frames_async (the plain form reads the rows as they are)
         launch_set_run(c->stream, c->fs, first, clear, traj);
-        replay_one_image_frame(c, mode);
+        replay_one_image_frame(c, mode, checked);
         set_null_canonical(c);
         c->async_pending = true; im.pending = true; c->phase = 0; c->frame_updated = false; clear = 0;
         first += 1; count -= 1;
@@ -1387,20 +1431,81 @@ int srukf_run_images_async(srukf_ctx* c, int first, int count, int mode, double*
     }
     launch_set_run(c->stream, c->fs, first, clear, traj);
     if (c->use_graph && !c->profiling) {
-        ReplayGraphs& g = im.graphs[mode == SRUKF_UPDATE_JOINT ? 1 : 0];      // (image frames only: never a captured frame without the association)
+        // (image frames only: never a captured frame without the association; plain and checked frames each have their own)
+        ReplayGraphs& g = (checked ? im.chk_graphs : im.graphs)[mode == SRUKF_UPDATE_JOINT ? 1 : 0];
         if (!g.one_exec) {
-            int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true); if (rc) return rc;
-            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true); if (rc) return rc;
+            int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true, checked); if (rc) return rc;
+            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true, checked); if (rc) return rc;
         }
         int f = 0;
         for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(g.eight_exec, c->stream));
         for (; f < count; f++) HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
     } else {
-        for (int f = 0; f < count; f++) replay_one_image_frame(c, mode);
+        for (int f = 0; f < count; f++) replay_one_image_frame(c, mode, checked);
     }
     c->async_pending = true; im.pending = true;
     c->phase = 0; c->frame_updated = false;
     HIPCHK(c, hipGetLastError());
+    return SRUKF_OK;
+}
+
+int srukf_run_images_async(srukf_ctx* c, int first, int count, int mode, double* d_traj) { return run_images_issue(c, first, count, mode, d_traj, nullptr, "run_images_async"); }
+
+// ---- checked image runs: the ambiguity veto and the sub-pixel peak inside an image run ----
+// srukf_associate_checked's parameter rules (params null: its defaults)
+static int checked_args(srukf_ctx* c, const srukf_match_params* params, MatchArgs* ma)
+{
+    srukf_match_params mp = { 0.8, 0.9, 4, 0 };
+    if (params) mp = *params;
+    if (!std::isfinite(mp.ratio) || mp.ratio <= 0.0) { c->err = "run_images_checked: ratio must be finite and positive"; return SRUKF_ERR_BAD_ARG; }
+    if (mp.exclusion < 1 || mp.exclusion > 20) { c->err = "run_images_checked: exclusion outside [1, 20]"; return SRUKF_ERR_BAD_ARG; }
+    if (!std::isfinite(mp.corr_threshold)) { c->err = "run_images_checked: corr_threshold is not finite"; return SRUKF_ERR_BAD_ARG; }
+    *ma = { .corr_threshold = mp.corr_threshold, .ratio = mp.ratio, .exclusion = mp.exclusion, .subpixel = mp.subpixel };
+    return SRUKF_OK;
+}
+
+int srukf_run_images_checked_async(srukf_ctx* c, int first, int count, int mode, const srukf_match_params* params, double* d_traj)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    MatchArgs ma;
+    const int rc = checked_args(c, params, &ma); if (rc) return rc;
+    return run_images_issue(c, first, count, mode, d_traj, &ma, "run_images_checked_async");
+}
+
+// Synchronous form: as srukf_run_images, no recovery inside the call
+int srukf_run_images_checked(srukf_ctx* c, int first, int count, int mode, const srukf_match_params* params, double* traj_host)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    double* dt = nullptr;
+    HIPCHK(c, srukf_dmalloc((void**)&dt, sizeof(double) * 8 * (size_t)count));
+    int rc = srukf_run_images_checked_async(c, first, count, mode, params, dt);
+    if (rc == SRUKF_OK) rc = srukf_synchronize(c);
+    if (traj_host && rc == SRUKF_OK) hipMemcpy(traj_host, dt, sizeof(double) * 8 * (size_t)count, hipMemcpyDeviceToHost);
+    srukf_dfree(dt);
+    return rc;
+}
+
+// rows [first, first + count) of the checked record, after waiting for the stream like srukf_get_image_matches.  Rows no checked run has written are zero (all of
+// them before the first checked run); a row a plain image run wrote after a checked one keeps the checked run's values
+int srukf_get_image_checks(srukf_ctx* c, int first, int count, double* corr2, double* z2, int* flags)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_checks: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_checks: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    if (!im.corr2_seq) {
+        if (corr2) memset(corr2, 0, sizeof(double) * m * N);
+        if (z2) memset(z2, 0, sizeof(double) * m * 2 * N);
+        if (flags) memset(flags, 0, sizeof(int) * m * N);
+        return SRUKF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (corr2) HIPCHK(c, hipMemcpy(corr2, im.corr2_seq + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
+    if (z2) HIPCHK(c, hipMemcpy(z2, im.z2_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
+    if (flags) HIPCHK(c, hipMemcpy(flags, im.flags_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
     return SRUKF_OK;
 }
 
@@ -1470,16 +1575,17 @@ int srukf_synchronize(srukf_ctx* c)
     if (c->async_pending) {
         c->async_pending = false;
         const bool image_run = c->img.pending;                  // the frames were image frames: a flagged block comes back to its checkpoint here (X, S, matchPatch)
-        c->img.pending = false;
+        const bool checked_run = c->img.checked;                // ... with a checked run among them: a flagged block leaves no valid score map
+        c->img.pending = false; c->img.checked = false;
         int rc = read_fs(c); if (rc) return rc;
         // joint frames: the sticky pair k_joint_dx left (first hit).  A clamp flag of an EARLIER frame goes first: from that frame on nothing is valid anyway
         if (c->hfs->joint_bad_frame > 0 && !(c->hfs->clamp_rows > 0 && c->hfs->clamp_frame < c->hfs->joint_bad_frame - 1)) {
             rc = joint_bad_report(c);
-            if (image_run) { images_restore(c); c->joint_bad_host = false; }
+            if (image_run) { images_restore(c); c->joint_bad_host = false; if (checked_run) c->match_valid = false; }
             return rc;
         }
         if (c->hfs->clamp_rows > 0) {
-            if (image_run) images_restore(c);
+            if (image_run) { images_restore(c); if (checked_run) c->match_valid = false; }
             c->clamp_frame_host = c->hfs->clamp_frame; c->clamp_row_host = c->hfs->clamp_first;
             char b[220]; snprintf(b, sizeof b, "GMW theta clamp active on %d pivot rows (first row %d), first in staged frame %d, during async frames%s", c->hfs->clamp_rows, c->hfs->clamp_first, c->hfs->clamp_frame,
                                  c->hfs->gmw_aborts > 0 ? " (a persistent factorisation launch was abandoned: the GPU is shared; see srukf_set_exclusive)" : "");

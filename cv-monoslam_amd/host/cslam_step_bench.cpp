@@ -15,6 +15,9 @@
 //              per staged frame (srukf_stage_images), then srukf_run_images_async + srukf_synchronize in blocks of `block` frames (default 8: the churn leg changes the
 //              map every ten frames), the warm-up frames first.  The filter is driven by what the device's association finds.  A flagged block comes back restored and
 //              is run step-wise (srukf_associate + srukf_update / srukf_update_joint), inside the timed region; "flagged_blocks" counts them.  Honours joint=1 and set=
+//              unique=<ratio>[,<exclusion>] and / or subpix=1 (assoc_replay only): the blocks are checked image runs (srukf_run_images_checked_async, DESIGN.md §21;
+//              subpix=1 alone: ratio 2, nothing vetoed; exclusion defaults to 4), a restored block runs srukf_associate_checked, and srukf_get_image_checks is read
+//              with the record after every block.  Adds, and only with them, "checked": {ratio, exclusion, subpixel, ambiguous, refined} to the output
 //     hint=1 : capi / assoc announce the NEXT frame's odometry with srukf_predict_motion_next before every update (a host that has its odometry
 //              file loaded, as the reference has: loadOdometryData reads it whole, SLAM.cpp:363-496)
 //     set=key:value : srukf_debug_set(ctx, key, value) after the context exists (capi / assoc; measurement switches, e.g. set=step_fuse_export:0)
@@ -50,6 +53,8 @@ int main(int argc, char** argv)
                                 "       (mode=assoc_replay [block=B]: the staged replay with the association on the device)\n", argv[0]); return 2; }
     std::string mode = "capi";
     int K = 200, W = 20, hint = 0, churn = 0, ransac = 0, ellipsoids = 0, joint = 0, block_frames = 8;
+    bool checked = false; srukf_match_params mpar = { 0.8, 2.0, 4, 0 };      // unique= / subpix=: checked image runs (assoc_replay)
+    long long ambiguous = 0, refined = 0;
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -61,6 +66,8 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "ellipsoids=", 11)) ellipsoids = atoi(argv[a] + 11);
         else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "block=", 6)) block_frames = atoi(argv[a] + 6);
+        else if (!strncmp(argv[a], "unique=", 7)) { checked = true; char* e = nullptr; mpar.ratio = strtod(argv[a] + 7, &e); if (e && *e == ',') mpar.exclusion = atoi(e + 1); }
+        else if (!strncmp(argv[a], "subpix=", 7)) { if (atoi(argv[a] + 7)) { checked = true; mpar.subpixel = 1; } }
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } sets.emplace_back(std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))), atoi(q + 1)); }
     }
     for (auto& kv : sets) (void)srukf_debug_set(nullptr, kv.first.c_str(), kv.second);      // process-wide keys (e.g. set=timing:1) apply in every mode; per-filter keys: mode=capi, below
@@ -94,6 +101,7 @@ int main(int argc, char** argv)
     const char* replay_form = "run_frames_async + synchronize";
     int flagged_blocks = 0;
     const bool areplay = mode == "assoc_replay";
+    if (checked && !areplay) { fprintf(stderr, "unique= / subpix= belong to mode=assoc_replay\n"); return 2; }
     if (areplay && (block_frames < 1 || W < 1)) { fprintf(stderr, "assoc_replay: block >= 1 and warmup >= 1 (frame 0 sets the appearance records up)\n"); return 2; }
     if (mode == "facade") {
         monoslam::CSLAM SLAM;
@@ -269,11 +277,11 @@ int main(int argc, char** argv)
                 for (int fr = 0; fr < W + K; fr++) memcpy(stack.data() + (size_t)fr * img, gray.data(), img);
                 CK(srukf_stage_images(c, W + K, stack.data()));
             }
-            std::vector<int> mrow((size_t)block_frames * N);
+            std::vector<int> mrow((size_t)block_frames * N), frow(checked ? (size_t)block_frames * N : 0), fl(checked ? N : 0);
             auto run = [&](int first, int end, bool timed) -> int {
                 for (int b = first; b < end; b += block_frames) {
                     const int cnt = end - b < block_frames ? end - b : block_frames;
-                    rc = srukf_run_images_async(c, b, cnt, upd, nullptr);
+                    rc = checked ? srukf_run_images_checked_async(c, b, cnt, upd, &mpar, nullptr) : srukf_run_images_async(c, b, cnt, upd, nullptr);
                     if (rc == SRUKF_OK) rc = srukf_synchronize(c);
                     if (rc == SRUKF_ERR_CLAMP_PENDING) {
                         // the block came back restored (X, S, matchPatch): its frames step by step, the device's association driving the filter as in the block
@@ -281,6 +289,10 @@ int main(int argc, char** argv)
                         for (int fr = b; fr < b + cnt; fr++) {
                             CK(srukf_predict_motion(c, &odo[3 * fr], &odo[3 * fr + 3]));
                             CK(srukf_predict_measurement(c, h.data(), Si.data(), vis.data()));
+                            if (checked) {
+                                CK(srukf_associate_checked(c, gray.data(), &mpar, zc.data(), md.data(), corr.data(), nullptr, nullptr, fl.data()));
+                                if (timed) for (int k = 0; k < N; k++) { ambiguous += (fl[k] >> 1) & 1; refined += (fl[k] >> 2) & 1; }
+                            } else
                             CK(srukf_associate(c, gray.data(), zc.data(), md.data(), corr.data()));
                             if (timed) for (int k = 0; k < N; k++) matches_dev += md[k];
                             if (joint) CK(srukf_update_joint(c, zc.data(), md.data(), SRUKF_NEEDNOT_REORDER));
@@ -291,6 +303,10 @@ int main(int argc, char** argv)
                         // (the record is the host's to read after every block: nPredictTimes / nMatchTimes and the border test need it)
                         CK(srukf_get_image_matches(c, b, cnt, nullptr, mrow.data(), nullptr, nullptr, nullptr));
                         for (int q = 0; q < cnt * N; q++) matches_dev += mrow[q];
+                        if (checked) {
+                            CK(srukf_get_image_checks(c, b, cnt, nullptr, nullptr, frow.data()));
+                            for (int q = 0; q < cnt * N; q++) { ambiguous += (frow[q] >> 1) & 1; refined += (frow[q] >> 2) & 1; }
+                        }
                     }
                 }
                 return 0;
@@ -322,9 +338,11 @@ int main(int argc, char** argv)
         srukf_debug_get(c, "meas_flag_ticks", &flag_ticks);
         srukf_destroy(c);
     }
-    char joint_json[200] = "";
+    char joint_json[420] = "";
     if (joint) snprintf(joint_json, sizeof joint_json, "\"joint\": 1, \"joint_flagged_frames\": %d, ", joint_flagged);
     if (areplay) snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"block_frames\": %d, \"flagged_blocks\": %d, ", block_frames, flagged_blocks);
+    if (checked) snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"checked\": {\"ratio\": %.6g, \"exclusion\": %d, \"subpixel\": %d, \"ambiguous\": %lld, \"refined\": %lld}, ",
+                          mpar.ratio, mpar.exclusion, mpar.subpixel, ambiguous, refined);
     if (mode == "replay") snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"replay_form\": \"%s\", \"exact_frames\": %d, ", replay_form, joint_flagged);
     printf("{\"mode\": \"%s\", %s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
            "\"pose\": [%.17g, %.17g, %.17g, %.17g], \"P_robot\": [%.17g, %.17g, %.17g, %.17g], \"device_matches\": %lld, \"stats_flag_us_into_first_launch\": %.2f, \"host_us_per_call\": {\"predict_motion\": %.2f, \"predict_measurement\": %.2f, \"association\": %.2f, \"update\": %.2f, \"get_robot\": %.2f}, "

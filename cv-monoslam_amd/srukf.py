@@ -32,6 +32,7 @@ EXPORTS = [
     "srukf_archive_set", "srukf_archive_count", "srukf_archive_get_template", "srukf_archive_search",
     "srukf_associate_checked", "srukf_get_match_scores",
     "srukf_stage_images", "srukf_run_images_async", "srukf_run_images", "srukf_get_image_matches",
+    "srukf_run_images_checked_async", "srukf_run_images_checked", "srukf_get_image_checks",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -165,6 +166,10 @@ def load_library(path=None):
         L.srukf_run_images_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.srukf_run_images.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp]
         L.srukf_get_image_matches.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _ip, _dp, _ip, _dp]
+    if hasattr(L, "srukf_run_images_checked"):         # (idem: checked image runs)
+        L.srukf_run_images_checked_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MatchParams), C.c_void_p]
+        L.srukf_run_images_checked.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MatchParams), _dp]
+        L.srukf_get_image_checks.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -622,6 +627,45 @@ class Filter:
                    visible=np.zeros((count, N), dtype=np.int32), h=np.zeros((count, 2 * N)))
         self._chk(self._lib.srukf_get_image_matches(self._h, int(first), int(count), _d(out["z"]), _i(out["matched"]), _d(out["corr"]), _i(out["visible"]),
                                                     _d(out["h"])))
+        return out
+
+    @staticmethod
+    def _match_params(corr_threshold, ratio, exclusion, subpixel):
+        """the parameters of a checked image run as the library's struct; types are checked here, values (ratio > 0, exclusion in [1, 20], finite) by the library"""
+        for name, v in (("corr_threshold", corr_threshold), ("ratio", ratio)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError(f"run_images_checked: {name} must be a real number")
+        if isinstance(exclusion, bool) or not isinstance(exclusion, (int, np.integer)):
+            raise TypeError("run_images_checked: exclusion must be an integer")
+        if not isinstance(subpixel, (bool, np.bool_)) and subpixel not in (0, 1):
+            raise TypeError("run_images_checked: subpixel must be a bool")
+        if not -2 ** 31 <= int(exclusion) < 2 ** 31:
+            raise ValueError("run_images_checked: exclusion does not fit an int")
+        return MatchParams(float(corr_threshold), float(ratio), int(exclusion), int(bool(subpixel)))
+
+    def run_images_checked_async(self, first, count, mode=UPDATE_BATCHED, corr_threshold=0.8, ratio=0.9, exclusion=4, subpixel=False, d_traj_ptr=None):
+        """run_images_async with associate_checked's association in every frame (srukf_run_images_checked_async): a match whose second peak reaches ratio * the best
+        is vetoed, subpixel=True refines the best peak.  The parameters may differ from run to run inside a block."""
+        self._image_run_args(first, count, mode)
+        mp = self._match_params(corr_threshold, ratio, exclusion, subpixel)
+        self._chk(self._lib.srukf_run_images_checked_async(self._h, int(first), int(count), int(mode), C.byref(mp), C.c_void_p(d_traj_ptr) if d_traj_ptr else None))
+
+    def run_images_checked(self, first, count, mode=UPDATE_BATCHED, corr_threshold=0.8, ratio=0.9, exclusion=4, subpixel=False):
+        """run_images_checked_async + synchronize -> traj[count, 8]; as run_images for a flagged block.  get_image_matches has z / matched / corr / visible / h,
+        get_image_checks the rest; match_scores(k) then answers for the run's last frame."""
+        self._image_run_args(first, count, mode)
+        mp = self._match_params(corr_threshold, ratio, exclusion, subpixel)
+        traj = np.empty((count, 8))
+        self._chk(self._lib.srukf_run_images_checked(self._h, int(first), int(count), int(mode), C.byref(mp), _d(traj)))
+        return traj
+
+    def get_image_checks(self, first, count):
+        """What checked image runs wrote beside get_image_matches' record for staged frames [first, first + count) (srukf_get_image_checks): dict of corr2[count, N],
+        z2[count, 2N], flags[count, N].  Rows no checked run has written are zero; a row a plain run_images wrote later keeps the checked run's values."""
+        self._image_run_args(first, count, UPDATE_BATCHED)
+        N = self.N
+        out = dict(corr2=np.zeros((count, N)), z2=np.zeros((count, 2 * N)), flags=np.zeros((count, N), dtype=np.int32))
+        self._chk(self._lib.srukf_get_image_checks(self._h, int(first), int(count), _d(out["corr2"]), _d(out["z2"]), _i(out["flags"])))
         return out
 
     def synchronize(self):

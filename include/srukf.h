@@ -507,6 +507,27 @@ int  srukf_run_images_async(srukf_ctx* ctx, int first, int count, int mode, doub
 int  srukf_run_images(srukf_ctx* ctx, int first, int count, int mode, double* traj_host);
 int  srukf_get_image_matches(srukf_ctx* ctx, int first, int count, double* z, int* matched, double* corr, int* visible, double* h);
 
+/* ---- checked image runs: the ambiguity veto and the sub-pixel peak inside an image run ----
+ * srukf_run_images_checked_async / srukf_run_images_checked: srukf_run_images_async / srukf_run_images with srukf_associate_checked's association in every frame
+ *   (k_associate_checked_staged in k_associate_staged's place, nothing else differs: the same frame form, the same wrapPatch, so matchPatch evolves identically
+ *   whichever kind of image run a frame uses).  The reference's part is dataAssociation, SLAM.cpp:1915-2009, as for srukf_associate; the rival test, the veto and the
+ *   parabola are ours (§17), with exactly the rules written out at srukf_associate_checked above: best, rival, ambiguous = raw && corr2 >= ratio * corr,
+ *   matched = raw && !ambiguous, the flag bits, the two forms of z (non-zero for a vetoed landmark; without + frac(h) under subpixel), zeros for a landmark that is
+ *   not visible or has no record.  The update reads that matched / z.  params == NULL: { 0.8, 0.9, 4, 0 }.  The parameters live in a small device struct written in
+ *   stream order in front of each run, so one set of captured frames (their own per update mode: never a plain image run's, nor the other way round) serves every
+ *   parameter value.  Plain and checked image runs may alternate inside one block; checkpoint and restore are srukf_run_images_async's.
+ *   Refusals: those of srukf_run_images_async with the same codes (SEQUENTIAL and the float-stored modes SRUKF_ERR_UNSUPPORTED, nothing staged SRUKF_ERR_SEQUENCE,
+ *   frames outside the stack SRUKF_ERR_DIM_MISMATCH), and SRUKF_ERR_BAD_ARG for ratio not finite or <= 0, exclusion outside [1, 20], corr_threshold not finite.
+ *   Nothing runs and no state changes in any of them.
+ *   Score maps: one per landmark, in the buffer of srukf_associate_checked — after a clean srukf_synchronize srukf_get_match_scores answers for the LAST frame the
+ *   last checked run executed (maps are not kept per frame).  A flagged block leaves no valid map: srukf_get_match_scores then returns SRUKF_ERR_SEQUENCE.
+ * srukf_get_image_checks: rows [first, first + count) of the checked record, after waiting for the stream like srukf_get_image_matches: corr2[count][N],
+ *   z2[count][2N], flags[count][N].  Any may be NULL.  Rows no checked run has written are zero; a row a plain image run wrote AFTER a checked one keeps the checked
+ *   run's values (the host knows which kind of run it issued for a frame).  SRUKF_ERR_SEQUENCE / SRUKF_ERR_DIM_MISMATCH as srukf_get_image_matches. */
+int  srukf_run_images_checked_async(srukf_ctx* ctx, int first, int count, int mode, const srukf_match_params* params, double* d_traj);
+int  srukf_run_images_checked(srukf_ctx* ctx, int first, int count, int mode, const srukf_match_params* params, double* traj_host);
+int  srukf_get_image_checks(srukf_ctx* ctx, int first, int count, double* corr2, double* z2, int* flags);
+
 /* ---- instrumentation ------------------------------------------------------------------------ */
 
 /* When on, every kernel launch is bracketed by HIP events on the context's stream and the
