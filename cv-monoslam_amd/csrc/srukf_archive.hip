@@ -8,6 +8,9 @@
 //     k_archive_search    one workgroup per visible record: the frame bytes of the gate's bounding box in LDS, the normalised cross correlation of every gated
 //                         candidate from exact integer sums, the first maximum in row-major order.  The gate (Si^T Si, its inverse, the distance) and the
 //                         first-maximum reduction are the association's (srukf_patch.h); the window rule, the score and the byte staging are this file's
+//   srukf_images_search_archive  the same search behind every frame of an image run: seq_archive_search = k_block_cov (P4, the launch srukf_get_robot
+//                         makes) + k_archive_frame_begin (pose, templates and hit counter zeroed) + k_archive_predict + k_warp_patch + k_archive_search_staged, which
+//                         is k_archive_search's body (one text: archive_search_body) on the frame's staged image, writing the frame's row of the search record
 // The robot pose and its 4 x 4 covariance are what srukf_get_robot returns at that moment (that call is made); every buffer written is the archive's own, and the
 // staging area is the archive's own pinned block (the context's may hold a statistics mirror the next srukf_predict_measurement reads).
 // This file is built with -ffp-contract=off: tests/np_archive.py restates its arithmetic.
@@ -109,19 +112,18 @@ __global__ __launch_bounds__(64) void k_archive_predict(srukf_params p, KWeights
 //   (NP = PT_TMPL_BYTES)  A = NP sum(vt) - sum(v) sum(t),  B = NP sum(v^2) - sum(v)^2,  C = NP sum(t^2) - sum(t)^2,  cc = (B == 0 || C == 0) ? 0 : (double)A / sqrt((double)B (double)C)
 // The staged bytes stay bytes (<= 97 x 97 in rows of 100): neighbouring lanes take neighbouring centres, so a wave's byte reads of one template position fall into
 // <= 17 consecutive dwords of a row (and the rows of a wave that spans two window rows lie 25 banks apart); the template is read as one broadcast dword per position.
-__global__ __launch_bounds__(256) void k_archive_search(srukf_params p, int cap, double thr, double chi2, const unsigned char* __restrict__ image,
-                                                        const double* __restrict__ h, const double* __restrict__ Si, const int* __restrict__ vis,
-                                                        const unsigned char* __restrict__ tmpl, int tmpl_stride, double* __restrict__ z, int* __restrict__ matched,
-                                                        double* __restrict__ corr)
+// the body of k_archive_search and k_archive_search_staged for record k: z (2), matched, corr are the record's own slots.  256 threads
+__device__ __forceinline__ void archive_search_body(int k, const srukf_params& p, int cap, double thr, double chi2, const unsigned char* __restrict__ image,
+                                                    const double* __restrict__ h, const double* __restrict__ Si, const unsigned char* __restrict__ tmpl, int tmpl_stride,
+                                                    double* __restrict__ z, int* __restrict__ matched, double* __restrict__ corr)
 {
     __shared__ unsigned char rg[AR_RG_W * AR_RG_STRIDE];
     __shared__ int tm[PT_TMPL_BYTES];
     __shared__ int tsum[2];
     __shared__ double bestv[256];
     __shared__ int besti[256];
-    const int k = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int W = (int)p.image_w, H = (int)p.image_h;
-    if (!vis[k]) { if (tid == 0) { matched[k] = 0; corr[k] = 0.0; z[2 * k] = 0.0; z[2 * k + 1] = 0.0; } return; }
     const double px = h[2 * k], py = h[2 * k + 1];
     const PatchGate g = patch_gate(Si + 4 * k);
     const double capd = (double)min(max(cap, PT_MATCH_HALF), AR_CAP_MAX);
@@ -173,11 +175,66 @@ __global__ __launch_bounds__(256) void k_archive_search(srukf_params p, int cap,
     if (tid == 0) {
         const double mx = bestv[0];
         const int c = besti[0];
-        corr[k] = mx;
-        if (mx > thr) { z[2 * k] = (double)(x0 + c % wx); z[2 * k + 1] = (double)(y0 + c / wx); matched[k] = 1; }
-        else { z[2 * k] = 0.0; z[2 * k + 1] = 0.0; matched[k] = 0; }
+        *corr = mx;
+        if (mx > thr) { z[0] = (double)(x0 + c % wx); z[1] = (double)(y0 + c / wx); *matched = 1; }
+        else { z[0] = 0.0; z[1] = 0.0; *matched = 0; }
     }
 }
+
+__global__ __launch_bounds__(256) void k_archive_search(srukf_params p, int cap, double thr, double chi2, const unsigned char* __restrict__ image,
+                                                        const double* __restrict__ h, const double* __restrict__ Si, const int* __restrict__ vis,
+                                                        const unsigned char* __restrict__ tmpl, int tmpl_stride, double* __restrict__ z, int* __restrict__ matched,
+                                                        double* __restrict__ corr)
+{
+    const int k = blockIdx.x;
+    if (!vis[k]) { if (threadIdx.x == 0) { matched[k] = 0; corr[k] = 0.0; z[2 * k] = 0.0; z[2 * k + 1] = 0.0; } return; }
+    archive_search_body(k, p, cap, thr, chi2, image, h, Si, tmpl, tmpl_stride, z + 2 * k, matched + k, corr + k);
+}
+
+// ---- the search behind every frame of an image run (srukf_images_search_archive) ----
+// The frame tail has advanced fs->frame by the time these run: the frame that was just updated is fs->frame - 1.  A frame outside the staged stack writes nothing
+// outside the archive's own scratch.
+
+// in front of a frame's search: the posterior pose into rob (k_block_cov has left P4 behind it), the templates zeroed (a template depends on this search's inputs
+// only), the frame's hit counter zeroed
+__global__ __launch_bounds__(256) void k_archive_frame_begin(int n, const double* __restrict__ X, double* __restrict__ rob, unsigned long long* __restrict__ tmpl8, int words,
+                                                             StagedArchive a)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g < words) tmpl8[g] = 0ull;
+    if (g < 4) rob[g] = X[n - 4 + g];
+    const int f = a.fs->frame - 1;
+    if (g == 0 && f >= 0 && f < a.frames) a.hits[f] = 0;
+}
+
+// k_archive_search on frame fs->frame - 1 of the staged stack, with half cap, threshold and chi2 read from a.args (written in stream order in front of the run: a captured
+// frame holds the pointer, not the values); the frame's h, Si, visible and the result go into its row of the record, its matches are counted in hits
+__global__ __launch_bounds__(256) void k_archive_search_staged(srukf_params p, StagedArchive a, const double* __restrict__ h, const double* __restrict__ Si,
+                                                               const int* __restrict__ vis, const unsigned char* __restrict__ tmpl, int tmpl_stride)
+{
+    const int k = blockIdx.x, L = gridDim.x, tid = threadIdx.x;
+    const int f = a.fs->frame - 1;
+    if (f < 0 || f >= a.frames) return;
+    const ArchiveArgs ar = *a.args;
+    const size_t r1 = (size_t)f * L + k;
+    const int v = vis[k];
+    if (tid == 0) {
+        a.vis_seq[r1] = v; a.h_seq[2 * r1] = h[2 * k]; a.h_seq[2 * r1 + 1] = h[2 * k + 1];
+        for (int e = 0; e < 4; e++) a.Si_seq[4 * r1 + e] = Si[4 * k + e];
+    }
+    if (!v) { if (tid == 0) { a.m_seq[r1] = 0; a.corr_seq[r1] = 0.0; a.z_seq[2 * r1] = 0.0; a.z_seq[2 * r1 + 1] = 0.0; } return; }
+    const unsigned char* image = a.images + (size_t)f * (size_t)((int)p.image_w * (int)p.image_h);
+    archive_search_body(k, p, ar.half_cap, ar.corr_threshold, ar.chi2, image, h, Si, tmpl, tmpl_stride, a.z_seq + 2 * r1, a.m_seq + r1, a.corr_seq + r1);
+    if (tid == 0 && a.m_seq[r1]) atomicAdd(a.hits + f, 1);
+}
+
+__global__ void k_set_archive_args(ArchiveArgs* dst, ArchiveArgs v) { *dst = v; }
+
+void launch_archive_search_staged(hipStream_t st, int L, srukf_params p, StagedArchive a, const double* h, const double* Si, const int* vis, const unsigned char* tmpl)
+{
+    hipLaunchKernelGGL(k_archive_search_staged, dim3(L), dim3(256), 0, st, p, a, h, Si, vis, tmpl, PT_TMPL_STRIDE);
+}
+void launch_set_archive_args(hipStream_t st, ArchiveArgs* dst, ArchiveArgs v) { hipLaunchKernelGGL(k_set_archive_args, dim3(1), dim3(1), 0, st, dst, v); }
 
 namespace srukf_impl {
 
@@ -193,6 +250,79 @@ void archive_free(ArchiveState& a, hipStream_t st)
 
 // out (device) and hst (pinned) share one layout, in doubles: h 2L | Si 4L | z 2L | corr L | xyz 3L | visible L ints | matched L ints
 static size_t ar_out_doubles(int L) { return 12 * (size_t)L + ((size_t)L + 1) / 2 * 2; }
+struct ArOut { double *h, *Si, *z, *corr, *xyz; int *vis, *m; };
+static ArOut ar_out(const ArchiveState& a)
+{
+    const size_t L = (size_t)a.L;
+    ArOut o;
+    o.h = a.out; o.Si = o.h + 2 * L; o.z = o.Si + 4 * L; o.corr = o.z + 2 * L; o.xyz = o.corr + L;
+    o.vis = (int*)(o.xyz + 3 * L); o.m = o.vis + L;
+    return o;
+}
+static double ar_search_bytes(int half_cap, int L)
+{
+    const double side = 2.0 * half_cap + 1.0 + 2.0 * PT_MATCH_HALF;
+    return (side * side + PT_TMPL_BYTES) * L;
+}
+
+// stages (a) and (b) of a search over the archive's arrays, for the pose | P4 that stand in a.rob (the templates are zeroed): what srukf_archive_search and the
+// searching frames of an image run both launch
+static void archive_predict_warp(srukf_ctx* c)
+{
+    ArchiveState& a = c->archive;
+    const int L = a.L;
+    const ArOut o = ar_out(a);
+    KWeights w; host_weights(AR_NA, c->p, w);
+    {
+        ProfScope ps(c, KC_ARCHIVE_PREDICT, 0, 8.0 * 62 * L);
+        hipLaunchKernelGGL(k_archive_predict, dim3(L), dim3(64), 0, c->stream, c->p, w, a.X6, a.S66, a.rob, o.h, o.Si, o.vis, o.xyz);
+    }
+    KDims ad = {}; ad.N = L; ad.n = 4;                                                                  // k_warp_patch reads d.N and X[n - 4 .. n - 1]: the archive's pose
+    {
+        ProfScope ps(c, KC_ARCHIVE_WARP, 0, (double)(PT_PATCH_BYTES + PT_TMPL_BYTES) * L);
+        srukf_launch_warp_patch(c->stream, ad, c->p, a.rob, o.xyz, o.h, a.R, a.t, a.px, a.patch, o.vis, a.tmpl);
+    }
+}
+
+// srukf_archive_search's parameter rules (ap null: its defaults), for the step-wise call and the switch of the image runs
+static int archive_params(srukf_ctx* c, const srukf_archive_params* ap, srukf_archive_params* out)
+{
+    srukf_archive_params prm = { AR_CAP_MAX, 0.8, 5.99146454710798 };                                   // THRESHOLD_MATCH_PATCH, the gate of dataAssociation (1977)
+    if (ap) prm = *ap;
+    if (prm.half_cap < 10 || prm.half_cap > AR_CAP_MAX) { c->err = "archive_search: half_cap outside [10, 40]"; return SRUKF_ERR_BAD_ARG; }
+    if (!(prm.chi2 > 0.0) || !std::isfinite(prm.chi2) || !std::isfinite(prm.corr_threshold)) { c->err = "archive_search: chi2 / corr_threshold"; return SRUKF_ERR_BAD_ARG; }
+    *out = prm;
+    return SRUKF_OK;
+}
+
+namespace srukf_impl {
+
+// The search behind a frame of a searching image run (replay_one_image_frame, behind seq_refactor: the posterior).  P4 by the launch srukf_get_robot makes, straight
+// into rob's P4 slots; the pose, the zeroed templates and the zeroed hit counter by k_archive_frame_begin; then the step-wise call's two launches and the staged search.
+// Every launch on the filter's stream; images_archive_ensure has run (never inside a capture)
+void seq_archive_search(srukf_ctx* c)
+{
+    ArchiveState& a = c->archive;
+    const ImageReplay& im = c->img;
+    const int L = a.L;
+    const ArOut o = ar_out(a);
+    const ImageArchiveRecord r = image_archive_record(im.frames, L);
+    double* rec = im.ar_rec; int* reci = (int*)(rec + r.ints);
+    const StagedArchive sa = { im.images, im.frames, rec + r.h, rec + r.Si, rec + r.z, rec + r.corr, reci + r.vis_i, reci + r.m_i, reci + r.hits_i, c->fs, im.ar_args };
+    {
+        ProfScope ps(c, KC_ARCHIVE_PREDICT, 0, 8.0 * (20 + (double)L * PT_TMPL_STRIDE / 8));
+        srukf_launch_block_cov(c->stream, c->d, c->S, c->d.n - 4, 4, a.rob + 4, nullptr);
+        const int words = L * (PT_TMPL_STRIDE / 8);
+        hipLaunchKernelGGL(k_archive_frame_begin, dim3((words + 255) / 256), dim3(256), 0, c->stream, c->d.n, c->X, a.rob, (unsigned long long*)a.tmpl, words, sa);
+    }
+    archive_predict_warp(c);
+    {
+        ProfScope ps(c, KC_ARCHIVE_SEARCH, 0, ar_search_bytes(c->img_search_args.half_cap, L));
+        launch_archive_search_staged(c->stream, L, c->p, sa, o.h, o.Si, o.vis, a.tmpl);
+    }
+}
+
+}  // namespace srukf_impl
 
 extern "C" {
 
@@ -213,6 +343,7 @@ int srukf_archive_set(srukf_ctx* c, int L, const double* X6, const double* S66, 
     }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    images_archive_drop(c, c->stream);                           // (the record of the searching image runs and their captured frames are sized by L and hold these pointers)
     archive_free(c->archive, c->stream);
     if (L == 0) return SRUKF_OK;
     ArchiveState& a = c->archive;
@@ -257,12 +388,10 @@ int srukf_archive_search(srukf_ctx* c, const unsigned char* gray, const srukf_ar
                          double* corr)
 {
     if (!c) return SRUKF_ERR_BAD_ARG;
-    srukf_archive_params prm = { AR_CAP_MAX, 0.8, 5.99146454710798 };                                   // THRESHOLD_MATCH_PATCH, the gate of dataAssociation (1977)
-    if (ap) prm = *ap;
-    if (prm.half_cap < 10 || prm.half_cap > AR_CAP_MAX) { c->err = "archive_search: half_cap outside [10, 40]"; return SRUKF_ERR_BAD_ARG; }
-    if (!(prm.chi2 > 0.0) || !std::isfinite(prm.chi2) || !std::isfinite(prm.corr_threshold)) { c->err = "archive_search: chi2 / corr_threshold"; return SRUKF_ERR_BAD_ARG; }
+    srukf_archive_params prm;
+    int rc = archive_params(c, ap, &prm); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = take_frame(c, gray); if (rc) return rc;
+    rc = take_frame(c, gray); if (rc) return rc;
     ArchiveState& a = c->archive;
     const int L = a.L;
     if (L == 0) { if (gray) HIPCHK(c, hipStreamSynchronize(c->stream)); return SRUKF_OK; }
@@ -270,24 +399,13 @@ int srukf_archive_search(srukf_ctx* c, const unsigned char* gray, const srukf_ar
     double* hrob = a.hst + od;
     rc = srukf_get_robot(c, hrob, hrob + 4); if (rc) return rc;                                         // pose | P4, exactly as the caller would get them now
     HIPCHK(c, hipMemcpyAsync(a.rob, hrob, sizeof(double) * 20, hipMemcpyHostToDevice, c->stream));
-    double* dh = a.out; double* dSi = dh + 2 * (size_t)L; double* dz = dSi + 4 * (size_t)L; double* dcorr = dz + 2 * (size_t)L; double* dxyz = dcorr + L;
-    int* dvis = (int*)(dxyz + 3 * (size_t)L); int* dm = dvis + L;
+    const ArOut o = ar_out(a);
     HIPCHK(c, hipMemsetAsync(a.tmpl, 0, (size_t)L * PT_TMPL_STRIDE, c->stream));  // a template depends on this call's inputs only
-    KWeights w; host_weights(AR_NA, c->p, w);
+    archive_predict_warp(c);
     {
-        ProfScope ps(c, KC_ARCHIVE_PREDICT, 0, 8.0 * 62 * L);
-        hipLaunchKernelGGL(k_archive_predict, dim3(L), dim3(64), 0, c->stream, c->p, w, a.X6, a.S66, a.rob, dh, dSi, dvis, dxyz);
-    }
-    KDims ad = {}; ad.N = L; ad.n = 4;                                                                  // k_warp_patch reads d.N and X[n - 4 .. n - 1]: the archive's pose
-    {
-        ProfScope ps(c, KC_ARCHIVE_WARP, 0, (double)(PT_PATCH_BYTES + PT_TMPL_BYTES) * L);
-        srukf_launch_warp_patch(c->stream, ad, c->p, a.rob, dxyz, dh, a.R, a.t, a.px, a.patch, dvis, a.tmpl);
-    }
-    {
-        const double side = 2.0 * prm.half_cap + 1.0;
-        ProfScope ps(c, KC_ARCHIVE_SEARCH, 0, ((side + 2.0 * PT_MATCH_HALF) * (side + 2.0 * PT_MATCH_HALF) + PT_TMPL_BYTES) * L);
-        hipLaunchKernelGGL(k_archive_search, dim3(L), dim3(256), 0, c->stream, c->p, prm.half_cap, prm.corr_threshold, prm.chi2, c->d_image, dh, dSi, dvis, a.tmpl,
-                           PT_TMPL_STRIDE, dz, dm, dcorr);
+        ProfScope ps(c, KC_ARCHIVE_SEARCH, 0, ar_search_bytes(prm.half_cap, L));
+        hipLaunchKernelGGL(k_archive_search, dim3(L), dim3(256), 0, c->stream, c->p, prm.half_cap, prm.corr_threshold, prm.chi2, c->d_image, o.h, o.Si, o.vis, a.tmpl,
+                           PT_TMPL_STRIDE, o.z, o.m, o.corr);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(a.hst, a.out, sizeof(double) * od, hipMemcpyDeviceToHost, c->stream));
@@ -300,6 +418,19 @@ int srukf_archive_search(srukf_ctx* c, const unsigned char* gray, const srukf_ar
     if (corr) memcpy(corr, hs + 8 * (size_t)L, sizeof(double) * L);
     if (visible) memcpy(visible, hi, sizeof(int) * L);
     if (matched) memcpy(matched, hi + L, sizeof(int) * L);
+    return SRUKF_OK;
+}
+
+// The switch of the image runs: on the handle, like the archive; the parameters are srukf_archive_search's, checked by its rules.  Touches no
+// device: the values reach it in stream order in front of the next searching run (run_images_issue)
+int srukf_images_search_archive(srukf_ctx* c, int on, const srukf_archive_params* ap)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    srukf_archive_params prm = { AR_CAP_MAX, 0.8, 5.99146454710798 };
+    if (on) { const int rc = archive_params(c, ap, &prm); if (rc) return rc; }
+    if (c->async_pending && c->img.pending) { c->err = "images_search_archive: an image run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    c->img_search = on != 0;
+    c->img_search_args = ArchiveArgs{ prm.half_cap, prm.corr_threshold, prm.chi2 };
     return SRUKF_OK;
 }
 

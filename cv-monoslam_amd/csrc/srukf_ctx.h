@@ -8,7 +8,8 @@
 //   srukf_ransac.hip  1-point RANSAC: the consensus over all single-match hypotheses, the measurement prediction from the posterior
 //   srukf_overlay.hip colour-frame intake (srukf_set_frame_bgr) and the 2-D feature overlay (srukf_render_overlay)
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
-//   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search)
+//   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search), step-wise and behind the frames of an image run
+//                     (srukf_images_search_archive: seq_archive_search, k_archive_search_staged; srukf_get_image_archive: srukf_replay.hip)
 //   srukf_joint.hip   the joint measurement update's kernels (srukf_update_joint, SRUKF_UPDATE_JOINT frames of the staged replay; host code: srukf_step.hip, srukf_replay.hip)
 //   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip; srukf_run_images_checked*: srukf_replay.hip)
 //   srukf_patch.h     (through srukf_launch.h) the appearance record's sizes, the checked association's buffer layouts, the search kernels' shared front
@@ -102,6 +103,14 @@ struct ImageReplay {
     MatchArgs* match_args = nullptr; const double* chk_scores = nullptr;
     bool checked = false;
     ReplayGraphs chk_graphs[2];
+    // Searching image runs (srukf_images_search_archive), allocated by images_archive_ensure in front of the first one: the per-frame record of
+    // the archive search (ar_rec: ImageArchiveRecord for frames x ar_L, zero until a searching run writes a row), the parameters the searching frames read (ar_args,
+    // written in stream order in front of every searching run) and captured frames of their own per kind of image run and update mode (ar_graphs[checked][mode]: a
+    // searching run never replays a frame captured without the search, nor the other way round; they hold the archive's pointers and L workgroups: images_archive_drop).
+    // ar_valid: a searching run has written the record and no flagged block has been restored since; searching: the block in flight holds a searching run
+    double* ar_rec = nullptr; ArchiveArgs* ar_args = nullptr; int ar_L = 0;
+    bool ar_valid = false, searching = false;
+    ReplayGraphs ar_graphs[2][2];
 };
 
 // ---- the context: who owns what across a map change ("who owns what across a map change") ----------------------
@@ -141,6 +150,8 @@ struct srukf_handle_scope : srukf_switches {
     unsigned char *d_image = nullptr, *d_bgr = nullptr, *d_ovl = nullptr; bool frame_valid = false, bgr_valid = false;
     DetScratch det;                        // srukf_detect_features
     ArchiveState archive;                  // srukf_archive_set / srukf_archive_search
+    bool img_search = false;               // srukf_images_search_archive: every frame of every later image run is followed by a search of the archive, with ...
+    ArchiveArgs img_search_args = { 40, 0.8, 5.99146454710798 };   // ... these parameters.  Survives map changes; srukf_reset clears it
     std::string err;
     // the pool allocations among the members above (det and archive: det_scratch_free / archive_free).  A new buffer of this scope is added HERE
     template <class F> void each_device_buffer(F f) const { void* b[] = { d_image, d_bgr, d_ovl }; for (void* q : b) f(q); }
@@ -312,7 +323,7 @@ struct srukf_map_scope : srukf_life {
                       red_head0_tiles, split_fold_list, red_syrk_tiles, ckS, ckX, syrk_tiles, pxy_tiles, syrk_head_tiles, syrk_head_tiles_b, fs,
                       odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt, jointZd, jointW, jointRd,
                       img.images, img.ck_tmpl, img.corr_seq, img.h_seq, img.xyz, img.ckS, img.ckX, img.vis_seq,
-                      img.corr2_seq, img.z2_seq, img.flags_seq, img.match_args };
+                      img.corr2_seq, img.z2_seq, img.flags_seq, img.match_args, img.ar_rec, img.ar_args };
         for (void* q : b) f(q);
     }
 };
@@ -382,6 +393,7 @@ int ensure_appearance(srukf_ctx* c);      // the per-landmark appearance records
 
 // ---- archive search (srukf_archive.hip) ----
 void archive_free(ArchiveState& a, hipStream_t st);
+void seq_archive_search(srukf_ctx* c);                 // the search behind a frame of a searching image run (behind seq_refactor)
 
 // ---- display ellipsoids (srukf_display.hip) ----
 void launch_lm_ellipsoid(hipStream_t st, int N, double eps, const double* cov, double* axis, double* sigma, int* rot);
@@ -487,6 +499,7 @@ void seq_joint_launches(srukf_ctx* c, const double* z_dev, const int* m_dev);
 int update_null_set(srukf_ctx* c);
 int mixed_red_ensure(srukf_ctx* c);
 void drop_graphs(srukf_map_scope* c);
+void images_archive_drop(srukf_map_scope* c, hipStream_t st);      // the searching image runs' record, parameters and captured frames go (the archive changes; the caller has synchronised the stream)
 void images_drop(srukf_map_scope* c, hipStream_t st);      // the staged images, their record, checkpoint and captured frames go (the caller has synchronised the stream)
 void exact_path(srukf_ctx* c, const double* Gbuf, double* Sout);      // the exact column path for Gbuf -> Sout (D, theta, clamp count as side effects)
 void set_null_canonical(srukf_ctx* c);

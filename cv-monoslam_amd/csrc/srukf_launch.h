@@ -76,6 +76,23 @@ struct StagedChecked {
     const MatchArgs* ma;
 };
 
+// The archive search behind every frame of an image run (srukf_images_search_archive).  ArchiveArgs: srukf_archive_search's parameters on the
+// device, written in stream order in front of a run (MatchArgs' pattern).  ImageArchiveRecord: the per-frame record, one allocation — h [F][2L] | Si [F][4L] |
+// z [F][2L] | corr [F][L] (offsets in doubles), then from `ints` (in doubles) on, as ints: visible [F][L] | matched [F][L] | hits [F]; `doubles`: its size.
+// StagedArchive: what k_archive_search_staged takes of it — the staged image stack, the record's arrays, the frame counter (the frame searched is fs->frame - 1: the
+// frame tail has advanced it), the parameters
+struct ArchiveArgs { int half_cap; double corr_threshold, chi2; };
+struct ImageArchiveRecord { size_t h, Si, z, corr, ints, vis_i, m_i, hits_i, doubles; };
+constexpr ImageArchiveRecord image_archive_record(size_t F, size_t L)
+{
+    return { .h = 0, .Si = 2 * F * L, .z = 6 * F * L, .corr = 8 * F * L, .ints = 9 * F * L, .vis_i = 0, .m_i = F * L, .hits_i = 2 * F * L, .doubles = 9 * F * L + (2 * F * L + F + 1) / 2 };
+}
+struct StagedArchive {
+    const unsigned char* images; int frames;
+    double* h_seq; double* Si_seq; double* z_seq; double* corr_seq; int* vis_seq; int* m_seq; int* hits;
+    const FrameScalars* fs; const ArchiveArgs* args;
+};
+
 extern "C" {
 // ---- srukf_predict.hip ----
 void srukf_launch_landmarks_cartesian(hipStream_t st, KDims d, const double* X, const double* S, double* xyz, double* cov);
@@ -198,3 +215,9 @@ void launch_joint_form(hipStream_t st, KDims d, KWeights w, const JointFrame& f,
                        double* Zd, double* W, int* status);
 void launch_joint_factor(hipStream_t st, KDims d, double* W, double* Rd, int* status);
 void launch_joint_dx(hipStream_t st, KDims d, double* W, const double* Rd, const int* status, double* Ut, double* X, FrameScalars* fs, const RankArgs& ra);
+
+// ---- srukf_archive.hip (the search behind the frames of an image run; C++ linkage) ----
+// k_archive_search_staged: k_archive_search (one text of its body) on frame fs->frame - 1 of the staged images, L workgroups; h / Si / vis / tmpl: the archive's own
+// arrays as k_archive_predict and k_warp_patch left them.  launch_set_archive_args: *dst = v on the stream
+void launch_archive_search_staged(hipStream_t st, int L, srukf_params p, StagedArchive a, const double* h, const double* Si, const int* vis, const unsigned char* tmpl);
+void launch_set_archive_args(hipStream_t st, ArchiveArgs* dst, ArchiveArgs v);

@@ -930,7 +930,7 @@ int read_fs_host(srukf_ctx* c)
 
 void drop_graphs(srukf_map_scope* c)
 {
-    for (ReplayGraphs* gs : { c->graphs, c->img.graphs, c->img.chk_graphs }) for (int m = 0; m < 2; m++) {      // the captured frames of both update modes: without the association, with it, with the checked one
+    for (ReplayGraphs* gs : { c->graphs, c->img.graphs, c->img.chk_graphs, c->img.ar_graphs[0], c->img.ar_graphs[1] }) for (int m = 0; m < 2; m++) {      // the captured frames of both update modes: without the association, with it, with the checked one, with the archive search behind either
         ReplayGraphs& g = gs[m];
         for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec, &g.block_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
         for (hipGraph_t* q : { &g.one, &g.eight, &g.block }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
@@ -938,12 +938,26 @@ void drop_graphs(srukf_map_scope* c)
     }
 }
 
+// the archive changes (srukf_archive_set): the searching frames were captured with its pointers and L workgroups, the record is sized by L.  The next searching run
+// builds both again (images_archive_ensure)
+void images_archive_drop(srukf_map_scope* c, hipStream_t st)
+{
+    ImageReplay& im = c->img;
+    for (int k = 0; k < 2; k++) for (int m = 0; m < 2; m++) {
+        ReplayGraphs& g = im.ar_graphs[k][m];
+        for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
+        for (hipGraph_t* q : { &g.one, &g.eight }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
+    }
+    for (void* b : { (void*)im.ar_rec, (void*)im.ar_args }) if (b) srukf_dfree_on(b, st);
+    im.ar_rec = nullptr; im.ar_args = nullptr; im.ar_L = 0; im.ar_valid = false;
+}
+
 void images_drop(srukf_map_scope* c, hipStream_t st)
 {
     ImageReplay& im = c->img;
     if (im.images) drop_graphs(c);                               // (the captured image frames hold these pointers)
     for (void* b : { (void*)im.images, (void*)im.ck_tmpl, (void*)im.corr_seq, (void*)im.h_seq, (void*)im.xyz, (void*)im.ckS, (void*)im.ckX, (void*)im.vis_seq,
-                      (void*)im.corr2_seq, (void*)im.z2_seq, (void*)im.flags_seq, (void*)im.match_args }) if (b) srukf_dfree_on(b, st);
+                      (void*)im.corr2_seq, (void*)im.z2_seq, (void*)im.flags_seq, (void*)im.match_args, (void*)im.ar_rec, (void*)im.ar_args }) if (b) srukf_dfree_on(b, st);
     im = ImageReplay{};
 }
 
@@ -1007,7 +1021,9 @@ static void replay_one_frame(srukf_ctx* c, int mode)
 // below "fused tail" mode), and k_pxy has run.  The points go to the image state's own scratch, not c->G.
 // joint_ensure has run for JOINT (run_images_async: never inside a capture)
 // checked: a frame of a checked image run — the same frame with k_associate_checked_staged in k_associate_staged's place; images_checked_ensure has run
-static void replay_one_image_frame(srukf_ctx* c, int mode, bool checked)
+// search: a frame of a searching image run — the same frame with the archive search behind its tail, on the posterior (seq_archive_search: it
+// writes the archive's own buffers and the search record, nothing the filter reads); images_archive_ensure has run
+static void replay_one_image_frame(srukf_ctx* c, int mode, bool checked, bool search)
 {
     ImageReplay& im = c->img;
     const KDims& d = c->d;
@@ -1028,13 +1044,14 @@ static void replay_one_image_frame(srukf_ctx* c, int mode, bool checked)
     if (mode == SRUKF_UPDATE_JOINT) seq_joint_launches(c, nullptr, nullptr);
     else seq_gain_only(c, nullptr, nullptr, FORM_PLAIN);
     seq_refactor(c, refactor_frame_tail(c), FORM_PLAIN);
+    if (search) seq_archive_search(c);
 }
 
-// images: frames of an image run (checked: of a checked one)
-static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge, bool images = false, bool checked = false)
+// images: frames of an image run (checked: of a checked one; search: of a searching one)
+static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge, bool images = false, bool checked = false, bool search = false)
 {
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    for (int q = 0; q < nframes; q++) { if (images) replay_one_image_frame(c, mode, checked); else replay_one_frame(c, mode); }
+    for (int q = 0; q < nframes; q++) { if (images) replay_one_image_frame(c, mode, checked, search); else replay_one_frame(c, mode); }
     const hipError_t launch_err = hipGetLastError();            // a failed launch inside the capture must not leave the stream capturing
     HIPCHK(c, hipStreamEndCapture(c->stream, g));
     HIPCHK(c, launch_err);
@@ -1384,6 +1401,27 @@ static int images_checked_ensure(srukf_ctx* c, const char* who)
     return SRUKF_OK;
 }
 
+// what a searching image run needs beyond srukf_stage_images' buffers, allocated in front of the first one and outside any capture: the search record for the
+// archive's L (zeroed) and the parameters' place on the device.  srukf_archive_set drops both with the captured searching frames (images_archive_drop)
+static int images_archive_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    if (im.ar_rec) return SRUKF_OK;
+    const int L = c->archive.L;
+    const size_t bytes = sizeof(double) * image_archive_record((size_t)im.frames, (size_t)L).doubles;
+    hipError_t e = srukf_dmalloc(&im.ar_rec, bytes);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.ar_args, sizeof(ArchiveArgs));
+    if (e == hipSuccess) e = hipMemsetAsync(im.ar_rec, 0, bytes, c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* b : { (void*)im.ar_rec, (void*)im.ar_args }) if (b) srukf_dfree_on(b, c->stream);
+        im.ar_rec = nullptr; im.ar_args = nullptr;
+        c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
+    }
+    im.ar_L = L;
+    return SRUKF_OK;
+}
+
 // srukf_run_images_async (chk null) and srukf_run_images_checked_async (chk: the validated parameters): one body, the frames differ in the association launch
 static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double* d_traj, const MatchArgs* chk, const char* who)
 {
@@ -1404,6 +1442,16 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         srukf_launch_set_match_args(c->stream, im.match_args, *chk);      // in stream order: behind the frames of an earlier run of the block, in front of this run's
         im.checked = true; c->match_valid = true;
     }
+    // the archive search behind every frame (srukf_images_search_archive).  An empty archive: a plain run, and a record of L = 0
+    const bool search = c->img_search && c->archive.L > 0;
+    if (c->img_search) {
+        if (search) {
+            const int rca = images_archive_ensure(c, who); if (rca) return rca;                        // (idem)
+            launch_set_archive_args(c->stream, im.ar_args, c->img_search_args);      // in stream order, as the checked run's parameters
+            im.searching = true;
+        }
+        im.ar_valid = true;
+    }
     step_commit_motion(c); step_state_replaced(c);
     if (c->fs_seq_step) {                                      // the step-wise fast path pointed the frame scalars at its own three poses
         hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, c->stream, c->fs, c->odo_seq, c->seqF, c->p.a1, c->p.a2, c->p.a3, c->p.a4);
@@ -1422,7 +1470,7 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
     if (c->red_r > 0 && !c->null_canonical) {
         // null rows that are not (yet) sqrt(EPSILON) e_k: the run's first frame eagerly, as in srukf_run_frames_async (the plain form reads the rows as they are)
         launch_set_run(c->stream, c->fs, first, clear, traj);
-        replay_one_image_frame(c, mode, checked);
+        replay_one_image_frame(c, mode, checked, search);
         set_null_canonical(c);
         c->async_pending = true; im.pending = true; c->phase = 0; c->frame_updated = false; clear = 0;
         first += 1; count -= 1;
@@ -1432,16 +1480,17 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
     launch_set_run(c->stream, c->fs, first, clear, traj);
     if (c->use_graph && !c->profiling) {
         // (image frames only: never a captured frame without the association; plain and checked frames each have their own)
-        ReplayGraphs& g = (checked ? im.chk_graphs : im.graphs)[mode == SRUKF_UPDATE_JOINT ? 1 : 0];
+        // (searching frames: their own again, per kind of image run)
+        ReplayGraphs& g = (search ? im.ar_graphs[checked ? 1 : 0] : checked ? im.chk_graphs : im.graphs)[mode == SRUKF_UPDATE_JOINT ? 1 : 0];
         if (!g.one_exec) {
-            int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true, checked); if (rc) return rc;
-            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true, checked); if (rc) return rc;
+            int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true, checked, search); if (rc) return rc;
+            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true, checked, search); if (rc) return rc;
         }
         int f = 0;
         for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(g.eight_exec, c->stream));
         for (; f < count; f++) HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
     } else {
-        for (int f = 0; f < count; f++) replay_one_image_frame(c, mode, checked);
+        for (int f = 0; f < count; f++) replay_one_image_frame(c, mode, checked, search);
     }
     c->async_pending = true; im.pending = true;
     c->phase = 0; c->frame_updated = false;
@@ -1506,6 +1555,34 @@ int srukf_get_image_checks(srukf_ctx* c, int first, int count, double* corr2, do
     if (corr2) HIPCHK(c, hipMemcpy(corr2, im.corr2_seq + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
     if (z2) HIPCHK(c, hipMemcpy(z2, im.z2_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
     if (flags) HIPCHK(c, hipMemcpy(flags, im.flags_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    return SRUKF_OK;
+}
+
+// rows [first, first + count) of the record the searching image runs wrote (srukf_images_search_archive), after waiting for the stream like srukf_get_image_matches.
+// Rows no searching run has written are zero.  No record (no searching run since the images were staged or the archive was set; a flagged block restored since the
+// last one): SRUKF_ERR_SEQUENCE, the rule of srukf_get_match_scores
+int srukf_get_image_archive(srukf_ctx* c, int first, int count, int* L, double* h, double* Si, int* visible, double* z, int* matched, double* corr, int* hits)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_archive: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.ar_valid) { c->err = "get_image_archive: no record of a searching image run (srukf_images_search_archive; a flagged block leaves none)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_archive: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    const size_t n = im.ar_rec ? (size_t)im.ar_L : 0, a = (size_t)first, m = (size_t)count;
+    if (L) *L = (int)n;
+    if (hits) memset(hits, 0, sizeof(int) * m);
+    if (n == 0) return SRUKF_OK;                               // (an empty archive: the runs were plain ones)
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const ImageArchiveRecord r = image_archive_record((size_t)im.frames, n);
+    const double* rec = im.ar_rec; const int* reci = (const int*)(rec + r.ints);
+    if (h) HIPCHK(c, hipMemcpy(h, rec + r.h + a * 2 * n, sizeof(double) * m * 2 * n, hipMemcpyDeviceToHost));
+    if (Si) HIPCHK(c, hipMemcpy(Si, rec + r.Si + a * 4 * n, sizeof(double) * m * 4 * n, hipMemcpyDeviceToHost));
+    if (z) HIPCHK(c, hipMemcpy(z, rec + r.z + a * 2 * n, sizeof(double) * m * 2 * n, hipMemcpyDeviceToHost));
+    if (corr) HIPCHK(c, hipMemcpy(corr, rec + r.corr + a * n, sizeof(double) * m * n, hipMemcpyDeviceToHost));
+    if (visible) HIPCHK(c, hipMemcpy(visible, reci + r.vis_i + a * n, sizeof(int) * m * n, hipMemcpyDeviceToHost));
+    if (matched) HIPCHK(c, hipMemcpy(matched, reci + r.m_i + a * n, sizeof(int) * m * n, hipMemcpyDeviceToHost));
+    if (hits) HIPCHK(c, hipMemcpy(hits, reci + r.hits_i + a, sizeof(int) * m, hipMemcpyDeviceToHost));
     return SRUKF_OK;
 }
 
@@ -1576,16 +1653,17 @@ int srukf_synchronize(srukf_ctx* c)
         c->async_pending = false;
         const bool image_run = c->img.pending;                  // the frames were image frames: a flagged block comes back to its checkpoint here (X, S, matchPatch)
         const bool checked_run = c->img.checked;                // ... with a checked run among them: a flagged block leaves no valid score map
-        c->img.pending = false; c->img.checked = false;
+        const bool search_run = c->img.searching;               // ... with a searching run among them: a flagged block leaves no valid search record
+        c->img.pending = false; c->img.checked = false; c->img.searching = false;
         int rc = read_fs(c); if (rc) return rc;
         // joint frames: the sticky pair k_joint_dx left (first hit).  A clamp flag of an EARLIER frame goes first: from that frame on nothing is valid anyway
         if (c->hfs->joint_bad_frame > 0 && !(c->hfs->clamp_rows > 0 && c->hfs->clamp_frame < c->hfs->joint_bad_frame - 1)) {
             rc = joint_bad_report(c);
-            if (image_run) { images_restore(c); c->joint_bad_host = false; if (checked_run) c->match_valid = false; }
+            if (image_run) { images_restore(c); c->joint_bad_host = false; if (checked_run) c->match_valid = false; if (search_run) c->img.ar_valid = false; }
             return rc;
         }
         if (c->hfs->clamp_rows > 0) {
-            if (image_run) { images_restore(c); if (checked_run) c->match_valid = false; }
+            if (image_run) { images_restore(c); if (checked_run) c->match_valid = false; if (search_run) c->img.ar_valid = false; }
             c->clamp_frame_host = c->hfs->clamp_frame; c->clamp_row_host = c->hfs->clamp_first;
             char b[220]; snprintf(b, sizeof b, "GMW theta clamp active on %d pivot rows (first row %d), first in staged frame %d, during async frames%s", c->hfs->clamp_rows, c->hfs->clamp_first, c->hfs->clamp_frame,
                                  c->hfs->gmw_aborts > 0 ? " (a persistent factorisation launch was abandoned: the GPU is shared; see srukf_set_exclusive)" : "");

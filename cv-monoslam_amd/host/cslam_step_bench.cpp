@@ -18,6 +18,12 @@
 //              unique=<ratio>[,<exclusion>] and / or subpix=1 (assoc_replay only): the blocks are checked image runs (srukf_run_images_checked_async, DESIGN.md §21;
 //              subpix=1 alone: ratio 2, nothing vetoed; exclusion defaults to 4), a restored block runs srukf_associate_checked, and srukf_get_image_checks is read
 //              with the record after every block.  Adds, and only with them, "checked": {ratio, exclusion, subpixel, ambiguous, refined} to the output
+//              archive=<L>[,<half_cap>] (assoc_replay only): L records are archived from the bench's own frame — landmarks created on a context of their own at the
+//              pixels farthest from every landmark's, srukf_capture_appearance + srukf_get_landmark_record — and searched in every frame on the device
+//              (srukf_images_search_archive); hits are read after every block (srukf_get_image_archive).  archive_step=1 with it: the step-wise
+//              route instead — the switch stays off and srukf_archive_search runs on the frame after every block (with block=1: once per frame, what a host had
+//              to do before the switch).  Adds "archive": {records, half_cap, route, matched_records} to the output
+//              profile=1 (assoc_replay only): the timed blocks run with srukf_set_profiling on (eager launches); adds "profile_ms_per_frame" by kernel class
 //     hint=1 : capi / assoc announce the NEXT frame's odometry with srukf_predict_motion_next before every update (a host that has its odometry
 //              file loaded, as the reference has: loadOdometryData reads it whole, SLAM.cpp:363-496)
 //     set=key:value : srukf_debug_set(ctx, key, value) after the context exists (capi / assoc; measurement switches, e.g. set=step_fuse_export:0)
@@ -35,6 +41,7 @@
 //              instead of the host's Jacobi iteration per landmark); the run's figures are then also printed under "facade_ellipsoids_on_device"
 // scene.bin: int32 N, int32 F, double a1..a4, double X0[n], double S0[n*n], double z[F][2N]   (the file cslam_replay reads)
 // Prints ONE JSON object.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -50,11 +57,13 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 int main(int argc, char** argv)
 {
     if (argc < 4) { fprintf(stderr, "usage: %s scene.bin odometry.txt mode=<capi|facade|assoc|replay> [frames=K] [warmup=W] [hint=0|1]\n"
-                                "       (mode=assoc_replay [block=B]: the staged replay with the association on the device)\n", argv[0]); return 2; }
+                                "       (mode=assoc_replay [block=B] [archive=L[,half_cap]] [archive_step=1] [profile=1]: the staged replay with the association on the device)\n", argv[0]); return 2; }
     std::string mode = "capi";
     int K = 200, W = 20, hint = 0, churn = 0, ransac = 0, ellipsoids = 0, joint = 0, block_frames = 8;
     bool checked = false; srukf_match_params mpar = { 0.8, 2.0, 4, 0 };      // unique= / subpix=: checked image runs (assoc_replay)
     long long ambiguous = 0, refined = 0;
+    int arcL = 0, arc_step = 0, profile = 0; srukf_archive_params apar = { 40, 0.8, 5.99146454710798 };      // archive= / archive_step= / profile= (assoc_replay)
+    long long arc_hits = 0;
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -67,6 +76,9 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "block=", 6)) block_frames = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "unique=", 7)) { checked = true; char* e = nullptr; mpar.ratio = strtod(argv[a] + 7, &e); if (e && *e == ',') mpar.exclusion = atoi(e + 1); }
+        else if (!strncmp(argv[a], "archive=", 8)) { char* e = nullptr; arcL = (int)strtol(argv[a] + 8, &e, 10); if (e && *e == ',') apar.half_cap = atoi(e + 1); }
+        else if (!strncmp(argv[a], "archive_step=", 13)) arc_step = atoi(argv[a] + 13);
+        else if (!strncmp(argv[a], "profile=", 8)) profile = atoi(argv[a] + 8);
         else if (!strncmp(argv[a], "subpix=", 7)) { if (atoi(argv[a] + 7)) { checked = true; mpar.subpixel = 1; } }
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } sets.emplace_back(std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))), atoi(q + 1)); }
     }
@@ -97,11 +109,14 @@ int main(int argc, char** argv)
     long long flag_ticks = -1;                                       // last frame: start of the frame's first launch -> h / Si / visible flagged to the host (10 ns ticks)
     char churn_json[900] = "";
     char ell_json[200] = "";
+    char prof_json[1600] = "", arc_json[200] = "";
     int joint_flagged = 0;
     const char* replay_form = "run_frames_async + synchronize";
     int flagged_blocks = 0;
     const bool areplay = mode == "assoc_replay";
     if (checked && !areplay) { fprintf(stderr, "unique= / subpix= belong to mode=assoc_replay\n"); return 2; }
+    if ((arcL || arc_step || profile) && !areplay) { fprintf(stderr, "archive= / archive_step= / profile= belong to mode=assoc_replay\n"); return 2; }
+    if (arcL < 0 || arcL > 64 || (arc_step && !arcL)) { fprintf(stderr, "archive=<L>: 1 <= L <= 64 (archive_step=1 needs it)\n"); return 2; }
     if (areplay && (block_frames < 1 || W < 1)) { fprintf(stderr, "assoc_replay: block >= 1 and warmup >= 1 (frame 0 sets the appearance records up)\n"); return 2; }
     if (mode == "facade") {
         monoslam::CSLAM SLAM;
@@ -277,12 +292,51 @@ int main(int argc, char** argv)
                 for (int fr = 0; fr < W + K; fr++) memcpy(stack.data() + (size_t)fr * img, gray.data(), img);
                 CK(srukf_stage_images(c, W + K, stack.data()));
             }
-            std::vector<int> mrow((size_t)block_frames * N), frow(checked ? (size_t)block_frames * N : 0), fl(checked ? N : 0);
+            if (arcL) {
+                // the archive: arcL landmarks created on a context of their own at the robot's start state, at the grid pixels farthest from every landmark's first
+                // predicted pixel (h still holds frame 0's), their appearance captured from the bench's frame, their records read back
+                std::vector<double> uv;
+                std::vector<std::pair<double, std::pair<int, int>>> cand;
+                for (int y = 40; y <= 440; y += 20) for (int x = 40; x <= 600; x += 20) {
+                    double dmin = 1e30;
+                    for (int k = 0; k < N; k++) { const double d = hypot(h[2 * k] - x, h[2 * k + 1] - y); dmin = d < dmin ? d : dmin; }
+                    cand.push_back({ -dmin, { x, y } });
+                }
+                std::sort(cand.begin(), cand.end());
+                for (auto& cd : cand) {
+                    if ((int)uv.size() == 2 * arcL) break;
+                    bool ok = true;
+                    for (size_t q = 0; q < uv.size(); q += 2) if (hypot(uv[q] - cd.second.first, uv[q + 1] - cd.second.second) < 30.0) ok = false;
+                    if (ok) { uv.push_back(cd.second.first); uv.push_back(cd.second.second); }
+                }
+                if ((int)uv.size() != 2 * arcL) { fprintf(stderr, "archive=: no room for %d records\n", arcL); return 2; }
+                srukf_ctx* c2 = nullptr;
+                rc = srukf_create(&c2, 0, &p, 0, nullptr);
+                if (rc) { fprintf(stderr, "srukf_create (archive): %d %s\n", rc, srukf_last_error(nullptr)); return 1; }
+                const double X4[4] = { X0[n - 4], X0[n - 3], X0[n - 2], X0[n - 1] };
+                double S4[16] = { 0 }; S4[0] = p.sigma_x; S4[5] = p.sigma_y; S4[10] = p.sigma_z; S4[15] = p.sigma_theta;
+                std::vector<double> aX((size_t)6 * arcL), aS((size_t)36 * arcL), aR((size_t)9 * arcL), aT((size_t)3 * arcL), aP((size_t)2 * arcL);
+                std::vector<unsigned char> aPatch((size_t)441 * arcL);
+                rc = srukf_set_state(c2, X4, S4);
+                if (!rc) rc = srukf_add_landmarks(c2, arcL, uv.data());
+                if (!rc) rc = srukf_capture_appearance(c2, 0, arcL, uv.data(), gray.data());
+                for (int k = 0; k < arcL && !rc; k++) {
+                    int has = 0;
+                    rc = srukf_get_landmark_record(c2, k, &aX[6 * k], &aS[36 * k], &aPatch[441 * k], &aR[9 * k], &aT[3 * k], &aP[2 * k], &has);
+                    if (!rc && !has) rc = SRUKF_ERR_SEQUENCE;
+                }
+                if (rc) { fprintf(stderr, "archive records: %d %s\n", rc, srukf_last_error(c2)); return 1; }
+                srukf_destroy(c2);
+                CK(srukf_archive_set(c, arcL, aX.data(), aS.data(), aPatch.data(), aR.data(), aT.data(), aP.data()));
+                if (!arc_step) CK(srukf_images_search_archive(c, 1, &apar));
+            }
+            std::vector<int> mrow((size_t)block_frames * N), frow(checked ? (size_t)block_frames * N : 0), fl(checked ? N : 0), hrow(block_frames), am(arcL);
             auto run = [&](int first, int end, bool timed) -> int {
                 for (int b = first; b < end; b += block_frames) {
                     const int cnt = end - b < block_frames ? end - b : block_frames;
                     rc = checked ? srukf_run_images_checked_async(c, b, cnt, upd, &mpar, nullptr) : srukf_run_images_async(c, b, cnt, upd, nullptr);
                     if (rc == SRUKF_OK) rc = srukf_synchronize(c);
+                    const bool clean = rc == SRUKF_OK;
                     if (rc == SRUKF_ERR_CLAMP_PENDING) {
                         // the block came back restored (X, S, matchPatch): its frames step by step, the device's association driving the filter as in the block
                         if (timed) flagged_blocks++;
@@ -297,6 +351,10 @@ int main(int argc, char** argv)
                             if (timed) for (int k = 0; k < N; k++) matches_dev += md[k];
                             if (joint) CK(srukf_update_joint(c, zc.data(), md.data(), SRUKF_NEEDNOT_REORDER));
                             else CK(srukf_update(c, zc.data(), md.data(), SRUKF_NEEDNOT_REORDER, SRUKF_UPDATE_BATCHED));
+                            if (arcL) {                          // (a restored block leaves no search record either: the step-wise search, per frame)
+                                CK(srukf_archive_search(c, gray.data(), &apar, nullptr, nullptr, nullptr, nullptr, am.data(), nullptr));
+                                if (timed) for (int q = 0; q < arcL; q++) arc_hits += am[q];
+                            }
                         }
                     } else if (rc) { fprintf(stderr, "image block [%d, %d): %d %s\n", b, b + cnt, rc, srukf_last_error(c)); return 1; }
                     else if (timed) {
@@ -307,14 +365,33 @@ int main(int argc, char** argv)
                             CK(srukf_get_image_checks(c, b, cnt, nullptr, nullptr, frow.data()));
                             for (int q = 0; q < cnt * N; q++) { ambiguous += (frow[q] >> 1) & 1; refined += (frow[q] >> 2) & 1; }
                         }
+                        if (arcL && !arc_step) {                 // "did anything come back?": cnt ints
+                            CK(srukf_get_image_archive(c, b, cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hrow.data()));
+                            for (int q = 0; q < cnt; q++) arc_hits += hrow[q];
+                        }
+                    }
+                    if (clean && arcL && arc_step) {    // the step-wise route: one search on the posterior of the block's last frame
+                        CK(srukf_archive_search(c, gray.data(), &apar, nullptr, nullptr, nullptr, nullptr, am.data(), nullptr));
+                        if (timed) for (int q = 0; q < arcL; q++) arc_hits += am[q];
                     }
                 }
                 return 0;
             };
             if (run(f0, W, false)) return 1;
+            if (profile) { CK(srukf_set_profiling(c, 1)); CK(srukf_profile_reset(c)); }
             t0 = now_s();
             if (run(W, W + K, true)) return 1;
             CK(srukf_get_robot(c, pose, P4));
+            if (profile) {
+                size_t o = (size_t)snprintf(prof_json, sizeof prof_json, "\"profile_ms_per_frame\": {");
+                bool first_class = true;
+                for (int i = 0; i < srukf_profile_count(c); i++) {
+                    const char* name = nullptr; double ms = 0, fl_ = 0, by_ = 0; long long ln = 0;
+                    CK(srukf_profile_get(c, i, &name, &ms, &ln, &fl_, &by_));
+                    if (ln > 0 && o < sizeof prof_json - 80) { o += (size_t)snprintf(prof_json + o, sizeof prof_json - o, "%s\"%s\": %.5f", first_class ? "" : ", ", name, ms / K); first_class = false; }
+                }
+                snprintf(prof_json + o, sizeof prof_json - o, "}, ");
+            }
         } else
         for (int fr = f0; fr < W + K; fr++) {
             if (fr == W) t0 = now_s();
@@ -343,11 +420,13 @@ int main(int argc, char** argv)
     if (areplay) snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"block_frames\": %d, \"flagged_blocks\": %d, ", block_frames, flagged_blocks);
     if (checked) snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"checked\": {\"ratio\": %.6g, \"exclusion\": %d, \"subpixel\": %d, \"ambiguous\": %lld, \"refined\": %lld}, ",
                           mpar.ratio, mpar.exclusion, mpar.subpixel, ambiguous, refined);
+    if (arcL) snprintf(arc_json, sizeof arc_json, "\"archive\": {\"records\": %d, \"half_cap\": %d, \"route\": \"%s\", \"matched_records\": %lld}, ", arcL, apar.half_cap,
+                       arc_step ? "srukf_archive_search after every block" : "srukf_images_search_archive", arc_hits);
     if (mode == "replay") snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"replay_form\": \"%s\", \"exact_frames\": %d, ", replay_form, joint_flagged);
-    printf("{\"mode\": \"%s\", %s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
+    printf("{\"mode\": \"%s\", %s%s%s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
            "\"pose\": [%.17g, %.17g, %.17g, %.17g], \"P_robot\": [%.17g, %.17g, %.17g, %.17g], \"device_matches\": %lld, \"stats_flag_us_into_first_launch\": %.2f, \"host_us_per_call\": {\"predict_motion\": %.2f, \"predict_measurement\": %.2f, \"association\": %.2f, \"update\": %.2f, \"get_robot\": %.2f}, "
            "\"filter_driven_by\": \"%s\"}\n",
-           mode.c_str(), churn_json, ell_json, joint_json, hint, N, K, W, K / t_timed, t_timed / K * 1e6, pose[0], pose[1], pose[2], pose[3], P4[0], P4[1], P4[4], P4[5], matches_dev, flag_ticks * 0.01,
+           mode.c_str(), churn_json, ell_json, joint_json, arc_json, prof_json, hint, N, K, W, K / t_timed, t_timed / K * 1e6, pose[0], pose[1], pose[2], pose[3], P4[0], P4[1], P4[4], P4[5], matches_dev, flag_ticks * 0.01,
            tcall[0] / K * 1e6, tcall[1] / K * 1e6, tcall[2] / K * 1e6, tcall[3] / K * 1e6, tcall[4] / K * 1e6,
            areplay ? "device association" : "scene z / matched (host association)");
     fflush(stdout);                                                // (the line must not depend on what the runtimes' exit handlers do)

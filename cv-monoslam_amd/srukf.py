@@ -33,6 +33,7 @@ EXPORTS = [
     "srukf_associate_checked", "srukf_get_match_scores",
     "srukf_stage_images", "srukf_run_images_async", "srukf_run_images", "srukf_get_image_matches",
     "srukf_run_images_checked_async", "srukf_run_images_checked", "srukf_get_image_checks",
+    "srukf_images_search_archive", "srukf_get_image_archive",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -170,6 +171,9 @@ def load_library(path=None):
         L.srukf_run_images_checked_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MatchParams), C.c_void_p]
         L.srukf_run_images_checked.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MatchParams), _dp]
         L.srukf_get_image_checks.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _ip]
+    if hasattr(L, "srukf_images_search_archive"):
+        L.srukf_images_search_archive.argtypes = [C.c_void_p, C.c_int, C.POINTER(ArchiveParams)]
+        L.srukf_get_image_archive.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _dp, _dp, _ip, _dp, _ip, _dp, _ip]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -666,6 +670,43 @@ class Filter:
         N = self.N
         out = dict(corr2=np.zeros((count, N)), z2=np.zeros((count, 2 * N)), flags=np.zeros((count, N), dtype=np.int32))
         self._chk(self._lib.srukf_get_image_checks(self._h, int(first), int(count), _d(out["corr2"]), _d(out["z2"]), _i(out["flags"])))
+        return out
+
+    @staticmethod
+    def _archive_params(half_cap, corr_threshold, chi2):
+        """archive_search's parameters as the library's struct; types are checked here, values (half_cap in [10, 40], chi2 > 0, finite) by the library"""
+        if isinstance(half_cap, bool) or not isinstance(half_cap, (int, np.integer)):
+            raise TypeError("images_search_archive: half_cap must be an integer")
+        for name, v in (("corr_threshold", corr_threshold), ("chi2", chi2)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError(f"images_search_archive: {name} must be a real number")
+        if not -2 ** 31 <= int(half_cap) < 2 ** 31:
+            raise ValueError("images_search_archive: half_cap does not fit an int")
+        return ArchiveParams(int(half_cap), float(corr_threshold), float(chi2))
+
+    def images_search_archive(self, on, half_cap=40, corr_threshold=0.8, chi2=5.99146454710798):
+        """The switch of the searching image runs (srukf_images_search_archive): while on, every frame of every later run_images* / run_images_checked* is followed
+        by one archive_search of the whole archive on that frame's staged image, on the posterior; get_image_archive has the per-frame record.  Not while an image
+        run is in flight (SRUKF_ERR_SEQUENCE)."""
+        if not isinstance(on, (bool, np.bool_)) and not (isinstance(on, (int, np.integer)) and on in (0, 1)):
+            raise TypeError("images_search_archive: on must be a bool")
+        ap = self._archive_params(half_cap, corr_threshold, chi2)
+        self._chk(self._lib.srukf_images_search_archive(self._h, int(bool(on)), C.byref(ap)))
+
+    def get_image_archive(self, first, count):
+        """What the searching image runs wrote for staged frames [first, first + count) (srukf_get_image_archive): dict of L (the archive size of the rows),
+        h[count, 2L], Si[count, L, 2, 2], visible[count, L], z[count, 2L], matched[count, L], corr[count, L], hits[count].  Rows no searching run wrote are zero."""
+        self._image_run_args(first, count, UPDATE_BATCHED)
+        L, hits = C.c_int(0), np.zeros(count, dtype=np.int32)
+        self._chk(self._lib.srukf_get_image_archive(self._h, int(first), int(count), C.byref(L), None, None, None, None, None, None, _i(hits)))
+        L = int(L.value)
+        out = dict(L=L, h=np.zeros((count, 2 * L)), Si=np.zeros((count, L, 2, 2)), visible=np.zeros((count, L), dtype=np.int32), z=np.zeros((count, 2 * L)),
+                   matched=np.zeros((count, L), dtype=np.int32), corr=np.zeros((count, L)), hits=hits)
+        if L > 0:
+            L2 = C.c_int(0)
+            self._chk(self._lib.srukf_get_image_archive(self._h, int(first), int(count), C.byref(L2), _d(out["h"]), _d(out["Si"]), _i(out["visible"]), _d(out["z"]),
+                                                        _i(out["matched"]), _d(out["corr"]), _i(out["hits"])))
+            assert L2.value == L
         return out
 
     def synchronize(self):

@@ -528,6 +528,32 @@ int  srukf_run_images_checked_async(srukf_ctx* ctx, int first, int count, int mo
 int  srukf_run_images_checked(srukf_ctx* ctx, int first, int count, int mode, const srukf_match_params* params, double* traj_host);
 int  srukf_get_image_checks(srukf_ctx* ctx, int first, int count, double* corr2, double* z2, int* flags);
 
+/* ---- searching image runs: the archive searched by appearance behind every frame of an image run ----
+ * srukf_images_search_archive: a switch on the handle, like the archive itself: it survives map changes, srukf_reset and srukf_destroy clear it.  params == NULL:
+ *   { 40, 0.8, 5.99146454710798 }; the checks are srukf_archive_search's, with its messages (SRUKF_ERR_BAD_ARG: half_cap outside [10, 40], chi2 not a finite number
+ *   > 0, corr_threshold not finite); a refused call changes nothing.  Valid in any phase, but not while an image run is in flight (SRUKF_ERR_SEQUENCE:
+ *   srukf_synchronize first).  The call touches no device.
+ *   While on, every frame of every later image run — srukf_run_images* and srukf_run_images_checked*, BATCHED and JOINT — is followed by one srukf_archive_search of
+ *   the whole archive on that frame's own staged image, behind the frame's refactorisation: it sees the POSTERIOR pose and robot block, exactly what
+ *   srukf_archive_search(ctx, frame_f, ..) returns between frame f's srukf_update and frame f + 1's srukf_predict_motion, bit for bit (P4 by the launch
+ *   srukf_get_robot makes; stages (a), (b), (c) above, letter for letter: the two search kernels share one text).  The search writes nothing the filter reads:
+ *   trajectory, X, S, the association's record and every matchPatch are bit for bit those of the run without it.  The parameters live in a small device struct
+ *   written in stream order in front of each run; searching frames are captured frames of their own per kind of image run and update mode (a searching run never
+ *   replays a frame captured without the search, nor the other way round), and searching and non-searching runs may alternate inside one block.  Checkpoint and
+ *   restore are srukf_run_images_async's: the search owns every buffer it writes.  With the switch off an image run is exactly what it was.
+ *   srukf_archive_set drops the record and the captured searching frames (both depend on L); the switch stays on and the next image run builds both for the new
+ *   L.  With L = 0 a searching run is a plain one.  srukf_archive_get_template after a clean srukf_synchronize answers for the LAST frame the last searching run
+ *   executed (templates are not kept per frame).
+ * srukf_get_image_archive: rows [first, first + count) of the per-frame record, after waiting for the stream like srukf_get_image_matches.  *L: the archive size
+ *   the rows were written with; h[count][2L], Si[count][4L], visible[count][L], z[count][2L], matched[count][L], corr[count][L] as srukf_archive_search returns them
+ *   per frame; hits[count]: the number of matched records of the frame.  Any pointer may be NULL.  Rows no searching run has written are zero.  With an empty
+ *   archive *L = 0 and hits are zero.  SRUKF_ERR_SEQUENCE: no images staged, no record (no searching run since the images were staged or the archive was set), or a
+ *   block that srukf_synchronize found flagged and restored, until the next searching run (the rule of srukf_get_match_scores).  SRUKF_ERR_DIM_MISMATCH: rows
+ *   outside the staged stack.
+ * Both: SRUKF_ERR_BAD_ARG for a NULL handle (srukf_get_image_archive: first < 0, count < 1) before any device is touched. */
+int  srukf_images_search_archive(srukf_ctx* ctx, int on, const srukf_archive_params* params);
+int  srukf_get_image_archive(srukf_ctx* ctx, int first, int count, int* L, double* h, double* Si, int* visible, double* z, int* matched, double* corr, int* hits);
+
 /* ---- instrumentation ------------------------------------------------------------------------ */
 
 /* When on, every kernel launch is bracketed by HIP events on the context's stream and the
