@@ -518,6 +518,7 @@ int srukf_reset(srukf_ctx* c)
     c->frame_valid = false; c->bgr_valid = false;                // (the held frame goes with the state, gray and colour)
     archive_free(c->archive, c->stream);                         // (and the archive: srukf_archive_set)
     c->img_search = false; c->img_search_args = ArchiveArgs{ 40, 0.8, 5.99146454710798 };     // (and the switch that searches it behind image frames: srukf_images_search_archive)
+    c->img_policy = false; c->img_policy_args = SRUKF_POLICY_DEFAULTS;      // (and the switch of the map policy's verdict behind image frames: srukf_images_policy)
     match_drop(c);                                               // (and the score maps of srukf_associate_checked)
     images_drop(c, c->stream);                                   // (and the staged images of srukf_stage_images)
     if (c->red_r) { c->red_r = 0; drop_graphs(c); }            // the state is the robot block only: nothing to reduce until a state arrives

@@ -10,6 +10,7 @@
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search), step-wise and behind the frames of an image run
 //                     (srukf_images_search_archive: seq_archive_search, k_archive_search_staged; srukf_get_image_archive: srukf_replay.hip)
+//   srukf_policy.hip  the map policy's verdict (srukf_map_policy; srukf_images_policy: k_map_policy_staged behind the frames of an image run, issued by srukf_replay.hip)
 //   srukf_joint.hip   the joint measurement update's kernels (srukf_update_joint, SRUKF_UPDATE_JOINT frames of the staged replay; host code: srukf_step.hip, srukf_replay.hip)
 //   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip; srukf_run_images_checked*: srukf_replay.hip)
 //   srukf_patch.h     (through srukf_launch.h) the appearance record's sizes, the checked association's buffer layouts, the search kernels' shared front
@@ -111,6 +112,14 @@ struct ImageReplay {
     double* ar_rec = nullptr; ArchiveArgs* ar_args = nullptr; int ar_L = 0;
     bool ar_valid = false, searching = false;
     ReplayGraphs ar_graphs[2][2];
+    // The map policy behind image frames (srukf_images_policy), allocated by images_policy_ensure (the first policy run, or
+    // srukf_images_set_policy_state): the per-landmark state (pol_state [N]) and its copy in the block's checkpoint (pol_ck [N]: saved and restored with X, S and the
+    // matchPatch array), the record (pol_verdict [frames][N], pol_sum [frames], zero until a policy run writes a row) and the parameters the launches read (pol_args,
+    // written in stream order in front of every policy run).  pol_valid: a policy run has written the record.  No captured frames of their own: run_images_issue.
+    // ck_clean: the checkpoint is that of a block srukf_synchronize ended clean and nothing has written X, S or a matchPatch since (srukf_images_rewind; cleared by
+    // images_rewind_void, which every state-writing entry passes through step_invalidate)
+    srukf_policy_state *pol_state = nullptr, *pol_ck = nullptr; int* pol_verdict = nullptr; srukf_policy_summary* pol_sum = nullptr; srukf_policy_params* pol_args = nullptr;
+    bool pol_valid = false, ck_clean = false;
 };
 
 // ---- the context: who owns what across a map change ("who owns what across a map change") ----------------------
@@ -152,6 +161,8 @@ struct srukf_handle_scope : srukf_switches {
     ArchiveState archive;                  // srukf_archive_set / srukf_archive_search
     bool img_search = false;               // srukf_images_search_archive: every frame of every later image run is followed by a search of the archive, with ...
     ArchiveArgs img_search_args = { 40, 0.8, 5.99146454710798 };   // ... these parameters.  Survives map changes; srukf_reset clears it
+    bool img_policy = false;               // srukf_images_policy: every frame of every later image run is followed by the map policy's verdict, with ...
+    srukf_policy_params img_policy_args = SRUKF_POLICY_DEFAULTS;   // ... these parameters.  Survives map changes; srukf_reset clears it
     std::string err;
     // the pool allocations among the members above (det and archive: det_scratch_free / archive_free).  A new buffer of this scope is added HERE
     template <class F> void each_device_buffer(F f) const { void* b[] = { d_image, d_bgr, d_ovl }; for (void* q : b) f(q); }
@@ -323,7 +334,8 @@ struct srukf_map_scope : srukf_life {
                       red_head0_tiles, split_fold_list, red_syrk_tiles, ckS, ckX, syrk_tiles, pxy_tiles, syrk_head_tiles, syrk_head_tiles_b, fs,
                       odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt, jointZd, jointW, jointRd,
                       img.images, img.ck_tmpl, img.corr_seq, img.h_seq, img.xyz, img.ckS, img.ckX, img.vis_seq,
-                      img.corr2_seq, img.z2_seq, img.flags_seq, img.match_args, img.ar_rec, img.ar_args };
+                      img.corr2_seq, img.z2_seq, img.flags_seq, img.match_args, img.ar_rec, img.ar_args,
+                      img.pol_state, img.pol_ck, img.pol_verdict, img.pol_sum, img.pol_args };
         for (void* q : b) f(q);
     }
 };
@@ -394,6 +406,9 @@ int ensure_appearance(srukf_ctx* c);      // the per-landmark appearance records
 // ---- archive search (srukf_archive.hip) ----
 void archive_free(ArchiveState& a, hipStream_t st);
 void seq_archive_search(srukf_ctx* c);                 // the search behind a frame of a searching image run (behind seq_refactor)
+
+// ---- the map policy's verdict (srukf_policy.hip) ----
+int policy_params(srukf_ctx* c, const srukf_policy_params* pp, srukf_policy_params* out, const char* who);      // srukf_policy_params' rules (pp null: the defaults)
 
 // ---- display ellipsoids (srukf_display.hip) ----
 void launch_lm_ellipsoid(hipStream_t st, int N, double eps, const double* cov, double* axis, double* sigma, int* rot);

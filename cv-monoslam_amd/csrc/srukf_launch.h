@@ -221,3 +221,17 @@ void launch_joint_dx(hipStream_t st, KDims d, double* W, const double* Rd, const
 // arrays as k_archive_predict and k_warp_patch left them.  launch_set_archive_args: *dst = v on the stream
 void launch_archive_search_staged(hipStream_t st, int L, srukf_params p, StagedArchive a, const double* h, const double* Si, const int* vis, const unsigned char* tmpl);
 void launch_set_archive_args(hipStream_t st, ArchiveArgs* dst, ArchiveArgs v);
+
+// ---- srukf_policy.hip (the map policy's verdict; C++ linkage) ----
+// k_map_policy: one workgroup of 256 threads; X: the state (landmark k at 6k, the robot block last), h / vis / z / m: one frame's association, state / verdict [N] and
+// *sum: what it writes; prm: the parameters on the device.  k_map_policy_staged: the same body on row `frame` of the association's record (StagedPolicy: the record's
+// arrays, the policy state, the verdict rows [frames][N] and the summary rows [frames]); launch_set_policy_params: *dst = v on the stream
+struct StagedPolicy {
+    const double* X; int frames;
+    const double* h_seq; const int* vis_seq; const double* z_seq; const int* m_seq;
+    srukf_policy_state* st; int* verdict; srukf_policy_summary* sum;
+};
+void launch_map_policy(hipStream_t st, KDims d, srukf_params p, const srukf_policy_params* prm, const double* X, const double* h, const int* vis, const double* z, const int* m,
+                       srukf_policy_state* state, int* verdict, srukf_policy_summary* sum);
+void launch_map_policy_staged(hipStream_t st, KDims d, srukf_params p, const srukf_policy_params* prm, StagedPolicy a, int frame);
+void launch_set_policy_params(hipStream_t st, srukf_policy_params* dst, srukf_policy_params v);

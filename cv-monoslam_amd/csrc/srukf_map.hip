@@ -116,6 +116,7 @@ int srukf_set_landmark_appearance(srukf_ctx* c, int k, const unsigned char* patc
     HIPCHK(c, hipSetDevice(c->device));
     int rc = ensure_appearance(c); if (rc) return rc;
     const int one = 1;
+    c->img.ck_clean = false;                                             // (a matchPatch is written: srukf_images_rewind)
     HIPCHK(c, hipMemcpy(c->app_patch + (size_t)k * PT_PATCH_STRIDE, patch, PT_PATCH_BYTES, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(c->app_tmpl + (size_t)k * PT_TMPL_STRIDE, 0, PT_TMPL_STRIDE));
     HIPCHK(c, hipMemcpy(c->appR + 9 * k, R, sizeof(double) * 9, hipMemcpyHostToDevice));
@@ -139,6 +140,7 @@ int srukf_capture_appearance(srukf_ctx* c, int first, int K, const double* uv, c
     }
     HIPCHK(c, hipSetDevice(c->device));
     step_commit_motion(c);
+    c->img.ck_clean = false;                                             // (matchPatches are written: srukf_images_rewind)
     int rc = ensure_appearance(c); if (rc) return rc;
     rc = take_frame(c, gray); if (rc) return rc;
     double* d_uv = nullptr;
@@ -185,6 +187,7 @@ static int associate_frame(srukf_ctx* c, const unsigned char* gray, double* z, i
     // What does not need the frame goes out first — the warp uses the PREDICTED robot pose (wrapPatch reads m_X_k after predictMotion, SLAM.cpp:1812-1830) — and runs while
     // the host copies the frame into pinned memory: a hipMemcpyAsync from the caller's pageable buffer is staged by the runtime, synchronously, in front of everything.
     step_commit_motion(c);
+    c->img.ck_clean = false;                                             // (the warp writes every matchPatch: srukf_images_rewind)
     double* dxyz = c->G;                                                 // G is free outside the refactorisation
     srukf_launch_landmarks_cartesian(c->stream, c->d, c->X, c->S, dxyz, nullptr);                           // PointsMap::xyz (2574): the points only, no covariances
     srukf_launch_warp_patch(c->stream, c->d, c->p, c->X, dxyz, c->h, c->appR, c->appT, c->appPx, c->app_patch, c->has_app, c->app_tmpl);

@@ -957,7 +957,8 @@ void images_drop(srukf_map_scope* c, hipStream_t st)
     ImageReplay& im = c->img;
     if (im.images) drop_graphs(c);                               // (the captured image frames hold these pointers)
     for (void* b : { (void*)im.images, (void*)im.ck_tmpl, (void*)im.corr_seq, (void*)im.h_seq, (void*)im.xyz, (void*)im.ckS, (void*)im.ckX, (void*)im.vis_seq,
-                      (void*)im.corr2_seq, (void*)im.z2_seq, (void*)im.flags_seq, (void*)im.match_args, (void*)im.ar_rec, (void*)im.ar_args }) if (b) srukf_dfree_on(b, st);
+                      (void*)im.corr2_seq, (void*)im.z2_seq, (void*)im.flags_seq, (void*)im.match_args, (void*)im.ar_rec, (void*)im.ar_args,
+                      (void*)im.pol_state, (void*)im.pol_ck, (void*)im.pol_verdict, (void*)im.pol_sum, (void*)im.pol_args }) if (b) srukf_dfree_on(b, st);
     im = ImageReplay{};
 }
 
@@ -1366,6 +1367,11 @@ static void images_restore(srukf_ctx* c)
     hipMemcpyAsync(c->S, im.ckS, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream);
     hipMemcpyAsync(c->X, im.ckX, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream);
     hipMemcpyAsync(c->app_tmpl, im.ck_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream);
+    if (im.pol_state) {                                        // the policy state comes back too; the rows the block's frames wrote are no verdicts any more: zero, as unwritten rows are
+        hipMemcpyAsync(im.pol_state, im.pol_ck, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyDeviceToDevice, c->stream);
+        hipMemsetAsync(im.pol_verdict, 0, sizeof(int) * (size_t)im.frames * (size_t)c->d.N, c->stream);
+        hipMemsetAsync(im.pol_sum, 0, sizeof(srukf_policy_summary) * (size_t)im.frames, c->stream);
+    }
     if (c->null_canonical != im.ck_canon) { c->null_canonical = im.ck_canon; drop_graphs(c); }
     shadow_rebuild(c);
     hipStreamSynchronize(c->stream);
@@ -1422,6 +1428,40 @@ static int images_archive_ensure(srukf_ctx* c, const char* who)
     return SRUKF_OK;
 }
 
+// what the map policy behind image frames needs beyond srukf_stage_images' buffers, allocated in front of the first policy run or by
+// srukf_images_set_policy_state, outside any capture: the per-landmark state and its checkpoint copy, the record and the parameters' place on the device, all zeroed
+static int images_policy_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    if (im.pol_state) return SRUKF_OK;
+    const size_t N = c->d.N, f = (size_t)im.frames;
+    hipError_t e = srukf_dmalloc(&im.pol_state, sizeof(srukf_policy_state) * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.pol_ck, sizeof(srukf_policy_state) * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.pol_verdict, sizeof(int) * f * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.pol_sum, sizeof(srukf_policy_summary) * f);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.pol_args, sizeof(srukf_policy_params));
+    if (e == hipSuccess) e = hipMemsetAsync(im.pol_state, 0, sizeof(srukf_policy_state) * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.pol_ck, 0, sizeof(srukf_policy_state) * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.pol_verdict, 0, sizeof(int) * f * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.pol_sum, 0, sizeof(srukf_policy_summary) * f, c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* b : { (void*)im.pol_state, (void*)im.pol_ck, (void*)im.pol_verdict, (void*)im.pol_sum, (void*)im.pol_args }) if (b) srukf_dfree_on(b, c->stream);
+        im.pol_state = im.pol_ck = nullptr; im.pol_verdict = nullptr; im.pol_sum = nullptr; im.pol_args = nullptr;
+        c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
+    }
+    return SRUKF_OK;
+}
+
+// the map policy's verdict behind staged frame `frame` (srukf_images_policy): an eager launch with the frame index as a kernel argument — fs->frame has advanced
+// behind the tail, and a captured frame could not carry the index.  It reads the posterior X and row `frame` of the association's record
+static void issue_image_policy(srukf_ctx* c, int frame)
+{
+    const ImageReplay& im = c->img;
+    ProfScope ps(c, KC_MISC, 0, 80.0 * c->d.N);
+    launch_map_policy_staged(c->stream, c->d, c->p, im.pol_args, StagedPolicy{ c->X, im.frames, im.h_seq, im.vis_seq, c->z_seq, c->m_seq, im.pol_state, im.pol_verdict, im.pol_sum }, frame);
+}
+
 // srukf_run_images_async (chk null) and srukf_run_images_checked_async (chk: the validated parameters): one body, the frames differ in the association launch
 static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double* d_traj, const MatchArgs* chk, const char* who)
 {
@@ -1452,6 +1492,14 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         }
         im.ar_valid = true;
     }
+    // the map policy's verdict behind every frame (srukf_images_policy): no captured frames of its own — the run is issued frame by frame, the one-frame graph
+    // followed by the policy launch
+    const bool policy = c->img_policy;
+    if (policy) {
+        const int rcp = images_policy_ensure(c, who); if (rcp) return rcp;                            // (idem)
+        launch_set_policy_params(c->stream, im.pol_args, c->img_policy_args);      // in stream order, as the checked run's parameters
+        im.pol_valid = true;
+    }
     step_commit_motion(c); step_state_replaced(c);
     if (c->fs_seq_step) {                                      // the step-wise fast path pointed the frame scalars at its own three poses
         hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, c->stream, c->fs, c->odo_seq, c->seqF, c->p.a1, c->p.a2, c->p.a3, c->p.a4);
@@ -1463,6 +1511,7 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         HIPCHK(c, hipMemcpyAsync(im.ckS, c->S, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(im.ckX, c->X, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(im.ck_tmpl, c->app_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream));
+        if (im.pol_state) HIPCHK(c, hipMemcpyAsync(im.pol_ck, im.pol_state, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyDeviceToDevice, c->stream));
         im.ck_canon = c->null_canonical;
     }
     double* traj = d_traj ? d_traj - (size_t)8 * first : nullptr;
@@ -1471,6 +1520,7 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         // null rows that are not (yet) sqrt(EPSILON) e_k: the run's first frame eagerly, as in srukf_run_frames_async (the plain form reads the rows as they are)
         launch_set_run(c->stream, c->fs, first, clear, traj);
         replay_one_image_frame(c, mode, checked, search);
+        if (policy) issue_image_policy(c, first);
         set_null_canonical(c);
         c->async_pending = true; im.pending = true; c->phase = 0; c->frame_updated = false; clear = 0;
         first += 1; count -= 1;
@@ -1482,15 +1532,14 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         // (image frames only: never a captured frame without the association; plain and checked frames each have their own)
         // (searching frames: their own again, per kind of image run)
         ReplayGraphs& g = (search ? im.ar_graphs[checked ? 1 : 0] : checked ? im.chk_graphs : im.graphs)[mode == SRUKF_UPDATE_JOINT ? 1 : 0];
-        if (!g.one_exec) {
-            int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true, checked, search); if (rc) return rc;
-            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true, checked, search); if (rc) return rc;
-        }
+        if (!g.one_exec) { const int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true, checked, search); if (rc) return rc; }
+        if (!policy && !g.eight_exec) { const int rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true, checked, search); if (rc) return rc; }      // (a policy run launches single frames only)
         int f = 0;
+        if (policy) for (; f < count; f++) { HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream)); issue_image_policy(c, first + f); }
         for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(g.eight_exec, c->stream));
         for (; f < count; f++) HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
     } else {
-        for (int f = 0; f < count; f++) replay_one_image_frame(c, mode, checked, search);
+        for (int f = 0; f < count; f++) { replay_one_image_frame(c, mode, checked, search); if (policy) issue_image_policy(c, first + f); }
     }
     c->async_pending = true; im.pending = true;
     c->phase = 0; c->frame_updated = false;
@@ -1586,6 +1635,63 @@ int srukf_get_image_archive(srukf_ctx* c, int first, int count, int* L, double* 
     return SRUKF_OK;
 }
 
+// ---- the map policy's verdict behind image frames (the kernel and the switch: srukf_policy.hip) ----
+// the counters map[] holds (cslam.cpp:713-723) become the device state the next policy run advances
+int srukf_images_set_policy_state(srukf_ctx* c, const srukf_policy_state* state)
+{
+    if (!c || !state) return SRUKF_ERR_BAD_ARG;
+    ImageReplay& im = c->img;
+    if (!im.images) { c->err = "images_set_policy_state: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (c->async_pending) { c->err = "images_set_policy_state: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = images_policy_ensure(c, "images_set_policy_state"); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(im.pol_state, state, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                 // (pageable host memory)
+    im.ck_clean = false;                                        // the checkpoint's copy of the state is not this one: no srukf_images_rewind behind a seed
+    return SRUKF_OK;
+}
+
+// rows [first, first + count) of the policy record (what SLAM.cpp:2443-2459 and 556 would decide behind each frame), after waiting for the stream like
+// srukf_get_image_matches; the device state as it stands; the lowest frame of the range that asks for a map change
+int srukf_get_image_policy(srukf_ctx* c, int first, int count, int* verdict, srukf_policy_summary* summary, srukf_policy_state* state_out, int* first_change)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_policy: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.pol_state || !im.pol_valid) { c->err = "get_image_policy: no record of a policy run (srukf_images_policy)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_policy: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    if (verdict) HIPCHK(c, hipMemcpy(verdict, im.pol_verdict + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (state_out) HIPCHK(c, hipMemcpy(state_out, im.pol_state, sizeof(srukf_policy_state) * N, hipMemcpyDeviceToHost));
+    if (summary || first_change) {
+        std::vector<srukf_policy_summary> sm(m);
+        HIPCHK(c, hipMemcpy(sm.data(), im.pol_sum + a, sizeof(srukf_policy_summary) * m, hipMemcpyDeviceToHost));
+        if (summary) memcpy(summary, sm.data(), sizeof(srukf_policy_summary) * m);
+        if (first_change) { *first_change = -1; for (size_t q = 0; q < m; q++) if (sm[q].change) { *first_change = first + (int)q; break; } }
+    }
+    return SRUKF_OK;
+}
+
+// The checkpoint of the image block the last srukf_synchronize ended clean comes back (X, S, the matchPatch array, the policy state: images_restore), so that a host
+// can stop a block at the frame whose verdict asks for a map change (SLAM.cpp:552-562) by running the frames up to it again.  Only while nothing has written X, S or
+// a matchPatch since that srukf_synchronize (ImageReplay::ck_clean)
+int srukf_images_rewind(srukf_ctx* c)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    ImageReplay& im = c->img;
+    if (c->async_pending) { c->err = "images_rewind: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.images || !im.ck_clean) { c->err = "images_rewind: no image block that srukf_synchronize ended clean, or the state has been written since"; return SRUKF_ERR_SEQUENCE; }
+    HIPCHK(c, hipSetDevice(c->device));
+    step_state_replaced(c);                                     // (clears ck_clean: one rewind per block)
+    c->err.clear();
+    images_restore(c);
+    c->phase = 0; c->frame_updated = false;
+    HIPCHK(c, hipGetLastError());
+    return SRUKF_OK;
+}
+
 // Synchronous form.  No recovery inside the call: a flagged block comes back to its checkpoint (srukf_synchronize) and SRUKF_ERR_CLAMP_PENDING is returned
 int srukf_run_images(srukf_ctx* c, int first, int count, int mode, double* traj_host)
 {
@@ -1670,6 +1776,7 @@ int srukf_synchronize(srukf_ctx* c)
             c->err = b;
             return SRUKF_ERR_CLAMP_PENDING;
         }
+        if (image_run) c->img.ck_clean = true;                   // the block ended clean: its checkpoint is what srukf_images_rewind puts back
     }
     return SRUKF_OK;
 }

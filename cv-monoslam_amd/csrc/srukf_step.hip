@@ -33,7 +33,8 @@ void step_state_replaced(srukf_ctx* c) { step_ck_join(c); c->frame_updated = fal
 //                              that is not) is rewound and repeated on the other path, as srukf_run_frames does; what was submitted ahead is then ignored
 // Same kernels on the same values as the staged replay: bit-identical states (tests/test_gpu_parity_r5.py::test_step_api_equals_staged_replay).
 
-void step_invalidate(srukf_ctx* c) { step_ck_join(c); c->step_chain = false; c->proj_valid = false; c->robot_cached = false; c->view_cached = false; c->ck_valid = false; c->setstep_done = false; c->next_pose_pending = false; c->pre_issued = false; }
+// (and the image block's checkpoint is no longer a state srukf_images_rewind may put back: every entry that writes X or S passes here or through srukf_predict_motion)
+void step_invalidate(srukf_ctx* c) { step_ck_join(c); c->img.ck_clean = false; c->step_chain = false; c->proj_valid = false; c->robot_cached = false; c->view_cached = false; c->ck_valid = false; c->setstep_done = false; c->next_pose_pending = false; c->pre_issued = false; }
 
 static bool step_fast_eligible(const srukf_ctx* c) { return c->dbg.step_fast && !c->last_update_sequential && c->d.N > 0 && frame_form(c).fused_tail(); }
 
@@ -433,6 +434,7 @@ int srukf_predict_motion(srukf_ctx* c, const double odo_prev[3], const double od
     if (!c || !odo_prev || !odo_cur) return SRUKF_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->step_uncommitted) { step_commit_motion(c); step_invalidate(c); }      // a frame that was predicted and never updated: its motion step stands (as on the other path)
+    c->img.ck_clean = false;                                             // (the fast path does not pass step_invalidate: srukf_images_rewind)
     c->step_fast = false; c->robot_cached = false; c->view_cached = false; c->frame_updated = false;
     if (step_fast_eligible(c)) return step_predict_fast(c, odo_prev, odo_cur);
     step_invalidate(c);

@@ -1012,4 +1012,113 @@ void CSLAM::SLAM()
     m_totalTime += m_frameTime;
 }
 
+// Up to F frames of SLAM() as ONE image block on the device: the association (dataAssociationOnDevice's) and the update run inside the block, the
+// map policy's verdict (updateFeaturesInformation's tests 2443-2459, the addFeatures trigger 556) behind every frame; the block stops at the first frame whose
+// verdict asks for a map change, and that change is made by the unchanged host code on that frame.  gray: F frames of image_h x image_w, frame f for
+// m_frame.counter + f.  Returns the frames consumed, or 0 with nothing done where a block cannot stand for SLAM(): the caller then calls SLAM() for the frame.
+int CSLAM::SLAMBlock(const unsigned char* gray, int F)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const int N = m_nMapFeatures, c0 = m_frame.counter;
+    if (!ctx_ || !gray || N < 1 || c0 < 1) return 0;
+    if (c0 + F > m_odoCounter) F = m_odoCounter - c0;
+    if (c0 + F > CAPACITY + 1) F = CAPACITY + 1 - c0;
+    if (F < 1) return 0;
+    if (m_nAddings != 0 || isAdding || isUseRANSAC || searchArchivedLandmarks || reinsertLoopPoints || dataAssociation || addFeatures) return 0;
+    if (!jointUpdate && m_updateMode != SRUKF_UPDATE_BATCHED) return 0;
+    for (int f = 0; f < F; f++) if (m_odoTheta.at(2, c0 + f) == 1) return 0;                                   // a redirection restart inside the range
+    const size_t img = (size_t)m_params.image_w * (size_t)m_params.image_h;
+    // 1. odometry rows [c0 - 1, c0 + F) and the F frames
+    std::vector<double> odo(3 * (size_t)(F + 1)), z0(2 * (size_t)F * N, 0.0);
+    std::vector<int> m0((size_t)F * N, 0);
+    for (int f = 0; f <= F; f++) { const int c = c0 - 1 + f; odo[3 * f] = m_odoXY[2 * c]; odo[3 * f + 1] = m_odoXY[2 * c + 1]; odo[3 * f + 2] = m_odoTheta.at(1, c); }
+    if (!check(srukf_stage_sequence(ctx_, F, odo.data(), z0.data(), m0.data()))) return 0;
+    int rc = srukf_stage_images(ctx_, F, gray);
+    if (rc == SRUKF_ERR_UNSUPPORTED) return 0;
+    if (!check(rc)) return 0;
+    // 2. the counters map[] holds
+    std::vector<srukf_policy_state> st(N);
+    for (int k = 0; k < N; k++) st[k] = { map[k].nPredictTimes, map[k].nMatchTimes, { map[k].predictLocation.x, map[k].predictLocation.y } };
+    const srukf_policy_params pp = { (double)DIST_2_BORDER, 0.01, 10, m_minNUM };
+    if (!check(srukf_images_policy(ctx_, 1, &pp)) || !check(srukf_images_set_policy_state(ctx_, st.data()))) return 0;
+    // 3. one image block in jointUpdate's mode, checked with the switches of associateChecked
+    const int mode = jointUpdate ? SRUKF_UPDATE_JOINT : SRUKF_UPDATE_BATCHED;
+    const bool checked = rejectAmbiguousMatches || subpixelMatches;
+    const srukf_match_params mp = { 0.8, rejectAmbiguousMatches ? AMBIGUITY_RATIO : 2.0, AMBIGUITY_EXCLUSION, subpixelMatches ? 1 : 0 };
+    std::vector<double> traj(8 * (size_t)F);
+    auto run = [&](int count) { return checked ? srukf_run_images_checked(ctx_, 0, count, mode, &mp, traj.data()) : srukf_run_images(ctx_, 0, count, mode, traj.data()); };
+    rc = run(F);
+    if (rc == SRUKF_ERR_CLAMP_PENDING || rc == SRUKF_ERR_UNSUPPORTED) return 0;                                 // a flagged block (its restore has run), the float-stored modes
+    if (!check(rc)) return 0;
+    // 4. / 5. the record; a frame in front of the last asks for a map change: back to the block's start and up to that frame
+    int fc = -1, used = F;
+    if (!check(srukf_get_image_policy(ctx_, 0, F, nullptr, nullptr, nullptr, &fc))) return 0;
+    if (fc >= 0 && fc < F - 1) {
+        used = fc + 1;
+        if (!check(srukf_images_rewind(ctx_))) return 0;
+        rc = run(used);
+        if (rc == SRUKF_ERR_CLAMP_PENDING) return 0;
+        if (!check(rc)) return 0;
+    }
+    // 6. SLAM()'s bookkeeping for every consumed frame, from the records
+    std::vector<double> z(2 * (size_t)used * N), h(2 * (size_t)used * N), corr((size_t)used * N), corr2, z2;
+    std::vector<int> m((size_t)used * N), vis((size_t)used * N), fl;
+    if (!check(srukf_get_image_matches(ctx_, 0, used, z.data(), m.data(), corr.data(), vis.data(), h.data()))) return 0;
+    if (checked) {
+        corr2.resize((size_t)used * N); z2.resize(2 * (size_t)used * N); fl.resize((size_t)used * N);
+        if (!check(srukf_get_image_checks(ctx_, 0, used, corr2.data(), z2.data(), fl.data()))) return 0;
+    }
+    if (!check(srukf_get_image_policy(ctx_, 0, used, nullptr, nullptr, st.data(), nullptr))) return 0;
+    const int n = m_X_k.rows;
+    m_blockPath.assign(traj.begin(), traj.begin() + 8 * (size_t)used);
+    for (int f = 0; f < used; f++) {
+        const bool last = f == used - 1;
+        m_showCounter++;
+        mirrorsFresh_ = false;
+        clearAmbiguity();
+        m_nPredicts = 0; m_nMatches = 0; m_nLowInliers = 0; m_nHighInliers = 0;
+        for (int k = 0; k < N; k++) {
+            const size_t r = (size_t)f * N + k;
+            PointsMap& p = map[k];
+            p.isVisible = vis[r] != 0; p.isMatching = m[r] != 0;
+            p.inliner_L = p.inliner_H = false;
+            if (p.isVisible) m_nPredicts++;
+            if (p.isMatching) { p.matchLocation.x = z[2 * r]; p.matchLocation.y = z[2 * r + 1]; m_nMatches++; }
+            if (checked) {
+                p.isAmbiguous = (fl[r] & 2) != 0; p.corr = corr[r]; p.corr2 = corr2[r]; p.rivalLocation.x = z2[2 * r]; p.rivalLocation.y = z2[2 * r + 1];
+                if (p.isAmbiguous) { m_nAmbiguous++; m_ambiguousID.push_back(p.ID); }
+            }
+            if (last) { p.nPredictTimes = st[k].nPredictTimes; p.nMatchTimes = st[k].nMatchTimes; p.predictLocation.x = st[k].predictLocation[0]; p.predictLocation.y = st[k].predictLocation[1]; }
+        }
+        m_nAmbiguousTotal += m_nAmbiguous;
+        m_frame.index = (int)m_odoTheta.at(0, m_frame.counter);
+        if (!last) {
+            const double* t = &traj[8 * (size_t)f];                                                              // pose + the 2 x 2 block of P, as the trajectory holds them
+            for (int e = 0; e < 4; e++) m_X_k.at(n - 4 + e, 0) = t[e];
+            m_P_k.at(n - 4, n - 4) = t[4]; m_P_k.at(n - 4, n - 3) = t[5]; m_P_k.at(n - 3, n - 4) = t[6]; m_P_k.at(n - 3, n - 3) = t[7];
+            updateRobotInformation();
+            recordRobotInformation();
+            m_nAddings = 0;
+            m_frame.counter++;
+        }
+    }
+    // 7. the last consumed frame: SLAM()'s own tail on that frame (997-1010)
+    m_gryImage = gray + (size_t)(used - 1) * img; frameHeld_ = false;
+    updateFeaturesInformation();
+    refreshMirrors();
+    {
+        const int nl = m_X_k.rows; double* t = &m_blockPath[8 * (size_t)(used - 1)];                           // (the last frame's row as the mirrors have it, behind the deletions)
+        for (int e = 0; e < 4; e++) t[e] = m_X_k.at(nl - 4 + e, 0);
+        t[4] = m_P_k.at(nl - 4, nl - 4); t[5] = m_P_k.at(nl - 4, nl - 3); t[6] = m_P_k.at(nl - 3, nl - 4); t[7] = m_P_k.at(nl - 3, nl - 3);
+    }
+    updateRobotInformation();
+    recordRobotInformation();
+    m_nAddings = 0;
+    if (m_nMatches < m_minNUM && m_gryImage) addFeaturesOnDevice();                                            // 556-561 on the device
+    m_frame.counter++;
+    m_frameTime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / used;
+    m_totalTime += m_frameTime * used;
+    return used;
+}
+
 }  // namespace monoslam

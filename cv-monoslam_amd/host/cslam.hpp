@@ -98,6 +98,17 @@ public:
     void initializeParameters();                               // SLAM.cpp:158-353 (numeric defaults only)
     void resetAllParameters();                                 // SLAM.cpp:3090-3128
     void SLAM();                                               // SLAM.cpp:87-112
+    // Up to F frames of SLAM() as one image block on the device that stops at the first frame whose map-policy verdict asks for a map change:
+    // gray = F frames of image_h x image_w (frame f belongs to m_frame.counter + f).  Stages the odometry rows and the frames, seeds the policy state from map[],
+    // runs srukf_run_images* (jointUpdate's mode; checked with rejectAmbiguousMatches / subpixelMatches), rewinds and reruns up to first_change when that is not
+    // the last frame, then does SLAM()'s bookkeeping for every consumed frame from the records (counters, isMatching, matchLocation, predictLocation, m_nPredicts,
+    // m_nMatches, m_path and the RobotPath row from the trajectory; PointsMap::Si is not refreshed) and SLAM()'s own tail — updateFeaturesInformation,
+    // the mirrors, addFeatures on the device — on the last consumed frame, which m_gryImage then points at.  Returns the frames consumed (m_frame.counter has
+    // advanced by as many).  Returns 0 with nothing done — call SLAM() for the frame instead — with an empty map, a redirection flag inside the range,
+    // m_nAddings != 0 (the next update reorders), isAdding, isUseRANSAC, searchArchivedLandmarks, reinsertLoopPoints, a dataAssociation or addFeatures callback
+    // installed, an update mode the image runs do not have, float storage, and for a flagged block (srukf_synchronize has restored it)
+    int  SLAMBlock(const unsigned char* gray, int F);
+    std::vector<double> m_blockPath;                           // the last SLAMBlock's RobotPath numbers, 8 per consumed frame: x, y, z, theta, P00, P01, P10, P11
     void predictMotion();                                      // SLAM.cpp:1343-1466 (numeric tail 1430-1465)
     void predictMeasurement();                                 // SLAM.cpp:1604-1608
     void KalmanUpdate();                                       // SLAM.cpp:2048-2104

@@ -23,6 +23,9 @@
 //              (srukf_images_search_archive); hits are read after every block (srukf_get_image_archive).  archive_step=1 with it: the step-wise
 //              route instead — the switch stays off and srukf_archive_search runs on the frame after every block (with block=1: once per frame, what a host had
 //              to do before the switch).  Adds "archive": {records, half_cap, route, matched_records} to the output
+//              policy=1 (assoc_replay only): the map policy's verdict behind every frame (srukf_images_policy with the default parameters); the
+//              record's summaries are read after every block (srukf_get_image_policy).  The bench's map never changes: a block is not cut at first_change.  Adds
+//              "policy": {change_frames, deletes, need_add_frames} to the output
 //              profile=1 (assoc_replay only): the timed blocks run with srukf_set_profiling on (eager launches); adds "profile_ms_per_frame" by kernel class
 //     hint=1 : capi / assoc announce the NEXT frame's odometry with srukf_predict_motion_next before every update (a host that has its odometry
 //              file loaded, as the reference has: loadOdometryData reads it whole, SLAM.cpp:363-496)
@@ -57,13 +60,14 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 int main(int argc, char** argv)
 {
     if (argc < 4) { fprintf(stderr, "usage: %s scene.bin odometry.txt mode=<capi|facade|assoc|replay> [frames=K] [warmup=W] [hint=0|1]\n"
-                                "       (mode=assoc_replay [block=B] [archive=L[,half_cap]] [archive_step=1] [profile=1]: the staged replay with the association on the device)\n", argv[0]); return 2; }
+                                "       (mode=assoc_replay [block=B] [archive=L[,half_cap]] [archive_step=1] [policy=1] [profile=1]: the staged replay with the association on the device)\n", argv[0]); return 2; }
     std::string mode = "capi";
     int K = 200, W = 20, hint = 0, churn = 0, ransac = 0, ellipsoids = 0, joint = 0, block_frames = 8;
     bool checked = false; srukf_match_params mpar = { 0.8, 2.0, 4, 0 };      // unique= / subpix=: checked image runs (assoc_replay)
     long long ambiguous = 0, refined = 0;
     int arcL = 0, arc_step = 0, profile = 0; srukf_archive_params apar = { 40, 0.8, 5.99146454710798 };      // archive= / archive_step= / profile= (assoc_replay)
     long long arc_hits = 0;
+    int policy = 0; long long pol_change = 0, pol_deletes = 0, pol_adds = 0;      // policy= (assoc_replay)
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -79,6 +83,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "archive=", 8)) { char* e = nullptr; arcL = (int)strtol(argv[a] + 8, &e, 10); if (e && *e == ',') apar.half_cap = atoi(e + 1); }
         else if (!strncmp(argv[a], "archive_step=", 13)) arc_step = atoi(argv[a] + 13);
         else if (!strncmp(argv[a], "profile=", 8)) profile = atoi(argv[a] + 8);
+        else if (!strncmp(argv[a], "policy=", 7)) policy = atoi(argv[a] + 7);
         else if (!strncmp(argv[a], "subpix=", 7)) { if (atoi(argv[a] + 7)) { checked = true; mpar.subpixel = 1; } }
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } sets.emplace_back(std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))), atoi(q + 1)); }
     }
@@ -109,13 +114,13 @@ int main(int argc, char** argv)
     long long flag_ticks = -1;                                       // last frame: start of the frame's first launch -> h / Si / visible flagged to the host (10 ns ticks)
     char churn_json[900] = "";
     char ell_json[200] = "";
-    char prof_json[1600] = "", arc_json[200] = "";
+    char prof_json[1600] = "", arc_json[200] = "", pol_json[160] = "";
     int joint_flagged = 0;
     const char* replay_form = "run_frames_async + synchronize";
     int flagged_blocks = 0;
     const bool areplay = mode == "assoc_replay";
     if (checked && !areplay) { fprintf(stderr, "unique= / subpix= belong to mode=assoc_replay\n"); return 2; }
-    if ((arcL || arc_step || profile) && !areplay) { fprintf(stderr, "archive= / archive_step= / profile= belong to mode=assoc_replay\n"); return 2; }
+    if ((arcL || arc_step || profile || policy) && !areplay) { fprintf(stderr, "archive= / archive_step= / profile= / policy= belong to mode=assoc_replay\n"); return 2; }
     if (arcL < 0 || arcL > 64 || (arc_step && !arcL)) { fprintf(stderr, "archive=<L>: 1 <= L <= 64 (archive_step=1 needs it)\n"); return 2; }
     if (areplay && (block_frames < 1 || W < 1)) { fprintf(stderr, "assoc_replay: block >= 1 and warmup >= 1 (frame 0 sets the appearance records up)\n"); return 2; }
     if (mode == "facade") {
@@ -330,6 +335,8 @@ int main(int argc, char** argv)
                 CK(srukf_archive_set(c, arcL, aX.data(), aS.data(), aPatch.data(), aR.data(), aT.data(), aP.data()));
                 if (!arc_step) CK(srukf_images_search_archive(c, 1, &apar));
             }
+            if (policy) CK(srukf_images_policy(c, 1, nullptr));
+            std::vector<srukf_policy_summary> prow(block_frames);
             std::vector<int> mrow((size_t)block_frames * N), frow(checked ? (size_t)block_frames * N : 0), fl(checked ? N : 0), hrow(block_frames), am(arcL);
             auto run = [&](int first, int end, bool timed) -> int {
                 for (int b = first; b < end; b += block_frames) {
@@ -364,6 +371,11 @@ int main(int argc, char** argv)
                         if (checked) {
                             CK(srukf_get_image_checks(c, b, cnt, nullptr, nullptr, frow.data()));
                             for (int q = 0; q < cnt * N; q++) { ambiguous += (frow[q] >> 1) & 1; refined += (frow[q] >> 2) & 1; }
+                        }
+                        if (policy) {                            // "does the map have to change?": cnt summaries
+                            int fc = -1;
+                            CK(srukf_get_image_policy(c, b, cnt, nullptr, prow.data(), nullptr, &fc));
+                            for (int q = 0; q < cnt; q++) { pol_change += prow[q].change; pol_deletes += prow[q].n_deletes; pol_adds += prow[q].need_add; }
                         }
                         if (arcL && !arc_step) {                 // "did anything come back?": cnt ints
                             CK(srukf_get_image_archive(c, b, cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hrow.data()));
@@ -422,11 +434,12 @@ int main(int argc, char** argv)
                           mpar.ratio, mpar.exclusion, mpar.subpixel, ambiguous, refined);
     if (arcL) snprintf(arc_json, sizeof arc_json, "\"archive\": {\"records\": %d, \"half_cap\": %d, \"route\": \"%s\", \"matched_records\": %lld}, ", arcL, apar.half_cap,
                        arc_step ? "srukf_archive_search after every block" : "srukf_images_search_archive", arc_hits);
+    if (policy) snprintf(pol_json, sizeof pol_json, "\"policy\": {\"change_frames\": %lld, \"deletes\": %lld, \"need_add_frames\": %lld}, ", pol_change, pol_deletes, pol_adds);
     if (mode == "replay") snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"replay_form\": \"%s\", \"exact_frames\": %d, ", replay_form, joint_flagged);
-    printf("{\"mode\": \"%s\", %s%s%s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
+    printf("{\"mode\": \"%s\", %s%s%s%s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
            "\"pose\": [%.17g, %.17g, %.17g, %.17g], \"P_robot\": [%.17g, %.17g, %.17g, %.17g], \"device_matches\": %lld, \"stats_flag_us_into_first_launch\": %.2f, \"host_us_per_call\": {\"predict_motion\": %.2f, \"predict_measurement\": %.2f, \"association\": %.2f, \"update\": %.2f, \"get_robot\": %.2f}, "
            "\"filter_driven_by\": \"%s\"}\n",
-           mode.c_str(), churn_json, ell_json, joint_json, arc_json, prof_json, hint, N, K, W, K / t_timed, t_timed / K * 1e6, pose[0], pose[1], pose[2], pose[3], P4[0], P4[1], P4[4], P4[5], matches_dev, flag_ticks * 0.01,
+           mode.c_str(), churn_json, ell_json, joint_json, arc_json, pol_json, prof_json, hint, N, K, W, K / t_timed, t_timed / K * 1e6, pose[0], pose[1], pose[2], pose[3], P4[0], P4[1], P4[4], P4[5], matches_dev, flag_ticks * 0.01,
            tcall[0] / K * 1e6, tcall[1] / K * 1e6, tcall[2] / K * 1e6, tcall[3] / K * 1e6, tcall[4] / K * 1e6,
            areplay ? "device association" : "scene z / matched (host association)");
     fflush(stdout);                                                // (the line must not depend on what the runtimes' exit handlers do)

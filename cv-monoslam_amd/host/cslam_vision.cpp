@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -23,6 +23,11 @@
 // unique=<ratio>[,<exclusion>]: CSLAM::rejectAmbiguousMatches on (AMBIGUITY_RATIO = ratio, AMBIGUITY_EXCLUSION = exclusion, default 4).  Adds, and
 //   only with it, an "ambiguous <n> <IDs...>" line per frame: the landmarks this frame's association vetoed.
 // subpix=1: CSLAM::subpixelMatches on.
+// block=<F>: frames run through CSLAM::SLAMBlock, up to F at a time, with SLAM() for every frame a block cannot stand for (the first, a frame
+//   behind an addition, a restart, a flagged block); frames.bin is then not wrapped round: at most its F frames run.  Adds, and only when given (block=1 too: the
+//   step-wise route with the same lines), per frame a "policy" line (frame, the IDs updateFeaturesInformation deleted, landmarks added) and a "path" line (frame, pose and
+//   the 2 x 2 position block of P, %.17g), and at the end "blocks <n> early <n> full <n> fallback <n>".  Without it nothing changes.
+// min_matches=<n>: CSLAM::m_minNUM = n (addFeatures when fewer landmarks matched, SLAM.cpp:179, 556; default 5).
 // warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
 // Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
 #include <cstdio>
@@ -34,7 +39,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [min_matches=<n>]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -44,6 +49,7 @@ int main(int argc, char** argv)
     fclose(f);
     int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay;
     bool unique = false, subpix = false, joint = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
+    int minMatches = 0, block = 0, nBlocks = 0, nEarly = 0, nFull = 0, nFallback = 0;
     for (int a = 3; a < argc; a++)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
         else if (!strncmp(argv[a], "archive=", 8)) { archiveCap = atoi(argv[a] + 8); loops = true; }
@@ -53,6 +59,8 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "unique=", 7)) { unique = true; uniqueRatio = atof(argv[a] + 7); const char* cm = strchr(argv[a] + 7, ','); if (cm) uniqueExcl = atoi(cm + 1); }
         else if (!strncmp(argv[a], "subpix=", 7)) subpix = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6) != 0;
+        else if (!strncmp(argv[a], "block=", 6)) block = atoi(argv[a] + 6);
+        else if (!strncmp(argv[a], "min_matches=", 12)) minMatches = atoi(argv[a] + 12);
     if (warmup) {
         monoslam::CSLAM w;
         w.m_params.image_w = W; w.m_params.image_h = H; w.MIN_STEP_X = w.MIN_STEP_Y = 0.0;
@@ -74,6 +82,7 @@ int main(int argc, char** argv)
     if (unique) { SLAM.rejectAmbiguousMatches = true; SLAM.AMBIGUITY_RATIO = uniqueRatio; SLAM.AMBIGUITY_EXCLUSION = uniqueExcl; }
     SLAM.subpixelMatches = subpix;
     SLAM.jointUpdate = joint;
+    if (minMatches > 0) SLAM.m_minNUM = minMatches;
     const unsigned char* cur = nullptr;
     std::vector<unsigned char> bgr(colour ? (size_t)3 * W * H : 0);
     SLAM.dataAssociation = [&](monoslam::CSLAM& s) {                                         // loadPictures + dataAssociation (SLAM.cpp:95-97)
@@ -81,8 +90,54 @@ int main(int argc, char** argv)
         for (size_t q = 0; q < (size_t)W * H; q++) bgr[3 * q] = bgr[3 * q + 1] = bgr[3 * q + 2] = cur[q];
         if (s.loadPictures(bgr.data())) s.dataAssociationOnDeviceHeld();
     };
-    const int steps = SLAM.m_odoCounter - 1 - (redirect > 0 ? 1 : 0);
+    int steps = SLAM.m_odoCounter - 1 - (redirect > 0 ? 1 : 0);
     double addWall = -1.0;
+    if (block > 0) {
+        // the block-wise loop: SLAMBlock where it can stand for SLAM(), SLAM() with the association installed for the frame otherwise
+        if (block > 1 && (colour || loops || ransac || archiveCap > 0)) { fprintf(stderr, "block=<F> runs without colour=, loops, archive= and ransac=\n"); return 2; }
+        if (steps > F) steps = F;
+        const auto assoc = SLAM.dataAssociation;
+        auto report = [&](int fr, int nBefore) {
+            printf("policy frame %d deleted %d", fr, SLAM.m_nDeletes); for (int id : SLAM.m_deleteID) printf(" %d", id);
+            printf(" added %d\n", SLAM.m_nMapFeatures - (nBefore - SLAM.m_nDeletes));
+            printf("frame %d n_map %d matches %d\n", fr, SLAM.m_nMapFeatures, SLAM.m_nMatches);
+            printf("ids"); for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) printf(" %d", m->ID); printf("\n");
+            const int n = SLAM.m_X_k.rows;
+            printf("path %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", fr, SLAM.m_X_k.at(n - 4, 0), SLAM.m_X_k.at(n - 3, 0), SLAM.m_X_k.at(n - 2, 0), SLAM.m_X_k.at(n - 1, 0),
+                   SLAM.m_P_k.at(n - 4, n - 4), SLAM.m_P_k.at(n - 4, n - 3), SLAM.m_P_k.at(n - 3, n - 4), SLAM.m_P_k.at(n - 3, n - 3));
+        };
+        double wall = 0.0;
+        for (int fr = 0; fr < steps;) {
+            const int want = steps - fr < block ? steps - fr : block, nBefore = SLAM.m_nMapFeatures;
+            SLAM.dataAssociation = nullptr;
+            const int used = block > 1 ? SLAM.SLAMBlock(frames.data() + (size_t)fr * W * H, want) : 0;
+            if (!SLAM.lastError.empty()) { fprintf(stderr, "block at frame %d: %s\n", fr, SLAM.lastError.c_str()); return 1; }
+            if (used > 0) {
+                nBlocks++; if (used < want) nEarly++; if (used == block) nFull++;
+                wall += SLAM.m_frameTime * used;
+                for (int q = 0; q < used - 1; q++) {                                                             // (frames inside a block change nothing: the verdict said so)
+                    const double* t = &SLAM.m_blockPath[8 * (size_t)q];
+                    printf("policy frame %d deleted 0 added 0\n", fr + q);
+                    printf("path %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", fr + q, t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
+                }
+                report(fr + used - 1, nBefore);
+                fr += used;
+                continue;
+            }
+            if (block > 1) nFallback++;
+            cur = frames.data() + (size_t)fr * W * H;
+            SLAM.m_gryImage = cur;
+            SLAM.dataAssociation = assoc;
+            SLAM.SLAM();
+            if (!SLAM.lastError.empty()) { fprintf(stderr, "frame %d: %s\n", fr, SLAM.lastError.c_str()); return 1; }
+            wall += SLAM.m_frameTime;
+            report(fr, nBefore);
+            fr++;
+        }
+        printf("blocks %d early %d full %d fallback %d\n", nBlocks, nEarly, nFull, nFallback);
+        printf("block_frames %d frames %d us_per_frame %.2f\n", block, steps, wall / steps * 1e6);
+        return 0;
+    }
     for (int fr = 0; fr < steps; fr++) {
         cur = frames.data() + (size_t)(fr % F) * W * H;
         SLAM.m_gryImage = cur;

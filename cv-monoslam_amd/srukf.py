@@ -34,6 +34,7 @@ EXPORTS = [
     "srukf_stage_images", "srukf_run_images_async", "srukf_run_images", "srukf_get_image_matches",
     "srukf_run_images_checked_async", "srukf_run_images_checked", "srukf_get_image_checks",
     "srukf_images_search_archive", "srukf_get_image_archive",
+    "srukf_map_policy", "srukf_images_policy", "srukf_images_set_policy_state", "srukf_get_image_policy", "srukf_images_rewind",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -77,6 +78,25 @@ class ArchiveParams(C.Structure):
 class MatchParams(C.Structure):
     """struct srukf_match_params."""
     _fields_ = [("corr_threshold", C.c_double), ("ratio", C.c_double), ("exclusion", C.c_int), ("subpixel", C.c_int)]
+
+
+class PolicyParams(C.Structure):
+    """struct srukf_policy_params."""
+    _fields_ = [("border", C.c_double), ("rho_min", C.c_double), ("min_predictions", C.c_int), ("min_matches", C.c_int)]
+
+
+POLICY_SUMMARY_FIELDS = ("n_predicts", "n_matches", "n_deletes", "n_stores", "n_predicts_after", "n_matches_after", "need_add", "change")
+
+
+class PolicySummary(C.Structure):
+    """struct srukf_policy_summary."""
+    _fields_ = [(k, C.c_int) for k in POLICY_SUMMARY_FIELDS]
+
+
+# struct srukf_policy_state / srukf_policy_summary as numpy records; the verdict bits
+POLICY_STATE_DTYPE = np.dtype([("nPredictTimes", np.int32), ("nMatchTimes", np.int32), ("predictLocation", np.float64, (2,))])
+POLICY_SUMMARY_DTYPE = np.dtype([(k, np.int32) for k in POLICY_SUMMARY_FIELDS])
+POLICY_UNMATCHED, POLICY_RHO, POLICY_BEHIND, POLICY_PRED_BORDER, POLICY_MATCH_BORDER, POLICY_STORE = 1, 2, 4, 8, 16, 32
 
 
 class SrukfError(RuntimeError):
@@ -174,6 +194,12 @@ def load_library(path=None):
     if hasattr(L, "srukf_images_search_archive"):
         L.srukf_images_search_archive.argtypes = [C.c_void_p, C.c_int, C.POINTER(ArchiveParams)]
         L.srukf_get_image_archive.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _dp, _dp, _ip, _dp, _ip, _dp, _ip]
+    if hasattr(L, "srukf_map_policy"):
+        L.srukf_map_policy.argtypes = [C.c_void_p, C.POINTER(PolicyParams), C.c_void_p, _dp, _ip, _dp, _ip, _ip, C.POINTER(PolicySummary)]
+        L.srukf_images_policy.argtypes = [C.c_void_p, C.c_int, C.POINTER(PolicyParams)]
+        L.srukf_images_set_policy_state.argtypes = [C.c_void_p, C.c_void_p]
+        L.srukf_get_image_policy.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, C.c_void_p, C.c_void_p, _ip]
+        L.srukf_images_rewind.argtypes = [C.c_void_p]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -708,6 +734,70 @@ class Filter:
                                                         _i(out["matched"]), _d(out["corr"]), _i(out["hits"])))
             assert L2.value == L
         return out
+
+    # ---- the map policy's verdict (srukf_map_policy, srukf_images_policy) ----
+    @staticmethod
+    def _policy_params(border, rho_min, min_predictions, min_matches):
+        """the policy's parameters as the library's struct; types are checked here, values (border finite and >= 0, rho_min finite, counts >= 0) by the library"""
+        for name, v in (("border", border), ("rho_min", rho_min)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError(f"map policy: {name} must be a real number")
+        for name, v in (("min_predictions", min_predictions), ("min_matches", min_matches)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"map policy: {name} must be an integer")
+            if not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError(f"map policy: {name} does not fit an int")
+        return PolicyParams(float(border), float(rho_min), int(min_predictions), int(min_matches))
+
+    def _policy_state(self, state, who):
+        st = np.ascontiguousarray(state, dtype=POLICY_STATE_DTYPE)
+        if st.shape != (self.N,):
+            raise ValueError(f"{who}: state must have one POLICY_STATE_DTYPE entry per landmark")
+        return st.copy()
+
+    def map_policy(self, state, h, visible, z, matched, border=20.0, rho_min=0.01, min_predictions=10, min_matches=5):
+        """The map policy's verdict for one frame on the filter's current X (srukf_map_policy): state[N] (POLICY_STATE_DTYPE) is advanced with the frame's
+        association -> (verdict[N] of POLICY_* bits, summary dict, new state)."""
+        pp = self._policy_params(border, rho_min, min_predictions, min_matches)
+        N = self.N
+        st = self._policy_state(state, "map_policy")
+        h, z = _c(h).reshape(-1), _c(z).reshape(-1)
+        vis, m = _c(visible, np.int32).reshape(-1), _c(matched, np.int32).reshape(-1)
+        if h.size != 2 * N or z.size != 2 * N or vis.size != N or m.size != N:
+            raise ValueError("map_policy: h / z need 2N entries, visible / matched N")
+        verdict, sm = np.zeros(N, dtype=np.int32), PolicySummary()
+        self._chk(self._lib.srukf_map_policy(self._h, C.byref(pp), st.ctypes.data_as(C.c_void_p), _d(h), _i(vis), _d(z), _i(m), _i(verdict), C.byref(sm)))
+        return verdict, {k: int(getattr(sm, k)) for k in POLICY_SUMMARY_FIELDS}, st
+
+    def images_policy(self, on, border=20.0, rho_min=0.01, min_predictions=10, min_matches=5):
+        """The switch of the map policy behind image frames (srukf_images_policy): while on, every frame of every later run_images* / run_images_checked* is
+        followed by the verdict on that frame's posterior; get_image_policy has the per-frame record.  Not while an image run is in flight (SRUKF_ERR_SEQUENCE)."""
+        if not isinstance(on, (bool, np.bool_)) and not (isinstance(on, (int, np.integer)) and on in (0, 1)):
+            raise TypeError("images_policy: on must be a bool")
+        pp = self._policy_params(border, rho_min, min_predictions, min_matches)
+        self._chk(self._lib.srukf_images_policy(self._h, int(bool(on)), C.byref(pp)))
+
+    def set_policy_state(self, state):
+        """Seeds the policy state the staged images own (srukf_images_set_policy_state): state[N] of POLICY_STATE_DTYPE.  Images staged, no run pending."""
+        st = self._policy_state(state, "set_policy_state")
+        self._chk(self._lib.srukf_images_set_policy_state(self._h, st.ctypes.data_as(C.c_void_p)))
+
+    def get_image_policy(self, first, count):
+        """What the policy wrote behind staged frames [first, first + count) (srukf_get_image_policy): dict of verdict[count, N], summary (structured array
+        [count] of POLICY_SUMMARY_FIELDS), state[N] (the device state now) and first_change (the lowest frame whose summary has `change`, or -1)."""
+        self._image_run_args(first, count, UPDATE_BATCHED)
+        N = self.N
+        out = dict(verdict=np.zeros((count, N), dtype=np.int32), summary=np.zeros(count, dtype=POLICY_SUMMARY_DTYPE), state=np.zeros(N, dtype=POLICY_STATE_DTYPE))
+        fc = C.c_int(-1)
+        self._chk(self._lib.srukf_get_image_policy(self._h, int(first), int(count), _i(out["verdict"]), out["summary"].ctypes.data_as(C.c_void_p),
+                                                   out["state"].ctypes.data_as(C.c_void_p), C.byref(fc)))
+        out["first_change"] = int(fc.value)
+        return out
+
+    def images_rewind(self):
+        """Puts back the checkpoint of the image block the last synchronize ended clean: X, S, every matchPatch and the policy state (srukf_images_rewind).
+        SrukfError(SRUKF_ERR_SEQUENCE) when a run is pending, no image block has been synchronised, or the state has been written since."""
+        self._chk(self._lib.srukf_images_rewind(self._h))
 
     def synchronize(self):
         self._chk(self._lib.srukf_synchronize(self._h))

@@ -554,6 +554,64 @@ int  srukf_get_image_checks(srukf_ctx* ctx, int first, int count, double* corr2,
 int  srukf_images_search_archive(srukf_ctx* ctx, int on, const srukf_archive_params* params);
 int  srukf_get_image_archive(srukf_ctx* ctx, int first, int count, int* L, double* h, double* Si, int* visible, double* z, int* matched, double* corr, int* hits);
 
+/* ---- the map policy's verdict: which frame of an image run asks for a map change ----
+ * The deletion policy of CSLAM::updateFeaturesInformation (cslam.cpp:446-462; SLAM.cpp:2443-2459) and the addFeatures trigger (SLAM.cpp:556) as a read-only
+ * verdict: nothing is deleted or added, the filter's data are untouched.
+ * srukf_policy_state, per landmark: the counters of predictMeasurement / KalmanUpdate (cslam.cpp:713-723, 751) — visible: nPredictTimes++, predictLocation = h;
+ *   not visible: predictLocation keeps its last value; matched: nMatchTimes++.
+ * verdict[k], the tests of cslam.cpp:446-457 on the updated counters and the posterior X, each on its own:
+ *   SRUKF_POLICY_UNMATCHED     nPredictTimes > 2 nMatchTimes && nPredictTimes >= min_predictions
+ *   SRUKF_POLICY_RHO           rho < rho_min
+ *   SRUKF_POLICY_BEHIND        rho (zi - X[n - 2]) + cos(phi) cos(theta) < 0
+ *   SRUKF_POLICY_PRED_BORDER   predictLocation within `border` of an image edge
+ *   SRUKF_POLICY_MATCH_BORDER  matched, and z within `border` of an edge
+ *   SRUKF_POLICY_STORE         the landmark would be archived (isNeedStore, cslam.cpp:461-462): none of the first three, and PRED_BORDER with a match, or
+ *                              MATCH_BORDER without PRED_BORDER
+ *   Any of the first five bits is a deletion.  Verdicts are per landmark and independent: the reference's list walk skips the node that slides into a deleted
+ *   position (cslam.cpp:475-481), which only happens in a frame that already has a deletion, so `change` is exact; the host applies the walk when it deletes.
+ * srukf_policy_summary, per frame: n_predicts / n_matches as the host counts them (visible / matched landmarks), n_deletes, n_stores, n_predicts_after =
+ *   n_predicts - n_deletes and n_matches_after = n_matches - n_stores (the decrements of cslam.cpp:460-462), need_add = n_matches_after < min_matches
+ *   (SLAM.cpp:556), change = n_deletes > 0 || need_add.
+ * srukf_map_policy (step-wise; cslam.cpp:446-462, 713-723, 751 for one frame): the kernel on the filter's current X with the caller's association — h[2N],
+ *   visible[N] as srukf_predict_measurement returned them, z[2N], matched[N] as the update took them; state_inout[N] is advanced, verdict[N] and *summary are
+ *   written.  params NULL: { 20, 0.01, 10, 5 } (DIST_2_BORDER, 0.01, 10, the 5 of SLAM.cpp:556).  SRUKF_ERR_BAD_ARG: a NULL pointer; border not finite or < 0,
+ *   rho_min not finite, a negative count.  SRUKF_ERR_DIM_MISMATCH: an empty map.  SRUKF_ERR_SEQUENCE: staged frames in flight.
+ * srukf_images_policy: a switch on the handle, like srukf_images_search_archive: it survives map changes, srukf_reset and srukf_destroy clear it; params NULL: the
+ *   defaults; srukf_map_policy's parameter checks; not while an image run is in flight (SRUKF_ERR_SEQUENCE).  The call touches no device.  While on, every frame of
+ *   every later image run (srukf_run_images* and srukf_run_images_checked*, BATCHED and JOINT, searching or not) is followed by the same kernel on that frame's
+ *   posterior and its row of the association's record; it writes row `frame` of the policy record and advances the policy state the staged images own.  Such runs
+ *   are issued as the one-frame captured graph per frame with the policy launch behind it (no captured frames of their own; the parameters live in a device struct
+ *   written in stream order in front of each run, so changing one needs no recapture).  With the switch off an image run is exactly what it was.
+ * srukf_images_set_policy_state (the counters map[] holds, cslam.cpp:713-723): seeds the device state from state[N].  Legal with images staged and no run pending
+ *   (SRUKF_ERR_SEQUENCE otherwise).  Without it the state starts at zero.  A seed ends the block before it: srukf_images_rewind is refused until the next block.  The state lives and dies with the staged images (a map change, srukf_stage_images,
+ *   srukf_stage_sequence and srukf_reset drop it).
+ * srukf_get_image_policy (what updateFeaturesInformation, SLAM.cpp:2443-2459, and the trigger of SLAM.cpp:556 would decide behind frames [first, first + count)):
+ *   waits for the stream like srukf_get_image_matches.  verdict[count][N], summary[count], state_out[N] (the device state now) may each be NULL.  *first_change: the
+ *   lowest frame index in the range whose summary has `change`, or -1.  Rows no policy run has written are zero.  SRUKF_ERR_SEQUENCE: no images staged or no policy
+ *   run since they were; SRUKF_ERR_DIM_MISMATCH: rows outside the staged stack.
+ * srukf_images_rewind (the undo a host needs to stop a block at the frame whose verdict asks for a map change, SLAM.cpp:552-562): puts back the checkpoint of the
+ *   image block that the last srukf_synchronize ended clean — X, S, every matchPatch and the policy state, as a flagged block's automatic restore does (which puts
+ *   the policy state back too).  Either restore also zeroes every verdict and summary row: what the restored frames wrote is no verdict any more, and
+ *   srukf_get_image_policy reads such rows as rows no policy run has written (first_change -1) until frames run again.  SRUKF_ERR_SEQUENCE: a run is pending, no image block has been synchronised clean, or anything has written X, S or a matchPatch
+ *   since (srukf_predict_motion, srukf_set_state, srukf_run_frames*, srukf_associate*, an appearance capture, srukf_images_set_policy_state, ...; a second rewind of the same block).
+ * All: SRUKF_ERR_BAD_ARG for a NULL handle (srukf_get_image_policy: first < 0, count < 1; srukf_images_set_policy_state: state NULL) before any device is touched. */
+#define SRUKF_POLICY_UNMATCHED     1
+#define SRUKF_POLICY_RHO           2
+#define SRUKF_POLICY_BEHIND        4
+#define SRUKF_POLICY_PRED_BORDER   8
+#define SRUKF_POLICY_MATCH_BORDER 16
+#define SRUKF_POLICY_STORE        32
+typedef struct srukf_policy_params { double border; double rho_min; int min_predictions; int min_matches; } srukf_policy_params;
+#define SRUKF_POLICY_DEFAULTS { 20.0, 0.01, 10, 5 }
+typedef struct srukf_policy_state { int nPredictTimes; int nMatchTimes; double predictLocation[2]; } srukf_policy_state;
+typedef struct srukf_policy_summary { int n_predicts, n_matches, n_deletes, n_stores, n_predicts_after, n_matches_after, need_add, change; } srukf_policy_summary;
+int  srukf_map_policy(srukf_ctx* ctx, const srukf_policy_params* params, srukf_policy_state* state_inout, const double* h, const int* visible, const double* z,
+                      const int* matched, int* verdict, srukf_policy_summary* summary);
+int  srukf_images_policy(srukf_ctx* ctx, int on, const srukf_policy_params* params);
+int  srukf_images_set_policy_state(srukf_ctx* ctx, const srukf_policy_state* state);
+int  srukf_get_image_policy(srukf_ctx* ctx, int first, int count, int* verdict, srukf_policy_summary* summary, srukf_policy_state* state_out, int* first_change);
+int  srukf_images_rewind(srukf_ctx* ctx);
+
 /* ---- instrumentation ------------------------------------------------------------------------ */
 
 /* When on, every kernel launch is bracketed by HIP events on the context's stream and the
