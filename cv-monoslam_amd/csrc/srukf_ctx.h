@@ -120,6 +120,14 @@ struct ImageReplay {
     // images_rewind_void, which every state-writing entry passes through step_invalidate)
     srukf_policy_state *pol_state = nullptr, *pol_ck = nullptr; int* pol_verdict = nullptr; srukf_policy_summary* pol_sum = nullptr; srukf_policy_params* pol_args = nullptr;
     bool pol_valid = false, ck_clean = false;
+    // The 1-point RANSAC consensus inside image frames (srukf_images_ransac), allocated by images_ransac_ensure in front of the first run with
+    // the switch on: the scratch of the two launches (rs_D [N][N], rs_F [N][N] bytes, rs_votes [N]), the record (rs_flags / rs_rvotes / rs_dist [frames][N], rs_sum
+    // [frames], zero until such a frame writes a row, zeroed again by images_restore) and the threshold the launches read (rs_args, written in stream order in front
+    // of every such run).  rs_valid: such a run has written the record.  Captured frames of their own per kind of image run and update mode (rs_graphs)
+    double *rs_D = nullptr, *rs_dist = nullptr; unsigned char* rs_F = nullptr; int *rs_votes = nullptr, *rs_flags = nullptr, *rs_rvotes = nullptr;
+    RansacSummary* rs_sum = nullptr; RansacArgs* rs_args = nullptr;
+    bool rs_valid = false;
+    ReplayGraphs rs_graphs[2][2][2];       // [searching][checked][mode]: the frames with the consensus in them
 };
 
 // ---- the context: who owns what across a map change ("who owns what across a map change") ----------------------
@@ -163,6 +171,8 @@ struct srukf_handle_scope : srukf_switches {
     ArchiveArgs img_search_args = { 40, 0.8, 5.99146454710798 };   // ... these parameters.  Survives map changes; srukf_reset clears it
     bool img_policy = false;               // srukf_images_policy: every frame of every later image run is followed by the map policy's verdict, with ...
     srukf_policy_params img_policy_args = SRUKF_POLICY_DEFAULTS;   // ... these parameters.  Survives map changes; srukf_reset clears it
+    bool img_ransac = false;               // srukf_images_ransac: every frame of every later image run holds the 1-point RANSAC consensus between association and update, with ...
+    double img_ransac_thr = 8.0;           // ... this threshold.  Survives map changes and srukf_reset
     std::string err;
     // the pool allocations among the members above (det and archive: det_scratch_free / archive_free).  A new buffer of this scope is added HERE
     template <class F> void each_device_buffer(F f) const { void* b[] = { d_image, d_bgr, d_ovl }; for (void* q : b) f(q); }
@@ -335,7 +345,8 @@ struct srukf_map_scope : srukf_life {
                       odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt, jointZd, jointW, jointRd,
                       img.images, img.ck_tmpl, img.corr_seq, img.h_seq, img.xyz, img.ckS, img.ckX, img.vis_seq,
                       img.corr2_seq, img.z2_seq, img.flags_seq, img.match_args, img.ar_rec, img.ar_args,
-                      img.pol_state, img.pol_ck, img.pol_verdict, img.pol_sum, img.pol_args };
+                      img.pol_state, img.pol_ck, img.pol_verdict, img.pol_sum, img.pol_args,
+                      img.rs_D, img.rs_dist, img.rs_F, img.rs_votes, img.rs_flags, img.rs_rvotes, img.rs_sum, img.rs_args };
         for (void* q : b) f(q);
     }
 };

@@ -234,4 +234,20 @@ struct StagedPolicy {
 void launch_map_policy(hipStream_t st, KDims d, srukf_params p, const srukf_policy_params* prm, const double* X, const double* h, const int* vis, const double* z, const int* m,
                        srukf_policy_state* state, int* verdict, srukf_policy_summary* sum);
 void launch_map_policy_staged(hipStream_t st, KDims d, srukf_params p, const srukf_policy_params* prm, StagedPolicy a, int frame);
+
+// ---- srukf_ransac.hip (the consensus inside the frames of an image run; C++ linkage) ----
+// k_ransac_votes_staged (N workgroups) + k_ransac_pick_staged (one): k_ransac_votes / k_ransac_pick (one text of each body) on row fs->frame of the staged z_seq /
+// m_seq, with the context's live Ut (S^T DZ behind seq_pxy(FORM_PLAIN)), PxyR, h, Si, vis, X.  StagedRansac: the rows, the frame counter, the threshold on the device
+// (args: written in stream order, launch_set_ransac_args), the scratch (D [N][N], F [N][N] bytes, votes [N]) and the record (rec_flags / rec_votes / rec_dist
+// [frames][N], rec_sum [frames]).  The pick launch rewrites the frame's m_seq row to the inlier mask
+struct RansacArgs { double threshold; };
+struct RansacSummary { int best, n_active, n_low, outlier; };
+struct StagedRansac {
+    int frames; const double* z_seq; int* m_seq; const FrameScalars* fs; const RansacArgs* args;
+    double* D; unsigned char* F; int* votes;
+    int* rec_flags; int* rec_votes; double* rec_dist; RansacSummary* rec_sum;
+};
+void launch_ransac_staged(hipStream_t st, KDims d, KWeights w, srukf_params p, StagedRansac a, const double* X, const double* Ut, const double* PxyR, const double* h,
+                          const double* Si, const int* vis);
+void launch_set_ransac_args(hipStream_t st, RansacArgs* dst, RansacArgs v);
 void launch_set_policy_params(hipStream_t st, srukf_policy_params* dst, srukf_policy_params v);

@@ -5,6 +5,10 @@
 //     k_ransac_votes             one workgroup per hypothesis i: x(i) = X + K_i (z_i - h_i) restricted to the ten rows a pair needs, the projection of every
 //                                matched landmark j under it, d_ij, the votes of i (wave ballots, integer adds)
 //     k_ransac_pick              one workgroup: the hypothesis with the most votes (lowest index among equals), its mask and distances
+//   srukf_images_ransac          the same consensus inside every frame of an image run (the switch and the record: srukf_replay.hip):
+//     k_ransac_votes_staged      k_ransac_votes' body on the frame's own operands — c->Ut is S^T DZ behind seq_pxy(FORM_PLAIN), z / matched are row fs->frame of
+//                                z_seq / m_seq behind k_associate_staged — with the threshold in a device struct
+//     k_ransac_pick_staged       k_ransac_pick's rule, the frame's row of the record, and the frame's m_seq row rewritten to the consensus set for the update
 //   srukf_repredict_measurement  the slow path's measurement prediction from the posterior: k_motion with a zero control on a COPY of the state fills the table of
 //                                robot poses (the sigma points' robot parts as they stand), k_project / k_meas_* as in srukf_predict_measurement.  No new kernels.
 // The consensus reads the filter and writes nothing of it.  A frame predicted on the slow path has its predicted state and statistics in the context's buffers.  A frame
@@ -15,12 +19,12 @@
 #include "srukf_ctx.h"
 using namespace srukf_impl;
 
-// Hypothesis i = blockIdx.x.  act[k] = matched[k] && visible[k].  Ut[c][r] = (S^T DZ)^T (k_pxy), PxyR[e][c] the robot rows of the cross covariances.
-// D[i][j] = d_ij, F[i][j] = 1 for an inlier pair (rows of length N; only rows / columns of A are written), votes[i] for i in A.
-__global__ __launch_bounds__(256) void k_ransac_votes(KDims d, KWeights w, srukf_params p, const double* __restrict__ X, const double* __restrict__ Ut,
-                                                      const double* __restrict__ PxyR, const double* __restrict__ h, const double* __restrict__ Si,
-                                                      const int* __restrict__ vis, const double* __restrict__ z, const int* __restrict__ matched, double thr,
-                                                      double* __restrict__ D, unsigned char* __restrict__ F, int* __restrict__ votes)
+// The votes of hypothesis i = blockIdx.x: the one text of both launch fronts.  act[k] = matched[k] && visible[k].  Ut[c][r] = (S^T DZ)^T (k_pxy), PxyR[e][c] the robot
+// rows of the cross covariances.  D[i][j] = d_ij, F[i][j] = 1 for an inlier pair (rows of length N; only rows / columns of A are written), votes[i] for i in A.
+__device__ __forceinline__ void ransac_votes_body(KDims d, KWeights w, srukf_params p, const double* __restrict__ X, const double* __restrict__ Ut,
+                                                  const double* __restrict__ PxyR, const double* __restrict__ h, const double* __restrict__ Si,
+                                                  const int* __restrict__ vis, const double* __restrict__ z, const int* __restrict__ matched, double thr,
+                                                  double* __restrict__ D, unsigned char* __restrict__ F, int* __restrict__ votes)
 {
     __shared__ double sh[12];                                  // Si_i^-1 (4), y_i = Si_i^-T (z_i - h_i) (2), robot rows of x(i) (4), cos / sin of its heading
     __shared__ int wv[4];
@@ -70,17 +74,39 @@ __global__ __launch_bounds__(256) void k_ransac_votes(KDims d, KWeights w, srukf
     if (threadIdx.x == 0) votes[i] = (wv[0] + wv[1]) + (wv[2] + wv[3]);
 }
 
-// res = dist[N] (doubles) | inlier[N] | votes[N] | best (ints).  One workgroup.
-__global__ __launch_bounds__(256) void k_ransac_pick(int N, const int* __restrict__ vis, const int* __restrict__ matched, const double* __restrict__ D,
-                                                     const unsigned char* __restrict__ F, const int* __restrict__ votes, double* __restrict__ dist,
-                                                     int* __restrict__ inlier, int* __restrict__ votes_out, int* __restrict__ best_out)
+// step-wise: the caller's z / matched, the threshold as an argument
+__global__ __launch_bounds__(256) void k_ransac_votes(KDims d, KWeights w, srukf_params p, const double* __restrict__ X, const double* __restrict__ Ut,
+                                                      const double* __restrict__ PxyR, const double* __restrict__ h, const double* __restrict__ Si,
+                                                      const int* __restrict__ vis, const double* __restrict__ z, const int* __restrict__ matched, double thr,
+                                                      double* __restrict__ D, unsigned char* __restrict__ F, int* __restrict__ votes)
+{
+    ransac_votes_body(d, w, p, X, Ut, PxyR, h, Si, vis, z, matched, thr, D, F, votes);
+}
+
+// inside a frame of an image run (srukf_images_ransac), behind k_associate_staged and in front of k_gain / the joint kernels: z / matched are
+// row fs->frame of the staged z_seq / m_seq, the threshold is the device struct's, the rest the context's live buffers as seq_pxy(FORM_PLAIN) left them (Ut is still
+// S^T DZ: k_gain turns it into U^T afterwards).  A frame counter outside the staged stack writes nothing
+__global__ __launch_bounds__(256) void k_ransac_votes_staged(KDims d, KWeights w, srukf_params p, StagedRansac a, const double* __restrict__ X,
+                                                             const double* __restrict__ Ut, const double* __restrict__ PxyR, const double* __restrict__ h,
+                                                             const double* __restrict__ Si, const int* __restrict__ vis)
+{
+    const int f = a.fs->frame;
+    if (f < 0 || f >= a.frames) return;
+    ransac_votes_body(d, w, p, X, Ut, PxyR, h, Si, vis, a.z_seq + (size_t)f * 2 * d.N, a.m_seq + (size_t)f * d.N, a.args->threshold, a.D, a.F, a.votes);
+}
+
+// The pick rule, the one text of both launch fronts: the active hypothesis with the most votes, the lowest index among equals; -1 without an active one.  All 256
+// threads call it; active(i) / votes[i] are read once per index, seen(i, act, votes) is called once per index by the thread that owns it (i = tid + 256 q).
+// Ends behind a barrier: every thread's reads of the active set are complete when it returns
+template <class Active, class Seen>
+__device__ __forceinline__ int ransac_pick_best(int N, const int* __restrict__ votes, Active active, Seen seen)
 {
     __shared__ int bv[256], bi[256];
     int v = -1, b = -1;                                        // this thread's best: most votes, then lowest index (its indices ascend)
     for (int i = threadIdx.x; i < N; i += 256) {
-        const bool act = matched[i] != 0 && vis[i] != 0;
+        const bool act = active(i);
         const int vi = act ? votes[i] : 0;
-        votes_out[i] = vi;
+        seen(i, act, vi);
         if (act && vi > v) { v = vi; b = i; }
     }
     bv[threadIdx.x] = v; bi[threadIdx.x] = b;
@@ -92,7 +118,15 @@ __global__ __launch_bounds__(256) void k_ransac_pick(int N, const int* __restric
         }
         __syncthreads();
     }
-    const int best = bi[0];
+    return bi[0];
+}
+
+// res = dist[N] (doubles) | inlier[N] | votes[N] | best (ints).  One workgroup.
+__global__ __launch_bounds__(256) void k_ransac_pick(int N, const int* __restrict__ vis, const int* __restrict__ matched, const double* __restrict__ D,
+                                                     const unsigned char* __restrict__ F, const int* __restrict__ votes, double* __restrict__ dist,
+                                                     int* __restrict__ inlier, int* __restrict__ votes_out, int* __restrict__ best_out)
+{
+    const int best = ransac_pick_best(N, votes, [&](int i) { return matched[i] != 0 && vis[i] != 0; }, [&](int i, bool, int vi) { votes_out[i] = vi; });
     if (threadIdx.x == 0) *best_out = best;
     for (int j = threadIdx.x; j < N; j += 256) {
         const bool act = best >= 0 && matched[j] != 0 && vis[j] != 0;
@@ -100,6 +134,59 @@ __global__ __launch_bounds__(256) void k_ransac_pick(int N, const int* __restric
         dist[j] = act ? D[(size_t)best * N + j] : 0.0;
     }
 }
+
+// One workgroup behind k_ransac_votes_staged: k_ransac_pick's rule, the frame's row of the record (flags: bit 0 in A, bit 1 low-innovation inlier; votes; dist; the
+// summary), and the frame's m_seq row rewritten to the inlier mask, which the update that follows then takes for its matches (z_seq stays).  Fewer than two active
+// matches (the facade's m_nMatches < 2 branch): m_seq is left alone, the record says inlier = active, votes 0, best -1, dist 0.  The active set goes to LDS in the
+// first pass (act_s, N bytes of dynamic LDS) and ransac_pick_best's barriers stand between that pass and the rewrite.  A frame counter outside the staged stack
+// writes nothing
+__global__ __launch_bounds__(256) void k_ransac_pick_staged(int N, StagedRansac a, const int* __restrict__ vis)
+{
+    extern __shared__ unsigned char act_s[];
+    __shared__ int cnt[2][4];
+    const int f = a.fs->frame, tid = threadIdx.x;
+    if (f < 0 || f >= a.frames) return;
+    int* mrow = a.m_seq + (size_t)f * N;
+    int* rflags = a.rec_flags + (size_t)f * N;
+    int* rvotes = a.rec_votes + (size_t)f * N;
+    double* rdist = a.rec_dist + (size_t)f * N;
+    int n_act = 0;
+    const int best = ransac_pick_best(N, a.votes, [&](int i) { return mrow[i] != 0 && vis[i] != 0; }, [&](int i, bool act, int) { act_s[i] = act ? 1 : 0; n_act += act ? 1 : 0; });
+    for (int off = 32; off > 0; off >>= 1) n_act += __shfl_down(n_act, off, 64);
+    if ((tid & 63) == 0) cnt[0][tid >> 6] = n_act;
+    __syncthreads();
+    const int n_active = (cnt[0][0] + cnt[0][1]) + (cnt[0][2] + cnt[0][3]);
+    const bool vote = n_active >= 2;
+    int n_low = 0;
+    for (int j = tid; j < N; j += 256) {
+        const bool act = act_s[j] != 0;
+        const bool inl = act && (!vote || a.F[(size_t)best * N + j] != 0);
+        rflags[j] = (act ? 1 : 0) | (inl ? 2 : 0);
+        rvotes[j] = (vote && act) ? a.votes[j] : 0;
+        rdist[j] = (vote && act) ? a.D[(size_t)best * N + j] : 0.0;
+        if (vote) mrow[j] = inl ? 1 : 0;
+        n_low += inl ? 1 : 0;
+    }
+    for (int off = 32; off > 0; off >>= 1) n_low += __shfl_down(n_low, off, 64);
+    if ((tid & 63) == 0) cnt[1][tid >> 6] = n_low;
+    __syncthreads();
+    if (tid == 0) {
+        const int nl = (cnt[1][0] + cnt[1][1]) + (cnt[1][2] + cnt[1][3]);
+        RansacSummary o;
+        o.best = vote ? best : -1; o.n_active = n_active; o.n_low = nl; o.outlier = (vote && nl < n_active) ? 1 : 0;
+        a.rec_sum[f] = o;
+    }
+}
+
+__global__ void k_set_ransac_args(RansacArgs* dst, RansacArgs v) { *dst = v; }
+
+void launch_ransac_staged(hipStream_t st, KDims d, KWeights w, srukf_params p, StagedRansac a, const double* X, const double* Ut, const double* PxyR, const double* h,
+                          const double* Si, const int* vis)
+{
+    hipLaunchKernelGGL(k_ransac_votes_staged, dim3(d.N), dim3(256), 0, st, d, w, p, a, X, Ut, PxyR, h, Si, vis);
+    hipLaunchKernelGGL(k_ransac_pick_staged, dim3(1), dim3(256), (size_t)((d.N + 7) / 8 * 8), st, d.N, a, vis);
+}
+void launch_set_ransac_args(hipStream_t st, RansacArgs* dst, RansacArgs v) { hipLaunchKernelGGL(k_set_ransac_args, dim3(1), dim3(1), 0, st, dst, v); }
 
 namespace srukf_impl {
 

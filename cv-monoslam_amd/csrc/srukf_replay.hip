@@ -930,7 +930,9 @@ int read_fs_host(srukf_ctx* c)
 
 void drop_graphs(srukf_map_scope* c)
 {
-    for (ReplayGraphs* gs : { c->graphs, c->img.graphs, c->img.chk_graphs, c->img.ar_graphs[0], c->img.ar_graphs[1] }) for (int m = 0; m < 2; m++) {      // the captured frames of both update modes: without the association, with it, with the checked one, with the archive search behind either
+    ImageReplay& im = c->img;
+    for (ReplayGraphs* gs : { c->graphs, im.graphs, im.chk_graphs, im.ar_graphs[0], im.ar_graphs[1],
+                              im.rs_graphs[0][0], im.rs_graphs[0][1], im.rs_graphs[1][0], im.rs_graphs[1][1] }) for (int m = 0; m < 2; m++) {      // the captured frames of both update modes: without the association, with it, with the checked one, with the archive search behind either, with the consensus in any of these
         ReplayGraphs& g = gs[m];
         for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec, &g.block_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
         for (hipGraph_t* q : { &g.one, &g.eight, &g.block }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
@@ -943,8 +945,8 @@ void drop_graphs(srukf_map_scope* c)
 void images_archive_drop(srukf_map_scope* c, hipStream_t st)
 {
     ImageReplay& im = c->img;
-    for (int k = 0; k < 2; k++) for (int m = 0; m < 2; m++) {
-        ReplayGraphs& g = im.ar_graphs[k][m];
+    for (int k = 0; k < 2; k++) for (int m = 0; m < 2; m++) for (ReplayGraphs* gp : { &im.ar_graphs[k][m], &im.rs_graphs[1][k][m] }) {      // (the searching frames, with and without the consensus)
+        ReplayGraphs& g = *gp;
         for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
         for (hipGraph_t* q : { &g.one, &g.eight }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
     }
@@ -958,7 +960,8 @@ void images_drop(srukf_map_scope* c, hipStream_t st)
     if (im.images) drop_graphs(c);                               // (the captured image frames hold these pointers)
     for (void* b : { (void*)im.images, (void*)im.ck_tmpl, (void*)im.corr_seq, (void*)im.h_seq, (void*)im.xyz, (void*)im.ckS, (void*)im.ckX, (void*)im.vis_seq,
                       (void*)im.corr2_seq, (void*)im.z2_seq, (void*)im.flags_seq, (void*)im.match_args, (void*)im.ar_rec, (void*)im.ar_args,
-                      (void*)im.pol_state, (void*)im.pol_ck, (void*)im.pol_verdict, (void*)im.pol_sum, (void*)im.pol_args }) if (b) srukf_dfree_on(b, st);
+                      (void*)im.pol_state, (void*)im.pol_ck, (void*)im.pol_verdict, (void*)im.pol_sum, (void*)im.pol_args,
+                      (void*)im.rs_D, (void*)im.rs_dist, (void*)im.rs_F, (void*)im.rs_votes, (void*)im.rs_flags, (void*)im.rs_rvotes, (void*)im.rs_sum, (void*)im.rs_args }) if (b) srukf_dfree_on(b, st);
     im = ImageReplay{};
 }
 
@@ -1024,7 +1027,10 @@ static void replay_one_frame(srukf_ctx* c, int mode)
 // checked: a frame of a checked image run — the same frame with k_associate_checked_staged in k_associate_staged's place; images_checked_ensure has run
 // search: a frame of a searching image run — the same frame with the archive search behind its tail, on the posterior (seq_archive_search: it
 // writes the archive's own buffers and the search record, nothing the filter reads); images_archive_ensure has run
-static void replay_one_image_frame(srukf_ctx* c, int mode, bool checked, bool search)
+// ransac: a frame with the 1-point RANSAC consensus in it (srukf_images_ransac) — two more launches between the association and what stands in
+// k_gain's place: c->Ut is still S^T DZ there, PxyR / h / Si / vis / X are the predicted frame's, and this frame's rows of z_seq / m_seq are written: what
+// k_ransac_votes reads.  The pick launch rewrites the m_seq row to the consensus set, which the update then takes for its matches; images_ransac_ensure has run
+static void replay_one_image_frame(srukf_ctx* c, int mode, bool checked, bool search, bool ransac)
 {
     ImageReplay& im = c->img;
     const KDims& d = c->d;
@@ -1042,17 +1048,22 @@ static void replay_one_image_frame(srukf_ctx* c, int mode, bool checked, bool se
         else
         srukf_launch_associate_staged(c->stream, d, c->p, rec, c->h, c->Si, c->vis, c->has_app, c->app_tmpl);
     }
+    if (ransac) {
+        ProfScope ps(c, KC_MISC, 60.0 * d.N * d.N, 9.0 * d.N * d.N + 16.0 * 12 * d.N * d.N);
+        launch_ransac_staged(c->stream, d, c->w, c->p, StagedRansac{ im.frames, c->z_seq, c->m_seq, c->fs, im.rs_args, im.rs_D, im.rs_F, im.rs_votes,
+                                                                     im.rs_flags, im.rs_rvotes, im.rs_dist, im.rs_sum }, c->X, c->Ut, c->PxyR, c->h, c->Si, c->vis);
+    }
     if (mode == SRUKF_UPDATE_JOINT) seq_joint_launches(c, nullptr, nullptr);
     else seq_gain_only(c, nullptr, nullptr, FORM_PLAIN);
     seq_refactor(c, refactor_frame_tail(c), FORM_PLAIN);
     if (search) seq_archive_search(c);
 }
 
-// images: frames of an image run (checked: of a checked one; search: of a searching one)
-static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge, bool images = false, bool checked = false, bool search = false)
+// images: frames of an image run (checked: of a checked one; search: of a searching one; ransac: with the consensus in them)
+static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge, bool images = false, bool checked = false, bool search = false, bool ransac = false)
 {
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    for (int q = 0; q < nframes; q++) { if (images) replay_one_image_frame(c, mode, checked, search); else replay_one_frame(c, mode); }
+    for (int q = 0; q < nframes; q++) { if (images) replay_one_image_frame(c, mode, checked, search, ransac); else replay_one_frame(c, mode); }
     const hipError_t launch_err = hipGetLastError();            // a failed launch inside the capture must not leave the stream capturing
     HIPCHK(c, hipStreamEndCapture(c->stream, g));
     HIPCHK(c, launch_err);
@@ -1372,6 +1383,13 @@ static void images_restore(srukf_ctx* c)
         hipMemsetAsync(im.pol_verdict, 0, sizeof(int) * (size_t)im.frames * (size_t)c->d.N, c->stream);
         hipMemsetAsync(im.pol_sum, 0, sizeof(srukf_policy_summary) * (size_t)im.frames, c->stream);
     }
+    if (im.rs_flags) {                                         // the consensus record: what the block's frames wrote does not stand either
+        const size_t fN = (size_t)im.frames * (size_t)c->d.N;
+        hipMemsetAsync(im.rs_flags, 0, sizeof(int) * fN, c->stream);
+        hipMemsetAsync(im.rs_rvotes, 0, sizeof(int) * fN, c->stream);
+        hipMemsetAsync(im.rs_dist, 0, sizeof(double) * fN, c->stream);
+        hipMemsetAsync(im.rs_sum, 0, sizeof(RansacSummary) * (size_t)im.frames, c->stream);
+    }
     if (c->null_canonical != im.ck_canon) { c->null_canonical = im.ck_canon; drop_graphs(c); }
     shadow_rebuild(c);
     hipStreamSynchronize(c->stream);
@@ -1386,7 +1404,7 @@ static int images_checked_ensure(srukf_ctx* c, const char* who)
     ImageReplay& im = c->img;
     int rc = match_ensure(c, who); if (rc) return rc;
     if (im.chk_scores != c->match_scores) {
-        for (int m = 0; m < 2; m++) if (im.chk_graphs[m].one_exec) { HIPCHK(c, hipStreamSynchronize(c->stream)); drop_graphs(c); break; }
+        for (int m = 0; m < 2; m++) if (im.chk_graphs[m].one_exec || im.rs_graphs[0][1][m].one_exec || im.rs_graphs[1][1][m].one_exec) { HIPCHK(c, hipStreamSynchronize(c->stream)); drop_graphs(c); break; }
         im.chk_scores = c->match_scores;
     }
     if (im.corr2_seq) return SRUKF_OK;
@@ -1453,6 +1471,37 @@ static int images_policy_ensure(srukf_ctx* c, const char* who)
     return SRUKF_OK;
 }
 
+// what the consensus inside image frames needs beyond srukf_stage_images' buffers, allocated in front of the first run with the switch on,
+// outside any capture: the scratch of the two launches, the record (zeroed) and the threshold's place on the device
+static int images_ransac_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    if (im.rs_D) return SRUKF_OK;
+    const size_t N = c->d.N, f = (size_t)im.frames;
+    hipError_t e = srukf_dmalloc(&im.rs_D, sizeof(double) * N * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_F, (N * N + 7) / 8 * 8);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_votes, sizeof(int) * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_flags, sizeof(int) * f * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_rvotes, sizeof(int) * f * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_dist, sizeof(double) * f * N);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_sum, sizeof(RansacSummary) * f);
+    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_args, sizeof(RansacArgs));
+    if (e == hipSuccess) e = hipMemsetAsync(im.rs_D, 0, sizeof(double) * N * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.rs_F, 0, (N * N + 7) / 8 * 8, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.rs_votes, 0, sizeof(int) * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.rs_flags, 0, sizeof(int) * f * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.rs_rvotes, 0, sizeof(int) * f * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.rs_dist, 0, sizeof(double) * f * N, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(im.rs_sum, 0, sizeof(RansacSummary) * f, c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void* b : { (void*)im.rs_D, (void*)im.rs_F, (void*)im.rs_votes, (void*)im.rs_flags, (void*)im.rs_rvotes, (void*)im.rs_dist, (void*)im.rs_sum, (void*)im.rs_args }) if (b) srukf_dfree_on(b, c->stream);
+        im.rs_D = im.rs_dist = nullptr; im.rs_F = nullptr; im.rs_votes = im.rs_flags = im.rs_rvotes = nullptr; im.rs_sum = nullptr; im.rs_args = nullptr;
+        c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
+    }
+    return SRUKF_OK;
+}
+
 // the map policy's verdict behind staged frame `frame` (srukf_images_policy): an eager launch with the frame index as a kernel argument — fs->frame has advanced
 // behind the tail, and a captured frame could not carry the index.  It reads the posterior X and row `frame` of the association's record
 static void issue_image_policy(srukf_ctx* c, int frame)
@@ -1500,6 +1549,13 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         launch_set_policy_params(c->stream, im.pol_args, c->img_policy_args);      // in stream order, as the checked run's parameters
         im.pol_valid = true;
     }
+    // the 1-point RANSAC consensus inside every frame (srukf_images_ransac): captured frames of their own
+    const bool ransac = c->img_ransac;
+    if (ransac) {
+        const int rcr = images_ransac_ensure(c, who); if (rcr) return rcr;                            // (idem)
+        launch_set_ransac_args(c->stream, im.rs_args, RansacArgs{ c->img_ransac_thr });      // in stream order, as the checked run's parameters
+        im.rs_valid = true;
+    }
     step_commit_motion(c); step_state_replaced(c);
     if (c->fs_seq_step) {                                      // the step-wise fast path pointed the frame scalars at its own three poses
         hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, c->stream, c->fs, c->odo_seq, c->seqF, c->p.a1, c->p.a2, c->p.a3, c->p.a4);
@@ -1519,7 +1575,7 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
     if (c->red_r > 0 && !c->null_canonical) {
         // null rows that are not (yet) sqrt(EPSILON) e_k: the run's first frame eagerly, as in srukf_run_frames_async (the plain form reads the rows as they are)
         launch_set_run(c->stream, c->fs, first, clear, traj);
-        replay_one_image_frame(c, mode, checked, search);
+        replay_one_image_frame(c, mode, checked, search, ransac);
         if (policy) issue_image_policy(c, first);
         set_null_canonical(c);
         c->async_pending = true; im.pending = true; c->phase = 0; c->frame_updated = false; clear = 0;
@@ -1531,15 +1587,16 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
     if (c->use_graph && !c->profiling) {
         // (image frames only: never a captured frame without the association; plain and checked frames each have their own)
         // (searching frames: their own again, per kind of image run)
-        ReplayGraphs& g = (search ? im.ar_graphs[checked ? 1 : 0] : checked ? im.chk_graphs : im.graphs)[mode == SRUKF_UPDATE_JOINT ? 1 : 0];
-        if (!g.one_exec) { const int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true, checked, search); if (rc) return rc; }
-        if (!policy && !g.eight_exec) { const int rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true, checked, search); if (rc) return rc; }      // (a policy run launches single frames only)
+        // (frames with the consensus in them: their own again, per kind of image run and with or without the search)
+        ReplayGraphs& g = (ransac ? im.rs_graphs[search ? 1 : 0][checked ? 1 : 0] : search ? im.ar_graphs[checked ? 1 : 0] : checked ? im.chk_graphs : im.graphs)[mode == SRUKF_UPDATE_JOINT ? 1 : 0];
+        if (!g.one_exec) { const int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true, checked, search, ransac); if (rc) return rc; }
+        if (!policy && !g.eight_exec) { const int rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true, checked, search, ransac); if (rc) return rc; }      // (a policy run launches single frames only)
         int f = 0;
         if (policy) for (; f < count; f++) { HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream)); issue_image_policy(c, first + f); }
         for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(g.eight_exec, c->stream));
         for (; f < count; f++) HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
     } else {
-        for (int f = 0; f < count; f++) { replay_one_image_frame(c, mode, checked, search); if (policy) issue_image_policy(c, first + f); }
+        for (int f = 0; f < count; f++) { replay_one_image_frame(c, mode, checked, search, ransac); if (policy) issue_image_policy(c, first + f); }
     }
     c->async_pending = true; im.pending = true;
     c->phase = 0; c->frame_updated = false;
@@ -1670,6 +1727,47 @@ int srukf_get_image_policy(srukf_ctx* c, int first, int count, int* verdict, sru
         HIPCHK(c, hipMemcpy(sm.data(), im.pol_sum + a, sizeof(srukf_policy_summary) * m, hipMemcpyDeviceToHost));
         if (summary) memcpy(summary, sm.data(), sizeof(srukf_policy_summary) * m);
         if (first_change) { *first_change = -1; for (size_t q = 0; q < m; q++) if (sm[q].change) { *first_change = first + (int)q; break; } }
+    }
+    return SRUKF_OK;
+}
+
+// ---- the 1-point RANSAC consensus inside image frames (the kernels: srukf_ransac.hip) ----
+// The switch: on the handle, like srukf_images_policy.  Touches no device: the threshold reaches it in stream order in front of the next image run (run_images_issue)
+int srukf_images_ransac(srukf_ctx* c, int on, double threshold)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    if (on && (!std::isfinite(threshold) || threshold <= 0.0)) { c->err = "images_ransac: threshold must be finite and positive"; return SRUKF_ERR_BAD_ARG; }
+    if (c->async_pending) { c->err = "images_ransac: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    c->img_ransac = on != 0;
+    if (on) c->img_ransac_thr = threshold;
+    return SRUKF_OK;
+}
+
+// rows [first, first + count) of the consensus record, after waiting for the stream like srukf_get_image_matches; the lowest frame of the range whose consensus
+// dropped a match
+int srukf_get_image_ransac(srukf_ctx* c, int first, int count, int* flags, int* votes, double* dist, int* best, int* n_active, int* n_low, int* first_outlier)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_ransac: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.rs_flags || !im.rs_valid) { c->err = "get_image_ransac: no record of a run with the consensus in it (srukf_images_ransac)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_ransac: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    if (flags) HIPCHK(c, hipMemcpy(flags, im.rs_flags + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (votes) HIPCHK(c, hipMemcpy(votes, im.rs_rvotes + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (dist) HIPCHK(c, hipMemcpy(dist, im.rs_dist + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
+    if (best || n_active || n_low || first_outlier) {
+        std::vector<RansacSummary> sm(m);
+        HIPCHK(c, hipMemcpy(sm.data(), im.rs_sum + a, sizeof(RansacSummary) * m, hipMemcpyDeviceToHost));
+        if (first_outlier) *first_outlier = -1;
+        for (size_t q = 0; q < m; q++) {
+            if (best) best[q] = sm[q].best;
+            if (n_active) n_active[q] = sm[q].n_active;
+            if (n_low) n_low[q] = sm[q].n_low;
+            if (first_outlier && *first_outlier < 0 && sm[q].outlier) *first_outlier = first + (int)q;
+        }
     }
     return SRUKF_OK;
 }

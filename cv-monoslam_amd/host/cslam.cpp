@@ -1014,7 +1014,8 @@ void CSLAM::SLAM()
 
 // Up to F frames of SLAM() as ONE image block on the device: the association (dataAssociationOnDevice's) and the update run inside the block, the
 // map policy's verdict (updateFeaturesInformation's tests 2443-2459, the addFeatures trigger 556) behind every frame; the block stops at the first frame whose
-// verdict asks for a map change, and that change is made by the unchanged host code on that frame.  gray: F frames of image_h x image_w, frame f for
+// verdict asks for a map change, and that change is made by the unchanged host code on that frame.  With isUseRANSAC the consensus runs inside every frame
+//  and the block also stops IN FRONT OF the first frame whose consensus dropped a match: its rescue step is SLAM()'s.  gray: F frames of image_h x image_w, frame f for
 // m_frame.counter + f.  Returns the frames consumed, or 0 with nothing done where a block cannot stand for SLAM(): the caller then calls SLAM() for the frame.
 int CSLAM::SLAMBlock(const unsigned char* gray, int F)
 {
@@ -1024,7 +1025,7 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     if (c0 + F > m_odoCounter) F = m_odoCounter - c0;
     if (c0 + F > CAPACITY + 1) F = CAPACITY + 1 - c0;
     if (F < 1) return 0;
-    if (m_nAddings != 0 || isAdding || isUseRANSAC || searchArchivedLandmarks || reinsertLoopPoints || dataAssociation || addFeatures) return 0;
+    if (m_nAddings != 0 || isAdding || searchArchivedLandmarks || reinsertLoopPoints || dataAssociation || addFeatures) return 0;
     if (!jointUpdate && m_updateMode != SRUKF_UPDATE_BATCHED) return 0;
     for (int f = 0; f < F; f++) if (m_odoTheta.at(2, c0 + f) == 1) return 0;                                   // a redirection restart inside the range
     const size_t img = (size_t)m_params.image_w * (size_t)m_params.image_h;
@@ -1041,6 +1042,7 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     for (int k = 0; k < N; k++) st[k] = { map[k].nPredictTimes, map[k].nMatchTimes, { map[k].predictLocation.x, map[k].predictLocation.y } };
     const srukf_policy_params pp = { (double)DIST_2_BORDER, 0.01, 10, m_minNUM };
     if (!check(srukf_images_policy(ctx_, 1, &pp)) || !check(srukf_images_set_policy_state(ctx_, st.data()))) return 0;
+    if (!check(srukf_images_ransac(ctx_, isUseRANSAC ? 1 : 0, THRESHOLD_RANSAC))) return 0;                     // the consensus inside every frame, or not
     // 3. one image block in jointUpdate's mode, checked with the switches of associateChecked
     const int mode = jointUpdate ? SRUKF_UPDATE_JOINT : SRUKF_UPDATE_BATCHED;
     const bool checked = rejectAmbiguousMatches || subpixelMatches;
@@ -1050,12 +1052,16 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     rc = run(F);
     if (rc == SRUKF_ERR_CLAMP_PENDING || rc == SRUKF_ERR_UNSUPPORTED) return 0;                                 // a flagged block (its restore has run), the float-stored modes
     if (!check(rc)) return 0;
-    // 4. / 5. the record; a frame in front of the last asks for a map change: back to the block's start and up to that frame
-    int fc = -1, used = F;
+    // 4. / 5. the records; a frame in front of the last asks for a map change, or a frame's consensus dropped a match (that frame needs the rescue: it is not the
+    // block's): back to the block's start and up to the stop
+    int fc = -1, fo = -1, used = F;
     if (!check(srukf_get_image_policy(ctx_, 0, F, nullptr, nullptr, nullptr, &fc))) return 0;
-    if (fc >= 0 && fc < F - 1) {
-        used = fc + 1;
+    if (isUseRANSAC && !check(srukf_get_image_ransac(ctx_, 0, F, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fo))) return 0;
+    if (fc >= 0) used = std::min(used, fc + 1);
+    if (fo >= 0) used = std::min(used, fo);
+    if (used < F) {
         if (!check(srukf_images_rewind(ctx_))) return 0;
+        if (used == 0) return 0;                                                                                // the first frame is SLAM()'s: nothing done
         rc = run(used);
         if (rc == SRUKF_ERR_CLAMP_PENDING) return 0;
         if (!check(rc)) return 0;
@@ -1069,8 +1075,14 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
         if (!check(srukf_get_image_checks(ctx_, 0, used, corr2.data(), z2.data(), fl.data()))) return 0;
     }
     if (!check(srukf_get_image_policy(ctx_, 0, used, nullptr, nullptr, st.data(), nullptr))) return 0;
+    std::vector<int> rfl, ract, rlow;
+    if (isUseRANSAC) {
+        rfl.resize((size_t)used * N); ract.resize(used); rlow.resize(used);
+        if (!check(srukf_get_image_ransac(ctx_, 0, used, rfl.data(), nullptr, nullptr, nullptr, ract.data(), rlow.data(), nullptr))) return 0;
+    }
     const int n = m_X_k.rows;
     m_blockPath.assign(traj.begin(), traj.begin() + 8 * (size_t)used);
+    m_blockLowInliers.assign(used, 0);
     for (int f = 0; f < used; f++) {
         const bool last = f == used - 1;
         m_showCounter++;
@@ -1081,7 +1093,8 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
             const size_t r = (size_t)f * N + k;
             PointsMap& p = map[k];
             p.isVisible = vis[r] != 0; p.isMatching = m[r] != 0;
-            p.inliner_L = p.inliner_H = false;
+            p.inliner_L = isUseRANSAC && ract[f] >= 2 && (rfl[r] & SRUKF_RANSAC_INLIER) != 0;                   // (one match cannot out-vote itself: KalmanUpdate's m_nMatches < 2 branch)
+            p.inliner_H = false;
             if (p.isVisible) m_nPredicts++;
             if (p.isMatching) { p.matchLocation.x = z[2 * r]; p.matchLocation.y = z[2 * r + 1]; m_nMatches++; }
             if (checked) {
@@ -1091,6 +1104,8 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
             if (last) { p.nPredictTimes = st[k].nPredictTimes; p.nMatchTimes = st[k].nMatchTimes; p.predictLocation.x = st[k].predictLocation[0]; p.predictLocation.y = st[k].predictLocation[1]; }
         }
         m_nAmbiguousTotal += m_nAmbiguous;
+        if (isUseRANSAC && ract[f] >= 2) m_nLowInliers = rlow[f];
+        m_blockLowInliers[f] = m_nLowInliers;
         m_frame.index = (int)m_odoTheta.at(0, m_frame.counter);
         if (!last) {
             const double* t = &traj[8 * (size_t)f];                                                              // pose + the 2 x 2 block of P, as the trajectory holds them

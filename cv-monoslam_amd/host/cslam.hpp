@@ -105,10 +105,15 @@ public:
     // m_nMatches, m_path and the RobotPath row from the trajectory; PointsMap::Si is not refreshed) and SLAM()'s own tail — updateFeaturesInformation,
     // the mirrors, addFeatures on the device — on the last consumed frame, which m_gryImage then points at.  Returns the frames consumed (m_frame.counter has
     // advanced by as many).  Returns 0 with nothing done — call SLAM() for the frame instead — with an empty map, a redirection flag inside the range,
-    // m_nAddings != 0 (the next update reorders), isAdding, isUseRANSAC, searchArchivedLandmarks, reinsertLoopPoints, a dataAssociation or addFeatures callback
-    // installed, an update mode the image runs do not have, float storage, and for a flagged block (srukf_synchronize has restored it)
+    // m_nAddings != 0 (the next update reorders), isAdding, searchArchivedLandmarks, reinsertLoopPoints, a dataAssociation or addFeatures callback
+    // installed, an update mode the image runs do not have, float storage, and for a flagged block (srukf_synchronize has restored it).
+    // isUseRANSAC: the 1-point RANSAC consensus runs inside every frame of the block (srukf_images_ransac with THRESHOLD_RANSAC) and the block also
+    // ends IN FRONT OF the first frame whose consensus dropped a match: that frame needs the rescue step (rescueHighInnovationInliers), which only SLAM() has, so
+    // it is not consumed — the next call returns 0 for it and the caller's SLAM() runs it.  Consumed frames: inliner_L and m_nLowInliers from the consensus record,
+    // m_nHighInliers = 0
     int  SLAMBlock(const unsigned char* gray, int F);
     std::vector<double> m_blockPath;                           // the last SLAMBlock's RobotPath numbers, 8 per consumed frame: x, y, z, theta, P00, P01, P10, P11
+    std::vector<int> m_blockLowInliers;                        // ... and with isUseRANSAC its m_nLowInliers per consumed frame
     void predictMotion();                                      // SLAM.cpp:1343-1466 (numeric tail 1430-1465)
     void predictMeasurement();                                 // SLAM.cpp:1604-1608
     void KalmanUpdate();                                       // SLAM.cpp:2048-2104

@@ -26,6 +26,9 @@
 //              policy=1 (assoc_replay only): the map policy's verdict behind every frame (srukf_images_policy with the default parameters); the
 //              record's summaries are read after every block (srukf_get_image_policy).  The bench's map never changes: a block is not cut at first_change.  Adds
 //              "policy": {change_frames, deletes, need_add_frames} to the output
+//              ransac=<threshold> (assoc_replay): the 1-point RANSAC consensus inside every frame (srukf_images_ransac; threshold in pixels, 8 is the
+//              reference's); the record's summaries are read after every block (srukf_get_image_ransac).  The bench runs no rescue: a block is not cut at
+//              first_outlier.  A restored block runs srukf_ransac_consensus step-wise.  Adds "ransac": {threshold, outlier_frames, low_inliers} to the output
 //              profile=1 (assoc_replay only): the timed blocks run with srukf_set_profiling on (eager launches); adds "profile_ms_per_frame" by kernel class
 //     hint=1 : capi / assoc announce the NEXT frame's odometry with srukf_predict_motion_next before every update (a host that has its odometry
 //              file loaded, as the reference has: loadOdometryData reads it whole, SLAM.cpp:363-496)
@@ -68,6 +71,7 @@ int main(int argc, char** argv)
     int arcL = 0, arc_step = 0, profile = 0; srukf_archive_params apar = { 40, 0.8, 5.99146454710798 };      // archive= / archive_step= / profile= (assoc_replay)
     long long arc_hits = 0;
     int policy = 0; long long pol_change = 0, pol_deletes = 0, pol_adds = 0;      // policy= (assoc_replay)
+    double ransac_thr = 0.0; long long rs_outlier = 0, rs_low = 0;      // ransac=<threshold> (assoc_replay)
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -75,7 +79,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "warmup=", 7)) W = atoi(argv[a] + 7);
         else if (!strncmp(argv[a], "hint=", 5)) hint = atoi(argv[a] + 5);
         else if (!strncmp(argv[a], "churn=", 6)) churn = atoi(argv[a] + 6);
-        else if (!strncmp(argv[a], "ransac=", 7)) ransac = atoi(argv[a] + 7);
+        else if (!strncmp(argv[a], "ransac=", 7)) { ransac = atoi(argv[a] + 7); ransac_thr = atof(argv[a] + 7); }
         else if (!strncmp(argv[a], "ellipsoids=", 11)) ellipsoids = atoi(argv[a] + 11);
         else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "block=", 6)) block_frames = atoi(argv[a] + 6);
@@ -114,7 +118,7 @@ int main(int argc, char** argv)
     long long flag_ticks = -1;                                       // last frame: start of the frame's first launch -> h / Si / visible flagged to the host (10 ns ticks)
     char churn_json[900] = "";
     char ell_json[200] = "";
-    char prof_json[1600] = "", arc_json[200] = "", pol_json[160] = "";
+    char prof_json[1600] = "", arc_json[200] = "", pol_json[360] = "";
     int joint_flagged = 0;
     const char* replay_form = "run_frames_async + synchronize";
     int flagged_blocks = 0;
@@ -336,6 +340,8 @@ int main(int argc, char** argv)
                 if (!arc_step) CK(srukf_images_search_archive(c, 1, &apar));
             }
             if (policy) CK(srukf_images_policy(c, 1, nullptr));
+            if (ransac_thr > 0.0) CK(srukf_images_ransac(c, 1, ransac_thr));
+            std::vector<int> rlow(block_frames), ract(block_frames), rinl(N);
             std::vector<srukf_policy_summary> prow(block_frames);
             std::vector<int> mrow((size_t)block_frames * N), frow(checked ? (size_t)block_frames * N : 0), fl(checked ? N : 0), hrow(block_frames), am(arcL);
             auto run = [&](int first, int end, bool timed) -> int {
@@ -355,6 +361,14 @@ int main(int argc, char** argv)
                                 if (timed) for (int k = 0; k < N; k++) { ambiguous += (fl[k] >> 1) & 1; refined += (fl[k] >> 2) & 1; }
                             } else
                             CK(srukf_associate(c, gray.data(), zc.data(), md.data(), corr.data()));
+                            if (ransac_thr > 0.0) {              // (the consensus step-wise: the update takes matched & inlier, as the frames of a block do)
+                                int na = 0; for (int k = 0; k < N; k++) na += (md[k] != 0 && vis[k] != 0) ? 1 : 0;
+                                if (na >= 2) {
+                                    CK(srukf_ransac_consensus(c, zc.data(), md.data(), ransac_thr, rinl.data(), nullptr, nullptr, nullptr));
+                                    int nl = 0; for (int k = 0; k < N; k++) { md[k] = (md[k] != 0 && rinl[k] != 0) ? 1 : 0; nl += md[k]; }
+                                    if (timed) { rs_low += nl; rs_outlier += nl < na ? 1 : 0; }
+                                }
+                            }
                             if (timed) for (int k = 0; k < N; k++) matches_dev += md[k];
                             if (joint) CK(srukf_update_joint(c, zc.data(), md.data(), SRUKF_NEEDNOT_REORDER));
                             else CK(srukf_update(c, zc.data(), md.data(), SRUKF_NEEDNOT_REORDER, SRUKF_UPDATE_BATCHED));
@@ -376,6 +390,11 @@ int main(int argc, char** argv)
                             int fc = -1;
                             CK(srukf_get_image_policy(c, b, cnt, nullptr, prow.data(), nullptr, &fc));
                             for (int q = 0; q < cnt; q++) { pol_change += prow[q].change; pol_deletes += prow[q].n_deletes; pol_adds += prow[q].need_add; }
+                        }
+                        if (ransac_thr > 0.0) {                  // "which frame needs the rescue?": cnt summaries
+                            int fo = -1;
+                            CK(srukf_get_image_ransac(c, b, cnt, nullptr, nullptr, nullptr, nullptr, ract.data(), rlow.data(), &fo));
+                            for (int q = 0; q < cnt; q++) if (ract[q] >= 2) { rs_low += rlow[q]; rs_outlier += rlow[q] < ract[q] ? 1 : 0; }
                         }
                         if (arcL && !arc_step) {                 // "did anything come back?": cnt ints
                             CK(srukf_get_image_archive(c, b, cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hrow.data()));
@@ -435,6 +454,8 @@ int main(int argc, char** argv)
     if (arcL) snprintf(arc_json, sizeof arc_json, "\"archive\": {\"records\": %d, \"half_cap\": %d, \"route\": \"%s\", \"matched_records\": %lld}, ", arcL, apar.half_cap,
                        arc_step ? "srukf_archive_search after every block" : "srukf_images_search_archive", arc_hits);
     if (policy) snprintf(pol_json, sizeof pol_json, "\"policy\": {\"change_frames\": %lld, \"deletes\": %lld, \"need_add_frames\": %lld}, ", pol_change, pol_deletes, pol_adds);
+    if (areplay && ransac_thr > 0.0) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"ransac\": {\"threshold\": %.6g, \"outlier_frames\": %lld, \"low_inliers\": %lld}, ",
+                                              ransac_thr, rs_outlier, rs_low);
     if (mode == "replay") snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"replay_form\": \"%s\", \"exact_frames\": %d, ", replay_form, joint_flagged);
     printf("{\"mode\": \"%s\", %s%s%s%s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
            "\"pose\": [%.17g, %.17g, %.17g, %.17g], \"P_robot\": [%.17g, %.17g, %.17g, %.17g], \"device_matches\": %lld, \"stats_flag_us_into_first_launch\": %.2f, \"host_us_per_call\": {\"predict_motion\": %.2f, \"predict_measurement\": %.2f, \"association\": %.2f, \"update\": %.2f, \"get_robot\": %.2f}, "

@@ -26,7 +26,9 @@
 // block=<F>: frames run through CSLAM::SLAMBlock, up to F at a time, with SLAM() for every frame a block cannot stand for (the first, a frame
 //   behind an addition, a restart, a flagged block); frames.bin is then not wrapped round: at most its F frames run.  Adds, and only when given (block=1 too: the
 //   step-wise route with the same lines), per frame a "policy" line (frame, the IDs updateFeaturesInformation deleted, landmarks added) and a "path" line (frame, pose and
-//   the 2 x 2 position block of P, %.17g), and at the end "blocks <n> early <n> full <n> fallback <n>".  Without it nothing changes.
+//   the 2 x 2 position block of P, %.17g), and at the end "blocks <n> early <n> full <n> fallback <n>".  Without it nothing changes.  With ransac=<threshold> the
+//   consensus runs inside the blocks and every frame's "ransac" line follows its "path" line, the same through either route; a block ends in
+//   front of a frame whose consensus dropped a match, and SLAM() runs that frame with its rescue (a fallback).
 // min_matches=<n>: CSLAM::m_minNUM = n (addFeatures when fewer landmarks matched, SLAM.cpp:179, 556; default 5).
 // warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
 // Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
@@ -94,7 +96,7 @@ int main(int argc, char** argv)
     double addWall = -1.0;
     if (block > 0) {
         // the block-wise loop: SLAMBlock where it can stand for SLAM(), SLAM() with the association installed for the frame otherwise
-        if (block > 1 && (colour || loops || ransac || archiveCap > 0)) { fprintf(stderr, "block=<F> runs without colour=, loops, archive= and ransac=\n"); return 2; }
+        if (block > 1 && (colour || loops || archiveCap > 0)) { fprintf(stderr, "block=<F> runs without colour=, loops and archive=\n"); return 2; }
         if (steps > F) steps = F;
         const auto assoc = SLAM.dataAssociation;
         auto report = [&](int fr, int nBefore) {
@@ -105,6 +107,7 @@ int main(int argc, char** argv)
             const int n = SLAM.m_X_k.rows;
             printf("path %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", fr, SLAM.m_X_k.at(n - 4, 0), SLAM.m_X_k.at(n - 3, 0), SLAM.m_X_k.at(n - 2, 0), SLAM.m_X_k.at(n - 1, 0),
                    SLAM.m_P_k.at(n - 4, n - 4), SLAM.m_P_k.at(n - 4, n - 3), SLAM.m_P_k.at(n - 3, n - 4), SLAM.m_P_k.at(n - 3, n - 3));
+            if (ransac) printf("ransac low %d high %d\n", SLAM.m_nLowInliers, SLAM.m_nHighInliers);
         };
         double wall = 0.0;
         for (int fr = 0; fr < steps;) {
@@ -119,6 +122,7 @@ int main(int argc, char** argv)
                     const double* t = &SLAM.m_blockPath[8 * (size_t)q];
                     printf("policy frame %d deleted 0 added 0\n", fr + q);
                     printf("path %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", fr + q, t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
+                    if (ransac) printf("ransac low %d high 0\n", SLAM.m_blockLowInliers[q]);
                 }
                 report(fr + used - 1, nBefore);
                 fr += used;

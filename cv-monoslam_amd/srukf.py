@@ -35,6 +35,7 @@ EXPORTS = [
     "srukf_run_images_checked_async", "srukf_run_images_checked", "srukf_get_image_checks",
     "srukf_images_search_archive", "srukf_get_image_archive",
     "srukf_map_policy", "srukf_images_policy", "srukf_images_set_policy_state", "srukf_get_image_policy", "srukf_images_rewind",
+    "srukf_images_ransac", "srukf_get_image_ransac",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -200,6 +201,9 @@ def load_library(path=None):
         L.srukf_images_set_policy_state.argtypes = [C.c_void_p, C.c_void_p]
         L.srukf_get_image_policy.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, C.c_void_p, C.c_void_p, _ip]
         L.srukf_images_rewind.argtypes = [C.c_void_p]
+    if hasattr(L, "srukf_images_ransac"):              # (idem: the 1-point RANSAC consensus inside image frames)
+        L.srukf_images_ransac.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.srukf_get_image_ransac.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _ip, _ip]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -798,6 +802,31 @@ class Filter:
         """Puts back the checkpoint of the image block the last synchronize ended clean: X, S, every matchPatch and the policy state (srukf_images_rewind).
         SrukfError(SRUKF_ERR_SEQUENCE) when a run is pending, no image block has been synchronised, or the state has been written since."""
         self._chk(self._lib.srukf_images_rewind(self._h))
+
+    # ---- the 1-point RANSAC consensus inside image frames (srukf_images_ransac; DESIGN.md section 24) ----
+    def images_ransac(self, on, threshold=8.0):
+        """The switch of the consensus inside image frames (srukf_images_ransac): while on, every frame of every later run_images* / run_images_checked* runs
+        ransac_consensus' kernels between its association and its update, and the update uses the consensus set only (the frame's `matched` row is rewritten to it);
+        get_image_ransac has the per-frame record.  threshold: pixels, finite and positive.  Not while a run is in flight (SRUKF_ERR_SEQUENCE)."""
+        if not isinstance(on, (bool, np.bool_)) and not (isinstance(on, (int, np.integer)) and on in (0, 1)):
+            raise TypeError("images_ransac: on must be a bool")
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)):
+            raise TypeError("images_ransac: threshold must be a real number")
+        self._chk(self._lib.srukf_images_ransac(self._h, int(bool(on)), float(threshold)))
+
+    def get_image_ransac(self, first, count):
+        """What the consensus wrote for staged frames [first, first + count) (srukf_get_image_ransac): dict of flags[count, N] (bit 0: matched and visible, bit 1:
+        low-innovation inlier), votes[count, N], dist[count, N], best[count], n_active[count], n_low[count] and first_outlier (the lowest frame whose consensus
+        dropped a match, or -1).  Rows no such frame wrote are zero."""
+        self._image_run_args(first, count, UPDATE_BATCHED)
+        N = self.N
+        out = dict(flags=np.zeros((count, N), dtype=np.int32), votes=np.zeros((count, N), dtype=np.int32), dist=np.zeros((count, N)),
+                   best=np.zeros(count, dtype=np.int32), n_active=np.zeros(count, dtype=np.int32), n_low=np.zeros(count, dtype=np.int32))
+        fo = C.c_int(-1)
+        self._chk(self._lib.srukf_get_image_ransac(self._h, int(first), int(count), _i(out["flags"]), _i(out["votes"]), _d(out["dist"]), _i(out["best"]),
+                                                   _i(out["n_active"]), _i(out["n_low"]), C.byref(fo)))
+        out["first_outlier"] = int(fo.value)
+        return out
 
     def synchronize(self):
         self._chk(self._lib.srukf_synchronize(self._h))

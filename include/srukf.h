@@ -612,6 +612,33 @@ int  srukf_images_set_policy_state(srukf_ctx* ctx, const srukf_policy_state* sta
 int  srukf_get_image_policy(srukf_ctx* ctx, int first, int count, int* verdict, srukf_policy_summary* summary, srukf_policy_state* state_out, int* first_change);
 int  srukf_images_rewind(srukf_ctx* ctx);
 
+/* ---- 1-point RANSAC consensus inside the frames of an image run ----
+ * srukf_images_ransac: a switch on the handle, like srukf_images_policy: it survives map changes and srukf_reset (which drop the record with the staged
+ *   images); srukf_destroy ends it.  threshold: srukf_ransac_consensus' pixel distance (8 is the reference's constant); with `on` != 0 it must be finite and
+ *   positive (SRUKF_ERR_BAD_ARG); not while a run is in flight (SRUKF_ERR_SEQUENCE).  The call touches no device.  While on, every frame of every later image run
+ *   (srukf_run_images* and srukf_run_images_checked*, BATCHED and JOINT, with the archive search and / or the map policy behind them) runs srukf_ransac_consensus'
+ *   two kernels between its association and its update, on the operands the frame holds at that point (S^T DZ, the robot rows of the cross covariances, h, Si,
+ *   visible, the predicted X; this frame's rows of the association's record): A = { k : matched and visible }, every member a hypothesis, the one with the most
+ *   votes wins (lowest index among equals).  The frame's `matched` row is then REWRITTEN to the winner's consensus set and the update uses that set only;
+ *   srukf_get_image_matches and the map policy therefore see what the filter used (z is left as the association wrote it).  With fewer than two members of A
+ *   nothing is rewritten (one match cannot out-vote itself).  There is no rescue step on the device: a frame whose consensus dropped a match is marked
+ *   `outlier`, and a host that wants the rescue (srukf_repredict_measurement, the chi-square test, a second update) ends its block in front of that frame
+ *   (srukf_images_rewind, the frames up to it again) and runs it step-wise.  Such frames are captured frames of their own per kind of image run and update mode
+ *   (a run never replays a frame captured the other way); the threshold lives in a device struct written in stream order in front of each run, so changing it
+ *   needs no recapture.  With the switch off an image run is exactly what it was.
+ * srukf_get_image_ransac: rows [first, first + count) of the consensus record, after waiting for the stream like srukf_get_image_matches.  flags[count][N]: bit 0
+ *   (SRUKF_RANSAC_ACTIVE) the landmark was in A, bit 1 (SRUKF_RANSAC_INLIER) a low-innovation inlier; votes[count][N] and dist[count][N] as
+ *   srukf_ransac_consensus returns them (votes of every member of A; the distances under the winner); best / n_active / n_low [count]; *first_outlier: the lowest
+ *   frame of the range with n_active >= 2 && n_low < n_active, or -1.  A frame with n_active < 2: inlier = active, votes 0, dist 0, best -1, n_low = n_active.
+ *   Any pointer may be NULL.  Rows no such frame has written are zero, and so are all rows after a flagged block's restore or srukf_images_rewind (their frames'
+ *   results do not stand: first_outlier -1) until frames run again.  SRUKF_ERR_SEQUENCE: no images staged, or no run with the switch on since they were;
+ *   SRUKF_ERR_DIM_MISMATCH: rows outside the staged stack.
+ * Both: SRUKF_ERR_BAD_ARG for a NULL handle (srukf_get_image_ransac: first < 0, count < 1) before any device is touched. */
+#define SRUKF_RANSAC_ACTIVE 1
+#define SRUKF_RANSAC_INLIER 2
+int  srukf_images_ransac(srukf_ctx* ctx, int on, double threshold);
+int  srukf_get_image_ransac(srukf_ctx* ctx, int first, int count, int* flags, int* votes, double* dist, int* best, int* n_active, int* n_low, int* first_outlier);
+
 /* ---- instrumentation ------------------------------------------------------------------------ */
 
 /* When on, every kernel launch is bracketed by HIP events on the context's stream and the
