@@ -1,7 +1,7 @@
 // srukf_api.hip — C-ABI (include/srukf.h) over the gfx950 kernels: context lifetime and HBM buffers, state accessors, storage, profiling read-out (the step-wise
 // calls of a frame — predictMotion / predictMeasurement / KalmanUpdate, SLAM.cpp:87-112 — and their fast path: srukf_step.hip).  No CPU fallback: every numeric
 // result is produced by the kernels in srukf_predict.hip / srukf_factor.hip / srukf_gmw_persist.hip / srukf_rank.hip.  The launch sequences of a frame and the
-// staged replay are in srukf_replay.hip, the batched replay in srukf_batch.hip, map changes and data association in srukf_map.hip, the split form's plumbing in
+// staged replay are in srukf_replay.hip, its image runs in srukf_images.hip, the batched replay in srukf_batch.hip, map changes and data association in srukf_map.hip, the split form's plumbing in
 // srukf_split.hip, the debug hooks in srukf_debug.hip (round 4 had all of it in this file).
 
 #include "srukf_ctx.h"
@@ -382,6 +382,7 @@ static void map_scope_free(srukf_map_scope& m, hipStream_t st)
 {
     drop_graphs(&m);
     m.each_device_buffer([st](void* b) { if (b) srukf_dfree_on(b, st); });
+    images_drop(&m, st);
     ransac_scratch_free(m.ransac, st);
     gmw_plan_destroy(m.gplan, st);
     gmw_plan_destroy(m.gplan_red, st);
@@ -512,7 +513,7 @@ int srukf_reset(srukf_ctx* c)
     hs[0] = c->p.sigma_x; hs[1] = c->p.sigma_y; hs[2] = c->p.sigma_z; hs[3] = c->p.sigma_theta;
     for (int e = 0; e < 4; e++)
         HIPCHK(c, hipMemcpyAsync(c->S + (size_t)(d.n - 4 + e) * np + (d.n - 4 + e), hs + e, sizeof(double), hipMemcpyHostToDevice, c->stream));
-    launch_set_frame(c->stream, c->fs, 0, 1);
+    launch_set_run(c->stream, c->fs, 0, 1, nullptr);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->phase = 0; c->async_pending = false;
     c->frame_valid = false; c->bgr_valid = false;                // (the held frame goes with the state, gray and colour)

@@ -1,7 +1,9 @@
 // srukf_ctx.h — what the host-side translation units of libsrukf_hip.so share: the context (struct srukf_ctx), the helpers behind the C-ABI.  Internal:
 // include/srukf.h is the boundary.  What the kernel files offer (launchers, size / table helpers, their argument structs) comes from srukf_launch.h, declared there only.
 //   srukf_api.hip     context lifetime, state accessors, the step-wise calls (predictMotion / predictMeasurement / KalmanUpdate), storage, profiling read-out
-//   srukf_replay.hip  the launch sequences of a frame (seq_*), the rank-aware null set, graph cache, staged replay (srukf_run_frames*, srukf_run_images*)
+//   srukf_replay.hip  the launch sequences of a frame (seq_*), the rank-aware null set, graph cache, staged replay (srukf_run_frames*)
+//   srukf_images.hip  image runs of the staged replay: the association (checked or not), the consensus and the archive search inside captured frames (srukf_stage_images,
+//                     srukf_run_images*, srukf_get_image_*, srukf_images_*)
 //   srukf_split.hip   split form of the persistent factorisation: side stream, probe, buffers
 //   srukf_batch.hip   batched replay (srukf_run_frames_batch)
 //   srukf_map.hip     map changes (srukf_add_landmarks / srukf_delete_landmark / srukf_insert_landmarks) and data association
@@ -9,10 +11,10 @@
 //   srukf_overlay.hip colour-frame intake (srukf_set_frame_bgr) and the 2-D feature overlay (srukf_render_overlay)
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search), step-wise and behind the frames of an image run
-//                     (srukf_images_search_archive: seq_archive_search, k_archive_search_staged; srukf_get_image_archive: srukf_replay.hip)
-//   srukf_policy.hip  the map policy's verdict (srukf_map_policy; srukf_images_policy: k_map_policy_staged behind the frames of an image run, issued by srukf_replay.hip)
-//   srukf_joint.hip   the joint measurement update's kernels (srukf_update_joint, SRUKF_UPDATE_JOINT frames of the staged replay; host code: srukf_step.hip, srukf_replay.hip)
-//   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip; srukf_run_images_checked*: srukf_replay.hip)
+//                     (srukf_images_search_archive: seq_archive_search, k_archive_search_staged; srukf_get_image_archive: srukf_images.hip)
+//   srukf_policy.hip  the map policy's verdict (srukf_map_policy; srukf_images_policy: k_map_policy_staged behind the frames of an image run, issued by srukf_images.hip)
+//   srukf_joint.hip   the joint measurement update's kernels (srukf_update_joint, SRUKF_UPDATE_JOINT frames of the staged replay; host code: srukf_step.hip, srukf_replay.hip, srukf_images.hip)
+//   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip; srukf_run_images_checked*: srukf_images.hip)
 //   srukf_patch.h     (through srukf_launch.h) the appearance record's sizes, the checked association's buffer layouts, the search kernels' shared front
 //   srukf_debug.hip   srukf_debug_*, stand-alone primitives for the parity tests
 //   srukf_switches.h  where the switches of srukf_debug_set are stored: the process-wide struct g_sw, the per-filter DbgSwitches
@@ -28,6 +30,7 @@
 #include <algorithm>
 #include <utility>
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <map>
 #include "srukf_launch.h"
@@ -87,31 +90,31 @@ struct ArchiveState {
 // image runs of the staged replay (srukf_stage_images / srukf_run_images*): the staged gray frames [frames][image_h][image_w], the per-frame
 // record the association leaves beside the staged z_seq / m_seq rows it overwrites (corr_seq [F][N], vis_seq [F][N], h_seq [F][2N]), the Cartesian points the warp
 // reads (xyz, 3N: not c->G — nothing has shown G to be free inside a replayed block), and the block's checkpoint: X, S, the matchPatch array and whether the null rows
-// were canonical.  pending: the frames srukf_synchronize waits for are image frames (a flagged block comes back to the checkpoint there).  Captured frames of their own
-// per update mode.  Map-size scope, the staged sequence's lifetime: images_drop
-// Checked image runs (srukf_run_images_checked*), allocated by images_checked_ensure on the first one: the checked record corr2_seq [F][N],
-// z2_seq [F][2N], flags_seq [F][N] (zero until a checked run writes a row), the parameters the checked frames read (match_args, written in stream order in front of every
-// checked run) and captured frames of their own per update mode (chk_graphs: never the plain image run's, nor the other way round; they hold the pointer of the
-// filter's score buffer they were captured with, chk_scores).  checked: the block in flight holds a checked run (a flagged block then leaves no valid score map)
+// were canonical.  pending: the frames srukf_synchronize waits for are image frames (a flagged block comes back to the checkpoint there).  Map-size scope, the staged
+// sequence's lifetime: images_drop.
+// graphs: the captured frames (one and eight) of every form of an image frame and update mode, ONE table: graphs[ImageForm::index()][0 BATCHED / 1 JOINT].  A form
+// never replays a frame captured for another one (nor a frame of srukf_run_frames*, nor the other way round): the index is the guarantee.  drop_graphs walks the table.
+// The device buffers come in five groups, each named once (image_group, srukf_images.hip): allocation, images_drop and images_archive_drop all go through those lists
 struct ImageReplay {
     unsigned char *images = nullptr, *ck_tmpl = nullptr;
     double *corr_seq = nullptr, *h_seq = nullptr, *xyz = nullptr, *ckS = nullptr, *ckX = nullptr;
     int* vis_seq = nullptr;
     int frames = 0;
     bool pending = false, ck_canon = false;
-    ReplayGraphs graphs[2];
+    ReplayGraphs graphs[8][2];
+    // Checked image runs (srukf_run_images_checked*), allocated by images_checked_ensure on the first one: the checked record corr2_seq [F][N],
+    // z2_seq [F][2N], flags_seq [F][N] (zero until a checked run writes a row) and the parameters the checked frames read (match_args, written in stream order in front
+    // of every checked run).  The captured checked frames hold the pointer of the filter's score buffer they were captured with, chk_scores.  checked: the block in
+    // flight holds a checked run (a flagged block then leaves no valid score map)
     double *corr2_seq = nullptr, *z2_seq = nullptr; int* flags_seq = nullptr;
     MatchArgs* match_args = nullptr; const double* chk_scores = nullptr;
     bool checked = false;
-    ReplayGraphs chk_graphs[2];
     // Searching image runs (srukf_images_search_archive), allocated by images_archive_ensure in front of the first one: the per-frame record of
-    // the archive search (ar_rec: ImageArchiveRecord for frames x ar_L, zero until a searching run writes a row), the parameters the searching frames read (ar_args,
-    // written in stream order in front of every searching run) and captured frames of their own per kind of image run and update mode (ar_graphs[checked][mode]: a
-    // searching run never replays a frame captured without the search, nor the other way round; they hold the archive's pointers and L workgroups: images_archive_drop).
+    // the archive search (ar_rec: ImageArchiveRecord for frames x ar_L, zero until a searching run writes a row) and the parameters the searching frames read (ar_args,
+    // written in stream order in front of every searching run).  The captured searching frames hold the archive's pointers and L workgroups: images_archive_drop.
     // ar_valid: a searching run has written the record and no flagged block has been restored since; searching: the block in flight holds a searching run
     double* ar_rec = nullptr; ArchiveArgs* ar_args = nullptr; int ar_L = 0;
     bool ar_valid = false, searching = false;
-    ReplayGraphs ar_graphs[2][2];
     // The map policy behind image frames (srukf_images_policy), allocated by images_policy_ensure (the first policy run, or
     // srukf_images_set_policy_state): the per-landmark state (pol_state [N]) and its copy in the block's checkpoint (pol_ck [N]: saved and restored with X, S and the
     // matchPatch array), the record (pol_verdict [frames][N], pol_sum [frames], zero until a policy run writes a row) and the parameters the launches read (pol_args,
@@ -123,11 +126,10 @@ struct ImageReplay {
     // The 1-point RANSAC consensus inside image frames (srukf_images_ransac), allocated by images_ransac_ensure in front of the first run with
     // the switch on: the scratch of the two launches (rs_D [N][N], rs_F [N][N] bytes, rs_votes [N]), the record (rs_flags / rs_rvotes / rs_dist [frames][N], rs_sum
     // [frames], zero until such a frame writes a row, zeroed again by images_restore) and the threshold the launches read (rs_args, written in stream order in front
-    // of every such run).  rs_valid: such a run has written the record.  Captured frames of their own per kind of image run and update mode (rs_graphs)
+    // of every such run).  rs_valid: such a run has written the record
     double *rs_D = nullptr, *rs_dist = nullptr; unsigned char* rs_F = nullptr; int *rs_votes = nullptr, *rs_flags = nullptr, *rs_rvotes = nullptr;
     RansacSummary* rs_sum = nullptr; RansacArgs* rs_args = nullptr;
     bool rs_valid = false;
-    ReplayGraphs rs_graphs[2][2][2];       // [searching][checked][mode]: the frames with the consensus in them
 };
 
 // ---- the context: who owns what across a map change ("who owns what across a map change") ----------------------
@@ -334,7 +336,8 @@ struct srukf_map_scope : srukf_life {
     // one mode never replays the other's launch sequence; drop_graphs drops both
     ReplayGraphs graphs[2];
     ImageReplay img;                       // srukf_stage_images / srukf_run_images* (captured frames with the association in them: never the ones above, nor the other way round)
-    // the pool allocations among the members above (Si and vis are inside h, mcur inside zcur; ransac, gplan, gplan_red: ransac_scratch_free / gmw_plan_destroy).
+    // the pool allocations among the members above (Si and vis are inside h, mcur inside zcur; ransac, gplan, gplan_red, img: ransac_scratch_free / gmw_plan_destroy /
+    // images_drop).
     // A new buffer of this scope is added HERE
     template <class F> void each_device_buffer(F f) const {
         void* b[] = { X, S, G, Gbak, Wf, sigR, Cmat, Z, DZ, Ut, h, PxyR, D, zcur, odocur, small, mpart, dxp, theta, fold_sync, dxk,
@@ -342,11 +345,7 @@ struct srukf_map_scope : srukf_life {
                       S32, X32, U32, mx_part, mx_tasks, mx_tiles, A32, mxr_part, mxr_tasks, mxr_tiles, mxr_f64_tiles, mxr_xt,
                       perm, iperm, Sdis, pan[0], pan[1], red_perm, red_iperm, gdiag, shadowA, Utp, slabW, slabL, gsW, gsL, P1, pxy2_tiles, nskip,
                       red_head0_tiles, split_fold_list, red_syrk_tiles, ckS, ckX, syrk_tiles, pxy_tiles, syrk_head_tiles, syrk_head_tiles_b, fs,
-                      odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt, jointZd, jointW, jointRd,
-                      img.images, img.ck_tmpl, img.corr_seq, img.h_seq, img.xyz, img.ckS, img.ckX, img.vis_seq,
-                      img.corr2_seq, img.z2_seq, img.flags_seq, img.match_args, img.ar_rec, img.ar_args,
-                      img.pol_state, img.pol_ck, img.pol_verdict, img.pol_sum, img.pol_args,
-                      img.rs_D, img.rs_dist, img.rs_F, img.rs_votes, img.rs_flags, img.rs_rvotes, img.rs_sum, img.rs_args };
+                      odo_seq, z_seq, m_seq, odo_step, ckS2, ckX2, export_cnt, jointZd, jointW, jointRd };
         for (void* q : b) f(q);
     }
 };
@@ -379,8 +378,8 @@ hipError_t srukf_dfree_on(void* p, hipStream_t st);
 
 // ---- small kernels of the host layer behind launchers (srukf_replay.hip) ----
 void launch_refactor_reset(hipStream_t st, int np, unsigned long long* theta_bits, FrameScalars* fs, int reset_stats);
-void launch_set_frame(hipStream_t st, FrameScalars* fs, int frame, int clear_clamp);
-void launch_set_run(hipStream_t st, FrameScalars* fs, int frame, int clear_clamp, double* traj_base);
+void launch_set_seq(hipStream_t st, FrameScalars* fs, const double* odo_seq, int seqF, const srukf_params& p);
+void launch_set_run(hipStream_t st, FrameScalars* fs, int frame, int clear_clamp, double* traj_base);      // traj_base null: a frame outside a staged run
 void launch_set_step(hipStream_t st, FrameScalars* fs, double* odo, int seqF, double a1, double a2, double a3, double a4, int fresh, const double poses[9]);
 // device -> pinned host memory, two segments of 8-byte words; flag (pinned too, may be null) receives seq behind the data
 void launch_export(hipStream_t st, const void* a, size_t bytes_a, const void* b, size_t bytes_b, void* host_pinned, unsigned long long* flag = nullptr, unsigned long long seq = 0);
@@ -471,6 +470,16 @@ struct FrameForm {
     bool fused_tail() const { return meas >= MEAS_FUSED_TAIL; }
 };
 constexpr FrameForm FORM_SEPARATE_STATS{ MEAS_SEPARATE_STATS, false }, FORM_PLAIN{ MEAS_PLAIN, false }, FORM_FUSED_TAIL{ MEAS_FUSED_TAIL, true };
+// What a frame of an image run holds beyond the plain frame form (replay_one_image_frame): checked — k_associate_checked_staged in k_associate_staged's place;
+// search — the archive search behind its tail; ransac — the consensus between association and update.  index(): the form's row of ImageReplay::graphs.
+// The map policy is no part of the form: it has no captured frames of its own, it is an eager launch behind each frame and a property of the run (run_images_issue)
+struct ImageForm {
+    bool checked, search, ransac;
+    int index() const { return (checked ? 1 : 0) | (search ? 2 : 0) | (ransac ? 4 : 0); }
+    static ImageForm at(int index) { return ImageForm{ (index & 1) != 0, (index & 2) != 0, (index & 4) != 0 }; }
+};
+constexpr int IMAGE_FORMS = 8;
+static_assert(sizeof(ImageReplay::graphs) / sizeof(ImageReplay::graphs[0]) == IMAGE_FORMS, "ImageReplay::graphs has one row per form of an image frame");
 // What is asked of a refactorisation  S <- gmw(S^T S - U[ub:ue] U[ub:ue]^T):  the tail of a staged or fast-path frame (no backup, the last launch ends the frame) /
 // checked (G kept in Gbak, the host reads clamp_rows afterwards) / one column of SEQUENTIAL mode (as checked, behind a reset of the gamma / xi accumulators)
 struct RefactorRequest { enum Kind { FRAME_TAIL, CHECKED, SEQ_COLUMN } kind; int ub, ue; };
@@ -525,14 +534,26 @@ void seq_joint_launches(srukf_ctx* c, const double* z_dev, const int* m_dev);
 int update_null_set(srukf_ctx* c);
 int mixed_red_ensure(srukf_ctx* c);
 void drop_graphs(srukf_map_scope* c);
-void images_archive_drop(srukf_map_scope* c, hipStream_t st);      // the searching image runs' record, parameters and captured frames go (the archive changes; the caller has synchronised the stream)
-void images_drop(srukf_map_scope* c, hipStream_t st);      // the staged images, their record, checkpoint and captured frames go (the caller has synchronised the stream)
+void graphs_destroy(ReplayGraphs& g);                  // one set of captured frames goes (one, eight, block)
 void exact_path(srukf_ctx* c, const double* Gbuf, double* Sout);      // the exact column path for Gbuf -> Sout (D, theta, clamp count as side effects)
 void set_null_canonical(srukf_ctx* c);
 void canonicalize_null_rows(srukf_ctx* c);      // after update_null_set on a factor of the library's own making (NEED_REORDER, map changes): the next frame may take the fast path
 int read_fs(srukf_ctx* c);
 int read_fs_host(srukf_ctx* c);
 int set_shared(srukf_ctx* c, int shared, int tenants);
+
+// ---- what the staged replay (srukf_replay.hip) and the image runs (srukf_images.hip) share ----
+int replay_mode_check(srukf_ctx* c, int mode, const char* who);      // which update modes the staged replay has, and on which storage
+// nframes frames captured into *g / *ge: issue_frame enqueues one frame on c->stream (replay_one_frame, replay_one_image_frame); never leaves the stream capturing
+int capture_frames(srukf_ctx* c, int nframes, hipGraph_t* g, hipGraphExec_t* ge, const std::function<void()>& issue_frame);
+void replay_prologue(srukf_ctx* c);                    // in front of a run: a pending motion step committed, the frame scalars point at the staged sequence
+int replay_launch_graphs(srukf_ctx* c, const ReplayGraphs& g, int count);      // count frames: eight-frame graphs, then single frames
+int replay_epilogue(srukf_ctx* c);                     // behind what a run issued: frames are in flight (srukf_synchronize), the step-wise state machine is idle
+// run(dt) with dt = count trajectory rows on the device; copied to traj_host (may be null) when run returns SRUKF_OK
+int with_device_traj(srukf_ctx* c, int count, double* traj_host, const std::function<int(double*)>& run);
+void images_archive_drop(srukf_map_scope* c, hipStream_t st);      // the searching image runs' record, parameters and captured frames go (the archive changes; the caller has synchronised the stream)
+void images_drop(srukf_map_scope* c, hipStream_t st);      // the staged images, their record, checkpoint and captured frames go (the caller has synchronised the stream)
+void images_restore(srukf_ctx* c);                     // srukf_synchronize: a flagged block of image frames comes back to its checkpoint
 
 // ---- split form of the persistent factorisation (srukf_split.hip) ----
 bool split_form(const srukf_ctx* c, const GmwPlan& gp, bool ignore_starve = false);

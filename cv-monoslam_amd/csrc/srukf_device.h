@@ -61,10 +61,10 @@ struct FrameScalars {
     int ctl_next_valid;        // "table" mode: k_gain prepared fs->ctl for frame + 1 (0: the staged sequence ends with this frame)
     int frozen;                // staged replay: a frame was flagged -> k_motion and the persistent factorisation of the later frames of the run
                                // return at once (three quarters of a frame's time; the other kernels would pay a memory round trip per launch
-                               // for the test); cleared with the clamp counters (k_set_frame) and by the step-wise API
+                               // for the test); cleared with the clamp counters (k_set_run) and by the step-wise API
     int export_cnt;            // step-wise API: workgroups of the frame's last launch (k_rank_expand<2>) that are through; the last one exports status + robot view (StepExport)
     int joint_bad_frame, joint_bad_row;      // joint update (srukf_joint.hip): 1 + the FIRST frame whose innovation covariance had a non-positive pivot or whose innovation was not
-                               // finite (0: none) and that row; sticky: k_joint_dx keeps the first hit, cleared with the clamp counters (k_set_run, k_set_frame)
+                               // finite (0: none) and that row; sticky: k_joint_dx keeps the first hit, cleared with the clamp counters (k_set_run)
 };
 
 // control from two odometry poses (SLAM.cpp:1444-1458): Ut = (rot1, trans, rot2), Mt = control-noise sigmas

@@ -1,0 +1,513 @@
+// srukf_images.hip — image runs of the staged replay (DESIGN.md sections 20 - 24): the staged gray frames and the frames that associate on the device
+// (srukf_stage_images / srukf_run_images*), with the checked association (srukf_run_images_checked*), the archive search (srukf_images_search_archive), the map
+// policy's verdict (srukf_images_policy) and the 1-point RANSAC consensus (srukf_images_ransac) as options of a run, and the getters of their records.  No kernel:
+// the launch sequences, the graph cache and srukf_synchronize are srukf_replay.hip's; what the two files share is declared once in srukf_ctx.h.
+// A further per-frame option is: one bit of ImageForm, one group of image_group, one branch of replay_one_image_frame
+
+#include "srukf_ctx.h"
+using namespace srukf_impl;
+
+namespace srukf_impl {
+
+// Every device buffer of the image runs, by group, named ONCE: { address of the pointer, bytes, zeroed when allocated }.  image_buffers_alloc allocates a group,
+// images_drop and images_archive_drop free through the same lists: a buffer added HERE is freed without anyone remembering to list it.  The sizes are the allocation's
+// (image_bytes: of one staged frame, L: the archive's; whoever only frees passes neither).  Zeroed: the records (rows no run has written read as zero) and the
+// consensus scratch; not the parameter blocks (written in stream order in front of every run that reads them), the images, xyz and the checkpoint copies
+enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_GROUPS };
+struct ImageBuf { void** p; size_t bytes; bool zero; };
+static std::vector<ImageBuf> image_group(srukf_map_scope* c, ImageGroup g, size_t image_bytes = 0, size_t L = 0)
+{
+    ImageReplay& im = c->img;
+    const size_t N = c->d.N, np = c->d.np, f = (size_t)im.frames, D = sizeof(double), I = sizeof(int);
+    auto buf = [](auto** p, size_t bytes, bool zero = false) { return ImageBuf{ (void**)p, bytes, zero }; };
+    switch (g) {
+    case IMG_STAGED: return { buf(&im.images, f * image_bytes), buf(&im.corr_seq, D * f * N, true), buf(&im.vis_seq, I * f * N, true), buf(&im.h_seq, D * f * 2 * N, true),
+                              buf(&im.xyz, D * 3 * N), buf(&im.ck_tmpl, N * PT_TMPL_STRIDE), buf(&im.ckS, D * np * np), buf(&im.ckX, D * np) };
+    case IMG_CHECKED: return { buf(&im.corr2_seq, D * f * N, true), buf(&im.z2_seq, D * f * 2 * N, true), buf(&im.flags_seq, I * f * N, true), buf(&im.match_args, sizeof(MatchArgs)) };
+    case IMG_ARCHIVE: return { buf(&im.ar_rec, D * image_archive_record(f, L).doubles, true), buf(&im.ar_args, sizeof(ArchiveArgs)) };
+    case IMG_POLICY: return { buf(&im.pol_state, sizeof(srukf_policy_state) * N, true), buf(&im.pol_ck, sizeof(srukf_policy_state) * N, true), buf(&im.pol_verdict, I * f * N, true),
+                              buf(&im.pol_sum, sizeof(srukf_policy_summary) * f, true), buf(&im.pol_args, sizeof(srukf_policy_params)) };
+    case IMG_RANSAC: return { buf(&im.rs_D, D * N * N, true), buf(&im.rs_F, (N * N + 7) / 8 * 8, true), buf(&im.rs_votes, I * N, true), buf(&im.rs_flags, I * f * N, true),
+                              buf(&im.rs_rvotes, I * f * N, true), buf(&im.rs_dist, D * f * N, true), buf(&im.rs_sum, sizeof(RansacSummary) * f, true), buf(&im.rs_args, sizeof(RansacArgs)) };
+    default: return {};
+    }
+}
+
+static void image_buffers_free(const std::vector<ImageBuf>& bufs, hipStream_t st)
+{
+    for (const ImageBuf& b : bufs) if (*b.p) { srukf_dfree_on(*b.p, st); *b.p = nullptr; }
+}
+
+// a group allocated outside any capture, zeroed in stream order where marked; on any failure the whole group is freed and nulled, the sticky HIP error cleared
+static int image_buffers_alloc(srukf_ctx* c, const std::vector<ImageBuf>& bufs, const char* who)
+{
+    hipError_t e = hipSuccess;
+    for (const ImageBuf& b : bufs) if (e == hipSuccess) e = srukf_dmalloc_raw(b.p, b.bytes);
+    for (const ImageBuf& b : bufs) if (e == hipSuccess && b.zero) e = hipMemsetAsync(*b.p, 0, b.bytes, c->stream);
+    if (e == hipSuccess) return SRUKF_OK;
+    (void)hipGetLastError();
+    image_buffers_free(bufs, c->stream);
+    c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
+}
+
+// the archive changes (srukf_archive_set): the searching frames were captured with its pointers and L workgroups, the record is sized by L.  The next searching run
+// builds both again (images_archive_ensure)
+void images_archive_drop(srukf_map_scope* c, hipStream_t st)
+{
+    ImageReplay& im = c->img;
+    for (int i = 0; i < IMAGE_FORMS; i++) if (ImageForm::at(i).search) for (int m = 0; m < 2; m++) graphs_destroy(im.graphs[i][m]);
+    image_buffers_free(image_group(c, IMG_ARCHIVE), st);
+    im.ar_L = 0; im.ar_valid = false;
+}
+
+void images_drop(srukf_map_scope* c, hipStream_t st)
+{
+    ImageReplay& im = c->img;
+    if (im.images) drop_graphs(c);                               // (the captured image frames hold these pointers)
+    for (int g = 0; g < IMG_GROUPS; g++) image_buffers_free(image_group(c, (ImageGroup)g), st);
+    im = ImageReplay{};
+}
+
+// A frame of an image run (srukf_run_images*): the plain frame form as in replay_one_frame_joint, whatever "fused_motion" and its neighbours say,
+// with the association between k_pxy and what stands in k_gain's place.  Behind seq_pxy(FORM_PLAIN) the device holds h, Si, visible and the predicted pose in X: what
+// k_warp_patch and the matching front read (srukf_associate finds the same behind srukf_predict_measurement).  k_associate_staged writes this frame's rows of z_seq /
+// m_seq, which k_gain / the joint kernels then read as they read staged rows.  BATCHED: seq_gain_only — seq_gain is seq_pxy + seq_gain_only in this form (no gain fold
+// below "fused tail" mode), and k_pxy has run.  The points go to the image state's own scratch, not c->G.
+// joint_ensure has run for JOINT (run_images_async: never inside a capture)
+// form (ImageForm, srukf_ctx.h):
+// checked: a frame of a checked image run — the same frame with k_associate_checked_staged in k_associate_staged's place; images_checked_ensure has run
+// search: a frame of a searching image run — the same frame with the archive search behind its tail, on the posterior (seq_archive_search: it
+// writes the archive's own buffers and the search record, nothing the filter reads); images_archive_ensure has run
+// ransac: a frame with the 1-point RANSAC consensus in it (srukf_images_ransac) — two more launches between the association and what stands in
+// k_gain's place: c->Ut is still S^T DZ there, PxyR / h / Si / vis / X are the predicted frame's, and this frame's rows of z_seq / m_seq are written: what
+// k_ransac_votes reads.  The pick launch rewrites the m_seq row to the consensus set, which the update then takes for its matches; images_ransac_ensure has run
+static void replay_one_image_frame(srukf_ctx* c, int mode, ImageForm form)
+{
+    ImageReplay& im = c->img;
+    const KDims& d = c->d;
+    seq_predict_motion(c, nullptr);
+    seq_predict_measurement(c, FORM_PLAIN);
+    seq_pxy(c, FORM_PLAIN);
+    {
+        ProfScope ps(c, KC_MISC, 0, (double)(PT_REGION_W * PT_REGION_W + PT_TMPL_BYTES + PT_PATCH_BYTES) * d.N);
+        srukf_launch_landmarks_cartesian(c->stream, d, c->X, c->S, im.xyz, nullptr);      // the points only
+        srukf_launch_warp_patch(c->stream, d, c->p, c->X, im.xyz, c->h, c->appR, c->appT, c->appPx, c->app_patch, c->has_app, c->app_tmpl);
+        const StagedAssoc rec = { im.images, im.frames, c->z_seq, c->m_seq, im.corr_seq, im.vis_seq, im.h_seq, c->fs };
+        if (form.checked)
+            srukf_launch_associate_checked_staged(c->stream, d, c->p, StagedChecked{ rec, im.corr2_seq, im.z2_seq, im.flags_seq, c->match_scores, im.match_args },
+                                                  c->h, c->Si, c->vis, c->has_app, c->app_tmpl);
+        else
+        srukf_launch_associate_staged(c->stream, d, c->p, rec, c->h, c->Si, c->vis, c->has_app, c->app_tmpl);
+    }
+    if (form.ransac) {
+        ProfScope ps(c, KC_MISC, 60.0 * d.N * d.N, 9.0 * d.N * d.N + 16.0 * 12 * d.N * d.N);
+        launch_ransac_staged(c->stream, d, c->w, c->p, StagedRansac{ im.frames, c->z_seq, c->m_seq, c->fs, im.rs_args, im.rs_D, im.rs_F, im.rs_votes,
+                                                                     im.rs_flags, im.rs_rvotes, im.rs_dist, im.rs_sum }, c->X, c->Ut, c->PxyR, c->h, c->Si, c->vis);
+    }
+    if (mode == SRUKF_UPDATE_JOINT) seq_joint_launches(c, nullptr, nullptr);
+    else seq_gain_only(c, nullptr, nullptr, FORM_PLAIN);
+    seq_refactor(c, refactor_frame_tail(c), FORM_PLAIN);
+    if (form.search) seq_archive_search(c);
+}
+
+// the state the block of image frames started from comes back: X, S and the matchPatch array (its pixels persist from frame to frame, so a flagged block must not
+// leave its own behind), as srukf_run_frames' checkpoint comes back.  Keeps c->err
+void images_restore(srukf_ctx* c)
+{
+    ImageReplay& im = c->img;
+    const size_t np = c->d.np;
+    const std::string why = c->err;
+    hipMemcpyAsync(c->S, im.ckS, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream);
+    hipMemcpyAsync(c->X, im.ckX, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream);
+    hipMemcpyAsync(c->app_tmpl, im.ck_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream);
+    if (im.pol_state) {                                        // the policy state comes back too; the rows the block's frames wrote are no verdicts any more: zero, as unwritten rows are
+        hipMemcpyAsync(im.pol_state, im.pol_ck, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyDeviceToDevice, c->stream);
+        hipMemsetAsync(im.pol_verdict, 0, sizeof(int) * (size_t)im.frames * (size_t)c->d.N, c->stream);
+        hipMemsetAsync(im.pol_sum, 0, sizeof(srukf_policy_summary) * (size_t)im.frames, c->stream);
+    }
+    if (im.rs_flags) {                                         // the consensus record: what the block's frames wrote does not stand either
+        const size_t fN = (size_t)im.frames * (size_t)c->d.N;
+        hipMemsetAsync(im.rs_flags, 0, sizeof(int) * fN, c->stream);
+        hipMemsetAsync(im.rs_rvotes, 0, sizeof(int) * fN, c->stream);
+        hipMemsetAsync(im.rs_dist, 0, sizeof(double) * fN, c->stream);
+        hipMemsetAsync(im.rs_sum, 0, sizeof(RansacSummary) * (size_t)im.frames, c->stream);
+    }
+    if (c->null_canonical != im.ck_canon) { c->null_canonical = im.ck_canon; drop_graphs(c); }
+    shadow_rebuild(c);
+    hipStreamSynchronize(c->stream);
+    c->err = why;
+}
+
+}  // namespace srukf_impl
+
+extern "C" {
+
+// ---- image runs: the staged replay with the association on the device ----
+
+// The gray frames of the staged sequence, copied to the device once; with them the per-frame record, the scratch for the Cartesian points and the block's checkpoint
+// (X, S, matchPatch): everything an image run needs that can fail for want of memory is allocated here, outside any capture.
+int srukf_stage_images(srukf_ctx* c, int F, const unsigned char* gray)
+{
+    if (!c || F < 1 || !gray) return SRUKF_ERR_BAD_ARG;
+    if (!c->odo_seq) { c->err = "stage_images: no staged sequence (srukf_stage_sequence first)"; return SRUKF_ERR_SEQUENCE; }
+    if (F != c->seqF) { c->err = "stage_images: n_frames is not the staged sequence's"; return SRUKF_ERR_DIM_MISMATCH; }
+    if (c->d.N < 1) { c->err = "stage_images: the map is empty"; return SRUKF_ERR_DIM_MISMATCH; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));             // frames in flight may still read the images staged before
+    images_drop(c, c->stream);
+    int rc = ensure_appearance(c); if (rc) return rc;
+    ImageReplay& im = c->img;
+    const size_t img = (size_t)c->p.image_w * (size_t)c->p.image_h;
+    im.frames = F;                                          // (the group's sizes)
+    rc = image_buffers_alloc(c, image_group(c, IMG_STAGED, img), "stage_images");
+    if (rc) { images_drop(c, c->stream); return rc; }
+    hipError_t e = hipMemcpy(im.images, gray, (size_t)F * img, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { images_drop(c, c->stream); c->err = std::string("stage_images: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
+    return SRUKF_OK;
+}
+
+// what a checked image run needs beyond srukf_stage_images' buffers, allocated on the first one and outside any capture: the checked record (zeroed), the
+// parameters' place on the device, and the filter's score buffer if no srukf_associate_checked has made it.  Captured checked frames hold the score buffer's
+// pointer: they are dropped when it is not the one they were captured with (match_drop has run in between)
+static int images_checked_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    int rc = match_ensure(c, who); if (rc) return rc;
+    if (im.chk_scores != c->match_scores) {
+        for (int i = 0; i < IMAGE_FORMS; i++) if (ImageForm::at(i).checked && (im.graphs[i][0].one_exec || im.graphs[i][1].one_exec)) { HIPCHK(c, hipStreamSynchronize(c->stream)); drop_graphs(c); break; }
+        im.chk_scores = c->match_scores;
+    }
+    if (im.corr2_seq) return SRUKF_OK;
+    return image_buffers_alloc(c, image_group(c, IMG_CHECKED), who);
+}
+
+// what a searching image run needs beyond srukf_stage_images' buffers, allocated in front of the first one and outside any capture: the search record for the
+// archive's L (zeroed) and the parameters' place on the device.  srukf_archive_set drops both with the captured searching frames (images_archive_drop)
+static int images_archive_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    if (im.ar_rec) return SRUKF_OK;
+    const int L = c->archive.L;
+    const int rc = image_buffers_alloc(c, image_group(c, IMG_ARCHIVE, 0, (size_t)L), who); if (rc) return rc;
+    im.ar_L = L;
+    return SRUKF_OK;
+}
+
+// what the map policy behind image frames needs beyond srukf_stage_images' buffers, allocated in front of the first policy run or by
+// srukf_images_set_policy_state, outside any capture: the per-landmark state and its checkpoint copy, the record and the parameters' place on the device, all zeroed
+static int images_policy_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    if (im.pol_state) return SRUKF_OK;
+    return image_buffers_alloc(c, image_group(c, IMG_POLICY), who);
+}
+
+// what the consensus inside image frames needs beyond srukf_stage_images' buffers, allocated in front of the first run with the switch on,
+// outside any capture: the scratch of the two launches, the record (zeroed) and the threshold's place on the device
+static int images_ransac_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    if (im.rs_D) return SRUKF_OK;
+    return image_buffers_alloc(c, image_group(c, IMG_RANSAC), who);
+}
+
+// the map policy's verdict behind staged frame `frame` (srukf_images_policy): an eager launch with the frame index as a kernel argument — fs->frame has advanced
+// behind the tail, and a captured frame could not carry the index.  It reads the posterior X and row `frame` of the association's record
+static void issue_image_policy(srukf_ctx* c, int frame)
+{
+    const ImageReplay& im = c->img;
+    ProfScope ps(c, KC_MISC, 0, 80.0 * c->d.N);
+    launch_map_policy_staged(c->stream, c->d, c->p, im.pol_args, StagedPolicy{ c->X, im.frames, im.h_seq, im.vis_seq, c->z_seq, c->m_seq, im.pol_state, im.pol_verdict, im.pol_sum }, frame);
+}
+
+// srukf_run_images_async (chk null) and srukf_run_images_checked_async (chk: the validated parameters): one body, the frames differ in the association launch
+static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double* d_traj, const MatchArgs* chk, const char* who)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const std::string w = who;
+    { const int rcm = replay_mode_check(c, mode, who); if (rcm) return rcm; }
+    if (c->storage != SRUKF_STORAGE_F64) { c->err = w + ": image runs are available in SRUKF_STORAGE_F64 only"; return SRUKF_ERR_UNSUPPORTED; }
+    ImageReplay& im = c->img;
+    if (!im.images) { c->err = w + ": no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!c->odo_seq || im.frames != c->seqF || first + count > c->seqF) { c->err = "frames outside the staged sequence"; return SRUKF_ERR_DIM_MISMATCH; }
+    if (c->async_pending && !im.pending) { c->err = w + ": frames of srukf_run_frames_async are in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    c->joint_bad_host = false;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (mode == SRUKF_UPDATE_JOINT) { const int rcj = joint_ensure(c, who); if (rcj) return rcj; }      // (before any capture begins)
+    const ImageForm form{ chk != nullptr, c->img_search && c->archive.L > 0, c->img_ransac };
+    if (form.checked) {
+        const int rce = images_checked_ensure(c, who); if (rce) return rce;                           // (idem)
+        srukf_launch_set_match_args(c->stream, im.match_args, *chk);      // in stream order: behind the frames of an earlier run of the block, in front of this run's
+        im.checked = true; c->match_valid = true;
+    }
+    // the archive search behind every frame (srukf_images_search_archive).  An empty archive: a plain run, and a record of L = 0
+    if (c->img_search) {
+        if (form.search) {
+            const int rca = images_archive_ensure(c, who); if (rca) return rca;                        // (idem)
+            launch_set_archive_args(c->stream, im.ar_args, c->img_search_args);      // in stream order, as the checked run's parameters
+            im.searching = true;
+        }
+        im.ar_valid = true;
+    }
+    // the map policy's verdict behind every frame (srukf_images_policy): no captured frames of its own — the run is issued frame by frame, the one-frame graph
+    // followed by the policy launch
+    const bool policy = c->img_policy;
+    if (policy) {
+        const int rcp = images_policy_ensure(c, who); if (rcp) return rcp;                            // (idem)
+        launch_set_policy_params(c->stream, im.pol_args, c->img_policy_args);      // in stream order, as the checked run's parameters
+        im.pol_valid = true;
+    }
+    // the 1-point RANSAC consensus inside every frame (srukf_images_ransac): captured frames of their own
+    if (form.ransac) {
+        const int rcr = images_ransac_ensure(c, who); if (rcr) return rcr;                            // (idem)
+        launch_set_ransac_args(c->stream, im.rs_args, RansacArgs{ c->img_ransac_thr });      // in stream order, as the checked run's parameters
+        im.rs_valid = true;
+    }
+    replay_prologue(c);
+    if (!im.pending) {
+        // the block's checkpoint: a block is every image run since the last srukf_synchronize
+        const size_t np = c->d.np;
+        HIPCHK(c, hipMemcpyAsync(im.ckS, c->S, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(im.ckX, c->X, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(im.ck_tmpl, c->app_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream));
+        if (im.pol_state) HIPCHK(c, hipMemcpyAsync(im.pol_ck, im.pol_state, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyDeviceToDevice, c->stream));
+        im.ck_canon = c->null_canonical;
+    }
+    double* traj = d_traj ? d_traj - (size_t)8 * first : nullptr;
+    int clear = c->async_pending ? 0 : 1;
+    if (c->red_r > 0 && !c->null_canonical) {
+        // null rows that are not (yet) sqrt(EPSILON) e_k: the run's first frame eagerly, as in srukf_run_frames_async (the plain form reads the rows as they are)
+        launch_set_run(c->stream, c->fs, first, clear, traj);
+        replay_one_image_frame(c, mode, form);
+        if (policy) issue_image_policy(c, first);
+        set_null_canonical(c);
+        im.pending = true; clear = 0;
+        first += 1; count -= 1;
+        { const int rc = replay_epilogue(c); if (rc) return rc; }
+        if (count == 0) return SRUKF_OK;
+    }
+    launch_set_run(c->stream, c->fs, first, clear, traj);
+    if (c->use_graph && !c->profiling) {
+        // (the form's own captured frames, per update mode: never a frame captured for another form, nor one without the association)
+        ReplayGraphs& g = im.graphs[form.index()][mode == SRUKF_UPDATE_JOINT ? 1 : 0];
+        const auto frame = [=] { replay_one_image_frame(c, mode, form); };
+        if (!g.one_exec) { const int rc = capture_frames(c, 1, &g.one, &g.one_exec, frame); if (rc) return rc; }
+        if (!policy && !g.eight_exec) { const int rc = capture_frames(c, SRUKF_GRAPH_FRAMES, &g.eight, &g.eight_exec, frame); if (rc) return rc; }      // (a policy run launches single frames only)
+        if (policy) for (int f = 0; f < count; f++) { HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream)); issue_image_policy(c, first + f); }
+        else { const int rc = replay_launch_graphs(c, g, count); if (rc) return rc; }
+    } else {
+        for (int f = 0; f < count; f++) { replay_one_image_frame(c, mode, form); if (policy) issue_image_policy(c, first + f); }
+    }
+    im.pending = true;
+    return replay_epilogue(c);
+}
+
+int srukf_run_images_async(srukf_ctx* c, int first, int count, int mode, double* d_traj) { return run_images_issue(c, first, count, mode, d_traj, nullptr, "run_images_async"); }
+
+// ---- checked image runs: the ambiguity veto and the sub-pixel peak inside an image run ----
+// srukf_associate_checked's parameter rules (params null: its defaults)
+static int checked_args(srukf_ctx* c, const srukf_match_params* params, MatchArgs* ma)
+{
+    srukf_match_params mp = { 0.8, 0.9, 4, 0 };
+    if (params) mp = *params;
+    if (!std::isfinite(mp.ratio) || mp.ratio <= 0.0) { c->err = "run_images_checked: ratio must be finite and positive"; return SRUKF_ERR_BAD_ARG; }
+    if (mp.exclusion < 1 || mp.exclusion > 20) { c->err = "run_images_checked: exclusion outside [1, 20]"; return SRUKF_ERR_BAD_ARG; }
+    if (!std::isfinite(mp.corr_threshold)) { c->err = "run_images_checked: corr_threshold is not finite"; return SRUKF_ERR_BAD_ARG; }
+    *ma = { .corr_threshold = mp.corr_threshold, .ratio = mp.ratio, .exclusion = mp.exclusion, .subpixel = mp.subpixel };
+    return SRUKF_OK;
+}
+
+int srukf_run_images_checked_async(srukf_ctx* c, int first, int count, int mode, const srukf_match_params* params, double* d_traj)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    MatchArgs ma;
+    const int rc = checked_args(c, params, &ma); if (rc) return rc;
+    return run_images_issue(c, first, count, mode, d_traj, &ma, "run_images_checked_async");
+}
+
+// Synchronous form: as srukf_run_images, no recovery inside the call
+int srukf_run_images_checked(srukf_ctx* c, int first, int count, int mode, const srukf_match_params* params, double* traj_host)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return with_device_traj(c, count, traj_host, [=](double* dt) { const int rc = srukf_run_images_checked_async(c, first, count, mode, params, dt); return rc ? rc : srukf_synchronize(c); });
+}
+
+// rows [first, first + count) of the checked record, after waiting for the stream like srukf_get_image_matches.  Rows no checked run has written are zero (all of
+// them before the first checked run); a row a plain image run wrote after a checked one keeps the checked run's values
+int srukf_get_image_checks(srukf_ctx* c, int first, int count, double* corr2, double* z2, int* flags)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_checks: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_checks: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    if (!im.corr2_seq) {
+        if (corr2) memset(corr2, 0, sizeof(double) * m * N);
+        if (z2) memset(z2, 0, sizeof(double) * m * 2 * N);
+        if (flags) memset(flags, 0, sizeof(int) * m * N);
+        return SRUKF_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (corr2) HIPCHK(c, hipMemcpy(corr2, im.corr2_seq + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
+    if (z2) HIPCHK(c, hipMemcpy(z2, im.z2_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
+    if (flags) HIPCHK(c, hipMemcpy(flags, im.flags_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    return SRUKF_OK;
+}
+
+// rows [first, first + count) of the record the searching image runs wrote (srukf_images_search_archive), after waiting for the stream like srukf_get_image_matches.
+// Rows no searching run has written are zero.  No record (no searching run since the images were staged or the archive was set; a flagged block restored since the
+// last one): SRUKF_ERR_SEQUENCE, the rule of srukf_get_match_scores
+int srukf_get_image_archive(srukf_ctx* c, int first, int count, int* L, double* h, double* Si, int* visible, double* z, int* matched, double* corr, int* hits)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_archive: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.ar_valid) { c->err = "get_image_archive: no record of a searching image run (srukf_images_search_archive; a flagged block leaves none)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_archive: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    const size_t n = im.ar_rec ? (size_t)im.ar_L : 0, a = (size_t)first, m = (size_t)count;
+    if (L) *L = (int)n;
+    if (hits) memset(hits, 0, sizeof(int) * m);
+    if (n == 0) return SRUKF_OK;                               // (an empty archive: the runs were plain ones)
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const ImageArchiveRecord r = image_archive_record((size_t)im.frames, n);
+    const double* rec = im.ar_rec; const int* reci = (const int*)(rec + r.ints);
+    if (h) HIPCHK(c, hipMemcpy(h, rec + r.h + a * 2 * n, sizeof(double) * m * 2 * n, hipMemcpyDeviceToHost));
+    if (Si) HIPCHK(c, hipMemcpy(Si, rec + r.Si + a * 4 * n, sizeof(double) * m * 4 * n, hipMemcpyDeviceToHost));
+    if (z) HIPCHK(c, hipMemcpy(z, rec + r.z + a * 2 * n, sizeof(double) * m * 2 * n, hipMemcpyDeviceToHost));
+    if (corr) HIPCHK(c, hipMemcpy(corr, rec + r.corr + a * n, sizeof(double) * m * n, hipMemcpyDeviceToHost));
+    if (visible) HIPCHK(c, hipMemcpy(visible, reci + r.vis_i + a * n, sizeof(int) * m * n, hipMemcpyDeviceToHost));
+    if (matched) HIPCHK(c, hipMemcpy(matched, reci + r.m_i + a * n, sizeof(int) * m * n, hipMemcpyDeviceToHost));
+    if (hits) HIPCHK(c, hipMemcpy(hits, reci + r.hits_i + a, sizeof(int) * m, hipMemcpyDeviceToHost));
+    return SRUKF_OK;
+}
+
+// ---- the map policy's verdict behind image frames (the kernel and the switch: srukf_policy.hip) ----
+// the counters map[] holds (cslam.cpp:713-723) become the device state the next policy run advances
+int srukf_images_set_policy_state(srukf_ctx* c, const srukf_policy_state* state)
+{
+    if (!c || !state) return SRUKF_ERR_BAD_ARG;
+    ImageReplay& im = c->img;
+    if (!im.images) { c->err = "images_set_policy_state: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (c->async_pending) { c->err = "images_set_policy_state: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = images_policy_ensure(c, "images_set_policy_state"); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(im.pol_state, state, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                 // (pageable host memory)
+    im.ck_clean = false;                                        // the checkpoint's copy of the state is not this one: no srukf_images_rewind behind a seed
+    return SRUKF_OK;
+}
+
+// rows [first, first + count) of the policy record (what SLAM.cpp:2443-2459 and 556 would decide behind each frame), after waiting for the stream like
+// srukf_get_image_matches; the device state as it stands; the lowest frame of the range that asks for a map change
+int srukf_get_image_policy(srukf_ctx* c, int first, int count, int* verdict, srukf_policy_summary* summary, srukf_policy_state* state_out, int* first_change)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_policy: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.pol_state || !im.pol_valid) { c->err = "get_image_policy: no record of a policy run (srukf_images_policy)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_policy: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    if (verdict) HIPCHK(c, hipMemcpy(verdict, im.pol_verdict + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (state_out) HIPCHK(c, hipMemcpy(state_out, im.pol_state, sizeof(srukf_policy_state) * N, hipMemcpyDeviceToHost));
+    if (summary || first_change) {
+        std::vector<srukf_policy_summary> sm(m);
+        HIPCHK(c, hipMemcpy(sm.data(), im.pol_sum + a, sizeof(srukf_policy_summary) * m, hipMemcpyDeviceToHost));
+        if (summary) memcpy(summary, sm.data(), sizeof(srukf_policy_summary) * m);
+        if (first_change) { *first_change = -1; for (size_t q = 0; q < m; q++) if (sm[q].change) { *first_change = first + (int)q; break; } }
+    }
+    return SRUKF_OK;
+}
+
+// ---- the 1-point RANSAC consensus inside image frames (the kernels: srukf_ransac.hip) ----
+// The switch: on the handle, like srukf_images_policy.  Touches no device: the threshold reaches it in stream order in front of the next image run (run_images_issue)
+int srukf_images_ransac(srukf_ctx* c, int on, double threshold)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    if (on && (!std::isfinite(threshold) || threshold <= 0.0)) { c->err = "images_ransac: threshold must be finite and positive"; return SRUKF_ERR_BAD_ARG; }
+    if (c->async_pending) { c->err = "images_ransac: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    c->img_ransac = on != 0;
+    if (on) c->img_ransac_thr = threshold;
+    return SRUKF_OK;
+}
+
+// rows [first, first + count) of the consensus record, after waiting for the stream like srukf_get_image_matches; the lowest frame of the range whose consensus
+// dropped a match
+int srukf_get_image_ransac(srukf_ctx* c, int first, int count, int* flags, int* votes, double* dist, int* best, int* n_active, int* n_low, int* first_outlier)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_ransac: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.rs_flags || !im.rs_valid) { c->err = "get_image_ransac: no record of a run with the consensus in it (srukf_images_ransac)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_ransac: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    if (flags) HIPCHK(c, hipMemcpy(flags, im.rs_flags + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (votes) HIPCHK(c, hipMemcpy(votes, im.rs_rvotes + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (dist) HIPCHK(c, hipMemcpy(dist, im.rs_dist + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
+    if (best || n_active || n_low || first_outlier) {
+        std::vector<RansacSummary> sm(m);
+        HIPCHK(c, hipMemcpy(sm.data(), im.rs_sum + a, sizeof(RansacSummary) * m, hipMemcpyDeviceToHost));
+        if (first_outlier) *first_outlier = -1;
+        for (size_t q = 0; q < m; q++) {
+            if (best) best[q] = sm[q].best;
+            if (n_active) n_active[q] = sm[q].n_active;
+            if (n_low) n_low[q] = sm[q].n_low;
+            if (first_outlier && *first_outlier < 0 && sm[q].outlier) *first_outlier = first + (int)q;
+        }
+    }
+    return SRUKF_OK;
+}
+
+// The checkpoint of the image block the last srukf_synchronize ended clean comes back (X, S, the matchPatch array, the policy state: images_restore), so that a host
+// can stop a block at the frame whose verdict asks for a map change (SLAM.cpp:552-562) by running the frames up to it again.  Only while nothing has written X, S or
+// a matchPatch since that srukf_synchronize (ImageReplay::ck_clean)
+int srukf_images_rewind(srukf_ctx* c)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    ImageReplay& im = c->img;
+    if (c->async_pending) { c->err = "images_rewind: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.images || !im.ck_clean) { c->err = "images_rewind: no image block that srukf_synchronize ended clean, or the state has been written since"; return SRUKF_ERR_SEQUENCE; }
+    HIPCHK(c, hipSetDevice(c->device));
+    step_state_replaced(c);                                     // (clears ck_clean: one rewind per block)
+    c->err.clear();
+    images_restore(c);
+    c->phase = 0; c->frame_updated = false;
+    HIPCHK(c, hipGetLastError());
+    return SRUKF_OK;
+}
+
+// Synchronous form.  No recovery inside the call: a flagged block comes back to its checkpoint (srukf_synchronize) and SRUKF_ERR_CLAMP_PENDING is returned
+int srukf_run_images(srukf_ctx* c, int first, int count, int mode, double* traj_host)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    return with_device_traj(c, count, traj_host, [=](double* dt) { const int rc = srukf_run_images_async(c, first, count, mode, dt); return rc ? rc : srukf_synchronize(c); });
+}
+
+// rows [first, first + count) of what the association wrote (rows no image run has written: z / matched as staged, the rest zero).  Waits for the stream only: flags
+// of frames in flight are still srukf_synchronize's to report
+int srukf_get_image_matches(srukf_ctx* c, int first, int count, double* z, int* matched, double* corr, int* visible, double* h)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_matches: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_matches: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    if (z) HIPCHK(c, hipMemcpy(z, c->z_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
+    if (matched) HIPCHK(c, hipMemcpy(matched, c->m_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (corr) HIPCHK(c, hipMemcpy(corr, im.corr_seq + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
+    if (visible) HIPCHK(c, hipMemcpy(visible, im.vis_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (h) HIPCHK(c, hipMemcpy(h, im.h_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
+    return SRUKF_OK;
+}
+
+}  // extern "C"

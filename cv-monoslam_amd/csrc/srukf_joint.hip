@@ -22,7 +22,7 @@
 //                  launch that follows cleared as k_gain's block (0, 0) does; R_pp back into W's diagonal blocks (srukf_debug_copy "joint_R")
 // A non-positive pivot (Pzz is a Gram matrix plus the noise blocks: the inputs were not finite) sets *status = 1 + its row and the pivot is replaced by 1; an innovation
 // z - h that is not finite (Pzz does not depend on z) sets it the same way and enters W as zero.  k_joint_dx then leaves X alone and writes U^T = 0 (both copies), and
-// records frame + 1 and the row in the frame scalars' sticky pair (first hit only; k_set_run / k_set_frame clear it with the clamp counters): nothing loops, no NaN
+// records frame + 1 and the row in the frame scalars' sticky pair (first hit only; k_set_run clears it with the clamp counters): nothing loops, no NaN
 // reaches the state, and the later frames of a replayed block run to their end on finite data.  The step-wise call reads *status and returns SRUKF_ERR_UNSUPPORTED with
 // the row in srukf_last_error; the staged replay needs no host inside a block: srukf_synchronize reads the pair with the frame scalars.
 // Staged replay ("the joint frame of the replay"): z_cur / m_cur null -> this frame's rows of the staged z_seq / m_seq through fs->frame, as k_gain

@@ -310,7 +310,7 @@ static int map_change_factor(srukf_ctx* c, srukf_ctx* c2, int n2, const double* 
 {
     const int ldn = c2->d.np;
     for (int slow = 0; slow < 2; slow++) {
-        launch_set_frame(c->stream, c2->fs, 0, 1);
+        launch_set_run(c->stream, c2->fs, 0, 1, nullptr);
         launch_refactor_reset(c->stream, ldn, c2->theta, c2->fs, 1);
         launch_sym_permute(c->stream, n2, ldn, src, lds, c2->Gbak, d_map);
         srukf_launch_gmw_stats(c->stream, n2, ldn, c2->Gbak, c2->fs);

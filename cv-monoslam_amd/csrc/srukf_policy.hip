@@ -2,8 +2,8 @@
 // deletion tests of updateFeaturesInformation (cslam.cpp:446-462; SLAM.cpp:2443-2459) and the addFeatures trigger (SLAM.cpp:556), per landmark and per frame, from
 // the posterior X and the frame's association.  Read-only for the filter: it writes the policy state, the verdicts and the summary, nothing else.
 //   srukf_map_policy              step-wise: k_map_policy on the filter's current X with the caller's association
-//   srukf_images_policy           the switch of the image runs: k_map_policy_staged behind every frame (issue_image_policy: srukf_replay.hip)
-//   srukf_images_set_policy_state / srukf_get_image_policy / srukf_images_rewind: srukf_replay.hip
+//   srukf_images_policy           the switch of the image runs: k_map_policy_staged behind every frame (issue_image_policy: srukf_images.hip)
+//   srukf_images_set_policy_state / srukf_get_image_policy / srukf_images_rewind: srukf_images.hip
 // One workgroup of 256 threads, landmarks strided over the threads; the four counts are reduced by wave shuffles and through LDS.  No atomics, no flags: every
 // dependency is a launch boundary on the stream.  gfx950 only.
 #include "srukf_ctx.h"

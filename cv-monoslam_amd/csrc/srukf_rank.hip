@@ -275,7 +275,7 @@ __device__ __forceinline__ void rank_expand_body(int n, int ld, int r, double ep
             }
         }
         // the same row every frame: written by the first frame of a staged run only (fs->const_rows_ok: set for the frames after it
-        // by the next launch, cleared by k_set_run / k_set_frame; whoever else rewrites S goes through one of those first)
+        // by the next launch, cleared by k_set_run; whoever else rewrites S goes through it first)
         if (sigR && fs->const_rows_ok) return;
         for (int c = threadIdx.x; c < ld; c += 256) out[c] = (c == jj) ? rnd(sqrt(eps)) : 0.0;
         return;

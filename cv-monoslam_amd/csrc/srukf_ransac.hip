@@ -5,7 +5,7 @@
 //     k_ransac_votes             one workgroup per hypothesis i: x(i) = X + K_i (z_i - h_i) restricted to the ten rows a pair needs, the projection of every
 //                                matched landmark j under it, d_ij, the votes of i (wave ballots, integer adds)
 //     k_ransac_pick              one workgroup: the hypothesis with the most votes (lowest index among equals), its mask and distances
-//   srukf_images_ransac          the same consensus inside every frame of an image run (the switch and the record: srukf_replay.hip):
+//   srukf_images_ransac          the same consensus inside every frame of an image run (the switch and the record: srukf_images.hip):
 //     k_ransac_votes_staged      k_ransac_votes' body on the frame's own operands — c->Ut is S^T DZ behind seq_pxy(FORM_PLAIN), z / matched are row fs->frame of
 //                                z_seq / m_seq behind k_associate_staged — with the threshold in a device struct
 //     k_ransac_pick_staged       k_ransac_pick's rule, the frame's row of the record, and the frame's m_seq row rewritten to the consensus set for the update

@@ -1,6 +1,7 @@
 // srukf_replay.hip — the launch sequences of a frame (seq_*: which kernels run, in which order, for which launch plan), the rank-aware null set, the graph cache
 // and the staged replay (srukf_stage_sequence / srukf_run_frames*: the OnBnClickedAuto loop of MonoSLAMView.cpp:526-572 with inputs resident in HBM).
-// Also the small host-layer kernels (frame scalars, permutations, rounding) behind their launchers.
+// Also the small host-layer kernels (frame scalars, permutations, rounding) behind their launchers.  The image runs of the staged replay (srukf_run_images*)
+// are srukf_images.hip's; what it takes from here is declared in srukf_ctx.h under a heading of its own.
 
 #include "srukf_ctx.h"
 using namespace srukf_impl;
@@ -20,20 +21,7 @@ __global__ void k_set_seq(FrameScalars* fs, const double* odo_seq, int seqF, dou
     fs->a[0] = a1; fs->a[1] = a2; fs->a[2] = a3; fs->a[3] = a4;
 }
 
-__global__ void k_set_frame(FrameScalars* fs, int frame, int clear_clamp)
-{
-    fs->frame = frame;
-    srukf_prepare_control(fs);
-    fs->stat_count = 0;
-    fs->const_rows_ok = 0; fs->const_rows_pending = 0;         // whatever happened to S since the last staged frame: its first tail writes every row again
-    for (int q = 0; q < SRUKF_STAT_GROUPS; q++) fs->stat_cnt[q] = 0;
-    fs->traj_base = nullptr;
-    if (clear_clamp) { fs->clamp_rows = 0; fs->clamp_first = 0x7fffffff; fs->clamp_frame = 0x7fffffff; fs->frozen = 0; fs->gmw_aborts = 0; fs->joint_bad_frame = 0; fs->joint_bad_row = 0; }
-}
-
-__global__ void k_set_traj(FrameScalars* fs, double* traj_base) { fs->traj_base = traj_base; }
-
-// start of a staged replay: frame counter, flags and trajectory base in one launch
+// start of a staged replay, or of a single frame outside one (traj_base null): frame counter, flags and trajectory base in one launch
 __global__ void k_set_run(FrameScalars* fs, int frame, int clear_clamp, double* traj_base)
 {
     fs->frame = frame;
@@ -142,7 +130,7 @@ __global__ __launch_bounds__(256) void k_quantize(int n, int ld, double* __restr
 
 namespace srukf_impl {
 void launch_refactor_reset(hipStream_t st, int np, unsigned long long* theta_bits, FrameScalars* fs, int reset_stats) { hipLaunchKernelGGL(k_refactor_reset, dim3((np + 255) / 256), dim3(256), 0, st, np, theta_bits, fs, reset_stats); }
-void launch_set_frame(hipStream_t st, FrameScalars* fs, int frame, int clear_clamp) { hipLaunchKernelGGL(k_set_frame, dim3(1), dim3(1), 0, st, fs, frame, clear_clamp); }
+void launch_set_seq(hipStream_t st, FrameScalars* fs, const double* odo_seq, int seqF, const srukf_params& p) { hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, st, fs, odo_seq, seqF, p.a1, p.a2, p.a3, p.a4); }
 void launch_set_run(hipStream_t st, FrameScalars* fs, int frame, int clear_clamp, double* traj_base) { hipLaunchKernelGGL(k_set_run, dim3(1), dim3(1), 0, st, fs, frame, clear_clamp, traj_base); }
 void launch_set_step(hipStream_t st, FrameScalars* fs, double* odo, int seqF, double a1, double a2, double a3, double a4, int fresh, const double poses[9])
 {
@@ -564,8 +552,7 @@ void seq_refactor(srukf_ctx* c, const RefactorRequest& rq, FrameForm ff)
 int exact_repeat_begin(srukf_ctx* c, int frame, double* traj_base)
 {
     const size_t np = c->d.np;
-    launch_set_frame(c->stream, c->fs, frame, 1);
-    if (traj_base) hipLaunchKernelGGL(k_set_traj, dim3(1), dim3(1), 0, c->stream, c->fs, traj_base);
+    launch_set_run(c->stream, c->fs, frame, 1, traj_base);
     launch_refactor_reset(c->stream, (int)np, c->theta, c->fs, 0);
     HIPCHK(c, hipMemcpyAsync(c->G, c->Gbak, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream));
     return SRUKF_OK;
@@ -655,7 +642,7 @@ int refactor_reorder(srukf_ctx* c, int ub, int ue)
             srukf_launch_syrk(c->stream, d, c->Sdis, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, SyrkRider{});
         }
         for (int slow = 0; slow < 2; slow++) {
-            launch_set_frame(c->stream, c->fs, 0, 1);
+            launch_set_run(c->stream, c->fs, 0, 1, nullptr);
             launch_sym_permute(c->stream, n, np, c->G, np, c->Gbak, stage == 0 ? c->iperm : c->perm);
             if (stage == 0) HIPCHK(c, hipMemsetAsync(c->Sdis, 0, bytes, c->stream));
             run_gmw(c, c->Gbak, out, slow != 0);
@@ -928,41 +915,20 @@ int read_fs_host(srukf_ctx* c)
     return SRUKF_OK;
 }
 
+void graphs_destroy(ReplayGraphs& g)
+{
+    for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec, &g.block_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
+    for (hipGraph_t* q : { &g.one, &g.eight, &g.block }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
+    g.block_frames = 0;
+}
+
+// the captured frames of both update modes: the replay's, and every form of an image frame
 void drop_graphs(srukf_map_scope* c)
 {
-    ImageReplay& im = c->img;
-    for (ReplayGraphs* gs : { c->graphs, im.graphs, im.chk_graphs, im.ar_graphs[0], im.ar_graphs[1],
-                              im.rs_graphs[0][0], im.rs_graphs[0][1], im.rs_graphs[1][0], im.rs_graphs[1][1] }) for (int m = 0; m < 2; m++) {      // the captured frames of both update modes: without the association, with it, with the checked one, with the archive search behind either, with the consensus in any of these
-        ReplayGraphs& g = gs[m];
-        for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec, &g.block_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
-        for (hipGraph_t* q : { &g.one, &g.eight, &g.block }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
-        g.block_frames = 0;
+    for (int m = 0; m < 2; m++) {
+        graphs_destroy(c->graphs[m]);
+        for (int i = 0; i < IMAGE_FORMS; i++) graphs_destroy(c->img.graphs[i][m]);
     }
-}
-
-// the archive changes (srukf_archive_set): the searching frames were captured with its pointers and L workgroups, the record is sized by L.  The next searching run
-// builds both again (images_archive_ensure)
-void images_archive_drop(srukf_map_scope* c, hipStream_t st)
-{
-    ImageReplay& im = c->img;
-    for (int k = 0; k < 2; k++) for (int m = 0; m < 2; m++) for (ReplayGraphs* gp : { &im.ar_graphs[k][m], &im.rs_graphs[1][k][m] }) {      // (the searching frames, with and without the consensus)
-        ReplayGraphs& g = *gp;
-        for (hipGraphExec_t* e : { &g.one_exec, &g.eight_exec }) if (*e) { hipGraphExecDestroy(*e); *e = nullptr; }
-        for (hipGraph_t* q : { &g.one, &g.eight }) if (*q) { hipGraphDestroy(*q); *q = nullptr; }
-    }
-    for (void* b : { (void*)im.ar_rec, (void*)im.ar_args }) if (b) srukf_dfree_on(b, st);
-    im.ar_rec = nullptr; im.ar_args = nullptr; im.ar_L = 0; im.ar_valid = false;
-}
-
-void images_drop(srukf_map_scope* c, hipStream_t st)
-{
-    ImageReplay& im = c->img;
-    if (im.images) drop_graphs(c);                               // (the captured image frames hold these pointers)
-    for (void* b : { (void*)im.images, (void*)im.ck_tmpl, (void*)im.corr_seq, (void*)im.h_seq, (void*)im.xyz, (void*)im.ckS, (void*)im.ckX, (void*)im.vis_seq,
-                      (void*)im.corr2_seq, (void*)im.z2_seq, (void*)im.flags_seq, (void*)im.match_args, (void*)im.ar_rec, (void*)im.ar_args,
-                      (void*)im.pol_state, (void*)im.pol_ck, (void*)im.pol_verdict, (void*)im.pol_sum, (void*)im.pol_args,
-                      (void*)im.rs_D, (void*)im.rs_dist, (void*)im.rs_F, (void*)im.rs_votes, (void*)im.rs_flags, (void*)im.rs_rvotes, (void*)im.rs_sum, (void*)im.rs_args }) if (b) srukf_dfree_on(b, st);
-    im = ImageReplay{};
 }
 
 // shared: 0 exclusive, 1 shared (tenants persistent launches at a time), 2 one launch per panel
@@ -1018,52 +984,10 @@ static void replay_one_frame(srukf_ctx* c, int mode)
     seq_refactor(c, refactor_frame_tail(c), ff);
 }
 
-// A frame of an image run (srukf_run_images*): the plain frame form as in replay_one_frame_joint, whatever "fused_motion" and its neighbours say,
-// with the association between k_pxy and what stands in k_gain's place.  Behind seq_pxy(FORM_PLAIN) the device holds h, Si, visible and the predicted pose in X: what
-// k_warp_patch and the matching front read (srukf_associate finds the same behind srukf_predict_measurement).  k_associate_staged writes this frame's rows of z_seq /
-// m_seq, which k_gain / the joint kernels then read as they read staged rows.  BATCHED: seq_gain_only — seq_gain is seq_pxy + seq_gain_only in this form (no gain fold
-// below "fused tail" mode), and k_pxy has run.  The points go to the image state's own scratch, not c->G.
-// joint_ensure has run for JOINT (run_images_async: never inside a capture)
-// checked: a frame of a checked image run — the same frame with k_associate_checked_staged in k_associate_staged's place; images_checked_ensure has run
-// search: a frame of a searching image run — the same frame with the archive search behind its tail, on the posterior (seq_archive_search: it
-// writes the archive's own buffers and the search record, nothing the filter reads); images_archive_ensure has run
-// ransac: a frame with the 1-point RANSAC consensus in it (srukf_images_ransac) — two more launches between the association and what stands in
-// k_gain's place: c->Ut is still S^T DZ there, PxyR / h / Si / vis / X are the predicted frame's, and this frame's rows of z_seq / m_seq are written: what
-// k_ransac_votes reads.  The pick launch rewrites the m_seq row to the consensus set, which the update then takes for its matches; images_ransac_ensure has run
-static void replay_one_image_frame(srukf_ctx* c, int mode, bool checked, bool search, bool ransac)
-{
-    ImageReplay& im = c->img;
-    const KDims& d = c->d;
-    seq_predict_motion(c, nullptr);
-    seq_predict_measurement(c, FORM_PLAIN);
-    seq_pxy(c, FORM_PLAIN);
-    {
-        ProfScope ps(c, KC_MISC, 0, (double)(PT_REGION_W * PT_REGION_W + PT_TMPL_BYTES + PT_PATCH_BYTES) * d.N);
-        srukf_launch_landmarks_cartesian(c->stream, d, c->X, c->S, im.xyz, nullptr);      // the points only
-        srukf_launch_warp_patch(c->stream, d, c->p, c->X, im.xyz, c->h, c->appR, c->appT, c->appPx, c->app_patch, c->has_app, c->app_tmpl);
-        const StagedAssoc rec = { im.images, im.frames, c->z_seq, c->m_seq, im.corr_seq, im.vis_seq, im.h_seq, c->fs };
-        if (checked)
-            srukf_launch_associate_checked_staged(c->stream, d, c->p, StagedChecked{ rec, im.corr2_seq, im.z2_seq, im.flags_seq, c->match_scores, im.match_args },
-                                                  c->h, c->Si, c->vis, c->has_app, c->app_tmpl);
-        else
-        srukf_launch_associate_staged(c->stream, d, c->p, rec, c->h, c->Si, c->vis, c->has_app, c->app_tmpl);
-    }
-    if (ransac) {
-        ProfScope ps(c, KC_MISC, 60.0 * d.N * d.N, 9.0 * d.N * d.N + 16.0 * 12 * d.N * d.N);
-        launch_ransac_staged(c->stream, d, c->w, c->p, StagedRansac{ im.frames, c->z_seq, c->m_seq, c->fs, im.rs_args, im.rs_D, im.rs_F, im.rs_votes,
-                                                                     im.rs_flags, im.rs_rvotes, im.rs_dist, im.rs_sum }, c->X, c->Ut, c->PxyR, c->h, c->Si, c->vis);
-    }
-    if (mode == SRUKF_UPDATE_JOINT) seq_joint_launches(c, nullptr, nullptr);
-    else seq_gain_only(c, nullptr, nullptr, FORM_PLAIN);
-    seq_refactor(c, refactor_frame_tail(c), FORM_PLAIN);
-    if (search) seq_archive_search(c);
-}
-
-// images: frames of an image run (checked: of a checked one; search: of a searching one; ransac: with the consensus in them)
-static int capture_frames(srukf_ctx* c, int nframes, int mode, hipGraph_t* g, hipGraphExec_t* ge, bool images = false, bool checked = false, bool search = false, bool ransac = false)
+int capture_frames(srukf_ctx* c, int nframes, hipGraph_t* g, hipGraphExec_t* ge, const std::function<void()>& issue_frame)
 {
     HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    for (int q = 0; q < nframes; q++) { if (images) replay_one_image_frame(c, mode, checked, search, ransac); else replay_one_frame(c, mode); }
+    for (int q = 0; q < nframes; q++) issue_frame();
     const hipError_t launch_err = hipGetLastError();            // a failed launch inside the capture must not leave the stream capturing
     HIPCHK(c, hipStreamEndCapture(c->stream, g));
     HIPCHK(c, launch_err);
@@ -1092,7 +1016,7 @@ void set_null_canonical(srukf_ctx* c)
 // which update modes the staged replay has, and on which storage: BATCHED everywhere; JOINT on fp64 storage (the step-wise srukf_update_joint refuses
 // SRUKF_STORAGE_F32_MIXED too; SRUKF_STORAGE_F32: the replay's frame tails round in launches the step-wise call's checked refactorisation does not share —
 // not shown to round at the same points, so refused, include/srukf.h)
-static int replay_mode_check(srukf_ctx* c, int mode, const char* who)
+int srukf_impl::replay_mode_check(srukf_ctx* c, int mode, const char* who)
 {
     if (mode == SRUKF_UPDATE_BATCHED) return SRUKF_OK;
     if (mode != SRUKF_UPDATE_JOINT) { c->err = std::string(who) + " supports BATCHED and JOINT only (SEQUENTIAL needs a host check per column)"; return SRUKF_ERR_UNSUPPORTED; }
@@ -1101,6 +1025,46 @@ static int replay_mode_check(srukf_ctx* c, int mode, const char* who)
         return SRUKF_ERR_UNSUPPORTED;
     }
     return SRUKF_OK;
+}
+
+// What srukf_run_frames_async and the image runs (run_images_issue) share to the letter.  In front of a run:
+void srukf_impl::replay_prologue(srukf_ctx* c)
+{
+    step_commit_motion(c); step_state_replaced(c);
+    if (c->fs_seq_step) {                                      // the step-wise fast path pointed the frame scalars at its own three poses
+        launch_set_seq(c->stream, c->fs, c->odo_seq, c->seqF, c->p);
+        c->fs_seq_step = false;
+    }
+}
+
+// count frames from the captured frames of one form: a graph of SRUKF_GRAPH_FRAMES consecutive frames while that many are left (one host launch per 8 frames keeps the
+// host ahead of the device when several filters share one host thread), then single frames
+int srukf_impl::replay_launch_graphs(srukf_ctx* c, const ReplayGraphs& g, int count)
+{
+    int f = 0;
+    for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(g.eight_exec, c->stream));
+    for (; f < count; f++) HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
+    return SRUKF_OK;
+}
+
+// behind the frames a run issued
+int srukf_impl::replay_epilogue(srukf_ctx* c)
+{
+    c->async_pending = true;
+    c->phase = 0; c->frame_updated = false;
+    HIPCHK(c, hipGetLastError());
+    return SRUKF_OK;
+}
+
+// the synchronous entries' frame: the trajectory rows on the device around run(dt), copied to the host when it ends well
+int srukf_impl::with_device_traj(srukf_ctx* c, int count, double* traj_host, const std::function<int(double*)>& run)
+{
+    double* dt = nullptr;
+    HIPCHK(c, srukf_dmalloc((void**)&dt, sizeof(double) * 8 * (size_t)count));
+    const int rc = run(dt);
+    if (traj_host && rc == SRUKF_OK) hipMemcpy(traj_host, dt, sizeof(double) * 8 * (size_t)count, hipMemcpyDeviceToHost);
+    srukf_dfree(dt);
+    return rc;
 }
 
 // *c->hfs holds a set sticky pair of the joint update: the error the caller returns.  Frames before that one are valid; it and the later ones are not
@@ -1125,8 +1089,7 @@ static int run_staged_frame_exact(srukf_ctx* c, int frame, double* traj_row, int
     auto t0 = now();
     auto lap = [&](const char* what) { if (timing) { hipStreamSynchronize(c->stream); auto t1 = now(); fprintf(stderr, "[exact frame] %s %.0f us\n", what, std::chrono::duration<double, std::micro>(t1 - t0).count()); t0 = t1; } };
     double* tb = traj_row ? traj_row - (size_t)8 * frame : nullptr;
-    launch_set_frame(c->stream, c->fs, frame, 1);
-    hipLaunchKernelGGL(k_set_traj, dim3(1), dim3(1), 0, c->stream, c->fs, tb);
+    launch_set_run(c->stream, c->fs, frame, 1, tb);
     seq_predict_motion(c, nullptr);
     seq_predict_measurement(c, FORM_PLAIN);
     lap("predict");
@@ -1183,7 +1146,7 @@ int srukf_stage_sequence(srukf_ctx* c, int F, const double* odo, const double* z
     HIPCHK(c, hipMemcpy(c->z_seq, z, sizeof(double) * (size_t)F * 2 * N, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->m_seq, matched, sizeof(int) * (size_t)F * N, hipMemcpyHostToDevice));
     c->seqF = F;
-    hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, c->stream, c->fs, c->odo_seq, F, c->p.a1, c->p.a2, c->p.a3, c->p.a4);
+    launch_set_seq(c->stream, c->fs, c->odo_seq, F, c->p);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SRUKF_OK;
 }
@@ -1202,7 +1165,7 @@ int srukf_prepare_frames_mode(srukf_ctx* c, int count, int mode)
     if (g.block) { hipGraphDestroy(g.block); g.block = nullptr; }
     g.block_frames = 0;
     if (mode == SRUKF_UPDATE_JOINT) { rc = joint_ensure(c, "prepare_frames"); if (rc) return rc; }      // (before the capture begins)
-    rc = capture_frames(c, count, mode, &g.block, &g.block_exec);
+    rc = capture_frames(c, count, &g.block, &g.block_exec, [=] { replay_one_frame(c, mode); });
     if (rc) return rc;
     g.block_frames = count;
     return SRUKF_OK;
@@ -1220,11 +1183,7 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
     const KDims& d = c->d;
     const bool joint = mode == SRUKF_UPDATE_JOINT;
     if (joint) { const int rcj = joint_ensure(c, "run_frames_async"); if (rcj) return rcj; }      // (before any capture begins)
-    step_commit_motion(c); step_state_replaced(c);
-    if (c->fs_seq_step) {                                      // the step-wise fast path pointed the frame scalars at its own three poses
-        hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, c->stream, c->fs, c->odo_seq, c->seqF, c->p.a1, c->p.a2, c->p.a3, c->p.a4);
-        c->fs_seq_step = false;
-    }
+    replay_prologue(c);
     // traj rows are indexed by the absolute frame counter; offset so that frame `first` lands in row 0
     double* traj = d_traj ? d_traj - (size_t)8 * first : nullptr;
     int clear = c->async_pending ? 0 : 1;
@@ -1252,44 +1211,27 @@ int srukf_run_frames_async(srukf_ctx* c, int first, int count, int mode, double*
         // captured frame replays for all frames: the 45 launches cost one hipGraphLaunch on the host
         ReplayGraphs& g = replay_graphs(c, mode);               // (per mode: a BATCHED call never replays a captured JOINT frame, nor the other way round)
         if (!g.one_exec) {
-            int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec); if (rc) return rc;
-            // and a graph of SRUKF_GRAPH_FRAMES consecutive frames: one host launch per 8 frames keeps the host
-            // ahead of the device when several filters share one host thread
-            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec); if (rc) return rc;
+            const auto frame = [=] { replay_one_frame(c, mode); };
+            int rc = capture_frames(c, 1, &g.one, &g.one_exec, frame); if (rc) return rc;
+            rc = capture_frames(c, SRUKF_GRAPH_FRAMES, &g.eight, &g.eight_exec, frame); if (rc) return rc;      // (replay_launch_graphs)
         }
         if (g.block_exec && g.block_frames == count) HIPCHK(c, hipGraphLaunch(g.block_exec, c->stream));   // srukf_prepare_frames / srukf_prepare_frames_mode
-        else {
-            int f = 0;
-            for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(g.eight_exec, c->stream));
-            for (; f < count; f++) HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
-        }
+        else { const int rc = replay_launch_graphs(c, g, count); if (rc) return rc; }
     } else {
         for (int f = 0; f < count; f++) replay_one_frame(c, mode);
     }
     // fp32 storage in "fused tail" mode: S and X are rounded as they are written; the float copies (srukf_get_state_f32) once per run
     if (storage_f32_like(c) && ff.fused_tail()) quantize_state(c);
-    c->async_pending = true;
-    c->phase = 0; c->frame_updated = false;
-    HIPCHK(c, hipGetLastError());
-    return SRUKF_OK;
+    return replay_epilogue(c);
 }
 
 // Synchronous form (BATCHED or JOINT frames).  Unlike the asynchronous replay it never returns SRUKF_ERR_CLAMP_PENDING: the state before the
 // block is kept, and when a frame is flagged (theta clamp of the modified Cholesky, SLAM.cpp:2279-2285, or an abandoned
 // persistent launch) the block is rewound to that state, the frames before the flagged one are replayed, the flagged
-// frame runs on the exact path, and the replay continues behind it.
-int srukf_run_frames(srukf_ctx* c, int first, int count, int mode, double* traj_host)
+// frame runs on the exact path, and the replay continues behind it.  This is that loop (dt: the block's trajectory rows on the device); the entry is below
+static int run_frames_recovering(srukf_ctx* c, int first, int count, int mode, double* dt)
 {
-    if (!c || count < 1) return SRUKF_ERR_BAD_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t np = c->d.np;
-    if (!c->ckS) {
-        if (srukf_dmalloc((void**)&c->ckS, sizeof(double) * np * np) != hipSuccess || srukf_dmalloc((void**)&c->ckX, sizeof(double) * np) != hipSuccess) {
-            c->err = "run_frames: out of device memory (checkpoint)"; return SRUKF_ERR_NOMEM;
-        }
-    }
-    double* dt = nullptr;
-    HIPCHK(c, srukf_dmalloc((void**)&dt, sizeof(double) * 8 * (size_t)count));
     bool ck_canon = c->null_canonical;
     auto checkpoint = [&](bool save) {
         hipMemcpyAsync(save ? c->ckS : c->S, save ? c->S : c->ckS, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream);
@@ -1329,498 +1271,20 @@ int srukf_run_frames(srukf_ctx* c, int first, int count, int mode, double* traj_
         hipStreamSynchronize(c->stream);
         c->err = why;
     }
-    if (traj_host && rc == SRUKF_OK) hipMemcpy(traj_host, dt, sizeof(double) * 8 * (size_t)count, hipMemcpyDeviceToHost);
-    srukf_dfree(dt);
     return rc;
 }
 
-// ---- image runs: the staged replay with the association on the device ----
-
-// The gray frames of the staged sequence, copied to the device once; with them the per-frame record, the scratch for the Cartesian points and the block's checkpoint
-// (X, S, matchPatch): everything an image run needs that can fail for want of memory is allocated here, outside any capture.
-int srukf_stage_images(srukf_ctx* c, int F, const unsigned char* gray)
+int srukf_run_frames(srukf_ctx* c, int first, int count, int mode, double* traj_host)
 {
-    if (!c || F < 1 || !gray) return SRUKF_ERR_BAD_ARG;
-    if (!c->odo_seq) { c->err = "stage_images: no staged sequence (srukf_stage_sequence first)"; return SRUKF_ERR_SEQUENCE; }
-    if (F != c->seqF) { c->err = "stage_images: n_frames is not the staged sequence's"; return SRUKF_ERR_DIM_MISMATCH; }
-    if (c->d.N < 1) { c->err = "stage_images: the map is empty"; return SRUKF_ERR_DIM_MISMATCH; }
+    if (!c || count < 1) return SRUKF_ERR_BAD_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));             // frames in flight may still read the images staged before
-    images_drop(c, c->stream);
-    int rc = ensure_appearance(c); if (rc) return rc;
-    ImageReplay& im = c->img;
-    const size_t N = c->d.N, np = c->d.np, img = (size_t)c->p.image_w * (size_t)c->p.image_h, f = (size_t)F;
-    if (srukf_dmalloc(&im.images, f * img) != hipSuccess || srukf_dmalloc(&im.corr_seq, sizeof(double) * f * N) != hipSuccess ||
-        srukf_dmalloc(&im.vis_seq, sizeof(int) * f * N) != hipSuccess || srukf_dmalloc(&im.h_seq, sizeof(double) * f * 2 * N) != hipSuccess ||
-        srukf_dmalloc(&im.xyz, sizeof(double) * 3 * N) != hipSuccess || srukf_dmalloc(&im.ck_tmpl, N * PT_TMPL_STRIDE) != hipSuccess ||
-        srukf_dmalloc(&im.ckS, sizeof(double) * np * np) != hipSuccess || srukf_dmalloc(&im.ckX, sizeof(double) * np) != hipSuccess) {
-        (void)hipGetLastError();
-        images_drop(c, c->stream);
-        c->err = "stage_images: out of device memory"; return SRUKF_ERR_NOMEM;
-    }
-    im.frames = F;
-    hipError_t e = hipMemcpy(im.images, gray, f * img, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(im.corr_seq, 0, sizeof(double) * f * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.vis_seq, 0, sizeof(int) * f * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.h_seq, 0, sizeof(double) * f * 2 * N, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { images_drop(c, c->stream); c->err = std::string("stage_images: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
-    return SRUKF_OK;
-}
-
-// the state the block of image frames started from comes back: X, S and the matchPatch array (its pixels persist from frame to frame, so a flagged block must not
-// leave its own behind), as srukf_run_frames' checkpoint comes back.  Keeps c->err
-static void images_restore(srukf_ctx* c)
-{
-    ImageReplay& im = c->img;
     const size_t np = c->d.np;
-    const std::string why = c->err;
-    hipMemcpyAsync(c->S, im.ckS, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream);
-    hipMemcpyAsync(c->X, im.ckX, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream);
-    hipMemcpyAsync(c->app_tmpl, im.ck_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream);
-    if (im.pol_state) {                                        // the policy state comes back too; the rows the block's frames wrote are no verdicts any more: zero, as unwritten rows are
-        hipMemcpyAsync(im.pol_state, im.pol_ck, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyDeviceToDevice, c->stream);
-        hipMemsetAsync(im.pol_verdict, 0, sizeof(int) * (size_t)im.frames * (size_t)c->d.N, c->stream);
-        hipMemsetAsync(im.pol_sum, 0, sizeof(srukf_policy_summary) * (size_t)im.frames, c->stream);
-    }
-    if (im.rs_flags) {                                         // the consensus record: what the block's frames wrote does not stand either
-        const size_t fN = (size_t)im.frames * (size_t)c->d.N;
-        hipMemsetAsync(im.rs_flags, 0, sizeof(int) * fN, c->stream);
-        hipMemsetAsync(im.rs_rvotes, 0, sizeof(int) * fN, c->stream);
-        hipMemsetAsync(im.rs_dist, 0, sizeof(double) * fN, c->stream);
-        hipMemsetAsync(im.rs_sum, 0, sizeof(RansacSummary) * (size_t)im.frames, c->stream);
-    }
-    if (c->null_canonical != im.ck_canon) { c->null_canonical = im.ck_canon; drop_graphs(c); }
-    shadow_rebuild(c);
-    hipStreamSynchronize(c->stream);
-    c->err = why;
-}
-
-// what a checked image run needs beyond srukf_stage_images' buffers, allocated on the first one and outside any capture: the checked record (zeroed), the
-// parameters' place on the device, and the filter's score buffer if no srukf_associate_checked has made it.  Captured checked frames hold the score buffer's
-// pointer: they are dropped when it is not the one they were captured with (match_drop has run in between)
-static int images_checked_ensure(srukf_ctx* c, const char* who)
-{
-    ImageReplay& im = c->img;
-    int rc = match_ensure(c, who); if (rc) return rc;
-    if (im.chk_scores != c->match_scores) {
-        for (int m = 0; m < 2; m++) if (im.chk_graphs[m].one_exec || im.rs_graphs[0][1][m].one_exec || im.rs_graphs[1][1][m].one_exec) { HIPCHK(c, hipStreamSynchronize(c->stream)); drop_graphs(c); break; }
-        im.chk_scores = c->match_scores;
-    }
-    if (im.corr2_seq) return SRUKF_OK;
-    const size_t N = c->d.N, f = (size_t)im.frames;
-    hipError_t e = srukf_dmalloc(&im.corr2_seq, sizeof(double) * f * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.z2_seq, sizeof(double) * f * 2 * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.flags_seq, sizeof(int) * f * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.match_args, sizeof(MatchArgs));
-    if (e == hipSuccess) e = hipMemsetAsync(im.corr2_seq, 0, sizeof(double) * f * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.z2_seq, 0, sizeof(double) * f * 2 * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.flags_seq, 0, sizeof(int) * f * N, c->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* b : { (void*)im.corr2_seq, (void*)im.z2_seq, (void*)im.flags_seq, (void*)im.match_args }) if (b) srukf_dfree_on(b, c->stream);
-        im.corr2_seq = im.z2_seq = nullptr; im.flags_seq = nullptr; im.match_args = nullptr;
-        c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
-    }
-    return SRUKF_OK;
-}
-
-// what a searching image run needs beyond srukf_stage_images' buffers, allocated in front of the first one and outside any capture: the search record for the
-// archive's L (zeroed) and the parameters' place on the device.  srukf_archive_set drops both with the captured searching frames (images_archive_drop)
-static int images_archive_ensure(srukf_ctx* c, const char* who)
-{
-    ImageReplay& im = c->img;
-    if (im.ar_rec) return SRUKF_OK;
-    const int L = c->archive.L;
-    const size_t bytes = sizeof(double) * image_archive_record((size_t)im.frames, (size_t)L).doubles;
-    hipError_t e = srukf_dmalloc(&im.ar_rec, bytes);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.ar_args, sizeof(ArchiveArgs));
-    if (e == hipSuccess) e = hipMemsetAsync(im.ar_rec, 0, bytes, c->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* b : { (void*)im.ar_rec, (void*)im.ar_args }) if (b) srukf_dfree_on(b, c->stream);
-        im.ar_rec = nullptr; im.ar_args = nullptr;
-        c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
-    }
-    im.ar_L = L;
-    return SRUKF_OK;
-}
-
-// what the map policy behind image frames needs beyond srukf_stage_images' buffers, allocated in front of the first policy run or by
-// srukf_images_set_policy_state, outside any capture: the per-landmark state and its checkpoint copy, the record and the parameters' place on the device, all zeroed
-static int images_policy_ensure(srukf_ctx* c, const char* who)
-{
-    ImageReplay& im = c->img;
-    if (im.pol_state) return SRUKF_OK;
-    const size_t N = c->d.N, f = (size_t)im.frames;
-    hipError_t e = srukf_dmalloc(&im.pol_state, sizeof(srukf_policy_state) * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.pol_ck, sizeof(srukf_policy_state) * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.pol_verdict, sizeof(int) * f * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.pol_sum, sizeof(srukf_policy_summary) * f);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.pol_args, sizeof(srukf_policy_params));
-    if (e == hipSuccess) e = hipMemsetAsync(im.pol_state, 0, sizeof(srukf_policy_state) * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.pol_ck, 0, sizeof(srukf_policy_state) * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.pol_verdict, 0, sizeof(int) * f * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.pol_sum, 0, sizeof(srukf_policy_summary) * f, c->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* b : { (void*)im.pol_state, (void*)im.pol_ck, (void*)im.pol_verdict, (void*)im.pol_sum, (void*)im.pol_args }) if (b) srukf_dfree_on(b, c->stream);
-        im.pol_state = im.pol_ck = nullptr; im.pol_verdict = nullptr; im.pol_sum = nullptr; im.pol_args = nullptr;
-        c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
-    }
-    return SRUKF_OK;
-}
-
-// what the consensus inside image frames needs beyond srukf_stage_images' buffers, allocated in front of the first run with the switch on,
-// outside any capture: the scratch of the two launches, the record (zeroed) and the threshold's place on the device
-static int images_ransac_ensure(srukf_ctx* c, const char* who)
-{
-    ImageReplay& im = c->img;
-    if (im.rs_D) return SRUKF_OK;
-    const size_t N = c->d.N, f = (size_t)im.frames;
-    hipError_t e = srukf_dmalloc(&im.rs_D, sizeof(double) * N * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_F, (N * N + 7) / 8 * 8);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_votes, sizeof(int) * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_flags, sizeof(int) * f * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_rvotes, sizeof(int) * f * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_dist, sizeof(double) * f * N);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_sum, sizeof(RansacSummary) * f);
-    if (e == hipSuccess) e = srukf_dmalloc(&im.rs_args, sizeof(RansacArgs));
-    if (e == hipSuccess) e = hipMemsetAsync(im.rs_D, 0, sizeof(double) * N * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.rs_F, 0, (N * N + 7) / 8 * 8, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.rs_votes, 0, sizeof(int) * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.rs_flags, 0, sizeof(int) * f * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.rs_rvotes, 0, sizeof(int) * f * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.rs_dist, 0, sizeof(double) * f * N, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(im.rs_sum, 0, sizeof(RansacSummary) * f, c->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* b : { (void*)im.rs_D, (void*)im.rs_F, (void*)im.rs_votes, (void*)im.rs_flags, (void*)im.rs_rvotes, (void*)im.rs_dist, (void*)im.rs_sum, (void*)im.rs_args }) if (b) srukf_dfree_on(b, c->stream);
-        im.rs_D = im.rs_dist = nullptr; im.rs_F = nullptr; im.rs_votes = im.rs_flags = im.rs_rvotes = nullptr; im.rs_sum = nullptr; im.rs_args = nullptr;
-        c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
-    }
-    return SRUKF_OK;
-}
-
-// the map policy's verdict behind staged frame `frame` (srukf_images_policy): an eager launch with the frame index as a kernel argument — fs->frame has advanced
-// behind the tail, and a captured frame could not carry the index.  It reads the posterior X and row `frame` of the association's record
-static void issue_image_policy(srukf_ctx* c, int frame)
-{
-    const ImageReplay& im = c->img;
-    ProfScope ps(c, KC_MISC, 0, 80.0 * c->d.N);
-    launch_map_policy_staged(c->stream, c->d, c->p, im.pol_args, StagedPolicy{ c->X, im.frames, im.h_seq, im.vis_seq, c->z_seq, c->m_seq, im.pol_state, im.pol_verdict, im.pol_sum }, frame);
-}
-
-// srukf_run_images_async (chk null) and srukf_run_images_checked_async (chk: the validated parameters): one body, the frames differ in the association launch
-static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double* d_traj, const MatchArgs* chk, const char* who)
-{
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    const std::string w = who;
-    { const int rcm = replay_mode_check(c, mode, who); if (rcm) return rcm; }
-    if (c->storage != SRUKF_STORAGE_F64) { c->err = w + ": image runs are available in SRUKF_STORAGE_F64 only"; return SRUKF_ERR_UNSUPPORTED; }
-    ImageReplay& im = c->img;
-    if (!im.images) { c->err = w + ": no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (!c->odo_seq || im.frames != c->seqF || first + count > c->seqF) { c->err = "frames outside the staged sequence"; return SRUKF_ERR_DIM_MISMATCH; }
-    if (c->async_pending && !im.pending) { c->err = w + ": frames of srukf_run_frames_async are in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
-    c->joint_bad_host = false;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (mode == SRUKF_UPDATE_JOINT) { const int rcj = joint_ensure(c, who); if (rcj) return rcj; }      // (before any capture begins)
-    const bool checked = chk != nullptr;
-    if (checked) {
-        const int rce = images_checked_ensure(c, who); if (rce) return rce;                           // (idem)
-        srukf_launch_set_match_args(c->stream, im.match_args, *chk);      // in stream order: behind the frames of an earlier run of the block, in front of this run's
-        im.checked = true; c->match_valid = true;
-    }
-    // the archive search behind every frame (srukf_images_search_archive).  An empty archive: a plain run, and a record of L = 0
-    const bool search = c->img_search && c->archive.L > 0;
-    if (c->img_search) {
-        if (search) {
-            const int rca = images_archive_ensure(c, who); if (rca) return rca;                        // (idem)
-            launch_set_archive_args(c->stream, im.ar_args, c->img_search_args);      // in stream order, as the checked run's parameters
-            im.searching = true;
-        }
-        im.ar_valid = true;
-    }
-    // the map policy's verdict behind every frame (srukf_images_policy): no captured frames of its own — the run is issued frame by frame, the one-frame graph
-    // followed by the policy launch
-    const bool policy = c->img_policy;
-    if (policy) {
-        const int rcp = images_policy_ensure(c, who); if (rcp) return rcp;                            // (idem)
-        launch_set_policy_params(c->stream, im.pol_args, c->img_policy_args);      // in stream order, as the checked run's parameters
-        im.pol_valid = true;
-    }
-    // the 1-point RANSAC consensus inside every frame (srukf_images_ransac): captured frames of their own
-    const bool ransac = c->img_ransac;
-    if (ransac) {
-        const int rcr = images_ransac_ensure(c, who); if (rcr) return rcr;                            // (idem)
-        launch_set_ransac_args(c->stream, im.rs_args, RansacArgs{ c->img_ransac_thr });      // in stream order, as the checked run's parameters
-        im.rs_valid = true;
-    }
-    step_commit_motion(c); step_state_replaced(c);
-    if (c->fs_seq_step) {                                      // the step-wise fast path pointed the frame scalars at its own three poses
-        hipLaunchKernelGGL(k_set_seq, dim3(1), dim3(1), 0, c->stream, c->fs, c->odo_seq, c->seqF, c->p.a1, c->p.a2, c->p.a3, c->p.a4);
-        c->fs_seq_step = false;
-    }
-    if (!im.pending) {
-        // the block's checkpoint: a block is every image run since the last srukf_synchronize
-        const size_t np = c->d.np;
-        HIPCHK(c, hipMemcpyAsync(im.ckS, c->S, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(im.ckX, c->X, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(im.ck_tmpl, c->app_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream));
-        if (im.pol_state) HIPCHK(c, hipMemcpyAsync(im.pol_ck, im.pol_state, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyDeviceToDevice, c->stream));
-        im.ck_canon = c->null_canonical;
-    }
-    double* traj = d_traj ? d_traj - (size_t)8 * first : nullptr;
-    int clear = c->async_pending ? 0 : 1;
-    if (c->red_r > 0 && !c->null_canonical) {
-        // null rows that are not (yet) sqrt(EPSILON) e_k: the run's first frame eagerly, as in srukf_run_frames_async (the plain form reads the rows as they are)
-        launch_set_run(c->stream, c->fs, first, clear, traj);
-        replay_one_image_frame(c, mode, checked, search, ransac);
-        if (policy) issue_image_policy(c, first);
-        set_null_canonical(c);
-        c->async_pending = true; im.pending = true; c->phase = 0; c->frame_updated = false; clear = 0;
-        first += 1; count -= 1;
-        HIPCHK(c, hipGetLastError());
-        if (count == 0) return SRUKF_OK;
-    }
-    launch_set_run(c->stream, c->fs, first, clear, traj);
-    if (c->use_graph && !c->profiling) {
-        // (image frames only: never a captured frame without the association; plain and checked frames each have their own)
-        // (searching frames: their own again, per kind of image run)
-        // (frames with the consensus in them: their own again, per kind of image run and with or without the search)
-        ReplayGraphs& g = (ransac ? im.rs_graphs[search ? 1 : 0][checked ? 1 : 0] : search ? im.ar_graphs[checked ? 1 : 0] : checked ? im.chk_graphs : im.graphs)[mode == SRUKF_UPDATE_JOINT ? 1 : 0];
-        if (!g.one_exec) { const int rc = capture_frames(c, 1, mode, &g.one, &g.one_exec, true, checked, search, ransac); if (rc) return rc; }
-        if (!policy && !g.eight_exec) { const int rc = capture_frames(c, SRUKF_GRAPH_FRAMES, mode, &g.eight, &g.eight_exec, true, checked, search, ransac); if (rc) return rc; }      // (a policy run launches single frames only)
-        int f = 0;
-        if (policy) for (; f < count; f++) { HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream)); issue_image_policy(c, first + f); }
-        for (; f + SRUKF_GRAPH_FRAMES <= count; f += SRUKF_GRAPH_FRAMES) HIPCHK(c, hipGraphLaunch(g.eight_exec, c->stream));
-        for (; f < count; f++) HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
-    } else {
-        for (int f = 0; f < count; f++) { replay_one_image_frame(c, mode, checked, search, ransac); if (policy) issue_image_policy(c, first + f); }
-    }
-    c->async_pending = true; im.pending = true;
-    c->phase = 0; c->frame_updated = false;
-    HIPCHK(c, hipGetLastError());
-    return SRUKF_OK;
-}
-
-int srukf_run_images_async(srukf_ctx* c, int first, int count, int mode, double* d_traj) { return run_images_issue(c, first, count, mode, d_traj, nullptr, "run_images_async"); }
-
-// ---- checked image runs: the ambiguity veto and the sub-pixel peak inside an image run ----
-// srukf_associate_checked's parameter rules (params null: its defaults)
-static int checked_args(srukf_ctx* c, const srukf_match_params* params, MatchArgs* ma)
-{
-    srukf_match_params mp = { 0.8, 0.9, 4, 0 };
-    if (params) mp = *params;
-    if (!std::isfinite(mp.ratio) || mp.ratio <= 0.0) { c->err = "run_images_checked: ratio must be finite and positive"; return SRUKF_ERR_BAD_ARG; }
-    if (mp.exclusion < 1 || mp.exclusion > 20) { c->err = "run_images_checked: exclusion outside [1, 20]"; return SRUKF_ERR_BAD_ARG; }
-    if (!std::isfinite(mp.corr_threshold)) { c->err = "run_images_checked: corr_threshold is not finite"; return SRUKF_ERR_BAD_ARG; }
-    *ma = { .corr_threshold = mp.corr_threshold, .ratio = mp.ratio, .exclusion = mp.exclusion, .subpixel = mp.subpixel };
-    return SRUKF_OK;
-}
-
-int srukf_run_images_checked_async(srukf_ctx* c, int first, int count, int mode, const srukf_match_params* params, double* d_traj)
-{
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    MatchArgs ma;
-    const int rc = checked_args(c, params, &ma); if (rc) return rc;
-    return run_images_issue(c, first, count, mode, d_traj, &ma, "run_images_checked_async");
-}
-
-// Synchronous form: as srukf_run_images, no recovery inside the call
-int srukf_run_images_checked(srukf_ctx* c, int first, int count, int mode, const srukf_match_params* params, double* traj_host)
-{
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    double* dt = nullptr;
-    HIPCHK(c, srukf_dmalloc((void**)&dt, sizeof(double) * 8 * (size_t)count));
-    int rc = srukf_run_images_checked_async(c, first, count, mode, params, dt);
-    if (rc == SRUKF_OK) rc = srukf_synchronize(c);
-    if (traj_host && rc == SRUKF_OK) hipMemcpy(traj_host, dt, sizeof(double) * 8 * (size_t)count, hipMemcpyDeviceToHost);
-    srukf_dfree(dt);
-    return rc;
-}
-
-// rows [first, first + count) of the checked record, after waiting for the stream like srukf_get_image_matches.  Rows no checked run has written are zero (all of
-// them before the first checked run); a row a plain image run wrote after a checked one keeps the checked run's values
-int srukf_get_image_checks(srukf_ctx* c, int first, int count, double* corr2, double* z2, int* flags)
-{
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_checks: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_checks: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
-    if (!im.corr2_seq) {
-        if (corr2) memset(corr2, 0, sizeof(double) * m * N);
-        if (z2) memset(z2, 0, sizeof(double) * m * 2 * N);
-        if (flags) memset(flags, 0, sizeof(int) * m * N);
-        return SRUKF_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (corr2) HIPCHK(c, hipMemcpy(corr2, im.corr2_seq + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
-    if (z2) HIPCHK(c, hipMemcpy(z2, im.z2_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
-    if (flags) HIPCHK(c, hipMemcpy(flags, im.flags_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    return SRUKF_OK;
-}
-
-// rows [first, first + count) of the record the searching image runs wrote (srukf_images_search_archive), after waiting for the stream like srukf_get_image_matches.
-// Rows no searching run has written are zero.  No record (no searching run since the images were staged or the archive was set; a flagged block restored since the
-// last one): SRUKF_ERR_SEQUENCE, the rule of srukf_get_match_scores
-int srukf_get_image_archive(srukf_ctx* c, int first, int count, int* L, double* h, double* Si, int* visible, double* z, int* matched, double* corr, int* hits)
-{
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_archive: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (!im.ar_valid) { c->err = "get_image_archive: no record of a searching image run (srukf_images_search_archive; a flagged block leaves none)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_archive: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    const size_t n = im.ar_rec ? (size_t)im.ar_L : 0, a = (size_t)first, m = (size_t)count;
-    if (L) *L = (int)n;
-    if (hits) memset(hits, 0, sizeof(int) * m);
-    if (n == 0) return SRUKF_OK;                               // (an empty archive: the runs were plain ones)
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const ImageArchiveRecord r = image_archive_record((size_t)im.frames, n);
-    const double* rec = im.ar_rec; const int* reci = (const int*)(rec + r.ints);
-    if (h) HIPCHK(c, hipMemcpy(h, rec + r.h + a * 2 * n, sizeof(double) * m * 2 * n, hipMemcpyDeviceToHost));
-    if (Si) HIPCHK(c, hipMemcpy(Si, rec + r.Si + a * 4 * n, sizeof(double) * m * 4 * n, hipMemcpyDeviceToHost));
-    if (z) HIPCHK(c, hipMemcpy(z, rec + r.z + a * 2 * n, sizeof(double) * m * 2 * n, hipMemcpyDeviceToHost));
-    if (corr) HIPCHK(c, hipMemcpy(corr, rec + r.corr + a * n, sizeof(double) * m * n, hipMemcpyDeviceToHost));
-    if (visible) HIPCHK(c, hipMemcpy(visible, reci + r.vis_i + a * n, sizeof(int) * m * n, hipMemcpyDeviceToHost));
-    if (matched) HIPCHK(c, hipMemcpy(matched, reci + r.m_i + a * n, sizeof(int) * m * n, hipMemcpyDeviceToHost));
-    if (hits) HIPCHK(c, hipMemcpy(hits, reci + r.hits_i + a, sizeof(int) * m, hipMemcpyDeviceToHost));
-    return SRUKF_OK;
-}
-
-// ---- the map policy's verdict behind image frames (the kernel and the switch: srukf_policy.hip) ----
-// the counters map[] holds (cslam.cpp:713-723) become the device state the next policy run advances
-int srukf_images_set_policy_state(srukf_ctx* c, const srukf_policy_state* state)
-{
-    if (!c || !state) return SRUKF_ERR_BAD_ARG;
-    ImageReplay& im = c->img;
-    if (!im.images) { c->err = "images_set_policy_state: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (c->async_pending) { c->err = "images_set_policy_state: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
-    HIPCHK(c, hipSetDevice(c->device));
-    const int rc = images_policy_ensure(c, "images_set_policy_state"); if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(im.pol_state, state, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                 // (pageable host memory)
-    im.ck_clean = false;                                        // the checkpoint's copy of the state is not this one: no srukf_images_rewind behind a seed
-    return SRUKF_OK;
-}
-
-// rows [first, first + count) of the policy record (what SLAM.cpp:2443-2459 and 556 would decide behind each frame), after waiting for the stream like
-// srukf_get_image_matches; the device state as it stands; the lowest frame of the range that asks for a map change
-int srukf_get_image_policy(srukf_ctx* c, int first, int count, int* verdict, srukf_policy_summary* summary, srukf_policy_state* state_out, int* first_change)
-{
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_policy: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (!im.pol_state || !im.pol_valid) { c->err = "get_image_policy: no record of a policy run (srukf_images_policy)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_policy: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
-    if (verdict) HIPCHK(c, hipMemcpy(verdict, im.pol_verdict + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (state_out) HIPCHK(c, hipMemcpy(state_out, im.pol_state, sizeof(srukf_policy_state) * N, hipMemcpyDeviceToHost));
-    if (summary || first_change) {
-        std::vector<srukf_policy_summary> sm(m);
-        HIPCHK(c, hipMemcpy(sm.data(), im.pol_sum + a, sizeof(srukf_policy_summary) * m, hipMemcpyDeviceToHost));
-        if (summary) memcpy(summary, sm.data(), sizeof(srukf_policy_summary) * m);
-        if (first_change) { *first_change = -1; for (size_t q = 0; q < m; q++) if (sm[q].change) { *first_change = first + (int)q; break; } }
-    }
-    return SRUKF_OK;
-}
-
-// ---- the 1-point RANSAC consensus inside image frames (the kernels: srukf_ransac.hip) ----
-// The switch: on the handle, like srukf_images_policy.  Touches no device: the threshold reaches it in stream order in front of the next image run (run_images_issue)
-int srukf_images_ransac(srukf_ctx* c, int on, double threshold)
-{
-    if (!c) return SRUKF_ERR_BAD_ARG;
-    if (on && (!std::isfinite(threshold) || threshold <= 0.0)) { c->err = "images_ransac: threshold must be finite and positive"; return SRUKF_ERR_BAD_ARG; }
-    if (c->async_pending) { c->err = "images_ransac: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
-    c->img_ransac = on != 0;
-    if (on) c->img_ransac_thr = threshold;
-    return SRUKF_OK;
-}
-
-// rows [first, first + count) of the consensus record, after waiting for the stream like srukf_get_image_matches; the lowest frame of the range whose consensus
-// dropped a match
-int srukf_get_image_ransac(srukf_ctx* c, int first, int count, int* flags, int* votes, double* dist, int* best, int* n_active, int* n_low, int* first_outlier)
-{
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_ransac: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (!im.rs_flags || !im.rs_valid) { c->err = "get_image_ransac: no record of a run with the consensus in it (srukf_images_ransac)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_ransac: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
-    if (flags) HIPCHK(c, hipMemcpy(flags, im.rs_flags + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (votes) HIPCHK(c, hipMemcpy(votes, im.rs_rvotes + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (dist) HIPCHK(c, hipMemcpy(dist, im.rs_dist + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
-    if (best || n_active || n_low || first_outlier) {
-        std::vector<RansacSummary> sm(m);
-        HIPCHK(c, hipMemcpy(sm.data(), im.rs_sum + a, sizeof(RansacSummary) * m, hipMemcpyDeviceToHost));
-        if (first_outlier) *first_outlier = -1;
-        for (size_t q = 0; q < m; q++) {
-            if (best) best[q] = sm[q].best;
-            if (n_active) n_active[q] = sm[q].n_active;
-            if (n_low) n_low[q] = sm[q].n_low;
-            if (first_outlier && *first_outlier < 0 && sm[q].outlier) *first_outlier = first + (int)q;
+    if (!c->ckS) {
+        if (srukf_dmalloc((void**)&c->ckS, sizeof(double) * np * np) != hipSuccess || srukf_dmalloc((void**)&c->ckX, sizeof(double) * np) != hipSuccess) {
+            c->err = "run_frames: out of device memory (checkpoint)"; return SRUKF_ERR_NOMEM;
         }
     }
-    return SRUKF_OK;
-}
-
-// The checkpoint of the image block the last srukf_synchronize ended clean comes back (X, S, the matchPatch array, the policy state: images_restore), so that a host
-// can stop a block at the frame whose verdict asks for a map change (SLAM.cpp:552-562) by running the frames up to it again.  Only while nothing has written X, S or
-// a matchPatch since that srukf_synchronize (ImageReplay::ck_clean)
-int srukf_images_rewind(srukf_ctx* c)
-{
-    if (!c) return SRUKF_ERR_BAD_ARG;
-    ImageReplay& im = c->img;
-    if (c->async_pending) { c->err = "images_rewind: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
-    if (!im.images || !im.ck_clean) { c->err = "images_rewind: no image block that srukf_synchronize ended clean, or the state has been written since"; return SRUKF_ERR_SEQUENCE; }
-    HIPCHK(c, hipSetDevice(c->device));
-    step_state_replaced(c);                                     // (clears ck_clean: one rewind per block)
-    c->err.clear();
-    images_restore(c);
-    c->phase = 0; c->frame_updated = false;
-    HIPCHK(c, hipGetLastError());
-    return SRUKF_OK;
-}
-
-// Synchronous form.  No recovery inside the call: a flagged block comes back to its checkpoint (srukf_synchronize) and SRUKF_ERR_CLAMP_PENDING is returned
-int srukf_run_images(srukf_ctx* c, int first, int count, int mode, double* traj_host)
-{
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    double* dt = nullptr;
-    HIPCHK(c, srukf_dmalloc((void**)&dt, sizeof(double) * 8 * (size_t)count));
-    int rc = srukf_run_images_async(c, first, count, mode, dt);
-    if (rc == SRUKF_OK) rc = srukf_synchronize(c);
-    if (traj_host && rc == SRUKF_OK) hipMemcpy(traj_host, dt, sizeof(double) * 8 * (size_t)count, hipMemcpyDeviceToHost);
-    srukf_dfree(dt);
-    return rc;
-}
-
-// rows [first, first + count) of what the association wrote (rows no image run has written: z / matched as staged, the rest zero).  Waits for the stream only: flags
-// of frames in flight are still srukf_synchronize's to report
-int srukf_get_image_matches(srukf_ctx* c, int first, int count, double* z, int* matched, double* corr, int* visible, double* h)
-{
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
-    const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_matches: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_matches: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
-    if (z) HIPCHK(c, hipMemcpy(z, c->z_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
-    if (matched) HIPCHK(c, hipMemcpy(matched, c->m_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (corr) HIPCHK(c, hipMemcpy(corr, im.corr_seq + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
-    if (visible) HIPCHK(c, hipMemcpy(visible, im.vis_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (h) HIPCHK(c, hipMemcpy(h, im.h_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
-    return SRUKF_OK;
+    return with_device_traj(c, count, traj_host, [=](double* dt) { return run_frames_recovering(c, first, count, mode, dt); });
 }
 
 // What the last SRUKF_ERR_CLAMP_PENDING of srukf_synchronize was about: the first flagged staged frame (frames before it

@@ -362,7 +362,7 @@ static int step_update_slow(srukf_ctx* c, const double* z, const int* matched, i
     memcpy(hm, matched, sizeof(int) * N);
     HIPCHK(c, hipMemcpyAsync(c->zcur, hs, sizeof(double) * 2 * N, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->mcur, hm, sizeof(int) * N, hipMemcpyHostToDevice, c->stream));
-    launch_set_frame(c->stream, c->fs, 0, 1);
+    launch_set_run(c->stream, c->fs, 0, 1, nullptr);
     bool exact_ran = false;
     if (mode == STEP_UPDATE_JOINT) {
         seq_pxy(c, FORM_SEPARATE_STATS);
@@ -409,7 +409,7 @@ static int step_update_slow(srukf_ctx* c, const double* z, const int* matched, i
                     rc = exact_repeat_begin(c, 0, nullptr); if (rc) return rc;
                     exact_path(c, c->G, c->S);
                     quantize_state(c);
-                    launch_set_frame(c->stream, c->fs, 0, 1);
+                    launch_set_run(c->stream, c->fs, 0, 1, nullptr);
                 }
             }
         }

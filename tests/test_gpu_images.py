@@ -1,4 +1,4 @@
-"""GPU tests of the image runs of the staged replay (srukf_stage_images / srukf_run_images* / srukf_get_image_matches, k_associate_staged; csrc/srukf_replay.hip,
+"""GPU tests of the image runs of the staged replay (srukf_stage_images / srukf_run_images* / srukf_get_image_matches, k_associate_staged; csrc/srukf_images.hip,
 srukf_assoc.hip): staged camera frames replayed with the association on the device, against the step-wise calls (predict_motion, predict_measurement,
 associate, update / update_joint), against the staged replay fed with the record the image run left, across its graph forms, and at its edges.
 

@@ -1,4 +1,4 @@
-"""GPU tests of the searching image runs (srukf_images_search_archive / srukf_get_image_archive, k_archive_search_staged; csrc/srukf_archive.hip, srukf_replay.hip;
+"""GPU tests of the searching image runs (srukf_images_search_archive / srukf_get_image_archive, k_archive_search_staged; csrc/srukf_archive.hip, srukf_images.hip;
 DESIGN.md §22): the archive search behind every frame of an image run, against the step-wise call srukf_archive_search made between the frames of a twin, bit for
 bit; that it is read-only; across its graph forms, parameter values, a replaced archive, alternation with plain runs; its refusals; a flagged block.
 

@@ -1,4 +1,4 @@
-"""GPU tests of the checked image runs (srukf_run_images_checked* / srukf_get_image_checks, k_associate_checked_staged; csrc/srukf_replay.hip, srukf_unique.hip;
+"""GPU tests of the checked image runs (srukf_run_images_checked* / srukf_get_image_checks, k_associate_checked_staged; csrc/srukf_images.hip, srukf_unique.hip;
 DESIGN.md §21): image runs whose frames take srukf_associate_checked's decisions (ambiguity veto, sub-pixel peak) — against the plain image run under neutral
 parameters, against the step-wise calls (predict_motion, predict_measurement, associate_checked, update / update_joint), against the staged replay fed with the
 record the run left, across graph forms and parameter changes, for the score maps, and at the edges.

@@ -1,8 +1,9 @@
 """GPU tests of the 1-point RANSAC consensus inside image runs (srukf_images_ransac / srukf_get_image_ransac, k_ransac_votes_staged / k_ransac_pick_staged;
-csrc/srukf_ransac.hip, srukf_replay.hip): against a twin driven step by step (predict_motion -> predict_measurement -> associate -> ransac_consensus
+csrc/srukf_ransac.hip, srukf_images.hip): against a twin driven step by step (predict_motion -> predict_measurement -> associate -> ransac_consensus
 -> update / update_joint with matched & inlier), against the run with the switch off on a clean scene, across the graph forms, with fewer than two matches, with
-the map policy and the archive search behind the frames, through a threshold change, the switch's lifetime and a flagged block; and the step-wise consensus at
-N = 260, where the shared votes body strides twice.
+the map policy and the archive search behind the frames, through a threshold change, the switch's lifetime and a flagged block; every form of an image frame
+(checked, search, ransac: ImageForm, csrc/srukf_ctx.h) on one handle against fresh handles; and the step-wise consensus at N = 260, where the shared votes body
+strides twice.
 
 Scenes: tests/test_gpu_images.py's (N = 8, seed 13, texture seed 17, 640 x 480, at most 11 frames; landmark 5 has no record, landmark 2's was cut elsewhere).
 The outlier scene is that scene with landmark OUT_LM's patch cut (DX, DY) pixels aside of its record's pixel: the association finds it that far from where the
@@ -380,7 +381,67 @@ def test_flagged_block_leaves_a_zero_record(srukf, synth):
     f.close()
 
 
-# ---- 8. the step-wise consensus beyond one stride of the votes body ----
+# ---- 8. every form of an image frame on one handle ----
+CHECKED_PAR = dict(corr_threshold=0.8, ratio=0.8, exclusion=4, subpixel=True)      # not neutral: a plain frame replayed in a checked frame's place shows
+FORM_ORDER = (0, 7, 1, 6, 2, 5, 3, 4)                            # checked | 2 search | 4 ransac: every bit alternates at least four times
+F_FORMS = 9                                                      # one eight-frame graph and one single-frame graph
+
+
+def _form_run(srukf, synth, f, form, mode):
+    """switches of `form` set, frames 0..8 run: everything the run leaves and every record the form writes, as bytes; the block rewound behind it"""
+    import test_gpu_images_archive as gia
+    from test_gpu_images_checked import _check_bytes
+    checked, search, ransac = bool(form & 1), bool(form & 2), bool(form & 4)
+    f.images_search_archive(search)
+    f.images_ransac(ransac, THR)
+    t = f.run_images_checked(0, F_FORMS, mode=mode, **CHECKED_PAR) if checked else f.run_images(0, F_FORMS, mode=mode)
+    assert f.clamp_info() == (-1, -1), form
+    out = (t.tobytes(),) + _state_bytes(f) + _record_bytes(f.get_image_matches(0, F_FORMS)) + (_patch_bytes(f),)
+    if checked: out += _check_bytes(f.get_image_checks(0, F_FORMS))
+    if search:
+        arc = f.get_image_archive(0, F_FORMS)
+        out += gia._rows(arc) + (arc["hits"].tobytes(),)
+    if ransac: out += _ransac_bytes(f.get_image_ransac(0, F_FORMS))
+    f.images_rewind()
+    return out
+
+
+def _form_filter(srukf, synth):
+    import test_gpu_archive as ga
+    import test_gpu_images_archive as gia
+    f = _filter(srukf, _outlier_case(srukf, synth), F_FORMS)
+    ga.set_archive(f, gia._archive(srukf, synth), list(gia.ALL))
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def _fresh_form(srukf, synth, form, mode):
+    """a handle that runs nothing but this form; computed once per form and mode"""
+    f = _form_filter(srukf, synth)
+    out = _form_run(srukf, synth, f, form, mode)
+    f.close()
+    return out
+
+
+@pytest.mark.parametrize("mode_name", ["BATCHED", "JOINT"])
+def test_every_form_on_one_handle_is_the_fresh_handles(srukf, synth, mode_name):
+    """the outlier scene, 9 frames (an eight-frame graph and a single frame), the archive set: the eight combinations of checked, search and ransac run one
+    behind the other on ONE handle, each rewound, leave what a fresh handle that runs only that form leaves, byte for byte — trajectory, state, match record,
+    matchPatches and every record the form writes — and again in a second round, every graph captured by then: no form replays a frame captured for another"""
+    mode = getattr(srukf, "UPDATE_" + mode_name)
+    f = _form_filter(srukf, synth)
+    for rnd in (0, 1):
+        for form in FORM_ORDER:
+            got, want = _form_run(srukf, synth, f, form, mode), _fresh_form(srukf, synth, form, mode)
+            assert len(got) == len(want) and got == want, (rnd, form, [i for i, (a, b) in enumerate(zip(got, want)) if a != b])
+    f.close()
+    # the forms differ where they should: a table index that fell back to another form's graph on both sides would still have passed above
+    base = _fresh_form(srukf, synth, 0, mode)
+    for form in (1, 4):
+        assert _fresh_form(srukf, synth, form, mode)[:8] != base[:8], form
+
+
+# ---- 9. the step-wise consensus beyond one stride of the votes body ----
 @pytest.mark.parametrize("fast", [0, 1])
 def test_stepwise_consensus_at_260_landmarks(srukf, synth, oracle, fast):
     """N = 260 against tests/np_ransac.py: the votes body strides j by 256 and nothing else in the suite has N > 256.  Seed 9's first frame from the scene's own

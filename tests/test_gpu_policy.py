@@ -1,5 +1,5 @@
 """GPU tests of the map policy's verdict (srukf_map_policy, srukf_images_policy / srukf_images_set_policy_state / srukf_get_image_policy / srukf_images_rewind;
-csrc/srukf_policy.hip, srukf_replay.hip): the step-wise kernel against the numpy restatement (tests/np_policy.py), the staged form against a twin
+csrc/srukf_policy.hip, srukf_images.hip): the step-wise kernel against the numpy restatement (tests/np_policy.py), the staged form against a twin
 driven step by step, that the policy is read-only for the filter, the rewind of a clean block, a flagged block, and the switch's lifetime.
 
 Scene: tests/test_gpu_images.py's (N = 8, seed 13, texture seed 17, 640 x 480, at most 11 frames; landmark 5 has no appearance record and never matches, landmark
