@@ -13,6 +13,7 @@
 //   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search), step-wise and behind the frames of an image run
 //                     (srukf_images_search_archive: seq_archive_search, k_archive_search_staged; srukf_get_image_archive: srukf_images.hip)
 //   srukf_policy.hip  the map policy's verdict (srukf_map_policy; srukf_images_policy: k_map_policy_staged behind the frames of an image run, issued by srukf_images.hip)
+//   srukf_snapshot.hip the state a block of image frames is resumed from (srukf_images_snapshots / srukf_images_resume: k_image_snapshot in front of every frame, issued by srukf_images.hip)
 //   srukf_joint.hip   the joint measurement update's kernels (srukf_update_joint, SRUKF_UPDATE_JOINT frames of the staged replay; host code: srukf_step.hip, srukf_replay.hip, srukf_images.hip)
 //   srukf_unique.hip  the association that keeps the score map: ambiguity veto, sub-pixel peak (srukf_associate_checked; its host code is in srukf_map.hip; srukf_run_images_checked*: srukf_images.hip)
 //   srukf_patch.h     (through srukf_launch.h) the appearance record's sizes, the checked association's buffer layouts, the search kernels' shared front
@@ -94,14 +95,14 @@ struct ArchiveState {
 // sequence's lifetime: images_drop.
 // graphs: the captured frames (one and eight) of every form of an image frame and update mode, ONE table: graphs[ImageForm::index()][0 BATCHED / 1 JOINT].  A form
 // never replays a frame captured for another one (nor a frame of srukf_run_frames*, nor the other way round): the index is the guarantee.  drop_graphs walks the table.
-// The device buffers come in five groups, each named once (image_group, srukf_images.hip): allocation, images_drop and images_archive_drop all go through those lists
+// The device buffers come in six groups, each named once (image_group, srukf_images.hip): allocation, images_drop and images_archive_drop all go through those lists
 struct ImageReplay {
     unsigned char *images = nullptr, *ck_tmpl = nullptr;
     double *corr_seq = nullptr, *h_seq = nullptr, *xyz = nullptr, *ckS = nullptr, *ckX = nullptr;
     int* vis_seq = nullptr;
     int frames = 0;
     bool pending = false, ck_canon = false;
-    ReplayGraphs graphs[8][2];
+    ReplayGraphs graphs[16][2];
     // Checked image runs (srukf_run_images_checked*), allocated by images_checked_ensure on the first one: the checked record corr2_seq [F][N],
     // z2_seq [F][2N], flags_seq [F][N] (zero until a checked run writes a row) and the parameters the checked frames read (match_args, written in stream order in front
     // of every checked run).  The captured checked frames hold the pointer of the filter's score buffer they were captured with, chk_scores.  checked: the block in
@@ -130,6 +131,13 @@ struct ImageReplay {
     double *rs_D = nullptr, *rs_dist = nullptr; unsigned char* rs_F = nullptr; int *rs_votes = nullptr, *rs_flags = nullptr, *rs_rvotes = nullptr;
     RansacSummary* rs_sum = nullptr; RansacArgs* rs_args = nullptr;
     bool rs_valid = false;
+    // The state a block is resumed from (srukf_images_snapshots / srukf_images_resume), allocated by images_snapshot_ensure in front of the first
+    // run with the switch on: two slots of { X, S, the matchPatch array, the policy state } (slot f & 1: the state frame f started from), the tags and the latch
+    // (sn_ctl), the guard's parameters (sn_args, written in stream order in front of every such run).  The block, as srukf_images_resume needs it: blk_first its first
+    // frame, blk_end the frame behind its last, blk_snap: every run of it had the switch on and began where the one before ended
+    double *sn_X[2] = { nullptr, nullptr }, *sn_S[2] = { nullptr, nullptr }; unsigned char* sn_tmpl[2] = { nullptr, nullptr }; srukf_policy_state* sn_pol[2] = { nullptr, nullptr };
+    SnapshotCtl* sn_ctl = nullptr; SnapshotArgs* sn_args = nullptr;
+    int blk_first = 0, blk_end = 0; bool blk_snap = false;
 };
 
 // ---- the context: who owns what across a map change ("who owns what across a map change") ----------------------
@@ -175,6 +183,7 @@ struct srukf_handle_scope : srukf_switches {
     srukf_policy_params img_policy_args = SRUKF_POLICY_DEFAULTS;   // ... these parameters.  Survives map changes; srukf_reset clears it
     bool img_ransac = false;               // srukf_images_ransac: every frame of every later image run holds the 1-point RANSAC consensus between association and update, with ...
     double img_ransac_thr = 8.0;           // ... this threshold.  Survives map changes and srukf_reset
+    bool img_snap = false;                 // srukf_images_snapshots: every frame of every later image run begins with k_image_snapshot.  Survives map changes and srukf_reset
     std::string err;
     // the pool allocations among the members above (det and archive: det_scratch_free / archive_free).  A new buffer of this scope is added HERE
     template <class F> void each_device_buffer(F f) const { void* b[] = { d_image, d_bgr, d_ovl }; for (void* q : b) f(q); }
@@ -471,14 +480,15 @@ struct FrameForm {
 };
 constexpr FrameForm FORM_SEPARATE_STATS{ MEAS_SEPARATE_STATS, false }, FORM_PLAIN{ MEAS_PLAIN, false }, FORM_FUSED_TAIL{ MEAS_FUSED_TAIL, true };
 // What a frame of an image run holds beyond the plain frame form (replay_one_image_frame): checked — k_associate_checked_staged in k_associate_staged's place;
-// search — the archive search behind its tail; ransac — the consensus between association and update.  index(): the form's row of ImageReplay::graphs.
+// search — the archive search behind its tail; ransac — the consensus between association and update; snap — k_image_snapshot in front of it (DESIGN.md
+// section 25).  index(): the form's row of ImageReplay::graphs.
 // The map policy is no part of the form: it has no captured frames of its own, it is an eager launch behind each frame and a property of the run (run_images_issue)
 struct ImageForm {
-    bool checked, search, ransac;
-    int index() const { return (checked ? 1 : 0) | (search ? 2 : 0) | (ransac ? 4 : 0); }
-    static ImageForm at(int index) { return ImageForm{ (index & 1) != 0, (index & 2) != 0, (index & 4) != 0 }; }
+    bool checked, search, ransac, snap;
+    int index() const { return (checked ? 1 : 0) | (search ? 2 : 0) | (ransac ? 4 : 0) | (snap ? 8 : 0); }
+    static ImageForm at(int index) { return ImageForm{ (index & 1) != 0, (index & 2) != 0, (index & 4) != 0, (index & 8) != 0 }; }
 };
-constexpr int IMAGE_FORMS = 8;
+constexpr int IMAGE_FORMS = 16;
 static_assert(sizeof(ImageReplay::graphs) / sizeof(ImageReplay::graphs[0]) == IMAGE_FORMS, "ImageReplay::graphs has one row per form of an image frame");
 // What is asked of a refactorisation  S <- gmw(S^T S - U[ub:ue] U[ub:ue]^T):  the tail of a staged or fast-path frame (no backup, the last launch ends the frame) /
 // checked (G kept in Gbak, the host reads clamp_rows afterwards) / one column of SEQUENTIAL mode (as checked, behind a reset of the gamma / xi accumulators)
@@ -553,7 +563,7 @@ int replay_epilogue(srukf_ctx* c);                     // behind what a run issu
 int with_device_traj(srukf_ctx* c, int count, double* traj_host, const std::function<int(double*)>& run);
 void images_archive_drop(srukf_map_scope* c, hipStream_t st);      // the searching image runs' record, parameters and captured frames go (the archive changes; the caller has synchronised the stream)
 void images_drop(srukf_map_scope* c, hipStream_t st);      // the staged images, their record, checkpoint and captured frames go (the caller has synchronised the stream)
-void images_restore(srukf_ctx* c);                     // srukf_synchronize: a flagged block of image frames comes back to its checkpoint
+void images_restore(srukf_ctx* c, int slot = -1, int stop = 0);      // srukf_synchronize: a flagged block of image frames comes back to its checkpoint (slot >= 0: srukf_images_resume)
 
 // ---- split form of the persistent factorisation (srukf_split.hip) ----
 bool split_form(const srukf_ctx* c, const GmwPlan& gp, bool ignore_starve = false);

@@ -13,7 +13,7 @@ namespace srukf_impl {
 // images_drop and images_archive_drop free through the same lists: a buffer added HERE is freed without anyone remembering to list it.  The sizes are the allocation's
 // (image_bytes: of one staged frame, L: the archive's; whoever only frees passes neither).  Zeroed: the records (rows no run has written read as zero) and the
 // consensus scratch; not the parameter blocks (written in stream order in front of every run that reads them), the images, xyz and the checkpoint copies
-enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_GROUPS };
+enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_SNAPSHOT, IMG_GROUPS };
 struct ImageBuf { void** p; size_t bytes; bool zero; };
 static std::vector<ImageBuf> image_group(srukf_map_scope* c, ImageGroup g, size_t image_bytes = 0, size_t L = 0)
 {
@@ -29,6 +29,10 @@ static std::vector<ImageBuf> image_group(srukf_map_scope* c, ImageGroup g, size_
                               buf(&im.pol_sum, sizeof(srukf_policy_summary) * f, true), buf(&im.pol_args, sizeof(srukf_policy_params)) };
     case IMG_RANSAC: return { buf(&im.rs_D, D * N * N, true), buf(&im.rs_F, (N * N + 7) / 8 * 8, true), buf(&im.rs_votes, I * N, true), buf(&im.rs_flags, I * f * N, true),
                               buf(&im.rs_rvotes, I * f * N, true), buf(&im.rs_dist, D * f * N, true), buf(&im.rs_sum, sizeof(RansacSummary) * f, true), buf(&im.rs_args, sizeof(RansacArgs)) };
+    case IMG_SNAPSHOT: return { buf(&im.sn_S[0], D * np * np), buf(&im.sn_S[1], D * np * np), buf(&im.sn_X[0], D * np), buf(&im.sn_X[1], D * np),
+                                buf(&im.sn_tmpl[0], N * PT_TMPL_STRIDE), buf(&im.sn_tmpl[1], N * PT_TMPL_STRIDE),
+                                buf(&im.sn_pol[0], sizeof(srukf_policy_state) * N), buf(&im.sn_pol[1], sizeof(srukf_policy_state) * N),
+                                buf(&im.sn_ctl, sizeof(SnapshotCtl)), buf(&im.sn_args, sizeof(SnapshotArgs)) };
     default: return {};
     }
 }
@@ -81,10 +85,18 @@ void images_drop(srukf_map_scope* c, hipStream_t st)
 // ransac: a frame with the 1-point RANSAC consensus in it (srukf_images_ransac) — two more launches between the association and what stands in
 // k_gain's place: c->Ut is still S^T DZ there, PxyR / h / Si / vis / X are the predicted frame's, and this frame's rows of z_seq / m_seq are written: what
 // k_ransac_votes reads.  The pick launch rewrites the m_seq row to the consensus set, which the update then takes for its matches; images_ransac_ensure has run
+// snap: a frame that keeps the state it starts from while no stop of the block is on record (srukf_images_snapshots) — k_image_snapshot in front
+// of everything else: it reads X, S, the matchPatch array, the policy state and fs->frame as the frame before left them; images_snapshot_ensure has run
 static void replay_one_image_frame(srukf_ctx* c, int mode, ImageForm form)
 {
     ImageReplay& im = c->img;
     const KDims& d = c->d;
+    if (form.snap) {
+        const size_t np = d.np, N = d.N;
+        ProfScope ps(c, KC_MISC, 0, 16.0 * np * np);
+        launch_image_snapshot(c->stream, c->fs, im.sn_args, im.sn_ctl, ImageSnapshot{ c->X, c->S, c->app_tmpl, sizeof(double) * np, sizeof(double) * np * np, N * PT_TMPL_STRIDE,
+                              sizeof(srukf_policy_state) * N, { im.sn_X[0], im.sn_X[1] }, { im.sn_S[0], im.sn_S[1] }, { im.sn_tmpl[0], im.sn_tmpl[1] }, { im.sn_pol[0], im.sn_pol[1] } });
+    }
     seq_predict_motion(c, nullptr);
     seq_predict_measurement(c, FORM_PLAIN);
     seq_pxy(c, FORM_PLAIN);
@@ -112,27 +124,30 @@ static void replay_one_image_frame(srukf_ctx* c, int mode, ImageForm form)
 
 // the state the block of image frames started from comes back: X, S and the matchPatch array (its pixels persist from frame to frame, so a flagged block must not
 // leave its own behind), as srukf_run_frames' checkpoint comes back.  Keeps c->err
-void images_restore(srukf_ctx* c)
+// slot >= 0 (srukf_images_resume): snapshot slot `slot` in the checkpoint's place — the state frame `stop` of the stack started from; rows
+// >= stop of the policy and consensus records go, the rows in front of it stand, and the null rows are what the block's frames left (stop lies behind its first frame)
+void images_restore(srukf_ctx* c, int slot, int stop)
 {
     ImageReplay& im = c->img;
-    const size_t np = c->d.np;
+    const size_t np = c->d.np, N = (size_t)c->d.N;
     const std::string why = c->err;
-    hipMemcpyAsync(c->S, im.ckS, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream);
-    hipMemcpyAsync(c->X, im.ckX, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream);
-    hipMemcpyAsync(c->app_tmpl, im.ck_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream);
+    const bool ck = slot < 0;
+    const size_t r0 = ck ? 0 : (size_t)stop, rows = (size_t)im.frames - r0;
+    hipMemcpyAsync(c->S, ck ? im.ckS : im.sn_S[slot], sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream);
+    hipMemcpyAsync(c->X, ck ? im.ckX : im.sn_X[slot], sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream);
+    hipMemcpyAsync(c->app_tmpl, ck ? im.ck_tmpl : im.sn_tmpl[slot], N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream);
     if (im.pol_state) {                                        // the policy state comes back too; the rows the block's frames wrote are no verdicts any more: zero, as unwritten rows are
-        hipMemcpyAsync(im.pol_state, im.pol_ck, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyDeviceToDevice, c->stream);
-        hipMemsetAsync(im.pol_verdict, 0, sizeof(int) * (size_t)im.frames * (size_t)c->d.N, c->stream);
-        hipMemsetAsync(im.pol_sum, 0, sizeof(srukf_policy_summary) * (size_t)im.frames, c->stream);
+        hipMemcpyAsync(im.pol_state, ck ? im.pol_ck : im.sn_pol[slot], sizeof(srukf_policy_state) * N, hipMemcpyDeviceToDevice, c->stream);
+        if (rows) hipMemsetAsync(im.pol_verdict + r0 * N, 0, sizeof(int) * rows * N, c->stream);
+        if (rows) hipMemsetAsync(im.pol_sum + r0, 0, sizeof(srukf_policy_summary) * rows, c->stream);
     }
-    if (im.rs_flags) {                                         // the consensus record: what the block's frames wrote does not stand either
-        const size_t fN = (size_t)im.frames * (size_t)c->d.N;
-        hipMemsetAsync(im.rs_flags, 0, sizeof(int) * fN, c->stream);
-        hipMemsetAsync(im.rs_rvotes, 0, sizeof(int) * fN, c->stream);
-        hipMemsetAsync(im.rs_dist, 0, sizeof(double) * fN, c->stream);
-        hipMemsetAsync(im.rs_sum, 0, sizeof(RansacSummary) * (size_t)im.frames, c->stream);
+    if (im.rs_flags && rows) {                                 // the consensus record: what the block's frames wrote does not stand either
+        hipMemsetAsync(im.rs_flags + r0 * N, 0, sizeof(int) * rows * N, c->stream);
+        hipMemsetAsync(im.rs_rvotes + r0 * N, 0, sizeof(int) * rows * N, c->stream);
+        hipMemsetAsync(im.rs_dist + r0 * N, 0, sizeof(double) * rows * N, c->stream);
+        hipMemsetAsync(im.rs_sum + r0, 0, sizeof(RansacSummary) * rows, c->stream);
     }
-    if (c->null_canonical != im.ck_canon) { c->null_canonical = im.ck_canon; drop_graphs(c); }
+    if (ck && c->null_canonical != im.ck_canon) { c->null_canonical = im.ck_canon; drop_graphs(c); }
     shadow_rebuild(c);
     hipStreamSynchronize(c->stream);
     c->err = why;
@@ -212,6 +227,16 @@ static int images_ransac_ensure(srukf_ctx* c, const char* who)
     return image_buffers_alloc(c, image_group(c, IMG_RANSAC), who);
 }
 
+// what the snapshot launch in front of image frames needs, allocated in front of the first run with the switch on, outside any capture: the
+// two slots, the tags with the latch, and the guard's parameters' place on the device.  Nothing is zeroed: the parameter launch of the block's first run sets the
+// tags and the latch in stream order
+static int images_snapshot_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    if (im.sn_ctl) return SRUKF_OK;
+    return image_buffers_alloc(c, image_group(c, IMG_SNAPSHOT), who);
+}
+
 // the map policy's verdict behind staged frame `frame` (srukf_images_policy): an eager launch with the frame index as a kernel argument — fs->frame has advanced
 // behind the tail, and a captured frame could not carry the index.  It reads the posterior X and row `frame` of the association's record
 static void issue_image_policy(srukf_ctx* c, int frame)
@@ -235,7 +260,7 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
     c->joint_bad_host = false;
     HIPCHK(c, hipSetDevice(c->device));
     if (mode == SRUKF_UPDATE_JOINT) { const int rcj = joint_ensure(c, who); if (rcj) return rcj; }      // (before any capture begins)
-    const ImageForm form{ chk != nullptr, c->img_search && c->archive.L > 0, c->img_ransac };
+    const ImageForm form{ chk != nullptr, c->img_search && c->archive.L > 0, c->img_ransac, c->img_snap };
     if (form.checked) {
         const int rce = images_checked_ensure(c, who); if (rce) return rce;                           // (idem)
         srukf_launch_set_match_args(c->stream, im.match_args, *chk);      // in stream order: behind the frames of an earlier run of the block, in front of this run's
@@ -264,6 +289,17 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         launch_set_ransac_args(c->stream, im.rs_args, RansacArgs{ c->img_ransac_thr });      // in stream order, as the checked run's parameters
         im.rs_valid = true;
     }
+    // the state in front of every frame, kept while no stop is on record (srukf_images_snapshots): captured frames of their own.  The guard's parameters go to the
+    // device in stream order, as the checked run's; a run that begins a block also closes both slots and opens the latch
+    if (form.snap) {
+        const int rcs = images_snapshot_ensure(c, who); if (rcs) return rcs;                          // (idem)
+        launch_set_snapshot_args(c->stream, im.sn_args, SnapshotArgs{ im.pending ? im.blk_first : first, policy ? im.pol_sum : nullptr, form.ransac ? im.rs_sum : nullptr, im.pol_state },
+                                 im.sn_ctl, im.pending ? 0 : 1);
+    }
+    // the block as srukf_images_resume needs it: resumable while every run of it has the switch on and begins where the one before ended
+    if (!im.pending) { im.blk_first = first; im.blk_snap = form.snap; }
+    else im.blk_snap = im.blk_snap && form.snap && first == im.blk_end;
+    im.blk_end = first + count;
     replay_prologue(c);
     if (!im.pending) {
         // the block's checkpoint: a block is every image run since the last srukf_synchronize
@@ -478,6 +514,57 @@ int srukf_images_rewind(srukf_ctx* c)
     step_state_replaced(c);                                     // (clears ck_clean: one rewind per block)
     c->err.clear();
     images_restore(c);
+    c->phase = 0; c->frame_updated = false;
+    HIPCHK(c, hipGetLastError());
+    return SRUKF_OK;
+}
+
+// ---- the state at a block's stop (the kernel: srukf_snapshot.hip) ----
+// The switch: on the handle, like srukf_images_ransac.  Touches no device: the slots are allocated in front of the next image run (run_images_issue).  Not inside
+// a block: a block is resumable only if every run of it had the switch on
+int srukf_images_snapshots(srukf_ctx* c, int on)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    if (c->async_pending || c->img.pending) { c->err = "images_snapshots: a run is in flight or a block is pending (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    c->img_snap = on != 0;
+    return SRUKF_OK;
+}
+
+// the two tags, after waiting for the stream: the staged frames whose start the slots hold (-1: none of this block, or no run with the switch on yet)
+int srukf_get_image_snapshots(srukf_ctx* c, int frames[2])
+{
+    if (!c || !frames) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    frames[0] = frames[1] = -1;
+    if (!im.sn_ctl) return SRUKF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    SnapshotCtl ctl;
+    HIPCHK(c, hipMemcpy(&ctl, im.sn_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+    frames[0] = ctl.tag[0]; frames[1] = ctl.tag[1];
+    return SRUKF_OK;
+}
+
+// The block the last srukf_synchronize ended clean is cut to its first `keep` frames without running them again: the slot that holds the state frame
+// blk_first + keep started from comes back in the checkpoint's place (images_restore).  Legal where srukf_images_rewind is, in a block whose every run had the
+// switch on; one resume or one rewind per block.  A slot that does not hold that frame: SRUKF_ERR_SEQUENCE, nothing moved, the block can still be rewound
+int srukf_images_resume(srukf_ctx* c, int keep)
+{
+    if (!c || keep < 0) return SRUKF_ERR_BAD_ARG;
+    ImageReplay& im = c->img;
+    if (c->async_pending) { c->err = "images_resume: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.images || !im.ck_clean) { c->err = "images_resume: no image block that srukf_synchronize ended clean, or the state has been written since"; return SRUKF_ERR_SEQUENCE; }
+    if (keep < 0 || keep > im.blk_end - im.blk_first) { c->err = "images_resume: keep outside [0, frames the block ran]"; return SRUKF_ERR_BAD_ARG; }
+    if (!im.blk_snap || !im.sn_ctl) { c->err = "images_resume: the block ran without srukf_images_snapshots"; return SRUKF_ERR_SEQUENCE; }
+    if (keep == 0) return srukf_images_rewind(c);
+    if (keep == im.blk_end - im.blk_first) return SRUKF_OK;       // (the state is the one behind the block's last frame)
+    const int stop = im.blk_first + keep;
+    int tags[2];
+    { const int rc = srukf_get_image_snapshots(c, tags); if (rc) return rc; }
+    if (tags[stop & 1] != stop) { c->err = "images_resume: no slot holds the state in front of that frame (srukf_images_rewind and the frames again)"; return SRUKF_ERR_SEQUENCE; }
+    step_state_replaced(c);                                     // (clears ck_clean: one resume or one rewind per block)
+    c->err.clear();
+    images_restore(c, stop & 1, stop);
     c->phase = 0; c->frame_updated = false;
     HIPCHK(c, hipGetLastError());
     return SRUKF_OK;

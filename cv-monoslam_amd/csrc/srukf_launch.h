@@ -251,3 +251,25 @@ void launch_ransac_staged(hipStream_t st, KDims d, KWeights w, srukf_params p, S
                           const double* Si, const int* vis);
 void launch_set_ransac_args(hipStream_t st, RansacArgs* dst, RansacArgs v);
 void launch_set_policy_params(hipStream_t st, srukf_policy_params* dst, srukf_policy_params v);
+
+// ---- srukf_snapshot.hip (the state a block of image frames is resumed from; C++ linkage) ----
+// k_image_snapshot, the first launch of a frame with the snapshot bit: while no stop of the block is on record in front of frame fs->frame (the latch, see the file),
+// X, S, the matchPatch array and the policy state go into slot (frame & 1), and tag[slot] = frame.  SnapshotArgs: what the guard reads, on the device, written in
+// stream order in front of every run (launch_set_snapshot_args; begin: the run begins a block — tags -1, latch open): the block's first frame, the summaries of the
+// policy and the consensus (null: this run has none) and the policy state (null: not allocated).  SnapshotCtl: the two tags and the latch.  ImageSnapshot: the live
+// arrays, their sizes in bytes and the two slots; the grid is sized by S (image_snapshot_blocks: SNAPSHOT_TRIPS 16-byte trips per lane, at most SNAPSHOT_MAX_BLOCKS)
+struct SnapshotArgs { int b0; const srukf_policy_summary* pol_sum; const RansacSummary* rs_sum; const srukf_policy_state* pol_state; };
+struct SnapshotCtl { int tag[2]; int latch[2]; };
+struct ImageSnapshot {
+    const double* X_src; const double* S_src; const unsigned char* tmpl_src;
+    size_t X_bytes, S_bytes, tmpl_bytes, pol_bytes;
+    double* X[2]; double* S[2]; unsigned char* tmpl[2]; srukf_policy_state* pol[2];
+};
+#ifndef SRUKF_SNAPSHOT_TRIPS                                     // (measurement builds name other grids: DESIGN.md section 25)
+#define SRUKF_SNAPSHOT_TRIPS 4
+#define SRUKF_SNAPSHOT_MAX_BLOCKS 1024
+#endif
+constexpr int SNAPSHOT_TRIPS = SRUKF_SNAPSHOT_TRIPS, SNAPSHOT_MAX_BLOCKS = SRUKF_SNAPSHOT_MAX_BLOCKS;
+int image_snapshot_blocks(size_t S_bytes);
+void launch_image_snapshot(hipStream_t st, const FrameScalars* fs, const SnapshotArgs* args, SnapshotCtl* ctl, const ImageSnapshot& sn);
+void launch_set_snapshot_args(hipStream_t st, SnapshotArgs* dst, SnapshotArgs v, SnapshotCtl* ctl, int begin);

@@ -1043,6 +1043,8 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     const srukf_policy_params pp = { (double)DIST_2_BORDER, 0.01, 10, m_minNUM };
     if (!check(srukf_images_policy(ctx_, 1, &pp)) || !check(srukf_images_set_policy_state(ctx_, st.data()))) return 0;
     if (!check(srukf_images_ransac(ctx_, isUseRANSAC ? 1 : 0, THRESHOLD_RANSAC))) return 0;                     // the consensus inside every frame, or not
+    if ((resumeStoppedBlocks || snapshotsSet_) && !check(srukf_images_snapshots(ctx_, resumeStoppedBlocks ? 1 : 0))) return 0;      // the state at the stop, kept by the first run
+    snapshotsSet_ = resumeStoppedBlocks;
     // 3. one image block in jointUpdate's mode, checked with the switches of associateChecked
     const int mode = jointUpdate ? SRUKF_UPDATE_JOINT : SRUKF_UPDATE_BATCHED;
     const bool checked = rejectAmbiguousMatches || subpixelMatches;
@@ -1059,7 +1061,14 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     if (isUseRANSAC && !check(srukf_get_image_ransac(ctx_, 0, F, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fo))) return 0;
     if (fc >= 0) used = std::min(used, fc + 1);
     if (fo >= 0) used = std::min(used, fo);
-    if (used < F) {
+    // resumeStoppedBlocks: the first run kept the state at the stop (srukf_images_resume); where no slot holds it, the rewind and the frames again
+    bool resumed = false;
+    if (resumeStoppedBlocks && used > 0 && used < F) {
+        rc = srukf_images_resume(ctx_, used);
+        if (rc == SRUKF_OK) { resumed = true; m_nBlocksResumed++; }
+        else if (rc != SRUKF_ERR_SEQUENCE) { check(rc); return 0; }
+    }
+    if (used < F && !resumed) {
         if (!check(srukf_images_rewind(ctx_))) return 0;
         if (used == 0) return 0;                                                                                // the first frame is SLAM()'s: nothing done
         rc = run(used);

@@ -111,7 +111,12 @@ public:
     // ends IN FRONT OF the first frame whose consensus dropped a match: that frame needs the rescue step (rescueHighInnovationInliers), which only SLAM() has, so
     // it is not consumed — the next call returns 0 for it and the caller's SLAM() runs it.  Consumed frames: inliner_L and m_nLowInliers from the consensus record,
     // m_nHighInliers = 0
+    // resumeStoppedBlocks: the block's frames keep the state they start from while no stop is on record (srukf_images_snapshots), and a block
+    // that stops at 0 < used < F takes the state at the stop from the first run (srukf_images_resume) in place of the rewind and the second run; where no slot
+    // holds it (SRUKF_ERR_SEQUENCE) the rewind and the rerun follow as before.  m_nBlocksResumed counts the resumes.  Off: exactly the calls above
     int  SLAMBlock(const unsigned char* gray, int F);
+    bool resumeStoppedBlocks = false;
+    int  m_nBlocksResumed = 0;
     std::vector<double> m_blockPath;                           // the last SLAMBlock's RobotPath numbers, 8 per consumed frame: x, y, z, theta, P00, P01, P10, P11
     std::vector<int> m_blockLowInliers;                        // ... and with isUseRANSAC its m_nLowInliers per consumed frame
     void predictMotion();                                      // SLAM.cpp:1343-1466 (numeric tail 1430-1465)
@@ -316,6 +321,7 @@ private:
     void refreshMirrors();
     bool check(int rc);
     srukf_ctx* ctx_ = nullptr;
+    bool snapshotsSet_ = false;          // srukf_images_snapshots is on on the handle (SLAMBlock switches it off again when resumeStoppedBlocks goes off)
     bool mirrorsFresh_ = false;          // m_X_k / the robot block of m_P_k were fetched by this frame's display refresh
     int device_ = 0;
     FILE* robotFile_ = nullptr;

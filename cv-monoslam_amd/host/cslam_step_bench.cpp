@@ -29,6 +29,14 @@
 //              ransac=<threshold> (assoc_replay): the 1-point RANSAC consensus inside every frame (srukf_images_ransac; threshold in pixels, 8 is the
 //              reference's); the record's summaries are read after every block (srukf_get_image_ransac).  The bench runs no rescue: a block is not cut at
 //              first_outlier.  A restored block runs srukf_ransac_consensus step-wise.  Adds "ransac": {threshold, outlier_frames, low_inliers} to the output
+//              resume=1 (assoc_replay only): the blocks run with srukf_images_snapshots on: every frame begins with k_image_snapshot.  This measures
+//              the switch's price.  Adds "resume": 1 to the output
+//              stop=<k> with resume=0|1 (assoc_replay only; 0 < k < block): behind every timed block of `block` frames comes what a host does when the block has to
+//              stop behind its first k frames, timed with the block — resume=0: srukf_images_rewind and the first k frames again; resume=1: srukf_images_resume(k) —
+//              and the next block begins at the stop.  Two stops exist without inventing one: with policy=1 every block stops behind its first frame (the bench's
+//              texture flags every landmark in every frame), k = 1; without the policy the slots hold the starts of the block's last two frames,
+//              k = block - 1.  The tool runs BOTH legs on fresh handles, the other one first and untimed in the report, and exits with status 3 unless both end
+//              at the same pose and robot covariance, bit for bit.  Adds "stop": {k, resume, blocks} to the output
 //              profile=1 (assoc_replay only): the timed blocks run with srukf_set_profiling on (eager launches); adds "profile_ms_per_frame" by kernel class
 //     hint=1 : capi / assoc announce the NEXT frame's odometry with srukf_predict_motion_next before every update (a host that has its odometry
 //              file loaded, as the reference has: loadOdometryData reads it whole, SLAM.cpp:363-496)
@@ -63,7 +71,7 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 int main(int argc, char** argv)
 {
     if (argc < 4) { fprintf(stderr, "usage: %s scene.bin odometry.txt mode=<capi|facade|assoc|replay> [frames=K] [warmup=W] [hint=0|1]\n"
-                                "       (mode=assoc_replay [block=B] [archive=L[,half_cap]] [archive_step=1] [policy=1] [profile=1]: the staged replay with the association on the device)\n", argv[0]); return 2; }
+                                "       (mode=assoc_replay [block=B] [archive=L[,half_cap]] [archive_step=1] [policy=1] [profile=1] [resume=0|1 [stop=k]]: the staged replay with the association on the device)\n", argv[0]); return 2; }
     std::string mode = "capi";
     int K = 200, W = 20, hint = 0, churn = 0, ransac = 0, ellipsoids = 0, joint = 0, block_frames = 8;
     bool checked = false; srukf_match_params mpar = { 0.8, 2.0, 4, 0 };      // unique= / subpix=: checked image runs (assoc_replay)
@@ -72,6 +80,7 @@ int main(int argc, char** argv)
     long long arc_hits = 0;
     int policy = 0; long long pol_change = 0, pol_deletes = 0, pol_adds = 0;      // policy= (assoc_replay)
     double ransac_thr = 0.0; long long rs_outlier = 0, rs_low = 0;      // ransac=<threshold> (assoc_replay)
+    int resume = -1, stop_k = 0; long long stop_blocks = 0;      // resume= / stop= (assoc_replay)
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -88,6 +97,8 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "archive_step=", 13)) arc_step = atoi(argv[a] + 13);
         else if (!strncmp(argv[a], "profile=", 8)) profile = atoi(argv[a] + 8);
         else if (!strncmp(argv[a], "policy=", 7)) policy = atoi(argv[a] + 7);
+        else if (!strncmp(argv[a], "resume=", 7)) resume = atoi(argv[a] + 7) != 0;
+        else if (!strncmp(argv[a], "stop=", 5)) stop_k = atoi(argv[a] + 5);
         else if (!strncmp(argv[a], "subpix=", 7)) { if (atoi(argv[a] + 7)) { checked = true; mpar.subpixel = 1; } }
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } sets.emplace_back(std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))), atoi(q + 1)); }
     }
@@ -118,7 +129,7 @@ int main(int argc, char** argv)
     long long flag_ticks = -1;                                       // last frame: start of the frame's first launch -> h / Si / visible flagged to the host (10 ns ticks)
     char churn_json[900] = "";
     char ell_json[200] = "";
-    char prof_json[1600] = "", arc_json[200] = "", pol_json[360] = "";
+    char prof_json[1600] = "", arc_json[200] = "", pol_json[520] = "";
     int joint_flagged = 0;
     const char* replay_form = "run_frames_async + synchronize";
     int flagged_blocks = 0;
@@ -126,6 +137,10 @@ int main(int argc, char** argv)
     if (checked && !areplay) { fprintf(stderr, "unique= / subpix= belong to mode=assoc_replay\n"); return 2; }
     if ((arcL || arc_step || profile || policy) && !areplay) { fprintf(stderr, "archive= / archive_step= / profile= / policy= belong to mode=assoc_replay\n"); return 2; }
     if (arcL < 0 || arcL > 64 || (arc_step && !arcL)) { fprintf(stderr, "archive=<L>: 1 <= L <= 64 (archive_step=1 needs it)\n"); return 2; }
+    if ((resume >= 0 || stop_k) && !areplay) { fprintf(stderr, "resume= / stop= belong to mode=assoc_replay\n"); return 2; }
+    if (stop_k && (resume < 0 || stop_k < 1 || stop_k >= block_frames || arcL || profile)) { fprintf(stderr, "stop=<k> needs resume=0|1 and 0 < k < block, without archive= and profile=\n"); return 2; }
+    const int legs = stop_k ? 2 : 1;                                // stop=: both routes, the one asked for last (it is the one reported)
+    double leg_pose[2][4 + 16] = { { 0 } };
     if (areplay && (block_frames < 1 || W < 1)) { fprintf(stderr, "assoc_replay: block >= 1 and warmup >= 1 (frame 0 sets the appearance records up)\n"); return 2; }
     if (mode == "facade") {
         monoslam::CSLAM SLAM;
@@ -245,7 +260,9 @@ int main(int argc, char** argv)
         t_timed = now_s() - t0;
         srukf_destroy(c);
 #undef CK
-    } else {
+    } else for (int leg = 0; leg < legs; leg++) {
+        const int snap = legs == 2 ? (leg == 0 ? !resume : resume) : (resume > 0 ? 1 : 0);
+        matches_dev = 0; ambiguous = refined = 0; pol_change = pol_deletes = pol_adds = 0; rs_outlier = rs_low = 0; stop_blocks = 0; flagged_blocks = 0;
         srukf_params p;
         srukf_default_params(&p);
         p.a1 = a4[0]; p.a2 = a4[1]; p.a3 = a4[2]; p.a4 = a4[3];
@@ -341,12 +358,15 @@ int main(int argc, char** argv)
             }
             if (policy) CK(srukf_images_policy(c, 1, nullptr));
             if (ransac_thr > 0.0) CK(srukf_images_ransac(c, 1, ransac_thr));
+            if (snap) CK(srukf_images_snapshots(c, 1));
             std::vector<int> rlow(block_frames), ract(block_frames), rinl(N);
             std::vector<srukf_policy_summary> prow(block_frames);
             std::vector<int> mrow((size_t)block_frames * N), frow(checked ? (size_t)block_frames * N : 0), fl(checked ? N : 0), hrow(block_frames), am(arcL);
             auto run = [&](int first, int end, bool timed) -> int {
-                for (int b = first; b < end; b += block_frames) {
+                int step = block_frames;
+                for (int b = first; b < end; b += step) {
                     const int cnt = end - b < block_frames ? end - b : block_frames;
+                    step = block_frames;
                     rc = checked ? srukf_run_images_checked_async(c, b, cnt, upd, &mpar, nullptr) : srukf_run_images_async(c, b, cnt, upd, nullptr);
                     if (rc == SRUKF_OK) rc = srukf_synchronize(c);
                     const bool clean = rc == SRUKF_OK;
@@ -401,6 +421,17 @@ int main(int argc, char** argv)
                             for (int q = 0; q < cnt; q++) arc_hits += hrow[q];
                         }
                     }
+                    if (clean && timed && stop_k && cnt > stop_k) {      // the block has to stop behind its first stop_k frames
+                        if (snap) CK(srukf_images_resume(c, stop_k));
+                        else {
+                            CK(srukf_images_rewind(c));
+                            rc = checked ? srukf_run_images_checked_async(c, b, stop_k, upd, &mpar, nullptr) : srukf_run_images_async(c, b, stop_k, upd, nullptr);
+                            if (rc == SRUKF_OK) rc = srukf_synchronize(c);
+                            if (rc) { fprintf(stderr, "image block [%d, %d) again: %d %s\n", b, b + stop_k, rc, srukf_last_error(c)); return 1; }
+                        }
+                        stop_blocks++;
+                        step = stop_k;
+                    }
                     if (clean && arcL && arc_step) {    // the step-wise route: one search on the posterior of the block's last frame
                         CK(srukf_archive_search(c, gray.data(), &apar, nullptr, nullptr, nullptr, nullptr, am.data(), nullptr));
                         if (timed) for (int q = 0; q < arcL; q++) arc_hits += am[q];
@@ -445,6 +476,12 @@ int main(int argc, char** argv)
         t_timed = now_s() - t0;
         srukf_debug_get(c, "meas_flag_ticks", &flag_ticks);
         srukf_destroy(c);
+        memcpy(leg_pose[leg], pose, sizeof pose); memcpy(leg_pose[leg] + 4, P4, sizeof P4);
+    }
+    if (legs == 2 && memcmp(leg_pose[0], leg_pose[1], sizeof leg_pose[0]) != 0) {
+        fprintf(stderr, "stop=%d: the two routes end at different poses: resume=%d %.17g %.17g %.17g %.17g, resume=%d %.17g %.17g %.17g %.17g\n", stop_k, !resume, leg_pose[0][0], leg_pose[0][1],
+                leg_pose[0][2], leg_pose[0][3], resume, leg_pose[1][0], leg_pose[1][1], leg_pose[1][2], leg_pose[1][3]);
+        return 3;
     }
     char joint_json[420] = "";
     if (joint) snprintf(joint_json, sizeof joint_json, "\"joint\": 1, \"joint_flagged_frames\": %d, ", joint_flagged);
@@ -456,6 +493,8 @@ int main(int argc, char** argv)
     if (policy) snprintf(pol_json, sizeof pol_json, "\"policy\": {\"change_frames\": %lld, \"deletes\": %lld, \"need_add_frames\": %lld}, ", pol_change, pol_deletes, pol_adds);
     if (areplay && ransac_thr > 0.0) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"ransac\": {\"threshold\": %.6g, \"outlier_frames\": %lld, \"low_inliers\": %lld}, ",
                                               ransac_thr, rs_outlier, rs_low);
+    if (areplay && resume >= 0) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"resume\": %d, ", resume);
+    if (stop_k) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"stop\": {\"k\": %d, \"resume\": %d, \"blocks\": %lld, \"poses_equal\": 1}, ", stop_k, resume, stop_blocks);
     if (mode == "replay") snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"replay_form\": \"%s\", \"exact_frames\": %d, ", replay_form, joint_flagged);
     printf("{\"mode\": \"%s\", %s%s%s%s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "
            "\"pose\": [%.17g, %.17g, %.17g, %.17g], \"P_robot\": [%.17g, %.17g, %.17g, %.17g], \"device_matches\": %lld, \"stats_flag_us_into_first_launch\": %.2f, \"host_us_per_call\": {\"predict_motion\": %.2f, \"predict_measurement\": %.2f, \"association\": %.2f, \"update\": %.2f, \"get_robot\": %.2f}, "

@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -29,6 +29,8 @@
 //   the 2 x 2 position block of P, %.17g), and at the end "blocks <n> early <n> full <n> fallback <n>".  Without it nothing changes.  With ransac=<threshold> the
 //   consensus runs inside the blocks and every frame's "ransac" line follows its "path" line, the same through either route; a block ends in
 //   front of a frame whose consensus dropped a match, and SLAM() runs that frame with its rescue (a fallback).
+// resume=1 (with block=<F>): CSLAM::resumeStoppedBlocks on: a block that stops early takes the state at the stop from its first run instead of
+//   running the frames in front of the stop again; " resumed=<count>" is appended to the "blocks" line.  Without it the output is what it was.
 // min_matches=<n>: CSLAM::m_minNUM = n (addFeatures when fewer landmarks matched, SLAM.cpp:179, 556; default 5).
 // warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
 // Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
@@ -41,7 +43,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [min_matches=<n>]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [min_matches=<n>]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -50,7 +52,7 @@ int main(int argc, char** argv)
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
     int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay;
-    bool unique = false, subpix = false, joint = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
+    bool unique = false, subpix = false, joint = false, resume = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
     int minMatches = 0, block = 0, nBlocks = 0, nEarly = 0, nFull = 0, nFallback = 0;
     for (int a = 3; a < argc; a++)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
@@ -62,6 +64,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "subpix=", 7)) subpix = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6) != 0;
         else if (!strncmp(argv[a], "block=", 6)) block = atoi(argv[a] + 6);
+        else if (!strncmp(argv[a], "resume=", 7)) resume = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "min_matches=", 12)) minMatches = atoi(argv[a] + 12);
     if (warmup) {
         monoslam::CSLAM w;
@@ -84,6 +87,7 @@ int main(int argc, char** argv)
     if (unique) { SLAM.rejectAmbiguousMatches = true; SLAM.AMBIGUITY_RATIO = uniqueRatio; SLAM.AMBIGUITY_EXCLUSION = uniqueExcl; }
     SLAM.subpixelMatches = subpix;
     SLAM.jointUpdate = joint;
+    SLAM.resumeStoppedBlocks = resume;
     if (minMatches > 0) SLAM.m_minNUM = minMatches;
     const unsigned char* cur = nullptr;
     std::vector<unsigned char> bgr(colour ? (size_t)3 * W * H : 0);
@@ -138,7 +142,8 @@ int main(int argc, char** argv)
             report(fr, nBefore);
             fr++;
         }
-        printf("blocks %d early %d full %d fallback %d\n", nBlocks, nEarly, nFull, nFallback);
+        if (resume) printf("blocks %d early %d full %d fallback %d resumed=%d\n", nBlocks, nEarly, nFull, nFallback, SLAM.m_nBlocksResumed);
+        else printf("blocks %d early %d full %d fallback %d\n", nBlocks, nEarly, nFull, nFallback);
         printf("block_frames %d frames %d us_per_frame %.2f\n", block, steps, wall / steps * 1e6);
         return 0;
     }

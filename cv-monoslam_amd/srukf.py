@@ -36,6 +36,7 @@ EXPORTS = [
     "srukf_images_search_archive", "srukf_get_image_archive",
     "srukf_map_policy", "srukf_images_policy", "srukf_images_set_policy_state", "srukf_get_image_policy", "srukf_images_rewind",
     "srukf_images_ransac", "srukf_get_image_ransac",
+    "srukf_images_snapshots", "srukf_get_image_snapshots", "srukf_images_resume",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -204,6 +205,10 @@ def load_library(path=None):
     if hasattr(L, "srukf_images_ransac"):              # (idem: the 1-point RANSAC consensus inside image frames)
         L.srukf_images_ransac.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.srukf_get_image_ransac.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _dp, _ip, _ip, _ip, _ip]
+    if hasattr(L, "srukf_images_snapshots"):           # (idem: the state at a block's stop)
+        L.srukf_images_snapshots.argtypes = [C.c_void_p, C.c_int]
+        L.srukf_get_image_snapshots.argtypes = [C.c_void_p, _ip]
+        L.srukf_images_resume.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -827,6 +832,32 @@ class Filter:
                                                    _i(out["n_active"]), _i(out["n_low"]), C.byref(fo)))
         out["first_outlier"] = int(fo.value)
         return out
+
+    # ---- the state at a block's stop (srukf_images_snapshots / srukf_images_resume) ----
+    def images_snapshots(self, on):
+        """The switch of the snapshot launch in front of image frames (srukf_images_snapshots): while on, every frame of every later run_images* /
+        run_images_checked* first keeps the state it starts from (X, S, matchPatches, policy state) in slot frame & 1, as long as no frame of the block in front of
+        it has stopped the block; images_resume then cuts the block without running frames again.  Not while a run is in flight or a block is pending."""
+        if not isinstance(on, (bool, np.bool_)) and not (isinstance(on, (int, np.integer)) and on in (0, 1)):
+            raise TypeError("images_snapshots: on must be a bool")
+        self._chk(self._lib.srukf_images_snapshots(self._h, int(bool(on))))
+
+    def get_image_snapshots(self):
+        """The staged frames whose start the two slots hold, (slot 0, slot 1); -1: none (srukf_get_image_snapshots).  Waits for the stream."""
+        tags = np.full(2, -1, dtype=np.int32)
+        self._chk(self._lib.srukf_get_image_snapshots(self._h, _i(tags)))
+        return int(tags[0]), int(tags[1])
+
+    def images_resume(self, keep):
+        """Cuts the image block the last synchronize ended clean to its first `keep` frames without running them again (srukf_images_resume): X, S, every
+        matchPatch and the policy state become what the block's frame `keep` started from, rows >= keep of the policy and consensus records are zeroed.  keep 0 is
+        images_rewind, keep == the frames run changes nothing.  SrukfError(SRUKF_ERR_SEQUENCE) where images_rewind is refused, when a run of the block had the
+        switch off, or when no slot holds that frame (the block can then still be rewound)."""
+        if isinstance(keep, (bool, np.bool_)) or not isinstance(keep, (int, np.integer)):
+            raise TypeError("images_resume: keep must be an int")
+        if keep < 0:
+            raise ValueError("images_resume: keep must be >= 0")
+        self._chk(self._lib.srukf_images_resume(self._h, int(keep)))
 
     def synchronize(self):
         self._chk(self._lib.srukf_synchronize(self._h))

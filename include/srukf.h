@@ -639,6 +639,31 @@ int  srukf_images_rewind(srukf_ctx* ctx);
 int  srukf_images_ransac(srukf_ctx* ctx, int on, double threshold);
 int  srukf_get_image_ransac(srukf_ctx* ctx, int first, int count, int* flags, int* votes, double* dist, int* best, int* n_active, int* n_low, int* first_outlier);
 
+/* ---- the state at a block's stop: resume without running frames again ----
+ * A block is every image run between two srukf_synchronize calls.  A host that stops a block inside it (the policy's first_change, the consensus' first_outlier)
+ *   can put the checkpoint back and run the frames in front of the stop again (srukf_images_rewind), or, with this switch, take the state the first run already
+ *   passed through.
+ * srukf_images_snapshots: a switch on the handle, like srukf_images_ransac: it survives map changes and srukf_reset (which drop the slots with the staged images);
+ *   srukf_destroy ends it.  Not while a run is in flight or a block is pending (SRUKF_ERR_SEQUENCE).  The call touches no device.  While on, every frame of
+ *   every later image run (all kinds, BATCHED and JOINT) begins with one more launch, k_image_snapshot: while no frame of the block in [first frame, f) is an
+ *   `outlier` frame of the consensus and none in [first frame, f - 1) has the policy's `change`, it copies X, S, every matchPatch and the policy state into slot
+ *   f & 1 and tags the slot with f; otherwise it writes nothing.  So behind a policy stop at frame k the slot (k + 1) & 1 holds the state frame k + 1 started
+ *   from (k + 1 frames are kept), behind an outlier at frame k the slot k & 1 holds the state frame k started from, and behind a block without a stop the slots
+ *   hold the starts of its last two frames.  Such frames are captured frames of their own; the guard's parameters live in a device struct written in stream
+ *   order in front of each run.  The frames compute exactly what they compute without the launch.  With the switch off an image run is exactly what it was.
+ * srukf_get_image_snapshots: waits for the stream; frames[0], frames[1]: the staged frame each slot is tagged with, -1 for none (a new block clears both).
+ * srukf_images_resume(keep), keep counted from the block's first frame: legal exactly where srukf_images_rewind is, in a block whose every run had the switch
+ *   on (and began where the one before ended); SRUKF_ERR_SEQUENCE otherwise, the state untouched.  keep == 0 is srukf_images_rewind.  keep == the frames the
+ *   block ran: nothing moves, SRUKF_OK.  Any other keep: the slot (first + keep) & 1 must be tagged first + keep — if not, SRUKF_ERR_SEQUENCE, the state is
+ *   untouched and the block can still be rewound.  Then X, S, every matchPatch and the policy state come from the slot; rows >= keep of the policy record and of
+ *   the consensus record are zeroed, rows < keep stay; every other record (matches, checks, archive search) and the caller's trajectory rows are what the first run
+ *   wrote.  Afterwards the handle holds, byte for byte, what srukf_images_rewind followed by a run of the first keep frames leaves.  One resume or one rewind per
+ *   block.  keep < 0 or > the frames run: SRUKF_ERR_BAD_ARG.  A flagged block is restored by srukf_synchronize as before, and a resume is refused there.
+ * All: SRUKF_ERR_BAD_ARG for a NULL handle (srukf_get_image_snapshots: frames NULL; srukf_images_resume: keep < 0) before any device is touched. */
+int  srukf_images_snapshots(srukf_ctx* ctx, int on);
+int  srukf_get_image_snapshots(srukf_ctx* ctx, int frames[2]);
+int  srukf_images_resume(srukf_ctx* ctx, int keep);
+
 /* ---- instrumentation ------------------------------------------------------------------------ */
 
 /* When on, every kernel launch is bracketed by HIP events on the context's stream and the
