@@ -95,7 +95,7 @@ struct ArchiveState {
 // sequence's lifetime: images_drop.
 // graphs: the captured frames (one and eight) of every form of an image frame and update mode, ONE table: graphs[ImageForm::index()][0 BATCHED / 1 JOINT].  A form
 // never replays a frame captured for another one (nor a frame of srukf_run_frames*, nor the other way round): the index is the guarantee.  drop_graphs walks the table.
-// The device buffers come in six groups, each named once (image_group, srukf_images.hip): allocation, images_drop and images_archive_drop all go through those lists
+// The device buffers come in seven groups, each named once (image_group, srukf_images.hip): allocation, images_drop and images_archive_drop all go through those lists
 struct ImageReplay {
     unsigned char *images = nullptr, *ck_tmpl = nullptr;
     double *corr_seq = nullptr, *h_seq = nullptr, *xyz = nullptr, *ckS = nullptr, *ckX = nullptr;
@@ -138,7 +138,17 @@ struct ImageReplay {
     double *sn_X[2] = { nullptr, nullptr }, *sn_S[2] = { nullptr, nullptr }; unsigned char* sn_tmpl[2] = { nullptr, nullptr }; srukf_policy_state* sn_pol[2] = { nullptr, nullptr };
     SnapshotCtl* sn_ctl = nullptr; SnapshotArgs* sn_args = nullptr;
     int blk_first = 0, blk_end = 0; bool blk_snap = false;
+    // The display view behind image frames (srukf_images_display), allocated by images_display_ensure in front of the first run with the switch
+    // on: the record, one row of ImageDisplayRow(N).doubles doubles per staged frame (dp_rec) and one of N ints (dp_rot), zero until such a frame writes a row, zeroed
+    // again by images_restore.  dp_rows [frames]: the host's mark per row — a run with the switch on has issued the row's launches and no restore has zeroed it since
+    // (what srukf_render_image_overlay asks: rot cannot tell, 0 rotations is a legal value)
+    double* dp_rec = nullptr; int* dp_rot = nullptr;
+    std::vector<unsigned char> dp_rows;
 };
+
+// one frame's row of the display record, offsets in doubles: xyz [3N] | cov [9N] | axis [4N] | sigma [3N] | robot [20] = P4 | pose | Si [4N]
+struct ImageDisplayRow { size_t xyz, cov, axis, sigma, robot, Si, doubles; };
+constexpr ImageDisplayRow image_display_row(size_t N) { return { 0, 3 * N, 12 * N, 16 * N, 19 * N, 19 * N + 20, 23 * N + 20 }; }
 
 // ---- the context: who owns what across a map change ("who owns what across a map change") ----------------------
 // srukf_ctx = srukf_handle_scope + srukf_map_scope (which holds one srukf_life).  WHERE a member is declared says what a map change, a revive and srukf_destroy do
@@ -184,6 +194,7 @@ struct srukf_handle_scope : srukf_switches {
     bool img_ransac = false;               // srukf_images_ransac: every frame of every later image run holds the 1-point RANSAC consensus between association and update, with ...
     double img_ransac_thr = 8.0;           // ... this threshold.  Survives map changes and srukf_reset
     bool img_snap = false;                 // srukf_images_snapshots: every frame of every later image run begins with k_image_snapshot.  Survives map changes and srukf_reset
+    bool img_display = false;              // srukf_images_display: every frame of every later image run is followed by k_image_view + k_lm_ellipsoid into its row of the display record.  Survives map changes and srukf_reset
     std::string err;
     // the pool allocations among the members above (det and archive: det_scratch_free / archive_free).  A new buffer of this scope is added HERE
     template <class F> void each_device_buffer(F f) const { void* b[] = { d_image, d_bgr, d_ovl }; for (void* q : b) f(q); }

@@ -1,6 +1,7 @@
-// srukf_images.hip — image runs of the staged replay (DESIGN.md sections 20 - 24): the staged gray frames and the frames that associate on the device
+// srukf_images.hip — image runs of the staged replay (DESIGN.md sections 20 - 26): the staged gray frames and the frames that associate on the device
 // (srukf_stage_images / srukf_run_images*), with the checked association (srukf_run_images_checked*), the archive search (srukf_images_search_archive), the map
-// policy's verdict (srukf_images_policy) and the 1-point RANSAC consensus (srukf_images_ransac) as options of a run, and the getters of their records.  No kernel:
+// policy's verdict (srukf_images_policy), the 1-point RANSAC consensus (srukf_images_ransac) and the display view (srukf_images_display; section 26, with the overlay
+// of any staged frame, srukf_render_image_overlay) as options of a run, and the getters of their records.  No kernel:
 // the launch sequences, the graph cache and srukf_synchronize are srukf_replay.hip's; what the two files share is declared once in srukf_ctx.h.
 // A further per-frame option is: one bit of ImageForm, one group of image_group, one branch of replay_one_image_frame
 
@@ -13,7 +14,7 @@ namespace srukf_impl {
 // images_drop and images_archive_drop free through the same lists: a buffer added HERE is freed without anyone remembering to list it.  The sizes are the allocation's
 // (image_bytes: of one staged frame, L: the archive's; whoever only frees passes neither).  Zeroed: the records (rows no run has written read as zero) and the
 // consensus scratch; not the parameter blocks (written in stream order in front of every run that reads them), the images, xyz and the checkpoint copies
-enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_SNAPSHOT, IMG_GROUPS };
+enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_SNAPSHOT, IMG_DISPLAY, IMG_GROUPS };
 struct ImageBuf { void** p; size_t bytes; bool zero; };
 static std::vector<ImageBuf> image_group(srukf_map_scope* c, ImageGroup g, size_t image_bytes = 0, size_t L = 0)
 {
@@ -33,6 +34,7 @@ static std::vector<ImageBuf> image_group(srukf_map_scope* c, ImageGroup g, size_
                                 buf(&im.sn_tmpl[0], N * PT_TMPL_STRIDE), buf(&im.sn_tmpl[1], N * PT_TMPL_STRIDE),
                                 buf(&im.sn_pol[0], sizeof(srukf_policy_state) * N), buf(&im.sn_pol[1], sizeof(srukf_policy_state) * N),
                                 buf(&im.sn_ctl, sizeof(SnapshotCtl)), buf(&im.sn_args, sizeof(SnapshotArgs)) };
+    case IMG_DISPLAY: return { buf(&im.dp_rec, D * f * image_display_row(N).doubles, true), buf(&im.dp_rot, I * f * N, true) };
     default: return {};
     }
 }
@@ -125,7 +127,7 @@ static void replay_one_image_frame(srukf_ctx* c, int mode, ImageForm form)
 // the state the block of image frames started from comes back: X, S and the matchPatch array (its pixels persist from frame to frame, so a flagged block must not
 // leave its own behind), as srukf_run_frames' checkpoint comes back.  Keeps c->err
 // slot >= 0 (srukf_images_resume): snapshot slot `slot` in the checkpoint's place — the state frame `stop` of the stack started from; rows
-// >= stop of the policy and consensus records go, the rows in front of it stand, and the null rows are what the block's frames left (stop lies behind its first frame)
+// >= stop of the policy, consensus and display records go, the rows in front of it stand, and the null rows are what the block's frames left (stop lies behind its first frame)
 void images_restore(srukf_ctx* c, int slot, int stop)
 {
     ImageReplay& im = c->img;
@@ -146,6 +148,11 @@ void images_restore(srukf_ctx* c, int slot, int stop)
         hipMemsetAsync(im.rs_rvotes + r0 * N, 0, sizeof(int) * rows * N, c->stream);
         hipMemsetAsync(im.rs_dist + r0 * N, 0, sizeof(double) * rows * N, c->stream);
         hipMemsetAsync(im.rs_sum + r0, 0, sizeof(RansacSummary) * rows, c->stream);
+    }
+    if (im.dp_rec && rows) {                                   // the display record: the views of frames that do not stand are no views
+        hipMemsetAsync(im.dp_rec + r0 * image_display_row(N).doubles, 0, sizeof(double) * rows * image_display_row(N).doubles, c->stream);
+        hipMemsetAsync(im.dp_rot + r0 * N, 0, sizeof(int) * rows * N, c->stream);
+        std::fill(im.dp_rows.begin() + (std::ptrdiff_t)r0, im.dp_rows.end(), (unsigned char)0);
     }
     if (ck && c->null_canonical != im.ck_canon) { c->null_canonical = im.ck_canon; drop_graphs(c); }
     shadow_rebuild(c);
@@ -237,6 +244,37 @@ static int images_snapshot_ensure(srukf_ctx* c, const char* who)
     return image_buffers_alloc(c, image_group(c, IMG_SNAPSHOT), who);
 }
 
+// what the display view behind image frames needs beyond srukf_stage_images' buffers, allocated in front of the first run with the switch on,
+// outside any capture: the record (zeroed) and the host's marks of its rows
+static int images_display_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    if (im.dp_rec) return SRUKF_OK;
+    const int rc = image_buffers_alloc(c, image_group(c, IMG_DISPLAY), who); if (rc) return rc;
+    im.dp_rows.assign((size_t)im.frames, 0);
+    return SRUKF_OK;
+}
+
+// the display view behind staged frame `frame` (srukf_images_display; updateFeaturesInformation -> refreshFeaturesDisplay, SLAM.cpp:2566-2575, behind every frame):
+// two eager launches with the host's row pointers, as the policy's launch carries its frame index — k_image_view (xyz, cov, the robot block and the Si the frame's
+// association read, from the posterior X and S), then k_lm_ellipsoid on the row's cov.  They read X, S and c->Si and write the record only
+static void issue_image_display(srukf_ctx* c, int frame)
+{
+    ImageReplay& im = c->img;
+    const size_t N = (size_t)c->d.N;
+    const ImageDisplayRow r = image_display_row(N);
+    double* row = im.dp_rec + (size_t)frame * r.doubles;
+    {
+        ProfScope ps(c, KC_MISC, 126.0 * N * N, 144.0 * N * N + 8.0 * r.doubles);      // landmark k walks 6 k + 6 rows of S: 21 products and 6 doubles each
+        launch_image_view(c->stream, c->d, c->X, c->S, c->Si, row + r.xyz, row + r.cov, row + r.robot, row + r.Si);
+    }
+    {
+        ProfScope ps(c, KC_LM_ELLIPSOID, 0, 8.0 * 16 * N + 4.0 * N);
+        launch_lm_ellipsoid(c->stream, (int)N, c->p.epsilon, row + r.cov, row + r.axis, row + r.sigma, im.dp_rot + (size_t)frame * N);
+    }
+    im.dp_rows[(size_t)frame] = 1;
+}
+
 // the map policy's verdict behind staged frame `frame` (srukf_images_policy): an eager launch with the frame index as a kernel argument — fs->frame has advanced
 // behind the tail, and a captured frame could not carry the index.  It reads the posterior X and row `frame` of the association's record
 static void issue_image_policy(srukf_ctx* c, int frame)
@@ -283,6 +321,13 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         launch_set_policy_params(c->stream, im.pol_args, c->img_policy_args);      // in stream order, as the checked run's parameters
         im.pol_valid = true;
     }
+    // the display view behind every frame (srukf_images_display): like the policy no captured frames of its own — the run is issued frame by frame, the one-frame
+    // graph followed by the display launches, then the policy's.  The two read the same posterior and write records of their own: their order is fixed (display
+    // first), not needed
+    const bool display = c->img_display;
+    if (display) { const int rcd = images_display_ensure(c, who); if (rcd) return rcd; }                // (idem)
+    else if (im.dp_rec) std::fill(im.dp_rows.begin() + first, im.dp_rows.begin() + first + count, (unsigned char)0);      // frames run again without the switch: their rows are an earlier run's, kept but not drawable
+    const bool single = policy || display;
     // the 1-point RANSAC consensus inside every frame (srukf_images_ransac): captured frames of their own
     if (form.ransac) {
         const int rcr = images_ransac_ensure(c, who); if (rcr) return rcr;                            // (idem)
@@ -316,6 +361,7 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         // null rows that are not (yet) sqrt(EPSILON) e_k: the run's first frame eagerly, as in srukf_run_frames_async (the plain form reads the rows as they are)
         launch_set_run(c->stream, c->fs, first, clear, traj);
         replay_one_image_frame(c, mode, form);
+        if (display) issue_image_display(c, first);
         if (policy) issue_image_policy(c, first);
         set_null_canonical(c);
         im.pending = true; clear = 0;
@@ -329,11 +375,19 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         ReplayGraphs& g = im.graphs[form.index()][mode == SRUKF_UPDATE_JOINT ? 1 : 0];
         const auto frame = [=] { replay_one_image_frame(c, mode, form); };
         if (!g.one_exec) { const int rc = capture_frames(c, 1, &g.one, &g.one_exec, frame); if (rc) return rc; }
-        if (!policy && !g.eight_exec) { const int rc = capture_frames(c, SRUKF_GRAPH_FRAMES, &g.eight, &g.eight_exec, frame); if (rc) return rc; }      // (a policy run launches single frames only)
-        if (policy) for (int f = 0; f < count; f++) { HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream)); issue_image_policy(c, first + f); }
+        if (!single && !g.eight_exec) { const int rc = capture_frames(c, SRUKF_GRAPH_FRAMES, &g.eight, &g.eight_exec, frame); if (rc) return rc; }      // (a policy or display run launches single frames only)
+        if (single) for (int f = 0; f < count; f++) {
+            HIPCHK(c, hipGraphLaunch(g.one_exec, c->stream));
+            if (display) issue_image_display(c, first + f);
+            if (policy) issue_image_policy(c, first + f);
+        }
         else { const int rc = replay_launch_graphs(c, g, count); if (rc) return rc; }
     } else {
-        for (int f = 0; f < count; f++) { replay_one_image_frame(c, mode, form); if (policy) issue_image_policy(c, first + f); }
+        for (int f = 0; f < count; f++) {
+            replay_one_image_frame(c, mode, form);
+            if (display) issue_image_display(c, first + f);
+            if (policy) issue_image_policy(c, first + f);
+        }
     }
     im.pending = true;
     return replay_epilogue(c);
@@ -567,6 +621,83 @@ int srukf_images_resume(srukf_ctx* c, int keep)
     images_restore(c, stop & 1, stop);
     c->phase = 0; c->frame_updated = false;
     HIPCHK(c, hipGetLastError());
+    return SRUKF_OK;
+}
+
+// ---- the display view behind image frames, the overlay of any staged frame (the kernels: srukf_predict.hip, srukf_display.hip, srukf_overlay.hip) ----
+// The switch: on the handle, like srukf_images_snapshots.  Touches no device: the record is allocated in front of the next image run (run_images_issue).  Not inside
+// a block: a block's rows are all written or none
+int srukf_images_display(srukf_ctx* c, int on)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    if (c->async_pending || c->img.pending) { c->err = "images_display: a run is in flight or a block is pending (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    c->img_display = on != 0;
+    return SRUKF_OK;
+}
+
+// rows [first, first + count) of the display record (what updateFeaturesInformation -> refreshFeaturesDisplay, SLAM.cpp:2566-2575, and recordRobotInformation would
+// have refreshed behind each frame), after waiting for the stream like srukf_get_image_matches.  A record no run has allocated reads as zeros (the rule of
+// srukf_get_image_checks)
+int srukf_get_image_display(srukf_ctx* c, int first, int count, double* xyz, double* cov, double* axis, double* sigma, int* rot, double* pose4, double* P4, double* Si)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    if (!xyz && !cov && !axis && !sigma && !rot && !pose4 && !P4 && !Si) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_display: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_display: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    const ImageDisplayRow r = image_display_row(N);
+    std::vector<double> rec(m * r.doubles, 0.0);
+    if (rot) memset(rot, 0, sizeof(int) * m * N);
+    if (im.dp_rec) {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(rec.data(), im.dp_rec + a * r.doubles, sizeof(double) * m * r.doubles, hipMemcpyDeviceToHost));
+        if (rot) HIPCHK(c, hipMemcpy(rot, im.dp_rot + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    }
+    for (size_t q = 0; q < m; q++) {
+        const double* row = rec.data() + q * r.doubles;
+        if (xyz) memcpy(xyz + q * 3 * N, row + r.xyz, sizeof(double) * 3 * N);
+        if (cov) memcpy(cov + q * 9 * N, row + r.cov, sizeof(double) * 9 * N);
+        if (axis) memcpy(axis + q * 4 * N, row + r.axis, sizeof(double) * 4 * N);
+        if (sigma) memcpy(sigma + q * 3 * N, row + r.sigma, sizeof(double) * 3 * N);
+        if (P4) memcpy(P4 + q * 16, row + r.robot, sizeof(double) * 16);
+        if (pose4) memcpy(pose4 + q * 4, row + r.robot + 16, sizeof(double) * 4);
+        if (Si) memcpy(Si + q * 4 * N, row + r.Si, sizeof(double) * 4 * N);
+    }
+    return SRUKF_OK;
+}
+
+// display2DFeatureModel + draw2DEllipse (SLAM.cpp:3009-3083) for staged frame `frame`, from what the device holds and with nothing uploaded: srukf_render_overlay's
+// two launches on the frame's rows of h_seq, the display record's Si, z_seq and m_seq (behind a consensus run the masked row: what the filter used), over the
+// frame's place in the staged stack, gray byte three times.  Which rows are drawable is the host's mark per row (ImageReplay::dp_rows): set when a run with the
+// display switch issues the row's launches, cleared when images_restore zeroes the row.  It writes the overlay's own buffers (ov_rec, d_ovl) only.
+// (k_overlay reads the gray frame in dwords: a stack whose frames are no multiple of four bytes has frames that do not start on one)
+int srukf_render_image_overlay(srukf_ctx* c, int frame, unsigned char* out_bgr)
+{
+    if (!c || !out_bgr || frame < 0) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "render_image_overlay: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (frame >= im.frames) { c->err = "render_image_overlay: frame outside the staged images"; return SRUKF_ERR_BAD_ARG; }
+    if (!im.dp_rec || !im.dp_rows[(size_t)frame]) { c->err = "render_image_overlay: no run with srukf_images_display on has written that frame's row"; return SRUKF_ERR_SEQUENCE; }
+    const int W = (int)c->p.image_w, H = (int)c->p.image_h, N = c->d.N;
+    if (W < 1 || H < 1 || (double)W * H > 268435456.0) { c->err = "render_image_overlay: image size"; return SRUKF_ERR_BAD_ARG; }
+    const int npix = W * H;
+    if (npix % 4) { c->err = "render_image_overlay: image_w * image_h must be a multiple of four"; return SRUKF_ERR_UNSUPPORTED; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!c->d_ovl) HIPCHK(c, srukf_dmalloc((void**)&c->d_ovl, overlay_bgr_bytes(npix)));
+    if (!c->ov_rec) HIPCHK(c, srukf_dmalloc(&c->ov_rec, overlay_rec_bytes(N)));
+    const size_t f = (size_t)frame, n = (size_t)N;
+    const ImageDisplayRow r = image_display_row(n);
+    {
+        ProfScope ps(c, KC_OVERLAY, 0, 4.0 * npix);
+        launch_overlay(c->stream, W, H, N, im.h_seq + f * 2 * n, im.dp_rec + f * r.doubles + r.Si, c->z_seq + f * 2 * n, c->m_seq + f * n, c->ov_rec,
+                       nullptr, im.images + f * (size_t)npix, c->d_ovl);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out_bgr, c->d_ovl, 3 * (size_t)npix, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (out_bgr is pageable host memory)
     return SRUKF_OK;
 }
 

@@ -273,3 +273,9 @@ constexpr int SNAPSHOT_TRIPS = SRUKF_SNAPSHOT_TRIPS, SNAPSHOT_MAX_BLOCKS = SRUKF
 int image_snapshot_blocks(size_t S_bytes);
 void launch_image_snapshot(hipStream_t st, const FrameScalars* fs, const SnapshotArgs* args, SnapshotCtl* ctl, const ImageSnapshot& sn);
 void launch_set_snapshot_args(hipStream_t st, SnapshotArgs* dst, SnapshotArgs v, SnapshotCtl* ctl, int begin);
+
+// ---- srukf_predict.hip (the display view behind the frames of an image run; C++ linkage) ----
+// k_image_view, N + 1 workgroups: k_landmarks_cartesian's body per landmark into xyz [3N] / cov [9N], k_block_cov's body for the robot block into robot [20]
+// (P4 | pose), and the innovation factors Si [4N] as the frame's association read them into Si_row [4N].  The output pointers are one frame's rows of the
+// display record (ImageDisplayRow, srukf_ctx.h): the host computes them, the kernel knows no frame index
+void launch_image_view(hipStream_t st, KDims d, const double* X, const double* S, const double* Si, double* xyz, double* cov, double* robot, double* Si_row);

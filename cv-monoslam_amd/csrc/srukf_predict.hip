@@ -634,12 +634,11 @@ __global__ __launch_bounds__(256) void k_traj(KDims d, const double* __restrict_
 // k_block_cov: small diagonal blocks of P = S^T S for the accessors (robot 4x4: SLAM.cpp:3539-3556;
 // landmark 6x6: 2748).  out[bs*bs], block starts at row/col `off`.  One workgroup.
 // X (may be null): the bs state entries of the block are appended behind the bs x bs values (the robot view the step-wise API hands back with a frame's status)
-__global__ __launch_bounds__(256) void k_block_cov(KDims d, const double* __restrict__ S, int off, int bs, double* __restrict__ out, const double* __restrict__ X)
+// block_cov_body: the kernel's body, ONE text for its two callers (k_block_cov, and the last workgroup of k_image_view); red: 16 * 21 doubles of LDS
+__device__ __forceinline__ void block_cov_body(double* red, int ld, const double* __restrict__ S, int off, int bs, double* __restrict__ out, const double* __restrict__ X)
 {
     // one pass over the rows k <= off + bs - 1 for all bs (bs + 1) / 2 column pairs at once (bs <= 6: 21 sums), one block reduction — round 4 ran one reduction per pair,
     // ten dependent passes for the robot block that the step-wise API hands back with every frame's status
-    __shared__ double red[16 * 21];
-    const int ld = d.np;
     if (X && (int)threadIdx.x < bs) out[bs * bs + threadIdx.x] = X[off + threadIdx.x];
     double v[21];
 #pragma unroll
@@ -669,15 +668,22 @@ __global__ __launch_bounds__(256) void k_block_cov(KDims d, const double* __rest
         for (int b = a; b < 6; b++) { if (a < bs && b < bs) { out[a * bs + b] = v[q]; out[b * bs + a] = v[q]; } q++; }
 }
 
+__global__ __launch_bounds__(256) void k_block_cov(KDims d, const double* __restrict__ S, int off, int bs, double* __restrict__ out, const double* __restrict__ X)
+{
+    __shared__ double red[16 * 21];
+    block_cov_body(red, d.np, S, off, bs, out, X);
+}
+
 // k_landmarks_cartesian: getFeatureCartesianInformation (SLAM.cpp:2721-2751) for ALL landmarks in one launch — the
 // per-paint loop of OpenGlDisplay.cpp:449-583 reads xyz and the 3x3 Cartesian covariance of every landmark, which the
 // reference takes from m_P_k = S^T S (a 2 n^3 gemm per frame, 2404).  One workgroup per landmark: the 6x6 block of P
 // (21 column dot products over the rows k <= 6 id + 5), then cov = J P66 J^T with J = [I3 | d(xyz)/d(theta, phi, rho)].
-__global__ __launch_bounds__(256) void k_landmarks_cartesian(KDims d, const double* __restrict__ X, const double* __restrict__ S,
-                                                             double* __restrict__ xyz, double* __restrict__ cov)
+// landmark_cartesian_body: the kernel's body for landmark `id`, ONE text for its two callers (k_landmarks_cartesian, and workgroups 0 .. N - 1 of k_image_view);
+// red: 16 * 21 doubles of LDS
+__device__ __forceinline__ void landmark_cartesian_body(double* red, int id, int ld, const double* __restrict__ X, const double* __restrict__ S,
+                                                        double* __restrict__ xyz, double* __restrict__ cov)
 {
-    __shared__ double red[16 * 21];
-    const int id = blockIdx.x, off = 6 * id, ld = d.np;
+    const int off = 6 * id;
     double v[21];
 #pragma unroll
     for (int q = 0; q < 21; q++) v[q] = 0.0;
@@ -719,6 +725,27 @@ __global__ __launch_bounds__(256) void k_landmarks_cartesian(KDims d, const doub
     double JP[3][6];
     for (int a = 0; a < 3; a++) for (int b = 0; b < 6; b++) { double t = 0.0; for (int k = 0; k < 6; k++) t += J[a][k] * P[k][b]; JP[a][b] = t; }
     for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) { double t = 0.0; for (int k = 0; k < 6; k++) t += JP[a][k] * J[b][k]; cov[9 * id + 3 * a + b] = t; }   // 2749
+}
+
+__global__ __launch_bounds__(256) void k_landmarks_cartesian(KDims d, const double* __restrict__ X, const double* __restrict__ S,
+                                                             double* __restrict__ xyz, double* __restrict__ cov)
+{
+    __shared__ double red[16 * 21];
+    landmark_cartesian_body(red, blockIdx.x, d.np, X, S, xyz, cov);
+}
+
+// k_image_view: the display view behind one frame of an image run (srukf_images_display), N + 1 workgroups, one launch.  Workgroups 0 .. N - 1:
+// k_landmarks_cartesian's body for landmark blockIdx.x into the frame's xyz / cov rows, and Si[4k .. 4k + 3] (the innovation factor the frame's association read:
+// nothing behind the statistics launch writes it) into the frame's Si row.  Workgroup N: k_block_cov's body for the robot block, P4[16] | pose[4] into `robot`.
+// The rows are the host's pointers; every input is final at the launch boundary in front of it, and no workgroup reads what another one writes
+__global__ __launch_bounds__(256) void k_image_view(KDims d, const double* __restrict__ X, const double* __restrict__ S, const double* __restrict__ Si,
+                                                    double* __restrict__ xyz, double* __restrict__ cov, double* __restrict__ robot, double* __restrict__ Si_row)
+{
+    __shared__ double red[16 * 21];
+    const int k = blockIdx.x;
+    if (k == d.N) { block_cov_body(red, d.np, S, d.n - 4, 4, robot, X); return; }
+    if (threadIdx.x < 4) Si_row[4 * k + threadIdx.x] = Si[4 * k + threadIdx.x];
+    landmark_cartesian_body(red, k, d.np, X, S, xyz, cov);
 }
 
 // ---- host-callable launchers -------------------------------------------------------------------
@@ -786,6 +813,11 @@ void srukf_launch_block_cov(hipStream_t st, KDims d, const double* S, int off, i
     hipLaunchKernelGGL(k_block_cov, dim3(1), dim3(256), 0, st, d, S, off, bs, out, X);
 }
 }  // extern "C"
+
+void launch_image_view(hipStream_t st, KDims d, const double* X, const double* S, const double* Si, double* xyz, double* cov, double* robot, double* Si_row)
+{
+    hipLaunchKernelGGL(k_image_view, dim3(d.N + 1), dim3(256), 0, st, d, X, S, Si, xyz, cov, robot, Si_row);
+}
 
 // stand-alone projection kernel for the parity tests (srukf_project_host)
 __global__ void k_project_points(srukf_params p, int count, const double* feat6, const double* pos3, const double* psi,

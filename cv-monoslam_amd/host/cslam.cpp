@@ -1045,6 +1045,9 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     if (!check(srukf_images_ransac(ctx_, isUseRANSAC ? 1 : 0, THRESHOLD_RANSAC))) return 0;                     // the consensus inside every frame, or not
     if ((resumeStoppedBlocks || snapshotsSet_) && !check(srukf_images_snapshots(ctx_, resumeStoppedBlocks ? 1 : 0))) return 0;      // the state at the stop, kept by the first run
     snapshotsSet_ = resumeStoppedBlocks;
+    if ((blockDisplay || displaySet_) && !check(srukf_images_display(ctx_, blockDisplay ? 1 : 0))) return 0;                // the display view behind every frame
+    displaySet_ = blockDisplay;
+    m_blockDisplay.clear(); m_blockDisplayIDs.clear();
     // 3. one image block in jointUpdate's mode, checked with the switches of associateChecked
     const int mode = jointUpdate ? SRUKF_UPDATE_JOINT : SRUKF_UPDATE_BATCHED;
     const bool checked = rejectAmbiguousMatches || subpixelMatches;
@@ -1088,6 +1091,25 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     if (isUseRANSAC) {
         rfl.resize((size_t)used * N); ract.resize(used); rlow.resize(used);
         if (!check(srukf_get_image_ransac(ctx_, 0, used, rfl.data(), nullptr, nullptr, nullptr, ract.data(), rlow.data(), nullptr))) return 0;
+    }
+    if (blockDisplay) {                                                                                         // the display view of every consumed frame, IDs in state order
+        const size_t U = (size_t)used;
+        std::vector<double> xyz(U * 3 * N), cov(U * 9 * N), axis(U * 4 * N), sigma(U * 3 * N), pose(U * 4), P4(U * 16), Si(U * 4 * N);
+        std::vector<int> rot(U * N);
+        if (!check(srukf_get_image_display(ctx_, 0, used, xyz.data(), cov.data(), axis.data(), sigma.data(), rot.data(), pose.data(), P4.data(), Si.data()))) return 0;
+        m_blockDisplay.resize(U);
+        for (size_t f = 0; f < U; f++) {
+            BlockDisplayFrame& d = m_blockDisplay[f];
+            d.xyz.assign(xyz.begin() + f * 3 * N, xyz.begin() + (f + 1) * 3 * N); d.cov.assign(cov.begin() + f * 9 * N, cov.begin() + (f + 1) * 9 * N);
+            d.axis.assign(axis.begin() + f * 4 * N, axis.begin() + (f + 1) * 4 * N); d.sigma.assign(sigma.begin() + f * 3 * N, sigma.begin() + (f + 1) * 3 * N);
+            d.Si.assign(Si.begin() + f * 4 * N, Si.begin() + (f + 1) * 4 * N); d.rot.assign(rot.begin() + f * N, rot.begin() + (f + 1) * N);
+            std::copy(pose.begin() + f * 4, pose.begin() + (f + 1) * 4, d.pose); std::copy(P4.begin() + f * 16, P4.begin() + (f + 1) * 16, d.P4);
+        }
+        for (int k = 0; k < N; k++) m_blockDisplayIDs.push_back(map[k].ID);
+        if (blockOverlayLast) {                                                                                 // (in front of the tail: a map change drops the staged frames)
+            m_srcImage.resize(3 * img);
+            if (!check(srukf_render_image_overlay(ctx_, used - 1, m_srcImage.data()))) return 0;
+        }
     }
     const int n = m_X_k.rows;
     m_blockPath.assign(traj.begin(), traj.begin() + 8 * (size_t)used);
@@ -1143,6 +1165,13 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     m_frameTime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / used;
     m_totalTime += m_frameTime * used;
     return used;
+}
+
+// display2DFeatureModel (SLAM.cpp:3009-3051) for consumed frame f of the last SLAMBlock, from the device's own rows
+bool CSLAM::renderBlockOverlay(int f, unsigned char* out_bgr)
+{
+    if (!ctx_ || !out_bgr || f < 0 || f >= (int)m_blockDisplay.size()) return false;
+    return srukf_render_image_overlay(ctx_, f, out_bgr) == SRUKF_OK;
 }
 
 }  // namespace monoslam

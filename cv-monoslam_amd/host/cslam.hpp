@@ -114,7 +114,23 @@ public:
     // resumeStoppedBlocks: the block's frames keep the state they start from while no stop is on record (srukf_images_snapshots), and a block
     // that stops at 0 < used < F takes the state at the stop from the first run (srukf_images_resume) in place of the rewind and the second run; where no slot
     // holds it (SRUKF_ERR_SEQUENCE) the rewind and the rerun follow as before.  m_nBlocksResumed counts the resumes.  Off: exactly the calls above
+    // blockDisplay: the block's frames leave the display view SLAM() refreshes after every update (updateFeaturesInformation ->
+    // refreshFeaturesDisplay, SLAM.cpp:2566-2575) in a record on the device (srukf_images_display); behind step 6 the rows of the consumed frames are read into
+    // m_blockDisplay, one BlockDisplayFrame each, with the block's landmark IDs in state order in m_blockDisplayIDs.  The last frame's tail is unchanged (its row
+    // is the view in front of that tail's map changes).  renderBlockOverlay(f, out): display2DFeatureModel (3009-3051) for consumed frame f of the last block over
+    // its gray image, image_h x image_w x 3 bytes (srukf_render_image_overlay); false where no block with blockDisplay has consumed that frame, or the map has
+    // changed since — the last frame's tail may change it, so with blockOverlayLast SLAMBlock itself leaves the last consumed frame's overlay in m_srcImage, drawn
+    // in front of that tail.  Off and never on: exactly the calls above
     int  SLAMBlock(const unsigned char* gray, int F);
+    struct BlockDisplayFrame {
+        std::vector<double> xyz, cov, axis, sigma, Si;         // [3N], [9N], [4N] (quaternion r, x, y, z), [3N], [4N]
+        std::vector<int> rot;                                  // [N]
+        double pose[4], P4[16];
+    };
+    bool blockDisplay = false, blockOverlayLast = false;
+    std::vector<BlockDisplayFrame> m_blockDisplay;             // the last SLAMBlock's display view per consumed frame (blockDisplay; empty without)
+    std::vector<int> m_blockDisplayIDs;                        // ... and the block's landmark IDs in state order
+    bool renderBlockOverlay(int f, unsigned char* out_bgr);
     bool resumeStoppedBlocks = false;
     int  m_nBlocksResumed = 0;
     std::vector<double> m_blockPath;                           // the last SLAMBlock's RobotPath numbers, 8 per consumed frame: x, y, z, theta, P00, P01, P10, P11
@@ -321,6 +337,7 @@ private:
     void refreshMirrors();
     bool check(int rc);
     srukf_ctx* ctx_ = nullptr;
+    bool displaySet_ = false;            // srukf_images_display is on on the handle (SLAMBlock switches it off again when blockDisplay goes off)
     bool snapshotsSet_ = false;          // srukf_images_snapshots is on on the handle (SLAMBlock switches it off again when resumeStoppedBlocks goes off)
     bool mirrorsFresh_ = false;          // m_X_k / the robot block of m_P_k were fetched by this frame's display refresh
     int device_ = 0;

@@ -37,6 +37,9 @@
 //              texture flags every landmark in every frame), k = 1; without the policy the slots hold the starts of the block's last two frames,
 //              k = block - 1.  The tool runs BOTH legs on fresh handles, the other one first and untimed in the report, and exits with status 3 unless both end
 //              at the same pose and robot covariance, bit for bit.  Adds "stop": {k, resume, blocks} to the output
+//              display=1 (assoc_replay only): the blocks run with srukf_images_display on: every frame is followed by k_image_view + k_lm_ellipsoid and
+//              the run is issued frame by frame.  This measures the switch's price: with policy=1 the two launches alone, without it also the eight-frame graphs the
+//              run gives up.  Adds "display": 1 to the output
 //              profile=1 (assoc_replay only): the timed blocks run with srukf_set_profiling on (eager launches); adds "profile_ms_per_frame" by kernel class
 //     hint=1 : capi / assoc announce the NEXT frame's odometry with srukf_predict_motion_next before every update (a host that has its odometry
 //              file loaded, as the reference has: loadOdometryData reads it whole, SLAM.cpp:363-496)
@@ -81,6 +84,7 @@ int main(int argc, char** argv)
     int policy = 0; long long pol_change = 0, pol_deletes = 0, pol_adds = 0;      // policy= (assoc_replay)
     double ransac_thr = 0.0; long long rs_outlier = 0, rs_low = 0;      // ransac=<threshold> (assoc_replay)
     int resume = -1, stop_k = 0; long long stop_blocks = 0;      // resume= / stop= (assoc_replay)
+    int display = 0;      // display= (assoc_replay)
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -99,6 +103,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "policy=", 7)) policy = atoi(argv[a] + 7);
         else if (!strncmp(argv[a], "resume=", 7)) resume = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "stop=", 5)) stop_k = atoi(argv[a] + 5);
+        else if (!strncmp(argv[a], "display=", 8)) display = atoi(argv[a] + 8) != 0;
         else if (!strncmp(argv[a], "subpix=", 7)) { if (atoi(argv[a] + 7)) { checked = true; mpar.subpixel = 1; } }
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } sets.emplace_back(std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))), atoi(q + 1)); }
     }
@@ -137,6 +142,7 @@ int main(int argc, char** argv)
     if (checked && !areplay) { fprintf(stderr, "unique= / subpix= belong to mode=assoc_replay\n"); return 2; }
     if ((arcL || arc_step || profile || policy) && !areplay) { fprintf(stderr, "archive= / archive_step= / profile= / policy= belong to mode=assoc_replay\n"); return 2; }
     if (arcL < 0 || arcL > 64 || (arc_step && !arcL)) { fprintf(stderr, "archive=<L>: 1 <= L <= 64 (archive_step=1 needs it)\n"); return 2; }
+    if (display && !areplay) { fprintf(stderr, "display= belongs to mode=assoc_replay\n"); return 2; }
     if ((resume >= 0 || stop_k) && !areplay) { fprintf(stderr, "resume= / stop= belong to mode=assoc_replay\n"); return 2; }
     if (stop_k && (resume < 0 || stop_k < 1 || stop_k >= block_frames || arcL || profile)) { fprintf(stderr, "stop=<k> needs resume=0|1 and 0 < k < block, without archive= and profile=\n"); return 2; }
     const int legs = stop_k ? 2 : 1;                                // stop=: both routes, the one asked for last (it is the one reported)
@@ -359,6 +365,7 @@ int main(int argc, char** argv)
             if (policy) CK(srukf_images_policy(c, 1, nullptr));
             if (ransac_thr > 0.0) CK(srukf_images_ransac(c, 1, ransac_thr));
             if (snap) CK(srukf_images_snapshots(c, 1));
+            if (display) CK(srukf_images_display(c, 1));
             std::vector<int> rlow(block_frames), ract(block_frames), rinl(N);
             std::vector<srukf_policy_summary> prow(block_frames);
             std::vector<int> mrow((size_t)block_frames * N), frow(checked ? (size_t)block_frames * N : 0), fl(checked ? N : 0), hrow(block_frames), am(arcL);
@@ -494,6 +501,7 @@ int main(int argc, char** argv)
     if (areplay && ransac_thr > 0.0) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"ransac\": {\"threshold\": %.6g, \"outlier_frames\": %lld, \"low_inliers\": %lld}, ",
                                               ransac_thr, rs_outlier, rs_low);
     if (areplay && resume >= 0) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"resume\": %d, ", resume);
+    if (areplay && display) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"display\": 1, ");
     if (stop_k) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"stop\": {\"k\": %d, \"resume\": %d, \"blocks\": %lld, \"poses_equal\": 1}, ", stop_k, resume, stop_blocks);
     if (mode == "replay") snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"replay_form\": \"%s\", \"exact_frames\": %d, ", replay_form, joint_flagged);
     printf("{\"mode\": \"%s\", %s%s%s%s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "

@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [display=<file>]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -31,9 +31,14 @@
 //   front of a frame whose consensus dropped a match, and SLAM() runs that frame with its rescue (a fallback).
 // resume=1 (with block=<F>): CSLAM::resumeStoppedBlocks on: a block that stops early takes the state at the stop from its first run instead of
 //   running the frames in front of the stop again; " resumed=<count>" is appended to the "blocks" line.  Without it the output is what it was.
+// display=<file> (with block=<F>, block=1 too): CSLAM::blockDisplay and ellipsoidsOnDevice on; <file> gets, per frame and per landmark of the map
+//   behind that frame's tail, one line "frame ID" and xyz, cov, axis, sigma as %a (a NaN as "nan" whatever its sign): for the last consumed frame of a block (and
+//   every frame of block=1) from map[], for the frames in front of it from m_blockDisplay.  The same file through either route.  With overlay=<file> the overlay of
+//   the last block's last consumed frame goes to <file> (CSLAM::blockOverlayLast: drawn in front of that frame's tail); stdout is what it is without both.
 // min_matches=<n>: CSLAM::m_minNUM = n (addFeatures when fewer landmarks matched, SLAM.cpp:179, 556; default 5).
 // warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
 // Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,7 +48,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [min_matches=<n>]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [display=<file>] [min_matches=<n>]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -51,7 +56,7 @@ int main(int argc, char** argv)
     std::vector<unsigned char> frames((size_t)W * H * F);
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
-    int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay;
+    int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay, display;
     bool unique = false, subpix = false, joint = false, resume = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
     int minMatches = 0, block = 0, nBlocks = 0, nEarly = 0, nFull = 0, nFallback = 0;
     for (int a = 3; a < argc; a++)
@@ -65,6 +70,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6) != 0;
         else if (!strncmp(argv[a], "block=", 6)) block = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "resume=", 7)) resume = atoi(argv[a] + 7) != 0;
+        else if (!strncmp(argv[a], "display=", 8)) display = argv[a] + 8;
         else if (!strncmp(argv[a], "min_matches=", 12)) minMatches = atoi(argv[a] + 12);
     if (warmup) {
         monoslam::CSLAM w;
@@ -103,6 +109,30 @@ int main(int argc, char** argv)
         if (block > 1 && (colour || loops || archiveCap > 0)) { fprintf(stderr, "block=<F> runs without colour=, loops and archive=\n"); return 2; }
         if (steps > F) steps = F;
         const auto assoc = SLAM.dataAssociation;
+        FILE* fd = nullptr;
+        if (!display.empty()) {
+            fd = fopen(display.c_str(), "w");
+            if (!fd) { perror(display.c_str()); return 1; }
+            SLAM.blockDisplay = true; SLAM.ellipsoidsOnDevice = true;
+            SLAM.blockOverlayLast = !overlay.empty();
+        }
+        auto num = [&](double v) { if (std::isnan(v)) fprintf(fd, " nan"); else fprintf(fd, " %a", v); };
+        auto displayLine = [&](int fr, int id, const double* xyz, const double* cov, const double* axis, const double* sigma) {
+            fprintf(fd, "%d %d", fr, id);
+            for (int e = 0; e < 3; e++) num(xyz[e]);
+            for (int e = 0; e < 9; e++) num(cov[e]);
+            for (int e = 0; e < 4; e++) num(axis[e]);
+            for (int e = 0; e < 3; e++) num(sigma[e]);
+            fprintf(fd, "\n");
+        };
+        auto displayFromMap = [&](int fr) {
+            if (!fd) return;
+            for (const monoslam::PointsMap* m = SLAM.map; m; m = m->next) {
+                const double xyz[3] = { m->xyz.x, m->xyz.y, m->xyz.z }, axis[4] = { m->axis.r, m->axis.x, m->axis.y, m->axis.z }, sigma[3] = { m->sigma.x, m->sigma.y, m->sigma.z };
+                displayLine(fr, m->ID, xyz, m->cov, axis, sigma);
+            }
+        };
+        bool overlayDrawn = false;
         auto report = [&](int fr, int nBefore) {
             printf("policy frame %d deleted %d", fr, SLAM.m_nDeletes); for (int id : SLAM.m_deleteID) printf(" %d", id);
             printf(" added %d\n", SLAM.m_nMapFeatures - (nBefore - SLAM.m_nDeletes));
@@ -127,8 +157,14 @@ int main(int argc, char** argv)
                     printf("policy frame %d deleted 0 added 0\n", fr + q);
                     printf("path %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", fr + q, t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
                     if (ransac) printf("ransac low %d high 0\n", SLAM.m_blockLowInliers[q]);
+                    if (fd) {
+                        const auto& d = SLAM.m_blockDisplay[(size_t)q];
+                        for (size_t k = 0; k < SLAM.m_blockDisplayIDs.size(); k++) displayLine(fr + q, SLAM.m_blockDisplayIDs[k], &d.xyz[3 * k], &d.cov[9 * k], &d.axis[4 * k], &d.sigma[3 * k]);
+                    }
                 }
                 report(fr + used - 1, nBefore);
+                displayFromMap(fr + used - 1);
+                overlayDrawn = SLAM.blockOverlayLast;
                 fr += used;
                 continue;
             }
@@ -140,7 +176,15 @@ int main(int argc, char** argv)
             if (!SLAM.lastError.empty()) { fprintf(stderr, "frame %d: %s\n", fr, SLAM.lastError.c_str()); return 1; }
             wall += SLAM.m_frameTime;
             report(fr, nBefore);
+            displayFromMap(fr);
             fr++;
+        }
+        if (fd) fclose(fd);
+        if (fd && !overlay.empty()) {
+            if (!overlayDrawn) { fprintf(stderr, "overlay: no block consumed a frame\n"); return 1; }
+            FILE* fo = fopen(overlay.c_str(), "wb");
+            if (!fo || fwrite(SLAM.m_srcImage.data(), 1, SLAM.m_srcImage.size(), fo) != SLAM.m_srcImage.size()) { perror(overlay.c_str()); return 1; }
+            fclose(fo);
         }
         if (resume) printf("blocks %d early %d full %d fallback %d resumed=%d\n", nBlocks, nEarly, nFull, nFallback, SLAM.m_nBlocksResumed);
         else printf("blocks %d early %d full %d fallback %d\n", nBlocks, nEarly, nFull, nFallback);

@@ -37,6 +37,7 @@ EXPORTS = [
     "srukf_map_policy", "srukf_images_policy", "srukf_images_set_policy_state", "srukf_get_image_policy", "srukf_images_rewind",
     "srukf_images_ransac", "srukf_get_image_ransac",
     "srukf_images_snapshots", "srukf_get_image_snapshots", "srukf_images_resume",
+    "srukf_images_display", "srukf_get_image_display", "srukf_render_image_overlay",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -209,6 +210,10 @@ def load_library(path=None):
         L.srukf_images_snapshots.argtypes = [C.c_void_p, C.c_int]
         L.srukf_get_image_snapshots.argtypes = [C.c_void_p, _ip]
         L.srukf_images_resume.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "srukf_images_display"):             # (idem: the display view behind image frames, the overlay of a staged frame)
+        L.srukf_images_display.argtypes = [C.c_void_p, C.c_int]
+        L.srukf_get_image_display.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp]
+        L.srukf_render_image_overlay.argtypes = [C.c_void_p, C.c_int, _bp]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -858,6 +863,39 @@ class Filter:
         if keep < 0:
             raise ValueError("images_resume: keep must be >= 0")
         self._chk(self._lib.srukf_images_resume(self._h, int(keep)))
+
+    # ---- the display view behind image frames, the overlay of a staged frame (srukf_images_display) ----
+    def images_display(self, on):
+        """The switch of the display view behind image frames (srukf_images_display): while on, every frame of every later run_images* / run_images_checked* is
+        followed by get_frame_view_display's launches into that frame's row of a record (get_image_display), and render_image_overlay can draw the frame.  The
+        run is issued frame by frame, as with images_policy.  Not while a run is in flight or a block is pending."""
+        if not isinstance(on, (bool, np.bool_)) and not (isinstance(on, (int, np.integer)) and on in (0, 1)):
+            raise TypeError("images_display: on must be a bool")
+        self._chk(self._lib.srukf_images_display(self._h, int(bool(on))))
+
+    def get_image_display(self, first, count):
+        """The display view behind staged frames [first, first + count) (srukf_get_image_display): dict of xyz[count, N, 3], cov[count, N, 3, 3],
+        axis[count, N, 4], sigma[count, N, 3], rot[count, N], pose[count, 4], P4[count, 4, 4] and Si[count, N, 2, 2] (what the frame's association read).
+        Rows no run with images_display on has written are zero."""
+        self._image_run_args(first, count, UPDATE_BATCHED)
+        N = self.N
+        out = dict(xyz=np.zeros((count, N, 3)), cov=np.zeros((count, N, 3, 3)), axis=np.zeros((count, N, 4)), sigma=np.zeros((count, N, 3)),
+                   rot=np.zeros((count, N), dtype=np.int32), pose=np.zeros((count, 4)), P4=np.zeros((count, 4, 4)), Si=np.zeros((count, N, 2, 2)))
+        self._chk(self._lib.srukf_get_image_display(self._h, int(first), int(count), _d(out["xyz"]), _d(out["cov"]), _d(out["axis"]), _d(out["sigma"]),
+                                                    _i(out["rot"]), _d(out["pose"]), _d(out["P4"]), _d(out["Si"])))
+        return out
+
+    def render_image_overlay(self, frame):
+        """render_overlay for staged frame `frame` from what the device holds (srukf_render_image_overlay): the frame's gray image with the predicted cross, the
+        matched cross and the chi-square ellipse of every landmark the filter used.  Returns bgr[image_h, image_w, 3] uint8.  SrukfError(SRUKF_ERR_SEQUENCE)
+        when no run with images_display on has written that frame's row."""
+        if isinstance(frame, (bool, np.bool_)) or not isinstance(frame, (int, np.integer)):
+            raise TypeError("render_image_overlay: frame must be an int")
+        if frame < 0:
+            raise ValueError("render_image_overlay: frame must be >= 0")
+        out = np.zeros((int(self.params.image_h), int(self.params.image_w), 3), dtype=np.uint8)
+        self._chk(self._lib.srukf_render_image_overlay(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out
 
     def synchronize(self):
         self._chk(self._lib.srukf_synchronize(self._h))

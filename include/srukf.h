@@ -664,6 +664,31 @@ int  srukf_images_snapshots(srukf_ctx* ctx, int on);
 int  srukf_get_image_snapshots(srukf_ctx* ctx, int frames[2]);
 int  srukf_images_resume(srukf_ctx* ctx, int keep);
 
+/* ---- the display view behind every frame of an image run, the overlay of any staged frame ----
+ * srukf_images_display: a switch on the handle, like srukf_images_snapshots: it survives map changes and srukf_reset (which drop the record with the staged
+ *   images); srukf_destroy ends it.  Not while a run is in flight or a block is pending (SRUKF_ERR_SEQUENCE).  The call touches no device.  While on, every frame
+ *   of every later image run (all kinds, BATCHED and JOINT) is followed by what the reference's SLAM() refreshes for its display after every update
+ *   (updateFeaturesInformation -> refreshFeaturesDisplay, SLAM.cpp:2566-2575; recordRobotInformation 3539-3556), written into the frame's row of a record:
+ *   srukf_get_frame_view_display's xyz, cov, axis, sigma, pose4 and P4 and srukf_get_landmarks_display's rot on the frame's posterior, bit for bit, and Si, the
+ *   innovation factors the frame's association read (srukf_predict_measurement's).  Two launches behind the frame (k_image_view, k_lm_ellipsoid); the run is
+ *   issued frame by frame as a policy run is, so a run without the policy gives up its eight-frame graphs.  The launches read the state and write the record
+ *   only: the filter computes exactly what it computes without them.  With the switch off an image run is exactly what it was.
+ * srukf_get_image_display: rows [first, first + count) of that record, after waiting for the stream like srukf_get_image_matches: xyz[count][N][3],
+ *   cov[count][N][9], axis[count][N][4] (quaternion r, x, y, z), sigma[count][N][3], rot[count][N], pose4[count][4], P4[count][16], Si[count][N][4].  Any
+ *   pointer may be NULL, not all of them (SRUKF_ERR_BAD_ARG).  Rows no such frame has written are zero — all of them before the first run with the switch on —
+ *   and so are rows >= the stop after srukf_images_resume and all rows after a flagged block's restore or srukf_images_rewind, until frames run again.  A row
+ *   whose frame a run without the switch has run again keeps the earlier run's values (srukf_get_image_checks' rule) and is no longer drawable.
+ *   SRUKF_ERR_SEQUENCE: no images staged; SRUKF_ERR_DIM_MISMATCH: rows outside the staged stack.
+ * srukf_render_image_overlay: srukf_render_overlay (display2DFeatureModel, SLAM.cpp:3009-3051) for staged frame `frame` with nothing uploaded: the frame's
+ *   predicted pixels, the record's Si row, the frame's z and `matched` rows (behind a consensus run the rewritten row: what the filter used) drawn over the
+ *   frame's gray image in the staged stack, gray byte three times, into out_bgr[image_h][image_w][3].  Waits for the stream first; reads and writes nothing the
+ *   filter reads.  SRUKF_ERR_SEQUENCE: no images staged, or no run with the switch on has written that frame's row since it was last zeroed (the library keeps a
+ *   mark per row on the host); SRUKF_ERR_BAD_ARG: frame outside the stack, out_bgr NULL; SRUKF_ERR_UNSUPPORTED: image_w * image_h is no multiple of four.
+ * All: SRUKF_ERR_BAD_ARG for a NULL handle (srukf_get_image_display: first < 0, count < 1) before any device is touched. */
+int  srukf_images_display(srukf_ctx* ctx, int on);
+int  srukf_get_image_display(srukf_ctx* ctx, int first, int count, double* xyz, double* cov, double* axis, double* sigma, int* rot, double* pose4, double* P4, double* Si);
+int  srukf_render_image_overlay(srukf_ctx* ctx, int frame, unsigned char* out_bgr);
+
 /* ---- instrumentation ------------------------------------------------------------------------ */
 
 /* When on, every kernel launch is bracketed by HIP events on the context's stream and the
