@@ -8,6 +8,8 @@
 //   srukf_batch.hip   batched replay (srukf_run_frames_batch)
 //   srukf_map.hip     map changes (srukf_add_landmarks / srukf_delete_landmark / srukf_insert_landmarks) and data association
 //   srukf_ransac.hip  1-point RANSAC: the consensus over all single-match hypotheses, the measurement prediction from the posterior
+//   srukf_rescue.hip  the rescue gate: would a match the consensus dropped be rescued? (srukf_rescue_gate; srukf_images_rescue_gate: k_rescue_gate_staged behind the
+//                     tail of the frames that hold the consensus, issued by srukf_images.hip)
 //   srukf_overlay.hip colour-frame intake (srukf_set_frame_bgr) and the 2-D feature overlay (srukf_render_overlay)
 //   srukf_loop.hip    loop points: the record an archived landmark takes along, the placement of re-inserted landmarks
 //   srukf_archive.hip the archive on the handle and its search by appearance (srukf_archive_set / srukf_archive_search), step-wise and behind the frames of an image run
@@ -77,6 +79,8 @@ struct RansacScratch {
     double *Ut = nullptr, *D = nullptr, *zin = nullptr, *res = nullptr, *X = nullptr, *S = nullptr, *odo = nullptr;
     double *sigR = nullptr, *Cm = nullptr, *Z = nullptr, *DZ = nullptr, *h = nullptr, *PxyR = nullptr, *mpart = nullptr;
     unsigned char* F = nullptr; int* votes = nullptr; FrameScalars* fs = nullptr;
+    // srukf_rescue_gate: rq_in = z (mp) | matched, inlier (N ints each); rq_out = h2 (2N) | Si2 (4N) | chi2 (N) | flags (N ints); rq_scr = PxyR (5 mp) | vis (N ints)
+    double *rq_in = nullptr, *rq_out = nullptr, *rq_scr = nullptr;
 };
 
 // the archive searched by appearance (srukf_archive.hip): L records in the layouts of srukf_insert_landmarks (patch / tmpl with the strides of the map's appearance
@@ -95,14 +99,14 @@ struct ArchiveState {
 // sequence's lifetime: images_drop.
 // graphs: the captured frames (one and eight) of every form of an image frame and update mode, ONE table: graphs[ImageForm::index()][0 BATCHED / 1 JOINT].  A form
 // never replays a frame captured for another one (nor a frame of srukf_run_frames*, nor the other way round): the index is the guarantee.  drop_graphs walks the table.
-// The device buffers come in seven groups, each named once (image_group, srukf_images.hip): allocation, images_drop and images_archive_drop all go through those lists
+// The device buffers come in eight groups, each named once (image_group, srukf_images.hip): allocation, images_drop and images_archive_drop all go through those lists
 struct ImageReplay {
     unsigned char *images = nullptr, *ck_tmpl = nullptr;
     double *corr_seq = nullptr, *h_seq = nullptr, *xyz = nullptr, *ckS = nullptr, *ckX = nullptr;
     int* vis_seq = nullptr;
     int frames = 0;
     bool pending = false, ck_canon = false;
-    ReplayGraphs graphs[16][2];
+    ReplayGraphs graphs[32][2];
     // Checked image runs (srukf_run_images_checked*), allocated by images_checked_ensure on the first one: the checked record corr2_seq [F][N],
     // z2_seq [F][2N], flags_seq [F][N] (zero until a checked run writes a row) and the parameters the checked frames read (match_args, written in stream order in front
     // of every checked run).  The captured checked frames hold the pointer of the filter's score buffer they were captured with, chk_scores.  checked: the block in
@@ -131,6 +135,13 @@ struct ImageReplay {
     double *rs_D = nullptr, *rs_dist = nullptr; unsigned char* rs_F = nullptr; int *rs_votes = nullptr, *rs_flags = nullptr, *rs_rvotes = nullptr;
     RansacSummary* rs_sum = nullptr; RansacArgs* rs_args = nullptr;
     bool rs_valid = false;
+    // The rescue gate behind the tail of such frames (srukf_images_rescue_gate), allocated by images_rescue_ensure in front of the first run with
+    // both switches on: the record (rq_flags [frames][N], rq_h2 [frames][2N], rq_Si2 [frames][4N], rq_chi2 [frames][N], rq_sum [frames], zero until such a frame writes
+    // a row, zeroed again by images_restore), what meas_final_tail stores besides (rq_vis [N], rq_PxyR [5 mp]) and the threshold the launches read (rq_args, written in
+    // stream order in front of every such run).  rq_valid: such a run has written the record
+    int *rq_flags = nullptr, *rq_vis = nullptr; double *rq_h2 = nullptr, *rq_Si2 = nullptr, *rq_chi2 = nullptr, *rq_PxyR = nullptr;
+    RescueSummary* rq_sum = nullptr; RescueArgs* rq_args = nullptr;
+    bool rq_valid = false;
     // The state a block is resumed from (srukf_images_snapshots / srukf_images_resume), allocated by images_snapshot_ensure in front of the first
     // run with the switch on: two slots of { X, S, the matchPatch array, the policy state } (slot f & 1: the state frame f started from), the tags and the latch
     // (sn_ctl), the guard's parameters (sn_args, written in stream order in front of every such run).  The block, as srukf_images_resume needs it: blk_first its first
@@ -193,6 +204,8 @@ struct srukf_handle_scope : srukf_switches {
     srukf_policy_params img_policy_args = SRUKF_POLICY_DEFAULTS;   // ... these parameters.  Survives map changes; srukf_reset clears it
     bool img_ransac = false;               // srukf_images_ransac: every frame of every later image run holds the 1-point RANSAC consensus between association and update, with ...
     double img_ransac_thr = 8.0;           // ... this threshold.  Survives map changes and srukf_reset
+    bool img_rescue = false;               // srukf_images_rescue_gate: every frame of every later image run that holds the consensus is followed by the rescue gate, with ...
+    double img_rescue_chi2 = 5.99146454710798;      // ... this threshold (CHI2INV_TABLE(0, 2)).  Survives map changes and srukf_reset
     bool img_snap = false;                 // srukf_images_snapshots: every frame of every later image run begins with k_image_snapshot.  Survives map changes and srukf_reset
     bool img_display = false;              // srukf_images_display: every frame of every later image run is followed by k_image_view + k_lm_ellipsoid into its row of the display record.  Survives map changes and srukf_reset
     std::string err;
@@ -492,15 +505,18 @@ struct FrameForm {
 constexpr FrameForm FORM_SEPARATE_STATS{ MEAS_SEPARATE_STATS, false }, FORM_PLAIN{ MEAS_PLAIN, false }, FORM_FUSED_TAIL{ MEAS_FUSED_TAIL, true };
 // What a frame of an image run holds beyond the plain frame form (replay_one_image_frame): checked — k_associate_checked_staged in k_associate_staged's place;
 // search — the archive search behind its tail; ransac — the consensus between association and update; snap — k_image_snapshot in front of it (DESIGN.md
-// section 25).  index(): the form's row of ImageReplay::graphs.
+// section 25); rescue — the rescue gate behind its tail, in front of the archive search (only ever set with ransac).  index(): the form's row
+// of ImageReplay::graphs.  IMAGE_FORMS counts the forms without the gate, as it did; a gated form's row is its ungated form's + IMAGE_FORMS (IMAGE_FORM_ROWS rows in all,
+// of which only those with ransac are ever issued or captured)
 // The map policy is no part of the form: it has no captured frames of its own, it is an eager launch behind each frame and a property of the run (run_images_issue)
-struct ImageForm {
-    bool checked, search, ransac, snap;
-    int index() const { return (checked ? 1 : 0) | (search ? 2 : 0) | (ransac ? 4 : 0) | (snap ? 8 : 0); }
-    static ImageForm at(int index) { return ImageForm{ (index & 1) != 0, (index & 2) != 0, (index & 4) != 0, (index & 8) != 0 }; }
-};
 constexpr int IMAGE_FORMS = 16;
-static_assert(sizeof(ImageReplay::graphs) / sizeof(ImageReplay::graphs[0]) == IMAGE_FORMS, "ImageReplay::graphs has one row per form of an image frame");
+constexpr int IMAGE_FORM_ROWS = 2 * IMAGE_FORMS;
+struct ImageForm {
+    bool checked, search, ransac, snap, rescue;
+    int index() const { return ((checked ? 1 : 0) | (search ? 2 : 0) | (ransac ? 4 : 0) | (snap ? 8 : 0)) + (rescue ? IMAGE_FORMS : 0); }
+    static ImageForm at(int index) { return ImageForm{ (index & 1) != 0, (index & 2) != 0, (index & 4) != 0, (index & 8) != 0, index >= IMAGE_FORMS }; }
+};
+static_assert(sizeof(ImageReplay::graphs) / sizeof(ImageReplay::graphs[0]) == IMAGE_FORM_ROWS, "ImageReplay::graphs has one row per form of an image frame");
 // What is asked of a refactorisation  S <- gmw(S^T S - U[ub:ue] U[ub:ue]^T):  the tail of a staged or fast-path frame (no backup, the last launch ends the frame) /
 // checked (G kept in Gbak, the host reads clamp_rows afterwards) / one column of SEQUENTIAL mode (as checked, behind a reset of the gamma / xi accumulators)
 struct RefactorRequest { enum Kind { FRAME_TAIL, CHECKED, SEQ_COLUMN } kind; int ub, ue; };

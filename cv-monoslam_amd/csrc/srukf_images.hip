@@ -1,6 +1,6 @@
 // srukf_images.hip — image runs of the staged replay (DESIGN.md sections 20 - 26): the staged gray frames and the frames that associate on the device
 // (srukf_stage_images / srukf_run_images*), with the checked association (srukf_run_images_checked*), the archive search (srukf_images_search_archive), the map
-// policy's verdict (srukf_images_policy), the 1-point RANSAC consensus (srukf_images_ransac) and the display view (srukf_images_display; section 26, with the overlay
+// policy's verdict (srukf_images_policy), the 1-point RANSAC consensus (srukf_images_ransac), its rescue gate (srukf_images_rescue_gate; section 27) and the display view (srukf_images_display; section 26, with the overlay
 // of any staged frame, srukf_render_image_overlay) as options of a run, and the getters of their records.  No kernel:
 // the launch sequences, the graph cache and srukf_synchronize are srukf_replay.hip's; what the two files share is declared once in srukf_ctx.h.
 // A further per-frame option is: one bit of ImageForm, one group of image_group, one branch of replay_one_image_frame
@@ -14,12 +14,12 @@ namespace srukf_impl {
 // images_drop and images_archive_drop free through the same lists: a buffer added HERE is freed without anyone remembering to list it.  The sizes are the allocation's
 // (image_bytes: of one staged frame, L: the archive's; whoever only frees passes neither).  Zeroed: the records (rows no run has written read as zero) and the
 // consensus scratch; not the parameter blocks (written in stream order in front of every run that reads them), the images, xyz and the checkpoint copies
-enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_SNAPSHOT, IMG_DISPLAY, IMG_GROUPS };
+enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_SNAPSHOT, IMG_DISPLAY, IMG_RESCUE, IMG_GROUPS };
 struct ImageBuf { void** p; size_t bytes; bool zero; };
 static std::vector<ImageBuf> image_group(srukf_map_scope* c, ImageGroup g, size_t image_bytes = 0, size_t L = 0)
 {
     ImageReplay& im = c->img;
-    const size_t N = c->d.N, np = c->d.np, f = (size_t)im.frames, D = sizeof(double), I = sizeof(int);
+    const size_t N = c->d.N, np = c->d.np, mp = c->d.mp, f = (size_t)im.frames, D = sizeof(double), I = sizeof(int);
     auto buf = [](auto** p, size_t bytes, bool zero = false) { return ImageBuf{ (void**)p, bytes, zero }; };
     switch (g) {
     case IMG_STAGED: return { buf(&im.images, f * image_bytes), buf(&im.corr_seq, D * f * N, true), buf(&im.vis_seq, I * f * N, true), buf(&im.h_seq, D * f * 2 * N, true),
@@ -35,6 +35,8 @@ static std::vector<ImageBuf> image_group(srukf_map_scope* c, ImageGroup g, size_
                                 buf(&im.sn_pol[0], sizeof(srukf_policy_state) * N), buf(&im.sn_pol[1], sizeof(srukf_policy_state) * N),
                                 buf(&im.sn_ctl, sizeof(SnapshotCtl)), buf(&im.sn_args, sizeof(SnapshotArgs)) };
     case IMG_DISPLAY: return { buf(&im.dp_rec, D * f * image_display_row(N).doubles, true), buf(&im.dp_rot, I * f * N, true) };
+    case IMG_RESCUE: return { buf(&im.rq_flags, I * f * N, true), buf(&im.rq_h2, D * f * 2 * N, true), buf(&im.rq_Si2, D * f * 4 * N, true), buf(&im.rq_chi2, D * f * N, true),
+                              buf(&im.rq_sum, sizeof(RescueSummary) * f, true), buf(&im.rq_vis, I * N, true), buf(&im.rq_PxyR, D * 5 * mp, true), buf(&im.rq_args, sizeof(RescueArgs)) };
     default: return {};
     }
 }
@@ -61,7 +63,7 @@ static int image_buffers_alloc(srukf_ctx* c, const std::vector<ImageBuf>& bufs, 
 void images_archive_drop(srukf_map_scope* c, hipStream_t st)
 {
     ImageReplay& im = c->img;
-    for (int i = 0; i < IMAGE_FORMS; i++) if (ImageForm::at(i).search) for (int m = 0; m < 2; m++) graphs_destroy(im.graphs[i][m]);
+    for (int i = 0; i < IMAGE_FORM_ROWS; i++) if (ImageForm::at(i).search) for (int m = 0; m < 2; m++) graphs_destroy(im.graphs[i][m]);
     image_buffers_free(image_group(c, IMG_ARCHIVE), st);
     im.ar_L = 0; im.ar_valid = false;
 }
@@ -87,6 +89,8 @@ void images_drop(srukf_map_scope* c, hipStream_t st)
 // ransac: a frame with the 1-point RANSAC consensus in it (srukf_images_ransac) — two more launches between the association and what stands in
 // k_gain's place: c->Ut is still S^T DZ there, PxyR / h / Si / vis / X are the predicted frame's, and this frame's rows of z_seq / m_seq are written: what
 // k_ransac_votes reads.  The pick launch rewrites the m_seq row to the consensus set, which the update then takes for its matches; images_ransac_ensure has run
+// rescue (only with ransac): a frame with the rescue gate behind its tail (srukf_images_rescue_gate) — two more launches on the posterior, in
+// front of the archive search: they read X, S, the frame's row of z_seq and of the consensus record and write the gate's own record; images_rescue_ensure has run
 // snap: a frame that keeps the state it starts from while no stop of the block is on record (srukf_images_snapshots) — k_image_snapshot in front
 // of everything else: it reads X, S, the matchPatch array, the policy state and fs->frame as the frame before left them; images_snapshot_ensure has run
 static void replay_one_image_frame(srukf_ctx* c, int mode, ImageForm form)
@@ -121,6 +125,11 @@ static void replay_one_image_frame(srukf_ctx* c, int mode, ImageForm form)
     if (mode == SRUKF_UPDATE_JOINT) seq_joint_launches(c, nullptr, nullptr);
     else seq_gain_only(c, nullptr, nullptr, FORM_PLAIN);
     seq_refactor(c, refactor_frame_tail(c), FORM_PLAIN);
+    if (form.ransac && form.rescue) {
+        ProfScope ps(c, KC_MISC, 0, 16.0 * d.np);
+        launch_rescue_gate_staged(c->stream, d, c->w, c->p, StagedRescue{ im.frames, c->z_seq, c->fs, im.rq_args, im.rs_flags, im.rs_sum,
+                                  RescueRow{ im.rq_flags, im.rq_h2, im.rq_Si2, im.rq_chi2 }, im.rq_sum, RescueScratch{ im.rq_vis, im.rq_PxyR } }, c->X, c->S);
+    }
     if (form.search) seq_archive_search(c);
 }
 
@@ -148,6 +157,13 @@ void images_restore(srukf_ctx* c, int slot, int stop)
         hipMemsetAsync(im.rs_rvotes + r0 * N, 0, sizeof(int) * rows * N, c->stream);
         hipMemsetAsync(im.rs_dist + r0 * N, 0, sizeof(double) * rows * N, c->stream);
         hipMemsetAsync(im.rs_sum + r0, 0, sizeof(RansacSummary) * rows, c->stream);
+    }
+    if (im.rq_flags && rows) {                                 // the rescue gate's record goes with it
+        hipMemsetAsync(im.rq_flags + r0 * N, 0, sizeof(int) * rows * N, c->stream);
+        hipMemsetAsync(im.rq_h2 + r0 * 2 * N, 0, sizeof(double) * rows * 2 * N, c->stream);
+        hipMemsetAsync(im.rq_Si2 + r0 * 4 * N, 0, sizeof(double) * rows * 4 * N, c->stream);
+        hipMemsetAsync(im.rq_chi2 + r0 * N, 0, sizeof(double) * rows * N, c->stream);
+        hipMemsetAsync(im.rq_sum + r0, 0, sizeof(RescueSummary) * rows, c->stream);
     }
     if (im.dp_rec && rows) {                                   // the display record: the views of frames that do not stand are no views
         hipMemsetAsync(im.dp_rec + r0 * image_display_row(N).doubles, 0, sizeof(double) * rows * image_display_row(N).doubles, c->stream);
@@ -197,7 +213,7 @@ static int images_checked_ensure(srukf_ctx* c, const char* who)
     ImageReplay& im = c->img;
     int rc = match_ensure(c, who); if (rc) return rc;
     if (im.chk_scores != c->match_scores) {
-        for (int i = 0; i < IMAGE_FORMS; i++) if (ImageForm::at(i).checked && (im.graphs[i][0].one_exec || im.graphs[i][1].one_exec)) { HIPCHK(c, hipStreamSynchronize(c->stream)); drop_graphs(c); break; }
+        for (int i = 0; i < IMAGE_FORM_ROWS; i++) if (ImageForm::at(i).checked && (im.graphs[i][0].one_exec || im.graphs[i][1].one_exec)) { HIPCHK(c, hipStreamSynchronize(c->stream)); drop_graphs(c); break; }
         im.chk_scores = c->match_scores;
     }
     if (im.corr2_seq) return SRUKF_OK;
@@ -232,6 +248,15 @@ static int images_ransac_ensure(srukf_ctx* c, const char* who)
     ImageReplay& im = c->img;
     if (im.rs_D) return SRUKF_OK;
     return image_buffers_alloc(c, image_group(c, IMG_RANSAC), who);
+}
+
+// what the rescue gate behind such frames needs, allocated in front of the first run with both switches on, outside any capture: the record
+// (zeroed), the scratch of the launch and the threshold's place on the device
+static int images_rescue_ensure(srukf_ctx* c, const char* who)
+{
+    ImageReplay& im = c->img;
+    if (im.rq_flags) return SRUKF_OK;
+    return image_buffers_alloc(c, image_group(c, IMG_RESCUE), who);
 }
 
 // what the snapshot launch in front of image frames needs, allocated in front of the first run with the switch on, outside any capture: the
@@ -298,7 +323,7 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
     c->joint_bad_host = false;
     HIPCHK(c, hipSetDevice(c->device));
     if (mode == SRUKF_UPDATE_JOINT) { const int rcj = joint_ensure(c, who); if (rcj) return rcj; }      // (before any capture begins)
-    const ImageForm form{ chk != nullptr, c->img_search && c->archive.L > 0, c->img_ransac, c->img_snap };
+    const ImageForm form{ chk != nullptr, c->img_search && c->archive.L > 0, c->img_ransac, c->img_snap, c->img_ransac && c->img_rescue };
     if (form.checked) {
         const int rce = images_checked_ensure(c, who); if (rce) return rce;                           // (idem)
         srukf_launch_set_match_args(c->stream, im.match_args, *chk);      // in stream order: behind the frames of an earlier run of the block, in front of this run's
@@ -334,11 +359,18 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
         launch_set_ransac_args(c->stream, im.rs_args, RansacArgs{ c->img_ransac_thr });      // in stream order, as the checked run's parameters
         im.rs_valid = true;
     }
+    // the rescue gate behind every such frame (srukf_images_rescue_gate): captured frames of their own; chi2 in stream order, so that changing it needs no recapture
+    if (form.rescue) {
+        const int rcq = images_rescue_ensure(c, who); if (rcq) return rcq;                            // (idem)
+        launch_set_rescue_args(c->stream, im.rq_args, RescueArgs{ c->img_rescue_chi2 });
+        im.rq_valid = true;
+    }
     // the state in front of every frame, kept while no stop is on record (srukf_images_snapshots): captured frames of their own.  The guard's parameters go to the
     // device in stream order, as the checked run's; a run that begins a block also closes both slots and opens the latch
     if (form.snap) {
         const int rcs = images_snapshot_ensure(c, who); if (rcs) return rcs;                          // (idem)
-        launch_set_snapshot_args(c->stream, im.sn_args, SnapshotArgs{ im.pending ? im.blk_first : first, policy ? im.pol_sum : nullptr, form.ransac ? im.rs_sum : nullptr, im.pol_state },
+        launch_set_snapshot_args(c->stream, im.sn_args, SnapshotArgs{ im.pending ? im.blk_first : first, policy ? im.pol_sum : nullptr, form.ransac ? im.rs_sum : nullptr, im.pol_state,
+                                               form.rescue ? im.rq_sum : nullptr },
                                  im.sn_ctl, im.pending ? 0 : 1);
     }
     // the block as srukf_images_resume needs it: resumable while every run of it has the switch on and begins where the one before ended
@@ -550,6 +582,47 @@ int srukf_get_image_ransac(srukf_ctx* c, int first, int count, int* flags, int* 
             if (n_active) n_active[q] = sm[q].n_active;
             if (n_low) n_low[q] = sm[q].n_low;
             if (first_outlier && *first_outlier < 0 && sm[q].outlier) *first_outlier = first + (int)q;
+        }
+    }
+    return SRUKF_OK;
+}
+
+// ---- the rescue gate behind the frames that hold the consensus (the kernels: srukf_rescue.hip) ----
+// The switch: on the handle, like srukf_images_ransac.  Touches no device: chi2 reaches it in stream order in front of the next image run (run_images_issue).  It takes
+// effect only in frames whose consensus runs: with srukf_images_ransac off a run issues the plain frames
+int srukf_images_rescue_gate(srukf_ctx* c, int on, double chi2)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    if (on && (!std::isfinite(chi2) || chi2 <= 0.0)) { c->err = "images_rescue_gate: chi2 must be finite and positive"; return SRUKF_ERR_BAD_ARG; }
+    if (c->async_pending) { c->err = "images_rescue_gate: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
+    c->img_rescue = on != 0;
+    if (on) c->img_rescue_chi2 = chi2;
+    return SRUKF_OK;
+}
+
+// rows [first, first + count) of the gate's record, after waiting for the stream like srukf_get_image_matches; the lowest frame of the range that would rescue a match
+int srukf_get_image_rescue(srukf_ctx* c, int first, int count, int* flags, double* h2, double* Si2, double* chi2, int* n_cand, int* n_high, int* first_rescue)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_image_rescue: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (!im.rq_flags || !im.rq_valid) { c->err = "get_image_rescue: no record of a run with the rescue gate in it (srukf_images_ransac and srukf_images_rescue_gate)"; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > im.frames) { c->err = "get_image_rescue: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    if (flags) HIPCHK(c, hipMemcpy(flags, im.rq_flags + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
+    if (h2) HIPCHK(c, hipMemcpy(h2, im.rq_h2 + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
+    if (Si2) HIPCHK(c, hipMemcpy(Si2, im.rq_Si2 + a * 4 * N, sizeof(double) * m * 4 * N, hipMemcpyDeviceToHost));
+    if (chi2) HIPCHK(c, hipMemcpy(chi2, im.rq_chi2 + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
+    if (n_cand || n_high || first_rescue) {
+        std::vector<RescueSummary> sm(m);
+        HIPCHK(c, hipMemcpy(sm.data(), im.rq_sum + a, sizeof(RescueSummary) * m, hipMemcpyDeviceToHost));
+        if (first_rescue) *first_rescue = -1;
+        for (size_t q = 0; q < m; q++) {
+            if (n_cand) n_cand[q] = sm[q].n_cand;
+            if (n_high) n_high[q] = sm[q].n_high;
+            if (first_rescue && *first_rescue < 0 && sm[q].n_high > 0) *first_rescue = first + (int)q;
         }
     }
     return SRUKF_OK;

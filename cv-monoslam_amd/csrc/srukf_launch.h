@@ -250,6 +250,28 @@ struct StagedRansac {
 void launch_ransac_staged(hipStream_t st, KDims d, KWeights w, srukf_params p, StagedRansac a, const double* X, const double* Ut, const double* PxyR, const double* h,
                           const double* Si, const int* vis);
 void launch_set_ransac_args(hipStream_t st, RansacArgs* dst, RansacArgs v);
+// ---- srukf_rescue.hip (the rescue gate; C++ linkage) ----
+// k_rescue_gate (step-wise) / k_rescue_gate_staged (behind the tail of a frame of an image run): one body, N workgroups of 256.  Landmark k is a candidate when its
+// frame has any (n_active >= 2, 0 < n_low < n_active) and it is in A and no low-innovation inlier; its workgroup forms h', Si', visible' of
+// srukf_repredict_measurement for the posterior (X, S) and the chi-square test of dataAssociation (1977); every other workgroup zeroes its entry.  RescueRow: one
+// frame's row of the record (flags: bit 0 candidate, bit 1 rescued; h2 [2N]; Si2 [4N]; chi2 [N]: y0^2 + y1^2, 0 where it was not formed).  RescueScratch: what
+// meas_final_tail stores besides (vis [N], PxyR [5 mp]).  StagedRescue: the staged rows, the consensus record the candidates come from, the frame counter (the tail
+// has advanced it: the frame is fs->frame - 1), the threshold on the device (args: written in stream order, launch_set_rescue_args) and the record, rec_sum
+// [frames] written by k_rescue_sum_staged (one workgroup behind the gate: integer counts of the row)
+struct RescueArgs { double chi2; };
+struct RescueSummary { int n_cand, n_high; };
+struct RescueRow { int* flags; double* h2; double* Si2; double* chi2; };
+struct RescueScratch { int* vis; double* PxyR; };
+struct StagedRescue {
+    int frames; const double* z_seq; const FrameScalars* fs; const RescueArgs* args;
+    const int* rs_flags; const RansacSummary* rs_sum;
+    RescueRow rec; RescueSummary* rec_sum; RescueScratch scr;
+};
+void launch_rescue_gate_staged(hipStream_t st, KDims d, KWeights w, srukf_params p, StagedRescue a, const double* X, const double* S);
+// frame_has: the caller's matched / inlier hold a frame with candidates (the rule above); cand[k] = frame_has && matched[k] && !inlier[k]
+void launch_rescue_gate(hipStream_t st, KDims d, KWeights w, srukf_params p, const double* X, const double* S, const double* z, const int* matched, const int* inlier,
+                        int frame_has, double chi2, RescueRow row, RescueScratch scr);
+void launch_set_rescue_args(hipStream_t st, RescueArgs* dst, RescueArgs v);
 void launch_set_policy_params(hipStream_t st, srukf_policy_params* dst, srukf_policy_params v);
 
 // ---- srukf_snapshot.hip (the state a block of image frames is resumed from; C++ linkage) ----
@@ -258,7 +280,8 @@ void launch_set_policy_params(hipStream_t st, srukf_policy_params* dst, srukf_po
 // stream order in front of every run (launch_set_snapshot_args; begin: the run begins a block — tags -1, latch open): the block's first frame, the summaries of the
 // policy and the consensus (null: this run has none) and the policy state (null: not allocated).  SnapshotCtl: the two tags and the latch.  ImageSnapshot: the live
 // arrays, their sizes in bytes and the two slots; the grid is sized by S (image_snapshot_blocks: SNAPSHOT_TRIPS 16-byte trips per lane, at most SNAPSHOT_MAX_BLOCKS)
-struct SnapshotArgs { int b0; const srukf_policy_summary* pol_sum; const RansacSummary* rs_sum; const srukf_policy_state* pol_state; };
+struct SnapshotArgs { int b0; const srukf_policy_summary* pol_sum; const RansacSummary* rs_sum; const srukf_policy_state* pol_state;
+                      const RescueSummary* rq_sum; };      // rq_sum (the rescue gate is on): the consensus term is "frame f - 1 rescued a match"
 struct SnapshotCtl { int tag[2]; int latch[2]; };
 struct ImageSnapshot {
     const double* X_src; const double* S_src; const unsigned char* tmpl_src;

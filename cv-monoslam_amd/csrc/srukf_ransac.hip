@@ -192,7 +192,7 @@ namespace srukf_impl {
 
 void ransac_scratch_free(RansacScratch& s, hipStream_t st)
 {
-    void* bufs[] = { s.Ut, s.D, s.F, s.votes, s.zin, s.res, s.X, s.S, s.odo, s.sigR, s.Cm, s.Z, s.DZ, s.h, s.PxyR, s.mpart, s.fs };
+    void* bufs[] = { s.Ut, s.D, s.F, s.votes, s.zin, s.res, s.X, s.S, s.odo, s.sigR, s.Cm, s.Z, s.DZ, s.h, s.PxyR, s.mpart, s.fs, s.rq_in, s.rq_out, s.rq_scr };
     for (void* b : bufs) if (b) srukf_dfree_on(b, st);
     s = RansacScratch{};
 }

@@ -927,7 +927,7 @@ void drop_graphs(srukf_map_scope* c)
 {
     for (int m = 0; m < 2; m++) {
         graphs_destroy(c->graphs[m]);
-        for (int i = 0; i < IMAGE_FORMS; i++) graphs_destroy(c->img.graphs[i][m]);
+        for (int i = 0; i < IMAGE_FORM_ROWS; i++) graphs_destroy(c->img.graphs[i][m]);
     }
 }
 

@@ -3,6 +3,7 @@
 // array and the policy state into slot (frame & 1) and tags the slot with the frame.  Nothing else in the frame reads what it writes.
 // The guard G(f) — "as far as the device knows, the host will still consume frame f - 1" — is a latch, double-buffered by frame parity:
 //   G(b0) = true,  G(f) = G(f - 1) && !outlier[f - 1] && !(f - 2 >= b0 && change[f - 2])
+// (while the rescue gate is on, DESIGN.md section 27: n_high[f - 1] > 0, "frame f - 1 rescued a match", in outlier[f - 1]'s place; written behind that frame's tail)
 // Every workgroup of frame f's launch forms G(f) from latch[(f - 1) & 1] (written by frame f - 1's launch), the consensus summary of frame f - 1 (written inside that
 // frame) and the policy summary of frame f - 2 (its launch sits in front of frame f - 1); thread 0 of workgroup 0 stores it in latch[f & 1] for frame f + 1's launch.
 // The only dependencies are launch boundaries on the stream: no polling, no atomics, and no word one workgroup of a launch writes and another of the same launch reads
@@ -29,7 +30,8 @@ __global__ __launch_bounds__(256) void k_image_snapshot(const FrameScalars* __re
     if (f > b0) {
         g = ctl->latch[(f - 1) & 1] != 0;
         const RansacSummary* rs = args->rs_sum;
-        if (rs && rs[f - 1].outlier) g = false;
+        const RescueSummary* rq = args->rq_sum;                 // the rescue gate is on: frame f - 1 stops the block only if it rescued a match
+        if (rs && (rq ? rq[f - 1].n_high > 0 : rs[f - 1].outlier != 0)) g = false;
         const srukf_policy_summary* ps = args->pol_sum;
         if (ps && f - 2 >= b0 && ps[f - 2].change) g = false;
     }

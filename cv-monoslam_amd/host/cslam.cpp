@@ -918,10 +918,20 @@ bool CSLAM::rescueHighInnovationInliers()
 {
     const int N = m_nMapFeatures;
     if (m_nLowInliers == 0 || m_nLowInliers == m_nMatches) return true;
+    const double CHI2INV_0_2 = 5.99146454710798;
+    if (rescueGateOnDevice) {
+        // the same rule on the device, from the posterior in place; the full prediction only when the second update will need it
+        std::vector<int> inl(N), fl(N);
+        int nh = 0;
+        for (int k = 0; k < N; k++) inl[k] = map[k].inliner_L ? 1 : 0;
+        if (!check(srukf_rescue_gate(ctx_, ransacZ_.data(), ransacM_.data(), inl.data(), CHI2INV_0_2, fl.data(), nullptr, nullptr, nullptr, &nh))) return false;
+        for (int k = 0; k < N; k++) if (fl[k] & SRUKF_RESCUE_RESCUED) { map[k].inliner_H = true; m_nHighInliers++; }
+        if (nh == 0) { m_nGateSkips++; return true; }
+        return check(srukf_repredict_measurement(ctx_, nullptr, nullptr, nullptr));
+    }
     std::vector<double> h(2 * N), Si(4 * N);
     std::vector<int> vis(N);
     if (!check(srukf_repredict_measurement(ctx_, h.data(), Si.data(), vis.data()))) return false;
-    const double CHI2INV_0_2 = 5.99146454710798;
     for (int k = 0; k < N; k++) {
         if (!ransacM_[k] || map[k].inliner_L || !vis[k]) continue;
         const double s00 = Si[4 * k], s01 = Si[4 * k + 1], s11 = Si[4 * k + 3];
@@ -1015,7 +1025,8 @@ void CSLAM::SLAM()
 // Up to F frames of SLAM() as ONE image block on the device: the association (dataAssociationOnDevice's) and the update run inside the block, the
 // map policy's verdict (updateFeaturesInformation's tests 2443-2459, the addFeatures trigger 556) behind every frame; the block stops at the first frame whose
 // verdict asks for a map change, and that change is made by the unchanged host code on that frame.  With isUseRANSAC the consensus runs inside every frame
-//  and the block also stops IN FRONT OF the first frame whose consensus dropped a match: its rescue step is SLAM()'s.  gray: F frames of image_h x image_w, frame f for
+//  and the block also stops IN FRONT OF the first frame whose consensus dropped a match: its rescue step is SLAM()'s — with rescueGateOnDevice
+//  in front of the first frame that would rescue one, and a frame whose dropped matches stay dropped is consumed.  gray: F frames of image_h x image_w, frame f for
 // m_frame.counter + f.  Returns the frames consumed, or 0 with nothing done where a block cannot stand for SLAM(): the caller then calls SLAM() for the frame.
 int CSLAM::SLAMBlock(const unsigned char* gray, int F)
 {
@@ -1043,6 +1054,9 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     const srukf_policy_params pp = { (double)DIST_2_BORDER, 0.01, 10, m_minNUM };
     if (!check(srukf_images_policy(ctx_, 1, &pp)) || !check(srukf_images_set_policy_state(ctx_, st.data()))) return 0;
     if (!check(srukf_images_ransac(ctx_, isUseRANSAC ? 1 : 0, THRESHOLD_RANSAC))) return 0;                     // the consensus inside every frame, or not
+    const bool gate = isUseRANSAC && rescueGateOnDevice;                                                        // the rescue gate behind every such frame
+    if ((gate || rescueSet_) && !check(srukf_images_rescue_gate(ctx_, gate ? 1 : 0, 5.99146454710798))) return 0;
+    rescueSet_ = gate;
     if ((resumeStoppedBlocks || snapshotsSet_) && !check(srukf_images_snapshots(ctx_, resumeStoppedBlocks ? 1 : 0))) return 0;      // the state at the stop, kept by the first run
     snapshotsSet_ = resumeStoppedBlocks;
     if ((blockDisplay || displaySet_) && !check(srukf_images_display(ctx_, blockDisplay ? 1 : 0))) return 0;                // the display view behind every frame
@@ -1061,7 +1075,8 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     // block's): back to the block's start and up to the stop
     int fc = -1, fo = -1, used = F;
     if (!check(srukf_get_image_policy(ctx_, 0, F, nullptr, nullptr, nullptr, &fc))) return 0;
-    if (isUseRANSAC && !check(srukf_get_image_ransac(ctx_, 0, F, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fo))) return 0;
+    if (gate) { if (!check(srukf_get_image_rescue(ctx_, 0, F, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fo))) return 0; }      // first_rescue: a frame that only dropped matches stands
+    else if (isUseRANSAC && !check(srukf_get_image_ransac(ctx_, 0, F, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fo))) return 0;
     if (fc >= 0) used = std::min(used, fc + 1);
     if (fo >= 0) used = std::min(used, fo);
     // resumeStoppedBlocks: the first run kept the state at the stop (srukf_images_resume); where no slot holds it, the rewind and the frames again

@@ -133,6 +133,13 @@ public:
     bool renderBlockOverlay(int f, unsigned char* out_bgr);
     bool resumeStoppedBlocks = false;
     int  m_nBlocksResumed = 0;
+    // rescueGateOnDevice (with isUseRANSAC): the test "would a dropped match be rescued?" runs on the device.  SLAMBlock switches
+    // srukf_images_rescue_gate on with CHI2INV_TABLE(0,2) and stops in front of the first frame that WOULD RESCUE a match (first_rescue) instead of the first that
+    // dropped one: a consumed frame with dropped, un-rescued matches is what SLAM() leaves for it (inliner_L from the consensus record, inliner_H false,
+    // m_nHighInliers 0).  rescueHighInnovationInliers asks srukf_rescue_gate first and calls srukf_repredict_measurement only when a match is rescued (the second
+    // update needs the full prediction); m_nGateSkips counts the repredictions saved.  Off: exactly the calls above
+    bool rescueGateOnDevice = false;
+    int  m_nGateSkips = 0;
     std::vector<double> m_blockPath;                           // the last SLAMBlock's RobotPath numbers, 8 per consumed frame: x, y, z, theta, P00, P01, P10, P11
     std::vector<int> m_blockLowInliers;                        // ... and with isUseRANSAC its m_nLowInliers per consumed frame
     void predictMotion();                                      // SLAM.cpp:1343-1466 (numeric tail 1430-1465)
@@ -338,6 +345,7 @@ private:
     bool check(int rc);
     srukf_ctx* ctx_ = nullptr;
     bool displaySet_ = false;            // srukf_images_display is on on the handle (SLAMBlock switches it off again when blockDisplay goes off)
+    bool rescueSet_ = false;             // srukf_images_rescue_gate is on on the handle (SLAMBlock switches it off again when rescueGateOnDevice or isUseRANSAC goes off)
     bool snapshotsSet_ = false;          // srukf_images_snapshots is on on the handle (SLAMBlock switches it off again when resumeStoppedBlocks goes off)
     bool mirrorsFresh_ = false;          // m_X_k / the robot block of m_P_k were fetched by this frame's display refresh
     int device_ = 0;

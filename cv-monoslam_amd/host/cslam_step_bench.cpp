@@ -29,6 +29,8 @@
 //              ransac=<threshold> (assoc_replay): the 1-point RANSAC consensus inside every frame (srukf_images_ransac; threshold in pixels, 8 is the
 //              reference's); the record's summaries are read after every block (srukf_get_image_ransac).  The bench runs no rescue: a block is not cut at
 //              first_outlier.  A restored block runs srukf_ransac_consensus step-wise.  Adds "ransac": {threshold, outlier_frames, low_inliers} to the output
+//              rescue=1 (assoc_replay with ransac=<threshold>): the rescue gate behind every such frame (srukf_images_rescue_gate with CHI2INV_TABLE(0,2));
+//              the record's summaries are read after every block (srukf_get_image_rescue) and "rescue_frames" (frames with n_high > 0) joins "ransac" in the output
 //              resume=1 (assoc_replay only): the blocks run with srukf_images_snapshots on: every frame begins with k_image_snapshot.  This measures
 //              the switch's price.  Adds "resume": 1 to the output
 //              stop=<k> with resume=0|1 (assoc_replay only; 0 < k < block): behind every timed block of `block` frames comes what a host does when the block has to
@@ -83,6 +85,7 @@ int main(int argc, char** argv)
     long long arc_hits = 0;
     int policy = 0; long long pol_change = 0, pol_deletes = 0, pol_adds = 0;      // policy= (assoc_replay)
     double ransac_thr = 0.0; long long rs_outlier = 0, rs_low = 0;      // ransac=<threshold> (assoc_replay)
+    int rescue = 0; long long rq_high = 0;                              // rescue=1 (assoc_replay with ransac=)
     int resume = -1, stop_k = 0; long long stop_blocks = 0;      // resume= / stop= (assoc_replay)
     int display = 0;      // display= (assoc_replay)
     std::vector<std::pair<std::string, int>> sets;
@@ -93,6 +96,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "hint=", 5)) hint = atoi(argv[a] + 5);
         else if (!strncmp(argv[a], "churn=", 6)) churn = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "ransac=", 7)) { ransac = atoi(argv[a] + 7); ransac_thr = atof(argv[a] + 7); }
+        else if (!strncmp(argv[a], "rescue=", 7)) rescue = atoi(argv[a] + 7);
         else if (!strncmp(argv[a], "ellipsoids=", 11)) ellipsoids = atoi(argv[a] + 11);
         else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "block=", 6)) block_frames = atoi(argv[a] + 6);
@@ -268,7 +272,7 @@ int main(int argc, char** argv)
 #undef CK
     } else for (int leg = 0; leg < legs; leg++) {
         const int snap = legs == 2 ? (leg == 0 ? !resume : resume) : (resume > 0 ? 1 : 0);
-        matches_dev = 0; ambiguous = refined = 0; pol_change = pol_deletes = pol_adds = 0; rs_outlier = rs_low = 0; stop_blocks = 0; flagged_blocks = 0;
+        matches_dev = 0; ambiguous = refined = 0; pol_change = pol_deletes = pol_adds = 0; rs_outlier = rs_low = 0; rq_high = 0; stop_blocks = 0; flagged_blocks = 0;
         srukf_params p;
         srukf_default_params(&p);
         p.a1 = a4[0]; p.a2 = a4[1]; p.a3 = a4[2]; p.a4 = a4[3];
@@ -364,9 +368,10 @@ int main(int argc, char** argv)
             }
             if (policy) CK(srukf_images_policy(c, 1, nullptr));
             if (ransac_thr > 0.0) CK(srukf_images_ransac(c, 1, ransac_thr));
+            if (ransac_thr > 0.0 && rescue) CK(srukf_images_rescue_gate(c, 1, 5.99146454710798));
             if (snap) CK(srukf_images_snapshots(c, 1));
             if (display) CK(srukf_images_display(c, 1));
-            std::vector<int> rlow(block_frames), ract(block_frames), rinl(N);
+            std::vector<int> rlow(block_frames), ract(block_frames), rinl(N), rhigh(block_frames);
             std::vector<srukf_policy_summary> prow(block_frames);
             std::vector<int> mrow((size_t)block_frames * N), frow(checked ? (size_t)block_frames * N : 0), fl(checked ? N : 0), hrow(block_frames), am(arcL);
             auto run = [&](int first, int end, bool timed) -> int {
@@ -422,6 +427,11 @@ int main(int argc, char** argv)
                             int fo = -1;
                             CK(srukf_get_image_ransac(c, b, cnt, nullptr, nullptr, nullptr, nullptr, ract.data(), rlow.data(), &fo));
                             for (int q = 0; q < cnt; q++) if (ract[q] >= 2) { rs_low += rlow[q]; rs_outlier += rlow[q] < ract[q] ? 1 : 0; }
+                            if (rescue) {                        // "which frame really needs it?": cnt summaries more
+                                int fr = -1;
+                                CK(srukf_get_image_rescue(c, b, cnt, nullptr, nullptr, nullptr, nullptr, nullptr, rhigh.data(), &fr));
+                                for (int q = 0; q < cnt; q++) rq_high += rhigh[q] > 0 ? 1 : 0;
+                            }
                         }
                         if (arcL && !arc_step) {                 // "did anything come back?": cnt ints
                             CK(srukf_get_image_archive(c, b, cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, hrow.data()));
@@ -498,7 +508,10 @@ int main(int argc, char** argv)
     if (arcL) snprintf(arc_json, sizeof arc_json, "\"archive\": {\"records\": %d, \"half_cap\": %d, \"route\": \"%s\", \"matched_records\": %lld}, ", arcL, apar.half_cap,
                        arc_step ? "srukf_archive_search after every block" : "srukf_images_search_archive", arc_hits);
     if (policy) snprintf(pol_json, sizeof pol_json, "\"policy\": {\"change_frames\": %lld, \"deletes\": %lld, \"need_add_frames\": %lld}, ", pol_change, pol_deletes, pol_adds);
-    if (areplay && ransac_thr > 0.0) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"ransac\": {\"threshold\": %.6g, \"outlier_frames\": %lld, \"low_inliers\": %lld}, ",
+    if (areplay && ransac_thr > 0.0 && rescue)
+        snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"ransac\": {\"threshold\": %.6g, \"outlier_frames\": %lld, \"low_inliers\": %lld, \"rescue_gate\": 1, \"rescue_frames\": %lld}, ",
+                 ransac_thr, rs_outlier, rs_low, rq_high);
+    else if (areplay && ransac_thr > 0.0) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"ransac\": {\"threshold\": %.6g, \"outlier_frames\": %lld, \"low_inliers\": %lld}, ",
                                               ransac_thr, rs_outlier, rs_low);
     if (areplay && resume >= 0) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"resume\": %d, ", resume);
     if (areplay && display) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"display\": 1, ");

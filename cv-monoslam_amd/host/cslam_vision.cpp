@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [display=<file>]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -31,6 +31,9 @@
 //   front of a frame whose consensus dropped a match, and SLAM() runs that frame with its rescue (a fallback).
 // resume=1 (with block=<F>): CSLAM::resumeStoppedBlocks on: a block that stops early takes the state at the stop from its first run instead of
 //   running the frames in front of the stop again; " resumed=<count>" is appended to the "blocks" line.  Without it the output is what it was.
+// rescue=1 (with ransac=<threshold>): CSLAM::rescueGateOnDevice on: the rescue's chi-square test runs on the device, a block ends only in front of
+//   a frame that would rescue a match, and SLAM() calls srukf_repredict_measurement only in such a frame.  With block=<F> " gate_skips=<count>" is appended to the
+//   "blocks" line (the repredictions SLAM() saved).  Every other line is what it is without it.
 // display=<file> (with block=<F>, block=1 too): CSLAM::blockDisplay and ellipsoidsOnDevice on; <file> gets, per frame and per landmark of the map
 //   behind that frame's tail, one line "frame ID" and xyz, cov, axis, sigma as %a (a NaN as "nan" whatever its sign): for the last consumed frame of a block (and
 //   every frame of block=1) from map[], for the frames in front of it from m_blockDisplay.  The same file through either route.  With overlay=<file> the overlay of
@@ -48,7 +51,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [display=<file>] [min_matches=<n>]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>] [min_matches=<n>]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -57,7 +60,7 @@ int main(int argc, char** argv)
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
     int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay, display;
-    bool unique = false, subpix = false, joint = false, resume = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
+    bool unique = false, subpix = false, joint = false, resume = false, rescue = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
     int minMatches = 0, block = 0, nBlocks = 0, nEarly = 0, nFull = 0, nFallback = 0;
     for (int a = 3; a < argc; a++)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
@@ -70,6 +73,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "joint=", 6)) joint = atoi(argv[a] + 6) != 0;
         else if (!strncmp(argv[a], "block=", 6)) block = atoi(argv[a] + 6);
         else if (!strncmp(argv[a], "resume=", 7)) resume = atoi(argv[a] + 7) != 0;
+        else if (!strncmp(argv[a], "rescue=", 7)) rescue = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "display=", 8)) display = argv[a] + 8;
         else if (!strncmp(argv[a], "min_matches=", 12)) minMatches = atoi(argv[a] + 12);
     if (warmup) {
@@ -94,6 +98,7 @@ int main(int argc, char** argv)
     SLAM.subpixelMatches = subpix;
     SLAM.jointUpdate = joint;
     SLAM.resumeStoppedBlocks = resume;
+    SLAM.rescueGateOnDevice = rescue;
     if (minMatches > 0) SLAM.m_minNUM = minMatches;
     const unsigned char* cur = nullptr;
     std::vector<unsigned char> bgr(colour ? (size_t)3 * W * H : 0);
@@ -186,8 +191,10 @@ int main(int argc, char** argv)
             if (!fo || fwrite(SLAM.m_srcImage.data(), 1, SLAM.m_srcImage.size(), fo) != SLAM.m_srcImage.size()) { perror(overlay.c_str()); return 1; }
             fclose(fo);
         }
-        if (resume) printf("blocks %d early %d full %d fallback %d resumed=%d\n", nBlocks, nEarly, nFull, nFallback, SLAM.m_nBlocksResumed);
-        else printf("blocks %d early %d full %d fallback %d\n", nBlocks, nEarly, nFull, nFallback);
+        printf("blocks %d early %d full %d fallback %d", nBlocks, nEarly, nFull, nFallback);
+        if (resume) printf(" resumed=%d", SLAM.m_nBlocksResumed);
+        if (rescue) printf(" gate_skips=%d", SLAM.m_nGateSkips);
+        printf("\n");
         printf("block_frames %d frames %d us_per_frame %.2f\n", block, steps, wall / steps * 1e6);
         return 0;
     }

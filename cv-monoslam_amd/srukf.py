@@ -38,6 +38,7 @@ EXPORTS = [
     "srukf_images_ransac", "srukf_get_image_ransac",
     "srukf_images_snapshots", "srukf_get_image_snapshots", "srukf_images_resume",
     "srukf_images_display", "srukf_get_image_display", "srukf_render_image_overlay",
+    "srukf_images_rescue_gate", "srukf_get_image_rescue", "srukf_rescue_gate",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -214,6 +215,10 @@ def load_library(path=None):
         L.srukf_images_display.argtypes = [C.c_void_p, C.c_int]
         L.srukf_get_image_display.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp]
         L.srukf_render_image_overlay.argtypes = [C.c_void_p, C.c_int, _bp]
+    if hasattr(L, "srukf_images_rescue_gate"):         # (idem: the rescue gate on the device)
+        L.srukf_images_rescue_gate.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        L.srukf_get_image_rescue.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip]
+        L.srukf_rescue_gate.argtypes = [C.c_void_p, _dp, _ip, _ip, C.c_double, _ip, _dp, _dp, _dp, _ip]
     L.srukf_set_storage.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_exclusive.argtypes = [C.c_void_p, C.c_int]
     L.srukf_set_rank_aware.argtypes = [C.c_void_p, C.c_int]
@@ -376,6 +381,20 @@ class Filter:
         h, Si, vis = np.empty(2 * self.N), np.empty((self.N, 2, 2)), np.empty(self.N, dtype=np.int32)
         self._chk(self._lib.srukf_repredict_measurement(self._h, _d(h), _d(Si), _i(vis)))
         return h, Si, vis
+
+    def rescue_gate(self, z, matched, inlier, chi2=5.99146454710798):
+        """The rescue gate after an update of this frame (srukf_rescue_gate): for the matches the consensus dropped (matched and not inlier,
+        in a frame with at least two matches of which some but not all are inliers), repredict_measurement's h, Si from the posterior and the chi-square test, in
+        one launch that changes neither state nor phase.  Returns dict of flags[N] (bit 0 candidate, bit 1 rescued), h2[2N], Si2[N, 2, 2], chi2[N], n_high."""
+        z, m, inl = _c(z), _c(matched, np.int32), _c(inlier, np.int32)
+        assert z.shape == (2 * self.N,) and m.shape == (self.N,) and inl.shape == (self.N,)
+        if isinstance(chi2, bool) or not isinstance(chi2, (int, float, np.integer, np.floating)):
+            raise TypeError("rescue_gate: chi2 must be a real number")
+        out = dict(flags=np.zeros(self.N, dtype=np.int32), h2=np.zeros(2 * self.N), Si2=np.zeros((self.N, 2, 2)), chi2=np.zeros(self.N))
+        nh = C.c_int(0)
+        self._chk(self._lib.srukf_rescue_gate(self._h, _d(z), _i(m), _i(inl), float(chi2), _i(out["flags"]), _d(out["h2"]), _d(out["Si2"]), _d(out["chi2"]), C.byref(nh)))
+        out["n_high"] = int(nh.value)
+        return out
 
     def set_new_landmarks(self, K_new):
         """m_nFilters: the last K_new landmarks of the map were just added (NEED_REORDER updates use it)."""
@@ -836,6 +855,31 @@ class Filter:
         self._chk(self._lib.srukf_get_image_ransac(self._h, int(first), int(count), _i(out["flags"]), _i(out["votes"]), _d(out["dist"]), _i(out["best"]),
                                                    _i(out["n_active"]), _i(out["n_low"]), C.byref(fo)))
         out["first_outlier"] = int(fo.value)
+        return out
+
+    # ---- the rescue gate behind the frames that hold the consensus (srukf_images_rescue_gate) ----
+    def images_rescue_gate(self, on, chi2=5.99146454710798):
+        """The switch of the rescue gate (srukf_images_rescue_gate): while on together with images_ransac, every frame of every later run_images* /
+        run_images_checked* is followed by the test whether a match its consensus dropped would be rescued (get_image_rescue has the record), and the snapshot
+        guard stops on a rescue instead of a dropped match.  chi2: finite and positive.  Not while a run is in flight (SRUKF_ERR_SEQUENCE)."""
+        if not isinstance(on, (bool, np.bool_)) and not (isinstance(on, (int, np.integer)) and on in (0, 1)):
+            raise TypeError("images_rescue_gate: on must be a bool")
+        if isinstance(chi2, bool) or not isinstance(chi2, (int, float, np.integer, np.floating)):
+            raise TypeError("images_rescue_gate: chi2 must be a real number")
+        self._chk(self._lib.srukf_images_rescue_gate(self._h, int(bool(on)), float(chi2)))
+
+    def get_image_rescue(self, first, count):
+        """What the rescue gate wrote for staged frames [first, first + count) (srukf_get_image_rescue): dict of flags[count, N] (bit 0: candidate, bit 1: rescued),
+        h2[count, 2N], Si2[count, N, 2, 2], chi2[count, N], n_cand[count], n_high[count] and first_rescue (the lowest frame that would rescue a match, or -1).
+        Rows of non-candidates and rows no such frame wrote are zero."""
+        self._image_run_args(first, count, UPDATE_BATCHED)
+        N = self.N
+        out = dict(flags=np.zeros((count, N), dtype=np.int32), h2=np.zeros((count, 2 * N)), Si2=np.zeros((count, N, 2, 2)), chi2=np.zeros((count, N)),
+                   n_cand=np.zeros(count, dtype=np.int32), n_high=np.zeros(count, dtype=np.int32))
+        fr = C.c_int(-1)
+        self._chk(self._lib.srukf_get_image_rescue(self._h, int(first), int(count), _i(out["flags"]), _d(out["h2"]), _d(out["Si2"]), _d(out["chi2"]),
+                                                   _i(out["n_cand"]), _i(out["n_high"]), C.byref(fr)))
+        out["first_rescue"] = int(fr.value)
         return out
 
     # ---- the state at a block's stop (srukf_images_snapshots / srukf_images_resume; DESIGN.md section 25) ----

@@ -664,6 +664,35 @@ int  srukf_images_snapshots(srukf_ctx* ctx, int on);
 int  srukf_get_image_snapshots(srukf_ctx* ctx, int frames[2]);
 int  srukf_images_resume(srukf_ctx* ctx, int keep);
 
+/* ---- the rescue gate on the device: would a match the consensus dropped be rescued? ----
+ * The rule, in all three calls.  A frame has candidates when n_active >= 2 and 0 < n_low < n_active (rescueHighInnovationInliers' condition); its candidates are
+ *   the landmarks in A (matched and visible) that are no low-innovation inliers.  For a candidate k the gate forms h', Si' and visible' as
+ *   srukf_repredict_measurement defines them for the posterior (X, S) of the frame's update; k is RESCUED when visible', Si'[0] != 0, Si'[3] != 0 and
+ *   y = Si'^-T (z - h') (forward substitution: y0 = v0 / Si'[0], y1 = (v1 - Si'[1] y0) / Si'[3]) has y0^2 + y1^2 < chi2, strictly (dataAssociation's gate, 1977;
+ *   CHI2INV_TABLE(0, 2) = 5.99146454710798).  flags: bit 0 (SRUKF_RESCUE_CANDIDATE), bit 1 (SRUKF_RESCUE_RESCUED); h2 [2N], Si2 [4N], chi2 [N] (y0^2 + y1^2; 0 where
+ *   the test was not formed) hold values for candidates and zeros for everybody else.  The gate decides, it updates nothing: the second update stays the host's.
+ * srukf_images_rescue_gate: a switch on the handle, like srukf_images_ransac: it survives map changes and srukf_reset (which drop the record with the staged
+ *   images).  With `on` != 0 chi2 must be finite and positive (SRUKF_ERR_BAD_ARG); not while a run is in flight (SRUKF_ERR_SEQUENCE).  The call touches no device.
+ *   It takes effect only in frames whose consensus runs: with srukf_images_ransac off it adds no launch.  While both are on, every frame of every later image run
+ *   has the gate behind its tail (two launches, in front of the archive search; captured frames of their own; chi2 in a device struct written in stream order in
+ *   front of each run, so changing it needs no recapture), the frames compute exactly what they compute without it, and the snapshot guard of
+ *   srukf_images_snapshots reads "frame f - 1 rescued a match" where it read "frame f - 1 dropped a match": behind a rescue at frame k the slot k & 1 holds the
+ *   state frame k started from and srukf_images_resume(k - first frame of the block) is legal; a frame that only dropped matches stops nothing.
+ * srukf_get_image_rescue: rows [first, first + count) of the gate's record, after waiting for the stream like srukf_get_image_matches.  n_cand / n_high [count]:
+ *   candidates and rescued candidates of each frame; *first_rescue: the lowest frame of the range with n_high > 0, or -1.  Any pointer may be NULL.  Rows no such
+ *   frame has written are zero, and so are the rows a flagged block's restore, srukf_images_rewind or srukf_images_resume zeroes in the consensus record.  SRUKF_ERR_SEQUENCE: no images staged, or no run with both
+ *   switches on since they were; SRUKF_ERR_DIM_MISMATCH: rows outside the staged stack.
+ * srukf_rescue_gate: step-wise, where srukf_repredict_measurement is legal (after a srukf_update, in the same frame; SRUKF_ERR_SEQUENCE otherwise).  z, matched:
+ *   what the consensus was given (matched: the set A, i.e. matched and visible); inlier: its low-innovation inliers.  One launch that reads the posterior in place
+ *   and a copy of the results; outputs are host pointers, any may be NULL.  It changes neither phase nor state and drops nothing the first update prepared for the
+ *   next frame: srukf_repredict_measurement (when *n_high > 0: the second update needs the full prediction) or the next srukf_predict_motion follow as before.
+ *   chi2 not finite and positive, or a NULL z / matched / inlier: SRUKF_ERR_BAD_ARG before any device is touched. */
+#define SRUKF_RESCUE_CANDIDATE 1
+#define SRUKF_RESCUE_RESCUED 2
+int  srukf_images_rescue_gate(srukf_ctx* ctx, int on, double chi2);
+int  srukf_get_image_rescue(srukf_ctx* ctx, int first, int count, int* flags, double* h2, double* Si2, double* chi2, int* n_cand, int* n_high, int* first_rescue);
+int  srukf_rescue_gate(srukf_ctx* ctx, const double* z, const int* matched, const int* inlier, double chi2, int* flags, double* h2, double* Si2, double* chi2_out, int* n_high);
+
 /* ---- the display view behind every frame of an image run, the overlay of any staged frame ----
  * srukf_images_display: a switch on the handle, like srukf_images_snapshots: it survives map changes and srukf_reset (which drop the record with the staged
  *   images); srukf_destroy ends it.  Not while a run is in flight or a block is pending (SRUKF_ERR_SEQUENCE).  The call touches no device.  While on, every frame
