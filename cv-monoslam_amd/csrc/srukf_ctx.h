@@ -92,67 +92,60 @@ struct ArchiveState {
     unsigned char *patch = nullptr, *tmpl = nullptr;
 };
 
-// image runs of the staged replay (srukf_stage_images / srukf_run_images*): the staged gray frames [frames][image_h][image_w], the per-frame
-// record the association leaves beside the staged z_seq / m_seq rows it overwrites (corr_seq [F][N], vis_seq [F][N], h_seq [F][2N]), the Cartesian points the warp
-// reads (xyz, 3N: not c->G — nothing has shown G to be free inside a replayed block), and the block's checkpoint: X, S, the matchPatch array and whether the null rows
-// were canonical.  pending: the frames srukf_synchronize waits for are image frames (a flagged block comes back to the checkpoint there).  Map-size scope, the staged
-// sequence's lifetime: images_drop.
+// { X, S, the matchPatch array, the policy state } of an image run, kept on the device: the block's checkpoint and the two snapshot slots are one of these each
+// (image_state_copy, srukf_images.hip, is the one place that knows the four sizes).  pol is only ever copied while the policy group exists
+struct ImageState { double *X = nullptr, *S = nullptr; unsigned char* tmpl = nullptr; srukf_policy_state* pol = nullptr; };
+
+// image runs of the staged replay (srukf_stage_images / srukf_run_images*; DESIGN.md sections 20 - 27).  Map-size scope, the staged sequence's lifetime: images_drop.
+// Every device buffer below is named once, in image_group (srukf_images.hip), with its size, whether it is zeroed, and for a per-frame record column its row width
+// and whether a restored block's rows stand: allocation (image_group_ensure, in front of the first run that needs the group, outside any capture), images_drop,
+// images_archive_drop, images_restore and the getters all read that table.  Here only what the table cannot say.
 // graphs: the captured frames (one and eight) of every form of an image frame and update mode, ONE table: graphs[ImageForm::index()][0 BATCHED / 1 JOINT].  A form
 // never replays a frame captured for another one (nor a frame of srukf_run_frames*, nor the other way round): the index is the guarantee.  drop_graphs walks the table.
-// The device buffers come in eight groups, each named once (image_group, srukf_images.hip): allocation, images_drop and images_archive_drop all go through those lists
 struct ImageReplay {
-    unsigned char *images = nullptr, *ck_tmpl = nullptr;
-    double *corr_seq = nullptr, *h_seq = nullptr, *xyz = nullptr, *ckS = nullptr, *ckX = nullptr;
+    // the staged gray frames [frames][image_h][image_w]; the record the association leaves beside the staged z_seq / m_seq rows it overwrites (corr_seq, vis_seq,
+    // h_seq); the Cartesian points the warp reads (xyz: not c->G — nothing has shown G to be free inside a replayed block)
+    unsigned char* images = nullptr;
+    double *corr_seq = nullptr, *h_seq = nullptr, *xyz = nullptr;
     int* vis_seq = nullptr;
     int frames = 0;
-    bool pending = false, ck_canon = false;
     ReplayGraphs graphs[32][2];
-    // Checked image runs (srukf_run_images_checked*), allocated by images_checked_ensure on the first one: the checked record corr2_seq [F][N],
-    // z2_seq [F][2N], flags_seq [F][N] (zero until a checked run writes a row) and the parameters the checked frames read (match_args, written in stream order in front
-    // of every checked run).  The captured checked frames hold the pointer of the filter's score buffer they were captured with, chk_scores.  checked: the block in
-    // flight holds a checked run (a flagged block then leaves no valid score map)
+    // The block: every image run since the last srukf_synchronize.  ck: the state it started from (ck.pol lives in the policy group), ck_canon: whether the null rows
+    // were canonical then.  pending / checked / searching: the frames srukf_synchronize waits for are image frames / with a checked / a searching run among them
+    // (images_block_end takes the three).  ck_clean: ck is that of a block srukf_synchronize ended clean and nothing has written X, S, a matchPatch or the policy
+    // state since (srukf_images_rewind / _resume; cleared by step_invalidate, which every state-writing entry passes, and by the few that do not pass it, each in place)
+    ImageState ck;
+    bool pending = false, ck_canon = false, checked = false, searching = false, ck_clean = false;
+    // Checked image runs: the checked record, and the parameters the checked frames read (written in stream order in front of every checked
+    // run).  The captured checked frames hold the pointer of the filter's score buffer they were captured with, chk_scores
     double *corr2_seq = nullptr, *z2_seq = nullptr; int* flags_seq = nullptr;
     MatchArgs* match_args = nullptr; const double* chk_scores = nullptr;
-    bool checked = false;
-    // Searching image runs (srukf_images_search_archive), allocated by images_archive_ensure in front of the first one: the per-frame record of
-    // the archive search (ar_rec: ImageArchiveRecord for frames x ar_L, zero until a searching run writes a row) and the parameters the searching frames read (ar_args,
-    // written in stream order in front of every searching run).  The captured searching frames hold the archive's pointers and L workgroups: images_archive_drop.
-    // ar_valid: a searching run has written the record and no flagged block has been restored since; searching: the block in flight holds a searching run
+    // Searching image runs: ar_rec, ONE allocation laid out column-major over frames (ImageArchiveRecord for frames x ar_L), and the
+    // parameters.  The captured searching frames hold the archive's pointers and L workgroups: images_archive_drop.  ar_valid: a searching run has written the
+    // record and no flagged block has been restored since
     double* ar_rec = nullptr; ArchiveArgs* ar_args = nullptr; int ar_L = 0;
-    bool ar_valid = false, searching = false;
-    // The map policy behind image frames (srukf_images_policy), allocated by images_policy_ensure (the first policy run, or
-    // srukf_images_set_policy_state): the per-landmark state (pol_state [N]) and its copy in the block's checkpoint (pol_ck [N]: saved and restored with X, S and the
-    // matchPatch array), the record (pol_verdict [frames][N], pol_sum [frames], zero until a policy run writes a row) and the parameters the launches read (pol_args,
-    // written in stream order in front of every policy run).  pol_valid: a policy run has written the record.  No captured frames of their own: run_images_issue.
-    // ck_clean: the checkpoint is that of a block srukf_synchronize ended clean and nothing has written X, S or a matchPatch since (srukf_images_rewind; cleared by
-    // images_rewind_void, which every state-writing entry passes through step_invalidate)
-    srukf_policy_state *pol_state = nullptr, *pol_ck = nullptr; int* pol_verdict = nullptr; srukf_policy_summary* pol_sum = nullptr; srukf_policy_params* pol_args = nullptr;
-    bool pol_valid = false, ck_clean = false;
-    // The 1-point RANSAC consensus inside image frames (srukf_images_ransac), allocated by images_ransac_ensure in front of the first run with
-    // the switch on: the scratch of the two launches (rs_D [N][N], rs_F [N][N] bytes, rs_votes [N]), the record (rs_flags / rs_rvotes / rs_dist [frames][N], rs_sum
-    // [frames], zero until such a frame writes a row, zeroed again by images_restore) and the threshold the launches read (rs_args, written in stream order in front
-    // of every such run).  rs_valid: such a run has written the record
+    bool ar_valid = false;
+    // The map policy behind image frames: the per-landmark state, the record and the parameters.  No captured frames of their own:
+    // run_images_issue.  pol_valid (and rs_valid, rq_valid below): a run with the switch on has written the record
+    srukf_policy_state* pol_state = nullptr; int* pol_verdict = nullptr; srukf_policy_summary* pol_sum = nullptr; srukf_policy_params* pol_args = nullptr;
+    bool pol_valid = false;
+    // The 1-point RANSAC consensus inside image frames: the scratch of the two launches (rs_D, rs_F, rs_votes), the record, the threshold
     double *rs_D = nullptr, *rs_dist = nullptr; unsigned char* rs_F = nullptr; int *rs_votes = nullptr, *rs_flags = nullptr, *rs_rvotes = nullptr;
     RansacSummary* rs_sum = nullptr; RansacArgs* rs_args = nullptr;
     bool rs_valid = false;
-    // The rescue gate behind the tail of such frames (srukf_images_rescue_gate), allocated by images_rescue_ensure in front of the first run with
-    // both switches on: the record (rq_flags [frames][N], rq_h2 [frames][2N], rq_Si2 [frames][4N], rq_chi2 [frames][N], rq_sum [frames], zero until such a frame writes
-    // a row, zeroed again by images_restore), what meas_final_tail stores besides (rq_vis [N], rq_PxyR [5 mp]) and the threshold the launches read (rq_args, written in
-    // stream order in front of every such run).  rq_valid: such a run has written the record
+    // The rescue gate behind the tail of such frames: the record, what meas_final_tail stores besides (rq_vis, rq_PxyR), the threshold
     int *rq_flags = nullptr, *rq_vis = nullptr; double *rq_h2 = nullptr, *rq_Si2 = nullptr, *rq_chi2 = nullptr, *rq_PxyR = nullptr;
     RescueSummary* rq_sum = nullptr; RescueArgs* rq_args = nullptr;
     bool rq_valid = false;
-    // The state a block is resumed from (srukf_images_snapshots / srukf_images_resume), allocated by images_snapshot_ensure in front of the first
-    // run with the switch on: two slots of { X, S, the matchPatch array, the policy state } (slot f & 1: the state frame f started from), the tags and the latch
-    // (sn_ctl), the guard's parameters (sn_args, written in stream order in front of every such run).  The block, as srukf_images_resume needs it: blk_first its first
-    // frame, blk_end the frame behind its last, blk_snap: every run of it had the switch on and began where the one before ended
-    double *sn_X[2] = { nullptr, nullptr }, *sn_S[2] = { nullptr, nullptr }; unsigned char* sn_tmpl[2] = { nullptr, nullptr }; srukf_policy_state* sn_pol[2] = { nullptr, nullptr };
+    // The state a block is resumed from: two slots (sn[f & 1]: the state frame f started from), the tags and the latch (sn_ctl), the guard's
+    // parameters.  The block, as srukf_images_resume needs it: blk_first its first frame, blk_end the frame behind its last, blk_snap: every run of it had the switch
+    // on and began where the one before ended
+    ImageState sn[2];
     SnapshotCtl* sn_ctl = nullptr; SnapshotArgs* sn_args = nullptr;
     int blk_first = 0, blk_end = 0; bool blk_snap = false;
-    // The display view behind image frames (srukf_images_display), allocated by images_display_ensure in front of the first run with the switch
-    // on: the record, one row of ImageDisplayRow(N).doubles doubles per staged frame (dp_rec) and one of N ints (dp_rot), zero until such a frame writes a row, zeroed
-    // again by images_restore.  dp_rows [frames]: the host's mark per row — a run with the switch on has issued the row's launches and no restore has zeroed it since
-    // (what srukf_render_image_overlay asks: rot cannot tell, 0 rotations is a legal value)
+    // The display view behind image frames: one row of ImageDisplayRow per staged frame (dp_rec) and one of rotation counts (dp_rot).
+    // dp_rows [frames]: the host's mark per row — a run with the switch on has issued the row's launches and no restore has zeroed it since (what
+    // srukf_render_image_overlay asks: rot cannot tell, 0 rotations is a legal value)
     double* dp_rec = nullptr; int* dp_rot = nullptr;
     std::vector<unsigned char> dp_rows;
 };
@@ -590,7 +583,9 @@ int replay_epilogue(srukf_ctx* c);                     // behind what a run issu
 int with_device_traj(srukf_ctx* c, int count, double* traj_host, const std::function<int(double*)>& run);
 void images_archive_drop(srukf_map_scope* c, hipStream_t st);      // the searching image runs' record, parameters and captured frames go (the archive changes; the caller has synchronised the stream)
 void images_drop(srukf_map_scope* c, hipStream_t st);      // the staged images, their record, checkpoint and captured frames go (the caller has synchronised the stream)
-void images_restore(srukf_ctx* c, int slot = -1, int stop = 0);      // srukf_synchronize: a flagged block of image frames comes back to its checkpoint (slot >= 0: srukf_images_resume)
+// srukf_synchronize, behind the frames it waited for: the flags of the block in flight go; read: the frame scalars came back; flagged: they hold a flag — a block of
+// image frames then comes back to its checkpoint and leaves no score map and no search record; a block that ended clean can be rewound or resumed
+void images_block_end(srukf_ctx* c, bool read, bool flagged);
 
 // ---- split form of the persistent factorisation (srukf_split.hip) ----
 bool split_form(const srukf_ctx* c, const GmwPlan& gp, bool ignore_starve = false);

@@ -1,45 +1,68 @@
-// srukf_images.hip — image runs of the staged replay (DESIGN.md sections 20 - 26): the staged gray frames and the frames that associate on the device
-// (srukf_stage_images / srukf_run_images*), with the checked association (srukf_run_images_checked*), the archive search (srukf_images_search_archive), the map
-// policy's verdict (srukf_images_policy), the 1-point RANSAC consensus (srukf_images_ransac), its rescue gate (srukf_images_rescue_gate; section 27) and the display view (srukf_images_display; section 26, with the overlay
-// of any staged frame, srukf_render_image_overlay) as options of a run, and the getters of their records.  No kernel:
-// the launch sequences, the graph cache and srukf_synchronize are srukf_replay.hip's; what the two files share is declared once in srukf_ctx.h.
-// A further per-frame option is: one bit of ImageForm, one group of image_group, one branch of replay_one_image_frame
+// srukf_images.hip — image runs of the staged replay (DESIGN.md sections 20 - 27): the staged gray frames and the frames that associate on the device
+// (srukf_stage_images / srukf_run_images*), their per-frame options — the checked association (srukf_run_images_checked*), the archive search
+// (srukf_images_search_archive), the map policy's verdict (srukf_images_policy), the 1-point RANSAC consensus (srukf_images_ransac), its rescue gate
+// (srukf_images_rescue_gate), the snapshots (srukf_images_snapshots / _resume) and the display view (srukf_images_display, with the overlay of any staged frame,
+// srukf_render_image_overlay) — and the getters of their records.  No kernel: the launch sequences, the graph cache and srukf_synchronize are srukf_replay.hip's;
+// what the two files share is declared once in srukf_ctx.h.
+// A further per-frame option is: its switch on the handle and its members of ImageReplay (srukf_ctx.h); one group of image_group, each record column with its row
+// and whether a restored block's rows stand; in run_images_issue one image_group_ensure and the parameters' launch; a captured launch: one bit of ImageForm and one
+// branch of replay_one_image_frame, an eager one behind each frame: one issue_image_* at the three issue sites; a getter built from image_getter_front and
+// image_rows_get.  Allocation, freeing, images_restore and the row arithmetic need no line
 
 #include "srukf_ctx.h"
 using namespace srukf_impl;
 
 namespace srukf_impl {
 
-// Every device buffer of the image runs, by group, named ONCE: { address of the pointer, bytes, zeroed when allocated }.  image_buffers_alloc allocates a group,
-// images_drop and images_archive_drop free through the same lists: a buffer added HERE is freed without anyone remembering to list it.  The sizes are the allocation's
-// (image_bytes: of one staged frame, L: the archive's; whoever only frees passes neither).  Zeroed: the records (rows no run has written read as zero) and the
-// consensus scratch; not the parameter blocks (written in stream order in front of every run that reads them), the images, xyz and the checkpoint copies
-enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_SNAPSHOT, IMG_DISPLAY, IMG_RESCUE, IMG_GROUPS };
-struct ImageBuf { void** p; size_t bytes; bool zero; };
+// Every device buffer of the image runs, by group, named ONCE.  buf: { address of the pointer, bytes, zeroed when allocated }.  col: a per-frame record column —
+// frames rows of `row` bytes, zeroed (rows no run has written read as zero); THE place a column's row width is written: allocation, images_restore and the getters
+// take it from here (image_col).  block: the rows a restored block wrote do not stand (images_restore zeroes them); the association's and the checked record keep
+// them.  The archive record is the one exception: a single allocation laid out column-major over frames (ImageArchiveRecord, srukf_launch.h), invalidated whole
+// (ar_valid) — srukf_get_image_archive and seq_archive_search do its arithmetic.
+// image_buffers_alloc allocates a group, images_drop and images_archive_drop free through the same lists: a buffer added HERE is freed without anyone remembering
+// to list it.  The sizes are the allocation's (image_bytes: of one staged frame, L: the archive's; whoever only frees passes neither).  Not zeroed: the parameter
+// blocks (written in stream order in front of every run that reads them), the images, xyz and the copies of the state
+enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_SNAPSHOT, IMG_RESCUE, IMG_DISPLAY, IMG_GROUPS };
+struct ImageBuf { void** p; size_t bytes; bool zero; size_t row; bool block; };
+struct ImageStateBytes { size_t X, S, tmpl, pol; };
+static ImageStateBytes image_state_bytes(const KDims& d)
+{
+    const size_t np = d.np, N = d.N;
+    return { sizeof(double) * np, sizeof(double) * np * np, N * PT_TMPL_STRIDE, sizeof(srukf_policy_state) * N };
+}
 static std::vector<ImageBuf> image_group(srukf_map_scope* c, ImageGroup g, size_t image_bytes = 0, size_t L = 0)
 {
     ImageReplay& im = c->img;
-    const size_t N = c->d.N, np = c->d.np, mp = c->d.mp, f = (size_t)im.frames, D = sizeof(double), I = sizeof(int);
-    auto buf = [](auto** p, size_t bytes, bool zero = false) { return ImageBuf{ (void**)p, bytes, zero }; };
+    const size_t N = c->d.N, mp = c->d.mp, f = (size_t)im.frames, D = sizeof(double), I = sizeof(int);
+    const ImageStateBytes sb = image_state_bytes(c->d);
+    auto buf = [](auto** p, size_t bytes, bool zero = false) { return ImageBuf{ (void**)p, bytes, zero, 0, false }; };
+    auto col = [f](auto** p, size_t row, bool block) { return ImageBuf{ (void**)p, f * row, true, row, block }; };
     switch (g) {
-    case IMG_STAGED: return { buf(&im.images, f * image_bytes), buf(&im.corr_seq, D * f * N, true), buf(&im.vis_seq, I * f * N, true), buf(&im.h_seq, D * f * 2 * N, true),
-                              buf(&im.xyz, D * 3 * N), buf(&im.ck_tmpl, N * PT_TMPL_STRIDE), buf(&im.ckS, D * np * np), buf(&im.ckX, D * np) };
-    case IMG_CHECKED: return { buf(&im.corr2_seq, D * f * N, true), buf(&im.z2_seq, D * f * 2 * N, true), buf(&im.flags_seq, I * f * N, true), buf(&im.match_args, sizeof(MatchArgs)) };
+    case IMG_STAGED: return { buf(&im.images, f * image_bytes), col(&im.corr_seq, D * N, false), col(&im.vis_seq, I * N, false), col(&im.h_seq, D * 2 * N, false),
+                              buf(&im.xyz, D * 3 * N), buf(&im.ck.tmpl, sb.tmpl), buf(&im.ck.S, sb.S), buf(&im.ck.X, sb.X) };
+    case IMG_CHECKED: return { col(&im.corr2_seq, D * N, false), col(&im.z2_seq, D * 2 * N, false), col(&im.flags_seq, I * N, false), buf(&im.match_args, sizeof(MatchArgs)) };
     case IMG_ARCHIVE: return { buf(&im.ar_rec, D * image_archive_record(f, L).doubles, true), buf(&im.ar_args, sizeof(ArchiveArgs)) };
-    case IMG_POLICY: return { buf(&im.pol_state, sizeof(srukf_policy_state) * N, true), buf(&im.pol_ck, sizeof(srukf_policy_state) * N, true), buf(&im.pol_verdict, I * f * N, true),
-                              buf(&im.pol_sum, sizeof(srukf_policy_summary) * f, true), buf(&im.pol_args, sizeof(srukf_policy_params)) };
-    case IMG_RANSAC: return { buf(&im.rs_D, D * N * N, true), buf(&im.rs_F, (N * N + 7) / 8 * 8, true), buf(&im.rs_votes, I * N, true), buf(&im.rs_flags, I * f * N, true),
-                              buf(&im.rs_rvotes, I * f * N, true), buf(&im.rs_dist, D * f * N, true), buf(&im.rs_sum, sizeof(RansacSummary) * f, true), buf(&im.rs_args, sizeof(RansacArgs)) };
-    case IMG_SNAPSHOT: return { buf(&im.sn_S[0], D * np * np), buf(&im.sn_S[1], D * np * np), buf(&im.sn_X[0], D * np), buf(&im.sn_X[1], D * np),
-                                buf(&im.sn_tmpl[0], N * PT_TMPL_STRIDE), buf(&im.sn_tmpl[1], N * PT_TMPL_STRIDE),
-                                buf(&im.sn_pol[0], sizeof(srukf_policy_state) * N), buf(&im.sn_pol[1], sizeof(srukf_policy_state) * N),
-                                buf(&im.sn_ctl, sizeof(SnapshotCtl)), buf(&im.sn_args, sizeof(SnapshotArgs)) };
-    case IMG_DISPLAY: return { buf(&im.dp_rec, D * f * image_display_row(N).doubles, true), buf(&im.dp_rot, I * f * N, true) };
-    case IMG_RESCUE: return { buf(&im.rq_flags, I * f * N, true), buf(&im.rq_h2, D * f * 2 * N, true), buf(&im.rq_Si2, D * f * 4 * N, true), buf(&im.rq_chi2, D * f * N, true),
-                              buf(&im.rq_sum, sizeof(RescueSummary) * f, true), buf(&im.rq_vis, I * N, true), buf(&im.rq_PxyR, D * 5 * mp, true), buf(&im.rq_args, sizeof(RescueArgs)) };
+    case IMG_POLICY: return { buf(&im.pol_state, sb.pol, true), buf(&im.ck.pol, sb.pol, true), col(&im.pol_verdict, I * N, true),
+                              col(&im.pol_sum, sizeof(srukf_policy_summary), true), buf(&im.pol_args, sizeof(srukf_policy_params)) };
+    case IMG_RANSAC: return { buf(&im.rs_D, D * N * N, true), buf(&im.rs_F, (N * N + 7) / 8 * 8, true), buf(&im.rs_votes, I * N, true), col(&im.rs_flags, I * N, true),
+                              col(&im.rs_rvotes, I * N, true), col(&im.rs_dist, D * N, true), col(&im.rs_sum, sizeof(RansacSummary), true), buf(&im.rs_args, sizeof(RansacArgs)) };
+    case IMG_SNAPSHOT: return { buf(&im.sn[0].S, sb.S), buf(&im.sn[1].S, sb.S), buf(&im.sn[0].X, sb.X), buf(&im.sn[1].X, sb.X), buf(&im.sn[0].tmpl, sb.tmpl), buf(&im.sn[1].tmpl, sb.tmpl),
+                                buf(&im.sn[0].pol, sb.pol), buf(&im.sn[1].pol, sb.pol), buf(&im.sn_ctl, sizeof(SnapshotCtl)), buf(&im.sn_args, sizeof(SnapshotArgs)) };
+    case IMG_RESCUE: return { col(&im.rq_flags, I * N, true), col(&im.rq_h2, D * 2 * N, true), col(&im.rq_Si2, D * 4 * N, true), col(&im.rq_chi2, D * N, true),
+                              col(&im.rq_sum, sizeof(RescueSummary), true), buf(&im.rq_vis, I * N, true), buf(&im.rq_PxyR, D * 5 * mp, true), buf(&im.rq_args, sizeof(RescueArgs)) };
+    case IMG_DISPLAY: return { col(&im.dp_rec, D * image_display_row(N).doubles, true), col(&im.dp_rot, I * N, true) };
     default: return {};
     }
 }
+
+// the entry of record column *col in its group's list, and where a frame's row of it begins
+template <class T> static const ImageBuf& image_col(const std::vector<ImageBuf>& cols, T* const* col)
+{
+    for (const ImageBuf& b : cols) if ((const void*)b.p == (const void*)col && b.row) return b;
+    fprintf(stderr, "image_col: not a record column of this group\n");
+    abort();
+}
+template <class T> static T* image_row(const std::vector<ImageBuf>& cols, T* const* col, size_t frame) { return (T*)((char*)*col + frame * image_col(cols, col).row); }
 
 static void image_buffers_free(const std::vector<ImageBuf>& bufs, hipStream_t st)
 {
@@ -56,6 +79,14 @@ static int image_buffers_alloc(srukf_ctx* c, const std::vector<ImageBuf>& bufs, 
     (void)hipGetLastError();
     image_buffers_free(bufs, c->stream);
     c->err = std::string(who) + ": out of device memory"; return SRUKF_ERR_NOMEM;
+}
+
+// what an option needs beyond srukf_stage_images' buffers, allocated in front of the first run that needs it, never inside a capture (the captured frames hold the
+// pointers): a group is all there or not at all, so its first buffer answers for it
+static int image_group_ensure(srukf_ctx* c, ImageGroup g, const char* who, size_t L = 0)
+{
+    const std::vector<ImageBuf> bufs = image_group(c, g, 0, L);
+    return *bufs.front().p ? SRUKF_OK : image_buffers_alloc(c, bufs, who);
 }
 
 // the archive changes (srukf_archive_set): the searching frames were captured with its pointers and L workgroups, the record is sized by L.  The next searching run
@@ -76,6 +107,19 @@ void images_drop(srukf_map_scope* c, hipStream_t st)
     im = ImageReplay{};
 }
 
+// { X, S, the matchPatch array, the policy state } from one place to another in stream order (the matchPatches' pixels persist from frame to frame, so a block that
+// does not stand must not leave its own behind); the policy state only while the policy group exists.  The first error, every copy issued
+static ImageState image_state_live(srukf_ctx* c) { return ImageState{ c->X, c->S, c->app_tmpl, c->img.pol_state }; }
+static hipError_t image_state_copy(srukf_ctx* c, const ImageState& to, const ImageState& from)
+{
+    const ImageStateBytes sb = image_state_bytes(c->d);
+    const hipError_t e[4] = { hipMemcpyAsync(to.S, from.S, sb.S, hipMemcpyDeviceToDevice, c->stream), hipMemcpyAsync(to.X, from.X, sb.X, hipMemcpyDeviceToDevice, c->stream),
+                              hipMemcpyAsync(to.tmpl, from.tmpl, sb.tmpl, hipMemcpyDeviceToDevice, c->stream),
+                              c->img.pol_state ? hipMemcpyAsync(to.pol, from.pol, sb.pol, hipMemcpyDeviceToDevice, c->stream) : hipSuccess };
+    for (const hipError_t q : e) if (q != hipSuccess) return q;
+    return hipSuccess;
+}
+
 // A frame of an image run (srukf_run_images*): the plain frame form as in replay_one_frame_joint, whatever "fused_motion" and its neighbours say,
 // with the association between k_pxy and what stands in k_gain's place.  Behind seq_pxy(FORM_PLAIN) the device holds h, Si, visible and the predicted pose in X: what
 // k_warp_patch and the matching front read (srukf_associate finds the same behind srukf_predict_measurement).  k_associate_staged writes this frame's rows of z_seq /
@@ -88,20 +132,22 @@ void images_drop(srukf_map_scope* c, hipStream_t st)
 // writes the archive's own buffers and the search record, nothing the filter reads); images_archive_ensure has run
 // ransac: a frame with the 1-point RANSAC consensus in it (srukf_images_ransac) — two more launches between the association and what stands in
 // k_gain's place: c->Ut is still S^T DZ there, PxyR / h / Si / vis / X are the predicted frame's, and this frame's rows of z_seq / m_seq are written: what
-// k_ransac_votes reads.  The pick launch rewrites the m_seq row to the consensus set, which the update then takes for its matches; images_ransac_ensure has run
+// k_ransac_votes reads.  The pick launch rewrites the m_seq row to the consensus set, which the update then takes for its matches
 // rescue (only with ransac): a frame with the rescue gate behind its tail (srukf_images_rescue_gate) — two more launches on the posterior, in
-// front of the archive search: they read X, S, the frame's row of z_seq and of the consensus record and write the gate's own record; images_rescue_ensure has run
+// front of the archive search: they read X, S, the frame's row of z_seq and of the consensus record and write the gate's own record
 // snap: a frame that keeps the state it starts from while no stop of the block is on record (srukf_images_snapshots) — k_image_snapshot in front
-// of everything else: it reads X, S, the matchPatch array, the policy state and fs->frame as the frame before left them; images_snapshot_ensure has run
+// of everything else: it reads X, S, the matchPatch array, the policy state and fs->frame as the frame before left them
+// (every form's group is allocated: run_images_issue's image_group_ensure, never inside a capture)
 static void replay_one_image_frame(srukf_ctx* c, int mode, ImageForm form)
 {
     ImageReplay& im = c->img;
     const KDims& d = c->d;
     if (form.snap) {
-        const size_t np = d.np, N = d.N;
-        ProfScope ps(c, KC_MISC, 0, 16.0 * np * np);
-        launch_image_snapshot(c->stream, c->fs, im.sn_args, im.sn_ctl, ImageSnapshot{ c->X, c->S, c->app_tmpl, sizeof(double) * np, sizeof(double) * np * np, N * PT_TMPL_STRIDE,
-                              sizeof(srukf_policy_state) * N, { im.sn_X[0], im.sn_X[1] }, { im.sn_S[0], im.sn_S[1] }, { im.sn_tmpl[0], im.sn_tmpl[1] }, { im.sn_pol[0], im.sn_pol[1] } });
+        const ImageStateBytes sb = image_state_bytes(d);
+        const ImageState* sn = im.sn;
+        ProfScope ps(c, KC_MISC, 0, 2.0 * sb.S);
+        launch_image_snapshot(c->stream, c->fs, im.sn_args, im.sn_ctl, ImageSnapshot{ c->X, c->S, c->app_tmpl, sb.X, sb.S, sb.tmpl, sb.pol,
+                              { sn[0].X, sn[1].X }, { sn[0].S, sn[1].S }, { sn[0].tmpl, sn[1].tmpl }, { sn[0].pol, sn[1].pol } });
     }
     seq_predict_motion(c, nullptr);
     seq_predict_measurement(c, FORM_PLAIN);
@@ -133,47 +179,78 @@ static void replay_one_image_frame(srukf_ctx* c, int mode, ImageForm form)
     if (form.search) seq_archive_search(c);
 }
 
-// the state the block of image frames started from comes back: X, S and the matchPatch array (its pixels persist from frame to frame, so a flagged block must not
-// leave its own behind), as srukf_run_frames' checkpoint comes back.  Keeps c->err
+// ---- what the getters of the records are built from ----
+// The common front: rows [first, first + count) of the staged stack are asked for.  no_record: the getter refuses without its record, in these words (null: there
+// is one, or the getter reads an unallocated record as zeros); wait: the stream is waited for, as srukf_get_image_matches waits (flags of frames in flight are
+// still srukf_synchronize's to report)
+static int image_getter_front(srukf_ctx* c, const char* who, int first, int count, const char* no_record = nullptr, bool wait = true)
+{
+    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const std::string w = who;
+    if (!c->img.images) { c->err = w + ": no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (no_record) { c->err = w + ": " + no_record; return SRUKF_ERR_SEQUENCE; }
+    if (first + count > c->img.frames) { c->err = w + ": frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
+    if (!wait) return SRUKF_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SRUKF_OK;
+}
+
+// rows [first, first + count) of `row` bytes from src to the host, when the caller wants them; a column no run has allocated reads as zeros
+static int image_rows_copy(srukf_ctx* c, void* dst, const void* src, size_t row, int first, int count)
+{
+    if (!dst) return SRUKF_OK;
+    if (!src) { memset(dst, 0, (size_t)count * row); return SRUKF_OK; }
+    HIPCHK(c, hipMemcpy(dst, (const char*)src + (size_t)first * row, (size_t)count * row, hipMemcpyDeviceToHost));
+    return SRUKF_OK;
+}
+template <class T> static int image_rows_get(srukf_ctx* c, const std::vector<ImageBuf>& cols, T* const* col, int first, int count, T* dst)
+{
+    return image_rows_copy(c, dst, *col, image_col(cols, col).row, first, count);
+}
+
+// rows [first, first + count) of a summary column into sm; *first_hit (may be null): the lowest frame of the range whose summary satisfies hit, or -1
+template <class S, class Hit> static int image_summaries_get(srukf_ctx* c, const std::vector<ImageBuf>& cols, S* const* col, int first, int count, std::vector<S>& sm, int* first_hit, Hit hit)
+{
+    sm.resize((size_t)count);
+    const int rc = image_rows_get(c, cols, col, first, count, sm.data()); if (rc) return rc;
+    if (!first_hit) return SRUKF_OK;
+    *first_hit = -1;
+    for (int q = 0; q < count && *first_hit < 0; q++) if (hit(sm[(size_t)q])) *first_hit = first + q;
+    return SRUKF_OK;
+}
+
+// the state the block of image frames started from comes back (the checkpoint), as srukf_run_frames' checkpoint comes back, and every block-scoped record column is
+// zeroed from the block's first row on: what its frames wrote are no verdicts, consensus sets or views any more (DESIGN.md sections 23 - 27).  Keeps c->err
 // slot >= 0 (srukf_images_resume): snapshot slot `slot` in the checkpoint's place — the state frame `stop` of the stack started from; rows
-// >= stop of the policy, consensus and display records go, the rows in front of it stand, and the null rows are what the block's frames left (stop lies behind its first frame)
-void images_restore(srukf_ctx* c, int slot, int stop)
+// >= stop go, the rows in front of it stand, and the null rows are what the block's frames left (stop lies behind its first frame)
+static void images_restore(srukf_ctx* c, int slot = -1, int stop = 0)
 {
     ImageReplay& im = c->img;
-    const size_t np = c->d.np, N = (size_t)c->d.N;
     const std::string why = c->err;
     const bool ck = slot < 0;
     const size_t r0 = ck ? 0 : (size_t)stop, rows = (size_t)im.frames - r0;
-    hipMemcpyAsync(c->S, ck ? im.ckS : im.sn_S[slot], sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream);
-    hipMemcpyAsync(c->X, ck ? im.ckX : im.sn_X[slot], sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream);
-    hipMemcpyAsync(c->app_tmpl, ck ? im.ck_tmpl : im.sn_tmpl[slot], N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream);
-    if (im.pol_state) {                                        // the policy state comes back too; the rows the block's frames wrote are no verdicts any more: zero, as unwritten rows are
-        hipMemcpyAsync(im.pol_state, ck ? im.pol_ck : im.sn_pol[slot], sizeof(srukf_policy_state) * N, hipMemcpyDeviceToDevice, c->stream);
-        if (rows) hipMemsetAsync(im.pol_verdict + r0 * N, 0, sizeof(int) * rows * N, c->stream);
-        if (rows) hipMemsetAsync(im.pol_sum + r0, 0, sizeof(srukf_policy_summary) * rows, c->stream);
-    }
-    if (im.rs_flags && rows) {                                 // the consensus record: what the block's frames wrote does not stand either
-        hipMemsetAsync(im.rs_flags + r0 * N, 0, sizeof(int) * rows * N, c->stream);
-        hipMemsetAsync(im.rs_rvotes + r0 * N, 0, sizeof(int) * rows * N, c->stream);
-        hipMemsetAsync(im.rs_dist + r0 * N, 0, sizeof(double) * rows * N, c->stream);
-        hipMemsetAsync(im.rs_sum + r0, 0, sizeof(RansacSummary) * rows, c->stream);
-    }
-    if (im.rq_flags && rows) {                                 // the rescue gate's record goes with it
-        hipMemsetAsync(im.rq_flags + r0 * N, 0, sizeof(int) * rows * N, c->stream);
-        hipMemsetAsync(im.rq_h2 + r0 * 2 * N, 0, sizeof(double) * rows * 2 * N, c->stream);
-        hipMemsetAsync(im.rq_Si2 + r0 * 4 * N, 0, sizeof(double) * rows * 4 * N, c->stream);
-        hipMemsetAsync(im.rq_chi2 + r0 * N, 0, sizeof(double) * rows * N, c->stream);
-        hipMemsetAsync(im.rq_sum + r0, 0, sizeof(RescueSummary) * rows, c->stream);
-    }
-    if (im.dp_rec && rows) {                                   // the display record: the views of frames that do not stand are no views
-        hipMemsetAsync(im.dp_rec + r0 * image_display_row(N).doubles, 0, sizeof(double) * rows * image_display_row(N).doubles, c->stream);
-        hipMemsetAsync(im.dp_rot + r0 * N, 0, sizeof(int) * rows * N, c->stream);
-        std::fill(im.dp_rows.begin() + (std::ptrdiff_t)r0, im.dp_rows.end(), (unsigned char)0);
-    }
+    (void)image_state_copy(c, image_state_live(c), ck ? im.ck : im.sn[slot]);
+    for (int g = 0; g < IMG_GROUPS; g++)
+        for (const ImageBuf& b : image_group(c, (ImageGroup)g)) if (b.block && *b.p && rows) hipMemsetAsync((char*)*b.p + r0 * b.row, 0, rows * b.row, c->stream);
+    if (im.dp_rec) std::fill(im.dp_rows.begin() + (std::ptrdiff_t)r0, im.dp_rows.end(), (unsigned char)0);      // (the host's marks of the display rows)
     if (ck && c->null_canonical != im.ck_canon) { c->null_canonical = im.ck_canon; drop_graphs(c); }
     shadow_rebuild(c);
     hipStreamSynchronize(c->stream);
     c->err = why;
+}
+
+void images_block_end(srukf_ctx* c, bool read, bool flagged)
+{
+    ImageReplay& im = c->img;
+    const bool image_run = im.pending, checked_run = im.checked, search_run = im.searching;
+    im.pending = false; im.checked = false; im.searching = false;
+    if (!image_run || !read) return;
+    if (!flagged) { im.ck_clean = true; return; }                // the block ended clean: its checkpoint is what srukf_images_rewind puts back
+    images_restore(c);
+    c->joint_bad_host = false;
+    if (checked_run) c->match_valid = false;                     // a checked run among the frames: a flagged block leaves no valid score map ...
+    if (search_run) im.ar_valid = false;                         // ... a searching run: no valid search record
 }
 
 }  // namespace srukf_impl
@@ -205,9 +282,9 @@ int srukf_stage_images(srukf_ctx* c, int F, const unsigned char* gray)
     return SRUKF_OK;
 }
 
-// what a checked image run needs beyond srukf_stage_images' buffers, allocated on the first one and outside any capture: the checked record (zeroed), the
-// parameters' place on the device, and the filter's score buffer if no srukf_associate_checked has made it.  Captured checked frames hold the score buffer's
-// pointer: they are dropped when it is not the one they were captured with (match_drop has run in between)
+// The three options whose first run needs more than their group (image_group_ensure):
+// a checked image run — the filter's score buffer if no srukf_associate_checked has made it.  Captured checked frames hold the score buffer's pointer: they are
+// dropped when it is not the one they were captured with (match_drop has run in between)
 static int images_checked_ensure(srukf_ctx* c, const char* who)
 {
     ImageReplay& im = c->img;
@@ -216,68 +293,27 @@ static int images_checked_ensure(srukf_ctx* c, const char* who)
         for (int i = 0; i < IMAGE_FORM_ROWS; i++) if (ImageForm::at(i).checked && (im.graphs[i][0].one_exec || im.graphs[i][1].one_exec)) { HIPCHK(c, hipStreamSynchronize(c->stream)); drop_graphs(c); break; }
         im.chk_scores = c->match_scores;
     }
-    if (im.corr2_seq) return SRUKF_OK;
-    return image_buffers_alloc(c, image_group(c, IMG_CHECKED), who);
+    return image_group_ensure(c, IMG_CHECKED, who);
 }
 
-// what a searching image run needs beyond srukf_stage_images' buffers, allocated in front of the first one and outside any capture: the search record for the
-// archive's L (zeroed) and the parameters' place on the device.  srukf_archive_set drops both with the captured searching frames (images_archive_drop)
+// a searching image run — the record is sized by the archive's L, kept in ar_L.  srukf_archive_set drops both with the captured searching frames (images_archive_drop)
 static int images_archive_ensure(srukf_ctx* c, const char* who)
 {
     ImageReplay& im = c->img;
-    if (im.ar_rec) return SRUKF_OK;
-    const int L = c->archive.L;
-    const int rc = image_buffers_alloc(c, image_group(c, IMG_ARCHIVE, 0, (size_t)L), who); if (rc) return rc;
-    im.ar_L = L;
-    return SRUKF_OK;
+    const bool had = im.ar_rec != nullptr;
+    const int rc = image_group_ensure(c, IMG_ARCHIVE, who, (size_t)c->archive.L);
+    if (rc == SRUKF_OK && !had) im.ar_L = c->archive.L;
+    return rc;
 }
 
-// what the map policy behind image frames needs beyond srukf_stage_images' buffers, allocated in front of the first policy run or by
-// srukf_images_set_policy_state, outside any capture: the per-landmark state and its checkpoint copy, the record and the parameters' place on the device, all zeroed
-static int images_policy_ensure(srukf_ctx* c, const char* who)
-{
-    ImageReplay& im = c->img;
-    if (im.pol_state) return SRUKF_OK;
-    return image_buffers_alloc(c, image_group(c, IMG_POLICY), who);
-}
-
-// what the consensus inside image frames needs beyond srukf_stage_images' buffers, allocated in front of the first run with the switch on,
-// outside any capture: the scratch of the two launches, the record (zeroed) and the threshold's place on the device
-static int images_ransac_ensure(srukf_ctx* c, const char* who)
-{
-    ImageReplay& im = c->img;
-    if (im.rs_D) return SRUKF_OK;
-    return image_buffers_alloc(c, image_group(c, IMG_RANSAC), who);
-}
-
-// what the rescue gate behind such frames needs, allocated in front of the first run with both switches on, outside any capture: the record
-// (zeroed), the scratch of the launch and the threshold's place on the device
-static int images_rescue_ensure(srukf_ctx* c, const char* who)
-{
-    ImageReplay& im = c->img;
-    if (im.rq_flags) return SRUKF_OK;
-    return image_buffers_alloc(c, image_group(c, IMG_RESCUE), who);
-}
-
-// what the snapshot launch in front of image frames needs, allocated in front of the first run with the switch on, outside any capture: the
-// two slots, the tags with the latch, and the guard's parameters' place on the device.  Nothing is zeroed: the parameter launch of the block's first run sets the
-// tags and the latch in stream order
-static int images_snapshot_ensure(srukf_ctx* c, const char* who)
-{
-    ImageReplay& im = c->img;
-    if (im.sn_ctl) return SRUKF_OK;
-    return image_buffers_alloc(c, image_group(c, IMG_SNAPSHOT), who);
-}
-
-// what the display view behind image frames needs beyond srukf_stage_images' buffers, allocated in front of the first run with the switch on,
-// outside any capture: the record (zeroed) and the host's marks of its rows
+// a run with the display view — the host's marks of the record's rows
 static int images_display_ensure(srukf_ctx* c, const char* who)
 {
     ImageReplay& im = c->img;
-    if (im.dp_rec) return SRUKF_OK;
-    const int rc = image_buffers_alloc(c, image_group(c, IMG_DISPLAY), who); if (rc) return rc;
-    im.dp_rows.assign((size_t)im.frames, 0);
-    return SRUKF_OK;
+    const bool had = im.dp_rec != nullptr;
+    const int rc = image_group_ensure(c, IMG_DISPLAY, who);
+    if (rc == SRUKF_OK && !had) im.dp_rows.assign((size_t)im.frames, 0);
+    return rc;
 }
 
 // the display view behind staged frame `frame` (srukf_images_display; updateFeaturesInformation -> refreshFeaturesDisplay, SLAM.cpp:2566-2575, behind every frame):
@@ -342,7 +378,7 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
     // followed by the policy launch
     const bool policy = c->img_policy;
     if (policy) {
-        const int rcp = images_policy_ensure(c, who); if (rcp) return rcp;                            // (idem)
+        const int rcp = image_group_ensure(c, IMG_POLICY, who); if (rcp) return rcp;      // (idem)
         launch_set_policy_params(c->stream, im.pol_args, c->img_policy_args);      // in stream order, as the checked run's parameters
         im.pol_valid = true;
     }
@@ -355,20 +391,20 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
     const bool single = policy || display;
     // the 1-point RANSAC consensus inside every frame (srukf_images_ransac): captured frames of their own
     if (form.ransac) {
-        const int rcr = images_ransac_ensure(c, who); if (rcr) return rcr;                            // (idem)
+        const int rcr = image_group_ensure(c, IMG_RANSAC, who); if (rcr) return rcr;      // (idem)
         launch_set_ransac_args(c->stream, im.rs_args, RansacArgs{ c->img_ransac_thr });      // in stream order, as the checked run's parameters
         im.rs_valid = true;
     }
     // the rescue gate behind every such frame (srukf_images_rescue_gate): captured frames of their own; chi2 in stream order, so that changing it needs no recapture
     if (form.rescue) {
-        const int rcq = images_rescue_ensure(c, who); if (rcq) return rcq;                            // (idem)
+        const int rcq = image_group_ensure(c, IMG_RESCUE, who); if (rcq) return rcq;      // (idem)
         launch_set_rescue_args(c->stream, im.rq_args, RescueArgs{ c->img_rescue_chi2 });
         im.rq_valid = true;
     }
     // the state in front of every frame, kept while no stop is on record (srukf_images_snapshots): captured frames of their own.  The guard's parameters go to the
     // device in stream order, as the checked run's; a run that begins a block also closes both slots and opens the latch
     if (form.snap) {
-        const int rcs = images_snapshot_ensure(c, who); if (rcs) return rcs;                          // (idem)
+        const int rcs = image_group_ensure(c, IMG_SNAPSHOT, who); if (rcs) return rcs;      // (idem)
         launch_set_snapshot_args(c->stream, im.sn_args, SnapshotArgs{ im.pending ? im.blk_first : first, policy ? im.pol_sum : nullptr, form.ransac ? im.rs_sum : nullptr, im.pol_state,
                                                form.rescue ? im.rq_sum : nullptr },
                                  im.sn_ctl, im.pending ? 0 : 1);
@@ -380,11 +416,7 @@ static int run_images_issue(srukf_ctx* c, int first, int count, int mode, double
     replay_prologue(c);
     if (!im.pending) {
         // the block's checkpoint: a block is every image run since the last srukf_synchronize
-        const size_t np = c->d.np;
-        HIPCHK(c, hipMemcpyAsync(im.ckS, c->S, sizeof(double) * np * np, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(im.ckX, c->X, sizeof(double) * np, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(im.ck_tmpl, c->app_tmpl, (size_t)c->d.N * PT_TMPL_STRIDE, hipMemcpyDeviceToDevice, c->stream));
-        if (im.pol_state) HIPCHK(c, hipMemcpyAsync(im.pol_ck, im.pol_state, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, image_state_copy(c, im.ck, image_state_live(c)));
         im.ck_canon = c->null_canonical;
     }
     double* traj = d_traj ? d_traj - (size_t)8 * first : nullptr;
@@ -460,23 +492,14 @@ int srukf_run_images_checked(srukf_ctx* c, int first, int count, int mode, const
 // them before the first checked run); a row a plain image run wrote after a checked one keeps the checked run's values
 int srukf_get_image_checks(srukf_ctx* c, int first, int count, double* corr2, double* z2, int* flags)
 {
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    int rc = image_getter_front(c, "get_image_checks", first, count, nullptr, c && c->img.corr2_seq);
+    if (rc) return rc;
     const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_checks: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_checks: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
-    if (!im.corr2_seq) {
-        if (corr2) memset(corr2, 0, sizeof(double) * m * N);
-        if (z2) memset(z2, 0, sizeof(double) * m * 2 * N);
-        if (flags) memset(flags, 0, sizeof(int) * m * N);
-        return SRUKF_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (corr2) HIPCHK(c, hipMemcpy(corr2, im.corr2_seq + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
-    if (z2) HIPCHK(c, hipMemcpy(z2, im.z2_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
-    if (flags) HIPCHK(c, hipMemcpy(flags, im.flags_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    return SRUKF_OK;
+    const std::vector<ImageBuf> cols = image_group(c, IMG_CHECKED);
+    rc = image_rows_get(c, cols, &im.corr2_seq, first, count, corr2);
+    if (!rc) rc = image_rows_get(c, cols, &im.z2_seq, first, count, z2);
+    if (!rc) rc = image_rows_get(c, cols, &im.flags_seq, first, count, flags);
+    return rc;
 }
 
 // rows [first, first + count) of the record the searching image runs wrote (srukf_images_search_archive), after waiting for the stream like srukf_get_image_matches.
@@ -484,17 +507,15 @@ int srukf_get_image_checks(srukf_ctx* c, int first, int count, double* corr2, do
 // last one): SRUKF_ERR_SEQUENCE, the rule of srukf_get_match_scores
 int srukf_get_image_archive(srukf_ctx* c, int first, int count, int* L, double* h, double* Si, int* visible, double* z, int* matched, double* corr, int* hits)
 {
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    const size_t n = c && c->img.ar_rec ? (size_t)c->img.ar_L : 0, a = (size_t)first, m = (size_t)count;
+    const int rc = image_getter_front(c, "get_image_archive", first, count, c && !c->img.ar_valid ? "no record of a searching image run (srukf_images_search_archive; a flagged block leaves none)" : nullptr,
+                                      n > 0);                  // (an empty archive: the runs were plain ones, nothing to wait for)
+    if (rc) return rc;
     const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_archive: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (!im.ar_valid) { c->err = "get_image_archive: no record of a searching image run (srukf_images_search_archive; a flagged block leaves none)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_archive: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    const size_t n = im.ar_rec ? (size_t)im.ar_L : 0, a = (size_t)first, m = (size_t)count;
     if (L) *L = (int)n;
     if (hits) memset(hits, 0, sizeof(int) * m);
-    if (n == 0) return SRUKF_OK;                               // (an empty archive: the runs were plain ones)
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n == 0) return SRUKF_OK;
+    // (the one record that is no set of columns of image_group: ImageArchiveRecord's blocks, frames x n each)
     const ImageArchiveRecord r = image_archive_record((size_t)im.frames, n);
     const double* rec = im.ar_rec; const int* reci = (const int*)(rec + r.ints);
     if (h) HIPCHK(c, hipMemcpy(h, rec + r.h + a * 2 * n, sizeof(double) * m * 2 * n, hipMemcpyDeviceToHost));
@@ -516,7 +537,7 @@ int srukf_images_set_policy_state(srukf_ctx* c, const srukf_policy_state* state)
     if (!im.images) { c->err = "images_set_policy_state: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
     if (c->async_pending) { c->err = "images_set_policy_state: a run is in flight (srukf_synchronize first)"; return SRUKF_ERR_SEQUENCE; }
     HIPCHK(c, hipSetDevice(c->device));
-    const int rc = images_policy_ensure(c, "images_set_policy_state"); if (rc) return rc;
+    const int rc = image_group_ensure(c, IMG_POLICY, "images_set_policy_state"); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(im.pol_state, state, sizeof(srukf_policy_state) * (size_t)c->d.N, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                 // (pageable host memory)
     im.ck_clean = false;                                        // the checkpoint's copy of the state is not this one: no srukf_images_rewind behind a seed
@@ -527,23 +548,18 @@ int srukf_images_set_policy_state(srukf_ctx* c, const srukf_policy_state* state)
 // srukf_get_image_matches; the device state as it stands; the lowest frame of the range that asks for a map change
 int srukf_get_image_policy(srukf_ctx* c, int first, int count, int* verdict, srukf_policy_summary* summary, srukf_policy_state* state_out, int* first_change)
 {
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    int rc = image_getter_front(c, "get_image_policy", first, count, c && !(c->img.pol_state && c->img.pol_valid) ? "no record of a policy run (srukf_images_policy)" : nullptr);
+    if (rc) return rc;
     const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_policy: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (!im.pol_state || !im.pol_valid) { c->err = "get_image_policy: no record of a policy run (srukf_images_policy)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_policy: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
-    if (verdict) HIPCHK(c, hipMemcpy(verdict, im.pol_verdict + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (state_out) HIPCHK(c, hipMemcpy(state_out, im.pol_state, sizeof(srukf_policy_state) * N, hipMemcpyDeviceToHost));
-    if (summary || first_change) {
-        std::vector<srukf_policy_summary> sm(m);
-        HIPCHK(c, hipMemcpy(sm.data(), im.pol_sum + a, sizeof(srukf_policy_summary) * m, hipMemcpyDeviceToHost));
-        if (summary) memcpy(summary, sm.data(), sizeof(srukf_policy_summary) * m);
-        if (first_change) { *first_change = -1; for (size_t q = 0; q < m; q++) if (sm[q].change) { *first_change = first + (int)q; break; } }
+    const std::vector<ImageBuf> cols = image_group(c, IMG_POLICY);
+    rc = image_rows_get(c, cols, &im.pol_verdict, first, count, verdict);
+    if (!rc) rc = image_rows_copy(c, state_out, im.pol_state, image_state_bytes(c->d).pol, 0, 1);      // (no per-frame column: the state as it stands)
+    if (!rc && (summary || first_change)) {
+        std::vector<srukf_policy_summary> sm;
+        rc = image_summaries_get(c, cols, &im.pol_sum, first, count, sm, first_change, [](const srukf_policy_summary& s) { return s.change != 0; });
+        if (!rc && summary) std::copy(sm.begin(), sm.end(), summary);
     }
-    return SRUKF_OK;
+    return rc;
 }
 
 // ---- the 1-point RANSAC consensus inside image frames (the kernels: srukf_ransac.hip) ----
@@ -562,29 +578,23 @@ int srukf_images_ransac(srukf_ctx* c, int on, double threshold)
 // dropped a match
 int srukf_get_image_ransac(srukf_ctx* c, int first, int count, int* flags, int* votes, double* dist, int* best, int* n_active, int* n_low, int* first_outlier)
 {
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    int rc = image_getter_front(c, "get_image_ransac", first, count, c && !(c->img.rs_flags && c->img.rs_valid) ? "no record of a run with the consensus in it (srukf_images_ransac)" : nullptr);
+    if (rc) return rc;
     const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_ransac: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (!im.rs_flags || !im.rs_valid) { c->err = "get_image_ransac: no record of a run with the consensus in it (srukf_images_ransac)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_ransac: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
-    if (flags) HIPCHK(c, hipMemcpy(flags, im.rs_flags + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (votes) HIPCHK(c, hipMemcpy(votes, im.rs_rvotes + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (dist) HIPCHK(c, hipMemcpy(dist, im.rs_dist + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
-    if (best || n_active || n_low || first_outlier) {
-        std::vector<RansacSummary> sm(m);
-        HIPCHK(c, hipMemcpy(sm.data(), im.rs_sum + a, sizeof(RansacSummary) * m, hipMemcpyDeviceToHost));
-        if (first_outlier) *first_outlier = -1;
-        for (size_t q = 0; q < m; q++) {
+    const std::vector<ImageBuf> cols = image_group(c, IMG_RANSAC);
+    rc = image_rows_get(c, cols, &im.rs_flags, first, count, flags);
+    if (!rc) rc = image_rows_get(c, cols, &im.rs_rvotes, first, count, votes);
+    if (!rc) rc = image_rows_get(c, cols, &im.rs_dist, first, count, dist);
+    if (!rc && (best || n_active || n_low || first_outlier)) {
+        std::vector<RansacSummary> sm;
+        rc = image_summaries_get(c, cols, &im.rs_sum, first, count, sm, first_outlier, [](const RansacSummary& s) { return s.outlier != 0; });
+        for (size_t q = 0; !rc && q < sm.size(); q++) {
             if (best) best[q] = sm[q].best;
             if (n_active) n_active[q] = sm[q].n_active;
             if (n_low) n_low[q] = sm[q].n_low;
-            if (first_outlier && *first_outlier < 0 && sm[q].outlier) *first_outlier = first + (int)q;
         }
     }
-    return SRUKF_OK;
+    return rc;
 }
 
 // ---- the rescue gate behind the frames that hold the consensus (the kernels: srukf_rescue.hip) ----
@@ -603,29 +613,24 @@ int srukf_images_rescue_gate(srukf_ctx* c, int on, double chi2)
 // rows [first, first + count) of the gate's record, after waiting for the stream like srukf_get_image_matches; the lowest frame of the range that would rescue a match
 int srukf_get_image_rescue(srukf_ctx* c, int first, int count, int* flags, double* h2, double* Si2, double* chi2, int* n_cand, int* n_high, int* first_rescue)
 {
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    int rc = image_getter_front(c, "get_image_rescue", first, count,
+                                c && !(c->img.rq_flags && c->img.rq_valid) ? "no record of a run with the rescue gate in it (srukf_images_ransac and srukf_images_rescue_gate)" : nullptr);
+    if (rc) return rc;
     const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_rescue: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (!im.rq_flags || !im.rq_valid) { c->err = "get_image_rescue: no record of a run with the rescue gate in it (srukf_images_ransac and srukf_images_rescue_gate)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_rescue: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
-    if (flags) HIPCHK(c, hipMemcpy(flags, im.rq_flags + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (h2) HIPCHK(c, hipMemcpy(h2, im.rq_h2 + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
-    if (Si2) HIPCHK(c, hipMemcpy(Si2, im.rq_Si2 + a * 4 * N, sizeof(double) * m * 4 * N, hipMemcpyDeviceToHost));
-    if (chi2) HIPCHK(c, hipMemcpy(chi2, im.rq_chi2 + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
-    if (n_cand || n_high || first_rescue) {
-        std::vector<RescueSummary> sm(m);
-        HIPCHK(c, hipMemcpy(sm.data(), im.rq_sum + a, sizeof(RescueSummary) * m, hipMemcpyDeviceToHost));
-        if (first_rescue) *first_rescue = -1;
-        for (size_t q = 0; q < m; q++) {
+    const std::vector<ImageBuf> cols = image_group(c, IMG_RESCUE);
+    rc = image_rows_get(c, cols, &im.rq_flags, first, count, flags);
+    if (!rc) rc = image_rows_get(c, cols, &im.rq_h2, first, count, h2);
+    if (!rc) rc = image_rows_get(c, cols, &im.rq_Si2, first, count, Si2);
+    if (!rc) rc = image_rows_get(c, cols, &im.rq_chi2, first, count, chi2);
+    if (!rc && (n_cand || n_high || first_rescue)) {
+        std::vector<RescueSummary> sm;
+        rc = image_summaries_get(c, cols, &im.rq_sum, first, count, sm, first_rescue, [](const RescueSummary& s) { return s.n_high > 0; });
+        for (size_t q = 0; !rc && q < sm.size(); q++) {
             if (n_cand) n_cand[q] = sm[q].n_cand;
             if (n_high) n_high[q] = sm[q].n_high;
-            if (first_rescue && *first_rescue < 0 && sm[q].n_high > 0) *first_rescue = first + (int)q;
         }
     }
-    return SRUKF_OK;
+    return rc;
 }
 
 // The checkpoint of the image block the last srukf_synchronize ended clean comes back (X, S, the matchPatch array, the policy state: images_restore), so that a host
@@ -713,23 +718,19 @@ int srukf_images_display(srukf_ctx* c, int on)
 // srukf_get_image_checks)
 int srukf_get_image_display(srukf_ctx* c, int first, int count, double* xyz, double* cov, double* axis, double* sigma, int* rot, double* pose4, double* P4, double* Si)
 {
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
     if (!xyz && !cov && !axis && !sigma && !rot && !pose4 && !P4 && !Si) return SRUKF_ERR_BAD_ARG;
+    int rc = image_getter_front(c, "get_image_display", first, count, nullptr, c && c->img.dp_rec);
+    if (rc) return rc;
     const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_display: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_display: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
+    const std::vector<ImageBuf> cols = image_group(c, IMG_DISPLAY);
+    const size_t N = c->d.N, m = (size_t)count, doubles = image_col(cols, &im.dp_rec).row / sizeof(double);
     const ImageDisplayRow r = image_display_row(N);
-    std::vector<double> rec(m * r.doubles, 0.0);
-    if (rot) memset(rot, 0, sizeof(int) * m * N);
-    if (im.dp_rec) {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(rec.data(), im.dp_rec + a * r.doubles, sizeof(double) * m * r.doubles, hipMemcpyDeviceToHost));
-        if (rot) HIPCHK(c, hipMemcpy(rot, im.dp_rot + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    }
+    std::vector<double> rec(m * doubles);
+    rc = image_rows_get(c, cols, &im.dp_rec, first, count, rec.data());
+    if (!rc) rc = image_rows_get(c, cols, &im.dp_rot, first, count, rot);
+    if (rc) return rc;
     for (size_t q = 0; q < m; q++) {
-        const double* row = rec.data() + q * r.doubles;
+        const double* row = rec.data() + q * doubles;
         if (xyz) memcpy(xyz + q * 3 * N, row + r.xyz, sizeof(double) * 3 * N);
         if (cov) memcpy(cov + q * 9 * N, row + r.cov, sizeof(double) * 9 * N);
         if (axis) memcpy(axis + q * 4 * N, row + r.axis, sizeof(double) * 4 * N);
@@ -765,7 +766,8 @@ int srukf_render_image_overlay(srukf_ctx* c, int frame, unsigned char* out_bgr)
     const ImageDisplayRow r = image_display_row(n);
     {
         ProfScope ps(c, KC_OVERLAY, 0, 4.0 * npix);
-        launch_overlay(c->stream, W, H, N, im.h_seq + f * 2 * n, im.dp_rec + f * r.doubles + r.Si, c->z_seq + f * 2 * n, c->m_seq + f * n, c->ov_rec,
+        // (z_seq / m_seq: the staged sequence's own rows, srukf_stage_sequence)
+        launch_overlay(c->stream, W, H, N, image_row(image_group(c, IMG_STAGED), &im.h_seq, f), image_row(image_group(c, IMG_DISPLAY), &im.dp_rec, f) + r.Si, c->z_seq + f * 2 * n, c->m_seq + f * n, c->ov_rec,
                        nullptr, im.images + f * (size_t)npix, c->d_ovl);
     }
     HIPCHK(c, hipGetLastError());
@@ -786,19 +788,17 @@ int srukf_run_images(srukf_ctx* c, int first, int count, int mode, double* traj_
 // of frames in flight are still srukf_synchronize's to report
 int srukf_get_image_matches(srukf_ctx* c, int first, int count, double* z, int* matched, double* corr, int* visible, double* h)
 {
-    if (!c || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    int rc = image_getter_front(c, "get_image_matches", first, count);
+    if (rc) return rc;
     const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "get_image_matches: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (first + count > im.frames) { c->err = "get_image_matches: frames outside the staged images"; return SRUKF_ERR_DIM_MISMATCH; }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t N = c->d.N, a = (size_t)first, m = (size_t)count;
-    if (z) HIPCHK(c, hipMemcpy(z, c->z_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
-    if (matched) HIPCHK(c, hipMemcpy(matched, c->m_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (corr) HIPCHK(c, hipMemcpy(corr, im.corr_seq + a * N, sizeof(double) * m * N, hipMemcpyDeviceToHost));
-    if (visible) HIPCHK(c, hipMemcpy(visible, im.vis_seq + a * N, sizeof(int) * m * N, hipMemcpyDeviceToHost));
-    if (h) HIPCHK(c, hipMemcpy(h, im.h_seq + a * 2 * N, sizeof(double) * m * 2 * N, hipMemcpyDeviceToHost));
-    return SRUKF_OK;
+    const std::vector<ImageBuf> cols = image_group(c, IMG_STAGED);
+    // (z_seq / m_seq are the staged sequence's own, srukf_stage_sequence: a pair and a flag per landmark, the rows of h_seq and vis_seq)
+    rc = image_rows_copy(c, z, c->z_seq, image_col(cols, &im.h_seq).row, first, count);
+    if (!rc) rc = image_rows_copy(c, matched, c->m_seq, image_col(cols, &im.vis_seq).row, first, count);
+    if (!rc) rc = image_rows_get(c, cols, &im.corr_seq, first, count, corr);
+    if (!rc) rc = image_rows_get(c, cols, &im.vis_seq, first, count, visible);
+    if (!rc) rc = image_rows_get(c, cols, &im.h_seq, first, count, h);
+    return rc;
 }
 
 }  // extern "C"

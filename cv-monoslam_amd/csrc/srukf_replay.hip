@@ -1310,6 +1310,19 @@ int srukf_set_rank_aware(srukf_ctx* c, int on)
 // How many of the n pivots the refactorisation skips (0: the rank-aware form is off or found nothing to skip).
 int srukf_null_directions(srukf_ctx* c) { return c ? (c->red_r > 0 ? c->d.n - c->red_r : 0) : SRUKF_ERR_BAD_ARG; }
 
+// what the frames srukf_synchronize has waited for left in *c->hfs (read_fs): the first flag as an error, or SRUKF_OK
+static int flagged_frames_report(srukf_ctx* c)
+{
+    // joint frames: the sticky pair k_joint_dx left (first hit).  A clamp flag of an EARLIER frame goes first: from that frame on nothing is valid anyway
+    if (c->hfs->joint_bad_frame > 0 && !(c->hfs->clamp_rows > 0 && c->hfs->clamp_frame < c->hfs->joint_bad_frame - 1)) return joint_bad_report(c);
+    if (c->hfs->clamp_rows <= 0) return SRUKF_OK;
+    c->clamp_frame_host = c->hfs->clamp_frame; c->clamp_row_host = c->hfs->clamp_first;
+    char b[220]; snprintf(b, sizeof b, "GMW theta clamp active on %d pivot rows (first row %d), first in staged frame %d, during async frames%s", c->hfs->clamp_rows, c->hfs->clamp_first, c->hfs->clamp_frame,
+                         c->hfs->gmw_aborts > 0 ? " (a persistent factorisation launch was abandoned: the GPU is shared; see srukf_set_exclusive)" : "");
+    c->err = b;
+    return SRUKF_ERR_CLAMP_PENDING;
+}
+
 int srukf_synchronize(srukf_ctx* c)
 {
     if (!c) return SRUKF_ERR_BAD_ARG;
@@ -1317,30 +1330,13 @@ int srukf_synchronize(srukf_ctx* c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     c->joint_bad_host = false;
-    if (c->async_pending) {
-        c->async_pending = false;
-        const bool image_run = c->img.pending;                  // the frames were image frames: a flagged block comes back to its checkpoint here (X, S, matchPatch)
-        const bool checked_run = c->img.checked;                // ... with a checked run among them: a flagged block leaves no valid score map
-        const bool search_run = c->img.searching;               // ... with a searching run among them: a flagged block leaves no valid search record
-        c->img.pending = false; c->img.checked = false; c->img.searching = false;
-        int rc = read_fs(c); if (rc) return rc;
-        // joint frames: the sticky pair k_joint_dx left (first hit).  A clamp flag of an EARLIER frame goes first: from that frame on nothing is valid anyway
-        if (c->hfs->joint_bad_frame > 0 && !(c->hfs->clamp_rows > 0 && c->hfs->clamp_frame < c->hfs->joint_bad_frame - 1)) {
-            rc = joint_bad_report(c);
-            if (image_run) { images_restore(c); c->joint_bad_host = false; if (checked_run) c->match_valid = false; if (search_run) c->img.ar_valid = false; }
-            return rc;
-        }
-        if (c->hfs->clamp_rows > 0) {
-            if (image_run) { images_restore(c); if (checked_run) c->match_valid = false; if (search_run) c->img.ar_valid = false; }
-            c->clamp_frame_host = c->hfs->clamp_frame; c->clamp_row_host = c->hfs->clamp_first;
-            char b[220]; snprintf(b, sizeof b, "GMW theta clamp active on %d pivot rows (first row %d), first in staged frame %d, during async frames%s", c->hfs->clamp_rows, c->hfs->clamp_first, c->hfs->clamp_frame,
-                                 c->hfs->gmw_aborts > 0 ? " (a persistent factorisation launch was abandoned: the GPU is shared; see srukf_set_exclusive)" : "");
-            c->err = b;
-            return SRUKF_ERR_CLAMP_PENDING;
-        }
-        if (image_run) c->img.ck_clean = true;                   // the block ended clean: its checkpoint is what srukf_images_rewind puts back
-    }
-    return SRUKF_OK;
+    if (!c->async_pending) return SRUKF_OK;
+    c->async_pending = false;
+    int rc = read_fs(c);
+    const bool read = rc == SRUKF_OK;
+    if (read) rc = flagged_frames_report(c);
+    images_block_end(c, read, rc != SRUKF_OK);                  // the frames were image frames: a flagged block comes back to its checkpoint here (X, S, matchPatch)
+    return rc;
 }
 
 }  // extern "C"
