@@ -111,6 +111,8 @@ void srukf_launch_gain_b(hipStream_t st, KDims d, KWeights w, const GainArgs* ta
 int srukf_gain_part_doubles(int np);
 void srukf_launch_traj(hipStream_t st, KDims d, const double* X, const double* S, FrameScalars* fs, double* traj, int advance);
 void srukf_launch_block_cov(hipStream_t st, KDims d, const double* S, int off, int bs, double* out, const double* X);
+// ... for K landmarks in one launch: the 6 x 6 block of landmark ids[q] (device table, each in [0, N)) into out + 36 q
+void srukf_launch_block_cov_many(hipStream_t st, KDims d, const double* S, const int* ids, int K, double* out);
 void srukf_launch_project_points(hipStream_t st, srukf_params p, int count, const double* feat6, const double* pos3, const double* psi, const double* err2, double* out);
 
 // ---- srukf_factor.hip ----
@@ -302,3 +304,15 @@ void launch_set_snapshot_args(hipStream_t st, SnapshotArgs* dst, SnapshotArgs v,
 // (P4 | pose), and the innovation factors Si [4N] as the frame's association read them into Si_row [4N].  The output pointers are one frame's rows of the
 // display record (ImageDisplayRow, srukf_ctx.h): the host computes them, the kernel knows no frame index
 void launch_image_view(hipStream_t st, KDims d, const double* X, const double* S, const double* Si, double* xyz, double* cov, double* robot, double* Si_row);
+
+// ---- srukf_loop.hip, srukf_map.hip (deleting several landmarks in one call; C++ linkage) ----
+// the records of K landmarks, two launches of K workgroups: k_block_cov (srukf_launch_block_cov_many) leaves the 6 x 6 blocks of P = S^T S at 6 ids[q] in P66 [K][36],
+// k_lm_records packs landmark ids[q]'s record (k_lm_record's body: X6 | S66 | R | t | px | has_app | patch, SRUKF_LM_RECORD_DOUBLES doubles) at
+// out + q * SRUKF_LM_RECORD_DOUBLES.  ids on the device, each in [0, N)
+void launch_lm_records(hipStream_t st, int K, KDims d, const double* S, const double* X, const int* ids, double eps, const unsigned char* app_patch, const double* appR,
+                       const double* appT, const double* appPx, const int* has_app, double* P66, double* out);
+// k_appearance_gather, M workgroups of 64: the appearance record of landmark src_of[a] of one map-size scope (AppearanceArrays: initPatch at PT_PATCH_STRIDE,
+// matchPatch at PT_TMPL_STRIDE, R [9], t [3], px [2], has_app) becomes the one of landmark a of another, a < M; the two byte arrays move in 16-byte accesses.
+// src_of on the device, each entry inside the source's arrays
+struct AppearanceArrays { unsigned char* patch; unsigned char* tmpl; double* R; double* T; double* px; int* has; };
+void launch_appearance_gather(hipStream_t st, int M, const int* src_of, AppearanceArrays src, AppearanceArrays dst);

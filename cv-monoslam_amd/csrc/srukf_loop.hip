@@ -2,22 +2,24 @@
 // state with the archived mean and square-root block (integrateFeaturesInformation's isLoop branch, 948-1015).  gfx950 only.
 //   k_lm_record   the upper Cholesky factor of the landmark's marginal block P66 (left in `small` by k_block_cov), its six rows of X and its appearance
 //                 record packed into one staging block: srukf_get_landmark_record needs one device-to-host copy
+//   k_lm_records  the same for K landmarks in one launch, behind k_block_cov over the same K landmarks
 //   k_lm_insert   the grown X' and S': old rows / columns at their new indices, the new landmarks' blocks on the diagonal, zero elsewhere.  Pure copies
 // This file is built with -ffp-contract=off: the factor must round as written (tests/np_loop.py restates it bit for bit).
 #include "srukf_ctx.h"
 using namespace srukf_impl;
 
-// one workgroup: thread 0 factors, the others copy the patch.  P66 symmetric row-major; eps = params.epsilon.
+// lm_record_body: one landmark's record, ONE text for its two callers (k_lm_record: one workgroup; k_lm_records: one per landmark).
+// Thread 0 factors, all nt threads copy the patch.  P66 symmetric row-major; eps = params.epsilon.
 //   d_j = max(eps, P_jj - sum_{m<j} S_mj^2),  S_jj = sqrt(d_j),  S_ji = (P_ji - sum_{m<j} S_mj S_mi) / S_jj  (i > j), sums in ascending m
-__global__ __launch_bounds__(64) void k_lm_record(const double* __restrict__ P66, const double* __restrict__ X, int k, double eps,
-                                                  const unsigned char* __restrict__ app_patch, int patch_stride, const double* __restrict__ appR,
-                                                  const double* __restrict__ appT, const double* __restrict__ appPx, const int* __restrict__ has_app,
-                                                  double* __restrict__ out)
+__device__ __forceinline__ void lm_record_body(int nt, const double* P66, const double* __restrict__ X, int k, double eps,
+                                               const unsigned char* __restrict__ app_patch, int patch_stride, const double* __restrict__ appR,
+                                               const double* __restrict__ appT, const double* __restrict__ appPx, const int* __restrict__ has_app,
+                                               double* __restrict__ out)
 {
     const int t = threadIdx.x;
     const bool app = has_app && has_app[k] != 0;
     unsigned char* pb = (unsigned char*)(out + LM_REC_DOUBLES);
-    for (int i = t; i < 8 * LM_REC_PATCH_DOUBLES; i += 64) pb[i] = (app && i < PT_PATCH_BYTES) ? app_patch[(size_t)k * patch_stride + i] : 0;
+    for (int i = t; i < 8 * LM_REC_PATCH_DOUBLES; i += nt) pb[i] = (app && i < PT_PATCH_BYTES) ? app_patch[(size_t)k * patch_stride + i] : 0;
     if (t != 0) return;
     double S[36];
     for (int e = 0; e < 36; e++) S[e] = 0.0;
@@ -40,6 +42,26 @@ __global__ __launch_bounds__(64) void k_lm_record(const double* __restrict__ P66
     for (int e = 0; e < 3; e++) out[51 + e] = app ? appT[3 * k + e] : 0.0;
     for (int e = 0; e < 2; e++) out[54 + e] = app ? appPx[2 * k + e] : 0.0;
     out[LM_REC_DOUBLES - 1] = app ? 1.0 : 0.0;
+}
+
+__global__ __launch_bounds__(64) void k_lm_record(const double* __restrict__ P66, const double* __restrict__ X, int k, double eps,
+                                                  const unsigned char* __restrict__ app_patch, int patch_stride, const double* __restrict__ appR,
+                                                  const double* __restrict__ appT, const double* __restrict__ appPx, const int* __restrict__ has_app,
+                                                  double* __restrict__ out)
+{
+    lm_record_body(64, P66, X, k, eps, app_patch, patch_stride, appR, appT, appPx, has_app, out);
+}
+
+// k_lm_records: the records of K landmarks in one launch (srukf_delete_landmarks).  Workgroup q packs landmark ids[q]'s record at
+// out + q * SRUKF_LM_RECORD_DOUBLES from its block P66 + 36 q (k_block_cov with the same ids, the launch in front).  No workgroup reads what another one writes.
+// ids[q] in [0, N): the host has checked them
+__global__ __launch_bounds__(64) void k_lm_records(const double* __restrict__ P66, const double* __restrict__ X, const int* __restrict__ ids, double eps,
+                                                   const unsigned char* __restrict__ app_patch, int patch_stride, const double* __restrict__ appR,
+                                                   const double* __restrict__ appT, const double* __restrict__ appPx, const int* __restrict__ has_app,
+                                                   double* __restrict__ out)
+{
+    lm_record_body(64, P66 + 36 * (size_t)blockIdx.x, X, ids[blockIdx.x], eps, app_patch, patch_stride, appR, appT, appPx, has_app,
+                   out + (size_t)blockIdx.x * SRUKF_LM_RECORD_DOUBLES);
 }
 
 // state index of the grown state -> index of the old one: landmarks before the insertion point keep theirs, the L new ones have none (-1),
@@ -86,3 +108,10 @@ void launch_lm_insert(hipStream_t st, const double* S, int ld, const double* X, 
 }
 
 }  // namespace srukf_impl
+
+void launch_lm_records(hipStream_t st, int K, KDims d, const double* S, const double* X, const int* ids, double eps, const unsigned char* app_patch, const double* appR,
+                       const double* appT, const double* appPx, const int* has_app, double* P66, double* out)
+{
+    srukf_launch_block_cov_many(st, d, S, ids, K, P66);
+    hipLaunchKernelGGL(k_lm_records, dim3(K), dim3(64), 0, st, P66, X, ids, eps, app_patch, PT_PATCH_STRIDE, appR, appT, appPx, has_app, out);
+}

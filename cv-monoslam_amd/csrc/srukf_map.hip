@@ -69,6 +69,31 @@ static void clear_appearance(srukf_ctx* b, int to, int count)
     hipMemsetAsync(b->has_app + to, 0, sizeof(int) * m, b->stream);
 }
 
+// k_appearance_gather: landmark src_of[a]'s appearance record of one scope becomes landmark a's of another (a map change moves every kept record in one launch; six
+// copies per landmark before).  One workgroup (one wave) per destination landmark: lanes 0 .. 27 the initPatch, 28 .. 47 the matchPatch, 16 bytes each (the strides
+// are multiples of 16 and the arrays start at an allocation), lanes 48 .. 62 the fifteen scalars.  Pure copies; no workgroup reads what another one writes
+constexpr int AG_PATCH_V = PT_PATCH_STRIDE / 16, AG_TMPL_V = PT_TMPL_STRIDE / 16, AG_SCALARS = AG_PATCH_V + AG_TMPL_V;
+static_assert(PT_PATCH_STRIDE % 16 == 0 && PT_TMPL_STRIDE % 16 == 0 && AG_SCALARS + 15 <= 64, "one wave moves a record in 16-byte accesses");
+__global__ __launch_bounds__(64) void k_appearance_gather(int M, const int* __restrict__ src_of, AppearanceArrays src, AppearanceArrays dst)
+{
+    const int a = blockIdx.x, t = threadIdx.x;
+    if (a >= M) return;
+    const size_t k = (size_t)src_of[a];
+    if (t < AG_PATCH_V) ((uint4*)(dst.patch + (size_t)a * PT_PATCH_STRIDE))[t] = ((const uint4*)(src.patch + k * PT_PATCH_STRIDE))[t];
+    else if (t < AG_SCALARS) ((uint4*)(dst.tmpl + (size_t)a * PT_TMPL_STRIDE))[t - AG_PATCH_V] = ((const uint4*)(src.tmpl + k * PT_TMPL_STRIDE))[t - AG_PATCH_V];
+    else if (t < AG_SCALARS + 9) dst.R[9 * (size_t)a + (t - AG_SCALARS)] = src.R[9 * k + (t - AG_SCALARS)];
+    else if (t < AG_SCALARS + 12) dst.T[3 * (size_t)a + (t - AG_SCALARS - 9)] = src.T[3 * k + (t - AG_SCALARS - 9)];
+    else if (t < AG_SCALARS + 14) dst.px[2 * (size_t)a + (t - AG_SCALARS - 12)] = src.px[2 * k + (t - AG_SCALARS - 12)];
+    else if (t == AG_SCALARS + 14) dst.has[a] = src.has[k];
+}
+
+void launch_appearance_gather(hipStream_t st, int M, const int* src_of, AppearanceArrays src, AppearanceArrays dst)
+{
+    if (M > 0) hipLaunchKernelGGL(k_appearance_gather, dim3(M), dim3(64), 0, st, M, src_of, src, dst);
+}
+
+static AppearanceArrays appearance_arrays(srukf_ctx* c) { return { c->app_patch, c->app_tmpl, c->appR, c->appT, c->appPx, c->has_app }; }
+
 namespace srukf_impl {
 
 void match_drop(srukf_ctx* c)
@@ -389,49 +414,125 @@ int srukf_add_landmarks(srukf_ctx* c, int K, const double* uv)
     if (c->app_patch) {                                      // the old landmarks keep their appearance records
         rc = ensure_appearance(c2);
         if (rc) return map_change_fail(c, c2, rc, c2->err);
-        for (int k = 0; k < c->d.N; k++) copy_appearance(c, k, c2, k);
-        hipStreamSynchronize(c->stream);
+        int* d_src = nullptr;                                // the identity table: the same launch a deletion issues with its keep table
+        std::vector<int> ident(c->d.N);
+        for (int k = 0; k < c->d.N; k++) ident[k] = k;
+        if (c->d.N > 0 && srukf_dmalloc((void**)&d_src, sizeof(int) * c->d.N) != hipSuccess) return map_change_fail(c, c2, SRUKF_ERR_NOMEM, "add_landmarks: out of device memory");
+        if (d_src) hipMemcpy(d_src, ident.data(), sizeof(int) * c->d.N, hipMemcpyHostToDevice);
+        launch_appearance_gather(c->stream, c->d.N, d_src, appearance_arrays(c), appearance_arrays(c2));
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (d_src) srukf_dfree(d_src);
+        if (e != hipSuccess) return map_change_fail(c, c2, mt, e);
     }
     return map_change_finish(c, c2, mt, K);
 }
 
-// deleteOneFeature, numeric part (SLAM.cpp:2637-2668): landmark id (0-based, state order) leaves the state.  The
+// deleteOneFeature, numeric part (SLAM.cpp:2637-2668): a landmark (0-based, state order) leaves the state.  The
 // reference drops its 6 rows and columns from S and folds the 6 removed rows V back in with six
 // S <- gmw(S^T S + v v^T); the sum of those is the remaining block of P = S^T S, so the device takes S^T S
-// (k_syrk), compacts it and factors it once (the batched form of the six updates, as in srukf_update).
-int srukf_delete_landmark(srukf_ctx* c, int id)
+// (k_syrk), compacts it and factors it once (the batched form of the six updates, as in srukf_update).  K deletions in any order rebuild the same remaining block,
+// P[keep, keep]: K landmarks leave in one pass of the same launches with the keep map of all of them.
+// rec != NULL: the records of the K landmarks (srukf_get_landmark_record's, in the order of ids) are taken before anything moves — one launch, one copy.
+}  // extern "C"
+
+namespace {
+struct LmRecordsOut { double* X6; double* S66; unsigned char* patch; double* R; double* t; double* px; int* has_app; };
+}
+
+// one record of k_lm_record's staging block into the caller's arrays at entry q
+static void unpack_lm_record(const double* h, const LmRecordsOut& o, size_t q)
 {
-    if (!c) return SRUKF_ERR_BAD_ARG;
+    if (o.X6) memcpy(o.X6 + 6 * q, h, sizeof(double) * 6);
+    if (o.S66) memcpy(o.S66 + 36 * q, h + 6, sizeof(double) * 36);
+    if (o.R) memcpy(o.R + 9 * q, h + 42, sizeof(double) * 9);
+    if (o.t) memcpy(o.t + 3 * q, h + 51, sizeof(double) * 3);
+    if (o.px) memcpy(o.px + 2 * q, h + 54, sizeof(double) * 2);
+    if (o.has_app) o.has_app[q] = h[LM_REC_DOUBLES - 1] != 0.0 ? 1 : 0;
+    if (o.patch) memcpy(o.patch + (size_t)PT_PATCH_BYTES * q, h + LM_REC_DOUBLES, PT_PATCH_BYTES);
+}
+
+// the one body of srukf_delete_landmark (K = 1, no records) and srukf_delete_landmarks.  who: the call's name, in c->err and on the timing line
+static int delete_landmarks_body(srukf_ctx* c, const char* who, int K, const int* ids, const LmRecordsOut* rec)
+{
     const int N = c->d.N, n = c->d.n, np = c->d.np;
-    if (id < 0 || id >= N) { c->err = "delete_landmark: no such landmark"; return SRUKF_ERR_BAD_ARG; }
+    std::vector<char> gone(N > 0 ? N : 1, 0);
+    for (int q = 0; q < K; q++) {
+        if (ids[q] < 0 || ids[q] >= N) { c->err = std::string(who) + ": no such landmark"; return SRUKF_ERR_BAD_ARG; }
+        if (gone[ids[q]]) { c->err = std::string(who) + ": a landmark is named twice"; return SRUKF_ERR_BAD_ARG; }
+        gone[ids[q]] = 1;
+    }
     HIPCHK(c, hipSetDevice(c->device));
-    MapTimer mt("delete_landmark");
+    MapTimer mt(who);
     srukf_ctx* c2 = nullptr;
-    int rc = map_change_begin(c, mt, N - 1, &c2); if (rc) return rc;
-    const int nn = n - 6, ldn = c2->d.np;
-    std::vector<int> map(nn);
-    for (int a = 0; a < nn; a++) map[a] = a < 6 * id ? a : a + 6;
+    int rc = map_change_begin(c, mt, N - K, &c2); if (rc) return rc;
+    const int N2 = N - K, nn = n - 6 * K, ldn = c2->d.np;
+    // one table, one copy: the keep map of the state's rows [nn] | the kept landmarks' old positions [N2] | the landmarks that leave [K]
+    std::vector<int> tab((size_t)nn + N2 + K);
+    int k_new = c->K_new > 0 ? c->K_new : 0;                  // m_nFilters-- for each of the landmarks added last that goes (SLAM.cpp:2468-2492)
+    for (int k = 0, a = 0; k < N; k++) {
+        if (gone[k]) { if (k >= N - c->K_new && k_new > 0) k_new--; continue; }
+        for (int e = 0; e < 6; e++) tab[6 * a + e] = 6 * k + e;
+        tab[nn + a] = k; a++;
+    }
+    for (int e = 0; e < 4; e++) tab[6 * N2 + e] = 6 * N + e;  // the robot block
+    for (int q = 0; q < K; q++) tab[(size_t)nn + N2 + q] = ids[q];
     int* d_map = nullptr;
-    if (srukf_dmalloc((void**)&d_map, sizeof(int) * nn) != hipSuccess) return map_change_fail(c, c2, SRUKF_ERR_NOMEM, "delete_landmark: out of device memory");
-    hipMemcpy(d_map, map.data(), sizeof(int) * nn, hipMemcpyHostToDevice);
+    if (srukf_dmalloc((void**)&d_map, sizeof(int) * tab.size()) != hipSuccess) return map_change_fail(c, c2, SRUKF_ERR_NOMEM, std::string(who) + ": out of device memory");
+    const int *d_src = d_map + nn, *d_ids = d_map + nn + N2;
+    hipMemcpy(d_map, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice);
+    // the records first: they read X, S and the appearance arrays of the scope that leaves, and G is free until k_syrk writes it (stream order)
+    const size_t rec_bytes = sizeof(double) * SRUKF_LM_RECORD_DOUBLES * (size_t)K, scratch_bytes = rec_bytes + sizeof(double) * 36 * (size_t)K;      // records | the K blocks of P
+    double* d_rec = nullptr; bool own_rec = false; std::vector<double> h_own; const double* h_rec = nullptr;
+    if (rec) {
+        if (scratch_bytes <= sizeof(double) * (size_t)np * np) d_rec = c->G;
+        else if (srukf_dmalloc((void**)&d_rec, scratch_bytes) != hipSuccess) { srukf_dfree(d_map); return map_change_fail(c, c2, SRUKF_ERR_NOMEM, std::string(who) + ": out of device memory"); }
+        else own_rec = true;
+        double* h = c->hstage;
+        if (rec_bytes > c->hstage_bytes) { h_own.resize(SRUKF_LM_RECORD_DOUBLES * (size_t)K); h = h_own.data(); }
+        h_rec = h;
+        launch_lm_records(c->stream, K, c->d, c->S, c->X, d_ids, c->p.epsilon, c->app_patch, c->appR, c->appT, c->appPx, c->has_app,
+                          d_rec + SRUKF_LM_RECORD_DOUBLES * (size_t)K, d_rec);
+        hipMemcpyAsync(h, d_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream);
+    }
     launch_refactor_reset(c->stream, np, c->theta, c->fs, 1);
     srukf_launch_syrk(c->stream, c->d, c->S, c->Ut, 0, 0, c->G, c->fs, c->syrk_tiles, c->n_syrk_tiles, SyrkRider{});   // P = S^T S
     launch_gather(c->stream, nn, ldn, c->X, c2->X, d_map);
     rc = map_change_factor(c, c2, nn, c->G, np, d_map, true);
-    if (rc) { srukf_dfree(d_map); return map_change_fail(c, c2, rc, c2->err); }
+    if (rc) { srukf_dfree(d_map); if (own_rec) srukf_dfree(d_rec); return map_change_fail(c, c2, rc, c2->err); }
     hipError_t e = hipStreamSynchronize(c->stream);
-    srukf_dfree(d_map);
+    if (own_rec) srukf_dfree(d_rec);
     mt.mark("numeric");
-    if (e != hipSuccess) return map_change_fail(c, c2, mt, e);
-    // m_nFilters-- when one of the landmarks added last is the one that goes (SLAM.cpp:2468-2492)
-    const int k_new = c->K_new > 0 ? (id >= N - c->K_new ? c->K_new - 1 : c->K_new) : 0;
-    if (c->app_patch) {
+    if (e != hipSuccess) { srukf_dfree(d_map); return map_change_fail(c, c2, mt, e); }
+    if (rec) for (int q = 0; q < K; q++) unpack_lm_record(h_rec + SRUKF_LM_RECORD_DOUBLES * (size_t)q, *rec, (size_t)q);
+    if (c->app_patch) {                                      // the kept landmarks keep their appearance records: one launch
         rc = ensure_appearance(c2);
-        if (rc) return map_change_fail(c, c2, rc, c2->err);
-        for (int k = 0, a = 0; k < N; k++) if (k != id) copy_appearance(c, k, c2, a++);
-        hipStreamSynchronize(c->stream);
+        if (rc) { srukf_dfree(d_map); return map_change_fail(c, c2, rc, c2->err); }
+        launch_appearance_gather(c->stream, N2, d_src, appearance_arrays(c), appearance_arrays(c2));
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { srukf_dfree(d_map); return map_change_fail(c, c2, mt, e); }
     }
+    srukf_dfree(d_map);
     return map_change_finish(c, c2, mt, k_new);
+}
+
+extern "C" {
+
+int srukf_delete_landmark(srukf_ctx* c, int id)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    return delete_landmarks_body(c, "delete_landmark", 1, &id, nullptr);
+}
+
+// K landmarks leave together; the records of the ones that leave (any array may be NULL) arrive with the call.  See include/srukf.h
+int srukf_delete_landmarks(srukf_ctx* c, int K, const int* ids, double* records_X6, double* records_S66, unsigned char* patches, double* R, double* t, double* px, int* has_app)
+{
+    if (!c) return SRUKF_ERR_BAD_ARG;
+    if (K < 1 || !ids) { c->err = "delete_landmarks: K < 1 or no ids"; return SRUKF_ERR_BAD_ARG; }
+    const LmRecordsOut rec = { records_X6, records_S66, patches, R, t, px, has_app };
+    const bool any = records_X6 || records_S66 || patches || R || t || px || has_app;
+    return delete_landmarks_body(c, "delete_landmarks", K, ids, any ? &rec : nullptr);
 }
 
 // What an archived landmark takes along (FeatureInfo, SLAM.cpp:1357-1378, 2516-2532): its six rows of X, the upper Cholesky factor of its marginal block

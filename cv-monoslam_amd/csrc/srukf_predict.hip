@@ -668,9 +668,13 @@ __device__ __forceinline__ void block_cov_body(double* red, int ld, const double
         for (int b = a; b < 6; b++) { if (a < bs && b < bs) { out[a * bs + b] = v[q]; out[b * bs + a] = v[q]; } q++; }
 }
 
-__global__ __launch_bounds__(256) void k_block_cov(KDims d, const double* __restrict__ S, int off, int bs, double* __restrict__ out, const double* __restrict__ X)
+// ids (may be null; then one workgroup, `off` and `out` as given): workgroup q forms the 6 x 6 block of landmark ids[q] into out + 36 q — the blocks of the landmarks
+// a deletion takes out, for their records (srukf_delete_landmarks).  The same single call of the body either way
+__global__ __launch_bounds__(256) void k_block_cov(KDims d, const double* __restrict__ S, int off, int bs, double* __restrict__ out, const double* __restrict__ X,
+                                                   const int* __restrict__ ids)
 {
     __shared__ double red[16 * 21];
+    if (ids) { off = 6 * ids[blockIdx.x]; out += 36 * (size_t)blockIdx.x; }
     block_cov_body(red, d.np, S, off, bs, out, X);
 }
 
@@ -810,7 +814,11 @@ void srukf_launch_traj(hipStream_t st, KDims d, const double* X, const double* S
 }
 void srukf_launch_block_cov(hipStream_t st, KDims d, const double* S, int off, int bs, double* out, const double* X)
 {
-    hipLaunchKernelGGL(k_block_cov, dim3(1), dim3(256), 0, st, d, S, off, bs, out, X);
+    hipLaunchKernelGGL(k_block_cov, dim3(1), dim3(256), 0, st, d, S, off, bs, out, X, (const int*)nullptr);
+}
+void srukf_launch_block_cov_many(hipStream_t st, KDims d, const double* S, const int* ids, int K, double* out)
+{
+    hipLaunchKernelGGL(k_block_cov, dim3(K), dim3(256), 0, st, d, S, 0, 6, out, (const double*)nullptr, ids);
 }
 }  // extern "C"
 

@@ -126,6 +126,45 @@ bool CSLAM::deleteOneFeature(int id)
     return true;
 }
 
+// Ours, beside deleteOneFeature: the landmarks at the positions `ids` (distinct, state order of the map as it is) leave the filter and the map in ONE device call
+// (srukf_delete_landmarks), one compaction of mapStore and one refresh of the mirrors.  stored (may be NULL): ids.size() entries; entry q gets
+// what recordFeature gives for landmark ids[q] on the state before the call (sr, initPatch, initRotation, initTrans, hasInitPatch, hasRecord)
+bool CSLAM::deleteFeatures(const std::vector<int>& ids, std::vector<FeatureInfo>* stored)
+{
+    const int K = (int)ids.size(), N = m_nMapFeatures;
+    if (!ctx_ || K < 1) { lastError = "deleteFeatures: no landmarks named"; return false; }
+    if (stored && (int)stored->size() != K) { lastError = "deleteFeatures: one FeatureInfo per landmark"; return false; }
+    std::vector<char> gone(N, 0);
+    for (int id : ids) {
+        if (id < 0 || id >= N || gone[id]) { lastError = "deleteFeatures: no such landmark, or one named twice"; return false; }
+        gone[id] = 1;
+    }
+    Stopwatch sw(m_deleteTime); m_nDeleteCalls++;
+    mirrorsFresh_ = false;
+    if (stored) {
+        std::vector<double> sr(36 * (size_t)K), R(9 * (size_t)K), t(3 * (size_t)K); std::vector<unsigned char> patch(441 * (size_t)K); std::vector<int> has(K);
+        if (!check(srukf_delete_landmarks(ctx_, K, ids.data(), nullptr, sr.data(), patch.data(), R.data(), t.data(), nullptr, has.data()))) return false;
+        for (int q = 0; q < K; q++) {
+            FeatureInfo& fi = (*stored)[q];
+            memcpy(fi.sr, &sr[36 * (size_t)q], sizeof fi.sr); memcpy(fi.initPatch, &patch[441 * (size_t)q], 441);
+            memcpy(fi.initRotation, &R[9 * (size_t)q], sizeof fi.initRotation); memcpy(fi.initTrans, &t[3 * (size_t)q], sizeof fi.initTrans);
+            fi.hasInitPatch = has[q] != 0; fi.hasRecord = true;
+        }
+    } else if (!check(srukf_delete_landmarks(ctx_, K, ids.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return false;
+    size_t a = 0;
+    const int armed = m_nAddings;
+    for (int k = 0; k < N; k++) {
+        if (!gone[k]) { if (a != (size_t)k) mapStore[a] = mapStore[k]; a++; }
+        else if (armed > 0 && k >= N - armed) m_nAddings--;                                                     // 2468-2492, once per armed landmark that leaves
+    }
+    mapStore.resize(a); relinkMap();
+    m_nMapFeatures = N - K;
+    const int n = 6 * m_nMapFeatures + 4;
+    m_X_k.create(n, 1); m_S_k.create(n, n); m_P_k.create(n, n);
+    refreshMirrors();
+    return true;
+}
+
 // ---- data association on the device ------------------------------------------------------------------------------
 bool CSLAM::setFeatureAppearance(int id, const unsigned char* patch, const double R[9], const double t[3], const double px[2])
 {
@@ -431,6 +470,9 @@ bool CSLAM::refreshFeaturesDisplay(bool withMirrors)
 }
 
 // SLAM.cpp:2397-2621.  m_P_k = S^T S (2404) is what refreshMirrors / the device accessors stand for.
+// deleteTogether: the same walk with no device call in it (pass 1: the tests read only X, which a deletion gathers, and the nodes' counters, so the frame's
+// deletion set is known before the first landmark leaves; positions are collected in the indexing the frame began with), then ONE deleteFeatures call for
+// all of them (pass 2), whose records fill the entries recordFeature fills in the walk otherwise.  Same deleted IDs, counters and map IDs afterwards
 bool CSLAM::updateFeaturesInformation()
 {
     if (!m_nMapFeatures || !ctx_) return true;                                                                  // 2399-2402
@@ -439,11 +481,14 @@ bool CSLAM::updateFeaturesInformation()
     if (!refreshFeaturesDisplay(true)) return false;
     const double imageWidth = m_params.image_w, imageHeight = m_params.image_h;
     m_nDeletes = 0; m_nStores = 0; m_deleteID.clear();                                                           // 2419-2422
-    int id = 0;
+    const bool together = deleteTogether;
+    std::vector<int> leave; std::vector<FeatureInfo> infos; std::vector<char> store;                            // pass 1's collection (together)
+    int id = 0, gone = 0;                                                                                       // id: position in the state as it is; id + gone: as the frame began
+    int nLeft = m_nMapFeatures;                                                                                 // landmarks left (== m_nMapFeatures when every deletion runs at once)
     PointsMap* map_p = map;
     while (NULL != map_p) {                                                                                      // 2425
-        const int dim = m_X_k.rows;
-        const double zi = m_X_k.at(6 * id + 2, 0), theta = m_X_k.at(6 * id + 3, 0), phi = m_X_k.at(6 * id + 4, 0), rho = m_X_k.at(6 * id + 5, 0);
+        const int dim = m_X_k.rows, at = together ? id + gone : id;                                              // (together: m_X_k is still the frame's)
+        const double zi = m_X_k.at(6 * at + 2, 0), theta = m_X_k.at(6 * at + 3, 0), phi = m_X_k.at(6 * at + 4, 0), rho = m_X_k.at(6 * at + 5, 0);
         const double Hlr_z = rho * (zi - m_X_k.at(dim - 2, 0)) + cos(phi) * cos(theta);                          // 2435
         const double px = map_p->predictLocation.x, py = map_p->predictLocation.y, dpx = imageWidth - px, dpy = imageHeight - py;
         const bool unmatched = map_p->nPredictTimes > 2 * map_p->nMatchTimes && map_p->nPredictTimes >= 10;
@@ -461,24 +506,37 @@ bool CSLAM::updateFeaturesInformation()
             else if (predBorder) { m_nPredicts--; if (map_p->isMatching) { isNeedStore = true; m_nStores++; m_nMatches--; } }      // 2489-2502
             else if (matchBorder) { isNeedStore = true; m_nStores++; m_nPredicts--; m_nMatches--; }              // 2503-2512
             m_deleteID.push_back(map_p->ID);                                                                     // 2514
+            FeatureInfo fi;
             if (isNeedStore) {                                                                                   // 2516-2532
-                FeatureInfo fi;
                 fi.ID = map_p->ID; fi.isLoop = map_p->isLoop; fi.nPredictTimes = map_p->nPredictTimes; fi.nMatchTimes = map_p->nMatchTimes;
                 fi.initXYZ = map_p->xyz; fi.initPixel = map_p->initPixel;
-                for (int e = 0; e < 6; e++) fi.state[e] = m_X_k.at(6 * id + e, 0);
+                for (int e = 0; e < 6; e++) fi.state[e] = m_X_k.at(6 * at + e, 0);
                 fi.position = map_p->xyz; memcpy(fi.cov, map_p->cov, sizeof fi.cov); fi.axis = map_p->axis; fi.sigma = map_p->sigma;
-                if (reinsertLoopPoints && !recordFeature(fi, id)) return false;                                   // before the landmark leaves
-                m_featuresAllInfo.push_back(fi);
+                if (!together) {
+                    if (reinsertLoopPoints && !recordFeature(fi, id)) return false;                               // before the landmark leaves
+                    m_featuresAllInfo.push_back(fi);
+                }
             }
-            if (!deleteOneFeature(id)) return false;                                                             // 2554 (m_nDeletes++, m_nMapFeatures--: 2662-2664)
+            if (together) {                                                                                      // pass 1: the landmark leaves with the others, below
+                leave.push_back(at); infos.push_back(fi); store.push_back(isNeedStore ? 1 : 0);
+                gone++; nLeft--;
+                map_p = map_p->next;                                                                             // the node that would now be at position id
+            } else {
+                if (!deleteOneFeature(id)) return false;                                                         // 2554 (m_nDeletes++, m_nMapFeatures--: 2662-2664)
+                nLeft = m_nMapFeatures;
+                map_p = (id < m_nMapFeatures) ? &mapStore[id] : nullptr;                                         // 2555-2570: the node now at position id
+            }
             m_nDeletes++;
-            map_p = (id < m_nMapFeatures) ? &mapStore[id] : nullptr;                                             // 2555-2570: the node now at position id
         } else {
             map_p->isVisible = false;                                                                            // 2598
         }
-        if (id == m_nMapFeatures || !map_p) break;                                                               // 2607-2615 (a NULL node is dereferenced there)
+        if (id == nLeft || !map_p) break;                                                                        // 2607-2615 (a NULL node is dereferenced there)
         id++;
         map_p = map_p->next;
+    }
+    if (together && !leave.empty()) {                                                                            // pass 2: one device call, one compaction, one refresh
+        if (!deleteFeatures(leave, reinsertLoopPoints ? &infos : nullptr)) return false;
+        for (size_t q = 0; q < infos.size(); q++) if (store[q]) m_featuresAllInfo.push_back(infos[q]);
     }
     return true;
 }

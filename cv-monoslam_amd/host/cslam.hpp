@@ -177,6 +177,13 @@ public:
     bool integrateFeaturesInformation(int K, const double* keyPoints /*2K*/);
     // deleteOneFeature (SLAM.cpp:2637-2706): the id-th landmark of the state (0-based) leaves the filter and the map
     bool deleteOneFeature(int id);
+    // ours, beside it: the landmarks at the positions ids (distinct, any order) leave the filter and the map in one device call (srukf_delete_landmarks),
+    // one compaction of the map and one refresh of the mirrors.  stored (may be NULL; ids.size() entries): entry q receives the record recordFeature reads for
+    // ids[q] (sr, initPatch, initRotation, initTrans, hasInitPatch, hasRecord), taken on the state before the call
+    bool deleteFeatures(const std::vector<int>& ids, std::vector<FeatureInfo>* stored = nullptr);
+    // true: updateFeaturesInformation decides the frame's deletions in a walk without device calls (same tests, same traversal, same counters) and lets them
+    // leave together through deleteFeatures.  false (default): one deleteOneFeature per landmark inside the walk, as the reference
+    bool   deleteTogether = false;
 
     // ---- data association on the device ----------------------------------------------------------------
     // the appearance fields of PointsMap the reference fills at creation (SLAM.cpp:920-925): initPatch = the 21 x 21 gray

@@ -53,6 +53,10 @@
 //              integrateFeaturesInformation (joint initialisation on the device); the next frame's KalmanUpdate then runs FLAG_4_NEED_REORDER.  N stays where it
 //              was.  Every landmark is "found" at its predicted pixel + 0.5 px of noise (new landmarks have no entry in the scene's z).  Prints frames/s,
 //              the map changes and their wall time per operation, and how many frames ran on the step-wise fast path / on the other one
+//              drop=<k> (default 1: the above): every change starves k landmarks, no two of them neighbours in the state (the walk of updateFeaturesInformation
+//              does not test the node behind a deleted one in the same frame), and addFeatures hands k key points.  together=1: CSLAM::deleteTogether on — the
+//              landmarks of a frame leave in one device call.  With either, "deletion_calls" and "landmarks_deleted" follow "ms_per_deletion"
+//              (which is per call)
 //     ransac=1 (facade): CSLAM::isUseRANSAC on (KalmanUpdate runs the 1-point RANSAC steps: consensus, update, and the rescue when matches remain outside it)
 //     joint=1 : every update is the joint measurement update (capi / assoc: srukf_update_joint; facade: CSLAM::jointUpdate).  Adds, and only with it,
 //              "joint": 1 and "joint_flagged_frames" (updates whose refactorisation was flagged and went to the exact path) to the output
@@ -88,6 +92,7 @@ int main(int argc, char** argv)
     int rescue = 0; long long rq_high = 0;                              // rescue=1 (assoc_replay with ransac=)
     int resume = -1, stop_k = 0; long long stop_blocks = 0;      // resume= / stop= (assoc_replay)
     int display = 0;      // display= (assoc_replay)
+    int drop = 1, together = 0; long long landmarks_deleted = 0;      // drop= / together= (facade with churn=)
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
         if (!strncmp(argv[a], "mode=", 5)) mode = argv[a] + 5;
@@ -108,6 +113,8 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "resume=", 7)) resume = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "stop=", 5)) stop_k = atoi(argv[a] + 5);
         else if (!strncmp(argv[a], "display=", 8)) display = atoi(argv[a] + 8) != 0;
+        else if (!strncmp(argv[a], "drop=", 5)) drop = atoi(argv[a] + 5);
+        else if (!strncmp(argv[a], "together=", 9)) together = atoi(argv[a] + 9) != 0;
         else if (!strncmp(argv[a], "subpix=", 7)) { if (atoi(argv[a] + 7)) { checked = true; mpar.subpixel = 1; } }
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } sets.emplace_back(std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))), atoi(q + 1)); }
     }
@@ -152,8 +159,11 @@ int main(int argc, char** argv)
     const int legs = stop_k ? 2 : 1;                                // stop=: both routes, the one asked for last (it is the one reported)
     double leg_pose[2][4 + 16] = { { 0 } };
     if (areplay && (block_frames < 1 || W < 1)) { fprintf(stderr, "assoc_replay: block >= 1 and warmup >= 1 (frame 0 sets the appearance records up)\n"); return 2; }
+    if ((drop != 1 || together) && !(mode == "facade" && churn > 0)) { fprintf(stderr, "drop= / together= belong to mode=facade churn=P\n"); return 2; }
+    if (drop < 1 || drop > 16) { fprintf(stderr, "drop=<k>: 1 <= k <= 16\n"); return 2; }
     if (mode == "facade") {
         monoslam::CSLAM SLAM;
+        SLAM.deleteTogether = together != 0;
         SLAM.m_params.a1 = a4[0]; SLAM.m_params.a2 = a4[1]; SLAM.m_params.a3 = a4[2]; SLAM.m_params.a4 = a4[3];
         SLAM.isUseRANSAC = ransac != 0;
         SLAM.jointUpdate = joint != 0;
@@ -170,22 +180,32 @@ int main(int argc, char** argv)
                 const int fr = s.m_frame.counter - 1;
                 const bool change = fr >= 10 && fr % churn == 0;
                 int idx = 0, victim = -1;
+                std::vector<int> more;                                                                          // drop > 1: the victims behind the first
                 if (change) {
                     // the next landmark (from a rotating start) that has been predicted often enough for the rule to remove it in THIS frame
                     const int start = (victim_turn * 7) % s.m_nMapFeatures; victim_turn++;
-                    for (int q = 0; q < s.m_nMapFeatures && victim < 0; q++) { const int k = (start + q) % s.m_nMapFeatures; if (s.map[k].nPredictTimes >= 10) victim = k; }
+                    for (int q = 0; q < s.m_nMapFeatures && (victim < 0 || (int)more.size() < drop - 1); q++) {
+                        const int k = (start + q) % s.m_nMapFeatures;
+                        if (s.map[k].nPredictTimes < 10) continue;
+                        if (victim < 0) { victim = k; continue; }
+                        bool neighbour = std::abs(k - victim) <= 1;                                             // (the walk skips the node behind a deleted one)
+                        for (int v : more) neighbour = neighbour || std::abs(k - v) <= 1;
+                        if (!neighbour) more.push_back(k);
+                    }
                     s.isAdding = true;
                 }
                 for (monoslam::PointsMap* mp = s.map; NULL != mp; mp = mp->next, idx++) {
                     mp->isMatching = mp->isVisible;
                     mp->matchLocation.x = mp->predictLocation.x + 0.5 * gauss(); mp->matchLocation.y = mp->predictLocation.y + 0.5 * gauss();
-                    if (idx == victim && mp->nPredictTimes >= 10) { mp->isMatching = false; mp->nMatchTimes = 0; }      // the policy's rule 2443: it leaves in this frame
+                    const bool starve = idx == victim || std::find(more.begin(), more.end(), idx) != more.end();
+                    if (starve && mp->nPredictTimes >= 10) { mp->isMatching = false; mp->nMatchTimes = 0; }      // the policy's rule 2443: it leaves in this frame
                 }
             };
             SLAM.addFeatures = [&](monoslam::CSLAM& s, std::vector<double>& kp) {
                 s.isAdding = false;
                 kp.assign({ 60.0 + 520.0 * rnd(), 60.0 + 360.0 * rnd() });                                  // one key point where the detector "found" a corner
-                return 1;
+                for (int q = 1; q < drop; q++) { kp.push_back(60.0 + 520.0 * rnd()); kp.push_back(60.0 + 360.0 * rnd()); }      // (drop=<k>: k of them)
+                return drop;
             };
         } else
         SLAM.dataAssociation = [&](monoslam::CSLAM& s) {
@@ -205,6 +225,7 @@ int main(int argc, char** argv)
             const int counter = SLAM.m_frame.counter - 1;
             const double f0 = now_s();
             SLAM.SLAM();
+            landmarks_deleted += SLAM.m_nDeletes;
             if (churn > 0) { const int ph = counter >= 10 ? (counter % churn < 3 ? counter % churn : 3) : 3; by_phase[ph] += now_s() - f0; n_phase[ph]++; }
         }
         t_timed = now_s() - t0;
@@ -221,6 +242,12 @@ int main(int argc, char** argv)
                      (SLAM.m_addTime - add0 + SLAM.m_deleteTime - del0) / t_timed, SLAM.m_nMapFeatures, fast1, slow1,
                      n_phase[0] ? by_phase[0] / n_phase[0] * 1e6 : 0.0, n_phase[1] ? by_phase[1] / n_phase[1] * 1e6 : 0.0, n_phase[2] ? by_phase[2] / n_phase[2] * 1e6 : 0.0,
                      n_phase[3] ? by_phase[3] / n_phase[3] * 1e6 : 0.0);
+            if (drop != 1 || together) {                                                                        // beside ms_per_deletion (per call), and only then
+                char extra[120];
+                snprintf(extra, sizeof extra, "\"deletion_calls\": %d, \"landmarks_deleted\": %lld, \"drop\": %d, \"together\": %d, ", nd, landmarks_deleted, drop, together);
+                std::string cj = churn_json; const size_t at = cj.find("\"map_change_share_of_wall\"");
+                if (at != std::string::npos) { cj.insert(at, extra); snprintf(churn_json, sizeof churn_json, "%s", cj.c_str()); }
+            }
         }
         if (!SLAM.lastError.empty()) { fprintf(stderr, "%s\n", SLAM.lastError.c_str()); return 1; }
         joint_flagged = SLAM.m_nJointFlagged;

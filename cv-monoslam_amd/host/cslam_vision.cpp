@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>] [together=1]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -38,6 +38,9 @@
 //   behind that frame's tail, one line "frame ID" and xyz, cov, axis, sigma as %a (a NaN as "nan" whatever its sign): for the last consumed frame of a block (and
 //   every frame of block=1) from map[], for the frames in front of it from m_blockDisplay.  The same file through either route.  With overlay=<file> the overlay of
 //   the last block's last consumed frame goes to <file> (CSLAM::blockOverlayLast: drawn in front of that frame's tail); stdout is what it is without both.
+// together=1: CSLAM::deleteTogether on: the landmarks a frame's updateFeaturesInformation deletes leave in one device call.  Every line is what it
+//   is without it (the pose and covariance figures within rounding when a frame deletes more than one landmark).
+// set=key:value: srukf_debug_set(NULL, key, value) for a process-wide measurement switch (set=timing:1: the phases of every map change on stderr).
 // min_matches=<n>: CSLAM::m_minNUM = n (addFeatures when fewer landmarks matched, SLAM.cpp:179, 556; default 5).
 // warmup: one frame of a throwaway facade first (code objects loaded, device memory pool grown), so that the timings printed are steady-state ones.
 // Prints every detection pass with its inputs ("pass" blocks) and, after every frame, the map ("frame" lines + the init pixels of every landmark).
@@ -51,7 +54,7 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>] [min_matches=<n>]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>] [min_matches=<n>] [together=1]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
@@ -61,6 +64,7 @@ int main(int argc, char** argv)
     fclose(f);
     int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay, display;
     bool unique = false, subpix = false, joint = false, resume = false, rescue = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
+    bool together = false;
     int minMatches = 0, block = 0, nBlocks = 0, nEarly = 0, nFull = 0, nFallback = 0;
     for (int a = 3; a < argc; a++)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
@@ -76,6 +80,8 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "rescue=", 7)) rescue = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "display=", 8)) display = argv[a] + 8;
         else if (!strncmp(argv[a], "min_matches=", 12)) minMatches = atoi(argv[a] + 12);
+        else if (!strncmp(argv[a], "together=", 9)) together = atoi(argv[a] + 9) != 0;
+        else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } (void)srukf_debug_set(nullptr, std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))).c_str(), atoi(q + 1)); }
     if (warmup) {
         monoslam::CSLAM w;
         w.m_params.image_w = W; w.m_params.image_h = H; w.MIN_STEP_X = w.MIN_STEP_Y = 0.0;
@@ -99,6 +105,7 @@ int main(int argc, char** argv)
     SLAM.jointUpdate = joint;
     SLAM.resumeStoppedBlocks = resume;
     SLAM.rescueGateOnDevice = rescue;
+    SLAM.deleteTogether = together;
     if (minMatches > 0) SLAM.m_minNUM = minMatches;
     const unsigned char* cur = nullptr;
     std::vector<unsigned char> bgr(colour ? (size_t)3 * W * H : 0);

@@ -39,6 +39,7 @@ EXPORTS = [
     "srukf_images_snapshots", "srukf_get_image_snapshots", "srukf_images_resume",
     "srukf_images_display", "srukf_get_image_display", "srukf_render_image_overlay",
     "srukf_images_rescue_gate", "srukf_get_image_rescue", "srukf_rescue_gate",
+    "srukf_delete_landmarks",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -162,6 +163,8 @@ def load_library(path=None):
     L.srukf_add_landmarks.argtypes = [C.c_void_p, C.c_int, _dp]
     L.srukf_delete_landmark.argtypes = [C.c_void_p, C.c_int]
     _bp = C.POINTER(C.c_ubyte)
+    if hasattr(L, "srukf_delete_landmarks"):           # (an A/B build of an older library, bench.py --lib, deletes one landmark per call)
+        L.srukf_delete_landmarks.argtypes = [C.c_void_p, C.c_int, _ip, _dp, _dp, _bp, _dp, _dp, _dp, _ip]
     L.srukf_set_landmark_appearance.argtypes = [C.c_void_p, C.c_int, _bp, _dp, _dp, _dp]
     L.srukf_associate.argtypes = [C.c_void_p, _bp, _dp, _ip, _dp]
     L.srukf_get_match_patch.argtypes = [C.c_void_p, C.c_int, _bp]
@@ -627,6 +630,24 @@ class Filter:
         """deleteOneFeature: landmark idx (0-based state order) leaves the map; the filter shrinks to N - 1."""
         self._chk(self._lib.srukf_delete_landmark(self._h, int(idx)))
         self._refresh_dims()
+
+    def delete_landmarks(self, ids, records=False):
+        """Several landmarks leave the map in one device call (srukf_delete_landmarks): ids are distinct 0-based positions, in any order; the filter shrinks
+        to N - len(ids).  records=True: returns what get_landmark_record(id) gives for each id on the state before the call, as a dict of arrays X6[K,6],
+        S66[K,6,6], patch[K,21,21] uint8, R[K,3,3], t[K,3], px[K,2], has_app[K] bool, in the order of ids."""
+        ids = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32).ravel()
+        K = int(ids.shape[0])
+        if not records:
+            self._chk(self._lib.srukf_delete_landmarks(self._h, K, _i(ids) if K else None, None, None, None, None, None, None, None))
+            self._refresh_dims()
+            return None
+        M = max(K, 1)
+        x6, S, patch = np.zeros((M, 6)), np.zeros((M, 6, 6)), np.zeros((M, 21, 21), dtype=np.uint8)
+        R, t, px, has = np.zeros((M, 3, 3)), np.zeros((M, 3)), np.zeros((M, 2)), np.zeros(M, dtype=np.int32)
+        self._chk(self._lib.srukf_delete_landmarks(self._h, K, _i(ids) if K else None, _d(x6), _d(S), patch.ctypes.data_as(C.POINTER(C.c_ubyte)), _d(R), _d(t), _d(px),
+                                                   _i(has)))
+        self._refresh_dims()
+        return {"X6": x6[:K], "S66": S[:K], "patch": patch[:K], "R": R[:K], "t": t[:K], "px": px[:K], "has_app": has[:K] != 0}
 
     def stage_sequence(self, odo, z, matched):
         odo, z, m = _c(odo), _c(z), _c(matched, np.int32)

@@ -431,6 +431,15 @@ int  srukf_get_state_f32(srukf_ctx* ctx, float* X, float* S);
  * FLAG_4_UPDATING), i.e. S becomes the factor of the remaining block of P = S^T S.  The context shrinks to N - 1
  * landmarks in place. */
 int  srukf_delete_landmark(srukf_ctx* ctx, int id);
+/* K landmarks leave in one call: ids[K] are distinct 0-based positions in the current state, in any order.  X' = X[keep] with the kept landmarks in their
+ * old order, S' = the upper factor of (S^T S)[keep, keep] — what K calls of srukf_delete_landmark rebuild, in any order, by one product, one compaction
+ * and one factorisation.  The context shrinks to N - K landmarks in place, once (K = N leaves the robot block); of the landmarks the last srukf_add_landmarks
+ * armed, the ones with ids >= N - K_new leave K_new too.  srukf_delete_landmark(ctx, id) is the K = 1 call.
+ * records_X6 [K][6], records_S66 [K][36], patches [K][441], R [K][9], t [K][3], px [K][2], has_app [K] (each may be NULL): entry q holds what
+ * srukf_get_landmark_record(ctx, ids[q], ...) returns on the state before the call, byte for byte; all K arrive in one device round trip.
+ * SRUKF_ERR_BAD_ARG, with the handle left as it was: a NULL handle, K < 1, NULL ids, an id outside [0, N), an id named twice. */
+int  srukf_delete_landmarks(srukf_ctx* ctx, int K, const int* ids, double* records_X6, double* records_S66,
+                            unsigned char* patches, double* R, double* t, double* px, int* has_app);
 
 /* ---- benchmark seam: whole frames with inputs pre-staged in HBM --------------------------- */
 
