@@ -148,6 +148,11 @@ struct ImageReplay {
     // srukf_render_image_overlay asks: rot cannot tell, 0 rotations is a legal value)
     double* dp_rec = nullptr; int* dp_rot = nullptr;
     std::vector<unsigned char> dp_rows;
+    // Colour frames in the staged stack (srukf_stage_images_bgr): bgr holds bgr_pix pixels of 3 bytes, padded to whole groups of four —
+    // the whole stack, tight like `images`, when bgr_kept, else the transit buffer of the staging call, freed before it returns.  The overlays of a run of frames
+    // (srukf_render_image_overlays): ovs_count output frames (ovs_out) and record slabs (ovs_rec), the largest count asked for so far
+    unsigned char* bgr = nullptr; size_t bgr_pix = 0; bool bgr_kept = false;
+    unsigned char* ovs_out = nullptr; void* ovs_rec = nullptr; int ovs_count = 0;
 };
 
 // one frame's row of the display record, offsets in doubles: xyz [3N] | cov [9N] | axis [4N] | sigma [3N] | robot [20] = P4 | pose | Si [4N]
@@ -455,6 +460,11 @@ size_t overlay_bgr_bytes(int npix);
 void launch_bgr2gray(hipStream_t st, int npix, const unsigned char* bgr, unsigned char* gray);
 void launch_overlay(hipStream_t st, int W, int H, int N, const double* h, const double* Si, const double* z, const int* matched, void* rec,
                     const unsigned char* bgr /* NULL: gray three times */, const unsigned char* gray, unsigned char* out);
+constexpr int OVERLAY_BLOCK_MAX = 65535;                     // frames in one launch_overlay_block: the frame is gridDim.y
+// the same for `count` staged frames in two launches (W H a multiple of four, N >= 1, count <= OVERLAY_BLOCK_MAX): every pointer is the first frame's, the rows' strides are in elements, the
+// stacks tight, rec count slabs of overlay_rec_bytes(N)
+void launch_overlay_block(hipStream_t st, int W, int H, int N, int count, const double* h, size_t h_stride, const double* Si, size_t Si_stride, const double* z, size_t z_stride,
+                          const int* matched, size_t m_stride, void* rec, const unsigned char* bgr /* NULL: gray three times */, const unsigned char* gray, unsigned char* out);
 
 // ---- loop points (srukf_loop.hip) ----
 // k_lm_record's staging block: X6 | S66 | R | t | px | has_app, then the patch at its stride (zero-filled behind its bytes)

@@ -1,8 +1,9 @@
-// srukf_images.hip — image runs of the staged replay (DESIGN.md sections 20 - 27): the staged gray frames and the frames that associate on the device
+// srukf_images.hip — image runs of the staged replay (DESIGN.md sections 20 - 27, 29): the staged gray frames and the frames that associate on the device
 // (srukf_stage_images / srukf_run_images*), their per-frame options — the checked association (srukf_run_images_checked*), the archive search
 // (srukf_images_search_archive), the map policy's verdict (srukf_images_policy), the 1-point RANSAC consensus (srukf_images_ransac), its rescue gate
 // (srukf_images_rescue_gate), the snapshots (srukf_images_snapshots / _resume) and the display view (srukf_images_display, with the overlay of any staged frame,
-// srukf_render_image_overlay) — and the getters of their records.  No kernel: the launch sequences, the graph cache and srukf_synchronize are srukf_replay.hip's;
+// srukf_render_image_overlay), colour frames in the staged stack and the overlays of a run of frames (srukf_stage_images_bgr, srukf_get_staged_image,
+// srukf_render_image_overlays; section 29) — and the getters of their records.  No kernel: the launch sequences, the graph cache and srukf_synchronize are srukf_replay.hip's;
 // what the two files share is declared once in srukf_ctx.h.
 // A further per-frame option is: its switch on the handle and its members of ImageReplay (srukf_ctx.h); one group of image_group, each record column with its row
 // and whether a restored block's rows stand; in run_images_issue one image_group_ensure and the parameters' launch; a captured launch: one bit of ImageForm and one
@@ -22,7 +23,7 @@ namespace srukf_impl {
 // image_buffers_alloc allocates a group, images_drop and images_archive_drop free through the same lists: a buffer added HERE is freed without anyone remembering
 // to list it.  The sizes are the allocation's (image_bytes: of one staged frame, L: the archive's; whoever only frees passes neither).  Not zeroed: the parameter
 // blocks (written in stream order in front of every run that reads them), the images, xyz and the copies of the state
-enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_SNAPSHOT, IMG_RESCUE, IMG_DISPLAY, IMG_GROUPS };
+enum ImageGroup { IMG_STAGED, IMG_CHECKED, IMG_ARCHIVE, IMG_POLICY, IMG_RANSAC, IMG_SNAPSHOT, IMG_RESCUE, IMG_DISPLAY, IMG_COLOUR, IMG_OVERLAYS, IMG_GROUPS };
 struct ImageBuf { void** p; size_t bytes; bool zero; size_t row; bool block; };
 struct ImageStateBytes { size_t X, S, tmpl, pol; };
 static ImageStateBytes image_state_bytes(const KDims& d)
@@ -51,6 +52,8 @@ static std::vector<ImageBuf> image_group(srukf_map_scope* c, ImageGroup g, size_
     case IMG_RESCUE: return { col(&im.rq_flags, I * N, true), col(&im.rq_h2, D * 2 * N, true), col(&im.rq_Si2, D * 4 * N, true), col(&im.rq_chi2, D * N, true),
                               col(&im.rq_sum, sizeof(RescueSummary), true), buf(&im.rq_vis, I * N, true), buf(&im.rq_PxyR, D * 5 * mp, true), buf(&im.rq_args, sizeof(RescueArgs)) };
     case IMG_DISPLAY: return { col(&im.dp_rec, D * image_display_row(N).doubles, true), col(&im.dp_rot, I * N, true) };
+    case IMG_COLOUR: return { buf(&im.bgr, 12 * ((im.bgr_pix + 3) / 4)) };      // (whole groups of four pixels: what k_bgr2gray and k_overlay* may read)
+    case IMG_OVERLAYS: return { buf(&im.ovs_out, (size_t)im.ovs_count * 3 * image_bytes), buf(&im.ovs_rec, (size_t)im.ovs_count * overlay_rec_bytes((int)N)) };
     default: return {};
     }
 }
@@ -261,24 +264,79 @@ extern "C" {
 
 // The gray frames of the staged sequence, copied to the device once; with them the per-frame record, the scratch for the Cartesian points and the block's checkpoint
 // (X, S, matchPatch): everything an image run needs that can fail for want of memory is allocated here, outside any capture.
-int srukf_stage_images(srukf_ctx* c, int F, const unsigned char* gray)
+// One body behind srukf_stage_images (colour < 0: src is the gray stack) and srukf_stage_images_bgr (colour = keep_colour: src is F frames of B, G, R bytes).
+// The colour route: both stacks are tight, so the F frames are one run of F W H pixels and k_bgr2gray converts it as it converts one frame — its groups of four
+// pixels count from the start of the STACK, dword-aligned in both buffers wherever a frame begins, and only the stack's last group can be a partial one (its gray
+// bytes go one by one, inside [0, F W H)).  The run is walked in chunks of STAGE_CHUNK pixels, a multiple of four, each copied and converted in stream order:
+// with keep_colour = 0 the colour bytes pass through ONE transit buffer of min(F W H, STAGE_CHUNK) pixels — at most 12 MiB — which the next chunk's copy
+// overwrites behind this chunk's launch; it is freed before the call returns.  The chunk also keeps every index of a launch below 2^31
+constexpr size_t STAGE_CHUNK = (size_t)1 << 22;                  // pixels; a multiple of four
+static int stage_images_any(srukf_ctx* c, int F, const unsigned char* src, int colour, const char* who)
 {
-    if (!c || F < 1 || !gray) return SRUKF_ERR_BAD_ARG;
-    if (!c->odo_seq) { c->err = "stage_images: no staged sequence (srukf_stage_sequence first)"; return SRUKF_ERR_SEQUENCE; }
-    if (F != c->seqF) { c->err = "stage_images: n_frames is not the staged sequence's"; return SRUKF_ERR_DIM_MISMATCH; }
-    if (c->d.N < 1) { c->err = "stage_images: the map is empty"; return SRUKF_ERR_DIM_MISMATCH; }
+    const std::string w = who;
+    if (!c->odo_seq) { c->err = w + ": no staged sequence (srukf_stage_sequence first)"; return SRUKF_ERR_SEQUENCE; }
+    if (F != c->seqF) { c->err = w + ": n_frames is not the staged sequence's"; return SRUKF_ERR_DIM_MISMATCH; }
+    if (c->d.N < 1) { c->err = w + ": the map is empty"; return SRUKF_ERR_DIM_MISMATCH; }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));             // frames in flight may still read the images staged before
     images_drop(c, c->stream);
     int rc = ensure_appearance(c); if (rc) return rc;
     ImageReplay& im = c->img;
-    const size_t img = (size_t)c->p.image_w * (size_t)c->p.image_h;
+    const size_t img = (size_t)c->p.image_w * (size_t)c->p.image_h, total = (size_t)F * img;
     im.frames = F;                                          // (the group's sizes)
-    rc = image_buffers_alloc(c, image_group(c, IMG_STAGED, img), "stage_images");
+    rc = image_buffers_alloc(c, image_group(c, IMG_STAGED, img), who);
     if (rc) { images_drop(c, c->stream); return rc; }
-    hipError_t e = hipMemcpy(im.images, gray, (size_t)F * img, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { images_drop(c, c->stream); c->err = std::string("stage_images: ") + hipGetErrorString(e); return SRUKF_ERR_HIP; }
+    hipError_t e = hipSuccess;
+    if (colour < 0) e = hipMemcpy(im.images, src, total, hipMemcpyHostToDevice);
+    else {
+        im.bgr_kept = colour != 0;
+        im.bgr_pix = im.bgr_kept ? total : std::min(total, STAGE_CHUNK);
+        rc = image_buffers_alloc(c, image_group(c, IMG_COLOUR), who);
+        if (rc) { images_drop(c, c->stream); return rc; }
+        for (size_t off = 0; off < total && e == hipSuccess; off += STAGE_CHUNK) {
+            const size_t n = std::min(total - off, STAGE_CHUNK);
+            unsigned char* d = im.bgr_kept ? im.bgr + 3 * off : im.bgr;
+            e = hipMemcpyAsync(d, src + 3 * off, 3 * n, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) break;
+            ProfScope ps(c, KC_BGR2GRAY, 0, 4.0 * (double)n);
+            launch_bgr2gray(c->stream, (int)n, d, im.images + off);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // (src is the caller's pageable memory)
+    if (e != hipSuccess) { images_drop(c, c->stream); c->err = w + ": " + hipGetErrorString(e); return SRUKF_ERR_HIP; }
+    if (colour == 0) { image_buffers_free(image_group(c, IMG_COLOUR), c->stream); im.bgr_pix = 0; }      // the transit buffer
+    return SRUKF_OK;
+}
+
+int srukf_stage_images(srukf_ctx* c, int F, const unsigned char* gray)
+{
+    if (!c || F < 1 || !gray) return SRUKF_ERR_BAD_ARG;
+    return stage_images_any(c, F, gray, -1, "stage_images");
+}
+
+// loadPictures (SLAM.cpp:529-543) for the whole stack: F colour frames become the staged gray frames, by srukf_set_frame_bgr's rule (k_bgr2gray), and with
+// keep_colour the colour stack stays beside them as the overlays' source.  Behind the call the handle is what srukf_stage_images with the converted bytes leaves;
+// the held frame (d_image, d_bgr) is neither read nor written
+int srukf_stage_images_bgr(srukf_ctx* c, int F, const unsigned char* bgr, int keep_colour)
+{
+    if (!c || F < 1 || !bgr || (keep_colour != 0 && keep_colour != 1)) return SRUKF_ERR_BAD_ARG;
+    return stage_images_any(c, F, bgr, keep_colour, "stage_images_bgr");
+}
+
+// frame `frame` of the staged stack: its gray bytes and, from a kept colour stack, its colour bytes.  Waits for the stream
+int srukf_get_staged_image(srukf_ctx* c, int frame, unsigned char* gray_out, unsigned char* bgr_out)
+{
+    if (!c || frame < 0 || (!gray_out && !bgr_out)) return SRUKF_ERR_BAD_ARG;
+    const ImageReplay& im = c->img;
+    if (!im.images) { c->err = "get_staged_image: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (frame >= im.frames) { c->err = "get_staged_image: frame outside the staged images"; return SRUKF_ERR_BAD_ARG; }
+    if (bgr_out && !im.bgr_kept) { c->err = "get_staged_image: no colour stack is kept (srukf_stage_images_bgr with keep_colour)"; return SRUKF_ERR_SEQUENCE; }
+    const size_t img = (size_t)c->p.image_w * (size_t)c->p.image_h, f = (size_t)frame;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (gray_out) HIPCHK(c, hipMemcpy(gray_out, im.images + f * img, img, hipMemcpyDeviceToHost));
+    if (bgr_out) HIPCHK(c, hipMemcpy(bgr_out, im.bgr + 3 * f * img, 3 * img, hipMemcpyDeviceToHost));
     return SRUKF_OK;
 }
 
@@ -744,20 +802,31 @@ int srukf_get_image_display(srukf_ctx* c, int first, int count, double* xyz, dou
 
 // display2DFeatureModel + draw2DEllipse (SLAM.cpp:3009-3083) for staged frame `frame`, from what the device holds and with nothing uploaded: srukf_render_overlay's
 // two launches on the frame's rows of h_seq, the display record's Si, z_seq and m_seq (behind a consensus run the masked row: what the filter used), over the
-// frame's place in the staged stack, gray byte three times.  Which rows are drawable is the host's mark per row (ImageReplay::dp_rows): set when a run with the
+// frame's place in the staged stack, gray byte three times (srukf_stage_images).  Which rows are drawable is the host's mark per row (ImageReplay::dp_rows): set when a run with the
 // display switch issues the row's launches, cleared when images_restore zeroes the row.  It writes the overlay's own buffers (ov_rec, d_ovl) only.
 // (k_overlay reads the gray frame in dwords: a stack whose frames are no multiple of four bytes has frames that do not start on one)
+// With a kept colour stack (srukf_stage_images_bgr) the frame's colour bytes are the source instead.
+// The refusals of both overlay calls, in one order: frames [first, first + count) must lie in the stack and every one of them be drawable
+static int image_overlay_front(srukf_ctx* c, const char* who, int first, int count)
+{
+    const ImageReplay& im = c->img;
+    const std::string w = who;
+    if (!im.images) { c->err = w + ": no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
+    if (first >= im.frames || count > im.frames - first) { c->err = w + ": frame outside the staged images"; return SRUKF_ERR_BAD_ARG; }
+    for (int q = first; q < first + count; q++)
+        if (!im.dp_rec || !im.dp_rows[(size_t)q]) { c->err = w + ": no run with srukf_images_display on has written that frame's row (frame " + std::to_string(q) + ")"; return SRUKF_ERR_SEQUENCE; }
+    const int W = (int)c->p.image_w, H = (int)c->p.image_h;
+    if (W < 1 || H < 1 || (double)W * H > 268435456.0) { c->err = w + ": image size"; return SRUKF_ERR_BAD_ARG; }
+    if ((W * H) % 4) { c->err = w + ": image_w * image_h must be a multiple of four"; return SRUKF_ERR_UNSUPPORTED; }
+    return SRUKF_OK;
+}
+
 int srukf_render_image_overlay(srukf_ctx* c, int frame, unsigned char* out_bgr)
 {
     if (!c || !out_bgr || frame < 0) return SRUKF_ERR_BAD_ARG;
+    { const int rc = image_overlay_front(c, "render_image_overlay", frame, 1); if (rc) return rc; }
     const ImageReplay& im = c->img;
-    if (!im.images) { c->err = "render_image_overlay: no staged images (srukf_stage_images)"; return SRUKF_ERR_SEQUENCE; }
-    if (frame >= im.frames) { c->err = "render_image_overlay: frame outside the staged images"; return SRUKF_ERR_BAD_ARG; }
-    if (!im.dp_rec || !im.dp_rows[(size_t)frame]) { c->err = "render_image_overlay: no run with srukf_images_display on has written that frame's row"; return SRUKF_ERR_SEQUENCE; }
-    const int W = (int)c->p.image_w, H = (int)c->p.image_h, N = c->d.N;
-    if (W < 1 || H < 1 || (double)W * H > 268435456.0) { c->err = "render_image_overlay: image size"; return SRUKF_ERR_BAD_ARG; }
-    const int npix = W * H;
-    if (npix % 4) { c->err = "render_image_overlay: image_w * image_h must be a multiple of four"; return SRUKF_ERR_UNSUPPORTED; }
+    const int W = (int)c->p.image_w, H = (int)c->p.image_h, N = c->d.N, npix = W * H;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!c->d_ovl) HIPCHK(c, srukf_dmalloc((void**)&c->d_ovl, overlay_bgr_bytes(npix)));
@@ -765,13 +834,45 @@ int srukf_render_image_overlay(srukf_ctx* c, int frame, unsigned char* out_bgr)
     const size_t f = (size_t)frame, n = (size_t)N;
     const ImageDisplayRow r = image_display_row(n);
     {
-        ProfScope ps(c, KC_OVERLAY, 0, 4.0 * npix);
+        ProfScope ps(c, KC_OVERLAY, 0, (im.bgr_kept ? 6.0 : 4.0) * npix);
         // (z_seq / m_seq: the staged sequence's own rows, srukf_stage_sequence)
         launch_overlay(c->stream, W, H, N, image_row(image_group(c, IMG_STAGED), &im.h_seq, f), image_row(image_group(c, IMG_DISPLAY), &im.dp_rec, f) + r.Si, c->z_seq + f * 2 * n, c->m_seq + f * n, c->ov_rec,
-                       nullptr, im.images + f * (size_t)npix, c->d_ovl);
+                       im.bgr_kept ? im.bgr + f * 3 * (size_t)npix : nullptr, im.images + f * (size_t)npix, c->d_ovl);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out_bgr, c->d_ovl, 3 * (size_t)npix, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                  // (out_bgr is pageable host memory)
+    return SRUKF_OK;
+}
+
+// srukf_render_image_overlay for frames [first, first + count) in two launches and one copy: out_bgr holds count tight frames, frame
+// first + q of it byte for byte the single call's.  A row of the range that is not drawable refuses the whole call and leaves out_bgr untouched.  The scratch
+// (count output frames and record slabs) is a group of image_group that grows to the largest count asked for
+int srukf_render_image_overlays(srukf_ctx* c, int first, int count, unsigned char* out_bgr)
+{
+    if (!c || !out_bgr || first < 0 || count < 1) return SRUKF_ERR_BAD_ARG;
+    { const int rc = image_overlay_front(c, "render_image_overlays", first, count); if (rc) return rc; }
+    if (count > OVERLAY_BLOCK_MAX) { c->err = "render_image_overlays: more than 65535 frames in one call"; return SRUKF_ERR_UNSUPPORTED; }
+    ImageReplay& im = c->img;
+    const int W = (int)c->p.image_w, H = (int)c->p.image_h, N = c->d.N, npix = W * H;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (count > im.ovs_count) {
+        image_buffers_free(image_group(c, IMG_OVERLAYS), c->stream);
+        im.ovs_count = count;
+        const int rc = image_buffers_alloc(c, image_group(c, IMG_OVERLAYS, (size_t)npix), "render_image_overlays");
+        if (rc) { im.ovs_count = 0; return rc; }
+    }
+    const size_t f = (size_t)first, n = (size_t)N, m = (size_t)count;
+    const std::vector<ImageBuf> staged = image_group(c, IMG_STAGED), display = image_group(c, IMG_DISPLAY);
+    {
+        ProfScope ps(c, KC_OVERLAY, 0, (im.bgr_kept ? 6.0 : 4.0) * npix * m);
+        launch_overlay_block(c->stream, W, H, N, count, image_row(staged, &im.h_seq, f), image_col(staged, &im.h_seq).row / sizeof(double),
+                             image_row(display, &im.dp_rec, f) + image_display_row(n).Si, image_col(display, &im.dp_rec).row / sizeof(double), c->z_seq + f * 2 * n, 2 * n,
+                             c->m_seq + f * n, n, im.ovs_rec, im.bgr_kept ? im.bgr + f * 3 * (size_t)npix : nullptr, im.images + f * (size_t)npix, im.ovs_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out_bgr, im.ovs_out, m * 3 * (size_t)npix, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                  // (out_bgr is pageable host memory)
     return SRUKF_OK;
 }

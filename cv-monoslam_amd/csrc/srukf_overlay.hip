@@ -6,6 +6,10 @@
 //                 larger eigenvalue -> one OvRec.  fp64 + - * / sqrt in the order written, no contraction (-ffp-contract=off): tests/np_overlay.py restates it.
 // k_overlay       one workgroup per tile of 1024 pixels; the source pixel, then every landmark whose boxes meet the tile, in state order, later over earlier and
 //                 within a landmark predicted cross, matched cross, ellipse.  Every pixel has one owner: no atomics, nothing depends on scheduling.
+// k_overlay_prep_block / k_overlay_block  the same two for a run of staged frames, the frame a grid dimension (srukf_render_image_overlays).
+//                 They call the bodies the single-frame kernels call (ov_prep_one, ov_raster_tile): the painted bytes are equal by construction.
+// A stack of colour frames needs no kernel of its own: frames are tight in both stacks (3 W H and W H bytes), so F frames are ONE run of F W H pixels to k_bgr2gray,
+// whose groups of four are dword-aligned from the start of the stack whatever W H is (srukf_stage_images_bgr walks the run in chunks that are multiples of four).
 //
 // The frames have no row padding, so both pixel kernels walk the frame as ONE run of W H pixels in groups of four: 12 colour bytes = three dwords, 4 gray bytes =
 // one dword, every group dword-aligned whatever W is (a row-based split would be aligned only when W is a multiple of four).  A group may straddle two rows; each
@@ -54,11 +58,11 @@ __global__ __launch_bounds__(OV_THREADS) void k_bgr2gray(int npix, const unsigne
     }
 }
 
-__global__ __launch_bounds__(64) void k_overlay_prep(int N, const double* __restrict__ h, const double* __restrict__ Si, const double* __restrict__ z,
-                                                     const int* __restrict__ matched, OvRec* __restrict__ rec)
+namespace {
+
+// landmark k's record: the body of both prep kernels
+__device__ __forceinline__ OvRec ov_prep_one(int k, const double* __restrict__ h, const double* __restrict__ Si, const double* __restrict__ z, const int* __restrict__ matched)
 {
-    const int k = blockIdx.x * 64 + threadIdx.x;
-    if (k >= N) return;
     OvRec r;
     r.flags = 0; r.px = r.py = r.mx = r.my = 0; r.a = r.b = 1; r.pad_ = 0; r.c = 1.0; r.s = 0.0;
     const double hx = h[2 * k], hy = h[2 * k + 1], zx = z[2 * k], zy = z[2 * k + 1];
@@ -85,18 +89,17 @@ __global__ __launch_bounds__(64) void k_overlay_prep(int N, const double* __rest
             }
         }
     }
-    rec[k] = r;
+    return r;
 }
 
-__global__ __launch_bounds__(OV_THREADS) void k_overlay(int W, int npix, int N, const unsigned int* __restrict__ bgr, const unsigned char* __restrict__ gray,
-                                                        const OvRec* __restrict__ rec, unsigned int* __restrict__ out)
+// tile `tile` of one frame: the body of both raster kernels.  list [OV_CHUNK] and nlist are the calling kernel's own LDS
+__device__ __forceinline__ void ov_raster_tile(OvRec* list, int& nlist, int tile, int W, int npix, int N, const unsigned int* __restrict__ bgr,
+                                               const unsigned char* __restrict__ gray, const OvRec* __restrict__ rec, unsigned int* __restrict__ out)
 {
-    __shared__ OvRec list[OV_CHUNK];
-    __shared__ int nlist;
-    const int tile0 = blockIdx.x * OV_TILE, tile1 = min(tile0 + OV_TILE, npix) - 1;            // first and last pixel of the tile (tile0 < npix by the grid)
+    const int tile0 = tile * OV_TILE, tile1 = min(tile0 + OV_TILE, npix) - 1;                  // first and last pixel of the tile (tile0 < npix by the grid)
     const int ty0 = tile0 / W, ty1 = tile1 / W;
     const int tx0 = ty0 == ty1 ? tile0 - ty0 * W : 0, tx1 = ty0 == ty1 ? tile1 - ty1 * W : W - 1;
-    const int g = blockIdx.x * OV_THREADS + threadIdx.x, p0 = 4 * g;
+    const int g = tile * OV_THREADS + threadIdx.x, p0 = 4 * g;
     const bool live = p0 < npix;
     // the source: the held colour frame, or the gray byte three times.  col[j] = B | G << 8 | R << 16
     unsigned col[4] = { 0, 0, 0, 0 };
@@ -175,6 +178,44 @@ __global__ __launch_bounds__(OV_THREADS) void k_overlay(int W, int npix, int N, 
     }
 }
 
+}  // namespace
+
+__global__ __launch_bounds__(64) void k_overlay_prep(int N, const double* __restrict__ h, const double* __restrict__ Si, const double* __restrict__ z,
+                                                     const int* __restrict__ matched, OvRec* __restrict__ rec)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k < N) rec[k] = ov_prep_one(k, h, Si, z, matched);
+}
+
+__global__ __launch_bounds__(OV_THREADS) void k_overlay(int W, int npix, int N, const unsigned int* __restrict__ bgr, const unsigned char* __restrict__ gray,
+                                                        const OvRec* __restrict__ rec, unsigned int* __restrict__ out)
+{
+    __shared__ OvRec list[OV_CHUNK];
+    __shared__ int nlist;
+    ov_raster_tile(list, nlist, blockIdx.x, W, npix, N, bgr, gray, rec, out);
+}
+
+// The two kernels for a run of staged frames: blockIdx.y is the frame.  Frame q reads its own rows (strides in elements), writes its own slab of N records, and the
+// raster reads frame q's source and writes frame q's output.  npix is a multiple of four (srukf_render_image_overlays refuses anything else), so every frame of the
+// tight stacks starts on a dword: 3 npix / 4 dwords of colour and of output per frame, npix bytes of gray
+struct OvBlockRows { const double *h, *Si, *z; const int* matched; size_t h_stride, Si_stride, z_stride, m_stride; };
+
+__global__ __launch_bounds__(64) void k_overlay_prep_block(int N, OvBlockRows rows, OvRec* __restrict__ rec)
+{
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    const size_t q = blockIdx.y;
+    if (k < N) rec[q * (size_t)N + k] = ov_prep_one(k, rows.h + q * rows.h_stride, rows.Si + q * rows.Si_stride, rows.z + q * rows.z_stride, rows.matched + q * rows.m_stride);
+}
+
+__global__ __launch_bounds__(OV_THREADS) void k_overlay_block(int W, int npix, int N, const unsigned int* __restrict__ bgr, const unsigned char* __restrict__ gray,
+                                                              const OvRec* __restrict__ rec, unsigned int* __restrict__ out)
+{
+    __shared__ OvRec list[OV_CHUNK];
+    __shared__ int nlist;
+    const size_t q = blockIdx.y, dwords = 3 * ((size_t)npix / 4);
+    ov_raster_tile(list, nlist, blockIdx.x, W, npix, N, bgr ? bgr + q * dwords : nullptr, gray + q * (size_t)npix, rec + q * (size_t)N, out + q * dwords);
+}
+
 namespace srukf_impl {
 
 size_t overlay_rec_bytes(int N) { return sizeof(OvRec) * (size_t)(N > 0 ? N : 1); }
@@ -193,6 +234,19 @@ void launch_overlay(hipStream_t st, int W, int H, int N, const double* h, const 
     const int npix = W * H;
     if (N > 0) hipLaunchKernelGGL(k_overlay_prep, dim3((N + 63) / 64), dim3(64), 0, st, N, h, Si, z, matched, (OvRec*)rec);
     hipLaunchKernelGGL(k_overlay, dim3((npix + OV_TILE - 1) / OV_TILE), dim3(OV_THREADS), 0, st, W, npix, N, (const unsigned int*)bgr, gray, (const OvRec*)rec,
+                       (unsigned int*)out);
+}
+
+// count staged frames in two launches.  Every pointer is the first frame's; the strides of the rows are in elements, the stacks are tight (bgr and out: 3 npix
+// bytes per frame, gray: npix), rec holds count slabs of N records.  W H is a multiple of four, N >= 1 and 1 <= count <= OVERLAY_BLOCK_MAX: the frame is
+// gridDim.y (srukf_render_image_overlays refuses a larger count)
+void launch_overlay_block(hipStream_t st, int W, int H, int N, int count, const double* h, size_t h_stride, const double* Si, size_t Si_stride, const double* z, size_t z_stride,
+                          const int* matched, size_t m_stride, void* rec, const unsigned char* bgr, const unsigned char* gray, unsigned char* out)
+{
+    const int npix = W * H;
+    const OvBlockRows rows = { h, Si, z, matched, h_stride, Si_stride, z_stride, m_stride };
+    hipLaunchKernelGGL(k_overlay_prep_block, dim3((N + 63) / 64, count), dim3(64), 0, st, N, rows, (OvRec*)rec);
+    hipLaunchKernelGGL(k_overlay_block, dim3((npix + OV_TILE - 1) / OV_TILE, count), dim3(OV_THREADS), 0, st, W, npix, N, (const unsigned int*)bgr, gray, (const OvRec*)rec,
                        (unsigned int*)out);
 }
 

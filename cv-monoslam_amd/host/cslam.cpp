@@ -1086,11 +1086,18 @@ void CSLAM::SLAM()
 //  and the block also stops IN FRONT OF the first frame whose consensus dropped a match: its rescue step is SLAM()'s — with rescueGateOnDevice
 //  in front of the first frame that would rescue one, and a frame whose dropped matches stay dropped is consumed.  gray: F frames of image_h x image_w, frame f for
 // m_frame.counter + f.  Returns the frames consumed, or 0 with nothing done where a block cannot stand for SLAM(): the caller then calls SLAM() for the frame.
-int CSLAM::SLAMBlock(const unsigned char* gray, int F)
+int CSLAM::SLAMBlock(const unsigned char* gray, int F) { return slamBlock(gray, F, false); }
+
+// The same for the frames cvQueryFrame / cvLoadImage deliver: bgr = F frames of image_h x image_w x 3 bytes, B, G, R.  The device makes of them
+// what loadPictures makes (srukf_stage_images_bgr); with blockDisplay the colour stack stays and the overlays are drawn on it
+int CSLAM::SLAMBlockColour(const unsigned char* bgr, int F) { return slamBlock(bgr, F, true); }
+
+// the one body behind both: frames = gray, or with colour the B, G, R frames
+int CSLAM::slamBlock(const unsigned char* frames, int F, bool colour)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const int N = m_nMapFeatures, c0 = m_frame.counter;
-    if (!ctx_ || !gray || N < 1 || c0 < 1) return 0;
+    if (!ctx_ || !frames || N < 1 || c0 < 1) return 0;
     if (c0 + F > m_odoCounter) F = m_odoCounter - c0;
     if (c0 + F > CAPACITY + 1) F = CAPACITY + 1 - c0;
     if (F < 1) return 0;
@@ -1103,7 +1110,7 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     std::vector<int> m0((size_t)F * N, 0);
     for (int f = 0; f <= F; f++) { const int c = c0 - 1 + f; odo[3 * f] = m_odoXY[2 * c]; odo[3 * f + 1] = m_odoXY[2 * c + 1]; odo[3 * f + 2] = m_odoTheta.at(1, c); }
     if (!check(srukf_stage_sequence(ctx_, F, odo.data(), z0.data(), m0.data()))) return 0;
-    int rc = srukf_stage_images(ctx_, F, gray);
+    int rc = colour ? srukf_stage_images_bgr(ctx_, F, frames, blockDisplay ? 1 : 0) : srukf_stage_images(ctx_, F, frames);
     if (rc == SRUKF_ERR_UNSUPPORTED) return 0;
     if (!check(rc)) return 0;
     // 2. the counters map[] holds
@@ -1119,7 +1126,7 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
     snapshotsSet_ = resumeStoppedBlocks;
     if ((blockDisplay || displaySet_) && !check(srukf_images_display(ctx_, blockDisplay ? 1 : 0))) return 0;                // the display view behind every frame
     displaySet_ = blockDisplay;
-    m_blockDisplay.clear(); m_blockDisplayIDs.clear();
+    m_blockDisplay.clear(); m_blockDisplayIDs.clear(); m_blockOverlays.clear();
     // 3. one image block in jointUpdate's mode, checked with the switches of associateChecked
     const int mode = jointUpdate ? SRUKF_UPDATE_JOINT : SRUKF_UPDATE_BATCHED;
     const bool checked = rejectAmbiguousMatches || subpixelMatches;
@@ -1183,6 +1190,14 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
             m_srcImage.resize(3 * img);
             if (!check(srukf_render_image_overlay(ctx_, used - 1, m_srcImage.data()))) return 0;
         }
+        if (blockOverlayAll) {                                                                                  // every consumed frame's, in one device call
+            m_blockOverlays.resize(U * 3 * img);
+            if (!check(srukf_render_image_overlays(ctx_, 0, used, m_blockOverlays.data()))) return 0;
+        }
+    }
+    if (colour) {                                                                                               // the gray frame the tail reads, as loadPictures leaves it; read
+        m_grayStore.resize(img);                                                                                // here, where a refusal still leaves the facade as it was
+        if (!check(srukf_get_staged_image(ctx_, used - 1, m_grayStore.data(), nullptr))) return 0;
     }
     const int n = m_X_k.rows;
     m_blockPath.assign(traj.begin(), traj.begin() + 8 * (size_t)used);
@@ -1222,7 +1237,8 @@ int CSLAM::SLAMBlock(const unsigned char* gray, int F)
         }
     }
     // 7. the last consumed frame: SLAM()'s own tail on that frame (997-1010)
-    m_gryImage = gray + (size_t)(used - 1) * img; frameHeld_ = false;
+    m_gryImage = colour ? m_grayStore.data() : frames + (size_t)(used - 1) * img;                              // (colour: read back in front of step 6)
+    frameHeld_ = false;
     updateFeaturesInformation();
     refreshMirrors();
     {

@@ -121,13 +121,20 @@ public:
     // its gray image, image_h x image_w x 3 bytes (srukf_render_image_overlay); false where no block with blockDisplay has consumed that frame, or the map has
     // changed since — the last frame's tail may change it, so with blockOverlayLast SLAMBlock itself leaves the last consumed frame's overlay in m_srcImage, drawn
     // in front of that tail.  Off and never on: exactly the calls above
+    // SLAMBlockColour: SLAMBlock for the frames the reference's host has — bgr = F frames of image_h x image_w x 3 bytes, B, G, R, as
+    // cvQueryFrame / cvLoadImage deliver them.  The device converts them as loadPictures does (srukf_stage_images_bgr) and, with blockDisplay, keeps the colour
+    // stack: the overlays are then drawn on the colour frames.  The tail's gray frame is read back into m_grayStore, which m_gryImage then points at.
+    // blockOverlayAll (with blockDisplay): either call leaves the overlays of all consumed frames in m_blockOverlays, `used` tight frames of
+    // image_h x image_w x 3 bytes from one srukf_render_image_overlays, drawn where blockOverlayLast draws.  Off: exactly the calls above
     int  SLAMBlock(const unsigned char* gray, int F);
+    int  SLAMBlockColour(const unsigned char* bgr, int F);
     struct BlockDisplayFrame {
         std::vector<double> xyz, cov, axis, sigma, Si;         // [3N], [9N], [4N] (quaternion r, x, y, z), [3N], [4N]
         std::vector<int> rot;                                  // [N]
         double pose[4], P4[16];
     };
-    bool blockDisplay = false, blockOverlayLast = false;
+    bool blockDisplay = false, blockOverlayLast = false, blockOverlayAll = false;
+    std::vector<unsigned char> m_blockOverlays;                // the last block's overlays, one per consumed frame (blockOverlayAll; empty without)
     std::vector<BlockDisplayFrame> m_blockDisplay;             // the last SLAMBlock's display view per consumed frame (blockDisplay; empty without)
     std::vector<int> m_blockDisplayIDs;                        // ... and the block's landmark IDs in state order
     bool renderBlockOverlay(int f, unsigned char* out_bgr);
@@ -351,6 +358,7 @@ private:
     void refreshMirrors();
     bool check(int rc);
     srukf_ctx* ctx_ = nullptr;
+    int  slamBlock(const unsigned char* frames, int F, bool colour);      // the one body behind SLAMBlock and SLAMBlockColour
     bool displaySet_ = false;            // srukf_images_display is on on the handle (SLAMBlock switches it off again when blockDisplay goes off)
     bool rescueSet_ = false;             // srukf_images_rescue_gate is on on the handle (SLAMBlock switches it off again when rescueGateOnDevice or isUseRANSAC goes off)
     bool snapshotsSet_ = false;          // srukf_images_snapshots is on on the handle (SLAMBlock switches it off again when resumeStoppedBlocks goes off)

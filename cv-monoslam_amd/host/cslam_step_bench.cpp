@@ -42,6 +42,10 @@
 //              display=1 (assoc_replay only): the blocks run with srukf_images_display on: every frame is followed by k_image_view + k_lm_ellipsoid and
 //              the run is issued frame by frame.  This measures the switch's price: with policy=1 the two launches alone, without it also the eight-frame graphs the
 //              run gives up.  Adds "display": 1 to the output
+//              colour=1 (assoc_replay only): the frames are staged as B = G = R colour frames through srukf_stage_images_bgr (the conversion keeps such
+//              a frame byte for byte, so the run is the gray one's).  Adds "staging_ms": the wall time of srukf_stage_images on the gray stack, of the same
+//              conversion done on the host in front of it, and of srukf_stage_images_bgr with keep_colour 0 and 1 (the last one stays staged), each for the
+//              W + K frames of the run
 //              profile=1 (assoc_replay only): the timed blocks run with srukf_set_profiling on (eager launches); adds "profile_ms_per_frame" by kernel class
 //     hint=1 : capi / assoc announce the NEXT frame's odometry with srukf_predict_motion_next before every update (a host that has its odometry
 //              file loaded, as the reference has: loadOdometryData reads it whole, SLAM.cpp:363-496)
@@ -92,6 +96,7 @@ int main(int argc, char** argv)
     int rescue = 0; long long rq_high = 0;                              // rescue=1 (assoc_replay with ransac=)
     int resume = -1, stop_k = 0; long long stop_blocks = 0;      // resume= / stop= (assoc_replay)
     int display = 0;      // display= (assoc_replay)
+    int colour = 0; char col_json[240] = "";      // colour= (assoc_replay)
     int drop = 1, together = 0; long long landmarks_deleted = 0;      // drop= / together= (facade with churn=)
     std::vector<std::pair<std::string, int>> sets;
     for (int a = 3; a < argc; a++) {
@@ -113,6 +118,7 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "resume=", 7)) resume = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "stop=", 5)) stop_k = atoi(argv[a] + 5);
         else if (!strncmp(argv[a], "display=", 8)) display = atoi(argv[a] + 8) != 0;
+        else if (!strncmp(argv[a], "colour=", 7)) colour = atoi(argv[a] + 7) != 0;
         else if (!strncmp(argv[a], "drop=", 5)) drop = atoi(argv[a] + 5);
         else if (!strncmp(argv[a], "together=", 9)) together = atoi(argv[a] + 9) != 0;
         else if (!strncmp(argv[a], "subpix=", 7)) { if (atoi(argv[a] + 7)) { checked = true; mpar.subpixel = 1; } }
@@ -145,7 +151,7 @@ int main(int argc, char** argv)
     long long flag_ticks = -1;                                       // last frame: start of the frame's first launch -> h / Si / visible flagged to the host (10 ns ticks)
     char churn_json[900] = "";
     char ell_json[200] = "";
-    char prof_json[1600] = "", arc_json[200] = "", pol_json[520] = "";
+    char prof_json[1600] = "", arc_json[200] = "", pol_json[760] = "";
     int joint_flagged = 0;
     const char* replay_form = "run_frames_async + synchronize";
     int flagged_blocks = 0;
@@ -154,6 +160,7 @@ int main(int argc, char** argv)
     if ((arcL || arc_step || profile || policy) && !areplay) { fprintf(stderr, "archive= / archive_step= / profile= / policy= belong to mode=assoc_replay\n"); return 2; }
     if (arcL < 0 || arcL > 64 || (arc_step && !arcL)) { fprintf(stderr, "archive=<L>: 1 <= L <= 64 (archive_step=1 needs it)\n"); return 2; }
     if (display && !areplay) { fprintf(stderr, "display= belongs to mode=assoc_replay\n"); return 2; }
+    if (colour && !areplay) { fprintf(stderr, "colour= belongs to mode=assoc_replay\n"); return 2; }
     if ((resume >= 0 || stop_k) && !areplay) { fprintf(stderr, "resume= / stop= belong to mode=assoc_replay\n"); return 2; }
     if (stop_k && (resume < 0 || stop_k < 1 || stop_k >= block_frames || arcL || profile)) { fprintf(stderr, "stop=<k> needs resume=0|1 and 0 < k < block, without archive= and profile=\n"); return 2; }
     const int legs = stop_k ? 2 : 1;                                // stop=: both routes, the one asked for last (it is the one reported)
@@ -353,7 +360,22 @@ int main(int argc, char** argv)
                 CK(srukf_stage_sequence(c, W + K, odo.data(), z0.data(), m0.data()));
                 std::vector<unsigned char> stack((size_t)(W + K) * img);
                 for (int fr = 0; fr < W + K; fr++) memcpy(stack.data() + (size_t)fr * img, gray.data(), img);
+                auto ms = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count() * 1e3; };
+                auto ta = std::chrono::steady_clock::now();
                 CK(srukf_stage_images(c, W + K, stack.data()));
+                const double t_gray = ms(ta);
+                if (colour) {
+                    std::vector<unsigned char> bgr(3 * stack.size()), back(stack.size());
+                    for (size_t q = 0; q < stack.size(); q++) bgr[3 * q] = bgr[3 * q + 1] = bgr[3 * q + 2] = stack[q];
+                    ta = std::chrono::steady_clock::now();                   // what a host without the call does: loadPictures' rule on the CPU
+                    for (size_t q = 0; q < stack.size(); q++) back[q] = (unsigned char)((4899u * bgr[3 * q] + 9617u * bgr[3 * q + 1] + 1868u * bgr[3 * q + 2] + 8192u) >> 14);
+                    const double t_host = ms(ta);
+                    if (back != stack) { fprintf(stderr, "colour=1: the host conversion changed a B = G = R frame\n"); return 3; }
+                    double t_bgr[2];
+                    for (int keep = 0; keep < 2; keep++) { ta = std::chrono::steady_clock::now(); CK(srukf_stage_images_bgr(c, W + K, bgr.data(), keep)); t_bgr[keep] = ms(ta); }
+                    snprintf(col_json, sizeof col_json, "\"staging_ms\": {\"frames\": %d, \"stage_images\": %.3f, \"host_conversion\": %.3f, \"stage_images_bgr_keep0\": %.3f, \"stage_images_bgr_keep1\": %.3f}, ",
+                             W + K, t_gray, t_host, t_bgr[0], t_bgr[1]);
+                }
             }
             if (arcL) {
                 // the archive: arcL landmarks created on a context of their own at the robot's start state, at the grid pixels farthest from every landmark's first
@@ -542,6 +564,7 @@ int main(int argc, char** argv)
                                               ransac_thr, rs_outlier, rs_low);
     if (areplay && resume >= 0) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"resume\": %d, ", resume);
     if (areplay && display) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"display\": 1, ");
+    if (colour) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "%s", col_json);
     if (stop_k) snprintf(pol_json + strlen(pol_json), sizeof pol_json - strlen(pol_json), "\"stop\": {\"k\": %d, \"resume\": %d, \"blocks\": %lld, \"poses_equal\": 1}, ", stop_k, resume, stop_blocks);
     if (mode == "replay") snprintf(joint_json + strlen(joint_json), sizeof joint_json - strlen(joint_json), "\"replay_form\": \"%s\", \"exact_frames\": %d, ", replay_form, joint_flagged);
     printf("{\"mode\": \"%s\", %s%s%s%s%s%s\"hint\": %d, \"landmarks\": %d, \"frames\": %d, \"warmup\": %d, \"frames_per_s\": %.2f, \"us_per_frame\": %.2f, "

@@ -1,7 +1,7 @@
 // cslam_vision — C++ host that runs the CSLAM facade as the reference runs: gray frame in, pose out.  The host points m_gryImage at each
 // frame and installs no addFeatures callback, so SLAM() finds new landmarks on the device (detectAndfilteringFeatures / insureEnoughFeatures
 // -> integrateFeaturesInformation -> srukf_capture_appearance) and associates them on the device (dataAssociationOnDevice).
-//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>] [together=1]
+//   cslam_vision frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1|2] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>] [overlays=<file>] [together=1]
 // frames.bin: int32 W, int32 H, int32 F, then F frames of H x W uint8.  Frame f of the loop (0-based) sees image f % F.
 // redirect=<counter>: flags that odometry sample as a heading jump: predictMotion takes the redirection restart (SLAM.cpp:1354-1428), whose
 //   addFeatures runs with isAdding (archived features projected, empty map).
@@ -18,6 +18,9 @@
 // joint=1: CSLAM::jointUpdate (every update of the frame is the joint measurement update).  Adds, and only with it, a last line "joint flagged <n>".
 // colour=1: every gray frame is fed as a B = G = R colour frame through CSLAM::loadPictures (srukf_set_frame_bgr) and associated on the held frame
 //   (dataAssociationOnDeviceHeld).  The conversion keeps such a frame byte for byte (the weights sum to 2^14), so the output equals the default run's.
+//   With block=<F> the blocks' frames go the same way through CSLAM::SLAMBlockColour.
+// colour=2: frames.bin holds B, G, R frames, F frames of H x W x 3 uint8, as cvQueryFrame / cvLoadImage deliver them.  Step-wise they go through
+//   CSLAM::loadPictures, with block=<F> through CSLAM::SLAMBlockColour; the output is that of the run on the frames loadPictures makes of them.
 // overlay=<file>: after the last frame, CSLAM::display2DFeatureModel's bytes (H x W x 3, B G R) go to <file> and the rows they were drawn from to <file>.in:
 //   per map node "h.x h.y Si00 Si01 Si10 Si11 z.x z.y matched" (%a).  Nothing else changes.
 // unique=<ratio>[,<exclusion>]: CSLAM::rejectAmbiguousMatches on (AMBIGUITY_RATIO = ratio, AMBIGUITY_EXCLUSION = exclusion, default 4).  Adds, and
@@ -38,6 +41,9 @@
 //   behind that frame's tail, one line "frame ID" and xyz, cov, axis, sigma as %a (a NaN as "nan" whatever its sign): for the last consumed frame of a block (and
 //   every frame of block=1) from map[], for the frames in front of it from m_blockDisplay.  The same file through either route.  With overlay=<file> the overlay of
 //   the last block's last consumed frame goes to <file> (CSLAM::blockOverlayLast: drawn in front of that frame's tail); stdout is what it is without both.
+// overlays=<file> (with block=<F> display=<file>): CSLAM::blockOverlayAll on: the overlay of every frame a block consumed is appended to <file>,
+//   H x W x 3 bytes each, in frame order (frames SLAM() ran are not among them); with colour= they are drawn on the colour frames.  Adds, and only with it, a
+//   last line "overlay_frames" with the frames whose overlays the file holds.
 // together=1: CSLAM::deleteTogether on: the landmarks a frame's updateFeaturesInformation deletes leave in one device call.  Every line is what it
 //   is without it (the pose and covariance figures within rounding when a frame deletes more than one landmark).
 // set=key:value: srukf_debug_set(NULL, key, value) for a process-wide measurement switch (set=timing:1: the phases of every map change on stderr).
@@ -54,15 +60,19 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>] [min_matches=<n>] [together=1]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s frames.bin odometry.txt [redirect=<counter>] [warmup] [loops] [archive=<half_cap>] [ransac=<threshold>] [colour=1|2] [overlay=<file>] [unique=<ratio>[,<exclusion>]] [subpix=1] [joint=1] [block=<F>] [resume=1] [rescue=1] [display=<file>] [overlays=<file>] [min_matches=<n>] [together=1]\n", argv[0]); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     int W = 0, H = 0, F = 0;
     if (fread(&W, 4, 1, f) != 1 || fread(&H, 4, 1, f) != 1 || fread(&F, 4, 1, f) != 1 || W < 8 || H < 8 || F < 1) { fprintf(stderr, "bad frames file\n"); return 2; }
-    std::vector<unsigned char> frames((size_t)W * H * F);
+    int colour = 0;                                                                          // (colour=2 says what the file holds: before it is read)
+    for (int a = 3; a < argc; a++) if (!strncmp(argv[a], "colour=", 7)) colour = atoi(argv[a] + 7);
+    if (colour < 0 || colour > 2) { fprintf(stderr, "colour=1 or colour=2\n"); return 2; }
+    const size_t fb = (size_t)W * H * (colour == 2 ? 3 : 1);                                 // bytes of one frame of the file
+    std::vector<unsigned char> frames(fb * F);
     if (fread(frames.data(), 1, frames.size(), f) != frames.size()) { fprintf(stderr, "short frames file\n"); return 2; }
     fclose(f);
-    int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false, colour = false; double ransacThr = 8.0; std::string overlay, display;
+    int redirect = 0, archiveCap = 0; bool warmup = false, loops = false, ransac = false; double ransacThr = 8.0; std::string overlay, display, overlays;
     bool unique = false, subpix = false, joint = false, resume = false, rescue = false; double uniqueRatio = 0.9; int uniqueExcl = 4;
     bool together = false;
     int minMatches = 0, block = 0, nBlocks = 0, nEarly = 0, nFull = 0, nFallback = 0;
@@ -70,7 +80,8 @@ int main(int argc, char** argv)
         if (!strncmp(argv[a], "redirect=", 9)) redirect = atoi(argv[a] + 9); else if (!strcmp(argv[a], "warmup")) warmup = true; else if (!strcmp(argv[a], "loops")) loops = true;
         else if (!strncmp(argv[a], "archive=", 8)) { archiveCap = atoi(argv[a] + 8); loops = true; }
         else if (!strncmp(argv[a], "ransac=", 7)) { ransac = true; ransacThr = atof(argv[a] + 7); }
-        else if (!strncmp(argv[a], "colour=", 7)) colour = atoi(argv[a] + 7) != 0;
+        else if (!strncmp(argv[a], "colour=", 7)) {}                                          // (read above)
+        else if (!strncmp(argv[a], "overlays=", 9)) overlays = argv[a] + 9;
         else if (!strncmp(argv[a], "overlay=", 8)) overlay = argv[a] + 8;
         else if (!strncmp(argv[a], "unique=", 7)) { unique = true; uniqueRatio = atof(argv[a] + 7); const char* cm = strchr(argv[a] + 7, ','); if (cm) uniqueExcl = atoi(cm + 1); }
         else if (!strncmp(argv[a], "subpix=", 7)) subpix = atoi(argv[a] + 7) != 0;
@@ -82,11 +93,13 @@ int main(int argc, char** argv)
         else if (!strncmp(argv[a], "min_matches=", 12)) minMatches = atoi(argv[a] + 12);
         else if (!strncmp(argv[a], "together=", 9)) together = atoi(argv[a] + 9) != 0;
         else if (!strncmp(argv[a], "set=", 4)) { const char* q = strchr(argv[a] + 4, ':'); if (!q) { fprintf(stderr, "set=key:value\n"); return 2; } (void)srukf_debug_set(nullptr, std::string((const char*)argv[a] + 4, (size_t)(q - (argv[a] + 4))).c_str(), atoi(q + 1)); }
+    if (!overlays.empty() && (block < 1 || display.empty())) { fprintf(stderr, "overlays=<file> needs block=<F> and display=<file>\n"); return 2; }
     if (warmup) {
         monoslam::CSLAM w;
         w.m_params.image_w = W; w.m_params.image_h = H; w.MIN_STEP_X = w.MIN_STEP_Y = 0.0;
         if (!w.loadOdometryData(argv[2])) { fprintf(stderr, "%s\n", w.lastError.c_str()); return 1; }
-        w.m_gryImage = frames.data();
+        std::vector<unsigned char> g0((size_t)W * H);                                        // (any gray frame will do: colour=2 has none on the host)
+        w.m_gryImage = colour == 2 ? g0.data() : frames.data();
         w.SLAM();
         if (!w.lastError.empty()) { fprintf(stderr, "warmup: %s\n", w.lastError.c_str()); return 1; }
     }
@@ -108,17 +121,25 @@ int main(int argc, char** argv)
     SLAM.deleteTogether = together;
     if (minMatches > 0) SLAM.m_minNUM = minMatches;
     const unsigned char* cur = nullptr;
-    std::vector<unsigned char> bgr(colour ? (size_t)3 * W * H : 0);
+    std::vector<unsigned char> bgr;
+    auto asColour = [&](const unsigned char* gray, int n) {                                  // n gray frames as B = G = R frames, in bgr
+        bgr.resize((size_t)3 * W * H * n);
+        for (size_t q = 0; q < (size_t)W * H * n; q++) bgr[3 * q] = bgr[3 * q + 1] = bgr[3 * q + 2] = gray[q];
+        return bgr.data();
+    };
     SLAM.dataAssociation = [&](monoslam::CSLAM& s) {                                         // loadPictures + dataAssociation (SLAM.cpp:95-97)
         if (!colour) { s.dataAssociationOnDevice(cur); return; }
-        for (size_t q = 0; q < (size_t)W * H; q++) bgr[3 * q] = bgr[3 * q + 1] = bgr[3 * q + 2] = cur[q];
-        if (s.loadPictures(bgr.data())) s.dataAssociationOnDeviceHeld();
+        if (s.loadPictures(colour == 2 ? cur : asColour(cur, 1))) s.dataAssociationOnDeviceHeld();
     };
+    // the gray frame the host shows the facade.  colour=2: the host has none — loadPictures fills m_grayStore and points m_gryImage at it; until the first one has
+    // run the pointer only says that frames come from a camera (predictMotion builds the filter on it)
+    if (colour == 2) SLAM.m_grayStore.assign((size_t)W * H, 0);
+    auto showFrame = [&](const unsigned char* fr) { cur = fr; SLAM.m_gryImage = colour == 2 ? SLAM.m_grayStore.data() : fr; };
     int steps = SLAM.m_odoCounter - 1 - (redirect > 0 ? 1 : 0);
     double addWall = -1.0;
     if (block > 0) {
         // the block-wise loop: SLAMBlock where it can stand for SLAM(), SLAM() with the association installed for the frame otherwise
-        if (block > 1 && (colour || loops || archiveCap > 0)) { fprintf(stderr, "block=<F> runs without colour=, loops and archive=\n"); return 2; }
+        if (block > 1 && (loops || archiveCap > 0)) { fprintf(stderr, "block=<F> runs without loops and archive=\n"); return 2; }
         if (steps > F) steps = F;
         const auto assoc = SLAM.dataAssociation;
         FILE* fd = nullptr;
@@ -127,6 +148,13 @@ int main(int argc, char** argv)
             if (!fd) { perror(display.c_str()); return 1; }
             SLAM.blockDisplay = true; SLAM.ellipsoidsOnDevice = true;
             SLAM.blockOverlayLast = !overlay.empty();
+            SLAM.blockOverlayAll = !overlays.empty();
+        }
+        FILE* fall = nullptr;
+        std::vector<int> overlayFrames;
+        if (SLAM.blockOverlayAll) {
+            fall = fopen(overlays.c_str(), "wb");
+            if (!fall) { perror(overlays.c_str()); return 1; }
         }
         auto num = [&](double v) { if (std::isnan(v)) fprintf(fd, " nan"); else fprintf(fd, " %a", v); };
         auto displayLine = [&](int fr, int id, const double* xyz, const double* cov, const double* axis, const double* sigma) {
@@ -159,7 +187,8 @@ int main(int argc, char** argv)
         for (int fr = 0; fr < steps;) {
             const int want = steps - fr < block ? steps - fr : block, nBefore = SLAM.m_nMapFeatures;
             SLAM.dataAssociation = nullptr;
-            const int used = block > 1 ? SLAM.SLAMBlock(frames.data() + (size_t)fr * W * H, want) : 0;
+            const unsigned char* blk = frames.data() + (size_t)fr * fb;
+            const int used = block <= 1 ? 0 : colour == 2 ? SLAM.SLAMBlockColour(blk, want) : colour ? SLAM.SLAMBlockColour(asColour(blk, want), want) : SLAM.SLAMBlock(blk, want);
             if (!SLAM.lastError.empty()) { fprintf(stderr, "block at frame %d: %s\n", fr, SLAM.lastError.c_str()); return 1; }
             if (used > 0) {
                 nBlocks++; if (used < want) nEarly++; if (used == block) nFull++;
@@ -177,12 +206,13 @@ int main(int argc, char** argv)
                 report(fr + used - 1, nBefore);
                 displayFromMap(fr + used - 1);
                 overlayDrawn = SLAM.blockOverlayLast;
+                if (fall && fwrite(SLAM.m_blockOverlays.data(), 1, SLAM.m_blockOverlays.size(), fall) != SLAM.m_blockOverlays.size()) { perror(overlays.c_str()); return 1; }
+                if (fall) for (int q = 0; q < used; q++) overlayFrames.push_back(fr + q);
                 fr += used;
                 continue;
             }
             if (block > 1) nFallback++;
-            cur = frames.data() + (size_t)fr * W * H;
-            SLAM.m_gryImage = cur;
+            showFrame(frames.data() + (size_t)fr * fb);
             SLAM.dataAssociation = assoc;
             SLAM.SLAM();
             if (!SLAM.lastError.empty()) { fprintf(stderr, "frame %d: %s\n", fr, SLAM.lastError.c_str()); return 1; }
@@ -192,6 +222,7 @@ int main(int argc, char** argv)
             fr++;
         }
         if (fd) fclose(fd);
+        if (fall) fclose(fall);
         if (fd && !overlay.empty()) {
             if (!overlayDrawn) { fprintf(stderr, "overlay: no block consumed a frame\n"); return 1; }
             FILE* fo = fopen(overlay.c_str(), "wb");
@@ -203,11 +234,11 @@ int main(int argc, char** argv)
         if (rescue) printf(" gate_skips=%d", SLAM.m_nGateSkips);
         printf("\n");
         printf("block_frames %d frames %d us_per_frame %.2f\n", block, steps, wall / steps * 1e6);
+        if (SLAM.blockOverlayAll) { printf("overlay_frames"); for (int q : overlayFrames) printf(" %d", q); printf("\n"); }
         return 0;
     }
     for (int fr = 0; fr < steps; fr++) {
-        cur = frames.data() + (size_t)(fr % F) * W * H;
-        SLAM.m_gryImage = cur;
+        showFrame(frames.data() + (size_t)(fr % F) * fb);
         const size_t logged = SLAM.m_detectLog.size(), searches = SLAM.m_archiveLog.size();
         const int reacquiredBefore = SLAM.m_nArchiveReacquired;
         const double addBefore = SLAM.m_detectTime;

@@ -40,6 +40,7 @@ EXPORTS = [
     "srukf_images_display", "srukf_get_image_display", "srukf_render_image_overlay",
     "srukf_images_rescue_gate", "srukf_get_image_rescue", "srukf_rescue_gate",
     "srukf_delete_landmarks",
+    "srukf_stage_images_bgr", "srukf_get_staged_image", "srukf_render_image_overlays",
 ]
 
 STATUS = {0: "SRUKF_OK", -1: "SRUKF_ERR_BAD_ARG", -2: "SRUKF_ERR_DIM_MISMATCH", -3: "SRUKF_ERR_HIP",
@@ -218,6 +219,10 @@ def load_library(path=None):
         L.srukf_images_display.argtypes = [C.c_void_p, C.c_int]
         L.srukf_get_image_display.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp]
         L.srukf_render_image_overlay.argtypes = [C.c_void_p, C.c_int, _bp]
+    if hasattr(L, "srukf_stage_images_bgr"):           # (idem: colour frames in the staged stack, the overlays of a run of frames)
+        L.srukf_stage_images_bgr.argtypes = [C.c_void_p, C.c_int, _bp, C.c_int]
+        L.srukf_get_staged_image.argtypes = [C.c_void_p, C.c_int, _bp, _bp]
+        L.srukf_render_image_overlays.argtypes = [C.c_void_p, C.c_int, C.c_int, _bp]
     if hasattr(L, "srukf_images_rescue_gate"):         # (idem: the rescue gate on the device)
         L.srukf_images_rescue_gate.argtypes = [C.c_void_p, C.c_int, C.c_double]
         L.srukf_get_image_rescue.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _ip, _ip, _ip]
@@ -960,6 +965,50 @@ class Filter:
             raise ValueError("render_image_overlay: frame must be >= 0")
         out = np.zeros((int(self.params.image_h), int(self.params.image_w), 3), dtype=np.uint8)
         self._chk(self._lib.srukf_render_image_overlay(self._h, int(frame), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out
+
+    # ---- colour frames in the staged stack, the overlays of a run of frames ----
+    def stage_images_bgr(self, bgr, keep_colour=True):
+        """stage_images for colour frames bgr[F, image_h, image_w, 3] uint8 (B, G, R), converted on the device by set_frame_bgr's rule (srukf_stage_images_bgr).
+        Behind it the filter is what stage_images with the converted frames leaves.  keep_colour: the colour stack stays on the device and
+        render_image_overlay(s) draw on it."""
+        if not isinstance(bgr, np.ndarray) or bgr.dtype != np.uint8:
+            raise TypeError("stage_images_bgr: bgr must be a uint8 array")
+        if not isinstance(keep_colour, (bool, np.bool_)):
+            raise TypeError("stage_images_bgr: keep_colour must be a bool")
+        if bgr.ndim != 4 or bgr.shape[1:] != (int(self.params.image_h), int(self.params.image_w), 3):
+            raise ValueError(f"stage_images_bgr: bgr must be [F, {int(self.params.image_h)}, {int(self.params.image_w)}, 3], got {bgr.shape}")
+        if bgr.shape[0] < 1:
+            raise ValueError("stage_images_bgr: no frames")
+        bgr = np.ascontiguousarray(bgr)
+        self._chk(self._lib.srukf_stage_images_bgr(self._h, bgr.shape[0], bgr.ctypes.data_as(C.POINTER(C.c_ubyte)), int(bool(keep_colour))))
+
+    def get_staged_image(self, frame, want_bgr=False):
+        """Frame `frame` of the staged stack (srukf_get_staged_image): gray[image_h, image_w] uint8, or with want_bgr (gray, bgr[image_h, image_w, 3]).
+        SrukfError(SRUKF_ERR_SEQUENCE) for want_bgr when no colour stack is kept."""
+        if isinstance(frame, (bool, np.bool_)) or not isinstance(frame, (int, np.integer)):
+            raise TypeError("get_staged_image: frame must be an int")
+        if not isinstance(want_bgr, (bool, np.bool_)):
+            raise TypeError("get_staged_image: want_bgr must be a bool")
+        if frame < 0:
+            raise ValueError("get_staged_image: frame must be >= 0")
+        H, W = int(self.params.image_h), int(self.params.image_w)
+        gray = np.zeros((H, W), dtype=np.uint8)
+        bgr = np.zeros((H, W, 3), dtype=np.uint8) if want_bgr else None
+        self._chk(self._lib.srukf_get_staged_image(self._h, int(frame), gray.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                   bgr.ctypes.data_as(C.POINTER(C.c_ubyte)) if want_bgr else None))
+        return (gray, bgr) if want_bgr else gray
+
+    def render_image_overlays(self, first, count):
+        """render_image_overlay for staged frames [first, first + count) in one device call (srukf_render_image_overlays): bgr[count, image_h, image_w, 3]
+        uint8, frame q of it what render_image_overlay(first + q) returns.  SrukfError(SRUKF_ERR_SEQUENCE) when a frame of the range is not drawable."""
+        for name, v in (("first", first), ("count", count)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"render_image_overlays: {name} must be an int")
+        if first < 0 or count < 1:
+            raise ValueError("render_image_overlays: first must be >= 0 and count >= 1")
+        out = np.zeros((int(count), int(self.params.image_h), int(self.params.image_w), 3), dtype=np.uint8)
+        self._chk(self._lib.srukf_render_image_overlays(self._h, int(first), int(count), out.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return out
 
     def synchronize(self):

@@ -727,6 +727,29 @@ int  srukf_images_display(srukf_ctx* ctx, int on);
 int  srukf_get_image_display(srukf_ctx* ctx, int first, int count, double* xyz, double* cov, double* axis, double* sigma, int* rot, double* pose4, double* P4, double* Si);
 int  srukf_render_image_overlay(srukf_ctx* ctx, int frame, unsigned char* out_bgr);
 
+/* ---- colour frames in the staged stack, the overlays of a run of frames ----
+ * srukf_stage_images_bgr: srukf_stage_images for the frames the reference's host has: bgr[n_frames][image_h][image_w][3], interleaved B, G, R bytes, no row
+ *   padding (cvQueryFrame / cvLoadImage).  The device converts them with srukf_set_frame_bgr's rule — OpenCV 2.4's fixed-point CV_RGB2GRAY applied to B, G, R
+ *   in memory order as loadPictures applies it (SLAM.cpp:529-543), gray = (4899 c0 + 9617 c1 + 1868 c2 + 8192) >> 14 — into the staged gray stack.  Behind the
+ *   call the handle is what srukf_stage_images with the converted bytes leaves: every run, record, getter, rewind, resume and refusal of the image runs behaves
+ *   the same.  The refusals are srukf_stage_images', in its order and with its codes; keep_colour outside {0, 1}: SRUKF_ERR_BAD_ARG.  keep_colour = 1 keeps the
+ *   colour stack beside the gray one (3 bytes per pixel more) as the source of srukf_render_image_overlay(s); keep_colour = 0 passes the colour bytes through
+ *   a transit buffer of at most 12 MiB.  Whatever drops the staged images drops the colour stack: a map change, srukf_reset, srukf_stage_sequence, a later
+ *   srukf_stage_images or srukf_stage_images_bgr.  The frame the handle holds (srukf_set_frame_bgr, srukf_associate_held) is neither read nor written.
+ * srukf_get_staged_image: frame `frame` of the staged stack, after waiting for the stream: gray_out[image_h][image_w] and / or, from a kept colour stack,
+ *   bgr_out[image_h][image_w][3].  Either pointer may be NULL, not both (SRUKF_ERR_BAD_ARG).  SRUKF_ERR_SEQUENCE: no images staged, or bgr_out without a kept
+ *   colour stack; SRUKF_ERR_BAD_ARG: frame outside the stack.
+ * srukf_render_image_overlay draws over the frame's colour bytes when a colour stack is kept, otherwise over the gray byte three times.  Its refusals and
+ *   their codes are what they were; the text srukf_last_error gives for a row that is not drawable now ends in " (frame <q>)".
+ * srukf_render_image_overlays: srukf_render_image_overlay for frames [first, first + count) in two launches and one copy: out_bgr[count][image_h][image_w][3],
+ *   frame first + q of it byte for byte the single call's.  The refusals are the single call's (frames outside the stack: SRUKF_ERR_BAD_ARG); when any row of
+ *   the range is not drawable: SRUKF_ERR_SEQUENCE, srukf_last_error names the first such frame, and out_bgr is untouched; count > 65 535: SRUKF_ERR_UNSUPPORTED.  Its device scratch grows to the
+ *   largest count asked for and goes with the staged images.
+ * All: SRUKF_ERR_BAD_ARG for a NULL handle or NULL frames / out_bgr (first or frame < 0, count or n_frames < 1) before any device is touched. */
+int  srukf_stage_images_bgr(srukf_ctx* ctx, int n_frames, const unsigned char* bgr, int keep_colour);
+int  srukf_get_staged_image(srukf_ctx* ctx, int frame, unsigned char* gray_out, unsigned char* bgr_out);
+int  srukf_render_image_overlays(srukf_ctx* ctx, int first, int count, unsigned char* out_bgr);
+
 /* ---- instrumentation ------------------------------------------------------------------------ */
 
 /* When on, every kernel launch is bracketed by HIP events on the context's stream and the
